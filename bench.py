@@ -128,8 +128,9 @@ def run_batch(args, rank, world, local_rank, dist, torch):
     if args.dynamic:
         # chunks of n_slots scenarios claimed from a counter in the process group's store (activesetmethods_amd.batch.claim_chunks)
         mine, stats = batch.solve_batch_dynamic(problems.__getitem__, total, par, n_slots, hb, reduce_device=args.reduce_device)
-        runs, st1 = list(mine.values()), hb.stats()
+        scenarios, runs, st1 = list(mine), list(mine.values()), hb.stats()
     else:
+        scenarios = list(range(lo, hi))
         runs, stats, st1 = batch.solve_batch_lockstep(plist, par, n_slots, rank=rank, world=world, reduce_device=args.reduce_device, batch=hb)
     torch.cuda.synchronize()
     mine = time.perf_counter() - t0
@@ -137,6 +138,8 @@ def run_batch(args, rank, world, local_rank, dist, torch):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     thr = _cpu_throttled_s() - thr0
+    if args.dump_outputs and rank == 0:
+        dump_scenarios(args.dump_outputs, scenarios, runs)
     rank_s, rank_thr = [mine], [thr]
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=args.reduce_device)
@@ -248,6 +251,8 @@ def run_batch_pool(args, rank, world, local_rank, dist, torch, base, problems, t
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_scenarios(args.dump_outputs, list(range(*batch.partition(total, world, rank))), slps)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=args.reduce_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -264,6 +269,36 @@ def run_batch_pool(args, rank, world, local_rank, dist, torch, base, problems, t
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+SOLUTION = ("x", "lam", "mult_x_L", "mult_x_U")      # iterate and multipliers, as an SLP run hands them to its caller
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> array) as float64 `dirname/<name>.npy`."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (nbytes, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def dump_scenarios(dirname, scenarios, runs):
+    """--dump-outputs of a scenario batch: the final iterate and multipliers of every scenario this rank solved, one row per scenario in
+    index order; above the size limit a fixed, seeded sample of the rows (`scenario` holds the indices kept)."""
+    import numpy as np
+    order = np.argsort(scenarios, kind="stable")
+    row_bytes = 8 * (1 + sum(np.size(getattr(runs[0], k)) for k in SOLUTION))
+    keep = DUMP_LIMIT_BYTES // row_bytes
+    if len(order) > keep:
+        order = order[np.sort(np.random.default_rng(0).choice(len(order), keep, replace=False))]
+    out = {"scenario": np.asarray(scenarios)[order]}
+    out.update({k: np.stack([getattr(runs[i], k) for i in order]) for k in SOLUTION})
+    dump_outputs(dirname, out)
 
 
 def _freeze_heap():
@@ -537,6 +572,8 @@ def main():
     ap.add_argument("--host-eval", action="store_true", help="evaluate f, grad f, g, Jacobian values with the NumPy callbacks instead of the device kernels")
     ap.add_argument("--kernel-breakdown", action="store_true",
                     help="time every kernel family with HIP events (adds kernels_ms; default: only the dominant kernel, k_syrk, is timed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, rank 0, at most 64 MB)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -549,6 +586,10 @@ def main():
     args.steps = wl["steps"] if args.steps is None else args.steps
     args.warmup = wl["warmup"] if args.warmup is None else args.warmup
     args.algorithm = wl["algorithm"] if args.algorithm is None else args.algorithm
+    if args.workload == "c5" and args.scenarios_per_gpu is not None:
+        args.steps = args.scenarios_per_gpu
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -556,7 +597,6 @@ def main():
     # launched on), 2 = every kernel family (perturbs the latency-bound small workloads)
     os.environ.setdefault("ASM_HIP_TIMING", "2" if args.kernel_breakdown else "1")
     if args.workload == "c5":
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")     # one hardware queue per concurrent scenario stream (ROCm default: 4)
         import torch as _t
         nvis = _t.cuda.device_count()
         if nvis and world > nvis:
@@ -580,14 +620,12 @@ def main():
     args.reduce_device = None if dist is None else ("cpu" if rehearsal else "cuda")
 
     if args.workload == "c5":
-        if args.scenarios_per_gpu is not None:
-            args.steps = args.scenarios_per_gpu
         return run_batch(args, rank, world, local_rank, dist, torch)
     pr, pr_host = make_problem(args.workload, not args.host_eval)
     state = {"device_eval": not args.host_eval}
     run_steps(pr, args.algorithm, local_rank, args.warmup, state)
-    opt = state["opt"]
-    opt.kernel_stats(reset=True)
+    if state.get("opt") is not None:        # with --warmup 0 the first timed step creates the handle
+        state["opt"].kernel_stats(reset=True)
     _freeze_heap()
 
     def barrier():
@@ -602,11 +640,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     assert done == args.steps
+    if args.dump_outputs and rank == 0:     # the SLP state after the last timed step: written before the untimed pass below advances the run
+        dump_outputs(args.dump_outputs, {k: getattr(state["slp"], k) for k in ("p",) + SOLUTION})
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=args.reduce_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    opt = state["opt"]
     ks = opt.kernel_stats()
     trace = list(state.get("trace_all", []))        # (the all-families pass below appends to the live list)
     # ---- roofline.  Every launch of the two MFMA kernel families is timed with HIP events on the stream it runs on:

@@ -186,6 +186,35 @@ def test_bench_launcher_starts_one_rank_per_gpu(tmp_path):
     assert bench.launch_ranks(2, [out, "7"], script=str(child)) == 7      # a failing rank's exit code is returned
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float64 DIR/<name>.npy; a scenario batch is written in scenario order, and above the size limit as
+    the same seeded sample of rows every time."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.dump_outputs(str(tmp_path / "one"), {"x": np.arange(5, dtype=np.float32), "lam": [1, 2]})
+    x, lam = np.load(tmp_path / "one" / "x.npy"), np.load(tmp_path / "one" / "lam.npy")
+    assert x.dtype == lam.dtype == np.float64 and np.array_equal(x, np.arange(5)) and np.array_equal(lam, [1, 2])
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+
+    def runs(scenarios):
+        return [types.SimpleNamespace(**{k: np.full(3 + j, 10.0 * s + j) for j, k in enumerate(bench.SOLUTION)}) for s in scenarios]
+    bench.dump_scenarios(str(tmp_path / "batch"), [4, 2, 3], runs([4, 2, 3]))
+    assert np.array_equal(np.load(tmp_path / "batch" / "scenario.npy"), [2, 3, 4])
+    assert np.array_equal(np.load(tmp_path / "batch" / "x.npy")[:, 0], [20, 30, 40])
+    assert np.load(tmp_path / "batch" / "mult_x_U.npy").shape == (3, 6)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 19 * 4)          # four rows of 1 + 3 + 4 + 5 + 6 numbers
+    for d in ("s1", "s2"):
+        bench.dump_scenarios(str(tmp_path / d), list(range(10)), runs(range(10)))
+    kept = np.load(tmp_path / "s1" / "scenario.npy")
+    assert len(kept) == 4 and np.all(np.diff(kept) > 0) and np.array_equal(kept, np.load(tmp_path / "s2" / "scenario.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "lam.npy")[:, 0], 10.0 * kept + 1)
+
+
 def test_function_model_follows_the_wrapper():
     """moi_evaluator.FunctionModel against src/MOI_wrapper.jl:683-1012 on a hand-worked model: block order of the rows, the
     Jacobian pattern with the duplicates quadratic terms emit, the 1/2 convention of diagonal quadratic terms, bounds, sense."""
