@@ -37,7 +37,8 @@ class SlpResult(C.Structure):
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
-                ("panel_ms", C.c_double), ("panel_launches", C.c_int64), ("panel_ops", C.c_int64), ("panel_flops", C.c_double), ("panel_bytes", C.c_double)]
+                ("panel_ms", C.c_double), ("panel_launches", C.c_int64), ("panel_ops", C.c_int64), ("panel_flops", C.c_double), ("panel_bytes", C.c_double),
+                ("panel_grid_max", C.c_int64)]
 
 
 _P = C.c_void_p
@@ -98,6 +99,7 @@ PROTOTYPES = {
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),
     "asm_test_panel_timeout": (C.c_int, [_P, C.c_int]),
     "asm_test_set_band": (C.c_int, [_P, C.c_int]),
+    "asm_test_set_factor": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
     "asm_test_gemm_nt": (C.c_int, [_P, _D, _D, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int, _D]),
     "asm_test_trsm_rows": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int, _D]),
     "asm_test_gemv": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, _D, _D, _D]),

@@ -151,6 +151,7 @@ struct Sched {
     std::vector<hipEvent_t> res_pool;
     double res_ms = 0.0;
     uint64_t res_launches = 0, res_ops = 0;
+    uint64_t res_grid_max = 0;                              // most workgroups of one (merged) OP_RESIDENT launch
     hipEvent_t res_event() {
         if (!res_pool.empty()) { hipEvent_t e = res_pool.back(); res_pool.pop_back(); return e; }
         hipEvent_t e;
@@ -330,6 +331,7 @@ struct Sched {
             const Op& X = *L.op;
             AsmBt bt{(const void*)(d_blob + L.tab), X.arg_size, X.gz};
             const bool timed = time_resident && (X.flags & OP_RESIDENT);
+            if (X.flags & OP_RESIDENT) res_grid_max = std::max<uint64_t>(res_grid_max, (uint64_t)X.gx * X.gy * X.gz * L.nb);
             hipEvent_t ea = nullptr, eb = nullptr;
             if (timed) { ea = res_event(); eb = res_event(); chk(hipEventRecord(ea, stream), "hipEventRecord"); }
             X.thunk(X.kfn, dim3(X.gx, X.gy, X.gz * L.nb), dim3(X.bx, X.by, X.bz), X.shmem, stream, bt);

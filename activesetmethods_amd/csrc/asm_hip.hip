@@ -273,6 +273,11 @@ struct asm_handle {
     double* d_redpart = nullptr;    // partial results / arrival counter of the multi-workgroup interior-point reductions
     unsigned* d_redcnt = nullptr;
     int main_band = 0;              // band of the matrix in the main factor buffers (test hook asm_test_set_band; 0 = dense)
+    // test hook asm_test_set_factor: where the kernel hooks factor (0: the main buffers, 1: a factor buffer of their own made by
+    // ns_alloc_factor with this band hint) and the guard settings they factor with (k_diag_prepare mode / rel / absv, chol threshold)
+    int test_layout = 0, test_band_hint = 0, test_mode = 0;
+    double test_rel = 0.0, test_abs = 0.0, test_thr = 1e-14;
+    FacBuf test_fac;
     int ns_Zk = 0;                  // rows of the orthonormal basis of the previous LP still resident in d_nsG (0: none)
     int *d_nsqi = nullptr;          // sel | bpos | rpos | cnt
     double *d_nsq = nullptr;        // Csel | d, u, lam, v, w | pbar, tbar, u0, qh
@@ -326,7 +331,8 @@ struct asm_handle {
     std::vector<hipEvent_t> event_pool;
     bool batch_slot = false;        // slot of an asm_batch: the stream belongs to the batch, no look-ahead stream, no event timing
     bool fused_panel = true;        // Cholesky inner panels as one dataflow launch (k_chol_panel) instead of three launches per 64-wide step
-    int panel_wgs = 240;            // its grid bound: every workgroup must be able to become resident
+    int panel_wgs = 240;            // its grid bound: every workgroup must be able to become resident (a batch slot: its group's share)
+    int panel_wgs_dev = 240;        // the bound of the whole device (ASM_PANEL_WGS) the shares of a batch's groups are taken from
     int num_cus = 256;              // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     unsigned *d_pflags = nullptr, *d_ptmo = nullptr;
     bool test_no_polish = false;    // test hook: the active-set attempts of an LP all fail (asm_test_no_polish)
@@ -816,7 +822,7 @@ struct Dev {
         const bool skip_inv = !want_inverse && fsmall && Ms <= ASM_SMALL_USE;
         // a factor of ONE wide block gets its explicit inverse inside the panel launches (helper workgroups of k_chol_panel_inv)
         static const bool inv_env = [] { const char* v = std::getenv("ASM_PANEL_INV"); return !(v && v[0] == '0'); }();
-        panel_inv_now = !skip_inv && inv_env && h->fused_panel && Ms <= fwb && fband == 0 && fBinv && fBinvT && ASM_PNL_WT * (ASM_PNL_NS + 1) <= h->panel_wgs;
+        panel_inv_now = !skip_inv && inv_env && h->fused_panel && Ms <= fwb && fband == 0 && fBinv && fBinvT && panel_inv_grid(Ms) <= h->panel_wgs;
         const bool inv_done = panel_inv_now;
         chol_launches(Ms, thr);
         panel_inv_now = false;
@@ -831,6 +837,19 @@ struct Dev {
         if (fwb == 1024) trtri_launches<1024>(Ms); else trtri_launches<512>(Ms);
         end(id);
         h->stats.nfact += 1;
+    }
+    // the largest grid of the k_chol_panel_inv launches of a factor of one wide block (Ms <= fwb <= CHOL_NBO: the inner panels of chol_chain's
+    // only outer panel): G row-tile workgroups + one helper per 64 x 64 tile of the block rows a launch finishes.  All of them must be resident
+    // within the handle's budget (a batch slot: its group's share); at most ASM_PNL_WT + ASM_PNL_NS * ASM_PNL_WT = 176, 144 for Ms <= 1024
+    int panel_inv_grid(int Ms) const {
+        const int T = (Ms + ASM_NB - 1) / ASM_NB;
+        int grid = 0;
+        for (int I0 = 0, I1 = 0; I0 < Ms; I0 = I1) {
+            I1 = (Ms - I0 <= CHOL_NBI + 2 * ASM_NB) ? Ms : std::min(I0 + CHOL_NBI, Ms);
+            const int nrt = (Ms - I0 + ASM_NB - 1) / ASM_NB, nst = (I1 - I0 + ASM_NB - 1) / ASM_NB;
+            grid = std::max(grid, std::max(1, std::min(nrt, h->panel_wgs)) + nst * T);
+        }
+        return grid;
     }
     // block chain of one outer panel [K0, K1): 64-wide potrf / panel solve steps whose rank-64 updates stay inside a
     // 512-wide inner panel; the rest of the outer panel is updated once per inner panel with K = 512
@@ -3387,6 +3406,7 @@ int asm_create(int device, asm_handle** out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 16) { h->num_cus = prop.multiProcessorCount; h->panel_wgs = 2 * prop.multiProcessorCount - 32; }
         if (const char* pw = std::getenv("ASM_PANEL_WGS")) h->panel_wgs = std::max(1, std::atoi(pw));
+        h->panel_wgs_dev = h->panel_wgs;
     }
     *out = h;
     return ASM_OK;
@@ -3892,22 +3912,48 @@ int asm_test_syrk_update(asm_handle* h, const double* Pm, int64_t Ms, int64_t K,
     });
 }
 
+// S into the buffers the hooks factor in (asm_test_set_factor): the main buffers, or a factor buffer of the null-space form's kind, made for
+// this order (released with the other null-space buffers at the next set-up)
 static void test_load_S(asm_handle* h, const double* S, int64_t N) {
     test_alloc(h, N, 16);
     h->main_band_cur = 0;
+    double* dst = h->d_S;
+    int64_t ld = h->Mp;
+    if (h->test_layout == 1) {
+        h->test_fac = FacBuf();
+        ns_alloc_factor(h, h->test_fac, N, h->test_band_hint);
+        h->test_fac.band = h->main_band;
+        HIPCHK(hipStreamSynchronize(h->stream));          // (the buffers are cleared on the stream)
+        dst = h->test_fac.S;
+        ld = h->test_fac.ld;
+    }
     for (int64_t i = 0; i < N; ++i)
-        HIPCHK(hipMemcpy(h->d_S + i * h->Mp, S + i * N, N * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dst + i * ld, S + i * N, N * sizeof(double), hipMemcpyHostToDevice));
+}
+// factorisation of the loaded matrix with the hooks' guard settings, in the buffers it was loaded into
+static void test_factor(asm_handle* h, Dev& d, int64_t N) {
+    if (h->test_layout == 1) d.use_factor(h->test_fac);
+    d.diag_prepare((int)N, h->test_mode, h->test_rel, h->test_abs);
+    d.chol((int)N, h->test_thr);
+}
+
+int asm_test_set_factor(asm_handle* h, int layout, int band_hint, int mode, double rel, double absv, double thr) {
+    return guarded(h, [&] {
+        if (layout < 0 || layout > 1 || band_hint < 0 || mode < 0 || mode > 1 || !(rel >= 0.0) || !(absv >= 0.0) || !(thr >= 0.0))
+            throw std::invalid_argument("asm_test_set_factor: bad argument");
+        h->test_layout = layout; h->test_band_hint = band_hint; h->test_mode = mode;
+        h->test_rel = rel; h->test_abs = absv; h->test_thr = thr;
+    });
 }
 
 int asm_test_cholesky(asm_handle* h, const double* S, int64_t N, double* L_out) {
     return guarded(h, [&] {
         test_load_S(h, S, N);
         Dev d(h);
-        d.diag_prepare((int)N, 0, 0.0, 0.0);
-        d.chol((int)N);
+        test_factor(h, d, N);
         HIPCHK(hipStreamSynchronize(h->stream));
         for (int64_t i = 0; i < N; ++i) {
-            HIPCHK(hipMemcpy(L_out + i * N, h->d_S + i * h->Mp, N * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(L_out + i * N, d.fS + i * d.fld, N * sizeof(double), hipMemcpyDeviceToHost));
             for (int64_t j = i + 1; j < N; ++j) L_out[i * N + j] = 0.0;
         }
         d.resolve_timing();
@@ -3947,8 +3993,7 @@ int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double*
     return guarded(h, [&] {
         test_load_S(h, S, N);
         Dev d(h);
-        d.diag_prepare((int)N, 0, 0.0, 0.0);
-        d.chol((int)N);
+        test_factor(h, d, N);
         d.chol_solve(b, x, (int)N);
         d.resolve_timing();
     });
@@ -3984,16 +4029,15 @@ int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* 
         if (N <= 0 || nrhs <= 0 || !S || !R || !X_out) throw std::invalid_argument("asm_test_trsm_rows: bad argument");
         test_load_S(h, S, N);
         Dev d(h);
-        d.diag_prepare((int)N, 0, 0.0, 0.0);
-        d.chol((int)N);
+        test_factor(h, d, N);
         const int64_t ldr = round_up(N, 32);
         double *dR = nullptr, *dX = nullptr, *dLt = nullptr;
-        dmalloc(&dR, nrhs * ldr); dmalloc(&dX, nrhs * ldr); dmalloc(&dLt, h->Mp * h->Mp);
+        dmalloc(&dR, nrhs * ldr); dmalloc(&dX, nrhs * ldr); dmalloc(&dLt, d.fld * d.fld);
         HIPCHK(hipMemset(dR, 0, nrhs * ldr * sizeof(double)));
         HIPCHK(hipMemset(dX, 0, nrhs * ldr * sizeof(double)));
-        HIPCHK(hipMemset(dLt, 0, h->Mp * h->Mp * sizeof(double)));
+        HIPCHK(hipMemset(dLt, 0, d.fld * d.fld * sizeof(double)));
         for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(dR + r * ldr, R + r * N, N * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, h->stream, (const double*)h->d_S, h->Mp, N, N, dLt, h->Mp, (int64_t)-1);
+        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, h->stream, (const double*)d.fS, d.fld, N, N, dLt, d.fld, (int64_t)-1);
         d.trsm_rows(dR, dX, ldr, (int)nrhs, (int)N, backward ? dLt : nullptr);
         HIPCHK(hipStreamSynchronize(h->stream));
         const double* out = backward ? dR : dX;
@@ -4248,10 +4292,12 @@ void run_fibers(asm_batch* b, int count, W&& work) {
     st.emit_ms = st.wait_ms = st.host_ms = 0.0;
     st.panel_ms = st.panel_flops = st.panel_bytes = 0.0;
     st.panel_launches = st.panel_ops = 0;
+    st.panel_grid_max = 0;
     for (asm_handle* sh : b->slots) { st.panel_flops += sh->kstats.flops[ASM_K_PANEL_KERNEL]; st.panel_bytes += sh->kstats.bytes[ASM_K_PANEL_KERNEL]; }
     for (BatchGroup* g : b->groups) {
         const asmb::Sched& S = g->sched;
         st.panel_ms += S.res_ms; st.panel_launches += (int64_t)S.res_launches; st.panel_ops += (int64_t)S.res_ops;
+        st.panel_grid_max = std::max(st.panel_grid_max, (int64_t)S.res_grid_max);
         st.rounds += (int64_t)S.n_rounds; st.ops += (int64_t)S.n_ops; st.launches += (int64_t)S.n_launches; st.releases += (int64_t)S.n_releases;
         st.blob_bytes += (int64_t)S.blob_bytes; st.emit_ms += S.t_emit_ms; st.wait_ms += S.t_wait_ms; st.host_ms += S.t_host_ms;
     }
@@ -4281,10 +4327,12 @@ void batch_make_groups(asm_batch* b, int n_groups) {
         g->hi = (int)((int64_t)n * (k + 1) / n_groups);
         // the all-resident panel kernels of the groups run side by side: together they must fit the chip (workgroups are dealt to the XCDs
         // round-robin and each XCD places its share on its own - a consumer can become resident before its producer, and with the chip
-        // full of spinning consumers the producer never would)
-        g->sched.init(b->device, g->stream, std::max(16, b->slots[0]->panel_wgs / n_groups));
+        // full of spinning consumers the producer never would).  The slots size their panel grids to the same share: a resident launch
+        // wider than the share would go out unmerged at its full grid
+        const int share = std::max(16, b->slots[0]->panel_wgs_dev / n_groups);
+        g->sched.init(b->device, g->stream, share);
         if (const char* nb = std::getenv("ASM_BATCH_NO_BARRIERS")) g->sched.use_barriers = !(nb[0] == '1');
-        for (int s = g->lo; s < g->hi; ++s) { b->slots[s]->stream = g->stream; b->slots[s]->stream2 = g->stream; }
+        for (int s = g->lo; s < g->hi; ++s) { b->slots[s]->stream = g->stream; b->slots[s]->stream2 = g->stream; b->slots[s]->panel_wgs = share; }
     }
 }
 }  // namespace

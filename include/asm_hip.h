@@ -280,6 +280,8 @@ typedef struct {
     double  panel_ms;
     int64_t panel_launches, panel_ops;
     double  panel_flops, panel_bytes;
+    int64_t panel_grid_max;   /* most workgroups of any all-resident launch the batch made (merged launches included): stays within the
+                               * group's share of the device's panel budget */
 } asm_batch_stats;
 int asm_batch_get_stats(const asm_batch* b, asm_batch_stats* out);
 
@@ -287,6 +289,11 @@ int asm_batch_get_stats(const asm_batch* b, asm_batch_stats* out);
  * (0 = dense): factorisation and substitutions stop at the band, as they do for S0 = A_EF A_EF' of the null-space form (its equality
  * rows are put in reverse Cuthill-McKee order at set-up). */
 int asm_test_set_band(asm_handle* h, int band);
+/* Test hook: how asm_test_cholesky / asm_test_chol_solve / asm_test_trsm_rows factor from now on.  layout 0: in the main buffers (wide
+ * blocks of 1024 above order 1536, else 512); layout 1: in a factor buffer of the null-space form's kind (ns_alloc_factor with band_hint:
+ * one 1024-wide block up to order 1024).  mode / rel / absv: the regularisation of the diagonal (k_diag_prepare), thr: the static pivot
+ * guard of the factorisation.  (0, 0, 0, 0.0, 0.0, 1e-14) are the settings the hooks use until this is called. */
+int asm_test_set_factor(asm_handle* h, int layout, int band_hint, int mode, double rel, double absv, double thr);
 
 /* ---- kernel-level test hooks (used by tests/ to check each kernel against NumPy) ---------------- */
 int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const int32_t* idx, int64_t Ms,

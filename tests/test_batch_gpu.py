@@ -155,3 +155,51 @@ def test_batched_slp_runs_equal_per_scenario_runs_bit_for_bit():
             assert np.array_equal(r.mult_x_U, one.mult_x_U) and np.array_equal(r.mult_x_L, one.mult_x_L)
             assert r.obj_val == one.obj_val
     opt.close()
+
+
+def test_batch_panel_grids_stay_within_the_group_share(monkeypatch):
+    """A batch of two groups under ASM_PANEL_WGS=32 gives each group a share of 16 workgroups for its all-resident panel launches: the slots
+    size their panel grids to it (G = min(nrt, 16) with nrt > 16 here: the row-form Schur matrix of a dense sub-LP with 1150 rows), so no
+    resident launch - merged or not - is wider than the share, and the solves equal, bit for bit, those of handles whose own budget is 16."""
+    from activesetmethods_amd import _lib
+    from activesetmethods_amd.subproblem import QpData, HipSubOptimizer
+    from tests.util import random_subproblem
+    lib = _lib.load()
+    base = random_subproblem(9, 1000, 1150, density=1.0, n_range=3)
+    sps = [_perturbed(base, s) for s in range(2)]
+    fr = np.zeros(2, np.int32)
+    monkeypatch.setenv("ASM_PANEL_WGS", "32")
+    monkeypatch.setenv("ASM_BATCH_GROUPS", "2")
+    from activesetmethods_amd import batch
+    hb = batch.HipBatch.__new__(batch.HipBatch)          # owns the batch: destroyed once, by hb.close()
+    hb._lib, hb._C, hb._err = lib, C, RuntimeError
+    hb.n, hb.m, hb.n_slots = base["n"], base["m"], 2
+    hb._b = C.c_void_p()
+    assert lib.asm_batch_create(0, 2, C.byref(hb._b)) == 0
+    try:
+        assert lib.asm_batch_groups(hb._b) == 2
+        f64 = lambda a: np.ascontiguousarray(a, np.float64)
+        jr, jc = np.ascontiguousarray(base["j_row"], np.int64), np.ascontiguousarray(base["j_col"], np.int64)
+        gl, gu, xl, xu = map(f64, (base["c_lb"], base["c_ub"], base["v_lb"], base["v_ub"]))
+        assert lib.asm_batch_setup(hb._b, base["n"], base["m"], len(jr), _lib.i64ptr(jr), _lib.i64ptr(jc), _lib.dptr(gl), _lib.dptr(gu), _lib.dptr(xl),
+                                   _lib.dptr(xu)) == 0
+        stack = lambda k: np.stack([sp[k] for sp in sps])
+        out = hb.sublp_solve(stack("dE"), stack("df"), np.array([sp["f"] for sp in sps]), stack("E"), stack("x_k"), np.array([sp["delta"] for sp in sps]), fr,
+                             bounds=(stack("c_lb"), stack("c_ub"), stack("v_lb"), stack("v_ub")))
+        st = _lib.BatchStats()
+        assert lib.asm_batch_get_stats(hb._b, C.byref(st)) == 0
+    finally:
+        hb.close()
+    print("panel_grid_max", st.panel_grid_max, "panel_launches", st.panel_launches)
+    assert st.panel_ops > 0
+    assert 0 < st.panel_grid_max <= 16, st.panel_grid_max
+    monkeypatch.setenv("ASM_PANEL_WGS", "16")
+    for s, sp in enumerate(sps):
+        opt = HipSubOptimizer(QpData(sp["df"], sp["f"], sp["dE"], sp["E"], sp["c_lb"], sp["c_ub"], sp["v_lb"], sp["v_ub"]), sp["j_row"], sp["j_col"])
+        try:
+            ref = opt.sub_optimize(sp["x_k"], sp["delta"], False)
+            assert ref[5] == out[5][s] == 1
+            for a, c in zip(ref[:4], (out[0][s], out[1][s], out[2][s], out[3][s])):
+                assert np.array_equal(a, c)
+        finally:
+            opt.close()

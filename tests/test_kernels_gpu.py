@@ -258,3 +258,256 @@ def test_banded_cholesky_and_solves(hip_lib, handle, N, band, nrhs):
             assert np.abs(X - ref).max() / np.abs(ref).max() < 1e-9
     finally:
         assert hip_lib.asm_test_set_band(handle, 0) == 0
+
+
+# ----------------------------------------------------------------------------- the Cholesky family in every launch configuration
+# Handles whose per-handle knobs (asm_create reads them) select the other launch sequences of Dev::chol / chol_chain (asm_hip.hip):
+#   D     the default (panel_wgs = 2 #CU - 32 = 480 on an MI355X: one workgroup per row tile, G = nrt)
+#   W1/5/16  ASM_PANEL_WGS: G = min(nrt, panel_wgs) < nrt, each workgroup owns row tiles rt, rt + G, ...; no k_chol_panel_band (the generic banded
+#            chain: k_chol_panel + rowlim + banded rank-K updates) and no k_chol_panel_inv (k_trtri_* instead)
+#   W175  the budget just below the old worst-case gate of the in-launch inverse (ASM_PNL_WT (ASM_PNL_NS + 1) = 176); the gate is the launch's
+#         own grid (at most 144 for a factor of one 1024-wide block), so W175 takes D's sequence
+#   U     ASM_HIP_FUSED_PANEL=0: k_potrf_diag / k_trsm_panel / k_panel_update64, three launches per 64-wide step
+CONFIGS = {"D": {}, "W1": {"ASM_PANEL_WGS": "1"}, "W5": {"ASM_PANEL_WGS": "5"}, "W16": {"ASM_PANEL_WGS": "16"},
+           "W175": {"ASM_PANEL_WGS": "175"}, "U": {"ASM_HIP_FUSED_PANEL": "0"}}
+PANEL_WGS_D = 480
+U64 = 2.0 ** -53
+# condition-free backward-error bars (u = 2^-53); largest ratios measured on an MI355X over every shape and configuration: 2.12 (factor,
+# N = 1), 1.43 (solves); the printed "ratio" lines of the tests (pytest -s) give them per case
+C_FAC = 4.0        # factor: ||S v - L (L' v)||_inf <= C_FAC N u ||S||_inf ||v||_inf
+C_SOL = 4.0        # solves: ||S x - b||_inf <= C_SOL N u (||S||_inf ||x||_inf + ||b||_inf), the same for the rows of the triangular solves
+
+
+@pytest.fixture(scope="module")
+def config_handle(hip_lib):
+    """config_handle(name): a handle created under the configuration's environment (made on first use, destroyed with the module)."""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            with pytest.MonkeyPatch.context() as mp:
+                mp.delenv("ASM_PANEL_WGS", raising=False)
+                mp.delenv("ASM_HIP_FUSED_PANEL", raising=False)
+                for k, v in CONFIGS[name].items():
+                    mp.setenv(k, v)
+                h = C.c_void_p()
+                assert hip_lib.asm_create(0, C.byref(h)) == 0
+            made[name] = h
+        return made[name]
+    yield get
+    for h in made.values():
+        hip_lib.asm_destroy(h)
+
+
+def _wide_block(layout, N, band_hint):
+    """The wide-block width the factor's substitutions use: main buffers h->wb (pitch Mp >= N), a factor buffer ns_alloc_factor's rule."""
+    if layout == 0:
+        return 1024 if N > 1536 else 512
+    ld = -(-N // 32) * 32
+    wb = 1024 if (ld <= 1024 or ld > 1536) else 512
+    return 512 if (band_hint > 0 and band_hint <= 512 and ld > 1024) else wb
+
+
+def kernel_selection(config, layout, N, band=0, band_hint=0):
+    """The launch sequence Dev::chol chooses for this configuration (band_panels_ok, the gate of the in-launch inverse panel_inv_grid,
+    fused or not), everything but the grid G = min(nrt, panel_wgs) of the panel launches.  Configurations with the same selection give the
+    same factor, inverses and solutions BIT FOR BIT: a row tile's sums are made in the same order by whichever workgroup owns it
+    (chol_panel_body), the helpers of k_chol_panel_inv and the k_trtri_* / substitution launches do not depend on G.  U against D is held
+    to the error bars only (potrf64_body<false> and the fused bodies are not claimed to make the same sums)."""
+    env = CONFIGS[config]
+    if env.get("ASM_HIP_FUSED_PANEL") == "0":
+        return ("unfused",)
+    pw = int(env.get("ASM_PANEL_WGS", PANEL_WGS_D))
+    nb, nbi = 64, 512
+    if band > 0 and N > nbi + 2 * nb:
+        nrt = (nbi + 2 * nb + -(-band // 64) * 64 + nb - 1) // nb + 1
+        m = nrt - nbi // nb
+        if nrt <= 40 and nrt + m * (m + 1) // 2 <= pw:
+            return ("band",)
+    inv = False
+    if band == 0 and N <= _wide_block(layout, N, band_hint):
+        T, grid, I0 = -(-N // nb), 0, 0
+        while I0 < N:
+            I1 = N if N - I0 <= nbi + 2 * nb else min(I0 + nbi, N)
+            grid = max(grid, max(1, min(-(-(N - I0) // nb), pw)) + (-(-(I1 - I0) // nb)) * T)
+            I0 = I1
+        inv = grid <= pw
+    return ("panel", inv)
+
+
+def _ld(a):
+    return np.asarray(a, np.longdouble)
+
+
+def _spd(N, band, seed):
+    rng = np.random.default_rng(seed)
+    if band:
+        Bm = np.zeros((N, N))
+        for d in range(0, band // 2 + 1):
+            Bm[np.arange(d, N), np.arange(0, N - d)] = rng.standard_normal(N - d)
+        return Bm @ Bm.T + 0.5 * np.eye(N), rng
+    Bm = rng.standard_normal((N, N + 5))
+    return Bm @ Bm.T + 0.1 * np.eye(N), rng
+
+
+def _run_hooks(hip_lib, h, S, b, R, setting, layout, band, band_hint, wf, wb_):
+    """L, x = S^-1 b, rows of R forward-solved (first wf) and fully solved (first wb_) through the hooks with the given factor settings."""
+    N = S.shape[0]
+    mode, rel, absv, thr = setting
+    assert hip_lib.asm_test_set_band(h, band) == 0
+    assert hip_lib.asm_test_set_factor(h, layout, band_hint, mode, rel, absv, thr) == 0
+    try:
+        L = np.zeros((N, N))
+        assert hip_lib.asm_test_cholesky(h, _d(S), N, _d(L)) == 0, hip_lib.asm_last_error(h)
+        x = np.zeros(N)
+        assert hip_lib.asm_test_chol_solve(h, _d(S), N, _d(b), _d(x)) == 0, hip_lib.asm_last_error(h)
+        Xf = np.zeros((wf, N)); Xb = np.zeros((wb_, N))
+        assert hip_lib.asm_test_trsm_rows(h, _d(S), N, _d(np.ascontiguousarray(R[:wf])), wf, 0, _d(Xf)) == 0, hip_lib.asm_last_error(h)
+        assert hip_lib.asm_test_trsm_rows(h, _d(S), N, _d(np.ascontiguousarray(R[:wb_])), wb_, 1, _d(Xb)) == 0, hip_lib.asm_last_error(h)
+    finally:
+        assert hip_lib.asm_test_set_factor(h, 0, 0, 0, 0.0, 0.0, 1e-14) == 0
+        assert hip_lib.asm_test_set_band(h, 0) == 0
+    return L, x, Xf, Xb
+
+
+RATIOS = {}
+
+
+def _check_bounds(tag, S, Sl, nS, L, x, b, Xf, Xb, R, Sv, V):
+    """Condition-free backward errors in long double: the factor on probe vectors, the solve, the forward rows (L x' = r') and the full rows."""
+    N = S.shape[0]
+    Ll = _ld(L)
+    fac = np.abs(Sv - Ll @ (Ll.T @ V)).max(axis=0) / (N * U64 * nS * np.abs(V).max(axis=0))
+    sol = np.abs(Sl @ _ld(x) - _ld(b)).max() / (N * U64 * (nS * np.abs(x).max() + np.abs(b).max()))
+    nL = np.abs(L).sum(axis=1).max()
+    fwd = (np.abs(_ld(Xf) @ Ll.T - _ld(R[:len(Xf)])).max(axis=1) / (N * U64 * (nL * np.abs(Xf).max(axis=1) + np.abs(R[:len(Xf)]).max(axis=1)))).max()
+    bwd = (np.abs(_ld(Xb) @ Sl - _ld(R[:len(Xb)])).max(axis=1) / (N * U64 * (nS * np.abs(Xb).max(axis=1) + np.abs(R[:len(Xb)]).max(axis=1)))).max()
+    r = (float(fac.max()), float(sol), float(fwd), float(bwd))
+    RATIOS[tag] = r
+    print("ratio %s fac %.3f sol %.3f fwd %.3f bwd %.3f" % ((tag,) + r))
+    assert r[0] <= C_FAC, (tag, r)
+    assert max(r[1:]) <= C_SOL, (tag, r)
+
+
+# (layout, N, band, band_hint): blocking edges ASM_NB 64, CHOL_NBI 512 (+128 remainder rule), CHOL_NBO 1024, wb switch at 1536, look-ahead from
+# N > 2048, thin last tile at N mod 64 <= 16; the factor layout (one 1024-wide block up to 1024: k_chol_panel_inv at the k x k orders of the
+# null-space form); banded factors (k_chol_panel_band on D, the generic banded chain elsewhere) and S0's narrow band in a factor buffer (wb 512)
+SHAPES = ([(0, N, 0, 0) for N in (1, 2, 63, 64, 65, 129, 512, 513, 519, 530, 640, 641, 1031, 1536, 1537, 2113, 3079)]
+          + [(1, N, 0, 0) for N in (257, 512, 519, 530, 700, 1024, 1031, 1600)]
+          + [(0, N, bd, 0) for N, bd in ((700, 90), (2300, 267), (3100, 1398), (5000, 150), (2245, 40), (1100, 40), (2049, 500))]
+          + [(1, 2100, 268, 268)])
+
+
+@pytest.mark.parametrize("layout,N,band,band_hint", SHAPES)
+def test_cholesky_in_every_launch_configuration(hip_lib, config_handle, layout, N, band, band_hint):
+    """Factor, single right-hand-side solve and multi right-hand-side block substitution (forward only / forward + backward) in every
+    configuration: condition-free backward errors against long-double products, the factor against LAPACK, and bit-identity of the
+    configurations whose launch sequence differs only in the panel grid."""
+    S, rng = _spd(N, band, N + 7 * band + layout)
+    b = rng.standard_normal(N)
+    big = N > 1600
+    wf, wb_ = ((1, 4) if big else (130, 1)) if N % 2 else ((4, 1) if big else (1, 130))
+    R = rng.standard_normal((max(wf, wb_), N))
+    Sl = _ld(S)
+    nS = float(np.abs(S).sum(axis=1).max())
+    V = np.column_stack([np.ones(N)] + [rng.standard_normal(N) for _ in range(3)])
+    Sv = Sl @ _ld(V)
+    Lref = np.linalg.cholesky(S)
+    out, sel = {}, {}
+    for cfg in CONFIGS:
+        sel[cfg] = kernel_selection(cfg, layout, N, band, band_hint)
+        L, x, Xf, Xb = out[cfg] = _run_hooks(hip_lib, config_handle(cfg), S, b, R, (0, 0.0, 0.0, 1e-14), layout, band, band_hint, wf, wb_)
+        assert np.isfinite(L).all() and np.abs(L - Lref).max() / np.abs(Lref).max() < 1e-11, cfg
+        same = [c for c in out if c != cfg and sel[c] == sel[cfg]]
+        if same:               # the same kernels, another grid: the same bits (and so the same error ratios)
+            for a, c in zip(out[cfg], out[same[0]]):
+                assert np.array_equal(a, c), (cfg, same[0], sel[cfg])
+        else:
+            _check_bounds("%d/%d/%d/%s" % (layout, N, band, cfg), S, Sl, nS, L, x, b, Xf, Xb, R, Sv, V)
+
+
+# ----------------------------------------------------------------------------- dropped pivots (static guard) in every configuration
+# dependent rows (pivot / diag0 = 1e-12, tests/util.py:designed_pivot_spd) at the tile edges 63 / 64, the inner-panel edge 511 / 512, the outer-panel
+# edge 1023 / 1024 (N > 2048: row 1024 is factored by the look-ahead chain beside the trailing update), in the thin last tile, inside band panels;
+# row 0 a zero row.  (layout, N, band, rows)
+PIVOT_CASES = [(0, 2113, 0, (0, 63, 64, 511, 512, 1023, 1024, 2112)),
+               (1, 705, 0, (0, 63, 64, 511, 512, 704)),                   # one 1024-wide block: k_chol_panel_inv with dropped pivots
+               (0, 1100, 40, (1, 63, 64, 130, 511, 512, 1099))]
+
+
+@pytest.mark.parametrize("layout,N,band,rows", PIVOT_CASES)
+@pytest.mark.parametrize("setting", ["s0", "ipm", "hook"])
+def test_cholesky_dropped_pivots(hip_lib, config_handle, layout, N, band, rows, setting):
+    """The production guard settings on matrices with designed dependent rows: the dropped set is the designed one and the oracle's
+    (_chol_guard_loop on the same prepared matrix) in every configuration, L is finite and its other columns are the oracle's, the solution
+    solves the system with the dropped rows and columns removed and its dropped unknowns are ~ 0."""
+    from oracle.lp_solver import _chol_guard_loop
+    from tests.util import designed_pivot_spd, guard_prepare, expected_dropped, GUARD_SETTINGS, DEP_LEVEL
+    st = GUARD_SETTINGS[setting]
+    S, lv = designed_pivot_spd(N + len(rows), N, {j: (0.0 if j == 0 else DEP_LEVEL) for j in rows}, band=band)
+    Sp, d0 = guard_prepare(S, *st[:3])
+    Lo = _chol_guard_loop(Sp, d0, st[3])
+    want = expected_dropped(lv, setting)
+    assert np.array_equal(np.flatnonzero(np.diag(Lo) > 1e100), want)
+    keep = np.setdiff1d(np.arange(N), want)
+    rng = np.random.default_rng(N)
+    b = rng.standard_normal(N)
+    b[lv == 0.0] = 0.0                  # (a zero row kept by the regularised guard: its unknown is b_j / 1e-30)
+    R = rng.standard_normal((3, N))
+    Sk = _ld(Sp[np.ix_(keep, keep)])
+    nS = float(np.abs(Sp[np.ix_(keep, keep)]).sum(axis=1).max())
+    scale = np.abs(Lo[:, keep]).max()
+    near_singular = bool((lv[keep] < 1.0).any())
+    Vk = _ld(rng.standard_normal((len(keep), 4)))
+    SkV = Sk @ Vk
+    out, sel = {}, {}
+    for cfg in CONFIGS:
+        sel[cfg] = kernel_selection(cfg, layout, N, band, 0)
+        L, x, Xf, Xb = out[cfg] = _run_hooks(hip_lib, config_handle(cfg), S, b, R, st, layout, band, 0, 3, 3)
+        assert np.isfinite(L).all() and np.isfinite(x).all(), cfg
+        assert np.array_equal(np.flatnonzero(np.diag(L) > 1e100), want), (cfg, np.flatnonzero(np.diag(L) > 1e100))
+        below = np.arange(N)[:, None] > want[None, :]            # the entries under the dropped pivots: S_ij / 1e128
+        assert np.abs(L[:, want]).max(initial=0.0) < 1e129 and np.abs(L[:, want][below]).max(initial=0.0) < 1e-100, cfg
+        assert np.abs(x[want]).max(initial=0.0) < 1e-100 and np.abs(Xb[:, want]).max(initial=0.0) < 1e-100, cfg
+        if near_singular:
+            # kept rows with pivots of 1e-12: their columns of L are determined to ~1e-7 only and the substitutions through explicit block
+            # inverses are not backward stable at that condition - the factor's backward error on the kept rows is what is condition-free
+            Lk = _ld(L[np.ix_(keep, keep)])
+            ratio = (np.abs(SkV - Lk @ (Lk.T @ Vk)).max(axis=0) / (N * U64 * nS * np.abs(Vk).max(axis=0))).max()
+            print("ratio pivots %d/%d/%d/%s/%s fac %.3f" % (layout, N, band, setting, cfg, ratio))
+            assert ratio <= C_FAC, (cfg, ratio)
+        else:
+            assert np.abs(L[:, keep] - Lo[:, keep]).max() / scale < 1e-11, cfg
+            ratio = np.abs(Sk @ _ld(x[keep]) - _ld(b[keep])).max() / (N * U64 * (nS * np.abs(x[keep]).max() + np.abs(b[keep]).max()))
+            ratio_b = max(np.abs(Sk @ _ld(Xb[r, keep]) - _ld(R[r, keep])).max() / (N * U64 * (nS * np.abs(Xb[r, keep]).max() + np.abs(R[r, keep]).max()))
+                          for r in range(3))
+            print("ratio pivots %d/%d/%d/%s/%s sol %.3f rows %.3f" % (layout, N, band, setting, cfg, ratio, ratio_b))
+            assert max(ratio, ratio_b) <= C_SOL, (cfg, ratio, ratio_b)
+        same = [c for c in out if c != cfg and sel[c] == sel[cfg]]
+        if same:
+            for a, c in zip(out[cfg], out[same[0]]):
+                assert np.array_equal(a, c), (cfg, same[0], sel[cfg])
+
+
+def test_cholesky_selection_threshold_ladder(hip_lib, config_handle):
+    """The thresholds of the cold basis-column selection (NS_SEL_THR, absolute on a matrix of unit diagonal there): designed pivots at 1e-1,
+    1e-3, 1e-6, 1e-9 and 1e-13 of a unit-diagonal matrix give the expected dropped set at each threshold, in every configuration."""
+    from oracle.lp_solver import _chol_guard_loop
+    from tests.util import designed_pivot_spd
+    N = 300
+    ladder = {63: 1e-1, 64: 1e-3, 130: 1e-6, 256: 1e-9, 299: 1e-13}
+    S, lv = designed_pivot_spd(11, N, ladder)
+    dg = 1.0 / np.sqrt(np.diag(S))
+    S = S * dg[:, None] * dg[None, :]          # unit diagonal: the relative guard is the absolute one (the pivot levels are scale-free)
+    for thr in (1e-2, 1e-4, 1e-7, 1e-10):
+        want = np.array(sorted(j for j, l in ladder.items() if l < thr))
+        assert np.array_equal(np.flatnonzero(np.diag(_chol_guard_loop(S, np.ones(N), thr)) > 1e100), want)
+        for cfg in CONFIGS:
+            h = config_handle(cfg)
+            assert hip_lib.asm_test_set_factor(h, 0, 0, 0, 0.0, 0.0, thr) == 0
+            L = np.zeros((N, N))
+            try:
+                assert hip_lib.asm_test_cholesky(h, _d(S), N, _d(L)) == 0, hip_lib.asm_last_error(h)
+            finally:
+                assert hip_lib.asm_test_set_factor(h, 0, 0, 0, 0.0, 0.0, 1e-14) == 0
+            assert np.isfinite(L).all() and np.array_equal(np.flatnonzero(np.diag(L) > 1e100), want), (thr, cfg)

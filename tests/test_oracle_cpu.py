@@ -361,3 +361,37 @@ def test_best_iterate_snapshot_and_last_resort_rule(monkeypatch):
     qp2, out = oracle_solve(sp)
     assert out[5] == 1 and out[6]['stats']['path'] == 'ipm-conv'
     assert np.abs(out[0] - ref[0]).max() <= 1e-6 * max(1.0, np.abs(ref[0]).max())
+
+
+@pytest.mark.parametrize("N,band,rows", [(705, 0, (0, 63, 64, 511, 512, 704)), (1100, 40, (1, 63, 64, 130, 511, 512, 1099))])
+def test_designed_pivot_generator_against_the_guarded_oracle(N, band, rows):
+    """tests/util.py:designed_pivot_spd puts the pivots of its dependent rows at the designed level (1e-12 of the diagonal, 100x from the
+    guard thresholds 1e-14 and 1e-10), and the oracle's guarded factorisation drops exactly the designed set under every production guard
+    setting - else the GPU tests of the dropped pivots would compare the kernels against a wrong expectation."""
+    from oracle.lp_solver import _chol_guard_loop
+    from tests.util import designed_pivot_spd, guard_prepare, expected_dropped, GUARD_SETTINGS, DEP_LEVEL
+    S, lv = designed_pivot_spd(N + len(rows), N, {j: (0.0 if j == 0 else DEP_LEVEL) for j in rows}, band=band)
+    assert np.array_equal(S, S.T)
+    L = _chol_guard_loop(S, np.diag(S).copy(), 0.0)          # no guard: the pivots as they come out
+    piv = np.diag(L) ** 2 / np.where(np.diag(S) > 0, np.diag(S), 1.0)
+    dep = np.flatnonzero((lv < 1.0) & (lv > 0.0))
+    assert np.all(np.abs(piv[dep] / DEP_LEVEL - 1.0) < 0.05), piv[dep]
+    assert piv[lv == 1.0].min() > 1e-3
+    for name, (mode, rel, absv, thr) in GUARD_SETTINGS.items():
+        Sp, d0 = guard_prepare(S, mode, rel, absv)
+        Lg = _chol_guard_loop(Sp, d0, thr)
+        assert np.array_equal(np.flatnonzero(np.diag(Lg) > 1e100), expected_dropped(lv, name)), name
+    assert np.array_equal(expected_dropped(lv, "s0"), np.flatnonzero(lv < 1.0))
+
+
+def test_designed_pivot_ladder_against_the_guarded_oracle():
+    """The ladder of the selection thresholds (NS_SEL_THR): designed pivots 1e-1 ... 1e-13 are dropped exactly below each threshold."""
+    from oracle.lp_solver import _chol_guard_loop
+    from tests.util import designed_pivot_spd
+    ladder = {63: 1e-1, 64: 1e-3, 130: 1e-6, 256: 1e-9, 299: 1e-13}
+    S, lv = designed_pivot_spd(11, 300, ladder)
+    dg = 1.0 / np.sqrt(np.diag(S))
+    S = S * dg[:, None] * dg[None, :]
+    for thr in (1e-2, 1e-4, 1e-7, 1e-10):
+        got = np.flatnonzero(np.diag(_chol_guard_loop(S, np.ones(300), thr)) > 1e100)
+        assert np.array_equal(got, sorted(j for j, l in ladder.items() if l < thr)), thr

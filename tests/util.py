@@ -227,3 +227,76 @@ def oracle_evaluate(om, x):
     vals = W.eval_constraint_jacobian(om, [0.0] * len(j_str), xs)
     grad = W.eval_objective_gradient(om, [0.0] * om["n"], xs)
     return W.eval_objective(om, xs), np.array(grad), np.array(g, float), np.array(vals, float), j_str
+
+
+# ----------------------------------------------------------------------------- guarded Cholesky: matrices with designed pivots
+GUARD_SETTINGS = {      # (k_diag_prepare mode, rel, absv, pivot threshold) as the library factors (asm_hip.hip)
+    "hook": (0, 0.0, 0.0, 1e-14),        # the kernel hooks' default
+    "ipm": (0, 1e-13, 1e-30, 1e-14),     # Schur matrices of the interior-point iterations
+    "s0": (1, 0.0, 0.0, 1e-10),          # S0 = A_EF A_EF' of the null-space form, the active-set solves
+}
+DEP_LEVEL = 1e-12       # designed pivot / diag0 of a dependent row: 100x above 1e-14, 100x below 1e-10
+
+
+def designed_pivot_spd(seed, N, levels, band=0, K=None):
+    """SPD S = B B' + diag(delta) whose pivots are designed: row j of B in `levels` is a combination of two earlier independent rows of B
+    (exactly: its Schur complement in B B' is zero up to rounding) and delta_j puts its pivot at levels[j] * S_jj, i.e. the guarded
+    factorisation sees pivot / diag0 = levels[j] (a level 0 row is a zero row, S_jj = 0).  The other rows are independent (K >= 2 N
+    columns: their pivots are >= ~1/2 of their diagonal) and get no diagonal.  band > 0: B has half-bandwidth band // 2 - 2 and the
+    combinations use the two rows just above, so S stays within `band` of the diagonal.  Returns S and the designed levels (1 for the
+    independent rows)."""
+    rng = np.random.default_rng(seed)
+    lv = np.ones(N)
+    for j, l in levels.items():
+        lv[j] = l
+    dep = lv < 1.0
+    if band > 0:
+        hb = band // 2 - 2
+        assert hb >= 1
+        B = np.zeros((N, N))
+        for d in range(-hb, hb + 1):
+            i = np.arange(max(0, -d), min(N, N - d))
+            B[i, i + d] = rng.standard_normal(len(i))
+        B[np.arange(N), np.arange(N)] += 3.0
+    else:
+        K = K or 2 * N + 8
+        B = rng.standard_normal((N, K))
+    for j in np.flatnonzero(dep):
+        B[j] = 0.0
+        if lv[j] == 0.0:
+            continue
+        if band > 0:
+            src = [i for i in (j - 1, j - 2) if i >= 0 and not dep[i]]
+        else:
+            src = list(rng.choice([i for i in range(j) if not dep[i]], size=min(2, int((~dep[:j]).sum())), replace=False)) if j else []
+        assert src, "row %d: no earlier independent row to depend on" % j
+        for i in src:
+            B[j] += rng.uniform(0.5, 1.5) * B[i]
+    S = B @ B.T
+    for j in np.flatnonzero(dep):
+        if lv[j] > 0.0:
+            S[j, j] += lv[j] / (1.0 - lv[j]) * S[j, j]       # the Schur complement of B B' at j is 0: the pivot is this delta
+    S = np.tril(S) + np.tril(S, -1).T
+    if band > 0:
+        i, k = np.nonzero(S)
+        assert np.abs(i - k).max() <= band
+    return S, lv
+
+
+def guard_prepare(S, mode, rel, absv):
+    """k_diag_prepare restated: the matrix the guarded factorisation sees and the diag0 its threshold is relative to."""
+    S = S.copy()
+    d0 = np.diag(S).copy()
+    reg = rel * d0 + absv if mode == 0 else np.full(len(d0), rel * max(d0.max(initial=0.0), 1e-300))
+    S[np.arange(len(d0)), np.arange(len(d0))] = d0 + reg
+    return S, d0
+
+
+def expected_dropped(levels, setting):
+    """Rows the guard drops by design: pivot level below the threshold (a zero row only when the diagonal is not regularised)."""
+    mode, rel, absv, thr = GUARD_SETTINGS[setting] if isinstance(setting, str) else setting
+    lv = np.asarray(levels)
+    drop = lv < thr
+    if mode == 0 and absv > 0.0:
+        drop &= lv > 0.0           # S_jj = 0 + absv > thr * 0: a zero row is kept (its unknown is b_j / absv)
+    return np.flatnonzero(drop)
