@@ -140,7 +140,6 @@ struct Sched {
     unsigned *h_sig = nullptr, *d_sig = nullptr;
     unsigned round = 0;
     int panel_wgs = 480;
-    bool use_barriers = true;
     // statistics
     uint64_t n_rounds = 0, n_ops = 0, n_launches = 0, n_releases = 0, blob_bytes = 0;
     double t_emit_ms = 0, t_wait_ms = 0, t_host_ms = 0;
@@ -186,10 +185,8 @@ struct Sched {
         chk(hipHostMalloc((void**)&h_out, out_cap, hipHostMallocMapped), "hipHostMalloc(out)");
         chk(hipHostGetDevicePointer((void**)&d_out, h_out, 0), "hipHostGetDevicePointer(out)");
     }
-    void init(int dev, hipStream_t s, int pwgs) {
-        device = dev; stream = s; panel_wgs = pwgs;
-        if (const char* v = std::getenv("ASM_BATCH_VERBOSE")) verbose = v[0] == '1';
-        if (const char* v = std::getenv("ASM_HIP_TIMING")) time_resident = v[0] != '0'; else time_resident = true;      // as for a handle: the panel family is timed by default
+    void init(int dev, hipStream_t s, int pwgs, bool verbose_, bool time_resident_) {
+        device = dev; stream = s; panel_wgs = pwgs; verbose = verbose_; time_resident = time_resident_;
         chk(hipHostMalloc((void**)&h_sig, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(sig)");
         chk(hipHostGetDevicePointer((void**)&d_sig, h_sig, 0), "hipHostGetDevicePointer(sig)");
         *h_sig = 0;
@@ -430,7 +427,7 @@ inline void flush_wait() {
 // alignment point `tag` (tags grow in program order inside one cycle); no-op outside a batch
 inline void barrier(int tag) {
     Fiber* f = cur;
-    if (!f || !f->sched->use_barriers) return;
+    if (!f) return;
     f->tag = tag;
     f->state = Fiber::WAIT_BARRIER;
     yield_to_scheduler(f);
@@ -490,8 +487,7 @@ inline hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemc
     if (!f) {
         // outside a batch: device-to-device copies of the solver's vectors (4 - 150 KB, ~60 per LP) as a copy kernel of this library - the
         // runtime's blit path brackets each copy with its own barrier / signal packets
-        static const bool own = [] { const char* v = std::getenv("ASM_HIP_OWN_COPIES"); return !(v && v[0] == '0'); }();
-        if (own && kind == hipMemcpyDeviceToDevice && bytes > 0 && bytes <= ((size_t)64 << 20)) {
+        if (kind == hipMemcpyDeviceToDevice && bytes > 0 && bytes <= ((size_t)64 << 20)) {
             k_bcopy<<<dim3((unsigned)std::min<size_t>(256, std::max<size_t>(1, (bytes + 16383) / 16384))), dim3(256), 0, st>>>(AsmBt{nullptr, 0, 1}, (char*)dst, (const char*)src, (int64_t)bytes);
             return hipGetLastError();
         }
@@ -519,8 +515,7 @@ inline hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemc
 inline hipError_t memset_async(void* dst, int value, size_t bytes, hipStream_t st) {
     Fiber* f = cur;
     if (!f) {
-        static const bool own = [] { const char* v = std::getenv("ASM_HIP_OWN_COPIES"); return !(v && v[0] == '0'); }();
-        if (own && bytes > 0 && bytes <= ((size_t)64 << 20)) {
+        if (bytes > 0 && bytes <= ((size_t)64 << 20)) {
             k_bfill<<<dim3((unsigned)std::min<size_t>(256, std::max<size_t>(1, (bytes + 16383) / 16384))), dim3(256), 0, st>>>(AsmBt{nullptr, 0, 1}, (char*)dst, value, (int64_t)bytes);
             return hipGetLastError();
         }

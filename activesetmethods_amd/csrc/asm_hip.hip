@@ -62,6 +62,9 @@ const double EQP_RUNAWAY = 10.0, EQP_MAXCHG = 0.03;
 const int EQP_MINCHG = 32;  // oracle/lp_solver.py: growth of the primal residual between two rounds of a bulk correction that ends the attempt
 const int64_t RCM_MAX_PAIRS = 50000000;      // sum over the columns of (rows in the column)^2 beyond which no row order is computed
 const double IPM_MU0_NORMAL = 0.3;      // oracle/lp_solver.py: initial complementarity of a normal-phase LP in units of scale_q
+const double IPM_TOL0 = 3e-10;      // oracle/lp_solver.py: IPM_STAGES - tolerance of the first identification (then 0.1 IPM_TOL0, then 1e-12)
+const int IPM_SIG_EXP = 3;          // oracle/lp_solver.py: centring parameter sigma = (mu_aff / mu) ** 3
+const double IPM_ETA0 = 0.995;      // oracle/lp_solver.py: fraction of the step to the boundary while mu >= 1 (then max(IPM_ETA0, 1 - mu / scale_q), at most 0.999999)
 const double IPM_ACCEPT = 1e-8, IPM_ACCEPT_DUAL = 1e-8;      // oracle/lp_solver.py: last-resort acceptance of a converged iterate (primal residual and gap; dual residual)
 const int NS_MAX_SPLIT = 8;
 const double NS_SEL_THR[4] = {1e-2, 1e-4, 1e-7, 1e-10};
@@ -194,6 +197,27 @@ struct FacBuf {
                                     // operation stops `band` rows below the panel's last column
 };
 
+// environment knobs of a handle, read once in asm_create (README.md lists them)
+struct HandleKnobs {
+    int timing = 1;                 // ASM_HIP_TIMING: 0, 1 or 2, the initial asm_handle::timing
+    bool verbose = false;           // ASM_HIP_VERBOSE=1: solver diagnostics on stderr
+    bool spin_read = true;          // ASM_HIP_SPIN=0: hipMemcpyAsync + hipStreamSynchronize instead (14.5 us per read-back instead of 6.7 us)
+    int panel_wgs = 0;              // ASM_PANEL_WGS: grid bound of the panel kernels on the whole device (0: by the device's CU count)
+    bool ns_defer = true;           // ASM_NS_DEFER=0: the step of a null-space iteration is taken on the host
+    double ns_rerr = NS_RERR;       // ASM_NS_RERR: accuracy bound of the reduced solves of a null-space iteration (test knob - a tiny bound
+                                    // sends every LP through the fall-back to the row form)
+};
+HandleKnobs read_knobs() {
+    HandleKnobs k;
+    if (const char* v = std::getenv("ASM_HIP_TIMING")) if (v[0] >= '0' && v[0] <= '2') k.timing = v[0] - '0';
+    if (const char* v = std::getenv("ASM_HIP_VERBOSE")) k.verbose = v[0] == '1';
+    if (const char* v = std::getenv("ASM_HIP_SPIN")) k.spin_read = v[0] != '0';
+    if (const char* v = std::getenv("ASM_PANEL_WGS")) k.panel_wgs = std::max(1, std::atoi(v));
+    if (const char* v = std::getenv("ASM_NS_DEFER")) k.ns_defer = v[0] != '0';
+    if (const char* v = std::getenv("ASM_NS_RERR")) k.ns_rerr = std::atof(v);
+    return k;
+}
+
 }  // namespace
 
 struct asm_handle {
@@ -306,7 +330,6 @@ struct asm_handle {
     unsigned* h_seq = nullptr;      // sequence word the host spins on (host-mapped), d_hseq its device address
     unsigned* d_hseq = nullptr;
     unsigned scal_seq = 0;          // last sequence number handed to a publishing kernel
-    bool spin_read = true;          // ASM_HIP_SPIN=0: hipMemcpyAsync + hipStreamSynchronize instead (14.5 us per read-back instead of 6.7 us)
     int* d_idx = nullptr;
     double* h_pin = nullptr;        // pinned staging (max(ldn, Mp) doubles) x 2
     double* d_dl = nullptr;         // the answer of an LP packed on the device (k_as_pack) and its pinned host image: one device-to-host copy per LP instead of eight
@@ -330,15 +353,14 @@ struct asm_handle {
     std::vector<TimedRegion> regions;
     std::vector<hipEvent_t> event_pool;
     bool batch_slot = false;        // slot of an asm_batch: the stream belongs to the batch, no look-ahead stream, no event timing
-    bool fused_panel = true;        // Cholesky inner panels as one dataflow launch (k_chol_panel) instead of three launches per 64-wide step
-    int panel_wgs = 240;            // its grid bound: every workgroup must be able to become resident (a batch slot: its group's share)
+    int panel_wgs = 240;            // grid bound of the Cholesky panel kernels: every workgroup must be able to become resident (a batch slot: its group's share)
     int panel_wgs_dev = 240;        // the bound of the whole device (ASM_PANEL_WGS) the shares of a batch's groups are taken from
     int num_cus = 256;              // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     unsigned *d_pflags = nullptr, *d_ptmo = nullptr;
     bool test_no_polish = false;    // test hook: the active-set attempts of an LP all fail (asm_test_no_polish)
     unsigned panel_epoch = 0;
     int timing = 1;                 // HIP-event timing: 0 off, 1 the dominant kernel only (every k_syrk launch), 2 every kernel family
-    bool verbose = false;
+    HandleKnobs knobs;
 };
 
 namespace {
@@ -605,13 +627,11 @@ struct Dev {
         int id = begin(ASM_K_TRSV, 2.0 * Ma * (double)Mb * K, 8.0 * ((double)(Ma + Mb) * K + (double)Ma * Mb));
         // 64 x 64 tiles leave CUs idle when there are few right-hand sides: 32-row tiles then (same sums, same order)
         const int64_t t64 = (int64_t)((Mb + 63) / 64) * ((Ma + 63) / 64);
-        static const int ta_env = [] { const char* v = std::getenv("ASM_GEMM_TA"); return v ? std::atoi(v) : 0; }();
         // ... and 96 columns per workgroup when 32 x 64 tiles overshoot one workgroup per CU and 32 x 96 tiles do not
         const int64_t t3264 = (int64_t)((Mb + 63) / 64) * ((Ma + 31) / 32), t3296 = (int64_t)((Mb + 95) / 96) * ((Ma + 31) / 32);
-        static const int tb_env = [] { const char* v = std::getenv("ASM_GEMM_TB"); return v ? std::atoi(v) : 0; }();
-        if ((ta_env == 32 || (ta_env == 0 && t64 < 2 * (int64_t)h->num_cus)) && Ma > 32 && (tb_env == 96 || (tb_env == 0 && t3264 > h->num_cus && t3296 <= h->num_cus)))
+        if (t64 < 2 * (int64_t)h->num_cus && Ma > 32 && t3264 > h->num_cus && t3296 <= h->num_cus)
             hipLaunchKernelGGL(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
-        else if ((ta_env == 32 || (ta_env == 0 && t64 < 2 * (int64_t)h->num_cus)) && Ma > 32)
+        else if (t64 < 2 * (int64_t)h->num_cus && Ma > 32)
             hipLaunchKernelGGL(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         else
             hipLaunchKernelGGL(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), 0, h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
@@ -755,9 +775,7 @@ struct Dev {
         // timed on the stream it is launched on (HIP events see only their own stream)
         int kid = begin(ASM_K_SYRK_KERNEL, fl, 8.0 * ((double)(Ms + MsB) * K + (double)Ms * MsB), cur);
         struct EndGuard { Dev* d; int id; ~EndGuard() { d->end(id); } } guard_{this, kid};
-        // ASM_SYRK_UPD=0: the Cholesky updates through the generic kernel (ablation: what the dedicated kernel is worth)
-        static const bool use_upd = [] { const char* v = std::getenv("ASM_SYRK_UPD"); return !(v && v[0] == '0'); }();
-        if (T == 4 && mode == 1 && !nz && !idx && !theta && K % (2 * ASM_UPD_KC) == 0 && use_upd)      // Cholesky updates: their own kernel
+        if (T == 4 && mode == 1 && !nz && !idx && !theta && K % (2 * ASM_UPD_KC) == 0)      // Cholesky updates: their own kernel
             hipLaunchKernelGGL(k_syrk_upd, dim3((unsigned)blocks), dim3(256), 0, cur, A, ld, row0, Ms, K, S, ldS, srow0, MsB, ntj);
         else if (T == 4 && mode == 1 && !nz && K % 16 == 0)      // 16-wide k-chunks, two workgroups per CU
             hipLaunchKernelGGL((k_syrk<4, 8, 16, 4>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, cur, A, ld, idx, row0, Ms, K, theta, diag, S,
@@ -821,8 +839,7 @@ struct Dev {
         int id = begin(ASM_K_CHOL, fband > 0 ? (double)Ms * bw * bw : (double)Ms * Ms * Ms / 3.0, 8.0 * 1.5 * Ms * bw);
         const bool skip_inv = !want_inverse && fsmall && Ms <= ASM_SMALL_USE;
         // a factor of ONE wide block gets its explicit inverse inside the panel launches (helper workgroups of k_chol_panel_inv)
-        static const bool inv_env = [] { const char* v = std::getenv("ASM_PANEL_INV"); return !(v && v[0] == '0'); }();
-        panel_inv_now = !skip_inv && inv_env && h->fused_panel && Ms <= fwb && fband == 0 && fBinv && fBinvT && panel_inv_grid(Ms) <= h->panel_wgs;
+        panel_inv_now = !skip_inv && Ms <= fwb && fband == 0 && fBinv && fBinvT && panel_inv_grid(Ms) <= h->panel_wgs;
         const bool inv_done = panel_inv_now;
         chol_launches(Ms, thr);
         panel_inv_now = false;
@@ -832,7 +849,7 @@ struct Dev {
             return;
         }
         // explicit inverses of the wide diagonal blocks by divide and conquer over the 64-wide sub-blocks: diagonal
-        // blocks from k_potrf_diag, then log2 levels of two launches each (the scratch T uses the buffer of the
+        // blocks from the panel kernels, then log2 levels of two launches each (the scratch T uses the buffer of the
         // transposed copy, which is written afterwards)
         if (fwb == 1024) trtri_launches<1024>(Ms); else trtri_launches<512>(Ms);
         end(id);
@@ -860,7 +877,7 @@ struct Dev {
             const int I1 = (K1 - I0 <= CHOL_NBI + 2 * ASM_NB) ? K1 : std::min(I0 + CHOL_NBI, K1);
             Inext = I1;
             const int Mi = rowlim(Ms, I1);           // banded factor: the rows below are out of this inner panel's reach
-            if (h->fused_panel) {
+            {      // (scope of the panel launch's timing region: it ends before the update of the rest of the outer panel)
                 // the <= 8 steps of this inner panel in one dataflow launch (k_chol_panel): row tiles are owned by workgroups,
                 // diagonal-block factors and the panel tiles other workgroups need travel through release / acquire flags
                 const int nrt = (Mi - I0 + ASM_NB - 1) / ASM_NB;
@@ -891,18 +908,6 @@ struct Dev {
                 else
                     asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), 0, cur, fS, fld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
                                        fLinv, h->d_pflags, h->d_ptmo, h->panel_epoch);
-            } else
-            for (int k0 = I0; k0 < I1; k0 += ASM_NB) {
-                int nb = std::min(ASM_NB, Mi - k0);
-                hipLaunchKernelGGL(k_potrf_diag, dim3(1), dim3(256), 0, cur, fS, fld, k0, nb, h->d_diag0, thr, fLinv);
-                int k1 = k0 + nb;
-                if (k1 < Mi) {
-                    int rem = Mi - k1;
-                    hipLaunchKernelGGL(k_trsm_panel, dim3((unsigned)((rem + 63) / 64)), dim3(256), 0, cur, fS, fld, k0, nb, Mi, fLinv);
-                    if (k1 < I1)   // update the remaining columns of this inner panel only (rank 64: dedicated 64 x 64-tile kernel)
-                        hipLaunchKernelGGL(k_panel_update64, dim3((unsigned)((rem + 63) / 64), (unsigned)((std::min(I1, Mi) - k1 + 63) / 64)), dim3(256), 0,
-                                           cur, fS, fld, k0, k1, std::min(I1, Mi), Mi);
-                }
             }
             if (I1 < K1 && I1 < Mi) {
                 int rem = Mi - I1;
@@ -914,8 +919,7 @@ struct Dev {
     // Possible when a panel and the band's reach fit ASM_PNL_NRT row tiles and the workgroups (one per row tile + one per trailing tile) are
     // all resident; a batch slot keeps the launch sequence (its panel launches are merged across scenarios).
     bool band_panels_ok(int Ms) const {
-        static const bool env = [] { const char* v = std::getenv("ASM_BAND_PANELS"); return !(v && v[0] == '0'); }();
-        if (!env || fband <= 0 || !h->fused_panel || h->batch_slot || Ms <= CHOL_NBI + 2 * ASM_NB) return false;
+        if (fband <= 0 || h->batch_slot || Ms <= CHOL_NBI + 2 * ASM_NB) return false;
         const int nrt = (CHOL_NBI + 2 * ASM_NB + (int)round_up(fband, 64) + ASM_NB - 1) / ASM_NB + 1;
         const int m = nrt - CHOL_NBI / ASM_NB;
         return nrt <= ASM_PNL_NRT && nrt + m * (m + 1) / 2 <= h->panel_wgs;
@@ -1223,7 +1227,7 @@ struct Solver {
     unsigned grid_all() const { return (unsigned)((std::max(std::max(lp.n, lp.M), std::max<int64_t>(lp.ns, 1)) + 255) / 256); }
     // Sequence number for the next publishing kernel (0 = the kernel does not publish: copy path)
     unsigned pub_next() {
-        if (!h->spin_read) return 0;
+        if (!h->knobs.spin_read) return 0;
         h->scal_seq += 1;
         if (h->scal_seq == 0) h->scal_seq = 1;
         return h->scal_seq;
@@ -1273,11 +1277,9 @@ struct Solver {
         ip.col_ok = h->col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
         ipm_upload_lp();
         P.ncomp = ip.ncomp;
-        static const bool origin_env = [] { const char* v = std::getenv("ASM_IPM_ORIGIN_START"); return !(v && v[0] == '0'); }();      // (measurement knob)
-        hipLaunchKernelGGL(k_ipm_init_p, dim3(grid_all()), dim3(256), 0, h->stream, P, (origin_env && lp.ns == 0) ? 1 : 0);
+        hipLaunchKernelGGL(k_ipm_init_p, dim3(grid_all()), dim3(256), 0, h->stream, P, lp.ns == 0 ? 1 : 0);
         dev.gemv_n_dev(h->d_Ah, P.p, P.act);
-        static const double mu_env = [] { const char* v = std::getenv("ASM_IPM_MU0"); return v ? std::atof(v) : IPM_MU0_NORMAL; }();      // (measurement knob)
-        hipLaunchKernelGGL(k_ipm_init_rest, dim3(grid_all()), dim3(256), 0, h->stream, P, lp.ns == 0 ? mu_env : 1.0);
+        hipLaunchKernelGGL(k_ipm_init_rest, dim3(grid_all()), dim3(256), 0, h->stream, P, lp.ns == 0 ? IPM_MU0_NORMAL : 1.0);
     }
 
     void ipm_measures() {
@@ -1334,9 +1336,6 @@ struct Solver {
 
     // ------------------------------------------------------------ null-space form (oracle: class NullSpace / IPM.run use_ns)
     bool use_ns = false, ns_was_cold = false;
-    // ASM_NS_SPLIT=T,n : tile size and number of k slices of the reduced Newton matrix's build (tuning knob; default by size)
-    int ns_split_T = [] { const char* v = std::getenv("ASM_NS_SPLIT"); return v ? std::atoi(v) : 0; }();
-    int ns_split_n = [] { const char* v = std::getenv("ASM_NS_SPLIT"); const char* c = v ? std::strchr(v, ',') : nullptr; return c ? std::atoi(c + 1) : 0; }();
     bool ns_lp = false;       // this LP has a valid null-space basis (set up before the warm attempt: the active-set solves use it too)
     int ns_k = 0;
     SolveHint* cur_hint = nullptr;
@@ -1353,7 +1352,7 @@ struct Solver {
         if (h->ns_kcap > 0) {
             // the null space grew beyond what the first LP of the form reserved (fewer fixed columns than then): the k-sized buffers are
             // released and re-made; the carried basis goes with them
-            if (h->verbose) std::fprintf(stderr, "[asm] null-space form: dimension %d exceeds the reserved %d - buffers re-allocated\n", k, h->ns_kcap);
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] null-space form: dimension %d exceeds the reserved %d - buffers re-allocated\n", k, h->ns_kcap);
             HIPCHK(hipStreamSynchronize(h->stream));
             auto drop = [&](void* q) {
                 if (!q) return;
@@ -1481,7 +1480,7 @@ struct Solver {
         }
         double t_v = now_ms();
         auto vlap = [&](const char* what) {
-            if (!h->verbose) return;
+            if (!h->knobs.verbose) return;
             HIPCHK(hipStreamSynchronize(h->stream));
             const double t = now_ms();
             std::fprintf(stderr, "[asm] ns set-up %-10s +%.2f ms\n", what, t - t_v);
@@ -1703,9 +1702,9 @@ struct Solver {
         // the k range (free columns + inequality rows, 19 000 at n = 11 192) is long and the matrix small (k = 519: 45 tiles of 64 x 64):
         // split-K fills the chip; the slices are added in a fixed order while the unregularised copy N0 is made
         // (measured at k = 519, k range 19 000: 32 x 32 tiles x 8 slices 1.19 ms per iteration, 64 x 64 x 8 1.21, 32 x 32 x 4 1.21, unsplit 1.40)
-        const int T = ns_split_T > 0 ? ns_split_T : Dev::pick_tile(k);
+        const int T = Dev::pick_tile(k);
         const int64_t ntile = ((k + 32 * T - 1) / (32 * T));
-        int nsplit = ns_split_n > 0 ? ns_split_n : (int)std::min<int64_t>(NS_MAX_SPLIT, std::max<int64_t>(1, 1224 / std::max<int64_t>(1, ntile * (ntile + 1) / 2)));
+        int nsplit = (int)std::min<int64_t>(NS_MAX_SPLIT, std::max<int64_t>(1, 1224 / std::max<int64_t>(1, ntile * (ntile + 1) / 2)));
         nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, h->ns_ldg / 512));
         if (nsplit > 1) {
             const int64_t pstride = h->ns_fN.ld * h->ns_fN.ld;
@@ -1886,25 +1885,21 @@ struct Solver {
         hipLaunchKernelGGL(k_ipm_dir, dim3(g), dim3(256), 0, h->stream, P, D, d_tN);
     }
 
-    // accuracy bound of the reduced solves of a null-space iteration (ASM_NS_RERR: test knob - a tiny bound sends every LP through the fall-back to the row form)
-    static double ns_rerr() { static const double e = [] { const char* v = std::getenv("ASM_NS_RERR"); return v ? std::atof(v) : NS_RERR; }(); return e; }
-    static int sig_exp() { static const int e = [] { const char* v = std::getenv("ASM_IPM_SIGEXP"); return v ? std::atoi(v) : 3; }(); return e; }      // (measurement knob)
-    static double eta0() { static const double e = [] { const char* v = std::getenv("ASM_IPM_ETA0"); return v ? std::atof(v) : 0.995; }(); return e; }
     int btag = 100;      // alignment tags of a scenario batch grow in program order inside one LP (asm_batch.hip.h)
     int ipm_run(double tol, int max_more) {
         const int M = (int)lp.M;
         int done = 0;
         // null-space iterations apply their step on the device (k_ns_update_dev) and are checked with the NEXT measures: one read-back per
         // iteration.  ns_pending: the last iteration was one of those and its accuracy check is still owed
-        static const bool ns_defer = [] { const char* v = std::getenv("ASM_NS_DEFER"); return !(v && v[0] == '0'); }();      // (measurement knob)
+        const bool ns_defer = h->knobs.ns_defer;
         bool ns_pending = false;
         while (true) {
             asmb::barrier(btag);                 // scenario batch: iterations of different scenarios run in lockstep (min-PC-first)
             ipm_measures();
             if (ns_pending) {
                 ns_pending = false;
-                if (h->verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e (null-space step, applied on the device)\n", h->h_scal[SC_AP], h->h_scal[SC_AD]);
-                if (h->h_scal[SC_NSERR] > ns_rerr()) {
+                if (h->knobs.verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e (null-space step, applied on the device)\n", h->h_scal[SC_AP], h->h_scal[SC_AD]);
+                if (h->h_scal[SC_NSERR] > h->knobs.ns_rerr) {
                     // the reduced system lost its accuracy and the device left the iterate alone: redo the iteration in row form
                     // (oracle: IPM.run) - measured again below as the row form measures it
                     ns_finish_y();
@@ -1912,7 +1907,7 @@ struct Solver {
                     continue;
                 }
             }
-            if (h->verbose) std::fprintf(stderr, "[asm] ipm %3d pinf %.3e dinf %.3e gap %.3e\n", ip.iters, ip.pinf, ip.dinf, ip.gap);
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] ipm %3d pinf %.3e dinf %.3e gap %.3e\n", ip.iters, ip.pinf, ip.dinf, ip.gap);
             if (ip.pinf <= tol && ip.gap <= tol && (ip.dinf <= tol || (ip.gap <= IPM_GAP_DONE * tol && ip.dinf <= IPM_DINF_FLOOR))) {
                 if (ns_live()) ns_finish_y();
                 return ip.status = ASM_OPTIMAL;
@@ -2023,7 +2018,7 @@ struct Solver {
                 cg_fail = false;
                 if (use_ns) ns_newton(0, dirA, dirA); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
                 hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, 0u);
-                hipLaunchKernelGGL(k_ipm_muaff, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, sig_exp());
+                hipLaunchKernelGGL(k_ipm_muaff, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, IPM_SIG_EXP);
                 if (use_ns) ns_newton(1, dirA, dirC); else ipm_solve(1, dirA, dirC, 0.0, 0.0, deferred ? 2 : 0);
                 if (use_ns && ns_defer) {       // step lengths stay on the device (k_ns_update_dev below)
                     hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirC, 0u);
@@ -2051,17 +2046,16 @@ struct Solver {
                 }
                 return true;
             };
-            static const bool spec_env = [] { const char* v = std::getenv("ASM_IPM_DEFER_CHECK"); return !(v && v[0] == '0'); }();
-            const bool defer = spec_env && !use_ns && !use_col && !use_red;      // the factor of S itself is the preconditioner
+            const bool defer = !use_ns && !use_col && !use_red;      // the factor of S itself is the preconditioner
             if (!(defer && solves(true))) solves(false);
             if (use_ns && ns_defer) {
-                const double eta = ip.mu >= 1.0 ? eta0() : std::min(std::max(eta0(), 1.0 - ip.mu / lp.scale_q), 0.999999);
-                hipLaunchKernelGGL(k_ns_update_dev, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, eta, nsv(14), h->ldn, ns_rerr());
+                const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
+                hipLaunchKernelGGL(k_ns_update_dev, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, eta, nsv(14), h->ldn, h->knobs.ns_rerr);
                 ns_pending = true;
                 continue;
             }
-            if (h->verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e  cg steps so far %lld\n", ap, ad, (long long)h->stats_pcg);
-            if (use_ns && h->h_scal[SC_NSERR] > ns_rerr()) {
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e  cg steps so far %lld\n", ap, ad, (long long)h->stats_pcg);
+            if (use_ns && h->h_scal[SC_NSERR] > h->knobs.ns_rerr) {
                 ns_finish_y();
                 ip.ns_off = true;          // the reduced system lost its accuracy: redo the iteration in row form (oracle: IPM.run)
                 continue;
@@ -2074,7 +2068,7 @@ struct Solver {
                 ip.red_off = true;
                 continue;
             }
-            const double eta = ip.mu >= 1.0 ? eta0() : std::min(std::max(eta0(), 1.0 - ip.mu / lp.scale_q), 0.999999);
+            const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
             if (use_ns)
                 hipLaunchKernelGGL(k_ns_update, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), nsv(14),
                                    1.0 - std::min(1.0, eta * ap), h->ldn);
@@ -2272,7 +2266,7 @@ struct Solver {
             h->stats.kkt_pr = pr;
             h->stats.kkt_du = du;
             final_sets = cur;
-            if (h->verbose) {
+            if (h->knobs.verbose) {
                 const double t_now = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
                 std::fprintf(stderr, "[asm] eqp round %d: pr %.3e du %.3e changes %d  (%.2f ms)\n", k, pr, du, h->h_ascnt[AC_NCHG], t_now - t_round);
                 t_round = t_now;
@@ -2372,7 +2366,7 @@ struct Solver {
             hipLaunchKernelGGL(k_face_ns_step, dim3(1), dim3(1024), 0, h->stream, A, S_[4], d_pa, d_sa, d_acta, TOL_P);
             as_read();                                    // (the host copy of u is no longer needed by the device after this)
             const int nviol = h->h_ascnt[AC_NVIOL];
-            if (h->verbose && (st < 5 || st % 20 == 0 || nviol == 0))
+            if (h->knobs.verbose && (st < 5 || st % 20 == 0 || nviol == 0))
                 std::fprintf(stderr, "[asm] face primal anchored %d: members %d viol %d hres %.2e\n", st, k, nviol, h->h_asscal[AS_HARDRES]);
             if (h->h_asscal[AS_HARDRES] > TOL_P) return false;
             if (nviol == 0) {
@@ -2436,7 +2430,7 @@ struct Solver {
         as_read();
         h->stats.kkt_pr = h->h_asscal[AS_PR];
         h->stats.kkt_du = h->h_asscal[AS_DU];
-        if (h->verbose) std::fprintf(stderr, "[asm] face polish: projection of the iterate on its partition pr %.3e du %.3e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
+        if (h->knobs.verbose) std::fprintf(stderr, "[asm] face polish: projection of the iterate on its partition pr %.3e du %.3e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
         if (!(h->h_asscal[AS_PR] <= TOL_P && h->h_asscal[AS_DU] <= TOL_D)) return 0;
         dcopy(d_p0, A.p, n); dcopy(d_s0, A.s, ns); dcopy(d_y0, A.y, M); dcopy(d_act0, A.act, M); dcopy(d_z0, A.z, n);
         part_factor = true;            // the factor in d_S belongs to the partition: the first dual / primal round below re-use it
@@ -2448,7 +2442,7 @@ struct Solver {
             as_solve(S_[5], nullptr, nullptr, 2, r == 0);
             hipLaunchKernelGGL(k_face_dual_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[5], FACE_TOL_M);
             as_read();
-            if (h->verbose) std::fprintf(stderr, "[asm] face dual %d: nH %d nF %d viol %d\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL]);
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] face dual %d: nH %d nF %d viol %d\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL]);
             if (h->h_ascnt[AC_NVIOL] == 0) { okd = true; break; }
         }
         if (okd) { dcopy(d_yf, A.y, M); dcopy(d_zf, A.z, n); }
@@ -2460,7 +2454,7 @@ struct Solver {
                 as_solve(S_[4], nullptr, nullptr, 1, r == 0);
                 hipLaunchKernelGGL(k_face_primal_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 0);
                 as_read();
-                if (h->verbose) std::fprintf(stderr, "[asm] face primal bulk %d: nH %d nF %d viol %d rel %d hres %.2e\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL], h->h_ascnt[AC_NREL], h->h_asscal[AS_HARDRES]);
+                if (h->knobs.verbose) std::fprintf(stderr, "[asm] face primal bulk %d: nH %d nF %d viol %d rel %d hres %.2e\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL], h->h_ascnt[AC_NREL], h->h_asscal[AS_HARDRES]);
                 if (h->h_asscal[AS_HARDRES] > TOL_P) break;            // over-determined working set
                 if (h->h_ascnt[AC_NVIOL] > 0) continue;
                 if (h->h_ascnt[AC_NREL] == 0) { okp = true; break; }
@@ -2482,7 +2476,7 @@ struct Solver {
             as_read();
             h->stats.kkt_pr = h->h_asscal[AS_PR];
             h->stats.kkt_du = h->h_asscal[AS_DU];
-            if (h->verbose) std::fprintf(stderr, "[asm] face kkt pr %.2e du %.2e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] face kkt pr %.2e du %.2e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
             if (h->h_asscal[AS_PR] <= TOL_P && h->h_asscal[AS_DU] <= TOL_D) { final_sets = 4; return 2; }
         }
         dcopy(A.p, d_p0, n); dcopy(A.s, d_s0, ns); dcopy(A.y, d_y0, M); dcopy(A.act, d_act0, M); dcopy(A.z, d_z0, n);
@@ -2519,7 +2513,7 @@ struct Solver {
     bool snap_e = false;      // the snapshot of the best iterate holds the null-space form's component e
     int solve_scaled(const ActiveSet* warm, SolveHint& hint) {
         int st = solve_scaled_impl(warm, hint);
-        if (h->verbose) std::fprintf(stderr, "[asm] phases: warm %.2f ms, ipm %.2f ms (%d its), polish %.2f ms, path %d\n", t_warm, t_ipm, ip.iters, t_polish, h->stats.path);
+        if (h->knobs.verbose) std::fprintf(stderr, "[asm] phases: warm %.2f ms, ipm %.2f ms (%d its), polish %.2f ms, path %d\n", t_warm, t_ipm, ip.iters, t_polish, h->stats.path);
         return st;
     }
     int solve_scaled_impl(const ActiveSet* warm, SolveHint& hint) {
@@ -2544,7 +2538,7 @@ struct Solver {
             if (ns_lp) ns_lp_vectors();
             h->stats.ns_dim = ns_lp ? ns_k : 0;
             h->stats.ns_cold = (ns_lp && (had == 0 || ns_was_cold)) ? 1 : 0;
-            if (h->verbose) {
+            if (h->knobs.verbose) {
                 HIPCHK(hipStreamSynchronize(h->stream));
                 std::fprintf(stderr, "[asm] null-space set-up: %s, k = %d, %s basis columns, %.2f ms\n", ns_lp ? "ok" : "not usable", ns_k, ns_was_cold ? "fresh" : "retained", now_ms() - t0);
             }
@@ -2569,8 +2563,7 @@ struct Solver {
         btag = 90;
         asmb::barrier(btag);
         ipm_init();
-        static const double tol0_env = [] { const char* v = std::getenv("ASM_IPM_TOL0"); return v ? std::atof(v) : 3e-10; }();      // (measurement knob: tolerance of the first identification)
-        const double tols[3] = {tol0_env, 0.1 * tol0_env, 1e-12};      // oracle: IPM_STAGES
+        const double tols[3] = {IPM_TOL0, 0.1 * IPM_TOL0, 1e-12};      // oracle: IPM_STAGES
         const int more[3] = {IPM_MAXIT, 6, 6};
         bool have_sets = false;
         double best_m = INF, m_last = INF;
@@ -2609,7 +2602,7 @@ struct Solver {
             }
             double t1 = now_ms();
             identify_dev(3);
-            if (h->verbose) { HIPCHK(hipStreamSynchronize(h->stream)); std::fprintf(stderr, "[asm] stage %d identify %.2f ms\n", stage, now_ms() - t1); }
+            if (h->knobs.verbose) { HIPCHK(hipStreamSynchronize(h->stream)); std::fprintf(stderr, "[asm] stage %d identify %.2f ms\n", stage, now_ms() - t1); }
             have_sets = true;
             bool tried_ln = false;
             if (ns_lp) {
@@ -2642,7 +2635,7 @@ struct Solver {
             // times worse than the best - the best iterate comes back, the final attempts run on it and on the partition identified from it
             hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
             ipm_measures();
-            if (h->verbose) std::fprintf(stderr, "[asm] last stage ended %.1e against %.1e at best: best iterate restored (pinf %.3e dinf %.3e gap %.3e)\n", m_last, best_m, ip.pinf, ip.dinf, ip.gap);
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] last stage ended %.1e against %.1e at best: best iterate restored (pinf %.3e dinf %.3e gap %.3e)\n", m_last, best_m, ip.pinf, ip.dinf, ip.gap);
             h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap;
             h->stats.restored = 1;
             identify_dev(3);
@@ -2781,7 +2774,7 @@ void free_device(asm_handle* h) {
 }
 
 void check_panel_timeout(asm_handle* h) {
-    if (!h->fused_panel || !h->d_ptmo) return;
+    if (!h->d_ptmo) return;
     unsigned tmo = 0;
     HIPCHK(hipMemcpy(&tmo, h->d_ptmo, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (tmo != 0) {
@@ -3014,7 +3007,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
             h->ns_eidx_h = eidx;
             h->d_nsEidx = ialloc(eidx, nE); h->d_nsEpos = ialloc(epos, h->M); h->d_nsIidx = ialloc(iidx, h->ns_nI); h->d_nsIpos = ialloc(ipos, h->M);
             h->d_nscnt = ialloc({}, 16);
-            const int f0_band = (std::getenv("ASM_HIP_NO_BAND") || 2 * (int64_t)s0_band >= nE) ? 0 : std::max(s0_band, 1);
+            const int f0_band = 2 * (int64_t)s0_band >= nE ? 0 : std::max(s0_band, 1);
             ns_alloc_factor(h, h->ns_f0, h->ns_nEp, f0_band);
             h->ns_f0.band = f0_band;
             if (h->ns_f0.band > 0) {            // S0 is then built entry by entry from its structural pattern (k_ns_s0_sparse)
@@ -3030,7 +3023,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     // row order of the factorisations (see asm_handle::row_band)
     h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->main_band_cur = 0;
     h->d_rowperm = h->d_rowpos = h->d_rowpairs = h->d_cpos = nullptr;
-    if (h->sp_ok && !std::getenv("ASM_HIP_NO_BAND") && h->M >= 256) {
+    if (h->sp_ok && h->M >= 256) {
         std::vector<int> all(h->M), pairs_pos;
         for (int64_t i = 0; i < h->M; ++i) all[i] = (int)i;
         int bw = 0;
@@ -3056,7 +3049,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     }
     // column order of the column form (K = Th + A' D^-1 A couples two columns when they share a row)
     h->col_band = 0; h->n_colpairs = 0; h->d_colperm = h->d_colpos = h->d_colpairs = nullptr;
-    if (h->sp_ok && h->col_capable && !std::getenv("ASM_HIP_NO_BAND") && n >= 256) {
+    if (h->sp_ok && h->col_capable && n >= 256) {
         std::vector<int> all(n), pairs_pos;
         for (int64_t j = 0; j < n; ++j) all[j] = (int)j;
         int bw = 0;
@@ -3143,7 +3136,7 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
     vec c(n), rel(n);
     const double tr0 = Solver::now_ms();
     auto lap = [&](const char* what) {
-        if (!h->verbose) return;
+        if (!h->knobs.verbose) return;
         HIPCHK(hipStreamSynchronize(h->stream));
         static thread_local double last = 0.0;
         const double t = Solver::now_ms();
@@ -3394,18 +3387,12 @@ int asm_create(int device, asm_handle** out) {
     }
     std::memset(&h->kstats, 0, sizeof(h->kstats));
     std::memset(&h->stats, 0, sizeof(h->stats));
-    const char* tm = std::getenv("ASM_HIP_TIMING");
-    h->timing = (tm && tm[0] >= '0' && tm[0] <= '2') ? tm[0] - '0' : 1;
-    const char* vb = std::getenv("ASM_HIP_VERBOSE");
-    h->verbose = vb && vb[0] == '1';
-    const char* sp = std::getenv("ASM_HIP_SPIN");
-    h->spin_read = !(sp && sp[0] == '0');
-    const char* fp = std::getenv("ASM_HIP_FUSED_PANEL");
-    h->fused_panel = !(fp && fp[0] == '0');
+    h->knobs = read_knobs();
+    h->timing = h->knobs.timing;
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 16) { h->num_cus = prop.multiProcessorCount; h->panel_wgs = 2 * prop.multiProcessorCount - 32; }
-        if (const char* pw = std::getenv("ASM_PANEL_WGS")) h->panel_wgs = std::max(1, std::atoi(pw));
+        if (h->knobs.panel_wgs > 0) h->panel_wgs = h->knobs.panel_wgs;
         h->panel_wgs_dev = h->panel_wgs;
     }
     *out = h;
@@ -4247,6 +4234,8 @@ struct asm_batch {
     std::vector<int> J_ref;         // basis columns of the null-space form every scenario starts from (first cold selection of the batch)
     bool setup_done = false;
     asm_batch_stats stats;
+    bool verbose = false;           // ASM_BATCH_VERBOSE=1: per-kernel merge statistics of every group at release
+    bool time_panels = true;        // HIP events around the groups' merged panel launches (off when ASM_HIP_TIMING=0, as for a handle)
 };
 
 namespace {
@@ -4330,8 +4319,7 @@ void batch_make_groups(asm_batch* b, int n_groups) {
         // full of spinning consumers the producer never would).  The slots size their panel grids to the same share: a resident launch
         // wider than the share would go out unmerged at its full grid
         const int share = std::max(16, b->slots[0]->panel_wgs_dev / n_groups);
-        g->sched.init(b->device, g->stream, share);
-        if (const char* nb = std::getenv("ASM_BATCH_NO_BARRIERS")) g->sched.use_barriers = !(nb[0] == '1');
+        g->sched.init(b->device, g->stream, share, b->verbose, b->time_panels);
         for (int s = g->lo; s < g->hi; ++s) { b->slots[s]->stream = g->stream; b->slots[s]->stream2 = g->stream; b->slots[s]->panel_wgs = share; }
     }
 }
@@ -4374,6 +4362,8 @@ int asm_batch_create(int device, int n_slots, asm_batch** out) {
             // all-resident panel kernels of four streams crowd each other out of the compute units)
             int ng = n_slots >= 48 ? 3 : (n_slots >= 16 ? 2 : 1);
             if (const char* e = std::getenv("ASM_BATCH_GROUPS")) ng = std::max(1, std::atoi(e));
+            if (const char* v = std::getenv("ASM_BATCH_VERBOSE")) b->verbose = v[0] == '1';
+            b->time_panels = b->slots[0]->knobs.timing != 0;      // ASM_HIP_TIMING as the slots read it
             batch_make_groups(b, ng);
         } catch (const std::exception&) { rc = ASM_ERR_HIP; }
     }

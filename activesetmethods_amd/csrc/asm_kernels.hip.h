@@ -11,8 +11,6 @@
 //   k_scale_rows      HBM   row max + scaled copy
 //   k_gemv_n/t        HBM   Ah x , Ah' y
 //   k_syrk<T>         MFMA  S = Ah[idx,:] diag(theta) Ah[idx,:]' (+diag)  and  S22 -= P P'   (v_mfma_f64_16x16x4_f64)
-//   k_potrf_diag      LDS   64x64 diagonal block Cholesky with static pivot guard
-//   k_trsm_panel      LDS   panel  P = S21 L11^-T
 //   k_trtri_*, k_wtrsv_*<WB>  HBM   wide (512 / 1024) block inverses and the wide-block forward / backward substitution
 //   k_spmv_*          HBM   matrix-vector products on the CSR / CSC copy of sparse patterns
 #pragma once
@@ -605,9 +603,9 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
     int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
     return __hiloint2double(hi, lo);
 }
-// body shared by the stand-alone kernel and the fused panel kernel: D, W are ASM_NB x ASM_DP LDS buffers, T 4 x (16 x 17)
+// body of the diagonal-block step of the panel kernels: D, W are ASM_NB x ASM_DP LDS buffers, T 4 x (16 x 17)
 typedef double potrf_T_t[16 * 17];
-template <bool SC1, bool OPQ = false, bool PADSKIP = false>
+template <bool OPQ = false, bool PADSKIP = false>
 __device__ __forceinline__ void potrf64_body(double* __restrict__ D, double* __restrict__ W, potrf_T_t* __restrict__ T, double* __restrict__ d0,
                                              double* __restrict__ dinv, double* __restrict__ S, int64_t ldS, int k0, int nb,
                                              const double* __restrict__ diag0, double thr, double* __restrict__ Linv) {
@@ -786,109 +784,8 @@ __device__ __forceinline__ void potrf64_body(double* __restrict__ D, double* __r
     _Pragma("unroll") for (int e_it = 0; e_it < ASM_NB * ASM_NB / 256; ++e_it) {      /* constant trip count, fully unrolled: all of a thread's loads in flight */
         const int e = tid + 256 * e_it;
         const double v = W[(e >> 6) * ASM_DP + (e & 63)];
-        if (SC1) __hip_atomic_store(out + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // write-through: read by other workgroups of this launch
-        else out[e] = v;
+        __hip_atomic_store(out + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // write-through: read by other workgroups of this launch
     }
-}
-__global__ __launch_bounds__(256) void k_potrf_diag(AsmBt abt, double* __restrict__ S, int64_t ldS, int k0, int nb, const double* __restrict__ diag0, double thr, double* __restrict__ Linv) {
-    ASM_BARGS(abt, S, ldS, k0, nb, diag0, thr, Linv);
-    __shared__ double D[ASM_NB * ASM_DP];
-    __shared__ double W[ASM_NB * ASM_DP];
-    __shared__ potrf_T_t T[4];
-    __shared__ double d0[ASM_NB], dinv[ASM_NB];
-    potrf64_body<false>(D, W, T, d0, dinv, S, ldS, k0, nb, diag0, thr, Linv);
-}
-
-// Panel solve through the explicit inverse:  S[i, k0:k1] <- S[i, k0:k1] * Linv11'  for the 64 rows of this tile, as one
-// 64x64x64 product on the matrix cores: wavefront w owns rows 16w..16w+15 (four 16x16 tiles, 16 k-steps of
-// v_mfma_f64_16x16x4_f64).  X Linv' = sum_q X[r][q] Linv[c][q], so the right operand is needed transposed - which is the
-// row-major Linv itself; both operands sit in LDS with pitch = 2 mod 32 doubles (conflict-free fragment reads).  Linv is
-// lower triangular with explicit zeros above the diagonal, so the full product is the triangular one.
-#define ASM_XP 66
-__global__ __launch_bounds__(256) void k_trsm_panel(AsmBt abt, double* __restrict__ S, int64_t ldS, int k0, int nb, int Ms, const double* __restrict__ Linv) {
-    ASM_BARGS(abt, S, ldS, k0, nb, Ms, Linv);
-    __shared__ double Xa[ASM_NB * ASM_XP];      // the tile  X[r][q]
-    __shared__ double Li[ASM_NB * ASM_XP];      // Linv[c][q]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i0 = k0 + nb + blockIdx.x * ASM_NB;
-    const double* Lb = Linv + (int64_t)(k0 / ASM_NB) * ASM_NB * ASM_NB;
-    _Pragma("unroll") for (int e_it = 0; e_it < ASM_NB * ASM_NB / 256; ++e_it) {      /* constant trip count, fully unrolled: all of a thread's loads in flight */
-        const int e = tid + 256 * e_it;
-        int rr = e >> 6, c = e & 63;
-        Li[rr * ASM_XP + c] = Lb[e];
-        int gi = i0 + rr;
-        const double v = S[(int64_t)min(gi, Ms - 1) * ldS + k0 + min(c, nb - 1)];
-        Xa[rr * ASM_XP + c] = ((gi < Ms) & (c < nb)) ? v : 0.0;
-    }
-    __syncthreads();
-    v4f64 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = (v4f64){0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (int kk = 0; kk < ASM_NB; kk += 4) {
-        double af = Xa[(w * 16 + (lane & 15)) * ASM_XP + kk + (lane >> 4)];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            double bf = Li[(t * 16 + (lane & 15)) * ASM_XP + kk + (lane >> 4)];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[t], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = w * 16 + (lane >> 4) + 4 * r, col = t * 16 + (lane & 15);
-            int gi = i0 + row;
-            if (gi < Ms && col < nb) S[(int64_t)gi * ldS + k0 + col] = acc[t][r];
-        }
-}
-
-// In-panel rank-64 update of the Cholesky:  S[r, c] -= P[r, :] . P[c, :]  for rows r >= k1 and columns k1 <= c < c_end
-// (c <= r), P = S[:, k0:k0+64] the panel just solved.  One workgroup per 64 x 64 tile: both operand tiles are staged whole
-// (pitch = 2 mod 32 doubles), 16 k-steps of v_mfma_f64_16x16x4_f64 per wavefront, the accumulators start from the S tile
-// and the left operand is negated - the generic k_syrk pays its k-chunk pipeline and 128 x 128 tiles for K = 64.
-__global__ __launch_bounds__(256) void k_panel_update64(AsmBt abt, double* __restrict__ S, int64_t ldS, int k0, int k1, int c_end, int Ms) {
-    ASM_BARGS(abt, S, ldS, k0, k1, c_end, Ms);
-    __shared__ double Pa[ASM_NB * ASM_XP];
-    __shared__ double Pb[ASM_NB * ASM_XP];
-    const int ti = blockIdx.x, tj = blockIdx.y;
-    if (tj > ti) return;                                   // strictly upper tile
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r0 = k1 + ti * ASM_NB, c0 = k1 + tj * ASM_NB;
-    _Pragma("unroll") for (int e_it = 0; e_it < ASM_NB * ASM_NB / 256; ++e_it) {      /* constant trip count, fully unrolled: all of a thread's loads in flight */
-        const int e = tid + 256 * e_it;
-        int rr = e >> 6, c = e & 63;
-        const double va = S[(int64_t)min(r0 + rr, Ms - 1) * ldS + k0 + c], vb = S[(int64_t)min(c0 + rr, Ms - 1) * ldS + k0 + c];
-        Pa[rr * ASM_XP + c] = (r0 + rr < Ms) ? -va : 0.0;
-        Pb[rr * ASM_XP + c] = (c0 + rr < Ms) ? vb : 0.0;
-    }
-    v4f64 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = r0 + w * 16 + (lane >> 4) + 4 * r, col = c0 + t * 16 + (lane & 15);
-            const int rc = min(row, Ms - 1);
-            const double v = S[(int64_t)rc * ldS + min(col, min(c_end - 1, rc))];
-            acc[t][r] = ((row < Ms) & (col < c_end) & (col <= row)) ? v : 0.0;
-        }
-    __syncthreads();
-#pragma unroll 4
-    for (int kk = 0; kk < ASM_NB; kk += 4) {
-        double af = Pa[(w * 16 + (lane & 15)) * ASM_XP + kk + (lane >> 4)];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            double bf = Pb[(t * 16 + (lane & 15)) * ASM_XP + kk + (lane >> 4)];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[t], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = r0 + w * 16 + (lane >> 4) + 4 * r, col = c0 + t * 16 + (lane & 15);
-            if (row < Ms && col < c_end && col <= row) S[(int64_t)row * ldS + col] = acc[t][r];
-        }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -954,6 +851,8 @@ __global__ __launch_bounds__(256) void k_pnl_wait_probe(AsmBt abt, unsigned* fla
     ASM_BARGS(abt, flag, epoch, tmo);
     pnl_wait(flag, epoch, tmo);
 }
+// LDS pitch of the 64 x 64 operand tiles of the panel kernels: 2 mod 32 doubles (conflict-free fragment reads)
+#define ASM_XP 66
 #define ASM_PNL_LDS (2 * ASM_NB * ASM_XP + 4 * 16 * 17 + 2 * ASM_NB)
 #define ASM_PNL_NRT 40      // BAND variant: most row tiles of one launch (panel + reach of the band)
 #define ASM_PNL_NS 10       // most 64-wide steps of one panel launch: eight, or up to ten when the last inner panel absorbs a short remainder (flag words: NS for the diagonal blocks + NS * NS for the panel tiles)
@@ -986,7 +885,7 @@ __device__ __forceinline__ void chol_panel_body(double* __restrict__ sm, double*
 #define QSTAMP(cond) do {} while (0)
 #endif
     if (wg == 0) {
-        potrf64_body<true, OPQ, THIN>(B0, B1, Tt, d0, dinv, S, ldS, I0, min(ASM_NB, Ms - I0), diag0, thr, Linv);
+        potrf64_body<OPQ, THIN>(B0, B1, Tt, d0, dinv, S, ldS, I0, min(ASM_NB, Ms - I0), diag0, thr, Linv);
         pnl_publish(flags + 0, epoch);
     }
     for (int k = 0; k < nsteps; ++k) {
@@ -1173,7 +1072,7 @@ __device__ __forceinline__ void chol_panel_body(double* __restrict__ sm, double*
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 QSTAMP(k == 1 && rt == 2);
-                potrf64_body<true, OPQ, THIN>(B0, B1, Tt, d0, dinv, S, ldS, kn, min(ASM_NB, Ms - kn), diag0, thr, Linv);
+                potrf64_body<OPQ, THIN>(B0, B1, Tt, d0, dinv, S, ldS, kn, min(ASM_NB, Ms - kn), diag0, thr, Linv);
                 QSTAMP(k == 1 && rt == 2);
                 pnl_publish(flags + rt, epoch);
                 QSTAMP(k == 1 && rt == 2);
@@ -1560,7 +1459,7 @@ __global__ __launch_bounds__(256) void k_tile_nzflags(AsmBt abt, const double* _
 
 // ---------------------------------------------------------------------------------------------------
 // Wide-block triangular solves.  After the factorisation the 512 x 512 diagonal blocks of L are inverted explicitly
-// (k_trtri_init / k_trtri_level, from the 64 x 64 block inverses of k_potrf_diag), so a solve needs 2-3 launches per wide
+// (k_trtri_init / k_trtri_level, from the 64 x 64 block inverses of the panel kernels), so a solve needs 2-3 launches per wide
 // block and direction instead of one per 64-wide block.
 // WB = width of a wide block (template parameter: 512 for small systems, 1024 otherwise - asm_hip.hip: pick_wb)
 // Block inversion by divide and conquer (dependent chain of 2*log2 launches).  The inverse of a lower-triangular 2h x 2h block [L11 0; L21 L22] is [X11 0; -X22 L21 X11  X22];

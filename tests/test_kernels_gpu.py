@@ -267,9 +267,8 @@ def test_banded_cholesky_and_solves(hip_lib, handle, N, band, nrhs):
 #            chain: k_chol_panel + rowlim + banded rank-K updates) and no k_chol_panel_inv (k_trtri_* instead)
 #   W175  the budget just below the old worst-case gate of the in-launch inverse (ASM_PNL_WT (ASM_PNL_NS + 1) = 176); the gate is the launch's
 #         own grid (at most 144 for a factor of one 1024-wide block), so W175 takes D's sequence
-#   U     ASM_HIP_FUSED_PANEL=0: k_potrf_diag / k_trsm_panel / k_panel_update64, three launches per 64-wide step
 CONFIGS = {"D": {}, "W1": {"ASM_PANEL_WGS": "1"}, "W5": {"ASM_PANEL_WGS": "5"}, "W16": {"ASM_PANEL_WGS": "16"},
-           "W175": {"ASM_PANEL_WGS": "175"}, "U": {"ASM_HIP_FUSED_PANEL": "0"}}
+           "W175": {"ASM_PANEL_WGS": "175"}}
 PANEL_WGS_D = 480
 U64 = 2.0 ** -53
 # condition-free backward-error bars (u = 2^-53); largest ratios measured on an MI355X over every shape and configuration: 2.12 (factor,
@@ -287,7 +286,6 @@ def config_handle(hip_lib):
         if name not in made:
             with pytest.MonkeyPatch.context() as mp:
                 mp.delenv("ASM_PANEL_WGS", raising=False)
-                mp.delenv("ASM_HIP_FUSED_PANEL", raising=False)
                 for k, v in CONFIGS[name].items():
                     mp.setenv(k, v)
                 h = C.c_void_p()
@@ -309,14 +307,11 @@ def _wide_block(layout, N, band_hint):
 
 
 def kernel_selection(config, layout, N, band=0, band_hint=0):
-    """The launch sequence Dev::chol chooses for this configuration (band_panels_ok, the gate of the in-launch inverse panel_inv_grid,
-    fused or not), everything but the grid G = min(nrt, panel_wgs) of the panel launches.  Configurations with the same selection give the
-    same factor, inverses and solutions BIT FOR BIT: a row tile's sums are made in the same order by whichever workgroup owns it
-    (chol_panel_body), the helpers of k_chol_panel_inv and the k_trtri_* / substitution launches do not depend on G.  U against D is held
-    to the error bars only (potrf64_body<false> and the fused bodies are not claimed to make the same sums)."""
+    """The launch sequence Dev::chol chooses for this configuration (band_panels_ok, the gate of the in-launch inverse panel_inv_grid),
+    everything but the grid G = min(nrt, panel_wgs) of the panel launches.  Configurations with the same selection give the same factor,
+    inverses and solutions BIT FOR BIT: a row tile's sums are made in the same order by whichever workgroup owns it (chol_panel_body), the
+    helpers of k_chol_panel_inv and the k_trtri_* / substitution launches do not depend on G."""
     env = CONFIGS[config]
-    if env.get("ASM_HIP_FUSED_PANEL") == "0":
-        return ("unfused",)
     pw = int(env.get("ASM_PANEL_WGS", PANEL_WGS_D))
     nb, nbi = 64, 512
     if band > 0 and N > nbi + 2 * nb:

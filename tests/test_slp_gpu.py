@@ -415,7 +415,7 @@ def test_scenario_batch_is_independent_of_the_stream_pool():
 def test_device_side_step_of_null_space_iterations_is_bit_identical():
     """The null-space iterations apply their step on the device and are checked with the next measures (one read-back per iteration,
     k_ns_update_dev); ASM_NS_DEFER=0 is the host-side step of the rounds before.  Same arithmetic: the two runs must agree bit for bit
-    (knobs are read once per process, hence two child processes, one after the other)."""
+    (each setting in a child process of its own, one after the other)."""
     import hashlib, os, subprocess, sys
     code = ("import hashlib, numpy as np, activesetmethods_amd as A\n"
             "from activesetmethods_amd import acopf\n"
