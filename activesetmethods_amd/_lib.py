@@ -34,6 +34,11 @@ class SlpResult(C.Structure):
                 ("obj_val", C.c_double), ("prim_infeas", C.c_double), ("dual_infeas", C.c_double), ("compl_", C.c_double)]
 
 
+class SlpTrInfo(C.Structure):
+    """asm_slp_tr_info: final radius; steps with rho >= 0 / < 0; radius decreases / increases."""
+    _fields_ = [("delta", C.c_double), ("accepted", C.c_int32), ("rejected", C.c_int32), ("shrunk", C.c_int32), ("expanded", C.c_int32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
@@ -75,8 +80,10 @@ PROTOTYPES = {
     "asm_slp_merit": (C.c_int, [_P, C.c_int, C.c_double, _D, _D, _D, C.c_int, C.c_double, _D]),
     "asm_slp_line_search": (C.c_int, [_P, _D, _D, _D, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _D, _D,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "asm_slp_step_quality": (C.c_int, [_P, _D, _D, _D, C.c_int, C.c_double, _D]),
     "asm_sublp_set_ns_basis": (C.c_int, [_P, _I32, C.c_int64]),
     "asm_slp_run": (C.c_int, [_P, C.POINTER(SlpParams), _D, _D, _D, _D, _D, _D, C.POINTER(SlpResult)]),
+    "asm_slp_run_tr": (C.c_int, [_P, C.POINTER(SlpParams), C.c_double, _D, _D, _D, _D, _D, _D, C.POINTER(SlpResult), C.POINTER(SlpTrInfo)]),
     "asm_batch_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
     "asm_batch_destroy": (C.c_int, [_P]),
     "asm_batch_last_error": (C.c_char_p, [_P]),
@@ -91,6 +98,8 @@ PROTOTYPES = {
     "asm_batch_ns_basis": (C.c_int, [_P, _I32, _I64]),
     "asm_batch_sublp_solve": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _I32, _D, _D, _D, _D, _D, _I32]),
     "asm_batch_slp_run": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), _D, _D, _D, _D, _D, C.POINTER(SlpResult)]),
+    "asm_batch_slp_run_tr": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), C.c_double, _D, _D, _D, _D, _D, C.POINTER(SlpResult),
+                                       C.POINTER(SlpTrInfo)]),
     "asm_batch_get_stats": (C.c_int, [_P, C.POINTER(BatchStats)]),
     "asm_test_syrk": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, _D, C.c_int]),
     "asm_test_syrk_update": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, C.c_int]),

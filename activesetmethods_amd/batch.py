@@ -87,9 +87,11 @@ def slp_params(par, max_lp_solves=0):
 
 
 class NativeRun:
-    """Outcome of one native SLP run (asm_slp_result + the final iterate): the attributes `local_stats` and the tests read from an SlpLS."""
+    """Outcome of one native SLP run (asm_slp_result + the final iterate): the attributes `local_stats` and the tests read from an SlpLS.
+    Trust Region (`tr`: asm_slp_tr_info) adds the final radius `delta` and the step counts `accepted`, `rejected`, `shrunk`, `expanded`;
+    they are None for Line Search."""
 
-    def __init__(self, res, x, lam, mult_x_U, mult_x_L, g):
+    def __init__(self, res, x, lam, mult_x_U, mult_x_L, g, tr=None):
         self.ret, self.iter, self.lp_solves = int(res.status), int(res.iter), int(res.lp_solves)
         self.restoration_solves, self.ls_trials, self.slot = int(res.restoration_solves), int(res.ls_trials), int(res.slot)
         self.paths = [int(v) for v in res.paths]
@@ -97,6 +99,9 @@ class NativeRun:
         self.obj_val, self.prim_infeas, self.dual_infeas, self.compl = float(res.obj_val), float(res.prim_infeas), float(res.dual_infeas), float(res.compl_)
         self.x, self.lam, self.mult_x_U, self.mult_x_L, self.E = x, lam, mult_x_U, mult_x_L, g
         self.trace = [dict(fr=True)] * self.restoration_solves       # (local_stats counts the restoration solves from the trace)
+        self.delta = float(tr.delta) if tr is not None else None
+        self.accepted, self.rejected, self.shrunk, self.expanded = ((int(tr.accepted), int(tr.rejected), int(tr.shrunk), int(tr.expanded))
+                                                                    if tr is not None else (None, None, None, None))
 
 
 class HipBatch:
@@ -175,20 +180,27 @@ class HipBatch:
         return {k: getattr(s, k) for k, _ in s._fields_}
 
     def slp_run(self, g_L, g_U, x_L, x_U, x0, parameters, max_lp_solves=0):
-        """Complete Line-Search SLP runs of `len(g_L)` scenarios (rows of the 2-D arrays): list of NativeRun in scenario order."""
+        """Complete SLP runs (`parameters.algorithm`: Line Search or Trust Region) of `len(g_L)` scenarios (rows of the 2-D arrays): list of
+        NativeRun in scenario order."""
         from . import _lib
         f64 = lambda a_: np.ascontiguousarray(a_, np.float64)
         g_L, g_U, x_L, x_U, x0 = map(f64, (g_L, g_U, x_L, x_U, x0))
         S = x0.shape[0]
         assert g_L.shape == (S, self.m) and g_U.shape == (S, self.m) and x_L.shape == (S, self.n) and x_U.shape == (S, self.n) and x0.shape == (S, self.n)
-        if parameters.algorithm != "Line Search":
-            raise ValueError("the native driver restates run!(::SlpLS) only")
+        if parameters.algorithm not in ("Line Search", "Trust Region"):
+            raise ValueError("the native drivers restate run!(::SlpLS) and run!(::SlpTR) only, not %r" % parameters.algorithm)
         par = slp_params(parameters, max_lp_solves)
         x = np.empty((S, self.n)); lam = np.empty((S, max(self.m, 1))); mU = np.empty((S, self.n)); mL = np.empty((S, self.n)); g = np.empty((S, max(self.m, 1)))
         res = (_lib.SlpResult * S)()
-        self._check(self._lib.asm_batch_slp_run(self._b, S, _lib.dptr(g_L), _lib.dptr(g_U), _lib.dptr(x_L), _lib.dptr(x_U), _lib.dptr(x0), self._C.byref(par),
-                                                _lib.dptr(x), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(g), res))
-        return [NativeRun(res[s], x[s], lam[s, :self.m], mU[s], mL[s], g[s, :self.m]) for s in range(S)]
+        bounds = (_lib.dptr(g_L), _lib.dptr(g_U), _lib.dptr(x_L), _lib.dptr(x_U), _lib.dptr(x0), self._C.byref(par))
+        outs = (_lib.dptr(x), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(g), res)
+        if parameters.algorithm == "Trust Region":
+            tr = (_lib.SlpTrInfo * S)()
+            self._check(self._lib.asm_batch_slp_run_tr(self._b, S, *bounds, float(parameters.tr_size), *outs, tr))
+        else:
+            tr = [None] * S
+            self._check(self._lib.asm_batch_slp_run(self._b, S, *bounds, *outs))
+        return [NativeRun(res[s], x[s], lam[s, :self.m], mU[s], mL[s], g[s, :self.m], tr[s]) for s in range(S)]
 
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.

@@ -226,16 +226,12 @@ __global__ __launch_bounds__(1024) void k_slp_norms(AsmBt abt, SlpVecs V, double
 // alpha = 0), ps = p_slack as 2 entries per row (second NaN when the row has one slack).
 //   mode 0 (phi):        normal  f_trial + nu . viol(Et)                restoration  prim_infeas + alpha * sum(slacks) + nu . viol(lhs)
 //   mode 1 (derivative): normal  df . p - nu . viol(E)                  restoration  sum(slacks) - nu . viol(E - viol(E))
-__global__ __launch_bounds__(1024) void k_slp_merit(AsmBt abt, SlpVecs V, const double* __restrict__ Et, const double* __restrict__ nu, const double* __restrict__ ps, const double* __restrict__ p, double alpha, int feasibility, double prim_infeas, const double* __restrict__ f_trial, int mode, double* __restrict__ out, TrialAlphas al, int64_t ldE) {
-    ASM_BARGS(abt, V, Et, nu, ps, p, alpha, feasibility, prim_infeas, f_trial, mode, out, al, ldE);
-    __shared__ double sh[16];
+// One workgroup's merit value (valid on thread 0): the body of k_slp_merit and of k_slp_tr_quality, so that both kernels make the same
+// instructions in the same reduction order.
+__device__ __forceinline__ double slp_merit_wg(const SlpVecs& V, const double* __restrict__ Et, const double* __restrict__ nu, const double* __restrict__ ps,
+                                               const double* __restrict__ p, double alpha, int feasibility, double prim_infeas,
+                                               const double* __restrict__ f_trial, int mode, double* sh) {
     double pen = 0.0, ssum = 0.0, dfp = 0.0;
-    if (gridDim.x > 1) {              // batched line search: one workgroup per trial point
-        alpha = al.a[blockIdx.x];
-        Et += blockIdx.x * ldE;
-        f_trial += blockIdx.x;
-        out += blockIdx.x;
-    }
     for (int64_t i = threadIdx.x; i < V.m; i += 1024) {
         const double lo = V.g_L[i], up = V.g_U[i], e = V.E[i];
         const double viol = fmax(0.0, fmax(e - up, lo - e));
@@ -255,8 +251,30 @@ __global__ __launch_bounds__(1024) void k_slp_merit(AsmBt abt, SlpVecs V, const 
     pen = blk_reduce_sum(pen, sh);
     ssum = blk_reduce_sum(ssum, sh);
     dfp = blk_reduce_sum(dfp, sh);
-    if (threadIdx.x == 0) {
-        if (mode == 0) out[0] = feasibility ? prim_infeas + alpha * ssum + pen : f_trial[0] + pen;
-        else out[0] = feasibility ? ssum - pen : dfp - pen;
+    if (mode == 0) return feasibility ? prim_infeas + alpha * ssum + pen : f_trial[0] + pen;
+    return feasibility ? ssum - pen : dfp - pen;
+}
+__global__ __launch_bounds__(1024) void k_slp_merit(AsmBt abt, SlpVecs V, const double* __restrict__ Et, const double* __restrict__ nu, const double* __restrict__ ps, const double* __restrict__ p, double alpha, int feasibility, double prim_infeas, const double* __restrict__ f_trial, int mode, double* __restrict__ out, TrialAlphas al, int64_t ldE) {
+    ASM_BARGS(abt, V, Et, nu, ps, p, alpha, feasibility, prim_infeas, f_trial, mode, out, al, ldE);
+    __shared__ double sh[16];
+    if (gridDim.x > 1) {              // batched line search: one workgroup per trial point
+        alpha = al.a[blockIdx.x];
+        Et += blockIdx.x * ldE;
+        f_trial += blockIdx.x;
+        out += blockIdx.x;
     }
+    const double v = slp_merit_wg(V, Et, nu, ps, p, alpha, feasibility, prim_infeas, f_trial, mode, sh);
+    if (threadIdx.x == 0) out[0] = v;
+}
+// step_quality's three merit quantities (slp_trust_region.jl:213-216) in one launch of 3 workgroups, workgroup b = out[b]:
+//   b = 0  compute_derivative            (mode 1, at E)
+//   b = 1  compute_phi(x, 0, p)          (mode 0, alpha 0, at E and f)
+//   b = 2  compute_phi(x, 1, p)          (mode 0, alpha 1, at the trial values Et and f_trial)
+// each the value one asm_slp_merit call returns, bit for bit (same body, same reduction order).
+__global__ __launch_bounds__(1024) void k_slp_tr_quality(AsmBt abt, SlpVecs V, const double* __restrict__ Et, const double* __restrict__ nu, const double* __restrict__ ps, const double* __restrict__ p, int feasibility, double prim_infeas, const double* __restrict__ f, const double* __restrict__ f_trial, double* __restrict__ out) {
+    ASM_BARGS(abt, V, Et, nu, ps, p, feasibility, prim_infeas, f, f_trial, out);
+    __shared__ double sh[16];
+    const int b = blockIdx.x;
+    const double v = slp_merit_wg(V, b == 2 ? Et : V.E, nu, ps, p, b == 2 ? 1.0 : 0.0, feasibility, prim_infeas, b == 2 ? f_trial : f, b == 0 ? 1 : 0, sh);
+    if (threadIdx.x == 0) out[b] = v;
 }

@@ -3850,6 +3850,36 @@ static void slp_merit_and_search(asm_handle* h, const double* p, const double* n
     *phi0_out = phi0; *D_out = D; *trials_out = trials;
 }
 
+// step_quality's merit values (slp_trust_region.jl:213-216): out3 = { compute_derivative, compute_phi(x, 0, p), compute_phi(x, 1, p) } with one
+// upload of nu | slacks | p, the trial point x + p evaluated on the device and one read-back (three asm_slp_merit calls: three uploads, three read-backs).  The
+// same launches per quantity as asm_slp_merit makes (k_axpy_out + ev_launch at alpha = 1, the merit body of k_slp_merit): same values.
+static void slp_tr_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
+    const int64_t n = h->n, m = h->m;
+    double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
+    double *nud = v, *psd = v + m, *pd = psd + 2 * m, *outd = pd + n + h->ldn + h->Mp;
+    double* st = h->h_ev;
+    if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
+    std::memcpy(st + 3 * m, p, n * sizeof(double));
+    HIPCHK(hipMemcpyAsync(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_axpy_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->d_ev_x, 1.0, (const double*)pd, h->d_ev_xt, n);
+    ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
+    hipLaunchKernelGGL(k_slp_tr_quality, dim3(3), dim3(1024), 0, h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), (const double*)h->d_ev_Et,
+                       (const double*)nud, (const double*)psd, (const double*)pd, feasibility, prim_infeas, (const double*)h->d_ev_f,
+                       (const double*)(h->d_ev_f + 1), outd);
+    HIPCHK(hipMemcpyAsync(st, outd, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 3; ++k) out3[k] = st[k];
+}
+
+int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
+    return guarded(h, [&] {
+        if (!h->ev_ready || !h->inputs_ready || !p || !out3 || (h->m > 0 && (!nu || !p_slack)))
+            throw std::logic_error("asm_slp_step_quality: asm_eval_functions first / bad argument");
+        HIPCHK(hipSetDevice(h->device));
+        slp_tr_step_quality(h, p, nu, p_slack, feasibility, prim_infeas, out3);
+    });
+}
+
 // --------------------------------------------------------------------------------- kernel test hooks
 static void test_alloc(asm_handle* h, int64_t M, int64_t K) {
     // minimal "problem" so that the generic buffers exist: dense pattern M x K
@@ -4215,6 +4245,167 @@ void slp_run_ls(asm_handle* h, const asm_slp_params* par, const double* x0, doub
     if (g_out && h->m) std::memcpy(g_out, r.E.data(), h->m * sizeof(double));
 }
 
+// run!(::SlpTR), slp_trust_region.jl:87-251 - statement by statement the library calls of SlpTR.run in activesetmethods_amd/slp.py with
+// Parameters(device_eval=True).  One difference from the host driver: compute_nu's ||df||_2 is summed here in index order, NumPy's norm
+// may round it differently in the last bit.  It only enters nu at iter 1 and through nu only the merit values and rho: iterates,
+// multipliers, radius and counts stay bit-identical unless rho falls within an ulp of 0, 0.25 or 0.75.  The same holds for the 1-norm of
+// the violations in the status-OTHER branch (device evaluator instead of the host's eval_g, a plain sum), which only decides ret 6 / -5.
+struct SlpRunTR {
+    asm_handle* h;
+    const asm_slp_params& o;
+    int64_t n, m;
+    vec x, p, lam, mU, mL, ps, df, E, nu, rn;
+    double f = 0.0, phi = INF, prim_infeas = INF, dual_infeas = INF, compl_ = INF;
+    double Delta, Delta_max = 2.0, alpha1 = 0.1, alpha2 = 0.25;     // slp_trust_region.jl:62-65
+    bool fr = false;
+    int iter = 1, ret = -5, lp_solves = 0, fr_solves = 0;
+    asm_slp_result* res;
+    asm_slp_tr_info info{};
+
+    SlpRunTR(asm_handle* hh, const asm_slp_params& par, double tr_size, asm_slp_result* r)
+        : h(hh), o(par), n(hh->n), m(hh->m), Delta(tr_size), res(r) {
+        x.assign(n, 0.0); p.assign(n, 0.0); lam.assign(m, 0.0); mU.assign(n, 0.0); mL.assign(n, 0.0);
+        ps.assign(2 * std::max<int64_t>(m, 1), 0.0); df.assign(n, 0.0); E.assign(std::max<int64_t>(m, 1), 0.0); nu.assign(m, 0.0);
+        rn.assign(std::max<int64_t>(m, 1), 0.0);
+    }
+    void chk(int rc, const char* what) {
+        if (rc != ASM_OK) throw HipError(std::string(what) + ": " + h->err);
+    }
+    bool feasible_enough() const { return prim_infeas <= o.tol_infeas; }
+    double finite_or_zero(double v) const { return std::isfinite(v) ? v : 0.0; }
+
+    // slp.jl:54-66 (the base compute_nu!, not the Line-Search one)
+    void compute_nu() {
+        if (iter == 1) {
+            double norm_df = 1.0;
+            if (!fr) {
+                double s = 0.0;
+                for (int64_t j = 0; j < n; ++j) s += df[j] * df[j];
+                norm_df = std::sqrt(s);
+            }
+            chk(asm_jac_row_norms(h, rn.data()), "asm_jac_row_norms");
+            for (int64_t i = 0; i < m; ++i) nu[i] = std::max(1.0, norm_df / std::max(1.0, rn[i]));
+        } else {
+            for (int64_t i = 0; i < m; ++i) nu[i] = std::max(nu[i], std::fabs(lam[i]));
+        }
+    }
+
+    // step_quality (slp_trust_region.jl:213-251) as SlpTR.step_quality: the three merit values from one launch, the rest on the host
+    double step_quality() {
+        double q[3];
+        chk(guarded(h, [&] { slp_tr_step_quality(h, p.data(), nu.data(), ps.data(), fr ? 1 : 0, finite_or_zero(prim_infeas), q); }), "slp_tr_step_quality");
+        phi = q[2] - q[1];
+        const double phi_pre = q[0];
+        if (std::fabs(phi_pre) > 0.0) {
+            const double rho = phi / phi_pre, D0 = Delta;
+            if (rho <= 0) Delta *= alpha1;
+            else if (rho <= 0.25) Delta *= alpha2;
+            else if (rho > 0.75) Delta = std::min(2 * Delta, Delta_max);
+            if (Delta < D0) info.shrunk += 1;
+            else if (Delta > D0) info.expanded += 1;
+            return rho;
+        }
+        const double rho = -phi;
+        if (std::fabs(phi) < 1.e-8) {
+            if (fr) fr = false;
+            else if (feasible_enough()) ret = (dual_infeas <= o.tol_residual && compl_ <= o.tol_residual) ? 0 : 6;
+            else ret = 2;
+        }
+        return rho;
+    }
+
+    void run(const double* x0) {
+        // slp_trust_region.jl:104-114 (the clamp tests x_U > -Inf, sic)
+        for (int64_t j = 0; j < n; ++j) {
+            double v = x0[j];
+            if (h->v_lb[j] > -INF) v = std::max(v, h->v_lb[j]);
+            if (h->v_ub[j] > -INF) v = std::min(v, h->v_ub[j]);
+            x[j] = v;
+        }
+        iter = 1;
+        while (true) {
+            if (o.max_lp_solves > 0 && lp_solves >= o.max_lp_solves) break;
+            asmb::next_cycle();
+            asmb::barrier(11);
+            chk(asm_eval_functions(h, x.data(), &f, df.data(), E.data()), "asm_eval_functions");      // :120
+            int32_t status = 0;
+            chk(asm_sublp_solve_resident(h, Delta, fr ? 1 : 0, p.data(), lam.data(), mU.data(), mL.data(), ps.data(), &status), "asm_sublp_solve_resident");
+            lp_solves += 1;
+            if (fr) fr_solves += 1;
+            if (res) {
+                const int pth = h->stats.path;
+                if (pth >= 0 && pth < 12) res->paths[pth] += 1;
+                res->ipm_iters += h->stats.ipm_iters;
+                res->ns_cold += h->stats.ns_cold;
+            }
+            if (status != ASM_OPTIMAL && status != ASM_INFEASIBLE) {                                     // :130-136 (`slp.ret == -3`: a comparison, sic)
+                double fc = 0.0, v1 = 0.0;
+                vec Ec(std::max<int64_t>(m, 1));
+                chk(asm_eval_constraints(h, x.data(), &fc, Ec.data()), "asm_eval_constraints");
+                for (int64_t i = 0; i < m; ++i) v1 += std::max(0.0, std::max(Ec[i] - h->c_ub[i], h->c_lb[i] - Ec[i]));
+                for (int64_t j = 0; j < n; ++j) v1 += std::max(0.0, std::max(x[j] - h->v_ub[j], h->v_lb[j] - x[j]));
+                if (v1 <= o.tol_infeas) ret = 6;
+                break;
+            }
+            if (status == ASM_INFEASIBLE) {                                                              // :137-150
+                if (fr) { ret = feasible_enough() ? 6 : 2; break; }
+                fr = true;
+                continue;
+            }
+            asmb::barrier(930);
+            compute_nu();                                                                                 // :152
+            double nrm[4];
+            chk(asm_slp_norms(h, lam.data(), mU.data(), mL.data(), nrm), "asm_slp_norms");             // :154-156, this LP's multipliers
+            prim_infeas = nrm[0]; dual_infeas = nrm[2]; compl_ = nrm[3];
+            double pmax = 0.0;
+            for (int64_t j = 0; j < n; ++j) pmax = std::max(pmax, std::fabs(p[j]));
+            if (feasible_enough() && compl_ <= o.tol_residual && pmax <= o.tol_direction) {               // :163-175
+                if (fr) { fr = false; iter += 1; continue; }
+                if (dual_infeas <= o.tol_residual) { ret = 0; break; }
+            }
+            if (iter >= o.max_iter) { ret = feasible_enough() ? 6 : -1; break; }                         // :178-184
+            asmb::barrier(940);
+            const double rho = step_quality();                                                            // :187-196
+            if (ret == 0 || ret == 2 || ret == 6) break;
+            if (rho >= 0) {
+                for (int64_t j = 0; j < n; ++j) x[j] = x[j] + p[j];
+                info.accepted += 1;
+            } else {
+                info.rejected += 1;
+            }
+            iter += 1;
+        }
+        // :198: objective at the final point
+        double f_end = 0.0;
+        vec Et(std::max<int64_t>(m, 1));
+        asmb::barrier(995);
+        chk(asm_eval_constraints(h, x.data(), &f_end, Et.data()), "asm_eval_constraints");
+        info.delta = Delta;
+        if (res) {
+            res->status = ret; res->iter = iter; res->lp_solves = lp_solves; res->restoration_solves = fr_solves; res->ls_trials = 0;
+            res->obj_val = f_end; res->prim_infeas = prim_infeas; res->dual_infeas = dual_infeas; res->compl_ = compl_;
+        }
+    }
+};
+
+void check_tr_size(double tr_size, const char* what) {
+    if (!std::isfinite(tr_size) || !(tr_size > 0.0)) throw std::invalid_argument(std::string(what) + ": tr_size must be finite and > 0");
+}
+
+void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const double* x0, double* x_out, double* lambda, double* mult_x_U, double* mult_x_L,
+                double* g_out, asm_slp_result* res, asm_slp_tr_info* tr) {
+    if (!h->ev_ready) throw std::logic_error("asm_slp_run_tr: asm_eval_setup first (the native driver evaluates on the device)");
+    if (res) std::memset(res, 0, sizeof(*res));
+    SlpRunTR r(h, *par, tr_size, res);
+    r.run(x0);
+    if (x_out) std::memcpy(x_out, r.x.data(), h->n * sizeof(double));
+    if (lambda && h->m) std::memcpy(lambda, r.lam.data(), h->m * sizeof(double));
+    if (mult_x_U) std::memcpy(mult_x_U, r.mU.data(), h->n * sizeof(double));
+    if (mult_x_L) std::memcpy(mult_x_L, r.mL.data(), h->n * sizeof(double));
+    if (g_out && h->m) std::memcpy(g_out, r.E.data(), h->m * sizeof(double));
+    if (tr) *tr = r.info;
+}
+
 }  // namespace
 
 // A batch is split into groups: each group = a contiguous range of slots, one stream, one scheduler, one host thread (group 0 runs on the
@@ -4335,6 +4526,15 @@ int asm_slp_run(asm_handle* h, const asm_slp_params* par, const double* x0, doub
     });
 }
 
+int asm_slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const double* x0, double* x, double* lambda, double* mult_x_U, double* mult_x_L,
+                   double* g, asm_slp_result* res, asm_slp_tr_info* tr) {
+    return guarded(h, [&] {
+        if (!par || !x0) throw std::invalid_argument("asm_slp_run_tr: null pointer");
+        check_tr_size(tr_size, "asm_slp_run_tr");
+        slp_run_tr(h, par, tr_size, x0, x, lambda, mult_x_U, mult_x_L, g, res, tr);
+    });
+}
+
 int asm_batch_create(int device, int n_slots, asm_batch** out) {
     if (!out || n_slots < 1 || n_slots > 4096) return ASM_ERR_ARG;
     *out = nullptr;
@@ -4450,48 +4650,81 @@ int asm_batch_sublp_solve(asm_batch* b, int count, const double* c_lb, const dou
     });
 }
 
-// n_scen complete SLP runs (Line Search): the slots' fibers take the scenarios in index order; every array has a leading scenario dimension
+}  // extern "C"
+
+namespace {
+// n_scen complete SLP runs of one algorithm: the slots' fibers take the scenarios in index order; every array has a leading scenario dimension.
+// run_one(h, sc) solves scenario sc on handle h (bounds and basis columns already set).
+template <class RunOne>
+void batch_slp_runs(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
+                    const double* x0, asm_slp_result* res, RunOne&& run_one) {
+    const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+    HIPCHK(hipSetDevice(b->device));
+    if (b->J_ref.empty()) {
+        // reference selection of the null-space basis columns: one LP of scenario 0 at its start point on slot 0 (cold selection); EVERY
+        // scenario, 0 included, then starts from these columns - the results do not depend on the slot or on what it solved before
+        asm_handle* h0 = b->slots[0];
+        bcheck(b, 0, asm_sublp_set_bounds(h0, c_lb, c_ub, v_lb, v_ub), "asm_sublp_set_bounds");
+        h0->hint[0].ns_J.clear();
+        vec xs(n), dfs(n), Es(std::max<int64_t>(m, 1)), pp(n), ll(std::max<int64_t>(m, 1)), uu(n), lo(n), sl(2 * std::max<int64_t>(m, 1));
+        for (int64_t j = 0; j < n; ++j) {
+            double v = x0[j];
+            if (v_lb[j] > -INF) v = std::max(v, v_lb[j]);
+            if (v_ub[j] > -INF) v = std::min(v, v_ub[j]);
+            xs[j] = v;
+        }
+        double f0 = 0.0;
+        int32_t st0 = 0;
+        bcheck(b, 0, asm_eval_functions(h0, xs.data(), &f0, dfs.data(), Es.data()), "asm_eval_functions");
+        bcheck(b, 0, asm_sublp_solve_resident(h0, 1000.0, 0, pp.data(), ll.data(), uu.data(), lo.data(), sl.data(), &st0), "asm_sublp_solve_resident");
+        b->J_ref = h0->hint[0].ns_J;
+    }
+    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
+    std::atomic<int64_t> next{0};
+    run_fibers(b, count, [&](int s) {
+        asm_handle* h = b->slots[s];
+        for (;;) {
+            const int64_t sc = next.fetch_add(1);
+            if (sc >= n_scen) break;
+            bcheck(b, s, asm_sublp_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n), "asm_sublp_set_bounds");
+            // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
+            if (!b->J_ref.empty()) h->hint[0].ns_J = b->J_ref;
+            else h->hint[0].ns_J.clear();
+            run_one(h, sc);
+            res[sc].slot = s;
+        }
+    });
+}
+}  // namespace
+
+extern "C" {
+
+// n_scen complete SLP runs (Line Search)
 int asm_batch_slp_run(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* x0,
                       const asm_slp_params* par, double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res) {
     return bguarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_slp_run: asm_batch_setup first");
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run: bad argument");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
-        HIPCHK(hipSetDevice(b->device));
-        if (b->J_ref.empty()) {
-            // reference selection of the null-space basis columns: one LP of scenario 0 at its start point on slot 0 (cold selection); EVERY
-            // scenario, 0 included, then starts from these columns - the results do not depend on the slot or on what it solved before
-            asm_handle* h0 = b->slots[0];
-            bcheck(b, 0, asm_sublp_set_bounds(h0, c_lb, c_ub, v_lb, v_ub), "asm_sublp_set_bounds");
-            h0->hint[0].ns_J.clear();
-            vec xs(n), dfs(n), Es(std::max<int64_t>(m, 1)), pp(n), ll(std::max<int64_t>(m, 1)), uu(n), lo(n), sl(2 * std::max<int64_t>(m, 1));
-            for (int64_t j = 0; j < n; ++j) {
-                double v = x0[j];
-                if (v_lb[j] > -INF) v = std::max(v, v_lb[j]);
-                if (v_ub[j] > -INF) v = std::min(v, v_ub[j]);
-                xs[j] = v;
-            }
-            double f0 = 0.0;
-            int32_t st0 = 0;
-            bcheck(b, 0, asm_eval_functions(h0, xs.data(), &f0, dfs.data(), Es.data()), "asm_eval_functions");
-            bcheck(b, 0, asm_sublp_solve_resident(h0, 1000.0, 0, pp.data(), ll.data(), uu.data(), lo.data(), sl.data(), &st0), "asm_sublp_solve_resident");
-            b->J_ref = h0->hint[0].ns_J;
-        }
-        const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
-        std::atomic<int64_t> next{0};
-        run_fibers(b, count, [&](int s) {
-            asm_handle* h = b->slots[s];
-            for (;;) {
-                const int64_t sc = next.fetch_add(1);
-                if (sc >= n_scen) break;
-                bcheck(b, s, asm_sublp_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n), "asm_sublp_set_bounds");
-                // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
-                if (!b->J_ref.empty()) h->hint[0].ns_J = b->J_ref;
-                else h->hint[0].ns_J.clear();
-                slp_run_ls(h, par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
-                           mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc);
-                res[sc].slot = s;
-            }
+        batch_slp_runs(b, n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
+            slp_run_ls(h, par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
+                       mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc);
+        });
+    });
+}
+
+// n_scen complete SLP runs (Trust Region)
+int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* x0,
+                         const asm_slp_params* par, double tr_size, double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g,
+                         asm_slp_result* res, asm_slp_tr_info* tr) {
+    return bguarded(b, [&] {
+        if (!b->setup_done) throw std::logic_error("asm_batch_slp_run_tr: asm_batch_setup first");
+        if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run_tr: bad argument");
+        check_tr_size(tr_size, "asm_batch_slp_run_tr");
+        const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+        batch_slp_runs(b, n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
+            slp_run_tr(h, par, tr_size, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
+                       mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc, tr ? tr + sc : nullptr);
         });
     });
 }

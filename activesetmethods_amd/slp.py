@@ -395,11 +395,16 @@ class SlpTR(AbstractSlpOptimizer):
         self._finish()
 
 
-def optimize(model, max_lp_solves=None):
-    """src/model.jl:63-80 (an unset `external_optimizer` selects the HIP sub-optimizer instead of status -12)."""
+def optimize(model, max_lp_solves=None, native=False):
+    """src/model.jl:63-80 (an unset `external_optimizer` selects the HIP sub-optimizer instead of status -12).
+
+    native=True: the whole run inside the library (asm_slp_run / asm_slp_run_tr by `parameters.algorithm`) on a fresh handle; needs
+    `device_eval=True` and a model built from a FunctionModel.  The model is filled as the host drivers fill it; returns the NativeRun."""
     par = model.parameters
     if par.method != "SLP":
         raise ValueError("The method is not defined")
+    if native:
+        return _optimize_native(model, max_lp_solves)
     if par.algorithm == "Line Search":
         slp = SlpLS(model)
     elif par.algorithm == "Trust Region":
@@ -408,3 +413,25 @@ def optimize(model, max_lp_solves=None):
         raise ValueError("unknown algorithm %r" % par.algorithm)
     slp.run(max_lp_solves)
     return slp
+
+
+def _optimize_native(model, max_lp_solves=None):
+    par = model.parameters
+    fm = getattr(model, "function_model", None)
+    if not getattr(par, "device_eval", False) or fm is None:
+        raise ValueError("optimize(native=True) needs Parameters(device_eval=True) and a model built from a FunctionModel")
+    if par.algorithm not in ("Line Search", "Trust Region"):
+        raise ValueError("unknown algorithm %r" % par.algorithm)
+    opt = HipSubOptimizer(QpData(np.zeros(model.n), 0.0, np.zeros(len(model.j_row)), np.zeros(model.m), model.g_L, model.g_U, model.x_L, model.x_U),
+                          model.j_row, model.j_col)
+    try:
+        opt.eval_setup(fm)
+        run = opt.slp_run(model.x, par, max_lp_solves or 0)
+    finally:
+        opt.close()
+    model.obj_val = run.obj_val                                   # as _finish fills it
+    model.status = int(run.ret)
+    model.x[:] = run.x; model.g[:] = run.E; model.mult_g[:] = run.lam
+    model.mult_x_U[:] = run.mult_x_U; model.mult_x_L[:] = run.mult_x_L
+    model.statistics.update(iter=run.iter, lp_solves=run.lp_solves)
+    return run

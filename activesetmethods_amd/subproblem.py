@@ -277,6 +277,35 @@ class HipSubOptimizer:
                                                   float(min_alpha), C.byref(alpha), C.byref(phi), C.byref(trials), C.byref(ok)))
         return alpha.value, phi.value, trials.value, bool(ok.value)
 
+    def step_quality(self, p, nu, p_slack, feasibility, prim_infeas):
+        """step_quality's merit values (slp_trust_region.jl:213-216) with x + p evaluated on the device (asm_slp_step_quality):
+        (compute_derivative, compute_phi(x, 0, p), compute_phi(x, 1, p)), each equal to the slp_merit call's value."""
+        ps = self._flat_slacks(p_slack)
+        p, nu = _f64(p), _f64(nu)
+        out = np.empty(3)
+        self._check(self._lib.asm_slp_step_quality(self._h, _lib.dptr(p), _lib.dptr(nu), _lib.dptr(ps), int(bool(feasibility)),
+                                                   float(prim_infeas) if np.isfinite(prim_infeas) else 0.0, _lib.dptr(out)))
+        return tuple(float(v) for v in out)
+
+    def slp_run(self, x0, parameters, max_lp_solves=0):
+        """One complete SLP run inside the library (asm_slp_run for Line Search, asm_slp_run_tr for Trust Region, by
+        `parameters.algorithm`) from x0 on this handle; needs eval_setup.  Returns a batch.NativeRun."""
+        from .batch import NativeRun, slp_params
+        if parameters.algorithm not in ("Line Search", "Trust Region"):
+            raise ValueError("the native drivers restate run!(::SlpLS) and run!(::SlpTR) only, not %r" % parameters.algorithm)
+        par = slp_params(parameters, max_lp_solves)
+        x0 = _f64(x0)
+        x = np.empty(self.n); lam = np.empty(max(self.m, 1)); mU = np.empty(self.n); mL = np.empty(self.n); g = np.empty(max(self.m, 1))
+        res = _lib.SlpResult()
+        outs = (_lib.dptr(x), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(g), C.byref(res))
+        tr = None
+        if parameters.algorithm == "Trust Region":
+            tr = _lib.SlpTrInfo()
+            self._check(self._lib.asm_slp_run_tr(self._h, C.byref(par), float(parameters.tr_size), _lib.dptr(x0), *outs, C.byref(tr)))
+        else:
+            self._check(self._lib.asm_slp_run(self._h, C.byref(par), _lib.dptr(x0), *outs))
+        return NativeRun(res, x, lam[:self.m], mU, mL, g[:self.m], tr)
+
     # per-iteration reductions on the resident Jacobian (common.jl:35-44, slp.jl:54-66)
     def kt_residuals(self, df, lam, mult_x_U, mult_x_L):
         out = C.c_double(0.0)

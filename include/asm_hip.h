@@ -200,6 +200,9 @@ int asm_slp_merit(asm_handle* h, int mode, double alpha, const double* p, const 
  * *ok = 0: alpha fell below min_alpha with the test still failing (*alpha is that last trial, as the reference leaves it). */
 int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double phi0,
                         double D, double eta, double tau, double min_alpha, double* alpha, double* phi_alpha, int* trials, int* ok);
+/* step_quality's merit values (slp_trust_region.jl:213-216): out3 = { compute_derivative, compute_phi(x, 0, p), compute_phi(x, 1, p) }
+ * with x+p evaluated on the device; equal bit for bit to three asm_slp_merit calls.  Needs asm_eval_functions. */
+int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3);
 
 /* Seed the retained basis columns of the null-space form (0-based; what asm_sublp_ns_basis returns): the next normal-phase LP builds its
  * basis from them instead of selecting columns from scratch.  asm_sublp_set_bounds keeps the columns (same pattern), drops the basis. */
@@ -224,6 +227,19 @@ typedef struct {
  * Needs asm_sublp_setup + asm_eval_setup on the handle. */
 int asm_slp_run(asm_handle* h, const asm_slp_params* par, const double* x0, double* x, double* lambda, double* mult_x_U, double* mult_x_L,
                 double* g, asm_slp_result* res);
+
+/* ---- native SLP caller: run!(::SlpTR) (slp_trust_region.jl:87-251), the same library calls as the host driver (SlpTR.run with
+ * device_eval): asm_eval_functions, asm_sublp_solve_resident at the radius, asm_jac_row_norms (first iteration), asm_slp_norms,
+ * asm_slp_step_quality.  res is filled as asm_slp_run fills it (ls_trials = 0).  tr_size: the initial radius (parameters.jl: tr_size),
+ * finite and > 0 (else ASM_ERR_ARG). */
+typedef struct {
+    double  delta;             /* final trust-region radius */
+    int32_t accepted;          /* steps with rho >= 0 (x moved) */
+    int32_t rejected;          /* steps with rho < 0 (x kept) */
+    int32_t shrunk, expanded;  /* radius decreases / increases */
+} asm_slp_tr_info;
+int asm_slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const double* x0, double* x, double* lambda,
+                   double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res, asm_slp_tr_info* tr /* may be NULL */);
 
 /* ---- scenario batches: B sub-problems with the same pattern advance through ONE launch sequence on ONE stream --------------------------
  * The reference has no batching (one Optimizer <-> one Model <-> one SLP object, src/MOI_wrapper.jl:1093-1152); these entries are
@@ -267,6 +283,11 @@ int asm_batch_sublp_solve(asm_batch* b, int count, const double* c_lb, const dou
 int asm_batch_slp_run(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
                       const double* x0, const asm_slp_params* par,
                       double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res);
+/* the same with asm_slp_run_tr per scenario (same reference basis-column selection); tr [n_scen] may be NULL */
+int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
+                         const double* x0, const asm_slp_params* par, double tr_size,
+                         double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res,
+                         asm_slp_tr_info* tr);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
