@@ -318,12 +318,16 @@ class AcopfModel:
         return v
 
 
-def function_model(case):
+def function_model(case, nlp="acopf_ohm"):
     """The same polar ACOPF as a FunctionModel (moi_evaluator.py), i.e. the way the reference receives it: affine and quadratic
     scalar functions in the wrapper's six lists (angle differences linear <= / >=; reference angle, dc-line loss and the nodal
     balances of buses without shunt linear ==; thermal limits quadratic <=; balances of buses with a shunt quadratic ==) and
     Ohm's law as the NLP block (src/MOI_wrapper.jl:683-689).  Rows and pattern come out in the wrapper's order, which is a
-    permutation of `AcopfModel`'s; the NLP block carries the parameters of its device kernel (csrc/asm_eval_kernels.hip.h)."""
+    permutation of `AcopfModel`'s; the NLP block carries the parameters of its device kernel (csrc/asm_eval_kernels.hip.h).
+    nlp="acopf_ohm": the hand-written Ohm's-law kernel; nlp="expr": the same rows as expressions (nlexpr.ExprBlock) - each row's
+    pattern is then its distinct variables in ascending order, the same entries as the kernel's in another order."""
+    if nlp not in ("acopf_ohm", "expr"):
+        raise ValueError("nlp must be 'acopf_ohm' or 'expr', not %r" % (nlp,))
     from .moi_evaluator import FunctionModel, ScalarFunction, NlpBlock
     mdl = AcopfModel(case)
     c = case
@@ -361,8 +365,12 @@ def function_model(case):
             fm.add_constraint(ScalarFunction(0.0, aff, quad), "eq", rhs[b])
     fm.objective = ScalarFunction(float(np.sum(c["cost0"])), [(float(c["cost1"][g]), V(mdl.pg[g])) for g in range(mdl.ng)],
                                   [(2.0 * float(c["cost2"][g]), V(mdl.pg[g]), V(mdl.pg[g])) for g in range(mdl.ng) if c["cost2"][g] != 0.0])
-    # ---- NLP block: Ohm's law, rows pfr | qfr | pto | qto, pattern in 4 groups x 5 sub-blocks of n_branch
     nl = mdl.nl
+    fm.acopf_model = mdl
+    if nlp == "expr":
+        fm.nlp = _ohm_expr_block(mdl)
+        return fm
+    # ---- NLP block: Ohm's law, rows pfr | qfr | pto | qto, pattern in 4 groups x 5 sub-blocks of n_branch
     rows, cols = [], []
     for g, pv in enumerate((mdl.pf, mdl.qf, mdl.pt, mdl.qt)):
         r = np.arange(g * nl, (g + 1) * nl) + 1
@@ -385,8 +393,27 @@ def function_model(case):
     dpar = np.concatenate([mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q, mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t]).astype(np.float64)
     fm.nlp = NlpBlock(np.zeros(4 * nl), np.zeros(4 * nl), np.concatenate(rows), np.concatenate(cols), eval_g, eval_jac_g,
                       device=("acopf_ohm", ipar, dpar))
-    fm.acopf_model = mdl
     return fm
+
+
+def _ohm_expr_block(mdl):
+    """Ohm's law (rows pfr | qfr | pto | qto, `AcopfModel._flows`) as expressions: x[p / q flow] - flow(vm_f, vm_t, va_f - va_t)."""
+    from .nlexpr import ExprBlock, var, sin, cos
+    c = mdl.c
+    f, t = c["f_bus"], c["t_bus"]
+    rows = [[], [], [], []]
+    for l in range(mdl.nl):
+        vf, vt = var(mdl.vm[f[l]]), var(mdl.vm[t[l]])
+        d = var(mdl.va[f[l]]) - var(mdl.va[t[l]])
+        cs, sn = cos(d), sin(d)
+        vv = vf * vt
+        kffp, kffq, kttp, kttq = (float(a[l]) for a in (mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q))
+        af, bf, at, bt = (float(a[l]) for a in (mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t))
+        rows[0].append(var(mdl.pf[l]) - (kffp * vf * vf + af * vv * cs + bf * vv * sn))
+        rows[1].append(var(mdl.qf[l]) - (kffq * vf * vf - bf * vv * cs + af * vv * sn))
+        rows[2].append(var(mdl.pt[l]) - (kttp * vt * vt + at * vv * cs - bt * vv * sn))
+        rows[3].append(var(mdl.qt[l]) - (kttq * vt * vt - bt * vv * cs - at * vv * sn))
+    return ExprBlock([(e, 0.0, 0.0) for grp in rows for e in grp], n=mdl.n)
 
 
 def acopf_problem(case, name="acopf"):

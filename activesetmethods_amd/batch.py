@@ -113,6 +113,7 @@ class HipBatch:
         import ctypes as C
         from . import _lib
         from .subproblem import AsmHipError
+        from .moi_evaluator import nlp_kind
         self._lib, self._C, self._err = _lib.load(), C, AsmHipError
         fm = getattr(problem, "function_model", None)
         if fm is None:
@@ -134,8 +135,8 @@ class HipBatch:
         kind, rows, nnz = 0, 0, 0
         ipar, dpar = np.zeros(1, np.int64), np.zeros(1)
         if fm.nlp is not None:
-            name, ipar, dpar = fm.nlp.device
-            kind = {"acopf_ohm": 1, "dense_quadratic": 2}[name]
+            kind = nlp_kind(fm.nlp.device)
+            _, ipar, dpar = fm.nlp.device
             rows, nnz = fm.nlp.m, len(fm.nlp.rows)
             ipar, dpar = np.ascontiguousarray(ipar, np.int64), np.ascontiguousarray(dpar, np.float64)
         a = lambda k: fl[k]

@@ -4,13 +4,16 @@
 //     so that values, gradient and Jacobian entries are BIT-IDENTICAL to the host restatement
 //     (activesetmethods_amd/moi_evaluator.py);
 //   * two NLP-block kernels: Ohm's-law rows of the polar ACOPF model (test/opf.jl:6-10) and the dense quadratic rows of the
-//     synthetic NLP of BASELINE.json configs[1];
+//     synthetic NLP of BASELINE.json configs[1]; and the kernels of a general expression block (a tape of the reference's
+//     @NLconstraint / @NLobjective expressions, reverse-mode derivatives);
 //   * the per-iteration reductions of the SLP callers (KT_residuals, norm_violations, norm_complementarity: common.jl:35-98;
 //     compute_phi, compute_derivative: slp.jl:79-147) on the evaluation results already in HBM.
 // Jacobian values are written straight into the handle's `dE` buffer in j_str order: they never cross PCIe.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/asm_hip.h"
 
 struct FnStore {
     int64_t n_rows, n;
@@ -161,6 +164,134 @@ __global__ __launch_bounds__(256) void k_nlp_dense_quadratic(AsmBt abt, const do
     }
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if (lane == 0) E[r0 + i] = acc;
+}
+
+// ---- NLP block 3: expression tape (include/asm_hip.h, "Expression block").  Rows 0..R-1 are constraint rows, R..R+T-1 objective terms.
+// Set up by asm_eval_setup: node references a / b made absolute (index into the whole tape), VAR nodes of a row carry the offset of
+// their Jacobian value from j0 in `slot`, VAR nodes of a term the position of their adjoint in the per-variable gradient list.
+// The node values live in HBM (val: 8 trial points x L) - a runtime-indexed per-thread array would spill to scratch; adj: L adjoints
+// (one point: the Jacobian and the gradient are only formed at the iterate).
+struct ExprTape {
+    const int64_t *ptr, *jptr, *a, *b, *slot, *gptr;   // ptr [R+T+1], jptr [R+1] (row Jacobian ranges from j0), gptr [n+1]
+    const int32_t* op;
+    const double* cst;
+    double *val, *adj, *tval, *gocc;                   // tval [8 x T] term values, gocc [gptr[n]] term adjoints of the VAR nodes
+    int64_t R, T, L, n;
+};
+// u ^ e (e != 0): |e| - 1 products left to right, then one more; 1 / u^|e| for e < 0.  *d = d/du, with the same factors.
+__device__ __forceinline__ double expr_powi(double u, int64_t e, double* d) {
+#pragma clang fp contract(off)
+    const int64_t k = e < 0 ? -e : e;
+    double p = 1.0;
+    for (int64_t i = 1; i < k; ++i) p = p * u;
+    const double pk = p * u;
+    if (e > 0) { *d = (double)e * p; return pk; }
+    *d = (double)e / (pk * u);
+    return 1.0 / pk;
+}
+// forward sweep over nodes [k0, k1) at x: every node value into val (absolute indices), returns the last one
+__device__ __forceinline__ double expr_forward(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, double* val) {
+#pragma clang fp contract(off)
+    double v = 0.0;
+    for (int64_t k = k0; k < k1; ++k) {
+        const int64_t a = X.a[k], b = X.b[k];
+        switch (X.op[k]) {
+            case ASM_OP_CONST: v = X.cst[a]; break;
+            case ASM_OP_VAR: v = x[a]; break;
+            case ASM_OP_ADD: v = val[a] + val[b]; break;
+            case ASM_OP_SUB: v = val[a] - val[b]; break;
+            case ASM_OP_MUL: v = val[a] * val[b]; break;
+            case ASM_OP_DIV: v = val[a] / val[b]; break;
+            case ASM_OP_NEG: v = -val[a]; break;
+            case ASM_OP_POWI: { double d; v = expr_powi(val[a], b, &d); break; }
+            case ASM_OP_SQRT: v = sqrt(val[a]); break;
+            case ASM_OP_EXP: v = exp(val[a]); break;
+            case ASM_OP_LOG: v = log(val[a]); break;
+            case ASM_OP_SIN: v = sin(val[a]); break;
+            default: v = cos(val[a]); break;       // ASM_OP_COS (asm_eval_setup admits no other op)
+        }
+        val[k] = v;
+    }
+    return v;
+}
+// reverse sweep over nodes [k0, k1) (values from the forward sweep in val): adjoints into adj, the adjoint of every VAR node k to
+// out[X.slot[k]] - added to it (ACC: constraint rows, several VAR nodes may share a Jacobian value) or stored (term occurrences)
+template <bool ACC>
+__device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int64_t k1, const double* val, double* adj, double* out) {
+#pragma clang fp contract(off)
+    for (int64_t k = k0; k < k1 - 1; ++k) adj[k] = 0.0;
+    adj[k1 - 1] = 1.0;
+    for (int64_t k = k1 - 1; k >= k0; --k) {
+        const double w = adj[k];
+        const int64_t a = X.a[k], b = X.b[k];
+        switch (X.op[k]) {
+            case ASM_OP_CONST: break;
+            case ASM_OP_VAR:
+                if (ACC) out[X.slot[k]] = out[X.slot[k]] + w;
+                else out[X.slot[k]] = w;
+                break;
+            case ASM_OP_ADD: adj[a] = adj[a] + w; adj[b] = adj[b] + w; break;
+            case ASM_OP_SUB: adj[a] = adj[a] + w; adj[b] = adj[b] - w; break;
+            case ASM_OP_MUL: { const double va = val[a], vb = val[b]; adj[a] = adj[a] + w * vb; adj[b] = adj[b] + w * va; break; }
+            case ASM_OP_DIV: { const double t = w / val[b]; adj[a] = adj[a] + t; adj[b] = adj[b] - t * val[k]; break; }
+            case ASM_OP_NEG: adj[a] = adj[a] - w; break;
+            case ASM_OP_POWI: { double d; (void)expr_powi(val[a], b, &d); adj[a] = adj[a] + w * d; break; }
+            case ASM_OP_SQRT: adj[a] = adj[a] + (0.5 * w) / val[k]; break;
+            case ASM_OP_EXP: adj[a] = adj[a] + w * val[k]; break;
+            case ASM_OP_LOG: adj[a] = adj[a] + w / val[a]; break;
+            case ASM_OP_SIN: adj[a] = adj[a] + w * cos(val[a]); break;
+            default: adj[a] = adj[a] - w * sin(val[a]); break;     // ASM_OP_COS
+        }
+    }
+}
+// constraint rows: one thread per row; E at r0 + row, Jacobian values at j0 + jptr[row].. (blockIdx.y = trial point, as k_fn_rows)
+__global__ __launch_bounds__(256) void k_nlp_expr_rows(AsmBt abt, ExprTape X, const double* __restrict__ x, double* __restrict__ E, double* __restrict__ dE, int64_t r0, int64_t j0, int write_jac, int64_t ldx, int64_t ldE) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, x, E, dE, r0, j0, write_jac, ldx, ldE);
+    const int64_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= X.R) return;
+    x += blockIdx.y * ldx;
+    E += blockIdx.y * ldE;
+    double* val = X.val + blockIdx.y * X.L;
+    const int64_t k0 = X.ptr[r], k1 = X.ptr[r + 1];
+    E[r0 + r] = expr_forward(X, k0, k1, x, val);
+    if (!write_jac || blockIdx.y) return;
+    double* o = dE + j0;
+    for (int64_t j = X.jptr[r]; j < X.jptr[r + 1]; ++j) o[j] = 0.0;
+    expr_reverse<true>(X, k0, k1, val, X.adj, o);
+}
+// objective terms: one thread per term; its value to tval[trial * T + term], with write_grad (one point) its VAR-node adjoints to gocc
+__global__ __launch_bounds__(256) void k_nlp_expr_terms(AsmBt abt, ExprTape X, const double* __restrict__ x, int write_grad, int64_t ldx) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, x, write_grad, ldx);
+    const int64_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= X.T) return;
+    x += blockIdx.y * ldx;
+    double* val = X.val + blockIdx.y * X.L;
+    const int64_t k0 = X.ptr[X.R + t], k1 = X.ptr[X.R + t + 1];
+    X.tval[blockIdx.y * X.T + t] = expr_forward(X, k0, k1, x, val);
+    if (!write_grad || blockIdx.y) return;
+    expr_reverse<false>(X, k0, k1, val, X.adj, X.gocc);
+}
+// the objective: one thread sums the term values in term order and applies the sense scale (as k_fn_objective); blockIdx.x = trial point
+__global__ __launch_bounds__(64) void k_nlp_expr_objective(AsmBt abt, ExprTape X, double scale, double* __restrict__ f_out) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, scale, f_out);
+    if (threadIdx.x) return;
+    const double* tv = X.tval + blockIdx.x * X.T;
+    double v = 0.0;
+    for (int64_t t = 0; t < X.T; ++t) v = v + tv[t];
+    f_out[blockIdx.x] = scale * v;
+}
+// the objective gradient: one thread per variable gathers its term adjoints in (term, node) order (as k_fn_gradient)
+__global__ __launch_bounds__(256) void k_nlp_expr_gradient(AsmBt abt, ExprTape X, double scale, double* __restrict__ df) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, scale, df);
+    const int64_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= X.n) return;
+    double g = 0.0;
+    for (int64_t o = X.gptr[j]; o < X.gptr[j + 1]; ++o) g = g + X.gocc[o];
+    df[j] = g * scale;
 }
 
 __global__ __launch_bounds__(256) void k_axpy_out(AsmBt abt, const double* __restrict__ x, double alpha, const double* __restrict__ p, double* __restrict__ out, int64_t n) {

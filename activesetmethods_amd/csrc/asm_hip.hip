@@ -319,6 +319,8 @@ struct asm_handle {
     int ev_nlp_kind = 0;
     int64_t ev_nlp_rows = 0, ev_nlp_nnz = 0, ev_fn_nnz = 0;
     FnStore ev_F;
+    ExprTape ev_X{};                // nlp_kind ASM_NLP_EXPR: the tape and its workspace (asm_eval_kernels.hip.h)
+    std::vector<int64_t> j_row_h, j_col_h;   // j_str as asm_sublp_setup received it (the expression block's pattern is checked against it)
     std::vector<void*> ev_bufs;
     int64_t* d_ev_ipar = nullptr;
     double *d_ev_dpar = nullptr, *d_ev_x = nullptr, *d_ev_xt = nullptr, *d_ev_df = nullptr, *d_ev_E = nullptr, *d_ev_Et = nullptr, *d_ev_f = nullptr;
@@ -2791,6 +2793,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     h->inputs_ready = false;
     h->J_valid = false;
     h->n = n; h->m = m; h->nnz = nnz;
+    h->j_row_h.assign(j_row, j_row + nnz); h->j_col_h.assign(j_col, j_col + nnz);
     h->c_lb.assign(c_lb, c_lb + m); h->c_ub.assign(c_ub, c_ub + m);
     h->v_lb.assign(v_lb, v_lb + n); h->v_ub.assign(v_ub, v_ub + n);
     h->kind.resize(m);
@@ -3346,9 +3349,22 @@ void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool ful
     const unsigned nt = (unsigned)ntrial;
     if (F.n_rows > 0)
         hipLaunchKernelGGL(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), 0, h->stream, F, xd, Ed, h->d_dE, full ? 1 : 0, ldx, ldE);
-    hipLaunchKernelGGL(k_fn_objective, dim3(nt), dim3(256), 0, h->stream, F, xd, fd, ldx);
-    if (full) hipLaunchKernelGGL(k_fn_gradient, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, F, xd, h->d_ev_df);
-    if (h->ev_nlp_kind == 1) {
+    const ExprTape& X = h->ev_X;
+    const bool expr_obj = h->ev_nlp_kind == ASM_NLP_EXPR && X.T > 0;     // the expression objective replaces the store's objective row
+    if (!expr_obj) {
+        hipLaunchKernelGGL(k_fn_objective, dim3(nt), dim3(256), 0, h->stream, F, xd, fd, ldx);
+        if (full) hipLaunchKernelGGL(k_fn_gradient, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, F, xd, h->d_ev_df);
+    }
+    if (h->ev_nlp_kind == ASM_NLP_EXPR) {
+        if (X.R > 0)
+            hipLaunchKernelGGL(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), 0, h->stream, X, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz,
+                               full ? 1 : 0, ldx, ldE);
+        if (expr_obj) {
+            hipLaunchKernelGGL(k_nlp_expr_terms, dim3((unsigned)((X.T + 255) / 256), nt), dim3(256), 0, h->stream, X, xd, full ? 1 : 0, ldx);
+            hipLaunchKernelGGL(k_nlp_expr_objective, dim3(nt), dim3(64), 0, h->stream, X, F.objective_scale, fd);
+            if (full) hipLaunchKernelGGL(k_nlp_expr_gradient, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, X, F.objective_scale, h->d_ev_df);
+        }
+    } else if (h->ev_nlp_kind == 1) {
         const int64_t nl = h->ev_nlp_rows / 4;
         hipLaunchKernelGGL(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), 0, h->stream, (const int64_t*)h->d_ev_ipar, (const double*)h->d_ev_dpar,
                            xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
@@ -3604,13 +3620,93 @@ int asm_kt_residuals(asm_handle* h, const double* df, const double* lambda, cons
 }
 
 // --------------------------------------------------------------------------------- device-side evaluators (rows a2 / f3)
+namespace {
+// the host-side form of an expression block (include/asm_hip.h, "Expression block") after validation: node references absolute,
+// the slots of the VAR nodes (rows: Jacobian value from j0; terms: position in the per-variable gradient list)
+struct ExprHost {
+    int64_t R = 0, T = 0, L = 0;
+    std::vector<int64_t> ptr, jptr, a, b, slot, gptr;
+    std::vector<int32_t> op;
+};
+void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_nnz, int64_t nlp_rows, int64_t nlp_nnz, const int64_t* ip, int64_t n_ipar,
+                  int64_t n_dpar) {
+    auto bad = [](const std::string& what) { throw std::invalid_argument("asm_eval_setup: expression block: " + what); };
+    if (!ip || n_ipar < 3) bad("ipar too short");
+    const int64_t R = ip[0], T = ip[1], L = ip[2], n = h->n;
+    if (R != nlp_rows) bad("ipar[0] (rows) differs from nlp_rows");
+    if (R < 0 || T < 0 || L < 0 || L > (int64_t)1 << 40 || R + T > L) bad("bad row / term / node count");
+    if (n_ipar != 3 + R + T + 1 + 3 * L) bad("ipar size differs from 3 + R + T + 1 + 3 L");
+    const int64_t *ptr = ip + 3, *op = ptr + R + T + 1, *a = op + L, *b = a + L;
+    if (ptr[0] != 0 || ptr[R + T] != L) bad("ptr must run from 0 to L");
+    for (int64_t r = 0; r < R + T; ++r)
+        if (ptr[r + 1] <= ptr[r]) bad("row / term " + std::to_string(r) + " has no nodes");
+    xh.R = R; xh.T = T; xh.L = L;
+    xh.ptr.assign(ptr, ptr + R + T + 1);
+    xh.op.resize(L); xh.a.resize(L); xh.b.resize(L); xh.slot.assign(L, -1);
+    for (int64_t r = 0; r < R + T; ++r) {
+        const int64_t k0 = ptr[r];
+        for (int64_t k = k0; k < ptr[r + 1]; ++k) {
+            const int64_t o = op[k], ka = a[k], kb = b[k], loc = k - k0;
+            const std::string at = "node " + std::to_string(loc) + " of " + (r < R ? "row " + std::to_string(r) : "term " + std::to_string(r - R));
+            if (o < ASM_OP_CONST || o >= ASM_OP_COUNT) bad(at + ": unknown op " + std::to_string(o));
+            int64_t aa = ka, bb = 0;
+            if (o == ASM_OP_CONST) {
+                if (ka < 0 || ka >= n_dpar) bad(at + ": constant index out of range");
+            } else if (o == ASM_OP_VAR) {
+                if (ka < 0 || ka >= n) bad(at + ": variable out of range");
+            } else {
+                if (ka < 0 || ka >= loc) bad(at + ": operand a is not an earlier node of its row");
+                aa = k0 + ka;
+                if (o >= ASM_OP_ADD && o <= ASM_OP_DIV) {
+                    if (kb < 0 || kb >= loc) bad(at + ": operand b is not an earlier node of its row");
+                    bb = k0 + kb;
+                } else if (o == ASM_OP_POWI) {
+                    if (kb == 0 || kb < -ASM_EXPR_MAX_POWI || kb > ASM_EXPR_MAX_POWI) bad(at + ": POWI exponent must be a nonzero integer of magnitude <= 64");
+                    bb = kb;
+                }
+            }
+            xh.op[k] = (int32_t)o; xh.a[k] = aa; xh.b[k] = bb;
+        }
+    }
+    // Jacobian pattern: each row's distinct variables ascending; it must be the block's part of j_str
+    xh.jptr.assign(1, 0);
+    std::vector<int64_t> vars;
+    for (int64_t r = 0; r < R; ++r) {
+        vars.clear();
+        for (int64_t k = ptr[r]; k < ptr[r + 1]; ++k)
+            if (op[k] == ASM_OP_VAR) vars.push_back(a[k]);
+        std::sort(vars.begin(), vars.end());
+        vars.erase(std::unique(vars.begin(), vars.end()), vars.end());
+        const int64_t j0 = xh.jptr.back();
+        if (j0 + (int64_t)vars.size() > nlp_nnz) bad("nlp_nnz is smaller than the pattern of the rows");
+        for (size_t q = 0; q < vars.size(); ++q) {
+            const int64_t e = fn_nnz + j0 + (int64_t)q;
+            if (h->j_row_h[e] != n_rows + r + 1 || h->j_col_h[e] != vars[q] + 1)
+                bad("j_str entry " + std::to_string(e + 1) + " differs from the pattern of row " + std::to_string(r) + " (its distinct variables, ascending)");
+        }
+        for (int64_t k = ptr[r]; k < ptr[r + 1]; ++k)
+            if (op[k] == ASM_OP_VAR) xh.slot[k] = j0 + (std::lower_bound(vars.begin(), vars.end(), a[k]) - vars.begin());
+        xh.jptr.push_back(j0 + (int64_t)vars.size());
+    }
+    if (xh.jptr.back() != nlp_nnz) bad("nlp_nnz differs from the size of the rows' pattern");
+    // objective terms: the VAR nodes grouped by variable, in (term, node) order inside each group
+    xh.gptr.assign(n + 1, 0);
+    for (int64_t k = ptr[R]; k < L; ++k)
+        if (op[k] == ASM_OP_VAR) ++xh.gptr[a[k] + 1];
+    for (int64_t j = 0; j < n; ++j) xh.gptr[j + 1] += xh.gptr[j];
+    std::vector<int64_t> fill(xh.gptr.begin(), xh.gptr.end() - 1);
+    for (int64_t k = ptr[R]; k < L; ++k)
+        if (op[k] == ASM_OP_VAR) xh.slot[k] = fill[a[k]]++;
+}
+}  // namespace
+
 int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const int64_t* aff_var, const double* aff_coef, const int64_t* quad_ptr,
                    const int64_t* q_v1, const int64_t* q_v2, const double* q_coef, const double* constant, const int64_t* jac_off,
                    const int64_t* g_ptr, const int64_t* g_kind, const double* g_coef, const int64_t* g_other, double objective_scale, int nlp_kind,
                    int64_t nlp_rows, int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
     return guarded(h, [&] {
         if (!h->setup_done) throw std::logic_error("asm_eval_setup: asm_sublp_setup first (it fixes n, m and the j_str order of dE)");
-        if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < 0 || nlp_kind > 2)
+        if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < ASM_NLP_NONE || nlp_kind > ASM_NLP_EXPR)
             throw std::invalid_argument("asm_eval_setup: bad argument");
         const int64_t fn_nnz = jac_off[n_rows];
         if (n_rows + nlp_rows != h->m || fn_nnz + nlp_nnz != h->nnz)
@@ -3618,6 +3714,8 @@ int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const 
         if (nlp_kind == 1 && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
             throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
         if (nlp_kind == 2 && (nlp_nnz != nlp_rows * h->n || n_dpar != 2 * nlp_rows * h->n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
+        ExprHost xh;
+        if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
         HIPCHK(hipSetDevice(h->device));
         for (void* q : h->ev_bufs) (void)hipFree(q);
         h->ev_bufs.clear();
@@ -3637,6 +3735,18 @@ int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const 
                                           HIPCHK(hipMemset(d, 0, std::max<int64_t>(cnt, 1) * sizeof(double))); return d; };
         h->d_ev_x = dalloc(n); h->d_ev_xt = dalloc(8 * round_up(n, 32)); h->d_ev_df = dalloc(n); h->d_ev_E = dalloc(m); h->d_ev_Et = dalloc(8 * round_up(std::max<int64_t>(m, 1), 32));
         h->d_ev_f = dalloc(16);      // xt / Et / f[1..8]: eight trial points of the batched line search
+        h->ev_X = ExprTape{};
+        if (nlp_kind == ASM_NLP_EXPR) {
+            ExprTape& X = h->ev_X;
+            X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = h->n;
+            X.ptr = ev_upload(h, xh.ptr.data(), (int64_t)xh.ptr.size()); X.jptr = ev_upload(h, xh.jptr.data(), (int64_t)xh.jptr.size());
+            X.a = ev_upload(h, xh.a.data(), xh.L); X.b = ev_upload(h, xh.b.data(), xh.L); X.slot = ev_upload(h, xh.slot.data(), xh.L);
+            X.op = ev_upload(h, xh.op.data(), xh.L); X.gptr = ev_upload(h, xh.gptr.data(), (int64_t)xh.gptr.size());
+            X.cst = h->d_ev_dpar;
+            // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
+            X.val = dalloc(8 * xh.L); X.adj = dalloc(xh.L);
+            X.tval = dalloc(8 * xh.T); X.gocc = dalloc(xh.gptr[h->n]);
+        }
         // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
         h->d_ev_vecs = dalloc(2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
         HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));

@@ -75,16 +75,33 @@ class ScalarFunction:
         return vals
 
 
+# the device kernels an NLP block can name (NlpBlock.device[0]) -> nlp_kind of asm_eval_setup (include/asm_hip.h: ASM_NLP_*)
+NLP_KINDS = {"acopf_ohm": 1, "dense_quadratic": 2, "expr": 3}
+
+
+def nlp_kind(device):
+    """asm_eval_setup's nlp_kind for an NlpBlock.device tuple (name, ipar, dpar)."""
+    name = device[0]
+    if name not in NLP_KINDS:
+        raise ValueError("unknown NLP device kernel %r (known: %s)" % (name, ", ".join(sorted(NLP_KINDS))))
+    return NLP_KINDS[name]
+
+
 class NlpBlock:
     """The `nlp_data` of the wrapper: bounds, pattern (1-based rows inside the block, 1-based columns) and callbacks
     eval_g(x, out) / eval_jac_g(x, out) in the pattern's order; `device` names a device kernel of libasmhip
-    (None: host only) with its parameter arrays."""
+    (None: host only) with its parameter arrays.  has_objective: the block also carries the objective, eval_f(x) /
+    eval_grad_f(x, grad) without the sense scale; it overrides the model's own objective (MOI_wrapper.jl:809-861)."""
 
-    def __init__(self, g_L, g_U, rows, cols, eval_g, eval_jac_g, device=None):
+    def __init__(self, g_L, g_U, rows, cols, eval_g, eval_jac_g, device=None, has_objective=False, eval_f=None, eval_grad_f=None):
         self.g_L, self.g_U = np.asarray(g_L, float), np.asarray(g_U, float)
         self.rows, self.cols = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
         self.eval_g, self.eval_jac_g = eval_g, eval_jac_g
         self.device = device
+        if has_objective and (eval_f is None or eval_grad_f is None):
+            raise ValueError("an NLP block with an objective needs eval_f and eval_grad_f")
+        self.has_objective = bool(has_objective)
+        self.eval_f, self.eval_grad_f = eval_f, eval_grad_f
 
     @property
     def m(self):
@@ -156,11 +173,15 @@ class FunctionModel:
     # ---- callbacks (MOI_wrapper.jl:1046-1069 with eval_objective :809-820, eval_objective_gradient :852-861,
     #      eval_constraint :875-887, eval_constraint_jacobian :932-944)
     def eval_f(self, x):
+        if self.nlp is not None and self.nlp.has_objective:       # NLP objectives override regular objectives (:811-813)
+            return self.objective_scale * self.nlp.eval_f(x)
         return self.objective_scale * (self.objective.value(x) if self.objective is not None else 0.0)
 
     def eval_grad_f(self, x, grad):
         grad[:] = 0.0
-        if self.objective is not None:
+        if self.nlp is not None and self.nlp.has_objective:       # :853-854
+            self.nlp.eval_grad_f(x, grad)
+        elif self.objective is not None:
             self.objective.add_gradient(grad, x)
         grad *= self.objective_scale
         return grad

@@ -1,0 +1,361 @@
+"""General nonlinear expressions for the NLP block: what the reference's users write as @NLconstraint / @NLobjective, and what
+a Julia binding receives from `MOI.constraint_expr` / `MOI.objective_expr` after `MOI.initialize(evaluator, [:ExprGraph])`.
+
+    x = variables(n)                       x[j] is variable j (0-based)
+    e = x[0] * x[1] - sin(x[2]) / 2        + - * / unary -, ** int, sin cos exp log sqrt
+    ExprBlock(constraints=[(e, lo, hi)], objective=None, n=n)
+
+ExprBlock flattens every row (and every objective term) into the tape of include/asm_hip.h ("Expression block", nlp_kind 3):
+nodes (op, a, b) in SSA order, references local to the row, shared sub-expressions emitted once, each variable once per row.
+It is an NlpBlock (moi_evaluator.py) whose `device` is ("expr", ipar, dpar) and whose host callbacks interpret the same tape with
+the same formulas in the same order as the kernels of csrc/asm_eval_kernels.hip.h (vectorised over rows, one IEEE operation per
+node and row): with + - * / unary - and ** only, host and device agree bit for bit.
+
+The objective, when given, is split into terms along its left spine of additions (((t1 + t2) + t3) -> [t1, t2, t3]) and summed
+in term order from 0.0; it replaces the FunctionModel's own objective (`has_objective`, MOI_wrapper.jl:809-861).
+"""
+import numbers
+import struct
+
+import numpy as np
+
+from .moi_evaluator import NlpBlock
+
+# op codes of include/asm_hip.h (ASM_OP_*)
+CONST, VAR, ADD, SUB, MUL, DIV, NEG, POWI, SQRT, EXP, LOG, SIN, COS = range(13)
+OP_COUNT = 13
+MAX_POWI = 64
+_BINARY = (ADD, SUB, MUL, DIV)
+_UNARY = (NEG, POWI, SQRT, EXP, LOG, SIN, COS)
+
+
+class Expr:
+    """A node of an expression graph: op code, operands (Expr), and for CONST the value, for VAR the variable, for POWI the
+    exponent."""
+    __slots__ = ("op", "args", "arg")
+    __array_priority__ = 100                    # numpy scalars on the left defer to Expr's reflected operators
+
+    def __init__(self, op, args=(), arg=None):
+        self.op, self.args, self.arg = op, tuple(args), arg
+
+    # ---- operator overloading
+    def __add__(self, o): return Expr(ADD, (self, _wrap(o)))
+    def __radd__(self, o): return Expr(ADD, (_wrap(o), self))
+    def __sub__(self, o): return Expr(SUB, (self, _wrap(o)))
+    def __rsub__(self, o): return Expr(SUB, (_wrap(o), self))
+    def __mul__(self, o): return Expr(MUL, (self, _wrap(o)))
+    def __rmul__(self, o): return Expr(MUL, (_wrap(o), self))
+    def __truediv__(self, o): return Expr(DIV, (self, _wrap(o)))
+    def __rtruediv__(self, o): return Expr(DIV, (_wrap(o), self))
+    def __neg__(self): return Expr(NEG, (self,))
+    def __pos__(self): return self
+
+    def __pow__(self, e):
+        if not isinstance(e, numbers.Integral) or isinstance(e, bool):
+            raise TypeError("only integer exponents are supported (x ** k)")
+        e = int(e)
+        if e == 0:
+            return Expr(CONST, arg=1.0)
+        if e == 1:
+            return self
+        if abs(e) > MAX_POWI:
+            raise ValueError("exponent magnitude above %d" % MAX_POWI)
+        return Expr(POWI, (self,), e)
+
+    def __repr__(self):
+        return "Expr(op=%d, arg=%r, %d args)" % (self.op, self.arg, len(self.args))
+
+
+def _wrap(v):
+    if isinstance(v, Expr):
+        return v
+    if isinstance(v, numbers.Real):
+        return Expr(CONST, arg=float(v))
+    raise TypeError("cannot use %r in an expression" % (v,))
+
+
+def const(v):
+    return Expr(CONST, arg=float(v))
+
+
+def var(j):
+    return Expr(VAR, arg=int(j))
+
+
+def variables(n):
+    return [var(j) for j in range(n)]
+
+
+def _unary(op):
+    def f(u):
+        return Expr(op, (_wrap(u),))
+    return f
+
+
+sqrt, exp, log, sin, cos = (_unary(o) for o in (SQRT, EXP, LOG, SIN, COS))
+
+
+def _split_terms(e):
+    terms = []
+    while e.op == ADD:
+        terms.append(e.args[1])
+        e = e.args[0]
+    terms.append(e)
+    return terms[::-1]
+
+
+# ---------------------------------------------------------------------------------------------------- tape
+class Tape:
+    """Rows (constraint rows, then objective terms) as flat arrays: ptr [R+T+1], op / a / b [L] with row-local references, the
+    constants in `dpar` (one entry per distinct value)."""
+
+    def __init__(self, rows, n_constraint_rows):
+        self.R, self.T = n_constraint_rows, len(rows) - n_constraint_rows
+        self.consts, cidx = [], {}
+        ptr, op, a, b = [0], [], [], []
+        for root in rows:
+            memo, vidx = {}, {}
+            stack = [(root, False)]
+            while stack:                                  # post-order without recursion (long sums make deep graphs)
+                e, done = stack.pop()
+                if id(e) in memo:
+                    continue
+                if not done:
+                    stack.append((e, True))
+                    for c in reversed(e.args):
+                        if id(c) not in memo:
+                            stack.append((c, False))
+                    continue
+                k = len(op) - ptr[-1]
+                if e.op == CONST:
+                    key = struct.pack("<d", e.arg)
+                    if key not in cidx:
+                        cidx[key] = len(self.consts)
+                        self.consts.append(e.arg)
+                    op.append(CONST); a.append(cidx[key]); b.append(0)
+                elif e.op == VAR:
+                    if e.arg in vidx:                     # each variable once per row
+                        memo[id(e)] = vidx[e.arg]
+                        continue
+                    vidx[e.arg] = k
+                    op.append(VAR); a.append(e.arg); b.append(0)
+                elif e.op in _BINARY:
+                    op.append(e.op); a.append(memo[id(e.args[0])]); b.append(memo[id(e.args[1])])
+                elif e.op == POWI:
+                    op.append(POWI); a.append(memo[id(e.args[0])]); b.append(e.arg)
+                else:
+                    op.append(e.op); a.append(memo[id(e.args[0])]); b.append(0)
+                memo[id(e)] = k
+            ptr.append(len(op))
+        self.ptr = np.asarray(ptr, np.int64)
+        self.op, self.a, self.b = (np.asarray(v, np.int64) for v in (op, a, b))
+        self.L = len(op)
+
+    def ipar(self):
+        return np.concatenate([[self.R, self.T, self.L], self.ptr, self.op, self.a, self.b]).astype(np.int64)
+
+    def dpar(self):
+        return np.asarray(self.consts, np.float64)
+
+
+def parse_ipar(ipar):
+    """(R, T, L, ptr, op, a, b) of an ipar array (no checks: the library validates)."""
+    ipar = np.asarray(ipar, np.int64)
+    R, T, L = (int(v) for v in ipar[:3])
+    ptr = ipar[3:3 + R + T + 1]
+    o = 3 + R + T + 1
+    return R, T, L, ptr, ipar[o:o + L], ipar[o + L:o + 2 * L], ipar[o + 2 * L:o + 3 * L]
+
+
+def _powi(u, e):
+    """u ** e and its derivative with the factors of expr_powi (asm_eval_kernels.hip.h)."""
+    k = abs(e)
+    p = np.ones_like(u)
+    for _ in range(1, k):
+        p = p * u
+    pk = p * u
+    if e > 0:
+        return pk, float(e) * p
+    return 1.0 / pk, float(e) / (pk * u)
+
+
+class _Sweep:
+    """The host twin of expr_forward / expr_reverse for a group of rows: rows padded to the longest, node position k evaluated
+    for all rows at once, grouped by op (each node of each row is still the one IEEE operation the kernel performs)."""
+
+    def __init__(self, ptr, op, a, b, slot):
+        self.nr = len(ptr) - 1
+        lens = np.diff(ptr)
+        self.lens = lens
+        self.K = int(lens.max()) if self.nr else 0
+        self.last = lens - 1
+        self.steps = []
+        for k in range(self.K):
+            rows = np.nonzero(lens > k)[0]
+            g = ptr[rows] + k
+            ops = op[g]
+            groups = []
+            for o in np.unique(ops):
+                sel = ops == o
+                r = rows[sel]
+                groups.append((int(o), r, a[g[sel]], b[g[sel]], slot[g[sel]]))
+            self.steps.append(groups)
+
+    def forward(self, x, consts):
+        V = np.zeros((self.nr, max(self.K, 1)))
+        with np.errstate(all="ignore"):
+            for k, groups in enumerate(self.steps):
+                for o, r, a, b, _ in groups:
+                    if o == CONST:
+                        v = consts[a]
+                    elif o == VAR:
+                        v = x[a]
+                    elif o == ADD:
+                        v = V[r, a] + V[r, b]
+                    elif o == SUB:
+                        v = V[r, a] - V[r, b]
+                    elif o == MUL:
+                        v = V[r, a] * V[r, b]
+                    elif o == DIV:
+                        v = V[r, a] / V[r, b]
+                    elif o == NEG:
+                        v = -V[r, a]
+                    elif o == POWI:
+                        v = np.empty(len(r))
+                        for e in np.unique(b):
+                            s = b == e
+                            v[s] = _powi(V[r[s], a[s]], int(e))[0]
+                    elif o == SQRT:
+                        v = np.sqrt(V[r, a])
+                    elif o == EXP:
+                        v = np.exp(V[r, a])
+                    elif o == LOG:
+                        v = np.log(V[r, a])
+                    elif o == SIN:
+                        v = np.sin(V[r, a])
+                    else:
+                        v = np.cos(V[r, a])
+                    V[r, k] = v
+        return V, V[np.arange(self.nr), self.last]
+
+    def reverse(self, V, out, accumulate):
+        """Adjoints from the last node of every row back; VAR-node adjoints added to (or stored into) out[slot]."""
+        W = np.zeros_like(V)
+        W[np.arange(self.nr), self.last] = 1.0
+        with np.errstate(all="ignore"):
+            for k in range(self.K - 1, -1, -1):
+                for o, r, a, b, slot in self.steps[k]:
+                    w = W[r, k]
+                    if o == CONST:
+                        continue
+                    if o == VAR:
+                        out[slot] = out[slot] + w if accumulate else w
+                    elif o == ADD:
+                        W[r, a] = W[r, a] + w
+                        W[r, b] = W[r, b] + w
+                    elif o == SUB:
+                        W[r, a] = W[r, a] + w
+                        W[r, b] = W[r, b] - w
+                    elif o == MUL:
+                        va, vb = V[r, a], V[r, b]
+                        W[r, a] = W[r, a] + w * vb
+                        W[r, b] = W[r, b] + w * va
+                    elif o == DIV:
+                        t = w / V[r, b]
+                        W[r, a] = W[r, a] + t
+                        W[r, b] = W[r, b] - t * V[r, k]
+                    elif o == NEG:
+                        W[r, a] = W[r, a] - w
+                    elif o == POWI:
+                        d = np.empty(len(r))
+                        for e in np.unique(b):
+                            s = b == e
+                            d[s] = _powi(V[r[s], a[s]], int(e))[1]
+                        W[r, a] = W[r, a] + w * d
+                    elif o == SQRT:
+                        W[r, a] = W[r, a] + (0.5 * w) / V[r, k]
+                    elif o == EXP:
+                        W[r, a] = W[r, a] + w * V[r, k]
+                    elif o == LOG:
+                        W[r, a] = W[r, a] + w / V[r, a]
+                    elif o == SIN:
+                        W[r, a] = W[r, a] + w * np.cos(V[r, a])
+                    else:
+                        W[r, a] = W[r, a] - w * np.sin(V[r, a])
+
+
+class ExprBlock(NlpBlock):
+    """An NLP block of expressions: `constraints` = [(expr, lo, hi)] (lo == hi: equality; +-inf: one-sided), `objective` = an
+    expression or None.  Rows of the Jacobian pattern: each row's distinct variables in ascending order (1-based block rows and
+    columns, as NlpBlock)."""
+
+    def __init__(self, constraints=(), objective=None, n=None):
+        cons = [(_wrap(e), float(lo), float(hi)) for e, lo, hi in constraints]
+        terms = _split_terms(_wrap(objective)) if objective is not None else []
+        tape = Tape([e for e, _, _ in cons] + terms, len(cons))
+        self.tape = tape
+        R, T = tape.R, tape.T
+        ptr, op, a = tape.ptr, tape.op, tape.a
+        if n is not None and np.any(a[op == VAR] >= n):
+            raise ValueError("a variable index is out of range for n = %d" % n)
+        # pattern and slots: rows -> position in the block's Jacobian values; terms -> position in the per-variable gradient lists
+        slot = np.full(tape.L, -1, np.int64)
+        rows, cols = [], []
+        for r in range(R):
+            k = np.arange(ptr[r], ptr[r + 1])
+            kv = k[op[k] == VAR]
+            vs = np.unique(a[kv])
+            slot[kv] = len(cols) + np.searchsorted(vs, a[kv])
+            rows += [r + 1] * len(vs)
+            cols += (vs + 1).tolist()
+        n_var = int(n) if n is not None else (int(a[op == VAR].max()) + 1 if np.any(op == VAR) else 0)
+        kt = np.arange(ptr[R], tape.L)
+        kv = kt[op[kt] == VAR]
+        order = np.lexsort((kv, a[kv]))                    # by variable, then (term, node) = node order
+        slot[kv[order]] = np.arange(len(kv))
+        self.g_ptr = np.concatenate([[0], np.cumsum(np.bincount(a[kv], minlength=n_var))]).astype(np.int64)
+        self.n_var = n_var
+        self._consts = tape.dpar()
+        self._rows = _Sweep(ptr[:R + 1], op, tape.a, tape.b, slot)
+        self._terms = _Sweep(ptr[R:] - ptr[R], op[ptr[R]:], tape.a[ptr[R]:], tape.b[ptr[R]:], slot[ptr[R]:])
+        self._n_occ = len(kv)
+        super().__init__([lo for _, lo, _ in cons], [hi for _, _, hi in cons], rows, cols, self._eval_g, self._eval_jac_g,
+                         device=("expr", tape.ipar(), self._consts),
+                         has_objective=T > 0, eval_f=self._eval_f if T > 0 else None, eval_grad_f=self._eval_grad_f if T > 0 else None)
+
+    # ---- host callbacks (the twins of k_nlp_expr_rows / _terms / _objective / _gradient)
+    def _eval_g(self, x, out):
+        out[:] = self._rows.forward(np.asarray(x, float), self._consts)[1]
+        return out
+
+    def _eval_jac_g(self, x, out):
+        V, _ = self._rows.forward(np.asarray(x, float), self._consts)
+        vals = np.zeros(len(self.rows))
+        self._rows.reverse(V, vals, True)
+        out[:] = vals
+        return out
+
+    def _eval_f(self, x):
+        """The sum of the terms in term order from 0.0 (unscaled: FunctionModel applies the sense)."""
+        tv = self._terms.forward(np.asarray(x, float), self._consts)[1]
+        v = 0.0
+        for t in tv:
+            v = v + float(t)
+        return v
+
+    def _eval_grad_f(self, x, grad):
+        """Per variable, the adjoints of its VAR nodes in (term, node) order from 0.0 (unscaled)."""
+        V, _ = self._terms.forward(np.asarray(x, float), self._consts)
+        occ = np.zeros(self._n_occ)
+        self._terms.reverse(V, occ, False)
+        n = len(grad)
+        gp = np.zeros(n + 1, np.int64)
+        gp[:len(self.g_ptr)] = self.g_ptr
+        gp[len(self.g_ptr):] = self.g_ptr[-1]
+        cnt = np.diff(gp)
+        g = np.zeros(n)
+        for i in range(int(cnt.max()) if n else 0):
+            s = cnt > i
+            g[s] = g[s] + occ[gp[:-1][s] + i]
+        grad[:] = g
+        return grad

@@ -6,6 +6,8 @@ pattern `j_str` in the wrapper's row order (src/MOI_wrapper.jl:683-746), the sta
 (src/MOI_wrapper.jl:1113-1130) and the four evaluation callbacks (src/MOI_wrapper.jl:1037-1069).
 
   toy_problem()            examples/toy_example.jl:12-18 == test/ext_solver.jl:12-18
+  toy_expr_problem()       the same toy as the example writes it: affine row, three @NLconstraint rows as expressions
+  hs071_problem()          Hock-Schittkowski 71: expression objective and constraints
   synthetic_dense_nlp()    BASELINE.json configs[1]  ("C2")
 """
 import numpy as np
@@ -148,3 +150,38 @@ def synthetic_dense_function_model(n=1000, m=500):
     fm.nlp = NlpBlock(pr.g_L, pr.g_U, pr.j_row, pr.j_col, pr.eval_g, pr.eval_jac_g,
                       device=("dense_quadratic", np.zeros(1, np.int64), np.concatenate([d["A"].ravel(), d["Q"].ravel()])))
     return fm
+
+
+# --------------------------------------------------------------------------- expression models (nlexpr.py, nlp_kind 3)
+def toy_expr_function_model():
+    """examples/toy_example.jl as written: @objective X^2 + X (a quadratic function of the wrapper), @NLconstraint X^2 - X == 2,
+    X*Y == 1, X*Y >= 0 (the expression block) and @constraint X >= -2 (an affine row, first in the wrapper's row order)."""
+    from .moi_evaluator import FunctionModel, ScalarFunction
+    from .nlexpr import ExprBlock, variables
+    X, Y = variables(2)
+    fm = FunctionModel(2)
+    fm.objective = ScalarFunction(0.0, [(1.0, 1)], [(2.0, 1, 1)])
+    fm.add_constraint(ScalarFunction(0.0, [(1.0, 1)]), "ge", -2.0)
+    fm.nlp = ExprBlock([(X ** 2 - X, 2.0, 2.0), (X * Y, 1.0, 1.0), (X * Y, 0.0, INF)], n=2)
+    return fm
+
+
+def toy_expr_problem():
+    return toy_expr_function_model().to_problem("toy-expr")
+
+
+def hs071_function_model():
+    """Hock-Schittkowski problem 71:  min x1 x4 (x1 + x2 + x3) + x3  s.t.  x1 x2 x3 x4 >= 25,  x1^2 + x2^2 + x3^2 + x4^2 == 40,
+    1 <= xi <= 5, start (1, 5, 5, 1).  Objective and both constraints are expressions (an @NLobjective overrides the model's)."""
+    from .moi_evaluator import FunctionModel
+    from .nlexpr import ExprBlock, variables
+    x1, x2, x3, x4 = variables(4)
+    fm = FunctionModel(4, np.ones(4), np.full(4, 5.0))
+    fm.start = {1: 1.0, 2: 5.0, 3: 5.0, 4: 1.0}
+    fm.nlp = ExprBlock([(x1 * x2 * x3 * x4, 25.0, INF), (x1 ** 2 + x2 ** 2 + x3 ** 2 + x4 ** 2, 40.0, 40.0)],
+                       objective=x1 * x4 * (x1 + x2 + x3) + x3, n=4)
+    return fm
+
+
+def hs071_problem():
+    return hs071_function_model().to_problem("hs071")

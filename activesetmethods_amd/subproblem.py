@@ -13,6 +13,7 @@ import ctypes as C
 from collections.abc import Mapping
 import numpy as np
 from . import _lib
+from .moi_evaluator import nlp_kind
 
 
 class AsmHipError(RuntimeError):
@@ -208,8 +209,8 @@ class HipSubOptimizer:
         if fm.nlp is not None:
             if fm.nlp.device is None:
                 raise AsmHipError("the model's NLP block has no device kernel")
-            name, ipar, dpar = fm.nlp.device
-            kind = {"acopf_ohm": 1, "dense_quadratic": 2}[name]
+            kind = nlp_kind(fm.nlp.device)
+            _, ipar, dpar = fm.nlp.device
             rows, nnz = fm.nlp.m, len(fm.nlp.rows)
             ipar, dpar = np.ascontiguousarray(ipar, np.int64), np.ascontiguousarray(dpar, np.float64)
         self._ev_keep = (fl, ipar, dpar)

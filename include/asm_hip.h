@@ -171,8 +171,35 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *   objective_scale              +1 MIN, -1 MAX, 0 FEASIBILITY (MOI_wrapper.jl:1037-1054)
  *   nlp_kind                     0 none; 1 Ohm's-law rows of the polar ACOPF model (4 rows and 20 values per branch;
  *                                ipar = [n_branch, va0, vm0, pf0, pt0, qf0, qt0, f_bus.., t_bus..], dpar = 8 coefficient
- *                                arrays); 2 dense quadratic rows g = A x + 1/2 Q x^2 (dpar = A then Q, row-major)
- * The affine / quadratic part is bit-identical to the host evaluator (no fused multiply-add, the reference's term order). */
+ *                                arrays); 2 dense quadratic rows g = A x + 1/2 Q x^2 (dpar = A then Q, row-major);
+ *                                3 expression block (below)
+ * The affine / quadratic part is bit-identical to the host evaluator (no fused multiply-add, the reference's term order).
+ *
+ * Expression block (nlp_kind = ASM_NLP_EXPR): the constraint and objective expressions of the reference's NLP block
+ * (@NLconstraint / @NLobjective, MOI.constraint_expr / MOI.objective_expr) as a tape.
+ *   R = nlp_rows constraint rows, then T >= 0 objective terms; each row / term is a list of nodes in SSA order, node = (op, a, b)
+ *   with a / b the indices of EARLIER nodes of the same row or term, counted from its first node (0-based); its value is its
+ *   last node.  Operands by op code:
+ *     ASM_OP_CONST  a = index into dpar                 ASM_OP_VAR   a = variable (0-based)
+ *     ASM_OP_ADD / SUB / MUL / DIV   a op b             ASM_OP_NEG   -a
+ *     ASM_OP_POWI   a ^ b, b an integer, 1 <= |b| <= ASM_EXPR_MAX_POWI (|b| - 1 products left to right; 1 / that for b < 0)
+ *     ASM_OP_SQRT / EXP / LOG / SIN / COS   of a        (b unused: 0)
+ *   ipar = [R, T, L, ptr[R+T+1], op[L], a[L], b[L]] (ptr[0] = 0, ptr[R+T] = L, every row / term at least one node);
+ *   dpar = the constants.
+ *   Jacobian pattern: each row's distinct variables in ascending order, rows in order; nlp_nnz = the sum of their counts and
+ *   the block's part of j_str (entries from jac_off[n_rows] on) must be exactly this pattern.
+ *   T > 0: the objective is the sum of the T terms in term order (from 0.0), times objective_scale; it replaces the function
+ *   store's objective row (has_objective of the reference's NLP block, MOI_wrapper.jl:809-861).  Gradient per variable: the
+ *   adjoints of its VAR nodes summed in (term, node) order, times objective_scale.  Jacobian value: the adjoints of the row's
+ *   VAR nodes of that variable, added in reverse node order.
+ *   Derivatives are reverse-mode with fixed formulas and no fused multiply-add: with ADD..POWI only, device values equal the
+ *   host twin (activesetmethods_amd/nlexpr.py) bit for bit.
+ *   A malformed tape (forward or out-of-row reference, unknown op, variable / constant out of range, bad POWI exponent, size
+ *   mismatch, a pattern that differs from j_str) is rejected with ASM_ERR_ARG and the handle keeps its previous evaluator. */
+enum { ASM_NLP_NONE = 0, ASM_NLP_ACOPF_OHM = 1, ASM_NLP_DENSE_QUADRATIC = 2, ASM_NLP_EXPR = 3 };
+enum { ASM_OP_CONST = 0, ASM_OP_VAR = 1, ASM_OP_ADD = 2, ASM_OP_SUB = 3, ASM_OP_MUL = 4, ASM_OP_DIV = 5, ASM_OP_NEG = 6, ASM_OP_POWI = 7,
+       ASM_OP_SQRT = 8, ASM_OP_EXP = 9, ASM_OP_LOG = 10, ASM_OP_SIN = 11, ASM_OP_COS = 12, ASM_OP_COUNT = 13 };
+enum { ASM_EXPR_MAX_POWI = 64 };
 int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const int64_t* aff_var, const double* aff_coef,
                    const int64_t* quad_ptr, const int64_t* q_v1, const int64_t* q_v2, const double* q_coef,
                    const double* constant, const int64_t* jac_off,
