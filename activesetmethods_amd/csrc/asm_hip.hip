@@ -29,6 +29,7 @@
 #include <numeric>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -197,6 +198,67 @@ struct FacBuf {
                                     // operation stops `band` rows below the panel's last column
 };
 
+// The device and pinned host buffers of one lifetime.  Each allocation is recorded with the field that points to it (and, for mapped host
+// memory, the field that holds its device address); release() frees them all and nulls those fields.  Sizes are max(count, 1) elements.
+class BufPool {
+  public:
+    enum Where { DEVICE, PINNED, MAPPED };      // MAPPED: pinned, host-mapped and coherent, its device address into *dev
+    BufPool() = default;
+    BufPool(const BufPool&) = delete;
+    BufPool& operator=(const BufPool&) = delete;
+    ~BufPool() { release(); }
+
+    // uninitialised
+    template <class T>
+    T* alloc(T*& f, int64_t count, Where where = DEVICE, T** dev = nullptr) {
+        const size_t bytes = std::max<int64_t>(count, 1) * sizeof(T);
+        void* p = nullptr;
+        if (where == DEVICE) HIPCHK(hipMalloc(&p, bytes));
+        else HIPCHK(hipHostMalloc(&p, bytes, where == MAPPED ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault));
+        own_.push_back({p, where != DEVICE, (void**)&f, (void**)dev});
+        f = (T*)p;
+        if (dev) HIPCHK(hipHostGetDevicePointer((void**)dev, p, 0));
+        return f;
+    }
+    // device buffer cleared by hipMemsetAsync on `s`, or by a synchronous hipMemset without a stream
+    template <class T>
+    T* zeroed(T*& f, int64_t count, hipStream_t s) {
+        HIPCHK(hipMemsetAsync((void*)alloc(f, count), 0, std::max<int64_t>(count, 1) * sizeof(T), s));
+        return f;
+    }
+    template <class T>
+    T* zeroed(T*& f, int64_t count) {
+        HIPCHK(hipMemset((void*)alloc(f, count), 0, std::max<int64_t>(count, 1) * sizeof(T)));
+        return f;
+    }
+    // device buffer holding src[0, count) (synchronous copy); zero_first: cleared by a synchronous hipMemset before
+    template <class T>
+    T* upload(T*& f, const std::remove_const_t<T>* src, int64_t count, bool zero_first = false) {
+        if (zero_first) zeroed(f, count);
+        else alloc(f, count);
+        if (count > 0) HIPCHK(hipMemcpy((void*)f, src, count * sizeof(T), hipMemcpyHostToDevice));
+        return f;
+    }
+    void release() {
+        for (const Buf& b : own_) {
+            if (b.host) (void)hipHostFree(b.p);
+            else (void)hipFree(b.p);
+            *b.field = nullptr;
+            if (b.dev) *b.dev = nullptr;
+        }
+        own_.clear();
+    }
+
+  private:
+    struct Buf {
+        void* p;
+        bool host;
+        void** field;
+        void** dev;
+    };
+    std::vector<Buf> own_;
+};
+
 // environment knobs of a handle, read once in asm_create (README.md lists them)
 struct HandleKnobs {
     int timing = 1;                 // ASM_HIP_TIMING: 0, 1 or 2, the initial asm_handle::timing
@@ -227,6 +289,9 @@ struct asm_handle {
     std::vector<hipEvent_t> la_events;
     std::string err;
     bool setup_done = false, inputs_ready = false;
+    // owners of the device / pinned buffers below, one per lifetime: the problem skeleton (until the next set-up), the null-space buffers
+    // sized by k (until the dimension outgrows them), the device evaluator (until the next asm_eval_setup)
+    BufPool mem, mem_nsk, mem_ev;
 
     // ---- problem (subproblem.jl:51-215) ----
     int64_t n = 0, m = 0, nnz = 0, nadj = 0, M = 0, Mp = 0, ldn = 0, ns = 0;
@@ -305,7 +370,6 @@ struct asm_handle {
     int ns_Zk = 0;                  // rows of the orthonormal basis of the previous LP still resident in d_nsG (0: none)
     int *d_nsqi = nullptr;          // sel | bpos | rpos | cnt
     double *d_nsq = nullptr;        // Csel | d, u, lam, v, w | pbar, tbar, u0, qh
-    std::vector<void*> ns_bufs;     // everything above, for release
     double* d_ipm_snap = nullptr;   // best-iterate safeguard: copy of the iterate at the end of the best interior-point stage so far
     double* d_ipm = nullptr;        // arena of the device-resident interior-point state
     int* d_ipm_i = nullptr;
@@ -321,7 +385,6 @@ struct asm_handle {
     FnStore ev_F;
     ExprTape ev_X{};                // nlp_kind ASM_NLP_EXPR: the tape and its workspace (asm_eval_kernels.hip.h)
     std::vector<int64_t> j_row_h, j_col_h;   // j_str as asm_sublp_setup received it (the expression block's pattern is checked against it)
-    std::vector<void*> ev_bufs;
     int64_t* d_ev_ipar = nullptr;
     double *d_ev_dpar = nullptr, *d_ev_x = nullptr, *d_ev_xt = nullptr, *d_ev_df = nullptr, *d_ev_E = nullptr, *d_ev_Et = nullptr, *d_ev_f = nullptr;
     double *d_ev_vecs = nullptr, *h_ev = nullptr;     // reduction inputs (lambda, multipliers, nu, slacks, p, bounds) / pinned staging
@@ -367,35 +430,23 @@ struct asm_handle {
 
 namespace {
 
-template <class T>
-void dmalloc(T** p, int64_t count) {
-    HIPCHK(hipMalloc((void**)p, std::max<int64_t>(count, 1) * sizeof(T)));
-}
-
 // after host -> device copies whose source must stay untouched until they have run: in a scenario batch the payload was copied when the
 // operation was recorded, nothing to wait for
 inline void h2d_done(asm_handle* h) {
     if (!asmb::in_fiber()) HIPCHK(hipStreamSynchronize(h->stream));
 }
 
-double* ns_dalloc(asm_handle* h, int64_t count) {
-    double* d = nullptr;
-    dmalloc(&d, count);
-    h->ns_bufs.push_back((void*)d);
-    HIPCHK(hipMemsetAsync(d, 0, std::max<int64_t>(count, 1) * sizeof(double), h->stream));
-    return d;
-}
-// buffers of one Cholesky factor of order <= N (pitch = N rounded up to 32) with the block inverses of the substitution kernels
-void ns_alloc_factor(asm_handle* h, FacBuf& f, int64_t N, int band_hint = 0) {
+// buffers of one Cholesky factor of order <= N (pitch = N rounded up to 32) with the block inverses of the substitution kernels, from `pool`
+void ns_alloc_factor(asm_handle* h, BufPool& pool, FacBuf& f, int64_t N, int band_hint = 0) {
     f.ld = round_up(std::max<int64_t>(N, 1), 32);
     f.wb = (f.ld <= 1024 || f.ld > 1536) ? 1024 : 512;      // one wide block (= the whole inverse) when the factor fits into it
     // a narrow band: the explicit inverse of a wide diagonal block is dense whatever the band, its cost grows with the square of the block
     // width - half the width is a quarter of the inverse (case300-sized S0, band 268 of 2 100: 16 % of a scenario batch's kernel time at 1024)
     if (band_hint > 0 && band_hint <= 512 && f.ld > 1024) f.wb = 512;
-    f.S = ns_dalloc(h, f.ld * f.ld);
-    f.Linv = ns_dalloc(h, (f.ld / ASM_NB + 1) * ASM_NB * ASM_NB);
-    f.Binv = ns_dalloc(h, (f.ld / f.wb + 1) * (int64_t)f.wb * f.wb);
-    f.BinvT = ns_dalloc(h, (f.ld / f.wb + 1) * (int64_t)f.wb * f.wb);
+    pool.zeroed(f.S, f.ld * f.ld, h->stream);
+    pool.zeroed(f.Linv, (f.ld / ASM_NB + 1) * ASM_NB * ASM_NB, h->stream);
+    pool.zeroed(f.Binv, (f.ld / f.wb + 1) * (int64_t)f.wb * f.wb, h->stream);
+    pool.zeroed(f.BinvT, (f.ld / f.wb + 1) * (int64_t)f.wb * f.wb, h->stream);
 }
 
 // =====================================================================================================
@@ -518,10 +569,7 @@ struct Dev {
         }
         if (A == h->d_Ah && (int64_t)h->ldn * h->Mp <= ((int64_t)1 << 27)) {
             // dense LP matrix of moderate size: through a transposed copy (made once per LP), one row-wise launch
-            if (!h->d_AhTg) {
-                dmalloc(&h->d_AhTg, h->ldn * h->Mp);
-                HIPCHK(hipMemsetAsync(h->d_AhTg, 0, h->ldn * h->Mp * sizeof(double), h->stream));
-            }
+            if (!h->d_AhTg) h->mem.zeroed(h->d_AhTg, h->ldn * h->Mp, h->stream);
             if (!h->ahTg_valid) {
                 hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), 0, h->stream, h->d_Ah,
                                    h->ldn, h->M, h->n, h->d_AhTg, h->Mp, (int64_t)-1);
@@ -1356,41 +1404,28 @@ struct Solver {
             // released and re-made; the carried basis goes with them
             if (h->knobs.verbose) std::fprintf(stderr, "[asm] null-space form: dimension %d exceeds the reserved %d - buffers re-allocated\n", k, h->ns_kcap);
             HIPCHK(hipStreamSynchronize(h->stream));
-            auto drop = [&](void* q) {
-                if (!q) return;
-                auto it = std::find(h->ns_bufs.begin(), h->ns_bufs.end(), q);
-                if (it != h->ns_bufs.end()) h->ns_bufs.erase(it);
-                (void)hipFree(q);
-            };
-            drop(h->d_nsR); drop(h->d_nsX); drop(h->d_nsG); drop(h->d_nsN0); drop(h->d_nsNp); drop(h->d_nsZT); drop(h->d_nsJ); drop(h->d_nsqi); drop(h->d_nsq);
-            for (FacBuf* f : {&h->ns_fN, &h->ns_fC}) { drop(f->S); drop(f->Linv); drop(f->Binv); drop(f->BinvT); *f = FacBuf(); }
-            h->d_nsR = h->d_nsX = h->d_nsG = h->d_nsN0 = h->d_nsNp = h->d_nsZT = h->d_nsq = nullptr;
-            h->d_nsJ = h->d_nsqi = nullptr;
+            h->mem_nsk.release();
+            h->ns_fN = FacBuf(); h->ns_fC = FacBuf();
             h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0;
         }
+        BufPool& P = h->mem_nsk;
         const int cap = (int)round_up(k + k / 4 + 64, 64);
-        h->d_nsR = ns_dalloc(h, (int64_t)cap * h->ns_nEp);
-        h->d_nsX = ns_dalloc(h, (int64_t)cap * h->ns_nEp);
-        h->d_nsG = ns_dalloc(h, (int64_t)cap * h->ns_ldg);
-        ns_alloc_factor(h, h->ns_fN, cap);
+        P.zeroed(h->d_nsR, (int64_t)cap * h->ns_nEp, h->stream);
+        P.zeroed(h->d_nsX, (int64_t)cap * h->ns_nEp, h->stream);
+        P.zeroed(h->d_nsG, (int64_t)cap * h->ns_ldg, h->stream);
+        ns_alloc_factor(h, P, h->ns_fN, cap);
         h->ns_fN.small = true;
-        h->d_nsN0 = ns_dalloc(h, h->ns_fN.ld * h->ns_fN.ld);
-        h->d_nsNp = ns_dalloc(h, NS_MAX_SPLIT * h->ns_fN.ld * h->ns_fN.ld);       // split-K slices of the reduced Newton matrix
-        h->d_nsZT = ns_dalloc(h, h->ldn * h->ns_fN.ld);        // transposed copy of the basis rows (right operand of the orthonormalisation product)
-        int* dj = nullptr;
-        dmalloc(&dj, cap);
-        h->ns_bufs.push_back((void*)dj);
-        h->d_nsJ = dj;
+        P.zeroed(h->d_nsN0, h->ns_fN.ld * h->ns_fN.ld, h->stream);
+        P.zeroed(h->d_nsNp, NS_MAX_SPLIT * h->ns_fN.ld * h->ns_fN.ld, h->stream);       // split-K slices of the reduced Newton matrix
+        P.zeroed(h->d_nsZT, h->ldn * h->ns_fN.ld, h->stream);        // transposed copy of the basis rows (right operand of the orthonormalisation product)
+        P.alloc(h->d_nsJ, cap);
         h->ns_kcap = cap;
         // active-set solves in reduced coordinates: up to 2 cap constraints (an over-determined working set has more than k)
         h->ns_ccap = (int)std::min<int64_t>(2 * cap, h->Mp);
-        ns_alloc_factor(h, h->ns_fC, h->ns_ccap);
+        ns_alloc_factor(h, P, h->ns_fC, h->ns_ccap);
         h->ns_fC.small = true;
-        int* qi = nullptr;
-        dmalloc(&qi, (int64_t)h->ns_ccap + h->ldn + h->ns_nIp + 16);
-        h->ns_bufs.push_back((void*)qi);
-        h->d_nsqi = qi;
-        h->d_nsq = ns_dalloc(h, (int64_t)h->ns_ccap * h->ns_fN.ld + 5 * (int64_t)h->ns_ccap + h->ldn + h->Mp + 2 * h->ns_fN.ld + 64);
+        P.alloc(h->d_nsqi, (int64_t)h->ns_ccap + h->ldn + h->ns_nIp + 16);
+        P.zeroed(h->d_nsq, (int64_t)h->ns_ccap * h->ns_fN.ld + 5 * (int64_t)h->ns_ccap + h->ldn + h->Mp + 2 * h->ns_fN.ld + 64, h->stream);
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     // In place  Zt = L^-1 Zt  with the k x k factor just made in h->ns_fN.  When the factor fits into one wide block the explicit inverse of
@@ -1527,7 +1562,7 @@ struct Solver {
             ns_was_cold = true;
             // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main matrix buffer,
             // guarded Cholesky of T in index order with the absolute thresholds NS_SEL_THR in turn until exactly k columns are kept
-            if (!h->d_nsYt) h->d_nsYt = ns_dalloc(h, (int64_t)h->ldn * h->ns_nEp + (int64_t)h->ldn * h->ns_nEp);
+            if (!h->d_nsYt) h->mem.zeroed(h->d_nsYt, (int64_t)h->ldn * h->ns_nEp + (int64_t)h->ldn * h->ns_nEp, h->stream);
             double* Yr = h->d_nsYt;                                  // right-hand sides, then garbage
             double* Yt = h->d_nsYt + (int64_t)h->ldn * h->ns_nEp;   // L0^-1 a_j as rows
             const double* vals = dev.sparse_vals(h->d_Ah);
@@ -2717,62 +2752,29 @@ int row_kind(double lb, double ub) {
     return 9;
 }
 
+// releases every buffer of the handle and resets the state that describes them
 void free_device(asm_handle* h) {
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
-    F(h->d_perm); F(h->d_ustart); F(h->d_uoff); F(h->d_adjoff);
-    F(h->d_dE); F(h->d_J); F(h->d_Ah); F(h->d_S); F(h->d_c); F(h->d_rho); F(h->d_theta); F(h->d_diag); F(h->d_diag0);
-    F(h->d_vecN); F(h->d_vecM); F(h->d_vecM2); F(h->d_partial); F(h->d_idx); F(h->d_Linv); F(h->d_Binv); F(h->d_wpart); F(h->d_BinvT); F(h->d_wt);
-    h->d_Binv = h->d_wpart = h->d_BinvT = h->d_wt = nullptr; F(h->d_ipm); F(h->d_ipm_i); F(h->d_nz);
-    F(h->d_ipm_snap); h->d_ipm_snap = nullptr;
-    h->d_nz = nullptr; h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
-    F(h->d_idxI); F(h->d_rdI); F(h->d_rce); F(h->d_rze); F(h->d_sdiag);
-    F(h->d_redpart); F(h->d_redcnt); h->d_redpart = nullptr; h->d_redcnt = nullptr;
-    F(h->d_AhTg); h->d_AhTg = nullptr; h->ahTg_valid = false;
-    h->d_idxI = nullptr; h->d_rdI = h->d_rce = h->d_rze = h->d_sdiag = nullptr;
-    F(h->d_AhT); F(h->d_cdinv); F(h->d_cth); F(h->d_cu); F(h->d_ct); F(h->d_cv); F(h->d_cw); F(h->d_nzT);
-    h->d_AhT = h->d_cdinv = h->d_cth = h->d_cu = h->d_ct = h->d_cv = h->d_cw = nullptr; h->d_nzT = nullptr;
+    h->mem.release(); h->mem_nsk.release(); h->mem_ev.release();
+    h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
+    h->ahTg_valid = false;
     h->col_capable = h->ahT_valid = h->nzT_valid = false;
-    F(h->d_sp_ptr); F(h->d_sp_col); F(h->d_sc_ptr); F(h->d_sc_row); F(h->d_sc_pos); F(h->d_sp_off); F(h->d_spv_Ah); F(h->d_spv_J);
-    h->d_sp_ptr = h->d_sp_col = h->d_sc_ptr = h->d_sc_row = h->d_sc_pos = nullptr;
-    h->d_sp_off = nullptr; h->d_spv_Ah = h->d_spv_J = nullptr;
     h->sp_ok = h->spv_Ah_valid = h->spv_J_valid = false; h->sp_nnz = 0;
-    if (h->h_scal) (void)hipHostFree(h->h_scal);
-    if (h->h_seq) (void)hipHostFree(h->h_seq);
-    h->d_ipm = nullptr; h->d_ipm_i = nullptr; h->h_scal = nullptr; h->h_seq = nullptr; h->d_hscal = nullptr; h->d_hseq = nullptr;
-    F(h->d_pflags); F(h->d_ptmo);
-    h->d_pflags = h->d_ptmo = nullptr;
-    for (void* q : h->ns_bufs) F(q);
-    h->ns_bufs.clear();
-    h->ns_cap = false; h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0; h->ns_fC = FacBuf(); h->d_nsqi = nullptr; h->d_nsq = nullptr;
-    h->d_nsEidx = h->d_nsEpos = h->d_nsIidx = h->d_nsIpos = h->d_nsJ = h->d_nscnt = nullptr;
-    h->d_nsS0pairs = nullptr; h->ns_npairs = 0;
-    h->ns_f0 = FacBuf(); h->ns_fN = FacBuf();
-    h->d_nsLt = h->d_nsR = h->d_nsX = h->d_nsG = h->d_nsth = h->d_nsFm = h->d_nsv = h->d_nsYt = h->d_nsN0 = h->d_nsZT = nullptr;
-    F(h->d_as); F(h->d_as_i);
-    if (h->h_ascnt) (void)hipHostFree(h->h_ascnt);
-    if (h->h_asscal) (void)hipHostFree(h->h_asscal);
-    h->d_as = nullptr; h->d_as_i = nullptr; h->h_ascnt = nullptr; h->h_asscal = nullptr;
-    for (void* q : h->ev_bufs) F(q);
-    h->ev_bufs.clear();
-    h->ev_ready = false; h->d_ev_ipar = nullptr;
-    h->d_ev_dpar = h->d_ev_x = h->d_ev_xt = h->d_ev_df = h->d_ev_E = h->d_ev_Et = h->d_ev_f = h->d_ev_vecs = nullptr;
-    if (h->h_ev) (void)hipHostFree(h->h_ev);
-    h->h_ev = nullptr;
-    F(h->d_Zbuf); F(h->d_nsu); F(h->d_nsdots);
-    if (h->h_nsdots) (void)hipHostFree(h->h_nsdots);
-    h->d_Zbuf = h->d_nsu = h->d_nsdots = h->h_nsdots = nullptr;
-    if (h->h_pin) (void)hipHostFree(h->h_pin);
-    if (h->h_up) (void)hipHostFree(h->h_up);
-    h->h_up = nullptr;
-    if (h->h_dl) (void)hipHostFree(h->h_dl);
-    F(h->d_dl);
-    h->h_dl = h->d_dl = nullptr;
-    h->d_perm = h->d_ustart = h->d_uoff = h->d_adjoff = nullptr;
-    h->d_dE = h->d_J = h->d_Ah = h->d_S = h->d_c = h->d_rho = h->d_theta = h->d_diag = h->d_diag0 = nullptr;
-    h->d_vecN = h->d_vecM = h->d_vecM2 = h->d_partial = nullptr;
-    h->d_Linv = nullptr;
-    h->d_idx = nullptr;
-    h->h_pin = nullptr;
+    h->ns_cap = false; h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0; h->ns_npairs = 0;
+    h->ns_f0 = FacBuf(); h->ns_fN = FacBuf(); h->ns_fC = FacBuf(); h->test_fac = FacBuf();
+    h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
+    h->ev_ready = false;
+}
+
+// forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
+// the null-space form stay
+void reset_warm(asm_handle* h, bool keep_ns_J) {
+    std::vector<int> J;
+    if (keep_ns_J) J.swap(h->hint[0].ns_J);
+    h->warm[0] = ActiveSet(); h->warm[1] = ActiveSet();
+    h->hint[0] = SolveHint(); h->hint[1] = SolveHint();
+    h->hint[0].ns_J.swap(J);
+    h->ns_Zk = 0;
+    h->hint[1].prefer_ref = true;     // restoration LPs usually have a non-unique optimum (oracle/subproblem.py)
 }
 
 void check_panel_timeout(asm_handle* h) {
@@ -2885,65 +2887,49 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         }
     }
 
-    dmalloc(&h->d_dE, nnz);
-    dmalloc(&h->d_J, h->Mp * h->ldn);
-    dmalloc(&h->d_Ah, h->Mp * h->ldn);
-    dmalloc(&h->d_S, h->Mp * h->Mp);
-    dmalloc(&h->d_c, h->ldn); dmalloc(&h->d_rho, h->Mp); dmalloc(&h->d_theta, h->ldn);
-    dmalloc(&h->d_diag, h->Mp); dmalloc(&h->d_diag0, h->Mp);
-    dmalloc(&h->d_vecN, h->ldn); dmalloc(&h->d_vecM, h->Mp); dmalloc(&h->d_vecM2, h->Mp);
-    dmalloc(&h->d_partial, (int64_t)ASM_TMAXCHUNKS * h->ldn);
-    dmalloc(&h->d_idx, h->Mp);
-    dmalloc(&h->d_Linv, (h->Mp / ASM_NB + 1) * ASM_NB * ASM_NB);
-    dmalloc(&h->d_pflags, ASM_PNL_FLAGS);
-    dmalloc(&h->d_ptmo, 4);
-    HIPCHK(hipMemsetAsync(h->d_ptmo, 0, 4 * sizeof(unsigned), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_pflags, 0, ASM_PNL_FLAGS * sizeof(unsigned), h->stream));
+    BufPool& P = h->mem;
+    const hipStream_t s = h->stream;
+    P.alloc(h->d_dE, nnz);
+    P.zeroed(h->d_J, h->Mp * h->ldn, s);
+    P.zeroed(h->d_Ah, h->Mp * h->ldn, s);
+    P.alloc(h->d_S, h->Mp * h->Mp);
+    P.alloc(h->d_c, h->ldn); P.alloc(h->d_rho, h->Mp); P.alloc(h->d_theta, h->ldn);
+    P.alloc(h->d_diag, h->Mp); P.alloc(h->d_diag0, h->Mp);
+    P.zeroed(h->d_vecN, h->ldn, s); P.zeroed(h->d_vecM, h->Mp, s); P.alloc(h->d_vecM2, h->Mp);
+    P.alloc(h->d_partial, (int64_t)ASM_TMAXCHUNKS * h->ldn);
+    P.alloc(h->d_idx, h->Mp);
+    P.alloc(h->d_Linv, (h->Mp / ASM_NB + 1) * ASM_NB * ASM_NB);
+    P.zeroed(h->d_pflags, ASM_PNL_FLAGS, s);
+    P.zeroed(h->d_ptmo, 4, s);
     h->wb = h->M > 1536 ? 1024 : 512;      // wide-block width of the triangular solves (k_wtrsv_*<WB>)
     if (h->M >= RED_MIN_M) {
-        dmalloc(&h->d_idxI, h->Mp); dmalloc(&h->d_rdI, h->Mp); dmalloc(&h->d_rce, h->Mp); dmalloc(&h->d_rze, h->Mp); dmalloc(&h->d_sdiag, h->Mp);
+        P.alloc(h->d_idxI, h->Mp); P.alloc(h->d_rdI, h->Mp); P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); P.alloc(h->d_sdiag, h->Mp);
     }
     // column form of the restoration-phase Newton system (every row owns a slack column there): n x n instead of M x M
     h->col_capable = h->M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)h->M && n <= h->Mp;
     if (h->col_capable) {
         h->ldT = round_up(h->M, 32);
-        dmalloc(&h->d_AhT, n * h->ldT);
-        HIPCHK(hipMemsetAsync(h->d_AhT, 0, n * h->ldT * sizeof(double), h->stream));
-        dmalloc(&h->d_cdinv, h->ldT); dmalloc(&h->d_cth, h->ldn); dmalloc(&h->d_cu, h->Mp); dmalloc(&h->d_ct, h->ldn);
-        dmalloc(&h->d_cv, h->ldn); dmalloc(&h->d_cw, h->Mp);
-        HIPCHK(hipMemsetAsync(h->d_cdinv, 0, h->ldT * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_cth, 0, h->ldn * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_cu, 0, h->Mp * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_ct, 0, h->ldn * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_cv, 0, h->ldn * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_cw, 0, h->Mp * sizeof(double), h->stream));
-        dmalloc(&h->d_nzT, (n / 32 + 2) * (h->ldT / ASM_KC + 1));
+        P.zeroed(h->d_AhT, n * h->ldT, s);
+        P.zeroed(h->d_cdinv, h->ldT, s); P.zeroed(h->d_cth, h->ldn, s); P.zeroed(h->d_cu, h->Mp, s); P.zeroed(h->d_ct, h->ldn, s);
+        P.zeroed(h->d_cv, h->ldn, s); P.zeroed(h->d_cw, h->Mp, s);
+        P.alloc(h->d_nzT, (n / 32 + 2) * (h->ldT / ASM_KC + 1));
     }
-    dmalloc(&h->d_Binv, (h->Mp / h->wb + 1) * (int64_t)h->wb * h->wb);
-    dmalloc(&h->d_BinvT, (h->Mp / h->wb + 1) * (int64_t)h->wb * h->wb);
-    dmalloc(&h->d_wpart, (h->Mp / ASM_WBROWS + 2) * (int64_t)1024);
-    dmalloc(&h->d_wt, 1024);
+    P.alloc(h->d_Binv, (h->Mp / h->wb + 1) * (int64_t)h->wb * h->wb);
+    P.alloc(h->d_BinvT, (h->Mp / h->wb + 1) * (int64_t)h->wb * h->wb);
+    P.alloc(h->d_wpart, (h->Mp / ASM_WBROWS + 2) * (int64_t)1024);
+    P.alloc(h->d_wt, 1024);
     h->nz_half = (h->Mp / 32 + 1) * (h->ldn / ASM_KC + 1);
-    dmalloc(&h->d_nz, 2 * h->nz_half);
+    P.alloc(h->d_nz, 2 * h->nz_half);
     if (h->sp_nnz > 0) {
-        dmalloc(&h->d_sp_ptr, h->M + 1); dmalloc(&h->d_sp_col, h->sp_nnz); dmalloc(&h->d_sp_off, h->sp_nnz);
-        dmalloc(&h->d_sc_ptr, n + 1); dmalloc(&h->d_sc_row, h->sp_nnz); dmalloc(&h->d_sc_pos, h->sp_nnz);
-        dmalloc(&h->d_spv_Ah, h->sp_nnz); dmalloc(&h->d_spv_J, h->sp_nnz);
-        HIPCHK(hipMemcpy(h->d_sp_ptr, sp_ptr.data(), sp_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sp_col, sp_col.data(), sp_col.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sp_off, sp_off.data(), sp_off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sc_ptr, sc_ptr.data(), sc_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sc_row, sc_row.data(), sc_row.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sc_pos, sc_pos.data(), sc_pos.size() * sizeof(int), hipMemcpyHostToDevice));
+        P.upload(h->d_sp_ptr, sp_ptr.data(), h->M + 1); P.upload(h->d_sp_col, sp_col.data(), h->sp_nnz); P.upload(h->d_sp_off, sp_off.data(), h->sp_nnz);
+        P.upload(h->d_sc_ptr, sc_ptr.data(), n + 1); P.upload(h->d_sc_row, sc_row.data(), h->sp_nnz); P.upload(h->d_sc_pos, sc_pos.data(), h->sp_nnz);
+        P.alloc(h->d_spv_Ah, h->sp_nnz); P.alloc(h->d_spv_J, h->sp_nnz);
         h->sp_ok = true;
     }
     h->nsp = round_up(std::max<int64_t>(h->ns, 1), 16);
     {
-        int64_t nd = 24 * h->ldn + 23 * h->Mp + 16 * h->nsp + 64;
-        dmalloc(&h->d_ipm, nd);
-        HIPCHK(hipMemsetAsync(h->d_ipm, 0, nd * sizeof(double), h->stream));
-        dmalloc(&h->d_ipm_snap, 6 * h->ldn + 3 * h->Mp + 3 * h->nsp);
-        dmalloc(&h->d_ipm_i, 3 * h->Mp + h->nsp);
+        P.zeroed(h->d_ipm, 24 * h->ldn + 23 * h->Mp + 16 * h->nsp + 64, s);
+        P.alloc(h->d_ipm_snap, 6 * h->ldn + 3 * h->Mp + 3 * h->nsp);
         std::vector<int> iv(3 * h->Mp + h->nsp, -1);
         for (int64_t i = 0; i < h->M; ++i) iv[i] = h->rtype[i];
         for (int64_t k = 0; k < h->ns; ++k) {
@@ -2951,28 +2937,21 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
             if (iv[h->Mp + r_] < 0) iv[h->Mp + r_] = (int)k; else iv[2 * h->Mp + r_] = (int)k;
             iv[3 * h->Mp + k] = r_;
         }
-        HIPCHK(hipMemcpy(h->d_ipm_i, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice));
-        dmalloc(&h->d_redpart, IPM_RED_MAXWG * IPM_RED_SLOTS);
-        dmalloc(&h->d_redcnt, 4);
-        HIPCHK(hipMemsetAsync(h->d_redcnt, 0, 4 * sizeof(unsigned), h->stream));
-        HIPCHK(hipHostMalloc((void**)&h->h_scal, 64 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostMalloc((void**)&h->h_seq, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&h->d_hscal, h->h_scal, 0));
-        HIPCHK(hipHostGetDevicePointer((void**)&h->d_hseq, h->h_seq, 0));
+        P.upload(h->d_ipm_i, iv.data(), (int64_t)iv.size());
+        P.alloc(h->d_redpart, IPM_RED_MAXWG * IPM_RED_SLOTS);
+        P.zeroed(h->d_redcnt, 4, s);
+        P.alloc(h->h_scal, 64, BufPool::MAPPED, &h->d_hscal);
+        P.alloc(h->h_seq, 16, BufPool::MAPPED, &h->d_hseq);
         *h->h_seq = 0;
         h->scal_seq = 0;
-        const int64_t nas = 17 * h->ldn + 17 * h->Mp + 4 * h->nsp + 64, nasi = 6 * (h->Mp + h->ldn + h->nsp) + 3 * h->Mp + 2 * h->ldn + 64;
-        dmalloc(&h->d_as, nas);
-        HIPCHK(hipMemsetAsync(h->d_as, 0, nas * sizeof(double), h->stream));
-        dmalloc(&h->d_as_i, nasi);
-        HIPCHK(hipMemsetAsync(h->d_as_i, 0, nasi * sizeof(int), h->stream));
-        HIPCHK(hipHostMalloc((void**)&h->h_ascnt, 64 * sizeof(int)));
-        HIPCHK(hipHostMalloc((void**)&h->h_asscal, 64 * sizeof(double)));
-        dmalloc(&h->d_Zbuf, (int64_t)(FACE_STEPS + 1) * h->ldn);
-        HIPCHK(hipMemsetAsync(h->d_Zbuf, 0, (int64_t)(FACE_STEPS + 1) * h->ldn * sizeof(double), h->stream));
-        dmalloc(&h->d_nsu, FACE_STEPS + 8);
-        dmalloc(&h->d_nsdots, FACE_STEPS + 8);
-        HIPCHK(hipHostMalloc((void**)&h->h_nsdots, (FACE_STEPS + 8) * sizeof(double)));
+        P.zeroed(h->d_as, 17 * h->ldn + 17 * h->Mp + 4 * h->nsp + 64, s);
+        P.zeroed(h->d_as_i, 6 * (h->Mp + h->ldn + h->nsp) + 3 * h->Mp + 2 * h->ldn + 64, s);
+        P.alloc(h->h_ascnt, 64, BufPool::PINNED);
+        P.alloc(h->h_asscal, 64, BufPool::PINNED);
+        P.zeroed(h->d_Zbuf, (int64_t)(FACE_STEPS + 1) * h->ldn, s);
+        P.alloc(h->d_nsu, FACE_STEPS + 8);
+        P.alloc(h->d_nsdots, FACE_STEPS + 8);
+        P.alloc(h->h_nsdots, FACE_STEPS + 8, BufPool::PINNED);
     }
     // null-space form of the normal-phase Newton system: static part (index lists, factor of S0, work vectors); the buffers
     // sized by the null-space dimension k are allocated by the first LP that uses the form (Solver::ns_reserve)
@@ -2989,14 +2968,6 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
                 if (h->rtype[i] == 0) { epos[i] = (int)eidx.size(); eidx.push_back((int)i); }
                 else { ipos[i] = (int)iidx.size(); iidx.push_back((int)i); }
             }
-            auto ialloc = [&](const std::vector<int>& v, int64_t cnt) {
-                int* d = nullptr;
-                dmalloc(&d, cnt);
-                h->ns_bufs.push_back((void*)d);
-                HIPCHK(hipMemset(d, 0, std::max<int64_t>(cnt, 1) * sizeof(int)));
-                if (!v.empty()) HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-                return d;
-            };
             // the equality rows in reverse Cuthill-McKee order of their coupling graph: S0 = A_EF A_EF' and its factor are banded in that order
             int s0_band = 0;
             std::vector<int> s0_pairs;
@@ -3008,24 +2979,24 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
                 for (int q = 0; q < nE; ++q) epos[eidx[q]] = q;
             }
             h->ns_eidx_h = eidx;
-            h->d_nsEidx = ialloc(eidx, nE); h->d_nsEpos = ialloc(epos, h->M); h->d_nsIidx = ialloc(iidx, h->ns_nI); h->d_nsIpos = ialloc(ipos, h->M);
-            h->d_nscnt = ialloc({}, 16);
+            P.upload(h->d_nsEidx, eidx.data(), nE, true); P.upload(h->d_nsEpos, epos.data(), h->M, true);
+            P.upload(h->d_nsIidx, iidx.data(), h->ns_nI, true); P.upload(h->d_nsIpos, ipos.data(), h->M, true);
+            P.zeroed(h->d_nscnt, 16);
             const int f0_band = 2 * (int64_t)s0_band >= nE ? 0 : std::max(s0_band, 1);
-            ns_alloc_factor(h, h->ns_f0, h->ns_nEp, f0_band);
+            ns_alloc_factor(h, P, h->ns_f0, h->ns_nEp, f0_band);
             h->ns_f0.band = f0_band;
             if (h->ns_f0.band > 0) {            // S0 is then built entry by entry from its structural pattern (k_ns_s0_sparse)
                 h->ns_npairs = (int64_t)s0_pairs.size() / 2;
-                h->d_nsS0pairs = ialloc(s0_pairs, (int64_t)s0_pairs.size());
+                P.upload(h->d_nsS0pairs, s0_pairs.data(), (int64_t)s0_pairs.size(), true);
             }
-            h->d_nsLt = ns_dalloc(h, (int64_t)h->ns_nEp * h->ns_nEp);
-            h->d_nsth = ns_dalloc(h, h->ns_ldg);
-            h->d_nsFm = ns_dalloc(h, h->ldn);
-            h->d_nsv = ns_dalloc(h, 11 * h->ldn + 3 * h->Mp + 2 * h->ns_nEp);
+            P.zeroed(h->d_nsLt, (int64_t)h->ns_nEp * h->ns_nEp, s);
+            P.zeroed(h->d_nsth, h->ns_ldg, s);
+            P.zeroed(h->d_nsFm, h->ldn, s);
+            P.zeroed(h->d_nsv, 11 * h->ldn + 3 * h->Mp + 2 * h->ns_nEp, s);
         }
     }
     // row order of the factorisations (see asm_handle::row_band)
-    h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->main_band_cur = 0;
-    h->d_rowperm = h->d_rowpos = h->d_rowpairs = h->d_cpos = nullptr;
+    h->main_band_cur = 0;
     if (h->sp_ok && h->M >= 256) {
         std::vector<int> all(h->M), pairs_pos;
         for (int64_t i = 0; i < h->M; ++i) all[i] = (int)i;
@@ -3038,20 +3009,12 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
             for (int64_t q = 0; q < h->M; ++q) pos[ord[q]] = (int)q;
             for (size_t t = 0; t < pairs_pos.size(); ++t) pairs[t] = ord[pairs_pos[t]];
             h->n_rowpairs = (int64_t)pairs.size() / 2;
-            auto up = [&](const std::vector<int>& v) {
-                int* d = nullptr;
-                dmalloc(&d, (int64_t)v.size());
-                h->ns_bufs.push_back((void*)d);
-                HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-                return d;
-            };
-            h->d_rowperm = up(ord); h->d_rowpos = up(pos); h->d_rowpairs = up(pairs);
-            h->d_cpos = up(pos);                      // place of every row in the current row list of the interior-point factor (rewritten per iteration)
-            if (!h->d_rce) { dmalloc(&h->d_rce, h->Mp); dmalloc(&h->d_rze, h->Mp); }
+            P.upload(h->d_rowperm, ord.data(), h->M); P.upload(h->d_rowpos, pos.data(), h->M); P.upload(h->d_rowpairs, pairs.data(), (int64_t)pairs.size());
+            P.upload(h->d_cpos, pos.data(), h->M);      // place of every row in the current row list of the interior-point factor (rewritten per iteration)
+            if (!h->d_rce) { P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); }
         }
     }
     // column order of the column form (K = Th + A' D^-1 A couples two columns when they share a row)
-    h->col_band = 0; h->n_colpairs = 0; h->d_colperm = h->d_colpos = h->d_colpairs = nullptr;
     if (h->sp_ok && h->col_capable && n >= 256) {
         std::vector<int> all(n), pairs_pos;
         for (int64_t j = 0; j < n; ++j) all[j] = (int)j;
@@ -3063,42 +3026,26 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
             for (int64_t q = 0; q < n; ++q) pos[ord[q]] = (int)q;
             for (size_t t = 0; t < pairs_pos.size(); ++t) pairs[t] = ord[pairs_pos[t]];
             h->n_colpairs = (int64_t)pairs.size() / 2;
-            auto up = [&](const std::vector<int>& v) {
-                int* d = nullptr;
-                dmalloc(&d, (int64_t)v.size());
-                h->ns_bufs.push_back((void*)d);
-                HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-                return d;
-            };
-            h->d_colperm = up(ord); h->d_colpos = up(pos); h->d_colpairs = up(pairs);
-            if (!h->d_rce) { dmalloc(&h->d_rce, h->Mp); dmalloc(&h->d_rze, h->Mp); }
+            P.upload(h->d_colperm, ord.data(), n); P.upload(h->d_colpos, pos.data(), n); P.upload(h->d_colpairs, pairs.data(), (int64_t)pairs.size());
+            if (!h->d_rce) { P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); }
         }
     }
     h->pin_len = std::max(std::max(h->ldn, h->Mp), h->nsp);
-    HIPCHK(hipHostMalloc((void**)&h->h_pin, 2 * h->pin_len * sizeof(double)));
-    HIPCHK(hipHostMalloc((void**)&h->h_up, (3 * h->ldn + h->Mp + 3 * h->nsp + 16) * sizeof(double)));
+    P.alloc(h->h_pin, 2 * h->pin_len, BufPool::PINNED);
+    P.alloc(h->h_up, 3 * h->ldn + h->Mp + 3 * h->nsp + 16, BufPool::PINNED);
     std::memset(h->h_up, 0, (3 * h->ldn + h->Mp + 3 * h->nsp + 16) * sizeof(double));
     {
         const int64_t dl = 2 * h->ldn + 2 * h->Mp + h->nsp + (h->ldn + h->Mp + h->nsp + 1) / 2 + 16;
-        dmalloc(&h->d_dl, dl);
-        HIPCHK(hipHostMalloc((void**)&h->h_dl, dl * sizeof(double)));
+        P.alloc(h->d_dl, dl);
+        P.alloc(h->h_dl, dl, BufPool::PINNED);
     }
-    HIPCHK(hipMemsetAsync(h->d_J, 0, h->Mp * h->ldn * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_Ah, 0, h->Mp * h->ldn * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_vecN, 0, h->ldn * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
     if (!dense) {
-        dmalloc(&h->d_perm, nnz); dmalloc(&h->d_ustart, h->nu + 1); dmalloc(&h->d_uoff, h->nu); dmalloc(&h->d_adjoff, h->nu);
-        HIPCHK(hipMemcpy(h->d_perm, perm.data(), nnz * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ustart, ustart.data(), (h->nu + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_uoff, uoff.data(), h->nu * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_adjoff, adjoff.data(), h->nu * sizeof(int64_t), hipMemcpyHostToDevice));
+        P.upload(h->d_perm, perm.data(), nnz); P.upload(h->d_ustart, ustart.data(), h->nu + 1);
+        P.upload(h->d_uoff, uoff.data(), h->nu); P.upload(h->d_adjoff, adjoff.data(), h->nu);
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->warm[0] = ActiveSet(); h->warm[1] = ActiveSet(); h->last = ActiveSet();
-    h->hint[0] = SolveHint(); h->hint[1] = SolveHint();
-    h->ns_Zk = 0;
-    h->hint[1].prefer_ref = true;     // restoration LPs usually have a non-unique optimum (oracle/subproblem.py)
+    h->last = ActiveSet();
+    reset_warm(h, false);
     std::memset(&h->stats, 0, sizeof(h->stats));
     h->setup_done = true;
 }
@@ -3334,14 +3281,6 @@ int guarded(asm_handle* h, F&& fn) {
 }  // namespace
 
 namespace {
-template <class T>
-T* ev_upload(asm_handle* h, const T* src, int64_t count) {
-    T* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, std::max<int64_t>(count, 1) * sizeof(T)));
-    h->ev_bufs.push_back((void*)d);
-    if (count > 0) HIPCHK(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
 // kernels of one evaluation at the point in `xd`: values into Ed (m), objective into fd, optionally gradient / Jacobian values
 // `ntrial` > 1 (values only): the trial points of a batched line search, xd / Ed / fd advancing by ldx / ldE / 1 per point
 void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool full, int ntrial = 1, int64_t ldx = 0, int64_t ldE = 0) {
@@ -3461,12 +3400,8 @@ int asm_sublp_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, 
         }
         // the retained working sets and the basis Z belong to the old instance; the basis COLUMNS of the null-space form are kept - the
         // pattern is the same, and a set that no longer spans null(A_EF) is detected and re-selected by the next LP (Solver::ns_setup)
-        std::vector<int> keepJ = h->hint[0].ns_J;
-        h->warm[0] = ActiveSet(); h->warm[1] = ActiveSet(); h->last = ActiveSet();
-        h->hint[0] = SolveHint(); h->hint[1] = SolveHint();
-        h->hint[0].ns_J.swap(keepJ);
-        h->ns_Zk = 0;
-        h->hint[1].prefer_ref = true;
+        h->last = ActiveSet();
+        reset_warm(h, true);
         h->inputs_ready = false;
     });
 }
@@ -3519,12 +3454,7 @@ int asm_sublp_active_set(const asm_handle* h, int32_t* row_state, int32_t* bound
 
 int asm_sublp_reset_warm(asm_handle* h) {
     if (!h) return ASM_ERR_ARG;
-    h->warm[0] = ActiveSet();
-    h->warm[1] = ActiveSet();
-    h->hint[0] = SolveHint();
-    h->hint[1] = SolveHint();
-    h->ns_Zk = 0;
-    h->hint[1].prefer_ref = true;
+    reset_warm(h, false);
     return ASM_OK;
 }
 
@@ -3717,43 +3647,42 @@ int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const 
         ExprHost xh;
         if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
         HIPCHK(hipSetDevice(h->device));
-        for (void* q : h->ev_bufs) (void)hipFree(q);
-        h->ev_bufs.clear();
+        BufPool& P = h->mem_ev;
+        P.release();
         FnStore& F = h->ev_F;
         F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
         const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
-        F.aff_ptr = ev_upload(h, aff_ptr, n_rows + 2); F.aff_var = ev_upload(h, aff_var, na); F.aff_coef = ev_upload(h, aff_coef, na);
-        F.quad_ptr = ev_upload(h, quad_ptr, n_rows + 2); F.q_v1 = ev_upload(h, q_v1, nq); F.q_v2 = ev_upload(h, q_v2, nq); F.q_coef = ev_upload(h, q_coef, nq);
-        F.constant = ev_upload(h, constant, n_rows + 1); F.jac_off = ev_upload(h, jac_off, n_rows + 1);
-        F.g_ptr = ev_upload(h, g_ptr, h->n + 1); F.g_kind = ev_upload(h, g_kind, ng); F.g_coef = ev_upload(h, g_coef, ng); F.g_other = ev_upload(h, g_other, ng);
+        P.upload(F.aff_ptr, aff_ptr, n_rows + 2); P.upload(F.aff_var, aff_var, na); P.upload(F.aff_coef, aff_coef, na);
+        P.upload(F.quad_ptr, quad_ptr, n_rows + 2); P.upload(F.q_v1, q_v1, nq); P.upload(F.q_v2, q_v2, nq); P.upload(F.q_coef, q_coef, nq);
+        P.upload(F.constant, constant, n_rows + 1); P.upload(F.jac_off, jac_off, n_rows + 1);
+        P.upload(F.g_ptr, g_ptr, h->n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
         h->ev_nlp_kind = nlp_kind; h->ev_nlp_rows = nlp_rows; h->ev_nlp_nnz = nlp_nnz; h->ev_fn_nnz = fn_nnz;
-        h->d_ev_ipar = ev_upload(h, nlp_ipar, n_ipar);
-        h->d_ev_dpar = ev_upload(h, nlp_dpar, n_dpar);
-        h->d_ev_x = ev_upload<double>(h, nullptr, 0); (void)h->d_ev_x;
+        P.upload(h->d_ev_ipar, nlp_ipar, n_ipar);
+        P.upload(h->d_ev_dpar, nlp_dpar, n_dpar);
+        P.alloc(h->d_ev_x, 0);
         const int64_t n = h->n, m = std::max<int64_t>(h->m, 1);
-        auto dalloc = [&](int64_t cnt) { double* d = nullptr; HIPCHK(hipMalloc((void**)&d, std::max<int64_t>(cnt, 1) * sizeof(double))); h->ev_bufs.push_back((void*)d);
-                                          HIPCHK(hipMemset(d, 0, std::max<int64_t>(cnt, 1) * sizeof(double))); return d; };
-        h->d_ev_x = dalloc(n); h->d_ev_xt = dalloc(8 * round_up(n, 32)); h->d_ev_df = dalloc(n); h->d_ev_E = dalloc(m); h->d_ev_Et = dalloc(8 * round_up(std::max<int64_t>(m, 1), 32));
-        h->d_ev_f = dalloc(16);      // xt / Et / f[1..8]: eight trial points of the batched line search
+        P.zeroed(h->d_ev_x, n); P.zeroed(h->d_ev_xt, 8 * round_up(n, 32)); P.zeroed(h->d_ev_df, n); P.zeroed(h->d_ev_E, m);
+        P.zeroed(h->d_ev_Et, 8 * round_up(std::max<int64_t>(m, 1), 32));
+        P.zeroed(h->d_ev_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
         h->ev_X = ExprTape{};
         if (nlp_kind == ASM_NLP_EXPR) {
             ExprTape& X = h->ev_X;
             X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = h->n;
-            X.ptr = ev_upload(h, xh.ptr.data(), (int64_t)xh.ptr.size()); X.jptr = ev_upload(h, xh.jptr.data(), (int64_t)xh.jptr.size());
-            X.a = ev_upload(h, xh.a.data(), xh.L); X.b = ev_upload(h, xh.b.data(), xh.L); X.slot = ev_upload(h, xh.slot.data(), xh.L);
-            X.op = ev_upload(h, xh.op.data(), xh.L); X.gptr = ev_upload(h, xh.gptr.data(), (int64_t)xh.gptr.size());
+            P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
+            P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
+            P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
             X.cst = h->d_ev_dpar;
             // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
-            X.val = dalloc(8 * xh.L); X.adj = dalloc(xh.L);
-            X.tval = dalloc(8 * xh.T); X.gocc = dalloc(xh.gptr[h->n]);
+            P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
+            P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[h->n]);
         }
         // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
-        h->d_ev_vecs = dalloc(2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
+        P.zeroed(h->d_ev_vecs, 2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
         HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), n * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + n, h->v_ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        if (!h->h_ev) HIPCHK(hipHostMalloc((void**)&h->h_ev, (4 * (n + m) + 64) * sizeof(double)));
+        if (!h->h_ev) h->mem.alloc(h->h_ev, 4 * (n + m) + 64, BufPool::PINNED);
         h->ev_ready = true;
     });
 }
@@ -4048,7 +3977,7 @@ static void test_load_S(asm_handle* h, const double* S, int64_t N) {
     int64_t ld = h->Mp;
     if (h->test_layout == 1) {
         h->test_fac = FacBuf();
-        ns_alloc_factor(h, h->test_fac, N, h->test_band_hint);
+        ns_alloc_factor(h, h->mem, h->test_fac, N, h->test_band_hint);
         h->test_fac.band = h->main_band;
         HIPCHK(hipStreamSynchronize(h->stream));          // (the buffers are cleared on the stream)
         dst = h->test_fac.S;
@@ -4131,10 +4060,10 @@ int asm_test_gemm_nt(asm_handle* h, const double* A, const double* B, const doub
         if (Ma <= 0 || Mb <= 0 || K <= 0 || K % 32 != 0 || !A || !B || !C_out || (mode != 0 && !C0)) throw std::invalid_argument("asm_test_gemm_nt: bad argument");
         HIPCHK(hipSetDevice(h->device));
         double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-        dmalloc(&dA, Ma * K); dmalloc(&dB, Mb * K); dmalloc(&dC, Ma * Mb);
-        HIPCHK(hipMemcpy(dA, A, Ma * K * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dB, B, Mb * K * sizeof(double), hipMemcpyHostToDevice));
-        if (mode != 0) HIPCHK(hipMemcpy(dC, C0, Ma * Mb * sizeof(double), hipMemcpyHostToDevice));
+        BufPool tmp;
+        tmp.upload(dA, A, Ma * K); tmp.upload(dB, B, Mb * K);
+        if (mode != 0) tmp.upload(dC, C0, Ma * Mb);
+        else tmp.alloc(dC, Ma * Mb);
         const char* var = std::getenv("ASM_TEST_GEMM");      // tile variant under test: 32 (32 x 64), 32w (32 x 96), default 64 x 64
         if (var && std::string(var) == "32w")
             hipLaunchKernelGGL(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, (const double*)dA, K, (const double*)dB, K,
@@ -4147,7 +4076,6 @@ int asm_test_gemm_nt(asm_handle* h, const double* A, const double* B, const doub
                            (const double*)(mode != 0 ? dC : nullptr), Mb, dC, Mb, (int)Ma, (int)Mb, (int)K, mode);
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpy(C_out, dC, Ma * Mb * sizeof(double), hipMemcpyDeviceToHost));
-        (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
     });
 }
 
@@ -4159,17 +4087,14 @@ int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* 
         test_factor(h, d, N);
         const int64_t ldr = round_up(N, 32);
         double *dR = nullptr, *dX = nullptr, *dLt = nullptr;
-        dmalloc(&dR, nrhs * ldr); dmalloc(&dX, nrhs * ldr); dmalloc(&dLt, d.fld * d.fld);
-        HIPCHK(hipMemset(dR, 0, nrhs * ldr * sizeof(double)));
-        HIPCHK(hipMemset(dX, 0, nrhs * ldr * sizeof(double)));
-        HIPCHK(hipMemset(dLt, 0, d.fld * d.fld * sizeof(double)));
+        BufPool tmp;
+        tmp.zeroed(dR, nrhs * ldr); tmp.zeroed(dX, nrhs * ldr); tmp.zeroed(dLt, d.fld * d.fld);
         for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(dR + r * ldr, R + r * N, N * sizeof(double), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, h->stream, (const double*)d.fS, d.fld, N, N, dLt, d.fld, (int64_t)-1);
         d.trsm_rows(dR, dX, ldr, (int)nrhs, (int)N, backward ? dLt : nullptr);
         HIPCHK(hipStreamSynchronize(h->stream));
         const double* out = backward ? dR : dX;
         for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(X_out + r * N, out + r * ldr, N * sizeof(double), hipMemcpyDeviceToHost));
-        (void)hipFree(dR); (void)hipFree(dX); (void)hipFree(dLt);
         d.resolve_timing();
     });
 }
@@ -4194,7 +4119,8 @@ int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tfl
         HIPCHK(hipGetDeviceProperties(&prop, h->device));
         int blocks = prop.multiProcessorCount * waves_per_simd;          // 256-thread blocks: 4 wavefronts = one per SIMD
         double* d_out = nullptr;
-        HIPCHK(hipMalloc((void**)&d_out, 64));
+        BufPool tmp;
+        tmp.alloc(d_out, 8);
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0));
         HIPCHK(hipEventCreate(&e1));
@@ -4209,7 +4135,6 @@ int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tfl
         *tflops = flops / (ms * 1e-3) / 1e12;
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        (void)hipFree(d_out);
     });
 }
 

@@ -192,6 +192,87 @@ def test_c_abi_argument_errors(hip_lib):
     hip_lib.asm_destroy(h)
 
 
+def _abi_setup(lib, h, sp):
+    from activesetmethods_amd import _lib
+    jr, jc = (np.ascontiguousarray(sp[k], dtype=np.int64) for k in ('j_row', 'j_col'))
+    c_lb, c_ub, v_lb, v_ub = (np.ascontiguousarray(sp[k], dtype=np.float64) for k in ('c_lb', 'c_ub', 'v_lb', 'v_ub'))
+    return lib.asm_sublp_setup(h, sp['n'], sp['m'], len(jr), _lib.i64ptr(jr), _lib.i64ptr(jc), _lib.dptr(c_lb), _lib.dptr(c_ub),
+                               _lib.dptr(v_lb), _lib.dptr(v_ub))
+
+
+def _abi_solves(lib, h, sp):
+    """A normal-phase solve, then a restoration solve, on a set-up handle: per solve the raw bytes of status, step, multipliers, slacks and
+    active sets (outputs are zero-initialised, so entries the library leaves alone compare equal)."""
+    import ctypes as C
+    from activesetmethods_amd import _lib
+    n, m = sp['n'], sp['m']
+    dE, df, E, x_k = (np.ascontiguousarray(sp[k], dtype=np.float64) for k in ('dE', 'df', 'E', 'x_k'))
+    outs = []
+    for feasibility in (0, 1):
+        p, lam, mU, mL, ps = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(n), np.zeros(2 * max(m, 1))
+        st = C.c_int32(0)
+        assert lib.asm_sublp_solve(h, _lib.dptr(dE), _lib.dptr(df), float(sp['f']), _lib.dptr(E), _lib.dptr(x_k), float(sp['delta']), feasibility,
+                                   _lib.dptr(p), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(ps), C.byref(st)) == 0
+        assert st.value == 1, (feasibility, st.value)
+        nr, nsl = C.c_int64(0), C.c_int64(0)
+        assert lib.asm_sublp_active_set(h, None, None, None, C.byref(nr), C.byref(nsl)) == 0
+        rows, bnd, sl = np.zeros(nr.value, np.int32), np.zeros(n, np.int32), np.zeros(max(nsl.value, 1), np.int32)
+        assert lib.asm_sublp_active_set(h, _lib.i32ptr(rows), _lib.i32ptr(bnd), _lib.i32ptr(sl), None, None) == 0
+        outs.append([st.value] + [a.tobytes() for a in (p, lam, mU, mL, ps, rows, bnd, sl)])
+    return outs
+
+
+def test_resetup_across_skeletons_matches_fresh_handles(hip_lib):
+    """asm_sublp_setup on one handle across LP skeletons - null-space form, dense, two rejected set-ups, banded row order with the column
+    form, the first skeleton again: after every accepted set-up a normal-phase and a restoration solve equal a fresh handle's on the same
+    data bit for bit, and a rejected set-up leaves the handle without a skeleton."""
+    import ctypes as C
+    from tests.util import banded_subproblem
+    lib = hip_lib
+    sp_ns = equality_rich_subproblem(81, 300, 260, 160)
+    sp_dense = random_subproblem(7, 96, 48)
+    sp_band = banded_subproblem(501, 400, 600, 120, 30)
+    free = dict(sp_dense); free['c_lb'] = sp_dense['c_lb'].copy(); free['c_ub'] = sp_dense['c_ub'].copy()
+    free['c_lb'][0], free['c_ub'][0] = -np.inf, np.inf
+    bad_row = dict(sp_dense); bad_row['j_row'] = sp_dense['j_row'].copy(); bad_row['j_row'][0] = sp_dense['m'] + 1
+
+    def row_order(h):
+        band, n_e, e_band = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        assert lib.asm_sublp_row_order(h, None, C.byref(band), None, C.byref(n_e), C.byref(e_band)) == 0
+        return band.value, n_e.value
+
+    def fresh(sp):
+        g = C.c_void_p()
+        assert lib.asm_create(0, C.byref(g)) == 0
+        try:
+            assert _abi_setup(lib, g, sp) == 0
+            return _abi_solves(lib, g, sp)
+        finally:
+            lib.asm_destroy(g)
+
+    h = C.c_void_p()
+    assert lib.asm_create(0, C.byref(h)) == 0
+    try:
+        st = C.c_int32(0)
+        x = np.zeros(2 * (sp_dense['n'] + sp_dense['m']))
+        xp = x.ctypes.data_as(C.POINTER(C.c_double))
+        for step, sp in enumerate([sp_ns, sp_dense, None, sp_band, sp_ns]):
+            if sp is None:
+                for rejected, rc in ((free, -11), (bad_row, -1)):      # ASM_ERR_UNSUPPORTED (free row), ASM_ERR_ARG (j_row out of range)
+                    assert _abi_setup(lib, h, rejected) == rc
+                    assert lib.asm_sublp_solve_resident(h, 0.4, 0, xp, xp, xp, xp, xp, C.byref(st)) == -3     # ASM_ERR_STATE
+                continue
+            assert _abi_setup(lib, h, sp) == 0
+            band, n_e = row_order(h)
+            if sp is sp_ns:
+                assert n_e > 0, step                  # the null-space form's skeleton
+            if sp is sp_band:
+                assert band > 0, step                 # a banded row order
+            assert _abi_solves(lib, h, sp) == fresh(sp), step
+    finally:
+        lib.asm_destroy(h)
+
+
 def _lp_properties(sp, out, opt, feasibility=False):
     """Size-independent checks of an OPTIMAL sub-LP solution against the LP it solves (normal phase):
     primal feasibility of rows and box, dual sign feasibility, stationarity df - J'lambda - mult = 0 on the
