@@ -79,6 +79,9 @@ const double FACE_TOL_M = 1e-9;
 struct HipError : std::runtime_error {
     explicit HipError(const std::string& s) : std::runtime_error(s) {}
 };
+struct Unsupported : std::invalid_argument {      // valid input the library cannot represent (an LP skeleton the reference cannot build)
+    explicit Unsupported(const std::string& s) : std::invalid_argument(s) {}
+};
 #define HIPCHK(expr)                                                                                     \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
@@ -2789,6 +2792,8 @@ void check_panel_timeout(asm_handle* h) {
 
 void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j_row, const int64_t* j_col, const double* c_lb,
               const double* c_ub, const double* v_lb, const double* v_ub) {
+    if (n <= 0 || m < 0 || nnz < 0 || (nnz > 0 && (!j_row || !j_col)) || (m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub)
+        throw std::invalid_argument("asm_sublp_setup: bad dimensions or null pointer");
     HIPCHK(hipSetDevice(h->device));
     free_device(h);
     h->setup_done = false;
@@ -2802,7 +2807,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     h->adj.clear();
     for (int64_t i = 0; i < m; ++i) {
         h->kind[i] = row_kind(c_lb[i], c_ub[i]);
-        if (h->kind[i] == 9) throw std::invalid_argument("free constraint row (c_lb=-Inf, c_ub=+Inf) is not representable");
+        if (h->kind[i] == 9) throw Unsupported("free constraint row (c_lb=-Inf, c_ub=+Inf) is not representable");
         if (h->kind[i] == 2) h->adj.push_back(i);
     }
     h->nadj = (int64_t)h->adj.size();
@@ -3051,6 +3056,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
 }
 
 void do_upload(asm_handle* h, const double* dE, const double* df, double f, const double* E, const double* x_k) {
+    if ((h->nnz > 0 && !dE) || !df || (h->m > 0 && !E) || !x_k) throw std::invalid_argument("asm_sublp_upload: null pointer");
     if (!h->setup_done) throw std::logic_error("asm_sublp_setup has not been called");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -3059,6 +3065,37 @@ void do_upload(asm_handle* h, const double* dE, const double* df, double f, cons
     h->df.assign(df, df + h->n); h->E.assign(E, E + h->m); h->x_k.assign(x_k, x_k + h->n);
     h->f = f;
     h->inputs_ready = true;
+}
+
+void do_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub) {
+    if (!h->setup_done) throw std::logic_error("asm_sublp_set_bounds: asm_sublp_setup first");
+    if ((h->m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub) throw std::invalid_argument("asm_sublp_set_bounds: null pointer");
+    for (int64_t i = 0; i < h->m; ++i)
+        if (row_kind(c_lb[i], c_ub[i]) != h->kind[i])
+            throw Unsupported("asm_sublp_set_bounds: the kind of a row changes - the LP skeleton is not representable (call asm_sublp_setup)");
+    HIPCHK(hipSetDevice(h->device));
+    h->c_lb.assign(c_lb, c_lb + h->m); h->c_ub.assign(c_ub, c_ub + h->m);
+    h->v_lb.assign(v_lb, v_lb + h->n); h->v_ub.assign(v_ub, v_ub + h->n);
+    if (h->ev_ready) {              // the reductions' copy of the bounds
+        HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + h->n, h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    // the retained working sets and the basis Z belong to the old instance; the basis COLUMNS of the null-space form are kept - the
+    // pattern is the same, and a set that no longer spans null(A_EF) is detected and re-selected by the next LP (Solver::ns_setup)
+    h->last = ActiveSet();
+    reset_warm(h, true);
+    h->inputs_ready = false;
+}
+
+void do_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
+    if (k < 0 || (k > 0 && !J)) throw std::invalid_argument("asm_sublp_set_ns_basis: bad argument");
+    if (!h->setup_done) throw std::logic_error("asm_sublp_set_ns_basis: asm_sublp_setup first");
+    for (int64_t a = 0; a < k; ++a)
+        if (J[a] < 0 || J[a] >= h->n) throw std::invalid_argument("asm_sublp_set_ns_basis: column out of range");
+    h->hint[0].ns_J.assign(J, J + k);
+    h->ns_Zk = 0;
 }
 
 // the LP in caller units: min q'p + w's  s.t.  J_i p + E s (=,>=,<=) r_i (rows m.. = the extra `<=` rows of range constraints),
@@ -3160,6 +3197,8 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
 
 void do_solve(asm_handle* h, double delta, int feasibility, double* p_out, double* lambda, double* mult_x_U, double* mult_x_L,
               double* p_slack, int32_t* status) {
+    if (!p_out || (h->m > 0 && (!lambda || !p_slack)) || !mult_x_U || !mult_x_L || !status) throw std::invalid_argument("asm_sublp_solve: null output pointer");
+    if (!(delta >= 0.0)) throw std::invalid_argument("asm_sublp_solve: delta must be >= 0");
     if (!h->setup_done || !h->inputs_ready) throw std::logic_error("inputs have not been uploaded");
     HIPCHK(hipSetDevice(h->device));
     auto t0 = std::chrono::steady_clock::now();
@@ -3257,30 +3296,43 @@ void do_lp_solve(asm_handle* h, const double* dE, const double* q, const double*
     h->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-template <class F>
-int guarded(asm_handle* h, F&& fn) {
-    if (!h) return ASM_ERR_ARG;
+// what a batch slot threw in one step (in_slot): the exception unchanged, and where it happened for the message
+struct SlotError { std::exception_ptr e; const char* step; int slot; };
+
+// The one map from the exception being handled to an ASM_ERR_* code, its message into `err`.  The internals throw HipError or
+// asmb::BatchError for a device failure, Unsupported for input the library cannot represent, std::invalid_argument for bad input and
+// std::logic_error for a missing earlier call.
+int error_code(std::string& err) {
     try {
-        fn();
-        return ASM_OK;
-    } catch (const HipError& e) {
-        h->err = e.what();
-        return ASM_ERR_HIP;
-    } catch (const std::invalid_argument& e) {
-        h->err = e.what();
-        return std::string(e.what()).find("not representable") != std::string::npos ? ASM_ERR_UNSUPPORTED : ASM_ERR_ARG;
-    } catch (const std::logic_error& e) {
-        h->err = e.what();
-        return ASM_ERR_STATE;
-    } catch (const std::exception& e) {
-        h->err = e.what();
-        return ASM_ERR_ARG;
-    }
+        throw;
+    } catch (const SlotError& s) {
+        try { std::rethrow_exception(s.e); } catch (...) {
+            const int rc = error_code(err);
+            err = std::string(s.step) + " (slot " + std::to_string(s.slot) + "): " + err;
+            return rc;
+        }
+    } catch (const HipError& e) { err = e.what(); return ASM_ERR_HIP; }
+    catch (const asmb::BatchError& e) { err = e.what(); return ASM_ERR_HIP; }
+    catch (const Unsupported& e) { err = e.what(); return ASM_ERR_UNSUPPORTED; }
+    catch (const std::invalid_argument& e) { err = e.what(); return ASM_ERR_ARG; }
+    catch (const std::logic_error& e) { err = e.what(); return ASM_ERR_STATE; }
+    catch (const std::exception& e) { err = e.what(); return ASM_ERR_ARG; }
 }
 
-}  // namespace
+// the body of an entry on a handle or a batch: ASM_OK, or the code of what fn() throws (message in the owner's err)
+template <class Owner, class F>
+int guarded(Owner* o, F&& fn) {
+    if (!o) return ASM_ERR_ARG;
+    try { fn(); } catch (...) { return error_code(o->err); }
+    return ASM_OK;
+}
 
-namespace {
+// one slot's part of batch step `step`: what it throws keeps its type, so the batch entry returns the per-handle entry's code
+template <class F>
+void in_slot(const char* step, int slot, F&& fn) {
+    try { fn(); } catch (...) { throw SlotError{std::current_exception(), step, slot}; }
+}
+
 // kernels of one evaluation at the point in `xd`: values into Ed (m), objective into fd, optionally gradient / Jacobian values
 // `ntrial` > 1 (values only): the trial points of a batched line search, xd / Ed / fd advancing by ldx / ldE / 1 per point
 void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool full, int ntrial = 1, int64_t ldx = 0, int64_t ldE = 0) {
@@ -3375,60 +3427,29 @@ const char* asm_last_error(const asm_handle* h) { return h ? h->err.c_str() : "n
 
 int asm_sublp_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j_row, const int64_t* j_col,
                     const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub) {
-    return guarded(h, [&] {
-        if (n <= 0 || m < 0 || nnz < 0 || (nnz > 0 && (!j_row || !j_col)) || (m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub)
-            throw std::invalid_argument("asm_sublp_setup: bad dimensions or null pointer");
-        do_setup(h, n, m, nnz, j_row, j_col, c_lb, c_ub, v_lb, v_ub);
-    });
+    return guarded(h, [&] { do_setup(h, n, m, nnz, j_row, j_col, c_lb, c_ub, v_lb, v_ub); });
 }
 
 int asm_sublp_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub) {
-    return guarded(h, [&] {
-        if (!h->setup_done) throw std::logic_error("asm_sublp_set_bounds: asm_sublp_setup first");
-        if ((h->m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub) throw std::invalid_argument("asm_sublp_set_bounds: null pointer");
-        for (int64_t i = 0; i < h->m; ++i)
-            if (row_kind(c_lb[i], c_ub[i]) != h->kind[i])
-                throw std::invalid_argument("asm_sublp_set_bounds: the kind of a row changes - the LP skeleton is not representable (call asm_sublp_setup)");
-        HIPCHK(hipSetDevice(h->device));
-        h->c_lb.assign(c_lb, c_lb + h->m); h->c_ub.assign(c_ub, c_ub + h->m);
-        h->v_lb.assign(v_lb, v_lb + h->n); h->v_ub.assign(v_ub, v_ub + h->n);
-        if (h->ev_ready) {              // the reductions' copy of the bounds
-            HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + h->n, h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
-        }
-        // the retained working sets and the basis Z belong to the old instance; the basis COLUMNS of the null-space form are kept - the
-        // pattern is the same, and a set that no longer spans null(A_EF) is detected and re-selected by the next LP (Solver::ns_setup)
-        h->last = ActiveSet();
-        reset_warm(h, true);
-        h->inputs_ready = false;
-    });
+    return guarded(h, [&] { do_set_bounds(h, c_lb, c_ub, v_lb, v_ub); });
 }
 
 int asm_sublp_upload(asm_handle* h, const double* dE, const double* df, double f, const double* E, const double* x_k) {
-    return guarded(h, [&] {
-        if ((h->nnz > 0 && !dE) || !df || (h->m > 0 && !E) || !x_k) throw std::invalid_argument("asm_sublp_upload: null pointer");
-        do_upload(h, dE, df, f, E, x_k);
-    });
+    return guarded(h, [&] { do_upload(h, dE, df, f, E, x_k); });
 }
 
 int asm_sublp_solve_resident(asm_handle* h, double delta, int feasibility, double* p, double* lambda, double* mult_x_U,
                              double* mult_x_L, double* p_slack, int32_t* status) {
-    return guarded(h, [&] {
-        if (!p || (h->m > 0 && (!lambda || !p_slack)) || !mult_x_U || !mult_x_L || !status)
-            throw std::invalid_argument("asm_sublp_solve: null output pointer");
-        if (!(delta >= 0.0)) throw std::invalid_argument("asm_sublp_solve: delta must be >= 0");
-        do_solve(h, delta, feasibility, p, lambda, mult_x_U, mult_x_L, p_slack, status);
-    });
+    return guarded(h, [&] { do_solve(h, delta, feasibility, p, lambda, mult_x_U, mult_x_L, p_slack, status); });
 }
 
 int asm_sublp_solve(asm_handle* h, const double* dE, const double* df, double f, const double* E, const double* x_k, double delta,
                     int feasibility, double* p, double* lambda, double* mult_x_U, double* mult_x_L, double* p_slack,
                     int32_t* status) {
-    int rc = asm_sublp_upload(h, dE, df, f, E, x_k);
-    if (rc != ASM_OK) return rc;
-    return asm_sublp_solve_resident(h, delta, feasibility, p, lambda, mult_x_U, mult_x_L, p_slack, status);
+    return guarded(h, [&] {
+        do_upload(h, dE, df, f, E, x_k);
+        do_solve(h, delta, feasibility, p, lambda, mult_x_U, mult_x_L, p_slack, status);
+    });
 }
 
 int asm_lp_solve(asm_handle* h, const double* dE, const double* q, const double* r, const double* lb, const double* ub, int use_slacks,
@@ -3509,22 +3530,25 @@ int asm_kernel_stats_reset(asm_handle* h) {
 }
 
 // --------------------------------------------------------------------------------- norms on the resident Jacobian
+static void do_jac_row_norms(asm_handle* h, double* out_m) {
+    if (!out_m) throw std::invalid_argument("asm_jac_row_norms: null pointer");
+    if (!h->setup_done || !h->inputs_ready) throw std::logic_error("asm_jac_row_norms: no assembled Jacobian");
+    HIPCHK(hipSetDevice(h->device));
+    Dev d(h);
+    d.assemble();
+    if (h->m == 0) return;
+    hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((h->m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, h->d_vecM, h->m, h->ldn);
+    d.d2h(out_m, h->d_vecM, h->m);
+}
+
 int asm_jac_row_norms(asm_handle* h, double* out_m) {
-    return guarded(h, [&] {
-        if (!h->setup_done || !h->inputs_ready || !out_m) throw std::logic_error("asm_jac_row_norms: no assembled Jacobian");
-        HIPCHK(hipSetDevice(h->device));
-        Dev d(h);
-        d.assemble();
-        if (h->m == 0) return;
-        hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((h->m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, h->d_vecM, h->m, h->ldn);
-        d.d2h(out_m, h->d_vecM, h->m);
-    });
+    return guarded(h, [&] { do_jac_row_norms(h, out_m); });
 }
 
 int asm_kt_residuals(asm_handle* h, const double* df, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out) {
     return guarded(h, [&] {
-        if (!h->setup_done || !h->inputs_ready || !df || !mult_x_U || !mult_x_L || !out || (h->m > 0 && !lambda))
-            throw std::logic_error("asm_kt_residuals: no assembled Jacobian or null pointer");
+        if (!df || !mult_x_U || !mult_x_L || !out || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_kt_residuals: null pointer");
+        if (!h->setup_done || !h->inputs_ready) throw std::logic_error("asm_kt_residuals: no assembled Jacobian");
         HIPCHK(hipSetDevice(h->device));
         Dev d(h);
         d.assemble();
@@ -3630,108 +3654,123 @@ void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_
 }
 }  // namespace
 
+static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const int64_t* aff_var, const double* aff_coef, const int64_t* quad_ptr,
+                          const int64_t* q_v1, const int64_t* q_v2, const double* q_coef, const double* constant, const int64_t* jac_off,
+                          const int64_t* g_ptr, const int64_t* g_kind, const double* g_coef, const int64_t* g_other, double objective_scale, int nlp_kind,
+                          int64_t nlp_rows, int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
+    if (!h->setup_done) throw std::logic_error("asm_eval_setup: asm_sublp_setup first (it fixes n, m and the j_str order of dE)");
+    if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < ASM_NLP_NONE || nlp_kind > ASM_NLP_EXPR)
+        throw std::invalid_argument("asm_eval_setup: bad argument");
+    const int64_t fn_nnz = jac_off[n_rows];
+    if (n_rows + nlp_rows != h->m || fn_nnz + nlp_nnz != h->nnz)
+        throw std::invalid_argument("asm_eval_setup: row / Jacobian-entry counts do not match asm_sublp_setup");
+    if (nlp_kind == 1 && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
+        throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
+    if (nlp_kind == 2 && (nlp_nnz != nlp_rows * h->n || n_dpar != 2 * nlp_rows * h->n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
+    ExprHost xh;
+    if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& P = h->mem_ev;
+    P.release();
+    FnStore& F = h->ev_F;
+    F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
+    const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
+    P.upload(F.aff_ptr, aff_ptr, n_rows + 2); P.upload(F.aff_var, aff_var, na); P.upload(F.aff_coef, aff_coef, na);
+    P.upload(F.quad_ptr, quad_ptr, n_rows + 2); P.upload(F.q_v1, q_v1, nq); P.upload(F.q_v2, q_v2, nq); P.upload(F.q_coef, q_coef, nq);
+    P.upload(F.constant, constant, n_rows + 1); P.upload(F.jac_off, jac_off, n_rows + 1);
+    P.upload(F.g_ptr, g_ptr, h->n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
+    h->ev_nlp_kind = nlp_kind; h->ev_nlp_rows = nlp_rows; h->ev_nlp_nnz = nlp_nnz; h->ev_fn_nnz = fn_nnz;
+    P.upload(h->d_ev_ipar, nlp_ipar, n_ipar);
+    P.upload(h->d_ev_dpar, nlp_dpar, n_dpar);
+    P.alloc(h->d_ev_x, 0);
+    const int64_t n = h->n, m = std::max<int64_t>(h->m, 1);
+    P.zeroed(h->d_ev_x, n); P.zeroed(h->d_ev_xt, 8 * round_up(n, 32)); P.zeroed(h->d_ev_df, n); P.zeroed(h->d_ev_E, m);
+    P.zeroed(h->d_ev_Et, 8 * round_up(std::max<int64_t>(m, 1), 32));
+    P.zeroed(h->d_ev_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
+    h->ev_X = ExprTape{};
+    if (nlp_kind == ASM_NLP_EXPR) {
+        ExprTape& X = h->ev_X;
+        X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = h->n;
+        P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
+        P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
+        P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
+        X.cst = h->d_ev_dpar;
+        // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
+        P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
+        P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[h->n]);
+    }
+    // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
+    P.zeroed(h->d_ev_vecs, 2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
+    HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + n, h->v_ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    if (!h->h_ev) h->mem.alloc(h->h_ev, 4 * (n + m) + 64, BufPool::PINNED);
+    h->ev_ready = true;
+}
+
 int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const int64_t* aff_var, const double* aff_coef, const int64_t* quad_ptr,
                    const int64_t* q_v1, const int64_t* q_v2, const double* q_coef, const double* constant, const int64_t* jac_off,
                    const int64_t* g_ptr, const int64_t* g_kind, const double* g_coef, const int64_t* g_other, double objective_scale, int nlp_kind,
                    int64_t nlp_rows, int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
     return guarded(h, [&] {
-        if (!h->setup_done) throw std::logic_error("asm_eval_setup: asm_sublp_setup first (it fixes n, m and the j_str order of dE)");
-        if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < ASM_NLP_NONE || nlp_kind > ASM_NLP_EXPR)
-            throw std::invalid_argument("asm_eval_setup: bad argument");
-        const int64_t fn_nnz = jac_off[n_rows];
-        if (n_rows + nlp_rows != h->m || fn_nnz + nlp_nnz != h->nnz)
-            throw std::invalid_argument("asm_eval_setup: row / Jacobian-entry counts do not match asm_sublp_setup");
-        if (nlp_kind == 1 && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
-            throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
-        if (nlp_kind == 2 && (nlp_nnz != nlp_rows * h->n || n_dpar != 2 * nlp_rows * h->n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
-        ExprHost xh;
-        if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
-        HIPCHK(hipSetDevice(h->device));
-        BufPool& P = h->mem_ev;
-        P.release();
-        FnStore& F = h->ev_F;
-        F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
-        const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
-        P.upload(F.aff_ptr, aff_ptr, n_rows + 2); P.upload(F.aff_var, aff_var, na); P.upload(F.aff_coef, aff_coef, na);
-        P.upload(F.quad_ptr, quad_ptr, n_rows + 2); P.upload(F.q_v1, q_v1, nq); P.upload(F.q_v2, q_v2, nq); P.upload(F.q_coef, q_coef, nq);
-        P.upload(F.constant, constant, n_rows + 1); P.upload(F.jac_off, jac_off, n_rows + 1);
-        P.upload(F.g_ptr, g_ptr, h->n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
-        h->ev_nlp_kind = nlp_kind; h->ev_nlp_rows = nlp_rows; h->ev_nlp_nnz = nlp_nnz; h->ev_fn_nnz = fn_nnz;
-        P.upload(h->d_ev_ipar, nlp_ipar, n_ipar);
-        P.upload(h->d_ev_dpar, nlp_dpar, n_dpar);
-        P.alloc(h->d_ev_x, 0);
-        const int64_t n = h->n, m = std::max<int64_t>(h->m, 1);
-        P.zeroed(h->d_ev_x, n); P.zeroed(h->d_ev_xt, 8 * round_up(n, 32)); P.zeroed(h->d_ev_df, n); P.zeroed(h->d_ev_E, m);
-        P.zeroed(h->d_ev_Et, 8 * round_up(std::max<int64_t>(m, 1), 32));
-        P.zeroed(h->d_ev_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
-        h->ev_X = ExprTape{};
-        if (nlp_kind == ASM_NLP_EXPR) {
-            ExprTape& X = h->ev_X;
-            X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = h->n;
-            P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
-            P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
-            P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
-            X.cst = h->d_ev_dpar;
-            // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
-            P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
-            P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[h->n]);
-        }
-        // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
-        P.zeroed(h->d_ev_vecs, 2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
-        HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + n, h->v_ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        if (!h->h_ev) h->mem.alloc(h->h_ev, 4 * (n + m) + 64, BufPool::PINNED);
-        h->ev_ready = true;
+        do_eval_setup(h, n_rows, aff_ptr, aff_var, aff_coef, quad_ptr, q_v1, q_v2, q_coef, constant, jac_off, g_ptr, g_kind, g_coef, g_other, objective_scale,
+                      nlp_kind, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, nlp_dpar, n_dpar);
     });
 }
 
 // eval_functions! (slp.jl:186-191) on the device + what asm_sublp_upload does with the results: dE stays in HBM
+static void do_eval_functions(asm_handle* h, const double* x, double* f, double* df, double* E) {
+    if (!x || !f || !df || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_functions: null pointer");
+    if (!h->ev_ready) throw std::logic_error("asm_eval_functions: asm_eval_setup first");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->n, m = h->m;
+    std::memcpy(h->h_ev, x, n * sizeof(double));
+    HIPCHK(hipMemcpyAsync(h->d_ev_x, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    ev_launch(h, h->d_ev_x, h->d_ev_E, h->d_ev_f, true);
+    double* st = h->h_ev + n;
+    HIPCHK(hipMemcpyAsync(st, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (m) HIPCHK(hipMemcpyAsync(st + n, h->d_ev_E, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(st + n + m, h->d_ev_f, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::memcpy(df, st, n * sizeof(double));
+    if (m) std::memcpy(E, st + n, m * sizeof(double));
+    *f = st[n + m];
+    h->df.assign(df, df + n); h->E.assign(E, E + m); h->x_k.assign(x, x + n);
+    h->f = *f;
+    h->inputs_ready = true;
+    h->J_valid = false;
+}
+
 int asm_eval_functions(asm_handle* h, const double* x, double* f, double* df, double* E) {
-    return guarded(h, [&] {
-        if (!h->ev_ready || !x || !f || !df || (h->m > 0 && !E)) throw std::logic_error("asm_eval_functions: asm_eval_setup first / null pointer");
-        HIPCHK(hipSetDevice(h->device));
-        const int64_t n = h->n, m = h->m;
-        std::memcpy(h->h_ev, x, n * sizeof(double));
-        HIPCHK(hipMemcpyAsync(h->d_ev_x, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        ev_launch(h, h->d_ev_x, h->d_ev_E, h->d_ev_f, true);
-        double* st = h->h_ev + n;
-        HIPCHK(hipMemcpyAsync(st, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (m) HIPCHK(hipMemcpyAsync(st + n, h->d_ev_E, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(st + n + m, h->d_ev_f, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        std::memcpy(df, st, n * sizeof(double));
-        if (m) std::memcpy(E, st + n, m * sizeof(double));
-        *f = st[n + m];
-        h->df.assign(df, df + n); h->E.assign(E, E + m); h->x_k.assign(x, x + n);
-        h->f = *f;
-        h->inputs_ready = true;
-        h->J_valid = false;
-    });
+    return guarded(h, [&] { do_eval_functions(h, x, f, df, E); });
 }
 
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
+static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
+    if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
+    if (!h->ev_ready) throw std::logic_error("asm_eval_constraints: asm_eval_setup first");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->n, m = h->m;
+    std::memcpy(h->h_ev, x, n * sizeof(double));
+    HIPCHK(hipMemcpyAsync(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
+    double* st = h->h_ev + n;
+    if (m) HIPCHK(hipMemcpyAsync(st, h->d_ev_Et, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(st + m, h->d_ev_f + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (m) std::memcpy(E, st, m * sizeof(double));
+    *f = st[m];
+}
+
 int asm_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
-    return guarded(h, [&] {
-        if (!h->ev_ready || !x || !f || (h->m > 0 && !E)) throw std::logic_error("asm_eval_constraints: asm_eval_setup first / null pointer");
-        HIPCHK(hipSetDevice(h->device));
-        const int64_t n = h->n, m = h->m;
-        std::memcpy(h->h_ev, x, n * sizeof(double));
-        HIPCHK(hipMemcpyAsync(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
-        double* st = h->h_ev + n;
-        if (m) HIPCHK(hipMemcpyAsync(st, h->d_ev_Et, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(st + m, h->d_ev_f + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (m) std::memcpy(E, st, m * sizeof(double));
-        *f = st[m];
-    });
+    return guarded(h, [&] { do_eval_constraints(h, x, f, E); });
 }
 
 int asm_eval_jacobian_values(asm_handle* h, double* dE_out) {
     return guarded(h, [&] {
-        if (!h->setup_done || !dE_out) throw std::logic_error("asm_eval_jacobian_values: no setup / null pointer");
+        if (!dE_out) throw std::invalid_argument("asm_eval_jacobian_values: null pointer");
+        if (!h->setup_done) throw std::logic_error("asm_eval_jacobian_values: asm_sublp_setup first");
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipMemcpy(dE_out, h->d_dE, h->nnz * sizeof(double), hipMemcpyDeviceToHost));
     });
@@ -3740,37 +3779,39 @@ int asm_eval_jacobian_values(asm_handle* h, double* dE_out) {
 // --------------------------------------------------------------------------------- per-iteration reductions on the device (row f1)
 // out[4] = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }  (common.jl:35-98) from the
 // evaluation results of the last asm_eval_functions and the Jacobian assembled from its dE (assembled once, shared with the LP)
+static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4) {
+    if (!mult_x_U || !mult_x_L || !out4 || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_slp_norms: null pointer");
+    if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_norms: asm_eval_functions first");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->n, m = h->m;
+    Dev d(h);
+    d.assemble();
+    double* v = h->d_ev_vecs + 2 * m + 2 * n;       // lam | mU | mL
+    double *lam = v, *mU = v + m, *mL = mU + n, *jtl = mL + n + m + 2 * m + n /* after nu (m), ps (2m), p (n) */, *rown = jtl + h->ldn, *outd = rown + h->Mp;
+    double* st = h->h_ev;
+    if (m) std::memcpy(st, lambda, m * sizeof(double));
+    std::memcpy(st + m, mult_x_U, n * sizeof(double));
+    std::memcpy(st + m + n, mult_x_L, n * sizeof(double));
+    HIPCHK(hipMemcpyAsync(lam, st, (m + 2 * n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    // J' lambda over the first m rows: lambda padded with zeros on the extra range rows
+    HIPCHK(hipMemsetAsync(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
+    if (m) HIPCHK(hipMemcpyAsync(h->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    d.launch_gemv_t(h->d_J, h->d_vecM, jtl);
+    if (m) {
+        if (const double* vJ = d.sparse_vals(h->d_J))      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
+            hipLaunchKernelGGL(k_sp_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col, vJ, rown, m);
+        else
+            hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, rown, m, h->ldn);
+    }
+    hipLaunchKernelGGL(k_slp_norms, dim3(1), dim3(1024), 0, h->stream, ev_vecs(h, lam, mU, mL, jtl, rown), outd);
+    HIPCHK(hipMemcpyAsync(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < RN_COUNT; ++k) out4[k] = st[k];
+    d.resolve_timing();
+}
+
 int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4) {
-    return guarded(h, [&] {
-        if (!h->ev_ready || !h->inputs_ready || !mult_x_U || !mult_x_L || !out4 || (h->m > 0 && !lambda))
-            throw std::logic_error("asm_slp_norms: asm_eval_functions first / null pointer");
-        HIPCHK(hipSetDevice(h->device));
-        const int64_t n = h->n, m = h->m;
-        Dev d(h);
-        d.assemble();
-        double* v = h->d_ev_vecs + 2 * m + 2 * n;       // lam | mU | mL
-        double *lam = v, *mU = v + m, *mL = mU + n, *jtl = mL + n + m + 2 * m + n /* after nu (m), ps (2m), p (n) */, *rown = jtl + h->ldn, *outd = rown + h->Mp;
-        double* st = h->h_ev;
-        if (m) std::memcpy(st, lambda, m * sizeof(double));
-        std::memcpy(st + m, mult_x_U, n * sizeof(double));
-        std::memcpy(st + m + n, mult_x_L, n * sizeof(double));
-        HIPCHK(hipMemcpyAsync(lam, st, (m + 2 * n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        // J' lambda over the first m rows: lambda padded with zeros on the extra range rows
-        HIPCHK(hipMemsetAsync(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
-        if (m) HIPCHK(hipMemcpyAsync(h->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        d.launch_gemv_t(h->d_J, h->d_vecM, jtl);
-        if (m) {
-            if (const double* vJ = d.sparse_vals(h->d_J))      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
-                hipLaunchKernelGGL(k_sp_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col, vJ, rown, m);
-            else
-                hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, rown, m, h->ldn);
-        }
-        hipLaunchKernelGGL(k_slp_norms, dim3(1), dim3(1024), 0, h->stream, ev_vecs(h, lam, mU, mL, jtl, rown), outd);
-        HIPCHK(hipMemcpyAsync(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (int k = 0; k < RN_COUNT; ++k) out4[k] = st[k];
-        d.resolve_timing();
-    });
+    return guarded(h, [&] { do_slp_norms(h, lambda, mult_x_U, mult_x_L, out4); });
 }
 
 // compute_phi(x, alpha, p) (slp.jl:79-115; mode 0) and compute_derivative (slp.jl:122-147; mode 1) with the trial evaluation on the
@@ -3778,8 +3819,8 @@ int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, c
 int asm_slp_merit(asm_handle* h, int mode, double alpha, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas,
                   double* out) {
     return guarded(h, [&] {
-        if (!h->ev_ready || !h->inputs_ready || !p || !out || (h->m > 0 && (!nu || !p_slack)) || mode < 0 || mode > 1)
-            throw std::logic_error("asm_slp_merit: asm_eval_functions first / bad argument");
+        if (!p || !out || (h->m > 0 && (!nu || !p_slack)) || mode < 0 || mode > 1) throw std::invalid_argument("asm_slp_merit: bad argument");
+        if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_merit: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
         const int64_t n = h->n, m = h->m;
         double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
@@ -3811,8 +3852,9 @@ int asm_slp_merit(asm_handle* h, int mode, double alpha, const double* p, const 
 int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double phi0,
                         double D, double eta, double tau, double min_alpha, double* alpha_out, double* phi_out, int* trials_out, int* ok_out) {
     return guarded(h, [&] {
-        if (!h->ev_ready || !h->inputs_ready || !p || !alpha_out || !ok_out || (h->m > 0 && (!nu || !p_slack)) || !(tau > 0.0 && tau < 1.0))
-            throw std::logic_error("asm_slp_line_search: asm_eval_functions first / bad argument");
+        if (!p || !alpha_out || !ok_out || (h->m > 0 && (!nu || !p_slack)) || !(tau > 0.0 && tau < 1.0))
+            throw std::invalid_argument("asm_slp_line_search: bad argument");
+        if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_line_search: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
         const int64_t n = h->n, m = h->m;
         double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
@@ -3912,8 +3954,8 @@ static void slp_tr_step_quality(asm_handle* h, const double* p, const double* nu
 
 int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
     return guarded(h, [&] {
-        if (!h->ev_ready || !h->inputs_ready || !p || !out3 || (h->m > 0 && (!nu || !p_slack)))
-            throw std::logic_error("asm_slp_step_quality: asm_eval_functions first / bad argument");
+        if (!p || !out3 || (h->m > 0 && (!nu || !p_slack))) throw std::invalid_argument("asm_slp_step_quality: null pointer");
+        if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_step_quality: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
         slp_tr_step_quality(h, p, nu, p_slack, feasibility, prim_infeas, out3);
     });
@@ -4154,13 +4196,7 @@ int asm_test_assemble(asm_handle* h, const double* dE, double* J_out) {
 
 
 int asm_sublp_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
-    return guarded(h, [&] {
-        if (!h->setup_done || k < 0 || (k > 0 && !J)) throw std::invalid_argument("asm_sublp_set_ns_basis: setup first / bad argument");
-        for (int64_t a = 0; a < k; ++a)
-            if (J[a] < 0 || J[a] >= h->n) throw std::invalid_argument("asm_sublp_set_ns_basis: column out of range");
-        h->hint[0].ns_J.assign(J, J + k);
-        h->ns_Zk = 0;
-    });
+    return guarded(h, [&] { do_set_ns_basis(h, J, k); });
 }
 
 }  // extern "C"
@@ -4172,54 +4208,83 @@ int asm_sublp_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
 // =========================================================================================================
 namespace {
 
-struct SlpRunLS {
+// the start point clamped into the variable bounds as the reference does it (slp_line_search.jl:96-104, slp_trust_region.jl:104-114): the
+// upper clamp tests x_U > -Inf, sic
+void clamp_start(int64_t n, const double* x0, const double* lb, const double* ub, double* x) {
+    for (int64_t j = 0; j < n; ++j) {
+        double v = x0[j];
+        if (lb[j] > -INF) v = std::max(v, lb[j]);
+        if (ub[j] > -INF) v = std::min(v, ub[j]);
+        x[j] = v;
+    }
+}
+
+// the state both drivers keep: iterate, the last LP's step and multipliers, status, counts and the caller's result record
+struct SlpRun {
     asm_handle* h;
     const asm_slp_params& o;
     int64_t n, m;
     vec x, p, lam, mU, mL, ps, df, E, nu;
-    double f = 0.0, phi = INF, alpha = 1.0, D = 0.0, prim_infeas = INF, dual_infeas = INF, compl_ = INF;
+    double f = 0.0, phi = INF, prim_infeas = INF, dual_infeas = INF, compl_ = INF;
     bool fr = false;
-    int iter = 1, ret = -5, lp_solves = 0, fr_solves = 0, ls_trials = 0;
+    int iter = 1, ret = -5, lp_solves = 0, fr_solves = 0;
     asm_slp_result* res;
 
-    SlpRunLS(asm_handle* hh, const asm_slp_params& par, asm_slp_result* r) : h(hh), o(par), n(hh->n), m(hh->m), res(r) {
+    SlpRun(asm_handle* hh, const asm_slp_params& par, asm_slp_result* r) : h(hh), o(par), n(hh->n), m(hh->m), res(r) {
         x.assign(n, 0.0); p.assign(n, 0.0); lam.assign(m, 0.0); mU.assign(n, 0.0); mL.assign(n, 0.0);
         ps.assign(2 * std::max<int64_t>(m, 1), 0.0); df.assign(n, 0.0); E.assign(std::max<int64_t>(m, 1), 0.0); nu.assign(m, 0.0);
     }
-    void chk(int rc, const char* what) {
-        if (rc != ASM_OK) throw HipError(std::string(what) + ": " + h->err);
-    }
     bool feasible_enough() const { return prim_infeas <= o.tol_infeas; }
     double finite_or_zero(double v) const { return std::isfinite(v) ? v : 0.0; }
+    void count_lp() {            // the LP just solved
+        lp_solves += 1;
+        if (fr) fr_solves += 1;
+        if (res) {
+            const int pth = h->stats.path;
+            if (pth >= 0 && pth < 12) res->paths[pth] += 1;
+            res->ipm_iters += h->stats.ipm_iters;
+            res->ns_cold += h->stats.ns_cold;
+        }
+    }
+    // the objective at the final point (slp_line_search.jl:208-214, slp_trust_region.jl:198) and the result record
+    void finish(int tag, int ls_trials) {
+        double f_end = 0.0;
+        vec Et(std::max<int64_t>(m, 1));
+        asmb::barrier(tag);
+        do_eval_constraints(h, x.data(), &f_end, Et.data());
+        if (res) {
+            res->status = ret; res->iter = iter; res->lp_solves = lp_solves; res->restoration_solves = fr_solves; res->ls_trials = ls_trials;
+            res->obj_val = f_end; res->prim_infeas = prim_infeas; res->dual_infeas = dual_infeas; res->compl_ = compl_;
+        }
+    }
+    void outputs(double* x_out, double* lambda, double* mult_x_U, double* mult_x_L, double* g_out) const {
+        if (x_out) std::memcpy(x_out, x.data(), n * sizeof(double));
+        if (lambda && m) std::memcpy(lambda, lam.data(), m * sizeof(double));
+        if (mult_x_U) std::memcpy(mult_x_U, mU.data(), n * sizeof(double));
+        if (mult_x_L) std::memcpy(mult_x_L, mL.data(), n * sizeof(double));
+        if (g_out && m) std::memcpy(g_out, E.data(), m * sizeof(double));
+    }
+};
+
+struct SlpRunLS : SlpRun {
+    double alpha = 1.0, D = 0.0;
+    int ls_trials = 0;
+    using SlpRun::SlpRun;
 
     void run(const double* x0) {
-        // slp_line_search.jl:96-104 (the clamp tests x_U > -Inf, sic)
-        for (int64_t j = 0; j < n; ++j) {
-            double v = x0[j];
-            if (h->v_lb[j] > -INF) v = std::max(v, h->v_lb[j]);
-            if (h->v_ub[j] > -INF) v = std::min(v, h->v_ub[j]);
-            x[j] = v;
-        }
-        iter = 1;
+        clamp_start(n, x0, h->v_lb.data(), h->v_ub.data(), x.data());       // slp_line_search.jl:96-104
         while (true) {
             if (o.max_lp_solves > 0 && lp_solves >= o.max_lp_solves) break;
             asmb::next_cycle();
             asmb::barrier(10);
-            chk(asm_eval_functions(h, x.data(), &f, df.data(), E.data()), "asm_eval_functions");      // :109-110
+            do_eval_functions(h, x.data(), &f, df.data(), E.data());                                    // :109-110
             alpha = 0.0;
             double nrm[4];
-            chk(asm_slp_norms(h, lam.data(), mU.data(), mL.data(), nrm), "asm_slp_norms");             // :113-118, the previous LP's multipliers
+            do_slp_norms(h, lam.data(), mU.data(), mL.data(), nrm);                                     // :113-118, the previous LP's multipliers
             prim_infeas = nrm[0]; dual_infeas = nrm[2]; compl_ = nrm[3];
             int32_t status = 0;
-            chk(asm_sublp_solve_resident(h, 1000.0, fr ? 1 : 0, p.data(), lam.data(), mU.data(), mL.data(), ps.data(), &status), "asm_sublp_solve_resident");   // :122-123
-            lp_solves += 1;
-            if (fr) fr_solves += 1;
-            if (res) {
-                const int pth = h->stats.path;
-                if (pth >= 0 && pth < 12) res->paths[pth] += 1;
-                res->ipm_iters += h->stats.ipm_iters;
-                res->ns_cold += h->stats.ns_cold;
-            }
+            do_solve(h, 1000.0, fr ? 1 : 0, p.data(), lam.data(), mU.data(), mL.data(), ps.data(), &status);   // :122-123
+            count_lp();
             if (status != ASM_OPTIMAL && status != ASM_INFEASIBLE) {                                     // :127-133
                 if (feasible_enough()) ret = 6;
                 break;
@@ -4234,8 +4299,8 @@ struct SlpRunLS {
             int trials = 0, ok = 0;
             double phi_a = 0.0;
             // compute_phi, compute_derivative, compute_alpha (:222-244) - as asm_slp_merit (modes 0, 1) + asm_slp_line_search, with one upload
-            chk(guarded(h, [&] { slp_merit_and_search(h, p.data(), nu.data(), ps.data(), fr ? 1 : 0, finite_or_zero(prim_infeas), o.eta, o.tau, o.min_alpha, &phi, &D, &alpha,
-                                                      &phi_a, &trials, &ok); }), "slp_merit_and_search");
+            slp_merit_and_search(h, p.data(), nu.data(), ps.data(), fr ? 1 : 0, finite_or_zero(prim_infeas), o.eta, o.tau, o.min_alpha, &phi, &D, &alpha, &phi_a,
+                                 &trials, &ok);
             ls_trials += trials;
             if (!ok && fr) ret = -3;
             const bool valid = ok != 0;
@@ -4255,15 +4320,7 @@ struct SlpRunLS {
             for (int64_t j = 0; j < n; ++j) x[j] = x[j] + alpha * p[j];                                  // :201-203
             iter += 1;
         }
-        // :208-214: objective at the final point
-        double f_end = 0.0;
-        vec Et(std::max<int64_t>(m, 1));
-        asmb::barrier(990);
-        chk(asm_eval_constraints(h, x.data(), &f_end, Et.data()), "asm_eval_constraints");
-        if (res) {
-            res->status = ret; res->iter = iter; res->lp_solves = lp_solves; res->restoration_solves = fr_solves; res->ls_trials = ls_trials;
-            res->obj_val = f_end; res->prim_infeas = prim_infeas; res->dual_infeas = dual_infeas; res->compl_ = compl_;
-        }
+        finish(990, ls_trials);
     }
 };
 
@@ -4273,11 +4330,7 @@ void slp_run_ls(asm_handle* h, const asm_slp_params* par, const double* x0, doub
     if (res) std::memset(res, 0, sizeof(*res));
     SlpRunLS r(h, *par, res);
     r.run(x0);
-    if (x_out) std::memcpy(x_out, r.x.data(), h->n * sizeof(double));
-    if (lambda && h->m) std::memcpy(lambda, r.lam.data(), h->m * sizeof(double));
-    if (mult_x_U) std::memcpy(mult_x_U, r.mU.data(), h->n * sizeof(double));
-    if (mult_x_L) std::memcpy(mult_x_L, r.mL.data(), h->n * sizeof(double));
-    if (g_out && h->m) std::memcpy(g_out, r.E.data(), h->m * sizeof(double));
+    r.outputs(x_out, lambda, mult_x_U, mult_x_L, g_out);
 }
 
 // run!(::SlpTR), slp_trust_region.jl:87-251 - statement by statement the library calls of SlpTR.run in activesetmethods_amd/slp.py with
@@ -4285,29 +4338,13 @@ void slp_run_ls(asm_handle* h, const asm_slp_params* par, const double* x0, doub
 // may round it differently in the last bit.  It only enters nu at iter 1 and through nu only the merit values and rho: iterates,
 // multipliers, radius and counts stay bit-identical unless rho falls within an ulp of 0, 0.25 or 0.75.  The same holds for the 1-norm of
 // the violations in the status-OTHER branch (device evaluator instead of the host's eval_g, a plain sum), which only decides ret 6 / -5.
-struct SlpRunTR {
-    asm_handle* h;
-    const asm_slp_params& o;
-    int64_t n, m;
-    vec x, p, lam, mU, mL, ps, df, E, nu, rn;
-    double f = 0.0, phi = INF, prim_infeas = INF, dual_infeas = INF, compl_ = INF;
+struct SlpRunTR : SlpRun {
+    vec rn;
     double Delta, Delta_max = 2.0, alpha1 = 0.1, alpha2 = 0.25;     // slp_trust_region.jl:62-65
-    bool fr = false;
-    int iter = 1, ret = -5, lp_solves = 0, fr_solves = 0;
-    asm_slp_result* res;
     asm_slp_tr_info info{};
 
     SlpRunTR(asm_handle* hh, const asm_slp_params& par, double tr_size, asm_slp_result* r)
-        : h(hh), o(par), n(hh->n), m(hh->m), Delta(tr_size), res(r) {
-        x.assign(n, 0.0); p.assign(n, 0.0); lam.assign(m, 0.0); mU.assign(n, 0.0); mL.assign(n, 0.0);
-        ps.assign(2 * std::max<int64_t>(m, 1), 0.0); df.assign(n, 0.0); E.assign(std::max<int64_t>(m, 1), 0.0); nu.assign(m, 0.0);
-        rn.assign(std::max<int64_t>(m, 1), 0.0);
-    }
-    void chk(int rc, const char* what) {
-        if (rc != ASM_OK) throw HipError(std::string(what) + ": " + h->err);
-    }
-    bool feasible_enough() const { return prim_infeas <= o.tol_infeas; }
-    double finite_or_zero(double v) const { return std::isfinite(v) ? v : 0.0; }
+        : SlpRun(hh, par, r), rn(std::max<int64_t>(m, 1), 0.0), Delta(tr_size) {}
 
     // slp.jl:54-66 (the base compute_nu!, not the Line-Search one)
     void compute_nu() {
@@ -4318,7 +4355,7 @@ struct SlpRunTR {
                 for (int64_t j = 0; j < n; ++j) s += df[j] * df[j];
                 norm_df = std::sqrt(s);
             }
-            chk(asm_jac_row_norms(h, rn.data()), "asm_jac_row_norms");
+            do_jac_row_norms(h, rn.data());
             for (int64_t i = 0; i < m; ++i) nu[i] = std::max(1.0, norm_df / std::max(1.0, rn[i]));
         } else {
             for (int64_t i = 0; i < m; ++i) nu[i] = std::max(nu[i], std::fabs(lam[i]));
@@ -4328,7 +4365,7 @@ struct SlpRunTR {
     // step_quality (slp_trust_region.jl:213-251) as SlpTR.step_quality: the three merit values from one launch, the rest on the host
     double step_quality() {
         double q[3];
-        chk(guarded(h, [&] { slp_tr_step_quality(h, p.data(), nu.data(), ps.data(), fr ? 1 : 0, finite_or_zero(prim_infeas), q); }), "slp_tr_step_quality");
+        slp_tr_step_quality(h, p.data(), nu.data(), ps.data(), fr ? 1 : 0, finite_or_zero(prim_infeas), q);
         phi = q[2] - q[1];
         const double phi_pre = q[0];
         if (std::fabs(phi_pre) > 0.0) {
@@ -4350,33 +4387,19 @@ struct SlpRunTR {
     }
 
     void run(const double* x0) {
-        // slp_trust_region.jl:104-114 (the clamp tests x_U > -Inf, sic)
-        for (int64_t j = 0; j < n; ++j) {
-            double v = x0[j];
-            if (h->v_lb[j] > -INF) v = std::max(v, h->v_lb[j]);
-            if (h->v_ub[j] > -INF) v = std::min(v, h->v_ub[j]);
-            x[j] = v;
-        }
-        iter = 1;
+        clamp_start(n, x0, h->v_lb.data(), h->v_ub.data(), x.data());       // slp_trust_region.jl:104-114
         while (true) {
             if (o.max_lp_solves > 0 && lp_solves >= o.max_lp_solves) break;
             asmb::next_cycle();
             asmb::barrier(11);
-            chk(asm_eval_functions(h, x.data(), &f, df.data(), E.data()), "asm_eval_functions");      // :120
+            do_eval_functions(h, x.data(), &f, df.data(), E.data());                                    // :120
             int32_t status = 0;
-            chk(asm_sublp_solve_resident(h, Delta, fr ? 1 : 0, p.data(), lam.data(), mU.data(), mL.data(), ps.data(), &status), "asm_sublp_solve_resident");
-            lp_solves += 1;
-            if (fr) fr_solves += 1;
-            if (res) {
-                const int pth = h->stats.path;
-                if (pth >= 0 && pth < 12) res->paths[pth] += 1;
-                res->ipm_iters += h->stats.ipm_iters;
-                res->ns_cold += h->stats.ns_cold;
-            }
+            do_solve(h, Delta, fr ? 1 : 0, p.data(), lam.data(), mU.data(), mL.data(), ps.data(), &status);
+            count_lp();
             if (status != ASM_OPTIMAL && status != ASM_INFEASIBLE) {                                     // :130-136 (`slp.ret == -3`: a comparison, sic)
                 double fc = 0.0, v1 = 0.0;
                 vec Ec(std::max<int64_t>(m, 1));
-                chk(asm_eval_constraints(h, x.data(), &fc, Ec.data()), "asm_eval_constraints");
+                do_eval_constraints(h, x.data(), &fc, Ec.data());
                 for (int64_t i = 0; i < m; ++i) v1 += std::max(0.0, std::max(Ec[i] - h->c_ub[i], h->c_lb[i] - Ec[i]));
                 for (int64_t j = 0; j < n; ++j) v1 += std::max(0.0, std::max(x[j] - h->v_ub[j], h->v_lb[j] - x[j]));
                 if (v1 <= o.tol_infeas) ret = 6;
@@ -4390,7 +4413,7 @@ struct SlpRunTR {
             asmb::barrier(930);
             compute_nu();                                                                                 // :152
             double nrm[4];
-            chk(asm_slp_norms(h, lam.data(), mU.data(), mL.data(), nrm), "asm_slp_norms");             // :154-156, this LP's multipliers
+            do_slp_norms(h, lam.data(), mU.data(), mL.data(), nrm);                                     // :154-156, this LP's multipliers
             prim_infeas = nrm[0]; dual_infeas = nrm[2]; compl_ = nrm[3];
             double pmax = 0.0;
             for (int64_t j = 0; j < n; ++j) pmax = std::max(pmax, std::fabs(p[j]));
@@ -4410,16 +4433,8 @@ struct SlpRunTR {
             }
             iter += 1;
         }
-        // :198: objective at the final point
-        double f_end = 0.0;
-        vec Et(std::max<int64_t>(m, 1));
-        asmb::barrier(995);
-        chk(asm_eval_constraints(h, x.data(), &f_end, Et.data()), "asm_eval_constraints");
+        finish(995, 0);
         info.delta = Delta;
-        if (res) {
-            res->status = ret; res->iter = iter; res->lp_solves = lp_solves; res->restoration_solves = fr_solves; res->ls_trials = 0;
-            res->obj_val = f_end; res->prim_infeas = prim_infeas; res->dual_infeas = dual_infeas; res->compl_ = compl_;
-        }
     }
 };
 
@@ -4433,11 +4448,7 @@ void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const 
     if (res) std::memset(res, 0, sizeof(*res));
     SlpRunTR r(h, *par, tr_size, res);
     r.run(x0);
-    if (x_out) std::memcpy(x_out, r.x.data(), h->n * sizeof(double));
-    if (lambda && h->m) std::memcpy(lambda, r.lam.data(), h->m * sizeof(double));
-    if (mult_x_U) std::memcpy(mult_x_U, r.mU.data(), h->n * sizeof(double));
-    if (mult_x_L) std::memcpy(mult_x_L, r.mL.data(), h->n * sizeof(double));
-    if (g_out && h->m) std::memcpy(g_out, r.E.data(), h->m * sizeof(double));
+    r.outputs(x_out, lambda, mult_x_U, mult_x_L, g_out);
     if (tr) *tr = r.info;
 }
 
@@ -4465,24 +4476,9 @@ struct asm_batch {
 };
 
 namespace {
-template <class F>
-int bguarded(asm_batch* b, F&& fn) {
-    if (!b) return ASM_ERR_ARG;
-    try {
-        fn();
-        return ASM_OK;
-    } catch (const HipError& e) { b->err = e.what(); return ASM_ERR_HIP; }
-    catch (const asmb::BatchError& e) { b->err = e.what(); return ASM_ERR_HIP; }
-    catch (const std::invalid_argument& e) { b->err = e.what(); return ASM_ERR_ARG; }
-    catch (const std::logic_error& e) { b->err = e.what(); return ASM_ERR_STATE; }
-    catch (const std::exception& e) { b->err = e.what(); return ASM_ERR_ARG; }
-}
-void bcheck(asm_batch* b, int slot, int rc, const char* what) {
-    if (rc != ASM_OK) throw HipError(std::string(what) + " (slot " + std::to_string(slot) + "): " + b->slots[slot]->err);
-}
-// run `work(slot)` for every slot in [0, count): the slots of a group are fibers of the group's thread, launches merged across them
+// run `work(slot)` as step `step` for every slot in [0, count): the slots of a group are fibers of the group's thread, launches merged across them
 template <class W>
-void run_fibers(asm_batch* b, int count, W&& work) {
+void run_fibers(asm_batch* b, int count, const char* step, W&& work) {
     const double t0 = asmb::Sched::now_ms();
     auto run_group = [&](BatchGroup* g) {
         try {
@@ -4490,7 +4486,7 @@ void run_fibers(asm_batch* b, int count, W&& work) {
             asmb::Sched& S = g->sched;
             for (asmb::Fiber* f : S.fibers) { if (f->stack) munmap(f->stack, f->stack_size); delete f; }
             S.fibers.clear();
-            for (int s = g->lo; s < std::min(g->hi, count); ++s) S.add_fiber([&work, s] { work(s); });
+            for (int s = g->lo; s < std::min(g->hi, count); ++s) S.add_fiber([&work, step, s] { in_slot(step, s, [&] { work(s); }); });
             if (!S.fibers.empty()) S.run();
         } catch (...) {
             g->err = std::current_exception();
@@ -4600,7 +4596,7 @@ int asm_batch_create(int device, int n_slots, asm_batch** out) {
             if (const char* v = std::getenv("ASM_BATCH_VERBOSE")) b->verbose = v[0] == '1';
             b->time_panels = b->slots[0]->knobs.timing != 0;      // ASM_HIP_TIMING as the slots read it
             batch_make_groups(b, ng);
-        } catch (const std::exception&) { rc = ASM_ERR_HIP; }
+        } catch (...) { rc = error_code(b->err); }
     }
     if (rc != ASM_OK) {
         batch_free_groups(b);
@@ -4623,7 +4619,7 @@ int asm_batch_destroy(asm_batch* b) {
 }
 
 int asm_batch_set_groups(asm_batch* b, int n_groups) {
-    return bguarded(b, [&] {
+    return guarded(b, [&] {
         if (n_groups < 1) throw std::invalid_argument("asm_batch_set_groups: at least one group");
         batch_make_groups(b, n_groups);
     });
@@ -4636,8 +4632,9 @@ asm_handle* asm_batch_handle(asm_batch* b, int slot) { return (b && slot >= 0 &&
 
 int asm_batch_setup(asm_batch* b, int64_t n, int64_t m, int64_t nnz, const int64_t* j_row, const int64_t* j_col, const double* c_lb, const double* c_ub,
                     const double* v_lb, const double* v_ub) {
-    return bguarded(b, [&] {
-        for (size_t s = 0; s < b->slots.size(); ++s) bcheck(b, (int)s, asm_sublp_setup(b->slots[s], n, m, nnz, j_row, j_col, c_lb, c_ub, v_lb, v_ub), "asm_sublp_setup");
+    return guarded(b, [&] {
+        for (size_t s = 0; s < b->slots.size(); ++s)
+            in_slot("asm_sublp_setup", (int)s, [&] { do_setup(b->slots[s], n, m, nnz, j_row, j_col, c_lb, c_ub, v_lb, v_ub); });
         b->J_ref.clear();
         b->setup_done = true;
     });
@@ -4647,19 +4644,22 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
                          const int64_t* q_v1, const int64_t* q_v2, const double* q_coef, const double* constant, const int64_t* jac_off, const int64_t* g_ptr,
                          const int64_t* g_kind, const double* g_coef, const int64_t* g_other, double objective_scale, int nlp_kind, int64_t nlp_rows,
                          int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
-    return bguarded(b, [&] {
+    return guarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_eval_setup: asm_batch_setup first");
         for (size_t s = 0; s < b->slots.size(); ++s)
-            bcheck(b, (int)s, asm_eval_setup(b->slots[s], n_rows, aff_ptr, aff_var, aff_coef, quad_ptr, q_v1, q_v2, q_coef, constant, jac_off, g_ptr, g_kind, g_coef,
-                                             g_other, objective_scale, nlp_kind, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, nlp_dpar, n_dpar), "asm_eval_setup");
+            in_slot("asm_eval_setup", (int)s, [&] {
+                do_eval_setup(b->slots[s], n_rows, aff_ptr, aff_var, aff_coef, quad_ptr, q_v1, q_v2, q_coef, constant, jac_off, g_ptr, g_kind, g_coef, g_other,
+                              objective_scale, nlp_kind, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, nlp_dpar, n_dpar);
+            });
     });
 }
 
 int asm_batch_set_ns_basis(asm_batch* b, const int32_t* J, int64_t k) {
-    return bguarded(b, [&] {
-        if (!b->setup_done || k < 0 || (k > 0 && !J)) throw std::invalid_argument("asm_batch_set_ns_basis: setup first / bad argument");
+    return guarded(b, [&] {
+        if (k < 0 || (k > 0 && !J)) throw std::invalid_argument("asm_batch_set_ns_basis: bad argument");
+        if (!b->setup_done) throw std::logic_error("asm_batch_set_ns_basis: asm_batch_setup first");
+        for (size_t s = 0; s < b->slots.size(); ++s) in_slot("asm_sublp_set_ns_basis", (int)s, [&] { do_set_ns_basis(b->slots[s], J, k); });
         b->J_ref.assign(J, J + k);
-        for (size_t s = 0; s < b->slots.size(); ++s) bcheck(b, (int)s, asm_sublp_set_ns_basis(b->slots[s], J, k), "asm_sublp_set_ns_basis");
     });
 }
 
@@ -4667,20 +4667,20 @@ int asm_batch_set_ns_basis(asm_batch* b, const int32_t* J, int64_t k) {
 int asm_batch_sublp_solve(asm_batch* b, int count, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* dE,
                           const double* df, const double* f, const double* E, const double* x_k, const double* delta, const int32_t* feasibility, double* p,
                           double* lambda, double* mult_x_U, double* mult_x_L, double* p_slack, int32_t* status) {
-    return bguarded(b, [&] {
+    return guarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_sublp_solve: asm_batch_setup first");
         if (count < 1 || count > (int)b->slots.size() || !dE || !df || !f || !x_k || !delta || !feasibility || !p || !mult_x_U || !mult_x_L || !status)
             throw std::invalid_argument("asm_batch_sublp_solve: bad count or null pointer");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nnz = b->slots[0]->nnz;
         if (m > 0 && (!E || !lambda || !p_slack)) throw std::invalid_argument("asm_batch_sublp_solve: null pointer");
         HIPCHK(hipSetDevice(b->device));
-        run_fibers(b, count, [&](int s) {
+        run_fibers(b, count, "asm_sublp_solve", [&](int s) {
             asm_handle* h = b->slots[s];
-            if (c_lb && c_ub && v_lb && v_ub) bcheck(b, s, asm_sublp_set_bounds(h, c_lb + s * m, c_ub + s * m, v_lb + s * n, v_ub + s * n), "asm_sublp_set_bounds");
+            if (c_lb && c_ub && v_lb && v_ub) do_set_bounds(h, c_lb + s * m, c_ub + s * m, v_lb + s * n, v_ub + s * n);
             asmb::next_cycle();
-            bcheck(b, s, asm_sublp_solve(h, dE + s * nnz, df + s * n, f[s], E ? E + s * m : nullptr, x_k + s * n, delta[s], feasibility[s], p + s * n,
-                                         lambda ? lambda + s * m : nullptr, mult_x_U + s * n, mult_x_L + s * n, p_slack ? p_slack + s * 2 * m : nullptr, status + s),
-                   "asm_sublp_solve");
+            do_upload(h, dE + s * nnz, df + s * n, f[s], E ? E + s * m : nullptr, x_k + s * n);
+            do_solve(h, delta[s], feasibility[s], p + s * n, lambda ? lambda + s * m : nullptr, mult_x_U + s * n, mult_x_L + s * n,
+                     p_slack ? p_slack + s * 2 * m : nullptr, status + s);
         });
     });
 }
@@ -4691,7 +4691,7 @@ namespace {
 // n_scen complete SLP runs of one algorithm: the slots' fibers take the scenarios in index order; every array has a leading scenario dimension.
 // run_one(h, sc) solves scenario sc on handle h (bounds and basis columns already set).
 template <class RunOne>
-void batch_slp_runs(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
+void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
                     const double* x0, asm_slp_result* res, RunOne&& run_one) {
     const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
     HIPCHK(hipSetDevice(b->device));
@@ -4699,29 +4699,26 @@ void batch_slp_runs(asm_batch* b, int64_t n_scen, const double* c_lb, const doub
         // reference selection of the null-space basis columns: one LP of scenario 0 at its start point on slot 0 (cold selection); EVERY
         // scenario, 0 included, then starts from these columns - the results do not depend on the slot or on what it solved before
         asm_handle* h0 = b->slots[0];
-        bcheck(b, 0, asm_sublp_set_bounds(h0, c_lb, c_ub, v_lb, v_ub), "asm_sublp_set_bounds");
-        h0->hint[0].ns_J.clear();
-        vec xs(n), dfs(n), Es(std::max<int64_t>(m, 1)), pp(n), ll(std::max<int64_t>(m, 1)), uu(n), lo(n), sl(2 * std::max<int64_t>(m, 1));
-        for (int64_t j = 0; j < n; ++j) {
-            double v = x0[j];
-            if (v_lb[j] > -INF) v = std::max(v, v_lb[j]);
-            if (v_ub[j] > -INF) v = std::min(v, v_ub[j]);
-            xs[j] = v;
-        }
-        double f0 = 0.0;
-        int32_t st0 = 0;
-        bcheck(b, 0, asm_eval_functions(h0, xs.data(), &f0, dfs.data(), Es.data()), "asm_eval_functions");
-        bcheck(b, 0, asm_sublp_solve_resident(h0, 1000.0, 0, pp.data(), ll.data(), uu.data(), lo.data(), sl.data(), &st0), "asm_sublp_solve_resident");
+        in_slot(step, 0, [&] {
+            do_set_bounds(h0, c_lb, c_ub, v_lb, v_ub);
+            h0->hint[0].ns_J.clear();
+            vec xs(n), dfs(n), Es(std::max<int64_t>(m, 1)), pp(n), ll(std::max<int64_t>(m, 1)), uu(n), lo(n), sl(2 * std::max<int64_t>(m, 1));
+            clamp_start(n, x0, v_lb, v_ub, xs.data());
+            double f0 = 0.0;
+            int32_t st0 = 0;
+            do_eval_functions(h0, xs.data(), &f0, dfs.data(), Es.data());
+            do_solve(h0, 1000.0, 0, pp.data(), ll.data(), uu.data(), lo.data(), sl.data(), &st0);
+        });
         b->J_ref = h0->hint[0].ns_J;
     }
     const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
     std::atomic<int64_t> next{0};
-    run_fibers(b, count, [&](int s) {
+    run_fibers(b, count, step, [&](int s) {
         asm_handle* h = b->slots[s];
         for (;;) {
             const int64_t sc = next.fetch_add(1);
             if (sc >= n_scen) break;
-            bcheck(b, s, asm_sublp_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n), "asm_sublp_set_bounds");
+            do_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n);
             // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
             if (!b->J_ref.empty()) h->hint[0].ns_J = b->J_ref;
             else h->hint[0].ns_J.clear();
@@ -4737,11 +4734,11 @@ extern "C" {
 // n_scen complete SLP runs (Line Search)
 int asm_batch_slp_run(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* x0,
                       const asm_slp_params* par, double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res) {
-    return bguarded(b, [&] {
+    return guarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_slp_run: asm_batch_setup first");
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run: bad argument");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
-        batch_slp_runs(b, n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
+        batch_slp_runs(b, "asm_slp_run", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_ls(h, par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
                        mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc);
         });
@@ -4752,12 +4749,12 @@ int asm_batch_slp_run(asm_batch* b, int64_t n_scen, const double* c_lb, const do
 int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* x0,
                          const asm_slp_params* par, double tr_size, double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g,
                          asm_slp_result* res, asm_slp_tr_info* tr) {
-    return bguarded(b, [&] {
+    return guarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_slp_run_tr: asm_batch_setup first");
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run_tr: bad argument");
         check_tr_size(tr_size, "asm_batch_slp_run_tr");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
-        batch_slp_runs(b, n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
+        batch_slp_runs(b, "asm_slp_run_tr", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_tr(h, par, tr_size, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
                        mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc, tr ? tr + sc : nullptr);
         });

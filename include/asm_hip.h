@@ -31,7 +31,9 @@ typedef struct asm_handle asm_handle;
 /* MOI.TerminationStatusCode values this path can produce (subproblem.jl:491, 500-539). */
 enum { ASM_OPTIMAL = 1, ASM_INFEASIBLE = 2, ASM_DUAL_INFEASIBLE = 3, ASM_OTHER = 4 };
 
-/* error codes */
+/* error codes: ASM_ERR_ARG a bad argument (null pointer, size, value), ASM_ERR_HIP a device or HIP runtime failure, ASM_ERR_STATE a missing
+ * earlier call (asm_sublp_setup, asm_eval_setup, asm_eval_functions), ASM_ERR_UNSUPPORTED valid input the library cannot represent (an LP
+ * skeleton the reference cannot build).  A batch entry returns the code the per-handle entry returns for the same input. */
 enum { ASM_OK = 0, ASM_ERR_ARG = -1, ASM_ERR_HIP = -2, ASM_ERR_STATE = -3, ASM_ERR_UNSUPPORTED = -11 };
 
 /* Replaces `MOI.instantiate(slp.options.external_optimizer)` (slp.jl:32). */

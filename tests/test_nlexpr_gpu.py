@@ -106,8 +106,14 @@ def _with_ipar(fm, ipar, dpar=None):
 
 
 def test_eval_setup_rejects_malformed_tapes_and_keeps_the_handle():
-    """Each malformed tape returns ASM_ERR_ARG with a message; the handle keeps its evaluator and a valid tape is accepted after."""
-    from activesetmethods_amd import AsmHipError
+    """Each malformed tape returns ASM_ERR_ARG with a message, from asm_eval_setup and from asm_batch_eval_setup (whose message names the
+    slot); the handle keeps its evaluator and a valid tape is accepted after.  asm_eval_functions: ASM_ERR_ARG for a null x, ASM_ERR_STATE
+    before asm_eval_setup."""
+    import copy
+    import ctypes as C
+    import activesetmethods_amd as A
+    from activesetmethods_amd import AsmHipError, _lib, batch
+    lib = _lib.load()
     fm = problems.hs071_function_model()
     pr = fm.to_problem()
     opt = _handle_for(pr)
@@ -140,16 +146,26 @@ def test_eval_setup_rejects_malformed_tapes_and_keeps_the_handle():
         with pytest.raises(AsmHipError, match="error -1") as ei:
             opt.eval_setup(_with_ipar(fm, ip))
         assert "expression block" in str(ei.value) or "ipar" in str(ei.value), (name, str(ei.value))
+        bad_pr = copy.copy(pr)
+        bad_pr.function_model = _with_ipar(fm, ip)
+        with pytest.raises(AsmHipError, match=r"batch error -1: asm_eval_setup \(slot 0\): ") as eb:
+            batch.HipBatch(bad_pr, 2)
+        assert "expression block" in str(eb.value) or "ipar" in str(eb.value), (name, str(eb.value))
         after = opt.eval_functions(x)
         assert after[0] == before[0] and all(np.array_equal(u, v) for u, v in zip(after[1:], before[1:])), name
     opt.eval_setup(_with_ipar(fm, tape()))
     again = opt.eval_functions(x)
     assert again[0] == before[0] and np.array_equal(again[1], before[1]) and np.array_equal(again[2], before[2])
+    f, df, E = C.c_double(0.0), np.zeros(pr.n), np.zeros(pr.m)
+    xc = np.ascontiguousarray(x)
+    assert lib.asm_eval_functions(opt._h, None, C.byref(f), _lib.dptr(df), _lib.dptr(E)) == -1        # ASM_ERR_ARG: null x
     opt.close()
+    fresh = A.HipSubOptimizer(A.QpData(np.zeros(pr.n), 0.0, np.zeros(pr.nnz), np.zeros(pr.m), pr.g_L, pr.g_U, pr.x_L, pr.x_U), pr.j_row, pr.j_col)
+    assert lib.asm_eval_functions(fresh._h, _lib.dptr(xc), C.byref(f), _lib.dptr(df), _lib.dptr(E)) == -3   # ASM_ERR_STATE: no evaluator
+    fresh.close()
     # the same entries as the tape's pattern, in another order: not the pattern of a sorted row
     jc = pr.j_col.copy()
     jc[[0, 1]] = jc[[1, 0]]
-    import activesetmethods_amd as A
     opt = A.HipSubOptimizer(A.QpData(np.zeros(pr.n), 0.0, np.zeros(pr.nnz), np.zeros(pr.m), pr.g_L, pr.g_U, pr.x_L, pr.x_U), pr.j_row, jc)
     with pytest.raises(AsmHipError, match="error -1.*differs from the pattern"):
         opt.eval_setup(fm)

@@ -273,6 +273,61 @@ def test_resetup_across_skeletons_matches_fresh_handles(hip_lib):
         lib.asm_destroy(h)
 
 
+def test_batch_setup_rejections_return_the_handle_codes(hip_lib):
+    """asm_batch_setup returns what asm_sublp_setup returns for the same input - ASM_ERR_UNSUPPORTED for a free row, ASM_ERR_ARG for a j_row
+    out of range - with a message that names the step and the slot; after each, a valid set-up is accepted and a batch solve (normal phase,
+    then restoration) equals a fresh handle's bit for bit."""
+    import ctypes as C
+    from activesetmethods_amd import _lib
+    lib = hip_lib
+    sp = random_subproblem(7, 96, 48)
+    free = dict(sp); free['c_lb'] = sp['c_lb'].copy(); free['c_ub'] = sp['c_ub'].copy()
+    free['c_lb'][0], free['c_ub'][0] = -np.inf, np.inf
+    bad_row = dict(sp); bad_row['j_row'] = sp['j_row'].copy(); bad_row['j_row'][0] = sp['m'] + 1
+    n, m = sp['n'], sp['m']
+
+    def setup(b, d):
+        jr, jc = (np.ascontiguousarray(d[k], dtype=np.int64) for k in ('j_row', 'j_col'))
+        c_lb, c_ub, v_lb, v_ub = (np.ascontiguousarray(d[k], dtype=np.float64) for k in ('c_lb', 'c_ub', 'v_lb', 'v_ub'))
+        return lib.asm_batch_setup(b, d['n'], d['m'], len(jr), _lib.i64ptr(jr), _lib.i64ptr(jc), _lib.dptr(c_lb), _lib.dptr(c_ub), _lib.dptr(v_lb),
+                                   _lib.dptr(v_ub))
+
+    def batch_solves(b):           # _abi_solves through asm_batch_sublp_solve on slot 0
+        dE, df, E, x_k = (np.ascontiguousarray(sp[k], dtype=np.float64) for k in ('dE', 'df', 'E', 'x_k'))
+        f, delta, h0 = np.array([float(sp['f'])]), np.array([float(sp['delta'])]), lib.asm_batch_handle(b, 0)
+        outs = []
+        for feasibility in (0, 1):
+            p, lam, mU, mL, ps = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(n), np.zeros(2 * m)
+            st, fe = np.zeros(1, np.int32), np.array([feasibility], np.int32)
+            assert lib.asm_batch_sublp_solve(b, 1, None, None, None, None, _lib.dptr(dE), _lib.dptr(df), _lib.dptr(f), _lib.dptr(E), _lib.dptr(x_k),
+                                             _lib.dptr(delta), _lib.i32ptr(fe), _lib.dptr(p), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(ps),
+                                             _lib.i32ptr(st)) == 0, lib.asm_batch_last_error(b)
+            nr, nsl = C.c_int64(0), C.c_int64(0)
+            assert lib.asm_sublp_active_set(h0, None, None, None, C.byref(nr), C.byref(nsl)) == 0
+            rows, bnd, sl = np.zeros(nr.value, np.int32), np.zeros(n, np.int32), np.zeros(max(nsl.value, 1), np.int32)
+            assert lib.asm_sublp_active_set(h0, _lib.i32ptr(rows), _lib.i32ptr(bnd), _lib.i32ptr(sl), None, None) == 0
+            outs.append([int(st[0])] + [a.tobytes() for a in (p, lam, mU, mL, ps, rows, bnd, sl)])
+        return outs
+
+    g = C.c_void_p()
+    assert lib.asm_create(0, C.byref(g)) == 0
+    try:
+        assert _abi_setup(lib, g, sp) == 0
+        ref = _abi_solves(lib, g, sp)
+    finally:
+        lib.asm_destroy(g)
+    b = C.c_void_p()
+    assert lib.asm_batch_create(0, 2, C.byref(b)) == 0
+    try:
+        for rejected, rc in ((free, -11), (bad_row, -1)):      # ASM_ERR_UNSUPPORTED (free row), ASM_ERR_ARG (j_row out of range)
+            assert setup(b, rejected) == rc
+            assert lib.asm_batch_last_error(b).startswith(b"asm_sublp_setup (slot 0): "), lib.asm_batch_last_error(b)
+            assert setup(b, sp) == 0
+            assert batch_solves(b) == ref
+    finally:
+        lib.asm_batch_destroy(b)
+
+
 def _lp_properties(sp, out, opt, feasibility=False):
     """Size-independent checks of an OPTIMAL sub-LP solution against the LP it solves (normal phase):
     primal feasibility of rows and box, dual sign feasibility, stationarity df - J'lambda - mult = 0 on the
