@@ -313,11 +313,13 @@ struct asm_handle {
     int64_t *d_perm = nullptr, *d_ustart = nullptr, *d_uoff = nullptr, *d_adjoff = nullptr;
 
     // ---- device buffers ----
-    double *d_dE = nullptr, *d_J = nullptr, *d_Ah = nullptr, *d_S = nullptr;
+    double *d_dE = nullptr, *d_J = nullptr, *d_Ah = nullptr;
     double *d_c = nullptr, *d_rho = nullptr, *d_theta = nullptr, *d_diag = nullptr, *d_diag0 = nullptr;
     double *d_vecN = nullptr, *d_vecM = nullptr, *d_vecM2 = nullptr, *d_partial = nullptr;
-    double *d_Linv = nullptr, *d_Binv = nullptr, *d_BinvT = nullptr, *d_wpart = nullptr, *d_wt = nullptr;
-    int wb = 512;                  // wide-block width of the triangular solves
+    double *d_wpart = nullptr, *d_wt = nullptr;
+    // factor of the Newton systems of the row and column forms and of the active-set Gram matrices (Mp x Mp); its band is set by the build
+    // that fills it (0 = dense)
+    FacBuf main_fac;
     // column form: transposed copy of Ah (n x ldT), its chunk flags, work vectors
     bool col_capable = false, ahT_valid = false, nzT_valid = false;
     int64_t ldT = 0;
@@ -359,13 +361,12 @@ struct asm_handle {
     int col_band = 0;               // the same for the n columns (column form of the restoration-phase Newton system)
     int *d_colperm = nullptr, *d_colpos = nullptr, *d_colpairs = nullptr;
     int64_t n_colpairs = 0;
-    int main_band_cur = 0;          // band of the matrix now in the main factor buffers (set by the banded builds, 0 after every other build)
     double* d_AhTg = nullptr;       // transposed copy of a dense Ah for the products Ah'y (ldn rows of pitch Mp; made once per LP)
     bool ahTg_valid = false;
     double* d_redpart = nullptr;    // partial results / arrival counter of the multi-workgroup interior-point reductions
     unsigned* d_redcnt = nullptr;
-    int main_band = 0;              // band of the matrix in the main factor buffers (test hook asm_test_set_band; 0 = dense)
-    // test hook asm_test_set_factor: where the kernel hooks factor (0: the main buffers, 1: a factor buffer of their own made by
+    int test_band = 0;              // band of the matrices the kernel hooks load (test hook asm_test_set_band; 0 = dense)
+    // test hook asm_test_set_factor: where the kernel hooks factor (0: the main factor, 1: a factor buffer of their own made by
     // ns_alloc_factor with this band hint) and the guard settings they factor with (k_diag_prepare mode / rel / absv, chol threshold)
     int test_layout = 0, test_band_hint = 0, test_mode = 0;
     double test_rel = 0.0, test_abs = 0.0, test_thr = 1e-14;
@@ -455,25 +456,13 @@ void ns_alloc_factor(asm_handle* h, BufPool& pool, FacBuf& f, int64_t N, int ban
 // =====================================================================================================
 // device helpers
 // =====================================================================================================
+// The Cholesky / substitution launches work on the factor passed to them: matrix (lower triangle, pitch ld), inverses of its 64-wide diagonal
+// blocks, explicit inverses of its wide diagonal blocks and their transposes (FacBuf).
 struct Dev {
     asm_handle* h;
-    hipStream_t cur;                 // stream the factorisation kernels are launched on (h->stream, or the look-ahead stream)
-    double* solve_w = nullptr;       // buffer the wide-block substitution runs in (default d_vecM2)
-    const double* solve_src = nullptr;   // one-block systems: the right-hand side the forward product reads (no copy into solve_w first)
-    // the factor the Cholesky / substitution launches work on: matrix (lower triangle, pitch fld), inverses of its 64-wide diagonal
-    // blocks, explicit inverses of its wide diagonal blocks and their transposes.  Default: the handle's main buffers.
-    double *fS, *fLinv, *fBinv, *fBinvT;
-    int64_t fld;
-    int fwb;
-    bool fsmall = false;
-    int fband = 0;
-    explicit Dev(asm_handle* hh) : h(hh), cur(hh->stream) { use_main(); }
-    void use_main() { fS = h->d_S; fld = h->Mp; fLinv = h->d_Linv; fBinv = h->d_Binv; fBinvT = h->d_BinvT; fwb = h->wb; fsmall = false; fband = h->main_band > 0 ? h->main_band : h->main_band_cur; }
-    void use_factor(const FacBuf& f) { fS = f.S; fld = f.ld; fLinv = f.Linv; fBinv = f.Binv; fBinvT = f.BinvT; fwb = f.wb; fsmall = f.small; fband = f.band; }
-    // the matrix about to be built in the main buffers has this band (0 = dense)
-    void set_main_band(int b) { h->main_band_cur = b; if (fS == h->d_S) fband = h->main_band > 0 ? h->main_band : b; }
+    explicit Dev(asm_handle* hh) : h(hh) {}
     // first row that the columns [.., c1) of a banded matrix / factor cannot reach (the order Ms when the matrix is dense)
-    int rowlim(int Ms, int c1) const { return fband > 0 ? (int)std::min<int64_t>(Ms, round_up((int64_t)c1 + fband, 64)) : Ms; }
+    static int rowlim(const FacBuf& f, int Ms, int c1) { return f.band > 0 ? (int)std::min<int64_t>(Ms, round_up((int64_t)c1 + f.band, 64)) : Ms; }
 
     hipEvent_t get_event() {
         if (!h->event_pool.empty()) {
@@ -609,11 +598,11 @@ struct Dev {
     void gemv_n_dev(const double* A, const double* x, double* out) { launch_gemv_n(A, x, out); }
     void gemv_t_dev(const double* A, const double* y, double* out) { launch_gemv_t(A, y, out); }
     void syrk_dev(const int* idx_dev, int Ms, const double* theta_dev, const double* diag_dev) {
-        set_main_band(0);
+        h->main_fac.band = 0;
         const bool skip = h->nz_valid && idx_dev == nullptr && Ms == (int)h->M && pick_tile(Ms) == h->nz_T;
         int id = begin(ASM_K_SYRK, (skip ? h->nz_fraction : 1.0) * (double)Ms * (Ms + 1) * h->ldn,
                        8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(pick_tile(Ms), h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, diag_dev, h->d_S, h->Mp, 0, 0, -1,
+        launch_syrk(h->stream, pick_tile(Ms), h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, diag_dev, h->main_fac.S, h->main_fac.ld, 0, 0, -1,
                     skip ? h->d_nz : nullptr, h->nz_pitch);
         end(id);
     }
@@ -621,27 +610,29 @@ struct Dev {
     // chunk flags of the gathered row set (reduced row form of the interior-point system)
     // S[0:Ms,0:Ms] (lower) of the same matrix for a row list in the handle's reverse Cuthill-McKee order (asm_handle::row_band): banded,
     // built entry by entry from the structural pairs - cpos maps a row to its place in the list (-1: not in it).  The factorisation and the
-    // substitutions that follow stop at the band (main_band_cur).
+    // substitutions that follow stop at the band (the main factor's band).
     void schur_banded_dev(const int* cpos_dev, int Ms, const double* theta_dev, const double* diag_dev) {
+        FacBuf& f = h->main_fac;
         // the band plus what the blocked factorisation reads beyond it (an outer panel of CHOL_NBO columns, tile rounding)
-        const int64_t wz = std::min<int64_t>(round_up(h->row_band + 1, 64) + CHOL_NBO + 128, h->Mp);
-        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), 0, h->stream, h->d_S, h->Mp, Ms, (int)wz);
+        const int64_t wz = std::min<int64_t>(round_up(h->row_band + 1, 64) + CHOL_NBO + 128, f.ld);
+        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), 0, h->stream, f.S, f.ld, Ms, (int)wz);
         hipLaunchKernelGGL(k_schur_sparse, dim3((unsigned)((h->n_rowpairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowpairs, h->n_rowpairs, cpos_dev,
-                           h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), theta_dev, diag_dev, h->d_S, h->Mp, (const int*)nullptr);
-        set_main_band(h->row_band);
+                           h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), theta_dev, diag_dev, f.S, f.ld, (const int*)nullptr);
+        f.band = h->row_band;
     }
     // K = diag + Ah' diag(dinv) Ah (n x n, lower) with the COLUMNS in their reverse Cuthill-McKee order (asm_handle::col_band): the column form
     // of the restoration-phase Newton system, banded and built from the structural column pairs; `diag_place` is indexed by position
     void schur_banded_cols_dev(const double* dinv_dev, const double* diag_place) {
+        FacBuf& f = h->main_fac;
         const int n = (int)h->n;
-        const int64_t wz = std::min<int64_t>(round_up(h->col_band + 1, 64) + CHOL_NBO + 128, h->Mp);
-        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, h->d_S, h->Mp, n, (int)wz);
+        const int64_t wz = std::min<int64_t>(round_up(h->col_band + 1, 64) + CHOL_NBO + 128, f.ld);
+        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, f.S, f.ld, n, (int)wz);
         hipLaunchKernelGGL(k_schur_sparse, dim3((unsigned)((h->n_colpairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_colpairs, h->n_colpairs,
-                           (const int*)h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah), dinv_dev, diag_place, h->d_S, h->Mp, (const int*)h->d_sc_pos);
-        set_main_band(h->col_band);
+                           (const int*)h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah), dinv_dev, diag_place, f.S, f.ld, (const int*)h->d_sc_pos);
+        f.band = h->col_band;
     }
     void syrk_gathered_dev(const int* idx_dev, int Ms, const double* theta_dev, const double* diag_dev) {
-        set_main_band(0);
+        h->main_fac.band = 0;
         const int nch = (int)(h->ldn / ASM_KC);
         const int T = pick_tile(Ms), TS = 32 * T;
         const int nt = (Ms + TS - 1) / TS;
@@ -654,7 +645,7 @@ struct Dev {
             frac = executed_fraction(nz2, nt, nch);
         }
         int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * h->ldn, 8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(T, h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, diag_dev, h->d_S, h->Mp, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
+        launch_syrk(h->stream, T, h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, diag_dev, h->main_fac.S, h->main_fac.ld, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
         end(id);
     }
     // S[0:Ms,0:Ms] (lower, pitch ldS) = Ah[idx,:] diag(theta) Ah[idx,:]'  into an arbitrary buffer (null-space form: S0 = A_EF A_EF')
@@ -671,7 +662,7 @@ struct Dev {
             frac = executed_fraction(nz2, nt, nch, idx_dev == h->d_nsEidx ? 1 : -1);
         }
         int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * h->ldn, 8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(T, h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, nullptr, S, ldS, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
+        launch_syrk(h->stream, T, h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, nullptr, S, ldS, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
         end(id);
     }
     // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32
@@ -691,25 +682,25 @@ struct Dev {
         end(id);
     }
     // Rows of R (nrhs x ldr, zero beyond column Ms) are right-hand sides of  L x = r  (forward) and then  L' x = z  (backward) with the
-    // CURRENT factor (fS, its wide-block inverses) and its transposed copy Lt (same pitch).  Right-looking block substitution over the
+    // factor f (its matrix and wide-block inverses) and its transposed copy Lt (same pitch).  Right-looking block substitution over the
     // wide blocks: the block's solution is a product with the explicit inverse of the diagonal block, then ONE update of all the
     // remaining columns  R[:, rest] -= X_blk L[rest, blk]'  (K = the block width, every tile of the remainder in parallel) - both on the
     // matrix cores.  Forward: R -> X.  Backward (if Lt): X -> R.  The solution ends in R (backward) or X (forward only).
-    void trsm_rows(double* R, double* X, int64_t ldr, int nrhs, int Ms, const double* Lt) {
-        const int WB = fwb;
+    void trsm_rows(const FacBuf& f, double* R, double* X, int64_t ldr, int nrhs, int Ms, const double* Lt) {
+        const int WB = f.wb;
         const int nB = (Ms + WB - 1) / WB;
         for (int B = 0; B < nB; ++B) {
             const int b0 = B * WB, wv = std::min(WB, Ms - b0), b1 = b0 + wv, Kb = (int)round_up(wv, 32);
-            gemm_nt(R + b0, ldr, fBinv + (int64_t)B * WB * WB, WB, nullptr, 0, X + b0, ldr, nrhs, wv, Kb, 0);
-            if (b1 < Ms) gemm_nt(X + b0, ldr, fS + (int64_t)b1 * fld + b0, fld, R + b1, ldr, R + b1, ldr, nrhs, rowlim(Ms, b1) - b1, Kb, 1);
+            gemm_nt(R + b0, ldr, f.Binv + (int64_t)B * WB * WB, WB, nullptr, 0, X + b0, ldr, nrhs, wv, Kb, 0);
+            if (b1 < Ms) gemm_nt(X + b0, ldr, f.S + (int64_t)b1 * f.ld + b0, f.ld, R + b1, ldr, R + b1, ldr, nrhs, rowlim(f, Ms, b1) - b1, Kb, 1);
         }
         if (!Lt) return;
         for (int B = nB - 1; B >= 0; --B) {
             const int b0 = B * WB, wv = std::min(WB, Ms - b0), Kb = (int)round_up(wv, 32);
-            gemm_nt(X + b0, ldr, fBinvT + (int64_t)B * WB * WB, WB, nullptr, 0, R + b0, ldr, nrhs, wv, Kb, 0);
+            gemm_nt(X + b0, ldr, f.BinvT + (int64_t)B * WB * WB, WB, nullptr, 0, R + b0, ldr, nrhs, wv, Kb, 0);
             // rows of L in this block reach back `band` columns at most
-            const int c0 = fband > 0 ? std::max(0, (b0 - fband) / 64 * 64) : 0;
-            if (b0 > 0) gemm_nt(R + b0, ldr, Lt + (int64_t)c0 * fld + b0, fld, X + c0, ldr, X + c0, ldr, nrhs, b0 - c0, Kb, 1);
+            const int c0 = f.band > 0 ? std::max(0, (b0 - f.band) / 64 * 64) : 0;
+            if (b0 > 0) gemm_nt(R + b0, ldr, Lt + (int64_t)c0 * f.ld + b0, f.ld, X + c0, ldr, X + c0, ldr, nrhs, b0 - c0, Kb, 1);
         }
     }
     // out[i] = sum_j Ah_ij^2 thinv_j   (sparse patterns only)
@@ -736,13 +727,13 @@ struct Dev {
     }
     // S[0:n,0:n] (lower) = AhT diag(dinv) AhT' + diag(th)
     void syrk_col(const double* dinv_dev, const double* th_dev) {
-        set_main_band(0);
+        h->main_fac.band = 0;
         ensure_AhT();
         const int n = (int)h->n;
         const int nch = (int)(h->ldT / ASM_KC);
         const double frac = h->nzT_valid ? h->nzT_fraction : 1.0;
         int id = begin(ASM_K_SYRK, frac * (double)n * (n + 1) * h->ldT, 8.0 * (n * (double)h->ldT + 0.5 * n * (double)n));
-        launch_syrk(pick_tile(n), h->d_AhT, h->ldT, nullptr, 0, n, (int)h->ldT, dinv_dev, th_dev, h->d_S, h->Mp, 0, 0, -1,
+        launch_syrk(h->stream, pick_tile(n), h->d_AhT, h->ldT, nullptr, 0, n, (int)h->ldT, dinv_dev, th_dev, h->main_fac.S, h->main_fac.ld, 0, 0, -1,
                     h->nzT_valid ? h->d_nzT : nullptr, nch, frac);
         end(id);
     }
@@ -787,27 +778,23 @@ struct Dev {
             }
         return tot > 0 ? act / tot : 1.0;
     }
-    void chol_solve_dev(const double* rhs_dev, double* out_dev, int Ms) {
+    void chol_solve_dev(const FacBuf& f, const double* rhs_dev, double* out_dev, int Ms) {
         // the substitution runs in place in the caller's output buffer (w), z in d_vecM
-        if (fsmall && Ms <= ASM_SMALL_USE) {       // small systems: one workgroup, factor + inverses of its 64-wide diagonal blocks
-            hipLaunchKernelGGL(k_small_solve, dim3(1), dim3(1024), 0, h->stream, (const double*)fS, fld, (const double*)fLinv, Ms, rhs_dev, out_dev);
+        if (f.small && Ms <= ASM_SMALL_USE) {       // small systems: one workgroup, factor + inverses of its 64-wide diagonal blocks
+            hipLaunchKernelGGL(k_small_solve, dim3(1), dim3(1024), 0, h->stream, (const double*)f.S, f.ld, (const double*)f.Linv, Ms, rhs_dev, out_dev);
             return;
         }
         // a system of one wide block only READS its right-hand side (forward diagonal product); with more blocks the panel updates work in place
-        const bool one_block = Ms <= fwb;
+        const bool one_block = Ms <= f.wb;
         if (out_dev != rhs_dev && !one_block) HIPCHK(hipMemcpyAsync(out_dev, rhs_dev, Ms * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         int id = begin(ASM_K_TRSV, 2.0 * Ms * (double)Ms, 8.0 * Ms * (double)Ms);
-        solve_w = out_dev;
-        solve_src = one_block ? rhs_dev : nullptr;
-        solve_launches(Ms);
-        solve_src = nullptr;
-        solve_w = h->d_vecM2;
+        solve_launches(f, Ms, out_dev, one_block ? rhs_dev : out_dev);
         end(id);
     }
 
     static int pick_tile(int64_t Ms) { return Ms >= 3072 ? 4 : (Ms >= 768 ? 2 : 1); }
 
-    void launch_syrk(int T, const double* A, int64_t ld, const int* idx, int64_t row0, int Ms, int K, const double* theta,
+    void launch_syrk(hipStream_t s, int T, const double* A, int64_t ld, const int* idx, int64_t row0, int Ms, int K, const double* theta,
                      const double* diag, double* S, int64_t ldS, int64_t srow0, int mode, int MsB = -1,
                      const unsigned char* nz = nullptr, int nzpitch = 0, double nzfrac = -1.0, int nsplit = 1, int64_t ksplit = 0) {
         int TS = 32 * T;
@@ -826,27 +813,27 @@ struct Dev {
         double fl = (MsB == Ms && ntj == 0) ? (double)Ms * (Ms + 1) * K : 2.0 * ((double)Ms * MsB - 0.5 * (double)MsB * MsB) * K;
         if (nz) fl *= nzfrac >= 0.0 ? nzfrac : h->nz_fraction;
         // timed on the stream it is launched on (HIP events see only their own stream)
-        int kid = begin(ASM_K_SYRK_KERNEL, fl, 8.0 * ((double)(Ms + MsB) * K + (double)Ms * MsB), cur);
+        int kid = begin(ASM_K_SYRK_KERNEL, fl, 8.0 * ((double)(Ms + MsB) * K + (double)Ms * MsB), s);
         struct EndGuard { Dev* d; int id; ~EndGuard() { d->end(id); } } guard_{this, kid};
         if (T == 4 && mode == 1 && !nz && !idx && !theta && K % (2 * ASM_UPD_KC) == 0)      // Cholesky updates: their own kernel
-            hipLaunchKernelGGL(k_syrk_upd, dim3((unsigned)blocks), dim3(256), 0, cur, A, ld, row0, Ms, K, S, ldS, srow0, MsB, ntj);
+            hipLaunchKernelGGL(k_syrk_upd, dim3((unsigned)blocks), dim3(256), 0, s, A, ld, row0, Ms, K, S, ldS, srow0, MsB, ntj);
         else if (T == 4 && mode == 1 && !nz && K % 16 == 0)      // 16-wide k-chunks, two workgroups per CU
-            hipLaunchKernelGGL((k_syrk<4, 8, 16, 4>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, cur, A, ld, idx, row0, Ms, K, theta, diag, S,
+            hipLaunchKernelGGL((k_syrk<4, 8, 16, 4>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
                                ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
         else if (T == 4)
-            hipLaunchKernelGGL((k_syrk<4, 8, 32, 2>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, cur, A, ld, idx, row0, Ms, K, theta, diag, S,
+            hipLaunchKernelGGL((k_syrk<4, 8, 32, 2>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
                                ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
         else if (T == 2)
-            hipLaunchKernelGGL((k_syrk<2, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, cur, A, ld, idx, row0, Ms, K, theta, diag, S,
+            hipLaunchKernelGGL((k_syrk<2, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
                                ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
         else
-            hipLaunchKernelGGL((k_syrk<1, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, cur, A, ld, idx, row0, Ms, K, theta, diag, S,
+            hipLaunchKernelGGL((k_syrk<1, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
                                ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
     }
 
     // S[0:Ms,0:Ms] (lower) = Ah[idx,:] diag(theta) Ah[idx,:]' + diag     idx == nullptr -> identity
     void syrk(const int* idx_host, int Ms, const double* theta, const double* diag) {
-        set_main_band(0);
+        h->main_fac.band = 0;
         h2d(h->d_theta, theta, h->n, h->ldn);
         if (diag) h2d(h->d_diag, diag, Ms, Ms);
         if (idx_host) {
@@ -864,39 +851,36 @@ struct Dev {
                                nch, nz2, nch, (const int*)h->d_idx);
         const double frac = skip ? executed_fraction(nz2, nt, nch) : 1.0;
         int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * h->ldn, 8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(T, h->d_Ah, h->ldn, idx_host ? h->d_idx : nullptr, 0, Ms, (int)h->ldn, h->d_theta,
-                    diag ? h->d_diag : nullptr, h->d_S, h->Mp, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
+        launch_syrk(h->stream, T, h->d_Ah, h->ldn, idx_host ? h->d_idx : nullptr, 0, Ms, (int)h->ldn, h->d_theta,
+                    diag ? h->d_diag : nullptr, h->main_fac.S, h->main_fac.ld, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
         end(id);
     }
-    void diag_prepare(int Ms, int mode, double rel, double absv) {
-        hipLaunchKernelGGL(k_diag_prepare, dim3(1), dim3(1024), 0, h->stream, fS, fld, Ms, h->d_diag0, mode, rel, absv);
+    void diag_prepare(const FacBuf& f, int Ms, int mode, double rel, double absv) {
+        hipLaunchKernelGGL(k_diag_prepare, dim3(1), dim3(1024), 0, h->stream, f.S, f.ld, Ms, h->d_diag0, mode, rel, absv);
     }
     template <int WB>
-    void trtri_launches(int Ms) {
+    void trtri_launches(const FacBuf& f, int Ms) {
         constexpr int WSUB = WB / ASM_NB;
         const unsigned nW = (unsigned)((Ms + WB - 1) / WB);
-        hipLaunchKernelGGL((k_trtri_init<WB>), dim3(nW, WSUB * WSUB), dim3(256), 0, h->stream, fLinv, Ms, fBinv);
+        hipLaunchKernelGGL((k_trtri_init<WB>), dim3(nW, WSUB * WSUB), dim3(256), 0, h->stream, f.Linv, Ms, f.Binv);
         for (int hh = 1; hh < WSUB; hh *= 2)
             for (int stage = 0; stage < 2; ++stage)
                 hipLaunchKernelGGL((k_trtri_level<WB>), dim3(nW, (unsigned)(WSUB / (2 * hh)), (unsigned)(hh * hh)), dim3(256), 0, h->stream,
-                                   fS, fld, Ms, fBinv, fBinvT, hh, stage);
-        hipLaunchKernelGGL((k_transpose_wb<WB>), dim3(nW, WSUB * WSUB), dim3(256), 0, h->stream, fBinv, fBinvT);
+                                   f.S, f.ld, Ms, f.Binv, f.BinvT, hh, stage);
+        hipLaunchKernelGGL((k_transpose_wb<WB>), dim3(nW, WSUB * WSUB), dim3(256), 0, h->stream, f.Binv, f.BinvT);
     }
     // want_inverse = false: the caller only solves against the factor and the factor is a "small" one (one-workgroup solves): the
     // explicit inverses of the wide blocks are not built
-    bool panel_inv_now = false;      // the panel launches of the factorisation in progress also make the explicit inverse
-    void chol(int Ms, double thr = 1e-14, bool want_inverse = true) {
+    void chol(const FacBuf& f, int Ms, double thr = 1e-14, bool want_inverse = true) {
         if (Ms <= 0) return;
         // a banded factor (band b) costs about Ms (b + 64)^2 flops and touches Ms (b + 64) entries, not Ms^3 / 3 and Ms^2 / 2
-        const double bw = fband > 0 ? (double)std::min<int64_t>(Ms, (int64_t)fband + 64) : (double)Ms;
-        int id = begin(ASM_K_CHOL, fband > 0 ? (double)Ms * bw * bw : (double)Ms * Ms * Ms / 3.0, 8.0 * 1.5 * Ms * bw);
-        const bool skip_inv = !want_inverse && fsmall && Ms <= ASM_SMALL_USE;
+        const double bw = f.band > 0 ? (double)std::min<int64_t>(Ms, (int64_t)f.band + 64) : (double)Ms;
+        int id = begin(ASM_K_CHOL, f.band > 0 ? (double)Ms * bw * bw : (double)Ms * Ms * Ms / 3.0, 8.0 * 1.5 * Ms * bw);
+        const bool skip_inv = !want_inverse && f.small && Ms <= ASM_SMALL_USE;
         // a factor of ONE wide block gets its explicit inverse inside the panel launches (helper workgroups of k_chol_panel_inv)
-        panel_inv_now = !skip_inv && Ms <= fwb && fband == 0 && fBinv && fBinvT && panel_inv_grid(Ms) <= h->panel_wgs;
-        const bool inv_done = panel_inv_now;
-        chol_launches(Ms, thr);
-        panel_inv_now = false;
-        if (skip_inv || inv_done) {
+        const bool panel_inv = !skip_inv && Ms <= f.wb && f.band == 0 && f.Binv && f.BinvT && panel_inv_grid(Ms) <= h->panel_wgs;
+        chol_launches(f, Ms, thr, panel_inv);
+        if (skip_inv || panel_inv) {
             end(id);
             h->stats.nfact += 1;
             return;
@@ -904,11 +888,11 @@ struct Dev {
         // explicit inverses of the wide diagonal blocks by divide and conquer over the 64-wide sub-blocks: diagonal
         // blocks from the panel kernels, then log2 levels of two launches each (the scratch T uses the buffer of the
         // transposed copy, which is written afterwards)
-        if (fwb == 1024) trtri_launches<1024>(Ms); else trtri_launches<512>(Ms);
+        if (f.wb == 1024) trtri_launches<1024>(f, Ms); else trtri_launches<512>(f, Ms);
         end(id);
         h->stats.nfact += 1;
     }
-    // the largest grid of the k_chol_panel_inv launches of a factor of one wide block (Ms <= fwb <= CHOL_NBO: the inner panels of chol_chain's
+    // the largest grid of the k_chol_panel_inv launches of a factor of one wide block (Ms <= wb <= CHOL_NBO: the inner panels of chol_chain's
     // only outer panel): G row-tile workgroups + one helper per 64 x 64 tile of the block rows a launch finishes.  All of them must be resident
     // within the handle's budget (a batch slot: its group's share); at most ASM_PNL_WT + ASM_PNL_NS * ASM_PNL_WT = 176, 144 for Ms <= 1024
     int panel_inv_grid(int Ms) const {
@@ -922,14 +906,15 @@ struct Dev {
         return grid;
     }
     // block chain of one outer panel [K0, K1): 64-wide potrf / panel solve steps whose rank-64 updates stay inside a
-    // 512-wide inner panel; the rest of the outer panel is updated once per inner panel with K = 512
-    void chol_chain(int Ms, double thr, int K0, int K1, bool beside_updates = false) {
+    // 512-wide inner panel; the rest of the outer panel is updated once per inner panel with K = 512.  Launched on stream s; panel_inv: the
+    // panel launches also make the explicit inverse of the factor's one wide block
+    void chol_chain(const FacBuf& f, int Ms, double thr, int K0, int K1, hipStream_t s, bool panel_inv, bool beside_updates = false) {
         for (int I0 = K0, Inext = K0; I0 < K1; I0 = Inext) {
             // a remainder of at most two 64-wide steps joins the last inner panel (k = 519: one launch of nine steps instead of a panel launch, an
             // in-panel update and a second panel launch for the last seven columns)
             const int I1 = (K1 - I0 <= CHOL_NBI + 2 * ASM_NB) ? K1 : std::min(I0 + CHOL_NBI, K1);
             Inext = I1;
-            const int Mi = rowlim(Ms, I1);           // banded factor: the rows below are out of this inner panel's reach
+            const int Mi = rowlim(f, Ms, I1);           // banded factor: the rows below are out of this inner panel's reach
             {      // (scope of the panel launch's timing region: it ends before the update of the rest of the outer panel)
                 // the <= 8 steps of this inner panel in one dataflow launch (k_chol_panel): row tiles are owned by workgroups,
                 // diagonal-block factors and the panel tiles other workgroups need travel through release / acquire flags
@@ -946,42 +931,41 @@ struct Dev {
                     const double r = std::max(0, Mi - (k0 + ASM_NB)), w = std::max(0, std::min(I1, Mi) - (k0 + ASM_NB));
                     pfl += 2.0 / 3.0 * ASM_NB * ASM_NB * ASM_NB + 2.0 * r * ASM_NB * ASM_NB + 2.0 * ASM_NB * (r * w - 0.5 * w * w);
                 }
-                int pid = begin(ASM_K_PANEL_KERNEL, pfl, 8.0 * 2.0 * (double)(Mi - I0) * (double)(std::min(I1, Mi) - I0), cur);
+                int pid = begin(ASM_K_PANEL_KERNEL, pfl, 8.0 * 2.0 * (double)(Mi - I0) * (double)(std::min(I1, Mi) - I0), s);
                 struct PEnd { Dev* d; int id; ~PEnd() { d->end(id); } } pend_{this, pid};
                 // beside the trailing update the register-capped build must be used (its wavefronts have to fit into freed update slots)
-                if (panel_inv_now && !beside_updates) {
+                if (panel_inv && !beside_updates) {
                     // one wide block: its explicit inverse is made inside the launch by helper workgroups, one per 64 x 64 tile of the block
                     // rows this inner panel finishes (k_chol_panel_inv) - no k_trtri_* launches afterwards
                     const int nst = (std::min(I1, Ms) - I0 + ASM_NB - 1) / ASM_NB, T = (Ms + ASM_NB - 1) / ASM_NB;
-                    asmb::launch_resident(k_chol_panel_inv, dim3((unsigned)(G + nst * T)), dim3(256), 0, cur, fS, fld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
-                                       fLinv, h->d_pflags, h->d_ptmo, h->panel_epoch, fBinv, fBinvT, fwb, G);
+                    asmb::launch_resident(k_chol_panel_inv, dim3((unsigned)(G + nst * T)), dim3(256), 0, s, f.S, f.ld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
+                                       f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch, f.Binv, f.BinvT, f.wb, G);
                 } else if (beside_updates)
-                    asmb::launch_resident(k_chol_panel, dim3((unsigned)G), dim3(256), 0, cur, fS, fld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
-                                       fLinv, h->d_pflags, h->d_ptmo, h->panel_epoch);
+                    asmb::launch_resident(k_chol_panel, dim3((unsigned)G), dim3(256), 0, s, f.S, f.ld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
+                                       f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch);
                 else
-                    asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), 0, cur, fS, fld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
-                                       fLinv, h->d_pflags, h->d_ptmo, h->panel_epoch);
+                    asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), 0, s, f.S, f.ld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
+                                       f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch);
             }
             if (I1 < K1 && I1 < Mi) {
                 int rem = Mi - I1;
-                launch_syrk(pick_tile(rem), fS + I0, fld, nullptr, I1, rem, I1 - I0, nullptr, nullptr, fS, fld, I1, 1, std::min(K1 - I1, rem));
+                launch_syrk(s, pick_tile(rem), f.S + I0, f.ld, nullptr, I1, rem, I1 - I0, nullptr, nullptr, f.S, f.ld, I1, 1, std::min(K1 - I1, rem));
             }
         }
     }
     // Banded factor, every inner panel with its whole trailing update in ONE launch (k_chol_panel_band): no rank-K launches between the panels.
     // Possible when a panel and the band's reach fit ASM_PNL_NRT row tiles and the workgroups (one per row tile + one per trailing tile) are
     // all resident; a batch slot keeps the launch sequence (its panel launches are merged across scenarios).
-    bool band_panels_ok(int Ms) const {
-        if (fband <= 0 || h->batch_slot || Ms <= CHOL_NBI + 2 * ASM_NB) return false;
-        const int nrt = (CHOL_NBI + 2 * ASM_NB + (int)round_up(fband, 64) + ASM_NB - 1) / ASM_NB + 1;
+    bool band_panels_ok(const FacBuf& f, int Ms) const {
+        if (f.band <= 0 || h->batch_slot || Ms <= CHOL_NBI + 2 * ASM_NB) return false;
+        const int nrt = (CHOL_NBI + 2 * ASM_NB + (int)round_up(f.band, 64) + ASM_NB - 1) / ASM_NB + 1;
         const int m = nrt - CHOL_NBI / ASM_NB;
         return nrt <= ASM_PNL_NRT && nrt + m * (m + 1) / 2 <= h->panel_wgs;
     }
-    void chol_launches_band(int Ms, double thr) {
-        cur = h->stream;
+    void chol_launches_band(const FacBuf& f, int Ms, double thr) {
         for (int I0 = 0, I1 = 0; I0 < Ms; I0 = I1) {
             I1 = (Ms - I0 <= CHOL_NBI + 2 * ASM_NB) ? Ms : I0 + CHOL_NBI;
-            const int Mi = rowlim(Ms, I1);
+            const int Mi = rowlim(f, Ms, I1);
             const int nrt = (Mi - I0 + ASM_NB - 1) / ASM_NB, nst = (I1 - I0 + ASM_NB - 1) / ASM_NB, m = nrt - nst;
             h->panel_epoch += 1;
             if (h->panel_epoch == 0) h->panel_epoch = 1;
@@ -990,15 +974,15 @@ struct Dev {
                 const double r = std::max(0, Mi - (k0 + ASM_NB));
                 pfl += 2.0 / 3.0 * ASM_NB * ASM_NB * ASM_NB + 2.0 * r * ASM_NB * ASM_NB + 2.0 * ASM_NB * (0.5 * r * r);      // factor, panel solve, update of everything in reach
             }
-            int pid = begin(ASM_K_PANEL_KERNEL, pfl, 8.0 * 2.0 * (double)(Mi - I0) * (double)(Mi - I0) * 0.5, cur);
+            int pid = begin(ASM_K_PANEL_KERNEL, pfl, 8.0 * 2.0 * (double)(Mi - I0) * (double)(Mi - I0) * 0.5, h->stream);
             const int nhelp = (m * (m + 1) / 2 + ASM_BAND_TPH - 1) / ASM_BAND_TPH;      // helper workgroups: one per trailing tile
-            asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), 0, cur, fS, fld, I0, I1, Mi, (const double*)h->d_diag0, thr,
-                                  fLinv, h->d_pflags, h->d_ptmo, h->panel_epoch, nrt);
+            asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), 0, h->stream, f.S, f.ld, I0, I1, Mi, (const double*)h->d_diag0, thr,
+                                  f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch, nrt);
             end(pid);
         }
     }
-    void chol_launches(int Ms, double thr) {
-        if (band_panels_ok(Ms)) { chol_launches_band(Ms, thr); return; }
+    void chol_launches(const FacBuf& f, int Ms, double thr, bool panel_inv) {
+        if (band_panels_ok(f, Ms)) { chol_launches_band(f, Ms, thr); return; }
         // Two-level right-looking blocking with look-ahead.  64-wide steps inside a 1024-wide outer panel touch only the
         // panel's own columns; the trailing matrix is read-modify-written once per outer panel (K = 1024), in two parts:
         // (a) the columns of the NEXT outer panel, (b) the rest.  The next panel's serial block chain then runs on a second
@@ -1011,73 +995,69 @@ struct Dev {
             HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             h->la_events.push_back(e);
         }
-        cur = h->stream;
-        chol_chain(Ms, thr, 0, std::min(NBO, Ms));
+        chol_chain(f, Ms, thr, 0, std::min(NBO, Ms), h->stream, panel_inv);
         for (int p = 0; p < nP; ++p) {
             const int K0 = p * NBO, K1 = std::min(K0 + NBO, Ms);
             if (K1 >= Ms) break;
-            const int rem = rowlim(Ms, K1) - K1, wa = std::min(NBO, rem);   // next panel = first `wa` trailing columns (banded: `rem` stops where the panel's reach ends)
+            const int rem = rowlim(f, Ms, K1) - K1, wa = std::min(NBO, rem);   // next panel = first `wa` trailing columns (banded: `rem` stops where the panel's reach ends)
             hipEvent_t e_a = h->la_events[2 * p], e_c = h->la_events[2 * p + 1];
-            cur = h->stream;
             // (a) rows >= K1, columns of the next outer panel
-            launch_syrk(pick_tile(rem), fS + K0, fld, nullptr, K1, rem, K1 - K0, nullptr, nullptr, fS, fld, K1, 1, wa);
+            launch_syrk(h->stream, pick_tile(rem), f.S + K0, f.ld, nullptr, K1, rem, K1 - K0, nullptr, nullptr, f.S, f.ld, K1, 1, wa);
             if (la) {
                 HIPCHK(hipEventRecord(e_a, h->stream));
                 HIPCHK(hipStreamWaitEvent(h->stream2, e_a, 0));
-                cur = h->stream2;
-                chol_chain(Ms, thr, K1, std::min(K1 + NBO, Ms), true);     // next panel's chain beside (b)
+                chol_chain(f, Ms, thr, K1, std::min(K1 + NBO, Ms), h->stream2, panel_inv, true);     // next panel's chain beside (b)
                 HIPCHK(hipEventRecord(e_c, h->stream2));
-                cur = h->stream;
             }
             // (b) the rest of the trailing matrix
             const int rem2 = rem - wa;
             if (rem2 > 0)
-                launch_syrk(pick_tile(rem2), fS + K0, fld, nullptr, K1 + wa, rem2, K1 - K0, nullptr, nullptr, fS, fld, K1 + wa, 1);
+                launch_syrk(h->stream, pick_tile(rem2), f.S + K0, f.ld, nullptr, K1 + wa, rem2, K1 - K0, nullptr, nullptr, f.S, f.ld, K1 + wa, 1);
             if (la) HIPCHK(hipStreamWaitEvent(h->stream, e_c, 0));
-            else chol_chain(Ms, thr, K1, std::min(K1 + NBO, Ms));
+            else chol_chain(f, Ms, thr, K1, std::min(K1 + NBO, Ms), h->stream, panel_inv);
         }
-        cur = h->stream;
     }
     // out = (L L')^-1 rhs   (compact vectors of length Ms)
-    void chol_solve(const double* rhs, double* out, int Ms) {
+    void chol_solve(const FacBuf& f, const double* rhs, double* out, int Ms) {
         h2d(h->d_vecM2, rhs, Ms, Ms);
         int id = begin(ASM_K_TRSV, 2.0 * Ms * (double)Ms, 8.0 * Ms * (double)Ms);
-        solve_launches(Ms);
+        solve_launches(f, Ms, h->d_vecM2, h->d_vecM2);
         end(id);
         d2h(out, h->d_vecM2, Ms);
     }
-    void solve_launches(int Ms) {
-        if (fwb == 1024) solve_launches_wb<1024>(Ms); else solve_launches_wb<512>(Ms);
+    // the substitution runs in w (a copy of the right-hand side, updated in place); the forward diagonal products read src: w, or the
+    // right-hand side itself for a system of one wide block (no copy into w first)
+    void solve_launches(const FacBuf& f, int Ms, double* w, const double* src) {
+        if (f.wb == 1024) solve_launches_wb<1024>(f, Ms, w, src); else solve_launches_wb<512>(f, Ms, w, src);
     }
     template <int WB>
-    void solve_launches_wb(int Ms) {
-        // forward: w = copy of rhs (d_vecM2, updated in place), z -> d_vecM ; backward: x -> d_vecM2 (w is dead by then)
-        double* w = solve_w ? solve_w : h->d_vecM2;
+    void solve_launches_wb(const FacBuf& f, int Ms, double* w, const double* src) {
+        // forward: w updated in place, z -> d_vecM ; backward: x -> w (w is dead by then)
         double* z = h->d_vecM;
         const int nB = (Ms + WB - 1) / WB;
         for (int B = 0; B < nB; ++B) {
             int b1 = std::min((B + 1) * WB, Ms);
-            hipLaunchKernelGGL((k_wtrsv_fwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, fBinv, B, Ms, (const double*)(solve_src ? solve_src : w), z);
-            const int Me = rowlim(Ms, b1);
+            hipLaunchKernelGGL((k_wtrsv_fwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, f.Binv, B, Ms, src, z);
+            const int Me = rowlim(f, Ms, b1);
             int rem = Me - b1;
             if (rem > 0)
-                hipLaunchKernelGGL((k_wtrsv_fwd_panel<WB>), dim3((unsigned)((rem + 4 * ASM_FWD_RPW - 1) / (4 * ASM_FWD_RPW))), dim3(256), 0, h->stream, fS, fld, B, Me, z, w);
+                hipLaunchKernelGGL((k_wtrsv_fwd_panel<WB>), dim3((unsigned)((rem + 4 * ASM_FWD_RPW - 1) / (4 * ASM_FWD_RPW))), dim3(256), 0, h->stream, f.S, f.ld, B, Me, z, w);
         }
         for (int B = nB - 1; B >= 0; --B) {
             int b1 = std::min((B + 1) * WB, Ms);
-            const int Me = rowlim(Ms, b1);
+            const int Me = rowlim(f, Ms, b1);
             int rem = Me - b1;
             int np = 0;
             if (rem > 0) {
                 np = (rem + ASM_WBROWS - 1) / ASM_WBROWS;
-                hipLaunchKernelGGL((k_wtrsv_bwd_panel<WB>), dim3((unsigned)np), dim3(256), 0, h->stream, fS, fld, B, Me, w, h->d_wpart);
+                hipLaunchKernelGGL((k_wtrsv_bwd_panel<WB>), dim3((unsigned)np), dim3(256), 0, h->stream, f.S, f.ld, B, Me, w, h->d_wpart);
             }
             if (np > 0) {
                 hipLaunchKernelGGL((k_wtrsv_bwd_reduce<WB>), dim3(WB / ASM_NB), dim3(256), 0, h->stream, B, Ms, z, h->d_wpart, np, h->d_wt);
-                hipLaunchKernelGGL((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, fBinvT, B, Ms, h->d_wt, w, WB);
+                hipLaunchKernelGGL((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, f.BinvT, B, Ms, h->d_wt, w, WB);
             } else {
                 // last wide block (the only one of a small system): nothing to subtract, the diagonal product reads z itself
-                hipLaunchKernelGGL((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, fBinvT, B, Ms, (const double*)(z + (int64_t)B * WB), w, Ms - B * WB);
+                hipLaunchKernelGGL((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, f.BinvT, B, Ms, (const double*)(z + (int64_t)B * WB), w, Ms - B * WB);
             }
         }
     }
@@ -1454,17 +1434,14 @@ struct Solver {
         // the columns picked in index order can be badly conditioned, and the active-set solves need A_EF Z = 0 to 1e-13
         hipLaunchKernelGGL(k_ns_rows_e, dim3((unsigned)((h->ns_nEp + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sp_ptr, h->d_sp_col, vals, X,
                            (const double*)h->d_nsFm, (const double*)h->d_nsG, h->ns_ldg, h->d_nsR, (int64_t)h->ns_nEp);
-        dev.use_factor(h->ns_f0);
-        dev.trsm_rows(h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
+        dev.trsm_rows(h->ns_f0, h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
         hipLaunchKernelGGL(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X,
                            (const int*)h->d_nsJ, (const double*)h->d_nsFm, (const double*)h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 1);
-        dev.use_factor(h->ns_fN);
-        dev.launch_syrk(Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
+        dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
         hipLaunchKernelGGL(k_ns_fill, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, h->stream, h->d_diag0, 1.0, (int64_t)k);
-        dev.chol(k, thr);
+        dev.chol(h->ns_fN, k, thr);
         hipLaunchKernelGGL(k_ns_count_big, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
         const int bad2 = ns_read_cnt();
-        dev.use_main();
         if (bad2 > 0) return false;
         ns_ortho(k);
         hipLaunchKernelGGL(k_ns_gi, dim3((unsigned)((h->ns_nIp + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sp_ptr, h->d_sp_col, vals, X,
@@ -1482,18 +1459,15 @@ struct Solver {
         h2d_done(h);
         hipLaunchKernelGGL(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, (const int*)h->d_nsJ,
                            (const double*)h->d_nsFm, h->d_nsR, (int64_t)h->ns_nEp);
-        dev.use_factor(h->ns_f0);
-        dev.trsm_rows(h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
+        dev.trsm_rows(h->ns_f0, h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
         hipLaunchKernelGGL(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X,
                            (const int*)h->d_nsJ, (const double*)h->d_nsFm, (const double*)h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 0);
-        dev.use_factor(h->ns_fN);
         hipLaunchKernelGGL(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, (const double*)h->d_nsG, h->ns_ldg, (const int*)h->d_nsJ, k,
                            h->ns_fN.S, h->ns_fN.ld);
         hipLaunchKernelGGL(k_ns_fill, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, h->stream, h->d_diag0, 1.0, (int64_t)k);
-        dev.chol(k, NS_WARM_THR);
+        dev.chol(h->ns_fN, k, NS_WARM_THR);
         hipLaunchKernelGGL(k_ns_count_big, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
         const int bad = ns_read_cnt();
-        dev.use_main();
         if (bad > 0) return false;
         ns_ortho(k);
         return ns_reproject(k, NS_WARM_THR);
@@ -1526,7 +1500,6 @@ struct Solver {
             std::fprintf(stderr, "[asm] ns set-up %-10s +%.2f ms\n", what, t - t_v);
             t_v = t;
         };
-        dev.use_factor(h->ns_f0);
         if (h->ns_f0.band > 0) {
             // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
             // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
@@ -1538,12 +1511,11 @@ struct Solver {
             dev.syrk_gathered_into(h->d_nsEidx, nE, h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
         }
         vlap("S0 build");
-        dev.diag_prepare(nE, 1, 0.0, 0.0);
-        dev.chol(nE, 1e-10);
+        dev.diag_prepare(h->ns_f0, nE, 1, 0.0, 0.0);
+        dev.chol(h->ns_f0, nE, 1e-10);
         vlap("S0 factor");
         hipLaunchKernelGGL(k_ns_count_big, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_f0.S, h->ns_f0.ld, nE, NS_BIG, h->d_nscnt);
         const int dropped = ns_read_cnt();
-        dev.use_main();
         const int64_t k = nF - (nE - dropped);
         if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
         ns_reserve((int)k);
@@ -1563,7 +1535,7 @@ struct Solver {
         }
         if (!have) {
             ns_was_cold = true;
-            // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main matrix buffer,
+            // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main factor,
             // guarded Cholesky of T in index order with the absolute thresholds NS_SEL_THR in turn until exactly k columns are kept
             if (!h->d_nsYt) h->mem.zeroed(h->d_nsYt, (int64_t)h->ldn * h->ns_nEp + (int64_t)h->ldn * h->ns_nEp, h->stream);
             double* Yr = h->d_nsYt;                                  // right-hand sides, then garbage
@@ -1571,18 +1543,16 @@ struct Solver {
             const double* vals = dev.sparse_vals(h->d_Ah);
             hipLaunchKernelGGL(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, (const int*)nullptr,
                                (const double*)h->d_nsFm, Yr, (int64_t)h->ns_nEp);
-            dev.use_factor(h->ns_f0);
-            dev.trsm_rows(Yr, Yt, h->ns_nEp, (int)n, nE, nullptr);
-            dev.use_main();
+            dev.trsm_rows(h->ns_f0, Yr, Yt, h->ns_nEp, (int)n, nE, nullptr);
             std::vector<double> dg(n);
+            FacBuf& T = h->main_fac;
+            T.band = 0;
             for (int a = 0; a < 4 && !have; ++a) {
-                hipLaunchKernelGGL(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, h->d_S, h->Mp, (int)n, (const double*)h->d_nsFm);
-                dev.use_main();
-                dev.set_main_band(0);
-                dev.launch_syrk(Dev::pick_tile(n), Yt, h->ns_nEp, nullptr, 0, (int)n, h->ns_nEp, nullptr, nullptr, h->d_S, h->Mp, 0, 1);
+                hipLaunchKernelGGL(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, T.S, T.ld, (int)n, (const double*)h->d_nsFm);
+                dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, h->ns_nEp, nullptr, 0, (int)n, h->ns_nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
                 hipLaunchKernelGGL(k_ns_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_diag0, 1.0, n);
-                dev.chol((int)n, NS_SEL_THR[a]);
-                hipLaunchKernelGGL(k_ns_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->d_S, h->Mp, (int)n, h->d_vecN);
+                dev.chol(T, (int)n, NS_SEL_THR[a]);
+                hipLaunchKernelGGL(k_ns_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)T.S, T.ld, (int)n, h->d_vecN);
                 HIPCHK(hipMemcpyAsync(dg.data(), h->d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
                 HIPCHK(hipStreamSynchronize(h->stream));
                 std::vector<int> Jc;
@@ -1644,9 +1614,7 @@ struct Solver {
         hipLaunchKernelGGL(k_nseq_pfix, dim3(gN), dim3(256), 0, h->stream, A, pfix, ldn);
         dev.gemv_n_dev(h->d_Ah, pfix, aM);
         hipLaunchKernelGGL(k_nseq_be, dim3(gE), dim3(256), 0, h->stream, A, X, (const double*)aM, rE);
-        dev.use_factor(h->ns_f0);
-        dev.chol_solve_dev(rE, tE, nE);
-        dev.use_main();
+        dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
         hipLaunchKernelGGL(k_ns_rowvec_e, dim3(gM), dim3(256), 0, h->stream, X, (const double*)tE, yM, M);
         dev.gemv_t_dev(h->d_Ah, yM, x);
         hipLaunchKernelGGL(k_nseq_pbar, dim3(gN), dim3(256), 0, h->stream, A, (const double*)pfix, (const double*)x, (const double*)d_zero, Q.pbar, vz, ldn);
@@ -1675,23 +1643,22 @@ struct Solver {
         HIPCHK(hipMemsetAsync(Q.lam, 0, (size_t)h->ns_ccap * sizeof(double), h->stream));
         if (nact > 0) {
             hipLaunchKernelGGL(k_nseq_gather, dim3(gC, (unsigned)nact), dim3(256), 0, h->stream, A, cur, X, Q, (const double*)h->d_nsG, h->ns_ldg, k, ldn);
-            dev.use_factor(h->ns_fC);
-            dev.launch_syrk(Dev::pick_tile(nact), Q.Csel, Q.ldc, nullptr, 0, nact, (int)Q.ldc, nullptr, nullptr, h->ns_fC.S, h->ns_fC.ld, 0, 0);
-            dev.diag_prepare(nact, 1, 0.0, 0.0);
-            dev.chol(nact, 1e-10, false);
+            const FacBuf& C = h->ns_fC;
+            dev.launch_syrk(h->stream, Dev::pick_tile(nact), Q.Csel, Q.ldc, nullptr, 0, nact, (int)Q.ldc, nullptr, nullptr, C.S, C.ld, 0, 0);
+            dev.diag_prepare(C, nact, 1, 0.0, 0.0);
+            dev.chol(C, nact, 1e-10, false);
             for (int sw = 0; sw < 3; ++sw) {
                 nsq_gemv_n(Q, nact, Q.u, Q.v);                                                                           // C u
                 hipLaunchKernelGGL(k_nseq_sub, dim3(gA), dim3(256), 0, h->stream, (const double*)Q.d, (const double*)Q.v, Q.v, (int64_t)nact);
-                dev.chol_solve_dev(Q.v, Q.w, nact);
+                dev.chol_solve_dev(C, Q.v, Q.w, nact);
                 nsq_gemv_t(Q, nact, Q.w, t1);
                 hipLaunchKernelGGL(k_ns_add, dim3(gC), dim3(256), 0, h->stream, (const double*)Q.u, (const double*)t1, Q.u, Q.ldc);
                 nsq_gemv_t(Q, nact, Q.lam, t1);                                                                          // C' lam
                 hipLaunchKernelGGL(k_nseq_sub, dim3(gC), dim3(256), 0, h->stream, (const double*)Q.qh, (const double*)t1, t2, Q.ldc);
                 nsq_gemv_n(Q, nact, t2, Q.v);
-                dev.chol_solve_dev(Q.v, Q.w, nact);
+                dev.chol_solve_dev(C, Q.v, Q.w, nact);
                 hipLaunchKernelGGL(k_ns_add, dim3(gA), dim3(256), 0, h->stream, (const double*)Q.lam, (const double*)Q.w, Q.lam, (int64_t)nact);
             }
-            dev.use_main();
         }
         double *zu = nsv(3), *atw = nsv(4), *wN = nsv(2), *yM = nsv(5), *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         ns_gemv_t_dense(Q.u, k, zu);
@@ -1701,9 +1668,7 @@ struct Solver {
         hipLaunchKernelGGL(k_nseq_w, dim3(gN), dim3(256), 0, h->stream, A, Q, (const double*)atw, wN, ldn);
         dev.gemv_n_dev(h->d_Ah, wN, aM);
         hipLaunchKernelGGL(k_ns_gather_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)aM, 1.0, rE);
-        dev.use_factor(h->ns_f0);
-        dev.chol_solve_dev(rE, tE, nE);
-        dev.use_main();
+        dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
         hipLaunchKernelGGL(k_nseq_y, dim3(gM), dim3(256), 0, h->stream, A, X, (const double*)yM, (const double*)tE);
         dev.gemv_n_dev(h->d_Ah, A.p, A.t);
         dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
@@ -1720,9 +1685,7 @@ struct Solver {
         double *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         dev.gemv_n_dev(h->d_Ah, P.rdp, aM);
         hipLaunchKernelGGL(k_ns_gather_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)aM, 1.0, rE);
-        dev.use_factor(h->ns_f0);
-        dev.chol_solve_dev(rE, tE, nE);
-        dev.use_main();
+        dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
         // P.rdp already contains -A_E'y_E of the multipliers recovered at the end of an earlier stage: the solve gives the correction
         hipLaunchKernelGGL(k_ns_scatter_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)tE, P.y, 1);
     }
@@ -1737,7 +1700,6 @@ struct Solver {
         const double* th = h->d_nsth;
         const double* thI = h->d_nsth + ldn;
         // (theta~ was formed with the interior-point theta: k_ipm_theta_ns in ipm_run)
-        dev.use_factor(h->ns_fN);
         int id = dev.begin(ASM_K_SYRK, (double)k * (k + 1) * h->ns_ldg, 8.0 * (k * (double)h->ns_ldg + 0.5 * k * (double)k));
         // the k range (free columns + inequality rows, 19 000 at n = 11 192) is long and the matrix small (k = 519: 45 tiles of 64 x 64):
         // split-K fills the chip; the slices are added in a fixed order while the unregularised copy N0 is made
@@ -1748,17 +1710,17 @@ struct Solver {
         nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, h->ns_ldg / 512));
         if (nsplit > 1) {
             const int64_t pstride = h->ns_fN.ld * h->ns_fN.ld;
-            dev.launch_syrk(T, h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->d_nsNp, h->ns_fN.ld, 0, 0, -1, nullptr, 0, -1.0, nsplit, pstride);
+            dev.launch_syrk(h->stream, T, h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->d_nsNp, h->ns_fN.ld, 0, 0, -1, nullptr, 0, -1.0, nsplit, pstride);
             dev.end(id);
             hipLaunchKernelGGL(k_ns_reduce_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, (const double*)h->d_nsNp, nsplit, pstride, h->ns_fN.ld,
                                h->ns_fN.S, h->d_nsN0, k, k <= ASM_SMALL_USE ? 1 : 0, h->d_diag0, 1e-13, 1e-30);      // (+ k_diag_prepare, mode 0)
         } else {
-            dev.launch_syrk(Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
+            dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
             dev.end(id);
             hipLaunchKernelGGL(k_ns_copy_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, h->d_nsN0, h->ns_fN.ld, k, k <= ASM_SMALL_USE ? 1 : 0);
-            dev.diag_prepare(k, 0, 1e-13, 1e-30);
+            dev.diag_prepare(h->ns_fN, k, 0, 1e-13, 1e-30);
         }
-        dev.chol(k, 1e-14, false);
+        dev.chol(h->ns_fN, k, 1e-14, false);
         // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
         double* e = nsv(14);
         if (!ip.ns_e_ready) {
@@ -1799,11 +1761,9 @@ struct Solver {
             hipLaunchKernelGGL(k_ns_reduced_solve, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, (const double*)h->ns_fN.Linv,
                                (const double*)h->d_nsN0, k, (const double*)ru, du, P.scal + SC_NSERR);
         } else {
-            dev.use_factor(h->ns_fN);
-            dev.chol_solve_dev(ru, du, k);
+            dev.chol_solve_dev(h->ns_fN, ru, du, k);
             hipLaunchKernelGGL(k_ns_symv_res, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, h->stream, (const double*)h->d_nsN0, h->ns_fN.ld, k, (const double*)du, (const double*)ru, rr);
-            dev.chol_solve_dev(rr, dd, k);
-            dev.use_main();
+            dev.chol_solve_dev(h->ns_fN, rr, dd, k);
             hipLaunchKernelGGL(k_ns_add, dim3(gK), dim3(256), 0, h->stream, (const double*)du, (const double*)dd, du, (int64_t)k);
             hipLaunchKernelGGL(k_ns_symv_res, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, h->stream, (const double*)h->d_nsN0, h->ns_fN.ld, k, (const double*)du, (const double*)ru, rr);
             hipLaunchKernelGGL(k_ns_relres, dim3(1), dim3(1024), 0, h->stream, (const double*)rr, (const double*)ru, k, P.scal + SC_NSERR);
@@ -1845,28 +1805,28 @@ struct Solver {
         const unsigned gm = (unsigned)((lp.M + 255) / 256);
         if (use_red) {
             hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((nE + 255) / 256)), dim3(256), 0, h->stream, h->d_idx, nE, in, h->d_rce);
-            dev.chol_solve_dev(h->d_rce, h->d_rze, nE);
+            dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, nE);
             hipLaunchKernelGGL(k_red_scatter, dim3(gm), dim3(256), 0, h->stream, h->d_idx, nE, h->d_rze, h->d_idxI, nI, h->d_rdI, in, out);
             return;
         }
         if (use_perm) {
             hipLaunchKernelGGL(k_red_gather, dim3(gm), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, in, h->d_rce);
-            dev.chol_solve_dev(h->d_rce, h->d_rze, M);
+            dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, M);
             hipLaunchKernelGGL(k_red_scatter, dim3(gm), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, (const double*)h->d_rze, (const int*)h->d_rowperm, 0,
                                (const double*)h->d_rze, in, out);
             return;
         }
-        if (!use_col) { dev.chol_solve_dev(in, out, M); return; }
+        if (!use_col) { dev.chol_solve_dev(h->main_fac, in, out, M); return; }
         hipLaunchKernelGGL(k_col_scale, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, in, h->d_cu, lp.M);      // u = D^-1 r
         dev.gemv_t_dev(h->d_Ah, h->d_cu, h->d_ct);                                                                 // Ah' u
         if (h->col_band > 0) {                                                                                     // K^-1 (columns in banded order)
             const unsigned gn = (unsigned)((lp.n + 255) / 256);
             hipLaunchKernelGGL(k_red_gather, dim3(gn), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_ct, h->d_rce);
-            dev.chol_solve_dev(h->d_rce, h->d_rze, (int)lp.n);
+            dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, (int)lp.n);
             hipLaunchKernelGGL(k_red_scatter, dim3(gn), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_rze, (const int*)h->d_colperm, 0,
                                (const double*)h->d_rze, (const double*)h->d_ct, h->d_cv);
         } else {
-            dev.chol_solve_dev(h->d_ct, h->d_cv, (int)lp.n);                                                       // K^-1
+            dev.chol_solve_dev(h->main_fac, h->d_ct, h->d_cv, (int)lp.n);                                                       // K^-1
         }
         dev.gemv_n_dev(h->d_Ah, h->d_cv, h->d_cw);                                                                 // Ah v
         hipLaunchKernelGGL(k_col_finish, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, h->d_cu, h->d_cw, out, lp.M);
@@ -1994,8 +1954,8 @@ struct Solver {
                 } else {
                     dev.syrk_col(h->d_cdinv, h->d_cth);
                 }
-                dev.diag_prepare((int)lp.n, 0, 1e-13, 1e-30);
-                dev.chol((int)lp.n);
+                dev.diag_prepare(h->main_fac, (int)lp.n, 0, 1e-13, 1e-30);
+                dev.chol(h->main_fac, (int)lp.n);
             } else {
                 // reduced row form (oracle: IPM.run): inequality rows whose slack term dominates their Schur diagonal stay out
                 // of the factor and get a diagonal preconditioner
@@ -2032,19 +1992,19 @@ struct Solver {
                         h2d_done(h);      // the host vectors go out of scope
                         dev.syrk_gathered_dev(h->d_idx, nE, P.thp_inv, h->d_diag);
                     }
-                    dev.diag_prepare(nE, 0, 1e-13, 1e-30);
-                    dev.chol(nE);
+                    dev.diag_prepare(h->main_fac, nE, 0, 1e-13, 1e-30);
+                    dev.chol(h->main_fac, nE);
                 } else if (h->row_band > 0) {
                     // full row form, rows in the banded order: S is built entry by entry, factor and substitutions stop at the band
                     use_perm = true;
                     hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.M + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, (const double*)P.dS, h->d_diag);
                     dev.schur_banded_dev(h->d_rowpos, M, P.thp_inv, h->d_diag);
-                    dev.diag_prepare(M, 0, 1e-13, 1e-30);
-                    dev.chol(M);
+                    dev.diag_prepare(h->main_fac, M, 0, 1e-13, 1e-30);
+                    dev.chol(h->main_fac, M);
                 } else {
                     dev.syrk_dev(nullptr, M, P.thp_inv, P.dS);
-                    dev.diag_prepare(M, 0, 1e-13, 1e-30);
-                    dev.chol(M);
+                    dev.diag_prepare(h->main_fac, M, 0, 1e-13, 1e-30);
+                    dev.chol(h->main_fac, M);
                 }
             }
             ip.iters += 1;
@@ -2230,7 +2190,7 @@ struct Solver {
     //   mode 1: primal least-norm point only (p_ref = 0), 3 sweeps, the multipliers of that problem accumulated in uacc
     //   mode 2: basic least-squares multipliers only (y_ref = 0), 4 sweeps
     // Leaves t = Ah p and tN = Ah' y (mode 1: tN = Ah' u_full) for the tail kernel.
-    bool part_factor = false;   // d_S holds the factor of the partition's Schur matrix (face_polish re-uses it for the rounds on the same sets)
+    bool part_factor = false;   // the main factor is the factor of the partition's Schur matrix (face_polish re-uses it for the rounds on the same sets)
     void as_solve(const AsSets& cur, const double* p_ref, const double* y_ref, int mode, bool reuse_factor = false) {
         const unsigned gA = grid_all(), gM = (unsigned)((lp.M + 255) / 256 + 1), gN = (unsigned)((lp.n + 255) / 256);
         hipLaunchKernelGGL(k_as_setup, dim3(1), dim3(1024), 0, h->stream, A, cur, p_ref, h->ldn, h->Mp);
@@ -2248,8 +2208,8 @@ struct Solver {
             if (!(reuse_factor && part_factor)) {
                 if (h->row_band > 0) dev.schur_banded_dev(A.hpos, nH, A.Fmask, nullptr);        // Hidx is in the banded row order (k_as_setup)
                 else dev.syrk_gathered_dev(A.Hidx, nH, A.Fmask, nullptr);
-                dev.diag_prepare(nH, 1, 0.0, 0.0);
-                dev.chol(nH, 1e-10);
+                dev.diag_prepare(h->main_fac, nH, 1, 0.0, 0.0);
+                dev.chol(h->main_fac, nH, 1e-10);
                 part_factor = false;
             }
             const int sweeps = mode == 1 ? 3 : 4;
@@ -2258,7 +2218,7 @@ struct Solver {
                 if (mode != 2) {
                     dev.gemv_n_dev(h->d_Ah, A.pF, A.t);                                                  // A_HF pF
                     hipLaunchKernelGGL(k_as_res_p, dim3(gH), dim3(256), 0, h->stream, A);
-                    dev.chol_solve_dev(A.v, A.u, nH);
+                    dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
                     hipLaunchKernelGGL(k_as_scatter_h, dim3(gM), dim3(256), 0, h->stream, A, (const double*)A.u, mode == 1 ? 1 : 0);
                     dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' u
                     hipLaunchKernelGGL(k_as_add_f, dim3(gN), dim3(256), 0, h->stream, A);
@@ -2269,7 +2229,7 @@ struct Solver {
                     hipLaunchKernelGGL(k_as_rd, dim3(gN), dim3(256), 0, h->stream, A);
                     dev.gemv_n_dev(h->d_Ah, A.rd, A.t);                                                  // A_HF rd
                     hipLaunchKernelGGL(k_as_gather_h, dim3(gH), dim3(256), 0, h->stream, A);
-                    dev.chol_solve_dev(A.v, A.u, nH);
+                    dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
                     hipLaunchKernelGGL(k_as_add_yh, dim3(gH), dim3(256), 0, h->stream, A);
                 }
             }
@@ -2433,7 +2393,7 @@ struct Solver {
             if (nH0 > 0) {
                 dev.gemv_n_dev(h->d_Ah, A.rd, A.t);
                 hipLaunchKernelGGL(k_as_gather_h, dim3((unsigned)((nH0 + 255) / 256)), dim3(256), 0, h->stream, A);
-                dev.chol_solve_dev(A.v, A.u, nH0);
+                dev.chol_solve_dev(h->main_fac, A.v, A.u, nH0);
                 hipLaunchKernelGGL(k_as_scatter_h, dim3(gM), dim3(256), 0, h->stream, A, (const double*)A.u, 0);
                 dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
             } else {
@@ -2473,7 +2433,7 @@ struct Solver {
         if (h->knobs.verbose) std::fprintf(stderr, "[asm] face polish: projection of the iterate on its partition pr %.3e du %.3e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
         if (!(h->h_asscal[AS_PR] <= TOL_P && h->h_asscal[AS_DU] <= TOL_D)) return 0;
         dcopy(d_p0, A.p, n); dcopy(d_s0, A.s, ns); dcopy(d_y0, A.y, M); dcopy(d_act0, A.act, M); dcopy(d_z0, A.z, n);
-        part_factor = true;            // the factor in d_S belongs to the partition: the first dual / primal round below re-use it
+        part_factor = true;            // the main factor belongs to the partition: the first dual / primal round below re-use it
         // ---- dual: basic least-squares multipliers on the partition, sign repair (oracle: face_dual; independent of the primal
         // stage, run first so that its round 0 and the primal round 0 share the factorisation of the projection above)
         bool okd = false;
@@ -2897,16 +2857,18 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     P.alloc(h->d_dE, nnz);
     P.zeroed(h->d_J, h->Mp * h->ldn, s);
     P.zeroed(h->d_Ah, h->Mp * h->ldn, s);
-    P.alloc(h->d_S, h->Mp * h->Mp);
+    FacBuf& F = h->main_fac;
+    F.ld = h->Mp;
+    P.alloc(F.S, h->Mp * h->Mp);
     P.alloc(h->d_c, h->ldn); P.alloc(h->d_rho, h->Mp); P.alloc(h->d_theta, h->ldn);
     P.alloc(h->d_diag, h->Mp); P.alloc(h->d_diag0, h->Mp);
     P.zeroed(h->d_vecN, h->ldn, s); P.zeroed(h->d_vecM, h->Mp, s); P.alloc(h->d_vecM2, h->Mp);
     P.alloc(h->d_partial, (int64_t)ASM_TMAXCHUNKS * h->ldn);
     P.alloc(h->d_idx, h->Mp);
-    P.alloc(h->d_Linv, (h->Mp / ASM_NB + 1) * ASM_NB * ASM_NB);
+    P.alloc(F.Linv, (h->Mp / ASM_NB + 1) * ASM_NB * ASM_NB);
     P.zeroed(h->d_pflags, ASM_PNL_FLAGS, s);
     P.zeroed(h->d_ptmo, 4, s);
-    h->wb = h->M > 1536 ? 1024 : 512;      // wide-block width of the triangular solves (k_wtrsv_*<WB>)
+    F.wb = h->M > 1536 ? 1024 : 512;      // wide-block width of the triangular solves (k_wtrsv_*<WB>)
     if (h->M >= RED_MIN_M) {
         P.alloc(h->d_idxI, h->Mp); P.alloc(h->d_rdI, h->Mp); P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); P.alloc(h->d_sdiag, h->Mp);
     }
@@ -2919,8 +2881,8 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.zeroed(h->d_cv, h->ldn, s); P.zeroed(h->d_cw, h->Mp, s);
         P.alloc(h->d_nzT, (n / 32 + 2) * (h->ldT / ASM_KC + 1));
     }
-    P.alloc(h->d_Binv, (h->Mp / h->wb + 1) * (int64_t)h->wb * h->wb);
-    P.alloc(h->d_BinvT, (h->Mp / h->wb + 1) * (int64_t)h->wb * h->wb);
+    P.alloc(F.Binv, (h->Mp / F.wb + 1) * (int64_t)F.wb * F.wb);
+    P.alloc(F.BinvT, (h->Mp / F.wb + 1) * (int64_t)F.wb * F.wb);
     P.alloc(h->d_wpart, (h->Mp / ASM_WBROWS + 2) * (int64_t)1024);
     P.alloc(h->d_wt, 1024);
     h->nz_half = (h->Mp / 32 + 1) * (h->ldn / ASM_KC + 1);
@@ -3001,7 +2963,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         }
     }
     // row order of the factorisations (see asm_handle::row_band)
-    h->main_band_cur = 0;
+    h->main_fac.band = 0;
     if (h->sp_ok && h->M >= 256) {
         std::vector<int> all(h->M), pairs_pos;
         for (int64_t i = 0; i < h->M; ++i) all[i] = (int)i;
@@ -3980,12 +3942,13 @@ int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const in
         d.h2d(h->d_theta, theta, K, h->ldn);
         if (diag) d.h2d(h->d_diag, diag, Ms, Ms);
         if (idx) HIPCHK(hipMemcpy(h->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(h->d_S, 0, h->Mp * h->Mp * sizeof(double)));
-        d.launch_syrk(tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, idx ? h->d_idx : nullptr, 0, (int)Ms, (int)h->ldn, h->d_theta,
-                      diag ? h->d_diag : nullptr, h->d_S, h->Mp, 0, 0);
+        const FacBuf& F = h->main_fac;
+        HIPCHK(hipMemset(F.S, 0, F.ld * F.ld * sizeof(double)));
+        d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, idx ? h->d_idx : nullptr, 0, (int)Ms, (int)h->ldn, h->d_theta,
+                      diag ? h->d_diag : nullptr, F.S, F.ld, 0, 0);
         HIPCHK(hipStreamSynchronize(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(S_out + i * Ms, h->d_S + i * h->Mp, Ms * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(S_out + i * Ms, F.S + i * F.ld, Ms * sizeof(double), hipMemcpyDeviceToHost));
     });
 }
 
@@ -4000,39 +3963,38 @@ int asm_test_syrk_update(asm_handle* h, const double* Pm, int64_t Ms, int64_t K,
         HIPCHK(hipMemset(h->d_Ah, 0, h->Mp * h->ldn * sizeof(double)));
         for (int64_t i = 0; i < Ms; ++i)
             HIPCHK(hipMemcpy(h->d_Ah + (srow0 + i) * h->ldn, Pm + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+        const FacBuf& F = h->main_fac;
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(h->d_S + (srow0 + i) * h->Mp + srow0, S_inout + i * Ms, Ms * sizeof(double), hipMemcpyHostToDevice));
-        d.launch_syrk(tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, nullptr, srow0, (int)Ms, (int)K, nullptr, nullptr, h->d_S, h->Mp, srow0, 1, (int)MsB);
+            HIPCHK(hipMemcpy(F.S + (srow0 + i) * F.ld + srow0, S_inout + i * Ms, Ms * sizeof(double), hipMemcpyHostToDevice));
+        d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, nullptr, srow0, (int)Ms, (int)K, nullptr, nullptr, F.S, F.ld, srow0, 1, (int)MsB);
         HIPCHK(hipStreamSynchronize(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(S_inout + i * Ms, h->d_S + (srow0 + i) * h->Mp + srow0, Ms * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(S_inout + i * Ms, F.S + (srow0 + i) * F.ld + srow0, Ms * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
     });
 }
 
-// S into the buffers the hooks factor in (asm_test_set_factor): the main buffers, or a factor buffer of the null-space form's kind, made for
-// this order (released with the other null-space buffers at the next set-up)
+// S into the buffers the hooks factor in (asm_test_set_factor): the main factor, or a factor buffer of the null-space form's kind, made for
+// this order (released with the other null-space buffers at the next set-up); either has the band of asm_test_set_band
 static void test_load_S(asm_handle* h, const double* S, int64_t N) {
     test_alloc(h, N, 16);
-    h->main_band_cur = 0;
-    double* dst = h->d_S;
-    int64_t ld = h->Mp;
+    FacBuf* f = &h->main_fac;
     if (h->test_layout == 1) {
         h->test_fac = FacBuf();
         ns_alloc_factor(h, h->mem, h->test_fac, N, h->test_band_hint);
-        h->test_fac.band = h->main_band;
         HIPCHK(hipStreamSynchronize(h->stream));          // (the buffers are cleared on the stream)
-        dst = h->test_fac.S;
-        ld = h->test_fac.ld;
+        f = &h->test_fac;
     }
+    f->band = h->test_band;
     for (int64_t i = 0; i < N; ++i)
-        HIPCHK(hipMemcpy(dst + i * ld, S + i * N, N * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f->S + i * f->ld, S + i * N, N * sizeof(double), hipMemcpyHostToDevice));
 }
-// factorisation of the loaded matrix with the hooks' guard settings, in the buffers it was loaded into
-static void test_factor(asm_handle* h, Dev& d, int64_t N) {
-    if (h->test_layout == 1) d.use_factor(h->test_fac);
-    d.diag_prepare((int)N, h->test_mode, h->test_rel, h->test_abs);
-    d.chol((int)N, h->test_thr);
+// factorisation of the loaded matrix with the hooks' guard settings, in the buffers it was loaded into; returns that factor
+static const FacBuf& test_factor(asm_handle* h, Dev& d, int64_t N) {
+    const FacBuf& f = h->test_layout == 1 ? h->test_fac : h->main_fac;
+    d.diag_prepare(f, (int)N, h->test_mode, h->test_rel, h->test_abs);
+    d.chol(f, (int)N, h->test_thr);
+    return f;
 }
 
 int asm_test_set_factor(asm_handle* h, int layout, int band_hint, int mode, double rel, double absv, double thr) {
@@ -4048,10 +4010,10 @@ int asm_test_cholesky(asm_handle* h, const double* S, int64_t N, double* L_out) 
     return guarded(h, [&] {
         test_load_S(h, S, N);
         Dev d(h);
-        test_factor(h, d, N);
+        const FacBuf& f = test_factor(h, d, N);
         HIPCHK(hipStreamSynchronize(h->stream));
         for (int64_t i = 0; i < N; ++i) {
-            HIPCHK(hipMemcpy(L_out + i * N, d.fS + i * d.fld, N * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(L_out + i * N, f.S + i * f.ld, N * sizeof(double), hipMemcpyDeviceToHost));
             for (int64_t j = i + 1; j < N; ++j) L_out[i * N + j] = 0.0;
         }
         d.resolve_timing();
@@ -4066,7 +4028,7 @@ int asm_test_cholesky(asm_handle* h, const double* S, int64_t N, double* L_out) 
 int asm_test_set_band(asm_handle* h, int band) {
     return guarded(h, [&] {
         if (band < 0) throw std::invalid_argument("asm_test_set_band: bad argument");
-        h->main_band = band;
+        h->test_band = band;
     });
 }
 
@@ -4091,8 +4053,8 @@ int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double*
     return guarded(h, [&] {
         test_load_S(h, S, N);
         Dev d(h);
-        test_factor(h, d, N);
-        d.chol_solve(b, x, (int)N);
+        const FacBuf& f = test_factor(h, d, N);
+        d.chol_solve(f, b, x, (int)N);
         d.resolve_timing();
     });
 }
@@ -4126,14 +4088,14 @@ int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* 
         if (N <= 0 || nrhs <= 0 || !S || !R || !X_out) throw std::invalid_argument("asm_test_trsm_rows: bad argument");
         test_load_S(h, S, N);
         Dev d(h);
-        test_factor(h, d, N);
+        const FacBuf& f = test_factor(h, d, N);
         const int64_t ldr = round_up(N, 32);
         double *dR = nullptr, *dX = nullptr, *dLt = nullptr;
         BufPool tmp;
-        tmp.zeroed(dR, nrhs * ldr); tmp.zeroed(dX, nrhs * ldr); tmp.zeroed(dLt, d.fld * d.fld);
+        tmp.zeroed(dR, nrhs * ldr); tmp.zeroed(dX, nrhs * ldr); tmp.zeroed(dLt, f.ld * f.ld);
         for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(dR + r * ldr, R + r * N, N * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, h->stream, (const double*)d.fS, d.fld, N, N, dLt, d.fld, (int64_t)-1);
-        d.trsm_rows(dR, dX, ldr, (int)nrhs, (int)N, backward ? dLt : nullptr);
+        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, h->stream, (const double*)f.S, f.ld, N, N, dLt, f.ld, (int64_t)-1);
+        d.trsm_rows(f, dR, dX, ldr, (int)nrhs, (int)N, backward ? dLt : nullptr);
         HIPCHK(hipStreamSynchronize(h->stream));
         const double* out = backward ? dR : dX;
         for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(X_out + r * N, out + r * ldr, N * sizeof(double), hipMemcpyDeviceToHost));
