@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the SLP sub-problem hot path (BASELINE.json metric: SLP iterations/sec).
 
-  python bench.py --gpus N --steps K --warmup W [--workload c2|c2small] [--algorithm "Trust Region"]
+  python bench.py --gpus N --steps K --warmup W [--workload c2|c2small] [--algorithm "Trust Region"] [--full]
 
 N = 1 (default workload c4): a "step" is one SLP outer iteration that reaches the LP solve:
 evaluation, Jacobian assembly, LP formulation, the HIP LP solve and the merit/step logic.
@@ -14,9 +14,11 @@ value = work of all ranks / max-over-ranks time.  One JSON line is printed by ra
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one child process per
 GPU, spawned before anything touches the GPU); under `python -m torch.distributed.run` the ranks already exist and are used.
 
-The dominant kernel's roofline numbers come from HIP events recorded on the solver's own stream
-around each launch (include/asm_hip.h: asm_kernel_stats_get); the CPU baseline is the oracle's NumPy
-restatement of the same path (oracle/, "port") on a bounded sample of the same workload.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line.  The dominant kernel's roofline
+numbers in that line come from HIP events recorded on the solver's own stream around each launch of the timed steps
+(include/asm_hip.h: asm_kernel_stats_get).  `--full` adds what takes work of its own after the timed steps: the untimed
+all-families pass (roofline.step / .hbm), HiGHS on the non-canonical LP answers, and the CPU baselines - the oracle's
+NumPy restatement of the same path (oracle/, "port") and HiGHS on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -186,7 +188,7 @@ def run_batch(args, rank, world, local_rank, dist, torch):
                                "share_of_stream_time": d["panel_ms"] / max(1e-9, 1e3 * mine * hb.groups),
                                "algorithmic_bytes_per_launch": d["panel_bytes"] / d["panel_launches"],
                                "note": "rank 0; the groups' streams run side by side, so the family's share is taken of groups x wall time; traffic: no PMC pass of the batch is committed"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = c5_cpu_baseline(base, lo, args, runs)
         print(json.dumps(out))
     hb.close()
@@ -552,7 +554,7 @@ def launch_ranks(n, argv, script=None):
     return rc
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
@@ -560,7 +562,10 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c4 on one GPU (the configuration the metric is quoted on), c5 (scenario batch) on several")
     ap.add_argument("--algorithm", default=None)
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the all-families roofline pass, HiGHS on the "
+                         "non-canonical LP answers and the CPU baselines (default: off)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time budget of each CPU baseline")
     ap.add_argument("--scenarios-per-gpu", type=int, default=None, help="workload c5: scenarios per GPU (alias of --steps)")
     ap.add_argument("--max-iter", type=int, default=100, help="workload c5: SLP iteration cap per scenario")
     ap.add_argument("--slots", type=int, default=64, help="workload c5: scenarios advancing in lockstep per GPU (slots of the asm_batch)")
@@ -568,12 +573,17 @@ def main():
     ap.add_argument("--dynamic", action="store_true", help="workload c5: ranks claim chunks of scenarios from a shared counter instead of the static block partition")
     ap.add_argument("--batch-mode", default="lockstep", choices=["lockstep", "pool"], help="workload c5: lockstep batch (default) or the round-3 stream pool")
     ap.add_argument("--concurrency", type=int, default=2, help="workload c5, --batch-mode pool: scenarios in flight per GPU (one handle / HIP stream each)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--host-eval", action="store_true", help="evaluate f, grad f, g, Jacobian values with the NumPy callbacks instead of the device kernels")
     ap.add_argument("--kernel-breakdown", action="store_true",
                     help="time every kernel family with HIP events (adds kernels_ms; default: only the dominant kernel, k_syrk, is timed)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last step as DIR/<name>.npy (float64, rank 0, at most 64 MB)")
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -668,31 +678,32 @@ def main():
                 traffic=None, avg_launch_ms=fams[dom]["avg_launch_ms"], launches=fams[dom]["launches"], share_of_step_time=fams[dom]["share_of_step_time"],
                 algorithmic_bytes_per_launch=fams[dom]["algorithmic_bytes_per_launch"], families=fams)
     nfact = ks["chol"]["calls"]
-    # a second, untimed pass with every kernel family timed (perturbs the latency-bound chains, hence not the measured one): the whole
-    # step's algorithmic work and the HBM regime of SURVEY.md 8(d) (matrix-vector products, substitutions, assembly, scaling)
-    opt.kernel_timing(2)
-    opt.kernel_stats(reset=True)
-    n2 = max(3, min(10, args.steps))
-    t2 = time.perf_counter()
-    run_steps(pr, args.algorithm, local_rank, n2, state)
-    torch.cuda.synchronize()
-    dt2 = time.perf_counter() - t2
-    k2 = opt.kernel_stats()
-    opt.kernel_timing(1)
-    step_flops = sum(k2[k]["flops"] for k in ("syrk", "chol", "trsv", "gemv")) / n2
-    step_bytes = sum(k2[k]["bytes"] for k in ("assemble", "scale", "gemv", "trsv", "syrk", "chol")) / n2
-    roof["step"] = dict(flops=step_flops, bytes=step_bytes, tflops=step_flops / (1e-3 * 1e3 * elapsed / args.steps) / 1e12,
-                        frac=step_flops / (elapsed / args.steps) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-                        note="algorithmic flops / bytes of one step (Schur and reduced-matrix builds + factorisations + multi-right-hand-side and vector "
-                             "substitutions + matrix-vector products; assembly and scaling bytes) from the all-families pass, divided by the timed ms_per_step")
-    hb_ms = sum(k2[k]["ms"] for k in ("assemble", "scale", "gemv"))
-    hb_bytes = sum(k2[k]["bytes"] for k in ("assemble", "scale", "gemv"))
-    roof["hbm"] = dict(bound="hbm", kernels="k_assemble, scaling passes, k_spmv_* / k_gemv_* (matrix-vector products)", achieved=hb_bytes / (hb_ms * 1e-3) / 1e9 if hb_ms > 0 else 0.0,
-                       peak=HBM_PEAK_GBS, unit="GB/s", frac=(hb_bytes / (hb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if hb_ms > 0 else 0.0,
-                       share_of_step_time=(hb_ms / n2) / (1e3 * dt2 / n2) if dt2 > 0 else None,
-                       note="HBM regime of SURVEY.md 8(d): algorithmic bytes / HIP-event time of these families in the all-families pass; at these sizes "
-                            "(13 k - 64 k non-zeros) the launches are latency-bound, not bandwidth-bound")
-    roof["all_families_pass"] = dict(steps=n2, ms_per_step=1e3 * dt2 / n2, kernels_ms_per_step={k: round(v["ms"] / n2, 3) for k, v in k2.items()})
+    if args.full:
+        # a second, untimed pass with every kernel family timed (perturbs the latency-bound chains, hence not the measured one): the whole
+        # step's algorithmic work and the HBM regime of SURVEY.md 8(d) (matrix-vector products, substitutions, assembly, scaling)
+        opt.kernel_timing(2)
+        opt.kernel_stats(reset=True)
+        n2 = max(3, min(10, args.steps))
+        t2 = time.perf_counter()
+        run_steps(pr, args.algorithm, local_rank, n2, state)
+        torch.cuda.synchronize()
+        dt2 = time.perf_counter() - t2
+        k2 = opt.kernel_stats()
+        opt.kernel_timing(1)
+        step_flops = sum(k2[k]["flops"] for k in ("syrk", "chol", "trsv", "gemv")) / n2
+        step_bytes = sum(k2[k]["bytes"] for k in ("assemble", "scale", "gemv", "trsv", "syrk", "chol")) / n2
+        roof["step"] = dict(flops=step_flops, bytes=step_bytes, tflops=step_flops / (1e-3 * 1e3 * elapsed / args.steps) / 1e12,
+                            frac=step_flops / (elapsed / args.steps) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
+                            note="algorithmic flops / bytes of one step (Schur and reduced-matrix builds + factorisations + multi-right-hand-side and vector "
+                                 "substitutions + matrix-vector products; assembly and scaling bytes) from the all-families pass, divided by the timed ms_per_step")
+        hb_ms = sum(k2[k]["ms"] for k in ("assemble", "scale", "gemv"))
+        hb_bytes = sum(k2[k]["bytes"] for k in ("assemble", "scale", "gemv"))
+        roof["hbm"] = dict(bound="hbm", kernels="k_assemble, scaling passes, k_spmv_* / k_gemv_* (matrix-vector products)", achieved=hb_bytes / (hb_ms * 1e-3) / 1e9 if hb_ms > 0 else 0.0,
+                           peak=HBM_PEAK_GBS, unit="GB/s", frac=(hb_bytes / (hb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if hb_ms > 0 else 0.0,
+                           share_of_step_time=(hb_ms / n2) / (1e3 * dt2 / n2) if dt2 > 0 else None,
+                           note="HBM regime of SURVEY.md 8(d): algorithmic bytes / HIP-event time of these families in the all-families pass; at these sizes "
+                                "(13 k - 64 k non-zeros) the launches are latency-bound, not bandwidth-bound")
+        roof["all_families_pass"] = dict(steps=n2, ms_per_step=1e3 * dt2 / n2, kernels_ms_per_step={k: round(v["ms"] / n2, 3) for k, v in k2.items()})
     # HBM bytes per launch of the dominant family from the committed PMC passes (cannot be collected inside bench)
     for tag in ("r04", "r03", "r02"):
         tpath = os.path.join(ROOT, "profiles", "%s_%s_pmc_traffic.json" % (tag, args.workload))
@@ -744,15 +755,15 @@ def main():
                               "restoration_lps": sum(1 for r in timed if r["fr"]),
                               "slp_status_last": int(state["slp"].ret) if state.get("slp") is not None else None,
                               "slp_terminations": state.get("terminations", [])}
-        # every non-canonical answer of the timed steps ('ipm+ref': projection of the iterate, 'ipm-conv': the converged iterate) against an
+        # --full: every non-canonical answer of the timed steps ('ipm+ref': projection of the iterate, 'ipm-conv': the converged iterate) against an
         # independent LP code: HiGHS optimal value of the same LP vs the value of the LP at the GPU's step (its slacks re-optimised by HiGHS
         # with p fixed: restoration LPs), and feasibility of that step.  A failure is reported, not hidden.
         nc = [r for r in timed if r["stats"]["path"] in (9, 10) and r["status"] == 1][:5]
-        if nc:
+        if args.full and nc:
             out["lp_outcomes"]["non_canonical_check"] = check_non_canonical(pr_host, nc)
             if out["lp_outcomes"]["non_canonical_check"].get("failures", 0) > 0:
                 out["parity_failures"] = out["lp_outcomes"]["non_canonical_check"]["failures"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             mix = dict(steps=args.steps, col_iters=sum(r["stats"].get("col_iters", 0) for r in timed),
                        row_iters=sum(r["stats"]["ipm_iters"] - r["stats"].get("col_iters", 0) for r in timed),
                        eqp=sum(max(r["stats"]["nfact"] - r["stats"]["ipm_iters"], 0) for r in timed))   # active-set FACTORISATIONS

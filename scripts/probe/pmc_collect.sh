@@ -5,12 +5,13 @@ TAG=${1:-r03}; WL=${2:-c4}; STEPS=${3:-5}
 ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd $ROOT
 OUT=gpurun_out/pmc_${TAG}_${WL}
+RES=$(dirname $OUT)
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o p --output-format csv -- python3 bench.py --workload $WL --no-cpu-baseline > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o p --output-format csv -- python3 bench.py --workload $WL --full --no-cpu-baseline > $OUT/stats.log 2>&1
 echo stats rc=$?
-python3 scripts/prof_summary.py $OUT/stats/p $OUT/stats.log "rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $WL --no-cpu-baseline   (MI355X, round ${TAG#r}; ASM_HIP_TIMING=1)" > gpurun_out/${TAG}_${WL}_kernel_stats.txt
+python3 scripts/prof_summary.py $OUT/stats/p $OUT/stats.log "rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $WL --full --no-cpu-baseline   (MI355X, round ${TAG#r}; ASM_HIP_TIMING=1)" > $RES/${TAG}_${WL}_kernel_stats.txt
 rm -f $OUT/stats/p_kernel_trace.csv
-CMD="python3 bench.py --workload $WL --steps $STEPS --warmup 1 --no-cpu-baseline"
+CMD="python3 bench.py --workload $WL --steps $STEPS --warmup 1 --full --no-cpu-baseline"
 ASM_HIP_TIMING=0 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS --kernel-trace -d $OUT/mfma -o m --output-format csv -- $CMD > $OUT/mfma.log 2>&1
 echo mfma rc=$?
 ASM_HIP_TIMING=0 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace -d $OUT/clock -o c --output-format csv -- $CMD > $OUT/clock.log 2>&1

@@ -292,3 +292,15 @@ def test_dynamic_scenario_assignment_gloo_world2():
     # without a process group: one local counter
     from activesetmethods_amd.batch import claim_chunks
     assert list(claim_chunks(10, 4)) == [(0, 4), (4, 8), (8, 10)]
+
+
+def test_bench_full_is_opt_in():
+    """`bench.py` without `--full` runs only what its headline needs; the extra passes and CPU baselines are asked for with `--full`."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ap = bench.make_parser()
+    plain = ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and not plain.no_cpu_baseline and plain.steps == 3 and plain.warmup == 1
+    assert ap.parse_args(["--full"]).full and ap.parse_args(["--full", "--no-cpu-baseline"]).no_cpu_baseline
