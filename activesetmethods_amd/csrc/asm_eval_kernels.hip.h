@@ -189,6 +189,28 @@ __device__ __forceinline__ double expr_powi(double u, int64_t e, double* d) {
     *d = (double)e / (pk * u);
     return 1.0 / pk;
 }
+// ln 10 and ln 2 rounded to double (the adjoints of LOG10 / LOG2; the host twin uses the same two values)
+constexpr double EXPR_LN10 = 2.302585092994045684, EXPR_LN2 = 0.6931471805599453094;
+// The math-library ops after COS, out of line: inlined into the node loops, their polynomial constants are hoisted out of the
+// loop and held in registers across it (256 VGPRs, occupancy 2, against 98 and 4 with the call).  y: b's value (POW, ATAN2).
+__device__ __noinline__ double expr_libm(int32_t op, double u, double y) {
+    switch (op) {
+        case ASM_OP_TAN: return tan(u);
+        case ASM_OP_ASIN: return asin(u);
+        case ASM_OP_ACOS: return acos(u);
+        case ASM_OP_ATAN: return atan(u);
+        case ASM_OP_SINH: return sinh(u);
+        case ASM_OP_COSH: return cosh(u);
+        case ASM_OP_TANH: return tanh(u);
+        case ASM_OP_LOG10: return log10(u);
+        case ASM_OP_LOG2: return log2(u);
+        case ASM_OP_LOG1P: return log1p(u);
+        case ASM_OP_EXPM1: return expm1(u);
+        case ASM_OP_CBRT: return cbrt(u);
+        case ASM_OP_POW: return pow(u, y);
+        default: return atan2(u, y);      // ASM_OP_ATAN2
+    }
+}
 // forward sweep over nodes [k0, k1) at x: every node value into val (absolute indices), returns the last one
 __device__ __forceinline__ double expr_forward(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, double* val) {
 #pragma clang fp contract(off)
@@ -208,7 +230,14 @@ __device__ __forceinline__ double expr_forward(const ExprTape& X, int64_t k0, in
             case ASM_OP_EXP: v = exp(val[a]); break;
             case ASM_OP_LOG: v = log(val[a]); break;
             case ASM_OP_SIN: v = sin(val[a]); break;
-            default: v = cos(val[a]); break;       // ASM_OP_COS (asm_eval_setup admits no other op)
+            case ASM_OP_COS: v = cos(val[a]); break;
+            case ASM_OP_ABS: v = fabs(val[a]); break;
+            case ASM_OP_TAN: case ASM_OP_ASIN: case ASM_OP_ACOS: case ASM_OP_ATAN: case ASM_OP_SINH: case ASM_OP_COSH: case ASM_OP_TANH:
+            case ASM_OP_LOG10: case ASM_OP_LOG2: case ASM_OP_LOG1P: case ASM_OP_EXPM1: case ASM_OP_CBRT: case ASM_OP_POW: case ASM_OP_ATAN2:
+                v = expr_libm(X.op[k], val[a], val[b]);
+                break;
+            case ASM_OP_MIN: { const double u = val[a], y = val[b]; v = y < u ? y : u; break; }
+            default: { const double u = val[a], y = val[b]; v = y > u ? y : u; break; }   // ASM_OP_MAX (asm_eval_setup admits no other op)
         }
         val[k] = v;
     }
@@ -240,7 +269,34 @@ __device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int6
             case ASM_OP_EXP: adj[a] = adj[a] + w * val[k]; break;
             case ASM_OP_LOG: adj[a] = adj[a] + w / val[a]; break;
             case ASM_OP_SIN: adj[a] = adj[a] + w * cos(val[a]); break;
-            default: adj[a] = adj[a] - w * sin(val[a]); break;     // ASM_OP_COS
+            case ASM_OP_COS: adj[a] = adj[a] - w * sin(val[a]); break;
+            case ASM_OP_ABS: adj[a] = adj[a] + w * copysign(1.0, val[a]); break;
+            case ASM_OP_TAN: { const double v = val[k]; adj[a] = adj[a] + w * (1.0 + v * v); break; }
+            case ASM_OP_ASIN: { const double u = val[a]; adj[a] = adj[a] + w / sqrt(1.0 - u * u); break; }
+            case ASM_OP_ACOS: { const double u = val[a]; adj[a] = adj[a] - w / sqrt(1.0 - u * u); break; }
+            case ASM_OP_ATAN: { const double u = val[a]; adj[a] = adj[a] + w / (1.0 + u * u); break; }
+            case ASM_OP_SINH: adj[a] = adj[a] + w * expr_libm(ASM_OP_COSH, val[a], 0.0); break;
+            case ASM_OP_COSH: adj[a] = adj[a] + w * expr_libm(ASM_OP_SINH, val[a], 0.0); break;
+            case ASM_OP_TANH: { const double v = val[k]; adj[a] = adj[a] + w * (1.0 - v * v); break; }
+            case ASM_OP_LOG10: adj[a] = adj[a] + w / (val[a] * EXPR_LN10); break;
+            case ASM_OP_LOG2: adj[a] = adj[a] + w / (val[a] * EXPR_LN2); break;
+            case ASM_OP_LOG1P: adj[a] = adj[a] + w / (1.0 + val[a]); break;
+            case ASM_OP_EXPM1: adj[a] = adj[a] + w * (val[k] + 1.0); break;
+            case ASM_OP_CBRT: { const double v = val[k]; adj[a] = adj[a] + w / (3.0 * (v * v)); break; }
+            case ASM_OP_POW: {
+                const double u = val[a], y = val[b];
+                adj[a] = adj[a] + w * (y * expr_libm(ASM_OP_POW, u, y - 1.0));
+                adj[b] = adj[b] + w * (val[k] * log(u));
+                break;
+            }
+            case ASM_OP_ATAN2: {
+                const double u = val[a], y = val[b], t = u * u + y * y;
+                adj[a] = adj[a] + (w * y) / t;
+                adj[b] = adj[b] - (w * u) / t;
+                break;
+            }
+            case ASM_OP_MIN: { const int64_t c = val[b] < val[a] ? b : a; adj[c] = adj[c] + w; break; }
+            default: { const int64_t c = val[b] > val[a] ? b : a; adj[c] = adj[c] + w; break; }   // ASM_OP_MAX
         }
     }
 }

@@ -3573,7 +3573,7 @@ void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_
             } else {
                 if (ka < 0 || ka >= loc) bad(at + ": operand a is not an earlier node of its row");
                 aa = k0 + ka;
-                if (o >= ASM_OP_ADD && o <= ASM_OP_DIV) {
+                if ((o >= ASM_OP_ADD && o <= ASM_OP_DIV) || (o >= ASM_OP_POW && o <= ASM_OP_MAX)) {
                     if (kb < 0 || kb >= loc) bad(at + ": operand b is not an earlier node of its row");
                     bb = k0 + kb;
                 } else if (o == ASM_OP_POWI) {

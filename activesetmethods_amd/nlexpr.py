@@ -3,13 +3,15 @@ a Julia binding receives from `MOI.constraint_expr` / `MOI.objective_expr` after
 
     x = variables(n)                       x[j] is variable j (0-based)
     e = x[0] * x[1] - sin(x[2]) / 2        + - * / unary -, ** int, sin cos exp log sqrt
+    e = pow(x[0], 1.5) + abs(x[1] - 1)      abs tan asin acos atan sinh cosh tanh log10 log2 log1p expm1 cbrt, pow(u, v),
+                                           atan(y, x), minimum(...), maximum(...)
     ExprBlock(constraints=[(e, lo, hi)], objective=None, n=n)
 
 ExprBlock flattens every row (and every objective term) into the tape of include/asm_hip.h ("Expression block", nlp_kind 3):
 nodes (op, a, b) in SSA order, references local to the row, shared sub-expressions emitted once, each variable once per row.
 It is an NlpBlock (moi_evaluator.py) whose `device` is ("expr", ipar, dpar) and whose host callbacks interpret the same tape with
 the same formulas in the same order as the kernels of csrc/asm_eval_kernels.hip.h (vectorised over rows, one IEEE operation per
-node and row): with + - * / unary - and ** only, host and device agree bit for bit.
+node and row): with + - * / unary -, **, abs, minimum and maximum only, host and device agree bit for bit.
 
 The objective, when given, is split into terms along its left spine of additions (((t1 + t2) + t3) -> [t1, t2, t3]) and summed
 in term order from 0.0; it replaces the FunctionModel's own objective (`has_objective`, MOI_wrapper.jl:809-861).
@@ -22,11 +24,12 @@ import numpy as np
 from .moi_evaluator import NlpBlock
 
 # op codes of include/asm_hip.h (ASM_OP_*)
-CONST, VAR, ADD, SUB, MUL, DIV, NEG, POWI, SQRT, EXP, LOG, SIN, COS = range(13)
-OP_COUNT = 13
+(CONST, VAR, ADD, SUB, MUL, DIV, NEG, POWI, SQRT, EXP, LOG, SIN, COS, ABS, TAN, ASIN, ACOS, ATAN, SINH, COSH, TANH, LOG10, LOG2,
+ LOG1P, EXPM1, CBRT, POW, ATAN2, MIN, MAX) = range(30)
+OP_COUNT = 30
 MAX_POWI = 64
-_BINARY = (ADD, SUB, MUL, DIV)
-_UNARY = (NEG, POWI, SQRT, EXP, LOG, SIN, COS)
+_BINARY = (ADD, SUB, MUL, DIV, POW, ATAN2, MIN, MAX)
+LN10, LN2 = 2.302585092994045684, 0.6931471805599453094     # EXPR_LN10 / EXPR_LN2 of the kernels (log(10), log(2) as doubles)
 
 
 class Expr:
@@ -49,6 +52,7 @@ class Expr:
     def __rtruediv__(self, o): return Expr(DIV, (_wrap(o), self))
     def __neg__(self): return Expr(NEG, (self,))
     def __pos__(self): return self
+    def __abs__(self): return Expr(ABS, (self,))
 
     def __pow__(self, e):
         if not isinstance(e, numbers.Integral) or isinstance(e, bool):
@@ -93,6 +97,39 @@ def _unary(op):
 
 
 sqrt, exp, log, sin, cos = (_unary(o) for o in (SQRT, EXP, LOG, SIN, COS))
+tan, asin, acos, sinh, cosh, tanh, log10, log2, log1p, expm1, cbrt = (
+    _unary(o) for o in (TAN, ASIN, ACOS, SINH, COSH, TANH, LOG10, LOG2, LOG1P, EXPM1, CBRT))
+
+
+def atan(y, x=None):
+    """atan(y) or, as Julia's atan(y, x), the angle of (x, y)."""
+    if x is None:
+        return Expr(ATAN, (_wrap(y),))
+    return Expr(ATAN2, (_wrap(y), _wrap(x)))
+
+
+def pow(u, v):
+    """u ^ v for any exponent, a number or an expression (a POW node; ** keeps integer exponents to POWI)."""
+    return Expr(POW, (_wrap(u), _wrap(v)))
+
+
+def _chain(op, args):
+    if not args:
+        raise TypeError("at least one argument is needed")
+    e = _wrap(args[0])
+    for v in args[1:]:
+        e = Expr(op, (e, _wrap(v)))
+    return e
+
+
+def minimum(*args):
+    """min(a, b, c, ...) as a left-to-right chain of MIN nodes (a tie or a NaN takes the left operand and its derivative)."""
+    return _chain(MIN, args)
+
+
+def maximum(*args):
+    """max(a, b, c, ...) as a left-to-right chain of MAX nodes."""
+    return _chain(MAX, args)
 
 
 def _split_terms(e):
@@ -179,6 +216,10 @@ def _powi(u, e):
     return 1.0 / pk, float(e) / (pk * u)
 
 
+_NP_UNARY = {ABS: np.abs, TAN: np.tan, ASIN: np.arcsin, ACOS: np.arccos, ATAN: np.arctan, SINH: np.sinh, COSH: np.cosh,
+             TANH: np.tanh, LOG10: np.log10, LOG2: np.log2, LOG1P: np.log1p, EXPM1: np.expm1, CBRT: np.cbrt}
+
+
 class _Sweep:
     """The host twin of expr_forward / expr_reverse for a group of rows: rows padded to the longest, node position k evaluated
     for all rows at once, grouped by op (each node of each row is still the one IEEE operation the kernel performs)."""
@@ -233,8 +274,20 @@ class _Sweep:
                         v = np.log(V[r, a])
                     elif o == SIN:
                         v = np.sin(V[r, a])
-                    else:
+                    elif o == COS:
                         v = np.cos(V[r, a])
+                    elif o in _NP_UNARY:
+                        v = _NP_UNARY[o](V[r, a])
+                    elif o == POW:
+                        v = np.power(V[r, a], V[r, b])
+                    elif o == ATAN2:
+                        v = np.arctan2(V[r, a], V[r, b])
+                    elif o == MIN:
+                        u, y = V[r, a], V[r, b]
+                        v = np.where(y < u, y, u)
+                    else:                                 # MAX
+                        u, y = V[r, a], V[r, b]
+                        v = np.where(y > u, y, u)
                     V[r, k] = v
         return V, V[np.arange(self.nr), self.last]
 
@@ -280,8 +333,53 @@ class _Sweep:
                         W[r, a] = W[r, a] + w / V[r, a]
                     elif o == SIN:
                         W[r, a] = W[r, a] + w * np.cos(V[r, a])
-                    else:
+                    elif o == COS:
                         W[r, a] = W[r, a] - w * np.sin(V[r, a])
+                    elif o == ABS:
+                        W[r, a] = W[r, a] + w * np.copysign(1.0, V[r, a])
+                    elif o == TAN:
+                        v = V[r, k]
+                        W[r, a] = W[r, a] + w * (1.0 + v * v)
+                    elif o == ASIN:
+                        u = V[r, a]
+                        W[r, a] = W[r, a] + w / np.sqrt(1.0 - u * u)
+                    elif o == ACOS:
+                        u = V[r, a]
+                        W[r, a] = W[r, a] - w / np.sqrt(1.0 - u * u)
+                    elif o == ATAN:
+                        u = V[r, a]
+                        W[r, a] = W[r, a] + w / (1.0 + u * u)
+                    elif o == SINH:
+                        W[r, a] = W[r, a] + w * np.cosh(V[r, a])
+                    elif o == COSH:
+                        W[r, a] = W[r, a] + w * np.sinh(V[r, a])
+                    elif o == TANH:
+                        v = V[r, k]
+                        W[r, a] = W[r, a] + w * (1.0 - v * v)
+                    elif o == LOG10:
+                        W[r, a] = W[r, a] + w / (V[r, a] * LN10)
+                    elif o == LOG2:
+                        W[r, a] = W[r, a] + w / (V[r, a] * LN2)
+                    elif o == LOG1P:
+                        W[r, a] = W[r, a] + w / (1.0 + V[r, a])
+                    elif o == EXPM1:
+                        W[r, a] = W[r, a] + w * (V[r, k] + 1.0)
+                    elif o == CBRT:
+                        v = V[r, k]
+                        W[r, a] = W[r, a] + w / (3.0 * (v * v))
+                    elif o == POW:
+                        u, y = V[r, a], V[r, b]
+                        W[r, a] = W[r, a] + w * (y * np.power(u, y - 1.0))
+                        W[r, b] = W[r, b] + w * (V[r, k] * np.log(u))
+                    elif o == ATAN2:
+                        u, y = V[r, a], V[r, b]
+                        t = u * u + y * y
+                        W[r, a] = W[r, a] + (w * y) / t
+                        W[r, b] = W[r, b] - (w * u) / t
+                    else:                                 # MIN, MAX: all of w to the chosen operand (ties and NaN: a)
+                        u, y = V[r, a], V[r, b]
+                        c = np.where(y < u if o == MIN else y > u, b, a)
+                        W[r, c] = W[r, c] + w
 
 
 class ExprBlock(NlpBlock):

@@ -186,6 +186,27 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *     ASM_OP_ADD / SUB / MUL / DIV   a op b             ASM_OP_NEG   -a
  *     ASM_OP_POWI   a ^ b, b an integer, 1 <= |b| <= ASM_EXPR_MAX_POWI (|b| - 1 products left to right; 1 / that for b < 0)
  *     ASM_OP_SQRT / EXP / LOG / SIN / COS   of a        (b unused: 0)
+ *     ASM_OP_ABS .. ASM_OP_CBRT   unary, of a (b unused: 0);  ASM_OP_POW .. ASM_OP_MAX   binary, a and b as for ADD..DIV
+ *   Values and adjoints of the ops after COS (u = value of a, y = value of b, v = the node's value, w = the node's adjoint;
+ *   "+=" is adj = adj + (the right side), each parenthesis one rounding, in this order):
+ *     ABS    fabs(u)          adj[a] += w * copysign(1.0, u)           (+1 at +0.0, -1 at -0.0)
+ *     TAN    tan(u)           adj[a] += w * (1 + v*v)
+ *     ASIN   asin(u)          adj[a] += w / sqrt(1 - u*u)
+ *     ACOS   acos(u)          adj[a] -= w / sqrt(1 - u*u)
+ *     ATAN   atan(u)          adj[a] += w / (1 + u*u)
+ *     SINH   sinh(u)          adj[a] += w * cosh(u)
+ *     COSH   cosh(u)          adj[a] += w * sinh(u)
+ *     TANH   tanh(u)          adj[a] += w * (1 - v*v)
+ *     LOG10  log10(u)         adj[a] += w / (u * ln10)                  (ln10, ln2: the doubles nearest to ln 10, ln 2)
+ *     LOG2   log2(u)          adj[a] += w / (u * ln2)
+ *     LOG1P  log1p(u)         adj[a] += w / (1 + u)
+ *     EXPM1  expm1(u)         adj[a] += w * (v + 1)
+ *     CBRT   cbrt(u)          adj[a] += w / (3 * (v*v))
+ *     POW    pow(u, y)        adj[a] += w * (y * pow(u, y - 1));  then adj[b] += w * (v * log(u))  (a CONST b drops its adjoint)
+ *     ATAN2  atan2(u, y)      t = u*u + y*y;  adj[a] += (w * y) / t;  then adj[b] -= (w * u) / t   (Julia atan(a, b))
+ *     MIN    y < u ? y : u    w to the chosen operand: adj[b] += w if y < u, else adj[a] += w (ties and NaN go to a)
+ *     MAX    y > u ? y : u    adj[b] += w if y > u, else adj[a] += w
+ *   Domain errors (log of a negative number, asin outside [-1, 1], ...) give NaN or inf as the math library does.
  *   ipar = [R, T, L, ptr[R+T+1], op[L], a[L], b[L]] (ptr[0] = 0, ptr[R+T] = L, every row / term at least one node);
  *   dpar = the constants.
  *   Jacobian pattern: each row's distinct variables in ascending order, rows in order; nlp_nnz = the sum of their counts and
@@ -194,13 +215,16 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *   store's objective row (has_objective of the reference's NLP block, MOI_wrapper.jl:809-861).  Gradient per variable: the
  *   adjoints of its VAR nodes summed in (term, node) order, times objective_scale.  Jacobian value: the adjoints of the row's
  *   VAR nodes of that variable, added in reverse node order.
- *   Derivatives are reverse-mode with fixed formulas and no fused multiply-add: with ADD..POWI only, device values equal the
- *   host twin (activesetmethods_amd/nlexpr.py) bit for bit.
+ *   Derivatives are reverse-mode with fixed formulas and no fused multiply-add: with ADD..POWI, ABS, MIN and MAX only, device
+ *   values equal the host twin (activesetmethods_amd/nlexpr.py) bit for bit; the other ops differ in the math library's last bits.
  *   A malformed tape (forward or out-of-row reference, unknown op, variable / constant out of range, bad POWI exponent, size
  *   mismatch, a pattern that differs from j_str) is rejected with ASM_ERR_ARG and the handle keeps its previous evaluator. */
 enum { ASM_NLP_NONE = 0, ASM_NLP_ACOPF_OHM = 1, ASM_NLP_DENSE_QUADRATIC = 2, ASM_NLP_EXPR = 3 };
 enum { ASM_OP_CONST = 0, ASM_OP_VAR = 1, ASM_OP_ADD = 2, ASM_OP_SUB = 3, ASM_OP_MUL = 4, ASM_OP_DIV = 5, ASM_OP_NEG = 6, ASM_OP_POWI = 7,
-       ASM_OP_SQRT = 8, ASM_OP_EXP = 9, ASM_OP_LOG = 10, ASM_OP_SIN = 11, ASM_OP_COS = 12, ASM_OP_COUNT = 13 };
+       ASM_OP_SQRT = 8, ASM_OP_EXP = 9, ASM_OP_LOG = 10, ASM_OP_SIN = 11, ASM_OP_COS = 12,
+       ASM_OP_ABS = 13, ASM_OP_TAN = 14, ASM_OP_ASIN = 15, ASM_OP_ACOS = 16, ASM_OP_ATAN = 17, ASM_OP_SINH = 18, ASM_OP_COSH = 19,
+       ASM_OP_TANH = 20, ASM_OP_LOG10 = 21, ASM_OP_LOG2 = 22, ASM_OP_LOG1P = 23, ASM_OP_EXPM1 = 24, ASM_OP_CBRT = 25,
+       ASM_OP_POW = 26, ASM_OP_ATAN2 = 27, ASM_OP_MIN = 28, ASM_OP_MAX = 29, ASM_OP_COUNT = 30 };
 enum { ASM_EXPR_MAX_POWI = 64 };
 int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const int64_t* aff_var, const double* aff_coef,
                    const int64_t* quad_ptr, const int64_t* q_v1, const int64_t* q_v2, const double* q_coef,
