@@ -597,73 +597,67 @@ struct Dev {
     // device-pointer variants (the IPM keeps its vectors in HBM)
     void gemv_n_dev(const double* A, const double* x, double* out) { launch_gemv_n(A, x, out); }
     void gemv_t_dev(const double* A, const double* y, double* out) { launch_gemv_t(A, y, out); }
-    void syrk_dev(const int* idx_dev, int Ms, const double* theta_dev, const double* diag_dev) {
-        h->main_fac.band = 0;
-        const bool skip = h->nz_valid && idx_dev == nullptr && Ms == (int)h->M && pick_tile(Ms) == h->nz_T;
-        int id = begin(ASM_K_SYRK, (skip ? h->nz_fraction : 1.0) * (double)Ms * (Ms + 1) * h->ldn,
-                       8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(h->stream, pick_tile(Ms), h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, diag_dev, h->main_fac.S, h->main_fac.ld, 0, 0, -1,
-                    skip ? h->d_nz : nullptr, h->nz_pitch);
+    // Which chunk flags a Schur build skips by: Pattern = the fixed flags of all rows (tile_flags; of all columns for the transposed copy,
+    // ensure_AhT), used when they fit the build; PerCall = made here for the row list, their executed share cached in `cache_slot` (>= 0)
+    enum class NzFlags { Pattern, PerCall };
+    // S[0:Ms,0:Ms] (lower, pitch ldS) = A[idx,:] diag(theta) A[idx,:]' + diag   with A = Ah, or with cols = true its transposed copy AhT
+    // (column form: K = AhT diag(dinv) AhT' + diag(th)); idx == nullptr: the first Ms rows; everything already on the device
+    void schur_syrk(bool cols, const int* idx_dev, int Ms, const double* theta_dev, const double* diag_dev, double* S, int64_t ldS, NzFlags flags,
+                    int cache_slot = -1) {
+        if (cols) ensure_AhT();
+        const double* A = cols ? h->d_AhT : h->d_Ah;
+        const int64_t ld = cols ? h->ldT : h->ldn;
+        const int T = pick_tile(Ms);
+        int nch = (int)(ld / ASM_KC);
+        const unsigned char* nz = nullptr;
+        double frac = 1.0;
+        if (flags == NzFlags::PerCall) {
+            const int TS = 32 * T, nt = (Ms + TS - 1) / TS;
+            if (h->nz_valid && nt > 0) {
+                unsigned char* nz2 = h->d_nz + h->nz_half;
+                hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, A, ld, (int64_t)Ms, TS, nch, nz2, nch, idx_dev);
+                frac = executed_fraction(nz2, nt, nch, cache_slot);
+                nz = nz2;
+            }
+        } else if (cols) {
+            if (h->nzT_valid) { nz = h->d_nzT; frac = h->nzT_fraction; }
+        } else {
+            nch = h->nz_pitch;
+            if (h->nz_valid && idx_dev == nullptr && Ms == (int)h->M && T == h->nz_T) { nz = h->d_nz; frac = h->nz_fraction; }
+        }
+        int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * ld, 8.0 * (Ms * (double)ld + 0.5 * Ms * (double)Ms));
+        launch_syrk(h->stream, T, A, ld, idx_dev, 0, Ms, (int)ld, theta_dev, diag_dev, S, ldS, 0, 0, -1, nz, nch, frac);
         end(id);
     }
-    // S[0:Ms,0:Ms] (lower) = Ah[idx,:] diag(theta) Ah[idx,:]' + diag   with idx / theta / diag already on the device and the
-    // chunk flags of the gathered row set (reduced row form of the interior-point system)
-    // S[0:Ms,0:Ms] (lower) of the same matrix for a row list in the handle's reverse Cuthill-McKee order (asm_handle::row_band): banded,
-    // built entry by entry from the structural pairs - cpos maps a row to its place in the list (-1: not in it).  The factorisation and the
-    // substitutions that follow stop at the band (the main factor's band).
+    // The main factor's Schur matrix of a row list (reduced row form, active-set partitions): with the rows in the handle's banded order
+    // (row_band > 0) built from the structural pairs - cpos maps a row to its place in the list - else gathered through idx
+    void schur_rows(const int* idx_dev, const int* cpos_dev, int Ms, const double* theta_dev, const double* diag_dev) {
+        if (h->row_band > 0) schur_banded_dev(cpos_dev, Ms, theta_dev, diag_dev);
+        else schur_syrk(false, idx_dev, Ms, theta_dev, diag_dev, h->main_fac.S, h->main_fac.ld, NzFlags::PerCall);
+    }
+    // clears the lower band of a banded factor's first Ms rows before an entry-by-entry build: the band plus what the blocked factorisation
+    // reads beyond it (an outer panel of CHOL_NBO columns, tile rounding)
+    void zero_band(const FacBuf& f, int Ms, int band) {
+        const int64_t wz = std::min<int64_t>(round_up(band + 1, 64) + CHOL_NBO + 128, f.ld);
+        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), 0, h->stream, f.S, f.ld, Ms, (int)wz);
+    }
+    // S[0:Ms,0:Ms] (lower) = Ah[idx,:] diag(theta) Ah[idx,:]' + diag for a row list in the handle's reverse Cuthill-McKee order
+    // (asm_handle::row_band): banded, built entry by entry from the structural pairs - cpos maps a row to its place in the list (-1: not
+    // in it).  The factorisation and the substitutions that follow stop at the band (the main factor's band).
     void schur_banded_dev(const int* cpos_dev, int Ms, const double* theta_dev, const double* diag_dev) {
         FacBuf& f = h->main_fac;
-        // the band plus what the blocked factorisation reads beyond it (an outer panel of CHOL_NBO columns, tile rounding)
-        const int64_t wz = std::min<int64_t>(round_up(h->row_band + 1, 64) + CHOL_NBO + 128, f.ld);
-        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), 0, h->stream, f.S, f.ld, Ms, (int)wz);
+        zero_band(f, Ms, h->row_band);
         hipLaunchKernelGGL(k_schur_sparse, dim3((unsigned)((h->n_rowpairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowpairs, h->n_rowpairs, cpos_dev,
                            h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), theta_dev, diag_dev, f.S, f.ld, (const int*)nullptr);
-        f.band = h->row_band;
     }
     // K = diag + Ah' diag(dinv) Ah (n x n, lower) with the COLUMNS in their reverse Cuthill-McKee order (asm_handle::col_band): the column form
     // of the restoration-phase Newton system, banded and built from the structural column pairs; `diag_place` is indexed by position
     void schur_banded_cols_dev(const double* dinv_dev, const double* diag_place) {
         FacBuf& f = h->main_fac;
         const int n = (int)h->n;
-        const int64_t wz = std::min<int64_t>(round_up(h->col_band + 1, 64) + CHOL_NBO + 128, f.ld);
-        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, f.S, f.ld, n, (int)wz);
+        zero_band(f, n, h->col_band);
         hipLaunchKernelGGL(k_schur_sparse, dim3((unsigned)((h->n_colpairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_colpairs, h->n_colpairs,
                            (const int*)h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah), dinv_dev, diag_place, f.S, f.ld, (const int*)h->d_sc_pos);
-        f.band = h->col_band;
-    }
-    void syrk_gathered_dev(const int* idx_dev, int Ms, const double* theta_dev, const double* diag_dev) {
-        h->main_fac.band = 0;
-        const int nch = (int)(h->ldn / ASM_KC);
-        const int T = pick_tile(Ms), TS = 32 * T;
-        const int nt = (Ms + TS - 1) / TS;
-        const bool skip = h->nz_valid && nt > 0;
-        unsigned char* nz2 = h->d_nz + h->nz_half;
-        double frac = 1.0;
-        if (skip) {
-            hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, h->d_Ah, h->ldn, (int64_t)Ms, TS, nch,
-                               nz2, nch, idx_dev);
-            frac = executed_fraction(nz2, nt, nch);
-        }
-        int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * h->ldn, 8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(h->stream, T, h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, diag_dev, h->main_fac.S, h->main_fac.ld, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
-        end(id);
-    }
-    // S[0:Ms,0:Ms] (lower, pitch ldS) = Ah[idx,:] diag(theta) Ah[idx,:]'  into an arbitrary buffer (null-space form: S0 = A_EF A_EF')
-    void syrk_gathered_into(const int* idx_dev, int Ms, const double* theta_dev, double* S, int64_t ldS) {
-        const int nch = (int)(h->ldn / ASM_KC);
-        const int T = pick_tile(Ms), TS = 32 * T;
-        const int nt = (Ms + TS - 1) / TS;
-        const bool skip = h->nz_valid && nt > 0;
-        unsigned char* nz2 = h->d_nz + h->nz_half;
-        double frac = 1.0;
-        if (skip) {
-            hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, h->d_Ah, h->ldn, (int64_t)Ms, TS, nch,
-                               nz2, nch, idx_dev);
-            frac = executed_fraction(nz2, nt, nch, idx_dev == h->d_nsEidx ? 1 : -1);
-        }
-        int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * h->ldn, 8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(h->stream, T, h->d_Ah, h->ldn, idx_dev, 0, Ms, (int)h->ldn, theta_dev, nullptr, S, ldS, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
-        end(id);
     }
     // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32
     void gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, const double* C0, int64_t ldc0, double* C, int64_t ldc, int Ma, int Mb, int K, int mode) {
@@ -724,18 +718,6 @@ struct Dev {
             h->nzT_valid = true;
         }
         h->ahT_valid = true;
-    }
-    // S[0:n,0:n] (lower) = AhT diag(dinv) AhT' + diag(th)
-    void syrk_col(const double* dinv_dev, const double* th_dev) {
-        h->main_fac.band = 0;
-        ensure_AhT();
-        const int n = (int)h->n;
-        const int nch = (int)(h->ldT / ASM_KC);
-        const double frac = h->nzT_valid ? h->nzT_fraction : 1.0;
-        int id = begin(ASM_K_SYRK, frac * (double)n * (n + 1) * h->ldT, 8.0 * (n * (double)h->ldT + 0.5 * n * (double)n));
-        launch_syrk(h->stream, pick_tile(n), h->d_AhT, h->ldT, nullptr, 0, n, (int)h->ldT, dinv_dev, th_dev, h->main_fac.S, h->main_fac.ld, 0, 0, -1,
-                    h->nzT_valid ? h->d_nzT : nullptr, nch, frac);
-        end(id);
     }
     // per (row tile, k-chunk) non-zero flags of Ah for the chunk-skipping Schur build (sparse Jacobians only)
     void tile_flags() {
@@ -831,30 +813,6 @@ struct Dev {
                                ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
     }
 
-    // S[0:Ms,0:Ms] (lower) = Ah[idx,:] diag(theta) Ah[idx,:]' + diag     idx == nullptr -> identity
-    void syrk(const int* idx_host, int Ms, const double* theta, const double* diag) {
-        h->main_fac.band = 0;
-        h2d(h->d_theta, theta, h->n, h->ldn);
-        if (diag) h2d(h->d_diag, diag, Ms, Ms);
-        if (idx_host) {
-            HIPCHK(hipMemcpyAsync(h->d_idx, idx_host, Ms * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            h2d_done(h);
-        }
-        // sparse Jacobians: chunk flags of the gathered row set (second half of the flag buffer), as in the full Schur build
-        const int nch = (int)(h->ldn / ASM_KC);
-        const int T = pick_tile(Ms), TS = 32 * T;
-        const int nt = (Ms + TS - 1) / TS;
-        const bool skip = h->nz_valid && idx_host != nullptr && nt > 0;
-        unsigned char* nz2 = h->d_nz + h->nz_half;
-        if (skip)
-            hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, h->d_Ah, h->ldn, (int64_t)Ms, TS,
-                               nch, nz2, nch, (const int*)h->d_idx);
-        const double frac = skip ? executed_fraction(nz2, nt, nch) : 1.0;
-        int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * h->ldn, 8.0 * (Ms * (double)h->ldn + 0.5 * Ms * (double)Ms));
-        launch_syrk(h->stream, T, h->d_Ah, h->ldn, idx_host ? h->d_idx : nullptr, 0, Ms, (int)h->ldn, h->d_theta,
-                    diag ? h->d_diag : nullptr, h->main_fac.S, h->main_fac.ld, 0, 0, -1, skip ? nz2 : nullptr, nch, frac);
-        end(id);
-    }
     void diag_prepare(const FacBuf& f, int Ms, int mode, double rel, double absv) {
         hipLaunchKernelGGL(k_diag_prepare, dim3(1), dim3(1024), 0, h->stream, f.S, f.ld, Ms, h->d_diag0, mode, rel, absv);
     }
@@ -1153,34 +1111,24 @@ struct Solver {
     asm_handle* h;
     Dev dev;
     SLP lp;
-    vec tmpM, tmpN;
 
     explicit Solver(asm_handle* hh) : h(hh), dev(hh) {}
 
-    // t = Ah p + E s
-    void rowact(const vec& p, const vec& s, vec& t) {
-        t.resize(lp.M);
-        dev.gemv_n(h->d_Ah, p.data(), t.data());
-        for (int64_t k = 0; k < lp.ns; ++k) t[lp.srow[k]] += lp.scoef[k] * s[k];
-    }
     void atv(const vec& y, vec& out) {
         out.resize(lp.n);
         dev.gemv_t(h->d_Ah, y.data(), out.data());
     }
 
     // ---------------------------------------------------------------- interior point (oracle: class IPM)
+    // Form of the Newton system of an iteration (oracle: IPM.run, one branch per form): null-space (normal phase,
+    // many hard equality rows), column (restoration phase, dense or banded columns), reduced row (normal phase, large sparse problems),
+    // full row in the handle's banded row order, full dense row.  The first three fall back to the next in this order.
+    enum class NewtonForm { NullSpace, Column, ReducedRow, BandedRow, Row };
     struct IpmState {
-        vec p, s, g, y, tL, tU, muL, muU, ts, mus, pi, rp, rdp, rds;
-        std::vector<char> ineq, free_;
-        vec sg;
         int64_t ncomp = 1;
         vec pinf_hist;
-        bool stalled = false;
-        bool col_ok = false, col_off = false;     // column form available / abandoned for this LP
+        bool usable[3] = {false, false, false};   // NullSpace, Column, ReducedRow: available for this LP (ipm_init), cleared on fall-back
         int col_iters = 0;
-        bool red_ok = false, red_off = false;     // reduced row form (normal phase, large sparse problems)
-        int red_iters = 0;
-        bool ns_ok = false, ns_off = false, ns_ready = false;   // null-space form (normal phase, many hard equality rows)
         int ns_iters = 0, ns_k = 0;
         bool ns_e_ready = false;  // the component e of the iterate outside pbar + null(A_EF) has been split off
         int iters = 0;
@@ -1303,11 +1251,10 @@ struct Solver {
         for (int64_t i = 0; i < M; ++i) nineq += lp.rtype[i] != 0;
         for (int64_t j = 0; j < n; ++j) nfree += lp.ub[j] > lp.lb[j];
         ip.ncomp = std::max<int64_t>(2 * nfree + lp.ns + nineq, 1);
-        ip.red_ok = M >= RED_MIN_M && h->sp_ok;
-        ip.ns_ok = ns_lp && lp.ns == 0;      // basis made by solve_scaled before the warm attempt
-        ip.ns_ready = true;
+        ip.usable[(int)NewtonForm::ReducedRow] = M >= RED_MIN_M && h->sp_ok;
+        ip.usable[(int)NewtonForm::NullSpace] = ns_lp && lp.ns == 0;      // basis made by solve_scaled before the warm attempt
         ip.ns_k = ns_k;
-        ip.col_ok = h->col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
+        ip.usable[(int)NewtonForm::Column] = h->col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
         ipm_upload_lp();
         P.ncomp = ip.ncomp;
         hipLaunchKernelGGL(k_ipm_init_p, dim3(grid_all()), dim3(256), 0, h->stream, P, lp.ns == 0 ? 1 : 0);
@@ -1336,16 +1283,6 @@ struct Solver {
         ip.rpmax = h->h_scal[SC_RPMAX];
     }
 
-    // pull the iterate back to the host (identification, certificates, unpolished fallback)
-    void ipm_download() {
-        down(ip.p, P.p, lp.n); down(ip.tL, P.tL, lp.n); down(ip.tU, P.tU, lp.n); down(ip.muL, P.muL, lp.n); down(ip.muU, P.muU, lp.n);
-        down(ip.g, P.g, lp.M); down(ip.pi, P.pi, lp.M); down(ip.y, P.y, lp.M);
-        down(ip.s, P.s, lp.ns); down(ip.ts, P.ts, lp.ns); down(ip.mus, P.mus, lp.ns);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        ip.free_.resize(lp.n);
-        for (int64_t j = 0; j < lp.n; ++j) ip.free_[j] = lp.ub[j] > lp.lb[j];
-    }
-
     // rigorous primal-infeasibility certificate test (oracle: farkas_margin)
     double farkas_margin(const vec& y) {
         double ymax = 0.0;
@@ -1367,8 +1304,8 @@ struct Solver {
         return ynr - lhs;
     }
 
-    // ------------------------------------------------------------ null-space form (oracle: class NullSpace / IPM.run use_ns)
-    bool use_ns = false, ns_was_cold = false;
+    // ------------------------------------------------------------ null-space form (oracle: class NullSpace / IPM.run, null-space branch)
+    bool ns_was_cold = false;
     bool ns_lp = false;       // this LP has a valid null-space basis (set up before the warm attempt: the active-set solves use it too)
     int ns_k = 0;
     SolveHint* cur_hint = nullptr;
@@ -1503,12 +1440,12 @@ struct Solver {
         if (h->ns_f0.band > 0) {
             // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
             // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
-            const int64_t wz = std::min<int64_t>(round_up(h->ns_f0.band + 1, 64) + CHOL_NBO + 128, h->ns_f0.ld);      // band + what the blocked factorisation reads beyond it
-            hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)nE), dim3(256), 0, h->stream, h->ns_f0.S, h->ns_f0.ld, nE, (int)wz);
+            dev.zero_band(h->ns_f0, nE, h->ns_f0.band);
             hipLaunchKernelGGL(k_ns_s0_sparse, dim3((unsigned)((h->ns_npairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_nsS0pairs, h->ns_npairs, h->d_sp_ptr,
                                h->d_sp_col, dev.sparse_vals(h->d_Ah), (const int*)h->d_nsEidx, (const double*)h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
         } else {
-            dev.syrk_gathered_into(h->d_nsEidx, nE, h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
+            // S0 = A_EF A_EF' (the share of its chunk products cached per handle: the equality rows are fixed)
+            dev.schur_syrk(false, h->d_nsEidx, nE, h->d_nsFm, nullptr, h->ns_f0.S, h->ns_f0.ld, Dev::NzFlags::PerCall, 1);
         }
         vlap("S0 build");
         dev.diag_prepare(h->ns_f0, nE, 1, 0.0, 0.0);
@@ -1675,7 +1612,8 @@ struct Solver {
         h->stats.eqp += 1;
         return true;
     }
-    bool ns_live() const { return ip.ns_ok && !ip.ns_off; }
+    bool usable(NewtonForm f) const { return ip.usable[(int)f]; }      // (NullSpace, Column, ReducedRow)
+    bool ns_live() const { return usable(NewtonForm::NullSpace); }
     // least-squares multipliers of the equality rows for the current iterate (oracle: IPM.ns_finish_y); P.rdp is the dual residual of the last
     // measures (with the equality multipliers as they stand: 0, or the values recovered at the end of the previous stage)
     void ns_finish_y() {
@@ -1689,14 +1627,14 @@ struct Solver {
         // P.rdp already contains -A_E'y_E of the multipliers recovered at the end of an earlier stage: the solve gives the correction
         hipLaunchKernelGGL(k_ns_scatter_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)tE, P.y, 1);
     }
-    // Per iteration (oracle: IPM.run, use_ns branch): reduced matrix N = Zt Th Zt' + GI' D_I^-1 GI (an unregularised copy is kept for the
+    // Per iteration (oracle: IPM.run, null-space branch): reduced matrix N = Zt Th Zt' + GI' D_I^-1 GI (an unregularised copy is kept for the
     // refinement sweep), its factor, dpbar = A_EF' S0^-1 (-rp_E) and K dpbar (shared by predictor and corrector)
     void ns_iter_setup() {
         const int k = ip.ns_k;
         const int64_t M = lp.M, ldn = h->ldn;
         const NsIdx X = nsX();
         const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256);
-        double *dpb = nsv(0), *kdpb = nsv(1), *atw = nsv(4), *yM = nsv(5), *aM = nsv(6);
+        double *dpb = nsv(0), *kdpb = nsv(1), *yM = nsv(5);
         const double* th = h->d_nsth;
         const double* thI = h->d_nsth + ldn;
         // (theta~ was formed with the interior-point theta: k_ipm_theta_ns in ipm_run)
@@ -1737,7 +1675,6 @@ struct Solver {
                            P.scal + SC_NSERR, X, thI, yM, M);
         hipLaunchKernelGGL(k_ns_spmvt_kx, dim3((unsigned)((ldn * 8 + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_sc_ptr, (const int*)h->d_sc_row, (const int*)h->d_sc_pos, vals,
                            (const double*)yM, th, (const double*)dpb, kdpb, lp.n, ldn);
-        (void)aM; (void)atw;
     }
     // One Newton solve in null-space form (oracle: IPM.run, solve_ns): mode 0 affine, 1 Mehrotra corrector on `base`.  The relative residual of
     // the reduced solve (after its refinement sweep) is accumulated in SC_NSERR.
@@ -1746,7 +1683,7 @@ struct Solver {
         const int64_t M = lp.M, n = lp.n, ldn = h->ldn;
         const NsIdx X = nsX();
         const unsigned g = grid_all(), gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256), gK = (unsigned)((k + 255) / 256);
-        double *dpb = nsv(0), *kdpb = nsv(1), *ht = nsv(2), *v = nsv(3), *atw = nsv(4), *yM = nsv(5), *aM = nsv(6), *bI = nsv(7);
+        double *dpb = nsv(0), *kdpb = nsv(1), *ht = nsv(2), *v = nsv(3), *yM = nsv(5), *bI = nsv(7);
         double *ru = nsv(10), *du = nsv(11), *rr = nsv(12), *dd = nsv(13);
         const double* th = h->d_nsth;
         const double* thI = h->d_nsth + ldn;
@@ -1775,7 +1712,6 @@ struct Solver {
             hipLaunchKernelGGL(k_ns_dp, dim3(gN), dim3(256), 0, h->stream, P, D, th, (const double*)dpb, res, (const double*)v, ldn);
         }
         hipLaunchKernelGGL(k_ns_spmvn_rows, dim3(gM), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col, vals, P, D, X, thI, (const double*)bI, yM);
-        (void)aM; (void)atw;
     }
     // out[n] = Zt' u   (Zt dense, k rows of pitch ldg)
     void ns_gemv_t_dense(const double* u, int k, double* out) {
@@ -1791,45 +1727,44 @@ struct Solver {
         hipLaunchKernelGGL(k_gemv_t_stage2, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, h->d_partial, out, R, h->ldn);
     }
 
-    bool use_red = false;     // reduced row form: factor of the rows redE, diagonal on the rows redI
-    bool use_perm = false;    // full row form with the rows in the handle's banded order (row_band > 0): solves gather / scatter through d_rowperm
-    std::vector<int> redE, redI;
-    int nE = 0, nI = 0;
-    vec tmpM2;
-    bool use_col = false;     // form of the current factorisation
+    NewtonForm form = NewtonForm::Row;      // form of the current factorisation
+    // reduced row form: the rows kept in the factor (in the order of the factorisations) and the rows left to a diagonal preconditioner,
+    // chosen from host copies of the slack terms dS and of the Schur diagonal
+    struct ReducedRows {
+        std::vector<int> kept, diag;
+        vec dS, sdiag;
+    } red;
     int cg_max = 0;           // most CG steps any solve of the current iteration needed
     bool cg_fail = false;     // a solve of the current iteration left its CG loop without reaching the tolerance
-    // out = (approximate) S^-1 in : the Cholesky factor of S (row form) or Sherman-Morrison-Woodbury through the factor of K
+    // out = in through the main factor of a row (column) list: gather in[idx[0:cnt]], solve, scatter back; k_red_scatter gives the
+    // ndrop rows didx outside the list out = in / ddrop (pure permutations: none).  The scatter covers `len` rows.
+    void solve_list(const int* idx, int cnt, const int* didx, int ndrop, const double* ddrop, const double* in, double* out, int64_t len) {
+        hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, idx, cnt, in, h->d_rce);
+        dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, cnt);
+        hipLaunchKernelGGL(k_red_scatter, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, h->stream, idx, cnt, (const double*)h->d_rze, didx, ndrop, ddrop, in, out);
+    }
+    // out = (approximate) S^-1 in : the Cholesky factor of S (row forms) or Sherman-Morrison-Woodbury through the factor of K (column form)
     void precond(const double* in, double* out) {
-        const int M = (int)lp.M;
+        const int M = (int)lp.M, n = (int)lp.n;
         const unsigned gm = (unsigned)((lp.M + 255) / 256);
-        if (use_red) {
-            hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((nE + 255) / 256)), dim3(256), 0, h->stream, h->d_idx, nE, in, h->d_rce);
-            dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, nE);
-            hipLaunchKernelGGL(k_red_scatter, dim3(gm), dim3(256), 0, h->stream, h->d_idx, nE, h->d_rze, h->d_idxI, nI, h->d_rdI, in, out);
+        switch (form) {
+        case NewtonForm::ReducedRow:
+            solve_list(h->d_idx, (int)red.kept.size(), h->d_idxI, (int)red.diag.size(), h->d_rdI, in, out, M);
             return;
-        }
-        if (use_perm) {
-            hipLaunchKernelGGL(k_red_gather, dim3(gm), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, in, h->d_rce);
-            dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, M);
-            hipLaunchKernelGGL(k_red_scatter, dim3(gm), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, (const double*)h->d_rze, (const int*)h->d_rowperm, 0,
-                               (const double*)h->d_rze, in, out);
+        case NewtonForm::BandedRow:      // rows in the handle's banded order
+            solve_list(h->d_rowperm, M, h->d_rowperm, 0, h->d_rze, in, out, M);
             return;
+        case NewtonForm::Column:
+            hipLaunchKernelGGL(k_col_scale, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, in, h->d_cu, lp.M);      // u = D^-1 r
+            dev.gemv_t_dev(h->d_Ah, h->d_cu, h->d_ct);                                                                 // Ah' u
+            if (h->col_band > 0) solve_list(h->d_colperm, n, h->d_colperm, 0, h->d_rze, h->d_ct, h->d_cv, n);         // K^-1 (columns in banded order)
+            else dev.chol_solve_dev(h->main_fac, h->d_ct, h->d_cv, n);                                                 // K^-1
+            dev.gemv_n_dev(h->d_Ah, h->d_cv, h->d_cw);                                                                 // Ah v
+            hipLaunchKernelGGL(k_col_finish, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, h->d_cu, h->d_cw, out, lp.M);
+            return;
+        default:      // Row (the null-space form solves in ns_newton)
+            dev.chol_solve_dev(h->main_fac, in, out, M);
         }
-        if (!use_col) { dev.chol_solve_dev(h->main_fac, in, out, M); return; }
-        hipLaunchKernelGGL(k_col_scale, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, in, h->d_cu, lp.M);      // u = D^-1 r
-        dev.gemv_t_dev(h->d_Ah, h->d_cu, h->d_ct);                                                                 // Ah' u
-        if (h->col_band > 0) {                                                                                     // K^-1 (columns in banded order)
-            const unsigned gn = (unsigned)((lp.n + 255) / 256);
-            hipLaunchKernelGGL(k_red_gather, dim3(gn), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_ct, h->d_rce);
-            dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, (int)lp.n);
-            hipLaunchKernelGGL(k_red_scatter, dim3(gn), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_rze, (const int*)h->d_colperm, 0,
-                               (const double*)h->d_rze, (const double*)h->d_ct, h->d_cv);
-        } else {
-            dev.chol_solve_dev(h->main_fac, h->d_ct, h->d_cv, (int)lp.n);                                                       // K^-1
-        }
-        dev.gemv_n_dev(h->d_Ah, h->d_cv, h->d_cw);                                                                 // Ah v
-        hipLaunchKernelGGL(k_col_finish, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, h->d_cu, h->d_cw, out, lp.M);
     }
     // one Newton solve with the current factor (oracle: IPM.run.solve); mode 0 affine, 1 Mehrotra corrector built on
     // `base`, 2 Gondzio centrality corrector for `base` at the trial steps (tp, td)
@@ -1860,8 +1795,9 @@ struct Solver {
             unsigned pub = pub_next();
             hipLaunchKernelGGL(k_ipm_res, dim3(1), dim3(1024), 0, h->stream, P, d_sres, D.dy, pub, 0, 0.0, 0.0);
             read_scal(pub);
-            // the approximate preconditioner (column form) gets the tighter floor (oracle: IPM.run.solve)
-            const double tol = std::max(((use_col || use_red) ? 1e-13 : 1e-10) * h->h_scal[SC_RMAX], PCG_KAPPA * ip.rpmax);
+            // the approximate preconditioners (column and reduced row form) get the tighter floor (oracle: IPM.run.solve)
+            const bool approx = form == NewtonForm::Column || form == NewtonForm::ReducedRow;
+            const double tol = std::max((approx ? 1e-13 : 1e-10) * h->h_scal[SC_RMAX], PCG_KAPPA * ip.rpmax);
             if (h->h_scal[SC_EMAX] > tol) {
                 precond(P.res, d_corr);
                 hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(1024), 0, h->stream, P, d_corr, d_pcg);
@@ -1885,9 +1821,96 @@ struct Solver {
         hipLaunchKernelGGL(k_ipm_dir, dim3(g), dim3(256), 0, h->stream, P, D, d_tN);
     }
 
+    // reduced row form (oracle: IPM.run): inequality rows whose slack term dominates their Schur diagonal stay out of the factor and get a
+    // diagonal preconditioner.  Reads both vectors back.  False: too few such rows, or no row left for the factor.
+    bool red_select() {
+        dev.schur_diag(P.thp_inv, h->d_sdiag);
+        down(red.dS, P.dS, lp.M);
+        down(red.sdiag, h->d_sdiag, lp.M);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        red.kept.clear(); red.diag.clear();
+        for (int64_t q = 0; q < lp.M; ++q) {                 // kept rows in the order of the factorisations
+            const int64_t i = h->row_band > 0 ? h->row_perm_h[q] : q;
+            if (red.dS[i] > RED_TAU * red.sdiag[i]) red.diag.push_back((int)i);
+            else red.kept.push_back((int)i);
+        }
+        return (double)red.diag.size() >= RED_MIN_FRAC * (double)lp.M && !red.kept.empty();
+    }
+    // the form of this iteration's Newton system, first usable in the order of NewtonForm (oracle: IPM.run)
+    NewtonForm choose_form() {
+        if (usable(NewtonForm::NullSpace)) return NewtonForm::NullSpace;
+        if (usable(NewtonForm::Column)) return NewtonForm::Column;
+        if (usable(NewtonForm::ReducedRow) && red_select()) return NewtonForm::ReducedRow;
+        return h->row_band > 0 ? NewtonForm::BandedRow : NewtonForm::Row;
+    }
+    // The Newton matrix of the current form and its factor (oracle: IPM.run).  Column form: K = Th + Ah' D^-1 Ah (n x n) while its
+    // Sherman-Morrison-Woodbury preconditioner keeps the CG short; row forms: S = Ah Th^-1 Ah' + D (kept rows, or M x M); all three in
+    // the main factor, whose band is that of the handle's column or row order (0: none).
+    void newton_factor() {
+        if (form == NewtonForm::NullSpace) {      // null-space form (oracle: IPM.run): set up once per LP, k x k factorisation per iteration
+            ip.ns_iters += 1;
+            ns_iter_setup();
+            return;
+        }
+        const int M = (int)lp.M, n = (int)lp.n;
+        FacBuf& f = h->main_fac;
+        f.band = form == NewtonForm::Column ? h->col_band : h->row_band;
+        int dim = M;
+        switch (form) {
+        case NewtonForm::Column:
+            ip.col_iters += 1;
+            dim = n;
+            hipLaunchKernelGGL(k_ipm_col_prep, dim3(grid_all()), dim3(256), 0, h->stream, P, IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
+            if (h->col_band > 0) {
+                // columns in their banded order: K built from the structural column pairs, factor and substitutions stop at the band
+                hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_cth, h->d_diag);
+                dev.schur_banded_cols_dev(h->d_cdinv, h->d_diag);
+            } else {
+                dev.schur_syrk(true, nullptr, n, h->d_cdinv, h->d_cth, f.S, f.ld, Dev::NzFlags::Pattern);
+            }
+            break;
+        case NewtonForm::ReducedRow: {
+            // the kept rows with their slack terms; the others' diagonal (Schur diagonal + slack term) for the preconditioner
+            dim = (int)red.kept.size();
+            const int nd = (int)red.diag.size();
+            vec dE_(dim), dI_(nd);
+            for (int a = 0; a < dim; ++a) dE_[a] = red.dS[red.kept[a]];
+            for (int b = 0; b < nd; ++b) dI_[b] = red.sdiag[red.diag[b]] + red.dS[red.diag[b]];
+            HIPCHK(hipMemcpyAsync(h->d_idx, red.kept.data(), dim * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->d_idxI, red.diag.data(), nd * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->d_diag, dE_.data(), dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->d_rdI, dI_.data(), nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            std::vector<int> cp;
+            if (h->row_band > 0) {      // place of every row in the list (-1: not in it)
+                cp.assign(lp.M, -1);
+                for (int a = 0; a < dim; ++a) cp[red.kept[a]] = a;
+                HIPCHK(hipMemcpyAsync(h->d_cpos, cp.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            }
+            h2d_done(h);      // the host vectors go out of scope
+            dev.schur_rows(h->d_idx, h->d_cpos, dim, P.thp_inv, h->d_diag);
+            break;
+        }
+        case NewtonForm::BandedRow:
+            // full row form, rows in the banded order: S is built entry by entry, factor and substitutions stop at the band
+            hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.M + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, (const double*)P.dS, h->d_diag);
+            dev.schur_banded_dev(h->d_rowpos, M, P.thp_inv, h->d_diag);
+            break;
+        default:      // Row
+            dev.schur_syrk(false, nullptr, M, P.thp_inv, P.dS, f.S, f.ld, Dev::NzFlags::Pattern);
+        }
+        dev.diag_prepare(f, dim, 0, 1e-13, 1e-30);
+        dev.chol(f, dim);
+    }
+    // A form that lost its accuracy (or whose preconditioner needs too many CG steps) is not used again in this LP: the next iteration -
+    // this one again when its step was not applied - takes the next usable form (oracle: IPM.run).  The null-space form first recovers
+    // the equality rows' multipliers.
+    void drop_form(NewtonForm f) {
+        if (f == NewtonForm::NullSpace) ns_finish_y();
+        ip.usable[(int)f] = false;
+    }
+
     int btag = 100;      // alignment tags of a scenario batch grow in program order inside one LP (asm_batch.hip.h)
     int ipm_run(double tol, int max_more) {
-        const int M = (int)lp.M;
         int done = 0;
         // null-space iterations apply their step on the device (k_ns_update_dev) and are checked with the NEXT measures: one read-back per
         // iteration.  ns_pending: the last iteration was one of those and its accuracy check is still owed
@@ -1902,8 +1925,7 @@ struct Solver {
                 if (h->h_scal[SC_NSERR] > h->knobs.ns_rerr) {
                     // the reduced system lost its accuracy and the device left the iterate alone: redo the iteration in row form
                     // (oracle: IPM.run) - measured again below as the row form measures it
-                    ns_finish_y();
-                    ip.ns_off = true;
+                    drop_form(NewtonForm::NullSpace);
                     continue;
                 }
             }
@@ -1914,99 +1936,26 @@ struct Solver {
             }
             if (ip.iters >= 3 && ip.ymax > 1e3 * lp.scale_q) {
                 if (ns_live()) ns_finish_y();
-                down(ip.y, P.y, lp.M);
+                vec y;
+                down(y, P.y, lp.M);
                 HIPCHK(hipStreamSynchronize(h->stream));
-                if (farkas_margin(ip.y) > 1e-9) return ip.status = ASM_INFEASIBLE;
+                if (farkas_margin(y) > 1e-9) return ip.status = ASM_INFEASIBLE;
             }
             if (done >= max_more) { if (ns_live()) ns_finish_y(); return ip.status = ASM_OTHER; }
             // jammed: complementarity collapsed but the primal residual no longer decreases (oracle: IPM.run)
             ip.pinf_hist.push_back(ip.pinf);
             if (ip.iters >= 10 && ip.pinf > JAM_PINF && ip.gap <= 1e-2 * ip.pinf && ip.pinf > 0.5 * ip.pinf_hist[ip.pinf_hist.size() - 4]) {
-                ip.stalled = true;
                 if (ns_live()) ns_finish_y();
                 return ip.status = ASM_OTHER;
             }
-            if (ip.ns_ok && !ip.ns_off)      // null-space form: its theta~ in the same launch (ns_iter_setup)
+            if (ns_live())      // null-space form: its theta~ in the same launch (ns_iter_setup)
                 hipLaunchKernelGGL(k_ipm_theta_ns, dim3(std::max(grid_all(), (unsigned)((std::max<int64_t>(h->ldn, h->ns_nIp) + 255) / 256))), dim3(256), 0, h->stream, P, IPM_RHO_P, nsX(), h->d_nsth, h->ldn,
                                    h->ns_nIp);
             else
                 hipLaunchKernelGGL(k_ipm_theta, dim3(grid_all()), dim3(256), 0, h->stream, P, IPM_RHO_P);
-            // column form (oracle: IPM.run): K = Th + Ah' D^-1 Ah (n x n) while its Sherman-Morrison-Woodbury preconditioner
-            // keeps the CG short, the row form S = Ah Th^-1 Ah' + D (M x M) otherwise
-            use_red = false;
-            use_perm = false;
-            // null-space form (oracle: IPM.run): set up once per LP, k x k factorisation per iteration
-            use_ns = false;
-            if (ip.ns_ok && !ip.ns_off) {
-                use_ns = !ip.ns_off;
-            }
-            use_col = !use_ns && ip.col_ok && !ip.col_off;
-            if (use_ns) {
-                ip.ns_iters += 1;
-                ns_iter_setup();
-            } else if (use_col) {
-                ip.col_iters += 1;
-                hipLaunchKernelGGL(k_ipm_col_prep, dim3(grid_all()), dim3(256), 0, h->stream, P, IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
-                if (h->col_band > 0) {
-                    // columns in their banded order: K built from the structural column pairs, factor and substitutions stop at the band
-                    hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_cth, h->d_diag);
-                    dev.schur_banded_cols_dev(h->d_cdinv, h->d_diag);
-                } else {
-                    dev.syrk_col(h->d_cdinv, h->d_cth);
-                }
-                dev.diag_prepare(h->main_fac, (int)lp.n, 0, 1e-13, 1e-30);
-                dev.chol(h->main_fac, (int)lp.n);
-            } else {
-                // reduced row form (oracle: IPM.run): inequality rows whose slack term dominates their Schur diagonal stay out
-                // of the factor and get a diagonal preconditioner
-                if (ip.red_ok && !ip.red_off) {
-                    dev.schur_diag(P.thp_inv, h->d_sdiag);
-                    down(tmpM, P.dS, lp.M);
-                    down(tmpM2, h->d_sdiag, lp.M);
-                    HIPCHK(hipStreamSynchronize(h->stream));
-                    redE.clear(); redI.clear();
-                    for (int64_t q = 0; q < lp.M; ++q) {                 // kept rows in the order of the factorisations
-                        const int64_t i = h->row_band > 0 ? h->row_perm_h[q] : q;
-                        if (tmpM[i] > RED_TAU * tmpM2[i]) redI.push_back((int)i);
-                        else redE.push_back((int)i);
-                    }
-                    use_red = (double)redI.size() >= RED_MIN_FRAC * (double)lp.M && !redE.empty();
-                }
-                if (use_red) {
-                    ip.red_iters += 1;
-                    nE = (int)redE.size(); nI = (int)redI.size();
-                    vec dE_(nE), dI_(nI);
-                    for (int a = 0; a < nE; ++a) dE_[a] = tmpM[redE[a]];
-                    for (int b = 0; b < nI; ++b) dI_[b] = tmpM2[redI[b]] + tmpM[redI[b]];
-                    HIPCHK(hipMemcpyAsync(h->d_idx, redE.data(), nE * sizeof(int), hipMemcpyHostToDevice, h->stream));
-                    HIPCHK(hipMemcpyAsync(h->d_idxI, redI.data(), nI * sizeof(int), hipMemcpyHostToDevice, h->stream));
-                    HIPCHK(hipMemcpyAsync(h->d_diag, dE_.data(), nE * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                    HIPCHK(hipMemcpyAsync(h->d_rdI, dI_.data(), nI * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                    if (h->row_band > 0) {
-                        std::vector<int> cp(lp.M, -1);
-                        for (int a = 0; a < nE; ++a) cp[redE[a]] = a;
-                        HIPCHK(hipMemcpyAsync(h->d_cpos, cp.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
-                        h2d_done(h);
-                        dev.schur_banded_dev(h->d_cpos, nE, P.thp_inv, h->d_diag);
-                    } else {
-                        h2d_done(h);      // the host vectors go out of scope
-                        dev.syrk_gathered_dev(h->d_idx, nE, P.thp_inv, h->d_diag);
-                    }
-                    dev.diag_prepare(h->main_fac, nE, 0, 1e-13, 1e-30);
-                    dev.chol(h->main_fac, nE);
-                } else if (h->row_band > 0) {
-                    // full row form, rows in the banded order: S is built entry by entry, factor and substitutions stop at the band
-                    use_perm = true;
-                    hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.M + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, (const double*)P.dS, h->d_diag);
-                    dev.schur_banded_dev(h->d_rowpos, M, P.thp_inv, h->d_diag);
-                    dev.diag_prepare(h->main_fac, M, 0, 1e-13, 1e-30);
-                    dev.chol(h->main_fac, M);
-                } else {
-                    dev.syrk_dev(nullptr, M, P.thp_inv, P.dS);
-                    dev.diag_prepare(h->main_fac, M, 0, 1e-13, 1e-30);
-                    dev.chol(h->main_fac, M);
-                }
-            }
+            form = choose_form();
+            newton_factor();
+            const bool ns = form == NewtonForm::NullSpace;
             ip.iters += 1;
             done += 1;
             double ap = 0.0, ad = 0.0;
@@ -2016,11 +1965,11 @@ struct Solver {
             auto solves = [&](const bool deferred) -> bool {
                 cg_max = 0;
                 cg_fail = false;
-                if (use_ns) ns_newton(0, dirA, dirA); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
+                if (ns) ns_newton(0, dirA, dirA); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
                 hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, 0u);
                 hipLaunchKernelGGL(k_ipm_muaff, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, IPM_SIG_EXP);
-                if (use_ns) ns_newton(1, dirA, dirC); else ipm_solve(1, dirA, dirC, 0.0, 0.0, deferred ? 2 : 0);
-                if (use_ns && ns_defer) {       // step lengths stay on the device (k_ns_update_dev below)
+                if (ns) ns_newton(1, dirA, dirC); else ipm_solve(1, dirA, dirC, 0.0, 0.0, deferred ? 2 : 0);
+                if (ns && ns_defer) {       // step lengths stay on the device (k_ns_update_dev below)
                     hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirC, 0u);
                     return true;
                 }
@@ -2030,7 +1979,7 @@ struct Solver {
                 if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
                 ap = h->h_scal[SC_AP]; ad = h->h_scal[SC_AD];
                 // Gondzio multiple centrality correctors (oracle: IPM.run): dirA is free again and receives the candidate
-                for (int kc = 0; kc < (use_ns ? 0 : IPM_MCC); ++kc) {      // (no correctors in null-space form: a Newton solve costs more than the factorisation there)
+                for (int kc = 0; kc < (ns ? 0 : IPM_MCC); ++kc) {      // (no correctors in null-space form: a Newton solve costs more than the factorisation there)
                     if (std::min(ap, ad) >= 0.9) break;
                     const double tp = std::min(1.0, ap + MCC_DELTA), td = std::min(1.0, ad + MCC_DELTA);
                     ipm_solve(2, dirC, dirA, tp, td, deferred ? 2 : 0);
@@ -2046,36 +1995,28 @@ struct Solver {
                 }
                 return true;
             };
-            const bool defer = !use_ns && !use_col && !use_red;      // the factor of S itself is the preconditioner
+            const bool approx = form == NewtonForm::Column || form == NewtonForm::ReducedRow;
+            const bool defer = !ns && !approx;      // the factor of S itself is the preconditioner
             if (!(defer && solves(true))) solves(false);
-            if (use_ns && ns_defer) {
-                const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
+            const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
+            if (ns && ns_defer) {
                 hipLaunchKernelGGL(k_ns_update_dev, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, eta, nsv(14), h->ldn, h->knobs.ns_rerr);
                 ns_pending = true;
                 continue;
             }
             if (h->knobs.verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e  cg steps so far %lld\n", ap, ad, (long long)h->stats_pcg);
-            if (use_ns && h->h_scal[SC_NSERR] > h->knobs.ns_rerr) {
-                ns_finish_y();
-                ip.ns_off = true;          // the reduced system lost its accuracy: redo the iteration in row form (oracle: IPM.run)
+            // the reduced system lost its accuracy, or the preconditioner of the column / reduced row form did: redo the iteration in the
+            // next form (oracle: IPM.run)
+            if (ns ? h->h_scal[SC_NSERR] > h->knobs.ns_rerr : approx && cg_fail) {
+                drop_form(form);
                 continue;
             }
-            if (use_col && cg_fail) {      // column-form preconditioner lost its accuracy: redo this iteration in row form (oracle: IPM.run)
-                ip.col_off = true;
-                continue;
-            }
-            if (use_red && cg_fail) {      // same safety net for the reduced row form
-                ip.red_off = true;
-                continue;
-            }
-            const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
-            if (use_ns)
+            if (ns)
                 hipLaunchKernelGGL(k_ns_update, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), nsv(14),
                                    1.0 - std::min(1.0, eta * ap), h->ldn);
             else
                 hipLaunchKernelGGL(k_ipm_update, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad));
-            if (use_col && cg_max > COL_MAX_CG) ip.col_off = true;
-            if (use_red && cg_max > RED_MAX_CG) ip.red_off = true;
+            if (approx && cg_max > (form == NewtonForm::Column ? COL_MAX_CG : RED_MAX_CG)) drop_form(form);
         }
     }
 
@@ -2206,8 +2147,8 @@ struct Solver {
         }
         if (nH > 0 && nF > 0) {
             if (!(reuse_factor && part_factor)) {
-                if (h->row_band > 0) dev.schur_banded_dev(A.hpos, nH, A.Fmask, nullptr);        // Hidx is in the banded row order (k_as_setup)
-                else dev.syrk_gathered_dev(A.Hidx, nH, A.Fmask, nullptr);
+                h->main_fac.band = h->row_band;
+                dev.schur_rows(A.Hidx, A.hpos, nH, A.Fmask, nullptr);        // (Hidx is in the banded row order when there is one: k_as_setup)
                 dev.diag_prepare(h->main_fac, nH, 1, 0.0, 0.0);
                 dev.chol(h->main_fac, nH, 1e-10);
                 part_factor = false;
@@ -2511,6 +2452,15 @@ struct Solver {
     // oracle: solve_scaled
     double t_warm = 0, t_ipm = 0, t_polish = 0;
     bool snap_e = false;      // the snapshot of the best iterate holds the null-space form's component e
+    void stats_measures() { h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap; }
+    // best-iterate safeguard, second half (oracle: solve_scaled): the snapshot comes back, is measured and its partition identified
+    void restore_best() {
+        hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
+        ipm_measures();
+        stats_measures();
+        h->stats.restored = 1;
+        identify_dev(3);
+    }
     int solve_scaled(const ActiveSet* warm, SolveHint& hint) {
         int st = solve_scaled_impl(warm, hint);
         if (h->knobs.verbose) std::fprintf(stderr, "[asm] phases: warm %.2f ms, ipm %.2f ms (%d its), polish %.2f ms, path %d\n", t_warm, t_ipm, ip.iters, t_polish, h->stats.path);
@@ -2577,12 +2527,12 @@ struct Solver {
             h->stats.ipm_iters = ip.iters;
             h->stats.col_iters = ip.col_iters;
             h->stats.ns_iters = ip.ns_iters;
-            h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap;
+            stats_measures();
             if (st == ASM_INFEASIBLE) { h->stats.path = 6; return ASM_INFEASIBLE; }
             {
                 // best-iterate safeguard, first half (oracle: solve_scaled): the iterate at the end of the best stage so far is kept
                 m_last = std::max(ip.pinf, std::max(ip.dinf, ip.gap));
-                double* e_ns = (ip.ns_ok && ip.ns_e_ready) ? nsv(14) : nullptr;
+                double* e_ns = ip.ns_e_ready ? nsv(14) : nullptr;      // (set only by iterations in null-space form)
                 if (m_last < best_m) {
                     hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, e_ns, h->ldn, h->Mp, h->nsp, 0);
                     best_m = m_last; have_snap = true; snap_e = e_ns != nullptr;
@@ -2633,12 +2583,8 @@ struct Solver {
         if (have_snap && have_sets && m_last > IPM_DEGRADE * best_m) {
             // best-iterate safeguard, second half (oracle: solve_scaled): no stage ended in a successful polish and the last one ended IPM_DEGRADE
             // times worse than the best - the best iterate comes back, the final attempts run on it and on the partition identified from it
-            hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
-            ipm_measures();
+            restore_best();
             if (h->knobs.verbose) std::fprintf(stderr, "[asm] last stage ended %.1e against %.1e at best: best iterate restored (pinf %.3e dinf %.3e gap %.3e)\n", m_last, best_m, ip.pinf, ip.dinf, ip.gap);
-            h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap;
-            h->stats.restored = 1;
-            identify_dev(3);
         }
         if (have_sets) {
             double t1 = now_ms();
@@ -2673,11 +2619,7 @@ struct Solver {
         bool conv = have_sets && ip.pinf <= IPM_ACCEPT && ip.dinf <= IPM_ACCEPT_DUAL && ip.gap <= IPM_ACCEPT;
         if (!conv && have_sets && have_snap && best_m <= IPM_ACCEPT) {
             // ... or the best stage end did (the last iterations drifted out of the acceptance, but by less than IPM_DEGRADE): that iterate then
-            hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
-            ipm_measures();
-            h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap;
-            h->stats.restored = 1;
-            identify_dev(3);
+            restore_best();
             conv = true;
         }
         if (conv) {
