@@ -76,6 +76,8 @@ PROTOTYPES = {
     "asm_eval_functions": (C.c_int, [_P, _D, _D, _D, _D]),
     "asm_eval_constraints": (C.c_int, [_P, _D, _D, _D]),
     "asm_eval_jacobian_values": (C.c_int, [_P, _D]),
+    "asm_eval_set_data": (C.c_int, [_P, C.c_int64, C.c_int64, _D]),
+    "asm_eval_data_gradient": (C.c_int, [_P, _D, _D, _D]),
     "asm_slp_norms": (C.c_int, [_P, _D, _D, _D, _D]),
     "asm_slp_merit": (C.c_int, [_P, C.c_int, C.c_double, _D, _D, _D, C.c_int, C.c_double, _D]),
     "asm_slp_line_search": (C.c_int, [_P, _D, _D, _D, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _D, _D,
@@ -95,6 +97,8 @@ PROTOTYPES = {
     "asm_batch_eval_setup": (C.c_int, [_P, C.c_int64, _I64, _I64, _D, _I64, _I64, _I64, _D, _D, _I64, _I64, _I64, _D, _I64, C.c_double, C.c_int,
                                        C.c_int64, C.c_int64, _I64, C.c_int64, _D, C.c_int64]),
     "asm_batch_set_ns_basis": (C.c_int, [_P, _I32, C.c_int64]),
+    "asm_batch_set_scenario_data": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _D]),
+    "asm_batch_data_gradient": (C.c_int, [_P, C.c_int64, _D, _D, _D]),
     "asm_batch_ns_basis": (C.c_int, [_P, _I32, _I64]),
     "asm_batch_sublp_solve": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _I32, _D, _D, _D, _D, _D, _I32]),
     "asm_batch_slp_run": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), _D, _D, _D, _D, _D, C.POINTER(SlpResult)]),

@@ -318,16 +318,21 @@ class AcopfModel:
         return v
 
 
-def function_model(case, nlp="acopf_ohm"):
+def function_model(case, nlp="acopf_ohm", branch_params=False):
     """The same polar ACOPF as a FunctionModel (moi_evaluator.py), i.e. the way the reference receives it: affine and quadratic
     scalar functions in the wrapper's six lists (angle differences linear <= / >=; reference angle, dc-line loss and the nodal
     balances of buses without shunt linear ==; thermal limits quadratic <=; balances of buses with a shunt quadratic ==) and
     Ohm's law as the NLP block (src/MOI_wrapper.jl:683-689).  Rows and pattern come out in the wrapper's order, which is a
     permutation of `AcopfModel`'s; the NLP block carries the parameters of its device kernel (csrc/asm_eval_kernels.hip.h).
     nlp="acopf_ohm": the hand-written Ohm's-law kernel; nlp="expr": the same rows as expressions (nlexpr.ExprBlock) - each row's
-    pattern is then its distinct variables in ascending order, the same entries as the kernel's in another order."""
+    pattern is then its distinct variables in ascending order, the same entries as the kernel's in another order.
+    branch_params=True (nlp="expr"): the Ohm's-law coefficients are parameters (nlexpr.parameters) at dpar[0:8 n_branch], in the layout of
+    the kernel's dpar (k_ff_p, k_ff_q, k_tt_p, k_tt_q, a_f, b_f, a_t, b_t): every case with the same branches (line_scenario_case) gives
+    the same tape, the scenarios differ in dpar only."""
     if nlp not in ("acopf_ohm", "expr"):
         raise ValueError("nlp must be 'acopf_ohm' or 'expr', not %r" % (nlp,))
+    if branch_params and nlp != "expr":
+        raise ValueError("branch_params needs nlp='expr' (the Ohm's-law kernel's coefficients are its dpar already)")
     from .moi_evaluator import FunctionModel, ScalarFunction, NlpBlock
     mdl = AcopfModel(case)
     c = case
@@ -368,7 +373,7 @@ def function_model(case, nlp="acopf_ohm"):
     nl = mdl.nl
     fm.acopf_model = mdl
     if nlp == "expr":
-        fm.nlp = _ohm_expr_block(mdl)
+        fm.nlp = _ohm_expr_block(mdl, branch_params)
         return fm
     # ---- NLP block: Ohm's law, rows pfr | qfr | pto | qto, pattern in 4 groups x 5 sub-blocks of n_branch
     rows, cols = [], []
@@ -396,24 +401,31 @@ def function_model(case, nlp="acopf_ohm"):
     return fm
 
 
-def _ohm_expr_block(mdl):
-    """Ohm's law (rows pfr | qfr | pto | qto, `AcopfModel._flows`) as expressions: x[p / q flow] - flow(vm_f, vm_t, va_f - va_t)."""
-    from .nlexpr import ExprBlock, var, sin, cos
+def _ohm_expr_block(mdl, branch_params=False):
+    """Ohm's law (rows pfr | qfr | pto | qto, `AcopfModel._flows`) as expressions: x[p / q flow] - flow(vm_f, vm_t, va_f - va_t).
+    branch_params: the 8 coefficients of every branch are parameters, coefficient array by coefficient array (the kernel's dpar layout)."""
+    from .nlexpr import ExprBlock, var, sin, cos, parameters
     c = mdl.c
     f, t = c["f_bus"], c["t_bus"]
+    nl = mdl.nl
+    coef = (mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q, mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t)
+    par = parameters(np.concatenate(coef)) if branch_params else []
     rows = [[], [], [], []]
     for l in range(mdl.nl):
         vf, vt = var(mdl.vm[f[l]]), var(mdl.vm[t[l]])
         d = var(mdl.va[f[l]]) - var(mdl.va[t[l]])
         cs, sn = cos(d), sin(d)
         vv = vf * vt
-        kffp, kffq, kttp, kttq = (float(a[l]) for a in (mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q))
-        af, bf, at, bt = (float(a[l]) for a in (mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t))
+        if branch_params:
+            kffp, kffq, kttp, kttq, af, bf, at, bt = (par[q * nl + l] for q in range(8))
+        else:
+            kffp, kffq, kttp, kttq = (float(a[l]) for a in coef[:4])
+            af, bf, at, bt = (float(a[l]) for a in coef[4:])
         rows[0].append(var(mdl.pf[l]) - (kffp * vf * vf + af * vv * cs + bf * vv * sn))
         rows[1].append(var(mdl.qf[l]) - (kffq * vf * vf - bf * vv * cs + af * vv * sn))
         rows[2].append(var(mdl.pt[l]) - (kttp * vt * vt + at * vv * cs - bt * vv * sn))
         rows[3].append(var(mdl.qt[l]) - (kttq * vt * vt - bt * vv * cs - at * vv * sn))
-    return ExprBlock([(e, 0.0, 0.0) for grp in rows for e in grp], n=mdl.n)
+    return ExprBlock([(e, 0.0, 0.0) for grp in rows for e in grp], n=mdl.n, parameters=par)
 
 
 def acopf_problem(case, name="acopf"):
@@ -440,4 +452,15 @@ def scenario_case(base, scenario, lo=0.9, hi=1.1):
     f = lo + (hi - lo) * uniform01(1000 + int(scenario), base["n_bus"])
     c["pd"] = base["pd"] * f
     c["qd"] = base["qd"] * f
+    return c
+
+
+def line_scenario_case(base, scenario, lo=0.95, hi=1.05):
+    """Line-parameter scenario `scenario`: the series impedance r + jx of every branch of `base` scaled by an independent U(lo, hi)
+    factor (its admittance g + jb divided by it), seeded as `scenario_case`.  Same buses and branches, so the same pattern: with
+    function_model(..., nlp="expr", branch_params=True) or the Ohm's-law kernel the scenarios differ in the NLP block's data only."""
+    c = dict(base)
+    k = lo + (hi - lo) * uniform01(1000 + int(scenario), len(base["f_bus"]))
+    c["g"] = base["g"] / k
+    c["b"] = base["b"] / k
     return c

@@ -107,7 +107,7 @@ class NativeRun:
 class HipBatch:
     """`n_slots` sub-problem handles with one LP skeleton and one evaluator on one device, advanced in lockstep (asm_batch_*).
     `problem`: a Problem built from a FunctionModel (its pattern, functions and NLP block are shared by every scenario; scenarios differ in
-    bounds and start points)."""
+    bounds and start points, and through a scenario data table in the NLP block's data: slp_run(..., data=...))."""
 
     def __init__(self, problem, n_slots, device=0, groups=None):
         import ctypes as C
@@ -139,6 +139,8 @@ class HipBatch:
             _, ipar, dpar = fm.nlp.device
             rows, nnz = fm.nlp.m, len(fm.nlp.rows)
             ipar, dpar = np.ascontiguousarray(ipar, np.int64), np.ascontiguousarray(dpar, np.float64)
+        self.nlp_kind, self._ipar, self._dpar = kind, ipar, dpar
+        self.n_dpar = len(dpar) if kind else 0
         a = lambda k: fl[k]
         self._check(self._lib.asm_batch_eval_setup(self._b, fl["n_rows"], _lib.i64ptr(a("aff_ptr")), _lib.i64ptr(a("aff_var")), _lib.dptr(a("aff_coef")),
                                                    _lib.i64ptr(a("quad_ptr")), _lib.i64ptr(a("q_v1")), _lib.i64ptr(a("q_v2")), _lib.dptr(a("q_coef")),
@@ -180,9 +182,40 @@ class HipBatch:
         self._check(self._lib.asm_batch_get_stats(self._b, self._C.byref(s)))
         return {k: getattr(s, k) for k, _ in s._fields_}
 
-    def slp_run(self, g_L, g_U, x_L, x_U, x0, parameters, max_lp_solves=0):
+    def set_scenario_data(self, data, offset=0):
+        """The scenario data table (asm_batch_set_scenario_data): row s of `data` [n_scen x count] is written to dpar[offset, offset + count)
+        of the slot that takes scenario s; None clears it (every scenario then starts from the setup data)."""
+        from . import _lib
+        if data is None:
+            self._check(self._lib.asm_batch_set_scenario_data(self._b, 0, 0, 0, None))
+            return
+        t = np.ascontiguousarray(np.atleast_2d(data), np.float64)
+        self._check(self._lib.asm_batch_set_scenario_data(self._b, t.shape[0], int(offset), t.shape[1], _lib.dptr(t)))
+
+    def scenario_data(self, problems):
+        """The per-scenario data table of `problems` for this batch: None when every NLP block carries the batch's own data, else their dpar
+        stacked (offset 0).  A problem whose NLP block differs in kind or pattern (ipar) cannot share the batch's evaluator: ValueError."""
+        if not self.nlp_kind:
+            return None
+        rows, differ = [], False
+        from .moi_evaluator import nlp_kind
+        for pr in problems:
+            fm = getattr(pr, "function_model", None)
+            if fm is None or fm.nlp is None or fm.nlp.device is None:
+                raise ValueError("problem %r has no NLP block for the batch's evaluator" % (getattr(pr, "name", pr),))
+            _, ipar, dpar = fm.nlp.device
+            ipar, dpar = np.asarray(ipar, np.int64), np.asarray(dpar, np.float64)
+            if nlp_kind(fm.nlp.device) != self.nlp_kind or not np.array_equal(ipar, self._ipar) or len(dpar) != self.n_dpar:
+                raise ValueError("problem %r: its NLP block differs from the batch's in kind or pattern - only its data (dpar) may differ"
+                                 % (getattr(pr, "name", pr),))
+            differ = differ or not np.array_equal(dpar.view(np.int64), self._dpar.view(np.int64))
+            rows.append(dpar)
+        return np.stack(rows) if differ else None
+
+    def slp_run(self, g_L, g_U, x_L, x_U, x0, parameters, max_lp_solves=0, data=None, data_offset=0):
         """Complete SLP runs (`parameters.algorithm`: Line Search or Trust Region) of `len(g_L)` scenarios (rows of the 2-D arrays): list of
-        NativeRun in scenario order."""
+        NativeRun in scenario order.  `data` [n_scen x count]: scenario s solves with dpar[data_offset, data_offset + count) = data[s]
+        (the table stays set for data_gradient); None: every scenario with the setup data."""
         from . import _lib
         f64 = lambda a_: np.ascontiguousarray(a_, np.float64)
         g_L, g_U, x_L, x_U, x0 = map(f64, (g_L, g_U, x_L, x_U, x0))
@@ -190,6 +223,10 @@ class HipBatch:
         assert g_L.shape == (S, self.m) and g_U.shape == (S, self.m) and x_L.shape == (S, self.n) and x_U.shape == (S, self.n) and x0.shape == (S, self.n)
         if parameters.algorithm not in ("Line Search", "Trust Region"):
             raise ValueError("the native drivers restate run!(::SlpLS) and run!(::SlpTR) only, not %r" % parameters.algorithm)
+        if data is not None and np.atleast_2d(data).shape[0] != S:
+            raise ValueError("the data table has %d rows for %d scenarios" % (np.atleast_2d(data).shape[0], S))
+        if data is not None or self.nlp_kind:
+            self.set_scenario_data(data, data_offset)
         par = slp_params(parameters, max_lp_solves)
         x = np.empty((S, self.n)); lam = np.empty((S, max(self.m, 1))); mU = np.empty((S, self.n)); mL = np.empty((S, self.n)); g = np.empty((S, max(self.m, 1)))
         res = (_lib.SlpResult * S)()
@@ -202,6 +239,17 @@ class HipBatch:
             tr = [None] * S
             self._check(self._lib.asm_batch_slp_run(self._b, S, *bounds, *outs))
         return [NativeRun(res[s], x[s], lam[s, :self.m], mU[s], mL[s], g[s, :self.m], tr[s]) for s in range(S)]
+
+    def data_gradient(self, x, lam):
+        """asm_batch_data_gradient: d(f - lam' g) / d dpar per scenario (rows of x [n_scen x n], lam [n_scen x m]), each scenario with its
+        data (the table of the last slp_run, else the setup data); [n_scen x n_dpar]."""
+        from . import _lib
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float64)
+        S = x.shape[0]
+        lam = np.ascontiguousarray(np.reshape(lam, (S, self.m)) if self.m else np.zeros((S, 1)), np.float64)
+        out = np.empty((S, max(self.n_dpar, 1)))
+        self._check(self._lib.asm_batch_data_gradient(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(out)))
+        return out[:, :self.n_dpar]
 
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.
@@ -239,9 +287,10 @@ def solve_batch_lockstep(problems, parameters, n_slots, device=0, rank=0, world=
     own = batch is None
     if own:
         batch = HipBatch(problems[0], min(int(n_slots), len(problems)), device)
+    data = batch.scenario_data(problems)          # NLP blocks with other data (line parameters, ...): per scenario through the table
     t0 = time.perf_counter()
     runs = batch.slp_run(np.stack([p.g_L for p in problems]), np.stack([p.g_U for p in problems]), np.stack([p.x_L for p in problems]),
-                         np.stack([p.x_U for p in problems]), np.stack([p.x0 for p in problems]), parameters)
+                         np.stack([p.x_U for p in problems]), np.stack([p.x0 for p in problems]), parameters, data=data)
     st = local_stats(runs, time.perf_counter() - t0)
     bst = batch.stats()
     if own:
@@ -286,7 +335,7 @@ def solve_batch_dynamic(problem_of, total, parameters, n_slots, batch, chunk=Non
     for lo, hi in claim_chunks(total, chunk, store):
         prs = [problem_of(s) for s in range(lo, hi)]
         runs = batch.slp_run(np.stack([p.g_L for p in prs]), np.stack([p.g_U for p in prs]), np.stack([p.x_L for p in prs]),
-                             np.stack([p.x_U for p in prs]), np.stack([p.x0 for p in prs]), parameters)
+                             np.stack([p.x_U for p in prs]), np.stack([p.x0 for p in prs]), parameters, data=batch.scenario_data(prs))
         mine.update({lo + k: r for k, r in enumerate(runs)})
     st = local_stats(list(mine.values()), time.perf_counter() - t0)
     return mine, reduce_stats(st, reduce_device)

@@ -168,7 +168,8 @@ __global__ __launch_bounds__(256) void k_nlp_dense_quadratic(AsmBt abt, const do
 
 // ---- NLP block 3: expression tape (include/asm_hip.h, "Expression block").  Rows 0..R-1 are constraint rows, R..R+T-1 objective terms.
 // Set up by asm_eval_setup: node references a / b made absolute (index into the whole tape), VAR nodes of a row carry the offset of
-// their Jacobian value from j0 in `slot`, VAR nodes of a term the position of their adjoint in the per-variable gradient list.
+// their Jacobian value from j0 in `slot`, VAR nodes of a term the position of their adjoint in the per-variable gradient list, CONST nodes
+// their place in the per-dpar occurrence list of the data gradient.
 // The node values live in HBM (val: 8 trial points x L) - a runtime-indexed per-thread array would spill to scratch; adj: L adjoints
 // (one point: the Jacobian and the gradient are only formed at the iterate).
 struct ExprTape {
@@ -243,10 +244,13 @@ __device__ __forceinline__ double expr_forward(const ExprTape& X, int64_t k0, in
     }
     return v;
 }
-// reverse sweep over nodes [k0, k1) (values from the forward sweep in val): adjoints into adj, the adjoint of every VAR node k to
-// out[X.slot[k]] - added to it (ACC: constraint rows, several VAR nodes may share a Jacobian value) or stored (term occurrences)
-template <bool ACC>
-__device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int64_t k1, const double* val, double* adj, double* out) {
+// what a reverse sweep writes: EXPR_JAC the adjoint of every VAR node added to out[slot] (constraint rows, several VAR nodes may share a
+// Jacobian value); EXPR_GRAD the adjoint of every VAR node stored to out[slot] (term occurrences); EXPR_DATA wt * the adjoint of every CONST
+// node stored to out[slot] (data-gradient occurrences), nothing for the VAR nodes
+enum { EXPR_JAC = 0, EXPR_GRAD = 1, EXPR_DATA = 2 };
+// reverse sweep over nodes [k0, k1) (values from the forward sweep in val): adjoints into adj, the node adjoints MODE names to out
+template <int MODE>
+__device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int64_t k1, const double* val, double* adj, double* out, double wt = 0.0) {
 #pragma clang fp contract(off)
     for (int64_t k = k0; k < k1 - 1; ++k) adj[k] = 0.0;
     adj[k1 - 1] = 1.0;
@@ -254,10 +258,12 @@ __device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int6
         const double w = adj[k];
         const int64_t a = X.a[k], b = X.b[k];
         switch (X.op[k]) {
-            case ASM_OP_CONST: break;
+            case ASM_OP_CONST:
+                if constexpr (MODE == EXPR_DATA) out[X.slot[k]] = wt * w;
+                break;
             case ASM_OP_VAR:
-                if (ACC) out[X.slot[k]] = out[X.slot[k]] + w;
-                else out[X.slot[k]] = w;
+                if constexpr (MODE == EXPR_JAC) out[X.slot[k]] = out[X.slot[k]] + w;
+                else if constexpr (MODE == EXPR_GRAD) out[X.slot[k]] = w;
                 break;
             case ASM_OP_ADD: adj[a] = adj[a] + w; adj[b] = adj[b] + w; break;
             case ASM_OP_SUB: adj[a] = adj[a] + w; adj[b] = adj[b] - w; break;
@@ -314,7 +320,7 @@ __global__ __launch_bounds__(256) void k_nlp_expr_rows(AsmBt abt, ExprTape X, co
     if (!write_jac || blockIdx.y) return;
     double* o = dE + j0;
     for (int64_t j = X.jptr[r]; j < X.jptr[r + 1]; ++j) o[j] = 0.0;
-    expr_reverse<true>(X, k0, k1, val, X.adj, o);
+    expr_reverse<EXPR_JAC>(X, k0, k1, val, X.adj, o);
 }
 // objective terms: one thread per term; its value to tval[trial * T + term], with write_grad (one point) its VAR-node adjoints to gocc
 __global__ __launch_bounds__(256) void k_nlp_expr_terms(AsmBt abt, ExprTape X, const double* __restrict__ x, int write_grad, int64_t ldx) {
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(256) void k_nlp_expr_terms(AsmBt abt, ExprTape X, c
     const int64_t k0 = X.ptr[X.R + t], k1 = X.ptr[X.R + t + 1];
     X.tval[blockIdx.y * X.T + t] = expr_forward(X, k0, k1, x, val);
     if (!write_grad || blockIdx.y) return;
-    expr_reverse<false>(X, k0, k1, val, X.adj, X.gocc);
+    expr_reverse<EXPR_GRAD>(X, k0, k1, val, X.adj, X.gocc);
 }
 // the objective: one thread sums the term values in term order and applies the sense scale (as k_fn_objective); blockIdx.x = trial point
 __global__ __launch_bounds__(64) void k_nlp_expr_objective(AsmBt abt, ExprTape X, double scale, double* __restrict__ f_out) {
@@ -348,6 +354,29 @@ __global__ __launch_bounds__(256) void k_nlp_expr_gradient(AsmBt abt, ExprTape X
     double g = 0.0;
     for (int64_t o = X.gptr[j]; o < X.gptr[j + 1]; ++o) g = g + X.gocc[o];
     df[j] = g * scale;
+}
+// ---- data gradient of the Lagrangian (asm_eval_data_gradient): out[c] = d f / d dpar[c] - sum_r lam_r d g_r / d dpar[c].  The CONST nodes
+// are grouped by dpar index in cptr [n_dpar+1]; a CONST node's `slot` is its place in that list (node order inside a group), cocc the list.
+// Step 1: one thread per row (t < R) or term: forward sweep at x, reverse sweep with unit seed, and every CONST adjoint times the row's
+// weight -lam[t] (lam: the multipliers of the block's rows) or the objective's sense scale into cocc.  No Jacobian or gradient output.
+__global__ __launch_bounds__(256) void k_nlp_expr_const_adj(AsmBt abt, ExprTape X, const double* __restrict__ x, const double* __restrict__ lam, double scale, double* __restrict__ cocc) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, x, lam, scale, cocc);
+    const int64_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= X.R + X.T) return;
+    const int64_t k0 = X.ptr[t], k1 = X.ptr[t + 1];
+    (void)expr_forward(X, k0, k1, x, X.val);
+    expr_reverse<EXPR_DATA>(X, k0, k1, X.val, X.adj, cocc, t < X.R ? -lam[t] : scale);
+}
+// Step 2: one thread per dpar index sums its weighted occurrences in list order from 0.0 (fixed order, no atomics: the host twin's sum)
+__global__ __launch_bounds__(256) void k_nlp_expr_data_gather(AsmBt abt, const int64_t* __restrict__ cptr, const double* __restrict__ cocc, int64_t n_dpar, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, cptr, cocc, n_dpar, out);
+    const int64_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_dpar) return;
+    double g = 0.0;
+    for (int64_t o = cptr[c]; o < cptr[c + 1]; ++o) g = g + cocc[o];
+    out[c] = g;
 }
 
 __global__ __launch_bounds__(256) void k_axpy_out(AsmBt abt, const double* __restrict__ x, double alpha, const double* __restrict__ p, double* __restrict__ out, int64_t n) {

@@ -392,6 +392,11 @@ struct asm_handle {
     int64_t* d_ev_ipar = nullptr;
     double *d_ev_dpar = nullptr, *d_ev_x = nullptr, *d_ev_xt = nullptr, *d_ev_df = nullptr, *d_ev_E = nullptr, *d_ev_Et = nullptr, *d_ev_f = nullptr;
     double *d_ev_vecs = nullptr, *h_ev = nullptr;     // reduction inputs (lambda, multipliers, nu, slacks, p, bounds) / pinned staging
+    // NLP-block data (dpar): its length, and the range [dirty_lo, dirty_hi) asm_eval_set_data has written since asm_eval_setup (empty: the
+    // device holds the setup values); expression tapes with constants: the data-gradient occurrence list (asm_eval_data_gradient)
+    int64_t ev_n_dpar = 0, ev_dirty_lo = 0, ev_dirty_hi = 0;
+    int64_t* d_ev_cptr = nullptr;
+    double *d_ev_cocc = nullptr, *d_ev_lam = nullptr, *d_ev_dgrad = nullptr, *h_ev_dgrad = nullptr;
     bool J_valid = false;                               // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
     double* h_scal = nullptr;       // pinned scalar read-back; host-mapped: the reduction kernels store the block there themselves (scal_publish)
@@ -3483,7 +3488,7 @@ namespace {
 // the slots of the VAR nodes (rows: Jacobian value from j0; terms: position in the per-variable gradient list)
 struct ExprHost {
     int64_t R = 0, T = 0, L = 0;
-    std::vector<int64_t> ptr, jptr, a, b, slot, gptr;
+    std::vector<int64_t> ptr, jptr, a, b, slot, gptr, cptr;   // cptr [n_dpar+1]: the CONST nodes grouped by dpar index (empty: no CONST node)
     std::vector<int32_t> op;
 };
 void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_nnz, int64_t nlp_rows, int64_t nlp_nnz, const int64_t* ip, int64_t n_ipar,
@@ -3555,6 +3560,17 @@ void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_
     std::vector<int64_t> fill(xh.gptr.begin(), xh.gptr.end() - 1);
     for (int64_t k = ptr[R]; k < L; ++k)
         if (op[k] == ASM_OP_VAR) xh.slot[k] = fill[a[k]]++;
+    // data gradient: the CONST nodes of rows and terms grouped by dpar index, in node order inside each group
+    int64_t n_const = 0;
+    for (int64_t k = 0; k < L; ++k) n_const += op[k] == ASM_OP_CONST;
+    if (n_const == 0) return;
+    xh.cptr.assign(n_dpar + 1, 0);
+    for (int64_t k = 0; k < L; ++k)
+        if (op[k] == ASM_OP_CONST) ++xh.cptr[a[k] + 1];
+    for (int64_t c = 0; c < n_dpar; ++c) xh.cptr[c + 1] += xh.cptr[c];
+    std::vector<int64_t> cfill(xh.cptr.begin(), xh.cptr.end() - 1);
+    for (int64_t k = 0; k < L; ++k)
+        if (op[k] == ASM_OP_CONST) xh.slot[k] = cfill[a[k]]++;
 }
 }  // namespace
 
@@ -3586,6 +3602,7 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     h->ev_nlp_kind = nlp_kind; h->ev_nlp_rows = nlp_rows; h->ev_nlp_nnz = nlp_nnz; h->ev_fn_nnz = fn_nnz;
     P.upload(h->d_ev_ipar, nlp_ipar, n_ipar);
     P.upload(h->d_ev_dpar, nlp_dpar, n_dpar);
+    h->ev_n_dpar = n_dpar; h->ev_dirty_lo = h->ev_dirty_hi = 0;
     P.alloc(h->d_ev_x, 0);
     const int64_t n = h->n, m = std::max<int64_t>(h->m, 1);
     P.zeroed(h->d_ev_x, n); P.zeroed(h->d_ev_xt, 8 * round_up(n, 32)); P.zeroed(h->d_ev_df, n); P.zeroed(h->d_ev_E, m);
@@ -3602,6 +3619,11 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
         // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
         P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
         P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[h->n]);
+        if (!xh.cptr.empty()) {     // the data gradient's occurrence list, multipliers of the rows and result (tapes with constants only)
+            P.upload(h->d_ev_cptr, xh.cptr.data(), n_dpar + 1);
+            P.zeroed(h->d_ev_cocc, xh.cptr[n_dpar]); P.zeroed(h->d_ev_lam, xh.R); P.zeroed(h->d_ev_dgrad, n_dpar);
+            P.alloc(h->h_ev_dgrad, n_dpar, BufPool::PINNED);
+        }
     }
     // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
     P.zeroed(h->d_ev_vecs, 2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
@@ -3650,6 +3672,47 @@ int asm_eval_functions(asm_handle* h, const double* x, double* f, double* df, do
     return guarded(h, [&] { do_eval_functions(h, x, f, df, E); });
 }
 
+// dpar[offset, offset + count) := values on the device: every later evaluation reads it, nothing else changes
+static void do_set_data(asm_handle* h, int64_t offset, int64_t count, const double* values) {
+    if (!h->ev_ready) throw std::logic_error("asm_eval_set_data: asm_eval_setup first");
+    if (!values || offset < 0 || count < 0 || offset > h->ev_n_dpar - count)
+        throw std::invalid_argument("asm_eval_set_data: null pointer or a range outside [0, n_dpar = " + std::to_string(h->ev_n_dpar) + ")");
+    if (count == 0) return;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_ev_dpar + offset, values, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h2d_done(h);
+    if (h->ev_dirty_hi == h->ev_dirty_lo) { h->ev_dirty_lo = offset; h->ev_dirty_hi = offset + count; }
+    else { h->ev_dirty_lo = std::min(h->ev_dirty_lo, offset); h->ev_dirty_hi = std::max(h->ev_dirty_hi, offset + count); }
+}
+
+// out[c] = d(f - lambda' g) / d dpar[c] at x for an expression block (k_nlp_expr_const_adj + k_nlp_expr_data_gather); the inputs of the next
+// LP are not touched (x goes where asm_eval_constraints puts its trial point)
+static void do_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
+    if (!h->ev_ready) throw std::logic_error("asm_eval_data_gradient: asm_eval_setup first");
+    if (h->ev_nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument("asm_eval_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
+    if (!x || (h->m > 0 && !lambda) || (h->ev_n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
+    const int64_t n = h->n, nd = h->ev_n_dpar;
+    if (!h->d_ev_cocc) {            // no CONST node: nothing depends on the data
+        for (int64_t c = 0; c < nd; ++c) out[c] = 0.0;
+        return;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    const ExprTape& X = h->ev_X;
+    std::memcpy(h->h_ev, x, n * sizeof(double));
+    HIPCHK(hipMemcpyAsync(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (X.R > 0) {
+        std::memcpy(h->h_ev + n, lambda + h->ev_F.n_rows, X.R * sizeof(double));
+        HIPCHK(hipMemcpyAsync(h->d_ev_lam, h->h_ev + n, X.R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(k_nlp_expr_const_adj, dim3((unsigned)((X.R + X.T + 255) / 256)), dim3(256), 0, h->stream, X, (const double*)h->d_ev_xt,
+                       (const double*)h->d_ev_lam, h->ev_F.objective_scale, h->d_ev_cocc);
+    hipLaunchKernelGGL(k_nlp_expr_data_gather, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->stream, (const int64_t*)h->d_ev_cptr,
+                       (const double*)h->d_ev_cocc, nd, h->d_ev_dgrad);
+    HIPCHK(hipMemcpyAsync(h->h_ev_dgrad, h->d_ev_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::memcpy(out, h->h_ev_dgrad, nd * sizeof(double));
+}
+
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
 static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
     if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
@@ -3678,6 +3741,14 @@ int asm_eval_jacobian_values(asm_handle* h, double* dE_out) {
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipMemcpy(dE_out, h->d_dE, h->nnz * sizeof(double), hipMemcpyDeviceToHost));
     });
+}
+
+int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double* values) {
+    return guarded(h, [&] { do_set_data(h, offset, count, values); });
+}
+
+int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
+    return guarded(h, [&] { do_data_gradient(h, x, lambda, out); });
 }
 
 // --------------------------------------------------------------------------------- per-iteration reductions on the device (row f1)
@@ -4373,6 +4444,9 @@ struct asm_batch {
     std::vector<BatchGroup*> groups;
     std::string err;
     std::vector<int> J_ref;         // basis columns of the null-space form every scenario starts from (first cold selection of the batch)
+    std::vector<double> dpar0;      // the NLP-block data of asm_batch_eval_setup (what a scenario start restores)
+    std::vector<double> scen_tab;   // per-scenario data [scen_n x scen_cnt] for dpar[scen_off, scen_off + scen_cnt) (scen_cnt = 0: none)
+    int64_t scen_n = 0, scen_off = 0, scen_cnt = 0;
     bool setup_done = false;
     asm_batch_stats stats;
     bool verbose = false;           // ASM_BATCH_VERBOSE=1: per-kernel merge statistics of every group at release
@@ -4418,6 +4492,22 @@ void run_fibers(asm_batch* b, int count, const char* step, W&& work) {
     }
     for (BatchGroup* g : b->groups)
         if (g->err) { std::exception_ptr e = g->err; g->err = nullptr; std::rethrow_exception(e); }
+}
+// scenario sc's NLP-block data on slot handle h before its start: row sc of the scenario table, or the setup values.  What the slot's
+// earlier work wrote outside the range about to be written is restored first, so a result never depends on what the slot solved before.
+void batch_scenario_data(asm_batch* b, asm_handle* h, int64_t sc) {
+    const int64_t lo = h->ev_dirty_lo, hi = h->ev_dirty_hi;
+    const bool covered = b->scen_cnt > 0 && lo >= b->scen_off && hi <= b->scen_off + b->scen_cnt;
+    if (hi > lo && !covered) {
+        do_set_data(h, lo, hi - lo, b->dpar0.data() + lo);
+        h->ev_dirty_lo = h->ev_dirty_hi = 0;
+    }
+    if (b->scen_cnt > 0) do_set_data(h, b->scen_off, b->scen_cnt, b->scen_tab.data() + sc * b->scen_cnt);
+}
+// a batch call over n_scen scenarios with a scenario table of another height
+void check_scen(const asm_batch* b, int64_t n_scen, const char* what) {
+    if (b->scen_cnt > 0 && n_scen != b->scen_n)
+        throw std::invalid_argument(std::string(what) + ": " + std::to_string(n_scen) + " scenarios, the scenario data table has " + std::to_string(b->scen_n));
 }
 void batch_free_groups(asm_batch* b) {
     for (BatchGroup* g : b->groups) {
@@ -4555,6 +4645,26 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
                 do_eval_setup(b->slots[s], n_rows, aff_ptr, aff_var, aff_coef, quad_ptr, q_v1, q_v2, q_coef, constant, jac_off, g_ptr, g_kind, g_coef, g_other,
                               objective_scale, nlp_kind, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, nlp_dpar, n_dpar);
             });
+        if (n_dpar > 0) b->dpar0.assign(nlp_dpar, nlp_dpar + n_dpar);
+        else b->dpar0.clear();
+        b->scen_tab.clear();
+        b->scen_n = b->scen_off = b->scen_cnt = 0;
+    });
+}
+
+int asm_batch_set_scenario_data(asm_batch* b, int64_t n_scen, int64_t offset, int64_t count, const double* table) {
+    return guarded(b, [&] {
+        if (!b->setup_done || !b->slots[0]->ev_ready) throw std::logic_error("asm_batch_set_scenario_data: asm_batch_eval_setup first");
+        if (count == 0) {
+            b->scen_tab.clear();
+            b->scen_n = b->scen_off = b->scen_cnt = 0;
+            return;
+        }
+        const int64_t nd = (int64_t)b->dpar0.size();
+        if (!table || n_scen < 1 || count < 0 || offset < 0 || offset > nd - count)
+            throw std::invalid_argument("asm_batch_set_scenario_data: null table, no scenario or a range outside [0, n_dpar = " + std::to_string(nd) + ")");
+        b->scen_tab.assign(table, table + n_scen * count);
+        b->scen_n = n_scen; b->scen_off = offset; b->scen_cnt = count;
     });
 }
 
@@ -4577,10 +4687,12 @@ int asm_batch_sublp_solve(asm_batch* b, int count, const double* c_lb, const dou
             throw std::invalid_argument("asm_batch_sublp_solve: bad count or null pointer");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nnz = b->slots[0]->nnz;
         if (m > 0 && (!E || !lambda || !p_slack)) throw std::invalid_argument("asm_batch_sublp_solve: null pointer");
+        check_scen(b, count, "asm_batch_sublp_solve");
         HIPCHK(hipSetDevice(b->device));
         run_fibers(b, count, "asm_sublp_solve", [&](int s) {
             asm_handle* h = b->slots[s];
             if (c_lb && c_ub && v_lb && v_ub) do_set_bounds(h, c_lb + s * m, c_ub + s * m, v_lb + s * n, v_ub + s * n);
+            if (h->ev_ready) batch_scenario_data(b, h, s);
             asmb::next_cycle();
             do_upload(h, dE + s * nnz, df + s * n, f[s], E ? E + s * m : nullptr, x_k + s * n);
             do_solve(h, delta[s], feasibility[s], p + s * n, lambda ? lambda + s * m : nullptr, mult_x_U + s * n, mult_x_L + s * n,
@@ -4605,6 +4717,7 @@ void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double
         asm_handle* h0 = b->slots[0];
         in_slot(step, 0, [&] {
             do_set_bounds(h0, c_lb, c_ub, v_lb, v_ub);
+            batch_scenario_data(b, h0, 0);
             h0->hint[0].ns_J.clear();
             vec xs(n), dfs(n), Es(std::max<int64_t>(m, 1)), pp(n), ll(std::max<int64_t>(m, 1)), uu(n), lo(n), sl(2 * std::max<int64_t>(m, 1));
             clamp_start(n, x0, v_lb, v_ub, xs.data());
@@ -4623,6 +4736,7 @@ void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double
             const int64_t sc = next.fetch_add(1);
             if (sc >= n_scen) break;
             do_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n);
+            batch_scenario_data(b, h, sc);
             // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
             if (!b->J_ref.empty()) h->hint[0].ns_J = b->J_ref;
             else h->hint[0].ns_J.clear();
@@ -4641,6 +4755,7 @@ int asm_batch_slp_run(asm_batch* b, int64_t n_scen, const double* c_lb, const do
     return guarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_slp_run: asm_batch_setup first");
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run: bad argument");
+        check_scen(b, n_scen, "asm_batch_slp_run");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
         batch_slp_runs(b, "asm_slp_run", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_ls(h, par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
@@ -4657,10 +4772,35 @@ int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const
         if (!b->setup_done) throw std::logic_error("asm_batch_slp_run_tr: asm_batch_setup first");
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run_tr: bad argument");
         check_tr_size(tr_size, "asm_batch_slp_run_tr");
+        check_scen(b, n_scen, "asm_batch_slp_run_tr");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
         batch_slp_runs(b, "asm_slp_run_tr", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_tr(h, par, tr_size, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
                        mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc, tr ? tr + sc : nullptr);
+        });
+    });
+}
+
+// asm_eval_data_gradient of n_scen scenarios (each with its data, as asm_batch_slp_run gives it), the slots taking them in index order
+int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, double* out) {
+    return guarded(b, [&] {
+        if (!b->setup_done || !b->slots[0]->ev_ready) throw std::logic_error("asm_batch_data_gradient: asm_batch_eval_setup first");
+        if (b->slots[0]->ev_nlp_kind != ASM_NLP_EXPR)
+            throw std::invalid_argument("asm_batch_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
+        const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nd = (int64_t)b->dpar0.size();
+        if (n_scen < 1 || !x || (m > 0 && !lambda) || (nd > 0 && !out)) throw std::invalid_argument("asm_batch_data_gradient: bad argument");
+        check_scen(b, n_scen, "asm_batch_data_gradient");
+        HIPCHK(hipSetDevice(b->device));
+        std::atomic<int64_t> next{0};
+        run_fibers(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), "asm_eval_data_gradient", [&](int s) {
+            asm_handle* h = b->slots[s];
+            for (;;) {
+                const int64_t sc = next.fetch_add(1);
+                if (sc >= n_scen) break;
+                batch_scenario_data(b, h, sc);
+                asmb::next_cycle();
+                do_data_gradient(h, x + sc * n, m > 0 ? lambda + sc * m : nullptr, out + sc * nd);
+            }
         });
     });
 }

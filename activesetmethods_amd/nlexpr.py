@@ -15,6 +15,11 @@ node and row): with + - * / unary -, **, abs, minimum and maximum only, host and
 
 The objective, when given, is split into terms along its left spine of additions (((t1 + t2) + t3) -> [t1, t2, t3]) and summed
 in term order from 0.0; it replaces the FunctionModel's own objective (`has_objective`, MOI_wrapper.jl:809-861).
+
+Parameters (JuMP-style, for scenario and sensitivity studies): p = parameters([1.0, 2.0]) gives nodes that act as constants whose
+values change without a new tape.  ExprBlock(..., parameters=p) puts them at dpar[0:P] in declaration order, never merged with
+constants or with each other; set_parameter_values / asm_eval_set_data change them, data_gradient / asm_eval_data_gradient give the
+derivative of the Lagrangian with respect to every dpar entry (at an SLP solution: the derivative of the optimal value).
 """
 import numbers
 import struct
@@ -68,6 +73,19 @@ class Expr:
 
     def __repr__(self):
         return "Expr(op=%d, arg=%r, %d args)" % (self.op, self.arg, len(self.args))
+
+
+class Parameter(Expr):
+    """A parameter node: a CONST whose dpar slot belongs to it alone (ExprBlock(..., parameters=...) places it)."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "Parameter(%r)" % (self.arg,)
+
+
+def parameters(values):
+    """One parameter node per value, in order (their dpar slots are fixed by the ExprBlock that declares them)."""
+    return [Parameter(CONST, arg=float(v)) for v in np.atleast_1d(np.asarray(values, np.float64))]
 
 
 def _wrap(v):
@@ -144,11 +162,14 @@ def _split_terms(e):
 # ---------------------------------------------------------------------------------------------------- tape
 class Tape:
     """Rows (constraint rows, then objective terms) as flat arrays: ptr [R+T+1], op / a / b [L] with row-local references, the
-    constants in `dpar` (one entry per distinct value)."""
+    constants in `dpar`: the parameters first (one entry each, in declaration order), then one entry per distinct constant value."""
 
-    def __init__(self, rows, n_constraint_rows):
+    def __init__(self, rows, n_constraint_rows, params=()):
         self.R, self.T = n_constraint_rows, len(rows) - n_constraint_rows
-        self.consts, cidx = [], {}
+        self.consts, cidx = [float(p.arg) for p in params], {}
+        pidx = {id(p): i for i, p in enumerate(params)}
+        if len(pidx) != len(self.consts):
+            raise ValueError("a parameter is declared twice")
         ptr, op, a, b = [0], [], [], []
         for root in rows:
             memo, vidx = {}, {}
@@ -164,7 +185,11 @@ class Tape:
                             stack.append((c, False))
                     continue
                 k = len(op) - ptr[-1]
-                if e.op == CONST:
+                if isinstance(e, Parameter):
+                    if id(e) not in pidx:
+                        raise ValueError("an expression uses a parameter the block does not declare (ExprBlock(..., parameters=...))")
+                    op.append(CONST); a.append(pidx[id(e)]); b.append(0)
+                elif e.op == CONST:
                     key = struct.pack("<d", e.arg)
                     if key not in cidx:
                         cidx[key] = len(self.consts)
@@ -291,8 +316,10 @@ class _Sweep:
                     V[r, k] = v
         return V, V[np.arange(self.nr), self.last]
 
-    def reverse(self, V, out, accumulate):
-        """Adjoints from the last node of every row back; VAR-node adjoints added to (or stored into) out[slot]."""
+    def reverse(self, V, out, accumulate, weight=None):
+        """Adjoints from the last node of every row back; VAR-node adjoints added to (or stored into) out[slot].  With `weight`
+        (one per row; the data gradient, expr_reverse<EXPR_DATA>): weight[row] * the adjoint of every CONST node stored into
+        out[slot], nothing for the VAR nodes."""
         W = np.zeros_like(V)
         W[np.arange(self.nr), self.last] = 1.0
         with np.errstate(all="ignore"):
@@ -300,9 +327,12 @@ class _Sweep:
                 for o, r, a, b, slot in self.steps[k]:
                     w = W[r, k]
                     if o == CONST:
+                        if weight is not None:
+                            out[slot] = weight[r] * w
                         continue
                     if o == VAR:
-                        out[slot] = out[slot] + w if accumulate else w
+                        if weight is None:
+                            out[slot] = out[slot] + w if accumulate else w
                     elif o == ADD:
                         W[r, a] = W[r, a] + w
                         W[r, b] = W[r, b] + w
@@ -384,13 +414,17 @@ class _Sweep:
 
 class ExprBlock(NlpBlock):
     """An NLP block of expressions: `constraints` = [(expr, lo, hi)] (lo == hi: equality; +-inf: one-sided), `objective` = an
-    expression or None.  Rows of the Jacobian pattern: each row's distinct variables in ascending order (1-based block rows and
-    columns, as NlpBlock)."""
+    expression or None, `parameters` = the parameter nodes (nlexpr.parameters) the expressions use, at dpar[0:P] in this order.
+    Rows of the Jacobian pattern: each row's distinct variables in ascending order (1-based block rows and columns, as NlpBlock)."""
 
-    def __init__(self, constraints=(), objective=None, n=None):
+    def __init__(self, constraints=(), objective=None, n=None, parameters=()):
         cons = [(_wrap(e), float(lo), float(hi)) for e, lo, hi in constraints]
         terms = _split_terms(_wrap(objective)) if objective is not None else []
-        tape = Tape([e for e, _, _ in cons] + terms, len(cons))
+        params = list(parameters)
+        if not all(isinstance(p, Parameter) for p in params):
+            raise TypeError("parameters must be nodes made by nlexpr.parameters")
+        tape = Tape([e for e, _, _ in cons] + terms, len(cons), params)
+        self.n_params = len(params)
         self.tape = tape
         R, T = tape.R, tape.T
         ptr, op, a = tape.ptr, tape.op, tape.a
@@ -412,6 +446,10 @@ class ExprBlock(NlpBlock):
         order = np.lexsort((kv, a[kv]))                    # by variable, then (term, node) = node order
         slot[kv[order]] = np.arange(len(kv))
         self.g_ptr = np.concatenate([[0], np.cumsum(np.bincount(a[kv], minlength=n_var))]).astype(np.int64)
+        # data gradient: the CONST nodes grouped by dpar index, node order inside a group (the cptr / slot of asm_eval_setup)
+        kc = np.nonzero(op == CONST)[0]
+        slot[kc[np.argsort(a[kc], kind="stable")]] = np.arange(len(kc))
+        self.c_ptr = np.concatenate([[0], np.cumsum(np.bincount(a[kc], minlength=len(tape.consts)))]).astype(np.int64)
         self.n_var = n_var
         self._consts = tape.dpar()
         self._rows = _Sweep(ptr[:R + 1], op, tape.a, tape.b, slot)
@@ -420,6 +458,38 @@ class ExprBlock(NlpBlock):
         super().__init__([lo for _, lo, _ in cons], [hi for _, _, hi in cons], rows, cols, self._eval_g, self._eval_jac_g,
                          device=("expr", tape.ipar(), self._consts),
                          has_objective=T > 0, eval_f=self._eval_f if T > 0 else None, eval_grad_f=self._eval_grad_f if T > 0 else None)
+
+    # ---- parameters
+    def set_parameter_values(self, values):
+        """New values of the P parameters (declaration order): the host callbacks and the `device` tuple use them from now on."""
+        v = np.asarray(values, np.float64).ravel()
+        if len(v) != self.n_params:
+            raise ValueError("%d parameter values for %d parameters" % (len(v), self.n_params))
+        consts = self._consts.copy()
+        consts[:self.n_params] = v
+        self._consts = consts
+        self.device = ("expr", self.device[1], consts)
+
+    def data_gradient(self, x, lam, scale=1.0):
+        """Host twin of asm_eval_data_gradient: d(scale * f - lam' g) / d dpar[c] for every dpar entry c, with `lam` the multipliers
+        of the block's rows and `scale` the objective's sense scale.  The occurrences of every constant - (-lam[r]) * adjoint in a row
+        r, scale * adjoint in a term - are summed from 0.0 in (row, then term; node) order, as k_nlp_expr_data_gather does."""
+        x = np.asarray(x, float)
+        lam = np.asarray(lam, float)
+        R = self.tape.R
+        cocc = np.zeros(int(self.c_ptr[-1]))
+        if R:
+            V, _ = self._rows.forward(x, self._consts)
+            self._rows.reverse(V, cocc, False, weight=-lam[:R])
+        if self.tape.T:
+            V, _ = self._terms.forward(x, self._consts)
+            self._terms.reverse(V, cocc, False, weight=np.full(self.tape.T, float(scale)))
+        cnt = np.diff(self.c_ptr)
+        g = np.zeros(len(cnt))
+        for i in range(int(cnt.max()) if len(cnt) else 0):
+            s = cnt > i
+            g[s] = g[s] + cocc[self.c_ptr[:-1][s] + i]
+        return g
 
     # ---- host callbacks (the twins of k_nlp_expr_rows / _terms / _objective / _gradient)
     def _eval_g(self, x, out):

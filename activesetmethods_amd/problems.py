@@ -185,3 +185,25 @@ def hs071_function_model():
 
 def hs071_problem():
     return hs071_function_model().to_problem("hs071")
+
+
+def parametric_function_model(a=0.5, p=4.0):
+    """A parameterised model with a known solution (nlexpr.parameters at dpar[0] = a, dpar[1] = p):
+        min a x1^2 + x2^2 + x1   s.t.  x1 x2 - p >= 0,  x2 - x1 >= 0,  0.5 <= xi <= 10,  start (3, 3).
+    For 0 < a < 1 and sqrt(p) (1 - a) > 1/2 both rows are active at the optimum x1 = x2 = sqrt(p) (a vertex, which an SLP reaches in a
+    few steps) with multipliers (a + 1 + 1 / (2 sqrt(p)), sqrt(p) (1 - a) - 1/2); the optimal value V = (a + 1) p + sqrt(p) has
+    dV/da = p and dV/dp = a + 1 + 1 / (2 sqrt(p)) - what the data gradient of the Lagrangian gives at the solution."""
+    from .moi_evaluator import FunctionModel
+    from .nlexpr import ExprBlock, parameters, variables
+    x1, x2 = variables(2)
+    pa, pp = parameters([a, p])
+    fm = FunctionModel(2, np.full(2, 0.5), np.full(2, 10.0))
+    fm.start = {1: 3.0, 2: 3.0}
+    fm.nlp = ExprBlock([(x1 * x2 - pp, 0.0, INF), (x2 - x1, 0.0, INF)], objective=pa * x1 ** 2 + x2 ** 2 + x1, n=2, parameters=[pa, pp])
+    return fm
+
+
+def parametric_solution(a=0.5, p=4.0):
+    """(x*, V, dV/d(a, p)) of parametric_function_model."""
+    s = float(np.sqrt(p))
+    return np.array([s, s]), (a + 1.0) * p + s, np.array([p, a + 1.0 + 0.5 / s])

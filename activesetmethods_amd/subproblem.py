@@ -239,6 +239,21 @@ class HipSubOptimizer:
         self._check(self._lib.asm_eval_jacobian_values(self._h, _lib.dptr(dE)))
         return dE[:len(self.j_row)]
 
+    def set_eval_data(self, values, offset=0):
+        """Overwrite dpar[offset, offset + len(values)) of the NLP block on the device (asm_eval_set_data): the next evaluations
+        use the new data; pattern, bounds and the retained LP state stay."""
+        v = _f64(np.atleast_1d(values))
+        self._check(self._lib.asm_eval_set_data(self._h, int(offset), len(v), _lib.dptr(v)))
+
+    def eval_data_gradient(self, x, lam):
+        """d(f - lam' g) / d dpar at x (asm_eval_data_gradient; expression blocks only), lam [m] in the sign convention of
+        slp_run's multipliers: at an SLP solution, the derivative of the optimal value with respect to each dpar entry."""
+        x, lam = _f64(x), _f64(np.atleast_1d(lam) if self.m else np.zeros(1))
+        nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
+        out = np.empty(max(nd, 1))
+        self._check(self._lib.asm_eval_data_gradient(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(out)))
+        return out[:nd]
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)

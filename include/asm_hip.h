@@ -239,6 +239,26 @@ int asm_eval_constraints(asm_handle* h, const double* x, double* f, double* E);
 /* copy of the dE buffer (tests). */
 int asm_eval_jacobian_values(asm_handle* h, double* dE_out);
 
+/* ---- NLP-block data: parameters of scenario and sensitivity studies ----------------------------------------------------------------
+ * The data of the NLP block is its dpar as given to asm_eval_setup: kind 1 the 8 Ohm's-law coefficient arrays, kind 2 A then Q, kind 3
+ * the tape constants (a binding that owns parameter slots - nlexpr.py puts them at dpar[0, P) - writes their values here).  The pattern
+ * (ipar, j_str) never changes.
+ * asm_eval_set_data: dpar[offset, offset + count) := values on the device, without a new asm_eval_setup.  ASM_ERR_STATE before
+ * asm_eval_setup, ASM_ERR_ARG for a null pointer or a range outside [0, n_dpar).  No LP state changes (bounds, retained basis, hints);
+ * every later evaluation (asm_eval_functions, asm_eval_constraints, the merit and line-search entries, asm_slp_run(_tr)) is bit-identical
+ * to that of a handle set up from scratch with the changed dpar. */
+int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double* values);
+/* The data gradient of the Lagrangian at (x, lambda), expression blocks only (other kinds: ASM_ERR_ARG):
+ *   out[c] = d f / d dpar[c] - sum_i lambda_i d g_i / d dpar[c]      c < n_dpar
+ * f the objective as asm_eval_functions returns it (sense scale included), g the block's rows, lambda [m] in the sign convention of
+ * asm_slp_run (KT residual df - J'lambda - mult_x_U - mult_x_L): at an SLP solution out is dV/d dpar, V the optimal value (envelope
+ * theorem).  The inputs of the next LP are not touched (as asm_eval_constraints).
+ * Order: per node of a row or term a reverse sweep from a unit seed at x (the derivative formulas above); the adjoint w of every CONST node
+ * becomes one occurrence: (-lambda_r) * w for a node of block row r (problem row n_rows + r), objective_scale * w for a node of a term;
+ * out[c] sums the occurrences of dpar index c from 0.0 in (row, then term; node) order - rows before terms, nodes ascending.  Device and
+ * host twin (nlexpr.py: ExprBlock.data_gradient) agree bit for bit with ADD..POWI, ABS, MIN and MAX only, else in the last bits. */
+int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out);
+
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
 int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4);
@@ -320,6 +340,14 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
                          const int64_t* g_ptr, const int64_t* g_kind, const double* g_coef, const int64_t* g_other,
                          double objective_scale, int nlp_kind, int64_t nlp_rows, int64_t nlp_nnz,
                          const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar);
+/* Per-scenario NLP-block data: table [n_scen x count] for dpar[offset, offset + count) (count = 0 clears it; the other arguments are then
+ * ignored).  In asm_batch_slp_run(_tr), asm_batch_sublp_solve and asm_batch_data_gradient a slot that takes scenario s writes row s into its
+ * evaluator's data (asm_eval_set_data) next to its bounds; without a table each scenario start restores the data of asm_batch_eval_setup,
+ * so results never depend on what a slot solved before.  The reference basis-column LP on slot 0 uses scenario 0's data.  The table stays
+ * set until it is cleared or asm_batch_eval_setup is called again; a batch call over another number of scenarios is ASM_ERR_ARG. */
+int asm_batch_set_scenario_data(asm_batch* b, int64_t n_scen, int64_t offset, int64_t count, const double* table);
+/* asm_eval_data_gradient of n_scen scenarios, each with its data: x [n_scen x n], lambda [n_scen x m], out [n_scen x n_dpar] */
+int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, double* out);
 /* basis columns every scenario of asm_batch_slp_run starts from (default: selected by one LP of scenario 0 on slot 0) */
 int asm_batch_set_ns_basis(asm_batch* b, const int32_t* J, int64_t k);
 int asm_batch_ns_basis(const asm_batch* b, int32_t* J, int64_t* k);
