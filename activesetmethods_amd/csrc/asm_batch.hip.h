@@ -2,11 +2,14 @@
 // optimizer and no batching (src/MOI_wrapper.jl:1093-1152), so this is the build's own design for BASELINE.json's scenario batch.
 //
 // B scenarios are solved by B *fibers* (user-level contexts) of ONE host thread.  Each fiber runs the ordinary single-scenario solver
-// code on its own handle; what changes is what a launch does:
-//   * outside a fiber     hipLaunchKernelGGL / hipMemcpyAsync / ... go to the stream as before (bt.tab = nullptr);
+// code on its own handle.  That code makes every stream operation through the functions at the end of this header:
+//   asmb::launch / launch_resident(kernel, grid, block, stream, args...)      asmb::blocks(n, per) - the 1-D grid of ceil(n / per)
+//   asmb::copy_async / fill_async(..., stream)      asmb::copy / fill(...)      asmb::sync(stream)      asmb::free(p)
+// and what such a call does depends on where it is made:
+//   * outside a fiber     it is the plain stream operation (kernel launch with bt.tab = nullptr, copy, fill, synchronise, free);
 //   * inside a fiber      the operation is RECORDED (kernel, grid, packed arguments; copies become copy-kernel operations whose
 //                         payload travels in the round's blob), and the fiber yields when it needs a result on the host
-//                         (hipStreamSynchronize, read-backs) or reaches an alignment point (barrier).
+//                         (sync, copy, fill, free, read-backs) or reaches an alignment point (barrier).
 // When every fiber is blocked the scheduler MERGES the recorded lists position by position: operations of different fibers that are
 // the same kernel with the same grid become one launch with the scenario index in gridDim.z and an argument table in HBM (one H2D
 // copy of all tables + payloads per round), on one stream; a completion word in host-mapped memory ends the round.  Scenarios that
@@ -31,7 +34,7 @@
 
 #include "asm_bt.hip.h"
 
-// copy / fill operations of recorded streams (every hipMemcpyAsync / hipMemsetAsync inside a fiber becomes one of these)
+// copy / fill operations of recorded streams (every asmb::copy_async / asmb::fill_async inside a fiber becomes one of these)
 __global__ __launch_bounds__(256) void k_bcopy(AsmBt bt, char* dst, const char* src, int64_t bytes) {
     ASM_BARGS(bt, dst, src, bytes);
     const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
@@ -173,7 +176,7 @@ struct Sched {
     void reserve_blob(size_t need) {
         if (need <= blob_cap) return;
         if (h_blob) (void)hipHostFree(h_blob);
-        if (d_blob) (void)hipFree(d_blob);
+        if (d_blob) (void)::hipFree(d_blob);
         blob_cap = std::max<size_t>(need * 2, (size_t)4 << 20);
         chk(hipHostMalloc((void**)&h_blob, blob_cap), "hipHostMalloc(blob)");
         chk(hipMalloc((void**)&d_blob, blob_cap), "hipMalloc(blob)");
@@ -211,7 +214,7 @@ struct Sched {
         }
         fibers.clear();
         if (h_blob) (void)hipHostFree(h_blob);
-        if (d_blob) (void)hipFree(d_blob);
+        if (d_blob) (void)::hipFree(d_blob);
         if (h_out) (void)hipHostFree(h_out);
         if (h_sig) (void)hipHostFree(h_sig);
         h_blob = d_blob = h_out = d_out = nullptr;
@@ -323,7 +326,7 @@ struct Sched {
             }
         }
         // ---- one copy of the blob, then the launches, then the completion word
-        if (bo > 0) chk(hipMemcpyAsync(d_blob, h_blob, bo, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(blob)");
+        if (bo > 0) chk(::hipMemcpyAsync(d_blob, h_blob, bo, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(blob)");
         for (const Launch& L : launches) {
             const Op& X = *L.op;
             AsmBt bt{(const void*)(d_blob + L.tab), X.arg_size, X.gz};
@@ -360,7 +363,7 @@ struct Sched {
             if (__atomic_load_n(h_sig, __ATOMIC_ACQUIRE) == round) return;
             __builtin_ia32_pause();
             if ((spins & 0xfffff) == 0 && now_ms() - t0 > 60000.0) {
-                chk(hipStreamSynchronize(stream), "hipStreamSynchronize");      // a device fault surfaces here
+                chk(::hipStreamSynchronize(stream), "hipStreamSynchronize");      // a device fault surfaces here
                 if (__atomic_load_n(h_sig, __ATOMIC_ACQUIRE) == round) return;
                 throw BatchError("batch round: the stream finished without its completion word");
             }
@@ -458,31 +461,37 @@ inline Op& record(Fiber* f, void (*kern)(AsmBt, KA...), dim3 g, dim3 b, unsigned
     return f->ops.back();
 }
 
+// the grid of a one-dimensional launch: ceil(n / per) workgroups (n == 0 gives the zero grid that launch skips)
+inline dim3 blocks(int64_t n, int64_t per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+
+// kernel launch (no dynamic shared memory); the arguments are converted to the kernel's own parameter types.  A grid with a zero
+// dimension launches nothing
 template <class... KA, class... A>
-inline void launch(void (*kern)(AsmBt, KA...), dim3 g, dim3 b, unsigned sh, hipStream_t st, A&&... a) {
+inline void launch(void (*kern)(AsmBt, KA...), dim3 g, dim3 b, hipStream_t st, A&&... a) {
     static_assert(sizeof...(KA) == sizeof...(A), "kernel launch: argument count does not match the kernel's parameter list");
     if (g.x == 0 || g.y == 0 || g.z == 0) return;
     Fiber* f = cur;
     if (!f) {
-        kern<<<g, b, sh, st>>>(AsmBt{nullptr, 0, g.z}, conv<KA>(a)...);
+        kern<<<g, b, 0, st>>>(AsmBt{nullptr, 0, g.z}, conv<KA>(a)...);
         return;
     }
-    record<KA...>(f, kern, g, b, sh, 0u, conv<KA>(a)...);
+    record<KA...>(f, kern, g, b, 0u, 0u, conv<KA>(a)...);
 }
+// launch whose workgroups must all be resident at once (OP_RESIDENT): the merge keeps the joint grid inside Sched::panel_wgs
 template <class... KA, class... A>
-inline void launch_resident(void (*kern)(AsmBt, KA...), dim3 g, dim3 b, unsigned sh, hipStream_t st, A&&... a) {
+inline void launch_resident(void (*kern)(AsmBt, KA...), dim3 g, dim3 b, hipStream_t st, A&&... a) {
     static_assert(sizeof...(KA) == sizeof...(A), "kernel launch: argument count does not match the kernel's parameter list");
     Fiber* f = cur;
     if (!f) {
-        kern<<<g, b, sh, st>>>(AsmBt{nullptr, 0, g.z}, conv<KA>(a)...);
+        kern<<<g, b, 0, st>>>(AsmBt{nullptr, 0, g.z}, conv<KA>(a)...);
         return;
     }
-    record<KA...>(f, kern, g, b, sh, (unsigned)OP_RESIDENT, conv<KA>(a)...);
+    record<KA...>(f, kern, g, b, 0u, (unsigned)OP_RESIDENT, conv<KA>(a)...);
 }
 
 inline unsigned copy_grid(size_t bytes) { return (unsigned)std::min<size_t>(64, std::max<size_t>(1, (bytes + 16383) / 16384)); }
 
-inline hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
+inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
     Fiber* f = cur;
     if (!f) {
         // outside a batch: device-to-device copies of the solver's vectors (4 - 150 KB, ~60 per LP) as a copy kernel of this library - the
@@ -512,7 +521,7 @@ inline hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemc
     }
     return hipSuccess;
 }
-inline hipError_t memset_async(void* dst, int value, size_t bytes, hipStream_t st) {
+inline hipError_t fill_async(void* dst, int value, size_t bytes, hipStream_t st) {
     Fiber* f = cur;
     if (!f) {
         if (bytes > 0 && bytes <= ((size_t)64 << 20)) {
@@ -525,38 +534,30 @@ inline hipError_t memset_async(void* dst, int value, size_t bytes, hipStream_t s
     record<char*, int, int64_t>(f, k_bfill, dim3(copy_grid(bytes)), dim3(256), 0, 0u, (char*)dst, value, (int64_t)bytes);
     return hipSuccess;
 }
-inline hipError_t stream_synchronize(hipStream_t st) {
+// the host waits for the stream; inside a fiber: for everything the fiber has recorded
+inline hipError_t sync(hipStream_t st) {
     if (!cur) return ::hipStreamSynchronize(st);
     flush_wait();
     return hipSuccess;
 }
-inline hipError_t memcpy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+// synchronous copy / fill / free
+inline hipError_t copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     Fiber* f = cur;
     if (!f) return ::hipMemcpy(dst, src, bytes, kind);
-    hipError_t e = memcpy_async(dst, src, bytes, kind, nullptr);
+    hipError_t e = copy_async(dst, src, bytes, kind, nullptr);
     flush_wait();
     return e;
 }
-inline hipError_t memset_sync(void* dst, int value, size_t bytes) {
+inline hipError_t fill(void* dst, int value, size_t bytes) {
     Fiber* f = cur;
     if (!f) return ::hipMemset(dst, value, bytes);
-    hipError_t e = memset_async(dst, value, bytes, nullptr);
+    hipError_t e = fill_async(dst, value, bytes, nullptr);
     flush_wait();
     return e;
 }
-inline hipError_t free_sync(void* p) {
+inline hipError_t free(void* p) {
     if (cur) flush_wait();      // recorded operations may still use the buffer
     return ::hipFree(p);
 }
 
 }  // namespace asmb
-
-// From here on the solver code's stream operations go through the recorder (a no-op layer outside a fiber)
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) ::asmb::launch(kernel, grid, block, (unsigned)(shmem), stream, ##__VA_ARGS__)
-#define hipMemcpyAsync(...) ::asmb::memcpy_async(__VA_ARGS__)
-#define hipMemsetAsync(...) ::asmb::memset_async(__VA_ARGS__)
-#define hipStreamSynchronize(...) ::asmb::stream_synchronize(__VA_ARGS__)
-#define hipMemcpy(...) ::asmb::memcpy_sync(__VA_ARGS__)
-#define hipMemset(...) ::asmb::memset_sync(__VA_ARGS__)
-#define hipFree(...) ::asmb::free_sync(__VA_ARGS__)

@@ -3,9 +3,10 @@
 // partition identification -> active-set Schur/Cholesky polish) is specified in DESIGN.md; reference
 // citations for the formulation are given at each step (file:line under the reference tree).
 //
-// Round-1 split of work: every O(M*n) and O(M^3) operation (assembly, scaling, Ah x, Ah' y, the Schur
-// SYRK, the Cholesky factorisation and the triangular solves) runs on the GPU; the O(M+n) vector
-// algebra between them runs on the host and exchanges vectors through pinned staging buffers.
+// Split of work: the LP solve runs on the GPU from assembly to the polish, vector algebra included; the
+// host chooses the path, launches, and reads back a few scalars per iteration to decide the next step.
+// Stream operations of the solver go through asmb:: (asm_batch.hip.h): plain stream operations for a
+// single handle, recorded and merged across scenarios inside a scenario batch.
 #include "asm_kernels.hip.h"
 #include "asm_ipm_kernels.hip.h"
 #include "asm_as_kernels.hip.h"
@@ -223,29 +224,29 @@ class BufPool {
         if (dev) HIPCHK(hipHostGetDevicePointer((void**)dev, p, 0));
         return f;
     }
-    // device buffer cleared by hipMemsetAsync on `s`, or by a synchronous hipMemset without a stream
+    // device buffer cleared by asmb::fill_async on `s`, or by the synchronous asmb::fill without a stream
     template <class T>
     T* zeroed(T*& f, int64_t count, hipStream_t s) {
-        HIPCHK(hipMemsetAsync((void*)alloc(f, count), 0, std::max<int64_t>(count, 1) * sizeof(T), s));
+        HIPCHK(asmb::fill_async((void*)alloc(f, count), 0, std::max<int64_t>(count, 1) * sizeof(T), s));
         return f;
     }
     template <class T>
     T* zeroed(T*& f, int64_t count) {
-        HIPCHK(hipMemset((void*)alloc(f, count), 0, std::max<int64_t>(count, 1) * sizeof(T)));
+        HIPCHK(asmb::fill((void*)alloc(f, count), 0, std::max<int64_t>(count, 1) * sizeof(T)));
         return f;
     }
-    // device buffer holding src[0, count) (synchronous copy); zero_first: cleared by a synchronous hipMemset before
+    // device buffer holding src[0, count) (synchronous copy); zero_first: cleared by a synchronous fill before
     template <class T>
     T* upload(T*& f, const std::remove_const_t<T>* src, int64_t count, bool zero_first = false) {
         if (zero_first) zeroed(f, count);
         else alloc(f, count);
-        if (count > 0) HIPCHK(hipMemcpy((void*)f, src, count * sizeof(T), hipMemcpyHostToDevice));
+        if (count > 0) HIPCHK(asmb::copy((void*)f, src, count * sizeof(T), hipMemcpyHostToDevice));
         return f;
     }
     void release() {
         for (const Buf& b : own_) {
             if (b.host) (void)hipHostFree(b.p);
-            else (void)hipFree(b.p);
+            else (void)asmb::free(b.p);
             *b.field = nullptr;
             if (b.dev) *b.dev = nullptr;
         }
@@ -266,7 +267,7 @@ class BufPool {
 struct HandleKnobs {
     int timing = 1;                 // ASM_HIP_TIMING: 0, 1 or 2, the initial asm_handle::timing
     bool verbose = false;           // ASM_HIP_VERBOSE=1: solver diagnostics on stderr
-    bool spin_read = true;          // ASM_HIP_SPIN=0: hipMemcpyAsync + hipStreamSynchronize instead (14.5 us per read-back instead of 6.7 us)
+    bool spin_read = true;          // ASM_HIP_SPIN=0: asmb::copy_async + asmb::sync instead (14.5 us per read-back instead of 6.7 us)
     int panel_wgs = 0;              // ASM_PANEL_WGS: grid bound of the panel kernels on the whole device (0: by the device's CU count)
     bool ns_defer = true;           // ASM_NS_DEFER=0: the step of a null-space iteration is taken on the host
     double ns_rerr = NS_RERR;       // ASM_NS_RERR: accuracy bound of the reduced solves of a null-space iteration (test knob - a tiny bound
@@ -442,7 +443,7 @@ namespace {
 // after host -> device copies whose source must stay untouched until they have run: in a scenario batch the payload was copied when the
 // operation was recorded, nothing to wait for
 inline void h2d_done(asm_handle* h) {
-    if (!asmb::in_fiber()) HIPCHK(hipStreamSynchronize(h->stream));
+    if (!asmb::in_fiber()) HIPCHK(asmb::sync(h->stream));
 }
 
 // buffers of one Cholesky factor of order <= N (pitch = N rounded up to 32) with the block inverses of the substitution kernels, from `pool`
@@ -499,8 +500,8 @@ struct Dev {
     }
     void resolve_timing() {
         if (h->regions.empty()) return;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream2));
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::sync(h->stream2));
         for (auto& r : h->regions) {
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
@@ -515,13 +516,13 @@ struct Dev {
         double* st = h->h_pin;
         std::memcpy(st, src, cnt * sizeof(double));
         for (int64_t i = cnt; i < padded; ++i) st[i] = 0.0;
-        HIPCHK(hipMemcpyAsync(dst, st, padded * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(dst, st, padded * sizeof(double), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);   // staging buffer is reused by the next call
     }
     void d2h(double* dst, const double* src, int64_t cnt) {
         double* st = h->h_pin + h->pin_len;
-        HIPCHK(hipMemcpyAsync(st, src, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::copy_async(st, src, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         std::memcpy(dst, st, cnt * sizeof(double));
     }
 
@@ -535,7 +536,7 @@ struct Dev {
         else if (A == h->d_J) { v = h->d_spv_J; valid = &h->spv_J_valid; }
         else return nullptr;
         if (!*valid) {
-            hipLaunchKernelGGL(k_sp_gather, dim3((unsigned)((h->sp_nnz + 255) / 256)), dim3(256), 0, h->stream, A, h->d_sp_off, v, h->sp_nnz);
+            asmb::launch(k_sp_gather, asmb::blocks(h->sp_nnz), dim3(256), h->stream, A, h->d_sp_off, v, h->sp_nnz);
             *valid = true;
         }
         return v;
@@ -544,23 +545,22 @@ struct Dev {
         if (h->M == 0) return;                         // LP without rows
         if (const double* v = sparse_vals(A)) {
             int id = begin(ASM_K_GEMV, 2.0 * h->sp_nnz, 20.0 * h->sp_nnz + 12.0 * h->M);
-            hipLaunchKernelGGL(k_spmv_n, dim3((unsigned)((h->M + 255) / 256)), dim3(256), 0, h->stream, h->d_sp_ptr, h->d_sp_col, v, x, out, h->M);
+            asmb::launch(k_spmv_n, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, v, x, out, h->M);
             end(id);
             return;
         }
         int id = begin(ASM_K_GEMV, 2.0 * h->M * h->n, 8.0 * h->M * h->ldn);
-        hipLaunchKernelGGL(k_gemv_n, dim3((unsigned)((h->M + 3) / 4)), dim3(256), 0, h->stream, A, h->ldn, x, out, h->M, h->ldn);
+        asmb::launch(k_gemv_n, asmb::blocks(h->M, 4), dim3(256), h->stream, A, h->ldn, x, out, h->M, h->ldn);
         end(id);
     }
     void launch_gemv_t(const double* A, const double* y, double* out) {
         if (h->M == 0) {                               // LP without rows: A'y = 0
-            HIPCHK(hipMemsetAsync(out, 0, h->ldn * sizeof(double), h->stream));
+            HIPCHK(asmb::fill_async(out, 0, h->ldn * sizeof(double), h->stream));
             return;
         }
         if (const double* v = sparse_vals(A)) {
             int id = begin(ASM_K_GEMV, 2.0 * h->sp_nnz, 24.0 * h->sp_nnz + 12.0 * h->n);
-            hipLaunchKernelGGL(k_spmv_t, dim3((unsigned)((h->ldn * 8 + 255) / 256)), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, v,
-                               y, out, h->n, h->ldn);
+            asmb::launch(k_spmv_t, asmb::blocks(h->ldn * 8), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, v, y, out, h->n, h->ldn);
             end(id);
             return;
         }
@@ -568,12 +568,12 @@ struct Dev {
             // dense LP matrix of moderate size: through a transposed copy (made once per LP), one row-wise launch
             if (!h->d_AhTg) h->mem.zeroed(h->d_AhTg, h->ldn * h->Mp, h->stream);
             if (!h->ahTg_valid) {
-                hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), 0, h->stream, h->d_Ah,
-                                   h->ldn, h->M, h->n, h->d_AhTg, h->Mp, (int64_t)-1);
+                asmb::launch(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), h->stream, h->d_Ah, h->ldn, h->M, h->n, h->d_AhTg,
+                             h->Mp, (int64_t)-1);
                 h->ahTg_valid = true;
             }
             int id = begin(ASM_K_GEMV, 2.0 * h->M * h->n, 8.0 * h->M * h->ldn);
-            hipLaunchKernelGGL(k_gemv_n_exact, dim3((unsigned)((h->ldn + 3) / 4)), dim3(256), 0, h->stream, (const double*)h->d_AhTg, h->Mp, y, out, h->ldn, h->M);
+            asmb::launch(k_gemv_n_exact, asmb::blocks(h->ldn, 4), dim3(256), h->stream, h->d_AhTg, h->Mp, y, out, h->ldn, h->M);
             end(id);
             return;
         }
@@ -581,9 +581,8 @@ struct Dev {
         int64_t chunk = (h->M + R - 1) / R;
         R = (h->M + chunk - 1) / chunk;
         int id = begin(ASM_K_GEMV, 2.0 * h->M * h->n, 8.0 * h->M * h->ldn);
-        hipLaunchKernelGGL(k_gemv_t_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), 0, h->stream, A, h->ldn, y,
-                           h->d_partial, h->M, h->ldn, chunk);
-        hipLaunchKernelGGL(k_gemv_t_stage2, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, h->d_partial, out, R, h->ldn);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, A, h->ldn, y, h->d_partial, h->M, h->ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_partial, out, R, h->ldn);
         end(id);
     }
     // out[M] = A x   (host vectors)
@@ -620,7 +619,7 @@ struct Dev {
             const int TS = 32 * T, nt = (Ms + TS - 1) / TS;
             if (h->nz_valid && nt > 0) {
                 unsigned char* nz2 = h->d_nz + h->nz_half;
-                hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, A, ld, (int64_t)Ms, TS, nch, nz2, nch, idx_dev);
+                asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, A, ld, (int64_t)Ms, TS, nch, nz2, nch, idx_dev);
                 frac = executed_fraction(nz2, nt, nch, cache_slot);
                 nz = nz2;
             }
@@ -644,7 +643,7 @@ struct Dev {
     // reads beyond it (an outer panel of CHOL_NBO columns, tile rounding)
     void zero_band(const FacBuf& f, int Ms, int band) {
         const int64_t wz = std::min<int64_t>(round_up(band + 1, 64) + CHOL_NBO + 128, f.ld);
-        hipLaunchKernelGGL(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), 0, h->stream, f.S, f.ld, Ms, (int)wz);
+        asmb::launch(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), h->stream, f.S, f.ld, Ms, (int)wz);
     }
     // S[0:Ms,0:Ms] (lower) = Ah[idx,:] diag(theta) Ah[idx,:]' + diag for a row list in the handle's reverse Cuthill-McKee order
     // (asm_handle::row_band): banded, built entry by entry from the structural pairs - cpos maps a row to its place in the list (-1: not
@@ -652,8 +651,8 @@ struct Dev {
     void schur_banded_dev(const int* cpos_dev, int Ms, const double* theta_dev, const double* diag_dev) {
         FacBuf& f = h->main_fac;
         zero_band(f, Ms, h->row_band);
-        hipLaunchKernelGGL(k_schur_sparse, dim3((unsigned)((h->n_rowpairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowpairs, h->n_rowpairs, cpos_dev,
-                           h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), theta_dev, diag_dev, f.S, f.ld, (const int*)nullptr);
+        asmb::launch(k_schur_sparse, asmb::blocks(h->n_rowpairs), dim3(256), h->stream, h->d_rowpairs, h->n_rowpairs, cpos_dev, h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah),
+                     theta_dev, diag_dev, f.S, f.ld, nullptr);
     }
     // K = diag + Ah' diag(dinv) Ah (n x n, lower) with the COLUMNS in their reverse Cuthill-McKee order (asm_handle::col_band): the column form
     // of the restoration-phase Newton system, banded and built from the structural column pairs; `diag_place` is indexed by position
@@ -661,8 +660,8 @@ struct Dev {
         FacBuf& f = h->main_fac;
         const int n = (int)h->n;
         zero_band(f, n, h->col_band);
-        hipLaunchKernelGGL(k_schur_sparse, dim3((unsigned)((h->n_colpairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_colpairs, h->n_colpairs,
-                           (const int*)h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah), dinv_dev, diag_place, f.S, f.ld, (const int*)h->d_sc_pos);
+        asmb::launch(k_schur_sparse, asmb::blocks(h->n_colpairs), dim3(256), h->stream, h->d_colpairs, h->n_colpairs, h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah),
+                     dinv_dev, diag_place, f.S, f.ld, h->d_sc_pos);
     }
     // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32
     void gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, const double* C0, int64_t ldc0, double* C, int64_t ldc, int Ma, int Mb, int K, int mode) {
@@ -673,11 +672,11 @@ struct Dev {
         // ... and 96 columns per workgroup when 32 x 64 tiles overshoot one workgroup per CU and 32 x 96 tiles do not
         const int64_t t3264 = (int64_t)((Mb + 63) / 64) * ((Ma + 31) / 32), t3296 = (int64_t)((Mb + 95) / 96) * ((Ma + 31) / 32);
         if (t64 < 2 * (int64_t)h->num_cus && Ma > 32 && t3264 > h->num_cus && t3296 <= h->num_cus)
-            hipLaunchKernelGGL(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
+            asmb::launch(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         else if (t64 < 2 * (int64_t)h->num_cus && Ma > 32)
-            hipLaunchKernelGGL(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
+            asmb::launch(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         else
-            hipLaunchKernelGGL(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), 0, h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
+            asmb::launch(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         end(id);
     }
     // Rows of R (nrhs x ldr, zero beyond column Ms) are right-hand sides of  L x = r  (forward) and then  L' x = z  (backward) with the
@@ -705,20 +704,19 @@ struct Dev {
     // out[i] = sum_j Ah_ij^2 thinv_j   (sparse patterns only)
     void schur_diag(const double* thinv_dev, double* out_dev) {
         const double* v = sparse_vals(h->d_Ah);
-        hipLaunchKernelGGL(k_ipm_sdiag_csr, dim3((unsigned)((h->M + 255) / 256)), dim3(256), 0, h->stream, h->d_sp_ptr, h->d_sp_col, v, thinv_dev, out_dev, h->M);
+        asmb::launch(k_ipm_sdiag_csr, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, v, thinv_dev, out_dev, h->M);
     }
     // transposed copy of Ah and its chunk flags (column form of the restoration-phase Newton system), once per LP
     void ensure_AhT() {
         if (h->ahT_valid) return;
-        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), 0, h->stream, h->d_Ah,
-                           h->ldn, h->M, h->n, h->d_AhT, h->ldT, (int64_t)-1);
+        asmb::launch(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), h->stream, h->d_Ah, h->ldn, h->M, h->n, h->d_AhT, h->ldT,
+                     (int64_t)-1);
         h->nzT_valid = false;
         const int nch = (int)(h->ldT / ASM_KC);
         if (!h->dense_fast && nch <= ASM_MAXCHUNKS && h->nnz * 8 <= h->M * h->n) {
             const int T = pick_tile(h->n), TS = 32 * T;
             const int nt = (int)((h->n + TS - 1) / TS);
-            hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, h->d_AhT, h->ldT, h->n, TS, nch,
-                               h->d_nzT, nch, (const int*)nullptr);
+            asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, h->d_AhT, h->ldT, h->n, TS, nch, h->d_nzT, nch, nullptr);
             h->nzT_fraction = executed_fraction(h->d_nzT, nt, nch);
             h->nzT_valid = true;
         }
@@ -735,8 +733,7 @@ struct Dev {
         const int TS = 32 * h->nz_T;
         const int nt = (int)((h->M + TS - 1) / TS);
         h->nz_pitch = nch;
-        hipLaunchKernelGGL(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), 0, h->stream, h->d_Ah, h->ldn, h->M, TS,
-                           nch, h->d_nz, h->nz_pitch, (const int*)nullptr);
+        asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, h->d_Ah, h->ldn, h->M, TS, nch, h->d_nz, h->nz_pitch, nullptr);
         h->nz_valid = true;
         h->nz_fraction = executed_fraction(h->d_nz, nt, nch, 0);
     }
@@ -752,8 +749,8 @@ struct Dev {
     }
     double executed_fraction_now(const unsigned char* d_flags, int nt, int nch) {
         std::vector<unsigned char> fl((size_t)nt * nch);
-        HIPCHK(hipMemcpyAsync(fl.data(), d_flags, fl.size(), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::copy_async(fl.data(), d_flags, fl.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         double act = 0.0, tot = 0.0;
         for (int a = 0; a < nt; ++a)
             for (int b = 0; b <= a; ++b) {
@@ -768,12 +765,12 @@ struct Dev {
     void chol_solve_dev(const FacBuf& f, const double* rhs_dev, double* out_dev, int Ms) {
         // the substitution runs in place in the caller's output buffer (w), z in d_vecM
         if (f.small && Ms <= ASM_SMALL_USE) {       // small systems: one workgroup, factor + inverses of its 64-wide diagonal blocks
-            hipLaunchKernelGGL(k_small_solve, dim3(1), dim3(1024), 0, h->stream, (const double*)f.S, f.ld, (const double*)f.Linv, Ms, rhs_dev, out_dev);
+            asmb::launch(k_small_solve, dim3(1), dim3(1024), h->stream, f.S, f.ld, f.Linv, Ms, rhs_dev, out_dev);
             return;
         }
         // a system of one wide block only READS its right-hand side (forward diagonal product); with more blocks the panel updates work in place
         const bool one_block = Ms <= f.wb;
-        if (out_dev != rhs_dev && !one_block) HIPCHK(hipMemcpyAsync(out_dev, rhs_dev, Ms * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        if (out_dev != rhs_dev && !one_block) HIPCHK(asmb::copy_async(out_dev, rhs_dev, Ms * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         int id = begin(ASM_K_TRSV, 2.0 * Ms * (double)Ms, 8.0 * Ms * (double)Ms);
         solve_launches(f, Ms, out_dev, one_block ? rhs_dev : out_dev);
         end(id);
@@ -803,34 +800,33 @@ struct Dev {
         int kid = begin(ASM_K_SYRK_KERNEL, fl, 8.0 * ((double)(Ms + MsB) * K + (double)Ms * MsB), s);
         struct EndGuard { Dev* d; int id; ~EndGuard() { d->end(id); } } guard_{this, kid};
         if (T == 4 && mode == 1 && !nz && !idx && !theta && K % (2 * ASM_UPD_KC) == 0)      // Cholesky updates: their own kernel
-            hipLaunchKernelGGL(k_syrk_upd, dim3((unsigned)blocks), dim3(256), 0, s, A, ld, row0, Ms, K, S, ldS, srow0, MsB, ntj);
+            asmb::launch(k_syrk_upd, dim3((unsigned)blocks), dim3(256), s, A, ld, row0, Ms, K, S, ldS, srow0, MsB, ntj);
         else if (T == 4 && mode == 1 && !nz && K % 16 == 0)      // 16-wide k-chunks, two workgroups per CU
-            hipLaunchKernelGGL((k_syrk<4, 8, 16, 4>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
-                               ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
+            asmb::launch((k_syrk<4, 8, 16, 4>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), s, A, ld, idx, row0, Ms, K, theta, diag, S, ldS, srow0, mode, MsB, ntj, nz,
+                         nzpitch, ksplit);
         else if (T == 4)
-            hipLaunchKernelGGL((k_syrk<4, 8, 32, 2>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
-                               ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
+            asmb::launch((k_syrk<4, 8, 32, 2>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(512), s, A, ld, idx, row0, Ms, K, theta, diag, S, ldS, srow0, mode, MsB, ntj, nz,
+                         nzpitch, ksplit);
         else if (T == 2)
-            hipLaunchKernelGGL((k_syrk<2, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
-                               ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
+            asmb::launch((k_syrk<2, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), s, A, ld, idx, row0, Ms, K, theta, diag, S, ldS, srow0, mode, MsB, ntj, nz,
+                         nzpitch, ksplit);
         else
-            hipLaunchKernelGGL((k_syrk<1, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), 0, s, A, ld, idx, row0, Ms, K, theta, diag, S,
-                               ldS, srow0, mode, MsB, ntj, nz, nzpitch, ksplit);
+            asmb::launch((k_syrk<1, 4, 32, 1>), dim3((unsigned)blocks, (unsigned)nsplit), dim3(256), s, A, ld, idx, row0, Ms, K, theta, diag, S, ldS, srow0, mode, MsB, ntj, nz,
+                         nzpitch, ksplit);
     }
 
     void diag_prepare(const FacBuf& f, int Ms, int mode, double rel, double absv) {
-        hipLaunchKernelGGL(k_diag_prepare, dim3(1), dim3(1024), 0, h->stream, f.S, f.ld, Ms, h->d_diag0, mode, rel, absv);
+        asmb::launch(k_diag_prepare, dim3(1), dim3(1024), h->stream, f.S, f.ld, Ms, h->d_diag0, mode, rel, absv);
     }
     template <int WB>
     void trtri_launches(const FacBuf& f, int Ms) {
         constexpr int WSUB = WB / ASM_NB;
         const unsigned nW = (unsigned)((Ms + WB - 1) / WB);
-        hipLaunchKernelGGL((k_trtri_init<WB>), dim3(nW, WSUB * WSUB), dim3(256), 0, h->stream, f.Linv, Ms, f.Binv);
+        asmb::launch((k_trtri_init<WB>), dim3(nW, WSUB * WSUB), dim3(256), h->stream, f.Linv, Ms, f.Binv);
         for (int hh = 1; hh < WSUB; hh *= 2)
             for (int stage = 0; stage < 2; ++stage)
-                hipLaunchKernelGGL((k_trtri_level<WB>), dim3(nW, (unsigned)(WSUB / (2 * hh)), (unsigned)(hh * hh)), dim3(256), 0, h->stream,
-                                   f.S, f.ld, Ms, f.Binv, f.BinvT, hh, stage);
-        hipLaunchKernelGGL((k_transpose_wb<WB>), dim3(nW, WSUB * WSUB), dim3(256), 0, h->stream, f.Binv, f.BinvT);
+                asmb::launch((k_trtri_level<WB>), dim3(nW, (unsigned)(WSUB / (2 * hh)), (unsigned)(hh * hh)), dim3(256), h->stream, f.S, f.ld, Ms, f.Binv, f.BinvT, hh, stage);
+        asmb::launch((k_transpose_wb<WB>), dim3(nW, WSUB * WSUB), dim3(256), h->stream, f.Binv, f.BinvT);
     }
     // want_inverse = false: the caller only solves against the factor and the factor is a "small" one (one-workgroup solves): the
     // explicit inverses of the wide blocks are not built
@@ -901,14 +897,14 @@ struct Dev {
                     // one wide block: its explicit inverse is made inside the launch by helper workgroups, one per 64 x 64 tile of the block
                     // rows this inner panel finishes (k_chol_panel_inv) - no k_trtri_* launches afterwards
                     const int nst = (std::min(I1, Ms) - I0 + ASM_NB - 1) / ASM_NB, T = (Ms + ASM_NB - 1) / ASM_NB;
-                    asmb::launch_resident(k_chol_panel_inv, dim3((unsigned)(G + nst * T)), dim3(256), 0, s, f.S, f.ld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
-                                       f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch, f.Binv, f.BinvT, f.wb, G);
+                    asmb::launch_resident(k_chol_panel_inv, dim3((unsigned)(G + nst * T)), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, h->d_diag0, thr, f.Linv, h->d_pflags,
+                                          h->d_ptmo, h->panel_epoch, f.Binv, f.BinvT, f.wb, G);
                 } else if (beside_updates)
-                    asmb::launch_resident(k_chol_panel, dim3((unsigned)G), dim3(256), 0, s, f.S, f.ld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
-                                       f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch);
+                    asmb::launch_resident(k_chol_panel, dim3((unsigned)G), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, h->d_diag0, thr, f.Linv, h->d_pflags, h->d_ptmo,
+                                          h->panel_epoch);
                 else
-                    asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), 0, s, f.S, f.ld, I0, std::min(I1, Ms), Mi, (const double*)h->d_diag0, thr,
-                                       f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch);
+                    asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, h->d_diag0, thr, f.Linv, h->d_pflags, h->d_ptmo,
+                                          h->panel_epoch);
             }
             if (I1 < K1 && I1 < Mi) {
                 int rem = Mi - I1;
@@ -939,8 +935,8 @@ struct Dev {
             }
             int pid = begin(ASM_K_PANEL_KERNEL, pfl, 8.0 * 2.0 * (double)(Mi - I0) * (double)(Mi - I0) * 0.5, h->stream);
             const int nhelp = (m * (m + 1) / 2 + ASM_BAND_TPH - 1) / ASM_BAND_TPH;      // helper workgroups: one per trailing tile
-            asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), 0, h->stream, f.S, f.ld, I0, I1, Mi, (const double*)h->d_diag0, thr,
-                                  f.Linv, h->d_pflags, h->d_ptmo, h->panel_epoch, nrt);
+            asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), h->stream, f.S, f.ld, I0, I1, Mi, h->d_diag0, thr, f.Linv, h->d_pflags, h->d_ptmo,
+                                  h->panel_epoch, nrt);
             end(pid);
         }
     }
@@ -1000,11 +996,11 @@ struct Dev {
         const int nB = (Ms + WB - 1) / WB;
         for (int B = 0; B < nB; ++B) {
             int b1 = std::min((B + 1) * WB, Ms);
-            hipLaunchKernelGGL((k_wtrsv_fwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, f.Binv, B, Ms, src, z);
+            asmb::launch((k_wtrsv_fwd_diag<WB>), dim3(WB / 4), dim3(256), h->stream, f.Binv, B, Ms, src, z);
             const int Me = rowlim(f, Ms, b1);
             int rem = Me - b1;
             if (rem > 0)
-                hipLaunchKernelGGL((k_wtrsv_fwd_panel<WB>), dim3((unsigned)((rem + 4 * ASM_FWD_RPW - 1) / (4 * ASM_FWD_RPW))), dim3(256), 0, h->stream, f.S, f.ld, B, Me, z, w);
+                asmb::launch((k_wtrsv_fwd_panel<WB>), dim3((unsigned)((rem + 4 * ASM_FWD_RPW - 1) / (4 * ASM_FWD_RPW))), dim3(256), h->stream, f.S, f.ld, B, Me, z, w);
         }
         for (int B = nB - 1; B >= 0; --B) {
             int b1 = std::min((B + 1) * WB, Ms);
@@ -1013,14 +1009,14 @@ struct Dev {
             int np = 0;
             if (rem > 0) {
                 np = (rem + ASM_WBROWS - 1) / ASM_WBROWS;
-                hipLaunchKernelGGL((k_wtrsv_bwd_panel<WB>), dim3((unsigned)np), dim3(256), 0, h->stream, f.S, f.ld, B, Me, w, h->d_wpart);
+                asmb::launch((k_wtrsv_bwd_panel<WB>), dim3((unsigned)np), dim3(256), h->stream, f.S, f.ld, B, Me, w, h->d_wpart);
             }
             if (np > 0) {
-                hipLaunchKernelGGL((k_wtrsv_bwd_reduce<WB>), dim3(WB / ASM_NB), dim3(256), 0, h->stream, B, Ms, z, h->d_wpart, np, h->d_wt);
-                hipLaunchKernelGGL((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, f.BinvT, B, Ms, h->d_wt, w, WB);
+                asmb::launch((k_wtrsv_bwd_reduce<WB>), dim3(WB / ASM_NB), dim3(256), h->stream, B, Ms, z, h->d_wpart, np, h->d_wt);
+                asmb::launch((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), h->stream, f.BinvT, B, Ms, h->d_wt, w, WB);
             } else {
                 // last wide block (the only one of a small system): nothing to subtract, the diagonal product reads z itself
-                hipLaunchKernelGGL((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), 0, h->stream, f.BinvT, B, Ms, (const double*)(z + (int64_t)B * WB), w, Ms - B * WB);
+                asmb::launch((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), h->stream, f.BinvT, B, Ms, z + (int64_t)B * WB, w, Ms - B * WB);
             }
         }
     }
@@ -1032,11 +1028,10 @@ struct Dev {
         if (h->dense_fast) {
             int64_t total = h->m * h->n;
             unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_assemble_dense, dim3(g), dim3(256), 0, h->stream, h->d_dE, h->d_J, h->m, h->n, h->ldn);
+            asmb::launch(k_assemble_dense, dim3(g), dim3(256), h->stream, h->d_dE, h->d_J, h->m, h->n, h->ldn);
         } else if (h->nu > 0) {
             unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_assemble, dim3(g), dim3(256), 0, h->stream, h->d_dE, h->d_perm, h->d_ustart, h->d_uoff,
-                               h->d_adjoff, h->d_J, h->nu);
+            asmb::launch(k_assemble, dim3(g), dim3(256), h->stream, h->d_dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, h->d_J, h->nu);
         }
         end(id);
     }
@@ -1049,19 +1044,16 @@ struct Dev {
         if (h->sp_ok) {                      // sparse pattern: the same maxima over the stored entries only
             const double* vJ = sparse_vals(h->d_J);
             int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * h->sp_nnz);
-            hipLaunchKernelGGL(k_sp_row_absmax, dim3((unsigned)((h->M + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, vJ, h->d_rho, h->M);
-            hipLaunchKernelGGL(k_sp_col_relmax, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_sc_ptr, (const int*)h->d_sc_row,
-                               (const int*)h->d_sc_pos, vJ, (const double*)h->d_rho, h->d_vecN, h->n, h->ldn);
+            asmb::launch(k_sp_row_absmax, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, vJ, h->d_rho, h->M);
+            asmb::launch(k_sp_col_relmax, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vJ, h->d_rho, h->d_vecN, h->n, h->ldn);
             end(id);
             d2h(rel, h->d_vecN, h->n);
             return;
         }
         int id = begin(ASM_K_SCALE, 0.0, 8.0 * 2.0 * h->M * h->ldn);
-        hipLaunchKernelGGL(k_row_absmax, dim3((unsigned)((h->M + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, h->d_rho, h->M, h->ldn);
-        hipLaunchKernelGGL(k_col_relmax_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), 0, h->stream, h->d_J,
-                           h->ldn, h->d_rho, h->d_partial, h->M, h->ldn, chunk);
-        hipLaunchKernelGGL(k_col_relmax_stage2, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, h->d_partial, h->d_vecN, R,
-                           h->ldn);
+        asmb::launch(k_row_absmax, asmb::blocks(h->M, 4), dim3(256), h->stream, h->d_J, h->ldn, h->d_rho, h->M, h->ldn);
+        asmb::launch(k_col_relmax_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, h->d_J, h->ldn, h->d_rho, h->d_partial, h->M, h->ldn, chunk);
+        asmb::launch(k_col_relmax_stage2, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_partial, h->d_vecN, R, h->ldn);
         end(id);
         d2h(rel, h->d_vecN, h->n);
     }
@@ -1075,16 +1067,14 @@ struct Dev {
         if (h->sp_ok) {
             const double* vJ = sparse_vals(h->d_J);
             int id = begin(ASM_K_SCALE, 0.0, 8.0 * 4.0 * h->sp_nnz);
-            hipLaunchKernelGGL(k_sp_scale_rows, dim3((unsigned)((h->M + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col,
-                               (const int64_t*)h->d_sp_off, vJ, (const double*)h->d_c, h->d_Ah, h->d_spv_Ah, h->d_rho, h->M);
+            asmb::launch(k_sp_scale_rows, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, h->d_sp_off, vJ, h->d_c, h->d_Ah, h->d_spv_Ah, h->d_rho, h->M);
             end(id);
             h->spv_Ah_valid = true;
             d2h(rho, h->d_rho, h->M);
             return;
         }
         int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * h->M * h->ldn);
-        hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)h->M), dim3(256), 0, h->stream, h->d_J, h->d_c, h->d_Ah, h->d_rho, h->n,
-                           h->ldn);
+        asmb::launch(k_scale_rows, dim3((unsigned)h->M), dim3(256), h->stream, h->d_J, h->d_c, h->d_Ah, h->d_rho, h->n, h->ldn);
         end(id);
         d2h(rho, h->d_rho, h->M);
     }
@@ -1106,9 +1096,9 @@ struct Solver {
     // out = A x for a k x ncols matrix of few, long rows (the basis Zt): one workgroup per row when that fills the chip better
     void gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
         if (rows <= 2048 && ncols >= 2048)
-            hipLaunchKernelGGL(k_gemv_n_wide, dim3((unsigned)rows), dim3(256), 0, h->stream, A, ld, x, out, rows, ncols);
+            asmb::launch(k_gemv_n_wide, dim3((unsigned)rows), dim3(256), h->stream, A, ld, x, out, rows, ncols);
         else
-            hipLaunchKernelGGL(k_gemv_n, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->stream, A, ld, x, out, rows, ncols);
+            asmb::launch(k_gemv_n, asmb::blocks(rows, 4), dim3(256), h->stream, A, ld, x, out, rows, ncols);
     }
     // workgroups of the interior-point reductions (k_ipm_measures / _steps / _muaff): 1024 elements per workgroup and sweep, at most IPM_RED_MAXWG
     unsigned red_grid() const { return (unsigned)std::min<int64_t>(IPM_RED_MAXWG, std::max<int64_t>(1, (std::max(std::max(lp.n, lp.M), lp.ns) + 4095) / 4096)); }
@@ -1173,11 +1163,11 @@ struct Solver {
         P.rtype = h->d_ipm_i; P.rs0 = h->d_ipm_i + lm; P.rs1 = h->d_ipm_i + 2 * lm; P.srow = h->d_ipm_i + 3 * lm;
     }
     void up(const double* dst, const vec& v) {
-        if (!v.empty()) HIPCHK(hipMemcpyAsync((void*)dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (!v.empty()) HIPCHK(asmb::copy_async((void*)dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     void down(vec& v, const double* src, int64_t cnt) {
         v.resize(cnt);
-        if (cnt) HIPCHK(hipMemcpyAsync(v.data(), src, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (cnt) HIPCHK(asmb::copy_async(v.data(), src, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     // push the (scaled) LP data of `lp` to the device
     void ipm_upload_lp() {
@@ -1192,14 +1182,14 @@ struct Solver {
             std::memcpy(st + ln, lp.lb.data(), lp.n * sizeof(double));
             std::memcpy(st + 2 * ln, lp.ub.data(), lp.n * sizeof(double));
             std::memcpy(st + 3 * ln, lp.r.data(), lp.M * sizeof(double));
-            HIPCHK(hipMemcpyAsync((void*)P.q, st, 3 * ln * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync((void*)P.r, st + 3 * ln, lp.M * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async((void*)P.q, st, 3 * ln * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async((void*)P.r, st + 3 * ln, lp.M * sizeof(double), hipMemcpyHostToDevice, h->stream));
             if (lp.ns) {
                 double* ss = st + 3 * ln + lm;
                 std::memcpy(ss, lp.w.data(), lp.ns * sizeof(double));
                 std::memcpy(ss + ls, lp.slo.data(), lp.ns * sizeof(double));
                 std::memcpy(ss + 2 * ls, h->scoef.data(), lp.ns * sizeof(double));
-                HIPCHK(hipMemcpyAsync((void*)P.w, ss, 3 * ls * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(asmb::copy_async((void*)P.w, ss, 3 * ls * sizeof(double), hipMemcpyHostToDevice, h->stream));
             }
             h2d_done(h);
             return;
@@ -1222,8 +1212,8 @@ struct Solver {
     // and then the sequence word; spin on the word (the stream is in order: everything before that kernel has finished too).
     void read_scal(unsigned pub) {
         if (pub == 0) {
-            HIPCHK(hipMemcpyAsync(h->h_scal, P.scal, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            HIPCHK(asmb::copy_async(h->h_scal, P.scal, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::sync(h->stream));
             return;
         }
         if (asmb::in_fiber()) {      // scenario batch: the publishing kernel is recorded; the round that launches it ends before this fiber resumes
@@ -1241,7 +1231,7 @@ struct Solver {
             else if (spins < 20200) sched_yield();
             else { struct timespec ts = {0, 20000}; nanosleep(&ts, nullptr); }
             if (((spins < 20200 && (spins & 0xfffff) == 0) || (spins >= 20200 && (spins & 0x3ff) == 0)) && now_ms() - t0 > 30000.0) {
-                HIPCHK(hipStreamSynchronize(h->stream));            // a device fault surfaces here
+                HIPCHK(asmb::sync(h->stream));            // a device fault surfaces here
                 if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
                 throw HipError("read_scal: the publishing kernel finished without setting its sequence word");
             }
@@ -1262,9 +1252,9 @@ struct Solver {
         ip.usable[(int)NewtonForm::Column] = h->col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
         ipm_upload_lp();
         P.ncomp = ip.ncomp;
-        hipLaunchKernelGGL(k_ipm_init_p, dim3(grid_all()), dim3(256), 0, h->stream, P, lp.ns == 0 ? 1 : 0);
+        asmb::launch(k_ipm_init_p, dim3(grid_all()), dim3(256), h->stream, P, lp.ns == 0 ? 1 : 0);
         dev.gemv_n_dev(h->d_Ah, P.p, P.act);
-        hipLaunchKernelGGL(k_ipm_init_rest, dim3(grid_all()), dim3(256), 0, h->stream, P, lp.ns == 0 ? IPM_MU0_NORMAL : 1.0);
+        asmb::launch(k_ipm_init_rest, dim3(grid_all()), dim3(256), h->stream, P, lp.ns == 0 ? IPM_MU0_NORMAL : 1.0);
     }
 
     void ipm_measures() {
@@ -1273,11 +1263,11 @@ struct Solver {
         const unsigned pub = pub_next();
         if (ns_live()) {
             // null-space form: the equality rows' multipliers are carried as 0, the dual residual that counts is Z'rdp (oracle: IPM.measures)
-            hipLaunchKernelGGL(k_ipm_measures, dim3(red_grid()), dim3(1024), 0, h->stream, P, 0u);
+            asmb::launch(k_ipm_measures, dim3(red_grid()), dim3(1024), h->stream, P, 0u);
             gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)P.rdp, nsv(12), (int64_t)ip.ns_k, h->ldn);
-            hipLaunchKernelGGL(k_ns_dinf, dim3(1), dim3(1024), 0, h->stream, P, (const double*)nsv(12), ip.ns_k, pub);
+            asmb::launch(k_ns_dinf, dim3(1), dim3(1024), h->stream, P, nsv(12), ip.ns_k, pub);
         } else {
-            hipLaunchKernelGGL(k_ipm_measures, dim3(red_grid()), dim3(1024), 0, h->stream, P, pub);
+            asmb::launch(k_ipm_measures, dim3(red_grid()), dim3(1024), h->stream, P, pub);
         }
         read_scal(pub);
         ip.pinf = h->h_scal[SC_PINF];
@@ -1317,8 +1307,8 @@ struct Solver {
     NsIdx nsX() const { NsIdx X; X.Eidx = h->d_nsEidx; X.Epos = h->d_nsEpos; X.Iidx = h->d_nsIidx; X.Ipos = h->d_nsIpos; X.nE = h->ns_nE; X.nI = h->ns_nI; return X; }
     int ns_read_cnt() {
         int v = 0;
-        HIPCHK(hipMemcpyAsync(&v, h->d_nscnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::copy_async(&v, h->d_nscnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         return v;
     }
     // buffers sized by the null-space dimension: right-hand-side blocks R, X (k x nEp), Gt = [Zt | GI'] (k x ldg), the k x k factor
@@ -1328,7 +1318,7 @@ struct Solver {
             // the null space grew beyond what the first LP of the form reserved (fewer fixed columns than then): the k-sized buffers are
             // released and re-made; the carried basis goes with them
             if (h->knobs.verbose) std::fprintf(stderr, "[asm] null-space form: dimension %d exceeds the reserved %d - buffers re-allocated\n", k, h->ns_kcap);
-            HIPCHK(hipStreamSynchronize(h->stream));
+            HIPCHK(asmb::sync(h->stream));
             h->mem_nsk.release();
             h->ns_fN = FacBuf(); h->ns_fC = FacBuf();
             h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0;
@@ -1351,18 +1341,18 @@ struct Solver {
         h->ns_fC.small = true;
         P.alloc(h->d_nsqi, (int64_t)h->ns_ccap + h->ldn + h->ns_nIp + 16);
         P.zeroed(h->d_nsq, (int64_t)h->ns_ccap * h->ns_fN.ld + 5 * (int64_t)h->ns_ccap + h->ldn + h->Mp + 2 * h->ns_fN.ld + 64, h->stream);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
     }
     // In place  Zt = L^-1 Zt  with the k x k factor just made in h->ns_fN.  When the factor fits into one wide block the explicit inverse of
     // that block IS L^-1: one transpose + one product on the matrix cores (the rows are n long); otherwise forward substitution per column.
     void ns_ortho(int k) {
         if (k <= h->ns_fN.wb) {
             const int kp = (int)round_up(k, 32);
-            hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((h->ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), 0, h->stream, (const double*)h->d_nsG, h->ns_ldg,
-                               (int64_t)k, h->ldn, h->d_nsZT, h->ns_fN.ld, (int64_t)-1);
+            asmb::launch(k_transpose_dense, dim3((unsigned)((h->ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), h->stream, h->d_nsG, h->ns_ldg, (int64_t)k, h->ldn,
+                         h->d_nsZT, h->ns_fN.ld, (int64_t)-1);
             dev.gemm_nt(h->ns_fN.Binv, h->ns_fN.wb, h->d_nsZT, h->ns_fN.ld, nullptr, 0, h->d_nsG, h->ns_ldg, k, (int)h->ldn, kp, 0);
         } else {
-            hipLaunchKernelGGL(k_ns_ortho, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, k, h->d_nsG, h->ns_ldg, h->ldn);
+            asmb::launch(k_ns_ortho, asmb::blocks(h->ldn), dim3(256), h->stream, h->ns_fN.S, h->ns_fN.ld, k, h->d_nsG, h->ns_ldg, h->ldn);
         }
     }
     // The k rows in d_nsG (an approximate or an outdated basis) projected onto null(A_EF) of THIS LP and orthonormalised with their own
@@ -1374,20 +1364,20 @@ struct Solver {
         const double* vals = dev.sparse_vals(h->d_Ah);
         // second pass (oracle: NullSpace.basis_from): project the rows once more and orthonormalise with their own Gram matrix (~ I) -
         // the columns picked in index order can be badly conditioned, and the active-set solves need A_EF Z = 0 to 1e-13
-        hipLaunchKernelGGL(k_ns_rows_e, dim3((unsigned)((h->ns_nEp + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sp_ptr, h->d_sp_col, vals, X,
-                           (const double*)h->d_nsFm, (const double*)h->d_nsG, h->ns_ldg, h->d_nsR, (int64_t)h->ns_nEp);
+        asmb::launch(k_ns_rows_e, dim3((unsigned)((h->ns_nEp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, h->d_nsFm, h->d_nsG, h->ns_ldg,
+                     h->d_nsR, (int64_t)h->ns_nEp);
         dev.trsm_rows(h->ns_f0, h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
-        hipLaunchKernelGGL(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X,
-                           (const int*)h->d_nsJ, (const double*)h->d_nsFm, (const double*)h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 1);
+        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm,
+                     h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 1);
         dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
-        hipLaunchKernelGGL(k_ns_fill, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, h->stream, h->d_diag0, 1.0, (int64_t)k);
+        asmb::launch(k_ns_fill, asmb::blocks(k), dim3(256), h->stream, h->d_diag0, 1.0, (int64_t)k);
         dev.chol(h->ns_fN, k, thr);
-        hipLaunchKernelGGL(k_ns_count_big, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
         const int bad2 = ns_read_cnt();
         if (bad2 > 0) return false;
         ns_ortho(k);
-        hipLaunchKernelGGL(k_ns_gi, dim3((unsigned)((h->ns_nIp + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sp_ptr, h->d_sp_col, vals, X,
-                           (const double*)h->d_nsG, h->ns_ldg, h->d_nsG + h->ldn, h->ns_nIp);
+        asmb::launch(k_ns_gi, dim3((unsigned)((h->ns_nIp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, h->d_nsG, h->ns_ldg,
+                     h->d_nsG + h->ldn, h->ns_nIp);
         return true;
     }
     // Orthonormal basis from the columns J of the projector P (oracle: NullSpace.basis_from): W = S0^-1 A_EF[:, J] by block
@@ -1397,18 +1387,16 @@ struct Solver {
         const int k = (int)J.size(), nE = h->ns_nE;
         const NsIdx X = nsX();
         const double* vals = dev.sparse_vals(h->d_Ah);
-        HIPCHK(hipMemcpyAsync(h->d_nsJ, J.data(), k * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(h->d_nsJ, J.data(), k * sizeof(int), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);
-        hipLaunchKernelGGL(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, (const int*)h->d_nsJ,
-                           (const double*)h->d_nsFm, h->d_nsR, (int64_t)h->ns_nEp);
+        asmb::launch(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm, h->d_nsR, (int64_t)h->ns_nEp);
         dev.trsm_rows(h->ns_f0, h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
-        hipLaunchKernelGGL(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X,
-                           (const int*)h->d_nsJ, (const double*)h->d_nsFm, (const double*)h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 0);
-        hipLaunchKernelGGL(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, (const double*)h->d_nsG, h->ns_ldg, (const int*)h->d_nsJ, k,
-                           h->ns_fN.S, h->ns_fN.ld);
-        hipLaunchKernelGGL(k_ns_fill, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, h->stream, h->d_diag0, 1.0, (int64_t)k);
+        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm,
+                     h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 0);
+        asmb::launch(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_nsG, h->ns_ldg, h->d_nsJ, k, h->ns_fN.S, h->ns_fN.ld);
+        asmb::launch(k_ns_fill, asmb::blocks(k), dim3(256), h->stream, h->d_diag0, 1.0, (int64_t)k);
         dev.chol(h->ns_fN, k, NS_WARM_THR);
-        hipLaunchKernelGGL(k_ns_count_big, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
         const int bad = ns_read_cnt();
         if (bad > 0) return false;
         ns_ortho(k);
@@ -1426,18 +1414,18 @@ struct Solver {
             if (!asmb::in_fiber()) {                // (pinned staging: the copy does not go through the runtime's pageable path)
                 double* fm = h->h_pin;
                 for (int64_t j = 0; j < h->ldn; ++j) fm[j] = (j < n && lp.ub[j] > lp.lb[j]) ? 1.0 : 0.0;
-                HIPCHK(hipMemcpyAsync(h->d_nsFm, fm, h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(asmb::copy_async(h->d_nsFm, fm, h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
             } else {
                 vec fm(h->ldn, 0.0);
                 for (int64_t j = 0; j < n; ++j) fm[j] = lp.ub[j] > lp.lb[j] ? 1.0 : 0.0;
-                HIPCHK(hipMemcpyAsync(h->d_nsFm, fm.data(), h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(asmb::copy_async(h->d_nsFm, fm.data(), h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
             }
             h2d_done(h);
         }
         double t_v = now_ms();
         auto vlap = [&](const char* what) {
             if (!h->knobs.verbose) return;
-            HIPCHK(hipStreamSynchronize(h->stream));
+            HIPCHK(asmb::sync(h->stream));
             const double t = now_ms();
             std::fprintf(stderr, "[asm] ns set-up %-10s +%.2f ms\n", what, t - t_v);
             t_v = t;
@@ -1446,8 +1434,8 @@ struct Solver {
             // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
             // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
             dev.zero_band(h->ns_f0, nE, h->ns_f0.band);
-            hipLaunchKernelGGL(k_ns_s0_sparse, dim3((unsigned)((h->ns_npairs + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_nsS0pairs, h->ns_npairs, h->d_sp_ptr,
-                               h->d_sp_col, dev.sparse_vals(h->d_Ah), (const int*)h->d_nsEidx, (const double*)h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
+            asmb::launch(k_ns_s0_sparse, asmb::blocks(h->ns_npairs), dim3(256), h->stream, h->d_nsS0pairs, h->ns_npairs, h->d_sp_ptr, h->d_sp_col, dev.sparse_vals(h->d_Ah),
+                         h->d_nsEidx, h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
         } else {
             // S0 = A_EF A_EF' (the share of its chunk products cached per handle: the equality rows are fixed)
             dev.schur_syrk(false, h->d_nsEidx, nE, h->d_nsFm, nullptr, h->ns_f0.S, h->ns_f0.ld, Dev::NzFlags::PerCall, 1);
@@ -1456,13 +1444,13 @@ struct Solver {
         dev.diag_prepare(h->ns_f0, nE, 1, 0.0, 0.0);
         dev.chol(h->ns_f0, nE, 1e-10);
         vlap("S0 factor");
-        hipLaunchKernelGGL(k_ns_count_big, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_f0.S, h->ns_f0.ld, nE, NS_BIG, h->d_nscnt);
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_f0.S, h->ns_f0.ld, nE, NS_BIG, h->d_nscnt);
         const int dropped = ns_read_cnt();
         const int64_t k = nF - (nE - dropped);
         if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
         ns_reserve((int)k);
-        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), 0, h->stream, (const double*)h->ns_f0.S, h->ns_f0.ld,
-                           (int64_t)nE, (int64_t)nE, h->d_nsLt, h->ns_f0.ld, (int64_t)(h->ns_f0.band > 0 ? h->ns_f0.band : nE));
+        asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), h->stream, h->ns_f0.S, h->ns_f0.ld, (int64_t)nE, (int64_t)nE,
+                     h->d_nsLt, h->ns_f0.ld, (int64_t)(h->ns_f0.band > 0 ? h->ns_f0.band : nE));
         std::vector<int>& J = cur_hint->ns_J;
         bool have = false;
         ns_was_cold = false;
@@ -1483,20 +1471,19 @@ struct Solver {
             double* Yr = h->d_nsYt;                                  // right-hand sides, then garbage
             double* Yt = h->d_nsYt + (int64_t)h->ldn * h->ns_nEp;   // L0^-1 a_j as rows
             const double* vals = dev.sparse_vals(h->d_Ah);
-            hipLaunchKernelGGL(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), 0, h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, (const int*)nullptr,
-                               (const double*)h->d_nsFm, Yr, (int64_t)h->ns_nEp);
+            asmb::launch(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, nullptr, h->d_nsFm, Yr, (int64_t)h->ns_nEp);
             dev.trsm_rows(h->ns_f0, Yr, Yt, h->ns_nEp, (int)n, nE, nullptr);
             std::vector<double> dg(n);
             FacBuf& T = h->main_fac;
             T.band = 0;
             for (int a = 0; a < 4 && !have; ++a) {
-                hipLaunchKernelGGL(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, T.S, T.ld, (int)n, (const double*)h->d_nsFm);
+                asmb::launch(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_nsFm);
                 dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, h->ns_nEp, nullptr, 0, (int)n, h->ns_nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
-                hipLaunchKernelGGL(k_ns_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_diag0, 1.0, n);
+                asmb::launch(k_ns_fill, asmb::blocks(n), dim3(256), h->stream, h->d_diag0, 1.0, n);
                 dev.chol(T, (int)n, NS_SEL_THR[a]);
-                hipLaunchKernelGGL(k_ns_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)T.S, T.ld, (int)n, h->d_vecN);
-                HIPCHK(hipMemcpyAsync(dg.data(), h->d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
+                asmb::launch(k_ns_diag, asmb::blocks(n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_vecN);
+                HIPCHK(asmb::copy_async(dg.data(), h->d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(asmb::sync(h->stream));
                 std::vector<int> Jc;
                 for (int64_t j = 0; j < n; ++j)
                     if (dg[j] < NS_BIG) Jc.push_back((int)j);
@@ -1536,14 +1523,14 @@ struct Solver {
     }
     // dense products with the gathered constraint matrix Csel (nact rows of pitch ldc)
     void nsq_gemv_n(const NsEq& Q, int nact, const double* x, double* out) {
-        hipLaunchKernelGGL(k_gemv_n, dim3((unsigned)((nact + 3) / 4)), dim3(256), 0, h->stream, (const double*)Q.Csel, Q.ldc, x, out, (int64_t)nact, Q.ldc);
+        asmb::launch(k_gemv_n, asmb::blocks(nact, 4), dim3(256), h->stream, Q.Csel, Q.ldc, x, out, (int64_t)nact, Q.ldc);
     }
     void nsq_gemv_t(const NsEq& Q, int nact, const double* y, double* out) {
         int64_t R = std::min<int64_t>((nact + 31) / 32, ASM_TMAXCHUNKS);
         int64_t chunk = (nact + R - 1) / R;
         R = (nact + chunk - 1) / chunk;
-        hipLaunchKernelGGL(k_gemv_t_stage1, dim3((unsigned)((Q.ldc + 255) / 256), (unsigned)R), dim3(256), 0, h->stream, (const double*)Q.Csel, Q.ldc, y, h->d_partial, (int64_t)nact, Q.ldc, chunk);
-        hipLaunchKernelGGL(k_gemv_t_stage2, dim3((unsigned)((Q.ldc + 255) / 256)), dim3(256), 0, h->stream, h->d_partial, out, R, Q.ldc);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((Q.ldc + 255) / 256), (unsigned)R), dim3(256), h->stream, Q.Csel, Q.ldc, y, h->d_partial, (int64_t)nact, Q.ldc, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(Q.ldc), dim3(256), h->stream, h->d_partial, out, R, Q.ldc);
     }
     // per LP (oracle: eqp_ns, the part that does not depend on the working set): pbar, A pbar, u0 = Z'(p_ref - pbar), Z'q
     void ns_lp_vectors() {
@@ -1553,15 +1540,15 @@ struct Solver {
         const NsEq Q = nsq();
         const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256), gE = (unsigned)((nE + 255) / 256);
         double *pfix = nsv(0), *x = nsv(1), *vz = nsv(2), *yM = nsv(5), *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
-        hipLaunchKernelGGL(k_nseq_pfix, dim3(gN), dim3(256), 0, h->stream, A, pfix, ldn);
+        asmb::launch(k_nseq_pfix, dim3(gN), dim3(256), h->stream, A, pfix, ldn);
         dev.gemv_n_dev(h->d_Ah, pfix, aM);
-        hipLaunchKernelGGL(k_nseq_be, dim3(gE), dim3(256), 0, h->stream, A, X, (const double*)aM, rE);
+        asmb::launch(k_nseq_be, dim3(gE), dim3(256), h->stream, A, X, aM, rE);
         dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
-        hipLaunchKernelGGL(k_ns_rowvec_e, dim3(gM), dim3(256), 0, h->stream, X, (const double*)tE, yM, M);
+        asmb::launch(k_ns_rowvec_e, dim3(gM), dim3(256), h->stream, X, tE, yM, M);
         dev.gemv_t_dev(h->d_Ah, yM, x);
-        hipLaunchKernelGGL(k_nseq_pbar, dim3(gN), dim3(256), 0, h->stream, A, (const double*)pfix, (const double*)x, (const double*)d_zero, Q.pbar, vz, ldn);
+        asmb::launch(k_nseq_pbar, dim3(gN), dim3(256), h->stream, A, pfix, x, d_zero, Q.pbar, vz, ldn);
         dev.gemv_n_dev(h->d_Ah, Q.pbar, Q.tbar);
-        HIPCHK(hipMemsetAsync(Q.u0, 0, 2 * Q.ldc * sizeof(double), h->stream));      // u0 and qh (contiguous)
+        HIPCHK(asmb::fill_async(Q.u0, 0, 2 * Q.ldc * sizeof(double), h->stream));      // u0 and qh (contiguous)
         gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)vz, Q.u0, (int64_t)k, ldn);
         gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)A.q, Q.qh, (int64_t)k, ldn);
     }
@@ -1573,45 +1560,45 @@ struct Solver {
         const NsIdx X = nsX();
         const NsEq Q = nsq();
         const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256), gE = (unsigned)((nE + 255) / 256);
-        hipLaunchKernelGGL(k_nseq_setup, dim3(1), dim3(1024), 0, h->stream, A, cur, X, Q, ldn);
+        asmb::launch(k_nseq_setup, dim3(1), dim3(1024), h->stream, A, cur, X, Q, ldn);
         int cnt[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(cnt, Q.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::copy_async(cnt, Q.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         const int nact = cnt[1];
         if (nact > NS_CMAX * k || nact > h->ns_ccap) return false;             // oracle: eqp_ns returns None - the polish attempt ends (eqp_loop)
         const unsigned gC = (unsigned)((Q.ldc + 255) / 256), gA = (unsigned)((nact + 255) / 256);
         double *t1 = nsv(12), *t2 = nsv(13);
-        HIPCHK(hipMemcpyAsync(Q.u, Q.u0, Q.ldc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemsetAsync(Q.lam, 0, (size_t)h->ns_ccap * sizeof(double), h->stream));
+        HIPCHK(asmb::copy_async(Q.u, Q.u0, Q.ldc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(asmb::fill_async(Q.lam, 0, (size_t)h->ns_ccap * sizeof(double), h->stream));
         if (nact > 0) {
-            hipLaunchKernelGGL(k_nseq_gather, dim3(gC, (unsigned)nact), dim3(256), 0, h->stream, A, cur, X, Q, (const double*)h->d_nsG, h->ns_ldg, k, ldn);
+            asmb::launch(k_nseq_gather, dim3(gC, (unsigned)nact), dim3(256), h->stream, A, cur, X, Q, h->d_nsG, h->ns_ldg, k, ldn);
             const FacBuf& C = h->ns_fC;
             dev.launch_syrk(h->stream, Dev::pick_tile(nact), Q.Csel, Q.ldc, nullptr, 0, nact, (int)Q.ldc, nullptr, nullptr, C.S, C.ld, 0, 0);
             dev.diag_prepare(C, nact, 1, 0.0, 0.0);
             dev.chol(C, nact, 1e-10, false);
             for (int sw = 0; sw < 3; ++sw) {
                 nsq_gemv_n(Q, nact, Q.u, Q.v);                                                                           // C u
-                hipLaunchKernelGGL(k_nseq_sub, dim3(gA), dim3(256), 0, h->stream, (const double*)Q.d, (const double*)Q.v, Q.v, (int64_t)nact);
+                asmb::launch(k_nseq_sub, dim3(gA), dim3(256), h->stream, Q.d, Q.v, Q.v, (int64_t)nact);
                 dev.chol_solve_dev(C, Q.v, Q.w, nact);
                 nsq_gemv_t(Q, nact, Q.w, t1);
-                hipLaunchKernelGGL(k_ns_add, dim3(gC), dim3(256), 0, h->stream, (const double*)Q.u, (const double*)t1, Q.u, Q.ldc);
+                asmb::launch(k_ns_add, dim3(gC), dim3(256), h->stream, Q.u, t1, Q.u, Q.ldc);
                 nsq_gemv_t(Q, nact, Q.lam, t1);                                                                          // C' lam
-                hipLaunchKernelGGL(k_nseq_sub, dim3(gC), dim3(256), 0, h->stream, (const double*)Q.qh, (const double*)t1, t2, Q.ldc);
+                asmb::launch(k_nseq_sub, dim3(gC), dim3(256), h->stream, Q.qh, t1, t2, Q.ldc);
                 nsq_gemv_n(Q, nact, t2, Q.v);
                 dev.chol_solve_dev(C, Q.v, Q.w, nact);
-                hipLaunchKernelGGL(k_ns_add, dim3(gA), dim3(256), 0, h->stream, (const double*)Q.lam, (const double*)Q.w, Q.lam, (int64_t)nact);
+                asmb::launch(k_ns_add, dim3(gA), dim3(256), h->stream, Q.lam, Q.w, Q.lam, (int64_t)nact);
             }
         }
         double *zu = nsv(3), *atw = nsv(4), *wN = nsv(2), *yM = nsv(5), *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         ns_gemv_t_dense(Q.u, k, zu);
-        hipLaunchKernelGGL(k_nseq_p, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, A, cur, Q, (const double*)zu, ldn);
-        hipLaunchKernelGGL(k_nseq_yi, dim3(gM), dim3(256), 0, h->stream, A, X, Q, yM);
+        asmb::launch(k_nseq_p, asmb::blocks(n), dim3(256), h->stream, A, cur, Q, zu, ldn);
+        asmb::launch(k_nseq_yi, dim3(gM), dim3(256), h->stream, A, X, Q, yM);
         dev.gemv_t_dev(h->d_Ah, yM, atw);
-        hipLaunchKernelGGL(k_nseq_w, dim3(gN), dim3(256), 0, h->stream, A, Q, (const double*)atw, wN, ldn);
+        asmb::launch(k_nseq_w, dim3(gN), dim3(256), h->stream, A, Q, atw, wN, ldn);
         dev.gemv_n_dev(h->d_Ah, wN, aM);
-        hipLaunchKernelGGL(k_ns_gather_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)aM, 1.0, rE);
+        asmb::launch(k_ns_gather_e, dim3(gE), dim3(256), h->stream, X, aM, 1.0, rE);
         dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
-        hipLaunchKernelGGL(k_nseq_y, dim3(gM), dim3(256), 0, h->stream, A, X, (const double*)yM, (const double*)tE);
+        asmb::launch(k_nseq_y, dim3(gM), dim3(256), h->stream, A, X, yM, tE);
         dev.gemv_n_dev(h->d_Ah, A.p, A.t);
         dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
         h->stats.eqp += 1;
@@ -1627,10 +1614,10 @@ struct Solver {
         const unsigned gE = (unsigned)((nE + 255) / 256);
         double *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         dev.gemv_n_dev(h->d_Ah, P.rdp, aM);
-        hipLaunchKernelGGL(k_ns_gather_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)aM, 1.0, rE);
+        asmb::launch(k_ns_gather_e, dim3(gE), dim3(256), h->stream, X, aM, 1.0, rE);
         dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
         // P.rdp already contains -A_E'y_E of the multipliers recovered at the end of an earlier stage: the solve gives the correction
-        hipLaunchKernelGGL(k_ns_scatter_e, dim3(gE), dim3(256), 0, h->stream, X, (const double*)tE, P.y, 1);
+        asmb::launch(k_ns_scatter_e, dim3(gE), dim3(256), h->stream, X, tE, P.y, 1);
     }
     // Per iteration (oracle: IPM.run, null-space branch): reduced matrix N = Zt Th Zt' + GI' D_I^-1 GI (an unregularised copy is kept for the
     // refinement sweep), its factor, dpbar = A_EF' S0^-1 (-rp_E) and K dpbar (shared by predictor and corrector)
@@ -1655,12 +1642,13 @@ struct Solver {
             const int64_t pstride = h->ns_fN.ld * h->ns_fN.ld;
             dev.launch_syrk(h->stream, T, h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->d_nsNp, h->ns_fN.ld, 0, 0, -1, nullptr, 0, -1.0, nsplit, pstride);
             dev.end(id);
-            hipLaunchKernelGGL(k_ns_reduce_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, (const double*)h->d_nsNp, nsplit, pstride, h->ns_fN.ld,
-                               h->ns_fN.S, h->d_nsN0, k, k <= ASM_SMALL_USE ? 1 : 0, h->d_diag0, 1e-13, 1e-30);      // (+ k_diag_prepare, mode 0)
+            asmb::launch(k_ns_reduce_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_nsNp, nsplit, pstride, h->ns_fN.ld, h->ns_fN.S, h->d_nsN0, k,
+                         k <= ASM_SMALL_USE ? 1 : 0, h->d_diag0, 1e-13, 1e-30);      // (+ k_diag_prepare, mode 0)
         } else {
             dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
             dev.end(id);
-            hipLaunchKernelGGL(k_ns_copy_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, h->d_nsN0, h->ns_fN.ld, k, k <= ASM_SMALL_USE ? 1 : 0);
+            asmb::launch(k_ns_copy_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->ns_fN.S, h->ns_fN.ld, h->d_nsN0, h->ns_fN.ld, k,
+                         k <= ASM_SMALL_USE ? 1 : 0);
             dev.diag_prepare(h->ns_fN, k, 0, 1e-13, 1e-30);
         }
         dev.chol(h->ns_fN, k, 1e-14, false);
@@ -1669,17 +1657,15 @@ struct Solver {
         if (!ip.ns_e_ready) {
             ip.ns_e_ready = true;
             double *d0 = nsv(2), *zz = nsv(3), *tk = nsv(12);
-            hipLaunchKernelGGL(k_ns_e0, dim3(gN), dim3(256), 0, h->stream, P, (const double*)nsq().pbar, d0, ldn);
+            asmb::launch(k_ns_e0, dim3(gN), dim3(256), h->stream, P, nsq().pbar, d0, ldn);
             gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)d0, tk, (int64_t)k, ldn);
             ns_gemv_t_dense(tk, k, zz);
-            hipLaunchKernelGGL(k_ns_e1, dim3(gN), dim3(256), 0, h->stream, P, (const double*)d0, (const double*)zz, e, ldn);
+            asmb::launch(k_ns_e1, dim3(gN), dim3(256), h->stream, P, d0, zz, e, ldn);
         }
         // (fused launches: negation + clearing of the residual measure; sparse product + its row- / column-wise kernel)
         const double* vals = dev.sparse_vals(h->d_Ah);
-        hipLaunchKernelGGL(k_ns_spmvn_wm_neg, dim3(std::max(gM, gN)), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col, vals, (const double*)e, dpb, ldn,
-                           P.scal + SC_NSERR, X, thI, yM, M);
-        hipLaunchKernelGGL(k_ns_spmvt_kx, dim3((unsigned)((ldn * 8 + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_sc_ptr, (const int*)h->d_sc_row, (const int*)h->d_sc_pos, vals,
-                           (const double*)yM, th, (const double*)dpb, kdpb, lp.n, ldn);
+        asmb::launch(k_ns_spmvn_wm_neg, dim3(std::max(gM, gN)), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, e, dpb, ldn, P.scal + SC_NSERR, X, thI, yM, M);
+        asmb::launch(k_ns_spmvt_kx, asmb::blocks(ldn * 8), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, yM, th, dpb, kdpb, lp.n, ldn);
     }
     // One Newton solve in null-space form (oracle: IPM.run, solve_ns): mode 0 affine, 1 Mehrotra corrector on `base`.  The relative residual of
     // the reduced solve (after its refinement sweep) is accumulated in SC_NSERR.
@@ -1694,42 +1680,39 @@ struct Solver {
         const double* thI = h->d_nsth + ldn;
         const double res = 1.0;
         const double* vals = dev.sparse_vals(h->d_Ah);
-        hipLaunchKernelGGL(k_ns_rhs1_bi, dim3(g), dim3(256), 0, h->stream, P, base, mode, X, thI, res, bI, yM);
-        hipLaunchKernelGGL(k_ns_spmvt_ht, dim3((unsigned)((ldn * 8 + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_sc_ptr, (const int*)h->d_sc_row, (const int*)h->d_sc_pos, vals,
-                           (const double*)yM, th, (const double*)P.hp, (const double*)kdpb, res, ht, v, n, ldn);
+        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), h->stream, P, base, mode, X, thI, res, bI, yM);
+        asmb::launch(k_ns_spmvt_ht, asmb::blocks(ldn * 8), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, yM, th, P.hp, kdpb, res, ht, v, n, ldn);
         gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)v, ru, (int64_t)k, ldn);
         if (k <= ASM_SMALL_USE) {
             // solve, refinement sweep on the unregularised matrix and the residual check in ONE one-workgroup launch
-            hipLaunchKernelGGL(k_ns_reduced_solve, dim3(1), dim3(1024), 0, h->stream, (const double*)h->ns_fN.S, h->ns_fN.ld, (const double*)h->ns_fN.Linv,
-                               (const double*)h->d_nsN0, k, (const double*)ru, du, P.scal + SC_NSERR);
+            asmb::launch(k_ns_reduced_solve, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, h->ns_fN.Linv, h->d_nsN0, k, ru, du, P.scal + SC_NSERR);
         } else {
             dev.chol_solve_dev(h->ns_fN, ru, du, k);
-            hipLaunchKernelGGL(k_ns_symv_res, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, h->stream, (const double*)h->d_nsN0, h->ns_fN.ld, k, (const double*)du, (const double*)ru, rr);
+            asmb::launch(k_ns_symv_res, asmb::blocks(k, 4), dim3(256), h->stream, h->d_nsN0, h->ns_fN.ld, k, du, ru, rr);
             dev.chol_solve_dev(h->ns_fN, rr, dd, k);
-            hipLaunchKernelGGL(k_ns_add, dim3(gK), dim3(256), 0, h->stream, (const double*)du, (const double*)dd, du, (int64_t)k);
-            hipLaunchKernelGGL(k_ns_symv_res, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, h->stream, (const double*)h->d_nsN0, h->ns_fN.ld, k, (const double*)du, (const double*)ru, rr);
-            hipLaunchKernelGGL(k_ns_relres, dim3(1), dim3(1024), 0, h->stream, (const double*)rr, (const double*)ru, k, P.scal + SC_NSERR);
+            asmb::launch(k_ns_add, dim3(gK), dim3(256), h->stream, du, dd, du, (int64_t)k);
+            asmb::launch(k_ns_symv_res, asmb::blocks(k, 4), dim3(256), h->stream, h->d_nsN0, h->ns_fN.ld, k, du, ru, rr);
+            asmb::launch(k_ns_relres, dim3(1), dim3(1024), h->stream, rr, ru, k, P.scal + SC_NSERR);
         }
         if (k <= ASM_SMALL_USE) {
-            hipLaunchKernelGGL(k_gemv_t_small_dp, dim3(gN), dim3(256), 0, h->stream, (const double*)h->d_nsG, h->ns_ldg, k, (const double*)du, P, D, th, (const double*)dpb, res, ldn);
+            asmb::launch(k_gemv_t_small_dp, dim3(gN), dim3(256), h->stream, h->d_nsG, h->ns_ldg, k, du, P, D, th, dpb, res, ldn);
         } else {
             ns_gemv_t_dense(du, k, v);
-            hipLaunchKernelGGL(k_ns_dp, dim3(gN), dim3(256), 0, h->stream, P, D, th, (const double*)dpb, res, (const double*)v, ldn);
+            asmb::launch(k_ns_dp, dim3(gN), dim3(256), h->stream, P, D, th, dpb, res, v, ldn);
         }
-        hipLaunchKernelGGL(k_ns_spmvn_rows, dim3(gM), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col, vals, P, D, X, thI, (const double*)bI, yM);
+        asmb::launch(k_ns_spmvn_rows, dim3(gM), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, P, D, X, thI, bI, yM);
     }
     // out[n] = Zt' u   (Zt dense, k rows of pitch ldg)
     void ns_gemv_t_dense(const double* u, int k, double* out) {
         if (k <= ASM_SMALL_USE) {
-            hipLaunchKernelGGL(k_gemv_t_small, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->d_nsG, h->ns_ldg, k, u, out, h->ldn);
+            asmb::launch(k_gemv_t_small, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_nsG, h->ns_ldg, k, u, out, h->ldn);
             return;
         }
         int64_t R = std::min<int64_t>((k + 31) / 32, ASM_TMAXCHUNKS);
         int64_t chunk = (k + R - 1) / R;
         R = (k + chunk - 1) / chunk;
-        hipLaunchKernelGGL(k_gemv_t_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), 0, h->stream, (const double*)h->d_nsG, h->ns_ldg, u,
-                           h->d_partial, (int64_t)k, h->ldn, chunk);
-        hipLaunchKernelGGL(k_gemv_t_stage2, dim3((unsigned)((h->ldn + 255) / 256)), dim3(256), 0, h->stream, h->d_partial, out, R, h->ldn);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, h->d_nsG, h->ns_ldg, u, h->d_partial, (int64_t)k, h->ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_partial, out, R, h->ldn);
     }
 
     NewtonForm form = NewtonForm::Row;      // form of the current factorisation
@@ -1744,9 +1727,9 @@ struct Solver {
     // out = in through the main factor of a row (column) list: gather in[idx[0:cnt]], solve, scatter back; k_red_scatter gives the
     // ndrop rows didx outside the list out = in / ddrop (pure permutations: none).  The scatter covers `len` rows.
     void solve_list(const int* idx, int cnt, const int* didx, int ndrop, const double* ddrop, const double* in, double* out, int64_t len) {
-        hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, idx, cnt, in, h->d_rce);
+        asmb::launch(k_red_gather, asmb::blocks(cnt), dim3(256), h->stream, idx, cnt, in, h->d_rce);
         dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, cnt);
-        hipLaunchKernelGGL(k_red_scatter, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, h->stream, idx, cnt, (const double*)h->d_rze, didx, ndrop, ddrop, in, out);
+        asmb::launch(k_red_scatter, asmb::blocks(len), dim3(256), h->stream, idx, cnt, h->d_rze, didx, ndrop, ddrop, in, out);
     }
     // out = (approximate) S^-1 in : the Cholesky factor of S (row forms) or Sherman-Morrison-Woodbury through the factor of K (column form)
     void precond(const double* in, double* out) {
@@ -1760,12 +1743,12 @@ struct Solver {
             solve_list(h->d_rowperm, M, h->d_rowperm, 0, h->d_rze, in, out, M);
             return;
         case NewtonForm::Column:
-            hipLaunchKernelGGL(k_col_scale, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, in, h->d_cu, lp.M);      // u = D^-1 r
+            asmb::launch(k_col_scale, dim3(gm), dim3(256), h->stream, h->d_cdinv, in, h->d_cu, lp.M);      // u = D^-1 r
             dev.gemv_t_dev(h->d_Ah, h->d_cu, h->d_ct);                                                                 // Ah' u
             if (h->col_band > 0) solve_list(h->d_colperm, n, h->d_colperm, 0, h->d_rze, h->d_ct, h->d_cv, n);         // K^-1 (columns in banded order)
             else dev.chol_solve_dev(h->main_fac, h->d_ct, h->d_cv, n);                                                 // K^-1
             dev.gemv_n_dev(h->d_Ah, h->d_cv, h->d_cw);                                                                 // Ah v
-            hipLaunchKernelGGL(k_col_finish, dim3(gm), dim3(256), 0, h->stream, h->d_cdinv, h->d_cu, h->d_cw, out, lp.M);
+            asmb::launch(k_col_finish, dim3(gm), dim3(256), h->stream, h->d_cdinv, h->d_cu, h->d_cw, out, lp.M);
             return;
         default:      // Row (the null-space form solves in ns_newton)
             dev.chol_solve_dev(h->main_fac, in, out, M);
@@ -1779,51 +1762,51 @@ struct Solver {
     void ipm_solve(int mode, const IpmDir& base, IpmDir& D, double tp = 0.0, double td = 0.0, int spec = 0) {
         const unsigned g = grid_all();
         
-        hipLaunchKernelGGL(k_ipm_rhs1, dim3(g), dim3(256), 0, h->stream, P, base, mode, tp, td, MCC_BMIN, MCC_BMAX);
+        asmb::launch(k_ipm_rhs1, dim3(g), dim3(256), h->stream, P, base, mode, tp, td, MCC_BMIN, MCC_BMAX);
         dev.gemv_n_dev(h->d_Ah, P.tmpn, P.t1);
-        hipLaunchKernelGGL(k_ipm_rhs2, dim3(g), dim3(256), 0, h->stream, P, mode == 2 ? 0.0 : 1.0);
+        asmb::launch(k_ipm_rhs2, dim3(g), dim3(256), h->stream, P, mode == 2 ? 0.0 : 1.0);
         precond(P.rhs, D.dy);
         if (spec) {
             dev.gemv_t_dev(h->d_Ah, D.dy, d_tN);
-            hipLaunchKernelGGL(k_vec_mul, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, d_tN, P.thp_inv, lp.n);
+            asmb::launch(k_vec_mul, asmb::blocks(lp.n), dim3(256), h->stream, d_tN, P.thp_inv, lp.n);
             dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
-            hipLaunchKernelGGL(k_ipm_res, dim3(1), dim3(1024), 0, h->stream, P, d_sres, D.dy, 0u, spec, 1e-10, PCG_KAPPA * ip.rpmax);
+            asmb::launch(k_ipm_res, dim3(1), dim3(1024), h->stream, P, d_sres, D.dy, 0u, spec, 1e-10, PCG_KAPPA * ip.rpmax);
         } else {
             // preconditioned CG on the unregularised Schur system, the Cholesky factor as preconditioner (oracle: IPM.run.solve).
             // The residual of this system is exactly the primal residual the step leaves behind, hence the tolerance.
             auto applyS = [&](const double* v) {          // d_sres = Ah Th^-1 Ah' v
                 dev.gemv_t_dev(h->d_Ah, v, d_tN);
-                hipLaunchKernelGGL(k_vec_mul, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, d_tN, P.thp_inv, lp.n);
+                asmb::launch(k_vec_mul, asmb::blocks(lp.n), dim3(256), h->stream, d_tN, P.thp_inv, lp.n);
                 dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
             };
             applyS(D.dy);
             unsigned pub = pub_next();
-            hipLaunchKernelGGL(k_ipm_res, dim3(1), dim3(1024), 0, h->stream, P, d_sres, D.dy, pub, 0, 0.0, 0.0);
+            asmb::launch(k_ipm_res, dim3(1), dim3(1024), h->stream, P, d_sres, D.dy, pub, 0, 0.0, 0.0);
             read_scal(pub);
             // the approximate preconditioners (column and reduced row form) get the tighter floor (oracle: IPM.run.solve)
             const bool approx = form == NewtonForm::Column || form == NewtonForm::ReducedRow;
             const double tol = std::max((approx ? 1e-13 : 1e-10) * h->h_scal[SC_RMAX], PCG_KAPPA * ip.rpmax);
             if (h->h_scal[SC_EMAX] > tol) {
                 precond(P.res, d_corr);
-                hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(1024), 0, h->stream, P, d_corr, d_pcg);
+                asmb::launch(k_pcg_start, dim3(1), dim3(1024), h->stream, P, d_corr, d_pcg);
                 bool converged = false;
                 for (int it = 0; it < PCG_MAXIT; ++it) {
                     applyS(d_pcg);
                     pub = pub_next();
-                    hipLaunchKernelGGL(k_pcg_step1, dim3(1), dim3(1024), 0, h->stream, P, d_sres, d_pcg, D.dy, pub);
+                    asmb::launch(k_pcg_step1, dim3(1), dim3(1024), h->stream, P, d_sres, d_pcg, D.dy, pub);
                     read_scal(pub);
                     h->stats_pcg += 1;
                     cg_max = std::max(cg_max, it + 1);
                     if (h->h_scal[SC_STOP] != 0.0) break;
                     if (h->h_scal[SC_EMAX] <= tol) { converged = true; break; }
                     precond(P.res, d_corr);
-                    hipLaunchKernelGGL(k_pcg_step2, dim3(1), dim3(1024), 0, h->stream, P, d_corr, d_pcg);
+                    asmb::launch(k_pcg_step2, dim3(1), dim3(1024), h->stream, P, d_corr, d_pcg);
                 }
                 if (!converged) cg_fail = true;
             }
         }
         dev.gemv_t_dev(h->d_Ah, D.dy, d_tN);
-        hipLaunchKernelGGL(k_ipm_dir, dim3(g), dim3(256), 0, h->stream, P, D, d_tN);
+        asmb::launch(k_ipm_dir, dim3(g), dim3(256), h->stream, P, D, d_tN);
     }
 
     // reduced row form (oracle: IPM.run): inequality rows whose slack term dominates their Schur diagonal stay out of the factor and get a
@@ -1832,7 +1815,7 @@ struct Solver {
         dev.schur_diag(P.thp_inv, h->d_sdiag);
         down(red.dS, P.dS, lp.M);
         down(red.sdiag, h->d_sdiag, lp.M);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         red.kept.clear(); red.diag.clear();
         for (int64_t q = 0; q < lp.M; ++q) {                 // kept rows in the order of the factorisations
             const int64_t i = h->row_band > 0 ? h->row_perm_h[q] : q;
@@ -1865,10 +1848,10 @@ struct Solver {
         case NewtonForm::Column:
             ip.col_iters += 1;
             dim = n;
-            hipLaunchKernelGGL(k_ipm_col_prep, dim3(grid_all()), dim3(256), 0, h->stream, P, IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
+            asmb::launch(k_ipm_col_prep, dim3(grid_all()), dim3(256), h->stream, P, IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
             if (h->col_band > 0) {
                 // columns in their banded order: K built from the structural column pairs, factor and substitutions stop at the band
-                hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_colperm, (int)lp.n, (const double*)h->d_cth, h->d_diag);
+                asmb::launch(k_red_gather, asmb::blocks(lp.n), dim3(256), h->stream, h->d_colperm, (int)lp.n, h->d_cth, h->d_diag);
                 dev.schur_banded_cols_dev(h->d_cdinv, h->d_diag);
             } else {
                 dev.schur_syrk(true, nullptr, n, h->d_cdinv, h->d_cth, f.S, f.ld, Dev::NzFlags::Pattern);
@@ -1881,15 +1864,15 @@ struct Solver {
             vec dE_(dim), dI_(nd);
             for (int a = 0; a < dim; ++a) dE_[a] = red.dS[red.kept[a]];
             for (int b = 0; b < nd; ++b) dI_[b] = red.sdiag[red.diag[b]] + red.dS[red.diag[b]];
-            HIPCHK(hipMemcpyAsync(h->d_idx, red.kept.data(), dim * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_idxI, red.diag.data(), nd * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_diag, dE_.data(), dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_rdI, dI_.data(), nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(h->d_idx, red.kept.data(), dim * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(h->d_idxI, red.diag.data(), nd * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(h->d_diag, dE_.data(), dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(h->d_rdI, dI_.data(), nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
             std::vector<int> cp;
             if (h->row_band > 0) {      // place of every row in the list (-1: not in it)
                 cp.assign(lp.M, -1);
                 for (int a = 0; a < dim; ++a) cp[red.kept[a]] = a;
-                HIPCHK(hipMemcpyAsync(h->d_cpos, cp.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(asmb::copy_async(h->d_cpos, cp.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
             }
             h2d_done(h);      // the host vectors go out of scope
             dev.schur_rows(h->d_idx, h->d_cpos, dim, P.thp_inv, h->d_diag);
@@ -1897,7 +1880,7 @@ struct Solver {
         }
         case NewtonForm::BandedRow:
             // full row form, rows in the banded order: S is built entry by entry, factor and substitutions stop at the band
-            hipLaunchKernelGGL(k_red_gather, dim3((unsigned)((lp.M + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_rowperm, M, (const double*)P.dS, h->d_diag);
+            asmb::launch(k_red_gather, asmb::blocks(lp.M), dim3(256), h->stream, h->d_rowperm, M, P.dS, h->d_diag);
             dev.schur_banded_dev(h->d_rowpos, M, P.thp_inv, h->d_diag);
             break;
         default:      // Row
@@ -1943,7 +1926,7 @@ struct Solver {
                 if (ns_live()) ns_finish_y();
                 vec y;
                 down(y, P.y, lp.M);
-                HIPCHK(hipStreamSynchronize(h->stream));
+                HIPCHK(asmb::sync(h->stream));
                 if (farkas_margin(y) > 1e-9) return ip.status = ASM_INFEASIBLE;
             }
             if (done >= max_more) { if (ns_live()) ns_finish_y(); return ip.status = ASM_OTHER; }
@@ -1954,10 +1937,10 @@ struct Solver {
                 return ip.status = ASM_OTHER;
             }
             if (ns_live())      // null-space form: its theta~ in the same launch (ns_iter_setup)
-                hipLaunchKernelGGL(k_ipm_theta_ns, dim3(std::max(grid_all(), (unsigned)((std::max<int64_t>(h->ldn, h->ns_nIp) + 255) / 256))), dim3(256), 0, h->stream, P, IPM_RHO_P, nsX(), h->d_nsth, h->ldn,
-                                   h->ns_nIp);
+                asmb::launch(k_ipm_theta_ns, dim3(std::max(grid_all(), (unsigned)((std::max<int64_t>(h->ldn, h->ns_nIp) + 255) / 256))), dim3(256), h->stream, P, IPM_RHO_P, nsX(),
+                             h->d_nsth, h->ldn, h->ns_nIp);
             else
-                hipLaunchKernelGGL(k_ipm_theta, dim3(grid_all()), dim3(256), 0, h->stream, P, IPM_RHO_P);
+                asmb::launch(k_ipm_theta, dim3(grid_all()), dim3(256), h->stream, P, IPM_RHO_P);
             form = choose_form();
             newton_factor();
             const bool ns = form == NewtonForm::NullSpace;
@@ -1971,15 +1954,15 @@ struct Solver {
                 cg_max = 0;
                 cg_fail = false;
                 if (ns) ns_newton(0, dirA, dirA); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
-                hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, 0u);
-                hipLaunchKernelGGL(k_ipm_muaff, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, IPM_SIG_EXP);
+                asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirA, 0u);
+                asmb::launch(k_ipm_muaff, dim3(red_grid()), dim3(1024), h->stream, P, dirA, IPM_SIG_EXP);
                 if (ns) ns_newton(1, dirA, dirC); else ipm_solve(1, dirA, dirC, 0.0, 0.0, deferred ? 2 : 0);
                 if (ns && ns_defer) {       // step lengths stay on the device (k_ns_update_dev below)
-                    hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirC, 0u);
+                    asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirC, 0u);
                     return true;
                 }
                 unsigned pub = pub_next();
-                hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirC, pub);
+                asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirC, pub);
                 read_scal(pub);
                 if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
                 ap = h->h_scal[SC_AP]; ad = h->h_scal[SC_AD];
@@ -1988,9 +1971,9 @@ struct Solver {
                     if (std::min(ap, ad) >= 0.9) break;
                     const double tp = std::min(1.0, ap + MCC_DELTA), td = std::min(1.0, ad + MCC_DELTA);
                     ipm_solve(2, dirC, dirA, tp, td, deferred ? 2 : 0);
-                    hipLaunchKernelGGL(k_ipm_diradd, dim3(grid_all()), dim3(256), 0, h->stream, P, dirA, dirC);
+                    asmb::launch(k_ipm_diradd, dim3(grid_all()), dim3(256), h->stream, P, dirA, dirC);
                     pub = pub_next();
-                    hipLaunchKernelGGL(k_ipm_steps, dim3(red_grid()), dim3(1024), 0, h->stream, P, dirA, pub);
+                    asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirA, pub);
                     read_scal(pub);
                     if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
                     const double ap2 = h->h_scal[SC_AP], ad2 = h->h_scal[SC_AD];
@@ -2005,7 +1988,7 @@ struct Solver {
             if (!(defer && solves(true))) solves(false);
             const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
             if (ns && ns_defer) {
-                hipLaunchKernelGGL(k_ns_update_dev, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, eta, nsv(14), h->ldn, h->knobs.ns_rerr);
+                asmb::launch(k_ns_update_dev, dim3(grid_all()), dim3(256), h->stream, P, dirC, eta, nsv(14), h->ldn, h->knobs.ns_rerr);
                 ns_pending = true;
                 continue;
             }
@@ -2017,10 +2000,10 @@ struct Solver {
                 continue;
             }
             if (ns)
-                hipLaunchKernelGGL(k_ns_update, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), nsv(14),
-                                   1.0 - std::min(1.0, eta * ap), h->ldn);
+                asmb::launch(k_ns_update, dim3(grid_all()), dim3(256), h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), nsv(14), 1.0 - std::min(1.0, eta * ap),
+                             h->ldn);
             else
-                hipLaunchKernelGGL(k_ipm_update, dim3(grid_all()), dim3(256), 0, h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad));
+                asmb::launch(k_ipm_update, dim3(grid_all()), dim3(256), h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad));
             if (approx && cg_max > (form == NewtonForm::Column ? COL_MAX_CG : RED_MAX_CG)) drop_form(form);
         }
     }
@@ -2069,29 +2052,29 @@ struct Solver {
     // per LP: reference point of the unique-optimum polish (0 clipped into the box), slack offsets of the rows
     void as_begin_lp() {
         as_bind();
-        hipLaunchKernelGGL(k_as_sl, dim3((unsigned)((lp.M + 255) / 256 + 1)), dim3(256), 0, h->stream, A);
-        hipLaunchKernelGGL(k_as_clip0, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, A.lb, A.ub, (const double*)nullptr, d_zero, lp.n);
+        asmb::launch(k_as_sl, dim3((unsigned)((lp.M + 255) / 256 + 1)), dim3(256), h->stream, A);
+        asmb::launch(k_as_clip0, asmb::blocks(lp.n), dim3(256), h->stream, A.lb, A.ub, nullptr, d_zero, lp.n);
     }
     void as_read() {
-        HIPCHK(hipMemcpyAsync(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::copy_async(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
     }
     void as_copy_sets(int dst, int src) {
-        hipLaunchKernelGGL(k_as_copy_sets, dim3(grid_all()), dim3(256), 0, h->stream, S_[dst], S_[src], lp.M, lp.n, lp.ns);
+        asmb::launch(k_as_copy_sets, dim3(grid_all()), dim3(256), h->stream, S_[dst], S_[src], lp.M, lp.n, lp.ns);
     }
     void as_upload_sets(const ActiveSet& as, int dst) {
         std::vector<int> buf((size_t)(lp.M + lp.n + lp.ns));
         for (int64_t i = 0; i < lp.M; ++i) buf[i] = as.rowst[i];
         for (int64_t j = 0; j < lp.n; ++j) buf[lp.M + j] = as.bst[j];
         for (int64_t k = 0; k < lp.ns; ++k) buf[lp.M + lp.n + k] = as.sst[k];
-        if (lp.M) HIPCHK(hipMemcpyAsync(S_[dst].rowst, buf.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(S_[dst].bst, buf.data() + lp.M, lp.n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        if (lp.ns) HIPCHK(hipMemcpyAsync(S_[dst].sst, buf.data() + lp.M + lp.n, lp.ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (lp.M) HIPCHK(asmb::copy_async(S_[dst].rowst, buf.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(S_[dst].bst, buf.data() + lp.M, lp.n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (lp.ns) HIPCHK(asmb::copy_async(S_[dst].sst, buf.data() + lp.M + lp.n, lp.ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);
     }
     void dcopy(double* dst, const double* src, int64_t cnt) {
-        if (cnt > 0) HIPCHK(hipMemcpyAsync(dst, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        if (cnt > 0) HIPCHK(asmb::copy_async(dst, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     }
     // final answer of the LP (device -> host): p, s, y, z, act and the working set `final_sets`
     void as_download(EqpOut& o, ActiveSet& as) {
@@ -2099,11 +2082,10 @@ struct Solver {
         if (!asmb::in_fiber() && h->d_dl) {
             // outside a batch: packed on the device, one copy into pinned memory (eight copies into pageable vectors cost the host tens of
             // microseconds each, with the GPU idle in between)
-            hipLaunchKernelGGL(k_as_pack, dim3(grid_all()), dim3(256), 0, h->stream, (const double*)A.p, (const double*)A.z, (const double*)A.y, (const double*)A.act,
-                               (const double*)A.s, S_[final_sets], n, M, ns, h->d_dl);
+            asmb::launch(k_as_pack, dim3(grid_all()), dim3(256), h->stream, A.p, A.z, A.y, A.act, A.s, S_[final_sets], n, M, ns, h->d_dl);
             const size_t bytes = (size_t)(2 * n + 2 * M + ns) * sizeof(double) + (size_t)(M + n + ns) * sizeof(int);
-            HIPCHK(hipMemcpyAsync(h->h_dl, h->d_dl, bytes, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            HIPCHK(asmb::copy_async(h->h_dl, h->d_dl, bytes, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::sync(h->stream));
             const double* st = h->h_dl;
             o.p.assign(st, st + n); o.z.assign(st + n, st + 2 * n); o.y.assign(st + 2 * n, st + 2 * n + M); o.act.assign(st + 2 * n + M, st + 2 * n + 2 * M);
             o.s.assign(st + 2 * n + 2 * M, st + 2 * n + 2 * M + ns);
@@ -2117,10 +2099,10 @@ struct Solver {
         }
         down(o.p, A.p, n); down(o.z, A.z, n); down(o.y, A.y, M); down(o.act, A.act, M); down(o.s, A.s, ns);
         std::vector<int> buf((size_t)(M + n + ns));
-        if (M) HIPCHK(hipMemcpyAsync(buf.data(), S_[final_sets].rowst, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(buf.data() + M, S_[final_sets].bst, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (ns) HIPCHK(hipMemcpyAsync(buf.data() + M + n, S_[final_sets].sst, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        if (M) HIPCHK(asmb::copy_async(buf.data(), S_[final_sets].rowst, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(buf.data() + M, S_[final_sets].bst, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (ns) HIPCHK(asmb::copy_async(buf.data() + M + n, S_[final_sets].sst, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         as.rowst.resize(M); as.bst.resize(n); as.sst.resize(ns);
         for (int64_t i = 0; i < M; ++i) as.rowst[i] = (int8_t)buf[i];
         for (int64_t j = 0; j < n; ++j) as.bst[j] = (int8_t)buf[M + j];
@@ -2128,7 +2110,7 @@ struct Solver {
         as.valid = true;
     }
     void identify_dev(int dst) {
-        hipLaunchKernelGGL(k_as_identify, dim3(grid_all()), dim3(256), 0, h->stream, P, S_[dst]);
+        asmb::launch(k_as_identify, dim3(grid_all()), dim3(256), h->stream, P, S_[dst]);
     }
 
     // Equality-constrained solve on the working set `cur` (oracle: eqp / _face_primal_solve / face_dual's solve).
@@ -2139,16 +2121,16 @@ struct Solver {
     bool part_factor = false;   // the main factor is the factor of the partition's Schur matrix (face_polish re-uses it for the rounds on the same sets)
     void as_solve(const AsSets& cur, const double* p_ref, const double* y_ref, int mode, bool reuse_factor = false) {
         const unsigned gA = grid_all(), gM = (unsigned)((lp.M + 255) / 256 + 1), gN = (unsigned)((lp.n + 255) / 256);
-        hipLaunchKernelGGL(k_as_setup, dim3(1), dim3(1024), 0, h->stream, A, cur, p_ref, h->ldn, h->Mp);
-        HIPCHK(hipMemcpyAsync(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        asmb::launch(k_as_setup, dim3(1), dim3(1024), h->stream, A, cur, p_ref, h->ldn, h->Mp);
+        HIPCHK(asmb::copy_async(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         const int nH = h->h_ascnt[AC_NH], nF = h->h_ascnt[AC_NF];
         const bool any_soft = h->h_ascnt[AC_ANYSOFT] != 0;
         as_nH = nH; as_nF = nF;
         if (nH > 0) {
             dev.gemv_n_dev(h->d_Ah, A.pB, A.t);
             if (any_soft) dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
-            hipLaunchKernelGGL(k_as_rhs, dim3(gA), dim3(256), 0, h->stream, A, y_ref);
+            asmb::launch(k_as_rhs, dim3(gA), dim3(256), h->stream, A, y_ref);
         }
         if (nH > 0 && nF > 0) {
             if (!(reuse_factor && part_factor)) {
@@ -2163,27 +2145,27 @@ struct Solver {
             for (int it = 0; it < sweeps; ++it) {
                 if (mode != 2) {
                     dev.gemv_n_dev(h->d_Ah, A.pF, A.t);                                                  // A_HF pF
-                    hipLaunchKernelGGL(k_as_res_p, dim3(gH), dim3(256), 0, h->stream, A);
+                    asmb::launch(k_as_res_p, dim3(gH), dim3(256), h->stream, A);
                     dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
-                    hipLaunchKernelGGL(k_as_scatter_h, dim3(gM), dim3(256), 0, h->stream, A, (const double*)A.u, mode == 1 ? 1 : 0);
+                    asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.u, mode == 1 ? 1 : 0);
                     dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' u
-                    hipLaunchKernelGGL(k_as_add_f, dim3(gN), dim3(256), 0, h->stream, A);
+                    asmb::launch(k_as_add_f, dim3(gN), dim3(256), h->stream, A);
                 }
                 if (mode != 1) {
-                    hipLaunchKernelGGL(k_as_scatter_h, dim3(gM), dim3(256), 0, h->stream, A, (const double*)A.yH, 0);
+                    asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.yH, 0);
                     dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' yH
-                    hipLaunchKernelGGL(k_as_rd, dim3(gN), dim3(256), 0, h->stream, A);
+                    asmb::launch(k_as_rd, dim3(gN), dim3(256), h->stream, A);
                     dev.gemv_n_dev(h->d_Ah, A.rd, A.t);                                                  // A_HF rd
-                    hipLaunchKernelGGL(k_as_gather_h, dim3(gH), dim3(256), 0, h->stream, A);
+                    asmb::launch(k_as_gather_h, dim3(gH), dim3(256), h->stream, A);
                     dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
-                    hipLaunchKernelGGL(k_as_add_yh, dim3(gH), dim3(256), 0, h->stream, A);
+                    asmb::launch(k_as_add_yh, dim3(gH), dim3(256), h->stream, A);
                 }
             }
         }
-        if (nH > 0) hipLaunchKernelGGL(k_as_merge, dim3(gA), dim3(256), 0, h->stream, A, mode != 1 ? 1 : 0);
+        if (nH > 0) asmb::launch(k_as_merge, dim3(gA), dim3(256), h->stream, A, mode != 1 ? 1 : 0);
         dev.gemv_n_dev(h->d_Ah, A.p, A.t);
         if (mode == 1) {
-            hipLaunchKernelGGL(k_as_scatter_h, dim3(gM), dim3(256), 0, h->stream, A, (const double*)A.uacc, 0);
+            asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.uacc, 0);
             dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
         } else {
             dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
@@ -2206,7 +2188,7 @@ struct Solver {
             } else {
                 as_solve(S_[cur], p_ref, y_ref, 0);
             }
-            hipLaunchKernelGGL(k_as_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[cur], S_[nx], S_[prev], have_prev ? 1 : 0, TOL_P, TOL_D);
+            asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, S_[cur], S_[nx], S_[prev], have_prev ? 1 : 0, TOL_P, TOL_D);
             as_read();
             const double pr = h->h_asscal[AS_PR], du = h->h_asscal[AS_DU];
             h->stats.kkt_pr = pr;
@@ -2302,14 +2284,13 @@ struct Solver {
         for (int st = 0; st < FACE_STEPS; ++st) {
             const int k = (int)members.size();
             if (k > 0) {
-                HIPCHK(hipMemcpyAsync(h->d_nsu, u.data(), k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                hipLaunchKernelGGL(k_face_ns_combine, dim3(gN), dim3(256), 0, h->stream, (const double*)p0, (const double*)h->d_Zbuf, ldz,
-                                   (const double*)h->d_nsu, k, A.p, n);
+                HIPCHK(asmb::copy_async(h->d_nsu, u.data(), k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                asmb::launch(k_face_ns_combine, dim3(gN), dim3(256), h->stream, p0, h->d_Zbuf, ldz, h->d_nsu, k, A.p, n);
             } else {
                 dcopy(A.p, p0, n);
             }
             dev.gemv_n_dev(h->d_Ah, A.p, A.t);
-            hipLaunchKernelGGL(k_face_ns_step, dim3(1), dim3(1024), 0, h->stream, A, S_[4], d_pa, d_sa, d_acta, TOL_P);
+            asmb::launch(k_face_ns_step, dim3(1), dim3(1024), h->stream, A, S_[4], d_pa, d_sa, d_acta, TOL_P);
             as_read();                                    // (the host copy of u is no longer needed by the device after this)
             const int nviol = h->h_ascnt[AC_NVIOL];
             if (h->knobs.verbose && (st < 5 || st % 20 == 0 || nviol == 0))
@@ -2321,7 +2302,7 @@ struct Solver {
                 for (int j = 0; j < k; ++j)
                     if (-sign[j] * u[j] > worst) { worst = -sign[j] * u[j]; jw = j; }
                 if (jw < 0) return true;                  // feasible, every multiplier has the right sign: THE least-norm point
-                hipLaunchKernelGGL(k_face_ns_unmark, dim3(1), dim3(64), 0, h->stream, A, S_[4], members[jw].first, members[jw].second);
+                asmb::launch(k_face_ns_unmark, dim3(1), dim3(64), h->stream, A, S_[4], members[jw].first, members[jw].second);
                 dcopy(d_pa, A.p, n); dcopy(d_sa, A.s, ns); dcopy(d_acta, A.act, M);
                 const int last = k - 1;
                 if (jw != last) {
@@ -2335,23 +2316,22 @@ struct Solver {
             }
             const int fam = h->h_ascnt[AC_NCHG];
             const int64_t e = h->h_ascnt[AC_NDIFF];
-            hipLaunchKernelGGL(k_face_ns_col, dim3(1), dim3(1024), 0, h->stream, A, (const double*)h->d_Ah, h->ldn, fam, e, (const double*)p0, (const double*)t0);
+            asmb::launch(k_face_ns_col, dim3(1), dim3(1024), h->stream, A, h->d_Ah, h->ldn, fam, e, p0, t0);
             if (nH0 > 0) {
                 dev.gemv_n_dev(h->d_Ah, A.rd, A.t);
-                hipLaunchKernelGGL(k_as_gather_h, dim3((unsigned)((nH0 + 255) / 256)), dim3(256), 0, h->stream, A);
+                asmb::launch(k_as_gather_h, asmb::blocks(nH0), dim3(256), h->stream, A);
                 dev.chol_solve_dev(h->main_fac, A.v, A.u, nH0);
-                hipLaunchKernelGGL(k_as_scatter_h, dim3(gM), dim3(256), 0, h->stream, A, (const double*)A.u, 0);
+                asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.u, 0);
                 dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
             } else {
-                HIPCHK(hipMemsetAsync(A.tN, 0, h->ldn * sizeof(double), h->stream));
+                HIPCHK(asmb::fill_async(A.tN, 0, h->ldn * sizeof(double), h->stream));
             }
             double* znew = h->d_Zbuf + (int64_t)k * ldz;
-            hipLaunchKernelGGL(k_face_ns_z, dim3(gN), dim3(256), 0, h->stream, A, znew);
-            hipLaunchKernelGGL(k_gemv_n, dim3((unsigned)((k + 1 + 3) / 4)), dim3(256), 0, h->stream, (const double*)h->d_Zbuf, ldz, (const double*)znew,
-                               h->d_nsdots, (int64_t)(k + 1), ldz);
-            HIPCHK(hipMemcpyAsync(h->h_nsdots, h->d_nsdots, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            asmb::launch(k_face_ns_z, dim3(gN), dim3(256), h->stream, A, znew);
+            asmb::launch(k_gemv_n, asmb::blocks(k + 1, 4), dim3(256), h->stream, h->d_Zbuf, ldz, znew, h->d_nsdots, (int64_t)(k + 1), ldz);
+            HIPCHK(asmb::copy_async(h->h_nsdots, h->d_nsdots, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::copy_async(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::sync(h->stream));
             const double zz = h->h_nsdots[k], cc = h->h_asscal[AS_PR];
             if (!(zz > 1e-10 * cc)) return false;        // dependent on the working set although it blocks
             vec trow(h->h_nsdots, h->h_nsdots + k + 1);
@@ -2370,9 +2350,9 @@ struct Solver {
     int face_polish() {
         if (h->test_no_polish) return 0;
         const int64_t n = lp.n, M = lp.M, ns = lp.ns;
-        hipLaunchKernelGGL(k_as_clip0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, A.lb, A.ub, (const double*)P.p, d_pref, n);
+        asmb::launch(k_as_clip0, asmb::blocks(n), dim3(256), h->stream, A.lb, A.ub, P.p, d_pref, n);
         as_solve(S_[3], d_pref, P.y, 0);
-        hipLaunchKernelGGL(k_as_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
+        asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
         as_read();
         h->stats.kkt_pr = h->h_asscal[AS_PR];
         h->stats.kkt_du = h->h_asscal[AS_DU];
@@ -2386,7 +2366,7 @@ struct Solver {
         as_copy_sets(5, 3);
         for (int r = 0; r < FACE_BULK; ++r) {
             as_solve(S_[5], nullptr, nullptr, 2, r == 0);
-            hipLaunchKernelGGL(k_face_dual_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[5], FACE_TOL_M);
+            asmb::launch(k_face_dual_finish, dim3(1), dim3(1024), h->stream, A, S_[5], FACE_TOL_M);
             as_read();
             if (h->knobs.verbose) std::fprintf(stderr, "[asm] face dual %d: nH %d nF %d viol %d\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL]);
             if (h->h_ascnt[AC_NVIOL] == 0) { okd = true; break; }
@@ -2398,7 +2378,7 @@ struct Solver {
             as_copy_sets(4, 3);
             for (int r = 0; r < FACE_BULK; ++r) {
                 as_solve(S_[4], nullptr, nullptr, 1, r == 0);
-                hipLaunchKernelGGL(k_face_primal_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 0);
+                asmb::launch(k_face_primal_finish, dim3(1), dim3(1024), h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 0);
                 as_read();
                 if (h->knobs.verbose) std::fprintf(stderr, "[asm] face primal bulk %d: nH %d nF %d viol %d rel %d hres %.2e\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL], h->h_ascnt[AC_NREL], h->h_asscal[AS_HARDRES]);
                 if (h->h_asscal[AS_HARDRES] > TOL_P) break;            // over-determined working set
@@ -2410,7 +2390,7 @@ struct Solver {
             if (!okp && face_primal_anchored()) {
                 // the answer is the least-norm point of the FINAL working set, computed like any other (fresh factorisation)
                 as_solve(S_[4], nullptr, nullptr, 1);
-                hipLaunchKernelGGL(k_face_primal_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 1);
+                asmb::launch(k_face_primal_finish, dim3(1), dim3(1024), h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 1);
                 as_read();
                 okp = h->h_asscal[AS_HARDRES] <= TOL_P && h->h_ascnt[AC_NVIOL] == 0;
             }
@@ -2418,7 +2398,7 @@ struct Solver {
         part_factor = false;
         if (okp && okd) {
             dcopy(A.y, d_yf, M); dcopy(A.z, d_zf, n);      // (p, s, act) are the primal stage's last solve; y, z come from the dual stage
-            hipLaunchKernelGGL(k_face_kkt, dim3(1), dim3(1024), 0, h->stream, A, S_[5]);
+            asmb::launch(k_face_kkt, dim3(1), dim3(1024), h->stream, A, S_[5]);
             as_read();
             h->stats.kkt_pr = h->h_asscal[AS_PR];
             h->stats.kkt_du = h->h_asscal[AS_DU];
@@ -2445,7 +2425,7 @@ struct Solver {
         ipm_run(1e-8, IPM_MAXIT);
         vec y1;
         down(y1, P.y, lp.M);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         int its = ip.iters;
         lp = saved;
         ip = saved_ip;
@@ -2460,7 +2440,7 @@ struct Solver {
     void stats_measures() { h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap; }
     // best-iterate safeguard, second half (oracle: solve_scaled): the snapshot comes back, is measured and its partition identified
     void restore_best() {
-        hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
+        asmb::launch(k_ipm_snapshot, dim3(grid_all()), dim3(256), h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
         ipm_measures();
         stats_measures();
         h->stats.restored = 1;
@@ -2494,7 +2474,7 @@ struct Solver {
             h->stats.ns_dim = ns_lp ? ns_k : 0;
             h->stats.ns_cold = (ns_lp && (had == 0 || ns_was_cold)) ? 1 : 0;
             if (h->knobs.verbose) {
-                HIPCHK(hipStreamSynchronize(h->stream));
+                HIPCHK(asmb::sync(h->stream));
                 std::fprintf(stderr, "[asm] null-space set-up: %s, k = %d, %s basis columns, %.2f ms\n", ns_lp ? "ok" : "not usable", ns_k, ns_was_cold ? "fresh" : "retained", now_ms() - t0);
             }
         }
@@ -2539,7 +2519,7 @@ struct Solver {
                 m_last = std::max(ip.pinf, std::max(ip.dinf, ip.gap));
                 double* e_ns = ip.ns_e_ready ? nsv(14) : nullptr;      // (set only by iterations in null-space form)
                 if (m_last < best_m) {
-                    hipLaunchKernelGGL(k_ipm_snapshot, dim3(grid_all()), dim3(256), 0, h->stream, P, h->d_ipm_snap, e_ns, h->ldn, h->Mp, h->nsp, 0);
+                    asmb::launch(k_ipm_snapshot, dim3(grid_all()), dim3(256), h->stream, P, h->d_ipm_snap, e_ns, h->ldn, h->Mp, h->nsp, 0);
                     best_m = m_last; have_snap = true; snap_e = e_ns != nullptr;
                 }
             }
@@ -2557,7 +2537,7 @@ struct Solver {
             }
             double t1 = now_ms();
             identify_dev(3);
-            if (h->knobs.verbose) { HIPCHK(hipStreamSynchronize(h->stream)); std::fprintf(stderr, "[asm] stage %d identify %.2f ms\n", stage, now_ms() - t1); }
+            if (h->knobs.verbose) { HIPCHK(asmb::sync(h->stream)); std::fprintf(stderr, "[asm] stage %d identify %.2f ms\n", stage, now_ms() - t1); }
             have_sets = true;
             bool tried_ln = false;
             if (ns_lp) {
@@ -2628,15 +2608,16 @@ struct Solver {
             conv = true;
         }
         if (conv) {
-            hipLaunchKernelGGL(k_as_clip0, dim3((unsigned)((lp.n + 255) / 256)), dim3(256), 0, h->stream, A.lb, A.ub, (const double*)P.p, A.p, lp.n);
+            asmb::launch(k_as_clip0, asmb::blocks(lp.n), dim3(256), h->stream, A.lb, A.ub, P.p, A.p, lp.n);
             dcopy(A.y, P.y, lp.M);
             if (lp.ns) {
-                hipLaunchKernelGGL(k_as_smax, dim3((unsigned)((lp.ns + 255) / 256)), dim3(256), 0, h->stream, (const double*)P.s, A.slo, A.s, lp.ns);
-                hipLaunchKernelGGL(k_as_sl_values, dim3((unsigned)((lp.M + 255) / 256 + 1)), dim3(256), 0, h->stream, A);      // the tail kernel must not recompute slacks from a stale working set
+                asmb::launch(k_as_smax, asmb::blocks(lp.ns), dim3(256), h->stream, P.s, A.slo, A.s, lp.ns);
+                asmb::launch(k_as_sl_values, dim3((unsigned)((lp.M + 255) / 256 + 1)), dim3(256), h->stream,
+                             A);      // the tail kernel must not recompute slacks from a stale working set
             }
             dev.gemv_n_dev(h->d_Ah, A.p, A.t);
             dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
-            hipLaunchKernelGGL(k_as_finish, dim3(1), dim3(1024), 0, h->stream, A, S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
+            asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
             as_read();
             final_sets = 3;
             h->stats.path = 10;
@@ -2690,9 +2671,9 @@ void reset_warm(asm_handle* h, bool keep_ns_J) {
 void check_panel_timeout(asm_handle* h) {
     if (!h->d_ptmo) return;
     unsigned tmo = 0;
-    HIPCHK(hipMemcpy(&tmo, h->d_ptmo, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCHK(asmb::copy(&tmo, h->d_ptmo, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (tmo != 0) {
-        HIPCHK(hipMemset(h->d_ptmo, 0, sizeof(unsigned)));      // reported once: the handle stays usable
+        HIPCHK(asmb::fill(h->d_ptmo, 0, sizeof(unsigned)));      // reported once: the handle stays usable
         throw HipError("k_chol_panel: a workgroup timed out waiting for a producer (grid not resident?)");
     }
 }
@@ -2957,7 +2938,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.upload(h->d_perm, perm.data(), nnz); P.upload(h->d_ustart, ustart.data(), h->nu + 1);
         P.upload(h->d_uoff, uoff.data(), h->nu); P.upload(h->d_adjoff, adjoff.data(), h->nu);
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(asmb::sync(h->stream));
     h->last = ActiveSet();
     reset_warm(h, false);
     std::memset(&h->stats, 0, sizeof(h->stats));
@@ -2968,7 +2949,7 @@ void do_upload(asm_handle* h, const double* dE, const double* df, double f, cons
     if ((h->nnz > 0 && !dE) || !df || (h->m > 0 && !E) || !x_k) throw std::invalid_argument("asm_sublp_upload: null pointer");
     if (!h->setup_done) throw std::logic_error("asm_sublp_setup has not been called");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h2d_done(h);
     h->J_valid = false;
     h->df.assign(df, df + h->n); h->E.assign(E, E + h->m); h->x_k.assign(x_k, x_k + h->n);
@@ -2986,10 +2967,10 @@ void do_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, const 
     h->c_lb.assign(c_lb, c_lb + h->m); h->c_ub.assign(c_ub, c_ub + h->m);
     h->v_lb.assign(v_lb, v_lb + h->n); h->v_ub.assign(v_ub, v_ub + h->n);
     if (h->ev_ready) {              // the reductions' copy of the bounds
-        HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + h->n, h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m + h->n, h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
     }
     // the retained working sets and the basis Z belong to the old instance; the basis COLUMNS of the null-space form are kept - the
     // pattern is the same, and a set that no longer spans null(A_EF) is detected and re-selected by the next LP (Solver::ns_setup)
@@ -3033,7 +3014,7 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
     const double tr0 = Solver::now_ms();
     auto lap = [&](const char* what) {
         if (!h->knobs.verbose) return;
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         static thread_local double last = 0.0;
         const double t = Solver::now_ms();
         std::fprintf(stderr, "[asm] solve_raw %-10s +%.2f ms\n", what, t - (last > tr0 ? last : tr0));
@@ -3184,8 +3165,8 @@ void do_lp_solve(asm_handle* h, const double* dE, const double* q, const double*
     const int64_t n = h->n, M = h->M;
     for (int64_t j = 0; j < n; ++j)
         if (!(lb[j] > -INF && ub[j] < INF && lb[j] <= ub[j])) throw std::invalid_argument("asm_lp_solve: every structural column needs a finite box (the trust region)");
-    HIPCHK(hipMemcpyAsync(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(asmb::copy_async(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::sync(h->stream));
     h->J_valid = false;
     LpRaw L;
     L.slacks = use_slacks != 0;
@@ -3248,29 +3229,28 @@ void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool ful
     const FnStore& F = h->ev_F;
     const unsigned nt = (unsigned)ntrial;
     if (F.n_rows > 0)
-        hipLaunchKernelGGL(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), 0, h->stream, F, xd, Ed, h->d_dE, full ? 1 : 0, ldx, ldE);
+        asmb::launch(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), h->stream, F, xd, Ed, h->d_dE, full ? 1 : 0, ldx, ldE);
     const ExprTape& X = h->ev_X;
     const bool expr_obj = h->ev_nlp_kind == ASM_NLP_EXPR && X.T > 0;     // the expression objective replaces the store's objective row
     if (!expr_obj) {
-        hipLaunchKernelGGL(k_fn_objective, dim3(nt), dim3(256), 0, h->stream, F, xd, fd, ldx);
-        if (full) hipLaunchKernelGGL(k_fn_gradient, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, F, xd, h->d_ev_df);
+        asmb::launch(k_fn_objective, dim3(nt), dim3(256), h->stream, F, xd, fd, ldx);
+        if (full) asmb::launch(k_fn_gradient, asmb::blocks(h->n), dim3(256), h->stream, F, xd, h->d_ev_df);
     }
     if (h->ev_nlp_kind == ASM_NLP_EXPR) {
         if (X.R > 0)
-            hipLaunchKernelGGL(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), 0, h->stream, X, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz,
-                               full ? 1 : 0, ldx, ldE);
+            asmb::launch(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), h->stream, X, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
         if (expr_obj) {
-            hipLaunchKernelGGL(k_nlp_expr_terms, dim3((unsigned)((X.T + 255) / 256), nt), dim3(256), 0, h->stream, X, xd, full ? 1 : 0, ldx);
-            hipLaunchKernelGGL(k_nlp_expr_objective, dim3(nt), dim3(64), 0, h->stream, X, F.objective_scale, fd);
-            if (full) hipLaunchKernelGGL(k_nlp_expr_gradient, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, X, F.objective_scale, h->d_ev_df);
+            asmb::launch(k_nlp_expr_terms, dim3((unsigned)((X.T + 255) / 256), nt), dim3(256), h->stream, X, xd, full ? 1 : 0, ldx);
+            asmb::launch(k_nlp_expr_objective, dim3(nt), dim3(64), h->stream, X, F.objective_scale, fd);
+            if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->n), dim3(256), h->stream, X, F.objective_scale, h->d_ev_df);
         }
     } else if (h->ev_nlp_kind == 1) {
         const int64_t nl = h->ev_nlp_rows / 4;
-        hipLaunchKernelGGL(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), 0, h->stream, (const int64_t*)h->d_ev_ipar, (const double*)h->d_ev_dpar,
-                           xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
+        asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, h->d_ev_ipar, h->d_ev_dpar, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz,
+                     full ? 1 : 0, ldx, ldE);
     } else if (h->ev_nlp_kind == 2) {
-        hipLaunchKernelGGL(k_nlp_dense_quadratic, dim3((unsigned)((h->ev_nlp_rows + 3) / 4), nt), dim3(256), 0, h->stream, (const double*)h->d_ev_dpar,
-                           h->ev_nlp_rows, h->n, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
+        asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((h->ev_nlp_rows + 3) / 4), nt), dim3(256), h->stream, h->d_ev_dpar, h->ev_nlp_rows, h->n, xd, Ed, h->d_dE, F.n_rows,
+                     h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
     }
 }
 SlpVecs ev_vecs(asm_handle* h, const double* lam, const double* mU, const double* mL, const double* jtl, const double* rown) {
@@ -3318,8 +3298,8 @@ int asm_create(int device, asm_handle** out) {
 int asm_destroy(asm_handle* h) {
     if (!h) return ASM_ERR_ARG;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->stream2) (void)hipStreamSynchronize(h->stream2);   // look-ahead chain may still be running after an exception
+    if (h->stream) (void)asmb::sync(h->stream);
+    if (h->stream2) (void)asmb::sync(h->stream2);   // look-ahead chain may still be running after an exception
     for (auto& r : h->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
     free_device(h);
@@ -3446,7 +3426,7 @@ static void do_jac_row_norms(asm_handle* h, double* out_m) {
     Dev d(h);
     d.assemble();
     if (h->m == 0) return;
-    hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((h->m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, h->d_vecM, h->m, h->ldn);
+    asmb::launch(k_row_norms, asmb::blocks(h->m, 4), dim3(256), h->stream, h->d_J, h->ldn, h->d_vecM, h->m, h->ldn);
     d.d2h(out_m, h->d_vecM, h->m);
 }
 
@@ -3466,7 +3446,7 @@ int asm_kt_residuals(asm_handle* h, const double* df, const double* lambda, cons
         for (int64_t i = 0; i < m; ++i) lam[i] = lambda[i];
         d.gemv_t(h->d_J, lam.data(), jtl.data());
         if (m > 0) {
-            hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, h->d_vecM, m, h->ldn);
+            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_J, h->ldn, h->d_vecM, m, h->ldn);
             d.d2h(rn.data(), h->d_vecM, m);
         }
         // common.jl:38-43
@@ -3627,10 +3607,10 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     }
     // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
     P.zeroed(h->d_ev_vecs, 2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
-    HIPCHK(hipMemcpy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_ev_vecs + 2 * h->m + n, h->v_ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m + n, h->v_ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
     if (!h->h_ev) h->mem.alloc(h->h_ev, 4 * (n + m) + 64, BufPool::PINNED);
     h->ev_ready = true;
 }
@@ -3652,13 +3632,13 @@ static void do_eval_functions(asm_handle* h, const double* x, double* f, double*
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n, m = h->m;
     std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(hipMemcpyAsync(h->d_ev_x, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(h->d_ev_x, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     ev_launch(h, h->d_ev_x, h->d_ev_E, h->d_ev_f, true);
     double* st = h->h_ev + n;
-    HIPCHK(hipMemcpyAsync(st, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (m) HIPCHK(hipMemcpyAsync(st + n, h->d_ev_E, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(st + n + m, h->d_ev_f, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(asmb::copy_async(st, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (m) HIPCHK(asmb::copy_async(st + n, h->d_ev_E, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::copy_async(st + n + m, h->d_ev_f, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
     std::memcpy(df, st, n * sizeof(double));
     if (m) std::memcpy(E, st + n, m * sizeof(double));
     *f = st[n + m];
@@ -3679,7 +3659,7 @@ static void do_set_data(asm_handle* h, int64_t offset, int64_t count, const doub
         throw std::invalid_argument("asm_eval_set_data: null pointer or a range outside [0, n_dpar = " + std::to_string(h->ev_n_dpar) + ")");
     if (count == 0) return;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_ev_dpar + offset, values, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(h->d_ev_dpar + offset, values, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h2d_done(h);
     if (h->ev_dirty_hi == h->ev_dirty_lo) { h->ev_dirty_lo = offset; h->ev_dirty_hi = offset + count; }
     else { h->ev_dirty_lo = std::min(h->ev_dirty_lo, offset); h->ev_dirty_hi = std::max(h->ev_dirty_hi, offset + count); }
@@ -3699,17 +3679,15 @@ static void do_data_gradient(asm_handle* h, const double* x, const double* lambd
     HIPCHK(hipSetDevice(h->device));
     const ExprTape& X = h->ev_X;
     std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(hipMemcpyAsync(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (X.R > 0) {
         std::memcpy(h->h_ev + n, lambda + h->ev_F.n_rows, X.R * sizeof(double));
-        HIPCHK(hipMemcpyAsync(h->d_ev_lam, h->h_ev + n, X.R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(h->d_ev_lam, h->h_ev + n, X.R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    hipLaunchKernelGGL(k_nlp_expr_const_adj, dim3((unsigned)((X.R + X.T + 255) / 256)), dim3(256), 0, h->stream, X, (const double*)h->d_ev_xt,
-                       (const double*)h->d_ev_lam, h->ev_F.objective_scale, h->d_ev_cocc);
-    hipLaunchKernelGGL(k_nlp_expr_data_gather, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->stream, (const int64_t*)h->d_ev_cptr,
-                       (const double*)h->d_ev_cocc, nd, h->d_ev_dgrad);
-    HIPCHK(hipMemcpyAsync(h->h_ev_dgrad, h->d_ev_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    asmb::launch(k_nlp_expr_const_adj, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, h->d_ev_xt, h->d_ev_lam, h->ev_F.objective_scale, h->d_ev_cocc);
+    asmb::launch(k_nlp_expr_data_gather, asmb::blocks(nd), dim3(256), h->stream, h->d_ev_cptr, h->d_ev_cocc, nd, h->d_ev_dgrad);
+    HIPCHK(asmb::copy_async(h->h_ev_dgrad, h->d_ev_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
     std::memcpy(out, h->h_ev_dgrad, nd * sizeof(double));
 }
 
@@ -3720,12 +3698,12 @@ static void do_eval_constraints(asm_handle* h, const double* x, double* f, doubl
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n, m = h->m;
     std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(hipMemcpyAsync(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
     double* st = h->h_ev + n;
-    if (m) HIPCHK(hipMemcpyAsync(st, h->d_ev_Et, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(st + m, h->d_ev_f + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (m) HIPCHK(asmb::copy_async(st, h->d_ev_Et, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::copy_async(st + m, h->d_ev_f + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
     if (m) std::memcpy(E, st, m * sizeof(double));
     *f = st[m];
 }
@@ -3739,7 +3717,7 @@ int asm_eval_jacobian_values(asm_handle* h, double* dE_out) {
         if (!dE_out) throw std::invalid_argument("asm_eval_jacobian_values: null pointer");
         if (!h->setup_done) throw std::logic_error("asm_eval_jacobian_values: asm_sublp_setup first");
         HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipMemcpy(dE_out, h->d_dE, h->nnz * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(dE_out, h->d_dE, h->nnz * sizeof(double), hipMemcpyDeviceToHost));
     });
 }
 
@@ -3767,20 +3745,20 @@ static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult
     if (m) std::memcpy(st, lambda, m * sizeof(double));
     std::memcpy(st + m, mult_x_U, n * sizeof(double));
     std::memcpy(st + m + n, mult_x_L, n * sizeof(double));
-    HIPCHK(hipMemcpyAsync(lam, st, (m + 2 * n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(lam, st, (m + 2 * n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     // J' lambda over the first m rows: lambda padded with zeros on the extra range rows
-    HIPCHK(hipMemsetAsync(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
-    if (m) HIPCHK(hipMemcpyAsync(h->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(asmb::fill_async(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
+    if (m) HIPCHK(asmb::copy_async(h->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     d.launch_gemv_t(h->d_J, h->d_vecM, jtl);
     if (m) {
         if (const double* vJ = d.sparse_vals(h->d_J))      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
-            hipLaunchKernelGGL(k_sp_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, (const int*)h->d_sp_ptr, (const int*)h->d_sp_col, vJ, rown, m);
+            asmb::launch(k_sp_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vJ, rown, m);
         else
-            hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, h->stream, h->d_J, h->ldn, rown, m, h->ldn);
+            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_J, h->ldn, rown, m, h->ldn);
     }
-    hipLaunchKernelGGL(k_slp_norms, dim3(1), dim3(1024), 0, h->stream, ev_vecs(h, lam, mU, mL, jtl, rown), outd);
-    HIPCHK(hipMemcpyAsync(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    asmb::launch(k_slp_norms, dim3(1), dim3(1024), h->stream, ev_vecs(h, lam, mU, mL, jtl, rown), outd);
+    HIPCHK(asmb::copy_async(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
     for (int k = 0; k < RN_COUNT; ++k) out4[k] = st[k];
     d.resolve_timing();
 }
@@ -3803,19 +3781,19 @@ int asm_slp_merit(asm_handle* h, int mode, double alpha, const double* p, const 
         double* st = h->h_ev;
         if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
         std::memcpy(st + 3 * m, p, n * sizeof(double));
-        HIPCHK(hipMemcpyAsync(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
         const double* Et = h->d_ev_E;
         const double* ft = h->d_ev_f;
         if (mode == 0 && alpha != 0.0) {
-            hipLaunchKernelGGL(k_axpy_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->d_ev_x, alpha, (const double*)pd, h->d_ev_xt, n);
+            asmb::launch(k_axpy_out, asmb::blocks(n), dim3(256), h->stream, h->d_ev_x, alpha, pd, h->d_ev_xt, n);
             ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
             Et = h->d_ev_Et;
             ft = h->d_ev_f + 1;
         }
-        hipLaunchKernelGGL(k_slp_merit, dim3(1), dim3(1024), 0, h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), Et, (const double*)nud,
-                           (const double*)psd, (const double*)pd, alpha, feasibility, prim_infeas, ft, mode, outd, TrialAlphas(), (int64_t)0);
-        HIPCHK(hipMemcpyAsync(st, outd, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        asmb::launch(k_slp_merit, dim3(1), dim3(1024), h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), Et, nud, psd, pd, alpha, feasibility, prim_infeas, ft,
+                     mode, outd, TrialAlphas(), (int64_t)0);
+        HIPCHK(asmb::copy_async(st, outd, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         *out = st[0];
     });
 }
@@ -3837,7 +3815,7 @@ int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const 
         double* st = h->h_ev;
         if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
         std::memcpy(st + 3 * m, p, n * sizeof(double));
-        HIPCHK(hipMemcpyAsync(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
         const SlpVecs V = ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr);
         constexpr int CH = 8;
         double alpha = 1.0, a[CH];
@@ -3849,12 +3827,11 @@ int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const 
             TrialAlphas al;
             for (int t = 0; t < CH; ++t) { a[t] = al.a[t] = alpha; alpha *= tau; }
             const int64_t ldx = round_up(n, 32), ldE = round_up(std::max<int64_t>(m, 1), 32);
-            hipLaunchKernelGGL(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), 0, h->stream, (const double*)h->d_ev_x, al, (const double*)pd, h->d_ev_xt, n, ldx);
+            asmb::launch(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), h->stream, h->d_ev_x, al, pd, h->d_ev_xt, n, ldx);
             ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false, CH, ldx, ldE);
-            hipLaunchKernelGGL(k_slp_merit, dim3(CH), dim3(1024), 0, h->stream, V, (const double*)h->d_ev_Et, (const double*)nud, (const double*)psd, (const double*)pd, 0.0,
-                               feasibility, prim_infeas, (const double*)(h->d_ev_f + 1), 0, outd, al, ldE);
-            HIPCHK(hipMemcpyAsync(st, outd, CH * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            asmb::launch(k_slp_merit, dim3(CH), dim3(1024), h->stream, V, h->d_ev_Et, nud, psd, pd, 0.0, feasibility, prim_infeas, h->d_ev_f + 1, 0, outd, al, ldE);
+            HIPCHK(asmb::copy_async(st, outd, CH * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::sync(h->stream));
             for (int t = 0; t < CH && *ok_out < 0; ++t) {
                 trials += 1;
                 if (!(st[t] > phi0 + eta * a[t] * D)) { *ok_out = 1; *alpha_out = a[t]; if (phi_out) *phi_out = st[t]; }
@@ -3876,12 +3853,12 @@ static void slp_merit_and_search(asm_handle* h, const double* p, const double* n
     double* st = h->h_ev;
     if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
     std::memcpy(st + 3 * m, p, n * sizeof(double));
-    HIPCHK(hipMemcpyAsync(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const SlpVecs V = ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr);
     constexpr int CH = 8;
     for (int mode = 0; mode < 2; ++mode)
-        hipLaunchKernelGGL(k_slp_merit, dim3(1), dim3(1024), 0, h->stream, V, (const double*)h->d_ev_E, (const double*)nud, (const double*)psd, (const double*)pd, 0.0, feasibility,
-                           prim_infeas, (const double*)h->d_ev_f, mode, outd + CH + mode, TrialAlphas(), (int64_t)0);
+        asmb::launch(k_slp_merit, dim3(1), dim3(1024), h->stream, V, h->d_ev_E, nud, psd, pd, 0.0, feasibility, prim_infeas, h->d_ev_f, mode, outd + CH + mode, TrialAlphas(),
+                     (int64_t)0);
     double alpha = 1.0, a[CH], phi0 = 0.0, D = 0.0;
     int trials = 0;
     *ok_out = -1;
@@ -3890,12 +3867,11 @@ static void slp_merit_and_search(asm_handle* h, const double* p, const double* n
         TrialAlphas al;
         for (int t = 0; t < CH; ++t) { a[t] = al.a[t] = alpha; alpha *= tau; }
         const int64_t ldx = round_up(n, 32), ldE = round_up(std::max<int64_t>(m, 1), 32);
-        hipLaunchKernelGGL(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), 0, h->stream, (const double*)h->d_ev_x, al, (const double*)pd, h->d_ev_xt, n, ldx);
+        asmb::launch(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), h->stream, h->d_ev_x, al, pd, h->d_ev_xt, n, ldx);
         ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false, CH, ldx, ldE);
-        hipLaunchKernelGGL(k_slp_merit, dim3(CH), dim3(1024), 0, h->stream, V, (const double*)h->d_ev_Et, (const double*)nud, (const double*)psd, (const double*)pd, 0.0,
-                           feasibility, prim_infeas, (const double*)(h->d_ev_f + 1), 0, outd, al, ldE);
-        HIPCHK(hipMemcpyAsync(st, outd, (CH + (round == 0 ? 2 : 0)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        asmb::launch(k_slp_merit, dim3(CH), dim3(1024), h->stream, V, h->d_ev_Et, nud, psd, pd, 0.0, feasibility, prim_infeas, h->d_ev_f + 1, 0, outd, al, ldE);
+        HIPCHK(asmb::copy_async(st, outd, (CH + (round == 0 ? 2 : 0)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
         if (round == 0) { phi0 = st[CH]; D = st[CH + 1]; }
         for (int t = 0; t < CH && *ok_out < 0; ++t) {
             trials += 1;
@@ -3916,14 +3892,13 @@ static void slp_tr_step_quality(asm_handle* h, const double* p, const double* nu
     double* st = h->h_ev;
     if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
     std::memcpy(st + 3 * m, p, n * sizeof(double));
-    HIPCHK(hipMemcpyAsync(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_axpy_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->d_ev_x, 1.0, (const double*)pd, h->d_ev_xt, n);
+    HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    asmb::launch(k_axpy_out, asmb::blocks(n), dim3(256), h->stream, h->d_ev_x, 1.0, pd, h->d_ev_xt, n);
     ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
-    hipLaunchKernelGGL(k_slp_tr_quality, dim3(3), dim3(1024), 0, h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), (const double*)h->d_ev_Et,
-                       (const double*)nud, (const double*)psd, (const double*)pd, feasibility, prim_infeas, (const double*)h->d_ev_f,
-                       (const double*)(h->d_ev_f + 1), outd);
-    HIPCHK(hipMemcpyAsync(st, outd, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    asmb::launch(k_slp_tr_quality, dim3(3), dim3(1024), h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), h->d_ev_Et, nud, psd, pd, feasibility, prim_infeas,
+                 h->d_ev_f, h->d_ev_f + 1, outd);
+    HIPCHK(asmb::copy_async(st, outd, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
     for (int k = 0; k < 3; ++k) out3[k] = st[k];
 }
 
@@ -3951,17 +3926,17 @@ int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const in
         test_alloc(h, M, K);
         Dev d(h);
         for (int64_t i = 0; i < M; ++i)
-            HIPCHK(hipMemcpy(h->d_Ah + i * h->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(asmb::copy(h->d_Ah + i * h->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
         d.h2d(h->d_theta, theta, K, h->ldn);
         if (diag) d.h2d(h->d_diag, diag, Ms, Ms);
-        if (idx) HIPCHK(hipMemcpy(h->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
+        if (idx) HIPCHK(asmb::copy(h->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
         const FacBuf& F = h->main_fac;
-        HIPCHK(hipMemset(F.S, 0, F.ld * F.ld * sizeof(double)));
+        HIPCHK(asmb::fill(F.S, 0, F.ld * F.ld * sizeof(double)));
         d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, idx ? h->d_idx : nullptr, 0, (int)Ms, (int)h->ldn, h->d_theta,
                       diag ? h->d_diag : nullptr, F.S, F.ld, 0, 0);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(S_out + i * Ms, F.S + i * F.ld, Ms * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(asmb::copy(S_out + i * Ms, F.S + i * F.ld, Ms * sizeof(double), hipMemcpyDeviceToHost));
     });
 }
 
@@ -3973,16 +3948,16 @@ int asm_test_syrk_update(asm_handle* h, const double* Pm, int64_t Ms, int64_t K,
         const int64_t N = srow0 + Ms;
         test_alloc(h, N, std::max<int64_t>(K, 16));
         Dev d(h);
-        HIPCHK(hipMemset(h->d_Ah, 0, h->Mp * h->ldn * sizeof(double)));
+        HIPCHK(asmb::fill(h->d_Ah, 0, h->Mp * h->ldn * sizeof(double)));
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(h->d_Ah + (srow0 + i) * h->ldn, Pm + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(asmb::copy(h->d_Ah + (srow0 + i) * h->ldn, Pm + i * K, K * sizeof(double), hipMemcpyHostToDevice));
         const FacBuf& F = h->main_fac;
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(F.S + (srow0 + i) * F.ld + srow0, S_inout + i * Ms, Ms * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(asmb::copy(F.S + (srow0 + i) * F.ld + srow0, S_inout + i * Ms, Ms * sizeof(double), hipMemcpyHostToDevice));
         d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, nullptr, srow0, (int)Ms, (int)K, nullptr, nullptr, F.S, F.ld, srow0, 1, (int)MsB);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(hipMemcpy(S_inout + i * Ms, F.S + (srow0 + i) * F.ld + srow0, Ms * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(asmb::copy(S_inout + i * Ms, F.S + (srow0 + i) * F.ld + srow0, Ms * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
     });
 }
@@ -3995,12 +3970,12 @@ static void test_load_S(asm_handle* h, const double* S, int64_t N) {
     if (h->test_layout == 1) {
         h->test_fac = FacBuf();
         ns_alloc_factor(h, h->mem, h->test_fac, N, h->test_band_hint);
-        HIPCHK(hipStreamSynchronize(h->stream));          // (the buffers are cleared on the stream)
+        HIPCHK(asmb::sync(h->stream));          // (the buffers are cleared on the stream)
         f = &h->test_fac;
     }
     f->band = h->test_band;
     for (int64_t i = 0; i < N; ++i)
-        HIPCHK(hipMemcpy(f->S + i * f->ld, S + i * N, N * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(f->S + i * f->ld, S + i * N, N * sizeof(double), hipMemcpyHostToDevice));
 }
 // factorisation of the loaded matrix with the hooks' guard settings, in the buffers it was loaded into; returns that factor
 static const FacBuf& test_factor(asm_handle* h, Dev& d, int64_t N) {
@@ -4024,9 +3999,9 @@ int asm_test_cholesky(asm_handle* h, const double* S, int64_t N, double* L_out) 
         test_load_S(h, S, N);
         Dev d(h);
         const FacBuf& f = test_factor(h, d, N);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < N; ++i) {
-            HIPCHK(hipMemcpy(L_out + i * N, f.S + i * f.ld, N * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(asmb::copy(L_out + i * N, f.S + i * f.ld, N * sizeof(double), hipMemcpyDeviceToHost));
             for (int64_t j = i + 1; j < N; ++j) L_out[i * N + j] = 0.0;
         }
         d.resolve_timing();
@@ -4056,8 +4031,8 @@ int asm_test_panel_timeout(asm_handle* h, int workgroups) {
         test_alloc(h, 64, 16);
         h->panel_epoch += 1;
         if (h->panel_epoch == 0) h->panel_epoch = 1;
-        hipLaunchKernelGGL(k_pnl_wait_probe, dim3((unsigned)workgroups), dim3(256), 0, h->stream, h->d_pflags, h->panel_epoch, h->d_ptmo);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        asmb::launch(k_pnl_wait_probe, dim3((unsigned)workgroups), dim3(256), h->stream, h->d_pflags, h->panel_epoch, h->d_ptmo);
+        HIPCHK(asmb::sync(h->stream));
         check_panel_timeout(h);
     });
 }
@@ -4083,16 +4058,16 @@ int asm_test_gemm_nt(asm_handle* h, const double* A, const double* B, const doub
         else tmp.alloc(dC, Ma * Mb);
         const char* var = std::getenv("ASM_TEST_GEMM");      // tile variant under test: 32 (32 x 64), 32w (32 x 96), default 64 x 64
         if (var && std::string(var) == "32w")
-            hipLaunchKernelGGL(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, (const double*)dA, K, (const double*)dB, K,
-                               (const double*)(mode != 0 ? dC : nullptr), Mb, dC, Mb, (int)Ma, (int)Mb, (int)K, mode);
+            asmb::launch(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), h->stream, dA, K, dB, K, (mode != 0 ? dC : nullptr), Mb, dC, Mb,
+                         (int)Ma, (int)Mb, (int)K, mode);
         else if (var && std::string(var) == "32")
-            hipLaunchKernelGGL(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), 0, h->stream, (const double*)dA, K, (const double*)dB, K,
-                               (const double*)(mode != 0 ? dC : nullptr), Mb, dC, Mb, (int)Ma, (int)Mb, (int)K, mode);
+            asmb::launch(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), h->stream, dA, K, dB, K, (mode != 0 ? dC : nullptr), Mb, dC, Mb,
+                         (int)Ma, (int)Mb, (int)K, mode);
         else
-        hipLaunchKernelGGL(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), 0, h->stream, (const double*)dA, K, (const double*)dB, K,
-                           (const double*)(mode != 0 ? dC : nullptr), Mb, dC, Mb, (int)Ma, (int)Mb, (int)K, mode);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpy(C_out, dC, Ma * Mb * sizeof(double), hipMemcpyDeviceToHost));
+        asmb::launch(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), h->stream, dA, K, dB, K, (mode != 0 ? dC : nullptr), Mb, dC, Mb, (int)Ma,
+                     (int)Mb, (int)K, mode);
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(C_out, dC, Ma * Mb * sizeof(double), hipMemcpyDeviceToHost));
     });
 }
 
@@ -4106,12 +4081,12 @@ int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* 
         double *dR = nullptr, *dX = nullptr, *dLt = nullptr;
         BufPool tmp;
         tmp.zeroed(dR, nrhs * ldr); tmp.zeroed(dX, nrhs * ldr); tmp.zeroed(dLt, f.ld * f.ld);
-        for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(dR + r * ldr, R + r * N, N * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, h->stream, (const double*)f.S, f.ld, N, N, dLt, f.ld, (int64_t)-1);
+        for (int64_t r = 0; r < nrhs; ++r) HIPCHK(asmb::copy(dR + r * ldr, R + r * N, N * sizeof(double), hipMemcpyHostToDevice));
+        asmb::launch(k_transpose_dense, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), h->stream, f.S, f.ld, N, N, dLt, f.ld, (int64_t)-1);
         d.trsm_rows(f, dR, dX, ldr, (int)nrhs, (int)N, backward ? dLt : nullptr);
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         const double* out = backward ? dR : dX;
-        for (int64_t r = 0; r < nrhs; ++r) HIPCHK(hipMemcpy(X_out + r * N, out + r * ldr, N * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < nrhs; ++r) HIPCHK(asmb::copy(X_out + r * N, out + r * ldr, N * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
     });
 }
@@ -4121,7 +4096,7 @@ int asm_test_gemv(asm_handle* h, const double* A, int64_t M, int64_t K, const do
         test_alloc(h, M, K);
         Dev d(h);
         for (int64_t i = 0; i < M; ++i)
-            HIPCHK(hipMemcpy(h->d_Ah + i * h->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(asmb::copy(h->d_Ah + i * h->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
         d.gemv_n(h->d_Ah, x, Ax);
         d.gemv_t(h->d_Ah, y, ATy);
         d.resolve_timing();
@@ -4141,11 +4116,11 @@ int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tfl
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0));
         HIPCHK(hipEventCreate(&e1));
-        hipLaunchKernelGGL(k_mfma_f64_peak<4>, dim3(blocks), dim3(256), 0, h->stream, d_out, iters / 10 + 1);   // warm-up
+        asmb::launch(k_mfma_f64_peak<4>, dim3(blocks), dim3(256), h->stream, d_out, iters / 10 + 1);   // warm-up
         HIPCHK(hipEventRecord(e0, h->stream));
-        hipLaunchKernelGGL(k_mfma_f64_peak<4>, dim3(blocks), dim3(256), 0, h->stream, d_out, iters);
+        asmb::launch(k_mfma_f64_peak<4>, dim3(blocks), dim3(256), h->stream, d_out, iters);
         HIPCHK(hipEventRecord(e1, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
         double flops = (double)blocks * 4.0 * (double)iters * 4.0 * 2.0 * 16 * 16 * 4;
@@ -4158,13 +4133,13 @@ int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tfl
 int asm_test_assemble(asm_handle* h, const double* dE, double* J_out) {
     return guarded(h, [&] {
         if (!h->setup_done) throw std::logic_error("setup first");
-        HIPCHK(hipMemcpy(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice));
         h->J_valid = false;
         Dev d(h);
         d.assemble();
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < h->M; ++i)
-            HIPCHK(hipMemcpy(J_out + i * h->n, h->d_J + i * h->ldn, h->n * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(asmb::copy(J_out + i * h->n, h->d_J + i * h->ldn, h->n * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
     });
 }
@@ -4520,7 +4495,7 @@ void batch_free_groups(asm_batch* b) {
 // `n_groups` groups of (almost) equal size over the slots; the slots' launches go to their group's stream
 void batch_make_groups(asm_batch* b, int n_groups) {
     HIPCHK(hipSetDevice(b->device));
-    for (BatchGroup* g : b->groups) HIPCHK(hipStreamSynchronize(g->stream));
+    for (BatchGroup* g : b->groups) HIPCHK(asmb::sync(g->stream));
     batch_free_groups(b);
     const int n = (int)b->slots.size();
     n_groups = std::max(1, std::min(n_groups, n));
@@ -4605,7 +4580,7 @@ int asm_batch_create(int device, int n_slots, asm_batch** out) {
 int asm_batch_destroy(asm_batch* b) {
     if (!b) return ASM_ERR_ARG;
     (void)hipSetDevice(b->device);
-    for (BatchGroup* g : b->groups) (void)hipStreamSynchronize(g->stream);
+    for (BatchGroup* g : b->groups) (void)asmb::sync(g->stream);
     for (asm_handle* h : b->slots) (void)asm_destroy(h);
     batch_free_groups(b);
     delete b;

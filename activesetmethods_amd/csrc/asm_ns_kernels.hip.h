@@ -264,20 +264,9 @@ __global__ __launch_bounds__(256) void k_ns_gi(AsmBt abt, const int* __restrict_
     GIt[(int64_t)c * ldz + t] = acc;
 }
 
+// k_ipm_theta and, in the same launch,
 // theta~ = [ (muL/tL + muU/tU + rho) Fm  (n, zero padded to ldn) | 1/dS on the inequality rows (nI, zero padded to nIp) ]
-__global__ __launch_bounds__(256) void k_ns_theta(AsmBt abt, IpmPtrs P, NsIdx X, double rho_p, double* __restrict__ th, int64_t ldn, int nIp) {
-    ASM_BARGS(abt, P, X, rho_p, th, ldn, nIp);
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < ldn) {
-        double v = 0.0;
-        if (t < P.n && P.ub[t] > P.lb[t]) v = P.muL[t] / P.tL[t] + P.muU[t] / P.tU[t] + rho_p;
-        th[t] = v;
-    }
-    if (t < nIp) th[ldn + t] = t < X.nI ? 1.0 / P.dS[X.Iidx[t]] : 0.0;
-}
-
-// k_ipm_theta + k_ns_theta in one launch (the reciprocal of dS on the inequality rows is formed from the row's own terms: another thread of
-// this launch writes P.dS)
+// (the reciprocal of dS on the inequality rows is formed from the row's own terms: another thread of this launch writes P.dS)
 __global__ __launch_bounds__(256) void k_ipm_theta_ns(AsmBt abt, IpmPtrs P, double rho_p, NsIdx X, double* __restrict__ th, int64_t ldn, int nIp) {
     ASM_BARGS(abt, P, rho_p, X, th, ldn, nIp);
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -318,55 +307,6 @@ __global__ __launch_bounds__(256) void k_ns_rowvec_e(AsmBt abt, NsIdx X, const d
     if (i >= M) return;
     const int ep = X.Epos[i];
     yM[i] = ep >= 0 ? tE[ep] : 0.0;
-}
-// inequality rows: bI = -res rp + sg rcg / pi,  yM = D_I^-1 bI ; equality rows: both zero
-__global__ __launch_bounds__(256) void k_ns_bi(AsmBt abt, IpmPtrs P, NsIdx X, const double* __restrict__ thI, double res, double* __restrict__ bI, double* __restrict__ yM) {
-    ASM_BARGS(abt, P, X, thI, res, bI, yM);
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.M) return;
-    const int ip = X.Ipos[i];
-    double b = 0.0, y = 0.0;
-    if (ip >= 0) {
-        b = -res * P.rp[i] + (double)P.rtype[i] * P.rcg[i] / P.pi[i];
-        y = thI[ip] * b;
-    }
-    bI[i] = b;
-    yM[i] = y;
-}
-// wM[i] = D_I^-1 aM[i] on the inequality rows, zero on the equality rows
-__global__ __launch_bounds__(256) void k_ns_wm(AsmBt abt, NsIdx X, const double* __restrict__ thI, const double* __restrict__ aM, double* __restrict__ wM, int64_t M) {
-    ASM_BARGS(abt, X, thI, aM, wM, M);
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= M) return;
-    const int ip = X.Ipos[i];
-    wM[i] = ip >= 0 ? thI[ip] * aM[i] : 0.0;
-}
-// free columns (th != 0):  out = th x + atw - (h ? h : 0) ; fixed / padded columns: 0       (K x - h,  K = Th + A_I' D_I^-1 A_I)
-__global__ __launch_bounds__(256) void k_ns_kx(AsmBt abt, const double* __restrict__ th, const double* __restrict__ x, const double* __restrict__ atw, const double* __restrict__ h, double* __restrict__ out, int64_t ldn) {
-    ASM_BARGS(abt, th, x, atw, h, out, ldn);
-    int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= ldn) return;
-    const double t = th[j];
-    out[j] = t != 0.0 ? t * x[j] + atw[j] - (h ? h[j] : 0.0) : 0.0;
-}
-// x[j] = 0 on the fixed / padded columns (th == 0)
-__global__ __launch_bounds__(256) void k_ns_mask(AsmBt abt, double* __restrict__ x, const double* __restrict__ th, int64_t ldn) {
-    ASM_BARGS(abt, x, th, ldn);
-    int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < ldn && th[j] == 0.0) x[j] = 0.0;
-}
-// h~ = hp + A_I' D_I^-1 bI on the free columns (zero elsewhere) ;  v = h~ - res K dpbar
-__global__ __launch_bounds__(256) void k_ns_ht(AsmBt abt, const double* __restrict__ th, const double* __restrict__ hp, const double* __restrict__ atw, const double* __restrict__ kdpb, double res, double* __restrict__ ht, double* __restrict__ v, int64_t n, int64_t ldn) {
-    ASM_BARGS(abt, th, hp, atw, kdpb, res, ht, v, n, ldn);
-    int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= ldn) return;
-    double h = 0.0, o = 0.0;
-    if (j < n && th[j] != 0.0) {
-        h = hp[j] + atw[j];
-        o = h - res * kdpb[j];
-    }
-    ht[j] = h;
-    v[j] = o;
 }
 // out = rhs - N0 x  with N0 symmetric, lower triangle stored (pitch ld): one wavefront per row
 __global__ __launch_bounds__(256) void k_ns_symv_res(AsmBt abt, const double* __restrict__ N0, int64_t ld, int k, const double* __restrict__ x, const double* __restrict__ rhs, double* __restrict__ out) {
@@ -426,28 +366,11 @@ __global__ __launch_bounds__(256) void k_ns_dp(AsmBt abt, IpmPtrs P, IpmDir D, c
     D.dp[t] = dp;
     if (t < P.n) { D.dmuL[t] = dL; D.dmuU[t] = dU; }
 }
-// inequality rows: dy = D_I^-1 (bI - aM), dpi = sg dy, dg = (rcg - g dpi)/pi, wM = D_I^-1 aM ; equality rows: dy = dpi = dg = wM = 0
-__global__ __launch_bounds__(256) void k_ns_rows(AsmBt abt, IpmPtrs P, IpmDir D, NsIdx X, const double* __restrict__ thI, const double* __restrict__ bI, const double* __restrict__ aM, double* __restrict__ wM) {
-    ASM_BARGS(abt, P, D, X, thI, bI, aM, wM);
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.M) return;
-    const int ip = X.Ipos[i];
-    double dy = 0.0, dpi = 0.0, dg = 0.0, w = 0.0;
-    if (ip >= 0) {
-        dy = thI[ip] * (bI[i] - aM[i]);
-        dpi = (double)P.rtype[i] * dy;
-        dg = (P.rcg[i] - P.g[i] * dpi) / P.pi[i];
-        w = thI[ip] * aM[i];
-    }
-    D.dy[i] = dy;
-    D.dpi[i] = dpi;
-    D.dg[i] = dg;
-    wM[i] = w;
-}
 // ---- fused forms of the null-space Newton solve (round 4: a null-space iteration is a chain of ~45 small launches; every pair
 // "sparse product, then a row- or column-wise kernel on its result" and every pair of adjacent element-wise kernels is one launch here).
-// The arithmetic of each element is the separate kernels' own, statement by statement.
-// k_ipm_rhs1 (complementarity right-hand sides) + k_ns_bi (its inequality-row part: row i needs only rcg[i])
+// The arithmetic of each element is that of the separate kernels these replaced, statement by statement.
+// k_ipm_rhs1 (complementarity right-hand sides), then from row i's own rcg[i]: bI = -res rp + sg rcg / pi and yM = D_I^-1 bI on the
+// inequality rows, both zero on the equality rows
 __global__ __launch_bounds__(256) void k_ns_rhs1_bi(AsmBt abt, IpmPtrs P, IpmDir A, int mode, NsIdx X, const double* __restrict__ thI, double res_bi, double* __restrict__ bI, double* __restrict__ yM) {
     ASM_BARGS(abt, P, A, mode, X, thI, res_bi, bI, yM);
     int64_t t = blockIdx.x * 256 + threadIdx.x;
@@ -487,7 +410,7 @@ __global__ __launch_bounds__(256) void k_ns_rhs1_bi(AsmBt abt, IpmPtrs P, IpmDir
         yM[t] = y;
     }
 }
-// k_spmv_t (atw = Ah' yM, eight lanes per column) + k_ns_ht
+// atw = Ah' yM (the sum of k_spmv_t, eight lanes per column), then h~ = hp + atw on the free columns (zero elsewhere) ;  v = h~ - res K dpbar
 __global__ __launch_bounds__(256) void k_ns_spmvt_ht(AsmBt abt, const int* __restrict__ cptr, const int* __restrict__ row, const int* __restrict__ pos, const double* __restrict__ vals, const double* __restrict__ y,
                                                      const double* __restrict__ th, const double* __restrict__ hp, const double* __restrict__ kdpb, double res, double* __restrict__ ht, double* __restrict__ v, int64_t n, int64_t ldn) {
     ASM_BARGS(abt, cptr, row, pos, vals, y, th, hp, kdpb, res, ht, v, n, ldn);
@@ -509,7 +432,7 @@ __global__ __launch_bounds__(256) void k_ns_spmvt_ht(AsmBt abt, const int* __res
         v[j] = o;
     }
 }
-// k_spmv_t (atw = Ah' wM) + k_ns_kx (h == nullptr form)
+// atw = Ah' wM (as above), then out = th x + atw on the free columns (th != 0), 0 on the fixed / padded columns     (K x,  K = Th + A_I' D_I^-1 A_I)
 __global__ __launch_bounds__(256) void k_ns_spmvt_kx(AsmBt abt, const int* __restrict__ cptr, const int* __restrict__ row, const int* __restrict__ pos, const double* __restrict__ vals, const double* __restrict__ y,
                                                      const double* __restrict__ th, const double* __restrict__ x, double* __restrict__ out, int64_t n, int64_t ldn) {
     ASM_BARGS(abt, cptr, row, pos, vals, y, th, x, out, n, ldn);
@@ -526,18 +449,8 @@ __global__ __launch_bounds__(256) void k_ns_spmvt_kx(AsmBt abt, const int* __res
         out[j] = t != 0.0 ? t * x[j] + acc : 0.0;
     }
 }
-// k_spmv_n (aM = Ah dpbar) + k_ns_wm
-__global__ __launch_bounds__(256) void k_ns_spmvn_wm(AsmBt abt, const int* __restrict__ ptr, const int* __restrict__ col, const double* __restrict__ vals, const double* __restrict__ x, NsIdx X,
-                                                     const double* __restrict__ thI, double* __restrict__ wM, int64_t M) {
-    ASM_BARGS(abt, ptr, col, vals, x, X, thI, wM, M);
-    int64_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= M) return;
-    double acc = 0.0;
-    for (int k = ptr[i]; k < ptr[i + 1]; ++k) acc += vals[k] * x[col[k]];
-    const int ip = X.Ipos[i];
-    wM[i] = ip >= 0 ? thI[ip] * acc : 0.0;
-}
-// k_ns_neg_clear + k_ns_spmvn_wm: dpbar = -e is formed on the way (stored by the first len threads), the products read -e directly
+// dpbar = -e (stored by the first len threads; the products read -e directly), *clear = 0 (the accumulated residual measure of the iteration's
+// reduced solves), and wM = D_I^-1 (Ah dpbar) on the inequality rows, zero on the equality rows (the row sum of k_spmv_n)
 __global__ __launch_bounds__(256) void k_ns_spmvn_wm_neg(AsmBt abt, const int* __restrict__ ptr, const int* __restrict__ col, const double* __restrict__ vals, const double* __restrict__ e,
                                                          double* __restrict__ dpb, int64_t len, double* __restrict__ clear, NsIdx X, const double* __restrict__ thI, double* __restrict__ wM, int64_t M) {
     ASM_BARGS(abt, ptr, col, vals, e, dpb, len, clear, X, thI, wM, M);
@@ -550,7 +463,8 @@ __global__ __launch_bounds__(256) void k_ns_spmvn_wm_neg(AsmBt abt, const int* _
     const int ip = X.Ipos[i];
     wM[i] = ip >= 0 ? thI[ip] * acc : 0.0;
 }
-// k_spmv_n (aM = Ah dp) + k_ns_rows
+// aM = Ah dp (the row sum of k_spmv_n), then on the inequality rows: dy = D_I^-1 (bI - aM), dpi = sg dy, dg = (rcg - g dpi)/pi, wM = D_I^-1 aM ;
+// on the equality rows: dy = dpi = dg = wM = 0
 __global__ __launch_bounds__(256) void k_ns_spmvn_rows(AsmBt abt, const int* __restrict__ ptr, const int* __restrict__ col, const double* __restrict__ vals, IpmPtrs P, IpmDir D, NsIdx X,
                                                        const double* __restrict__ thI, const double* __restrict__ bI, double* __restrict__ wM) {
     ASM_BARGS(abt, ptr, col, vals, P, D, X, thI, bI, wM);
@@ -571,7 +485,7 @@ __global__ __launch_bounds__(256) void k_ns_spmvn_rows(AsmBt abt, const int* __r
     D.dg[i] = dg;
     wM[i] = w;
 }
-// k_ipm_update + k_ns_scale of e (the component of the iterate outside pbar + null(A_EF) shrinks by 1 - a)
+// k_ipm_update + e *= es (the component of the iterate outside pbar + null(A_EF) shrinks by 1 - a)
 __global__ __launch_bounds__(256) void k_ns_update(AsmBt abt, IpmPtrs P, IpmDir C, double al, double be, double* __restrict__ e, double es, int64_t ldn) {
     ASM_BARGS(abt, P, C, al, be, e, es, ldn);
     int64_t t = blockIdx.x * 256 + threadIdx.x;
@@ -628,29 +542,12 @@ __global__ __launch_bounds__(256) void k_ns_update_dev(AsmBt abt, IpmPtrs P, Ipm
     }
     if (t < ldn) e[t] *= es;
 }
-// k_ns_neg (dpbar = -e) + clearing the accumulated residual measure of the iteration's reduced solves
-__global__ __launch_bounds__(256) void k_ns_neg_clear(AsmBt abt, const double* __restrict__ x, double* __restrict__ out, int64_t len, double* __restrict__ clear) {
-    ASM_BARGS(abt, x, out, len, clear);
-    int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < len) out[j] = -x[j];
-    if (j == 0) *clear = 0.0;
-}
 
 // out[Eidx[e]] = tE[e]   (add != 0: += )
 __global__ __launch_bounds__(256) void k_ns_scatter_e(AsmBt abt, NsIdx X, const double* __restrict__ tE, double* __restrict__ out, int add) {
     ASM_BARGS(abt, X, tE, out, add);
     int t = blockIdx.x * 256 + threadIdx.x;
     if (t < X.nE) out[X.Eidx[t]] = (add ? out[X.Eidx[t]] : 0.0) + tE[t];
-}
-// slot[0] = max_j |th_j dp_j - aty_j - hp_j| over the free columns: the dual-equation error of the step (one workgroup)
-__global__ __launch_bounds__(1024) void k_ns_err(AsmBt abt, const double* __restrict__ th, const double* __restrict__ dp, const double* __restrict__ aty, const double* __restrict__ hp, int64_t n, double* __restrict__ slot) {
-    ASM_BARGS(abt, th, dp, aty, hp, n, slot);
-    __shared__ double sh[16];
-    double m = 0.0;
-    for (int64_t j = threadIdx.x; j < n; j += 1024)
-        if (th[j] != 0.0) m = fmax(m, fabs(th[j] * dp[j] - aty[j] - hp[j]));
-    m = blk_reduce_max(m, sh);
-    if (threadIdx.x == 0) slot[0] = m;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -783,17 +680,6 @@ __global__ __launch_bounds__(256) void k_ns_e1(AsmBt abt, IpmPtrs P, const doubl
     int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= ldn) return;
     e[j] = (j < P.n && P.ub[j] > P.lb[j]) ? d0[j] - zz[j] : 0.0;
-}
-// x *= a
-__global__ __launch_bounds__(256) void k_ns_scale(AsmBt abt, double* __restrict__ x, double a, int64_t len) {
-    ASM_BARGS(abt, x, a, len);
-    int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < len) x[j] *= a;
-}
-__global__ __launch_bounds__(256) void k_ns_neg(AsmBt abt, const double* __restrict__ x, double* __restrict__ out, int64_t len) {
-    ASM_BARGS(abt, x, out, len);
-    int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < len) out[j] = -x[j];
 }
 // scal[SC_DINF] = max_c |zr_c| / scale_q  (the dual residual inside the null space of the equality rows), then the scalar block goes to the host
 __global__ __launch_bounds__(1024) void k_ns_dinf(AsmBt abt, IpmPtrs P, const double* __restrict__ zr, int k, unsigned pub) {
