@@ -78,6 +78,9 @@ PROTOTYPES = {
     "asm_eval_jacobian_values": (C.c_int, [_P, _D]),
     "asm_eval_set_data": (C.c_int, [_P, C.c_int64, C.c_int64, _D]),
     "asm_eval_data_gradient": (C.c_int, [_P, _D, _D, _D]),
+    "asm_eval_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
+    "asm_eval_hessian_lagrangian": (C.c_int, [_P, _D, C.c_double, _D, _D]),
+    "asm_eval_hessian_product": (C.c_int, [_P, _D, C.c_double, _D, _D, _D]),
     "asm_slp_norms": (C.c_int, [_P, _D, _D, _D, _D]),
     "asm_slp_merit": (C.c_int, [_P, C.c_int, C.c_double, _D, _D, _D, C.c_int, C.c_double, _D]),
     "asm_slp_line_search": (C.c_int, [_P, _D, _D, _D, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _D, _D,

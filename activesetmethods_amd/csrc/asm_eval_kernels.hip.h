@@ -379,6 +379,248 @@ __global__ __launch_bounds__(256) void k_nlp_expr_data_gather(AsmBt abt, const i
     out[c] = g;
 }
 
+// ---- Hessian of the Lagrangian (asm_eval_hessian_*; include/asm_hip.h, "Hessian of the Lagrangian").
+// Function store: one thread per pattern entry = one stored quadratic term; value = factor * q_coef (fill_hessian_lagrangian!,
+// MOI_wrapper.jl:946-958), factor = wobj (obj_factor * objective_scale) for a term of the objective row (row < 0), else lambda[row].
+__global__ __launch_bounds__(256) void k_fn_hessian(AsmBt abt, const int64_t* __restrict__ hq_term, const int64_t* __restrict__ hq_row, const double* __restrict__ q_coef, const double* __restrict__ lam, double wobj, int64_t count, double* __restrict__ values) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, hq_term, hq_row, q_coef, lam, wobj, count, values);
+    const int64_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    const int64_t r = hq_row[e];
+    values[e] = (r < 0 ? wobj : lam[r]) * q_coef[hq_term[e]];
+}
+// Expression block, forward over reverse: one thread per (row or term, seed variable j of its distinct variables).  The thread runs the
+// forward sweep with its tangent for x' = e_j (val, tval), then the reverse sweep with the tangent of every adjoint statement (adj, tadj):
+// the adjoint tangent that reaches the VAR nodes of variable i is d2(row) / dx_i dx_j.  Its four node arrays are a segment of the HBM
+// workspace (woff[s] = first node; the segments of a row's seed threads follow each other).  The thread's occurrence list
+// ovar[optr[s] .. optr[s+1]) names the variables i >= j of the row's interaction set, ascending; hocc[o] receives weight * h.
+struct ExprHess {
+    const int64_t *srow, *svar, *woff, *optr, *ovar;   // srow / svar / woff [S], optr [S+1], ovar [optr[S]]
+    double *val, *tval, *adj, *tadj, *hocc;             // four node arrays [woff[S-1] + nodes of the last row], hocc [optr[S]]
+    int64_t S;
+};
+// u ^ e with d = d/du (the factors of expr_powi) and d2 = d2/du2 = e (e - 1) u^(e-2): ((double)e * (double)(e - 1)) times the product of
+// |e| - 2 factors u (left to right from 1.0) for e >= 2, 0.0 for e = 1, ((double)e * (double)(e - 1)) / ((u^|e| * u) * u) for e < 0
+__device__ __forceinline__ double expr_powi2(double u, int64_t e, double* d, double* d2) {
+#pragma clang fp contract(off)
+    const int64_t k = e < 0 ? -e : e;
+    double p = 1.0, q = 1.0;
+    for (int64_t i = 1; i < k; ++i) { q = p; p = p * u; }
+    const double pk = p * u, ee = (double)e * (double)(e - 1);
+    if (e > 0) { *d = (double)e * p; *d2 = k > 1 ? ee * q : 0.0; return pk; }
+    const double pu = pk * u;
+    *d = (double)e / pu;
+    *d2 = ee / (pu * u);
+    return 1.0 / pk;
+}
+// sin, cos, exp and log of the second-order sweeps, out of line for the reason expr_libm is
+__device__ __noinline__ double expr_libm2(int32_t op, double u) {
+    switch (op) {
+        case ASM_OP_SIN: return sin(u);
+        case ASM_OP_COS: return cos(u);
+        case ASM_OP_EXP: return exp(u);
+        default: return log(u);           // ASM_OP_LOG
+    }
+}
+// forward sweep with tangent: tval = d val / d x_seed, statement by statement the tangent of expr_forward
+__device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, int64_t seed, double* val, double* tval) {
+#pragma clang fp contract(off)
+    for (int64_t k = k0; k < k1; ++k) {
+        const int64_t a = X.a[k], b = X.b[k];
+        const int32_t op = X.op[k];
+        double v, d;
+        if (op == ASM_OP_CONST) { v = X.cst[a]; d = 0.0; }
+        else if (op == ASM_OP_VAR) { v = x[a]; d = a == seed ? 1.0 : 0.0; }
+        else {
+            const double u = val[a], du = tval[a];
+            const bool binary = (op >= ASM_OP_ADD && op <= ASM_OP_DIV) || op >= ASM_OP_POW;
+            const double y = binary ? val[b] : 0.0, dy = binary ? tval[b] : 0.0;
+            switch (op) {
+                case ASM_OP_ADD: v = u + y; d = du + dy; break;
+                case ASM_OP_SUB: v = u - y; d = du - dy; break;
+                case ASM_OP_MUL: v = u * y; d = du * y + u * dy; break;
+                case ASM_OP_DIV: v = u / y; d = (du - v * dy) / y; break;
+                case ASM_OP_NEG: v = -u; d = -du; break;
+                case ASM_OP_POWI: { double d1, d2; v = expr_powi2(u, b, &d1, &d2); d = d1 * du; break; }
+                case ASM_OP_SQRT: v = sqrt(u); d = (0.5 * du) / v; break;
+                case ASM_OP_EXP: v = expr_libm2(ASM_OP_EXP, u); d = du * v; break;
+                case ASM_OP_LOG: v = expr_libm2(ASM_OP_LOG, u); d = du / u; break;
+                case ASM_OP_SIN: v = expr_libm2(ASM_OP_SIN, u); d = du * expr_libm2(ASM_OP_COS, u); break;
+                case ASM_OP_COS: v = expr_libm2(ASM_OP_COS, u); d = -(du * expr_libm2(ASM_OP_SIN, u)); break;
+                case ASM_OP_ABS: v = fabs(u); d = du * copysign(1.0, u); break;
+                case ASM_OP_MIN: { const bool c = y < u; v = c ? y : u; d = c ? dy : du; break; }
+                case ASM_OP_MAX: { const bool c = y > u; v = c ? y : u; d = c ? dy : du; break; }
+                default:
+                    v = expr_libm(op, u, y);
+                    switch (op) {
+                        case ASM_OP_TAN: d = du * (1.0 + v * v); break;
+                        case ASM_OP_ASIN: d = du / sqrt(1.0 - u * u); break;
+                        case ASM_OP_ACOS: d = -(du / sqrt(1.0 - u * u)); break;
+                        case ASM_OP_ATAN: d = du / (1.0 + u * u); break;
+                        case ASM_OP_SINH: d = du * expr_libm(ASM_OP_COSH, u, 0.0); break;
+                        case ASM_OP_COSH: d = du * expr_libm(ASM_OP_SINH, u, 0.0); break;
+                        case ASM_OP_TANH: d = du * (1.0 - v * v); break;
+                        case ASM_OP_LOG10: d = du / (u * EXPR_LN10); break;
+                        case ASM_OP_LOG2: d = du / (u * EXPR_LN2); break;
+                        case ASM_OP_LOG1P: d = du / (1.0 + u); break;
+                        case ASM_OP_EXPM1: d = du * (v + 1.0); break;
+                        case ASM_OP_CBRT: d = du / (3.0 * (v * v)); break;
+                        case ASM_OP_POW:
+                            d = du * (y * expr_libm(ASM_OP_POW, u, y - 1.0));
+                            if (X.op[b] != ASM_OP_CONST) d = d + dy * (v * expr_libm2(ASM_OP_LOG, u));
+                            break;
+                        default: { const double t = u * u + y * y; d = (du * y) / t - (dy * u) / t; break; }   // ASM_OP_ATAN2
+                    }
+            }
+        }
+        val[k] = v;
+        tval[k] = d;
+    }
+}
+// reverse sweep with tangent: adj as expr_reverse forms it, tadj = d adj / d x_seed, statement by statement; the adjoint tangent of a VAR
+// node whose variable is in the thread's occurrence list is added to hocc there (several VAR nodes of a variable: reverse node order)
+__device__ __forceinline__ void expr_reverse2(const ExprTape& X, int64_t k0, int64_t k1, const double* val, const double* tval, double* adj, double* tadj,
+                                              const int64_t* __restrict__ ovar, int64_t o0, int64_t o1, double* __restrict__ hocc) {
+#pragma clang fp contract(off)
+    for (int64_t k = k0; k < k1; ++k) { adj[k] = 0.0; tadj[k] = 0.0; }
+    adj[k1 - 1] = 1.0;
+    for (int64_t k = k1 - 1; k >= k0; --k) {
+        const int32_t op = X.op[k];
+        if (op == ASM_OP_CONST) continue;
+        const double w = adj[k], z = tadj[k];
+        const int64_t a = X.a[k], b = X.b[k];
+        if (op == ASM_OP_VAR) {
+            for (int64_t o = o0; o < o1; ++o)
+                if (ovar[o] == a) { hocc[o] = hocc[o] + z; break; }
+            continue;
+        }
+        const double u = val[a], du = tval[a], v = val[k], d = tval[k];
+        switch (op) {
+            case ASM_OP_ADD: adj[a] = adj[a] + w; tadj[a] = tadj[a] + z; adj[b] = adj[b] + w; tadj[b] = tadj[b] + z; break;
+            case ASM_OP_SUB: adj[a] = adj[a] + w; tadj[a] = tadj[a] + z; adj[b] = adj[b] - w; tadj[b] = tadj[b] - z; break;
+            case ASM_OP_MUL: {
+                const double y = val[b], dy = tval[b];
+                adj[a] = adj[a] + w * y; tadj[a] = tadj[a] + (z * y + w * dy);
+                adj[b] = adj[b] + w * u; tadj[b] = tadj[b] + (z * u + w * du);
+                break;
+            }
+            case ASM_OP_DIV: {
+                const double y = val[b], dy = tval[b], t = w / y, dt = (z - t * dy) / y;
+                adj[a] = adj[a] + t; tadj[a] = tadj[a] + dt;
+                adj[b] = adj[b] - t * v; tadj[b] = tadj[b] - (dt * v + t * d);
+                break;
+            }
+            case ASM_OP_NEG: adj[a] = adj[a] - w; tadj[a] = tadj[a] - z; break;
+            case ASM_OP_POWI: {
+                double d1, d2;
+                (void)expr_powi2(u, b, &d1, &d2);
+                adj[a] = adj[a] + w * d1; tadj[a] = tadj[a] + (z * d1 + w * (d2 * du));
+                break;
+            }
+            case ASM_OP_SQRT: { const double s = (0.5 * w) / v; adj[a] = adj[a] + s; tadj[a] = tadj[a] + (0.5 * z - s * d) / v; break; }
+            case ASM_OP_EXP: adj[a] = adj[a] + w * v; tadj[a] = tadj[a] + (z * v + w * d); break;
+            case ASM_OP_LOG: { const double q = w / u; adj[a] = adj[a] + q; tadj[a] = tadj[a] + (z - q * du) / u; break; }
+            case ASM_OP_SIN: {
+                const double c = expr_libm2(ASM_OP_COS, u), s = expr_libm2(ASM_OP_SIN, u);
+                adj[a] = adj[a] + w * c; tadj[a] = tadj[a] + (z * c - w * (s * du));
+                break;
+            }
+            case ASM_OP_COS: {
+                const double c = expr_libm2(ASM_OP_COS, u), s = expr_libm2(ASM_OP_SIN, u);
+                adj[a] = adj[a] - w * s; tadj[a] = tadj[a] - (z * s + w * (c * du));
+                break;
+            }
+            case ASM_OP_ABS: { const double s = copysign(1.0, u); adj[a] = adj[a] + w * s; tadj[a] = tadj[a] + z * s; break; }
+            case ASM_OP_TAN: { const double g = 1.0 + v * v; adj[a] = adj[a] + w * g; tadj[a] = tadj[a] + (z * g + w * (2.0 * (v * d))); break; }
+            case ASM_OP_ASIN: case ASM_OP_ACOS: {
+                const double r = sqrt(1.0 - u * u), q = w / r, dr = -((u * du) / r), dq = (z - q * dr) / r;
+                if (op == ASM_OP_ASIN) { adj[a] = adj[a] + q; tadj[a] = tadj[a] + dq; }
+                else { adj[a] = adj[a] - q; tadj[a] = tadj[a] - dq; }
+                break;
+            }
+            case ASM_OP_ATAN: { const double g = 1.0 + u * u, q = w / g; adj[a] = adj[a] + q; tadj[a] = tadj[a] + (z - q * (2.0 * (u * du))) / g; break; }
+            case ASM_OP_SINH: {
+                const double c = expr_libm(ASM_OP_COSH, u, 0.0), s = expr_libm(ASM_OP_SINH, u, 0.0);
+                adj[a] = adj[a] + w * c; tadj[a] = tadj[a] + (z * c + w * (s * du));
+                break;
+            }
+            case ASM_OP_COSH: {
+                const double c = expr_libm(ASM_OP_COSH, u, 0.0), s = expr_libm(ASM_OP_SINH, u, 0.0);
+                adj[a] = adj[a] + w * s; tadj[a] = tadj[a] + (z * s + w * (c * du));
+                break;
+            }
+            case ASM_OP_TANH: { const double g = 1.0 - v * v; adj[a] = adj[a] + w * g; tadj[a] = tadj[a] + (z * g - w * (2.0 * (v * d))); break; }
+            case ASM_OP_LOG10: case ASM_OP_LOG2: {
+                const double ln = op == ASM_OP_LOG10 ? EXPR_LN10 : EXPR_LN2, g = u * ln, q = w / g;
+                adj[a] = adj[a] + q; tadj[a] = tadj[a] + (z - q * (du * ln)) / g;
+                break;
+            }
+            case ASM_OP_LOG1P: { const double g = 1.0 + u, q = w / g; adj[a] = adj[a] + q; tadj[a] = tadj[a] + (z - q * du) / g; break; }
+            case ASM_OP_EXPM1: { const double g = v + 1.0; adj[a] = adj[a] + w * g; tadj[a] = tadj[a] + (z * g + w * d); break; }
+            case ASM_OP_CBRT: { const double g = 3.0 * (v * v), q = w / g; adj[a] = adj[a] + q; tadj[a] = tadj[a] + (z - q * (6.0 * (v * d))) / g; break; }
+            case ASM_OP_POW: {
+                const double y = val[b], dy = tval[b];
+                const bool bc = X.op[b] == ASM_OP_CONST;         // a CONST exponent: no term with dy, nothing to b
+                const double p1 = expr_libm(ASM_OP_POW, u, y - 1.0), p2 = expr_libm(ASM_OP_POW, u, y - 2.0), A = y * p1;
+                double dp1 = du * ((y - 1.0) * p2), lu = 0.0;
+                if (!bc) { lu = expr_libm2(ASM_OP_LOG, u); dp1 = dp1 + dy * (p1 * lu); }
+                double dA = y * dp1;
+                if (!bc) dA = dA + dy * p1;
+                adj[a] = adj[a] + w * A; tadj[a] = tadj[a] + (z * A + w * dA);
+                if (!bc) {
+                    const double B = v * lu, dB = d * lu + v * (du / u);
+                    adj[b] = adj[b] + w * B; tadj[b] = tadj[b] + (z * B + w * dB);
+                }
+                break;
+            }
+            case ASM_OP_ATAN2: {
+                const double y = val[b], dy = tval[b], t = u * u + y * y, dt = 2.0 * (u * du) + 2.0 * (y * dy);
+                const double qa = (w * y) / t, qb = (w * u) / t;
+                adj[a] = adj[a] + qa; tadj[a] = tadj[a] + ((z * y + w * dy) - qa * dt) / t;
+                adj[b] = adj[b] - qb; tadj[b] = tadj[b] - ((z * u + w * du) - qb * dt) / t;
+                break;
+            }
+            case ASM_OP_MIN: { const int64_t c = val[b] < u ? b : a; adj[c] = adj[c] + w; tadj[c] = tadj[c] + z; break; }
+            default: { const int64_t c = val[b] > u ? b : a; adj[c] = adj[c] + w; tadj[c] = tadj[c] + z; break; }   // ASM_OP_MAX
+        }
+    }
+}
+// lam: the multipliers of the block's rows; wobj = obj_factor * objective_scale, the weight of a term
+__global__ __launch_bounds__(256) void k_nlp_expr_hess(AsmBt abt, ExprTape X, ExprHess H, const double* __restrict__ x, const double* __restrict__ lam, double wobj) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, H, x, lam, wobj);
+    const int64_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= H.S) return;
+    const int64_t t = H.srow[s], k0 = X.ptr[t], k1 = X.ptr[t + 1], wb = H.woff[s] - k0, o0 = H.optr[s], o1 = H.optr[s + 1];
+    expr_forward2(X, k0, k1, x, H.svar[s], H.val + wb, H.tval + wb);
+    for (int64_t o = o0; o < o1; ++o) H.hocc[o] = 0.0;
+    expr_reverse2(X, k0, k1, H.val + wb, H.tval + wb, H.adj + wb, H.tadj + wb, H.ovar, o0, o1, H.hocc);
+    const double wt = t < X.R ? lam[t] : wobj;
+    for (int64_t o = o0; o < o1; ++o) H.hocc[o] = wt * H.hocc[o];
+}
+// one thread per block entry sums its occurrences in list order from 0.0 ((row, then term) order: no atomics, the host twin's sum)
+__global__ __launch_bounds__(256) void k_nlp_expr_hess_gather(AsmBt abt, const int64_t* __restrict__ eptr, const int64_t* __restrict__ eocc, const double* __restrict__ hocc, int64_t count, double* __restrict__ values) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, eptr, eocc, hocc, count, values);
+    const int64_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    double g = 0.0;
+    for (int64_t q = eptr[e]; q < eptr[e + 1]; ++q) g = g + hocc[eocc[q]];
+    values[e] = g;
+}
+// out = H v from the values: one thread per variable walks its list of (entry, other variable) in entry order - an off-diagonal entry
+// (i, j) is in the lists of i and of j - and sums values[entry] * v[other] from 0.0
+__global__ __launch_bounds__(256) void k_hess_product(AsmBt abt, const int64_t* __restrict__ pptr, const int64_t* __restrict__ pent, const int64_t* __restrict__ poth, const double* __restrict__ values, const double* __restrict__ v, int64_t n, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, pptr, pent, poth, values, v, n, out);
+    const int64_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double g = 0.0;
+    for (int64_t q = pptr[i]; q < pptr[i + 1]; ++q) g = g + values[pent[q]] * v[poth[q]];
+    out[i] = g;
+}
+
 __global__ __launch_bounds__(256) void k_axpy_out(AsmBt abt, const double* __restrict__ x, double alpha, const double* __restrict__ p, double* __restrict__ out, int64_t n) {
     ASM_BARGS(abt, x, alpha, p, out, n);
     int64_t j = blockIdx.x * 256 + threadIdx.x;

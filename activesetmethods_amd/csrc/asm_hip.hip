@@ -398,7 +398,15 @@ struct asm_handle {
     int64_t ev_n_dpar = 0, ev_dirty_lo = 0, ev_dirty_hi = 0;
     int64_t* d_ev_cptr = nullptr;
     double *d_ev_cocc = nullptr, *d_ev_lam = nullptr, *d_ev_dgrad = nullptr, *h_ev_dgrad = nullptr;
-    bool J_valid = false;                               // the dense J in HBM matches the dE in HBM
+    // Hessian of the Lagrangian (asm_eval_hessian_*): pattern, lists and workspace, made by the first of those calls after asm_eval_setup
+    // (hs_prepare) from the store and the tape in HBM - a handle that never asks holds none of it
+    bool hs_ready = false;
+    int64_t hs_nfn = 0, hs_wnodes = 0;       // entries of the function store (the block's follow); nodes of the workspace
+    std::vector<int64_t> hs_rows, hs_cols;   // the pattern, 1-based
+    ExprHess hs_H{};
+    int64_t *d_hs_qterm = nullptr, *d_hs_qrow = nullptr, *d_hs_eptr = nullptr, *d_hs_eocc = nullptr, *d_hs_pptr = nullptr, *d_hs_pent = nullptr, *d_hs_poth = nullptr;
+    double *d_hs_lam = nullptr, *d_hs_v = nullptr, *d_hs_vals = nullptr, *d_hs_out = nullptr, *h_hs = nullptr;
+    bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
     double* h_scal = nullptr;       // pinned scalar read-back; host-mapped: the reduction kernels store the block there themselves (scal_publish)
     double* d_hscal = nullptr;      // its device address
@@ -2653,7 +2661,7 @@ void free_device(asm_handle* h) {
     h->ns_cap = false; h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0; h->ns_npairs = 0;
     h->ns_f0 = FacBuf(); h->ns_fN = FacBuf(); h->ns_fC = FacBuf(); h->test_fac = FacBuf();
     h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
-    h->ev_ready = false;
+    h->ev_ready = false; h->hs_ready = false;
 }
 
 // forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
@@ -3572,6 +3580,8 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     HIPCHK(hipSetDevice(h->device));
     BufPool& P = h->mem_ev;
     P.release();
+    h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_nfn = h->hs_wnodes = 0;
+    std::vector<int64_t>().swap(h->hs_rows); std::vector<int64_t>().swap(h->hs_cols);
     FnStore& F = h->ev_F;
     F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
     const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
@@ -3691,6 +3701,213 @@ static void do_data_gradient(asm_handle* h, const double* x, const double* lambd
     std::memcpy(out, h->h_ev_dgrad, nd * sizeof(double));
 }
 
+// ---- Hessian of the Lagrangian (include/asm_hip.h, "Hessian of the Lagrangian")
+namespace {
+extern "C++" {
+template <class T>
+std::vector<T> hs_download(const T* dev, int64_t count) {
+    std::vector<T> v((size_t)std::max<int64_t>(count, 0));
+    if (count > 0) HIPCHK(asmb::copy(v.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
+    return v;
+}
+}
+// the interaction set P(last node) of the row or term with nodes [k0, k1) (absolute references), as pairs (j, i), j <= i, sorted by (j, i):
+// the union over the nodes the last one depends on of what each op adds (the header's rule; POW / ATAN2 cover their operands' sets)
+void hs_row_pairs(const int32_t* op, const int64_t* a, const int64_t* b, int64_t k0, int64_t k1, std::vector<std::vector<int64_t>>& L, std::vector<char>& reach,
+                  std::vector<std::pair<int64_t, int64_t>>& P) {
+    const int64_t len = k1 - k0;
+    if ((int64_t)L.size() < len) L.resize(len);
+    reach.assign(len, 0);
+    reach[len - 1] = 1;
+    for (int64_t q = len - 1; q >= 0; --q) {
+        const int32_t o = op[k0 + q];
+        if (!reach[q] || o == ASM_OP_CONST || o == ASM_OP_VAR) continue;
+        reach[a[k0 + q] - k0] = 1;
+        if ((o >= ASM_OP_ADD && o <= ASM_OP_DIV) || o >= ASM_OP_POW) reach[b[k0 + q] - k0] = 1;
+    }
+    P.clear();
+    auto cross = [&P](const std::vector<int64_t>& A, const std::vector<int64_t>& B) {
+        for (int64_t i : A)
+            for (int64_t j : B) P.emplace_back(std::min(i, j), std::max(i, j));
+    };
+    for (int64_t q = 0; q < len; ++q) {
+        const int64_t k = k0 + q;
+        const int32_t o = op[k];
+        std::vector<int64_t>& Lq = L[q];
+        Lq.clear();
+        if (o == ASM_OP_CONST) continue;
+        if (o == ASM_OP_VAR) { Lq.push_back(a[k]); continue; }
+        const std::vector<int64_t>& La = L[a[k] - k0];
+        const bool binary = (o >= ASM_OP_ADD && o <= ASM_OP_DIV) || o >= ASM_OP_POW;
+        if (!binary) Lq = La;
+        else {
+            const std::vector<int64_t>& Lb = L[b[k] - k0];
+            Lq.resize(La.size() + Lb.size());
+            Lq.erase(std::set_union(La.begin(), La.end(), Lb.begin(), Lb.end(), Lq.begin()), Lq.end());
+        }
+        if (!reach[q]) continue;
+        switch (o) {
+            case ASM_OP_ADD: case ASM_OP_SUB: case ASM_OP_NEG: case ASM_OP_MIN: case ASM_OP_MAX: break;
+            case ASM_OP_MUL: cross(La, L[b[k] - k0]); break;
+            case ASM_OP_DIV: cross(La, L[b[k] - k0]); cross(L[b[k] - k0], L[b[k] - k0]); break;
+            case ASM_OP_POWI: if (b[k] != 1) cross(La, La); break;
+            case ASM_OP_POW: case ASM_OP_ATAN2: cross(Lq, Lq); break;
+            default: cross(La, La); break;       // every other unary op
+        }
+    }
+    std::sort(P.begin(), P.end());
+    P.erase(std::unique(P.begin(), P.end()), P.end());
+}
+// pattern, seed threads, occurrence and product lists, workspace: once per asm_eval_setup, at the first Hessian call
+void hs_prepare(asm_handle* h) {
+    if (h->hs_ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    const FnStore& F = h->ev_F;
+    const ExprTape& X = h->ev_X;
+    const bool expr = h->ev_nlp_kind == ASM_NLP_EXPR;
+    const int64_t nr = F.n_rows, n = h->n;
+    // 1. function store: the objective row's quadratic terms (unless the block has the objective), then the rows' in row order
+    const std::vector<int64_t> qptr = hs_download(F.quad_ptr, nr + 2);
+    const std::vector<int64_t> q1 = hs_download(F.q_v1, qptr[nr + 1]), q2 = hs_download(F.q_v2, qptr[nr + 1]);
+    std::vector<int64_t> rows, cols, qterm, qrow;
+    auto store_row = [&](int64_t r, int64_t tag) {
+        for (int64_t k = qptr[r]; k < qptr[r + 1]; ++k) { rows.push_back(q1[k] + 1); cols.push_back(q2[k] + 1); qterm.push_back(k); qrow.push_back(tag); }
+    };
+    if (!(expr && X.T > 0)) store_row(nr, -1);
+    for (int64_t r = 0; r < nr; ++r) store_row(r, r);
+    const int64_t nfn = (int64_t)rows.size();
+    // 2. expression block: per row / term its interaction set, one seed thread per smaller index j with its occurrence list (i ascending)
+    std::vector<int64_t> srow, svar, woff, optr(1, 0), ovar, okey;
+    int64_t wnodes = 0;
+    if (expr) {
+        const std::vector<int64_t> ptr = hs_download(X.ptr, X.R + X.T + 1), ta = hs_download(X.a, X.L), tb = hs_download(X.b, X.L);
+        const std::vector<int32_t> top = hs_download(X.op, X.L);
+        std::vector<std::vector<int64_t>> L;
+        std::vector<char> reach;
+        std::vector<std::pair<int64_t, int64_t>> P;
+        for (int64_t t = 0; t < X.R + X.T; ++t) {
+            hs_row_pairs(top.data(), ta.data(), tb.data(), ptr[t], ptr[t + 1], L, reach, P);
+            for (size_t q = 0; q < P.size(); ++q) {
+                if (q == 0 || P[q].first != P[q - 1].first) {
+                    if (q) optr.push_back((int64_t)ovar.size());
+                    srow.push_back(t); svar.push_back(P[q].first); woff.push_back(wnodes);
+                    wnodes += ptr[t + 1] - ptr[t];
+                }
+                ovar.push_back(P[q].second);
+                okey.push_back(P[q].second * n + P[q].first);
+            }
+            if (!P.empty()) optr.push_back((int64_t)ovar.size());
+        }
+    }
+    const int64_t S = (int64_t)srow.size(), nocc = (int64_t)ovar.size();
+    // the block's entries: the distinct pairs (i, j), i >= j, sorted by (i, j); every entry's occurrences in list order
+    std::vector<int64_t> keys(okey);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    const int64_t nblk = (int64_t)keys.size();
+    std::vector<int64_t> eptr(nblk + 1, 0), eocc(nocc), oent(nocc);
+    for (int64_t o = 0; o < nocc; ++o) { oent[o] = std::lower_bound(keys.begin(), keys.end(), okey[o]) - keys.begin(); ++eptr[oent[o] + 1]; }
+    for (int64_t e = 0; e < nblk; ++e) eptr[e + 1] += eptr[e];
+    {
+        std::vector<int64_t> fill(eptr.begin(), eptr.end() - 1);
+        for (int64_t o = 0; o < nocc; ++o) eocc[fill[oent[o]]++] = o;
+    }
+    for (int64_t e = 0; e < nblk; ++e) { rows.push_back(keys[e] / n + 1); cols.push_back(keys[e] % n + 1); }
+    const int64_t nnz = nfn + nblk;
+    // 3. product lists: per variable (entry, other variable) in entry order, an off-diagonal entry in both lists
+    std::vector<int64_t> pptr(n + 1, 0);
+    for (int64_t e = 0; e < nnz; ++e) {
+        if (rows[e] < 1 || rows[e] > n || cols[e] < 1 || cols[e] > n) throw std::invalid_argument("asm_eval_hessian: a quadratic term names a variable outside [0, n)");
+        ++pptr[rows[e]];
+        if (rows[e] != cols[e]) ++pptr[cols[e]];
+    }
+    for (int64_t j = 0; j < n; ++j) pptr[j + 1] += pptr[j];
+    std::vector<int64_t> pent(pptr[n]), poth(pptr[n]), fill(pptr.begin(), pptr.end() - 1);
+    for (int64_t e = 0; e < nnz; ++e) {
+        const int64_t r = rows[e] - 1, c = cols[e] - 1;
+        pent[fill[r]] = e; poth[fill[r]++] = c;
+        if (r != c) { pent[fill[c]] = e; poth[fill[c]++] = r; }
+    }
+    BufPool& M = h->mem_ev;
+    M.upload(h->d_hs_qterm, qterm.data(), nfn); M.upload(h->d_hs_qrow, qrow.data(), nfn);
+    M.upload(h->d_hs_eptr, eptr.data(), nblk + 1); M.upload(h->d_hs_eocc, eocc.data(), nocc);
+    M.upload(h->d_hs_pptr, pptr.data(), n + 1); M.upload(h->d_hs_pent, pent.data(), pptr[n]); M.upload(h->d_hs_poth, poth.data(), pptr[n]);
+    ExprHess& H = h->hs_H;
+    H = ExprHess{};
+    H.S = S;
+    if (S > 0) {
+        M.upload(H.srow, srow.data(), S); M.upload(H.svar, svar.data(), S); M.upload(H.woff, woff.data(), S);
+        M.upload(H.optr, optr.data(), S + 1); M.upload(H.ovar, ovar.data(), nocc);
+        M.zeroed(H.val, wnodes); M.zeroed(H.tval, wnodes); M.zeroed(H.adj, wnodes); M.zeroed(H.tadj, wnodes); M.zeroed(H.hocc, nocc);
+    }
+    M.zeroed(h->d_hs_lam, h->m); M.zeroed(h->d_hs_v, n); M.zeroed(h->d_hs_vals, nnz); M.zeroed(h->d_hs_out, n);
+    M.alloc(h->h_hs, std::max(nnz, n), BufPool::PINNED);
+    h->hs_nfn = nfn; h->hs_wnodes = wnodes;
+    h->hs_rows.swap(rows); h->hs_cols.swap(cols);
+    h->hs_ready = true;
+}
+void hs_check(const asm_handle* h, const char* who) {
+    if (!h->ev_ready) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
+    if (h->ev_nlp_kind != ASM_NLP_NONE && h->ev_nlp_kind != ASM_NLP_EXPR)
+        throw std::invalid_argument(std::string(who) + ": second derivatives exist for the function store alone (nlp_kind 0) or with an expression block (nlp_kind 3)");
+}
+// the values at (x, obj_factor, lambda) into d_hs_vals; with v also H v into d_hs_out.  x goes where asm_eval_constraints puts its trial
+// point: the inputs of the next LP are not touched
+void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v) {
+    hs_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->n, m = h->m, nnz = (int64_t)h->hs_rows.size(), nfn = h->hs_nfn;
+    const FnStore& F = h->ev_F;
+    std::memcpy(h->h_ev, x, n * sizeof(double));
+    HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (m > 0) {
+        std::memcpy(h->h_ev + n, lambda, m * sizeof(double));
+        HIPCHK(asmb::copy_async(h->d_hs_lam, h->h_ev + n, m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    if (v) {
+        std::memcpy(h->h_ev + n + m, v, n * sizeof(double));
+        HIPCHK(asmb::copy_async(h->d_hs_v, h->h_ev + n + m, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    const double wobj = obj_factor * F.objective_scale;
+    if (nfn > 0) asmb::launch(k_fn_hessian, asmb::blocks(nfn), dim3(256), h->stream, h->d_hs_qterm, h->d_hs_qrow, F.q_coef, h->d_hs_lam, wobj, nfn, h->d_hs_vals);
+    if (h->hs_H.S > 0) {
+        asmb::launch(k_nlp_expr_hess, asmb::blocks(h->hs_H.S), dim3(256), h->stream, h->ev_X, h->hs_H, h->d_ev_xt, h->d_hs_lam + F.n_rows, wobj);
+        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, h->d_hs_eptr, h->d_hs_eocc, h->hs_H.hocc, nnz - nfn, h->d_hs_vals + nfn);
+    }
+    if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, h->d_hs_pptr, h->d_hs_pent, h->d_hs_poth, h->d_hs_vals, h->d_hs_v, n, h->d_hs_out);
+}
+void hs_read(asm_handle* h, const double* dev, int64_t count, double* out) {
+    if (count > 0) HIPCHK(asmb::copy_async(h->h_hs, dev, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
+    if (count > 0) std::memcpy(out, h->h_hs, count * sizeof(double));
+}
+}  // namespace
+
+static void do_hessian_structure(asm_handle* h, int64_t* nnz, int64_t* rows, int64_t* cols) {
+    hs_check(h, "asm_eval_hessian_structure");
+    if (!nnz || (rows == nullptr) != (cols == nullptr)) throw std::invalid_argument("asm_eval_hessian_structure: null pointer");
+    hs_prepare(h);
+    *nnz = (int64_t)h->hs_rows.size();
+    if (rows) {
+        std::copy(h->hs_rows.begin(), h->hs_rows.end(), rows);
+        std::copy(h->hs_cols.begin(), h->hs_cols.end(), cols);
+    }
+}
+static void do_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values) {
+    hs_check(h, "asm_eval_hessian_lagrangian");
+    if (!x || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
+    hs_prepare(h);
+    if (!h->hs_rows.empty() && !values) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
+    hs_launch(h, x, obj_factor, lambda, nullptr);
+    hs_read(h, h->d_hs_vals, (int64_t)h->hs_rows.size(), values);
+}
+static void do_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out) {
+    hs_check(h, "asm_eval_hessian_product");
+    if (!x || !v || !out || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_product: null pointer");
+    hs_launch(h, x, obj_factor, lambda, v);
+    hs_read(h, h->d_hs_out, h->n, out);
+}
+
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
 static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
     if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
@@ -3727,6 +3944,19 @@ int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double
 
 int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
     return guarded(h, [&] { do_data_gradient(h, x, lambda, out); });
+}
+
+int asm_eval_hessian_structure(const asm_handle* ch, int64_t* nnz, int64_t* rows, int64_t* cols) {
+    asm_handle* h = const_cast<asm_handle*>(ch);          // the pattern is made when it is first asked for
+    return guarded(h, [&] { do_hessian_structure(h, nnz, rows, cols); });
+}
+
+int asm_eval_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values) {
+    return guarded(h, [&] { do_hessian_lagrangian(h, x, obj_factor, lambda, values); });
+}
+
+int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out) {
+    return guarded(h, [&] { do_hessian_product(h, x, obj_factor, lambda, v, out); });
 }
 
 // --------------------------------------------------------------------------------- per-iteration reductions on the device (row f1)

@@ -91,9 +91,13 @@ class NlpBlock:
     """The `nlp_data` of the wrapper: bounds, pattern (1-based rows inside the block, 1-based columns) and callbacks
     eval_g(x, out) / eval_jac_g(x, out) in the pattern's order; `device` names a device kernel of libasmhip
     (None: host only) with its parameter arrays.  has_objective: the block also carries the objective, eval_f(x) /
-    eval_grad_f(x, grad) without the sense scale; it overrides the model's own objective (MOI_wrapper.jl:809-861)."""
+    eval_grad_f(x, grad) without the sense scale; it overrides the model's own objective (MOI_wrapper.jl:809-861).
+    Optional second derivatives (the evaluator's :Hess): hess_rows / hess_cols (1-based; an off-diagonal entry stands for both
+    symmetric positions, duplicates add) and eval_hess(x, obj_factor, lam, values) for obj_factor * hess f + sum lam_i hess g_i
+    with `lam` the block's multipliers; absent, the block announces no Hessian."""
 
-    def __init__(self, g_L, g_U, rows, cols, eval_g, eval_jac_g, device=None, has_objective=False, eval_f=None, eval_grad_f=None):
+    def __init__(self, g_L, g_U, rows, cols, eval_g, eval_jac_g, device=None, has_objective=False, eval_f=None, eval_grad_f=None,
+                 hess_rows=None, hess_cols=None, eval_hess=None):
         self.g_L, self.g_U = np.asarray(g_L, float), np.asarray(g_U, float)
         self.rows, self.cols = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
         self.eval_g, self.eval_jac_g = eval_g, eval_jac_g
@@ -102,10 +106,19 @@ class NlpBlock:
             raise ValueError("an NLP block with an objective needs eval_f and eval_grad_f")
         self.has_objective = bool(has_objective)
         self.eval_f, self.eval_grad_f = eval_f, eval_grad_f
+        self.hess_rows = None if hess_rows is None else np.asarray(hess_rows, np.int64)
+        self.hess_cols = None if hess_cols is None else np.asarray(hess_cols, np.int64)
+        self.eval_hess = eval_hess
 
     @property
     def m(self):
         return len(self.g_L)
+
+    def hessian_structure(self):
+        """(hess_rows, hess_cols) of a block that announces a Hessian."""
+        if self.eval_hess is None or self.hess_rows is None or self.hess_cols is None:
+            raise ValueError("the NLP block announces no Hessian (NlpBlock(..., hess_rows=, hess_cols=, eval_hess=))")
+        return self.hess_rows, self.hess_cols
 
 
 class FunctionModel:
@@ -205,6 +218,49 @@ class FunctionModel:
             self.nlp.eval_jac_g(x, values[off:])
         return values
 
+    # ---- MOI_wrapper.jl:748-774: one entry per stored quadratic term as given, the objective's first (unless the NLP block has
+    #      the objective), then the quadratic rows, then the block's pattern
+    def _hessian_functions(self):
+        """(function, multiplier index or None for the objective) of every function that contributes store entries, in order."""
+        out = []
+        if not (self.nlp is not None and self.nlp.has_objective) and self.objective is not None:
+            out.append((self.objective, None))
+        row = len(self.linear_le) + len(self.linear_ge) + len(self.linear_eq)
+        for lst in (self.quadratic_le, self.quadratic_ge, self.quadratic_eq):
+            for f, _ in lst:
+                out.append((f, row))
+                row += 1
+        return out
+
+    def hessian_lagrangian_structure(self):
+        h_str = [(a, b) for f, _ in self._hessian_functions() for _, a, b in f.quadratic]
+        if self.nlp is not None:
+            rows, cols = self.nlp.hessian_structure()
+            h_str += [(int(r), int(c)) for r, c in zip(rows, cols)]
+        return h_str
+
+    # ---- eval_h_cb (:1071-1083) with eval_hessian_lagrangian (:960-978) and fill_hessian_lagrangian! (:946-958):
+    #      values of obj_factor * objective_scale * hess f + sum_i lam[i] hess g_i in the pattern's order (plus sign: MOI)
+    def eval_hessian_lagrangian(self, x, obj_factor, lam, values):
+        if self.nlp is not None and self.nlp.eval_hess is None:
+            self.nlp.hessian_structure()                                            # raises: the block announces no Hessian
+        obj_factor = obj_factor * self.objective_scale                              # :1080
+        off = 0
+        for f, row in self._hessian_functions():
+            factor = obj_factor if row is None else lam[row]
+            for c, _, _ in f.quadratic:
+                values[off] = factor * c
+                off += 1
+        if self.nlp is not None:
+            self.nlp.eval_hess(x, obj_factor, np.asarray(lam, float)[self.nlp_constraint_offset:], values[off:])
+        return values
+
+    def hessian_lagrangian_product(self, x, obj_factor, lam, v):
+        """H v from the values, in the order of asm_eval_hessian_product (hessian_product below)."""
+        h_str = self.hessian_lagrangian_structure()
+        values = self.eval_hessian_lagrangian(x, obj_factor, lam, np.zeros(len(h_str)))
+        return hessian_product([r for r, _ in h_str], [c for _, c in h_str], values, v)
+
     # ---- start point (MOI_wrapper.jl:1113-1130): user start, else 0 projected onto the bounds
     def start_point(self):
         x0 = np.minimum(np.maximum(np.zeros(self.n), self.x_L), self.x_U)
@@ -256,3 +312,48 @@ class FunctionModel:
                     q_v1=i64(q1), q_v2=i64(q2), q_coef=f64(qc), constant=f64(const), jac_off=i64(jac_off[:len(fs) + 1]),
                     g_ptr=i64(g_ptr), g_kind=i64(g_kind), g_coef=f64(g_coef), g_other=i64(g_other),
                     objective_scale=self.objective_scale, nnz_functions=jac_off[len(fs)])
+
+
+# ---- the symmetric matrix behind a Hessian pattern (1-based rows / cols; an off-diagonal entry stands for both positions, duplicates add)
+def hessian_product(rows, cols, values, v):
+    """out = H v as k_hess_product forms it: out[i] sums, from 0.0 and in entry order, value * v[other index] of the entries that
+    name i (an off-diagonal entry is in the lists of both of its indices)."""
+    r, c = np.asarray(rows, np.int64) - 1, np.asarray(cols, np.int64) - 1
+    values, v = np.asarray(values, float), np.asarray(v, float)
+    e = np.arange(len(r))
+    off = r != c
+    idx = np.concatenate([r, c[off]])
+    ent = np.concatenate([e, e[off]])
+    oth = np.concatenate([c, r[off]])
+    order = np.lexsort((ent, idx))                          # by variable, then entry
+    idx, ent, oth = idx[order], ent[order], oth[order]
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(idx, minlength=len(v)))]).astype(np.int64)
+    cnt = np.diff(ptr)
+    out = np.zeros(len(v))
+    for i in range(int(cnt.max()) if len(cnt) else 0):
+        s = cnt > i
+        q = ptr[:-1][s] + i
+        out[s] = out[s] + values[ent[q]] * v[oth[q]]
+    return out
+
+
+def hessian_matrix(rows, cols, values, n, sparse=False):
+    """The symmetric n x n matrix of a pattern and its values: dense, or scipy.sparse CSR with sparse=True."""
+    r, c = np.asarray(rows, np.int64) - 1, np.asarray(cols, np.int64) - 1
+    values = np.asarray(values, float)
+    off = r != c
+    ri, ci, vv = np.concatenate([r, c[off]]), np.concatenate([c, r[off]]), np.concatenate([values, values[off]])
+    if sparse:
+        from scipy.sparse import coo_matrix
+        return coo_matrix((vv, (ri, ci)), shape=(n, n)).tocsr()
+    H = np.zeros((n, n))
+    np.add.at(H, (ri, ci), vv)
+    return H
+
+
+def lagrangian_hessian(fm, x, lam, sparse=False):
+    """The Hessian of the SLP drivers' Lagrangian f - lam' g (KT residual df - J' lam - ...) of a FunctionModel at (x, lam), e.g.
+    (mdl.x, mdl.lam) of a solved Model: the MOI Hessian at obj_factor 1 and -lam, as a symmetric matrix."""
+    h_str = fm.hessian_lagrangian_structure()
+    values = fm.eval_hessian_lagrangian(x, 1.0, -np.asarray(lam, float), np.zeros(len(h_str)))
+    return hessian_matrix([r for r, _ in h_str], [c for _, c in h_str], values, fm.n, sparse)

@@ -20,6 +20,10 @@ Parameters (JuMP-style, for scenario and sensitivity studies): p = parameters([1
 values change without a new tape.  ExprBlock(..., parameters=p) puts them at dpar[0:P] in declaration order, never merged with
 constants or with each other; set_parameter_values / asm_eval_set_data change them, data_gradient / asm_eval_data_gradient give the
 derivative of the Lagrangian with respect to every dpar entry (at an SLP solution: the derivative of the optimal value).
+
+Second derivatives: hessian_structure() / hessian_values(x, obj_factor, lam) are the host twin of the block's part of
+asm_eval_hessian_structure / asm_eval_hessian_lagrangian (forward over reverse per (row, seed variable); include/asm_hip.h,
+"Hessian of the Lagrangian"); the lists behind them are built when first asked for.
 """
 import numbers
 import struct
@@ -249,9 +253,11 @@ class _Sweep:
     """The host twin of expr_forward / expr_reverse for a group of rows: rows padded to the longest, node position k evaluated
     for all rows at once, grouped by op (each node of each row is still the one IEEE operation the kernel performs)."""
 
-    def __init__(self, ptr, op, a, b, slot):
-        self.nr = len(ptr) - 1
-        lens = np.diff(ptr)
+    def __init__(self, ptr, op, a, b, slot, lens=None):
+        """Rows ptr[r] .. ptr[r + 1]; with `lens`, row r is the nodes ptr[r] .. ptr[r] + lens[r] (rows may then repeat)."""
+        if lens is None:
+            lens = np.diff(ptr)
+        self.nr = len(lens)
         self.lens = lens
         self.K = int(lens.max()) if self.nr else 0
         self.last = lens - 1
@@ -412,6 +418,281 @@ class _Sweep:
                         W[r, c] = W[r, c] + w
 
 
+def _powi2(u, e):
+    """u ** e, its first and its second derivative with the factors of expr_powi2 (asm_eval_kernels.hip.h)."""
+    k = abs(e)
+    p, q = np.ones_like(u), np.ones_like(u)
+    for _ in range(1, k):
+        q = p
+        p = p * u
+    pk = p * u
+    ee = float(e) * float(e - 1)
+    if e > 0:
+        return pk, float(e) * p, (ee * q if k > 1 else np.zeros_like(u))
+    pu = pk * u
+    return 1.0 / pk, float(e) / pu, ee / (pu * u)
+
+
+def interaction_pairs(op, a, b):
+    """The interaction set P(last node) of one row (row-local references) as a set of (i, j), i >= j: the pattern rule of
+    include/asm_hip.h ("Hessian of the Lagrangian"), node by node."""
+    L, P = [], []
+    for o, ka, kb in zip(op.tolist(), a.tolist(), b.tolist()):
+        sq = lambda A, B: {(max(i, j), min(i, j)) for i in A for j in B}
+        if o == CONST:
+            L.append(frozenset()); P.append(frozenset())
+        elif o == VAR:
+            L.append(frozenset([ka])); P.append(frozenset())
+        elif o in (ADD, SUB, MIN, MAX):
+            L.append(L[ka] | L[kb]); P.append(P[ka] | P[kb])
+        elif o == NEG or (o == POWI and kb == 1):
+            L.append(L[ka]); P.append(P[ka])
+        elif o == MUL:
+            L.append(L[ka] | L[kb]); P.append(P[ka] | P[kb] | sq(L[ka], L[kb]))
+        elif o == DIV:
+            L.append(L[ka] | L[kb]); P.append(P[ka] | P[kb] | sq(L[ka], L[kb]) | sq(L[kb], L[kb]))
+        elif o in (POW, ATAN2):
+            L.append(L[ka] | L[kb]); P.append(frozenset(sq(L[-1], L[-1])))
+        else:                                         # every other unary op, POWI
+            L.append(L[ka]); P.append(P[ka] | sq(L[ka], L[ka]))
+    return set(P[-1])
+
+
+class _HessSweep(_Sweep):
+    """The host twin of expr_forward2 / expr_reverse2: one "row" per seed thread (a row or term of the tape with one seed variable),
+    node position k evaluated for all threads at once.  start / lens: the thread's nodes in the tape; seed: its seed variable;
+    okey: thread * n + variable of every occurrence, ascending (its index is the occurrence's place in hocc)."""
+
+    def __init__(self, start, lens, op, a, b, seed, okey, n):
+        super().__init__(start, op, a, b, np.zeros(len(op), np.int64), lens=lens)
+        self.aux = []
+        for groups in self.steps:
+            aux = []
+            for o, r, ka, kb, _ in groups:
+                if o == VAR:
+                    key = r * n + ka
+                    pos = np.minimum(np.searchsorted(okey, key), max(len(okey) - 1, 0))
+                    hit = (okey[pos] == key) if len(okey) else np.zeros(len(r), bool)
+                    aux.append(((ka == seed[r]).astype(np.float64), r[hit], pos[hit]))
+                elif o == POW:
+                    aux.append(op[start[r] + kb] == CONST)
+                else:
+                    aux.append(None)
+            self.aux.append(aux)
+
+    def forward2(self, x, consts):
+        V = np.zeros((self.nr, max(self.K, 1)))
+        D = np.zeros_like(V)
+        with np.errstate(all="ignore"):
+            for k, groups in enumerate(self.steps):
+                for (o, r, a, b, _), aux in zip(groups, self.aux[k]):
+                    if o == CONST:
+                        V[r, k] = consts[a]
+                        continue
+                    if o == VAR:
+                        V[r, k], D[r, k] = x[a], aux[0]
+                        continue
+                    u, du = V[r, a], D[r, a]
+                    if o in _BINARY:
+                        y, dy = V[r, b], D[r, b]
+                    if o == ADD:
+                        v, d = u + y, du + dy
+                    elif o == SUB:
+                        v, d = u - y, du - dy
+                    elif o == MUL:
+                        v, d = u * y, du * y + u * dy
+                    elif o == DIV:
+                        v = u / y
+                        d = (du - v * dy) / y
+                    elif o == NEG:
+                        v, d = -u, -du
+                    elif o == POWI:
+                        v, d = np.empty(len(r)), np.empty(len(r))
+                        for e in np.unique(b):
+                            s = b == e
+                            v[s], d1, _ = _powi2(u[s], int(e))
+                            d[s] = d1 * du[s]
+                    elif o == SQRT:
+                        v = np.sqrt(u)
+                        d = (0.5 * du) / v
+                    elif o == EXP:
+                        v = np.exp(u)
+                        d = du * v
+                    elif o == LOG:
+                        v, d = np.log(u), du / u
+                    elif o == SIN:
+                        v, d = np.sin(u), du * np.cos(u)
+                    elif o == COS:
+                        v, d = np.cos(u), -(du * np.sin(u))
+                    elif o == ABS:
+                        v, d = np.abs(u), du * np.copysign(1.0, u)
+                    elif o == MIN or o == MAX:
+                        c = y < u if o == MIN else y > u
+                        v, d = np.where(c, y, u), np.where(c, dy, du)
+                    elif o == POW:
+                        v = np.power(u, y)
+                        d = du * (y * np.power(u, y - 1.0))
+                        d = np.where(aux, d, d + dy * (v * np.log(u)))
+                    elif o == ATAN2:
+                        v = np.arctan2(u, y)
+                        t = u * u + y * y
+                        d = (du * y) / t - (dy * u) / t
+                    else:
+                        v = _NP_UNARY[o](u)
+                        if o == TAN:
+                            d = du * (1.0 + v * v)
+                        elif o == ASIN:
+                            d = du / np.sqrt(1.0 - u * u)
+                        elif o == ACOS:
+                            d = -(du / np.sqrt(1.0 - u * u))
+                        elif o == ATAN:
+                            d = du / (1.0 + u * u)
+                        elif o == SINH:
+                            d = du * np.cosh(u)
+                        elif o == COSH:
+                            d = du * np.sinh(u)
+                        elif o == TANH:
+                            d = du * (1.0 - v * v)
+                        elif o == LOG10:
+                            d = du / (u * LN10)
+                        elif o == LOG2:
+                            d = du / (u * LN2)
+                        elif o == LOG1P:
+                            d = du / (1.0 + u)
+                        elif o == EXPM1:
+                            d = du * (v + 1.0)
+                        else:                             # CBRT
+                            d = du / (3.0 * (v * v))
+                    V[r, k], D[r, k] = v, d
+        return V, D
+
+    def reverse2(self, V, D, hocc):
+        """Adjoints W and their tangents Z from the last node of every thread back; the adjoint tangent of a VAR node whose
+        variable is in the thread's occurrence list is added to hocc there."""
+        W = np.zeros_like(V)
+        Z = np.zeros_like(V)
+        W[np.arange(self.nr), self.last] = 1.0
+        with np.errstate(all="ignore"):
+            for k in range(self.K - 1, -1, -1):
+                for (o, r, a, b, _), aux in zip(self.steps[k], self.aux[k]):
+                    if o == CONST:
+                        continue
+                    w, z = W[r, k], Z[r, k]
+                    if o == VAR:
+                        _, rh, pos = aux
+                        hocc[pos] = hocc[pos] + Z[rh, k]
+                        continue
+                    u, du, v, d = V[r, a], D[r, a], V[r, k], D[r, k]
+                    if o in _BINARY:
+                        y, dy = V[r, b], D[r, b]
+
+                    def add(c, dw, dz):
+                        W[r, c] = W[r, c] + dw
+                        Z[r, c] = Z[r, c] + dz
+
+                    def sub(c, dw, dz):
+                        W[r, c] = W[r, c] - dw
+                        Z[r, c] = Z[r, c] - dz
+                    if o == ADD:
+                        add(a, w, z); add(b, w, z)
+                    elif o == SUB:
+                        add(a, w, z); sub(b, w, z)
+                    elif o == MUL:
+                        add(a, w * y, z * y + w * dy)
+                        add(b, w * u, z * u + w * du)
+                    elif o == DIV:
+                        t = w / y
+                        dt = (z - t * dy) / y
+                        add(a, t, dt)
+                        sub(b, t * v, dt * v + t * d)
+                    elif o == NEG:
+                        sub(a, w, z)
+                    elif o == POWI:
+                        d1, d2 = np.empty(len(r)), np.empty(len(r))
+                        for e in np.unique(b):
+                            s = b == e
+                            _, d1[s], d2[s] = _powi2(u[s], int(e))
+                        add(a, w * d1, z * d1 + w * (d2 * du))
+                    elif o == SQRT:
+                        s = (0.5 * w) / v
+                        add(a, s, (0.5 * z - s * d) / v)
+                    elif o == EXP:
+                        add(a, w * v, z * v + w * d)
+                    elif o == LOG:
+                        q = w / u
+                        add(a, q, (z - q * du) / u)
+                    elif o == SIN:
+                        c, s = np.cos(u), np.sin(u)
+                        add(a, w * c, z * c - w * (s * du))
+                    elif o == COS:
+                        c, s = np.cos(u), np.sin(u)
+                        sub(a, w * s, z * s + w * (c * du))
+                    elif o == ABS:
+                        s = np.copysign(1.0, u)
+                        add(a, w * s, z * s)
+                    elif o == TAN:
+                        g = 1.0 + v * v
+                        add(a, w * g, z * g + w * (2.0 * (v * d)))
+                    elif o == ASIN or o == ACOS:
+                        rt = np.sqrt(1.0 - u * u)
+                        q = w / rt
+                        dr = -((u * du) / rt)
+                        (add if o == ASIN else sub)(a, q, (z - q * dr) / rt)
+                    elif o == ATAN:
+                        g = 1.0 + u * u
+                        q = w / g
+                        add(a, q, (z - q * (2.0 * (u * du))) / g)
+                    elif o == SINH:
+                        c, s = np.cosh(u), np.sinh(u)
+                        add(a, w * c, z * c + w * (s * du))
+                    elif o == COSH:
+                        c, s = np.cosh(u), np.sinh(u)
+                        add(a, w * s, z * s + w * (c * du))
+                    elif o == TANH:
+                        g = 1.0 - v * v
+                        add(a, w * g, z * g - w * (2.0 * (v * d)))
+                    elif o == LOG10 or o == LOG2:
+                        ln = LN10 if o == LOG10 else LN2
+                        g = u * ln
+                        q = w / g
+                        add(a, q, (z - q * (du * ln)) / g)
+                    elif o == LOG1P:
+                        g = 1.0 + u
+                        q = w / g
+                        add(a, q, (z - q * du) / g)
+                    elif o == EXPM1:
+                        g = v + 1.0
+                        add(a, w * g, z * g + w * d)
+                    elif o == CBRT:
+                        g = 3.0 * (v * v)
+                        q = w / g
+                        add(a, q, (z - q * (6.0 * (v * d))) / g)
+                    elif o == POW:
+                        bc = aux                              # a CONST exponent: no term with dy, nothing to b
+                        p1, p2, lu = np.power(u, y - 1.0), np.power(u, y - 2.0), np.log(u)
+                        A = y * p1
+                        dp1 = du * ((y - 1.0) * p2)
+                        dp1 = np.where(bc, dp1, dp1 + dy * (p1 * lu))
+                        dA = y * dp1
+                        dA = np.where(bc, dA, dA + dy * p1)
+                        add(a, w * A, z * A + w * dA)
+                        B = v * lu
+                        dB = d * lu + v * (du / u)
+                        nb = ~bc
+                        rb, cb = r[nb], b[nb]
+                        W[rb, cb] = W[rb, cb] + (w * B)[nb]
+                        Z[rb, cb] = Z[rb, cb] + (z * B + w * dB)[nb]
+                    elif o == ATAN2:
+                        t = u * u + y * y
+                        dt = 2.0 * (u * du) + 2.0 * (y * dy)
+                        qa, qb = (w * y) / t, (w * u) / t
+                        add(a, qa, ((z * y + w * dy) - qa * dt) / t)
+                        sub(b, qb, ((z * u + w * du) - qb * dt) / t)
+                    else:                                 # MIN, MAX
+                        c = np.where(y < u if o == MIN else y > u, b, a)
+                        add(c, w, z)
+
+
 class ExprBlock(NlpBlock):
     """An NLP block of expressions: `constraints` = [(expr, lo, hi)] (lo == hi: equality; +-inf: one-sided), `objective` = an
     expression or None, `parameters` = the parameter nodes (nlexpr.parameters) the expressions use, at dpar[0:P] in this order.
@@ -425,6 +706,7 @@ class ExprBlock(NlpBlock):
             raise TypeError("parameters must be nodes made by nlexpr.parameters")
         tape = Tape([e for e, _, _ in cons] + terms, len(cons), params)
         self.n_params = len(params)
+        self.exprs = [e for e, _, _ in cons] + terms      # the graphs behind the tape: constraint rows, then objective terms
         self.tape = tape
         R, T = tape.R, tape.T
         ptr, op, a = tape.ptr, tape.op, tape.a
@@ -455,9 +737,66 @@ class ExprBlock(NlpBlock):
         self._rows = _Sweep(ptr[:R + 1], op, tape.a, tape.b, slot)
         self._terms = _Sweep(ptr[R:] - ptr[R], op[ptr[R]:], tape.a[ptr[R]:], tape.b[ptr[R]:], slot[ptr[R]:])
         self._n_occ = len(kv)
+        self._hess = None                                  # second-order lists: made when a Hessian is first asked for
         super().__init__([lo for _, lo, _ in cons], [hi for _, _, hi in cons], rows, cols, self._eval_g, self._eval_jac_g,
                          device=("expr", tape.ipar(), self._consts),
-                         has_objective=T > 0, eval_f=self._eval_f if T > 0 else None, eval_grad_f=self._eval_grad_f if T > 0 else None)
+                         has_objective=T > 0, eval_f=self._eval_f if T > 0 else None, eval_grad_f=self._eval_grad_f if T > 0 else None,
+                         eval_hess=self._eval_hess)
+
+    # ---- Hessian of the Lagrangian (the twin of asm_eval_hessian_*'s block part: k_nlp_expr_hess, k_nlp_expr_hess_gather)
+    def _hess_prepare(self):
+        if self._hess is None:
+            tape, n = self.tape, max(self.n_var, 1)
+            ptr, op, a, b = tape.ptr, tape.op, tape.a, tape.b
+            start, lens, seed, srow, okey, pairs = [], [], [], [], [], []
+            for t in range(tape.R + tape.T):
+                k0, k1 = int(ptr[t]), int(ptr[t + 1])
+                new = True
+                for j, i in sorted((j, i) for i, j in interaction_pairs(op[k0:k1], a[k0:k1], b[k0:k1])):
+                    if new or seed[-1] != j:                # one seed thread per smaller index j of the row's pairs
+                        start.append(k0); lens.append(k1 - k0); seed.append(j); srow.append(t)
+                        new = False
+                    okey.append((len(seed) - 1) * n + i)
+                    pairs.append(i * n + j)
+            i64 = lambda v: np.asarray(v, np.int64)
+            okey, pairs, srow = i64(okey), i64(pairs), i64(srow)
+            keys = np.unique(pairs)                        # the entries: distinct (i, j), i >= j, sorted by (i, j)
+            oent = np.searchsorted(keys, pairs)
+            self._hess = dict(sweep=_HessSweep(i64(start), i64(lens), op, a, b, i64(seed), okey, n), srow=srow, othread=okey // n,
+                              rows=keys // n + 1, cols=keys % n + 1, eocc=np.argsort(oent, kind="stable"),
+                              eptr=np.concatenate([[0], np.cumsum(np.bincount(oent, minlength=len(keys)))]).astype(np.int64))
+            self.hess_rows, self.hess_cols = self._hess["rows"], self._hess["cols"]
+        return self._hess
+
+    def hessian_structure(self):
+        """(rows, cols), 1-based: the distinct pairs (i, j), i >= j, sorted by (i, j), of the rows' and terms' interaction sets."""
+        H = self._hess_prepare()
+        return H["rows"], H["cols"]
+
+    def hessian_values(self, x, obj_factor, lam):
+        """Values of the block's entries of obj_factor * hess(sum of the terms) + sum_r lam[r] hess g_r (`lam`: the multipliers of the
+        block's rows; `obj_factor` with the sense scale already in it).  Per (row or term, seed variable j) a forward sweep with
+        tangent and a reverse sweep with adjoint tangents; every entry sums weight * h over its rows, then terms, from 0.0."""
+        H = self._hess_prepare()
+        x, lam = np.asarray(x, float), np.asarray(lam, float)
+        R, sweep, srow = self.tape.R, H["sweep"], H["srow"]
+        hocc = np.zeros(len(H["othread"]))
+        if sweep.nr:
+            V, D = sweep.forward2(x, self._consts)
+            sweep.reverse2(V, D, hocc)
+            wt = np.where(srow < R, lam[np.minimum(srow, R - 1)] if R else 0.0, float(obj_factor))
+            hocc = wt[H["othread"]] * hocc
+        eptr, eocc = H["eptr"], H["eocc"]
+        cnt = np.diff(eptr)
+        vals = np.zeros(len(cnt))
+        for i in range(int(cnt.max()) if len(cnt) else 0):
+            s = cnt > i
+            vals[s] = vals[s] + hocc[eocc[eptr[:-1][s] + i]]
+        return vals
+
+    def _eval_hess(self, x, obj_factor, lam, values):
+        values[:] = self.hessian_values(x, obj_factor, lam)
+        return values
 
     # ---- parameters
     def set_parameter_values(self, values):

@@ -254,6 +254,34 @@ class HipSubOptimizer:
         self._check(self._lib.asm_eval_data_gradient(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(out)))
         return out[:nd]
 
+    def hessian_structure(self):
+        """(rows, cols), 1-based, of the Hessian of the Lagrangian (asm_eval_hessian_structure): the function store's quadratic terms
+        as given, then the expression block's sorted lower-triangle pairs; an off-diagonal entry stands for both positions."""
+        nnz = C.c_int64(0)
+        self._check(self._lib.asm_eval_hessian_structure(self._h, C.byref(nnz), None, None))
+        rows, cols = np.zeros(max(nnz.value, 1), np.int64), np.zeros(max(nnz.value, 1), np.int64)
+        self._check(self._lib.asm_eval_hessian_structure(self._h, C.byref(nnz), _lib.i64ptr(rows), _lib.i64ptr(cols)))
+        return rows[:nnz.value], cols[:nnz.value]
+
+    def eval_hessian_lagrangian(self, x, obj_factor, lam):
+        """Values of obj_factor * objective_scale * hess f + sum_i lam[i] hess g_i at x in the pattern's order
+        (asm_eval_hessian_lagrangian; MOI sign: pass -lam for slp_run's multipliers)."""
+        x, lam = _f64(x), _f64(np.atleast_1d(lam) if self.m else np.zeros(1))
+        assert len(x) == self.n and len(lam) >= self.m
+        nnz = C.c_int64(0)
+        self._check(self._lib.asm_eval_hessian_structure(self._h, C.byref(nnz), None, None))
+        values = np.empty(max(nnz.value, 1))
+        self._check(self._lib.asm_eval_hessian_lagrangian(self._h, _lib.dptr(x), float(obj_factor), _lib.dptr(lam), _lib.dptr(values)))
+        return values[:nnz.value]
+
+    def hessian_product(self, x, obj_factor, lam, v):
+        """H v with H the symmetric matrix of eval_hessian_lagrangian(x, obj_factor, lam) (asm_eval_hessian_product)."""
+        x, v, lam = _f64(x), _f64(v), _f64(np.atleast_1d(lam) if self.m else np.zeros(1))
+        assert len(x) == self.n and len(v) == self.n and len(lam) >= self.m
+        out = np.empty(self.n)
+        self._check(self._lib.asm_eval_hessian_product(self._h, _lib.dptr(x), float(obj_factor), _lib.dptr(lam), _lib.dptr(v), _lib.dptr(out)))
+        return out
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)

@@ -259,6 +259,64 @@ int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double
  * host twin (nlexpr.py: ExprBlock.data_gradient) agree bit for bit with ADD..POWI, ABS, MIN and MAX only, else in the last bits. */
 int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out);
 
+/* ---- Hessian of the Lagrangian: hessian_lagrangian_structure / eval_hessian_lagrangian (MOI_wrapper.jl:748-774, 946-978; eval_h_cb :1071-1083)
+ *   H = obj_factor * objective_scale * hess f + sum_i lambda_i hess g_i        lambda [m], PLUS sign (the MOI convention, :960-978, :1080)
+ * asm_slp_run's multipliers belong to df - J'lambda: the Hessian of that Lagrangian is this one at (obj_factor 1, -lambda).
+ * Valid after asm_eval_setup (ASM_ERR_STATE before) for the function store alone (nlp_kind 0) or with an expression block (kind 3); kinds 1
+ * and 2 and null pointers: ASM_ERR_ARG.  The calls do not touch the inputs of the next LP, the retained basis or hints (as
+ * asm_eval_constraints).  Pattern, lists and workspace are made by the first of these calls after asm_eval_setup.
+ * Pattern (rows, cols 1-based; an off-diagonal entry (i, j) stands for both symmetric positions; duplicates add), in this order:
+ *   1. function store, as the reference: the objective row's quadratic terms (only when the block has no objective, T == 0), then the
+ *      quadratic rows in row order; one entry per stored term, (q_v1 + 1, q_v2 + 1) as given - not sorted, not brought to one triangle,
+ *      duplicates kept.  Value = factor * q_coef, factor = obj_factor * objective_scale (one product) or lambda[row].
+ *   2. expression block: the distinct pairs (i, j), i >= j, sorted by (i, j), of the union over rows and terms of each one's interaction set
+ *      P(last node).  With L(k) the variables node k depends on:
+ *        CONST, VAR: P = {}        ADD SUB NEG MIN MAX: P(a) u P(b)        MUL: P(a) u P(b) u L(a) x L(b)
+ *        DIV: P(a) u P(b) u L(a) x L(b) u L(b) x L(b)        POWI with exponent 1: P(a)        POW ATAN2: (L(a) u L(b))^2
+ *        every other unary op and POWI: P(a) u L(a) x L(a)
+ *      (pairs unordered, stored with the larger index first).
+ *   Value of a block entry (i, j): the sum from 0.0, in (row, then term) order, of wt * h over the rows and terms whose interaction set
+ *   holds the pair; wt = lambda[n_rows + r] for row r, obj_factor * objective_scale for a term; h = d2(row) / dx_i dx_j by forward over
+ *   reverse with seed j: the forward sweep carries the tangent d of every node value for x' = e_j, the reverse sweep the tangent z of every
+ *   adjoint, and h is the adjoint tangent that reaches the VAR nodes of variable i (several VAR nodes: added in reverse node order from 0.0).
+ *   The formulas are the tangents of the first-order statements, statement by statement (u, y, v, w as above; du, dy, d = tangents of u, y,
+ *   v; z = tangent of w; "tadj" the adjoint tangents; each parenthesis one rounding, no fused multiply-add):
+ *     ADD  d = du + dy                     tadj[a] += z;  tadj[b] += z           (SUB: d = du - dy, tadj[b] -= z;  NEG: d = -du, tadj[a] -= z)
+ *     MUL  d = du*y + u*dy                 tadj[a] += (z*y + w*dy);  tadj[b] += (z*u + w*du)
+ *     DIV  d = (du - v*dy) / y             t = w/y;  dt = (z - t*dy) / y;  tadj[a] += dt;  tadj[b] -= (dt*v + t*d)
+ *     POWI d = d1*du                       tadj[a] += (z*d1 + w*(d2*du)),  d1 as the first order, d2 = e (e-1) u^(e-2): ((double)e * (double)(e-1))
+ *                                          times the product of |e| - 2 factors u from 1.0 (e >= 2), 0.0 (e = 1), ee / ((u^|e| * u) * u) (e < 0)
+ *     SQRT d = (0.5*du) / v                s = (0.5*w) / v;  tadj[a] += (0.5*z - s*d) / v
+ *     EXP  d = du*v                        tadj[a] += (z*v + w*d)
+ *     LOG  d = du / u                      q = w/u;  tadj[a] += (z - q*du) / u
+ *     SIN  d = du*cos(u)                   tadj[a] += (z*cos(u) - w*(sin(u)*du))
+ *     COS  d = -(du*sin(u))                tadj[a] -= (z*sin(u) + w*(cos(u)*du))
+ *     ABS  d = du*copysign(1.0, u)         tadj[a] += z*copysign(1.0, u)                                       (zero curvature)
+ *     TAN  d = du*(1 + v*v)                g = 1 + v*v;  tadj[a] += (z*g + w*(2*(v*d)))
+ *     ASIN d = du / sqrt(1 - u*u)          r = sqrt(1 - u*u);  q = w/r;  dr = -((u*du) / r);  tadj[a] += (z - q*dr) / r      (ACOS: d, tadj negated)
+ *     ATAN d = du / (1 + u*u)              g = 1 + u*u;  q = w/g;  tadj[a] += (z - q*(2*(u*du))) / g
+ *     SINH d = du*cosh(u)                  tadj[a] += (z*cosh(u) + w*(sinh(u)*du))
+ *     COSH d = du*sinh(u)                  tadj[a] += (z*sinh(u) + w*(cosh(u)*du))
+ *     TANH d = du*(1 - v*v)                g = 1 - v*v;  tadj[a] += (z*g - w*(2*(v*d)))
+ *     LOG10 d = du / (u*ln10)              g = u*ln10;  q = w/g;  tadj[a] += (z - q*(du*ln10)) / g                            (LOG2: ln2)
+ *     LOG1P d = du / (1 + u)               g = 1 + u;  q = w/g;  tadj[a] += (z - q*du) / g
+ *     EXPM1 d = du*(v + 1)                 g = v + 1;  tadj[a] += (z*g + w*d)
+ *     CBRT d = du / (3*(v*v))              g = 3*(v*v);  q = w/g;  tadj[a] += (z - q*(6*(v*d))) / g
+ *     POW  p1 = pow(u, y-1), p2 = pow(u, y-2), lu = log(u), A = y*p1, B = v*lu;  d = du*A, then d = d + dy*B;
+ *          dp1 = du*((y-1)*p2), then dp1 = dp1 + dy*(p1*lu);  dA = y*dp1, then dA = dA + dy*p1;  tadj[a] += (z*A + w*dA);
+ *          dB = d*lu + v*(du/u);  tadj[b] += (z*B + w*dB).  A CONST b: every "then" step and the statements on b are left out.
+ *     ATAN2 t = u*u + y*y;  d = (du*y)/t - (dy*u)/t;  dt = 2*(u*du) + 2*(y*dy);  qa = (w*y)/t;  qb = (w*u)/t;
+ *          tadj[a] += ((z*y + w*dy) - qa*dt) / t;  tadj[b] -= ((z*u + w*du) - qb*dt) / t
+ *     MIN / MAX  d and z follow the chosen operand (same tie rule)
+ *   With ADD..POWI, ABS, MIN and MAX only, device values equal the host twin (nlexpr.py: ExprBlock.hessian_values) bit for bit.
+ * asm_eval_hessian_structure: *nnz and, unless rows == cols == NULL, the pattern.
+ * asm_eval_hessian_lagrangian: values [nnz] at (x, obj_factor, lambda).
+ * asm_eval_hessian_product: out [n] = H v from those values: out[i] sums, from 0.0 and in entry order over all nnz entries, value * v[other
+ * index] of the entries that name i (an off-diagonal entry contributes to both of its indices).  No atomics anywhere. */
+int asm_eval_hessian_structure(const asm_handle* h, int64_t* nnz, int64_t* rows, int64_t* cols);
+int asm_eval_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values);
+int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out);
+
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
 int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4);
