@@ -110,6 +110,9 @@ PROTOTYPES = {
     "asm_batch_get_stats": (C.c_int, [_P, C.POINTER(BatchStats)]),
     "asm_test_syrk": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, _D, C.c_int]),
     "asm_test_syrk_update": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, C.c_int]),
+    "asm_test_build_flagged": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, C.c_int, C.c_int, _D, C.c_int64, C.POINTER(C.c_ubyte), _D]),
+    "asm_test_build_split": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, C.c_int, C.c_double, C.c_double, _D, _D, _D, _D]),
+    "asm_test_build_dispatch": (C.c_int, [_P, _D, C.c_int, _I32, C.c_int64, _D, _D, _D, _D, _I64, _I32, _I32, _I32]),
     "asm_test_cholesky": (C.c_int, [_P, _D, C.c_int64, _D]),
     "asm_test_chol_solve": (C.c_int, [_P, _D, C.c_int64, _D, _D]),
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),

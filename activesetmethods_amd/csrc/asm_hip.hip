@@ -627,7 +627,7 @@ struct Dev {
             const int TS = 32 * T, nt = (Ms + TS - 1) / TS;
             if (h->nz_valid && nt > 0) {
                 unsigned char* nz2 = h->d_nz + h->nz_half;
-                asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, A, ld, (int64_t)Ms, TS, nch, nz2, nch, idx_dev);
+                launch_tile_flags(A, ld, Ms, T, nch, nz2, nch, idx_dev);
                 frac = executed_fraction(nz2, nt, nch, cache_slot);
                 nz = nz2;
             }
@@ -670,6 +670,20 @@ struct Dev {
         zero_band(f, n, h->col_band);
         asmb::launch(k_schur_sparse, asmb::blocks(h->n_colpairs), dim3(256), h->stream, h->d_colpairs, h->n_colpairs, h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah),
                      dinv_dev, diag_place, f.S, f.ld, h->d_sc_pos);
+    }
+    // S0 = A_EF diag(Fm) A_EF' of the null-space form (equality rows in their reverse Cuthill-McKee order, Fm in h->d_nsFm) into h->ns_f0.S
+    void ns_build_S0() {
+        const int nE = h->ns_nE;
+        if (h->ns_f0.band > 0) {
+            // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
+            // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
+            zero_band(h->ns_f0, nE, h->ns_f0.band);
+            asmb::launch(k_ns_s0_sparse, asmb::blocks(h->ns_npairs), dim3(256), h->stream, h->d_nsS0pairs, h->ns_npairs, h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah),
+                         h->d_nsEidx, h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
+        } else {
+            // S0 = A_EF A_EF' (the share of its chunk products cached per handle: the equality rows are fixed)
+            schur_syrk(false, h->d_nsEidx, nE, h->d_nsFm, nullptr, h->ns_f0.S, h->ns_f0.ld, NzFlags::PerCall, 1);
+        }
     }
     // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32
     void gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, const double* C0, int64_t ldc0, double* C, int64_t ldc, int Ma, int Mb, int K, int mode) {
@@ -724,7 +738,7 @@ struct Dev {
         if (!h->dense_fast && nch <= ASM_MAXCHUNKS && h->nnz * 8 <= h->M * h->n) {
             const int T = pick_tile(h->n), TS = 32 * T;
             const int nt = (int)((h->n + TS - 1) / TS);
-            asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, h->d_AhT, h->ldT, h->n, TS, nch, h->d_nzT, nch, nullptr);
+            launch_tile_flags(h->d_AhT, h->ldT, h->n, T, nch, h->d_nzT, nch, nullptr);
             h->nzT_fraction = executed_fraction(h->d_nzT, nt, nch);
             h->nzT_valid = true;
         }
@@ -741,9 +755,14 @@ struct Dev {
         const int TS = 32 * h->nz_T;
         const int nt = (int)((h->M + TS - 1) / TS);
         h->nz_pitch = nch;
-        asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, h->d_Ah, h->ldn, h->M, TS, nch, h->d_nz, h->nz_pitch, nullptr);
+        launch_tile_flags(h->d_Ah, h->ldn, h->M, h->nz_T, nch, h->d_nz, h->nz_pitch, nullptr);
         h->nz_valid = true;
         h->nz_fraction = executed_fraction(h->d_nz, nt, nch, 0);
+    }
+    // nz[t][c] (pitch nzpitch) = tile t (32 T rows of the list idx, or of the first Ms rows) of A has a non-zero in k-chunk c < nch
+    void launch_tile_flags(const double* A, int64_t ld, int64_t Ms, int T, int nch, unsigned char* nz, int nzpitch, const int* idx_dev) {
+        const int TS = 32 * T, nt = (int)((Ms + TS - 1) / TS);
+        asmb::launch(k_tile_nzflags, dim3((unsigned)nt, (unsigned)((nch + 7) / 8)), dim3(256), h->stream, A, ld, Ms, TS, nch, nz, nzpitch, idx_dev);
     }
     // fraction of (tile pair, chunk) products actually executed: keeps the flop accounting of the roofline honest
     double executed_fraction(const unsigned char* d_flags, int nt, int nch, int cache_slot = -1) {
@@ -823,8 +842,29 @@ struct Dev {
                          nzpitch, ksplit);
     }
 
-    void diag_prepare(const FacBuf& f, int Ms, int mode, double rel, double absv) {
-        asmb::launch(k_diag_prepare, dim3(1), dim3(1024), h->stream, f.S, f.ld, Ms, h->d_diag0, mode, rel, absv);
+    void diag_prepare(const FacBuf& f, int Ms, int mode, double rel, double absv, double* diag0 = nullptr) {
+        asmb::launch(k_diag_prepare, dim3(1), dim3(1024), h->stream, f.S, f.ld, Ms, diag0 ? diag0 : h->d_diag0, mode, rel, absv);
+    }
+    // The k x k matrix of a null-space iteration, fN.S (lower) = G diag(theta) G' with its diagonal regularised (S_ii += rel S_ii + absv, the
+    // plain diagonal kept in diag0), and its unregularised copy N0 (pitch fN.ld; mirrored into the upper triangle for the small systems).
+    // G is k x K (pitch K).  nsplit > 1: split-K, the slices summed into `parts` (nsplit copies, fN.ld^2 doubles apart) and added in a fixed
+    // order while the copy is made.  Everything up to the factorisation.
+    void ns_newton_matrix(const double* G, int64_t K, const double* theta, int k, int nsplit, double* parts, const FacBuf& fN, double* N0, double* diag0, double rel,
+                          double absv) {
+        int id = begin(ASM_K_SYRK, (double)k * (k + 1) * K, 8.0 * (k * (double)K + 0.5 * k * (double)k));
+        const int T = pick_tile(k);
+        if (nsplit > 1) {
+            const int64_t pstride = fN.ld * fN.ld;
+            launch_syrk(h->stream, T, G, K, nullptr, 0, k, (int)K, theta, nullptr, parts, fN.ld, 0, 0, -1, nullptr, 0, -1.0, nsplit, pstride);
+            end(id);
+            asmb::launch(k_ns_reduce_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, parts, nsplit, pstride, fN.ld, fN.S, N0, k,
+                         k <= ASM_SMALL_USE ? 1 : 0, diag0, rel, absv);      // (+ k_diag_prepare, mode 0)
+        } else {
+            launch_syrk(h->stream, T, G, K, nullptr, 0, k, (int)K, theta, nullptr, fN.S, fN.ld, 0, 0);
+            end(id);
+            asmb::launch(k_ns_copy_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, fN.S, fN.ld, N0, fN.ld, k, k <= ASM_SMALL_USE ? 1 : 0);
+            diag_prepare(fN, k, 0, rel, absv, diag0);
+        }
     }
     template <int WB>
     void trtri_launches(const FacBuf& f, int Ms) {
@@ -1438,16 +1478,7 @@ struct Solver {
             std::fprintf(stderr, "[asm] ns set-up %-10s +%.2f ms\n", what, t - t_v);
             t_v = t;
         };
-        if (h->ns_f0.band > 0) {
-            // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
-            // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
-            dev.zero_band(h->ns_f0, nE, h->ns_f0.band);
-            asmb::launch(k_ns_s0_sparse, asmb::blocks(h->ns_npairs), dim3(256), h->stream, h->d_nsS0pairs, h->ns_npairs, h->d_sp_ptr, h->d_sp_col, dev.sparse_vals(h->d_Ah),
-                         h->d_nsEidx, h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
-        } else {
-            // S0 = A_EF A_EF' (the share of its chunk products cached per handle: the equality rows are fixed)
-            dev.schur_syrk(false, h->d_nsEidx, nE, h->d_nsFm, nullptr, h->ns_f0.S, h->ns_f0.ld, Dev::NzFlags::PerCall, 1);
-        }
+        dev.ns_build_S0();
         vlap("S0 build");
         dev.diag_prepare(h->ns_f0, nE, 1, 0.0, 0.0);
         dev.chol(h->ns_f0, nE, 1e-10);
@@ -1638,7 +1669,6 @@ struct Solver {
         const double* th = h->d_nsth;
         const double* thI = h->d_nsth + ldn;
         // (theta~ was formed with the interior-point theta: k_ipm_theta_ns in ipm_run)
-        int id = dev.begin(ASM_K_SYRK, (double)k * (k + 1) * h->ns_ldg, 8.0 * (k * (double)h->ns_ldg + 0.5 * k * (double)k));
         // the k range (free columns + inequality rows, 19 000 at n = 11 192) is long and the matrix small (k = 519: 45 tiles of 64 x 64):
         // split-K fills the chip; the slices are added in a fixed order while the unregularised copy N0 is made
         // (measured at k = 519, k range 19 000: 32 x 32 tiles x 8 slices 1.19 ms per iteration, 64 x 64 x 8 1.21, 32 x 32 x 4 1.21, unsplit 1.40)
@@ -1646,19 +1676,7 @@ struct Solver {
         const int64_t ntile = ((k + 32 * T - 1) / (32 * T));
         int nsplit = (int)std::min<int64_t>(NS_MAX_SPLIT, std::max<int64_t>(1, 1224 / std::max<int64_t>(1, ntile * (ntile + 1) / 2)));
         nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, h->ns_ldg / 512));
-        if (nsplit > 1) {
-            const int64_t pstride = h->ns_fN.ld * h->ns_fN.ld;
-            dev.launch_syrk(h->stream, T, h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->d_nsNp, h->ns_fN.ld, 0, 0, -1, nullptr, 0, -1.0, nsplit, pstride);
-            dev.end(id);
-            asmb::launch(k_ns_reduce_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_nsNp, nsplit, pstride, h->ns_fN.ld, h->ns_fN.S, h->d_nsN0, k,
-                         k <= ASM_SMALL_USE ? 1 : 0, h->d_diag0, 1e-13, 1e-30);      // (+ k_diag_prepare, mode 0)
-        } else {
-            dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ns_ldg, h->d_nsth, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
-            dev.end(id);
-            asmb::launch(k_ns_copy_lower, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->ns_fN.S, h->ns_fN.ld, h->d_nsN0, h->ns_fN.ld, k,
-                         k <= ASM_SMALL_USE ? 1 : 0);
-            dev.diag_prepare(h->ns_fN, k, 0, 1e-13, 1e-30);
-        }
+        dev.ns_newton_matrix(h->d_nsG, h->ns_ldg, h->d_nsth, k, nsplit, h->d_nsNp, h->ns_fN, h->d_nsN0, h->d_diag0, 1e-13, 1e-30);
         dev.chol(h->ns_fN, k, 1e-14, false);
         // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
         double* e = nsv(14);
@@ -4167,6 +4185,135 @@ int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const in
         HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
             HIPCHK(asmb::copy(S_out + i * Ms, F.S + i * F.ld, Ms * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+// The chunk-skipping build on buffers of the caller's: S (ldS x ldS, pre-filled by the caller) gets A[rows] diag(theta) A[rows]' + diag in the lower
+// triangle of its first Ms rows, launched as Dev::schur_syrk launches a PerCall build - k_tile_nzflags for the row list, then k_syrk with the
+// chunk flags (use_flags = 0: the same launch without them, the dense sweep).  Returns the flags (nt x K / 32 bytes) and their executed share.
+int asm_test_build_flagged(asm_handle* h, const double* A, int64_t M, int64_t K, const int32_t* idx, int64_t Ms, const double* theta, const double* diag, int tile,
+                           int use_flags, double* S_inout, int64_t ldS, unsigned char* flags_out, double* fraction_out) {
+    return guarded(h, [&] {
+        if (!A || !theta || !S_inout || !flags_out || !fraction_out || M <= 0 || Ms <= 0 || K <= 0 || K % ASM_KC != 0 || K / ASM_KC > ASM_MAXCHUNKS || ldS < Ms ||
+            (!idx && Ms > M) || !(tile == 0 || tile == 1 || tile == 2 || tile == 4))
+            throw std::invalid_argument("asm_test_build_flagged: bad argument");
+        if (idx) for (int64_t a = 0; a < Ms; ++a) if (idx[a] < 0 || idx[a] >= M) throw std::invalid_argument("asm_test_build_flagged: row index out of range");
+        HIPCHK(hipSetDevice(h->device));
+        Dev d(h);
+        const int T = tile > 0 ? tile : Dev::pick_tile(Ms), TS = 32 * T, nt = (int)((Ms + TS - 1) / TS), nch = (int)(K / ASM_KC);
+        double *dA = nullptr, *dth = nullptr, *ddg = nullptr, *dS = nullptr;
+        int* didx = nullptr;
+        unsigned char* dnz = nullptr;
+        BufPool tmp;
+        tmp.upload(dA, A, M * K); tmp.upload(dth, theta, K); tmp.upload(dS, S_inout, ldS * ldS);
+        if (diag) tmp.upload(ddg, diag, Ms);
+        if (idx) tmp.upload(didx, idx, Ms);
+        tmp.zeroed(dnz, (int64_t)nt * nch);
+        d.launch_tile_flags(dA, K, Ms, T, nch, dnz, nch, didx);
+        const double frac = d.executed_fraction_now(dnz, nt, nch);
+        d.launch_syrk(h->stream, T, dA, K, didx, 0, (int)Ms, (int)K, dth, ddg, dS, ldS, 0, 0, -1, use_flags ? dnz : nullptr, nch, frac);
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(S_inout, dS, ldS * ldS * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(flags_out, dnz, (size_t)nt * nch, hipMemcpyDeviceToHost));
+        *fraction_out = frac;
+        d.resolve_timing();
+    });
+}
+
+// The k x k matrix of a null-space iteration on buffers of the caller's, by the statements of the solver (Dev::ns_newton_matrix: split-K build
+// + reduction for nsplit > 1, else the plain build, its copy and k_diag_prepare).  G is k x K; every output has the pitch ld = k rounded up to
+// 32 and is pre-filled by the caller: parts (nsplit x ld x ld; untouched for nsplit = 1), S, N0 (ld x ld each), diag0 (ld).
+int asm_test_build_split(asm_handle* h, const double* G, int64_t k, int64_t K, const double* theta, int nsplit, double rel, double absv, double* parts_inout,
+                         double* S_inout, double* N0_inout, double* diag0_inout) {
+    return guarded(h, [&] {
+        if (!G || !theta || !parts_inout || !S_inout || !N0_inout || !diag0_inout || k <= 0 || K <= 0 || K % ASM_KC != 0 || nsplit < 1 || nsplit > NS_MAX_SPLIT)
+            throw std::invalid_argument("asm_test_build_split: bad argument");
+        HIPCHK(hipSetDevice(h->device));
+        Dev d(h);
+        FacBuf f;
+        f.ld = round_up(k, 32);
+        const int64_t sq = f.ld * f.ld;
+        double *dG = nullptr, *dth = nullptr, *dP = nullptr, *dN0 = nullptr, *dd0 = nullptr;
+        BufPool tmp;
+        tmp.upload(dG, G, k * K); tmp.upload(dth, theta, K); tmp.upload(dP, parts_inout, nsplit * sq);
+        tmp.upload(f.S, S_inout, sq); tmp.upload(dN0, N0_inout, sq); tmp.upload(dd0, diag0_inout, f.ld);
+        d.ns_newton_matrix(dG, K, dth, (int)k, nsplit, dP, f, dN0, dd0, rel, absv);
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(parts_inout, dP, nsplit * sq * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(S_inout, f.S, sq * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(N0_inout, dN0, sq * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(diag0_inout, dd0, f.ld * sizeof(double), hipMemcpyDeviceToHost));
+        d.resolve_timing();
+    });
+}
+
+// The builds of a set-up handle through the solver's dispatch.  The Jacobian is assembled from dE and scaled by rows only (unit column scale),
+// the chunk flags made as at the start of an LP; then build `which`: 0 Dev::schur_syrk with Pattern flags over all rows; 1 the same on the
+// transposed copy (column form, theta = M weights, diag = n); 2 Dev::schur_rows of the row list idx (diag by place); 3
+// Dev::schur_banded_cols_dev (columns in their banded order, diag by place); 4 Dev::ns_build_S0 (theta = the n column weights); < 0 nothing.
+// The matrix is built in the factor buffer the solver uses, loaded from S_inout before (ld x ld with ld = info[4], or info[7] for which = 4)
+// and returned in it.  info: M, n, row_band, col_band, main pitch, nE, S0 band, S0 pitch, column form possible, row flags valid, column
+// flags valid, sparse pattern.  Ah_out: the operand as it stands on the device (M x n); orders (position -> index; -1 without one).
+int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const int32_t* idx, int64_t Ms, const double* theta, const double* diag, double* S_inout,
+                            double* Ah_out, int64_t* info, int32_t* row_order, int32_t* col_order, int32_t* e_order) {
+    return guarded(h, [&] {
+        if (!h->setup_done) throw std::logic_error("asm_test_build_dispatch: asm_sublp_setup first");
+        if (!info || (h->nnz > 0 && !dE) || which > 4) throw std::invalid_argument("asm_test_build_dispatch: bad argument");
+        HIPCHK(hipSetDevice(h->device));
+        const int64_t M = h->M, n = h->n;
+        Dev d(h);
+        HIPCHK(asmb::copy(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice));
+        h->J_valid = false;
+        d.assemble();
+        vec c(n, 1.0), rho(M);
+        d.scale(c.data(), rho.data());
+        d.tile_flags();
+        const bool ns = h->ns_cap;
+        const int64_t out[12] = {M, n, h->row_band, h->col_band, h->main_fac.ld, ns ? h->ns_nE : 0, ns ? h->ns_f0.band : 0, ns ? h->ns_f0.ld : 0, h->col_capable ? 1 : 0,
+                                 h->nz_valid ? 1 : 0, 0, h->sp_ok ? 1 : 0};
+        for (int k = 0; k < 12; ++k) info[k] = out[k];
+        if (Ah_out) for (int64_t i = 0; i < M; ++i) HIPCHK(asmb::copy(Ah_out + i * n, h->d_Ah + i * h->ldn, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (row_order) for (int64_t q = 0; q < M; ++q) row_order[q] = h->row_band > 0 ? h->row_perm_h[q] : -1;
+        if (col_order) {
+            if (h->col_band > 0) HIPCHK(asmb::copy(col_order, h->d_colperm, n * sizeof(int), hipMemcpyDeviceToHost));
+            else for (int64_t q = 0; q < n; ++q) col_order[q] = -1;
+        }
+        if (e_order && ns) for (int q = 0; q < h->ns_nE; ++q) e_order[q] = h->ns_eidx_h[q];
+        if (which < 0) return;
+        const FacBuf& f = which == 4 ? h->ns_f0 : h->main_fac;
+        const int64_t nth = (which == 1 || which == 3) ? M : n, ndg = which == 0 ? M : ((which == 1 || which == 3) ? n : Ms);
+        if (!theta || !S_inout || (which == 2 && (!idx || Ms <= 0 || Ms > M)) || ((which == 1 || which == 3) && (!h->col_capable || !diag)) ||
+            (which == 3 && h->col_band <= 0) || (which == 4 && !ns) || ((which == 1 || which == 3) && n > f.ld) || (which == 0 && M == 0))
+            throw std::invalid_argument("asm_test_build_dispatch: build not available on this handle");
+        double *dth = nullptr, *ddg = nullptr;
+        BufPool tmp;
+        tmp.zeroed(dth, std::max(h->ldn, h->Mp) + 64);
+        HIPCHK(asmb::copy(dth, theta, nth * sizeof(double), hipMemcpyHostToDevice));
+        if (diag && which != 4) tmp.upload(ddg, diag, ndg);
+        HIPCHK(asmb::copy(f.S, S_inout, f.ld * f.ld * sizeof(double), hipMemcpyHostToDevice));
+        switch (which) {
+        case 0: d.schur_syrk(false, nullptr, (int)M, dth, ddg, f.S, f.ld, Dev::NzFlags::Pattern); break;
+        case 1: d.schur_syrk(true, nullptr, (int)n, dth, ddg, f.S, f.ld, Dev::NzFlags::Pattern); break;
+        case 2: {
+            for (int64_t a = 0; a < Ms; ++a) if (idx[a] < 0 || idx[a] >= M) throw std::invalid_argument("asm_test_build_dispatch: row index out of range");
+            HIPCHK(asmb::copy(h->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
+            if (h->row_band > 0) {      // place of every row in the list (-1: not in it), as the reduced row form makes it
+                std::vector<int> cp(M, -1);
+                for (int64_t a = 0; a < Ms; ++a) cp[idx[a]] = (int)a;
+                HIPCHK(asmb::copy(h->d_cpos, cp.data(), M * sizeof(int), hipMemcpyHostToDevice));
+            }
+            d.schur_rows(h->d_idx, h->d_cpos, (int)Ms, dth, ddg);
+            break;
+        }
+        case 3: d.schur_banded_cols_dev(dth, ddg); break;
+        default:
+            HIPCHK(asmb::copy(h->d_nsFm, dth, h->ldn * sizeof(double), hipMemcpyDeviceToDevice));
+            d.ns_build_S0();
+        }
+        HIPCHK(asmb::sync(h->stream));
+        info[10] = h->nzT_valid ? 1 : 0;
+        HIPCHK(asmb::copy(S_inout, f.S, f.ld * f.ld * sizeof(double), hipMemcpyDeviceToHost));
+        d.resolve_timing();
     });
 }
 

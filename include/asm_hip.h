@@ -461,6 +461,26 @@ int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const in
 /* S[a,b] -= sum_k P[a,k] P[b,k], a >= b (b < MsB when MsB >= 0), the block at (srow0, srow0) of a larger matrix: the Cholesky update */
 int asm_test_syrk_update(asm_handle* h, const double* P /* Ms*K */, int64_t Ms, int64_t K, int64_t MsB, int64_t srow0,
                          double* S_inout /* Ms*Ms */, int tile);
+/* Test hook: the chunk-skipping Schur build as Dev::schur_syrk launches it for a row list (k_tile_nzflags, then k_syrk with the chunk list;
+ * use_flags = 0: the same launch without flags), on the caller's operand A (M x K, K a multiple of 32, at most 32768).  tile 1 / 2 / 4, or 0 =
+ * the solver's choice for Ms.  S_inout (ldS x ldS) is pre-filled by the caller; flags_out holds ceil(Ms / (32 tile)) x K / 32 bytes. */
+int asm_test_build_flagged(asm_handle* h, const double* A, int64_t M, int64_t K, const int32_t* idx /* Ms or NULL */, int64_t Ms,
+                           const double* theta /* K */, const double* diag /* Ms or NULL */, int tile, int use_flags, double* S_inout,
+                           int64_t ldS, unsigned char* flags_out, double* fraction_out);
+/* Test hook: the k x k matrix of a null-space iteration as the solver builds it, up to its factorisation (nsplit > 1: split-K slices and their
+ * reduction; 1: the plain build, its copy and the diagonal preparation).  G is k x K; with ld = k rounded up to 32 the caller pre-fills
+ * parts_inout (nsplit x ld x ld), S_inout, N0_inout (ld x ld) and diag0_inout (ld). */
+int asm_test_build_split(asm_handle* h, const double* G, int64_t k, int64_t K, const double* theta /* K */, int nsplit, double rel,
+                         double absv, double* parts_inout, double* S_inout, double* N0_inout, double* diag0_inout);
+/* Test hook: the Newton-matrix builds of a handle set up by asm_sublp_setup, through the solver's own dispatch.  The Jacobian is assembled
+ * from dE and scaled by rows (unit column scale).  which: 0 all rows (Pattern flags), 1 column form on the transposed copy, 2 the row list
+ * idx (gathered with per-call flags, or from the structural pairs in a banded row order), 3 column form from the structural column pairs,
+ * 4 S0 of the null-space form, < 0 only the outputs below.  S_inout is the whole factor buffer (info[4]^2 doubles, info[7]^2 for which = 4),
+ * pre-filled by the caller.  info (12): M, n, row_band, col_band, main pitch, nE, S0 band, S0 pitch, column form possible, row flags valid,
+ * column flags valid, sparse pattern.  Ah_out: the operand on the device (M x n).  Orders: position -> index, -1 without one. */
+int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const int32_t* idx, int64_t Ms, const double* theta,
+                            const double* diag, double* S_inout, double* Ah_out, int64_t* info, int32_t* row_order, int32_t* col_order,
+                            int32_t* e_order);
 int asm_test_cholesky(asm_handle* h, const double* S /* N*N sym */, int64_t N, double* L_out /* N*N lower */);
 int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x);
 /* the bounded wait of the dataflow panel kernel with a producer that never publishes: returns ASM_ERR_HIP (reported once), the

@@ -300,3 +300,155 @@ def expected_dropped(levels, setting):
     if mode == 0 and absv > 0.0:
         drop &= lv > 0.0           # S_jj = 0 + absv > thr * 0: a zero row is kept (its unknown is b_j / absv)
     return np.flatnonzero(drop)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# Newton-matrix builds (tests/test_builds_cpu.py, tests/test_builds_gpu.py): operands, the long-double reference and the rounding bound
+U = 2.0 ** -53
+SENTINEL = -7.25          # finite pre-fill of every output buffer: what a kernel does not own must keep it bit for bit
+
+# (name, Ms, K, tile (0 = the solver's choice), gathered row list, diag given) - what each case is there for:
+#   t1-long / t2-long / t4-long: K = 4096, the chunk list of the full tile has 128 entries (second ballot pass of k_syrk)
+#   t1-pairs (78 tile pairs), t4-pairs (78), t2-grid (Ms = 2100, 33 tiles = 561 tile pairs: a second dealt run and a second grid block of 512)
+#   t1-maxchunks: K = 32768 = ASM_MAXCHUNKS chunks;  pick: tile chosen by the solver's rule (Ms = 800 -> 64 rows)
+FLAGGED_CASES = [
+    ("t1-long", 100, 4096, 1, False, True),
+    ("t1-pairs", 370, 512, 1, True, False),
+    ("t1-maxchunks", 125, 32768, 1, False, True),
+    ("t2-long", 200, 4096, 2, True, True),
+    ("t2-grid", 2100, 256, 2, False, False),
+    ("t4-long", 300, 4096, 4, False, True),
+    ("t4-pairs", 1420, 256, 4, True, False),
+    ("pick", 800, 512, 0, True, True),
+]
+
+
+def pick_tile(Ms):
+    """The solver's tile choice (Dev::pick_tile)."""
+    return 4 if Ms >= 3072 else (2 if Ms >= 768 else 1)
+
+
+def flagged_operand(seed, Ms, K, tile, gathered, with_diag):
+    """Block-sparse operand of a chunk-skipping build.  With TS = 32 * tile rows per tile and 32 columns per chunk: tile 0 has a non-zero in
+    every chunk, tiles 1 and 2 hold the even and the odd chunks only (their lists do not intersect), every other tile a random eighth to
+    half of the chunks.  Inside a flagged (tile, chunk) block 30 % of the entries are set, in the top half of the tile's rows only, the
+    bottom half only, or all of them (flags computed from part of a tile's rows are wrong).  gathered: the rows sit at a non-monotone
+    permutation idx of a subset of a taller matrix whose other rows are dense.  theta is positive over eight decades with exact zeros and
+    one negative entry.  Returns A, idx (int32 or None), theta, diag (or None)."""
+    rng = np.random.default_rng(seed)
+    T = tile if tile > 0 else pick_tile(Ms)
+    TS, nch = 32 * T, K // 32
+    nt = (Ms + TS - 1) // TS
+    assert nt >= 3 and K % 32 == 0
+    B = np.zeros((Ms, K))
+    for t in range(nt):
+        r0, r1 = t * TS, min(Ms, (t + 1) * TS)
+        if t == 0:
+            on = np.ones(nch, bool)
+        elif t in (1, 2):
+            on = (np.arange(nch) % 2) == (t - 1)
+            on &= rng.random(nch) < 0.6
+            on[t - 1] = True
+        else:
+            on = rng.random(nch) < rng.uniform(0.125, 0.5)
+        for c in np.nonzero(on)[0]:
+            part = rng.integers(0, 3)
+            h = max(1, (r1 - r0) // 2)
+            a, b = (r0, r0 + h) if part == 0 else ((r0 + h, r1) if part == 1 and r0 + h < r1 else (r0, r1))
+            blk = np.where(rng.random((b - a, 32)) < 0.3, rng.standard_normal((b - a, 32)), 0.0)
+            if not blk.any():
+                blk[rng.integers(0, b - a), rng.integers(0, 32)] = 1.0 + rng.random()
+            B[a:b, 32 * c:32 * c + 32] = blk
+    theta = 10.0 ** rng.uniform(-4.0, 4.0, K)
+    theta[rng.random(K) < 0.05] = 0.0
+    theta[int(rng.integers(0, K))] = -3.5
+    diag = rng.uniform(0.5, 2.0, Ms) * 10.0 ** rng.uniform(-2, 2, Ms) if with_diag else None
+    if not gathered:
+        return B, None, theta, diag
+    M = Ms + Ms // 3 + 5
+    idx = rng.permutation(M)[:Ms].astype(np.int32)
+    assert np.any(np.diff(idx) < 0)
+    A = rng.standard_normal((M, K))
+    A[idx] = B
+    return A, idx, theta, diag
+
+
+def tile_chunk_flags(A, idx, Ms, TS):
+    """flags[t, c] = any(A[rows of tile t, 32 c : 32 c + 32] != 0) for the row list idx (None: the first Ms rows), tiles of TS rows."""
+    B = A[idx] if idx is not None else A[:Ms]
+    nt, nch = (Ms + TS - 1) // TS, A.shape[1] // 32
+    P = np.zeros((nt * TS, A.shape[1]), bool)
+    P[:Ms] = B != 0
+    return P.reshape(nt, TS, nch, 32).any(axis=(1, 3)).astype(np.uint8)
+
+
+def executed_fraction(flags):
+    """Share of the (tile pair, chunk) products a chunk-skipping build executes (the host formula of Dev::executed_fraction_now)."""
+    nt, nch = flags.shape
+    act = tot = 0.0
+    for a in range(nt):
+        for b in range(a + 1):
+            act += float(np.count_nonzero(flags[a] & flags[b]))
+            tot += float(nch)
+    return act / tot if tot > 0 else 1.0
+
+
+def build_reference(B, theta, diag=None, block=256):
+    """Lower triangles (the rest zero) of  ref = B diag(theta) B' + diag  and  mag = |B| diag(|theta|) |B|' + |diag|  in long double, and of
+    keff[i, j] = number of k with B_ik theta_k B_jk != 0 (int64)."""
+    Ms = B.shape[0]
+    Bl = B.astype(np.longdouble)
+    Wl = Bl * theta.astype(np.longdouble)
+    ind = ((B != 0) & (theta != 0)).astype(np.float64)
+    ref = np.zeros((Ms, Ms), np.longdouble)
+    mag = np.zeros((Ms, Ms), np.longdouble)
+    for i0 in range(0, Ms, block):
+        i1 = min(Ms, i0 + block)
+        ref[i0:i1, :i1] = Wl[i0:i1] @ Bl[:i1].T
+        mag[i0:i1, :i1] = np.abs(Wl[i0:i1]) @ np.abs(Bl[:i1]).T
+    keff = np.rint(ind @ ind.T).astype(np.int64)
+    if diag is not None:
+        ref[np.arange(Ms), np.arange(Ms)] += diag.astype(np.longdouble)
+        mag[np.arange(Ms), np.arange(Ms)] += np.abs(diag).astype(np.longdouble)
+    return np.tril(ref), np.tril(mag), np.tril(keff)
+
+
+def rounding_bound_ratio(S, ref, mag, keff, extra=0):
+    """Largest |S - ref| / (gamma_n mag) over the lower triangle, n = keff + 2 + extra per entry, gamma_n = n u / (1 - n u): the bound of
+    any summation order of keff non-zero products, with or without FMA (one rounding for theta, one per accumulated product, one for the
+    diagonal term; `extra` for the additions of split-K slices).  Entries with keff = 0 and no diagonal term must be exactly 0.0 (ratio inf
+    otherwise); with mag > 0 only from the diagonal term they must be exactly it, which the bound n = 2 allows for and `exact` reports."""
+    Ms = ref.shape[0]
+    low = np.tril(np.ones((Ms, Ms), bool))
+    n = (keff + 2 + extra).astype(np.longdouble)
+    gam = n * np.longdouble(U) / (1 - n * np.longdouble(U))
+    err = np.abs(S[:Ms, :Ms].astype(np.longdouble) - ref)
+    bound = gam * mag
+    ratio = np.zeros((Ms, Ms), np.longdouble)
+    pos = low & (bound > 0)
+    ratio[pos] = err[pos] / bound[pos]
+    ratio[low & (bound == 0) & (err != 0)] = np.inf
+    exact = bool(np.all(err[low & (keff == 0)] == 0))          # no product at all: exactly the diagonal term, or 0.0
+    return float(ratio.max()), exact
+
+
+# split-K builds of the k x k matrix of the null-space form: (k, K / 32, slice counts)
+SPLIT_KS = [1, 31, 32, 33, 137, 256, 257, 519, 530]
+SPLIT_CHUNKS = [1, 7, 8, 9, 16]
+SPLIT_COUNTS = [1, 2, 3, 4, 8]
+SPLIT_CASES = [(k, c, SPLIT_COUNTS) for k in SPLIT_KS for c in SPLIT_CHUNKS] + [(137, 599, [1, 3, 8]), (519, 599, [8])]      # (519, 599 x 32 = 19168, 8): the C4 shape
+
+
+def split_operand(seed, k, K):
+    """G (k x K, 70 % zeros) and a positive theta spread over eight decades (an interior point near convergence)."""
+    rng = np.random.default_rng(seed)
+    G = np.where(rng.random((k, K)) < 0.3, rng.standard_normal((k, K)), 0.0)
+    theta = 10.0 ** rng.uniform(-4.0, 4.0, K)
+    return G, theta
+
+
+def split_ranges(K, nsplit):
+    """Column range [k0, k1) of every slice of a split-K build: per = ceil((K / 32) / nsplit) * 32 columns each, the trailing ones short or empty."""
+    nch = K // 32
+    per = ((nch + nsplit - 1) // nsplit) * 32
+    return [(min(K, s * per), min(K, (s + 1) * per)) for s in range(nsplit)]
