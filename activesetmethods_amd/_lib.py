@@ -39,6 +39,15 @@ class SlpTrInfo(C.Structure):
     _fields_ = [("delta", C.c_double), ("accepted", C.c_int32), ("rejected", C.c_int32), ("shrunk", C.c_int32), ("expanded", C.c_int32)]
 
 
+class IpmStage(C.Structure):
+    """asm_ipm_stage: one stage of asm_test_ipm_stages (include/asm_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("spec", C.c_int32), ("sexp", C.c_int32), ("origin", C.c_int32), ("dir", C.c_int32),
+                ("with_e", C.c_int32), ("D", C.c_int32), ("B", C.c_int32), ("pub", C.c_uint32),
+                ("tp", C.c_double), ("td", C.c_double), ("res", C.c_double), ("crel", C.c_double), ("floor_", C.c_double), ("rho_p", C.c_double),
+                ("mu_factor", C.c_double), ("al", C.c_double), ("be", C.c_double), ("fixed", C.c_double),
+                ("x", C.c_int64 * 4), ("ix", C.c_int64 * 2), ("len", C.c_int64 * 3)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
@@ -113,6 +122,8 @@ PROTOTYPES = {
     "asm_test_build_flagged": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, C.c_int, C.c_int, _D, C.c_int64, C.POINTER(C.c_ubyte), _D]),
     "asm_test_build_split": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, C.c_int, C.c_double, C.c_double, _D, _D, _D, _D]),
     "asm_test_build_dispatch": (C.c_int, [_P, _D, C.c_int, _I32, C.c_int64, _D, _D, _D, _D, _I64, _I32, _I32, _I32]),
+    "asm_test_ipm_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I64, _D, C.c_int64, _I32, C.c_int64, _D, _D, C.POINTER(C.c_uint32),
+                                      _D, C.POINTER(C.c_uint32), C.POINTER(IpmStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_cholesky": (C.c_int, [_P, _D, C.c_int64, _D]),
     "asm_test_chol_solve": (C.c_int, [_P, _D, C.c_int64, _D, _D]),
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),

@@ -725,8 +725,12 @@ struct Dev {
     }
     // out[i] = sum_j Ah_ij^2 thinv_j   (sparse patterns only)
     void schur_diag(const double* thinv_dev, double* out_dev) {
-        const double* v = sparse_vals(h->d_Ah);
-        asmb::launch(k_ipm_sdiag_csr, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, v, thinv_dev, out_dev, h->M);
+        launch_sdiag_csr(h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), thinv_dev, out_dev, h->M);
+    }
+    unsigned launch_sdiag_csr(const int* ptr, const int* col, const double* vals, const double* thinv_dev, double* out_dev, int64_t M) {
+        const dim3 g = asmb::blocks(M);
+        asmb::launch(k_ipm_sdiag_csr, g, dim3(256), h->stream, ptr, col, vals, thinv_dev, out_dev, M);
+        return g.x;
     }
     // transposed copy of Ah and its chunk flags (column form of the restoration-phase Newton system), once per LP
     void ensure_AhT() {
@@ -1140,6 +1144,16 @@ struct SLP {
     double scale_q;
 };
 
+// Pitches and buffer lengths of the device-resident interior-point state for an LP of n columns, M rows and ns slack columns
+// (do_setup allocates by them; Solver::ipm_bind places the vectors)
+struct IpmLayout {
+    int64_t ldn, Mp, nsp;
+    IpmLayout(int64_t n, int64_t M, int64_t ns) : ldn(round_up(n, 32)), Mp(round_up(std::max<int64_t>(M, 1), 16)), nsp(round_up(std::max<int64_t>(ns, 1), 16)) {}
+    int64_t arena_len() const { return 24 * ldn + 23 * Mp + 16 * nsp + 64; }
+    int64_t snap_len() const { return 6 * ldn + 3 * Mp + 3 * nsp; }
+    int64_t int_len() const { return 3 * Mp + nsp; }
+};
+
 struct Solver {
     // out = A x for a k x ncols matrix of few, long rows (the basis Zt): one workgroup per row when that fills the chip better
     void gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
@@ -1184,9 +1198,26 @@ struct Solver {
     IpmDir dirA, dirC;
     double *d_sres = nullptr, *d_corr = nullptr, *d_tN = nullptr, *d_pcg = nullptr;
 
+    // where the interior-point state lives: the handle's arena (ipm_bind()), or buffers of a test hook's with the same pitches
+    struct IpmArena {
+        double* base = nullptr;       // IpmLayout::arena_len() doubles
+        int* ibase = nullptr;         // rtype | rs0 | rs1 (pitch lm each) | srow
+        double* snap = nullptr;       // best-iterate snapshot (IpmLayout::snap_len() doubles)
+        int64_t ln = 0, lm = 0, ls = 0;
+        double* hscal = nullptr; unsigned* hseq = nullptr; double* rpart = nullptr; unsigned* rcnt = nullptr;
+    } arena;
     void ipm_bind() {
-        double* a = h->d_ipm;
-        const int64_t ln = h->ldn, lm = h->Mp, ls = h->nsp;
+        IpmArena a;
+        a.base = h->d_ipm; a.ibase = h->d_ipm_i; a.snap = h->d_ipm_snap;
+        a.ln = h->ldn; a.lm = h->Mp; a.ls = h->nsp;
+        a.hscal = h->d_hscal; a.hseq = h->d_hseq; a.rpart = h->d_redpart; a.rcnt = h->d_redcnt;
+        ipm_bind(a);
+    }
+    // the ONLY place that lays the arena out
+    void ipm_bind(const IpmArena& ar) {
+        arena = ar;
+        double* a = ar.base;
+        const int64_t ln = ar.ln, lm = ar.lm, ls = ar.ls;
         auto N = [&]() { double* r_ = a; a += ln; return r_; };
         auto Mv = [&]() { double* r_ = a; a += lm; return r_; };
         auto Sv = [&]() { double* r_ = a; a += ls; return r_; };
@@ -1206,9 +1237,57 @@ struct Solver {
         P.s = Sv(); P.ts = Sv(); P.mus = Sv(); P.rds = Sv(); P.ths_inv = Sv(); P.hs = Sv(); P.rcs = Sv();
         dirA.ds = Sv(); dirA.dmus = Sv(); dirC.ds = Sv(); dirC.dmus = Sv();
         P.scal = a;
-        P.hscal = h->d_hscal; P.hseq = h->d_hseq;
-        P.rpart = h->d_redpart; P.rcnt = h->d_redcnt;
-        P.rtype = h->d_ipm_i; P.rs0 = h->d_ipm_i + lm; P.rs1 = h->d_ipm_i + 2 * lm; P.srow = h->d_ipm_i + 3 * lm;
+        P.hscal = ar.hscal; P.hseq = ar.hseq;
+        P.rpart = ar.rpart; P.rcnt = ar.rcnt;
+        P.rtype = ar.ibase; P.rs0 = ar.ibase + lm; P.rs1 = ar.ibase + 2 * lm; P.srow = ar.ibase + 3 * lm;
+    }
+    // ---- launch sites of the stage kernels (asm_ipm_kernels.hip.h): the solver and the test hook asm_test_ipm_stages launch through these
+    // members only; each returns the number of workgroups it launched
+    unsigned launch_init_p(int origin) { const unsigned g = grid_all(); asmb::launch(k_ipm_init_p, dim3(g), dim3(256), h->stream, P, origin); return g; }
+    unsigned launch_init_rest(double mu_factor) { const unsigned g = grid_all(); asmb::launch(k_ipm_init_rest, dim3(g), dim3(256), h->stream, P, mu_factor); return g; }
+    unsigned launch_measures(unsigned pub) { const unsigned g = red_grid(); asmb::launch(k_ipm_measures, dim3(g), dim3(1024), h->stream, P, pub); return g; }
+    unsigned launch_theta(double rho_p) { const unsigned g = grid_all(); asmb::launch(k_ipm_theta, dim3(g), dim3(256), h->stream, P, rho_p); return g; }
+    unsigned launch_rhs1(const IpmDir& base, int mode, double tp, double td) {
+        const unsigned g = grid_all();
+        asmb::launch(k_ipm_rhs1, dim3(g), dim3(256), h->stream, P, base, mode, tp, td, MCC_BMIN, MCC_BMAX);
+        return g;
+    }
+    unsigned launch_rhs2(double res) { const unsigned g = grid_all(); asmb::launch(k_ipm_rhs2, dim3(g), dim3(256), h->stream, P, res); return g; }
+    unsigned launch_vec_mul(double* x, const double* a, int64_t len) { const dim3 g = asmb::blocks(len); asmb::launch(k_vec_mul, g, dim3(256), h->stream, x, a, len); return g.x; }
+    unsigned launch_res(const double* dy, unsigned pub, int spec, double crel, double floor_) {
+        asmb::launch(k_ipm_res, dim3(1), dim3(1024), h->stream, P, d_sres, dy, pub, spec, crel, floor_);
+        return 1;
+    }
+    unsigned launch_pcg_start() { asmb::launch(k_pcg_start, dim3(1), dim3(1024), h->stream, P, d_corr, d_pcg); return 1; }
+    unsigned launch_pcg_step1(double* x, unsigned pub) { asmb::launch(k_pcg_step1, dim3(1), dim3(1024), h->stream, P, d_sres, d_pcg, x, pub); return 1; }
+    unsigned launch_pcg_step2() { asmb::launch(k_pcg_step2, dim3(1), dim3(1024), h->stream, P, d_corr, d_pcg); return 1; }
+    unsigned launch_dir(const IpmDir& D) { const unsigned g = grid_all(); asmb::launch(k_ipm_dir, dim3(g), dim3(256), h->stream, P, D, d_tN); return g; }
+    unsigned launch_steps(const IpmDir& D, unsigned pub) { const unsigned g = red_grid(); asmb::launch(k_ipm_steps, dim3(g), dim3(1024), h->stream, P, D, pub); return g; }
+    unsigned launch_muaff(const IpmDir& A_, int sexp) { const unsigned g = red_grid(); asmb::launch(k_ipm_muaff, dim3(g), dim3(1024), h->stream, P, A_, sexp); return g; }
+    unsigned launch_diradd(const IpmDir& D, const IpmDir& E) { const unsigned g = grid_all(); asmb::launch(k_ipm_diradd, dim3(g), dim3(256), h->stream, P, D, E); return g; }
+    unsigned launch_update(const IpmDir& C, double al, double be) { const unsigned g = grid_all(); asmb::launch(k_ipm_update, dim3(g), dim3(256), h->stream, P, C, al, be); return g; }
+    // best-iterate snapshot: dir 0 saves the iterate (and e, the null-space form's component, when given), 1 brings it back
+    unsigned launch_snapshot(double* e, int dir) {
+        const unsigned g = grid_all();
+        asmb::launch(k_ipm_snapshot, dim3(g), dim3(256), h->stream, P, arena.snap, e, arena.ln, arena.lm, arena.ls, dir);
+        return g;
+    }
+    unsigned launch_col_prep(double rho_p, double fixed, double* dinv, double* th) {
+        const unsigned g = grid_all();
+        asmb::launch(k_ipm_col_prep, dim3(g), dim3(256), h->stream, P, rho_p, fixed, dinv, th);
+        return g;
+    }
+    unsigned launch_col_scale(const double* dinv, const double* r, double* u) { const dim3 g = asmb::blocks(lp.M); asmb::launch(k_col_scale, g, dim3(256), h->stream, dinv, r, u, lp.M); return g.x; }
+    unsigned launch_col_finish(const double* dinv, const double* u, const double* w, double* out) {
+        const dim3 g = asmb::blocks(lp.M);
+        asmb::launch(k_col_finish, g, dim3(256), h->stream, dinv, u, w, out, lp.M);
+        return g.x;
+    }
+    unsigned launch_red_gather(const int* idx, int cnt, const double* in, double* out) { const dim3 g = asmb::blocks(cnt); asmb::launch(k_red_gather, g, dim3(256), h->stream, idx, cnt, in, out); return g.x; }
+    unsigned launch_red_scatter(const int* idx, int cnt, const double* ze, const int* didx, int ndrop, const double* ddrop, const double* in, double* out, int64_t len) {
+        const dim3 g = asmb::blocks(len);
+        asmb::launch(k_red_scatter, g, dim3(256), h->stream, idx, cnt, ze, didx, ndrop, ddrop, in, out);
+        return g.x;
     }
     void up(const double* dst, const vec& v) {
         if (!v.empty()) HIPCHK(asmb::copy_async((void*)dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1300,9 +1379,9 @@ struct Solver {
         ip.usable[(int)NewtonForm::Column] = h->col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
         ipm_upload_lp();
         P.ncomp = ip.ncomp;
-        asmb::launch(k_ipm_init_p, dim3(grid_all()), dim3(256), h->stream, P, lp.ns == 0 ? 1 : 0);
+        launch_init_p(lp.ns == 0 ? 1 : 0);
         dev.gemv_n_dev(h->d_Ah, P.p, P.act);
-        asmb::launch(k_ipm_init_rest, dim3(grid_all()), dim3(256), h->stream, P, lp.ns == 0 ? IPM_MU0_NORMAL : 1.0);
+        launch_init_rest(lp.ns == 0 ? IPM_MU0_NORMAL : 1.0);
     }
 
     void ipm_measures() {
@@ -1311,11 +1390,11 @@ struct Solver {
         const unsigned pub = pub_next();
         if (ns_live()) {
             // null-space form: the equality rows' multipliers are carried as 0, the dual residual that counts is Z'rdp (oracle: IPM.measures)
-            asmb::launch(k_ipm_measures, dim3(red_grid()), dim3(1024), h->stream, P, 0u);
+            launch_measures(0u);
             gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)P.rdp, nsv(12), (int64_t)ip.ns_k, h->ldn);
             asmb::launch(k_ns_dinf, dim3(1), dim3(1024), h->stream, P, nsv(12), ip.ns_k, pub);
         } else {
-            asmb::launch(k_ipm_measures, dim3(red_grid()), dim3(1024), h->stream, P, pub);
+            launch_measures(pub);
         }
         read_scal(pub);
         ip.pinf = h->h_scal[SC_PINF];
@@ -1753,14 +1832,13 @@ struct Solver {
     // out = in through the main factor of a row (column) list: gather in[idx[0:cnt]], solve, scatter back; k_red_scatter gives the
     // ndrop rows didx outside the list out = in / ddrop (pure permutations: none).  The scatter covers `len` rows.
     void solve_list(const int* idx, int cnt, const int* didx, int ndrop, const double* ddrop, const double* in, double* out, int64_t len) {
-        asmb::launch(k_red_gather, asmb::blocks(cnt), dim3(256), h->stream, idx, cnt, in, h->d_rce);
+        launch_red_gather(idx, cnt, in, h->d_rce);
         dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, cnt);
-        asmb::launch(k_red_scatter, asmb::blocks(len), dim3(256), h->stream, idx, cnt, h->d_rze, didx, ndrop, ddrop, in, out);
+        launch_red_scatter(idx, cnt, h->d_rze, didx, ndrop, ddrop, in, out, len);
     }
     // out = (approximate) S^-1 in : the Cholesky factor of S (row forms) or Sherman-Morrison-Woodbury through the factor of K (column form)
     void precond(const double* in, double* out) {
         const int M = (int)lp.M, n = (int)lp.n;
-        const unsigned gm = (unsigned)((lp.M + 255) / 256);
         switch (form) {
         case NewtonForm::ReducedRow:
             solve_list(h->d_idx, (int)red.kept.size(), h->d_idxI, (int)red.diag.size(), h->d_rdI, in, out, M);
@@ -1769,12 +1847,12 @@ struct Solver {
             solve_list(h->d_rowperm, M, h->d_rowperm, 0, h->d_rze, in, out, M);
             return;
         case NewtonForm::Column:
-            asmb::launch(k_col_scale, dim3(gm), dim3(256), h->stream, h->d_cdinv, in, h->d_cu, lp.M);      // u = D^-1 r
+            launch_col_scale(h->d_cdinv, in, h->d_cu);                                                                 // u = D^-1 r
             dev.gemv_t_dev(h->d_Ah, h->d_cu, h->d_ct);                                                                 // Ah' u
             if (h->col_band > 0) solve_list(h->d_colperm, n, h->d_colperm, 0, h->d_rze, h->d_ct, h->d_cv, n);         // K^-1 (columns in banded order)
             else dev.chol_solve_dev(h->main_fac, h->d_ct, h->d_cv, n);                                                 // K^-1
             dev.gemv_n_dev(h->d_Ah, h->d_cv, h->d_cw);                                                                 // Ah v
-            asmb::launch(k_col_finish, dim3(gm), dim3(256), h->stream, h->d_cdinv, h->d_cu, h->d_cw, out, lp.M);
+            launch_col_finish(h->d_cdinv, h->d_cu, h->d_cw, out);
             return;
         default:      // Row (the null-space form solves in ns_newton)
             dev.chol_solve_dev(h->main_fac, in, out, M);
@@ -1786,53 +1864,51 @@ struct Solver {
     // the residual check is not waited for - its verdict travels in scal[SC_SPEC] with the next block the iteration reads (ipm_run redoes the
     // iteration's solves with spec = 0 when one of them missed its tolerance: one host round trip per solve less in the common case).
     void ipm_solve(int mode, const IpmDir& base, IpmDir& D, double tp = 0.0, double td = 0.0, int spec = 0) {
-        const unsigned g = grid_all();
-        
-        asmb::launch(k_ipm_rhs1, dim3(g), dim3(256), h->stream, P, base, mode, tp, td, MCC_BMIN, MCC_BMAX);
+        launch_rhs1(base, mode, tp, td);
         dev.gemv_n_dev(h->d_Ah, P.tmpn, P.t1);
-        asmb::launch(k_ipm_rhs2, dim3(g), dim3(256), h->stream, P, mode == 2 ? 0.0 : 1.0);
+        launch_rhs2(mode == 2 ? 0.0 : 1.0);
         precond(P.rhs, D.dy);
         if (spec) {
             dev.gemv_t_dev(h->d_Ah, D.dy, d_tN);
-            asmb::launch(k_vec_mul, asmb::blocks(lp.n), dim3(256), h->stream, d_tN, P.thp_inv, lp.n);
+            launch_vec_mul(d_tN, P.thp_inv, lp.n);
             dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
-            asmb::launch(k_ipm_res, dim3(1), dim3(1024), h->stream, P, d_sres, D.dy, 0u, spec, 1e-10, PCG_KAPPA * ip.rpmax);
+            launch_res(D.dy, 0u, spec, 1e-10, PCG_KAPPA * ip.rpmax);
         } else {
             // preconditioned CG on the unregularised Schur system, the Cholesky factor as preconditioner (oracle: IPM.run.solve).
             // The residual of this system is exactly the primal residual the step leaves behind, hence the tolerance.
             auto applyS = [&](const double* v) {          // d_sres = Ah Th^-1 Ah' v
                 dev.gemv_t_dev(h->d_Ah, v, d_tN);
-                asmb::launch(k_vec_mul, asmb::blocks(lp.n), dim3(256), h->stream, d_tN, P.thp_inv, lp.n);
+                launch_vec_mul(d_tN, P.thp_inv, lp.n);
                 dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
             };
             applyS(D.dy);
             unsigned pub = pub_next();
-            asmb::launch(k_ipm_res, dim3(1), dim3(1024), h->stream, P, d_sres, D.dy, pub, 0, 0.0, 0.0);
+            launch_res(D.dy, pub, 0, 0.0, 0.0);
             read_scal(pub);
             // the approximate preconditioners (column and reduced row form) get the tighter floor (oracle: IPM.run.solve)
             const bool approx = form == NewtonForm::Column || form == NewtonForm::ReducedRow;
             const double tol = std::max((approx ? 1e-13 : 1e-10) * h->h_scal[SC_RMAX], PCG_KAPPA * ip.rpmax);
             if (h->h_scal[SC_EMAX] > tol) {
                 precond(P.res, d_corr);
-                asmb::launch(k_pcg_start, dim3(1), dim3(1024), h->stream, P, d_corr, d_pcg);
+                launch_pcg_start();
                 bool converged = false;
                 for (int it = 0; it < PCG_MAXIT; ++it) {
                     applyS(d_pcg);
                     pub = pub_next();
-                    asmb::launch(k_pcg_step1, dim3(1), dim3(1024), h->stream, P, d_sres, d_pcg, D.dy, pub);
+                    launch_pcg_step1(D.dy, pub);
                     read_scal(pub);
                     h->stats_pcg += 1;
                     cg_max = std::max(cg_max, it + 1);
                     if (h->h_scal[SC_STOP] != 0.0) break;
                     if (h->h_scal[SC_EMAX] <= tol) { converged = true; break; }
                     precond(P.res, d_corr);
-                    asmb::launch(k_pcg_step2, dim3(1), dim3(1024), h->stream, P, d_corr, d_pcg);
+                    launch_pcg_step2();
                 }
                 if (!converged) cg_fail = true;
             }
         }
         dev.gemv_t_dev(h->d_Ah, D.dy, d_tN);
-        asmb::launch(k_ipm_dir, dim3(g), dim3(256), h->stream, P, D, d_tN);
+        launch_dir(D);
     }
 
     // reduced row form (oracle: IPM.run): inequality rows whose slack term dominates their Schur diagonal stay out of the factor and get a
@@ -1874,10 +1950,10 @@ struct Solver {
         case NewtonForm::Column:
             ip.col_iters += 1;
             dim = n;
-            asmb::launch(k_ipm_col_prep, dim3(grid_all()), dim3(256), h->stream, P, IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
+            launch_col_prep(IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
             if (h->col_band > 0) {
                 // columns in their banded order: K built from the structural column pairs, factor and substitutions stop at the band
-                asmb::launch(k_red_gather, asmb::blocks(lp.n), dim3(256), h->stream, h->d_colperm, (int)lp.n, h->d_cth, h->d_diag);
+                launch_red_gather(h->d_colperm, (int)lp.n, h->d_cth, h->d_diag);
                 dev.schur_banded_cols_dev(h->d_cdinv, h->d_diag);
             } else {
                 dev.schur_syrk(true, nullptr, n, h->d_cdinv, h->d_cth, f.S, f.ld, Dev::NzFlags::Pattern);
@@ -1906,7 +1982,7 @@ struct Solver {
         }
         case NewtonForm::BandedRow:
             // full row form, rows in the banded order: S is built entry by entry, factor and substitutions stop at the band
-            asmb::launch(k_red_gather, asmb::blocks(lp.M), dim3(256), h->stream, h->d_rowperm, M, P.dS, h->d_diag);
+            launch_red_gather(h->d_rowperm, M, P.dS, h->d_diag);
             dev.schur_banded_dev(h->d_rowpos, M, P.thp_inv, h->d_diag);
             break;
         default:      // Row
@@ -1966,7 +2042,7 @@ struct Solver {
                 asmb::launch(k_ipm_theta_ns, dim3(std::max(grid_all(), (unsigned)((std::max<int64_t>(h->ldn, h->ns_nIp) + 255) / 256))), dim3(256), h->stream, P, IPM_RHO_P, nsX(),
                              h->d_nsth, h->ldn, h->ns_nIp);
             else
-                asmb::launch(k_ipm_theta, dim3(grid_all()), dim3(256), h->stream, P, IPM_RHO_P);
+                launch_theta(IPM_RHO_P);
             form = choose_form();
             newton_factor();
             const bool ns = form == NewtonForm::NullSpace;
@@ -1980,15 +2056,15 @@ struct Solver {
                 cg_max = 0;
                 cg_fail = false;
                 if (ns) ns_newton(0, dirA, dirA); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
-                asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirA, 0u);
-                asmb::launch(k_ipm_muaff, dim3(red_grid()), dim3(1024), h->stream, P, dirA, IPM_SIG_EXP);
+                launch_steps(dirA, 0u);
+                launch_muaff(dirA, IPM_SIG_EXP);
                 if (ns) ns_newton(1, dirA, dirC); else ipm_solve(1, dirA, dirC, 0.0, 0.0, deferred ? 2 : 0);
                 if (ns && ns_defer) {       // step lengths stay on the device (k_ns_update_dev below)
-                    asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirC, 0u);
+                    launch_steps(dirC, 0u);
                     return true;
                 }
                 unsigned pub = pub_next();
-                asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirC, pub);
+                launch_steps(dirC, pub);
                 read_scal(pub);
                 if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
                 ap = h->h_scal[SC_AP]; ad = h->h_scal[SC_AD];
@@ -1997,9 +2073,9 @@ struct Solver {
                     if (std::min(ap, ad) >= 0.9) break;
                     const double tp = std::min(1.0, ap + MCC_DELTA), td = std::min(1.0, ad + MCC_DELTA);
                     ipm_solve(2, dirC, dirA, tp, td, deferred ? 2 : 0);
-                    asmb::launch(k_ipm_diradd, dim3(grid_all()), dim3(256), h->stream, P, dirA, dirC);
+                    launch_diradd(dirA, dirC);
                     pub = pub_next();
-                    asmb::launch(k_ipm_steps, dim3(red_grid()), dim3(1024), h->stream, P, dirA, pub);
+                    launch_steps(dirA, pub);
                     read_scal(pub);
                     if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
                     const double ap2 = h->h_scal[SC_AP], ad2 = h->h_scal[SC_AD];
@@ -2029,7 +2105,7 @@ struct Solver {
                 asmb::launch(k_ns_update, dim3(grid_all()), dim3(256), h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), nsv(14), 1.0 - std::min(1.0, eta * ap),
                              h->ldn);
             else
-                asmb::launch(k_ipm_update, dim3(grid_all()), dim3(256), h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad));
+                launch_update(dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad));
             if (approx && cg_max > (form == NewtonForm::Column ? COL_MAX_CG : RED_MAX_CG)) drop_form(form);
         }
     }
@@ -2466,7 +2542,7 @@ struct Solver {
     void stats_measures() { h->stats.ipm_pinf = ip.pinf; h->stats.ipm_dinf = ip.dinf; h->stats.ipm_gap = ip.gap; }
     // best-iterate safeguard, second half (oracle: solve_scaled): the snapshot comes back, is measured and its partition identified
     void restore_best() {
-        asmb::launch(k_ipm_snapshot, dim3(grid_all()), dim3(256), h->stream, P, h->d_ipm_snap, snap_e ? nsv(14) : (double*)nullptr, h->ldn, h->Mp, h->nsp, 1);
+        launch_snapshot(snap_e ? nsv(14) : (double*)nullptr, 1);
         ipm_measures();
         stats_measures();
         h->stats.restored = 1;
@@ -2545,7 +2621,7 @@ struct Solver {
                 m_last = std::max(ip.pinf, std::max(ip.dinf, ip.gap));
                 double* e_ns = ip.ns_e_ready ? nsv(14) : nullptr;      // (set only by iterations in null-space form)
                 if (m_last < best_m) {
-                    asmb::launch(k_ipm_snapshot, dim3(grid_all()), dim3(256), h->stream, P, h->d_ipm_snap, e_ns, h->ldn, h->Mp, h->nsp, 0);
+                    launch_snapshot(e_ns, 0);
                     best_m = m_last; have_snap = true; snap_e = e_ns != nullptr;
                 }
             }
@@ -2726,8 +2802,8 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     }
     h->nadj = (int64_t)h->adj.size();
     h->M = m + h->nadj;
-    h->Mp = round_up(std::max<int64_t>(h->M, 1), 16);
-    h->ldn = round_up(n, 32);              // multiple of the SYRK k-chunk (ASM_KC)
+    h->Mp = IpmLayout(n, h->M, 0).Mp;
+    h->ldn = IpmLayout(n, h->M, 0).ldn;    // multiple of the SYRK k-chunk (ASM_KC)
     h->rtype.assign(h->M, 0);
     for (int64_t i = 0; i < m; ++i) h->rtype[i] = h->kind[i] == 0 ? 0 : (h->kind[i] == -1 ? -1 : 1);
     for (int64_t k = 0; k < h->nadj; ++k) h->rtype[m + k] = -1;
@@ -2847,11 +2923,12 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.alloc(h->d_spv_Ah, h->sp_nnz); P.alloc(h->d_spv_J, h->sp_nnz);
         h->sp_ok = true;
     }
-    h->nsp = round_up(std::max<int64_t>(h->ns, 1), 16);
+    const IpmLayout lay(n, h->M, h->ns);
+    h->nsp = lay.nsp;
     {
-        P.zeroed(h->d_ipm, 24 * h->ldn + 23 * h->Mp + 16 * h->nsp + 64, s);
-        P.alloc(h->d_ipm_snap, 6 * h->ldn + 3 * h->Mp + 3 * h->nsp);
-        std::vector<int> iv(3 * h->Mp + h->nsp, -1);
+        P.zeroed(h->d_ipm, lay.arena_len(), s);
+        P.alloc(h->d_ipm_snap, lay.snap_len());
+        std::vector<int> iv(lay.int_len(), -1);
         for (int64_t i = 0; i < h->M; ++i) iv[i] = h->rtype[i];
         for (int64_t k = 0; k < h->ns; ++k) {
             int r_ = h->srow[k];
@@ -4314,6 +4391,144 @@ int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const in
         info[10] = h->nzT_valid ? 1 : 0;
         HIPCHK(asmb::copy(S_inout, f.S, f.ld * f.ld * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
+    });
+}
+
+// The interior-point stage kernels (asm_ipm_kernels.hip.h), one launch per stage, through the launch-site members of Solver and on an arena
+// laid out by Solver::ipm_bind with the pitches of IpmLayout - see include/asm_hip.h.  Every offset and index a stage reads is checked here
+// against the buffers before anything is launched.
+int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t ncomp, double scale_q, int64_t* layout_out, double* dbl_inout, int64_t ndbl,
+                        const int32_t* ints, int64_t nint, double* snap_inout, double* rpart_inout, uint32_t* rcnt_inout, double* hscal_inout, uint32_t* hseq_inout,
+                        const asm_ipm_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return guarded(h, [&] {
+        const int64_t LIM = (int64_t)1 << 24;
+        if (!layout_out || n < 1 || M < 0 || ns < 0 || n > LIM || M > LIM || ns > LIM || ncomp < 1 || (ns > 0 && M == 0) || nstages < 0)
+            throw std::invalid_argument("asm_test_ipm_stages: bad size");
+        HIPCHK(hipSetDevice(h->device));
+        const IpmLayout lay(n, M, ns);
+        Solver S(h);
+        S.lp.n = n; S.lp.M = M; S.lp.ns = ns; S.lp.scale_q = scale_q;
+        Solver::IpmArena ar;
+        ar.ln = lay.ldn; ar.lm = lay.Mp; ar.ls = lay.nsp;
+        // the layout, from the pointers ipm_bind sets on a base address that is never dereferenced
+        ar.base = reinterpret_cast<double*>((uintptr_t)1 << 30);
+        S.ipm_bind(ar);
+        auto off = [&](const double* v) { return (int64_t)(((uintptr_t)v - (uintptr_t)ar.base) / sizeof(double)); };
+        {
+            const IpmPtrs& P = S.P;
+            const double* vs[ASM_IPM_NVEC] = {P.q, P.lb, P.ub, P.r, P.w, P.slo, P.scoef, P.p, P.s, P.g, P.y, P.tL, P.tU, P.muL, P.muU, P.ts, P.mus, P.pi, P.act, P.aty, P.rp,
+                                              P.rdp, P.rds, P.thp_inv, P.ths_inv, P.dS, P.hp, P.hs, P.tmpn, P.t1, P.rhs, P.res, P.rcL, P.rcU, P.rcs, P.rcg,
+                                              S.dirA.dp, S.dirA.ds, S.dirA.dg, S.dirA.dy, S.dirA.dmuL, S.dirA.dmuU, S.dirA.dmus, S.dirA.dpi,
+                                              S.dirC.dp, S.dirC.ds, S.dirC.dg, S.dirC.dy, S.dirC.dmuL, S.dirC.dmuU, S.dirC.dmus, S.dirC.dpi,
+                                              S.d_sres, S.d_corr, S.d_pcg, S.d_tN};
+            const int64_t head[8] = {lay.ldn, lay.Mp, lay.nsp, lay.arena_len(), lay.snap_len(), lay.int_len(), SC_COUNT, off(P.scal)};
+            for (int k = 0; k < 8; ++k) layout_out[k] = head[k];
+            for (int k = 0; k < ASM_IPM_NVEC; ++k) layout_out[8 + k] = off(vs[k]);
+            if (layout_out[7] + SC_COUNT > lay.arena_len()) throw std::logic_error("asm_test_ipm_stages: the arena is shorter than its layout");
+        }
+        if (!dbl_inout) return;      // layout query
+        if (!ints || !snap_inout || !rpart_inout || !rcnt_inout || !hscal_inout || !hseq_inout || (nstages > 0 && (!stages || !grid_out)) || ndbl < lay.arena_len() ||
+            nint < lay.int_len() || ndbl > ((int64_t)1 << 31) || nint > ((int64_t)1 << 31))
+            throw std::invalid_argument("asm_test_ipm_stages: bad buffer");
+        for (int64_t i = 0; i < M; ++i) {
+            const int rt = ints[i], k0 = ints[lay.Mp + i], k1 = ints[2 * lay.Mp + i];
+            if (rt < -1 || rt > 1 || k0 < -1 || k0 >= ns || k1 < -1 || k1 >= ns) throw std::invalid_argument("asm_test_ipm_stages: row type or slack index out of range");
+        }
+        for (int64_t k = 0; k < ns; ++k)
+            if (ints[3 * lay.Mp + k] < 0 || ints[3 * lay.Mp + k] >= M) throw std::invalid_argument("asm_test_ipm_stages: slack row out of range");
+        auto dspan = [&](int64_t off, int64_t len) {
+            if (off < 0 || len < 0 || off + len > ndbl) throw std::invalid_argument("asm_test_ipm_stages: vector outside the double block");
+        };
+        auto ilist = [&](int64_t off, int64_t len, int64_t bound) {      // an index list with entries in [0, bound)
+            if (off < 0 || len < 0 || off + len > nint) throw std::invalid_argument("asm_test_ipm_stages: list outside the int block");
+            for (int64_t a = 0; a < len; ++a)
+                if (ints[off + a] < 0 || ints[off + a] >= bound) throw std::invalid_argument("asm_test_ipm_stages: index out of range");
+        };
+        for (int64_t q = 0; q < nstages; ++q) {
+            const asm_ipm_stage& st = stages[q];
+            if (st.D < 0 || st.D > 1 || st.B < 0 || st.B > 1) throw std::invalid_argument("asm_test_ipm_stages: direction selector");
+            switch (st.kind) {
+            case ASM_IPM_VEC_MUL: dspan(st.x[0], st.len[0]); dspan(st.x[1], st.len[0]); break;
+            case ASM_IPM_SNAPSHOT: if (st.with_e) dspan(st.x[0], lay.ldn); break;
+            case ASM_IPM_COL_PREP: dspan(st.x[0], M); dspan(st.x[1], n); break;
+            case ASM_IPM_COL_SCALE: dspan(st.x[0], M); dspan(st.x[1], M); dspan(st.x[2], M); break;
+            case ASM_IPM_COL_FINISH: dspan(st.x[0], M); dspan(st.x[1], M); dspan(st.x[2], M); dspan(st.x[3], M); break;
+            case ASM_IPM_SDIAG_CSR: {
+                const int64_t R = st.len[0];
+                if (R < 0 || st.ix[0] < 0 || st.ix[0] + R + 1 > nint) throw std::invalid_argument("asm_test_ipm_stages: row pointers outside the int block");
+                for (int64_t i = 0; i < R; ++i) if (ints[st.ix[0] + i] > ints[st.ix[0] + i + 1]) throw std::invalid_argument("asm_test_ipm_stages: row pointers decrease");
+                if (ints[st.ix[0]] < 0) throw std::invalid_argument("asm_test_ipm_stages: negative row pointer");
+                const int64_t nnz = ints[st.ix[0] + R];
+                ilist(st.ix[1], nnz, st.len[1]);
+                dspan(st.x[0], nnz); dspan(st.x[1], st.len[1]); dspan(st.x[2], R);
+                break;
+            }
+            case ASM_IPM_RED_GATHER: ilist(st.ix[0], st.len[0], st.len[1]); dspan(st.x[0], st.len[1]); dspan(st.x[1], st.len[0]); break;
+            case ASM_IPM_RED_SCATTER:
+                if (st.len[2] < std::max(st.len[0], st.len[1])) throw std::invalid_argument("asm_test_ipm_stages: the scatter covers fewer rows than its lists hold");
+                ilist(st.ix[0], st.len[0], st.len[2]); ilist(st.ix[1], st.len[1], st.len[2]);
+                dspan(st.x[0], st.len[0]); dspan(st.x[1], st.len[1]); dspan(st.x[2], st.len[2]); dspan(st.x[3], st.len[2]);
+                break;
+            default:
+                if (st.kind < 0 || st.kind >= ASM_IPM_NKINDS) throw std::invalid_argument("asm_test_ipm_stages: unknown stage");
+            }
+        }
+        double *dD = nullptr, *dSnap = nullptr, *dRp = nullptr, *hScal = nullptr, *dhScal = nullptr;
+        int* dI = nullptr;
+        unsigned *dCnt = nullptr, *hSeq = nullptr, *dhSeq = nullptr;
+        BufPool tmp;
+        tmp.upload(dD, dbl_inout, ndbl);
+        tmp.upload(dI, (const int*)ints, nint);
+        tmp.upload(dSnap, snap_inout, lay.snap_len());
+        tmp.upload(dRp, rpart_inout, (int64_t)IPM_RED_MAXWG * IPM_RED_SLOTS);
+        tmp.upload(dCnt, (const unsigned*)rcnt_inout, 1);
+        tmp.alloc(hScal, 64, BufPool::MAPPED, &dhScal);
+        tmp.alloc(hSeq, 16, BufPool::MAPPED, &dhSeq);
+        std::memcpy(hScal, hscal_inout, SC_COUNT * sizeof(double));
+        *hSeq = *hseq_inout;
+        ar.base = dD; ar.ibase = dI; ar.snap = dSnap; ar.hscal = dhScal; ar.hseq = dhSeq; ar.rpart = dRp; ar.rcnt = dCnt;
+        S.ipm_bind(ar);
+        S.P.n = n; S.P.M = M; S.P.ns = ns; S.P.ncomp = ncomp; S.P.scale_q = scale_q;
+        for (int64_t q = 0; q < nstages; ++q) {      // one after the other on the handle's stream, no host synchronisation in between
+            const asm_ipm_stage& st = stages[q];
+            IpmDir& D = st.D ? S.dirC : S.dirA;
+            IpmDir& B = st.B ? S.dirC : S.dirA;
+            unsigned g = 0;
+            switch (st.kind) {
+            case ASM_IPM_INIT_P: g = S.launch_init_p(st.origin); break;
+            case ASM_IPM_INIT_REST: g = S.launch_init_rest(st.mu_factor); break;
+            case ASM_IPM_MEASURES: g = S.launch_measures(st.pub); break;
+            case ASM_IPM_THETA: g = S.launch_theta(st.rho_p); break;
+            case ASM_IPM_RHS1: g = S.launch_rhs1(B, st.mode, st.tp, st.td); break;
+            case ASM_IPM_RHS2: g = S.launch_rhs2(st.res); break;
+            case ASM_IPM_VEC_MUL: g = S.launch_vec_mul(dD + st.x[0], dD + st.x[1], st.len[0]); break;
+            case ASM_IPM_RES: g = S.launch_res(D.dy, st.pub, st.spec, st.crel, st.floor_); break;
+            case ASM_IPM_PCG_START: g = S.launch_pcg_start(); break;
+            case ASM_IPM_PCG_STEP1: g = S.launch_pcg_step1(D.dy, st.pub); break;
+            case ASM_IPM_PCG_STEP2: g = S.launch_pcg_step2(); break;
+            case ASM_IPM_DIR: g = S.launch_dir(D); break;
+            case ASM_IPM_STEPS: g = S.launch_steps(D, st.pub); break;
+            case ASM_IPM_MUAFF: g = S.launch_muaff(D, st.sexp); break;
+            case ASM_IPM_DIRADD: g = S.launch_diradd(D, B); break;
+            case ASM_IPM_UPDATE: g = S.launch_update(D, st.al, st.be); break;
+            case ASM_IPM_SNAPSHOT: g = S.launch_snapshot(st.with_e ? dD + st.x[0] : nullptr, st.dir); break;
+            case ASM_IPM_COL_PREP: g = S.launch_col_prep(st.rho_p, st.fixed, dD + st.x[0], dD + st.x[1]); break;
+            case ASM_IPM_COL_SCALE: g = S.launch_col_scale(dD + st.x[0], dD + st.x[1], dD + st.x[2]); break;
+            case ASM_IPM_COL_FINISH: g = S.launch_col_finish(dD + st.x[0], dD + st.x[1], dD + st.x[2], dD + st.x[3]); break;
+            case ASM_IPM_SDIAG_CSR: g = S.dev.launch_sdiag_csr(dI + st.ix[0], dI + st.ix[1], dD + st.x[0], dD + st.x[1], dD + st.x[2], st.len[0]); break;
+            case ASM_IPM_RED_GATHER: g = S.launch_red_gather(dI + st.ix[0], (int)st.len[0], dD + st.x[0], dD + st.x[1]); break;
+            default:
+                g = S.launch_red_scatter(dI + st.ix[0], (int)st.len[0], dD + st.x[0], dI + st.ix[1], (int)st.len[1], dD + st.x[1], dD + st.x[2], dD + st.x[3], st.len[2]);
+            }
+            grid_out[q] = g;
+        }
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(snap_inout, dSnap, lay.snap_len() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(rpart_inout, dRp, (size_t)IPM_RED_MAXWG * IPM_RED_SLOTS * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(rcnt_inout, dCnt, sizeof(unsigned), hipMemcpyDeviceToHost));
+        std::memcpy(hscal_inout, hScal, SC_COUNT * sizeof(double));
+        *hseq_inout = *hSeq;
     });
 }
 

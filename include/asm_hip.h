@@ -481,6 +481,65 @@ int asm_test_build_split(asm_handle* h, const double* G, int64_t k, int64_t K, c
 int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const int32_t* idx, int64_t Ms, const double* theta,
                             const double* diag, double* S_inout, double* Ah_out, int64_t* info, int32_t* row_order, int32_t* col_order,
                             int32_t* e_order);
+/* Test hook: the interior-point stage kernels (asm_ipm_kernels.hip.h), one launch per stage with the solver's own launch geometry, on a state the
+ * caller supplies.  The state of an LP with n columns, M rows and ns slack columns lives in an arena laid out by the solver's own binding
+ * routine with the pitches asm_sublp_setup chooses for these sizes (ldn = n rounded up to 32, Mp = max(M, 1) and nsp = max(ns, 1) rounded up
+ * to 16).  layout_out (ASM_IPM_LAYOUT_LEN) receives: ldn, Mp, nsp, arena length, snapshot length, int block length, number of scalars
+ * (SC_COUNT), offset of the scalar block, then the offsets of the ASM_IPM_NVEC vectors in this order:
+ *   q lb ub r w slo scoef | p s g y tL tU muL muU ts mus pi | act aty rp rdp rds thp_inv ths_inv dS hp hs tmpn t1 rhs res rcL rcU rcs rcg |
+ *   dirA: dp ds dg dy dmuL dmuU dmus dpi | dirC: the same eight | sres corr pcg tN
+ * (n-vectors have ldn, M-vectors Mp, slack vectors nsp entries).  With dbl_inout == NULL the call only reports the layout.
+ *   dbl_inout  (ndbl >= arena length)  the arena, followed by any vectors of the caller's that helper stages name by offset; returned whole.
+ *              The products with the LP matrix are inputs, not stages: the caller fills act, aty, t1, sres and tN.
+ *   ints       (nint >= int block length)  rtype | rs0 | rs1 (Mp each; rs0 / rs1 = the up to two slack columns of a row, -1 for none) |
+ *              srow (nsp), followed by the caller's index lists.
+ *   snap_inout (snapshot length), rpart_inout (64 workgroups x 8 slots), rcnt_inout (1), hscal_inout (SC_COUNT; the host-mapped copy of the
+ *              scalar block), hseq_inout (1; its sequence word): loaded before the first stage and returned after the last.
+ *   stages     run in order on the handle's stream with no host synchronisation in between; grid_out[q] = workgroups stage q launched.
+ * Scalars: PINF DINF MU YMAX AP AD SM EMAX RMAX RZ RPMAX RZ0 STOP NSERR SPEC (indices 0 .. 14).
+ * Every offset, length and index is checked against the buffers before the first launch (ASM_ERR_ARG otherwise). */
+enum {
+    ASM_IPM_INIT_P = 0,   /* origin */
+    ASM_IPM_INIT_REST,    /* mu_factor */
+    ASM_IPM_MEASURES,     /* pub */
+    ASM_IPM_THETA,        /* rho_p */
+    ASM_IPM_RHS1,         /* mode 0 / 1 / 2, tp, td; B = base direction */
+    ASM_IPM_RHS2,         /* res */
+    ASM_IPM_VEC_MUL,      /* x[0] (in / out) *= x[1], len[0] entries */
+    ASM_IPM_RES,          /* sres and D.dy; pub, spec, crel, floor_ */
+    ASM_IPM_PCG_START,    /* z = corr, p = pcg */
+    ASM_IPM_PCG_STEP1,    /* sres, p = pcg, x = D.dy; pub */
+    ASM_IPM_PCG_STEP2,    /* z = corr, p = pcg */
+    ASM_IPM_DIR,          /* D from D.dy and tN */
+    ASM_IPM_STEPS,        /* D; pub */
+    ASM_IPM_MUAFF,        /* D; sexp */
+    ASM_IPM_DIRADD,       /* D += B */
+    ASM_IPM_UPDATE,       /* D; al, be */
+    ASM_IPM_SNAPSHOT,     /* dir 0 save / 1 restore; with_e: e = x[0] (ldn entries) */
+    ASM_IPM_COL_PREP,     /* rho_p, fixed; dinv = x[0] (M), th = x[1] (n) */
+    ASM_IPM_COL_SCALE,    /* dinv = x[0], r = x[1], u = x[2] (M each) */
+    ASM_IPM_COL_FINISH,   /* dinv = x[0], u = x[1], w = x[2], out = x[3] (M each) */
+    ASM_IPM_SDIAG_CSR,    /* ptr = ix[0] (len[0] + 1), col = ix[1]; vals = x[0], thinv = x[1] (len[1]), out = x[2] (len[0]) */
+    ASM_IPM_RED_GATHER,   /* E = ix[0] (len[0] entries < len[1]); r = x[0] (len[1]), ce = x[1] */
+    ASM_IPM_RED_SCATTER,  /* E = ix[0] (len[0]), ze = x[0]; I = ix[1] (len[1]), dI = x[1]; r = x[2], z = x[3] (len[2] each: the rows covered, at least max(len[0], len[1]): the grid is sized by it) */
+    ASM_IPM_NKINDS
+};
+#define ASM_IPM_NVEC 56
+#define ASM_IPM_LAYOUT_LEN (8 + ASM_IPM_NVEC)
+typedef struct asm_ipm_stage {
+    int32_t kind;                 /* ASM_IPM_* */
+    int32_t mode, spec, sexp, origin, dir, with_e;
+    int32_t D, B;                 /* 0 = dirA, 1 = dirC */
+    uint32_t pub;                 /* publishing kernels: 0, or the sequence number to publish */
+    double tp, td, res, crel, floor_, rho_p, mu_factor, al, be, fixed;
+    int64_t x[4];                 /* offsets into dbl_inout */
+    int64_t ix[2];                /* offsets into ints */
+    int64_t len[3];
+} asm_ipm_stage;
+int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t ncomp, double scale_q, int64_t* layout_out,
+                        double* dbl_inout, int64_t ndbl, const int32_t* ints, int64_t nint, double* snap_inout, double* rpart_inout,
+                        uint32_t* rcnt_inout, double* hscal_inout, uint32_t* hseq_inout, const asm_ipm_stage* stages, int64_t nstages,
+                        uint32_t* grid_out);
 int asm_test_cholesky(asm_handle* h, const double* S /* N*N sym */, int64_t N, double* L_out /* N*N lower */);
 int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x);
 /* the bounded wait of the dataflow panel kernel with a producer that never publishes: returns ASM_ERR_HIP (reported once), the

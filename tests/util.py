@@ -452,3 +452,695 @@ def split_ranges(K, nsplit):
     nch = K // 32
     per = ((nch + nsplit - 1) // nsplit) * 32
     return [(min(K, s * per), min(K, (s + 1) * per)) for s in range(nsplit)]
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# Interior-point stage kernels (tests/test_ipm_stages_cpu.py, tests/test_ipm_stages_gpu.py): states, and a long-double twin of every stage
+# written from the statements of oracle/lp_solver.py (class IPM) and the comments of asm_ipm_kernels.hip.h.
+#
+# A state is a dict: sizes n, M, ns, ncomp, scale_q; the integer arrays rtype, srow, rs0, rs1; `scal` (the 15 scalars, names IPM_SCALARS);
+# and one float64 vector per name of IPM_VECTORS.  A twin function returns {output name: (value, magnitude, k)} in np.longdouble: `value`
+# is the statement evaluated in long double from the float64 inputs, `magnitude` the same formula with every term replaced by its absolute
+# value, k the operation count of the statement plus one, so that  |out - value| <= gamma_k magnitude  holds for float64 arithmetic in any
+# association, with or without FMA contraction.  An output that depends on another output of the same kernel (hp on rcL, dmuL on dp, ...)
+# is stated from the value the DEVICE wrote for that one (argument `dev`): a bound through a chain would have to carry the cancellation
+# of the intermediate, and what the kernel does is exactly the statement applied to its own rounded intermediate.
+IPM_SCALARS = "PINF DINF MU YMAX AP AD SM EMAX RMAX RZ RPMAX RZ0 STOP NSERR SPEC".split()
+# stage kinds (enum ASM_IPM_* of include/asm_hip.h) and the order in which asm_test_ipm_stages reports the vectors' offsets
+IPM_STAGE_KINDS = ("init_p", "init_rest", "measures", "theta", "rhs1", "rhs2", "vec_mul", "res", "pcg_start", "pcg_step1", "pcg_step2", "dir", "steps",
+                   "muaff", "diradd", "update", "snapshot", "col_prep", "col_scale", "col_finish", "sdiag_csr", "red_gather", "red_scatter")
+IPM_VECTORS = ("q lb ub r w slo scoef p s g y tL tU muL muU ts mus pi act aty rp rdp rds thp_inv ths_inv dS hp hs tmpn t1 rhs res rcL rcU rcs rcg "
+               "A.dp A.ds A.dg A.dy A.dmuL A.dmuU A.dmus A.dpi C.dp C.ds C.dg C.dy C.dmuL C.dmuU C.dmus C.dpi sres corr pcg tN").split()
+SC = {nm: i for i, nm in enumerate(IPM_SCALARS)}
+IPM_N = "q lb ub p tL tU muL muU aty rdp thp_inv hp tmpn rcL rcU A.dp A.dmuL A.dmuU C.dp C.dmuL C.dmuU tN".split()
+IPM_M = "r g y pi act rp dS t1 rhs res rcg A.dg A.dy A.dpi C.dg C.dy C.dpi sres corr pcg".split()
+IPM_S = "w slo scoef s ts mus rds ths_inv hs rcs A.ds A.dmus C.ds C.dmus".split()
+IPM_RHO_P, MCC_BMIN, MCC_BMAX, COL_FIXED = 1e-8, 0.1, 10.0, 1e200
+LD = np.longdouble
+BIG = 1e300
+
+
+def gamma(k):
+    k = np.asarray(k, LD)
+    return k * LD(U) / (1 - k * LD(U))
+
+
+def bound_ratio(out, val, mag, k):
+    """Largest |out - val| / (gamma_k mag); inf where mag == 0 and out != val."""
+    out, val, mag = np.atleast_1d(np.asarray(out, LD)), np.atleast_1d(np.asarray(val, LD)), np.atleast_1d(np.asarray(mag, LD))
+    if out.size == 0:
+        return 0.0
+    err = np.abs(out - val)
+    b = gamma(k) * mag
+    r = np.zeros(out.shape, LD)
+    pos = b > 0
+    r[pos] = err[pos] / b[pos]
+    r[(~pos) & (err != 0)] = np.inf
+    r[~np.isfinite(np.asarray(out, LD))] = np.inf
+    return float(r.max())
+
+
+def ipm_vec_len(st, name):
+    return st["n"] if name in IPM_N else (st["M"] if name in IPM_M else st["ns"])
+
+
+def ipm_slack_lists(M, srow):
+    """rs0 / rs1 of every row as asm_sublp_setup makes them: the first and the second slack column of the row, -1 for none."""
+    rs0 = np.full(M, -1, np.int32)
+    rs1 = np.full(M, -1, np.int32)
+    for k, r_ in enumerate(srow):
+        if rs0[r_] < 0:
+            rs0[r_] = k
+        else:
+            assert rs1[r_] < 0
+            rs1[r_] = k
+    return rs0, rs1
+
+
+def ipm_state(seed, n, M, ns, mu=1.0, fixed_frac=0.1):
+    """A scrambled interior-point state of sizes (n, M, ns), ns <= 2 M.  Rows: equalities, both inequality signs; slack columns dealt to rows,
+    at most two per row (the first with coefficient +1, the second -1, as the solver lays them out: range / equality rows of a restoration
+    LP).  About fixed_frac of the columns are fixed (ub == lb) and carry what the solver keeps there (tL = tU = 1, zero multipliers).  The
+    complementarity pairs have t over eight decades and multipliers mu / t times a factor over two decades - pairs of opposite extremes at
+    every level of mu.  Bounds are finite: the LP container's bounds are the finite trust region (oracle/lp_solver.py, module docstring),
+    and scale_lp divides by finite powers of two, so no infinity reaches these kernels.  Everything else - residuals, work vectors,
+    directions, products with the matrix - is standard normal, so every stage can be run on its own from this state."""
+    rng = np.random.default_rng(seed)
+    assert n >= 1 and 0 <= ns <= 2 * M
+    st = {"n": n, "M": M, "ns": ns}
+    st["rtype"] = rng.integers(-1, 2, M).astype(np.int32)
+    npair = max(ns - M, ns // 3) if ns >= 2 else 0                  # rows with two slack columns (rs0 and rs1 both set)
+    rows = rng.permutation(M)[:ns - npair]
+    srow = np.sort(np.concatenate([rows, rows[:npair]])).astype(np.int32)
+    st["srow"] = srow
+    st["rs0"], st["rs1"] = ipm_slack_lists(M, srow)
+    for nm in IPM_N + IPM_M + IPM_S:
+        st[nm] = rng.standard_normal(ipm_vec_len(st, nm))
+    sc = np.where(rng.random(ns) < 0.5, 1.0, -1.0)
+    for i in range(M):
+        if st["rs1"][i] >= 0:
+            sc[st["rs0"][i]], sc[st["rs1"][i]] = 1.0, -1.0
+    st["scoef"] = sc
+    st["lb"] = -10.0 ** rng.uniform(-2, 3, n)
+    st["ub"] = 10.0 ** rng.uniform(-2, 3, n)
+    fx = rng.random(n) < fixed_frac
+    st["ub"][fx] = st["lb"][fx]
+
+    def pair(cnt):
+        t = 10.0 ** rng.uniform(-6, 2, cnt)
+        return t, mu / t * 10.0 ** rng.uniform(-1, 1, cnt)
+    st["tL"], st["muL"] = pair(n)
+    st["tU"], st["muU"] = pair(n)
+    st["ts"], st["mus"] = pair(ns)
+    st["g"], st["pi"] = pair(M)
+    st["tL"][fx] = st["tU"][fx] = 1.0
+    st["muL"][fx] = st["muU"][fx] = 0.0
+    eq = st["rtype"] == 0
+    st["g"][eq] = 1.0
+    st["pi"][eq] = 0.0
+    st["y"] = np.where(eq, st["y"], st["rtype"] * st["pi"])
+    st["thp_inv"] = np.where(fx, 0.0, 10.0 ** rng.uniform(-6, 2, n))
+    st["ths_inv"] = 10.0 ** rng.uniform(-6, 2, ns)
+    st["dS"] = 10.0 ** rng.uniform(-6, 2, M)
+    st["scale_q"] = 4.0
+    st["ncomp"] = max(2 * int((~fx).sum()) + ns + int((~eq).sum()), 1)
+    scal = 10.0 ** rng.uniform(-3, 1, len(IPM_SCALARS))
+    scal[SC["MU"]] = mu
+    scal[SC["SM"]] = 0.3 * mu
+    scal[SC["AP"]], scal[SC["AD"]] = 0.75, 0.5
+    scal[SC["STOP"]] = scal[SC["SPEC"]] = 0.0
+    st["scal"] = scal
+    return st
+
+
+def _l(st, *names):
+    return [st[nm].astype(LD) for nm in names]
+
+
+def _slack_sum(st, v):
+    """(sum, magnitude, term count) per row of  sum_k scoef_k v_k  over the row's slack columns."""
+    M = st["M"]
+    a, m, c = np.zeros(M, LD), np.zeros(M, LD), np.zeros(M, np.int64)
+    if st["ns"]:
+        for rs in (st["rs0"], st["rs1"]):
+            has = rs >= 0
+            t = st["scoef"][rs[has]].astype(LD) * np.asarray(v, LD)[rs[has]]
+            a[has] += t
+            m[has] += np.abs(t)
+            c[has] += 1
+    return a, m, c
+
+
+def _free(st):
+    return st["ub"] > st["lb"]
+
+
+def tw_measures(st):
+    """rp, rdp, rds element by element and mu (oracle: IPM.measures).  mu: k = number of products + 3 (a rounding per product, one per
+    addition, the division by ncomp).  The maxima are exact statements on the written residuals: ipm_measures_exact."""
+    ineq, fr = st["rtype"] != 0, _free(st)
+    act, r, g, pi = _l(st, "act", "r", "g", "pi")
+    sa, sm_, _ = _slack_sum(st, st["s"])
+    gg = np.where(ineq, g, 0)
+    out = {"rp": (act + sa - (r + st["rtype"] * gg), np.abs(act) + sm_ + np.abs(r) + np.abs(gg), 7)}
+    q, aty, muL, muU, tL, tU = _l(st, "q", "aty", "muL", "muU", "tL", "tU")
+    out["rdp"] = (np.where(fr, q - aty - muL + muU, 0), np.where(fr, np.abs(q) + np.abs(aty) + np.abs(muL) + np.abs(muU), 0), 4)
+    w, sc, mus, ts = _l(st, "w", "scoef", "mus", "ts")
+    ys = st["y"].astype(LD)[st["srow"]]
+    out["rds"] = (w - sc * ys - mus, np.abs(w) + np.abs(sc * ys) + np.abs(mus), 4)
+    terms = np.concatenate([(g * pi)[ineq], (tL * muL)[fr], (tU * muU)[fr], ts * mus])
+    nc = LD(st["ncomp"])
+    out["MU"] = (terms.sum() / nc, np.abs(terms).sum() / nc, len(terms) + 3)
+    return out
+
+
+def ipm_measures_exact(st, rp, rdp, rds):
+    """PINF, DINF, YMAX, RPMAX in float64 from the residuals as written: divisions and maxima only, every operation correctly rounded."""
+    pinf = float((np.abs(rp) / (1.0 + np.abs(st["r"]))).max(initial=0.0))
+    dinf = max(float(np.abs(rdp).max(initial=0.0)), float(np.abs(rds).max(initial=0.0))) / st["scale_q"]
+    return {"PINF": pinf, "DINF": dinf, "YMAX": float(np.abs(st["y"]).max(initial=0.0)), "RPMAX": float(np.abs(rp).max(initial=0.0))}
+
+
+def ipm_theta_exact(st, rho_p):
+    """thp_inv, ths_inv, dS in float64: divisions and plain additions in the kernel's order (no a*b +/- c shape: nothing to contract)."""
+    fr = _free(st)
+    with np.errstate(all="ignore"):
+        th = np.where(fr, 1.0 / (st["muL"] / st["tL"] + st["muU"] / st["tU"] + rho_p), 0.0)
+        ths = st["ts"] / st["mus"]
+        d = np.where(st["rtype"] != 0, st["g"] / st["pi"], 0.0)
+    if st["ns"]:
+        for rs in (st["rs0"], st["rs1"]):
+            has = rs >= 0
+            d[has] = d[has] + ths[rs[has]]
+    return {"thp_inv": th, "ths_inv": ths, "dS": d}
+
+
+def _mcc(x, dx, z, dz, tp, td, lo, hi):
+    """Gondzio's projected complementarity term.  v = (x + tp dx)(z + td dz) has five operations; the result clamp(v) - v (at least -hi) is
+    a piecewise linear function of v with slopes in [-1, 0], so an error of v passes through at most unchanged, whatever branch the rounded
+    v selects; one more rounding for the subtraction, against lo or hi: k = 7, magnitude |v|-formula + hi."""
+    v = (x + tp * dx) * (z + td * dz)
+    mv = (np.abs(x) + abs(tp) * np.abs(dx)) * (np.abs(z) + abs(td) * np.abs(dz))
+    return np.maximum(np.minimum(np.maximum(v, lo), hi) - v, -hi), mv + abs(hi)
+
+
+def tw_rhs1(st, base, mode, tp=0.0, td=0.0, dev=None):
+    """rcL rcU rcs rcg, then (from the device's own rc*, `dev`) hp, hs and tmpn = thp_inv hp (oracle: IPM.run, solve / corr)."""
+    fr, ineq = _free(st), st["rtype"] != 0
+    sm = LD(st["scal"][SC["SM"]]) if mode else LD(0)
+    lo, hi = LD(MCC_BMIN * float(sm)), LD(MCC_BMAX * float(sm))      # (one correctly rounded product each, as the kernel forms them)
+    res = LD(0.0 if mode == 2 else 1.0)
+    tL, tU, muL, muU, ts, mus, g, pi = _l(st, "tL", "tU", "muL", "muU", "ts", "mus", "g", "pi")
+    dp, dmuL, dmuU, ds, dmus, dg, dpi = _l(st, base + ".dp", base + ".dmuL", base + ".dmuU", base + ".ds", base + ".dmus", base + ".dg", base + ".dpi")
+    out = {}
+    if mode == 2:
+        vL, mL = _mcc(tL, dp, muL, dmuL, tp, td, lo, hi)
+        vU, mU = _mcc(tU, -dp, muU, dmuU, tp, td, lo, hi)
+        out["rcL"] = (np.where(fr, vL, 0), np.where(fr, mL, 0), 7)
+        out["rcU"] = (np.where(fr, vU, 0), np.where(fr, mU, 0), 7)
+        out["rcs"] = _mcc(ts, ds, mus, dmus, tp, td, lo, hi) + (7,)
+        vg, mg = _mcc(g, dg, pi, dpi, tp, td, lo, hi)
+        out["rcg"] = (np.where(ineq, vg, 0), np.where(ineq, mg, 0), 7)
+    else:
+        c = LD(1 if mode else 0)
+        out["rcL"] = (sm - tL * muL - c * dp * dmuL, abs(sm) + np.abs(tL * muL) + c * np.abs(dp * dmuL), 5)
+        out["rcU"] = (sm - tU * muU + c * dp * dmuU, abs(sm) + np.abs(tU * muU) + c * np.abs(dp * dmuU), 5)
+        out["rcs"] = (sm - ts * mus - c * ds * dmus, abs(sm) + np.abs(ts * mus) + c * np.abs(ds * dmus), 5)
+        out["rcg"] = (sm - g * pi - c * dg * dpi, abs(sm) + np.abs(g * pi) + c * np.abs(dg * dpi), 5)
+    if dev is not None:
+        rcL, rcU, rcs, hpd = dev["rcL"].astype(LD), dev["rcU"].astype(LD), dev["rcs"].astype(LD), dev["hp"].astype(LD)
+        rdp, rds, thp = _l(st, "rdp", "rds", "thp_inv")
+        out["hp"] = (np.where(fr, -res * rdp + rcL / tL - rcU / tU, 0), np.where(fr, res * np.abs(rdp) + np.abs(rcL / tL) + np.abs(rcU / tU), 0), 6)
+        out["tmpn"] = (thp * hpd, np.abs(thp * hpd), 2)
+        out["hs"] = (-res * rds + rcs / ts, res * np.abs(rds) + np.abs(rcs / ts), 4)
+    return out
+
+
+def tw_rhs2(st, res):
+    """rhs = -res rp - t1 + sg rcg / pi - E (ths_inv hs)   (oracle: IPM.run, solve)."""
+    ineq = st["rtype"] != 0
+    rp, t1, rcg, pi = _l(st, "rp", "t1", "rcg", "pi")
+    with np.errstate(all="ignore"):
+        c = np.where(ineq, st["rtype"] * rcg / np.where(ineq, pi, 1), 0)
+    sa, sm_, _ = _slack_sum(st, st["ths_inv"].astype(LD) * st["hs"].astype(LD))
+    return {"rhs": (-LD(res) * rp - t1 + c - sa, abs(res) * np.abs(rp) + np.abs(t1) + np.abs(c) + sm_, 12)}
+
+
+def tw_res(st, D):
+    """res = rhs - (sres + dS dy); EMAX / RMAX / SPEC are exact statements on the written res (ipm_res_exact)."""
+    rhs, sres, dS, dy = _l(st, "rhs", "sres", "dS", D + ".dy")
+    return {"res": (rhs - (sres + dS * dy), np.abs(rhs) + np.abs(sres) + np.abs(dS * dy), 4)}
+
+
+def ipm_res_exact(st, res_written, spec, crel, floor_):
+    emax = float(np.abs(res_written).max(initial=0.0))
+    rmax = max(1.0, float(np.abs(st["rhs"]).max(initial=0.0)))
+    out = {"EMAX": emax, "RMAX": rmax, "SPEC": st["scal"][SC["SPEC"]]}
+    if spec:
+        bad = 1.0 if emax > max(crel * rmax, floor_) else 0.0
+        out["SPEC"] = bad if spec == 1 else max(st["scal"][SC["SPEC"]], bad)
+    return out
+
+
+def _dot(a, b):
+    return (a * b).sum(), np.abs(a * b).sum()
+
+
+def tw_pcg_start(st):
+    res, z = _l(st, "res", "corr")
+    v, m = _dot(res, z)
+    return {"RZ": (v, m, st["M"] + 2)}
+
+
+def tw_pcg_step1(st, D):
+    """acc = p'(sres + dS p) (three operations per term), alpha = rz / acc, x += alpha p, res -= alpha (sres + dS p).  The quotient carries
+    the relative error of acc, gamma_(M+4) kappa with kappa = magnitude(acc) / |acc| (the condition number of the sum), so the alpha
+    terms of the magnitudes are scaled by kappa; to first order in u, which k + 2 more than covers for kappa u << 1 (asserted by the
+    generator: kappa < 1e3)."""
+    p, sres, dS, x, res = _l(st, "pcg", "sres", "dS", D + ".dy", "res")
+    sp = sres + dS * p
+    acc, macc = (p * sp).sum(), (np.abs(p) * (np.abs(sres) + np.abs(dS * p))).sum()
+    rz, rz0 = LD(st["scal"][SC["RZ"]]), LD(st["scal"][SC["RZ0"]])
+    ok = bool(acc > 0 and rz > LD(1e-30) * rz0 and rz < LD(1e12) * acc)
+    if not ok:
+        return {"ok": False, "acc": acc, "macc": macc}
+    kap = macc / abs(acc)
+    al = rz / acc
+    M = st["M"]
+    return {"ok": True, "acc": acc, "macc": macc, "kappa": float(kap),
+            "x": (x + al * p, np.abs(x) + kap * np.abs(al * p), M + 9), "res": (res - al * sp, np.abs(res) + kap * abs(al) * (np.abs(sres) + np.abs(dS * p)), M + 10)}
+
+
+def tw_pcg_step2(st):
+    res, z, p = _l(st, "res", "corr", "pcg")
+    acc, macc = _dot(res, z)
+    rz = LD(st["scal"][SC["RZ"]])
+    kap = macc / abs(acc) if acc != 0 else LD(1)
+    be = acc / rz
+    M = st["M"]
+    return {"RZ": (acc, macc, M + 2), "pcg": (z + be * p, np.abs(z) + kap * np.abs(be * p), M + 6), "kappa": float(kap)}
+
+
+def tw_dir(st, D, dev):
+    """Newton direction from dy and tN = Ah' dy (oracle: IPM.run, solve); dmuL / dmuU / dmus / dg from the device's own dp / ds / dpi."""
+    fr, ineq = _free(st), st["rtype"] != 0
+    thp, hp, tN, rcL, rcU, muL, muU, tL, tU = _l(st, "thp_inv", "hp", "tN", "rcL", "rcU", "muL", "muU", "tL", "tU")
+    out = {D + ".dp": (thp * (hp + tN), np.abs(thp) * (np.abs(hp) + np.abs(tN)), 3)}
+    dp = dev[D + ".dp"].astype(LD)
+    out[D + ".dmuL"] = (np.where(fr, (rcL - muL * dp) / tL, 0), np.where(fr, (np.abs(rcL) + np.abs(muL * dp)) / np.abs(tL), 0), 4)
+    out[D + ".dmuU"] = (np.where(fr, (rcU + muU * dp) / tU, 0), np.where(fr, (np.abs(rcU) + np.abs(muU * dp)) / np.abs(tU), 0), 4)
+    ths, hs, sc, rcs, mus, ts = _l(st, "ths_inv", "hs", "scoef", "rcs", "mus", "ts")
+    dys = st[D + ".dy"].astype(LD)[st["srow"]]
+    out[D + ".ds"] = (ths * (hs + sc * dys), np.abs(ths) * (np.abs(hs) + np.abs(sc * dys)), 4)
+    ds = dev[D + ".ds"].astype(LD)
+    out[D + ".dmus"] = ((rcs - mus * ds) / ts, (np.abs(rcs) + np.abs(mus * ds)) / np.abs(ts), 4)
+    rcg, g, pi = _l(st, "rcg", "g", "pi")
+    dpi = dev[D + ".dpi"].astype(LD)
+    with np.errstate(all="ignore"):
+        out[D + ".dg"] = (np.where(ineq, (rcg - g * dpi) / np.where(ineq, pi, 1), 0), np.where(ineq, (np.abs(rcg) + np.abs(g * dpi)) / np.where(ineq, np.abs(pi), 1), 0), 4)
+    return out
+
+
+def ipm_dir_exact(st, D):
+    """dpi = sg dy on inequality rows (exact: sg = +-1), 0 on equality rows."""
+    return {D + ".dpi": np.where(st["rtype"] != 0, st["rtype"] * st[D + ".dy"], 0.0)}
+
+
+def ipm_ratio_candidates(st, D):
+    """Every eligible (ratio, where) of the ratio test as float64: -x / dx where dx < 0, one correctly rounded division each."""
+    fr, ineq = _free(st), st["rtype"] != 0
+
+    def cand(x, dx, mask):
+        sel = mask & (dx < 0)
+        with np.errstate(all="ignore"):
+            return np.where(sel, -x / np.where(sel, dx, -1.0), BIG)
+    dp = st[D + ".dp"]
+    allk = np.ones(st["ns"], bool)
+    prim = {"tL": cand(st["tL"], dp, fr), "tU": cand(st["tU"], -dp, fr), "ts": cand(st["ts"], st[D + ".ds"], allk), "g": cand(st["g"], st[D + ".dg"], ineq)}
+    dual = {"muL": cand(st["muL"], st[D + ".dmuL"], fr), "muU": cand(st["muU"], st[D + ".dmuU"], fr), "mus": cand(st["mus"], st[D + ".dmus"], allk),
+            "pi": cand(st["pi"], st[D + ".dpi"], ineq)}
+    return prim, dual
+
+
+def ipm_steps_exact(st, D):
+    """AP, AD (oracle: IPM.run, steps / _maxstep): minima of the eligible ratios, capped at 1."""
+    prim, dual = ipm_ratio_candidates(st, D)
+    return {"AP": min(1.0, min(float(v.min(initial=BIG)) for v in prim.values())), "AD": min(1.0, min(float(v.min(initial=BIG)) for v in dual.values()))}
+
+
+def tw_muaff(st, D, sexp):
+    """The accumulator  sum (t + ap dt)(m + ad dm)  over the complementarity pairs (five operations per product, one per addition; k = number
+    of products + 7 with the division by ncomp), and SM = (mu_aff / mu)^sexp mu (0 when mu is 0).  SM takes the accumulator to the power
+    sexp:  |(a + e)^p - a^p| <= p max(|a|, |a + e|)^(p-1) |e|, so with the magnitude in place of a and (1 + gamma_k)^p <= 1 + gamma_(p k) the
+    bound is gamma_(sexp (k + 3)) magnitude^sexp / mu^(sexp-1)."""
+    fr, ineq = _free(st), st["rtype"] != 0
+    ap, ad = LD(st["scal"][SC["AP"]]), LD(st["scal"][SC["AD"]])
+    tL, tU, muL, muU, ts, mus, g, pi = _l(st, "tL", "tU", "muL", "muU", "ts", "mus", "g", "pi")
+    dp, dmuL, dmuU, ds, dmus, dg, dpi = _l(st, D + ".dp", D + ".dmuL", D + ".dmuU", D + ".ds", D + ".dmus", D + ".dg", D + ".dpi")
+
+    def prod(x, dx, z, dz, sel):
+        return ((x + ap * dx) * (z + ad * dz))[sel], ((np.abs(x) + ap * np.abs(dx)) * (np.abs(z) + ad * np.abs(dz)))[sel]
+    parts = [prod(tL, dp, muL, dmuL, fr), prod(tU, -dp, muU, dmuU, fr), prod(ts, ds, mus, dmus, np.ones(st["ns"], bool)), prod(g, dg, pi, dpi, ineq)]
+    acc = sum(p_[0].sum() for p_ in parts)
+    macc = sum(p_[1].sum() for p_ in parts)
+    cnt = sum(len(p_[0]) for p_ in parts)
+    nc, mu = LD(st["ncomp"]), LD(st["scal"][SC["MU"]])
+    k = cnt + 7
+    if not mu > 0:
+        return {"acc": (acc, macc, k), "SM": (LD(0), LD(0), 1)}
+    r, mr = acc / nc / mu, macc / nc / mu
+    return {"acc": (acc, macc, k), "SM": (r ** sexp * mu, mr ** sexp * mu, sexp * (k + 3))}
+
+
+def ipm_sm_exact(acc, ncomp, mu, sexp):
+    """SM in float64 from the accumulator the device summed (a multi-workgroup launch leaves its partials in rpart)."""
+    mu_aff = acc / float(ncomp)
+    r = mu_aff / mu if mu > 0.0 else 0.0
+    return (r * r if sexp == 2 else (r * r * r * r if sexp == 4 else r * r * r)) * mu
+
+
+def tw_update(st, C, al, be, dev):
+    """iterate += (al, be) direction (oracle: IPM.run, last block); y of an inequality row is sg times the pi the device wrote (exact)."""
+    fr, ineq = _free(st), st["rtype"] != 0
+    al, be = LD(al), LD(be)
+    out = {}
+
+    def axpy(nm, a, d, sign=1):
+        x, dx = _l(st, nm, C + "." + d)
+        out[nm] = (x + sign * a * dx, np.abs(x) + np.abs(a * dx), 3)
+    axpy("p", al, "dp"); axpy("tL", al, "dp"); axpy("tU", al, "dp", -1); axpy("muL", be, "dmuL"); axpy("muU", be, "dmuU")
+    axpy("s", al, "ds"); axpy("ts", al, "ds"); axpy("mus", be, "dmus"); axpy("g", al, "dg"); axpy("pi", be, "dpi")
+    y, dy = _l(st, "y", C + ".dy")
+    out["y"] = (np.where(ineq, st["rtype"] * dev["pi"].astype(LD), y + be * dy), np.where(ineq, np.abs(dev["pi"].astype(LD)), np.abs(y) + np.abs(be * dy)), 3)
+    for nm in ("tL", "tU"):
+        out[nm] = (np.where(fr, out[nm][0], 1), np.where(fr, out[nm][1], 1), 3)
+    out["g"] = (np.where(ineq, out["g"][0], 1), np.where(ineq, out["g"][1], 1), 3)
+    return out
+
+
+def ipm_init_exact(st, origin, mu_factor):
+    """k_ipm_init_p then k_ipm_init_rest in float64 (oracle: IPM.__init__).  Single correctly rounded operations throughout: the slack
+    coefficients are +-1, so the products of the slack sum are exact and a fused multiply-add rounds as the plain addition does."""
+    lb, ub = st["lb"], st["ub"]
+    p = 0.5 * (lb + ub)
+    if origin:
+        w4 = 0.25 * (ub - lb)
+        p = np.minimum(np.maximum(0.0, lb + w4), ub - w4)
+    s = st["slo"] + 1.0
+    return {"p": p, "s": s}
+
+
+def ipm_init_rest_exact(st, mu_factor):
+    fr, ineq, sg = _free(st), st["rtype"] != 0, st["rtype"].astype(float)
+    mu0 = mu_factor * st["scale_q"]
+    with np.errstate(all="ignore"):
+        tl = np.where(fr, st["p"] - st["lb"], 1.0)
+        tu = np.where(fr, st["ub"] - st["p"], 1.0)
+        out = {"tL": tl, "tU": tu, "muL": np.where(fr, mu0 / tl, 0.0), "muU": np.where(fr, mu0 / tu, 0.0)}
+        ts = st["s"] - st["slo"]
+        out["ts"], out["mus"] = ts, mu0 / ts
+        a = st["act"].copy()
+        if st["ns"]:
+            sl = np.zeros(st["M"])
+            for rs in (st["rs0"], st["rs1"]):
+                has = rs >= 0
+                sl[has] = sl[has] + st["scoef"][rs[has]] * st["s"][rs[has]]
+            a = a + sl
+        g = np.where(ineq, np.maximum(sg * (a - st["r"]), 1.0), 1.0)
+        pi = np.where(ineq, mu0 / g, 0.0)
+    out["g"], out["pi"], out["y"] = g, pi, sg * pi
+    return out
+
+
+def ipm_col_prep_exact(st, rho_p, fixed):
+    fr = _free(st)
+    with np.errstate(all="ignore"):
+        return 1.0 / st["dS"], np.where(fr, st["muL"] / st["tL"] + st["muU"] / st["tU"] + rho_p, fixed)
+
+
+def tw_col_finish(dinv, u, w):
+    dinv, u, w = dinv.astype(LD), u.astype(LD), w.astype(LD)
+    return u - dinv * w, np.abs(u) + np.abs(dinv * w), 3
+
+
+def tw_sdiag_csr(ptr, col, vals, thinv):
+    """out_i = sum_k vals_k^2 thinv[col_k] as a running fused sum: each term passes the rounding of its square and at most cnt roundings of
+    the sum (the product with thinv is inside the fused operation), so k = terms + 2."""
+    R = len(ptr) - 1
+    v, cnt = np.zeros(R, LD), np.diff(ptr)
+    t = vals.astype(LD) ** 2 * thinv.astype(LD)[col]
+    row = np.repeat(np.arange(R), cnt)
+    np.add.at(v, row, t)
+    m = np.zeros(R, LD)
+    np.add.at(m, row, np.abs(t))
+    return v, m, cnt + 2
+
+
+# (n, M, ns): every length of {0 (ns, M), 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 8191, 12289, 70001, 262144, 262149}
+# appears, each of the three ranges is the longest somewhere; expected workgroups of the reductions = min(64, ceil(max / 4096)).
+# M = 0 is a bounds-only LP, which asm_sublp_setup accepts (m >= 0).
+IPM_CASES = [
+    (1, 1, 0), (256, 0, 0), (64, 63, 65), (255, 257, 256), (1025, 1023, 1024), (4096, 4095, 0), (4095, 4096, 4097), (4097, 1024, 63),
+    (8191, 12289, 4096), (70001, 65, 1), (262144, 1025, 255), (1023, 262149, 70001), (4097, 262144, 262149),
+]
+
+
+def ipm_red_grid(n, M, ns):
+    return min(64, max(1, (max(n, M, ns) + 4095) // 4096))
+
+
+def ipm_grid_all(n, M, ns):
+    return (max(n, M, ns, 1) + 255) // 256
+
+
+def ipm_decoys(st, D):
+    """Entries the ratio test (and the measures) must ignore, written into the state: a fixed column whose ratios would be the smallest of all
+    (1e-30), an equality row with negative dg and dpi and the same tiny ratios, and free columns with dp = 0.0 and dp = -0.0 on tiny
+    slacks (neither sign of zero is a negative component)."""
+    n, M = st["n"], st["M"]
+    if n >= 4:
+        j = n // 2
+        st["ub"][j] = st["lb"][j]
+        st["tL"][j] = st["tU"][j] = st["muL"][j] = st["muU"][j] = 1e-30
+        st[D + ".dp"][j] = -1.0
+        st[D + ".dmuL"][j] = st[D + ".dmuU"][j] = -1.0
+        for jz, z in ((0, 0.0), (n - 1, -0.0)):
+            st["ub"][jz] = st["lb"][jz] + 1.0
+            st["tL"][jz] = st["tU"][jz] = 1e-30
+            st["muL"][jz] = st["muU"][jz] = 1.0
+            st[D + ".dp"][jz] = z
+    if M >= 2:
+        i = M // 2
+        st["rtype"][i] = 0
+        st["g"][i] = st["pi"][i] = 1e-30
+        st[D + ".dg"][i] = st[D + ".dpi"][i] = -1.0
+    fr, eq = st["ub"] > st["lb"], st["rtype"] == 0
+    st["ncomp"] = max(2 * int(fr.sum()) + st["ns"] + int((~eq).sum()), 1)
+
+
+def ipm_plant(base, D, rg, pos, ratios=None):
+    """A copy of the state with a binding primal and a binding dual ratio at entry `pos` of range rg ('n': tL and muL of a free column, 'M': g
+    and pi of an inequality row, 's': ts and mus): half the smallest eligible ratio of the state (or `ratios`), made of x = ratio, dx = -1 so
+    that the quotient is exact.  Returns (state, ap, ad); asserts that the planted minimum is below 1 and unique by more than one ulp."""
+    st = dict(base)
+    for nm in ("ub", "lb", "rtype", "tL", "muL", "g", "pi", "ts", "mus", D + ".dp", D + ".dmuL", D + ".dg", D + ".dpi", D + ".ds", D + ".dmus", "tU", "muU", D + ".dmuU"):
+        st[nm] = base[nm].copy()
+    prim, dual = ipm_ratio_candidates(base, D)
+    if ratios is None:
+        ap = 0.5 * min(1.0, min(float(v.min(initial=BIG)) for v in prim.values()))
+        ad = 0.5 * min(1.0, min(float(v.min(initial=BIG)) for v in dual.values()))
+    else:
+        ap, ad = ratios
+    if rg == "n":
+        if not st["ub"][pos] > st["lb"][pos]:
+            st["ub"][pos] = st["lb"][pos] + 1.0
+        st["tL"][pos], st[D + ".dp"][pos], st["tU"][pos] = ap, -1.0, 1.0
+        st["muL"][pos], st[D + ".dmuL"][pos] = ad, -1.0
+        st["muU"][pos], st[D + ".dmuU"][pos] = 1.0, 1.0
+    elif rg == "M":
+        if st["rtype"][pos] == 0:
+            st["rtype"][pos] = 1
+        st["g"][pos], st[D + ".dg"][pos], st["pi"][pos], st[D + ".dpi"][pos] = ap, -1.0, ad, -1.0
+    else:
+        st["ts"][pos], st[D + ".ds"][pos], st["mus"][pos], st[D + ".dmus"][pos] = ap, -1.0, ad, -1.0
+    fr, eq = st["ub"] > st["lb"], st["rtype"] == 0
+    st["ncomp"] = max(2 * int(fr.sum()) + st["ns"] + int((~eq).sum()), 1)
+    if ratios is None:
+        for cands, a in (ipm_ratio_candidates(st, D)[0], ap), (ipm_ratio_candidates(st, D)[1], ad):
+            allc = np.sort(np.concatenate(list(cands.values())))
+            assert allc[0] == a and a < 1.0 and (len(allc) == 1 or allc[1] > np.nextafter(a, np.inf)), "planted minimum is not unique"
+    return st, ap, ad
+
+
+def ipm_planted_positions(st):
+    """(range, position) of every planted minimum of a case: first and last entry, the ends of the first wavefront, the last entry of a partial
+    wavefront, the first entry of a workgroup's second sweep, the last entry of the last workgroup's share, and - in the longest range - entries
+    beyond the end of each shorter range, where the clamped index re-reads that range's last element."""
+    L = {"n": st["n"], "M": st["M"], "s": st["ns"]}
+    gr = ipm_red_grid(st["n"], st["M"], st["ns"])
+    out = []
+    for rg, ln in L.items():
+        if ln == 0:
+            continue
+        pos = {0, ln - 1, min(63, ln - 1), min(64, ln - 1), (ln - 1) // 64 * 64, gr * 1024}
+        last_wg = [t for t in range(max(0, ln - gr * 1024 - 1024), ln) if (t // 1024) % gr == gr - 1]
+        if last_wg:
+            pos.add(last_wg[-1])
+        for other in L.values():
+            pos.update({other, other + 1, other + 70})
+        out += [(rg, p) for p in sorted(pos) if 0 <= p < ln]
+    return out
+
+
+def ipm_decoy_state(case, mus):
+    """State of the ratio-test cases: the decoys that must be ignored are in place (ipm_plant adds the binding entry)."""
+    st = ipm_state(700 + case, *IPM_CASES[case], mu=mus[(case + 3) % len(mus)])
+    ipm_decoys(st, "A")
+    return st
+
+
+IPM_MUS = [1e2, 1.0, 1e-2, 1e-4, 1e-6, 1e-8, 1e-10, 1e-12]      # complementarity levels the solver passes through, dealt to the cases
+
+
+# ---- the twin's stages chained into interior-point iterations (tests/test_ipm_stages_cpu.py): NumPy products with the matrix, the oracle's own
+# Cholesky factor as preconditioner, every stage the float64 rounding of the twin's long-double value
+def _f(tw, st, names=None):
+    for nm in (names or [k for k in tw if isinstance(tw[k], tuple)]):
+        if nm in SC:
+            st["scal"][SC[nm]] = float(tw[nm][0])
+        elif nm in st:
+            st[nm] = np.asarray(tw[nm][0], np.float64)
+
+
+def ipm_twin_start(lp):
+    """Start point of oracle IPM.__init__ through ipm_init_exact / ipm_init_rest_exact."""
+    from oracle import lp_solver as O
+    n, M, ns = lp.n, lp.M, lp.ns
+    st = {"n": n, "M": M, "ns": ns, "rtype": lp.rtype.astype(np.int32), "srow": lp.srow.astype(np.int32)}
+    st["rs0"], st["rs1"] = ipm_slack_lists(M, st["srow"])
+    for nm in IPM_N + IPM_M + IPM_S:
+        st[nm] = np.zeros(ipm_vec_len(st, nm))
+    for nm in ("q", "lb", "ub", "r", "w", "slo", "scoef"):
+        st[nm] = getattr(lp, nm).copy()
+    st["scale_q"] = max(1.0, np.abs(lp.q).max(initial=0.0), np.abs(lp.w).max(initial=0.0))
+    fr, ineq = lp.ub > lp.lb, lp.rtype != 0
+    st["ncomp"] = max(2 * int(fr.sum()) + ns + int(ineq.sum()), 1)
+    st["scal"] = np.zeros(len(IPM_SCALARS))
+    st.update(ipm_init_exact(st, 1 if ns == 0 else 0, 1.0))
+    st["act"] = lp.A @ st["p"]
+    st.update(ipm_init_rest_exact(st, O.IPM_MU0_NORMAL if ns == 0 else 1.0))
+    return st
+
+
+def ipm_twin_iteration(lp, st):
+    """One iteration of oracle IPM.run in row form from the twin's stages.  Returns (pinf, dinf, mu, ap, ad) of the iteration."""
+    from oracle import lp_solver as O
+    A, M = lp.A, lp.M
+    st["act"], st["aty"] = A @ st["p"], A.T @ st["y"]
+    tw = tw_measures(st)
+    _f(tw, st, ["rp", "rdp", "rds", "MU"])
+    for nm, v in ipm_measures_exact(st, st["rp"], st["rdp"], st["rds"]).items():
+        st["scal"][SC[nm]] = v
+    pinf, dinf, mu, rpmax = st["scal"][SC["PINF"]], st["scal"][SC["DINF"]], st["scal"][SC["MU"]], st["scal"][SC["RPMAX"]]
+    st.update(ipm_theta_exact(st, IPM_RHO_P))
+    S = O.dsyrk(1.0, A * np.sqrt(st["thp_inv"]), lower=True)
+    idx = np.arange(M)
+    S[idx, idx] += st["dS"]
+    d0 = S[idx, idx].copy()
+    S[idx, idx] += 1e-13 * d0 + 1e-30
+    L = O.chol_guard(S, d0)
+    applyS = lambda v: A @ (st["thp_inv"] * (A.T @ v))      # (k_vec_mul between the two products)
+
+    def solve(mode, base, D, tp=0.0, td=0.0):
+        _f(tw_rhs1(st, base, mode, tp, td), st, ["rcL", "rcU", "rcs", "rcg"])
+        t2 = tw_rhs1(st, base, mode, tp, td, dev=dict(st, hp=st["hp"]))
+        _f(t2, st, ["hp", "hs"])
+        _f(tw_rhs1(st, base, mode, tp, td, dev=st), st, ["tmpn"])
+        st["t1"] = A @ st["tmpn"]
+        _f(tw_rhs2(st, 0.0 if mode == 2 else 1.0), st)
+        st[D + ".dy"] = O.chol_solve(L, st["rhs"])
+        st["sres"] = applyS(st[D + ".dy"])
+        _f(tw_res(st, D), st)
+        ex = ipm_res_exact(st, st["res"], 0, 0.0, 0.0)
+        tol = max(O.PCG_FLOOR * ex["RMAX"], O.PCG_KAPPA * rpmax)
+        if ex["EMAX"] > tol:
+            st["corr"] = O.chol_solve(L, st["res"])
+            st["pcg"] = st["corr"].copy()
+            st["scal"][SC["RZ"]] = st["scal"][SC["RZ0"]] = float(tw_pcg_start(st)["RZ"][0])
+            for _ in range(O.PCG_MAXIT):
+                st["sres"] = applyS(st["pcg"])
+                t1 = tw_pcg_step1(st, D)
+                if not t1["ok"]:
+                    break
+                st[D + ".dy"], st["res"] = np.asarray(t1["x"][0], np.float64), np.asarray(t1["res"][0], np.float64)
+                if np.abs(st["res"]).max(initial=0.0) <= tol:
+                    break
+                st["corr"] = O.chol_solve(L, st["res"])
+                t2_ = tw_pcg_step2(st)
+                st["pcg"], st["scal"][SC["RZ"]] = np.asarray(t2_["pcg"][0], np.float64), float(t2_["RZ"][0])
+        st["tN"] = A.T @ st[D + ".dy"]
+        st.update(ipm_dir_exact(st, D))
+        own = [D + "." + c for c in ("dp", "ds")]
+        _f(tw_dir(st, D, st), st, own)
+        _f(tw_dir(st, D, st), st, [D + "." + c for c in ("dmuL", "dmuU", "dmus", "dg")])
+
+    def steps(D):
+        e = ipm_steps_exact(st, D)
+        st["scal"][SC["AP"]], st["scal"][SC["AD"]] = e["AP"], e["AD"]
+        return e["AP"], e["AD"]
+    solve(0, "A", "A")
+    steps("A")
+    _f(tw_muaff(st, "A", 3), st, ["SM"])
+    solve(1, "A", "C")
+    ap, ad = steps("C")
+    a_, c_ = "A", "C"
+    for _ in range(O.IPM_MCC):
+        if min(ap, ad) >= 0.9:
+            break
+        solve(2, c_, a_, min(1.0, ap + O.MCC_DELTA), min(1.0, ad + O.MCC_DELTA))
+        for c in ("dp", "ds", "dg", "dy", "dmuL", "dmuU", "dmus", "dpi"):
+            st[a_ + "." + c] = st[a_ + "." + c] + st[c_ + "." + c]
+        ap2, ad2 = steps(a_)
+        if not (ap2 >= ap and ad2 >= ad and ap2 + ad2 >= ap + ad + O.MCC_GAMMA * O.MCC_DELTA):
+            break
+        a_, c_ = c_, a_
+        ap, ad = ap2, ad2
+    eta = 0.995 if mu >= 1.0 else min(max(0.995, 1.0 - mu / st["scale_q"]), 0.999999)
+    al, be = min(1.0, eta * ap), min(1.0, eta * ad)
+    new_pi = np.asarray(tw_update(st, c_, al, be, {"pi": st["pi"]})["pi"][0], np.float64)
+    _f(tw_update(st, c_, al, be, {"pi": new_pi}), st)
+    return pinf, dinf, mu, ap, ad
+
+
+def ipm_stage_state(case):
+    """The state every stage is run from alone (tests/test_ipm_stages_gpu.py; its twin magnitudes are checked in tests/test_ipm_stages_cpu.py):
+    ipm_state with the decoy of k_ipm_measures - a fixed column with a huge dual residual - and a CG state with positive curvature and a
+    modest condition number of its dot products (tw_pcg_step1, tw_pcg_step2: kappa)."""
+    st = ipm_state(500 + case, *IPM_CASES[case], mu=IPM_MUS[case % len(IPM_MUS)])
+    fx = np.flatnonzero(st["ub"] == st["lb"])
+    if len(fx):
+        st["q"][fx[0]] = 1e250
+    rng = np.random.default_rng(900 + case)
+    st["sres"] = 0.5 * st["pcg"] + 0.2 * rng.standard_normal(st["M"])
+    st["corr"] = 0.5 * st["res"] + 0.2 * rng.standard_normal(st["M"])
+    st["scal"][SC["RZ"]], st["scal"][SC["RZ0"]] = 0.7, 2.1
+    return st
+
+
+def ipm_helper_operands(case, st):
+    """Operands of the column-form and reduced-row helper stages for a state: r, w (M) of the column form; kept rows E (a non-monotone
+    list) and dropped rows I with their diagonal dI, ze (|E|), and CSR rows (ptr, col, vals) with 0 .. 9 entries, row 0 empty."""
+    n, M = st["n"], st["M"]
+    rng = np.random.default_rng(77 + case)
+    op = {"r": rng.standard_normal(M), "w": rng.standard_normal(M)}
+    if M > 0:
+        perm = rng.permutation(M).astype(np.int32)
+        nE = M - M // 3
+        op["E"], op["I"] = perm[:nE], perm[nE:]
+        cnt = rng.integers(0, 10, M)
+        cnt[0] = 0
+        op["ptr"] = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+        nnz = int(op["ptr"][-1])
+        op["col"] = rng.integers(0, n, nnz).astype(np.int32)
+        op["ze"], op["dI"], op["vals"] = rng.standard_normal(nE), 10.0 ** rng.uniform(-3, 3, M - nE), rng.standard_normal(nnz)
+    return op
