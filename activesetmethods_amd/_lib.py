@@ -48,6 +48,13 @@ class IpmStage(C.Structure):
                 ("x", C.c_int64 * 4), ("ix", C.c_int64 * 2), ("len", C.c_int64 * 3)]
 
 
+class AsStage(C.Structure):
+    """asm_as_stage: one stage of asm_test_as_stages (include/asm_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("with_y", C.c_int32), ("accumulate", C.c_int32), ("check_only", C.c_int32), ("have_prev", C.c_int32),
+                ("rperm", C.c_int32), ("fam", C.c_int32), ("k", C.c_int32), ("set", C.c_int32 * 3), ("pad_", C.c_int32), ("e", C.c_int64),
+                ("tol_p", C.c_double), ("tol_d", C.c_double), ("tol_m", C.c_double), ("x", C.c_int64 * 4)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
@@ -124,6 +131,8 @@ PROTOTYPES = {
     "asm_test_build_dispatch": (C.c_int, [_P, _D, C.c_int, _I32, C.c_int64, _D, _D, _D, _D, _I64, _I32, _I32, _I32]),
     "asm_test_ipm_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I64, _D, C.c_int64, _I32, C.c_int64, _D, _D, C.POINTER(C.c_uint32),
                                       _D, C.POINTER(C.c_uint32), C.POINTER(IpmStage), C.c_int64, C.POINTER(C.c_uint32)]),
+    "asm_test_as_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I64, _D, C.c_int64, _I32, C.c_int64, _D, C.c_int64,
+                                     C.POINTER(AsStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_cholesky": (C.c_int, [_P, _D, C.c_int64, _D]),
     "asm_test_chol_solve": (C.c_int, [_P, _D, C.c_int64, _D, _D]),
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),

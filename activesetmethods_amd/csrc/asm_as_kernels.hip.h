@@ -442,6 +442,10 @@ __global__ __launch_bounds__(256) void k_face_ns_combine(AsmBt abt, const double
 // inequality of the face is violated, the anchor (pa, sa, acta) moves towards the candidate until the first one blocks and
 // that one is marked in W and reported (AC_NCHG = family: 0 row, 1 slack bound, 2 lower, 3 upper; AC_NDIFF = its index;
 // ties: family order, then lowest index).  AC_NVIOL = number of violated inequalities (0: the candidate is feasible).
+// The selection pass recomputes each ratio from the same memory with the same statements (quotients of differences: nothing to contract), so
+// with nviol > 0 the entry that gave alpha is found again and the sentinel 1e300 of `code` cannot survive - provided the ratios are numbers:
+// a ratio inf / inf (an infinite anchor margin) counts in nviol but never in alpha.  Then nothing is marked and nothing moves: AC_NCHG =
+// AC_NDIFF = -1 with AC_NVIOL > 0, which the host takes as the failure of the method.
 __device__ __forceinline__ double as_ratio(double g0, double g1) {
     const double a = fmax(g0, 0.0);
     return a / (a - g1);
@@ -519,6 +523,10 @@ __global__ __launch_bounds__(1024) void k_face_ns_step(AsmBt abt, AsPtrs A, AsSe
         if (g1 < -tol_p && as_ratio(A.ub[j] - pa[j], g1) == alpha) code = fmin(code, 3.0 * F40 + (double)j);
     }
     code = blk_reduce_min(code, sh);
+    if (!(code < 4.0 * F40)) {                        // no entry reproduced alpha (see above): report, mark nothing
+        if (threadIdx.x == 0) { A.cnt[AC_NVIOL] = (int)nviol; A.cnt[AC_NCHG] = -1; A.cnt[AC_NDIFF] = -1; A.scal[AS_HARDRES] = hres; }
+        return;
+    }
     const int fam = (int)(code / F40);
     const int64_t e = (int64_t)(code - (double)fam * F40);
     const double al = fmin(alpha, 1.0);

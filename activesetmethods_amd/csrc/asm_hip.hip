@@ -1154,6 +1154,17 @@ struct IpmLayout {
     int64_t int_len() const { return 3 * Mp + nsp; }
 };
 
+// Pitches and lengths of the two arenas of the device-resident active-set machinery (asm_as_kernels.hip.h): do_setup allocates by them,
+// Solver::as_bind places the vectors.  Doubles: 17 n-vectors, 17 M-vectors, 4 slack vectors, the scalar block.  Ints: six working sets
+// (rowst | bst | sst each), ksoft | Hidx | hpos, Fidx | fpos, the counter block.
+struct AsLayout {
+    int64_t ldn, Mp, nsp;
+    AsLayout(int64_t ln, int64_t lm, int64_t ls) : ldn(ln), Mp(lm), nsp(ls) {}
+    explicit AsLayout(const IpmLayout& l) : ldn(l.ldn), Mp(l.Mp), nsp(l.nsp) {}
+    int64_t dbl_len() const { return 17 * ldn + 17 * Mp + 4 * nsp + 64; }
+    int64_t int_len() const { return 6 * (Mp + ldn + nsp) + 3 * Mp + 2 * ldn + 64; }
+};
+
 struct Solver {
     // out = A x for a k x ncols matrix of few, long rows (the basis Zt): one workgroup per row when that fills the chip better
     void gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
@@ -2126,9 +2137,24 @@ struct Solver {
     int final_sets = 0;
     int as_nH = 0, as_nF = 0;
 
+    // where the active-set state lives: the handle's arenas (as_bind()), or buffers of a test hook's with the pitches of an AsLayout
+    struct AsArena {
+        double* base = nullptr;       // AsLayout::dbl_len() doubles
+        int* ibase = nullptr;         // AsLayout::int_len() ints
+        const int* rperm = nullptr;   // the row order of the factorisations, or null
+        int64_t ln = 0, lm = 0, ls = 0;
+    } as_arena;
     void as_bind() {
-        const int64_t ln = h->ldn, lm = h->Mp, ls = h->nsp;
-        double* a = h->d_as;
+        AsArena a;
+        a.base = h->d_as; a.ibase = h->d_as_i; a.rperm = h->row_band > 0 ? h->d_rowperm : nullptr;
+        a.ln = h->ldn; a.lm = h->Mp; a.ls = h->nsp;
+        as_bind(a);
+    }
+    // the ONLY place that lays the two arenas out (the LP vectors are those of the interior-point arena: ipm_bind comes first)
+    void as_bind(const AsArena& ar) {
+        as_arena = ar;
+        const int64_t ln = ar.ln, lm = ar.lm, ls = ar.ls;
+        double* a = ar.base;
         auto N = [&]() { double* r_ = a; a += ln; return r_; };
         auto Mv = [&]() { double* r_ = a; a += lm; return r_; };
         auto Sv = [&]() { double* r_ = a; a += ls; return r_; };
@@ -2142,20 +2168,81 @@ struct Solver {
         d_y0 = Mv(); d_act0 = Mv(); d_acta = Mv(); d_actf = Mv(); d_yf = Mv();
         A.s = Sv(); d_s0 = Sv(); d_sa = Sv(); d_sf = Sv();
         A.scal = a;
-        int* ia = h->d_as_i;
+        int* ia = ar.ibase;
         auto Ni = [&]() { int* r_ = ia; ia += ln; return r_; };
         auto Mi = [&]() { int* r_ = ia; ia += lm; return r_; };
         auto Si = [&]() { int* r_ = ia; ia += ls; return r_; };
         for (int k = 0; k < 6; ++k) { S_[k].rowst = Mi(); S_[k].bst = Ni(); S_[k].sst = Si(); }
         A.ksoft = Mi(); A.Hidx = Mi(); A.hpos = Mi(); A.Fidx = Ni(); A.fpos = Ni();
-        A.rperm = h->row_band > 0 ? h->d_rowperm : nullptr;
+        A.rperm = ar.rperm;
         A.cnt = ia;
     }
+    // ---- launch sites of the active-set kernels (asm_as_kernels.hip.h): the solver and the test hook asm_test_as_stages launch through these
+    // members only; each returns the number of workgroups it launched
+    unsigned as_grid_m1() const { return (unsigned)((lp.M + 255) / 256 + 1); }
+    unsigned as_grid_n() const { return (unsigned)((lp.n + 255) / 256); }
+    unsigned launch_as_sl() { const unsigned g = as_grid_m1(); asmb::launch(k_as_sl, dim3(g), dim3(256), h->stream, A); return g; }
+    unsigned launch_as_sl_values() { const unsigned g = as_grid_m1(); asmb::launch(k_as_sl_values, dim3(g), dim3(256), h->stream, A); return g; }
+    unsigned launch_as_clip0(const double* src, double* out) { const dim3 g = asmb::blocks(lp.n); asmb::launch(k_as_clip0, g, dim3(256), h->stream, A.lb, A.ub, src, out, lp.n); return g.x; }
+    unsigned launch_as_smax(const double* src, double* dst) { const dim3 g = asmb::blocks(lp.ns); asmb::launch(k_as_smax, g, dim3(256), h->stream, src, A.slo, dst, lp.ns); return g.x; }
+    unsigned launch_as_copy_sets(const AsSets& dst, const AsSets& src) {
+        const unsigned g = grid_all();
+        asmb::launch(k_as_copy_sets, dim3(g), dim3(256), h->stream, dst, src, lp.M, lp.n, lp.ns);
+        return g;
+    }
+    unsigned launch_as_pack(const AsSets& S, double* dst) {
+        const unsigned g = grid_all();
+        asmb::launch(k_as_pack, dim3(g), dim3(256), h->stream, A.p, A.z, A.y, A.act, A.s, S, lp.n, lp.M, lp.ns, dst);
+        return g;
+    }
+    unsigned launch_as_identify(const AsSets& S) { const unsigned g = grid_all(); asmb::launch(k_as_identify, dim3(g), dim3(256), h->stream, P, S); return g; }
+    unsigned launch_as_setup(const AsSets& cur, const double* p_ref) {
+        asmb::launch(k_as_setup, dim3(1), dim3(1024), h->stream, A, cur, p_ref, as_arena.ln, as_arena.lm);
+        return 1;
+    }
+    unsigned launch_as_rhs(const double* y_ref) { const unsigned g = grid_all(); asmb::launch(k_as_rhs, dim3(g), dim3(256), h->stream, A, y_ref); return g; }
+    // (grids over the nH hard rows: the count the host read back after k_as_setup)
+    unsigned launch_as_res_p(int nH) { const dim3 g = asmb::blocks(nH); asmb::launch(k_as_res_p, g, dim3(256), h->stream, A); return g.x; }
+    unsigned launch_as_gather_h(int nH) { const dim3 g = asmb::blocks(nH); asmb::launch(k_as_gather_h, g, dim3(256), h->stream, A); return g.x; }
+    unsigned launch_as_add_yh(int nH) { const dim3 g = asmb::blocks(nH); asmb::launch(k_as_add_yh, g, dim3(256), h->stream, A); return g.x; }
+    unsigned launch_as_scatter_h(const double* src, int accumulate) {
+        const unsigned g = as_grid_m1();
+        asmb::launch(k_as_scatter_h, dim3(g), dim3(256), h->stream, A, src, accumulate);
+        return g;
+    }
+    unsigned launch_as_add_f() { const unsigned g = as_grid_n(); asmb::launch(k_as_add_f, dim3(g), dim3(256), h->stream, A); return g; }
+    unsigned launch_as_rd() { const unsigned g = as_grid_n(); asmb::launch(k_as_rd, dim3(g), dim3(256), h->stream, A); return g; }
+    unsigned launch_as_merge(int with_y) { const unsigned g = grid_all(); asmb::launch(k_as_merge, dim3(g), dim3(256), h->stream, A, with_y); return g; }
+    unsigned launch_as_finish(const AsSets& cur, const AsSets& nx, const AsSets& prev, int have_prev, double tol_p, double tol_d) {
+        asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, cur, nx, prev, have_prev, tol_p, tol_d);
+        return 1;
+    }
+    unsigned launch_face_primal_finish(const AsSets& W, const AsSets& part, double tol_p, double tol_m, int check_only) {
+        asmb::launch(k_face_primal_finish, dim3(1), dim3(1024), h->stream, A, W, part, tol_p, tol_m, check_only);
+        return 1;
+    }
+    unsigned launch_face_ns_combine(const double* p0, const double* Zbuf, int64_t ldz, const double* u, int k, double* p) {
+        const unsigned g = as_grid_n();
+        asmb::launch(k_face_ns_combine, dim3(g), dim3(256), h->stream, p0, Zbuf, ldz, u, k, p, lp.n);
+        return g;
+    }
+    unsigned launch_face_ns_step(const AsSets& W, double* pa, double* sa, double* acta, double tol_p) {
+        asmb::launch(k_face_ns_step, dim3(1), dim3(1024), h->stream, A, W, pa, sa, acta, tol_p);
+        return 1;
+    }
+    unsigned launch_face_ns_unmark(const AsSets& W, int fam, int64_t e) { asmb::launch(k_face_ns_unmark, dim3(1), dim3(64), h->stream, A, W, fam, e); return 1; }
+    unsigned launch_face_ns_col(const double* Ah, int64_t ld, int fam, int64_t e, const double* p0, const double* t0) {
+        asmb::launch(k_face_ns_col, dim3(1), dim3(1024), h->stream, A, Ah, ld, fam, e, p0, t0);
+        return 1;
+    }
+    unsigned launch_face_ns_z(double* z) { const unsigned g = as_grid_n(); asmb::launch(k_face_ns_z, dim3(g), dim3(256), h->stream, A, z); return g; }
+    unsigned launch_face_dual_finish(const AsSets& D, double tol_m) { asmb::launch(k_face_dual_finish, dim3(1), dim3(1024), h->stream, A, D, tol_m); return 1; }
+    unsigned launch_face_kkt(const AsSets& D) { asmb::launch(k_face_kkt, dim3(1), dim3(1024), h->stream, A, D); return 1; }
     // per LP: reference point of the unique-optimum polish (0 clipped into the box), slack offsets of the rows
     void as_begin_lp() {
         as_bind();
-        asmb::launch(k_as_sl, dim3((unsigned)((lp.M + 255) / 256 + 1)), dim3(256), h->stream, A);
-        asmb::launch(k_as_clip0, asmb::blocks(lp.n), dim3(256), h->stream, A.lb, A.ub, nullptr, d_zero, lp.n);
+        launch_as_sl();
+        launch_as_clip0(nullptr, d_zero);
     }
     void as_read() {
         HIPCHK(asmb::copy_async(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -2163,7 +2250,7 @@ struct Solver {
         HIPCHK(asmb::sync(h->stream));
     }
     void as_copy_sets(int dst, int src) {
-        asmb::launch(k_as_copy_sets, dim3(grid_all()), dim3(256), h->stream, S_[dst], S_[src], lp.M, lp.n, lp.ns);
+        launch_as_copy_sets(S_[dst], S_[src]);
     }
     void as_upload_sets(const ActiveSet& as, int dst) {
         std::vector<int> buf((size_t)(lp.M + lp.n + lp.ns));
@@ -2184,7 +2271,7 @@ struct Solver {
         if (!asmb::in_fiber() && h->d_dl) {
             // outside a batch: packed on the device, one copy into pinned memory (eight copies into pageable vectors cost the host tens of
             // microseconds each, with the GPU idle in between)
-            asmb::launch(k_as_pack, dim3(grid_all()), dim3(256), h->stream, A.p, A.z, A.y, A.act, A.s, S_[final_sets], n, M, ns, h->d_dl);
+            launch_as_pack(S_[final_sets], h->d_dl);
             const size_t bytes = (size_t)(2 * n + 2 * M + ns) * sizeof(double) + (size_t)(M + n + ns) * sizeof(int);
             HIPCHK(asmb::copy_async(h->h_dl, h->d_dl, bytes, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(asmb::sync(h->stream));
@@ -2212,7 +2299,7 @@ struct Solver {
         as.valid = true;
     }
     void identify_dev(int dst) {
-        asmb::launch(k_as_identify, dim3(grid_all()), dim3(256), h->stream, P, S_[dst]);
+        launch_as_identify(S_[dst]);
     }
 
     // Equality-constrained solve on the working set `cur` (oracle: eqp / _face_primal_solve / face_dual's solve).
@@ -2222,8 +2309,7 @@ struct Solver {
     // Leaves t = Ah p and tN = Ah' y (mode 1: tN = Ah' u_full) for the tail kernel.
     bool part_factor = false;   // the main factor is the factor of the partition's Schur matrix (face_polish re-uses it for the rounds on the same sets)
     void as_solve(const AsSets& cur, const double* p_ref, const double* y_ref, int mode, bool reuse_factor = false) {
-        const unsigned gA = grid_all(), gM = (unsigned)((lp.M + 255) / 256 + 1), gN = (unsigned)((lp.n + 255) / 256);
-        asmb::launch(k_as_setup, dim3(1), dim3(1024), h->stream, A, cur, p_ref, h->ldn, h->Mp);
+        launch_as_setup(cur, p_ref);
         HIPCHK(asmb::copy_async(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
         const int nH = h->h_ascnt[AC_NH], nF = h->h_ascnt[AC_NF];
@@ -2232,7 +2318,7 @@ struct Solver {
         if (nH > 0) {
             dev.gemv_n_dev(h->d_Ah, A.pB, A.t);
             if (any_soft) dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
-            asmb::launch(k_as_rhs, dim3(gA), dim3(256), h->stream, A, y_ref);
+            launch_as_rhs(y_ref);
         }
         if (nH > 0 && nF > 0) {
             if (!(reuse_factor && part_factor)) {
@@ -2243,31 +2329,30 @@ struct Solver {
                 part_factor = false;
             }
             const int sweeps = mode == 1 ? 3 : 4;
-            const unsigned gH = (unsigned)((nH + 255) / 256);
             for (int it = 0; it < sweeps; ++it) {
                 if (mode != 2) {
                     dev.gemv_n_dev(h->d_Ah, A.pF, A.t);                                                  // A_HF pF
-                    asmb::launch(k_as_res_p, dim3(gH), dim3(256), h->stream, A);
+                    launch_as_res_p(nH);
                     dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
-                    asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.u, mode == 1 ? 1 : 0);
+                    launch_as_scatter_h(A.u, mode == 1 ? 1 : 0);
                     dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' u
-                    asmb::launch(k_as_add_f, dim3(gN), dim3(256), h->stream, A);
+                    launch_as_add_f();
                 }
                 if (mode != 1) {
-                    asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.yH, 0);
+                    launch_as_scatter_h(A.yH, 0);
                     dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' yH
-                    asmb::launch(k_as_rd, dim3(gN), dim3(256), h->stream, A);
+                    launch_as_rd();
                     dev.gemv_n_dev(h->d_Ah, A.rd, A.t);                                                  // A_HF rd
-                    asmb::launch(k_as_gather_h, dim3(gH), dim3(256), h->stream, A);
+                    launch_as_gather_h(nH);
                     dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
-                    asmb::launch(k_as_add_yh, dim3(gH), dim3(256), h->stream, A);
+                    launch_as_add_yh(nH);
                 }
             }
         }
-        if (nH > 0) asmb::launch(k_as_merge, dim3(gA), dim3(256), h->stream, A, mode != 1 ? 1 : 0);
+        if (nH > 0) launch_as_merge(mode != 1 ? 1 : 0);
         dev.gemv_n_dev(h->d_Ah, A.p, A.t);
         if (mode == 1) {
-            asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.uacc, 0);
+            launch_as_scatter_h(A.uacc, 0);
             dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
         } else {
             dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
@@ -2290,7 +2375,7 @@ struct Solver {
             } else {
                 as_solve(S_[cur], p_ref, y_ref, 0);
             }
-            asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, S_[cur], S_[nx], S_[prev], have_prev ? 1 : 0, TOL_P, TOL_D);
+            launch_as_finish(S_[cur], S_[nx], S_[prev], have_prev ? 1 : 0, TOL_P, TOL_D);
             as_read();
             const double pr = h->h_asscal[AS_PR], du = h->h_asscal[AS_DU];
             h->stats.kkt_pr = pr;
@@ -2373,7 +2458,6 @@ struct Solver {
 
     bool face_primal_anchored() {
         const int64_t n = lp.n, M = lp.M, ns = lp.ns, ldz = h->ldn;
-        const unsigned gM = (unsigned)((M + 255) / 256 + 1), gN = (unsigned)((n + 255) / 256);
         as_copy_sets(4, 3);
         as_solve(S_[4], nullptr, nullptr, 1);            // p0 = least-norm point of the partition; its factor, Hidx, Fmask stay
         const int nH0 = as_nH;
@@ -2387,12 +2471,12 @@ struct Solver {
             const int k = (int)members.size();
             if (k > 0) {
                 HIPCHK(asmb::copy_async(h->d_nsu, u.data(), k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                asmb::launch(k_face_ns_combine, dim3(gN), dim3(256), h->stream, p0, h->d_Zbuf, ldz, h->d_nsu, k, A.p, n);
+                launch_face_ns_combine(p0, h->d_Zbuf, ldz, h->d_nsu, k, A.p);
             } else {
                 dcopy(A.p, p0, n);
             }
             dev.gemv_n_dev(h->d_Ah, A.p, A.t);
-            asmb::launch(k_face_ns_step, dim3(1), dim3(1024), h->stream, A, S_[4], d_pa, d_sa, d_acta, TOL_P);
+            launch_face_ns_step(S_[4], d_pa, d_sa, d_acta, TOL_P);
             as_read();                                    // (the host copy of u is no longer needed by the device after this)
             const int nviol = h->h_ascnt[AC_NVIOL];
             if (h->knobs.verbose && (st < 5 || st % 20 == 0 || nviol == 0))
@@ -2404,7 +2488,7 @@ struct Solver {
                 for (int j = 0; j < k; ++j)
                     if (-sign[j] * u[j] > worst) { worst = -sign[j] * u[j]; jw = j; }
                 if (jw < 0) return true;                  // feasible, every multiplier has the right sign: THE least-norm point
-                asmb::launch(k_face_ns_unmark, dim3(1), dim3(64), h->stream, A, S_[4], members[jw].first, members[jw].second);
+                launch_face_ns_unmark(S_[4], members[jw].first, members[jw].second);
                 dcopy(d_pa, A.p, n); dcopy(d_sa, A.s, ns); dcopy(d_acta, A.act, M);
                 const int last = k - 1;
                 if (jw != last) {
@@ -2418,18 +2502,19 @@ struct Solver {
             }
             const int fam = h->h_ascnt[AC_NCHG];
             const int64_t e = h->h_ascnt[AC_NDIFF];
-            asmb::launch(k_face_ns_col, dim3(1), dim3(1024), h->stream, A, h->d_Ah, h->ldn, fam, e, p0, t0);
+            if (fam < 0) return false;                    // no blocking inequality could be named (a ratio that is not a number): k_face_ns_step
+            launch_face_ns_col(h->d_Ah, h->ldn, fam, e, p0, t0);
             if (nH0 > 0) {
                 dev.gemv_n_dev(h->d_Ah, A.rd, A.t);
-                asmb::launch(k_as_gather_h, asmb::blocks(nH0), dim3(256), h->stream, A);
+                launch_as_gather_h(nH0);
                 dev.chol_solve_dev(h->main_fac, A.v, A.u, nH0);
-                asmb::launch(k_as_scatter_h, dim3(gM), dim3(256), h->stream, A, A.u, 0);
+                launch_as_scatter_h(A.u, 0);
                 dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
             } else {
                 HIPCHK(asmb::fill_async(A.tN, 0, h->ldn * sizeof(double), h->stream));
             }
             double* znew = h->d_Zbuf + (int64_t)k * ldz;
-            asmb::launch(k_face_ns_z, dim3(gN), dim3(256), h->stream, A, znew);
+            launch_face_ns_z(znew);
             asmb::launch(k_gemv_n, asmb::blocks(k + 1, 4), dim3(256), h->stream, h->d_Zbuf, ldz, znew, h->d_nsdots, (int64_t)(k + 1), ldz);
             HIPCHK(asmb::copy_async(h->h_nsdots, h->d_nsdots, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(asmb::copy_async(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2452,9 +2537,9 @@ struct Solver {
     int face_polish() {
         if (h->test_no_polish) return 0;
         const int64_t n = lp.n, M = lp.M, ns = lp.ns;
-        asmb::launch(k_as_clip0, asmb::blocks(n), dim3(256), h->stream, A.lb, A.ub, P.p, d_pref, n);
+        launch_as_clip0(P.p, d_pref);
         as_solve(S_[3], d_pref, P.y, 0);
-        asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
+        launch_as_finish(S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
         as_read();
         h->stats.kkt_pr = h->h_asscal[AS_PR];
         h->stats.kkt_du = h->h_asscal[AS_DU];
@@ -2468,7 +2553,7 @@ struct Solver {
         as_copy_sets(5, 3);
         for (int r = 0; r < FACE_BULK; ++r) {
             as_solve(S_[5], nullptr, nullptr, 2, r == 0);
-            asmb::launch(k_face_dual_finish, dim3(1), dim3(1024), h->stream, A, S_[5], FACE_TOL_M);
+            launch_face_dual_finish(S_[5], FACE_TOL_M);
             as_read();
             if (h->knobs.verbose) std::fprintf(stderr, "[asm] face dual %d: nH %d nF %d viol %d\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL]);
             if (h->h_ascnt[AC_NVIOL] == 0) { okd = true; break; }
@@ -2480,7 +2565,7 @@ struct Solver {
             as_copy_sets(4, 3);
             for (int r = 0; r < FACE_BULK; ++r) {
                 as_solve(S_[4], nullptr, nullptr, 1, r == 0);
-                asmb::launch(k_face_primal_finish, dim3(1), dim3(1024), h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 0);
+                launch_face_primal_finish(S_[4], S_[3], TOL_P, FACE_TOL_M, 0);
                 as_read();
                 if (h->knobs.verbose) std::fprintf(stderr, "[asm] face primal bulk %d: nH %d nF %d viol %d rel %d hres %.2e\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL], h->h_ascnt[AC_NREL], h->h_asscal[AS_HARDRES]);
                 if (h->h_asscal[AS_HARDRES] > TOL_P) break;            // over-determined working set
@@ -2492,7 +2577,7 @@ struct Solver {
             if (!okp && face_primal_anchored()) {
                 // the answer is the least-norm point of the FINAL working set, computed like any other (fresh factorisation)
                 as_solve(S_[4], nullptr, nullptr, 1);
-                asmb::launch(k_face_primal_finish, dim3(1), dim3(1024), h->stream, A, S_[4], S_[3], TOL_P, FACE_TOL_M, 1);
+                launch_face_primal_finish(S_[4], S_[3], TOL_P, FACE_TOL_M, 1);
                 as_read();
                 okp = h->h_asscal[AS_HARDRES] <= TOL_P && h->h_ascnt[AC_NVIOL] == 0;
             }
@@ -2500,7 +2585,7 @@ struct Solver {
         part_factor = false;
         if (okp && okd) {
             dcopy(A.y, d_yf, M); dcopy(A.z, d_zf, n);      // (p, s, act) are the primal stage's last solve; y, z come from the dual stage
-            asmb::launch(k_face_kkt, dim3(1), dim3(1024), h->stream, A, S_[5]);
+            launch_face_kkt(S_[5]);
             as_read();
             h->stats.kkt_pr = h->h_asscal[AS_PR];
             h->stats.kkt_du = h->h_asscal[AS_DU];
@@ -2710,16 +2795,15 @@ struct Solver {
             conv = true;
         }
         if (conv) {
-            asmb::launch(k_as_clip0, asmb::blocks(lp.n), dim3(256), h->stream, A.lb, A.ub, P.p, A.p, lp.n);
+            launch_as_clip0(P.p, A.p);
             dcopy(A.y, P.y, lp.M);
             if (lp.ns) {
-                asmb::launch(k_as_smax, asmb::blocks(lp.ns), dim3(256), h->stream, P.s, A.slo, A.s, lp.ns);
-                asmb::launch(k_as_sl_values, dim3((unsigned)((lp.M + 255) / 256 + 1)), dim3(256), h->stream,
-                             A);      // the tail kernel must not recompute slacks from a stale working set
+                launch_as_smax(P.s, A.s);
+                launch_as_sl_values();      // the tail kernel must not recompute slacks from a stale working set
             }
             dev.gemv_n_dev(h->d_Ah, A.p, A.t);
             dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
-            asmb::launch(k_as_finish, dim3(1), dim3(1024), h->stream, A, S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
+            launch_as_finish(S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
             as_read();
             final_sets = 3;
             h->stats.path = 10;
@@ -2942,8 +3026,9 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.alloc(h->h_seq, 16, BufPool::MAPPED, &h->d_hseq);
         *h->h_seq = 0;
         h->scal_seq = 0;
-        P.zeroed(h->d_as, 17 * h->ldn + 17 * h->Mp + 4 * h->nsp + 64, s);
-        P.zeroed(h->d_as_i, 6 * (h->Mp + h->ldn + h->nsp) + 3 * h->Mp + 2 * h->ldn + 64, s);
+        const AsLayout alay(h->ldn, h->Mp, h->nsp);
+        P.zeroed(h->d_as, alay.dbl_len(), s);
+        P.zeroed(h->d_as_i, alay.int_len(), s);
         P.alloc(h->h_ascnt, 64, BufPool::PINNED);
         P.alloc(h->h_asscal, 64, BufPool::PINNED);
         P.zeroed(h->d_Zbuf, (int64_t)(FACE_STEPS + 1) * h->ldn, s);
@@ -4529,6 +4614,190 @@ int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t
         HIPCHK(asmb::copy(rcnt_inout, dCnt, sizeof(unsigned), hipMemcpyDeviceToHost));
         std::memcpy(hscal_inout, hScal, SC_COUNT * sizeof(double));
         *hseq_inout = *hSeq;
+    });
+}
+
+// The active-set and optimal-face kernels (asm_as_kernels.hip.h), one launch per stage, through the launch-site members of Solver and on arenas
+// laid out by Solver::as_bind with the pitches of AsLayout - see include/asm_hip.h.  Every offset, set number, family / index pair and every
+// index the caller's lists hold is checked here against the buffers before anything is launched.
+int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double scale_q, int64_t* layout_out, double* dbl_inout, int64_t ndbl, int32_t* int_inout,
+                       int64_t nint, const double* Ah, int64_t ah_rows, const asm_as_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return guarded(h, [&] {
+        const int64_t LIM = (int64_t)1 << 24;
+        if (!layout_out || n < 1 || M < 0 || ns < 0 || n > LIM || M > LIM || ns > LIM || (ns > 0 && M == 0) || nstages < 0)
+            throw std::invalid_argument("asm_test_as_stages: bad size");
+        HIPCHK(hipSetDevice(h->device));
+        const AsLayout lay{IpmLayout(n, M, ns)};
+        const int64_t ln = lay.ldn, lm = lay.Mp, ls = lay.nsp;
+        Solver S(h);
+        S.lp.n = n; S.lp.M = M; S.lp.ns = ns; S.lp.scale_q = scale_q;
+        IpmPtrs& P = S.P;
+        P = IpmPtrs();
+        // the LP vectors and the interior-point iterate k_as_identify reads follow the solver's two arenas
+        auto place_lp = [&](double* d, int* iv) {
+            double* a = d + lay.dbl_len();
+            auto N = [&]() { double* r_ = a; a += ln; return r_; };
+            auto Mv = [&]() { double* r_ = a; a += lm; return r_; };
+            auto Sv = [&]() { double* r_ = a; a += ls; return r_; };
+            P.q = N(); P.lb = N(); P.ub = N(); P.r = Mv(); P.w = Sv(); P.slo = Sv(); P.scoef = Sv();
+            P.p = N(); P.tL = N(); P.tU = N(); P.muL = N(); P.muU = N(); P.g = Mv(); P.pi = Mv(); P.y = Mv(); P.ts = Sv(); P.mus = Sv(); P.s = Sv();
+            int* ia = iv + lay.int_len();
+            P.rtype = ia; P.rs0 = ia + lm; P.rs1 = ia + 2 * lm; P.srow = ia + 3 * lm;
+            P.n = n; P.M = M; P.ns = ns; P.scale_q = scale_q;
+            Solver::AsArena ar;
+            ar.base = d; ar.ibase = iv; ar.rperm = ia + 3 * lm + ls; ar.ln = ln; ar.lm = lm; ar.ls = ls;
+            S.as_bind(ar);
+        };
+        const int64_t dbl_total = lay.dbl_len() + 8 * ln + 4 * lm + 6 * ls, int_total = lay.int_len() + 4 * lm + ls;
+        // the layout, from the pointers as_bind sets on host blocks of the full lengths
+        std::vector<double> hostd((size_t)dbl_total);
+        std::vector<int> hosti((size_t)int_total);
+        double* const fd = hostd.data();
+        int* const fi = hosti.data();
+        place_lp(fd, fi);
+        {
+            auto off = [&](const double* v) { return (int64_t)(v - fd); };
+            auto ioff = [&](const int* v) { return (int64_t)(v - fi); };
+            const AsPtrs& A = S.A;
+            const double* vs[ASM_AS_NVEC] = {A.Fmask, A.p, A.z, A.pB, A.pF, A.cF, A.rd, A.tN, A.xfull, A.nu, A.Hmask, A.sl, A.y, A.act, A.t, A.bH, A.v, A.u, A.yH, A.yfull, A.uacc,
+                                             A.ax, A.s, S.d_pref, S.d_zero, S.d_p0, S.d_z0, S.d_pa, S.d_pf, S.d_zf, S.d_y0, S.d_act0, S.d_acta, S.d_actf, S.d_yf, S.d_s0, S.d_sa,
+                                             S.d_sf, P.q, P.lb, P.ub, P.r, P.w, P.slo, P.scoef, P.p, P.tL, P.tU, P.muL, P.muU, P.g, P.pi, P.y, P.ts, P.mus, P.s};
+            const int* is[ASM_AS_NIVEC] = {S.S_[0].rowst, S.S_[0].bst, S.S_[0].sst, S.S_[1].rowst, S.S_[1].bst, S.S_[1].sst, S.S_[2].rowst, S.S_[2].bst, S.S_[2].sst,
+                                           S.S_[3].rowst, S.S_[3].bst, S.S_[3].sst, S.S_[4].rowst, S.S_[4].bst, S.S_[4].sst, S.S_[5].rowst, S.S_[5].bst, S.S_[5].sst,
+                                           A.ksoft, A.Hidx, A.hpos, A.Fidx, A.fpos, P.rtype, P.rs0, P.rs1, P.srow, A.rperm};
+            const int64_t head[9] = {ln, lm, ls, dbl_total, int_total, off(A.scal), AS_COUNT, ioff(A.cnt), AC_COUNT};
+            for (int k = 0; k < 9; ++k) layout_out[k] = head[k];
+            for (int k = 0; k < ASM_AS_NVEC; ++k) layout_out[9 + k] = off(vs[k]);
+            for (int k = 0; k < ASM_AS_NIVEC; ++k) layout_out[9 + ASM_AS_NVEC + k] = ioff(is[k]);
+            if (head[5] + AS_COUNT > lay.dbl_len() || head[7] + AC_COUNT > lay.int_len()) throw std::logic_error("asm_test_as_stages: an arena is shorter than its layout");
+        }
+        if (!dbl_inout) return;      // layout query
+        if (!int_inout || (nstages > 0 && (!stages || !grid_out)) || ndbl < dbl_total || nint < int_total || ndbl > ((int64_t)1 << 31) || nint > ((int64_t)1 << 31))
+            throw std::invalid_argument("asm_test_as_stages: bad buffer");
+        const int32_t* iv = int_inout;
+        auto ioff = [&](const int* v) { return (int64_t)(v - fi); };
+        const int64_t o_rt = ioff(P.rtype), o_rs0 = ioff(P.rs0), o_rs1 = ioff(P.rs1), o_srow = ioff(P.srow), o_rperm = ioff(S.A.rperm), o_ksoft = ioff(S.A.ksoft),
+                      o_hidx = ioff(S.A.Hidx), o_hpos = ioff(S.A.hpos), o_cnt = ioff(S.A.cnt);
+        for (int64_t i = 0; i < M; ++i) {
+            const int rt = iv[o_rt + i], k0 = iv[o_rs0 + i], k1 = iv[o_rs1 + i], rp = iv[o_rperm + i];
+            if (rt < -1 || rt > 1 || k0 < -1 || k0 >= ns || k1 < -1 || k1 >= ns) throw std::invalid_argument("asm_test_as_stages: row type or slack index out of range");
+            if (rp < 0 || rp >= M) throw std::invalid_argument("asm_test_as_stages: row order out of range");
+        }
+        for (int64_t k = 0; k < ns; ++k)
+            if (iv[o_srow + k] < 0 || iv[o_srow + k] >= M) throw std::invalid_argument("asm_test_as_stages: slack row out of range");
+        auto dspan = [&](int64_t off, int64_t len, bool nullable = false) {
+            if (nullable && off == -1) return;
+            if (off < 0 || len < 0 || off + len > ndbl) throw std::invalid_argument("asm_test_as_stages: vector outside the double block");
+        };
+        auto setno = [&](const asm_as_stage& st, int cnt) {
+            for (int a = 0; a < cnt; ++a)
+                if (st.set[a] < 0 || st.set[a] > 5) throw std::invalid_argument("asm_test_as_stages: set number");
+        };
+        auto fam_e = [&](const asm_as_stage& st) {
+            const int64_t lim = st.fam == 0 ? M : (st.fam == 1 ? ns : n);
+            if (st.fam < 0 || st.fam > 3 || st.e < 0 || st.e >= lim) throw std::invalid_argument("asm_test_as_stages: family / index out of range");
+        };
+        // lists a kernel reads that an earlier k_as_setup (ksoft: or k_face_ns_step / k_as_sl_values) of the same call did not write are the caller's
+        bool own_lists = false, own_ksoft = false, need_ah = false;
+        auto lists_ok = [&](bool hidx, bool hpos) {
+            if (own_lists) return;
+            const int nH = iv[o_cnt + AC_NH];
+            if (nH < 0 || nH > M) throw std::invalid_argument("asm_test_as_stages: hard-row count out of range");
+            if (hidx) for (int64_t a = 0; a < nH; ++a)
+                if (iv[o_hidx + a] < 0 || iv[o_hidx + a] >= M) throw std::invalid_argument("asm_test_as_stages: hard-row list out of range");
+            if (hpos) for (int64_t i = 0; i < M; ++i)
+                if (iv[o_hpos + i] < -1 || iv[o_hpos + i] >= lm) throw std::invalid_argument("asm_test_as_stages: hard-row position out of range");
+        };
+        auto ksoft_ok = [&]() {
+            if (own_ksoft) return;
+            for (int64_t i = 0; i < M; ++i)
+                if (iv[o_ksoft + i] < -1 || iv[o_ksoft + i] >= ns) throw std::invalid_argument("asm_test_as_stages: basic-slack index out of range");
+        };
+        for (int64_t q = 0; q < nstages; ++q) {
+            const asm_as_stage& st = stages[q];
+            switch (st.kind) {
+            case ASM_AS_IDENTIFY: setno(st, 1); break;
+            case ASM_AS_CLIP0: dspan(st.x[0], n, true); dspan(st.x[1], n); break;
+            case ASM_AS_SL: break;
+            case ASM_AS_SL_VALUES: own_ksoft = true; break;
+            case ASM_AS_SMAX: dspan(st.x[0], ns); dspan(st.x[1], ns); break;
+            case ASM_AS_SETUP: setno(st, 1); dspan(st.x[0], n, true); own_lists = own_ksoft = true; break;
+            case ASM_AS_RHS: dspan(st.x[0], M, true); lists_ok(true, false); break;
+            case ASM_AS_RES_P: case ASM_AS_GATHER_H: case ASM_AS_ADD_YH:
+                if (st.k < 0 || st.k > M) throw std::invalid_argument("asm_test_as_stages: host count of hard rows");
+                lists_ok(true, false);
+                break;
+            case ASM_AS_SCATTER_H: dspan(st.x[0], lm); lists_ok(false, true); break;
+            case ASM_AS_ADD_F: case ASM_AS_RD: break;
+            case ASM_AS_MERGE: lists_ok(false, true); break;
+            case ASM_AS_FINISH: setno(st, 3); ksoft_ok(); break;
+            case ASM_FACE_PRIMAL_FINISH: setno(st, 2); ksoft_ok(); lists_ok(false, true); break;
+            case ASM_FACE_NS_COMBINE:
+                if (st.k < 0 || st.k > 4096) throw std::invalid_argument("asm_test_as_stages: member count");
+                dspan(st.x[0], n); dspan(st.x[1], (int64_t)st.k * ln); dspan(st.x[2], st.k); dspan(st.x[3], n);
+                break;
+            case ASM_FACE_NS_STEP: setno(st, 1); dspan(st.x[0], n); dspan(st.x[1], ns); dspan(st.x[2], M); own_ksoft = true; break;
+            case ASM_FACE_NS_COL:
+                fam_e(st); dspan(st.x[0], n); dspan(st.x[1], M);
+                if (!Ah || ah_rows < M) throw std::invalid_argument("asm_test_as_stages: the matrix has fewer rows than the LP");
+                need_ah = true;
+                break;
+            case ASM_FACE_NS_Z: dspan(st.x[0], n); break;
+            case ASM_FACE_NS_UNMARK: setno(st, 1); fam_e(st); break;
+            case ASM_FACE_DUAL_FINISH: setno(st, 1); lists_ok(false, true); break;
+            case ASM_FACE_KKT: setno(st, 1); break;
+            case ASM_AS_PACK: setno(st, 1); dspan(st.x[0], 2 * n + 2 * M + ns + (M + n + ns + 1) / 2); break;
+            case ASM_AS_COPY_SETS: setno(st, 2); break;
+            default: throw std::invalid_argument("asm_test_as_stages: unknown stage");
+            }
+        }
+        double *dD = nullptr, *dAh = nullptr;
+        int* dI = nullptr;
+        BufPool tmp;
+        tmp.upload(dD, dbl_inout, ndbl);
+        tmp.upload(dI, (const int*)int_inout, nint);
+        if (need_ah) tmp.upload(dAh, Ah, ah_rows * ln);
+        place_lp(dD, dI);
+        const int* const rperm = S.A.rperm;
+        auto X = [&](int64_t off) { return off < 0 ? nullptr : dD + off; };
+        for (int64_t q = 0; q < nstages; ++q) {      // one after the other on the handle's stream, no host synchronisation in between
+            const asm_as_stage& st = stages[q];
+            auto SS = [&](int v) -> const AsSets& { return S.S_[v < 0 || v > 5 ? 0 : v]; };      // (the numbers a stage uses were checked above)
+            const AsSets &s0 = SS(st.set[0]), &s1 = SS(st.set[1]), &s2 = SS(st.set[2]);
+            S.A.rperm = st.rperm ? rperm : nullptr;
+            unsigned g = 0;
+            switch (st.kind) {
+            case ASM_AS_IDENTIFY: g = S.launch_as_identify(s0); break;
+            case ASM_AS_CLIP0: g = S.launch_as_clip0(X(st.x[0]), X(st.x[1])); break;
+            case ASM_AS_SL: g = S.launch_as_sl(); break;
+            case ASM_AS_SL_VALUES: g = S.launch_as_sl_values(); break;
+            case ASM_AS_SMAX: g = S.launch_as_smax(X(st.x[0]), X(st.x[1])); break;
+            case ASM_AS_SETUP: g = S.launch_as_setup(s0, X(st.x[0])); break;
+            case ASM_AS_RHS: g = S.launch_as_rhs(X(st.x[0])); break;
+            case ASM_AS_RES_P: g = S.launch_as_res_p(st.k); break;
+            case ASM_AS_SCATTER_H: g = S.launch_as_scatter_h(X(st.x[0]), st.accumulate); break;
+            case ASM_AS_ADD_F: g = S.launch_as_add_f(); break;
+            case ASM_AS_RD: g = S.launch_as_rd(); break;
+            case ASM_AS_GATHER_H: g = S.launch_as_gather_h(st.k); break;
+            case ASM_AS_ADD_YH: g = S.launch_as_add_yh(st.k); break;
+            case ASM_AS_MERGE: g = S.launch_as_merge(st.with_y); break;
+            case ASM_AS_FINISH: g = S.launch_as_finish(s0, s1, s2, st.have_prev, st.tol_p, st.tol_d); break;
+            case ASM_FACE_PRIMAL_FINISH: g = S.launch_face_primal_finish(s0, s1, st.tol_p, st.tol_m, st.check_only); break;
+            case ASM_FACE_NS_COMBINE: g = S.launch_face_ns_combine(X(st.x[0]), X(st.x[1]), ln, X(st.x[2]), st.k, X(st.x[3])); break;
+            case ASM_FACE_NS_STEP: g = S.launch_face_ns_step(s0, X(st.x[0]), X(st.x[1]), X(st.x[2]), st.tol_p); break;
+            case ASM_FACE_NS_COL: g = S.launch_face_ns_col(dAh, ln, st.fam, st.e, X(st.x[0]), X(st.x[1])); break;
+            case ASM_FACE_NS_Z: g = S.launch_face_ns_z(X(st.x[0])); break;
+            case ASM_FACE_NS_UNMARK: g = S.launch_face_ns_unmark(s0, st.fam, st.e); break;
+            case ASM_FACE_DUAL_FINISH: g = S.launch_face_dual_finish(s0, st.tol_m); break;
+            case ASM_FACE_KKT: g = S.launch_face_kkt(s0); break;
+            case ASM_AS_PACK: g = S.launch_as_pack(s0, X(st.x[0])); break;
+            default: g = S.launch_as_copy_sets(s0, s1);
+            }
+            grid_out[q] = g;
+        }
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(int_inout, dI, nint * sizeof(int), hipMemcpyDeviceToHost));
     });
 }
 

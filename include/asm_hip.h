@@ -540,6 +540,75 @@ int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t
                         double* dbl_inout, int64_t ndbl, const int32_t* ints, int64_t nint, double* snap_inout, double* rpart_inout,
                         uint32_t* rcnt_inout, double* hscal_inout, uint32_t* hseq_inout, const asm_ipm_stage* stages, int64_t nstages,
                         uint32_t* grid_out);
+/* Test hook: the active-set and optimal-face kernels (asm_as_kernels.hip.h), one launch per stage with the solver's own launch geometry, on a
+ * state the caller supplies.  The state of an LP with n columns, M rows and ns slack columns (ns > 0 needs M > 0; M = 0 is admitted) lives in the
+ * two arenas the solver's own binding routine lays out with the pitches asm_sublp_setup chooses (ldn, Mp, nsp as for asm_test_ipm_stages),
+ * followed by the LP vectors and the part of the interior-point iterate that k_as_identify reads.  layout_out (ASM_AS_LAYOUT_LEN) receives:
+ * ldn, Mp, nsp, length of the double block, length of the int block, offset of the scalar block `scal`, its length (PR DU EQRES HARDRES),
+ * offset of the counter block `cnt` in the int block, its length (NH NF ANYSOFT NCHG NDIFF NVIOL NREL), then the offsets of the ASM_AS_NVEC
+ * double vectors in this order:
+ *   Fmask p z pB pF cF rd tN xfull nu | Hmask sl y act t bH v u yH yfull uacc ax | s |                                  (AsPtrs)
+ *   pref zero p0 z0 pa pf zf | y0 act0 acta actf yf | s0 sa sf |                          (anchors and scratch vectors of the solver)
+ *   q lb ub r w slo scoef | ip.p ip.tL ip.tU ip.muL ip.muU ip.g ip.pi ip.y ip.ts ip.mus ip.s          (LP, interior-point iterate)
+ * and of the ASM_AS_NIVEC int vectors: rowst bst sst of the six working sets 0 .. 5 | ksoft Hidx hpos Fidx fpos | rtype rs0 rs1 srow rperm
+ * (n-vectors have ldn, M-vectors Mp, slack vectors nsp entries).  With dbl_inout == NULL the call only reports the layout.
+ *   dbl_inout (ndbl >= double block length)  the double block, followed by any vectors of the caller's that stages name by offset (x[]);
+ *             loaded before the first stage, returned whole after the last.  Products with the LP matrix are inputs, not stages: the caller
+ *             fills t and tN.
+ *   int_inout (nint >= int block length)  the int block, in / out like the doubles: the kernels write sets and index lists.  rperm must hold
+ *             row numbers whether a stage uses it or not.
+ *   Ah        (ah_rows >= M rows of ldn doubles, row-major) the scaled LP matrix; read and uploaded only when a k_face_ns_col stage is present.
+ *   stages    run in order on the handle's stream with no host synchronisation in between; grid_out[q] = workgroups stage q launched.
+ * Checked before the first launch (ASM_ERR_ARG otherwise): every offset and length against the blocks, set numbers (0 .. 5), fam (0 .. 3) and e
+ * (below M, ns, n, n for the families row, slack, lower, upper), k, rtype (-1 .. 1), rs0 / rs1 (-1 .. ns - 1), srow and rperm (0 .. M - 1); for a
+ * stage that reads ksoft, Hidx, hpos or the count cnt[NH] before a stage of the same call has written them, the loaded values (ksoft -1 ..
+ * ns - 1, Hidx 0 .. M - 1 over cnt[NH] <= M entries, hpos -1 .. Mp - 1).  k_face_ns_step marks the index its own ratio test finds; when
+ * the test finds none although an inequality is violated (a ratio that is not a number) it marks nothing and reports NCHG = NDIFF = -1.
+ * x[] entries of -1 pass a null pointer where the kernel takes one (*). */
+enum {
+    ASM_AS_IDENTIFY = 0,      /* set[0] = S (out); reads the ip.* vectors */
+    ASM_AS_CLIP0,             /* src = x[0] (*), out = x[1]  (n each) */
+    ASM_AS_SL,
+    ASM_AS_SL_VALUES,
+    ASM_AS_SMAX,              /* src = x[0], dst = x[1]  (ns each) */
+    ASM_AS_SETUP,             /* set[0] = cur; p_ref = x[0] (*); rperm != 0: rows compacted in the order of rperm */
+    ASM_AS_RHS,               /* y_ref = x[0] (*) */
+    ASM_AS_RES_P,             /* k = the host's count of hard rows: sizes the grid */
+    ASM_AS_SCATTER_H,         /* src = x[0] (Mp entries); accumulate */
+    ASM_AS_ADD_F,
+    ASM_AS_RD,
+    ASM_AS_GATHER_H,          /* k as for RES_P */
+    ASM_AS_ADD_YH,            /* k as for RES_P */
+    ASM_AS_MERGE,             /* with_y */
+    ASM_AS_FINISH,            /* set[0] = cur, set[1] = nx, set[2] = prev; have_prev, tol_p, tol_d */
+    ASM_FACE_PRIMAL_FINISH,   /* set[0] = W, set[1] = part; tol_p, tol_m, check_only */
+    ASM_FACE_NS_COMBINE,      /* p0 = x[0] (n), Zbuf = x[1] (k rows of ldn), u = x[2] (k), p = x[3] (n); k <= 4096 */
+    ASM_FACE_NS_STEP,         /* set[0] = W; pa = x[0] (n), sa = x[1] (ns), acta = x[2] (M); tol_p */
+    ASM_FACE_NS_COL,          /* fam, e; p0 = x[0] (n), t0 = x[1] (M); the matrix Ah */
+    ASM_FACE_NS_Z,            /* z = x[0] (n) */
+    ASM_FACE_NS_UNMARK,       /* set[0] = W; fam, e */
+    ASM_FACE_DUAL_FINISH,     /* set[0] = D; tol_m */
+    ASM_FACE_KKT,             /* set[0] = D */
+    ASM_AS_PACK,              /* set[0] = S; dst = x[0]: 2n + 2M + ns doubles, then M + n + ns 32-bit integers */
+    ASM_AS_COPY_SETS,         /* set[0] = dst, set[1] = src */
+    ASM_AS_NKINDS
+};
+#define ASM_AS_NVEC 56
+#define ASM_AS_NIVEC 28
+#define ASM_AS_LAYOUT_LEN (9 + ASM_AS_NVEC + ASM_AS_NIVEC)
+typedef struct asm_as_stage {
+    int32_t kind;                 /* ASM_AS_* / ASM_FACE_* */
+    int32_t with_y, accumulate, check_only, have_prev, rperm;      /* (the mode of an equality-constrained solve reaches its kernels as with_y / accumulate) */
+    int32_t fam, k;
+    int32_t set[3];               /* numbers of the working-set buffers the stage uses */
+    int32_t pad_;
+    int64_t e;
+    double tol_p, tol_d, tol_m;
+    int64_t x[4];                 /* offsets into dbl_inout */
+} asm_as_stage;
+int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double scale_q, int64_t* layout_out, double* dbl_inout, int64_t ndbl,
+                       int32_t* int_inout, int64_t nint, const double* Ah, int64_t ah_rows, const asm_as_stage* stages, int64_t nstages,
+                       uint32_t* grid_out);
 int asm_test_cholesky(asm_handle* h, const double* S /* N*N sym */, int64_t N, double* L_out /* N*N lower */);
 int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x);
 /* the bounded wait of the dataflow panel kernel with a producer that never publishes: returns ASM_ERR_HIP (reported once), the

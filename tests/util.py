@@ -1144,3 +1144,999 @@ def ipm_helper_operands(case, st):
         op["col"] = rng.integers(0, n, nnz).astype(np.int32)
         op["ze"], op["dI"], op["vals"] = rng.standard_normal(nE), 10.0 ** rng.uniform(-3, 3, M - nE), rng.standard_normal(nnz)
     return op
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# Twins of the active-set and optimal-face kernels (asm_as_kernels.hip.h), written from the kernels' statement lists.  A state is a dict with
+# the sizes, scale_q, one float64 vector per name of AS_VECTORS and one int32 vector per name of AS_IVECTORS (true lengths), `cnt` (AC_*) and
+# `scal` (AS_*).  A twin returns (exact, bounded): `exact` maps a vector name / "cnt.X" / "scal.X" to what the kernel must leave there bit for
+# bit - whole vectors, so entries the kernel does not write carry their input; vectors longer than the true length state the padding the
+# kernel owns - and `bounded` maps a name to (value, magnitude, k) in long double as for the interior-point twins.  Decisions are taken in long
+# double from the inputs; as_cmp files each one as clear (at least 64 rounding bounds away from its threshold), tie (exactly on it) or between,
+# and counts the branch it took in the census.  A maximum of rounded terms is stated as (max of the values, max of the magnitudes, k): the
+# maximum is 1-Lipschitz, so the bound on the terms carries over.
+AS_KINDS = ("identify", "clip0", "sl", "sl_values", "smax", "setup", "rhs", "res_p", "scatter_h", "add_f", "rd", "gather_h", "add_yh", "merge", "finish",
+            "primal_finish", "ns_combine", "ns_step", "ns_col", "ns_z", "ns_unmark", "dual_finish", "kkt", "pack", "copy_sets")
+AS_VECTORS = ("Fmask p z pB pF cF rd tN xfull nu Hmask sl y act t bH v u yH yfull uacc ax s pref zero p0 z0 pa pf zf y0 act0 acta actf yf s0 sa sf "
+              "q lb ub r w slo scoef ip.p ip.tL ip.tU ip.muL ip.muU ip.g ip.pi ip.y ip.ts ip.mus ip.s").split()
+AS_IVECTORS = ["S%d.%s" % (k, nm) for k in range(6) for nm in ("rowst", "bst", "sst")] + "ksoft Hidx hpos Fidx fpos rtype rs0 rs1 srow rperm".split()
+AS_N = "Fmask p z pB pF cF rd tN xfull nu pref zero p0 z0 pa pf zf q lb ub ip.p ip.tL ip.tU ip.muL ip.muU S.bst Fidx fpos".split()
+AS_M = "Hmask sl y act t bH v u yH yfull uacc ax y0 act0 acta actf yf r ip.g ip.pi ip.y S.rowst ksoft Hidx hpos rtype rs0 rs1 rperm".split()
+AC = {nm: i for i, nm in enumerate("NH NF ANYSOFT NCHG NDIFF NVIOL NREL".split())}
+AS = {nm: i for i, nm in enumerate("PR DU EQRES HARDRES".split())}
+TOL_P, TOL_D, FACE_TOL_M = 1e-9, 1e-6, 1e-9
+ISENT = -77               # pre-fill of every int output
+# branches of every kernel's decision tree (the census must count each at least once over AS_CASES x seeds)
+AS_BRANCHES = {
+    "identify": "fixed lower upper both free slack_basic slack_bound row_eq row_active row_inactive row_forced_rs0 row_forced_rs1".split(),
+    "setup": "soft_rs0 soft_rs1 hard inactive active_soft free at_lower at_upper any_soft no_soft pref_null pref_given rperm_on rperm_off".split(),
+    "finish": ("row_soft row_eq row_drop row_add row_keep col_fixed col_release_lo col_release_up col_fix_lo col_fix_up col_keep slack_free slack_low "
+               "slack_keep row_reactivated have_prev no_prev").split(),
+    "primal_finish": ("grow release unchanged check_only viol_row viol_lo viol_up viol_slack grow_row grow_lo grow_up grow_slack rel_row rel_slack "
+                      "rel_lo rel_up rel_mandatory_kept row_reactivated").split(),
+    # (a ratio a / (a - g1) with g1 < 0 is below 1: the kernel's fmin(alpha, 1.0) never binds, so it is no branch of the census)
+    "ns_step": "feasible blocked fam_row fam_slack fam_lower fam_upper alpha_below_1 nonbasic_reset".split(),
+    "ns_col": "fam_row fam_slack fam_lower fam_upper".split(),
+    "ns_unmark": "fam_row fam_slack fam_lower fam_upper".split(),
+    "dual_finish": "col_lo col_up col_keep row_drop row_keep slack_basic slack_keep row_reactivated none".split(),
+    "kkt": "row_eq row_ge row_le row_inactive col_fixed col_lo col_up col_free slack_basic slack_bound".split(),
+    "clip0": "src_null src_given below above inside".split(),
+    "scatter_h": "hard other accumulate plain".split(),
+    "merge": "with_y without_y".split(),
+    "rhs": "soft no_soft yref_null yref_given free bound".split(),
+}
+
+
+def as_len(st, nm):
+    if nm.startswith("S") and "." in nm and nm[1].isdigit():
+        nm = "S." + nm.split(".")[1]
+    return st["n"] if nm in AS_N else (st["M"] if nm in AS_M else st["ns"])
+
+
+def as_new_census():
+    return {k: {b: 0 for b in v} for k, v in AS_BRANCHES.items()}
+
+
+class AsBook:
+    """Census of branches and classes of decisions of one or more twin runs."""
+
+    def __init__(self):
+        self.census = as_new_census()
+        self.cls = {"clear": 0, "tie": 0, "between": 0}
+
+    def hit(self, kernel, branch, cnt=1):
+        self.census[kernel][branch] += int(cnt)
+
+    def cmp(self, val, mag, k, op, thr, mask=None):
+        """val `op` thr, element by element in long double, filing each entry of `mask`."""
+        val, mag, thr = np.asarray(val, LD), np.asarray(mag, LD), np.asarray(thr, LD)
+        val, mag, thr = np.broadcast_arrays(val, mag, thr)
+        res = {"<": val < thr, "<=": val <= thr, ">": val > thr, ">=": val >= thr}[op]
+        m = np.ones(val.shape, bool) if mask is None else mask
+        tie = (val == thr) & m
+        near = (np.abs(val - thr) < 64 * gamma(k) * mag) & ~tie & m
+        self.cls["tie"] += int(tie.sum())
+        self.cls["between"] += int(near.sum())
+        self.cls["clear"] += int(m.sum() - tie.sum() - near.sum())
+        return res
+
+
+def as_slack_lists(M, srow):
+    return ipm_slack_lists(M, srow)
+
+
+def _near(rng, cnt, frac=0.35):
+    """Factors that put a decision quantity near its threshold: a third of the entries at 0.2 .. 5 thresholds of either sign, the rest far."""
+    c = np.where(rng.random(cnt) < 0.5, 1.0, -1.0) * rng.uniform(0.2, 5.0, cnt)
+    return np.where(rng.random(cnt) < frac, c, np.nan)
+
+
+def as_state(seed, n, M, ns, scale_q=4.0):
+    """A scrambled active-set state: LP vectors with fixed columns, all three row types, both signs of scoef, rows with two, one and no slack
+    column; an interior-point iterate; six working sets; work vectors of O(1) entries; index lists of a consistent earlier k_as_setup on set 0.
+    About a third of the quantities that a kernel compares with a tolerance sit at 0.2 .. 5 times that tolerance (through t, p, y, tN, uacc, nu),
+    the others at O(1).  Nothing is re-drawn: a factor of 0.2 .. 5 leaves a distance of at least 0.2 tolerances (2e-10), six orders above 64
+    rounding bounds of O(1) data, so no entry can land between the classes - which the tests assert on every state they use."""
+    rng = np.random.default_rng(seed)
+    assert n >= 1 and 0 <= ns <= 2 * M
+    st = {"n": n, "M": M, "ns": ns, "scale_q": scale_q}
+    st["rtype"] = rng.integers(-1, 2, M).astype(np.int32)
+    npair = max(ns - M, ns // 3) if ns >= 2 else 0
+    rows = rng.permutation(M)[:ns - npair]
+    st["srow"] = np.sort(np.concatenate([rows, rows[:npair]])).astype(np.int32)
+    st["rs0"], st["rs1"] = ipm_slack_lists(M, st["srow"])
+    st["rperm"] = rng.permutation(M).astype(np.int32)
+    for nm in AS_VECTORS:
+        st[nm] = np.round(rng.standard_normal(as_len(st, nm)) * 2.0 ** 20) / 2.0 ** 20
+    st["scoef"] = np.where(rng.random(ns) < 0.5, 1.0, -1.0) * rng.choice([0.5, 1.0, 2.0], ns)
+    st["lb"] = -rng.uniform(0.1, 3.0, n)
+    st["ub"] = rng.uniform(0.1, 3.0, n)
+    fx = rng.random(n) < 0.1
+    st["ub"][fx] = st["lb"][fx]
+    for a, b, cnt in (("ip.tL", "ip.muL", n), ("ip.tU", "ip.muU", n), ("ip.ts", "ip.mus", ns), ("ip.g", "ip.pi", M)):
+        st[a] = 10.0 ** rng.uniform(-6, 2, cnt)
+        st[b] = 1e-3 / st[a] * 10.0 ** rng.uniform(-1, 1, cnt)
+    for k in range(6):
+        st["S%d.rowst" % k] = rng.integers(0, 2, M).astype(np.int32)
+        st["S%d.bst" % k] = rng.integers(-1, 2, n).astype(np.int32)
+        st["S%d.sst" % k] = rng.integers(0, 2, ns).astype(np.int32)
+        st["S%d.rowst" % k][st["srow"][st["S%d.sst" % k] == 1]] = 1            # (a basic slack makes its row active: every set the solver holds)
+    st["cnt"] = np.full(len(AC), ISENT, np.int32)
+    st["scal"] = np.full(len(AS), SENTINEL)
+    for nm in "ksoft Hidx hpos Fidx fpos".split():
+        st[nm] = np.full(as_len(st, nm), ISENT, np.int32)
+    ex, _ = tw_as_setup(st, 0, None, 0, AsBook())                              # lists of set 0, natural order
+    for nm in "ksoft Hidx hpos Fidx fpos Fmask Hmask".split():
+        st[nm] = ex[nm][:as_len(st, nm)].copy()
+    st["cnt"][:3] = [ex["cnt.NH"], ex["cnt.NF"], ex["cnt.ANYSOFT"]]
+    # quantities near their tolerances
+    den = 1.0 + np.abs(st["r"])
+    c = _near(rng, M)
+    hit = ~np.isnan(c) & (st["ksoft"] < 0)
+    st["t"][hit] = (st["r"] - st["rtype"] * c * TOL_P * den - _as_sl(st))[hit]           # rt (r - act) / den = c tol_p
+    c = _near(rng, M)
+    hit = ~np.isnan(c)
+    st["y"][hit] = (c * TOL_D * scale_q)[hit]
+    st["uacc"][hit] = (c * FACE_TOL_M)[hit]
+    st["sl"] = _as_sl(st).astype(np.float64)
+    c = _near(rng, n)
+    hit = ~np.isnan(c)
+    st["tN"][hit] = (st["q"] - c * TOL_D * scale_q)[hit]                                  # z = c td
+    c = _near(rng, n)
+    lo = ~np.isnan(c) & (rng.random(n) < 0.5)
+    up = ~np.isnan(c) & ~lo
+    st["p"][lo] = (st["lb"] - c * TOL_P)[lo]
+    st["p"][up] = (st["ub"] + c * TOL_P)[up]
+    c = _near(rng, n)
+    hit = ~np.isnan(c)
+    st["nu"][hit] = (c * FACE_TOL_M)[hit]
+    st["pa"] = st["lb"] + (st["ub"] - st["lb"]) * rng.uniform(0.1, 0.9, n)                # a feasible anchor
+    st["sa"] = st["slo"] + rng.uniform(0.1, 2.0, ns)
+    st["acta"] = st["r"] + st["rtype"] * rng.uniform(0.1, 2.0, M)
+    return st
+
+
+def _as_sl(st):
+    a, _, _ = _slack_sum(st, st["slo"])
+    return a.astype(np.float64)                   # at most two terms: tw_as_sl states the bound
+
+
+def _sets(st, k):
+    return st["S%d.rowst" % k], st["S%d.bst" % k], st["S%d.sst" % k]
+
+
+def tw_as_identify(st, dst, bk):
+    sq = LD(st["scale_q"])
+    lb, ub, tL, tU, muL, muU, ts, mus, slo, g, pi, r = _l(st, "lb", "ub", "ip.tL", "ip.tU", "ip.muL", "ip.muU", "ip.ts", "ip.mus", "slo", "ip.g", "ip.pi", "r")
+    free = st["ub"] > st["lb"]
+    width = np.where(free, ub - lb, LD(1))
+    # a / b < c / d with b, d > 0: compared as a d - c b against 0 would change the rounding; the kernel divides, so the twin states both
+    # quotients (k = 3: width, quotient) and compares their difference with 0
+    lo = bk.cmp(tL / width - muL / sq, np.abs(tL / width) + np.abs(muL / sq), 4, "<", 0, free)
+    up = bk.cmp(tU / width - muU / sq, np.abs(tU / width) + np.abs(muU / sq), 4, "<", 0, free)
+    bst = np.where(free, np.where(up, 1, np.where(lo, -1, 0)), -1).astype(np.int32)
+    sd = 1 + np.abs(slo)
+    sst = bk.cmp(ts / sd - mus / sq, np.abs(ts / sd) + np.abs(mus / sq), 4, ">=", 0).astype(np.int32)
+    rd = 1 + np.abs(r)
+    ineq = st["rtype"] != 0
+    ra = bk.cmp(g / rd - pi / sq, np.abs(g / rd) + np.abs(pi / sq), 4, "<", 0, ineq)
+    rowst = np.where(ineq, ra, True)
+    f0 = np.zeros(st["M"], bool)
+    f1 = np.zeros(st["M"], bool)
+    if st["ns"]:
+        h0, h1 = st["rs0"] >= 0, st["rs1"] >= 0
+        f0[h0] = sst[st["rs0"][h0]] == 1
+        f1[h1] = sst[st["rs1"][h1]] == 1
+    for nm, c in (("fixed", (~free).sum()), ("lower", (free & lo & ~up).sum()), ("upper", (free & up & ~lo).sum()), ("both", (free & lo & up).sum()),
+                  ("free", (free & ~lo & ~up).sum()), ("slack_basic", sst.sum()), ("slack_bound", (sst == 0).sum()), ("row_eq", (~ineq).sum()),
+                  ("row_active", (ineq & ra).sum()), ("row_inactive", (ineq & ~ra & ~f0 & ~f1).sum()), ("row_forced_rs0", (~rowst & f0).sum()),
+                  ("row_forced_rs1", (~rowst & ~f0 & f1).sum())):
+        bk.hit("identify", nm, c)
+    rowst = (rowst | f0 | f1).astype(np.int32)
+    return {"S%d.rowst" % dst: rowst, "S%d.bst" % dst: bst, "S%d.sst" % dst: sst}, {}
+
+
+def tw_as_clip0(st, src, out, bk):
+    """src: name or None; out: name."""
+    s = np.zeros(st["n"]) if src is None else st[src]
+    bk.hit("clip0", "src_null" if src is None else "src_given")
+    bk.hit("clip0", "below", (s < st["lb"]).sum()); bk.hit("clip0", "above", (s > st["ub"]).sum()); bk.hit("clip0", "inside", ((s >= st["lb"]) & (s <= st["ub"])).sum())
+    return {out: np.minimum(np.maximum(s, st["lb"]), st["ub"])}, {}
+
+
+def tw_as_sl(st, values=False):
+    a, m, c = _slack_sum(st, st["s"] if values else st["slo"])
+    ex = {"ksoft": np.full(st["M"], -1, np.int32)} if values else {}
+    return ex, {"sl": (a, m, c + 1)}
+
+
+def tw_as_smax(st, src, dst):
+    return {dst: np.maximum(st[src], st["slo"])}, {}
+
+
+def tw_as_setup(st, cur, p_ref, use_rperm, bk, ldn=None, ldT=None):
+    n, M, ns = st["n"], st["M"], st["ns"]
+    rowst, bst, sst = _sets(st, cur)
+    ldn = n if ldn is None else ldn
+    ldT = M if ldT is None else ldT
+    ks = np.full(M, -1, np.int32)
+    if ns:
+        h0, h1 = st["rs0"] >= 0, st["rs1"] >= 0
+        b0 = np.zeros(M, bool); b1 = np.zeros(M, bool)
+        b0[h0] = sst[st["rs0"][h0]] == 1
+        b1[h1] = sst[st["rs1"][h1]] == 1
+        ks = np.where(b0, st["rs0"], np.where(b1, st["rs1"], -1)).astype(np.int32)
+        bk.hit("setup", "soft_rs0", b0.sum()); bk.hit("setup", "soft_rs1", (~b0 & b1).sum())
+    soft = ks >= 0
+    y = np.where(soft, st["w"][np.maximum(ks, 0)] * st["scoef"][np.maximum(ks, 0)], 0.0) if ns else np.zeros(M)
+    hard = (rowst == 1) & ~soft
+    order = st["rperm"].astype(np.int64) if use_rperm else np.arange(M)
+    Hidx = st["Hidx"].copy()
+    hl = order[hard[order]]
+    Hidx[:len(hl)] = hl
+    hpos = np.full(M, -1, np.int32)
+    hpos[hl] = np.arange(len(hl))
+    Hmask = np.zeros(ldT)
+    Hmask[:M] = hard
+    fr = bst == 0
+    Fidx = st["Fidx"].copy()
+    fl = np.nonzero(fr)[0]
+    Fidx[:len(fl)] = fl
+    fpos = np.full(n, -1, np.int32)
+    fpos[fl] = np.arange(len(fl))
+    ref = np.zeros(n) if p_ref is None else st[p_ref]
+    pj = np.where(bst < 0, st["lb"], np.where(bst > 0, st["ub"], ref))
+    pad = lambda v: np.concatenate([v, np.zeros(ldn - n)])
+    for nm, c in (("hard", hard.sum()), ("inactive", ((rowst != 1) & ~soft).sum()), ("active_soft", soft.sum()), ("free", fr.sum()), ("at_lower", (bst < 0).sum()),
+                  ("at_upper", (bst > 0).sum()), ("any_soft", soft.any()), ("no_soft", not soft.any()), ("pref_null", p_ref is None), ("pref_given", p_ref is not None),
+                  ("rperm_on", bool(use_rperm)), ("rperm_off", not use_rperm)):
+        bk.hit("setup", nm, c)
+    ex = {"ksoft": ks, "y": y, "Hmask": Hmask, "hpos": hpos, "Hidx": Hidx, "Fmask": pad(fr.astype(np.float64)), "p": pad(pj), "pB": pad(np.where(fr, 0.0, pj)),
+          "pF": pad(np.where(fr, ref, 0.0)), "fpos": fpos, "Fidx": Fidx, "s": st["slo"].copy(), "cnt.NH": len(hl), "cnt.NF": len(fl), "cnt.ANYSOFT": int(soft.any())}
+    return ex, {}
+
+
+def tw_as_rhs(st, y_ref, bk):
+    n, nH = st["n"], int(st["cnt"][AC["NH"]])
+    soft = st["cnt"][AC["ANYSOFT"]] != 0
+    H = st["Hidx"][:nH]
+    r, t, sl, q, tN = _l(st, "r", "t", "sl", "q", "tN")
+    bH = st["bH"].astype(LD); mg = np.zeros(st["M"], LD)
+    bH[:nH] = r[H] - t[H] - sl[H]
+    mg[:nH] = np.abs(r[H]) + np.abs(t[H]) + np.abs(sl[H])
+    yH = st["yH"].copy(); yH[:nH] = 0.0 if y_ref is None else st[y_ref][H]
+    ua = st["uacc"].copy(); ua[:nH] = 0.0
+    fm = st["Fmask"] != 0.0
+    cF = np.where(fm, st["q"] - (st["tN"] if soft else 0.0), 0.0)                 # one subtraction: exact in float64
+    bk.hit("rhs", "soft" if soft else "no_soft"); bk.hit("rhs", "yref_null" if y_ref is None else "yref_given"); bk.hit("rhs", "free", fm.sum()); bk.hit("rhs", "bound", (~fm).sum())
+    own = np.zeros(st["M"], bool); own[:nH] = True
+    return {"yH": yH, "uacc": ua, "cF": cF}, {"bH": (bH, mg, 3, own)}
+
+
+def tw_as_res_p(st):
+    nH = int(st["cnt"][AC["NH"]])
+    v = st["v"].copy(); v[:nH] = st["bH"][:nH] - st["t"][st["Hidx"][:nH]]
+    return {"v": v}, {}
+
+
+def tw_as_gather_h(st):
+    nH = int(st["cnt"][AC["NH"]])
+    v = st["v"].copy(); v[:nH] = st["t"][st["Hidx"][:nH]]
+    return {"v": v}, {}
+
+
+def tw_as_add_yh(st):
+    nH = int(st["cnt"][AC["NH"]])
+    yH = st["yH"].copy(); yH[:nH] = yH[:nH] + st["u"][:nH]
+    return {"yH": yH}, {}
+
+
+def tw_as_scatter_h(st, src, accumulate, bk):
+    pos = st["hpos"]; hd = pos >= 0
+    yf = np.where(hd, st[src][np.maximum(pos, 0)], 0.0)
+    ex = {"yfull": yf}
+    if accumulate:
+        ua = st["uacc"].copy(); ua[pos[hd]] = ua[pos[hd]] + st[src][pos[hd]]
+        ex["uacc"] = ua
+    bk.hit("scatter_h", "hard", hd.sum()); bk.hit("scatter_h", "other", (~hd).sum()); bk.hit("scatter_h", "accumulate" if accumulate else "plain")
+    return ex, {}
+
+
+def tw_as_add_f(st):
+    pF, Fm, tN = _l(st, "pF", "Fmask", "tN")
+    return {}, {"pF": (pF + Fm * tN, np.abs(pF) + np.abs(Fm * tN), 3)}
+
+
+def tw_as_rd(st):
+    return {"rd": st["Fmask"] * (st["cF"] - st["tN"])}, {}                         # difference, then a product with 0 / 1: no a*b +/- c shape
+
+
+def tw_as_merge(st, with_y, bk):
+    ex = {"p": np.where(st["Fmask"] != 0.0, st["pF"], st["p"])}
+    if with_y:
+        pos = st["hpos"]
+        ex["y"] = np.where(pos >= 0, st["yH"][np.maximum(pos, 0)], st["y"])
+    bk.hit("merge", "with_y" if with_y else "without_y")
+    return ex, {}
+
+
+def _as_rows(st, ks):
+    """Basic slack values and activities of the tail kernels: (snew, its magnitude, act, its magnitude), long double, from t, sl, ksoft."""
+    r, t, sl, slo, scoef = _l(st, "r", "t", "sl", "slo", "scoef")
+    a0 = t + sl
+    m0 = np.abs(t) + np.abs(sl)
+    soft = ks >= 0
+    k = np.maximum(ks, 0)
+    if st["ns"] == 0:
+        return soft, k, np.zeros(0, LD), np.zeros(0, LD), a0, m0
+    snew = slo[k] + (r - a0) / scoef[k]
+    ms = np.abs(slo[k]) + (np.abs(r) + m0) / np.abs(scoef[k])
+    act = np.where(soft, a0 + scoef[k] * (snew - slo[k]), a0)
+    ma = np.where(soft, m0 + np.abs(scoef[k]) * (ms + np.abs(slo[k])), m0)
+    return soft, k, snew, ms, act, ma
+
+
+def tw_as_finish(st, cur, nx, prev, have_prev, tol_p, tol_d, bk):
+    n, M, ns = st["n"], st["M"], st["ns"]
+    rowst, bst, sst = _sets(st, cur)
+    td = LD(tol_d) * LD(st["scale_q"])
+    r, y, q, tN, p, lb, ub, w, slo, scoef = _l(st, "r", "y", "q", "tN", "p", "lb", "ub", "w", "slo", "scoef")
+    soft, k, snew, ms, act, ma = _as_rows(st, st["ksoft"])
+    s = st["s"].astype(LD); smag = np.abs(s)
+    sown = np.zeros(ns, bool)
+    if ns:
+        s[k[soft]] = snew[soft]; smag[k[soft]] = ms[soft]; sown[k[soft]] = True
+    rt = st["rtype"].astype(LD); ineq = st["rtype"] != 0
+    den = 1 + np.abs(r)
+    viol = np.where(ineq, np.maximum(0, rt * (r - act)), np.abs(act - r)) / den
+    pr_v, pr_m = [viol], [(ma + np.abs(r)) / den]
+    dr = np.where(rowst == 0, np.abs(y), np.where(st["rtype"] == 1, np.maximum(-y, 0), np.where(st["rtype"] == -1, np.maximum(y, 0), 0)))
+    du_v, du_m = [dr], [np.abs(dr)]
+    drop = bk.cmp(rt * y, np.abs(y), 1, "<", -td, ineq & (rowst == 1)) & ineq & (rowst == 1)
+    add = bk.cmp(rt * (r - act) / den, (ma + np.abs(r)) / den, 9, ">", tol_p, ineq & (rowst == 0)) & ineq & (rowst == 0)
+    nrow = np.where(drop, 0, np.where(add, 1, rowst)).astype(np.int32)
+    z = st["q"] - st["tN"]
+    zl = z.astype(LD)
+    fixed = st["ub"] <= st["lb"]
+    pr_v += [np.maximum(lb - p, 0), np.maximum(p - ub, 0)]; pr_m += [np.abs(lb) + np.abs(p), np.abs(p) + np.abs(ub)]
+    dz = np.where(fixed, 0, np.where(bst < 0, np.maximum(-zl, 0), np.where(bst > 0, np.maximum(zl, 0), np.abs(zl))))
+    du_v.append(dz); du_m.append(dz)
+    rl = bk.cmp(zl, np.abs(zl), 1, "<", -td, ~fixed & (bst < 0)) & ~fixed & (bst < 0)
+    ru = bk.cmp(zl, np.abs(zl), 1, ">", td, ~fixed & (bst > 0)) & ~fixed & (bst > 0)
+    fl = bk.cmp(p - (lb - LD(tol_p)), np.abs(p) + np.abs(lb) + tol_p, 3, "<", 0, bst == 0) & (bst == 0)
+    fu = bk.cmp(p - (ub + LD(tol_p)), np.abs(p) + np.abs(ub) + tol_p, 3, ">", 0, (bst == 0) & ~fl) & (bst == 0) & ~fl
+    nb = np.where(rl | ru, 0, np.where(fl, -1, np.where(fu, 1, bst))).astype(np.int32)
+    bnd = {}
+    if ns:
+        sd = 1 + np.abs(slo)
+        pr_v.append(np.maximum(slo - s, 0) / sd); pr_m.append((np.abs(slo) + smag) / sd)
+        zs = w - scoef * y[st["srow"]]
+        zm = np.abs(w) + np.abs(scoef * y[st["srow"]])
+        du_v.append(np.where(sst == 0, np.maximum(-zs, 0), np.abs(zs))); du_m.append(zm)
+        sf = bk.cmp(zs, zm, 3, "<", -td, sst == 0) & (sst == 0)
+        thr = slo - LD(tol_p) * sd
+        sl_ = bk.cmp(s - thr, smag + np.abs(slo) + tol_p * sd, 9, "<", 0, sst == 1) & (sst == 1)
+        nss = np.where(sf, 1, np.where(sl_, 0, sst)).astype(np.int32)
+        re = np.zeros(M, bool); re[st["srow"][nss == 1]] = True
+        bk.hit("finish", "row_reactivated", (re & (nrow == 0)).sum())
+        nrow = np.where(re, 1, nrow).astype(np.int32)
+        bk.hit("finish", "slack_free", sf.sum()); bk.hit("finish", "slack_low", sl_.sum()); bk.hit("finish", "slack_keep", (~sf & ~sl_).sum())
+        bnd["s"] = (s, smag, 5, sown)
+    else:
+        sf = sl_ = np.zeros(0, bool); nss = sst.copy()
+    nchg = int(drop.sum() + add.sum() + rl.sum() + ru.sum() + fl.sum() + fu.sum() + sf.sum() + sl_.sum())
+    for nm, c in (("row_soft", soft.sum()), ("row_eq", (~ineq).sum()), ("row_drop", drop.sum()), ("row_add", add.sum()), ("row_keep", (ineq & ~drop & ~add).sum()),
+                  ("col_fixed", fixed.sum()), ("col_release_lo", rl.sum()), ("col_release_up", ru.sum()), ("col_fix_lo", fl.sum()), ("col_fix_up", fu.sum()),
+                  ("col_keep", (~rl & ~ru & ~fl & ~fu).sum()), ("have_prev", bool(have_prev)), ("no_prev", not have_prev)):
+        bk.hit("finish", nm, c)
+    ex = {"z": z, "S%d.rowst" % nx: nrow, "S%d.bst" % nx: nb, "S%d.sst" % nx: nss, "cnt.NCHG": nchg}
+    if have_prev:
+        pr_, pb, ps = _sets(st, prev)
+        ex["cnt.NDIFF"] = int((nrow != pr_).sum() + (nb != pb).sum() + (nss != ps).sum())
+    else:
+        ex["cnt.NDIFF"] = -1
+    cat = lambda vs: np.concatenate([np.atleast_1d(np.asarray(v, LD)) for v in vs] + [np.zeros(1, LD)])
+    bnd["act"] = (act, ma, 5)
+    bnd["scal.PR"] = (cat(pr_v).max(), cat(pr_m).max(), 9)
+    bnd["scal.DU"] = (cat(du_v).max() / LD(st["scale_q"]), cat(du_m).max() / LD(st["scale_q"]), 4)
+    return ex, bnd
+
+
+def tw_face_dual_finish(st, D, tol_m, bk):
+    rowst, bst, sst = (a.copy() for a in _sets(st, D))
+    td = LD(tol_m) * LD(st["scale_q"])
+    z = st["q"] - st["tN"]
+    zl = z.astype(LD)
+    y, w, scoef = _l(st, "y", "w", "scoef")
+    free = st["ub"] > st["lb"]
+    cl = bk.cmp(zl, np.abs(zl), 1, "<", -td, free & (bst < 0)) & free & (bst < 0)
+    cu = bk.cmp(zl, np.abs(zl), 1, ">", td, free & (bst > 0)) & free & (bst > 0)
+    bst[cl | cu] = 0
+    rt = st["rtype"].astype(LD)
+    m = (st["hpos"] >= 0) & (st["rtype"] != 0)
+    rd = bk.cmp(rt * y, np.abs(y), 1, "<", -td, m) & m
+    rowst[rd] = 0
+    nv = int(cl.sum() + cu.sum() + rd.sum())
+    if st["ns"]:
+        zs = w - scoef * y[st["srow"]]
+        sb = bk.cmp(zs, np.abs(w) + np.abs(scoef * y[st["srow"]]), 3, "<", -td, sst == 0) & (sst == 0)
+        sst[sb] = 1
+        re = np.zeros(st["M"], bool); re[st["srow"][sst == 1]] = True
+        bk.hit("dual_finish", "row_reactivated", (re & (rowst == 0)).sum())
+        rowst[re] = 1
+        nv += int(sb.sum())
+        bk.hit("dual_finish", "slack_basic", sb.sum()); bk.hit("dual_finish", "slack_keep", (~sb).sum())
+    for nm, c in (("col_lo", cl.sum()), ("col_up", cu.sum()), ("col_keep", (~cl & ~cu).sum()), ("row_drop", rd.sum()), ("row_keep", (~rd).sum()), ("none", nv == 0)):
+        bk.hit("dual_finish", nm, c)
+    return {"z": z, "S%d.rowst" % D: rowst, "S%d.bst" % D: bst, "S%d.sst" % D: sst, "cnt.NVIOL": nv}, {}
+
+
+def tw_face_kkt(st, D, bk):
+    rowst, bst, sst = _sets(st, D)
+    rt = st["rtype"]
+    a, r, y, p, z = st["act"], st["r"], st["y"], st["p"], st["z"]
+    viol = np.where(rt == 0, np.abs(a - r), np.maximum(0.0, rt * (r - a))) / (1.0 + np.abs(r))
+    pr = max(viol.max(initial=0.0), np.maximum(st["lb"] - p, 0.0).max(initial=0.0), np.maximum(p - st["ub"], 0.0).max(initial=0.0))
+    dr = np.where(rowst == 0, np.abs(y), np.where(rt == 1, np.maximum(-y, 0.0), np.where(rt == -1, np.maximum(y, 0.0), 0.0)))
+    fixed = st["ub"] <= st["lb"]
+    dz = np.where(fixed, 0.0, np.where(bst < 0, np.maximum(-z, 0.0), np.where(bst > 0, np.maximum(z, 0.0), np.abs(z))))
+    du_v = [dr.astype(LD), dz.astype(LD), np.zeros(1, LD)]; du_m = list(du_v)
+    if st["ns"]:
+        pr = max(pr, (np.maximum(st["slo"] - st["s"], 0.0) / (1.0 + np.abs(st["slo"]))).max(initial=0.0))
+        w, scoef, yl = _l(st, "w", "scoef", "y")
+        zs = w - scoef * yl[st["srow"]]
+        du_v.append(np.where(sst == 0, np.maximum(-zs, 0), np.abs(zs))); du_m.append(np.abs(w) + np.abs(scoef * yl[st["srow"]]))
+        bk.hit("kkt", "slack_basic", (sst == 1).sum()); bk.hit("kkt", "slack_bound", (sst == 0).sum())
+    for nm, c in (("row_eq", (rt == 0).sum()), ("row_ge", ((rt == 1) & (rowst != 0)).sum()), ("row_le", ((rt == -1) & (rowst != 0)).sum()), ("row_inactive", (rowst == 0).sum()),
+                  ("col_fixed", fixed.sum()), ("col_lo", (~fixed & (bst < 0)).sum()), ("col_up", (~fixed & (bst > 0)).sum()), ("col_free", (~fixed & (bst == 0)).sum())):
+        bk.hit("kkt", nm, c)
+    sq = LD(st["scale_q"])
+    return {"scal.PR": pr}, {"scal.DU": (np.concatenate(du_v).max() / sq, np.concatenate(du_m).max() / sq, 4)}
+
+
+def tw_as_pack(st, S):
+    n, M, ns = st["n"], st["M"], st["ns"]
+    rowst, bst, sst = _sets(st, S)
+    d = np.concatenate([st["p"], st["z"], st["y"], st["act"], st["s"]])
+    i = np.concatenate([rowst, bst, sst]).astype(np.int32)
+    return d, i
+
+
+def tw_as_copy_sets(st, dst, src):
+    return {"S%d.%s" % (dst, nm): st["S%d.%s" % (src, nm)].copy() for nm in ("rowst", "bst", "sst")}, {}
+
+
+def tw_face_ns_combine(p0, Z, u):
+    """p = p0 + sum_c u_c z_c: (value, magnitude, k) with k = 2 terms + 1."""
+    p0, Z, u = np.asarray(p0, LD), np.asarray(Z, LD), np.asarray(u, LD)
+    val = p0 + (u[:, None] * Z).sum(axis=0) if len(u) else p0.copy()
+    mag = np.abs(p0) + (np.abs(u[:, None] * Z)).sum(axis=0) if len(u) else np.abs(p0)
+    return val, mag, 2 * len(u) + 1
+
+
+def tw_face_ns_z(st):
+    rd, Fm, tN = _l(st, "rd", "Fmask", "tN")
+    return {}, {"z": (rd - Fm * tN, np.abs(rd) + np.abs(Fm * tN), 3)}
+
+
+def tw_face_ns_unmark(st, W, fam, e, bk):
+    rowst, bst, sst = (a.copy() for a in _sets(st, W))
+    if fam == 0:
+        rowst[e] = 0
+    elif fam == 1:
+        sst[e] = 1; rowst[st["srow"][e]] = 1
+    else:
+        bst[e] = 0
+    bk.hit("ns_unmark", ("fam_row", "fam_slack", "fam_lower", "fam_upper")[fam])
+    return {"S%d.rowst" % W: rowst, "S%d.bst" % W: bst, "S%d.sst" % W: sst}, {}
+
+
+def as_col_row(st, fam, e):
+    """The row of the matrix k_face_ns_col reads for (fam, e), -1 for a bound."""
+    return e if fam == 0 else (int(st["srow"][e]) if fam == 1 else -1)
+
+
+def tw_face_ns_col(st, arow, fam, e, p0, t0, bk):
+    """arow: the row as_col_row names (n entries; unused for a bound)."""
+    n = st["n"]
+    row = as_col_row(st, fam, e)
+    if row >= 0:
+        c = st["Fmask"] * arow[:n]
+        g = (LD(st["r"][row]) - LD(st["sl"][row]) - LD(st[t0][row]), abs(LD(st["r"][row])) + abs(LD(st["sl"][row])) + abs(LD(st[t0][row])), 3)
+    else:
+        c = np.zeros(n); c[e] = 1.0
+        b = st["lb"][e] if fam == 2 else st["ub"][e]
+        g = (LD(b) - LD(st[p0][e]), abs(LD(b)) + abs(LD(st[p0][e])), 2)
+    cl = c.astype(LD)
+    bk.hit("ns_col", ("fam_row", "fam_slack", "fam_lower", "fam_upper")[fam])
+    return {"rd": c}, {"scal.EQRES": g, "scal.PR": ((cl * cl).sum(), (cl * cl).sum(), 2 * n + 1)}
+
+
+def as_step_candidates(st, W, act, s, tol_p):
+    """Eligible entries of the ratio test of k_face_ns_step in float64, as the kernel states them, from the activities `act` and slack values `s`
+    (the device's, or the twin's): per family (0 row, 1 slack, 2 lower, 3 upper) the index list and the ratios."""
+    rowst, bst, sst = _sets(st, W)
+    rt = st["rtype"]
+    den = 1.0 + np.abs(st["r"])
+
+    def ratio(g0, g1):
+        a = np.maximum(g0, 0.0)
+        return a / (a - g1)
+    out = []
+    with np.errstate(all="ignore"):
+        g1 = rt * (act - st["r"]) / den
+        m = (rt != 0) & (rowst == 0) & (g1 < -tol_p)
+        out.append((np.nonzero(m)[0], ratio(rt * (st["acta"] - st["r"]) / den, g1)[m]))
+        sd = 1.0 + np.abs(st["slo"])
+        g1 = (s - st["slo"]) / sd
+        m = (sst == 1) & (g1 < -tol_p)
+        out.append((np.nonzero(m)[0], ratio((st["sa"] - st["slo"]) / sd, g1)[m]))
+        g1 = st["p"] - st["lb"]
+        m = (bst == 0) & (g1 < -tol_p)
+        out.append((np.nonzero(m)[0], ratio(st["pa"] - st["lb"], g1)[m]))
+        g1 = st["ub"] - st["p"]
+        m = (bst == 0) & (g1 < -tol_p)
+        out.append((np.nonzero(m)[0], ratio(st["ub"] - st["pa"], g1)[m]))
+    return out
+
+
+def tw_face_ns_step(st, W, tol_p, bk, dev=None):
+    """k_face_ns_step.  The ratios are quotients of differences - no a*b +/- c shape - so, given the activities and slack values (dev = the
+    device's (act, s); default: float64 evaluation of the twin's own), the ratio test is a float64-exact statement: nviol, the step, family and
+    index (ties: family order, lowest index).  The anchor update pa + al (p - pa) is bounded (k = 4)."""
+    n, M, ns = st["n"], st["M"], st["ns"]
+    rowst, bst, sst = (a.copy() for a in _sets(st, W))
+    ks = np.full(M, -1, np.int32)
+    if ns:
+        h0, h1 = st["rs0"] >= 0, st["rs1"] >= 0
+        b0 = np.zeros(M, bool); b1 = np.zeros(M, bool)
+        b0[h0] = sst[st["rs0"][h0]] == 1
+        b1[h1] = sst[st["rs1"][h1]] == 1
+        ks = np.where(b0, st["rs0"], np.where(b1, st["rs1"], -1)).astype(np.int32)
+    soft, k, snew, ms, act, ma = _as_rows(st, ks)
+    s = st["s"].astype(LD); smag = np.abs(s); sown = np.zeros(ns, bool)
+    if ns:
+        s[k[soft]] = snew[soft]; smag[k[soft]] = ms[soft]; sown[k[soft]] = True
+        s = np.where(sst == 1, s, st["slo"].astype(LD))                       # A.s of the non-basic slacks: reset to slo
+        smag = np.where(sst == 1, smag, np.abs(st["slo"]).astype(LD))
+        sown |= sst != 1
+        bk.hit("ns_step", "nonbasic_reset", (sst != 1).sum())
+    a64, s64 = (act.astype(np.float64), s.astype(np.float64)) if dev is None else dev
+    cand = as_step_candidates(st, W, a64, s64, tol_p)
+    nviol = sum(len(i) for i, _ in cand)
+    hard = (rowst == 1) & ~soft
+    hres = (np.abs(a64 - st["r"]) / (1.0 + np.abs(st["r"])))[hard].max(initial=0.0)
+    ex = {"ksoft": ks, "cnt.NVIOL": nviol, "scal.HARDRES": hres}
+    bnd = {"act": (act, ma, 5), "s": (s, smag, 5, sown)}
+    info = {"nviol": nviol}
+    if nviol == 0:
+        bk.hit("ns_step", "feasible")
+        return ex, bnd, info
+    alpha = min(float(r_.min()) for i, r_ in cand if len(i))
+    fam = min(f for f, (i, r_) in enumerate(cand) if len(i) and r_.min() == alpha)
+    e = int(cand[fam][0][cand[fam][1] == alpha].min())
+    al = min(alpha, 1.0)
+    if fam == 0:
+        rowst[e] = 1
+    elif fam == 1:
+        sst[e] = 0
+    else:
+        bst[e] = -1 if fam == 2 else 1
+    bk.hit("ns_step", "blocked"); bk.hit("ns_step", ("fam_row", "fam_slack", "fam_lower", "fam_upper")[fam]); bk.hit("ns_step", "alpha_below_1")
+    ex.update({"S%d.rowst" % W: rowst, "S%d.bst" % W: bst, "S%d.sst" % W: sst, "cnt.NCHG": fam, "cnt.NDIFF": e})
+    all_ = LD(al)
+    for anc, cur_ in (("acta", a64), ("pa", st["p"]), ("sa", s64)):
+        x, c = st[anc].astype(LD), np.asarray(cur_, LD)
+        bnd[anc] = (x + all_ * (c - x), np.abs(x) + np.abs(all_) * (np.abs(c) + np.abs(x)), 4)
+    info.update({"alpha": alpha, "fam": fam, "e": e, "cand": cand})
+    return ex, bnd, info
+
+
+def tw_face_primal_finish(st, W, part, tol_p, tol_m, check_only, bk):
+    n, M, ns = st["n"], st["M"], st["ns"]
+    rowst, bst, sst = (a.copy() for a in _sets(st, W))
+    prow, pb, ps = _sets(st, part)
+    r, p, lb, ub, slo, scoef, tN, uacc = _l(st, "r", "p", "lb", "ub", "slo", "scoef", "tN", "uacc")
+    soft, k, snew, ms, act, ma = _as_rows(st, st["ksoft"])
+    s = st["s"].astype(LD); smag = np.abs(s); sown = np.zeros(ns, bool)
+    if ns:
+        s[k[soft]] = snew[soft]; smag[k[soft]] = ms[soft]; sown[k[soft]] = True
+    rt = st["rtype"].astype(LD); ineq = st["rtype"] != 0
+    den = 1 + np.abs(r)
+    m = ineq & (rowst == 0)
+    vr = bk.cmp(rt * (r - act) / den, (ma + np.abs(r)) / den, 9, ">", tol_p, m) & m
+    hd = st["hpos"] >= 0
+    hres_v = (np.abs(act - r) / den)[hd]; hres_m = ((ma + np.abs(r)) / den)[hd]
+    fb = bst == 0
+    vl = bk.cmp(p - (lb - LD(tol_p)), np.abs(p) + np.abs(lb) + tol_p, 3, "<", 0, fb) & fb
+    vu = bk.cmp(p - (ub + LD(tol_p)), np.abs(p) + np.abs(ub) + tol_p, 3, ">", 0, fb) & fb
+    if ns:
+        sd = 1 + np.abs(slo)
+        vs = bk.cmp(s - (slo - LD(tol_p) * sd), smag + np.abs(slo) + tol_p * sd, 9, "<", 0, sst == 1) & (sst == 1)
+    else:
+        vs = np.zeros(0, bool)
+    nviol = int(vr.sum() + (vl | vu).sum() + vs.sum())
+    for nm, c in (("viol_row", vr.sum()), ("viol_lo", vl.sum()), ("viol_up", vu.sum()), ("viol_slack", vs.sum())):
+        bk.hit("primal_finish", nm, c)
+    nrel = 0
+    if check_only:
+        bk.hit("primal_finish", "check_only")
+    elif nviol:
+        rowst[vr] = 1; bst[vl] = -1; bst[vu & ~vl] = 1
+        if ns:
+            sst[vs] = 0
+        bk.hit("primal_finish", "grow")
+        for nm, c in (("grow_row", vr.sum()), ("grow_lo", vl.sum()), ("grow_up", (vu & ~vl).sum()), ("grow_slack", vs.sum())):
+            bk.hit("primal_finish", nm, c)
+    else:
+        pos = np.maximum(st["hpos"], 0)
+        m = hd & (prow != 1) & ineq
+        rr = bk.cmp(rt * uacc[pos], np.abs(uacc[pos]), 1, "<", -LD(tol_m), m) & m
+        bk.hit("primal_finish", "rel_mandatory_kept", (hd & (prow == 1) & ineq).sum())
+        rowst[rr] = 0
+        nrel = int(rr.sum())
+        if ns:
+            ps_ = np.maximum(st["hpos"][st["srow"]], 0)
+            m = (sst == 0) & (ps != 0) & (st["hpos"][st["srow"]] >= 0)
+            rs = bk.cmp(scoef * uacc[ps_], np.abs(scoef * uacc[ps_]), 2, ">", tol_m, m) & m
+            sst[rs] = 1
+            nrel += int(rs.sum())
+            bk.hit("primal_finish", "rel_slack", rs.sum())
+        nu = (p - tN)
+        m = (bst != 0) & (pb == 0) & (st["ub"] > st["lb"])
+        rl = bk.cmp(nu, np.abs(p) + np.abs(tN), 2, "<", -LD(tol_m), m & (bst < 0)) & m & (bst < 0)
+        ru = bk.cmp(nu, np.abs(p) + np.abs(tN), 2, ">", tol_m, m & (bst > 0)) & m & (bst > 0)
+        bst[rl | ru] = 0
+        nrel += int(rl.sum() + ru.sum())
+        if ns:
+            re = np.zeros(M, bool); re[st["srow"][sst == 1]] = True
+            bk.hit("primal_finish", "row_reactivated", (re & (rowst == 0)).sum())
+            rowst[re] = 1
+        bk.hit("primal_finish", "release" if nrel else "unchanged")
+        for nm, c in (("rel_row", rr.sum()), ("rel_lo", rl.sum()), ("rel_up", ru.sum())):
+            bk.hit("primal_finish", nm, c)
+    ex = {"nu": st["p"] - st["tN"], "S%d.rowst" % W: rowst, "S%d.bst" % W: bst, "S%d.sst" % W: sst, "cnt.NVIOL": nviol, "cnt.NREL": nrel}
+    bnd = {"act": (act, ma, 5), "scal.HARDRES": (hres_v.max(initial=0), hres_m.max(initial=0), 9)}
+    if ns:
+        bnd["s"] = (s, smag, 5, sown)
+    return ex, bnd
+
+
+# (n, M, ns): ns = 0 and M = 0; one below, at and above 64, 256 and 1024; above 2048 (three and more sweeps of the one-workgroup loops); around
+# 70 000 in n and in M; ns > M (rows with two slack columns) and rows with none.  Each case runs with rperm null and with a permutation.
+AS_CASES = [
+    (1, 1, 0), (256, 0, 0), (64, 63, 65), (63, 65, 64), (65, 64, 63), (256, 256, 257), (1024, 1024, 1023), (255, 257, 256), (257, 255, 300), (1025, 1023, 1024), (1023, 1025, 1500), (2049, 3100, 2500), (4097, 2050, 0),
+    (70001, 1030, 257), (1030, 70003, 5000),
+]
+
+
+def as_grid_all(n, M, ns):
+    return (max(n, M, ns, 1) + 255) // 256
+
+
+# ---- planted ties: every operand a small dyadic rational, tolerances and scale_q powers of two, so the float64 evaluation is exact in any
+# association and the quantity sits exactly on its threshold: the side taken follows from < / <= / >= alone
+TIE_TOL_P, TIE_TOL_D, TIE_TOL_M, TIE_SQ = 2.0 ** -30, 2.0 ** -20, 2.0 ** -30, 4.0
+AS_TIE_SIZE = (2100, 2100, 1500)
+AS_TIES = {"identify": "lower upper slack row forced".split(), "finish": "row_drop row_add rel_lo rel_up fix_lo fix_up slack_free slack_low".split(),
+           "dual_finish": "col_lo col_up row slack".split(), "primal_finish": "viol_row viol_lo viol_up rel_row rel_lo rel_up".split(),
+           "ns_step": "thr_row thr_lower thr_upper thr_slack".split()}
+
+
+def _spots(mask):
+    """Entries of `mask` nearest to the first and last element, a wavefront edge (63 | 64) and a sweep edge (1023 | 1024)."""
+    idx = np.nonzero(mask)[0]
+    out = []
+    for want in (0, 63, 64, 1023, 1024, len(mask) - 1):
+        if len(idx):
+            out.append(int(idx[np.argmin(np.abs(idx - want))]))
+    return sorted(set(out))
+
+
+def as_tie_state(kernel, which, seed=5):
+    """A state of AS_TIE_SIZE with the comparison `which` of `kernel` planted exactly on its threshold at the _spots; returns (state, planted
+    index list).  scale_q and the tolerances to use are TIE_*."""
+    n, M, ns = AS_TIE_SIZE
+    st = as_state(seed, n, M, ns, TIE_SQ)
+    tp, td, tm = TIE_TOL_P, (TIE_TOL_M if kernel == "dual_finish" else TIE_TOL_D) * TIE_SQ, TIE_TOL_M      # (k_face_dual_finish: td = tol_m scale_q)
+    free = st["ub"] > st["lb"]
+    noslack = (st["rs0"] < 0)
+    if kernel == "identify":
+        if which in ("lower", "upper"):
+            I = _spots(free)
+            st["lb"][I], st["ub"][I] = -1.0, 1.0                                  # width 2
+            a, b = ("ip.tL", "ip.muL") if which == "lower" else ("ip.tU", "ip.muU")
+            st[a][I], st[b][I] = 1.0, 2.0                                          # 1 / 2 == 2 / 4
+        elif which == "slack":
+            I = _spots(np.ones(ns, bool))
+            st["slo"][I], st["ip.ts"][I], st["ip.mus"][I] = 1.0, 1.0, 2.0
+        elif which == "row":
+            I = _spots(noslack)
+            st["rtype"][I] = 1
+            st["r"][I], st["ip.g"][I], st["ip.pi"][I] = 1.0, 1.0, 2.0
+        else:                                                                      # a row made active only by a slack exactly on its threshold
+            I = _spots(st["rs1"] >= 0)
+            st["rtype"][I] = 1
+            st["ip.g"][I], st["ip.pi"][I] = 1.0, 0.0
+            for i in I:
+                st["ip.ts"][st["rs0"][i]], st["ip.mus"][st["rs0"][i]] = 1e-9, 1.0     # rs0 clearly at its bound
+                k = st["rs1"][i]
+                st["slo"][k], st["ip.ts"][k], st["ip.mus"][k] = 1.0, 1.0, 2.0
+        return st, I
+    if kernel in ("finish", "dual_finish", "primal_finish") and which in ("row_drop", "row", "rel_row"):
+        m = noslack & (st["S0.rowst"] == 1) if kernel != "primal_finish" else (st["hpos"] >= 0)
+        I = _spots(m)
+        st["rtype"][I] = 1
+        st["y"][I] = -td
+        st["uacc"][st["hpos"][I]] = -tm
+        for k in range(1, 6):
+            st["S%d.rowst" % k][I] = 1 if k != 3 else 0                            # in W and D, not mandatory
+        return st, I
+    if which in ("row_add", "viol_row", "thr_row"):
+        m = noslack & (st["S0.rowst"] == 0)
+        I = _spots(m)
+        st["rtype"][I] = 1
+        st["r"][I] = 1.0
+        st["t"][I] = 1.0 - 2.0 * tp                                                # rt (r - a) / 2 == tol_p ; g1 == -tol_p
+        st["sl"][I] = 0.0
+        for k in range(1, 6):
+            st["S%d.rowst" % k][I] = 0
+        st["acta"][I] = 2.0
+        return st, I
+    if which in ("rel_lo", "rel_up", "col_lo", "col_up"):
+        lo = which.endswith("lo")
+        I = _spots(free)
+        for k in range(6):
+            st["S%d.bst" % k][I] = -1 if lo else 1
+        st["S3.bst"][I] = 0                                                        # not mandatory
+        st["q"][I] = 1.0
+        st["tN"][I] = 1.0 + td if lo else 1.0 - td                                 # z == -td | td
+        st["p"][I] = -tm if lo else tm                                             # primal_finish: nu = p - tN
+        if kernel == "primal_finish":
+            st["tN"][I] = 0.0
+        return st, I
+    if which in ("fix_lo", "fix_up", "viol_lo", "viol_up", "thr_lower", "thr_upper"):
+        lo = which.endswith("lo") or which.endswith("lower")
+        I = _spots(free)
+        for k in range(6):
+            st["S%d.bst" % k][I] = 0
+        st["lb"][I], st["ub"][I] = -1.0, 1.0
+        st["p"][I] = -1.0 - tp if lo else 1.0 + tp
+        st["pa"][I] = 0.0
+        return st, I
+    if which in ("slack_free", "slack"):
+        I = _spots(np.ones(ns, bool))
+        for k in range(6):
+            st["S%d.sst" % k][I] = 0
+        st["w"][I], st["scoef"][I] = 1.0, 1.0
+        st["y"][st["srow"][I]] = 1.0 + td                                          # zs == -td
+        return st, I
+    if which in ("slack_low", "thr_slack"):
+        # a basic slack whose value lands exactly on slo - tol (1 + |slo|): slo = 1, scoef = 1, r = 1, sl = 1 (one slack column), t = 2 tol
+        I = [k for k in _spots(np.ones(ns, bool)) if st["rs1"][st["srow"][k]] < 0]
+        for k in range(6):
+            st["S%d.sst" % k][I] = 1
+            st["S%d.rowst" % k][st["srow"][I]] = 1
+        st["slo"][I], st["scoef"][I] = 1.0, 1.0
+        rows = st["srow"][I]
+        st["ksoft"][rows] = np.asarray(I, np.int32)
+        st["r"][rows], st["sl"][rows], st["t"][rows] = 1.0, 1.0, 2.0 * tp          # snew = 1 + (1 - 1 - 2 tol) = 1 - 2 tol
+        st["sa"][I] = 2.0
+        st["rtype"][rows] = 0
+        return st, I
+    raise KeyError((kernel, which))
+
+
+def as_ratio_tie_state(fams, spots, decoys=True, seed=9):
+    """k_face_ns_step: a feasible state (no violated inequality) into which entries with the exactly representable ratio 1 / 4 are planted in
+    the families `fams` at the index positions `spots` (wanted positions; the nearest admissible entry is taken), plus - with `decoys` -
+    ineligible entries that would have ratio 1 / 8: a row already in W, an equality row, a column in W, a margin g1 = -tol / 2 >= -tol.
+    Anchor margin g0 = 1 / 4 (rows: times den 2), candidate margin g1 = -3 / 4: ratio = (1/4) / (1/4 + 3/4)."""
+    n, M, ns = AS_TIE_SIZE
+    st = as_state(seed, n, M, ns, TIE_SQ)
+    W = 4
+    rowst, bst, sst = _sets(st, W)
+    noslack = st["rs0"] < 0
+    # feasible everywhere: rows of W-inactive inequalities sit at act = r + rt, free columns inside their box, basic slacks above slo
+    sst[:] = 0
+    st["sl"] = _as_sl(st)
+    st["t"] = st["r"] + st["rtype"] * 1.0 - st["sl"]
+    st["p"] = np.clip(st["p"], st["lb"], st["ub"])
+    planted = []
+
+    def near(mask, want, fam):
+        mask = mask.copy()
+        mask[[j for f, j in planted if (f >= 2) == (fam >= 2) and (f == fam or fam != 1 and f != 1)]] = False      # one plant per row / slack / column
+        idx = np.nonzero(mask)[0]
+        return int(idx[np.argmin(np.abs(idx - want))])
+    for fam in fams:
+        for want in spots:
+            if fam == 0:
+                i = near(noslack & (st["rtype"] != 0), want, fam)
+                rowst[i] = 0; st["rtype"][i] = 1; st["r"][i] = 1.0; st["sl"][i] = 0.0
+                st["acta"][i], st["t"][i] = 1.5, -0.5                               # g0 = 0.5 / 2, g1 = -1.5 / 2
+            elif fam == 1:
+                k = near(st["rs1"][st["srow"]] < 0, want, fam)
+                i = st["srow"][k]
+                sst[k] = 1; rowst[i] = 1
+                st["slo"][k], st["scoef"][k], st["r"][i], st["sl"][i], st["rtype"][i] = 1.0, 1.0, 1.0, 1.0, 0
+                st["t"][i] = 1.5                                                     # snew = 1 + (1 - 2.5) = -0.5 ; g1 = -1.5 / 2
+                st["sa"][k] = 1.5                                                    # g0 = 0.5 / 2
+                i = k
+            else:
+                i = near(st["ub"] > st["lb"], want, fam)
+                bst[i] = 0; st["lb"][i], st["ub"][i] = -1.0, 1.0
+                st["pa"][i], st["p"][i] = (-0.75, -1.75) if fam == 2 else (0.75, 1.75)
+            planted.append((fam, i))
+    if decoys:
+        free_rows = np.nonzero(noslack)[0]
+        used = {i for f, i in planted if f == 0}
+        dr = [i for i in free_rows if i not in used][:3]
+        for j, i in enumerate(dr):                                                  # ratio 1 / 8 if they counted: g0 = 1/4 (den 2), g1 = -7/4
+            st["r"][i], st["sl"][i], st["acta"][i], st["t"][i] = 1.0, 0.0, 1.5, -2.5
+            st["rtype"][i] = 1
+        rowst[dr[0]] = 1                                                            # already in W
+        st["rtype"][dr[1]] = 0; rowst[dr[1]] = 1                                    # an equality row (kept out of the hard residual's way: t = r)
+        st["t"][dr[1]] = 1.0
+        rowst[dr[2]] = 0; st["t"][dr[2]] = 1.0 - TIE_TOL_P                          # g1 = -tol / 2: not below -tol
+        usedc = {i for f, i in planted if f >= 2}
+        dc = [j for j in np.nonzero(st["ub"] > st["lb"])[0] if j not in usedc][:1]
+        for j in dc:
+            st["lb"][j], st["ub"][j], st["pa"][j], st["p"][j] = -1.0, 1.0, -0.75, -2.75
+            bst[j] = -1                                                             # a column in W
+    return st, planted
+
+
+# ---- one equality-constrained solve as Solver::as_solve sequences it (modes 0, 1, 2), with the products and the H-system solve done here in long
+# double.  `do(st, kind, **kw)` runs one stage - a twin on the CPU, the kernel on the device - and returns the state after it.
+def as_chain_lp(seed, n=48, M=30, ns=14):
+    """A small dense LP with a working set (set 0) whose A_HF has orthonormal rows times a diagonal of condition <= 100, so that the H-system
+    is well conditioned by construction (condition of S = A_HF A_HF' at most 1e4)."""
+    rng = np.random.default_rng(seed)
+    st = as_state(seed, n, M, ns, 8.0)
+    st["q"][0] = 8.0
+    rowst, bst, sst = _sets(st, 0)
+    ex, _ = tw_as_setup(st, 0, None, 0, AsBook())
+    H, F = ex["Hidx"][:ex["cnt.NH"]], ex["Fidx"][:ex["cnt.NF"]]
+    while len(H) > len(F) - 2:                                       # more free columns than hard rows
+        j = int(np.nonzero(bst != 0)[0][0]); bst[j] = 0
+        ex, _ = tw_as_setup(st, 0, None, 0, AsBook())
+        H, F = ex["Hidx"][:ex["cnt.NH"]], ex["Fidx"][:ex["cnt.NF"]]
+    A = rng.standard_normal((M, n))
+    Q, _ = np.linalg.qr(rng.standard_normal((len(F), len(H))))
+    A[np.ix_(H, F)] = (10.0 ** rng.uniform(-1, 1, len(H)))[:, None] * Q.T
+    st["sl"] = _as_sl(st)
+    st["s"] = st["slo"].copy()
+    return st, A
+
+
+def as_chain(st, A, cur, mode, p_ref, y_ref, do):
+    """k_as_setup ... k_as_merge and the final products, as Solver::as_solve launches them; returns the state before the tail kernel."""
+    n, M = st["n"], st["M"]
+    Al = A.astype(LD)
+    mul = lambda x: (Al @ x.astype(LD)).astype(np.float64)
+    mulT = lambda y: (Al.T @ y.astype(LD)).astype(np.float64)
+    st = do(st, "setup", cur=cur, p_ref=p_ref)
+    nH, nF, soft = (int(st["cnt"][AC[k]]) for k in ("NH", "NF", "ANYSOFT"))
+    if nH > 0:
+        st = dict(st, t=mul(st["pB"]))
+        if soft:
+            st = dict(st, tN=mulT(st["y"]))
+        st = do(st, "rhs", y_ref=y_ref)
+    if nH > 0 and nF > 0:
+        H = st["Hidx"][:nH]
+        AHF = Al[H] * st["Fmask"].astype(LD)
+        S = AHF @ AHF.T
+
+        def solve(v):
+            u = st["u"].copy()
+            u[:nH] = _ld_solve(S, v[:nH].astype(LD))
+            return u
+        for _ in range(3 if mode == 1 else 4):
+            if mode != 2:
+                st = dict(st, t=mul(st["pF"]))
+                st = do(st, "res_p", k=nH)
+                st = dict(st, u=solve(st["v"]))
+                st = do(st, "scatter_h", src="u", accumulate=1 if mode == 1 else 0)
+                st = dict(st, tN=mulT(st["yfull"]))
+                st = do(st, "add_f")
+            if mode != 1:
+                st = do(st, "scatter_h", src="yH", accumulate=0)
+                st = dict(st, tN=mulT(st["yfull"]))
+                st = do(st, "rd")
+                st = dict(st, t=mul(st["rd"]))
+                st = do(st, "gather_h", k=nH)
+                st = dict(st, u=solve(st["v"]))
+                st = do(st, "add_yh", k=nH)
+    if nH > 0:
+        st = do(st, "merge", with_y=0 if mode == 1 else 1)
+    st = dict(st, t=mul(st["p"]))
+    if mode == 1:
+        st = do(st, "scatter_h", src="uacc", accumulate=0)
+        st = dict(st, tN=mulT(st["yfull"]))
+    else:
+        st = dict(st, tN=mulT(st["y"]))
+    return st
+
+
+def _ld_solve(S, b):
+    """Cholesky solve in long double (S symmetric positive definite by construction)."""
+    N = len(b)
+    L = np.zeros((N, N), LD)
+    for j in range(N):
+        L[j, j] = np.sqrt(S[j, j] - (L[j, :j] * L[j, :j]).sum())
+        L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    x = b.copy()
+    for i in range(N):
+        x[i] = (x[i] - (L[i, :i] * x[:i]).sum()) / L[i, i]
+    for i in range(N - 1, -1, -1):
+        x[i] = (x[i] - (L[i + 1:, i] * x[i + 1:]).sum()) / L[i, i]
+    return x.astype(np.float64)
+
+
+def as_apply(st, tw):
+    """The state after a kernel whose twin result is `tw`: exact outputs as stated, bounded ones rounded to float64."""
+    st = dict(st)
+    ex, bnd = tw[0], tw[1]
+    for nm, want in ex.items():
+        if nm.startswith("cnt."):
+            st["cnt"] = st["cnt"].copy(); st["cnt"][AC[nm[4:]]] = want
+        elif nm.startswith("scal."):
+            st["scal"] = st["scal"].copy(); st["scal"][AS[nm[5:]]] = want
+        else:
+            st[nm] = np.asarray(want)[:len(st[nm])].astype(st[nm].dtype)
+    for nm, b in bnd.items():
+        if nm.startswith("scal."):
+            st["scal"] = st["scal"].copy(); st["scal"][AS[nm[5:]]] = float(b[0])
+        else:
+            own = np.ones(len(st[nm]), bool) if len(b) < 4 else b[3]
+            v = st[nm].copy(); v[own] = np.asarray(b[0])[own].astype(np.float64)
+            st[nm] = v
+    return st
+
+
+def as_twin_do(bk):
+    """The `do` of as_chain that runs the twins."""
+    def do(st, kind, **kw):
+        tw = {"setup": lambda: tw_as_setup(st, kw["cur"], kw["p_ref"], 0, bk), "rhs": lambda: tw_as_rhs(st, kw["y_ref"], bk), "res_p": lambda: tw_as_res_p(st),
+              "scatter_h": lambda: tw_as_scatter_h(st, kw["src"], kw["accumulate"], bk), "add_f": lambda: tw_as_add_f(st), "rd": lambda: tw_as_rd(st),
+              "gather_h": lambda: tw_as_gather_h(st), "add_yh": lambda: tw_as_add_yh(st), "merge": lambda: tw_as_merge(st, kw["with_y"], bk)}[kind]()
+        return as_apply(st, tw)
+    return do
+
+
+def as_oracle_lp(st, A, rp=0):
+    """The oracle's LP container for a state and a dense matrix."""
+    from oracle import lp_solver as O
+    lp = O.LP(st["q"], A, st["rtype"], st["r"], st["lb"], st["ub"], st["srow"], st["scoef"], st["w"], st["slo"])
+    if rp:
+        lp.row_pos = np.empty(lp.M, np.int64)
+        lp.row_pos[st["rperm"]] = np.arange(lp.M)
+    return lp
+
+
+def as_chain_errors(st0, A, fin, mode, p_ref, y_ref):
+    """A finished chain against oracle.eqp on the same working set.  The yardstick is the oracle's own error: eqp is run a second time on the
+    same LP with its rows and columns in reverse order (the same numbers summed in another order) and the two answers, mapped back, differ by
+    d_self - the rounding noise of this solve on this LP, measured, not estimated.  The chain must agree with the oracle within 10 d_self (and
+    never less than 10 units in the last place of the largest entry, for LPs on which the oracle happens to reproduce itself exactly).
+    Returns {name: (error, d_self, error / allowance)}.  Mode 1 compares p, mode 2 y, mode 0 both."""
+    from oracle import lp_solver as O
+    n, M, ns = st0["n"], st0["M"], st0["ns"]
+    lp = as_oracle_lp(st0, A)
+    sets = tuple(a.astype(np.int64) for a in _sets(st0, 0))
+    pr_ = np.zeros(n) if p_ref is None else st0[p_ref]
+    yr_ = np.zeros(M) if y_ref is None else st0[y_ref]
+    refine = 3 if mode == 1 else 4
+    p, s, y, _ = O.eqp(lp, sets, pr_, yr_, refine=refine)
+    lr = O.LP(st0["q"][::-1], A[::-1, ::-1], st0["rtype"][::-1], st0["r"][::-1], st0["lb"][::-1], st0["ub"][::-1], M - 1 - st0["srow"], st0["scoef"], st0["w"], st0["slo"])      # (slack columns keep their order: the first basic slack of a row counts)
+    p2, s2, y2, _ = O.eqp(lr, (sets[0][::-1], sets[1][::-1], sets[2]), pr_[::-1], yr_[::-1], refine=refine)
+    out = {}
+    for nm, a, b, c in (("p", p, p2[::-1], fin["p"]), ("y", y, y2[::-1], fin["y"])):
+        if (nm == "p" and mode == 2) or (nm == "y" and mode == 1):
+            continue
+        d_self = float(np.abs(a - b).max())
+        allow = 10.0 * max(d_self, U * float(np.abs(a).max(initial=0.0)))
+        err = float(np.abs(c - a).max())
+        out[nm] = (err, d_self, err / allow if allow > 0 else (0.0 if err == 0 else np.inf))
+    return out, lp, sets
