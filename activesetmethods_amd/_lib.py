@@ -55,6 +55,13 @@ class AsStage(C.Structure):
                 ("tol_p", C.c_double), ("tol_d", C.c_double), ("tol_m", C.c_double), ("x", C.c_int64 * 4)]
 
 
+class NsStage(C.Structure):
+    """asm_ns_stage: one stage of asm_test_ns_stages (include/asm_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("add", C.c_int32), ("D", C.c_int32), ("B", C.c_int32), ("pub", C.c_uint32),
+                ("rho_p", C.c_double), ("res", C.c_double), ("al", C.c_double), ("be", C.c_double), ("es", C.c_double), ("eta", C.c_double),
+                ("rerr", C.c_double), ("scale", C.c_double), ("val", C.c_double), ("x", C.c_int64 * 4), ("len", C.c_int64)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
@@ -133,6 +140,8 @@ PROTOTYPES = {
                                       _D, C.POINTER(C.c_uint32), C.POINTER(IpmStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_as_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I64, _D, C.c_int64, _I32, C.c_int64, _D, C.c_int64,
                                      C.POINTER(AsStage), C.c_int64, C.POINTER(C.c_uint32)]),
+    "asm_test_ns_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I32, _I32, _I32, _D, _D, _D, _I64, _I32, _D, C.c_int64, _D,
+                                     C.POINTER(C.c_uint32), C.POINTER(NsStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_cholesky": (C.c_int, [_P, _D, C.c_int64, _D]),
     "asm_test_chol_solve": (C.c_int, [_P, _D, C.c_int64, _D, _D]),
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),

@@ -192,6 +192,40 @@ static std::vector<int> rcm_order(const std::vector<int>& rows, const std::vecto
     }
     return order;
 }
+// CSC view of a CSR pattern with n columns: column pointers, row of every entry, and the place of its value in the CSR list (stable: rows
+// ascending inside a column)
+static void csc_from_csr(const std::vector<int>& sp_ptr, const std::vector<int>& sp_col, int64_t n, std::vector<int>& sc_ptr, std::vector<int>& sc_row, std::vector<int>& sc_pos) {
+    const int64_t R = (int64_t)sp_ptr.size() - 1, nnzS = (int64_t)sp_col.size();
+    sc_ptr.assign(n + 1, 0);
+    for (int64_t k = 0; k < nnzS; ++k) sc_ptr[sp_col[k] + 1] += 1;
+    for (int64_t j = 0; j < n; ++j) sc_ptr[j + 1] += sc_ptr[j];
+    std::vector<int> fill(sc_ptr.begin(), sc_ptr.end() - 1);
+    sc_row.resize(nnzS); sc_pos.resize(nnzS);
+    for (int64_t i = 0; i < R; ++i)
+        for (int k = sp_ptr[i]; k < sp_ptr[i + 1]; ++k) {
+            const int q = fill[sp_col[k]]++;
+            sc_row[q] = (int)i;
+            sc_pos[q] = k;
+        }
+}
+// Index lists of the null-space form for row types rtype[0:M] (0 = hard equality row): the equality rows E in reverse Cuthill-McKee order of
+// their coupling graph (S0 = A_EF A_EF' and its factor are banded in that order), the inequality rows I in index order, and each row's place
+// in its list (-1 in the other).  *s0_band / *s0_pairs: bandwidth and structural non-zeros of S0 in that order (rcm_order).
+static void ns_index_lists(const int* rtype, int64_t M, const std::vector<int>& sp_ptr, const std::vector<int>& sp_col, int64_t ncols, std::vector<int>& eidx,
+                           std::vector<int>& epos, std::vector<int>& iidx, std::vector<int>& ipos, int* s0_band, std::vector<int>* s0_pairs) {
+    eidx.clear(); iidx.clear();
+    epos.assign(M, -1); ipos.assign(M, -1);
+    for (int64_t i = 0; i < M; ++i) {
+        if (rtype[i] == 0) { epos[i] = (int)eidx.size(); eidx.push_back((int)i); }
+        else { ipos[i] = (int)iidx.size(); iidx.push_back((int)i); }
+    }
+    const int nE = (int)eidx.size();
+    const std::vector<int> ord = rcm_order(eidx, sp_ptr, sp_col, ncols, s0_band, s0_pairs);
+    std::vector<int> e2(nE);
+    for (int q = 0; q < nE; ++q) e2[q] = eidx[ord[q]];
+    eidx.swap(e2);
+    for (int q = 0; q < nE; ++q) epos[eidx[q]] = q;
+}
 
 struct FacBuf {
     double *S = nullptr, *Linv = nullptr, *Binv = nullptr, *BinvT = nullptr;
@@ -793,6 +827,8 @@ struct Dev {
             }
         return tot > 0 ? act / tot : 1.0;
     }
+    // v[0:len] = val
+    unsigned launch_ns_fill(double* v, double val, int64_t len) { const dim3 g = asmb::blocks(len); asmb::launch(k_ns_fill, g, dim3(256), h->stream, v, val, len); return g.x; }
     void chol_solve_dev(const FacBuf& f, const double* rhs_dev, double* out_dev, int Ms) {
         // the substitution runs in place in the caller's output buffer (w), z in d_vecM
         if (f.small && Ms <= ASM_SMALL_USE) {       // small systems: one workgroup, factor + inverses of its 64-wide diagonal blocks
@@ -1165,13 +1201,35 @@ struct AsLayout {
     int64_t int_len() const { return 6 * (Mp + ldn + nsp) + 3 * Mp + 2 * ldn + 64; }
 };
 
+// Pitches and lengths of the buffers of the null-space form that do not depend on the null-space dimension, for an LP with nE hard equality
+// rows and nI inequality rows (do_setup allocates by them; Solver::nsv places the work vectors).  theta~ = [n-part (ldn) | I-part (nIp)], a row
+// of Gt = [Zt | GI'] has the same shape (pitch ldg).  Work vectors: five n-sized, three M-sized, two E-sized, then six more of n entries
+// (10 .. 13 hold k <= n entries, 14 = e, 15).  kcap: rows reserved for a basis of k rows (Solver::ns_reserve).
+struct NsLayout {
+    int64_t ldn, Mp, nE, nI, nEp, nIp, ldg;
+    NsLayout(int64_t ln, int64_t lm, int64_t ne, int64_t ni)
+        : ldn(ln), Mp(lm), nE(ne), nI(ni), nEp(round_up(ne, 32)), nIp(round_up(std::max<int64_t>(ni, 1), 32)), ldg(ln + nIp) {}
+    int64_t th_len() const { return ldg; }
+    int64_t nsv_len() const { return 11 * ldn + 3 * Mp + 2 * nEp; }
+    int64_t nsv_off(int which) const {
+        if (which < 5) return (int64_t)which * ldn;
+        if (which < 8) return 5 * ldn + (int64_t)(which - 5) * Mp;
+        if (which < 10) return 5 * ldn + 3 * Mp + (int64_t)(which - 8) * nEp;
+        return 5 * ldn + 3 * Mp + 2 * nEp + (int64_t)(which - 10) * ldn;
+    }
+    static int kcap(int k) { return (int)round_up(k + k / 4 + 64, 64); }
+};
+
 struct Solver {
     // out = A x for a k x ncols matrix of few, long rows (the basis Zt): one workgroup per row when that fills the chip better
-    void gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
-        if (rows <= 2048 && ncols >= 2048)
+    unsigned gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
+        if (rows <= 2048 && ncols >= 2048) {
             asmb::launch(k_gemv_n_wide, dim3((unsigned)rows), dim3(256), h->stream, A, ld, x, out, rows, ncols);
-        else
-            asmb::launch(k_gemv_n, asmb::blocks(rows, 4), dim3(256), h->stream, A, ld, x, out, rows, ncols);
+            return (unsigned)rows;
+        }
+        const dim3 g = asmb::blocks(rows, 4);
+        asmb::launch(k_gemv_n, g, dim3(256), h->stream, A, ld, x, out, rows, ncols);
+        return g.x;
     }
     // workgroups of the interior-point reductions (k_ipm_measures / _steps / _muaff): 1024 elements per workgroup and sweep, at most IPM_RED_MAXWG
     unsigned red_grid() const { return (unsigned)std::min<int64_t>(IPM_RED_MAXWG, std::max<int64_t>(1, (std::max(std::max(lp.n, lp.M), lp.ns) + 4095) / 4096)); }
@@ -1251,6 +1309,15 @@ struct Solver {
         P.hscal = ar.hscal; P.hseq = ar.hseq;
         P.rpart = ar.rpart; P.rcnt = ar.rcnt;
         P.rtype = ar.ibase; P.rs0 = ar.ibase + lm; P.rs1 = ar.ibase + 2 * lm; P.srow = ar.ibase + 3 * lm;
+    }
+    // the vectors of the arena in the order the test hooks report them (include/asm_hip.h, asm_test_ipm_stages)
+    void ipm_vectors(const double* (&vs)[ASM_IPM_NVEC]) const {
+        const double* v[ASM_IPM_NVEC] = {P.q, P.lb, P.ub, P.r, P.w, P.slo, P.scoef, P.p, P.s, P.g, P.y, P.tL, P.tU, P.muL, P.muU, P.ts, P.mus, P.pi, P.act, P.aty, P.rp,
+                                         P.rdp, P.rds, P.thp_inv, P.ths_inv, P.dS, P.hp, P.hs, P.tmpn, P.t1, P.rhs, P.res, P.rcL, P.rcU, P.rcs, P.rcg,
+                                         dirA.dp, dirA.ds, dirA.dg, dirA.dy, dirA.dmuL, dirA.dmuU, dirA.dmus, dirA.dpi,
+                                         dirC.dp, dirC.ds, dirC.dg, dirC.dy, dirC.dmuL, dirC.dmuU, dirC.dmus, dirC.dpi,
+                                         d_sres, d_corr, d_pcg, d_tN};
+        for (int q = 0; q < ASM_IPM_NVEC; ++q) vs[q] = v[q];
     }
     // ---- launch sites of the stage kernels (asm_ipm_kernels.hip.h): the solver and the test hook asm_test_ipm_stages launch through these
     // members only; each returns the number of workgroups it launched
@@ -1402,8 +1469,8 @@ struct Solver {
         if (ns_live()) {
             // null-space form: the equality rows' multipliers are carried as 0, the dual residual that counts is Z'rdp (oracle: IPM.measures)
             launch_measures(0u);
-            gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)P.rdp, nsv(12), (int64_t)ip.ns_k, h->ldn);
-            asmb::launch(k_ns_dinf, dim3(1), dim3(1024), h->stream, P, nsv(12), ip.ns_k, pub);
+            launch_ns_zt(P.rdp, nsv(12), ip.ns_k);
+            launch_ns_dinf(nsv(12), ip.ns_k, pub);
         } else {
             launch_measures(pub);
         }
@@ -1442,7 +1509,34 @@ struct Solver {
     bool ns_lp = false;       // this LP has a valid null-space basis (set up before the warm attempt: the active-set solves use it too)
     int ns_k = 0;
     SolveHint* cur_hint = nullptr;
-    NsIdx nsX() const { NsIdx X; X.Eidx = h->d_nsEidx; X.Epos = h->d_nsEpos; X.Iidx = h->d_nsIidx; X.Ipos = h->d_nsIpos; X.nE = h->ns_nE; X.nI = h->ns_nI; return X; }
+    // where the buffers of a null-space iteration live: the handle's (ns_bind()), or buffers of a test hook's with the pitches of NsLayout
+    struct NsArena {
+        double *v = nullptr, *th = nullptr, *G = nullptr, *N0 = nullptr, *partial = nullptr;      // work vectors, theta~, Gt, unregularised N, scratch of Zt' u
+        const FacBuf* fN = nullptr;
+        const int *sp_ptr = nullptr, *sp_col = nullptr, *sc_ptr = nullptr, *sc_row = nullptr, *sc_pos = nullptr;
+        const double* vals = nullptr;     // values of the sparse pattern; null: the handle's gathered copy of Ah (Dev::sparse_vals)
+        NsIdx X = {nullptr, nullptr, nullptr, nullptr, 0, 0};
+        int64_t ldn = 0, Mp = 0, nEp = 0, nIp = 0, ldg = 0;
+        int64_t voff[16] = {0};           // offsets of the work vectors in v (NsLayout::nsv_off)
+    } ns_ar;
+    // bound once per LP, like the interior-point arena: at the start of ns_setup and again when ns_reserve has made the k-sized buffers
+    void ns_bind() {
+        NsArena a;
+        a.v = h->d_nsv; a.th = h->d_nsth; a.G = h->d_nsG; a.N0 = h->d_nsN0; a.partial = h->d_partial;
+        a.fN = &h->ns_fN;
+        a.sp_ptr = h->d_sp_ptr; a.sp_col = h->d_sp_col; a.sc_ptr = h->d_sc_ptr; a.sc_row = h->d_sc_row; a.sc_pos = h->d_sc_pos;
+        a.X.Eidx = h->d_nsEidx; a.X.Epos = h->d_nsEpos; a.X.Iidx = h->d_nsIidx; a.X.Ipos = h->d_nsIpos; a.X.nE = h->ns_nE; a.X.nI = h->ns_nI;
+        a.ldn = h->ldn; a.Mp = h->Mp; a.nEp = h->ns_nEp; a.nIp = h->ns_nIp; a.ldg = h->ns_ldg;
+        ns_bind(a);
+    }
+    void ns_bind(const NsArena& a) {
+        ns_ar = a;
+        const NsLayout nl(a.ldn, a.Mp, a.X.nE, a.X.nI);
+        for (int w = 0; w < 16; ++w) ns_ar.voff[w] = nl.nsv_off(w);
+    }
+    const NsArena& nsa() const { return ns_ar; }
+    NsIdx nsX() const { return nsa().X; }
+    const double* ns_vals() { const NsArena& a = nsa(); return a.vals ? a.vals : dev.sparse_vals(h->d_Ah); }
     int ns_read_cnt() {
         int v = 0;
         HIPCHK(asmb::copy_async(&v, h->d_nscnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1462,7 +1556,7 @@ struct Solver {
             h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0;
         }
         BufPool& P = h->mem_nsk;
-        const int cap = (int)round_up(k + k / 4 + 64, 64);
+        const int cap = NsLayout::kcap(k);
         P.zeroed(h->d_nsR, (int64_t)cap * h->ns_nEp, h->stream);
         P.zeroed(h->d_nsX, (int64_t)cap * h->ns_nEp, h->stream);
         P.zeroed(h->d_nsG, (int64_t)cap * h->ns_ldg, h->stream);
@@ -1508,7 +1602,7 @@ struct Solver {
         asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm,
                      h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 1);
         dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
-        asmb::launch(k_ns_fill, asmb::blocks(k), dim3(256), h->stream, h->d_diag0, 1.0, (int64_t)k);
+        dev.launch_ns_fill(h->d_diag0, 1.0, (int64_t)k);
         dev.chol(h->ns_fN, k, thr);
         asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
         const int bad2 = ns_read_cnt();
@@ -1532,7 +1626,7 @@ struct Solver {
         asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm,
                      h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 0);
         asmb::launch(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_nsG, h->ns_ldg, h->d_nsJ, k, h->ns_fN.S, h->ns_fN.ld);
-        asmb::launch(k_ns_fill, asmb::blocks(k), dim3(256), h->stream, h->d_diag0, 1.0, (int64_t)k);
+        dev.launch_ns_fill(h->d_diag0, 1.0, (int64_t)k);
         dev.chol(h->ns_fN, k, NS_WARM_THR);
         asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
         const int bad = ns_read_cnt();
@@ -1543,6 +1637,7 @@ struct Solver {
     // Per LP (oracle: NullSpace.__init__): factor S0, null-space dimension, basis columns (retained ones, else a guarded Cholesky of
     // P in index order), orthonormal basis.  False: the LP keeps the row form.
     bool ns_setup() {
+        ns_bind();
         const int nE = h->ns_nE;
         const int64_t n = lp.n;
         const NsIdx X = nsX();
@@ -1578,6 +1673,7 @@ struct Solver {
         const int64_t k = nF - (nE - dropped);
         if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
         ns_reserve((int)k);
+        ns_bind();
         asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), h->stream, h->ns_f0.S, h->ns_f0.ld, (int64_t)nE, (int64_t)nE,
                      h->d_nsLt, h->ns_f0.ld, (int64_t)(h->ns_f0.band > 0 ? h->ns_f0.band : nE));
         std::vector<int>& J = cur_hint->ns_J;
@@ -1608,7 +1704,7 @@ struct Solver {
             for (int a = 0; a < 4 && !have; ++a) {
                 asmb::launch(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_nsFm);
                 dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, h->ns_nEp, nullptr, 0, (int)n, h->ns_nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
-                asmb::launch(k_ns_fill, asmb::blocks(n), dim3(256), h->stream, h->d_diag0, 1.0, n);
+                dev.launch_ns_fill(h->d_diag0, 1.0, n);
                 dev.chol(T, (int)n, NS_SEL_THR[a]);
                 asmb::launch(k_ns_diag, asmb::blocks(n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_vecN);
                 HIPCHK(asmb::copy_async(dg.data(), h->d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1625,12 +1721,7 @@ struct Solver {
         h->ns_Zk = (int)k;
         return true;
     }
-    double* nsv(int which) const {      // work vectors: 0..4 n-sized, 5..7 M-sized, 8..9 E-sized, 10..13 k-sized (k <= n)
-        if (which < 5) return h->d_nsv + (int64_t)which * h->ldn;
-        if (which < 8) return h->d_nsv + 5 * h->ldn + (int64_t)(which - 5) * h->Mp;
-        if (which < 10) return h->d_nsv + 5 * h->ldn + 3 * h->Mp + (int64_t)(which - 8) * h->ns_nEp;
-        return h->d_nsv + 5 * h->ldn + 3 * h->Mp + 2 * h->ns_nEp + (int64_t)(which - 10) * h->ldn;      // 10..13 k-sized, 14..15 n-sized (14 = e)
-    }
+    double* nsv(int which) const { return ns_ar.v + ns_ar.voff[which]; }      // work vectors: 0..4 n-sized, 5..7 M-sized, 8..9 E-sized, 10..13 k-sized (k <= n), 14..15 n-sized (14 = e)
     // oracle: ns_applicable
     bool ns_applicable() const {
         if (!h->ns_cap || lp.ns != 0) return false;
@@ -1664,16 +1755,16 @@ struct Solver {
     // per LP (oracle: eqp_ns, the part that does not depend on the working set): pbar, A pbar, u0 = Z'(p_ref - pbar), Z'q
     void ns_lp_vectors() {
         const int k = ns_k, nE = h->ns_nE;
-        const int64_t M = lp.M, ldn = h->ldn;
+        const int64_t ldn = h->ldn;
         const NsIdx X = nsX();
         const NsEq Q = nsq();
-        const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256), gE = (unsigned)((nE + 255) / 256);
+        const unsigned gN = (unsigned)((ldn + 255) / 256), gE = (unsigned)((nE + 255) / 256);
         double *pfix = nsv(0), *x = nsv(1), *vz = nsv(2), *yM = nsv(5), *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         asmb::launch(k_nseq_pfix, dim3(gN), dim3(256), h->stream, A, pfix, ldn);
         dev.gemv_n_dev(h->d_Ah, pfix, aM);
         asmb::launch(k_nseq_be, dim3(gE), dim3(256), h->stream, A, X, aM, rE);
         dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
-        asmb::launch(k_ns_rowvec_e, dim3(gM), dim3(256), h->stream, X, tE, yM, M);
+        launch_ns_rowvec_e(tE, yM);
         dev.gemv_t_dev(h->d_Ah, yM, x);
         asmb::launch(k_nseq_pbar, dim3(gN), dim3(256), h->stream, A, pfix, x, d_zero, Q.pbar, vz, ldn);
         dev.gemv_n_dev(h->d_Ah, Q.pbar, Q.tbar);
@@ -1688,7 +1779,7 @@ struct Solver {
         const int64_t M = lp.M, n = lp.n, ldn = h->ldn;
         const NsIdx X = nsX();
         const NsEq Q = nsq();
-        const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256), gE = (unsigned)((nE + 255) / 256);
+        const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256);
         asmb::launch(k_nseq_setup, dim3(1), dim3(1024), h->stream, A, cur, X, Q, ldn);
         int cnt[2] = {0, 0};
         HIPCHK(asmb::copy_async(cnt, Q.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1710,12 +1801,12 @@ struct Solver {
                 asmb::launch(k_nseq_sub, dim3(gA), dim3(256), h->stream, Q.d, Q.v, Q.v, (int64_t)nact);
                 dev.chol_solve_dev(C, Q.v, Q.w, nact);
                 nsq_gemv_t(Q, nact, Q.w, t1);
-                asmb::launch(k_ns_add, dim3(gC), dim3(256), h->stream, Q.u, t1, Q.u, Q.ldc);
+                launch_ns_add(Q.u, t1, Q.u, Q.ldc);
                 nsq_gemv_t(Q, nact, Q.lam, t1);                                                                          // C' lam
                 asmb::launch(k_nseq_sub, dim3(gC), dim3(256), h->stream, Q.qh, t1, t2, Q.ldc);
                 nsq_gemv_n(Q, nact, t2, Q.v);
                 dev.chol_solve_dev(C, Q.v, Q.w, nact);
-                asmb::launch(k_ns_add, dim3(gA), dim3(256), h->stream, Q.lam, Q.w, Q.lam, (int64_t)nact);
+                launch_ns_add(Q.lam, Q.w, Q.lam, (int64_t)nact);
             }
         }
         double *zu = nsv(3), *atw = nsv(4), *wN = nsv(2), *yM = nsv(5), *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
@@ -1725,7 +1816,7 @@ struct Solver {
         dev.gemv_t_dev(h->d_Ah, yM, atw);
         asmb::launch(k_nseq_w, dim3(gN), dim3(256), h->stream, A, Q, atw, wN, ldn);
         dev.gemv_n_dev(h->d_Ah, wN, aM);
-        asmb::launch(k_ns_gather_e, dim3(gE), dim3(256), h->stream, X, aM, 1.0, rE);
+        launch_ns_gather_e(aM, 1.0, rE);
         dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
         asmb::launch(k_nseq_y, dim3(gM), dim3(256), h->stream, A, X, yM, tE);
         dev.gemv_n_dev(h->d_Ah, A.p, A.t);
@@ -1739,25 +1830,128 @@ struct Solver {
     // measures (with the equality multipliers as they stand: 0, or the values recovered at the end of the previous stage)
     void ns_finish_y() {
         const int nE = h->ns_nE;
-        const NsIdx X = nsX();
-        const unsigned gE = (unsigned)((nE + 255) / 256);
         double *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         dev.gemv_n_dev(h->d_Ah, P.rdp, aM);
-        asmb::launch(k_ns_gather_e, dim3(gE), dim3(256), h->stream, X, aM, 1.0, rE);
+        launch_ns_gather_e(aM, 1.0, rE);
         dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
         // P.rdp already contains -A_E'y_E of the multipliers recovered at the end of an earlier stage: the solve gives the correction
-        asmb::launch(k_ns_scatter_e, dim3(gE), dim3(256), h->stream, X, tE, P.y, 1);
+        launch_ns_scatter_e(tE, P.y, 1);
+    }
+    // ---- launch sites of the kernels of a null-space iteration (asm_ns_kernels.hip.h): the solver and the test hook asm_test_ns_stages launch
+    // through these members only; each carries its launch's grid and returns the number of workgroups it launched
+    unsigned launch_theta_ns(double rho_p) {
+        const NsArena& a = nsa();
+        const unsigned g = std::max(grid_all(), (unsigned)((std::max<int64_t>(a.ldn, a.nIp) + 255) / 256));
+        asmb::launch(k_ipm_theta_ns, dim3(g), dim3(256), h->stream, P, rho_p, a.X, a.th, a.ldn, (int)a.nIp);
+        return g;
+    }
+    unsigned launch_ns_update(const IpmDir& C, double al, double be, double es) {
+        const unsigned g = grid_all();
+        asmb::launch(k_ns_update, dim3(g), dim3(256), h->stream, P, C, al, be, nsv(14), es, nsa().ldn);
+        return g;
+    }
+    unsigned launch_ns_update_dev(const IpmDir& C, double eta, double rerr) {
+        const unsigned g = grid_all();
+        asmb::launch(k_ns_update_dev, dim3(g), dim3(256), h->stream, P, C, eta, nsv(14), nsa().ldn, rerr);
+        return g;
+    }
+    unsigned launch_ns_dinf(const double* zr, int k, unsigned pub) { asmb::launch(k_ns_dinf, dim3(1), dim3(1024), h->stream, P, zr, k, pub); return 1; }
+    // out[k] = Zt x   (x of ldn entries)
+    unsigned launch_ns_zt(const double* x, double* out, int k) { const NsArena& a = nsa(); return gemv_rows((const double*)a.G, a.ldg, x, out, (int64_t)k, a.ldn); }
+    unsigned launch_ns_e0(const double* pbar, double* d0) {
+        const NsArena& a = nsa();
+        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
+        asmb::launch(k_ns_e0, dim3(gN), dim3(256), h->stream, P, pbar, d0, a.ldn);
+        return gN;
+    }
+    unsigned launch_ns_e1(const double* d0, const double* zz, double* e) {
+        const NsArena& a = nsa();
+        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
+        asmb::launch(k_ns_e1, dim3(gN), dim3(256), h->stream, P, d0, zz, e, a.ldn);
+        return gN;
+    }
+    // dpbar = -e, SC_NSERR = 0, yM = D_I^-1 (Ah dpbar)
+    unsigned launch_ns_spmvn_wm_neg(const double* vals) {
+        const NsArena& a = nsa();
+        const unsigned gM = (unsigned)((lp.M + 255) / 256), gN = (unsigned)((a.ldn + 255) / 256), g = std::max(gM, gN);
+        asmb::launch(k_ns_spmvn_wm_neg, dim3(g), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, nsv(14), nsv(0), a.ldn, P.scal + SC_NSERR, a.X, (const double*)(a.th + a.ldn), nsv(5), lp.M);
+        return g;
+    }
+    // K dpbar = Th dpbar + Ah' yM
+    unsigned launch_ns_spmvt_kx(const double* vals) {
+        const NsArena& a = nsa();
+        const dim3 g = asmb::blocks(a.ldn * 8);
+        asmb::launch(k_ns_spmvt_kx, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, nsv(0), nsv(1), lp.n, a.ldn);
+        return g.x;
+    }
+    unsigned launch_ns_rhs1_bi(const IpmDir& base, int mode, double res) {
+        const NsArena& a = nsa();
+        const unsigned g = grid_all();
+        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), h->stream, P, base, mode, a.X, (const double*)(a.th + a.ldn), res, nsv(7), nsv(5));
+        return g;
+    }
+    unsigned launch_ns_spmvt_ht(const double* vals, double res) {
+        const NsArena& a = nsa();
+        const dim3 g = asmb::blocks(a.ldn * 8);
+        asmb::launch(k_ns_spmvt_ht, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, P.hp, nsv(1), res, nsv(2), nsv(3), lp.n, a.ldn);
+        return g.x;
+    }
+    unsigned launch_ns_reduced_solve(int k, const double* ru, double* du) {
+        const NsArena& a = nsa();
+        asmb::launch(k_ns_reduced_solve, dim3(1), dim3(1024), h->stream, a.fN->S, a.fN->ld, a.fN->Linv, a.N0, k, ru, du, P.scal + SC_NSERR);
+        return 1;
+    }
+    unsigned launch_ns_symv_res(int k, const double* x, const double* rhs, double* out) {
+        const NsArena& a = nsa();
+        const dim3 g = asmb::blocks(k, 4);
+        asmb::launch(k_ns_symv_res, g, dim3(256), h->stream, a.N0, a.fN->ld, k, x, rhs, out);
+        return g.x;
+    }
+    unsigned launch_ns_add(const double* a_, const double* b_, double* x, int64_t len) {
+        const unsigned g = (unsigned)((len + 255) / 256);
+        asmb::launch(k_ns_add, dim3(g), dim3(256), h->stream, a_, b_, x, len);
+        return g;
+    }
+    unsigned launch_ns_relres(const double* r, const double* rhs, int k) { asmb::launch(k_ns_relres, dim3(1), dim3(1024), h->stream, r, rhs, k, P.scal + SC_NSERR); return 1; }
+    unsigned launch_ns_gemv_t_small_dp(int k, const double* du, const IpmDir& D, double res) {
+        const NsArena& a = nsa();
+        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
+        asmb::launch(k_gemv_t_small_dp, dim3(gN), dim3(256), h->stream, a.G, a.ldg, k, du, P, D, (const double*)a.th, nsv(0), res, a.ldn);
+        return gN;
+    }
+    unsigned launch_ns_dp(const IpmDir& D, double res, const double* zu) {
+        const NsArena& a = nsa();
+        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
+        asmb::launch(k_ns_dp, dim3(gN), dim3(256), h->stream, P, D, (const double*)a.th, nsv(0), res, zu, a.ldn);
+        return gN;
+    }
+    unsigned launch_ns_spmvn_rows(const double* vals, const IpmDir& D) {
+        const NsArena& a = nsa();
+        const unsigned gM = (unsigned)((lp.M + 255) / 256);
+        asmb::launch(k_ns_spmvn_rows, dim3(gM), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, P, D, a.X, (const double*)(a.th + a.ldn), nsv(7), nsv(5));
+        return gM;
+    }
+    unsigned launch_ns_gather_e(const double* r, double scale, double* out) {
+        const NsIdx X = nsX();
+        const unsigned gE = (unsigned)((X.nE + 255) / 256);
+        asmb::launch(k_ns_gather_e, dim3(gE), dim3(256), h->stream, X, r, scale, out);
+        return gE;
+    }
+    unsigned launch_ns_scatter_e(const double* tE, double* out, int add) {
+        const NsIdx X = nsX();
+        const unsigned gE = (unsigned)((X.nE + 255) / 256);
+        asmb::launch(k_ns_scatter_e, dim3(gE), dim3(256), h->stream, X, tE, out, add);
+        return gE;
+    }
+    unsigned launch_ns_rowvec_e(const double* tE, double* yM) {
+        const unsigned gM = (unsigned)((lp.M + 255) / 256);
+        asmb::launch(k_ns_rowvec_e, dim3(gM), dim3(256), h->stream, nsX(), tE, yM, lp.M);
+        return gM;
     }
     // Per iteration (oracle: IPM.run, null-space branch): reduced matrix N = Zt Th Zt' + GI' D_I^-1 GI (an unregularised copy is kept for the
     // refinement sweep), its factor, dpbar = A_EF' S0^-1 (-rp_E) and K dpbar (shared by predictor and corrector)
     void ns_iter_setup() {
         const int k = ip.ns_k;
-        const int64_t M = lp.M, ldn = h->ldn;
-        const NsIdx X = nsX();
-        const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256);
-        double *dpb = nsv(0), *kdpb = nsv(1), *yM = nsv(5);
-        const double* th = h->d_nsth;
-        const double* thI = h->d_nsth + ldn;
         // (theta~ was formed with the interior-point theta: k_ipm_theta_ns in ipm_run)
         // the k range (free columns + inequality rows, 19 000 at n = 11 192) is long and the matrix small (k = 519: 45 tiles of 64 x 64):
         // split-K fills the chip; the slices are added in a fixed order while the unregularised copy N0 is made
@@ -1769,66 +1963,73 @@ struct Solver {
         dev.ns_newton_matrix(h->d_nsG, h->ns_ldg, h->d_nsth, k, nsplit, h->d_nsNp, h->ns_fN, h->d_nsN0, h->d_diag0, 1e-13, 1e-30);
         dev.chol(h->ns_fN, k, 1e-14, false);
         // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
-        double* e = nsv(14);
         if (!ip.ns_e_ready) {
             ip.ns_e_ready = true;
-            double *d0 = nsv(2), *zz = nsv(3), *tk = nsv(12);
-            asmb::launch(k_ns_e0, dim3(gN), dim3(256), h->stream, P, nsq().pbar, d0, ldn);
-            gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)d0, tk, (int64_t)k, ldn);
-            ns_gemv_t_dense(tk, k, zz);
-            asmb::launch(k_ns_e1, dim3(gN), dim3(256), h->stream, P, d0, zz, e, ldn);
+            ns_split_e(k, nsq().pbar);
         }
         // (fused launches: negation + clearing of the residual measure; sparse product + its row- / column-wise kernel)
-        const double* vals = dev.sparse_vals(h->d_Ah);
-        asmb::launch(k_ns_spmvn_wm_neg, dim3(std::max(gM, gN)), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, e, dpb, ldn, P.scal + SC_NSERR, X, thI, yM, M);
-        asmb::launch(k_ns_spmvt_kx, asmb::blocks(ldn * 8), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, yM, th, dpb, kdpb, lp.n, ldn);
+        const double* vals = ns_vals();
+        launch_ns_spmvn_wm_neg(vals);
+        launch_ns_spmvt_kx(vals);
+    }
+    // e = (I - Z Zt) Fm (p - pbar)  (work vectors: d0 = 2, Z Zt d0 = 3, Zt d0 = 12, e = 14)
+    void ns_split_e(int k, const double* pbar) {
+        double *d0 = nsv(2), *zz = nsv(3), *tk = nsv(12);
+        launch_ns_e0(pbar, d0);
+        launch_ns_zt(d0, tk, k);
+        ns_gemv_t_dense(tk, k, zz);
+        launch_ns_e1(d0, zz, nsv(14));
     }
     // One Newton solve in null-space form (oracle: IPM.run, solve_ns): mode 0 affine, 1 Mehrotra corrector on `base`.  The relative residual of
     // the reduced solve (after its refinement sweep) is accumulated in SC_NSERR.
+    // Work vectors: dpbar = 0, K dpbar = 1, h~ = 2, v = 3, yM = 5, bI = 7, ru = 10, du = 11, rr = 12, dd = 13.
     void ns_newton(int mode, const IpmDir& base, IpmDir& D) {
         const int k = ip.ns_k;
-        const int64_t M = lp.M, n = lp.n, ldn = h->ldn;
-        const NsIdx X = nsX();
-        const unsigned g = grid_all(), gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256), gK = (unsigned)((k + 255) / 256);
-        double *dpb = nsv(0), *kdpb = nsv(1), *ht = nsv(2), *v = nsv(3), *yM = nsv(5), *bI = nsv(7);
-        double *ru = nsv(10), *du = nsv(11), *rr = nsv(12), *dd = nsv(13);
-        const double* th = h->d_nsth;
-        const double* thI = h->d_nsth + ldn;
         const double res = 1.0;
-        const double* vals = dev.sparse_vals(h->d_Ah);
-        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), h->stream, P, base, mode, X, thI, res, bI, yM);
-        asmb::launch(k_ns_spmvt_ht, asmb::blocks(ldn * 8), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, yM, th, P.hp, kdpb, res, ht, v, n, ldn);
-        gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)v, ru, (int64_t)k, ldn);
-        if (k <= ASM_SMALL_USE) {
-            // solve, refinement sweep on the unregularised matrix and the residual check in ONE one-workgroup launch
-            asmb::launch(k_ns_reduced_solve, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, h->ns_fN.Linv, h->d_nsN0, k, ru, du, P.scal + SC_NSERR);
-        } else {
-            dev.chol_solve_dev(h->ns_fN, ru, du, k);
-            asmb::launch(k_ns_symv_res, asmb::blocks(k, 4), dim3(256), h->stream, h->d_nsN0, h->ns_fN.ld, k, du, ru, rr);
-            dev.chol_solve_dev(h->ns_fN, rr, dd, k);
-            asmb::launch(k_ns_add, dim3(gK), dim3(256), h->stream, du, dd, du, (int64_t)k);
-            asmb::launch(k_ns_symv_res, asmb::blocks(k, 4), dim3(256), h->stream, h->d_nsN0, h->ns_fN.ld, k, du, ru, rr);
-            asmb::launch(k_ns_relres, dim3(1), dim3(1024), h->stream, rr, ru, k, P.scal + SC_NSERR);
-        }
-        if (k <= ASM_SMALL_USE) {
-            asmb::launch(k_gemv_t_small_dp, dim3(gN), dim3(256), h->stream, h->d_nsG, h->ns_ldg, k, du, P, D, th, dpb, res, ldn);
-        } else {
-            ns_gemv_t_dense(du, k, v);
-            asmb::launch(k_ns_dp, dim3(gN), dim3(256), h->stream, P, D, th, dpb, res, v, ldn);
-        }
-        asmb::launch(k_ns_spmvn_rows, dim3(gM), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, P, D, X, thI, bI, yM);
+        const double* vals = ns_vals();
+        launch_ns_rhs1_bi(base, mode, res);
+        launch_ns_spmvt_ht(vals, res);
+        launch_ns_zt(nsv(3), nsv(10), k);
+        ns_reduced_solve(k);
+        ns_direction(k, D, res);
+        launch_ns_spmvn_rows(vals, D);
+    }
+    // du = N^-1 ru with one refinement sweep on the unregularised N0; SC_NSERR = max(SC_NSERR, relative residual)
+    unsigned ns_reduced_solve(int k) {
+        double *ru = nsv(10), *du = nsv(11), *rr = nsv(12), *dd = nsv(13);
+        // solve, refinement sweep on the unregularised matrix and the residual check in ONE one-workgroup launch
+        if (k <= ASM_SMALL_USE) return launch_ns_reduced_solve(k, ru, du);
+        const FacBuf& fN = *nsa().fN;
+        dev.chol_solve_dev(fN, ru, du, k);
+        const unsigned g = launch_ns_symv_res(k, du, ru, rr);
+        dev.chol_solve_dev(fN, rr, dd, k);
+        launch_ns_add(du, dd, du, (int64_t)k);
+        launch_ns_symv_res(k, du, ru, rr);
+        launch_ns_relres(rr, ru, k);
+        return g;
+    }
+    // dp = res dpbar + Z du with the bound multipliers' directions
+    unsigned ns_direction(int k, const IpmDir& D, double res) {
+        double *v = nsv(3), *du = nsv(11);
+        if (k <= ASM_SMALL_USE) return launch_ns_gemv_t_small_dp(k, du, D, res);
+        ns_gemv_t_dense(du, k, v);
+        return launch_ns_dp(D, res, v);
     }
     // out[n] = Zt' u   (Zt dense, k rows of pitch ldg)
-    void ns_gemv_t_dense(const double* u, int k, double* out) {
+    unsigned ns_gemv_t_dense(const double* u, int k, double* out) {
+        const NsArena& a = nsa();
         if (k <= ASM_SMALL_USE) {
-            asmb::launch(k_gemv_t_small, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_nsG, h->ns_ldg, k, u, out, h->ldn);
-            return;
+            const dim3 g = asmb::blocks(a.ldn);
+            asmb::launch(k_gemv_t_small, g, dim3(256), h->stream, a.G, a.ldg, k, u, out, a.ldn);
+            return g.x;
         }
         int64_t R = std::min<int64_t>((k + 31) / 32, ASM_TMAXCHUNKS);
         int64_t chunk = (k + R - 1) / R;
         R = (k + chunk - 1) / chunk;
-        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, h->d_nsG, h->ns_ldg, u, h->d_partial, (int64_t)k, h->ldn, chunk);
-        asmb::launch(k_gemv_t_stage2, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_partial, out, R, h->ldn);
+        const unsigned gx = (unsigned)((a.ldn + 255) / 256);
+        asmb::launch(k_gemv_t_stage1, dim3(gx, (unsigned)R), dim3(256), h->stream, a.G, a.ldg, u, a.partial, (int64_t)k, a.ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(a.ldn), dim3(256), h->stream, a.partial, out, R, a.ldn);
+        return gx * (unsigned)R;
     }
 
     NewtonForm form = NewtonForm::Row;      // form of the current factorisation
@@ -2050,8 +2251,7 @@ struct Solver {
                 return ip.status = ASM_OTHER;
             }
             if (ns_live())      // null-space form: its theta~ in the same launch (ns_iter_setup)
-                asmb::launch(k_ipm_theta_ns, dim3(std::max(grid_all(), (unsigned)((std::max<int64_t>(h->ldn, h->ns_nIp) + 255) / 256))), dim3(256), h->stream, P, IPM_RHO_P, nsX(),
-                             h->d_nsth, h->ldn, h->ns_nIp);
+                launch_theta_ns(IPM_RHO_P);
             else
                 launch_theta(IPM_RHO_P);
             form = choose_form();
@@ -2101,7 +2301,7 @@ struct Solver {
             if (!(defer && solves(true))) solves(false);
             const double eta = ip.mu >= 1.0 ? IPM_ETA0 : std::min(std::max(IPM_ETA0, 1.0 - ip.mu / lp.scale_q), 0.999999);
             if (ns && ns_defer) {
-                asmb::launch(k_ns_update_dev, dim3(grid_all()), dim3(256), h->stream, P, dirC, eta, nsv(14), h->ldn, h->knobs.ns_rerr);
+                launch_ns_update_dev(dirC, eta, h->knobs.ns_rerr);
                 ns_pending = true;
                 continue;
             }
@@ -2113,8 +2313,7 @@ struct Solver {
                 continue;
             }
             if (ns)
-                asmb::launch(k_ns_update, dim3(grid_all()), dim3(256), h->stream, P, dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), nsv(14), 1.0 - std::min(1.0, eta * ap),
-                             h->ldn);
+                launch_ns_update(dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad), 1.0 - std::min(1.0, eta * ap));
             else
                 launch_update(dirC, std::min(1.0, eta * ap), std::min(1.0, eta * ad));
             if (approx && cg_max > (form == NewtonForm::Column ? COL_MAX_CG : RED_MAX_CG)) drop_form(form);
@@ -2952,16 +3151,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
                 sp_col[k] = (int)(sp_off[k] % h->ldn);
             }
             for (int64_t i = 0; i < h->M; ++i) sp_ptr[i + 1] += sp_ptr[i];
-            sc_ptr.assign(n + 1, 0);
-            for (int64_t k = 0; k < nnzS; ++k) sc_ptr[sp_col[k] + 1] += 1;
-            for (int64_t j = 0; j < n; ++j) sc_ptr[j + 1] += sc_ptr[j];
-            std::vector<int> fill(sc_ptr.begin(), sc_ptr.end() - 1);
-            sc_row.resize(nnzS); sc_pos.resize(nnzS);
-            for (int64_t k = 0; k < nnzS; ++k) {                          // stable: rows ascending inside a column
-                int q = fill[sp_col[k]]++;
-                sc_row[q] = (int)(sp_off[k] / h->ldn);
-                sc_pos[q] = (int)k;
-            }
+            csc_from_csr(sp_ptr, sp_col, n, sc_ptr, sc_row, sc_pos);
             h->sp_nnz = nnzS;
         }
     }
@@ -3043,24 +3233,14 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         for (int64_t i = 0; i < h->M; ++i) nE += h->rtype[i] == 0;
         h->ns_cap = h->sp_ok && nE >= NS_MIN_E && (double)(n - nE) <= NS_MAX_RATIO * (double)h->M && n <= h->Mp && h->M < (int64_t)1 << 30;
         if (h->ns_cap) {
-            h->ns_nE = nE; h->ns_nI = (int)(h->M - nE);
-            h->ns_nEp = (int)round_up(nE, 32); h->ns_nIp = (int)round_up(std::max(h->ns_nI, 1), 32);
-            h->ns_ldg = h->ldn + h->ns_nIp;
-            std::vector<int> eidx, epos(h->M, -1), iidx, ipos(h->M, -1);
-            for (int64_t i = 0; i < h->M; ++i) {
-                if (h->rtype[i] == 0) { epos[i] = (int)eidx.size(); eidx.push_back((int)i); }
-                else { ipos[i] = (int)iidx.size(); iidx.push_back((int)i); }
-            }
-            // the equality rows in reverse Cuthill-McKee order of their coupling graph: S0 = A_EF A_EF' and its factor are banded in that order
+            const NsLayout nlay(h->ldn, h->Mp, nE, h->M - nE);
+            h->ns_nE = nE; h->ns_nI = (int)nlay.nI;
+            h->ns_nEp = (int)nlay.nEp; h->ns_nIp = (int)nlay.nIp;
+            h->ns_ldg = nlay.ldg;
+            std::vector<int> eidx, epos, iidx, ipos;
             int s0_band = 0;
             std::vector<int> s0_pairs;
-            {
-                const std::vector<int> ord = rcm_order(eidx, sp_ptr, sp_col, h->ldn, &s0_band, &s0_pairs);
-                std::vector<int> e2(nE);
-                for (int q = 0; q < nE; ++q) e2[q] = eidx[ord[q]];
-                eidx.swap(e2);
-                for (int q = 0; q < nE; ++q) epos[eidx[q]] = q;
-            }
+            ns_index_lists(h->rtype.data(), h->M, sp_ptr, sp_col, h->ldn, eidx, epos, iidx, ipos, &s0_band, &s0_pairs);
             h->ns_eidx_h = eidx;
             P.upload(h->d_nsEidx, eidx.data(), nE, true); P.upload(h->d_nsEpos, epos.data(), h->M, true);
             P.upload(h->d_nsIidx, iidx.data(), h->ns_nI, true); P.upload(h->d_nsIpos, ipos.data(), h->M, true);
@@ -3073,9 +3253,9 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
                 P.upload(h->d_nsS0pairs, s0_pairs.data(), (int64_t)s0_pairs.size(), true);
             }
             P.zeroed(h->d_nsLt, (int64_t)h->ns_nEp * h->ns_nEp, s);
-            P.zeroed(h->d_nsth, h->ns_ldg, s);
+            P.zeroed(h->d_nsth, nlay.th_len(), s);
             P.zeroed(h->d_nsFm, h->ldn, s);
-            P.zeroed(h->d_nsv, 11 * h->ldn + 3 * h->Mp + 2 * h->ns_nEp, s);
+            P.zeroed(h->d_nsv, nlay.nsv_len(), s);
         }
     }
     // row order of the factorisations (see asm_handle::row_band)
@@ -4500,13 +4680,9 @@ int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t
         S.ipm_bind(ar);
         auto off = [&](const double* v) { return (int64_t)(((uintptr_t)v - (uintptr_t)ar.base) / sizeof(double)); };
         {
-            const IpmPtrs& P = S.P;
-            const double* vs[ASM_IPM_NVEC] = {P.q, P.lb, P.ub, P.r, P.w, P.slo, P.scoef, P.p, P.s, P.g, P.y, P.tL, P.tU, P.muL, P.muU, P.ts, P.mus, P.pi, P.act, P.aty, P.rp,
-                                              P.rdp, P.rds, P.thp_inv, P.ths_inv, P.dS, P.hp, P.hs, P.tmpn, P.t1, P.rhs, P.res, P.rcL, P.rcU, P.rcs, P.rcg,
-                                              S.dirA.dp, S.dirA.ds, S.dirA.dg, S.dirA.dy, S.dirA.dmuL, S.dirA.dmuU, S.dirA.dmus, S.dirA.dpi,
-                                              S.dirC.dp, S.dirC.ds, S.dirC.dg, S.dirC.dy, S.dirC.dmuL, S.dirC.dmuU, S.dirC.dmus, S.dirC.dpi,
-                                              S.d_sres, S.d_corr, S.d_pcg, S.d_tN};
-            const int64_t head[8] = {lay.ldn, lay.Mp, lay.nsp, lay.arena_len(), lay.snap_len(), lay.int_len(), SC_COUNT, off(P.scal)};
+            const double* vs[ASM_IPM_NVEC];
+            S.ipm_vectors(vs);
+            const int64_t head[8] = {lay.ldn, lay.Mp, lay.nsp, lay.arena_len(), lay.snap_len(), lay.int_len(), SC_COUNT, off(S.P.scal)};
             for (int k = 0; k < 8; ++k) layout_out[k] = head[k];
             for (int k = 0; k < ASM_IPM_NVEC; ++k) layout_out[8 + k] = off(vs[k]);
             if (layout_out[7] + SC_COUNT > lay.arena_len()) throw std::logic_error("asm_test_ipm_stages: the arena is shorter than its layout");
@@ -4798,6 +4974,193 @@ int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double s
         HIPCHK(asmb::sync(h->stream));
         HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHK(asmb::copy(int_inout, dI, nint * sizeof(int), hipMemcpyDeviceToHost));
+    });
+}
+
+// The kernels of a null-space interior-point iteration and of ns_finish_y (asm_ns_kernels.hip.h), one launch site per stage, through the
+// launch-site members of Solver / Dev and on buffers of the caller's laid out with the pitches of IpmLayout and NsLayout - see
+// include/asm_hip.h.  The CSC view and the index lists are made by the routines do_setup uses; the factor is what Dev::chol leaves in a buffer
+// of ns_alloc_factor.  Every size, offset and index is checked here before anything is launched.
+int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double scale_q, const int32_t* rtype, const int32_t* ptr, const int32_t* col, const double* vals,
+                       const double* Nreg, const double* N0, int64_t* layout_out, int32_t* idx_out, double* dbl_inout, int64_t ndbl, double* hscal_inout,
+                       uint32_t* hseq_inout, const asm_ns_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return guarded(h, [&] {
+        const int64_t LIM = (int64_t)1 << 20;
+        if (!layout_out || !rtype || n < 1 || M < 1 || n > LIM || M > LIM || k < 1 || k > n || k > ASM_SMALL_MAX || nstages < 0)
+            throw std::invalid_argument("asm_test_ns_stages: bad size");
+        int64_t nE = 0;
+        for (int64_t i = 0; i < M; ++i) {
+            if (rtype[i] < -1 || rtype[i] > 1) throw std::invalid_argument("asm_test_ns_stages: row type out of range");
+            nE += rtype[i] == 0;
+        }
+        HIPCHK(hipSetDevice(h->device));
+        const IpmLayout lay(n, M, 0);
+        const NsLayout nl(lay.ldn, lay.Mp, nE, M - nE);
+        Solver S(h);
+        S.lp.n = n; S.lp.M = M; S.lp.ns = 0; S.lp.scale_q = scale_q;
+        Solver::IpmArena ar;
+        ar.ln = lay.ldn; ar.lm = lay.Mp; ar.ls = lay.nsp;
+        ar.base = reinterpret_cast<double*>((uintptr_t)1 << 30);      // the layout, from pointers that are never dereferenced
+        S.ipm_bind(ar);
+        // the factor buffer as ns_alloc_factor sizes it for order k
+        const int64_t fld = round_up(k, 32), linv_len = (fld / ASM_NB + 1) * ASM_NB * ASM_NB, g_rows = k + 1;
+        const int64_t o_th = lay.arena_len(), o_v = o_th + nl.th_len(), o_G = o_v + nl.nsv_len(), o_S = o_G + g_rows * nl.ldg, o_Linv = o_S + fld * fld,
+                      o_N0 = o_Linv + linv_len, o_part = o_N0 + fld * fld, o_end = o_part + (int64_t)ASM_TMAXCHUNKS * lay.ldn;
+        {
+            const double* vs[ASM_IPM_NVEC];
+            S.ipm_vectors(vs);
+            const int64_t head[ASM_NS_LAYOUT_HEAD] = {lay.ldn, lay.Mp, nl.nEp, nl.nIp, nl.ldg, fld, nE, M - nE, o_end, SC_COUNT,
+                                                      (int64_t)(S.P.scal - ar.base), o_th, o_G, g_rows, o_S, o_Linv, linv_len, o_N0, o_part, ASM_SMALL_USE};
+            for (int q = 0; q < ASM_NS_LAYOUT_HEAD; ++q) layout_out[q] = head[q];
+            for (int q = 0; q < 16; ++q) layout_out[ASM_NS_LAYOUT_HEAD + q] = o_v + nl.nsv_off(q);
+            for (int q = 0; q < ASM_IPM_NVEC; ++q) layout_out[ASM_NS_LAYOUT_HEAD + 16 + q] = (int64_t)(vs[q] - ar.base);
+        }
+        if (!dbl_inout) return;      // layout query
+        if (!ptr || !col || !vals || !Nreg || !N0 || !idx_out || !hscal_inout || !hseq_inout || (nstages > 0 && (!stages || !grid_out)) || ndbl < o_end ||
+            ndbl > ((int64_t)1 << 28))
+            throw std::invalid_argument("asm_test_ns_stages: bad buffer");
+        if (nE < 1) throw std::invalid_argument("asm_test_ns_stages: the null-space form needs an equality row");
+        if (ptr[0] != 0) throw std::invalid_argument("asm_test_ns_stages: row pointers do not start at 0");
+        for (int64_t i = 0; i < M; ++i)
+            if (ptr[i] > ptr[i + 1]) throw std::invalid_argument("asm_test_ns_stages: row pointers decrease");
+        const int64_t nnz = ptr[M];
+        if (nnz > ((int64_t)1 << 26)) throw std::invalid_argument("asm_test_ns_stages: too many entries");
+        for (int64_t e = 0; e < nnz; ++e)
+            if (col[e] < 0 || col[e] >= n) throw std::invalid_argument("asm_test_ns_stages: column index out of range");
+        auto dspan = [&](int64_t off, int64_t len) {
+            if (off < 0 || len < 0 || off + len > ndbl) throw std::invalid_argument("asm_test_ns_stages: vector outside the double block");
+        };
+        bool factored = false;
+        for (int64_t q = 0; q < nstages; ++q) {
+            const asm_ns_stage& st = stages[q];
+            if (st.D < 0 || st.D > 1 || st.B < 0 || st.B > 1 || st.mode < 0 || st.mode > 1) throw std::invalid_argument("asm_test_ns_stages: direction selector or mode");
+            switch (st.kind) {
+            case ASM_NS_FACTOR: factored = true; break;
+            case ASM_NS_REDUCED_SOLVE: case ASM_NS_NEWTON:
+                if (!factored) throw std::invalid_argument("asm_test_ns_stages: a solve before ASM_NS_FACTOR");
+                break;
+            case ASM_NS_CHOL_SOLVE:
+                if (!factored) throw std::invalid_argument("asm_test_ns_stages: a solve before ASM_NS_FACTOR");
+                dspan(st.x[0], k); dspan(st.x[1], k);
+                break;
+            case ASM_NS_E0: dspan(st.x[0], lay.ldn); break;
+            case ASM_NS_ZT: dspan(st.x[0], lay.ldn); dspan(st.x[1], k); break;
+            case ASM_NS_GEMV_T: dspan(st.x[0], k); dspan(st.x[1], lay.ldn); break;
+            case ASM_NS_SYMV_RES: dspan(st.x[0], k); dspan(st.x[1], k); dspan(st.x[2], k); break;
+            case ASM_NS_ADD: dspan(st.x[0], st.len); dspan(st.x[1], st.len); dspan(st.x[2], st.len); break;
+            case ASM_NS_RELRES: dspan(st.x[0], k); dspan(st.x[1], k); break;
+            case ASM_NS_DP: dspan(st.x[0], lay.ldn); break;
+            case ASM_NS_DINF: dspan(st.x[0], k); break;
+            case ASM_NS_GATHER_E: dspan(st.x[0], M); dspan(st.x[1], nE); break;
+            case ASM_NS_SCATTER_E: dspan(st.x[0], nE); dspan(st.x[1], M); break;
+            case ASM_NS_ROWVEC_E: dspan(st.x[0], nE); dspan(st.x[1], M); break;
+            case ASM_NS_FILL: dspan(st.x[0], st.len); break;
+            default:
+                if (st.kind < 0 || st.kind >= ASM_NS_NKINDS) throw std::invalid_argument("asm_test_ns_stages: unknown stage");
+            }
+        }
+        // CSC view and index lists, by the routines of do_setup
+        std::vector<int> sp_ptr(ptr, ptr + M + 1), sp_col(col, col + nnz), sc_ptr, sc_row, sc_pos, eidx, epos, iidx, ipos;
+        csc_from_csr(sp_ptr, sp_col, n, sc_ptr, sc_row, sc_pos);
+        ns_index_lists((const int*)rtype, M, sp_ptr, sp_col, lay.ldn, eidx, epos, iidx, ipos, nullptr, nullptr);
+        {
+            int32_t* o = idx_out;
+            auto put = [&](const std::vector<int>& v) { for (int x : v) *o++ = x; };
+            put(sc_ptr); put(sc_row); put(sc_pos); put(eidx); put(epos); put(iidx); put(ipos);
+        }
+        // the generic buffers the factorisation and the wide substitutions use (pivot reference, flags, scratch), for order k
+        test_alloc(h, round_up(k, 64), 16);
+        std::vector<int> iv(lay.int_len(), -1);
+        for (int64_t i = 0; i < lay.Mp; ++i) iv[i] = i < M ? rtype[i] : 0;
+        iv[3 * lay.Mp] = 0;
+        // N0 as ns_newton_matrix stores it (lower triangle; mirrored for the one-workgroup solve), N into the lower triangle of the factor buffer
+        for (int64_t i = 0; i < k; ++i)
+            for (int64_t j = 0; j <= i; ++j) {
+                dbl_inout[o_N0 + i * fld + j] = N0[i * k + j];
+                if (k <= ASM_SMALL_USE) dbl_inout[o_N0 + j * fld + i] = N0[i * k + j];
+            }
+        std::vector<double> dg0(k);
+        for (int64_t i = 0; i < k; ++i) dg0[i] = N0[i * k + i];
+        double *dD = nullptr, *dV = nullptr, *hScal = nullptr, *dhScal = nullptr;
+        int *dI = nullptr, *dPtr = nullptr, *dCol = nullptr, *dCp = nullptr, *dCr = nullptr, *dCq = nullptr, *dE = nullptr, *dEp = nullptr, *dIi = nullptr, *dIp = nullptr;
+        unsigned *hSeq = nullptr, *dhSeq = nullptr;
+        BufPool tmp;
+        FacBuf fN;
+        ns_alloc_factor(h, tmp, fN, k);
+        fN.small = true;
+        if (fN.ld != fld) throw std::logic_error("asm_test_ns_stages: factor pitch");
+        tmp.upload(dD, dbl_inout, ndbl);
+        tmp.upload(dI, iv.data(), (int64_t)iv.size());
+        tmp.upload(dPtr, sp_ptr.data(), M + 1); tmp.upload(dCol, sp_col.data(), std::max<int64_t>(nnz, 1)); tmp.upload(dV, vals, std::max<int64_t>(nnz, 1));
+        tmp.upload(dCp, sc_ptr.data(), n + 1); tmp.upload(dCr, sc_row.data(), std::max<int64_t>(nnz, 1)); tmp.upload(dCq, sc_pos.data(), std::max<int64_t>(nnz, 1));
+        iidx.push_back(0);      // (never empty: an LP without inequality rows)
+        tmp.upload(dE, eidx.data(), nE); tmp.upload(dEp, epos.data(), M); tmp.upload(dIi, iidx.data(), (int64_t)iidx.size()); tmp.upload(dIp, ipos.data(), M);
+        tmp.alloc(hScal, 64, BufPool::MAPPED, &dhScal);
+        tmp.alloc(hSeq, 16, BufPool::MAPPED, &dhSeq);
+        std::memcpy(hScal, hscal_inout, SC_COUNT * sizeof(double));
+        *hSeq = *hseq_inout;
+        HIPCHK(asmb::copy(h->d_diag0, dg0.data(), k * sizeof(double), hipMemcpyHostToDevice));
+        for (int64_t i = 0; i < k; ++i)
+            HIPCHK(asmb::copy(fN.S + i * fld, Nreg + i * k, (i + 1) * sizeof(double), hipMemcpyHostToDevice));
+        ar.base = dD; ar.ibase = dI; ar.hscal = dhScal; ar.hseq = dhSeq;
+        S.ipm_bind(ar);
+        S.P.n = n; S.P.M = M; S.P.ns = 0; S.P.ncomp = std::max<int64_t>(1, 2 * n + (M - nE)); S.P.scale_q = scale_q;
+        Solver::NsArena na;
+        na.v = dD + o_v; na.th = dD + o_th; na.G = dD + o_G; na.N0 = dD + o_N0; na.partial = dD + o_part;
+        na.fN = &fN;
+        na.sp_ptr = dPtr; na.sp_col = dCol; na.sc_ptr = dCp; na.sc_row = dCr; na.sc_pos = dCq; na.vals = dV;
+        na.X.Eidx = dE; na.X.Epos = dEp; na.X.Iidx = dIi; na.X.Ipos = dIp; na.X.nE = (int)nE; na.X.nI = (int)(M - nE);
+        na.ldn = lay.ldn; na.Mp = lay.Mp; na.nEp = nl.nEp; na.nIp = nl.nIp; na.ldg = nl.ldg;
+        S.ns_bind(na);
+        S.ip.ns_k = (int)k;
+        const int kk = (int)k;
+        for (int64_t q = 0; q < nstages; ++q) {      // one after the other on the handle's stream, no host synchronisation in between
+            const asm_ns_stage& st = stages[q];
+            IpmDir& D = st.D ? S.dirC : S.dirA;
+            IpmDir& B = st.B ? S.dirC : S.dirA;
+            auto X = [&](int a) { return dD + st.x[a]; };
+            unsigned g = 0;
+            switch (st.kind) {
+            case ASM_NS_THETA: g = S.launch_theta_ns(st.rho_p); break;
+            case ASM_NS_FACTOR: S.dev.chol(fN, kk, 1e-14, false); break;
+            case ASM_NS_E0: g = S.launch_ns_e0(X(0), S.nsv(2)); break;
+            case ASM_NS_ZT: g = S.launch_ns_zt(X(0), X(1), kk); break;
+            case ASM_NS_GEMV_T: g = S.ns_gemv_t_dense(X(0), kk, X(1)); break;
+            case ASM_NS_E1: g = S.launch_ns_e1(S.nsv(2), S.nsv(3), S.nsv(14)); break;
+            case ASM_NS_WM_NEG: g = S.launch_ns_spmvn_wm_neg(S.ns_vals()); break;
+            case ASM_NS_KX: g = S.launch_ns_spmvt_kx(S.ns_vals()); break;
+            case ASM_NS_RHS1_BI: g = S.launch_ns_rhs1_bi(B, st.mode, st.res); break;
+            case ASM_NS_HT: g = S.launch_ns_spmvt_ht(S.ns_vals(), st.res); break;
+            case ASM_NS_RU: g = S.launch_ns_zt(S.nsv(3), S.nsv(10), kk); break;
+            case ASM_NS_REDUCED_SOLVE: g = S.ns_reduced_solve(kk); break;
+            case ASM_NS_DIRECTION: g = S.ns_direction(kk, D, st.res); break;
+            case ASM_NS_ROWS: g = S.launch_ns_spmvn_rows(S.ns_vals(), D); break;
+            case ASM_NS_NEWTON: S.ns_newton(st.mode, B, D); break;
+            case ASM_NS_CHOL_SOLVE: S.dev.chol_solve_dev(fN, X(0), X(1), kk); g = kk <= ASM_SMALL_USE ? 1u : 0u; break;
+            case ASM_NS_SYMV_RES: g = S.launch_ns_symv_res(kk, X(0), X(1), X(2)); break;
+            case ASM_NS_ADD: g = S.launch_ns_add(X(0), X(1), X(2), st.len); break;
+            case ASM_NS_RELRES: g = S.launch_ns_relres(X(0), X(1), kk); break;
+            case ASM_NS_DP: g = S.launch_ns_dp(D, st.res, X(0)); break;
+            case ASM_NS_UPDATE: g = S.launch_ns_update(D, st.al, st.be, st.es); break;
+            case ASM_NS_UPDATE_DEV: g = S.launch_ns_update_dev(D, st.eta, st.rerr); break;
+            case ASM_NS_DINF: g = S.launch_ns_dinf(X(0), kk, st.pub); break;
+            case ASM_NS_GATHER_E: g = S.launch_ns_gather_e(X(0), st.scale, X(1)); break;
+            case ASM_NS_SCATTER_E: g = S.launch_ns_scatter_e(X(0), X(1), st.add); break;
+            case ASM_NS_ROWVEC_E: g = S.launch_ns_rowvec_e(X(0), X(1)); break;
+            default: g = S.dev.launch_ns_fill(X(0), st.val, st.len);
+            }
+            grid_out[q] = g;
+        }
+        HIPCHK(asmb::sync(h->stream));
+        if (factored) {      // the factor and the inverses of its 64-wide diagonal blocks, as the factorisation left them
+            HIPCHK(asmb::copy(dD + o_S, fN.S, fld * fld * sizeof(double), hipMemcpyDeviceToDevice));
+            HIPCHK(asmb::copy(dD + o_Linv, fN.Linv, linv_len * sizeof(double), hipMemcpyDeviceToDevice));
+        }
+        HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
+        std::memcpy(hscal_inout, hScal, SC_COUNT * sizeof(double));
+        *hseq_inout = *hSeq;
+        S.dev.resolve_timing();
+        check_panel_timeout(h);
     });
 }
 

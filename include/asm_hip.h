@@ -609,6 +609,75 @@ typedef struct asm_as_stage {
 int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double scale_q, int64_t* layout_out, double* dbl_inout, int64_t ndbl,
                        int32_t* int_inout, int64_t nint, const double* Ah, int64_t ah_rows, const asm_as_stage* stages, int64_t nstages,
                        uint32_t* grid_out);
+/* Test hook: the kernels of one null-space interior-point iteration and of ns_finish_y (asm_ns_kernels.hip.h), one launch site per stage with
+ * the solver's own launch geometry, on a state the caller supplies.  An LP with n columns and M rows (row types rtype: 0 = hard equality row,
+ * at least one; no slack columns, as the form requires) and a null-space basis of k rows, 1 <= k <= n, k <= 1024.  One double block holds, in
+ * this order: the interior-point arena (as for asm_test_ipm_stages with ns = 0) | theta~ (ldg = ldn + nIp) | the sixteen work vectors of the
+ * form at the offsets the solver computes (0 dpbar, 1 K dpbar, 2 h~ / d0, 3 v / Z Zt d0, 5 yM, 7 bI, 10 ru, 11 du, 12 rr, 13 dd, 14 e) | Gt =
+ * [Zt | GI'] (k + 1 rows of pitch ldg; the last row is never used) | the factor (fld x fld, fld = k rounded up to 32) | the inverses of its
+ * 64-wide diagonal blocks | the unregularised N0 (fld x fld) | the scratch of Zt' u on the multi-launch path | any vectors of the caller's that
+ * stages name by offset.  nEp = nE rounded up to 32, nIp = max(nI, 1) rounded up to 32.  layout_out (ASM_NS_LAYOUT_LEN) receives: ldn, Mp,
+ * nEp, nIp, ldg, fld, nE, nI, length of the block, number of scalars, offset of the scalar block, of theta~, of Gt, rows of Gt, offset of the
+ * factor, of the block inverses, their length, offset of N0, of the scratch, the largest order solved in one workgroup (ASM_SMALL_USE); then the
+ * offsets of the sixteen work vectors; then those of the ASM_IPM_NVEC arena vectors in the order of asm_test_ipm_stages.  With dbl_inout ==
+ * NULL the call only reports the layout (rtype is read, the matrix is not).
+ *   ptr, col, vals  the LP matrix as CSR (M + 1 pointers, columns < n).  The hook makes the CSC view and the index lists with the routines
+ *              asm_sublp_setup uses and returns them in idx_out: sc_ptr (n + 1) | sc_row | sc_pos (nnz each) | Eidx (nE) | Epos (M) | Iidx (nI) |
+ *              Ipos (M).
+ *   Nreg, N0   the regularised and the unregularised reduced matrix, dense k x k.  N0 is stored into the block as the solver's build stores it
+ *              (lower triangle; mirrored into the upper one for k <= ASM_SMALL_USE).  ASM_NS_FACTOR factors Nreg in a buffer of the null-space
+ *              form's kind with the pivot reference diag(N0), as Solver::ns_iter_setup does; the factor and its block inverses are returned in
+ *              the block (what the block held there on entry is ignored).
+ *   hscal_inout (number of scalars), hseq_inout (1): the host-mapped copy of the scalar block and its sequence word, in and out.
+ *   stages     run in order on the handle's stream with no host synchronisation in between; grid_out[q] = workgroups of stage q (composite
+ *              stages: of their first kernel of asm_ns_kernels.hip.h; 0 where none applies).
+ * Checked before the first launch (ASM_ERR_ARG otherwise): the sizes, row types (-1 .. 1), CSR pointers (from 0, not decreasing), columns (< n),
+ * every offset and length against the block, selectors, and that a stage that solves comes after ASM_NS_FACTOR in the same call. */
+enum {
+    ASM_NS_THETA = 0,         /* k_ipm_theta_ns; rho_p */
+    ASM_NS_FACTOR,            /* Dev::chol(fN, k, 1e-14, no explicit inverse) */
+    ASM_NS_E0,                /* k_ns_e0: pbar = x[0] (ldn) -> work vector 2 */
+    ASM_NS_ZT,                /* gemv_rows: x[1] (k) = Zt x[0] (ldn) */
+    ASM_NS_GEMV_T,            /* Solver::ns_gemv_t_dense: x[1] (ldn) = Zt' x[0] (k); k_gemv_t_small, or k_gemv_t_stage1 / 2 above ASM_SMALL_USE */
+    ASM_NS_E1,                /* k_ns_e1: work vectors 2, 3 -> e */
+    ASM_NS_WM_NEG,            /* k_ns_spmvn_wm_neg */
+    ASM_NS_KX,                /* k_ns_spmvt_kx */
+    ASM_NS_RHS1_BI,           /* k_ns_rhs1_bi; mode, B = base direction, res */
+    ASM_NS_HT,                /* k_ns_spmvt_ht; res */
+    ASM_NS_RU,                /* gemv_rows: ru = Zt v */
+    ASM_NS_REDUCED_SOLVE,     /* Solver::ns_reduced_solve: k_ns_reduced_solve, or chol_solve_dev / k_ns_symv_res / k_ns_add / k_ns_relres above ASM_SMALL_USE */
+    ASM_NS_DIRECTION,         /* Solver::ns_direction: k_gemv_t_small_dp, or ns_gemv_t_dense + k_ns_dp; D, res */
+    ASM_NS_ROWS,              /* k_ns_spmvn_rows; D */
+    ASM_NS_NEWTON,            /* Solver::ns_newton(mode, B, D): the six stages above in one */
+    ASM_NS_CHOL_SOLVE,        /* Dev::chol_solve_dev on the factor: x[1] = N^-1 x[0] (k each); k_small_solve up to ASM_SMALL_USE */
+    ASM_NS_SYMV_RES,          /* k_ns_symv_res: x[2] = x[1] - N0 x[0] (k each) */
+    ASM_NS_ADD,               /* k_ns_add: x[2] = x[0] + x[1] (len) */
+    ASM_NS_RELRES,            /* k_ns_relres: r = x[0], rhs = x[1] (k each) into scalar NSERR */
+    ASM_NS_DP,                /* k_ns_dp; D, res, zu = x[0] (ldn) */
+    ASM_NS_UPDATE,            /* k_ns_update; D, al, be, es */
+    ASM_NS_UPDATE_DEV,        /* k_ns_update_dev; D, eta, rerr */
+    ASM_NS_DINF,              /* k_ns_dinf: zr = x[0] (k); pub */
+    ASM_NS_GATHER_E,          /* k_ns_gather_e: x[1] (nE) = scale * x[0][Eidx] (M) */
+    ASM_NS_SCATTER_E,         /* k_ns_scatter_e: x[1][Eidx] (M) = (add ? x[1][Eidx] : 0) + x[0] (nE) */
+    ASM_NS_ROWVEC_E,          /* k_ns_rowvec_e: x[1] (M) from x[0] (nE) */
+    ASM_NS_FILL,              /* k_ns_fill: x[0][0:len] = val */
+    ASM_NS_NKINDS
+};
+#define ASM_NS_LAYOUT_HEAD 20
+#define ASM_NS_LAYOUT_LEN (ASM_NS_LAYOUT_HEAD + 16 + ASM_IPM_NVEC)
+typedef struct asm_ns_stage {
+    int32_t kind;                 /* ASM_NS_* */
+    int32_t mode, add;
+    int32_t D, B;                 /* 0 = dirA, 1 = dirC */
+    uint32_t pub;
+    double rho_p, res, al, be, es, eta, rerr, scale, val;
+    int64_t x[4];                 /* offsets into dbl_inout */
+    int64_t len;
+} asm_ns_stage;
+int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double scale_q, const int32_t* rtype, const int32_t* ptr,
+                       const int32_t* col, const double* vals, const double* Nreg, const double* N0, int64_t* layout_out, int32_t* idx_out,
+                       double* dbl_inout, int64_t ndbl, double* hscal_inout, uint32_t* hseq_inout, const asm_ns_stage* stages,
+                       int64_t nstages, uint32_t* grid_out);
 int asm_test_cholesky(asm_handle* h, const double* S /* N*N sym */, int64_t N, double* L_out /* N*N lower */);
 int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x);
 /* the bounded wait of the dataflow panel kernel with a producer that never publishes: returns ASM_ERR_HIP (reported once), the

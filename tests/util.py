@@ -2140,3 +2140,317 @@ def as_chain_errors(st0, A, fin, mode, p_ref, y_ref):
         err = float(np.abs(c - a).max())
         out[nm] = (err, d_self, err / allow if allow > 0 else (0.0 if err == 0 else np.inf))
     return out, lp, sets
+
+
+# ---- the kernels of a null-space interior-point iteration (asm_ns_kernels.hip.h; tests/test_ns_stages_*.py).  Twins as above: name -> (value in
+# long double, magnitude, k).  A sum of L products carries k = L + 2 (one rounding per product, at most L - 1 per partial sum in any order, one
+# spare), plus one per further operation of the statement.  Statements of one operation are exact: float64 NumPy, bit for bit.
+NS_STAGE_KINDS = ("theta", "factor", "e0", "zt", "gemv_t", "e1", "wm_neg", "kx", "rhs1_bi", "ht", "ru", "reduced_solve", "direction", "rows", "newton",
+                  "chol_solve", "symv_res", "add", "relres", "dp", "update", "update_dev", "dinf", "gather_e", "scatter_e", "rowvec_e", "fill")
+NS_VEC = {"dpb": 0, "kdpb": 1, "ht": 2, "v": 3, "yM": 5, "bI": 7, "ru": 10, "du": 11, "rr": 12, "dd": 13, "e": 14}      # Solver::nsv numbers
+NS_COL_COUNTS = (1, 7, 8, 9, 17, 0, 3, 2, 5, 4)      # entries per column, dealt in turn: eight lanes per column in k_ns_spmvt_*; 17 = three sweeps with a tail
+NS_SMALL_USE = 256
+
+
+def ns_state(seed, n, M, k, nI, mu=1.0, orth=True):
+    """An equality-rich sparse LP state without slack columns (ipm_state with ns = 0) for the null-space form: nI inequality rows of both signs,
+    the others hard equalities; columns 0 and n - 1 among the fixed ones; a sparse matrix with one empty row, one empty column (5) and column
+    lengths NS_COL_COUNTS (column n - 2, the last free one, has 7; the fixed column n - 1 is not empty); Zt with k orthonormal rows that are zero on the fixed columns (for k above the number of
+    free columns no such matrix exists: the rows beyond it are random unit vectors - the kernels treat Zt as a dense operand); GI' = (A_I Z)';
+    N0 = Zt Th Zt' + GI' D_I^-1 GI from the state's own theta~, N = N0 with the diagonal regularised as k_ns_reduce_lower does."""
+    rng = np.random.default_rng(seed)
+    st = ipm_state(seed, n, M, 0, mu)
+    assert 0 <= nI < M and 1 <= k <= n
+    rt = np.zeros(M, np.int32)
+    rows_i = np.sort(rng.permutation(M)[:nI])
+    rt[rows_i] = np.where(rng.random(nI) < 0.5, 1, -1)
+    st["rtype"] = rt
+    eq = rt == 0
+    t = 10.0 ** rng.uniform(-6, 2, M)
+    st["g"], st["pi"] = np.where(eq, 1.0, t), np.where(eq, 0.0, mu / t * 10.0 ** rng.uniform(-1, 1, M))
+    st["y"] = np.where(eq, st["y"], rt * st["pi"])
+    fx = st["ub"] == st["lb"]
+    fx[0] = fx[n - 1] = True
+    if n >= 3 and fx[n - 2]:      # the last free column is n - 2: its eight-lane sum reaches an output (a fixed column is written as 0 whatever the sum)
+        fx[n - 2] = False
+        st["ub"][n - 2] = st["lb"][n - 2] + 3.0
+        st["tL"][n - 2] = st["tU"][n - 2] = 0.5
+        st["muL"][n - 2] = st["muU"][n - 2] = 2.0 * mu
+        st["thp_inv"][n - 2] = 0.25
+    st["ub"] = np.where(fx, st["lb"], st["ub"])
+    st["tL"][fx] = st["tU"][fx] = 1.0
+    st["muL"][fx] = st["muU"][fx] = 0.0
+    st["thp_inv"][fx] = 0.0
+    st["ncomp"] = max(2 * int((~fx).sum()) + nI, 1)
+    A = np.zeros((M, n))
+    empty_row = M // 2
+    rows = np.array([i for i in range(M) if i != empty_row])
+    for j in range(n):
+        c = 7 if j == n - 2 else (0 if j == 5 else min(max(NS_COL_COUNTS[j % len(NS_COL_COUNTS)], 1 if j == n - 1 else 0), len(rows)))
+        A[rng.choice(rows, c, replace=False), j] = rng.standard_normal(c)
+    st["A"] = A
+    ptr, col, vals = [0], [], []
+    for i in range(M):
+        nz = np.flatnonzero(A[i])
+        col += list(nz); vals += list(A[i, nz]); ptr.append(len(col))
+    st["ptr"], st["col"], st["vals"] = np.array(ptr, np.int32), np.array(col, np.int32), np.array(vals)
+    st["E"], st["I"] = np.flatnonzero(eq), np.flatnonzero(~eq)
+    fr = np.flatnonzero(~fx)
+    kk = min(k, len(fr))
+    Zt = np.zeros((k, n))
+    Zt[:kk, fr] = np.linalg.qr(rng.standard_normal((len(fr), kk)))[0].T
+    for c in range(kk, k):
+        z = rng.standard_normal(len(fr))
+        Zt[c, fr] = z / np.linalg.norm(z)
+    st["k"], st["Zt"] = k, Zt
+    st["GI"] = (A[st["I"]] @ Zt.T).T.copy()                       # k x nI
+    th = ns_theta_exact(st, IPM_RHO_P)
+    st["th"], st["thI"] = th["th"], th["thI"]
+    st["N0"], st["N"] = ns_reduced_matrix(st)
+    for nm in NS_VEC:
+        st[nm] = rng.standard_normal(M if nm in ("yM", "bI") else n)
+    for nm in ("ru", "du", "rr", "dd"):
+        st[nm] = st[nm][:k].copy()
+    st["e"][fx] = 0.0
+    st["pbar"] = np.where(fx, st["lb"], rng.standard_normal(n))
+    st["scal"][SC["NSERR"]] = 0.0
+    return st
+
+
+def ns_reduced_matrix(st):
+    """(N0, N) of the state's theta~ in long double, rounded: N0 = Zt Th Zt' + GI' D_I^-1 GI, N = N0 with N_ii += 1e-13 N_ii + 1e-30."""
+    Zt, GI = st["Zt"].astype(LD), st["GI"].astype(LD)
+    N0 = np.asarray((Zt * st["th"].astype(LD)) @ Zt.T + (GI * st["thI"].astype(LD)) @ GI.T, np.float64)
+    N0 = 0.5 * (N0 + N0.T)
+    N = N0.copy()
+    d = np.arange(len(N0))
+    N[d, d] = N0[d, d] + (1e-13 * N0[d, d] + 1e-30)
+    return N0, N
+
+
+def ns_theta_exact(st, rho_p):
+    """theta~ of k_ipm_theta_ns in float64 (quotients and plain sums in the kernel's order: nothing to contract): the column part (zero on
+    fixed columns) and 1 / dS by position in I; with it k_ipm_theta's own outputs (ipm_theta_exact)."""
+    fr = _free(st)
+    with np.errstate(all="ignore"):
+        th = np.where(fr, st["muL"] / st["tL"] + st["muU"] / st["tU"] + rho_p, 0.0)
+        I = np.flatnonzero(st["rtype"] != 0)
+        thI = 1.0 / (st["g"][I] / st["pi"][I])
+    out = ipm_theta_exact(st, rho_p)
+    out.update(th=th, thI=thI)
+    return out
+
+
+def _rows_dot(st, x):
+    """Row sums of A x over the stored entries: (value, magnitude, entries) per row."""
+    A, x = st["A"].astype(LD), np.asarray(x, LD)
+    return A @ x, np.abs(A) @ np.abs(x), np.diff(st["ptr"]).astype(np.int64)
+
+
+def _cols_dot(st, y):
+    A, y = st["A"].astype(LD), np.asarray(y, LD)
+    return A.T @ y, np.abs(A).T @ np.abs(y), (st["A"] != 0).sum(0).astype(np.int64)
+
+
+def _at_I(st, vI, fill=0):
+    """An M-vector with vI on the inequality rows (by position in I), `fill` on the equality rows."""
+    out = np.full(st["M"], fill, LD)
+    out[st["I"]] = vI
+    return out
+
+
+def tw_ns_wm_neg(st):
+    """dpbar = -e and *clear = 0 (exact), wM = D_I^-1 (A dpbar) on the inequality rows, zero on the equality rows."""
+    a, m, L = _rows_dot(st, -st["e"])
+    thI = _at_I(st, st["thI"].astype(LD))
+    return {"dpb": -st["e"], "NSERR": 0.0, "yM": (thI * a, thI * m, L + 3)}
+
+
+def tw_ns_kx(st):
+    """K dpbar = Th dpbar + A' yM on the free columns (th != 0), zero elsewhere."""
+    a, m, L = _cols_dot(st, st["yM"])
+    th, x = _l(st, "th", "dpb")
+    on = st["th"] != 0
+    return {"kdpb": (np.where(on, th * x + a, 0), np.where(on, np.abs(th * x) + m, 0), L + 4)}
+
+
+def tw_ns_rhs1_bi(st, base, mode, res, dev):
+    """k_ipm_rhs1's complementarity right-hand sides (tw_rhs1, ns = 0), then from the device's own rcg: bI = -res rp + sg rcg / pi and, from
+    the device's bI, yM = D_I^-1 bI (one product: exact) on the inequality rows; both zero on the equality rows."""
+    out = tw_rhs1(st, base, mode, dev=dev)
+    out.pop("rcs", None); out.pop("hs", None)
+    ineq = st["rtype"] != 0
+    rp, pi = _l(st, "rp", "pi")
+    rcg = dev["rcg"].astype(LD)
+    with np.errstate(all="ignore"):
+        q = np.where(ineq, st["rtype"] * rcg / np.where(ineq, pi, 1), 0)
+    out["bI"] = (np.where(ineq, -LD(res) * rp + q, 0), np.where(ineq, abs(res) * np.abs(rp) + np.abs(q), 0), 5)
+    out["yM_exact"] = np.where(ineq, np.asarray(_at_I(st, st["thI"].astype(LD)), np.float64) * dev["bI"], 0.0)
+    return out
+
+
+def tw_ns_ht(st, res, dev):
+    """h~ = hp + A' yM on the free columns, and from the device's own h~: v = h~ - res K dpbar; zero on fixed columns."""
+    a, m, L = _cols_dot(st, st["yM"])
+    hp, kd = _l(st, "hp", "kdpb")
+    on = st["th"] != 0
+    h = dev["ht"].astype(LD)
+    return {"ht": (np.where(on, hp + a, 0), np.where(on, np.abs(hp) + m, 0), L + 3),
+            "v": (np.where(on, h - LD(res) * kd, 0), np.where(on, np.abs(h) + abs(res) * np.abs(kd), 0), 3)}
+
+
+def tw_ns_zt(st, x):
+    """Zt x: k sums of n products."""
+    Z, x = st["Zt"].astype(LD), np.asarray(x, LD)
+    return (Z @ x, np.abs(Z) @ np.abs(x), st["n"] + 2)
+
+
+def tw_ns_gemv_t(st, u):
+    """Zt' u: n sums of k products (k_gemv_t_small, or the two-stage kernels: any association)."""
+    Z, u = st["Zt"].astype(LD), np.asarray(u, LD)
+    return (Z.T @ u, np.abs(Z).T @ np.abs(u), st["k"] + 2)
+
+
+def tw_ns_symv_res(N0, x, rhs):
+    N0, x, rhs = np.asarray(N0, LD), np.asarray(x, LD), np.asarray(rhs, LD)
+    return (rhs - N0 @ x, np.abs(rhs) + np.abs(N0) @ np.abs(x), len(x) + 3)
+
+
+def ns_relres_exact(prev, r, rhs):
+    """max(prev, max|r| / max(1, max|rhs|)): maxima and one quotient, exact; a NaN entry is dropped by the maxima (fmax), as by Python's max()."""
+    a = float(np.fmax.reduce(np.abs(r), initial=0.0))
+    b = float(np.fmax.reduce(np.abs(rhs), initial=1.0))
+    return float(np.fmax(prev, a / b))
+
+
+def tw_ns_dp(st, D, res, dev, zu=None):
+    """dp = res dpbar + Z du on the free columns (zu given: the product is an input, k_ns_dp), and from the device's own dp the bound
+    multipliers' directions; zeros on the fixed columns."""
+    on = st["th"] != 0
+    dpb, rcL, rcU, muL, muU, tL, tU = _l(st, "dpb", "rcL", "rcU", "muL", "muU", "tL", "tU")
+    if zu is None:
+        a, m, kk = tw_ns_gemv_t(st, st["du"])
+    else:
+        a, m, kk = np.asarray(zu, LD), np.abs(np.asarray(zu, LD)), 1
+    dp = dev[D + ".dp"].astype(LD)
+    return {D + ".dp": (np.where(on, LD(res) * dpb + a, 0), np.where(on, abs(res) * np.abs(dpb) + m, 0), kk + 2),
+            D + ".dmuL": (np.where(on, (rcL - muL * dp) / tL, 0), np.where(on, (np.abs(rcL) + np.abs(muL * dp)) / tL, 0), 4),
+            D + ".dmuU": (np.where(on, (rcU + muU * dp) / tU, 0), np.where(on, (np.abs(rcU) + np.abs(muU * dp)) / tU, 0), 4)}
+
+
+def tw_ns_rows(st, D, dev):
+    """aM = A dp; on the inequality rows dy = D_I^-1 (bI - aM), wM = D_I^-1 aM, and from the device's own dy: dpi = sg dy (exact),
+    dg = (rcg - g dpi) / pi; zeros on the equality rows."""
+    a, m, L = _rows_dot(st, st[D + ".dp"])
+    ineq = st["rtype"] != 0
+    thI = _at_I(st, st["thI"].astype(LD))
+    bI, rcg, g, pi = _l(st, "bI", "rcg", "g", "pi")
+    dpi = dev[D + ".dpi"].astype(LD)
+    with np.errstate(all="ignore"):
+        dg = np.where(ineq, (rcg - g * dpi) / np.where(ineq, pi, 1), 0)
+        mg = np.where(ineq, (np.abs(rcg) + np.abs(g * dpi)) / np.where(ineq, pi, 1), 0)
+    return {D + ".dy": (thI * (bI - a), thI * (np.abs(bI) + m), L + 4), "yM": (thI * a, thI * m, L + 3), D + ".dg": (dg, mg, 4),
+            D + ".dpi_exact": np.where(ineq, st["rtype"] * dev[D + ".dy"], 0.0)}
+
+
+def tw_ns_update(st, C, al, be, es, dev):
+    """k_ipm_update (tw_update, ns = 0) and e *= es (one product: exact)."""
+    out = tw_update(st, C, al, be, dev)
+    for nm in ("s", "ts", "mus"):
+        out.pop(nm)
+    out["e_exact"] = st["e"] * es
+    return out
+
+
+def ns_ld_chol_solve(L, Linv, b):
+    """(L L')^-1 b in long double from the factor as returned.  Linv (the inverses of the 64-wide diagonal blocks) is what the one-workgroup
+    solve multiplies by; in exact arithmetic that is the substitution with L's diagonal blocks, which is what is computed here."""
+    L = np.tril(np.asarray(L, LD))
+    return _ld_trsv(L.T, _ld_trsv(L, np.asarray(b, LD), True), False)
+
+
+def _ld_trsv(T, b, lower):
+    k = len(b)
+    x = np.zeros(k, LD)
+    for i in (range(k) if lower else range(k - 1, -1, -1)):
+        x[i] = (b[i] - T[i] @ x) / T[i, i]
+    return x
+
+
+def tw_ns_reduced_solve(Lf, N0, ru, dtype=LD):
+    """The reduced solve as the kernels state it (oracle: solve_ns): du = N^-1 ru through the factor, one refinement sweep on N0, and the
+    relative residual.  dtype float64: the same algorithm in plain NumPy (the measured allowance of the test)."""
+    if dtype is LD:
+        solve = lambda b: ns_ld_chol_solve(Lf, None, b)
+    else:
+        from scipy.linalg import solve_triangular
+        Lt = np.tril(Lf)
+        solve = lambda b: solve_triangular(Lt.T, solve_triangular(Lt, b, lower=True), lower=False)
+    N0, ru = np.asarray(N0, dtype), np.asarray(ru, dtype)
+    du = solve(ru)
+    du = du + solve(ru - N0 @ du)
+    return du, ru - N0 @ du
+
+
+def ns_twin_iteration(lp, st, nsp, ns_e):
+    """One iteration of oracle IPM.run in null-space form from the twin's stages, every stage the float64 rounding of its long-double value; the
+    reduced solve in long double on the oracle's guarded factor of the twin's own N.  st as ipm_twin_start makes it, with A, ptr, col, Zt,
+    GI, E, I, k of the oracle's basis `nsp`.  Returns (pinf, dinf, mu, ap, ad, nserr) and the new e."""
+    from oracle import lp_solver as O
+    A = lp.A
+    st["act"], st["aty"] = A @ st["p"], A.T @ st["y"]
+    _f(tw_measures(st), st, ["rp", "rdp", "rds", "MU"])
+    for nm, v in ipm_measures_exact(st, st["rp"], st["rdp"], st["rds"]).items():
+        st["scal"][SC[nm]] = v
+    zr = np.asarray(tw_ns_zt(st, st["rdp"])[0], np.float64)
+    st["scal"][SC["DINF"]] = float(np.abs(zr).max(initial=0.0)) / st["scale_q"]
+    pinf, dinf, mu = st["scal"][SC["PINF"]], st["scal"][SC["DINF"]], st["scal"][SC["MU"]]
+    th = ns_theta_exact(st, IPM_RHO_P)
+    st.update(th)
+    st["N0"], st["N"] = ns_reduced_matrix(st)
+    Lf = O.chol_guard(st["N"].copy(), np.diag(st["N0"]).copy())
+    if ns_e is None:
+        d0 = np.where(_free(st), st["p"] - nsp.pbar, 0.0)
+        zz = np.asarray(tw_ns_gemv_t(st, np.asarray(tw_ns_zt(st, d0)[0], np.float64))[0], np.float64)
+        ns_e = np.where(_free(st), d0 - zz, 0.0)
+    st["e"] = ns_e
+    t = tw_ns_wm_neg(st)
+    st["dpb"], st["yM"], nserr = t["dpb"], np.asarray(t["yM"][0], np.float64), 0.0
+    _f(tw_ns_kx(st), st, ["kdpb"])
+
+    def newton(mode, base, D):
+        nonlocal nserr
+        _f(tw_rhs1(st, base, mode), st, ["rcL", "rcU", "rcg"])
+        _f(tw_rhs1(st, base, mode, dev=dict(st, hp=st["hp"])), st, ["hp"])
+        _f(tw_ns_rhs1_bi(st, base, mode, 1.0, dict(st)), st, ["bI"])
+        st["yM"] = tw_ns_rhs1_bi(st, base, mode, 1.0, dict(st))["yM_exact"]
+        _f(tw_ns_ht(st, 1.0, dict(st)), st, ["ht"])
+        _f(tw_ns_ht(st, 1.0, dict(st)), st, ["v"])
+        st["ru"] = np.asarray(tw_ns_zt(st, st["v"])[0], np.float64)
+        du, rr = tw_ns_reduced_solve(Lf, st["N0"], st["ru"])
+        st["du"] = np.asarray(du, np.float64)
+        rr = np.asarray(tw_ns_symv_res(st["N0"], st["du"], st["ru"])[0], np.float64)
+        nserr = ns_relres_exact(nserr, rr, st["ru"])
+        _f(tw_ns_dp(st, D, 1.0, dict(st)), st, [D + ".dp"])
+        _f(tw_ns_dp(st, D, 1.0, dict(st)), st, [D + ".dmuL", D + ".dmuU"])
+        _f(tw_ns_rows(st, D, dict(st)), st, [D + ".dy"])
+        st[D + ".dpi"] = tw_ns_rows(st, D, dict(st))[D + ".dpi_exact"]
+        t2 = tw_ns_rows(st, D, dict(st))
+        st[D + ".dg"], st["yM"] = np.asarray(t2[D + ".dg"][0], np.float64), np.asarray(t2["yM"][0], np.float64)
+
+    def steps(D):
+        e_ = ipm_steps_exact(st, D)
+        st["scal"][SC["AP"]], st["scal"][SC["AD"]] = e_["AP"], e_["AD"]
+        return e_["AP"], e_["AD"]
+    newton(0, "A", "A")
+    steps("A")
+    _f(tw_muaff(st, "A", 3), st, ["SM"])
+    newton(1, "A", "C")
+    ap, ad = steps("C")
+    eta = 0.995 if mu >= 1.0 else min(max(0.995, 1.0 - mu / st["scale_q"]), 0.999999)
+    al, be = min(1.0, eta * ap), min(1.0, eta * ad)
+    new_pi = np.asarray(tw_update(st, "C", al, be, {"pi": st["pi"]})["pi"][0], np.float64)
+    tu = tw_ns_update(st, "C", al, be, 1.0 - al, {"pi": new_pi})
+    _f(tu, st)
+    st["scal"][SC["NSERR"]] = nserr
+    return (pinf, dinf, mu, ap, ad, nserr), tu["e_exact"]
