@@ -125,6 +125,9 @@ PROTOTYPES = {
     "asm_batch_set_ns_basis": (C.c_int, [_P, _I32, C.c_int64]),
     "asm_batch_set_scenario_data": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _D]),
     "asm_batch_data_gradient": (C.c_int, [_P, C.c_int64, _D, _D, _D]),
+    "asm_batch_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
+    "asm_batch_hessian_lagrangian": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D]),
+    "asm_batch_hessian_product": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D]),
     "asm_batch_ns_basis": (C.c_int, [_P, _I32, _I64]),
     "asm_batch_sublp_solve": (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _I32, _D, _D, _D, _D, _D, _I32]),
     "asm_batch_slp_run": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), _D, _D, _D, _D, _D, C.POINTER(SlpResult)]),

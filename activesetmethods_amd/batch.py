@@ -113,12 +113,10 @@ class HipBatch:
         import ctypes as C
         from . import _lib
         from .subproblem import AsmHipError
-        from .moi_evaluator import nlp_kind
         self._lib, self._C, self._err = _lib.load(), C, AsmHipError
-        fm = getattr(problem, "function_model", None)
-        if fm is None:
+        if getattr(problem, "function_model", None) is None:
             raise ValueError("HipBatch needs a problem built from a FunctionModel (the batch evaluates on the device)")
-        self.n, self.m, self.n_slots = int(problem.n), int(problem.m), int(n_slots)
+        self.n_slots = int(n_slots)
         self._b = C.c_void_p()
         rc = self._lib.asm_batch_create(int(device), int(n_slots), C.byref(self._b))
         if rc != 0:
@@ -126,6 +124,17 @@ class HipBatch:
         if groups is not None:
             self._check(self._lib.asm_batch_set_groups(self._b, int(groups)))
         self.groups = int(self._lib.asm_batch_groups(self._b))
+        self.setup(problem)
+
+    def setup(self, problem):
+        """asm_batch_setup + asm_batch_eval_setup with `problem` (built from a FunctionModel) for every slot; on an existing batch: another
+        model on the same slots (a scenario data table, the basis columns and the Hessian lists of the earlier model are dropped)."""
+        from . import _lib
+        from .moi_evaluator import nlp_kind
+        fm = getattr(problem, "function_model", None)
+        if fm is None:
+            raise ValueError("HipBatch needs a problem built from a FunctionModel (the batch evaluates on the device)")
+        self.n, self.m = int(problem.n), int(problem.m)
         f64 = lambda a: np.ascontiguousarray(a, np.float64)
         jr, jc = np.ascontiguousarray(problem.j_row, np.int64), np.ascontiguousarray(problem.j_col, np.int64)
         gl, gu, xl, xu = map(f64, (problem.g_L, problem.g_U, problem.x_L, problem.x_U))
@@ -251,6 +260,57 @@ class HipBatch:
         self._check(self._lib.asm_batch_data_gradient(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(out)))
         return out[:, :self.n_dpar]
 
+    def hessian_structure(self):
+        """asm_batch_hessian_structure: the pattern (rows, cols) of the Hessian of the Lagrangian, 1-based int64, the same for every scenario
+        (an off-diagonal entry stands for both symmetric positions, duplicates add)."""
+        from . import _lib
+        nnz = self._C.c_int64(0)
+        self._check(self._lib.asm_batch_hessian_structure(self._b, self._C.byref(nnz), None, None))
+        rows, cols = np.zeros(max(int(nnz.value), 1), np.int64), np.zeros(max(int(nnz.value), 1), np.int64)
+        self._check(self._lib.asm_batch_hessian_structure(self._b, self._C.byref(nnz), _lib.i64ptr(rows), _lib.i64ptr(cols)))
+        return rows[:int(nnz.value)], cols[:int(nnz.value)]
+
+    def _hessian_args(self, x, obj_factor, lam, v=None):
+        """x [n_scen x n], lam [n_scen x m], obj_factor (scalar or [n_scen]) and v [n_scen x n] as contiguous float64 arrays; ValueError for
+        shapes that do not fit the batch."""
+        x = np.ascontiguousarray(x, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.n or x.shape[0] < 1:
+            raise ValueError("x has shape %r, expected [n_scen x %d] with at least one scenario" % (x.shape, self.n))
+        S = x.shape[0]
+        lam = np.ascontiguousarray(lam, np.float64) if self.m else np.zeros((S, 1))
+        if self.m and lam.shape != (S, self.m):
+            raise ValueError("lam has shape %r, expected %r" % (lam.shape, (S, self.m)))
+        of = np.asarray(obj_factor, np.float64)
+        if of.ndim == 0:
+            of = np.full(S, float(of))
+        if of.shape != (S,):
+            raise ValueError("obj_factor has shape %r, expected a scalar or %r" % (of.shape, (S,)))
+        of = np.ascontiguousarray(of)
+        if v is not None:
+            v = np.ascontiguousarray(v, np.float64)
+            if v.shape != (S, self.n):
+                raise ValueError("v has shape %r, expected %r" % (v.shape, (S, self.n)))
+        return S, x, of, lam, v
+
+    def eval_hessian_lagrangian(self, x, obj_factor, lam):
+        """asm_batch_hessian_lagrangian: the values [n_scen x nnz] of obj_factor * objective_scale * hess f + sum_i lam_i hess g_i (MOI
+        plus-sign convention) per scenario, each with its data (the table of the last slp_run / set_scenario_data, else the setup data);
+        `obj_factor`: a scalar or one per scenario."""
+        from . import _lib
+        S, x, of, lam, _ = self._hessian_args(x, obj_factor, lam)
+        nnz = len(self.hessian_structure()[0])
+        out = np.empty((S, max(nnz, 1)))
+        self._check(self._lib.asm_batch_hessian_lagrangian(self._b, S, _lib.dptr(x), _lib.dptr(of), _lib.dptr(lam), _lib.dptr(out)))
+        return out[:, :nnz]
+
+    def hessian_product(self, x, obj_factor, lam, v):
+        """asm_batch_hessian_product: H v per scenario, [n_scen x n] (arguments as eval_hessian_lagrangian, v [n_scen x n])."""
+        from . import _lib
+        S, x, of, lam, v = self._hessian_args(x, obj_factor, lam, v)
+        out = np.empty((S, self.n))
+        self._check(self._lib.asm_batch_hessian_product(self._b, S, _lib.dptr(x), _lib.dptr(of), _lib.dptr(lam), _lib.dptr(v), _lib.dptr(out)))
+        return out
+
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.
         Returns (p, lambda, mult_x_U, mult_x_L, p_slack, status) with a leading scenario dimension."""
@@ -279,6 +339,18 @@ class HipBatch:
         if rc != 0:
             raise self._err("asm_sublp_last_stats(slot %d): %d" % (slot, rc))
         return {k: getattr(s, k) for k, _ in s._fields_}
+
+
+def lagrangian_hessians(hb, runs, sparse=False):
+    """The Hessians of the SLP drivers' Lagrangian f - lam' g of the scenarios of a HipBatch at the runs' (x, lam) - e.g. what hb.slp_run
+    returned, each scenario with its data: the MOI Hessian at obj_factor 1 and -lam, one symmetric n x n matrix per run (dense, or
+    scipy.sparse CSR with sparse=True).  The batch counterpart of moi_evaluator.lagrangian_hessian."""
+    from .moi_evaluator import hessian_matrix
+    x = np.stack([np.asarray(r.x, float) for r in runs])
+    lam = -np.stack([np.asarray(r.lam, float) for r in runs]) if hb.m else np.zeros((len(runs), 0))
+    rows, cols = hb.hessian_structure()
+    values = hb.eval_hessian_lagrangian(x, 1.0, lam)
+    return [hessian_matrix(rows, cols, values[s], hb.n, sparse) for s in range(len(runs))]
 
 
 def solve_batch_lockstep(problems, parameters, n_slots, device=0, rank=0, world=1, reduce_device=None, batch=None):

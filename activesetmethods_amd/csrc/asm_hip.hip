@@ -27,6 +27,7 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <memory>
 #include <numeric>
 #include <stdexcept>
 #include <string>
@@ -297,6 +298,17 @@ class BufPool {
     std::vector<Buf> own_;
 };
 
+// What the Hessian of the Lagrangian needs besides a workspace, all of it fixed by the function store and the tape of asm_eval_setup: the
+// pattern and the index lists in HBM.  A lone handle owns one; the slots of a batch share the batch's (asm_batch_hessian_*).
+struct HsShared {
+    BufPool mem;
+    int64_t nfn = 0, wnodes = 0, S = 0, nocc = 0;   // entries of the function store (the block's follow); nodes of a workspace; seed threads; occurrences
+    std::vector<int64_t> rows, cols;                // the pattern, 1-based
+    int64_t *qterm = nullptr, *qrow = nullptr, *eptr = nullptr, *eocc = nullptr, *pptr = nullptr, *pent = nullptr, *poth = nullptr;
+    int64_t *srow = nullptr, *svar = nullptr, *woff = nullptr, *optr = nullptr, *ovar = nullptr;
+    int64_t nnz() const { return (int64_t)rows.size(); }
+};
+
 // environment knobs of a handle, read once in asm_create (README.md lists them)
 struct HandleKnobs {
     int timing = 1;                 // ASM_HIP_TIMING: 0, 1 or 2, the initial asm_handle::timing
@@ -433,12 +445,12 @@ struct asm_handle {
     int64_t* d_ev_cptr = nullptr;
     double *d_ev_cocc = nullptr, *d_ev_lam = nullptr, *d_ev_dgrad = nullptr, *h_ev_dgrad = nullptr;
     // Hessian of the Lagrangian (asm_eval_hessian_*): pattern, lists and workspace, made by the first of those calls after asm_eval_setup
-    // (hs_prepare) from the store and the tape in HBM - a handle that never asks holds none of it
+    // (hs_prepare) from the store and the tape in HBM - a handle that never asks holds none of it.  The pattern and the lists are hs_sh's:
+    // the handle's own (hs_own), or for a batch slot that asm_batch_hessian_* prepared the batch's; the workspace is the handle's (mem_ev)
     bool hs_ready = false;
-    int64_t hs_nfn = 0, hs_wnodes = 0;       // entries of the function store (the block's follow); nodes of the workspace
-    std::vector<int64_t> hs_rows, hs_cols;   // the pattern, 1-based
-    ExprHess hs_H{};
-    int64_t *d_hs_qterm = nullptr, *d_hs_qrow = nullptr, *d_hs_eptr = nullptr, *d_hs_eocc = nullptr, *d_hs_pptr = nullptr, *d_hs_pent = nullptr, *d_hs_poth = nullptr;
+    std::unique_ptr<HsShared> hs_own;
+    const HsShared* hs_sh = nullptr;
+    ExprHess hs_H{};                         // the lists of hs_sh with this handle's four node arrays and hocc
     double *d_hs_lam = nullptr, *d_hs_v = nullptr, *d_hs_vals = nullptr, *d_hs_out = nullptr, *h_hs = nullptr;
     bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
@@ -3038,7 +3050,8 @@ void free_device(asm_handle* h) {
     h->ns_cap = false; h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0; h->ns_npairs = 0;
     h->ns_f0 = FacBuf(); h->ns_fN = FacBuf(); h->ns_fC = FacBuf(); h->test_fac = FacBuf();
     h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
-    h->ev_ready = false; h->hs_ready = false;
+    h->ev_ready = false;
+    h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
 }
 
 // forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
@@ -3940,8 +3953,7 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     HIPCHK(hipSetDevice(h->device));
     BufPool& P = h->mem_ev;
     P.release();
-    h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_nfn = h->hs_wnodes = 0;
-    std::vector<int64_t>().swap(h->hs_rows); std::vector<int64_t>().swap(h->hs_cols);
+    h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
     FnStore& F = h->ev_F;
     F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
     const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
@@ -4118,9 +4130,8 @@ void hs_row_pairs(const int32_t* op, const int64_t* a, const int64_t* b, int64_t
     std::sort(P.begin(), P.end());
     P.erase(std::unique(P.begin(), P.end()), P.end());
 }
-// pattern, seed threads, occurrence and product lists, workspace: once per asm_eval_setup, at the first Hessian call
-void hs_prepare(asm_handle* h) {
-    if (h->hs_ready) return;
+// pattern, seed threads, occurrence and product lists of h's store and tape (downloaded with blocking copies: not inside a batch fiber) into sh
+void hs_build(const asm_handle* h, HsShared& sh) {
     HIPCHK(hipSetDevice(h->device));
     const FnStore& F = h->ev_F;
     const ExprTape& X = h->ev_X;
@@ -4188,23 +4199,43 @@ void hs_prepare(asm_handle* h) {
         pent[fill[r]] = e; poth[fill[r]++] = c;
         if (r != c) { pent[fill[c]] = e; poth[fill[c]++] = r; }
     }
+    BufPool& M = sh.mem;
+    M.upload(sh.qterm, qterm.data(), nfn); M.upload(sh.qrow, qrow.data(), nfn);
+    M.upload(sh.eptr, eptr.data(), nblk + 1); M.upload(sh.eocc, eocc.data(), nocc);
+    M.upload(sh.pptr, pptr.data(), n + 1); M.upload(sh.pent, pent.data(), pptr[n]); M.upload(sh.poth, poth.data(), pptr[n]);
+    if (S > 0) {
+        M.upload(sh.srow, srow.data(), S); M.upload(sh.svar, svar.data(), S); M.upload(sh.woff, woff.data(), S);
+        M.upload(sh.optr, optr.data(), S + 1); M.upload(sh.ovar, ovar.data(), nocc);
+    }
+    sh.nfn = nfn; sh.wnodes = wnodes; sh.S = S; sh.nocc = nocc;
+    sh.rows.swap(rows); sh.cols.swap(cols);
+}
+// the handle's own part on the lists of sh: the four node arrays, hocc and the value / product vectors.  Inside a batch fiber the clearing
+// fills are recorded with the slot's other operations
+void hs_attach(asm_handle* h, const HsShared* sh) {
     BufPool& M = h->mem_ev;
-    M.upload(h->d_hs_qterm, qterm.data(), nfn); M.upload(h->d_hs_qrow, qrow.data(), nfn);
-    M.upload(h->d_hs_eptr, eptr.data(), nblk + 1); M.upload(h->d_hs_eocc, eocc.data(), nocc);
-    M.upload(h->d_hs_pptr, pptr.data(), n + 1); M.upload(h->d_hs_pent, pent.data(), pptr[n]); M.upload(h->d_hs_poth, poth.data(), pptr[n]);
+    const bool rec = asmb::in_fiber();
+    auto zeroed = [&](double*& f, int64_t count) { if (rec) M.zeroed(f, count, h->stream); else M.zeroed(f, count); };
     ExprHess& H = h->hs_H;
     H = ExprHess{};
-    H.S = S;
-    if (S > 0) {
-        M.upload(H.srow, srow.data(), S); M.upload(H.svar, svar.data(), S); M.upload(H.woff, woff.data(), S);
-        M.upload(H.optr, optr.data(), S + 1); M.upload(H.ovar, ovar.data(), nocc);
-        M.zeroed(H.val, wnodes); M.zeroed(H.tval, wnodes); M.zeroed(H.adj, wnodes); M.zeroed(H.tadj, wnodes); M.zeroed(H.hocc, nocc);
+    H.S = sh->S;
+    if (sh->S > 0) {
+        H.srow = sh->srow; H.svar = sh->svar; H.woff = sh->woff; H.optr = sh->optr; H.ovar = sh->ovar;
+        zeroed(H.val, sh->wnodes); zeroed(H.tval, sh->wnodes); zeroed(H.adj, sh->wnodes); zeroed(H.tadj, sh->wnodes); zeroed(H.hocc, sh->nocc);
     }
-    M.zeroed(h->d_hs_lam, h->m); M.zeroed(h->d_hs_v, n); M.zeroed(h->d_hs_vals, nnz); M.zeroed(h->d_hs_out, n);
-    M.alloc(h->h_hs, std::max(nnz, n), BufPool::PINNED);
-    h->hs_nfn = nfn; h->hs_wnodes = wnodes;
-    h->hs_rows.swap(rows); h->hs_cols.swap(cols);
+    zeroed(h->d_hs_lam, h->m); zeroed(h->d_hs_v, h->n); zeroed(h->d_hs_vals, sh->nnz()); zeroed(h->d_hs_out, h->n);
+    M.alloc(h->h_hs, std::max(sh->nnz(), h->n), BufPool::PINNED);
+    h->hs_sh = sh;
     h->hs_ready = true;
+}
+// once per asm_eval_setup, at the first Hessian call of a handle
+void hs_prepare(asm_handle* h) {
+    if (h->hs_ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    auto own = std::make_unique<HsShared>();
+    hs_build(h, *own);
+    h->hs_own = std::move(own);
+    hs_attach(h, h->hs_own.get());
 }
 void hs_check(const asm_handle* h, const char* who) {
     if (!h->ev_ready) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
@@ -4216,7 +4247,8 @@ void hs_check(const asm_handle* h, const char* who) {
 void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v) {
     hs_prepare(h);
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n, m = h->m, nnz = (int64_t)h->hs_rows.size(), nfn = h->hs_nfn;
+    const HsShared& L = *h->hs_sh;
+    const int64_t n = h->n, m = h->m, nnz = L.nnz(), nfn = L.nfn;
     const FnStore& F = h->ev_F;
     std::memcpy(h->h_ev, x, n * sizeof(double));
     HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4229,12 +4261,19 @@ void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* 
         HIPCHK(asmb::copy_async(h->d_hs_v, h->h_ev + n + m, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     const double wobj = obj_factor * F.objective_scale;
-    if (nfn > 0) asmb::launch(k_fn_hessian, asmb::blocks(nfn), dim3(256), h->stream, h->d_hs_qterm, h->d_hs_qrow, F.q_coef, h->d_hs_lam, wobj, nfn, h->d_hs_vals);
+    if (nfn > 0) asmb::launch(k_fn_hessian, asmb::blocks(nfn), dim3(256), h->stream, L.qterm, L.qrow, F.q_coef, h->d_hs_lam, wobj, nfn, h->d_hs_vals);
     if (h->hs_H.S > 0) {
         asmb::launch(k_nlp_expr_hess, asmb::blocks(h->hs_H.S), dim3(256), h->stream, h->ev_X, h->hs_H, h->d_ev_xt, h->d_hs_lam + F.n_rows, wobj);
-        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, h->d_hs_eptr, h->d_hs_eocc, h->hs_H.hocc, nnz - nfn, h->d_hs_vals + nfn);
+        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, h->hs_H.hocc, nnz - nfn, h->d_hs_vals + nfn);
     }
-    if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, h->d_hs_pptr, h->d_hs_pent, h->d_hs_poth, h->d_hs_vals, h->d_hs_v, n, h->d_hs_out);
+    if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, L.pptr, L.pent, L.poth, h->d_hs_vals, h->d_hs_v, n, h->d_hs_out);
+}
+void hs_pattern(const HsShared& sh, int64_t* nnz, int64_t* rows, int64_t* cols) {
+    *nnz = sh.nnz();
+    if (rows) {
+        std::copy(sh.rows.begin(), sh.rows.end(), rows);
+        std::copy(sh.cols.begin(), sh.cols.end(), cols);
+    }
 }
 void hs_read(asm_handle* h, const double* dev, int64_t count, double* out) {
     if (count > 0) HIPCHK(asmb::copy_async(h->h_hs, dev, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -4247,19 +4286,15 @@ static void do_hessian_structure(asm_handle* h, int64_t* nnz, int64_t* rows, int
     hs_check(h, "asm_eval_hessian_structure");
     if (!nnz || (rows == nullptr) != (cols == nullptr)) throw std::invalid_argument("asm_eval_hessian_structure: null pointer");
     hs_prepare(h);
-    *nnz = (int64_t)h->hs_rows.size();
-    if (rows) {
-        std::copy(h->hs_rows.begin(), h->hs_rows.end(), rows);
-        std::copy(h->hs_cols.begin(), h->hs_cols.end(), cols);
-    }
+    hs_pattern(*h->hs_sh, nnz, rows, cols);
 }
 static void do_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values) {
     hs_check(h, "asm_eval_hessian_lagrangian");
     if (!x || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
     hs_prepare(h);
-    if (!h->hs_rows.empty() && !values) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
+    if (h->hs_sh->nnz() > 0 && !values) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
     hs_launch(h, x, obj_factor, lambda, nullptr);
-    hs_read(h, h->d_hs_vals, (int64_t)h->hs_rows.size(), values);
+    hs_read(h, h->d_hs_vals, h->hs_sh->nnz(), values);
 }
 static void do_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out) {
     hs_check(h, "asm_eval_hessian_product");
@@ -5646,6 +5681,8 @@ struct asm_batch {
     std::vector<double> dpar0;      // the NLP-block data of asm_batch_eval_setup (what a scenario start restores)
     std::vector<double> scen_tab;   // per-scenario data [scen_n x scen_cnt] for dpar[scen_off, scen_off + scen_cnt) (scen_cnt = 0: none)
     int64_t scen_n = 0, scen_off = 0, scen_cnt = 0;
+    std::unique_ptr<HsShared> hs;   // pattern and lists of the Hessian of the Lagrangian, one copy for every slot (asm_batch_hessian_*); dropped by
+                                    // asm_batch_eval_setup
     bool setup_done = false;
     asm_batch_stats stats;
     bool verbose = false;           // ASM_BATCH_VERBOSE=1: per-kernel merge statistics of every group at release
@@ -5707,6 +5744,12 @@ void batch_scenario_data(asm_batch* b, asm_handle* h, int64_t sc) {
 void check_scen(const asm_batch* b, int64_t n_scen, const char* what) {
     if (b->scen_cnt > 0 && n_scen != b->scen_n)
         throw std::invalid_argument(std::string(what) + ": " + std::to_string(n_scen) + " scenarios, the scenario data table has " + std::to_string(b->scen_n));
+}
+// forget the shared Hessian lists: the slots that use them go back to "not prepared" (their workspaces leave with their evaluator pools)
+void batch_hs_drop(asm_batch* b) {
+    for (asm_handle* h : b->slots)
+        if (h->hs_sh && h->hs_sh == b->hs.get()) { h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; }
+    b->hs.reset();
 }
 void batch_free_groups(asm_batch* b) {
     for (BatchGroup* g : b->groups) {
@@ -5826,6 +5869,7 @@ asm_handle* asm_batch_handle(asm_batch* b, int slot) { return (b && slot >= 0 &&
 int asm_batch_setup(asm_batch* b, int64_t n, int64_t m, int64_t nnz, const int64_t* j_row, const int64_t* j_col, const double* c_lb, const double* c_ub,
                     const double* v_lb, const double* v_ub) {
     return guarded(b, [&] {
+        batch_hs_drop(b);
         for (size_t s = 0; s < b->slots.size(); ++s)
             in_slot("asm_sublp_setup", (int)s, [&] { do_setup(b->slots[s], n, m, nnz, j_row, j_col, c_lb, c_ub, v_lb, v_ub); });
         b->J_ref.clear();
@@ -5839,6 +5883,7 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
                          int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
     return guarded(b, [&] {
         if (!b->setup_done) throw std::logic_error("asm_batch_eval_setup: asm_batch_setup first");
+        batch_hs_drop(b);
         for (size_t s = 0; s < b->slots.size(); ++s)
             in_slot("asm_eval_setup", (int)s, [&] {
                 do_eval_setup(b->slots[s], n_rows, aff_ptr, aff_var, aff_coef, quad_ptr, q_v1, q_v2, q_coef, constant, jac_off, g_ptr, g_kind, g_coef, g_other,
@@ -6001,6 +6046,70 @@ int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const
                 do_data_gradient(h, x + sc * n, m > 0 ? lambda + sc * m : nullptr, out + sc * nd);
             }
         });
+    });
+}
+
+}  // extern "C"
+
+namespace {
+// what every asm_batch_hessian_* entry starts with: state and kind checks, then the shared pattern and lists - built once per
+// asm_batch_eval_setup from slot 0's store and tape, on the calling thread (the build downloads with blocking copies)
+void batch_hs_prepare(asm_batch* b, const char* who) {
+    if (!b->setup_done || !b->slots[0]->ev_ready) throw std::logic_error(std::string(who) + ": asm_batch_eval_setup first");
+    hs_check(b->slots[0], who);
+    if (b->hs) return;
+    auto sh = std::make_unique<HsShared>();
+    hs_build(b->slots[0], *sh);
+    b->hs = std::move(sh);
+}
+// asm_eval_hessian_lagrangian (v == nullptr: values [n_scen x nnz] into out) or asm_eval_hessian_product (out [n_scen x n]) of n_scen
+// scenarios, each with its data, the slots taking them in index order.  A slot attaches its workspace to the shared lists when it takes
+// its first scenario (a slot that a per-handle call prepared keeps its own lists: same pattern, same bits)
+void batch_hessians(asm_batch* b, const char* who, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, const double* v,
+                    double* out) {
+    const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nnz = b->hs->nnz(), len = v ? n : nnz;
+    check_scen(b, n_scen, who);
+    HIPCHK(hipSetDevice(b->device));
+    std::atomic<int64_t> next{0};
+    run_fibers(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), v ? "asm_eval_hessian_product" : "asm_eval_hessian_lagrangian", [&](int s) {
+        asm_handle* h = b->slots[s];
+        for (;;) {
+            const int64_t sc = next.fetch_add(1);
+            if (sc >= n_scen) break;
+            if (!h->hs_ready) hs_attach(h, b->hs.get());
+            batch_scenario_data(b, h, sc);
+            asmb::next_cycle();
+            hs_launch(h, x + sc * n, obj_factor ? obj_factor[sc] : 1.0, m > 0 ? lambda + sc * m : nullptr, v ? v + sc * n : nullptr);
+            hs_read(h, v ? h->d_hs_out : h->d_hs_vals, len, out + sc * len);
+        }
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int asm_batch_hessian_structure(asm_batch* b, int64_t* nnz, int64_t* rows, int64_t* cols) {
+    return guarded(b, [&] {
+        batch_hs_prepare(b, "asm_batch_hessian_structure");
+        if (!nnz || (rows == nullptr) != (cols == nullptr)) throw std::invalid_argument("asm_batch_hessian_structure: null pointer");
+        hs_pattern(*b->hs, nnz, rows, cols);
+    });
+}
+
+int asm_batch_hessian_lagrangian(asm_batch* b, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, double* values) {
+    return guarded(b, [&] {
+        batch_hs_prepare(b, "asm_batch_hessian_lagrangian");
+        if (n_scen < 1 || !x || (b->slots[0]->m > 0 && !lambda) || (b->hs->nnz() > 0 && !values))
+            throw std::invalid_argument("asm_batch_hessian_lagrangian: no scenario or a null pointer");
+        batch_hessians(b, "asm_batch_hessian_lagrangian", n_scen, x, obj_factor, lambda, nullptr, values);
+    });
+}
+
+int asm_batch_hessian_product(asm_batch* b, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, const double* v, double* out) {
+    return guarded(b, [&] {
+        batch_hs_prepare(b, "asm_batch_hessian_product");
+        if (n_scen < 1 || !x || !v || !out || (b->slots[0]->m > 0 && !lambda)) throw std::invalid_argument("asm_batch_hessian_product: no scenario or a null pointer");
+        batch_hessians(b, "asm_batch_hessian_product", n_scen, x, obj_factor, lambda, v, out);
     });
 }
 

@@ -406,6 +406,26 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
 int asm_batch_set_scenario_data(asm_batch* b, int64_t n_scen, int64_t offset, int64_t count, const double* table);
 /* asm_eval_data_gradient of n_scen scenarios, each with its data: x [n_scen x n], lambda [n_scen x m], out [n_scen x n_dpar] */
 int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, double* out);
+/* ---- Hessian of the Lagrangian of n_scen scenarios (asm_eval_hessian_* with a leading scenario dimension): the MOI plus-sign convention
+ * of asm_eval_hessian_lagrangian - pass -lambda for the multipliers asm_batch_slp_run returns.  The pattern is the one
+ * asm_eval_hessian_structure gives on any slot, in the same order.
+ *   x, v, out [n_scen x n]; lambda [n_scen x m]; values [n_scen x nnz]; obj_factor [n_scen], or NULL for 1.0 in every scenario.
+ * n_scen may exceed n_slots: the slots take the scenarios in index order, and a slot that takes scenario s first gets scenario s's data
+ * (row s of the table of asm_batch_set_scenario_data, else the data of asm_batch_eval_setup), as in asm_batch_data_gradient.  The result
+ * for scenario s is bit-identical to the per-handle call on a fresh handle with the same model and asm_eval_set_data of row s: the same
+ * kernels run, merged over the slots into one launch each.  The LP inputs, retained bases and hints of the slots are not touched: an
+ * asm_batch_slp_run after these calls returns the bits it returns without them.
+ * The pattern and the index lists are built by the first of these calls after asm_batch_eval_setup, once for the batch, and shared by
+ * the slots; a slot adds its workspace (four node arrays, occurrence values, value and product vectors) when it first takes a scenario.
+ * asm_batch_eval_setup drops both.
+ * ASM_ERR_STATE before asm_batch_setup + asm_batch_eval_setup.  ASM_ERR_ARG: a null batch or required pointer (lambda with m == 0 and
+ * values with nnz == 0 are not required), n_scen < 1, rows without cols or the reverse, an n_scen other than the height of a set
+ * scenario table, nlp_kind 1 or 2 (as the per-handle entries).  The batch works on after any of them.
+ * asm_batch_hessian_structure: *nnz and, unless rows == cols == NULL, the pattern (1-based). */
+int asm_batch_hessian_structure(asm_batch* b, int64_t* nnz, int64_t* rows, int64_t* cols);
+int asm_batch_hessian_lagrangian(asm_batch* b, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, double* values);
+int asm_batch_hessian_product(asm_batch* b, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, const double* v,
+                              double* out);
 /* basis columns every scenario of asm_batch_slp_run starts from (default: selected by one LP of scenario 0 on slot 0) */
 int asm_batch_set_ns_basis(asm_batch* b, const int32_t* J, int64_t k);
 int asm_batch_ns_basis(const asm_batch* b, int32_t* J, int64_t* k);
