@@ -69,6 +69,17 @@ class BatchStats(C.Structure):
                 ("panel_grid_max", C.c_int64)]
 
 
+class KktParams(C.Structure):
+    """asm_kkt_params."""
+    _fields_ = [("max_iter", C.c_int32), ("rtol", C.c_double)]
+
+
+class KktInfo(C.Structure):
+    """asm_kkt_info: status 0 solved, 1 iteration limit, 2 reduced Hessian not positive definite, 3 dependent working rows."""
+    _fields_ = [("status", C.c_int32), ("cg_iters", C.c_int32), ("n_free", C.c_int32), ("n_rows", C.c_int32), ("dropped_pivots", C.c_int32),
+                ("res_stat", C.c_double), ("res_feas", C.c_double)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
@@ -101,6 +112,9 @@ PROTOTYPES = {
     "asm_eval_jacobian_values": (C.c_int, [_P, _D]),
     "asm_eval_set_data": (C.c_int, [_P, C.c_int64, C.c_int64, _D]),
     "asm_eval_data_gradient": (C.c_int, [_P, _D, _D, _D]),
+    "asm_eval_data_cross": (C.c_int, [_P, _D, _D, _D, _D, _D]),
+    "asm_kkt_solve": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_solution_sensitivity": (C.c_int, [_P, _D, _D, _I32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_eval_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
     "asm_eval_hessian_lagrangian": (C.c_int, [_P, _D, C.c_double, _D, _D]),
     "asm_eval_hessian_product": (C.c_int, [_P, _D, C.c_double, _D, _D, _D]),

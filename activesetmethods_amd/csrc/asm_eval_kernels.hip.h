@@ -423,15 +423,26 @@ __device__ __noinline__ double expr_libm2(int32_t op, double u) {
         default: return log(u);           // ASM_OP_LOG
     }
 }
-// forward sweep with tangent: tval = d val / d x_seed, statement by statement the tangent of expr_forward
-__device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, int64_t seed, double* val, double* tval) {
+// forward sweep with tangent: tval = d val / d x_seed, statement by statement the tangent of expr_forward.  DATA: the seed is a direction
+// dc in the constants instead - a CONST node with operand a has the tangent dc[a], every VAR node 0 (asm_eval_data_cross)
+template <bool DATA = false>
+__device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, int64_t seed, double* val, double* tval,
+                                              const double* __restrict__ dc = nullptr) {
 #pragma clang fp contract(off)
     for (int64_t k = k0; k < k1; ++k) {
         const int64_t a = X.a[k], b = X.b[k];
         const int32_t op = X.op[k];
         double v, d;
-        if (op == ASM_OP_CONST) { v = X.cst[a]; d = 0.0; }
-        else if (op == ASM_OP_VAR) { v = x[a]; d = a == seed ? 1.0 : 0.0; }
+        if (op == ASM_OP_CONST) {
+            v = X.cst[a];
+            if constexpr (DATA) d = dc[a];
+            else d = 0.0;
+        }
+        else if (op == ASM_OP_VAR) {
+            v = x[a];
+            if constexpr (DATA) d = 0.0;
+            else d = a == seed ? 1.0 : 0.0;
+        }
         else {
             const double u = val[a], du = tval[a];
             const bool binary = (op >= ASM_OP_ADD && op <= ASM_OP_DIV) || op >= ASM_OP_POW;
@@ -479,9 +490,11 @@ __device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int
     }
 }
 // reverse sweep with tangent: adj as expr_reverse forms it, tadj = d adj / d x_seed, statement by statement; the adjoint tangent of a VAR
-// node whose variable is in the thread's occurrence list is added to hocc there (several VAR nodes of a variable: reverse node order)
+// node whose variable is in the thread's occurrence list is added to hocc there (several VAR nodes of a variable: reverse node order).
+// DATA: every VAR node is an occurrence of its own instead - hocc[node] = wt * its adjoint tangent (one product), no list
+template <bool DATA = false>
 __device__ __forceinline__ void expr_reverse2(const ExprTape& X, int64_t k0, int64_t k1, const double* val, const double* tval, double* adj, double* tadj,
-                                              const int64_t* __restrict__ ovar, int64_t o0, int64_t o1, double* __restrict__ hocc) {
+                                              const int64_t* __restrict__ ovar, int64_t o0, int64_t o1, double* __restrict__ hocc, double wt = 0.0) {
 #pragma clang fp contract(off)
     for (int64_t k = k0; k < k1; ++k) { adj[k] = 0.0; tadj[k] = 0.0; }
     adj[k1 - 1] = 1.0;
@@ -491,8 +504,10 @@ __device__ __forceinline__ void expr_reverse2(const ExprTape& X, int64_t k0, int
         const double w = adj[k], z = tadj[k];
         const int64_t a = X.a[k], b = X.b[k];
         if (op == ASM_OP_VAR) {
-            for (int64_t o = o0; o < o1; ++o)
-                if (ovar[o] == a) { hocc[o] = hocc[o] + z; break; }
+            if constexpr (DATA) hocc[k] = wt * z;
+            else
+                for (int64_t o = o0; o < o1; ++o)
+                    if (ovar[o] == a) { hocc[o] = hocc[o] + z; break; }
             continue;
         }
         const double u = val[a], du = tval[a], v = val[k], d = tval[k];
@@ -608,6 +623,34 @@ __global__ __launch_bounds__(256) void k_nlp_expr_hess_gather(AsmBt abt, const i
     double g = 0.0;
     for (int64_t q = eptr[e]; q < eptr[e + 1]; ++q) g = g + hocc[eocc[q]];
     values[e] = g;
+}
+// ---- cross derivatives with respect to the data (asm_eval_data_cross; include/asm_hip.h, "Cross derivatives"): the forward-over-reverse
+// sweep of k_nlp_expr_hess seeded in the constants.  One thread per row (t < R) or term; its four node arrays are its nodes' places in four
+// HBM arrays of L doubles (the workspace scheme of ExprHess with one segment per row).  The tangent of a row's last node is wrow[t]
+// (d g_t / d dpar . dc); the adjoint tangent of every VAR node k, times -lam[t] or the objective's sense scale, is the occurrence vocc[k].
+struct ExprCross {
+    const int64_t *vptr, *vnode;                        // vptr [n+1]; vnode [vptr[n]]: the VAR nodes of each variable, (row, then term) ascending, node descending
+    double *val, *tval, *adj, *tadj, *vocc;             // [L] each
+};
+__global__ __launch_bounds__(256) void k_nlp_expr_cross(AsmBt abt, ExprTape X, ExprCross C, const double* __restrict__ x, const double* __restrict__ dc, const double* __restrict__ lam, double scale, double* __restrict__ wrow) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, C, x, dc, lam, scale, wrow);
+    const int64_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= X.R + X.T) return;
+    const int64_t k0 = X.ptr[t], k1 = X.ptr[t + 1];
+    expr_forward2<true>(X, k0, k1, x, -1, C.val, C.tval, dc);
+    if (t < X.R) wrow[t] = C.tval[k1 - 1];
+    expr_reverse2<true>(X, k0, k1, C.val, C.tval, C.adj, C.tadj, nullptr, 0, 0, C.vocc, t < X.R ? -lam[t] : scale);
+}
+// one thread per variable sums its occurrences in list order from 0.0 (fixed order, no atomics: the host twin's sum)
+__global__ __launch_bounds__(256) void k_nlp_expr_cross_gather(AsmBt abt, ExprCross C, int64_t n, double* __restrict__ u) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, C, n, u);
+    const int64_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    double g = 0.0;
+    for (int64_t q = C.vptr[j]; q < C.vptr[j + 1]; ++q) g = g + C.vocc[C.vnode[q]];
+    u[j] = g;
 }
 // out = H v from the values: one thread per variable walks its list of (entry, other variable) in entry order - an off-diagonal entry
 // (i, j) is in the lists of i and of j - and sums values[entry] * v[other] from 0.0

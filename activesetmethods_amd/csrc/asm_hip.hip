@@ -12,6 +12,7 @@
 #include "asm_as_kernels.hip.h"
 #include "asm_ns_kernels.hip.h"
 #include "asm_eval_kernels.hip.h"
+#include "asm_kkt_kernels.hip.h"
 #include "asm_batch.hip.h"
 #include "../../include/asm_hip.h"
 
@@ -342,6 +343,7 @@ struct asm_handle {
     // owners of the device / pinned buffers below, one per lifetime: the problem skeleton (until the next set-up), the null-space buffers
     // sized by k (until the dimension outgrows them), the device evaluator (until the next asm_eval_setup)
     BufPool mem, mem_nsk, mem_ev;
+    BufPool mem_kk;                 // the KKT solve on a working set (asm_kkt_solve): until the next asm_sublp_setup or asm_eval_setup
 
     // ---- problem (subproblem.jl:51-215) ----
     int64_t n = 0, m = 0, nnz = 0, nadj = 0, M = 0, Mp = 0, ldn = 0, ns = 0;
@@ -452,6 +454,22 @@ struct asm_handle {
     const HsShared* hs_sh = nullptr;
     ExprHess hs_H{};                         // the lists of hs_sh with this handle's four node arrays and hocc
     double *d_hs_lam = nullptr, *d_hs_v = nullptr, *d_hs_vals = nullptr, *d_hs_out = nullptr, *h_hs = nullptr;
+    // cross derivatives with respect to the data (asm_eval_data_cross): the per-variable occurrence list and the workspace, made by the first
+    // call after asm_eval_setup (cx_prepare) in the evaluator's pool
+    bool cx_ready = false;
+    ExprCross cx_C{};
+    int64_t *d_cx_vptr = nullptr, *d_cx_vnode = nullptr;
+    double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr;   // [lam (R) | dc (n_dpar)], [u (n) | w (R)], pinned staging of both and x
+    // KKT solve on a working set (asm_kkt_solve): Jacobian values and dense Jacobian of its own, the gathered working rows and their
+    // transposed copy, the factor of A A', work vectors and the scalar block of the conjugate-gradient kernels; made by the first call
+    // after asm_eval_setup (kk_prepare) in mem_kk
+    bool kk_ready = false;
+    int64_t kk_capW = 0, kk_ldT = 0;
+    FacBuf kk_fac;
+    double *d_kk_dE = nullptr, *d_kk_J = nullptr, *d_kk_Aw = nullptr, *d_kk_AwT = nullptr, *d_kk_vec = nullptr, *d_kk_row = nullptr;
+    double *d_kk_part = nullptr, *d_kk_scal = nullptr, *h_kk = nullptr;
+    unsigned* d_kk_arr = nullptr;
+    int *d_kk_wrow = nullptr, *d_kk_cnt = nullptr;
     bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
     double* h_scal = nullptr;       // pinned scalar read-back; host-mapped: the reduction kernels store the block there themselves (scal_publish)
@@ -3042,7 +3060,8 @@ int row_kind(double lb, double ub) {
 
 // releases every buffer of the handle and resets the state that describes them
 void free_device(asm_handle* h) {
-    h->mem.release(); h->mem_nsk.release(); h->mem_ev.release();
+    h->mem.release(); h->mem_nsk.release(); h->mem_ev.release(); h->mem_kk.release();
+    h->kk_ready = false; h->kk_fac = FacBuf();
     h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
     h->ahTg_valid = false;
     h->col_capable = h->ahT_valid = h->nzT_valid = false;
@@ -3052,6 +3071,7 @@ void free_device(asm_handle* h) {
     h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
     h->ev_ready = false;
     h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
+    h->cx_ready = false; h->cx_C = ExprCross{};
 }
 
 // forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
@@ -3954,6 +3974,8 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     BufPool& P = h->mem_ev;
     P.release();
     h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
+    h->cx_ready = false; h->cx_C = ExprCross{};
+    h->mem_kk.release(); h->kk_ready = false; h->kk_fac = FacBuf();
     FnStore& F = h->ev_F;
     F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
     const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
@@ -4303,6 +4325,319 @@ static void do_hessian_product(asm_handle* h, const double* x, double obj_factor
     hs_read(h, h->d_hs_out, h->n, out);
 }
 
+// ---- cross derivatives with respect to the data (include/asm_hip.h, "Cross derivatives of an expression block")
+namespace {
+// once per asm_eval_setup, at the first asm_eval_data_cross: the VAR nodes of every variable in (row, then term) order, node descending
+// inside a row or term, and the workspace (blocking copies: not inside a batch fiber)
+void cx_prepare(asm_handle* h) {
+    if (h->cx_ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    const ExprTape& X = h->ev_X;
+    const int64_t n = h->n, nt = X.R + X.T;
+    const std::vector<int64_t> ptr = hs_download(X.ptr, nt + 1), ta = hs_download(X.a, X.L);
+    const std::vector<int32_t> top = hs_download(X.op, X.L);
+    std::vector<int64_t> vptr(n + 1, 0);
+    for (int64_t k = 0; k < X.L; ++k)
+        if (top[k] == ASM_OP_VAR) ++vptr[ta[k] + 1];
+    for (int64_t j = 0; j < n; ++j) vptr[j + 1] += vptr[j];
+    std::vector<int64_t> vnode(vptr[n]), fill(vptr.begin(), vptr.end() - 1);
+    for (int64_t t = 0; t < nt; ++t)
+        for (int64_t k = ptr[t + 1] - 1; k >= ptr[t]; --k)
+            if (top[k] == ASM_OP_VAR) vnode[fill[ta[k]]++] = k;
+    BufPool& M = h->mem_ev;
+    ExprCross& C = h->cx_C;
+    C = ExprCross{};
+    M.upload(h->d_cx_vptr, vptr.data(), n + 1); M.upload(h->d_cx_vnode, vnode.data(), vptr[n]);
+    C.vptr = h->d_cx_vptr; C.vnode = h->d_cx_vnode;
+    M.zeroed(C.val, X.L); M.zeroed(C.tval, X.L); M.zeroed(C.adj, X.L); M.zeroed(C.tadj, X.L); M.zeroed(C.vocc, X.L);
+    M.zeroed(h->d_cx_in, X.R + h->ev_n_dpar); M.zeroed(h->d_cx_out, n + X.R);
+    M.alloc(h->h_cx, 2 * (n + X.R) + h->ev_n_dpar, BufPool::PINNED);
+    h->cx_ready = true;
+}
+void cx_check(const asm_handle* h, const char* who) {
+    if (!h->ev_ready) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
+    if (h->ev_nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument(std::string(who) + ": cross derivatives exist for expression blocks (nlp_kind 3) only");
+}
+}  // namespace
+// u = d/dc (grad_x L) . dc, w = (dg/dc) . dc at (x, lambda), L = f - lambda' g (k_nlp_expr_cross + k_nlp_expr_cross_gather); the inputs of
+// the next LP are not touched (x goes where asm_eval_constraints puts its trial point)
+static void do_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w) {
+    cx_check(h, "asm_eval_data_cross");
+    if (!x || !u || (h->m > 0 && (!lambda || !w)) || (h->ev_n_dpar > 0 && !dc)) throw std::invalid_argument("asm_eval_data_cross: null pointer");
+    const int64_t n = h->n, m = h->m, nd = h->ev_n_dpar;
+    for (int64_t j = 0; j < n; ++j) u[j] = 0.0;
+    for (int64_t i = 0; i < m; ++i) w[i] = 0.0;
+    if (!h->d_ev_cocc) return;      // no CONST node: nothing depends on the data
+    cx_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    const ExprTape& X = h->ev_X;
+    double* st = h->h_cx;
+    std::memcpy(st, x, n * sizeof(double));
+    if (X.R > 0) std::memcpy(st + n, lambda + h->ev_F.n_rows, X.R * sizeof(double));
+    std::memcpy(st + n + X.R, dc, nd * sizeof(double));
+    HIPCHK(asmb::copy_async(h->d_ev_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(h->d_cx_in, st + n, (X.R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, h->cx_C, h->d_ev_xt, h->d_cx_in + X.R, h->d_cx_in, h->ev_F.objective_scale,
+                 h->d_cx_out + n);
+    asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), h->stream, h->cx_C, n, h->d_cx_out);
+    double* back = st + n + X.R + nd;
+    HIPCHK(asmb::copy_async(back, h->d_cx_out, (n + X.R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::sync(h->stream));
+    std::memcpy(u, back, n * sizeof(double));
+    if (X.R > 0) std::memcpy(w + h->ev_F.n_rows, back + n, X.R * sizeof(double));
+}
+
+// ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set")
+namespace {
+// once per asm_eval_setup, at the first asm_kkt_solve: the buffers of the solve, sized for every working set the problem admits
+void kk_prepare(asm_handle* h) {
+    if (h->kk_ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->mem_kk;
+    const hipStream_t s = h->stream;
+    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32);
+    h->kk_capW = std::max<int64_t>(std::min(h->m, h->n), 1);
+    h->kk_ldT = round_up(h->kk_capW, 32);
+    M.alloc(h->d_kk_dE, h->nnz);
+    M.zeroed(h->d_kk_J, Mp * ldn, s);
+    M.zeroed(h->d_kk_Aw, h->kk_capW * ldn, s);
+    M.zeroed(h->d_kk_AwT, ldn * h->kk_ldT, s);
+    ns_alloc_factor(h, M, h->kk_fac, h->kk_capW);
+    M.zeroed(h->d_kk_vec, 16 * ldn, s);
+    M.zeroed(h->d_kk_row, 6 * Mp, s);
+    M.zeroed(h->d_kk_part, KK_MAXWG * KK_SLOTS, s);
+    M.zeroed(h->d_kk_scal, 16, s);
+    M.zeroed(h->d_kk_arr, 4, s);
+    M.zeroed(h->d_kk_wrow, Mp, s);
+    M.zeroed(h->d_kk_cnt, 4, s);
+    M.alloc(h->h_kk, 4 * ldn + 4 * Mp + 64, BufPool::PINNED);
+    HIPCHK(asmb::sync(s));
+    h->kk_ready = true;
+}
+// the scalar block of the last k_kkt_cg_dir on the host (h_scal): the kernel's own stores and the sequence word the host spins on, or
+// (pub == 0, ASM_HIP_SPIN=0) a copy and a stream synchronisation
+void kk_read_scal(asm_handle* h, unsigned pub) {
+    if (pub == 0) {
+        HIPCHK(asmb::copy_async(h->h_scal, h->d_kk_scal, KK_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+        return;
+    }
+    const double t0 = Solver::now_ms();
+    for (unsigned long spins = 1;; ++spins) {
+        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
+        if (spins < 20000) __builtin_ia32_pause();
+        else sched_yield();
+        if ((spins & 0xffff) == 0 && Solver::now_ms() - t0 > 30000.0) {
+            HIPCHK(asmb::sync(h->stream));            // a device fault surfaces here
+            if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
+            throw HipError("asm_kkt_solve: the publishing kernel finished without setting its sequence word");
+        }
+    }
+}
+}  // namespace
+static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru,
+                         const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
+    hs_check(h, "asm_kkt_solve");
+    const int64_t n = h->n, m = h->m, ldn = h->ldn;
+    if (!x || !bound_state || !ru || !dx || !info || (m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
+    int64_t nF = 0, nW = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument("asm_kkt_solve: bound_state holds a value outside {-1, 0, +1}");
+        nF += bound_state[j] == 0;
+    }
+    for (int64_t i = 0; i < m; ++i) {
+        if (row_state[i] != 0 && row_state[i] != 1) throw std::invalid_argument("asm_kkt_solve: row_state holds a value outside {0, 1}");
+        nW += row_state[i];
+    }
+    if (nW > nF) throw std::invalid_argument("asm_kkt_solve: more working rows (" + std::to_string(nW) + ") than free variables (" + std::to_string(nF) + ")");
+    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument("asm_kkt_solve: max_iter < 0 or rtol not >= 0");
+    const int64_t max_iter = par ? par->max_iter : 2 * (nF - nW) + 20;
+    const double rtol = par ? par->rtol : 1e-12;
+    if (asmb::in_fiber()) throw std::logic_error("asm_kkt_solve: not inside a scenario batch");
+    hs_prepare(h);
+    kk_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    Dev dev(h);
+    const hipStream_t s = h->stream;
+    const int64_t Mp = std::max<int64_t>(h->Mp, 32);
+    // the vectors over the variables (pitch ldn, zero beyond n and on B) and over the rows
+    double* const V = h->d_kk_vec;
+    double *mask = V, *d_ru = V + ldn, *dx0 = V + 2 * ldn, *cd = V + 3 * ldn, *cr = V + 4 * ldn, *cg = V + 5 * ldn, *cp = V + 6 * ldn, *hraw = V + 7 * ldn,
+           *hp = V + 8 * ldn, *tt = V + 9 * ldn, *ddx = V + 10 * ldn, *hdx = V + 11 * ldn, *qq = V + 12 * ldn, *jtl = V + 13 * ldn, *ddz = V + 14 * ldn;
+    double* const Rw = h->d_kk_row;
+    double *rww = Rw, *tw = Rw + Mp, *yw = Rw + 2 * Mp, *dlw = Rw + 3 * Mp, *adx = Rw + 4 * Mp, *dlf = Rw + 5 * Mp;
+    const KktRed R{h->d_kk_part, h->d_kk_arr, h->d_kk_scal, h->d_hscal, h->d_hseq};
+    // 1. the Hessian values of f - lambda' g at x, once: they stay in d_hs_vals for every product of the call (x goes to d_ev_xt)
+    {
+        std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
+        for (int64_t i = 0; i < m; ++i) nl[i] = -lambda[i];
+        hs_launch(h, x, 1.0, nl.data(), nullptr);      // (copies nl into the pinned staging buffer before it returns)
+    }
+    const HsShared& L = *h->hs_sh;
+    auto hess_product = [&](const double* v, double* out) {
+        asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, n, out);
+    };
+    // 2. the Jacobian at x: values into a buffer of the solve's own, assembled into its own dense J (the LP's dE and J stay)
+    {
+        const FnStore& F = h->ev_F;
+        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, 1, (int64_t)0, (int64_t)0);
+        const ExprTape& X = h->ev_X;
+        if (h->ev_nlp_kind == ASM_NLP_EXPR && X.R > 0)
+            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, F.n_rows, h->ev_fn_nnz, 1, (int64_t)0, (int64_t)0);
+        if (h->dense_fast) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->m * h->n + 255) / 256, 4096);
+            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, h->d_kk_dE, h->d_kk_J, h->m, h->n, ldn);
+        } else if (h->nu > 0) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
+            asmb::launch(k_assemble, dim3(g), dim3(256), s, h->d_kk_dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, h->d_kk_J, h->nu);
+        }
+    }
+    // 3. the sets and the right-hand sides
+    {
+        double* st = h->h_kk;
+        for (int64_t j = 0; j < ldn; ++j) { st[j] = (j < n && bound_state[j] == 0) ? 1.0 : 0.0; st[ldn + j] = j < n ? ru[j] : 0.0; }
+        int* wl = reinterpret_cast<int*>(st + 2 * ldn + Mp);
+        int64_t q = 0;
+        for (int64_t i = 0; i < m; ++i)
+            if (row_state[i]) { st[2 * ldn + q] = rw[i]; wl[q] = (int)i; ++q; }
+        for (; q < Mp; ++q) { st[2 * ldn + q] = 0.0; wl[q] = 0; }
+        HIPCHK(asmb::copy_async(mask, st, 2 * ldn * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(asmb::copy_async(rww, st + 2 * ldn, Mp * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(asmb::copy_async(h->d_kk_wrow, wl, Mp * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    const dim3 gl = asmb::blocks(ldn);
+    const dim3 gred((unsigned)std::min<int64_t>(gl.x, KK_MAXWG));
+    // A = J[W, F] as a dense operand and its transposed copy; S = A A' and its factor
+    if (nW > 0) {
+        asmb::launch(k_kkt_gather, dim3(gl.x, (unsigned)nW), dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, mask, nW, h->d_kk_Aw);
+        asmb::launch(k_transpose_dense, dim3((unsigned)((ldn + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, h->d_kk_Aw, ldn, nW, ldn, h->d_kk_AwT, h->kk_ldT, (int64_t)-1);
+        dev.launch_syrk(s, Dev::pick_tile(nW), h->d_kk_Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, h->kk_fac.S, h->kk_fac.ld, 0, 0);
+        dev.diag_prepare(h->kk_fac, (int)nW, 1, 0.0, 0.0);
+        const int nfact = h->stats.nfact;
+        dev.chol(h->kk_fac, (int)nW, 1e-10);
+        h->stats.nfact = nfact;          // (the LP statistics count the LP's factorisations)
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, h->kk_fac.S, h->kk_fac.ld, (int)nW, NS_BIG, h->d_kk_cnt);
+    } else {
+        HIPCHK(asmb::fill_async(h->d_kk_cnt, 0, 4 * sizeof(int), s));
+    }
+    // t = A' S^-1 A v  (v, t over the variables)
+    auto normal_part = [&](const double* v) {
+        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, v, tw, nW, ldn);
+        dev.chol_solve_dev(h->kk_fac, tw, yw, (int)nW);
+        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, yw, tt, ldn, nW);
+    };
+    // dst = P src = src - A' S^-1 A src
+    auto project = [&](const double* src, double* dst) {
+        if (nW == 0) {
+            if (src != dst) HIPCHK(asmb::copy_async(dst, src, ldn * sizeof(double), hipMemcpyDeviceToDevice, s));
+            return;
+        }
+        normal_part(src);
+        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, src, -1.0, tt, mask, ldn, dst);
+    };
+    // particular solution dx0 = -A' S^-1 rw_W
+    if (nW > 0) {
+        dev.chol_solve_dev(h->kk_fac, rww, yw, (int)nW);
+        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, yw, tt, ldn, nW);
+        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, -1.0, tt, 0.0, nullptr, mask, ldn, dx0);
+        // one refinement step of the normal-equation solve: dx0 -= A' S^-1 (A dx0 + rw_W)
+        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, dx0, adx, nW, ldn);
+        asmb::launch(k_kkt_axpby_mask, asmb::blocks(nW), dim3(256), s, 1.0, adx, 1.0, rww, nullptr, nW, tw);
+        dev.chol_solve_dev(h->kk_fac, tw, yw, (int)nW);
+        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, yw, tt, ldn, nW);
+        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, dx0, -1.0, tt, mask, ldn, dx0);
+    } else {
+        HIPCHK(asmb::fill_async(dx0, 0, ldn * sizeof(double), s));
+    }
+    // projected conjugate gradients on null(A): minimise 1/2 d'H_FF d + (ru_F + H_FF dx0)'d
+    int status = 0, iters = 0;
+    HIPCHK(asmb::fill_async(cd, 0, ldn * sizeof(double), s));
+    if (nF > nW) {
+        auto pub_next = [&]() -> unsigned {
+            if (!h->knobs.spin_read) return 0;
+            h->scal_seq += 1;
+            if (h->scal_seq == 0) h->scal_seq = 1;
+            return h->scal_seq;
+        };
+        hess_product(dx0, hraw);
+        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, d_ru, 1.0, hraw, mask, ldn, cr);
+        HIPCHK(asmb::fill_async(cp, 0, ldn * sizeof(double), s));
+        // the residual is kept projected (r = g = P P r): it then has no large component in range(A') for the projection's rounding to act on
+        project(cr, cr);
+        project(cr, cr);
+        unsigned pub = pub_next();
+        asmb::launch(k_kkt_cg_dir, gred, dim3(256), s, R, cr, cr, ldn, 1, rtol, pub);
+        kk_read_scal(h, pub);
+        int stop = (int)h->h_scal[KK_STOP];
+        while (stop == 0) {
+            if (iters >= max_iter) { status = 1; break; }
+            asmb::launch(k_kkt_cg_p, gl, dim3(256), s, h->d_kk_scal, cr, cp, ldn);
+            hess_product(cp, hraw);
+            asmb::launch(k_kkt_cg_curv, gred, dim3(256), s, R, cp, hraw, mask, hp, ldn);
+            asmb::launch(k_kkt_cg_step, gl, dim3(256), s, h->d_kk_scal, cp, hp, cd, cr, ldn);
+            project(cr, cr);
+            project(cr, cr);
+            pub = pub_next();
+            asmb::launch(k_kkt_cg_dir, gred, dim3(256), s, R, cr, cr, ldn, 0, rtol, pub);
+            kk_read_scal(h, pub);
+            stop = (int)h->h_scal[KK_STOP];
+            if (stop != 2) ++iters;
+        }
+        if (stop == 2) status = 2;
+    }
+    // the solution, its multipliers and residuals
+    asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, dx0, 1.0, cd, mask, ldn, ddx);
+    hess_product(ddx, hdx);
+    HIPCHK(asmb::fill_async(dlf, 0, Mp * sizeof(double), s));
+    if (nW > 0) {
+        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, hdx, 1.0, d_ru, mask, ldn, qq);
+        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, qq, tw, nW, ldn);
+        dev.chol_solve_dev(h->kk_fac, tw, dlw, (int)nW);
+        // one refinement step: dlam_W += S^-1 A (q - A' dlam_W)
+        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, dlw, tt, ldn, nW);
+        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, qq, -1.0, tt, mask, ldn, cg);
+        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, cg, tw, nW, ldn);
+        dev.chol_solve_dev(h->kk_fac, tw, yw, (int)nW);
+        asmb::launch(k_kkt_axpby_mask, asmb::blocks(nW), dim3(256), s, 1.0, dlw, 1.0, yw, nullptr, nW, dlw);
+        asmb::launch(k_kkt_scatter, asmb::blocks(nW), dim3(256), s, dlw, h->d_kk_wrow, nW, dlf);
+        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, ddx, adx, nW, ldn);
+        // J' dlam over all columns (the bound columns too) from the private dense J
+        int64_t Rc = std::min<int64_t>((m + 31) / 32, ASM_TMAXCHUNKS);
+        const int64_t chunk = (m + Rc - 1) / Rc;
+        Rc = (m + chunk - 1) / chunk;
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->d_kk_J, ldn, dlf, h->d_partial, m, ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, gl, dim3(256), s, h->d_partial, jtl, Rc, ldn);
+    } else {
+        HIPCHK(asmb::fill_async(jtl, 0, ldn * sizeof(double), s));
+    }
+    asmb::launch(k_kkt_finish, dim3(1), dim3(1024), s, R, hdx, d_ru, jtl, mask, n, adx, rww, nW, ddz);
+    double* back = h->h_kk + 2 * ldn + 2 * Mp;
+    HIPCHK(asmb::copy_async(back, ddx, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::copy_async(back + ldn, ddz, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (m > 0) HIPCHK(asmb::copy_async(back + 2 * ldn, dlf, m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::copy_async(back + 2 * ldn + Mp, h->d_kk_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::copy_async(back + 2 * ldn + Mp + 16, h->d_kk_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::sync(s));
+    dev.resolve_timing();
+    std::memcpy(dx, back, n * sizeof(double));
+    if (dz) std::memcpy(dz, back + ldn, n * sizeof(double));
+    if (m > 0) std::memcpy(dlam, back + 2 * ldn, m * sizeof(double));
+    const double* sc = back + 2 * ldn + Mp;
+    const int dropped = *reinterpret_cast<const int*>(back + 2 * ldn + Mp + 16);
+    if (dropped > 0) status = 3;
+    info->status = status; info->cg_iters = iters; info->n_free = (int32_t)nF; info->n_rows = (int32_t)nW; info->dropped_pivots = dropped;
+    info->res_stat = sc[KK_RSTAT]; info->res_feas = sc[KK_RFEAS];
+}
+static void do_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
+                                    const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
+    cx_check(h, "asm_solution_sensitivity");
+    if (!x || !bound_state || !dx || !info || (h->m > 0 && (!lambda || !row_state || !dlam)) || (h->ev_n_dpar > 0 && !dc))
+        throw std::invalid_argument("asm_solution_sensitivity: null pointer");
+    std::vector<double> u((size_t)std::max<int64_t>(h->n, 1)), w((size_t)std::max<int64_t>(h->m, 1));
+    do_data_cross(h, x, lambda, dc, u.data(), w.data());
+    do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info);
+}
+
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
 static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
     if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
@@ -4339,6 +4674,20 @@ int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double
 
 int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
     return guarded(h, [&] { do_data_gradient(h, x, lambda, out); });
+}
+
+int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w) {
+    return guarded(h, [&] { do_data_cross(h, x, lambda, dc, u, w); });
+}
+
+int asm_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru, const double* rw,
+                  const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
+    return guarded(h, [&] { do_kkt_solve(h, x, lambda, row_state, bound_state, ru, rw, par, dx, dlam, dz, info); });
+}
+
+int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
+                             const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
+    return guarded(h, [&] { do_solution_sensitivity(h, x, lambda, row_state, bound_state, dc, par, dx, dlam, dz, info); });
 }
 
 int asm_eval_hessian_structure(const asm_handle* ch, int64_t* nnz, int64_t* rows, int64_t* cols) {

@@ -24,6 +24,10 @@ derivative of the Lagrangian with respect to every dpar entry (at an SLP solutio
 Second derivatives: hessian_structure() / hessian_values(x, obj_factor, lam) are the host twin of the block's part of
 asm_eval_hessian_structure / asm_eval_hessian_lagrangian (forward over reverse per (row, seed variable); include/asm_hip.h,
 "Hessian of the Lagrangian"); the lists behind them are built when first asked for.
+
+Cross derivatives with respect to the data: data_cross(x, lam, dc) is the host twin of asm_eval_data_cross - the same sweep seeded in
+the constants - and gives d/dc (grad_x (f - lam' g)) . dc and (dg/dc) . dc, the right-hand sides of a solution sensitivity
+(activesetmethods_amd/sensitivity.py).
 """
 import numbers
 import struct
@@ -465,6 +469,7 @@ class _HessSweep(_Sweep):
 
     def __init__(self, start, lens, op, a, b, seed, okey, n):
         super().__init__(start, op, a, b, np.zeros(len(op), np.int64), lens=lens)
+        self.start = start
         self.aux = []
         for groups in self.steps:
             aux = []
@@ -480,7 +485,9 @@ class _HessSweep(_Sweep):
                     aux.append(None)
             self.aux.append(aux)
 
-    def forward2(self, x, consts):
+    def forward2(self, x, consts, dc=None):
+        """Values V and tangents D.  With `dc` (the data cross derivatives, expr_forward2<DATA>): the seed is that direction in the
+        constants - a CONST node with operand a has the tangent dc[a], every VAR node 0."""
         V = np.zeros((self.nr, max(self.K, 1)))
         D = np.zeros_like(V)
         with np.errstate(all="ignore"):
@@ -488,9 +495,11 @@ class _HessSweep(_Sweep):
                 for (o, r, a, b, _), aux in zip(groups, self.aux[k]):
                     if o == CONST:
                         V[r, k] = consts[a]
+                        if dc is not None:
+                            D[r, k] = dc[a]
                         continue
                     if o == VAR:
-                        V[r, k], D[r, k] = x[a], aux[0]
+                        V[r, k], D[r, k] = x[a], (aux[0] if dc is None else 0.0)
                         continue
                     u, du = V[r, a], D[r, a]
                     if o in _BINARY:
@@ -566,9 +575,10 @@ class _HessSweep(_Sweep):
                     V[r, k], D[r, k] = v, d
         return V, D
 
-    def reverse2(self, V, D, hocc):
+    def reverse2(self, V, D, hocc, weight=None):
         """Adjoints W and their tangents Z from the last node of every thread back; the adjoint tangent of a VAR node whose
-        variable is in the thread's occurrence list is added to hocc there."""
+        variable is in the thread's occurrence list is added to hocc there.  With `weight` (one per thread; expr_reverse2<DATA>):
+        every VAR node is an occurrence of its own, hocc[node in the tape] = weight * its adjoint tangent."""
         W = np.zeros_like(V)
         Z = np.zeros_like(V)
         W[np.arange(self.nr), self.last] = 1.0
@@ -579,6 +589,9 @@ class _HessSweep(_Sweep):
                         continue
                     w, z = W[r, k], Z[r, k]
                     if o == VAR:
+                        if weight is not None:
+                            hocc[self.start[r] + k] = weight[r] * z
+                            continue
                         _, rh, pos = aux
                         hocc[pos] = hocc[pos] + Z[rh, k]
                         continue
@@ -706,6 +719,7 @@ class ExprBlock(NlpBlock):
             raise TypeError("parameters must be nodes made by nlexpr.parameters")
         tape = Tape([e for e, _, _ in cons] + terms, len(cons), params)
         self.n_params = len(params)
+        self.params = params                               # the parameter nodes, in dpar order
         self.exprs = [e for e, _, _ in cons] + terms      # the graphs behind the tape: constraint rows, then objective terms
         self.tape = tape
         R, T = tape.R, tape.T
@@ -738,6 +752,7 @@ class ExprBlock(NlpBlock):
         self._terms = _Sweep(ptr[R:] - ptr[R], op[ptr[R]:], tape.a[ptr[R]:], tape.b[ptr[R]:], slot[ptr[R]:])
         self._n_occ = len(kv)
         self._hess = None                                  # second-order lists: made when a Hessian is first asked for
+        self._cross = None                                 # the same for the data cross derivatives
         super().__init__([lo for _, lo, _ in cons], [hi for _, _, hi in cons], rows, cols, self._eval_g, self._eval_jac_g,
                          device=("expr", tape.ipar(), self._consts),
                          has_objective=T > 0, eval_f=self._eval_f if T > 0 else None, eval_grad_f=self._eval_grad_f if T > 0 else None,
@@ -829,6 +844,40 @@ class ExprBlock(NlpBlock):
             s = cnt > i
             g[s] = g[s] + cocc[self.c_ptr[:-1][s] + i]
         return g
+
+    def data_cross(self, x, lam, dc, scale=1.0):
+        """Host twin of asm_eval_data_cross: (u, w) with u [n_var] = d/d dpar (grad_x (scale * f - lam' g)) . dc and w [R] =
+        (d g / d dpar) . dc, `lam` the multipliers of the block's rows, `dc` a direction in dpar.  Per row or term the forward-over-
+        reverse sweep of the Hessian seeded in the constants; the adjoint tangent of every VAR node, times -lam[r] in a row r and
+        `scale` in a term, is an occurrence; u[j] sums those of variable j from 0.0, rows before terms, nodes descending inside one
+        (k_nlp_expr_cross, k_nlp_expr_cross_gather)."""
+        tape = self.tape
+        R, T, L = tape.R, tape.T, tape.L
+        x, lam, dc = np.asarray(x, float), np.asarray(lam, float), np.asarray(dc, float)
+        if len(dc) != len(self._consts):
+            raise ValueError("%d data directions for %d constants" % (len(dc), len(self._consts)))
+        if self._cross is None:
+            ptr, op, a = tape.ptr, tape.op, tape.a
+            kv = np.nonzero(op == VAR)[0]
+            row = np.searchsorted(ptr, kv, side="right") - 1
+            order = np.lexsort((-kv, row, a[kv]))          # by variable, then row / term, then node descending
+            n_var = max(self.n_var, 1)
+            vptr = np.concatenate([[0], np.cumsum(np.bincount(a[kv], minlength=n_var))]).astype(np.int64)
+            sweep = _HessSweep(ptr[:-1].copy(), np.diff(ptr), op, a, tape.b, np.full(R + T, -1, np.int64), np.zeros(0, np.int64), n_var)
+            self._cross = (sweep, vptr, kv[order])
+        sweep, vptr, vnode = self._cross
+        u, w = np.zeros(len(vptr) - 1), np.zeros(R)
+        if not np.any(tape.op == CONST) or R + T == 0:
+            return u[:self.n_var], w
+        V, D = sweep.forward2(x, self._consts, dc=dc)
+        w[:] = D[np.arange(R), sweep.last[:R]]
+        vocc = np.zeros(L)
+        sweep.reverse2(V, D, vocc, weight=np.concatenate([-lam[:R], np.full(T, float(scale))]))
+        cnt = np.diff(vptr)
+        for i in range(int(cnt.max()) if len(cnt) else 0):
+            s = cnt > i
+            u[s] = u[s] + vocc[vnode[vptr[:-1][s] + i]]
+        return u[:self.n_var], w
 
     # ---- host callbacks (the twins of k_nlp_expr_rows / _terms / _objective / _gradient)
     def _eval_g(self, x, out):

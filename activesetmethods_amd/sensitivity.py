@@ -1,0 +1,200 @@
+"""Solution sensitivities at an SLP solution: how x* and its multipliers move with the data (include/asm_hip.h, "Cross derivatives of
+an expression block" and "The KKT solve on a working set").
+
+On the working set of a solution - the rows W that sit at a bound, the variables B that sit at a bound, F the other variables - the
+first-order change of (x*, lam*) along a direction dc of the data solves, with H the Hessian of f - lam' g, J the Jacobian, A = J[W, F],
+
+    H_FF dx_F - A' dlam_W = -u_F ,     A dx_F = -w_W ,     dx_B = 0 ,    dlam_i = 0 (i not in W)
+
+with u = d/dc (grad_x (f - lam' g)) . dc and w = (dg/dc) . dc (asm_eval_data_cross / ExprBlock.data_cross).  A constraint bound that
+moves by d(bound_i) enters as u = 0, w_i = -d(bound_i).
+
+    working_set          (row_state, bound_state) of a solution
+    kkt_reference        the system assembled densely and solved with numpy.linalg.solve: the independent answer
+    kkt_pcg              the NumPy twin of the device algorithm (asm_kkt_solve): Cholesky of A A', projected conjugate gradients
+    solution_sensitivity the device call on a handle, or on a fresh one for a Model
+    predict              the first-order prediction x + step * dx
+"""
+import numpy as np
+
+from .moi_evaluator import lagrangian_hessian
+
+PIVOT_THRESHOLD = 1e-10        # a pivot of A A' at or below this share of its diagonal entry is dropped (the library's static guard)
+DROPPED = 1e256                # ... by putting this value in its place: the row leaves the solves
+
+
+def dense_jacobian(fm, x):
+    """The m x n Jacobian of a FunctionModel at x (duplicates of the pattern add)."""
+    j_str = fm.jacobian_structure()
+    vals = fm.eval_jac_g(np.asarray(x, float), np.zeros(len(j_str)))
+    J = np.zeros((fm.m, fm.n))
+    if j_str:
+        r, c = np.array(j_str, np.int64).T - 1
+        np.add.at(J, (r, c), vals)
+    return J
+
+
+def working_set(problem, x, lam, mult_x_U, mult_x_L, tol=1e-8):
+    """(row_state [m] in {0, 1}, bound_state [n] in {-1, 0, +1}) at a solution of `problem` (n, m, x_L, x_U, g_L, g_U, eval_g).  A row is
+    in the working set when it is an equality or its value sits at a bound within tol * (1 + |bound|); a variable is at its lower
+    (-1) or upper (+1) bound likewise.  The multipliers are taken so that a solver's outputs pass through unchanged; only their
+    lengths are checked - activity decides, so that a degenerate active row (zero multiplier) stays in the set."""
+    x = np.asarray(x, float)
+    n, m = int(problem.n), int(problem.m)
+    if x.shape != (n,) or np.shape(lam) != (m,) or np.shape(mult_x_U) != (n,) or np.shape(mult_x_L) != (n,):
+        raise ValueError("x, lam, mult_x_U, mult_x_L must have shapes (n,), (m,), (n,), (n,)")
+    g_L, g_U = np.asarray(problem.g_L, float), np.asarray(problem.g_U, float)
+    x_L, x_U = np.asarray(problem.x_L, float), np.asarray(problem.x_U, float)
+    g = np.asarray(problem.eval_g(x, np.zeros(m)), float) if m else np.zeros(0)
+    with np.errstate(invalid="ignore"):
+        at = lambda v, b: np.isfinite(b) & (np.abs(v - b) <= tol * (1.0 + np.abs(b)))
+        row_state = ((g_L == g_U) | at(g, g_L) | at(g, g_U)).astype(np.int32)
+        lo, up = at(x, x_L), at(x, x_U)
+    bound_state = np.where(lo, -1, np.where(up, 1, 0)).astype(np.int32)
+    return row_state, bound_state
+
+
+def _sets(fm, row_state, bound_state, ru, rw):
+    rs, bs = np.asarray(row_state), np.asarray(bound_state)
+    ru, rw = np.asarray(ru, float), np.asarray(rw, float)
+    if rs.shape != (fm.m,) or bs.shape != (fm.n,) or ru.shape != (fm.n,) or rw.shape != (fm.m,):
+        raise ValueError("row_state, bound_state, ru, rw must have shapes (m,), (n,), (n,), (m,)")
+    if np.any((rs != 0) & (rs != 1)) or np.any(np.abs(bs) > 1):
+        raise ValueError("row_state must hold 0 / 1 and bound_state -1 / 0 / +1")
+    F, W = np.nonzero(bs == 0)[0], np.nonzero(rs == 1)[0]
+    if len(W) > len(F):
+        raise ValueError("more working rows (%d) than free variables (%d)" % (len(W), len(F)))
+    return F, W, ru, rw
+
+
+def _finish(H, J, F, W, ru, dxF, dlW, n, m):
+    dx, dlam = np.zeros(n), np.zeros(m)
+    dx[F], dlam[W] = dxF, dlW
+    full = H @ dx + ru - J[W].T @ dlW
+    dz = full.copy()
+    dz[F] = 0.0
+    return dx, dlam, dz
+
+
+def kkt_reference(fm, x, lam, row_state, bound_state, ru, rw):
+    """(dx, dlam, dz): the KKT system of the working set assembled densely, solved with numpy.linalg.solve."""
+    F, W, ru, rw = _sets(fm, row_state, bound_state, ru, rw)
+    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    A = J[np.ix_(W, F)]
+    nF, nW = len(F), len(W)
+    K = np.zeros((nF + nW, nF + nW))
+    K[:nF, :nF] = H[np.ix_(F, F)]
+    K[:nF, nF:] = -A.T
+    K[nF:, :nF] = A
+    sol = np.linalg.solve(K, np.concatenate([-ru[F], -rw[W]])) if nF + nW else np.zeros(0)
+    return _finish(H, J, F, W, ru, sol[:nF], sol[nF:], fm.n, fm.m)
+
+
+def _guarded_cholesky(S):
+    """Lower Cholesky factor with the library's static pivot guard: a pivot d <= PIVOT_THRESHOLD * S_ii becomes DROPPED.  Returns
+    (L, number of dropped pivots)."""
+    N = len(S)
+    L = np.zeros((N, N))
+    d0 = np.diag(S).copy()
+    dropped = 0
+    for j in range(N):
+        d = S[j, j] - L[j, :j] @ L[j, :j]
+        if not d > PIVOT_THRESHOLD * d0[j]:
+            d = DROPPED
+            dropped += 1
+        L[j, j] = np.sqrt(d)
+        L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return L, dropped
+
+
+def kkt_pcg(fm, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=1e-12):
+    """The NumPy twin of asm_kkt_solve, step by step the method of include/asm_hip.h: S = A A' factored with the pivot guard, the
+    particular solution dx0 = -A' S^-1 rw_W, projected conjugate gradients on null(A) with the projection applied twice per
+    iteration and the residual kept projected, the multipliers from S^-1 A (H_FF dx_F + ru_F); one refinement step for each of the
+    two normal-equation solves outside the iteration.  Returns (dx, dlam, dz, info), info a dict with the fields of
+    asm_kkt_info."""
+    F, W, ru, rw = _sets(fm, row_state, bound_state, ru, rw)
+    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    HF, A = H[np.ix_(F, F)], J[np.ix_(W, F)]
+    nF, nW = len(F), len(W)
+    if max_iter is None:
+        max_iter = 2 * (nF - nW) + 20
+    L, dropped = _guarded_cholesky(A @ A.T) if nW else (np.zeros((0, 0)), 0)
+
+    def s_solve(b):
+        if not nW:
+            return b
+        y = np.zeros(nW)
+        for i in range(nW):                                # forward, then backward substitution
+            y[i] = (b[i] - L[i, :i] @ y[:i]) / L[i, i]
+        z = np.zeros(nW)
+        for i in range(nW - 1, -1, -1):
+            z[i] = (y[i] - L[i + 1:, i] @ z[i + 1:]) / L[i, i]
+        return z
+
+    proj = lambda v: v - A.T @ s_solve(A @ v) if nW else v.copy()
+    dx0 = -(A.T @ s_solve(rw[W])) if nW else np.zeros(nF)
+    if nW:
+        dx0 = dx0 - A.T @ s_solve(A @ dx0 + rw[W])         # one refinement step of the normal-equation solve
+    d = np.zeros(nF)
+    status, iters = 0, 0
+    if nF > nW:
+        r = ru[F] + HF @ dx0
+        r = proj(proj(r))                                  # the residual is kept projected: r = g (no large component in range(A'))
+        g = r
+        rg, g0 = float(r @ g), float(np.sqrt(g @ g))
+        p = -g
+        stop = g0 == 0.0
+        while not stop:
+            if iters >= max_iter:
+                status = 1
+                break
+            hp = HF @ p
+            php = float(p @ hp)
+            if not php > 0.0:
+                status = 2
+                break
+            alpha = rg / php
+            d = d + alpha * p
+            r = r + alpha * hp
+            r = proj(proj(r))
+            g = r
+            rg_new = float(r @ g)
+            beta = rg_new / rg
+            rg = rg_new
+            iters += 1
+            stop = float(np.sqrt(g @ g)) <= rtol * g0
+            p = -g + beta * p
+    dxF = dx0 + d
+    q = HF @ dxF + ru[F]
+    dlW = s_solve(A @ q) if nW else np.zeros(0)
+    if nW:
+        dlW = dlW + s_solve(A @ (q - A.T @ dlW))           # one refinement step
+    if dropped:
+        status = 3
+    dx, dlam, dz = _finish(H, J, F, W, ru, dxF, dlW, fm.n, fm.m)
+    info = dict(status=status, cg_iters=iters, n_free=nF, n_rows=nW, dropped_pivots=dropped,
+                res_stat=float(np.abs(HF @ dxF - A.T @ dlW + ru[F]).max()) if nF else 0.0,
+                res_feas=float(np.abs(A @ dxF + rw[W]).max()) if nW else 0.0)
+    return dx, dlam, dz, info
+
+
+def solution_sensitivity(model_or_opt, fm, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):
+    """(dx, dlam, dz, info) of asm_solution_sensitivity for the FunctionModel `fm` (an expression block with its data) at the solution
+    (x, lam) with the working set given, along the direction dc of the block's data.  `model_or_opt`: a HipSubOptimizer whose
+    evaluator holds fm (eval_setup(fm)), or a Model built from fm - then a fresh handle is made for the call and closed again."""
+    from .subproblem import HipSubOptimizer, QpData
+    if isinstance(model_or_opt, HipSubOptimizer):
+        return model_or_opt.solution_sensitivity(x, lam, row_state, bound_state, dc, max_iter, rtol)
+    mdl = model_or_opt
+    opt = HipSubOptimizer(QpData(np.zeros(mdl.n), 0.0, np.zeros(len(mdl.j_row)), np.zeros(mdl.m), mdl.g_L, mdl.g_U, mdl.x_L, mdl.x_U), mdl.j_row, mdl.j_col)
+    try:
+        opt.eval_setup(fm)
+        return opt.solution_sensitivity(x, lam, row_state, bound_state, dc, max_iter, rtol)
+    finally:
+        opt.close()
+
+
+def predict(x, dx, step):
+    """The first-order prediction of the solution after the data moved by step * dc: x + step * dx."""
+    return np.asarray(x, float) + float(step) * np.asarray(dx, float)

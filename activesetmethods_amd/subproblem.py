@@ -282,6 +282,60 @@ class HipSubOptimizer:
         self._check(self._lib.asm_eval_hessian_product(self._h, _lib.dptr(x), float(obj_factor), _lib.dptr(lam), _lib.dptr(v), _lib.dptr(out)))
         return out
 
+    # ------------------------------------------------------------------ solution sensitivities (include/asm_hip.h: asm_eval_data_cross, asm_kkt_solve)
+    def _vec(self, a, length, name):
+        a = _f64(np.atleast_1d(a))
+        if a.shape != (length,):
+            raise ValueError("%s has shape %r, expected (%d,)" % (name, a.shape, length))
+        return a if length else np.zeros(1)
+
+    def _states(self, row_state, bound_state):
+        rs = np.ascontiguousarray(np.atleast_1d(row_state), dtype=np.int32) if self.m else np.zeros(0, np.int32)
+        bs = np.ascontiguousarray(np.atleast_1d(bound_state), dtype=np.int32)
+        if rs.shape != (self.m,) or bs.shape != (self.n,):
+            raise ValueError("row_state / bound_state have shapes %r / %r, expected (%d,) / (%d,)" % (rs.shape, bs.shape, self.m, self.n))
+        return (rs if self.m else np.zeros(1, np.int32)), bs
+
+    def data_cross(self, x, lam, dc):
+        """(u, w) of asm_eval_data_cross: u [n] = d/d dpar (grad_x (f - lam' g)) . dc and w [m] = (d g / d dpar) . dc for a direction dc in the
+        expression block's data, lam [m] in the sign convention of slp_run's multipliers."""
+        nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
+        x, lam, dc = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(dc, nd, "dc")
+        u, w = np.empty(self.n), np.empty(max(self.m, 1))
+        self._check(self._lib.asm_eval_data_cross(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(dc), _lib.dptr(u), _lib.dptr(w)))
+        return u, w[:self.m]
+
+    @staticmethod
+    def _kkt_params(max_iter, rtol):
+        if max_iter is None and rtol is None:
+            return None
+        if max_iter is None or rtol is None:
+            raise ValueError("give max_iter and rtol together (asm_kkt_params), or neither for the defaults")
+        return C.byref(_lib.KktParams(int(max_iter), float(rtol)))
+
+    def kkt_solve(self, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=None):
+        """(dx, dlam, dz, info) of asm_kkt_solve: the KKT system of the working set (row_state 0 / 1, bound_state -1 / 0 / +1) at (x, lam)
+        with the right-hand sides (-ru, -rw); info is the asm_kkt_info structure (status 0 solved, 1 iteration limit, 2 reduced Hessian
+        not positive definite, 3 dependent working rows)."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        ru, rw = self._vec(ru, self.n, "ru"), self._vec(rw, self.m, "rw")
+        rs, bs = self._states(row_state, bound_state)
+        dx, dlam, dz, info = np.empty(self.n), np.empty(max(self.m, 1)), np.empty(self.n), _lib.KktInfo()
+        self._check(self._lib.asm_kkt_solve(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), _lib.dptr(ru), _lib.dptr(rw),
+                                            self._kkt_params(max_iter, rtol), _lib.dptr(dx), _lib.dptr(dlam), _lib.dptr(dz), C.byref(info)))
+        return dx, dlam[:self.m], dz, info
+
+    def solution_sensitivity(self, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):
+        """(dx, dlam, dz, info) of asm_solution_sensitivity: the directional derivative of the solution and its multipliers along the
+        direction dc in the expression block's data, on the working set given."""
+        nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
+        x, lam, dc = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(dc, nd, "dc")
+        rs, bs = self._states(row_state, bound_state)
+        dx, dlam, dz, info = np.empty(self.n), np.empty(max(self.m, 1)), np.empty(self.n), _lib.KktInfo()
+        self._check(self._lib.asm_solution_sensitivity(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), _lib.dptr(dc),
+                                                       self._kkt_params(max_iter, rtol), _lib.dptr(dx), _lib.dptr(dlam), _lib.dptr(dz), C.byref(info)))
+        return dx, dlam[:self.m], dz, info
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)

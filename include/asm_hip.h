@@ -259,6 +259,23 @@ int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double
  * host twin (nlexpr.py: ExprBlock.data_gradient) agree bit for bit with ADD..POWI, ABS, MIN and MAX only, else in the last bits. */
 int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out);
 
+/* ---- Cross derivatives of an expression block with respect to its data: how the stationarity and feasibility residuals of an SLP
+ * solution move with dpar.  With L = f - lambda' g in the convention of asm_slp_run and asm_eval_data_gradient (f with the sense scale,
+ * lambda [m]) and a direction dc [n_dpar] in the data:
+ *   u [n] = d/d dpar (grad_x L) . dc        w [m] = (d g / d dpar) . dc    (0 for the rows of the function store: its constants are not data)
+ * Expression blocks only (other kinds: ASM_ERR_ARG); ASM_ERR_STATE before asm_eval_setup, ASM_ERR_ARG for a null pointer.  The inputs of the
+ * next LP are not touched (as asm_eval_constraints).  The per-variable occurrence list and the workspace are made by the first call after
+ * asm_eval_setup.  A tape without CONST node: u = w = 0 without a launch.
+ * Order: per row or term one forward-over-reverse sweep, the one of the Hessian (the statement tangents listed under "Hessian of the
+ * Lagrangian" below, each parenthesis one rounding, no fused multiply-add) with another seed: a CONST node with operand a has the tangent
+ * dc[a], every VAR node the tangent 0.  A CONST exponent of POW stays out of the sweep as in the first-order rule (no term with its
+ * tangent, nothing to its adjoint).  w[n_rows + r] is the tangent of the last node of block row r.  The adjoint tangent z that reaches a
+ * VAR node is one occurrence: (-lambda[n_rows + r]) * z for a node of block row r, objective_scale * z for a node of a term (one product).
+ * u[j] sums the occurrences of variable j from 0.0 in this order: rows in row order, then terms in term order; inside a row or term its VAR
+ * nodes of j in descending node order.  No atomics.  With ADD..POWI, ABS, MIN and MAX only, device and host twin (nlexpr.py:
+ * ExprBlock.data_cross) agree bit for bit, else in the math library's last bits. */
+int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w);
+
 /* ---- Hessian of the Lagrangian: hessian_lagrangian_structure / eval_hessian_lagrangian (MOI_wrapper.jl:748-774, 946-978; eval_h_cb :1071-1083)
  *   H = obj_factor * objective_scale * hess f + sum_i lambda_i hess g_i        lambda [m], PLUS sign (the MOI convention, :960-978, :1080)
  * asm_slp_run's multipliers belong to df - J'lambda: the Hessian of that Lagrangian is this one at (obj_factor 1, -lambda).
@@ -316,6 +333,50 @@ int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda,
 int asm_eval_hessian_structure(const asm_handle* h, int64_t* nnz, int64_t* rows, int64_t* cols);
 int asm_eval_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values);
 int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out);
+
+/* ---- The KKT solve on a working set: the equality-constrained QP behind solution sensitivities (and any later second-order step).
+ * With F = {j : bound_state[j] = 0} (the free variables, B its complement), W = {i : row_state[i] = 1} (the working rows), H the Hessian of
+ * f - lambda' g at x (what asm_eval_hessian_lagrangian(x, 1.0, -lambda) gives), J the Jacobian at x and A = J[W, F], asm_kkt_solve solves
+ *   H_FF dx_F - A' dlam_W = -ru_F ,    A dx_F = -rw_W ,    dx_B = 0 ,    dlam_i = 0 (i not in W) ,
+ *   dz_B = (H dx)_B + ru_B - (J_W' dlam_W)_B ,    dz_F = 0                       (dz may be NULL)
+ * Valid where the Hessian calls are: nlp_kind 0 or 3 after asm_eval_setup (ASM_ERR_STATE before); kinds 1 and 2, a null pointer, a state
+ * outside its value set (row_state 0 / 1, bound_state -1 / 0 / +1), |W| > |F| and par with max_iter < 0 or rtol not >= 0: ASM_ERR_ARG.
+ * par == NULL: max_iter = 2 (|F| - |W|) + 20, rtol = 1e-12.
+ * info.status is a result, not an error (the call returns ASM_OK and the handle works on):
+ *   0 solved   1 iteration limit   2 the reduced Hessian is not positive definite (p'Hp <= 0 met; the outputs are the iterate reached)
+ *   3 dependent working rows (dropped_pivots > 0; the answer is the least-squares one of the remaining rows)
+ * cg_iters, n_free = |F|, n_rows = |W|; res_stat / res_feas: the infinity norms of H_FF dx_F - A' dlam_W + ru_F and of A dx_F + rw_W for
+ * the returned solution.
+ * Everything runs on the handle's stream in buffers of the solve's own (released by asm_sublp_setup, asm_eval_setup and asm_destroy): the
+ * inputs of the next LP (dE, df, E, x_k), the retained basis, hints and active sets and the solver's factors do not change.  A and
+ * S = A A' are DENSE; the sparse, banded and null-space forms of the LP solver have no counterpart here.
+ * Method:
+ *   1. the Hessian values at (x, 1, -lambda), once; the Jacobian at x into a value buffer and a dense J of the solve's own
+ *   2. A gathered into a dense |W| x ldn operand with the columns of B zeroed; S = A A' by the rank-K build, factored by the library's
+ *      Cholesky with its static pivot guard (a pivot <= 1e-10 of its diagonal entry is dropped: its row leaves the solves)
+ *   3. particular solution dx0 = -A' S^-1 rw_W, with one refinement step of that normal-equation solve (dx0 -= A' S^-1 (A dx0 + rw_W))
+ *   4. projected conjugate gradients on null(A) for  min 1/2 d' H_FF d + (ru_F + H_FF dx0)' d :  P v = v - A' S^-1 A v, applied twice per
+ *      iteration; r0 = ru_F + H_FF dx0, g = P P r, p = -g; then  alpha = r'g / p'Hp, d += alpha p, r += alpha H p, g+ = P P r,
+ *      beta = r'g+ / r'g, p = -g+ + beta p.  The residual is kept projected (r := g after every projection, the same iteration in exact
+ *      arithmetic): its component in range(A') would otherwise stay as large as the right-hand side and the rounding of the normal-equation
+ *      solves, cond(A A') times the unit roundoff of that component, would bound what ||g|| can reach.  Stop at ||g||_2 <= rtol ||g0||_2, at once when g0 = 0 or |F| = |W| (a vertex), with status 2
+ *      when p'Hp <= 0.  H p is the Hessian product kernel on the values of step 1 with p zero on B.  alpha, beta and the curvature
+ *      test stay on the device; the host reads one stop word per iteration.
+ *   5. dx_F = dx0 + d;  dlam_W = S^-1 A q with q = H_FF dx_F + ru_F, and one refinement step dlam_W += S^-1 A (q - A' dlam_W);
+ *   6. dz and the residual norms.
+ * Sensitivity to constraint bounds needs no further entry: for a working row i whose bound moves by d(bound_i), call with ru = 0 and
+ * rw_i = -d(bound_i) (the loads of the ACOPF scenarios are such bounds). */
+typedef struct { int32_t max_iter; double rtol; } asm_kkt_params;
+typedef struct {
+    int32_t status, cg_iters, n_free, n_rows, dropped_pivots;
+    double res_stat, res_feas;
+} asm_kkt_info;
+int asm_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                  const double* ru, const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info);
+/* Solution sensitivity of an expression block's data: asm_eval_data_cross(x, lambda, dc) followed by asm_kkt_solve(ru = u, rw = w).  At an
+ * SLP solution with its working set, dx = (dx* / d dpar) . dc and dlam = (dlambda* / d dpar) . dc.  Expression blocks only. */
+int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                             const double* dc, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info);
 
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
