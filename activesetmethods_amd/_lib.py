@@ -115,6 +115,8 @@ PROTOTYPES = {
     "asm_eval_data_cross": (C.c_int, [_P, _D, _D, _D, _D, _D]),
     "asm_kkt_solve": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_solution_sensitivity": (C.c_int, [_P, _D, _D, _I32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_kkt_solve_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_solution_sensitivity_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_eval_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
     "asm_eval_hessian_lagrangian": (C.c_int, [_P, _D, C.c_double, _D, _D]),
     "asm_eval_hessian_product": (C.c_int, [_P, _D, C.c_double, _D, _D, _D]),
@@ -162,6 +164,7 @@ PROTOTYPES = {
     "asm_test_cholesky": (C.c_int, [_P, _D, C.c_int64, _D]),
     "asm_test_chol_solve": (C.c_int, [_P, _D, C.c_int64, _D, _D]),
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),
+    "asm_test_kkt_multi_rounds": (C.c_int, [_P, _I64, _I32]),
     "asm_test_panel_timeout": (C.c_int, [_P, C.c_int]),
     "asm_test_set_band": (C.c_int, [_P, C.c_int]),
     "asm_test_set_factor": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),

@@ -470,6 +470,15 @@ struct asm_handle {
     double *d_kk_part = nullptr, *d_kk_scal = nullptr, *h_kk = nullptr;
     unsigned* d_kk_arr = nullptr;
     int *d_kk_wrow = nullptr, *d_kk_cnt = nullptr;
+    // ... and of its many-column form (asm_kkt_solve_multi), made at the first such call (kkm_prepare): the blocks of one chunk over the
+    // variables, over the working rows and over all rows, the transposed factor, the unmasked transposed working rows, the per-column
+    // reduction state, the staging buffer
+    bool kkm_ready = false;
+    double *d_kkm_vec = nullptr, *d_kkm_row = nullptr, *d_kkm_dlf = nullptr, *d_kkm_Lt = nullptr, *d_kkm_AfT = nullptr, *d_kkm_part = nullptr, *d_kkm_scal = nullptr,
+           *h_kkm = nullptr;
+    unsigned *d_kkm_cnt = nullptr, *d_kkm_act = nullptr;
+    int64_t kkm_rounds = 0;         // lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
+    int kkm_last_active = 0;
     bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
     double* h_scal = nullptr;       // pinned scalar read-back; host-mapped: the reduction kernels store the block there themselves (scal_publish)
@@ -3061,7 +3070,7 @@ int row_kind(double lb, double ub) {
 // releases every buffer of the handle and resets the state that describes them
 void free_device(asm_handle* h) {
     h->mem.release(); h->mem_nsk.release(); h->mem_ev.release(); h->mem_kk.release();
-    h->kk_ready = false; h->kk_fac = FacBuf();
+    h->kk_ready = false; h->kkm_ready = false; h->kk_fac = FacBuf();
     h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
     h->ahTg_valid = false;
     h->col_capable = h->ahT_valid = h->nzT_valid = false;
@@ -3975,7 +3984,7 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     P.release();
     h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
     h->cx_ready = false; h->cx_C = ExprCross{};
-    h->mem_kk.release(); h->kk_ready = false; h->kk_fac = FacBuf();
+    h->mem_kk.release(); h->kk_ready = false; h->kkm_ready = false; h->kk_fac = FacBuf();
     FnStore& F = h->ev_F;
     F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
     const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
@@ -4638,6 +4647,300 @@ static void do_solution_sensitivity(asm_handle* h, const double* x, const double
     do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info);
 }
 
+// ---- many right-hand sides on one factor (include/asm_hip.h, "Many right-hand sides on one factor")
+static_assert(KKM_CW == ASM_KKT_CHUNK && KKM_CW % 32 == 0 && KKM_SCAL > KKM_ITERS, "the chunk width of the header is the kernels'");
+namespace {
+// at the first asm_kkt_solve_multi after asm_eval_setup: the buffers of one chunk, beside the single solve's in mem_kk
+void kkm_prepare(asm_handle* h) {
+    if (h->kkm_ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->mem_kk;
+    const hipStream_t s = h->stream;
+    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), ldT = h->kk_ldT, CW = KKM_CW, nd = std::max<int64_t>(h->ev_n_dpar, 1);
+    M.zeroed(h->d_kkm_vec, 14 * CW * ldn, s);
+    M.zeroed(h->d_kkm_row, 5 * CW * ldT, s);
+    M.zeroed(h->d_kkm_dlf, CW * Mp, s);
+    M.zeroed(h->d_kkm_Lt, h->kk_fac.ld * h->kk_fac.ld, s);
+    M.zeroed(h->d_kkm_AfT, ldn * ldT, s);
+    M.zeroed(h->d_kkm_part, CW * KK_MAXWG * KK_SLOTS, s);
+    M.zeroed(h->d_kkm_scal, CW * KKM_SCAL + 16, s);
+    M.zeroed(h->d_kkm_cnt, CW + 4, s);
+    M.zeroed(h->d_kkm_act, CW, s);
+    M.alloc(h->h_kkm, CW * (3 * ldn + ldT + Mp + KKM_SCAL + nd) + 64, BufPool::PINNED);
+    HIPCHK(asmb::sync(s));
+    h->kkm_ready = true;
+}
+}  // namespace
+// asm_kkt_solve_multi (DC == nullptr: the rows of RU, RW are the right-hand sides) and asm_solution_sensitivity_multi (the rows of DC
+// are directions of the data: the cross-derivative sweep makes each column's right-hand sides on the device).  Steps 1 and 2 of the
+// method once per call, then chunks of KKM_CW columns through steps 3 to 6 on blocks.
+static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                               const double* RU, const double* RW, const double* DC, bool sens, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
+                               asm_kkt_info* info) {
+    const std::string me(who);
+    if (sens) cx_check(h, who);
+    hs_check(h, who);
+    const int64_t n = h->n, m = h->m, ldn = h->ldn, nd = sens ? h->ev_n_dpar : 0;
+    if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
+    if (!x || !bound_state || !DX || !info || (m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
+    if (sens ? (nd > 0 && !DC) : (!RU || (m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
+    int64_t nF = 0, nW = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
+        nF += bound_state[j] == 0;
+    }
+    for (int64_t i = 0; i < m; ++i) {
+        if (row_state[i] != 0 && row_state[i] != 1) throw std::invalid_argument(me + ": row_state holds a value outside {0, 1}");
+        nW += row_state[i];
+    }
+    if (nW > nF) throw std::invalid_argument(me + ": more working rows (" + std::to_string(nW) + ") than free variables (" + std::to_string(nF) + ")");
+    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
+    const int64_t max_iter = par ? par->max_iter : 2 * (nF - nW) + 20;
+    const double rtol = par ? par->rtol : 1e-12;
+    if (asmb::in_fiber()) throw std::logic_error(me + ": not inside a scenario batch");
+    hs_prepare(h);
+    kk_prepare(h);
+    kkm_prepare(h);
+    const bool cross = sens && h->d_ev_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
+    if (cross) cx_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    Dev dev(h);
+    const hipStream_t s = h->stream;
+    const int64_t Mp = std::max<int64_t>(h->Mp, 32), ldT = h->kk_ldT, CW = KKM_CW, nWp = round_up(nW, 32);
+    double* const mask = h->d_kk_vec;
+    auto vblock = [&](int k) { return h->d_kkm_vec + (int64_t)k * CW * ldn; };
+    auto rblock = [&](int k) { return h->d_kkm_row + (int64_t)k * CW * ldT; };
+    double *b_ru = vblock(0), *dx0 = vblock(1), *cd = vblock(2), *cr = vblock(3), *cp = vblock(4), *hraw = vblock(5), *hp = vblock(6), *tt = vblock(7), *ddx = vblock(8),
+           *hdx = vblock(9), *qq = vblock(10), *jtl = vblock(11), *ddz = vblock(12), *cg = vblock(13);
+    double *rww = rblock(0), *tw = rblock(1), *xw = rblock(2), *dlw = rblock(3), *adx = rblock(4);
+    double* const dlf = h->d_kkm_dlf;
+    double* const scal = h->d_kkm_scal;
+    const KktMulti R{h->d_kkm_part, h->d_kkm_cnt, scal, h->d_kkm_act, h->d_hscal, h->d_hseq};
+    // 1. the Hessian values of f - lambda' g at x, once (x goes to d_ev_xt)
+    {
+        std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
+        for (int64_t i = 0; i < m; ++i) nl[i] = -lambda[i];
+        hs_launch(h, x, 1.0, nl.data(), nullptr);
+    }
+    const HsShared& L = *h->hs_sh;
+    // 2. the Jacobian at x into the solve's own value buffer and dense J
+    {
+        const FnStore& F = h->ev_F;
+        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, 1, (int64_t)0, (int64_t)0);
+        const ExprTape& X = h->ev_X;
+        if (h->ev_nlp_kind == ASM_NLP_EXPR && X.R > 0)
+            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, F.n_rows, h->ev_fn_nnz, 1, (int64_t)0, (int64_t)0);
+        if (h->dense_fast) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->m * h->n + 255) / 256, 4096);
+            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, h->d_kk_dE, h->d_kk_J, h->m, h->n, ldn);
+        } else if (h->nu > 0) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
+            asmb::launch(k_assemble, dim3(g), dim3(256), s, h->d_kk_dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, h->d_kk_J, h->nu);
+        }
+    }
+    // the sets
+    std::vector<int> wl((size_t)Mp, 0);
+    {
+        double* st = h->h_kk;
+        for (int64_t j = 0; j < ldn; ++j) st[j] = (j < n && bound_state[j] == 0) ? 1.0 : 0.0;
+        int* dl = reinterpret_cast<int*>(st + ldn);
+        int64_t q = 0;
+        for (int64_t i = 0; i < m; ++i)
+            if (row_state[i]) wl[q++] = (int)i;
+        std::copy(wl.begin(), wl.end(), dl);
+        HIPCHK(asmb::copy_async(mask, st, ldn * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(asmb::copy_async(h->d_kk_wrow, dl, Mp * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    const dim3 gl = asmb::blocks(ldn);
+    const unsigned gred = (unsigned)std::min<int64_t>(gl.x, KK_MAXWG);
+    // A = J[W, F] as a dense operand, its transposed copy with the k-padding cleared, the unmasked transposed rows (for J' dlam on B);
+    // S = A A', its factor with the wide-block inverses (Dev::chol makes them) and the factor's transposed copy for the backward pass
+    if (nW > 0) {
+        const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((nWp + 63) / 64));
+        asmb::launch(k_kkt_gather, dim3(gl.x, (unsigned)nW), dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, mask, nW, h->d_kk_Aw);
+        asmb::launch(k_kktm_gather_t, gt, dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, mask, nW, nWp, h->d_kk_AwT, ldT);
+        asmb::launch(k_kktm_gather_t, gt, dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, (const double*)nullptr, nW, nWp, h->d_kkm_AfT, ldT);
+        dev.launch_syrk(s, Dev::pick_tile(nW), h->d_kk_Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, h->kk_fac.S, h->kk_fac.ld, 0, 0);
+        dev.diag_prepare(h->kk_fac, (int)nW, 1, 0.0, 0.0);
+        const int nfact = h->stats.nfact;
+        dev.chol(h->kk_fac, (int)nW, 1e-10);
+        h->stats.nfact = nfact;
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, h->kk_fac.S, h->kk_fac.ld, (int)nW, NS_BIG, h->d_kk_cnt);
+        // (its rows up to |W| rounded up to 32 are cleared first: the k-padding beside the nW x nW square the transposition writes)
+        HIPCHK(asmb::fill_async(h->d_kkm_Lt, 0, nWp * h->kk_fac.ld * sizeof(double), s));
+        asmb::launch(k_transpose_dense, dim3((unsigned)((nW + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, h->kk_fac.S, h->kk_fac.ld, nW, nW, h->d_kkm_Lt, h->kk_fac.ld, nW);
+    } else {
+        HIPCHK(asmb::fill_async(h->d_kk_cnt, 0, 4 * sizeof(int), s));
+    }
+    // the blocks over the working rows are zero beyond column nW (the k-padding of the products that read them)
+    HIPCHK(asmb::fill_async(h->d_kkm_row, 0, 5 * CW * ldT * sizeof(double), s));
+    if (cross) {      // the multipliers of the expression rows, once
+        const ExprTape& X = h->ev_X;
+        if (X.R > 0) {
+            std::memcpy(h->h_cx, lambda + h->ev_F.n_rows, X.R * sizeof(double));
+            HIPCHK(asmb::copy_async(h->d_cx_in, h->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+    }
+    auto pub_next = [&]() -> unsigned {
+        if (!h->knobs.spin_read) return 0;
+        h->scal_seq += 1;
+        if (h->scal_seq == 0) h->scal_seq = 1;
+        return h->scal_seq;
+    };
+    // the number of columns still active after the last k_kktm_cg_dir
+    auto read_active = [&](unsigned pub) -> int {
+        if (pub == 0) {
+            HIPCHK(asmb::copy_async(h->h_scal, scal + CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(asmb::sync(s));
+        } else {
+            kk_read_scal(h, pub);
+        }
+        return (int)h->h_scal[0];
+    };
+    int dropped = 0;
+    h->kkm_rounds = 0;
+    h->kkm_last_active = 0;
+    for (int64_t c0 = 0; c0 < nrhs; c0 += CW) {
+        const int cols = (int)std::min<int64_t>(CW, nrhs - c0);
+        const dim3 glc(gl.x, (unsigned)cols), grc((unsigned)((nW + 255) / 256), (unsigned)cols);
+        double* st = h->h_kkm;                                   // [ru block | rw block | directions], then the results
+        double* back = st + CW * (ldn + ldT + std::max<int64_t>(h->ev_n_dpar, 1));
+        auto axpby = [&](double sa, const double* a, double sb, const double* b, const double* sc, double* out) {
+            asmb::launch(k_kktm_axpby, glc, dim3(256), s, sa, a, sb, b, (const double*)mask, ldn, ldn, sc, out);
+        };
+        auto axpby_rows = [&](double sa, const double* a, double sb, const double* b, double* out) {
+            asmb::launch(k_kktm_axpby, grc, dim3(256), s, sa, a, sb, b, (const double*)nullptr, nW, ldT, (const double*)nullptr, out);
+        };
+        auto hess_product = [&](const double* v, double* out) {
+            const dim3 g = asmb::blocks(n);
+            if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+            else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+            else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+            else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+        };
+        auto mul_A = [&](const double* v, double* t) { dev.gemm_nt(v, ldn, h->d_kk_Aw, ldn, nullptr, 0, t, ldT, cols, (int)nW, (int)ldn, 0); };                 // T = V A'
+        auto mul_AT = [&](const double* y, const double* at, double* v) { dev.gemm_nt(y, ldT, at, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)nWp, 0); };      // V = Y A
+        auto solve_S = [&](double* t) { dev.trsm_rows(h->kk_fac, t, xw, ldT, cols, (int)nW, h->d_kkm_Lt); };                                                    // in place
+        // v -= A' S^-1 A v for the columns that sc leaves active (all of them when sc == nullptr)
+        auto project = [&](double* v, const double* sc) {
+            if (nW == 0) return;
+            mul_A(v, tw);
+            solve_S(tw);
+            mul_AT(tw, h->d_kk_AwT, tt);
+            axpby(1.0, v, -1.0, tt, sc, v);
+        };
+        // 3. the right-hand sides of the chunk
+        if (!sens) {
+            for (int c = 0; c < cols; ++c) {
+                const double *u = RU + (c0 + c) * n, *w = RW ? RW + (c0 + c) * m : nullptr;
+                double *du = st + (int64_t)c * ldn, *dw = st + CW * ldn + (int64_t)c * ldT;
+                std::memcpy(du, u, n * sizeof(double));
+                for (int64_t j = n; j < ldn; ++j) du[j] = 0.0;
+                for (int64_t q = 0; q < ldT; ++q) dw[q] = q < nW ? w[wl[q]] : 0.0;
+            }
+            HIPCHK(asmb::copy_async(b_ru, st, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
+            HIPCHK(asmb::copy_async(rww, st + CW * ldn, (int64_t)cols * ldT * sizeof(double), hipMemcpyHostToDevice, s));
+        } else if (cross) {
+            // one sweep per direction, no synchronisation between them: every direction has its own staging row
+            const ExprTape& X = h->ev_X;
+            double* hd = st + CW * (ldn + ldT);
+            for (int c = 0; c < cols; ++c) {
+                std::memcpy(hd + (int64_t)c * nd, DC + (c0 + c) * nd, nd * sizeof(double));
+                HIPCHK(asmb::copy_async(h->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
+                asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->cx_C, h->d_ev_xt, h->d_cx_in + X.R, h->d_cx_in, h->ev_F.objective_scale, h->d_cx_out + n);
+                asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->cx_C, n, h->d_cx_out);
+                asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->d_cx_out, n, (int64_t)h->ev_F.n_rows, h->d_kk_wrow, nW, b_ru + (int64_t)c * ldn,
+                             rww + (int64_t)c * ldT);
+            }
+        } else {
+            HIPCHK(asmb::fill_async(b_ru, 0, CW * ldn * sizeof(double), s));
+            HIPCHK(asmb::fill_async(rww, 0, CW * ldT * sizeof(double), s));
+        }
+        HIPCHK(asmb::fill_async(scal, 0, (CW * KKM_SCAL + 16) * sizeof(double), s));
+        // particular solution dx0 = -A' S^-1 rw_W with one refinement step
+        if (nW > 0) {
+            HIPCHK(asmb::copy_async(tw, rww, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
+            solve_S(tw);
+            mul_AT(tw, h->d_kk_AwT, tt);
+            axpby(-1.0, tt, 0.0, nullptr, nullptr, dx0);
+            mul_A(dx0, adx);
+            axpby_rows(1.0, adx, 1.0, rww, tw);
+            solve_S(tw);
+            mul_AT(tw, h->d_kk_AwT, tt);
+            axpby(1.0, dx0, -1.0, tt, nullptr, dx0);
+        } else {
+            HIPCHK(asmb::fill_async(dx0, 0, CW * ldn * sizeof(double), s));
+        }
+        // 4. the columns' projected conjugate gradients in lockstep
+        HIPCHK(asmb::fill_async(cd, 0, CW * ldn * sizeof(double), s));
+        const bool run_cg = nF > nW;
+        if (run_cg) {
+            hess_product(dx0, hraw);
+            axpby(1.0, b_ru, 1.0, hraw, nullptr, cr);
+            HIPCHK(asmb::fill_async(cp, 0, CW * ldn * sizeof(double), s));
+            project(cr, nullptr);
+            project(cr, nullptr);
+            unsigned pub = pub_next();
+            asmb::launch(k_kktm_cg_dir, dim3(gred, (unsigned)cols), dim3(256), s, R, (const double*)cr, ldn, ldn, 1, rtol, pub);
+            int active = read_active(pub);
+            for (int64_t it = 0; active > 0 && it < max_iter; ++it) {
+                asmb::launch(k_kktm_cg_p, glc, dim3(256), s, (const double*)scal, (const double*)cr, cp, ldn, ldn);
+                hess_product(cp, hraw);
+                asmb::launch(k_kktm_cg_curv, dim3(gred, (unsigned)cols), dim3(256), s, R, (const double*)cp, (const double*)hraw, (const double*)mask, hp, ldn, ldn);
+                asmb::launch(k_kktm_cg_step, glc, dim3(256), s, (const double*)scal, (const double*)cp, (const double*)hp, cd, cr, ldn, ldn);
+                project(cr, scal);
+                project(cr, scal);
+                pub = pub_next();
+                asmb::launch(k_kktm_cg_dir, dim3(gred, (unsigned)cols), dim3(256), s, R, (const double*)cr, ldn, ldn, 0, rtol, pub);
+                active = read_active(pub);
+                h->kkm_rounds += 1;
+            }
+            h->kkm_last_active = active;
+        }
+        // 5., 6. the solutions, their multipliers and residuals
+        axpby(1.0, dx0, 1.0, cd, nullptr, ddx);
+        hess_product(ddx, hdx);
+        HIPCHK(asmb::fill_async(dlf, 0, CW * Mp * sizeof(double), s));
+        if (nW > 0) {
+            axpby(1.0, hdx, 1.0, b_ru, nullptr, qq);
+            mul_A(qq, tw);
+            solve_S(tw);
+            HIPCHK(asmb::copy_async(dlw, tw, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
+            mul_AT(dlw, h->d_kk_AwT, tt);
+            axpby(1.0, qq, -1.0, tt, nullptr, cg);
+            mul_A(cg, tw);
+            solve_S(tw);
+            axpby_rows(1.0, dlw, 1.0, tw, dlw);
+            asmb::launch(k_kktm_scatter, grc, dim3(256), s, (const double*)dlw, ldT, h->d_kk_wrow, nW, dlf, Mp);
+            mul_A(ddx, adx);
+            mul_AT(dlw, h->d_kkm_AfT, jtl);          // J_W' dlam_W over all columns, the bound columns too
+        } else {
+            HIPCHK(asmb::fill_async(jtl, 0, CW * ldn * sizeof(double), s));
+        }
+        asmb::launch(k_kktm_finish, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)hdx, (const double*)b_ru, (const double*)jtl, (const double*)mask, n, ldn,
+                     (const double*)adx, (const double*)rww, nW, ldT, ddz);
+        HIPCHK(asmb::copy_async(back, ddx, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::copy_async(back + CW * ldn, ddz, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::copy_async(back + 2 * CW * ldn, dlf, (int64_t)cols * Mp * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::copy_async(back + CW * (2 * ldn + Mp), scal, (int64_t)cols * KKM_SCAL * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (c0 == 0) HIPCHK(asmb::copy_async(back + CW * (2 * ldn + Mp + KKM_SCAL), h->d_kk_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::sync(s));
+        if (c0 == 0) dropped = *reinterpret_cast<const int*>(back + CW * (2 * ldn + Mp + KKM_SCAL));
+        for (int c = 0; c < cols; ++c) {
+            std::memcpy(DX + (c0 + c) * n, back + (int64_t)c * ldn, n * sizeof(double));
+            if (DZ) std::memcpy(DZ + (c0 + c) * n, back + CW * ldn + (int64_t)c * ldn, n * sizeof(double));
+            if (m > 0) std::memcpy(DLAM + (c0 + c) * m, back + 2 * CW * ldn + (int64_t)c * Mp, m * sizeof(double));
+            const double* sc = back + CW * (2 * ldn + Mp) + (int64_t)c * KKM_SCAL;
+            asm_kkt_info& o = info[c0 + c];
+            const int stop = (int)sc[KK_STOP];
+            o.status = dropped > 0 ? 3 : (stop == 2 ? 2 : (run_cg && stop == 0 ? 1 : 0));
+            o.cg_iters = (int32_t)sc[KKM_ITERS]; o.n_free = (int32_t)nF; o.n_rows = (int32_t)nW; o.dropped_pivots = dropped;
+            o.res_stat = sc[KK_RSTAT]; o.res_feas = sc[KK_RFEAS];
+        }
+    }
+    dev.resolve_timing();
+}
+
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
 static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
     if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
@@ -4688,6 +4991,25 @@ int asm_kkt_solve(asm_handle* h, const double* x, const double* lambda, const in
 int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
                              const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
     return guarded(h, [&] { do_solution_sensitivity(h, x, lambda, row_state, bound_state, dc, par, dx, dlam, dz, info); });
+}
+
+int asm_kkt_solve_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* RU,
+                        const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(h, [&] { do_kkt_solve_multi(h, "asm_kkt_solve_multi", x, lambda, row_state, bound_state, nrhs, RU, RW, nullptr, false, par, DX, DLAM, DZ, info); });
+}
+
+int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* DC,
+                                   const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(h, [&] {
+        do_kkt_solve_multi(h, "asm_solution_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, true, par, DX, DLAM, DZ, info);
+    });
+}
+
+int asm_test_kkt_multi_rounds(const asm_handle* h, int64_t* rounds, int32_t* last_active) {
+    if (!h || !rounds || !last_active) return ASM_ERR_ARG;
+    *rounds = h->kkm_rounds;
+    *last_active = h->kkm_last_active;
+    return ASM_OK;
 }
 
 int asm_eval_hessian_structure(const asm_handle* ch, int64_t* nnz, int64_t* rows, int64_t* cols) {

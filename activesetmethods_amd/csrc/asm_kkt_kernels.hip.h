@@ -170,3 +170,222 @@ __global__ __launch_bounds__(1024) void k_kkt_finish(AsmBt abt, KktRed R, const 
     rf = blk_reduce_max(rf, sh);
     if (threadIdx.x == 0) { R.scal[KK_RSTAT] = rs; R.scal[KK_RFEAS] = rf; }
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Many right-hand sides per solve (asm_kkt_solve_multi; include/asm_hip.h, "Many right-hand sides on one factor").  The columns of a
+// chunk are the rows of row-major blocks: KKM_CW rows of pitch ldv over the variables, of pitch ldr over the working rows.  Products
+// with A and A' and the substitutions are k_gemm_nt launches (Dev::gemm_nt, Dev::trsm_rows); the kernels here are the rest.  Each has
+// the column in blockIdx.y and does for it what its single-column form does: K independent iterations that advance together.  A
+// column whose stop code is set is frozen - no kernel writes its d, r or p again.  Every sum of a column runs in an order fixed by the
+// vector length alone, so a column's bits depend neither on the number of columns nor on its place among them.
+#define KKM_CW 64          // columns per chunk (= ASM_KKT_CHUNK)
+#define KKM_SCAL 16        // doubles per column's scalar block: the KK_* slots, then
+enum { KKM_ITERS = KK_COUNT };      // ... the iterations the column has completed
+struct KktMulti {
+    double* part;        // KKM_CW x KK_MAXWG x KK_SLOTS partial sums
+    unsigned* cnt;       // KKM_CW arrival counters of the columns' workgroups, then [KKM_CW] the counter of finished columns; 0 between launches
+    double* scal;        // KKM_CW x KKM_SCAL scalars in HBM, then [KKM_CW * KKM_SCAL] the number of active columns (as a double)
+    unsigned* active;    // KKM_CW flags: the column's iteration goes on
+    double* hscal;       // host-mapped: [0] the number of active columns
+    unsigned* hseq;      // its sequence word
+};
+__device__ __forceinline__ KktRed kkm_col(const KktMulti& M, int c) {
+    return KktRed{M.part + (int64_t)c * KK_MAXWG * KK_SLOTS, M.cnt + c, M.scal + (int64_t)c * KKM_SCAL, nullptr, nullptr};
+}
+
+// AT[j, q] = J[wrow[q], j] for q < nW (mask != nullptr: 0 where mask[j] == 0), 0 for nW <= q < nWp: the working rows transposed into an
+// ldn x ldt operand, its k-padding cleared (64 x 64 LDS tiles; blockIdx.x over j, blockIdx.y over q)
+__global__ __launch_bounds__(256) void k_kktm_gather_t(AsmBt abt, const double* __restrict__ J, int64_t ldn, const int* __restrict__ wrow, const double* __restrict__ mask, int64_t nW, int64_t nWp, double* __restrict__ AT, int64_t ldt) {
+    ASM_BARGS(abt, J, ldn, wrow, mask, nW, nWp, AT, ldt);
+    __shared__ double tile[64 * 65];
+    const int64_t q0 = (int64_t)blockIdx.y * 64, j0 = (int64_t)blockIdx.x * 64;
+    _Pragma("unroll") for (int e_it = 0; e_it < 16; ++e_it) {
+        const int e = threadIdx.x + 256 * e_it;
+        const int r = e >> 6, c = e & 63;          // row q0 + r of the gather, column j0 + c
+        double v = 0.0;
+        if (q0 + r < nW && j0 + c < ldn && (!mask || mask[j0 + c] != 0.0)) v = J[(int64_t)wrow[q0 + r] * ldn + j0 + c];
+        tile[r * 65 + c] = v;
+    }
+    __syncthreads();
+    _Pragma("unroll") for (int e_it = 0; e_it < 16; ++e_it) {
+        const int e = threadIdx.x + 256 * e_it;
+        const int r = e >> 6, c = e & 63;          // out row j0 + r, out column q0 + c
+        if (j0 + r < ldn && q0 + c < nWp) AT[(j0 + r) * ldt + q0 + c] = tile[c * 65 + r];
+    }
+}
+// OUT[c, :] = H V[c, :] for the NC columns of a chunk from the values evaluated once: one thread per variable walks its list as
+// k_hess_product does and uses every (value, other index) pair it reads for all the columns.  Per column the sum is k_hess_product's:
+// entry order, from 0.0, no contraction - the same bits.  Rows >= cols of V are read (they exist: the blocks have KKM_CW rows), not written.
+template <int NC>
+__global__ __launch_bounds__(256) void k_kktm_hess_product(AsmBt abt, const int64_t* __restrict__ pptr, const int64_t* __restrict__ pent, const int64_t* __restrict__ poth, const double* __restrict__ values, const double* __restrict__ V, int64_t ldv, int64_t n, int cols, double* __restrict__ OUT) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, pptr, pent, poth, values, V, ldv, n, cols, OUT);
+    const int64_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double g[NC];
+    _Pragma("unroll") for (int c = 0; c < NC; ++c) g[c] = 0.0;
+    for (int64_t q = pptr[i]; q < pptr[i + 1]; ++q) {
+        const double val = values[pent[q]];
+        const double* v = V + poth[q];
+        _Pragma("unroll") for (int c = 0; c < NC; ++c) g[c] = g[c] + val * v[(int64_t)c * ldv];
+    }
+    _Pragma("unroll") for (int c = 0; c < NC; ++c)
+        if (c < cols) OUT[(int64_t)c * ldv + i] = g[c];
+}
+// out[c, j] = sa * a[c, j] + sb * b[c, j] where mask[j] != 0, 0 elsewhere (b == nullptr: sa * a; mask == nullptr, blocks over the rows:
+// everywhere); scal != nullptr: the frozen columns are left alone.  Blocks of pitch ld, blockIdx.y = c.  (out may be a)
+__global__ __launch_bounds__(256) void k_kktm_axpby(AsmBt abt, double sa, const double* a, double sb, const double* b, const double* __restrict__ mask, int64_t len, int64_t ld, const double* __restrict__ scal, double* out) {
+    ASM_BARGS(abt, sa, a, sb, b, mask, len, ld, scal, out);
+    const int64_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= len || (scal && scal[c * KKM_SCAL + KK_STOP] != 0.0)) return;
+    const int64_t e = c * ld + j;
+    double v = sa * a[e];
+    if (b) v += sb * b[e];
+    out[e] = (!mask || mask[j] != 0.0) ? v : 0.0;
+}
+// out[c, wrow[q]] = y[c, q] (out cleared before; pitches ldy, ldo)
+__global__ __launch_bounds__(256) void k_kktm_scatter(AsmBt abt, const double* __restrict__ y, int64_t ldy, const int* __restrict__ wrow, int64_t nW, double* __restrict__ out, int64_t ldo) {
+    ASM_BARGS(abt, y, ldy, wrow, nW, out, ldo);
+    const int64_t c = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nW) out[c * ldo + wrow[q]] = y[c * ldy + q];
+}
+// the right-hand sides of one direction from the cross-derivative sweep's output cx = [u (n) | w of the expression rows]:
+// ru[j] = u[j], rww[q] = w[wrow[q]] (0 for a working row of the function store: its data are not parameters)
+__global__ __launch_bounds__(256) void k_kktm_cross_rhs(AsmBt abt, const double* __restrict__ cx, int64_t n, int64_t n_fn, const int* __restrict__ wrow, int64_t nW, double* __restrict__ ru, double* __restrict__ rww) {
+    ASM_BARGS(abt, cx, n, n_fn, wrow, nW, ru, rww);
+    const int64_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j < n) ru[j] = cx[j];
+    if (j < nW) {
+        const int64_t i = wrow[j];
+        rww[j] = i >= n_fn ? cx[n + i - n_fn] : 0.0;
+    }
+}
+// p[c] = -g[c] + beta_c p[c] for the active columns
+__global__ __launch_bounds__(256) void k_kktm_cg_p(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ g, double* __restrict__ p, int64_t len, int64_t ldv) {
+    ASM_BARGS(abt, scal, g, p, len, ldv);
+    const int64_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    const double* sc = scal + c * KKM_SCAL;
+    if (j >= len || sc[KK_STOP] != 0.0) return;
+    const double beta = sc[KK_BETA];
+    p[c * ldv + j] = beta * p[c * ldv + j] - g[c * ldv + j];
+}
+// per active column: hp = (H p) on F; p'Hp; alpha = r'g / p'Hp, or the curvature stop
+__global__ __launch_bounds__(256) void k_kktm_cg_curv(AsmBt abt, KktMulti M, const double* __restrict__ p, const double* __restrict__ hp_raw, const double* __restrict__ mask, double* __restrict__ hp, int64_t len, int64_t ldv) {
+    ASM_BARGS(abt, M, p, hp_raw, mask, hp, len, ldv);
+    __shared__ double sh[4];
+    __shared__ bool last;
+    const int64_t c = blockIdx.y;
+    const KktRed R = kkm_col(M, (int)c);
+    if (R.scal[KK_STOP] != 0.0) return;          // (set by an earlier launch: the same in every workgroup of the column)
+    double acc = 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256) {
+        const double v = mask[j] != 0.0 ? hp_raw[c * ldv + j] : 0.0;
+        hp[c * ldv + j] = v;
+        acc += p[c * ldv + j] * v;
+    }
+    acc = blk_reduce_sum(acc, sh);
+    if (gridDim.x > 1) {
+        if (threadIdx.x == 0) kk_store(R, 0, acc);
+        if (!kk_last_arrival(R, &last)) return;
+        if (threadIdx.x == 0) acc = kk_total(R, 0);
+    }
+    if (threadIdx.x == 0) {
+        R.scal[KK_PHP] = acc;
+        if (!(acc > 0.0)) {      // the curvature stop: the column leaves the active count that the round's k_kktm_cg_dir adds up
+            R.scal[KK_STOP] = 2.0;
+            __hip_atomic_store(M.active + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            R.scal[KK_ALPHA] = R.scal[KK_RG] / acc;
+        }
+    }
+}
+// d[c] += alpha_c p[c], r[c] += alpha_c hp[c] for the active columns
+__global__ __launch_bounds__(256) void k_kktm_cg_step(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ p, const double* __restrict__ hp, double* __restrict__ d, double* __restrict__ r, int64_t len, int64_t ldv) {
+    ASM_BARGS(abt, scal, p, hp, d, r, len, ldv);
+    const int64_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    const double* sc = scal + c * KKM_SCAL;
+    if (j >= len || sc[KK_STOP] != 0.0) return;
+    const double alpha = sc[KK_ALPHA];
+    const int64_t e = c * ldv + j;
+    d[e] += alpha * p[e];
+    r[e] += alpha * hp[e];
+}
+// per active column, with the projected residual r = g in place: r'g and g'g, beta, the convergence test against the column's own
+// ||g0|| and its iteration count (init: the reference norm, beta = 0, g0 = 0 stops at once).  The workgroup that finishes a column
+// counts the column in; the one that finishes the last column counts the columns still active and hands that word to the host.
+__global__ __launch_bounds__(256) void k_kktm_cg_dir(AsmBt abt, KktMulti M, const double* __restrict__ r, int64_t len, int64_t ldv, int init, double rtol, unsigned pub) {
+    ASM_BARGS(abt, M, r, len, ldv, init, rtol, pub);
+    __shared__ double sh[4];
+    __shared__ bool last, lastcol;
+    const int64_t c = blockIdx.y;
+    const KktRed R = kkm_col(M, (int)c);
+    if (!init && R.scal[KK_STOP] != 0.0) {        // frozen by an earlier launch: only counted in, by one of its workgroups
+        if (blockIdx.x != 0) return;
+    } else {
+        double gg = 0.0;
+        for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256) {
+            const double gj = r[c * ldv + j];
+            gg += gj * gj;
+        }
+        gg = blk_reduce_sum(gg, sh);
+        if (gridDim.x > 1) {
+            if (threadIdx.x == 0) kk_store(R, 0, gg);
+            if (!kk_last_arrival(R, &last)) return;
+            if (threadIdx.x == 0) gg = kk_total(R, 0);
+        }
+        if (threadIdx.x == 0) {
+            double stop;
+            if (init) {
+                R.scal[KK_RG] = gg; R.scal[KK_GG] = gg; R.scal[KK_R0] = sqrt(gg); R.scal[KK_BETA] = 0.0; R.scal[KK_ALPHA] = 0.0; R.scal[KK_PHP] = 0.0;
+                R.scal[KKM_ITERS] = 0.0;
+                stop = gg == 0.0 ? 1.0 : 0.0;
+            } else {
+                R.scal[KK_BETA] = gg / R.scal[KK_RG];
+                R.scal[KK_RG] = gg; R.scal[KK_GG] = gg;
+                R.scal[KKM_ITERS] += 1.0;
+                stop = sqrt(gg) <= rtol * R.scal[KK_R0] ? 1.0 : 0.0;
+            }
+            R.scal[KK_STOP] = stop;
+            __hip_atomic_store(M.active + c, stop == 0.0 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    // this workgroup has finished its column
+    if (threadIdx.x == 0) {
+        unsigned* colcnt = M.cnt + KKM_CW;
+        __threadfence();
+        const unsigned t = __hip_atomic_fetch_add(colcnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        lastcol = (t == gridDim.y - 1);
+        if (lastcol) __hip_atomic_store(colcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!lastcol) return;
+    double act = 0.0;
+    for (int cc = threadIdx.x; cc < (int)gridDim.y; cc += 256) act += (double)__hip_atomic_load(M.active + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    act = blk_reduce_sum(act, sh);
+    if (threadIdx.x == 0) {
+        M.scal[KKM_CW * KKM_SCAL] = act;
+        if (pub != 0) {
+            M.hscal[0] = act;
+            __threadfence_system();
+            __hip_atomic_store(M.hseq, pub, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+// the bound multipliers and the residuals of every column, one workgroup each (k_kkt_finish with the column in blockIdx.x)
+__global__ __launch_bounds__(1024) void k_kktm_finish(AsmBt abt, double* __restrict__ scal, const double* __restrict__ hdx, const double* __restrict__ ru, const double* __restrict__ jtl, const double* __restrict__ mask, int64_t n, int64_t ldv, const double* __restrict__ adx, const double* __restrict__ rww, int64_t nW, int64_t ldr, double* __restrict__ dz) {
+    ASM_BARGS(abt, scal, hdx, ru, jtl, mask, n, ldv, adx, rww, nW, ldr, dz);
+    __shared__ double sh[16];
+    const int64_t c = blockIdx.x;
+    double rs = 0.0, rf = 0.0;
+    for (int64_t j = threadIdx.x; j < n; j += 1024) {
+        const int64_t e = c * ldv + j;
+        const double v = (hdx[e] + ru[e]) - jtl[e];
+        const bool fr = mask[j] != 0.0;
+        dz[e] = fr ? 0.0 : v;
+        if (fr) rs = fmax(rs, fabs(v));
+    }
+    for (int64_t q = threadIdx.x; q < nW; q += 1024) rf = fmax(rf, fabs(adx[c * ldr + q] + rww[c * ldr + q]));
+    rs = blk_reduce_max(rs, sh);
+    rf = blk_reduce_max(rf, sh);
+    if (threadIdx.x == 0) { scal[c * KKM_SCAL + KK_RSTAT] = rs; scal[c * KKM_SCAL + KK_RFEAS] = rf; }
+}

@@ -13,6 +13,10 @@ moves by d(bound_i) enters as u = 0, w_i = -d(bound_i).
     kkt_reference        the system assembled densely and solved with numpy.linalg.solve: the independent answer
     kkt_pcg              the NumPy twin of the device algorithm (asm_kkt_solve): Cholesky of A A', projected conjugate gradients
     solution_sensitivity the device call on a handle, or on a fresh one for a Model
+    kkt_reference_multi  kkt_reference for many right-hand sides: one dense system, one numpy.linalg.solve with a matrix right-hand side
+    kkt_pcg_multi        kkt_pcg column by column: what the lockstep iteration of asm_kkt_solve_multi computes
+    solution_jacobian    dx*/dc and dlam*/dc for a list of constants, as matrices (asm_solution_sensitivity_multi, unit directions)
+    bound_jacobian       dx*/d(bound) and dlam*/d(bound) for a list of working rows (asm_kkt_solve_multi)
     predict              the first-order prediction x + step * dx
 """
 import numpy as np
@@ -177,6 +181,82 @@ def kkt_pcg(fm, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=1e-1
                 res_stat=float(np.abs(HF @ dxF - A.T @ dlW + ru[F]).max()) if nF else 0.0,
                 res_feas=float(np.abs(A @ dxF + rw[W]).max()) if nW else 0.0)
     return dx, dlam, dz, info
+
+
+def _rhs_matrices(fm, RU, RW):
+    RU, RW = np.asarray(RU, float), np.asarray(RW, float)
+    if RU.ndim != 2 or RW.ndim != 2 or RU.shape[0] < 1 or RU.shape[1] != fm.n or RW.shape != (RU.shape[0], fm.m):
+        raise ValueError("RU, RW must have shapes (nrhs, n), (nrhs, m) with nrhs >= 1")
+    return RU, RW
+
+
+def kkt_reference_multi(fm, x, lam, row_state, bound_state, RU, RW):
+    """(DX [nrhs x n], DLAM [nrhs x m], DZ [nrhs x n]): kkt_reference for the right-hand sides in the rows of RU, RW - the dense system
+    assembled once, numpy.linalg.solve with a matrix right-hand side."""
+    RU, RW = _rhs_matrices(fm, RU, RW)
+    F, W, _, _ = _sets(fm, row_state, bound_state, RU[0], RW[0])
+    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    A = J[np.ix_(W, F)]
+    nF, nW, K = len(F), len(W), len(RU)
+    M = np.zeros((nF + nW, nF + nW))
+    M[:nF, :nF] = H[np.ix_(F, F)]
+    M[:nF, nF:] = -A.T
+    M[nF:, :nF] = A
+    sol = np.linalg.solve(M, np.concatenate([-RU[:, F], -RW[:, W]], axis=1).T) if nF + nW else np.zeros((0, K))
+    DX, DLAM, DZ = np.zeros((K, fm.n)), np.zeros((K, fm.m)), np.zeros((K, fm.n))
+    for c in range(K):
+        DX[c], DLAM[c], DZ[c] = _finish(H, J, F, W, RU[c], sol[:nF, c], sol[nF:, c], fm.n, fm.m)
+    return DX, DLAM, DZ
+
+
+def kkt_pcg_multi(fm, x, lam, row_state, bound_state, RU, RW, max_iter=None, rtol=1e-12):
+    """The NumPy twin of asm_kkt_solve_multi: kkt_pcg column by column.  The device advances the columns together, each with its own
+    alpha, beta, reference norm, stop code and iteration count, and freezes a column when it stops - which is this loop.  Returns
+    (DX, DLAM, DZ, infos), infos a list of kkt_pcg's dicts."""
+    RU, RW = _rhs_matrices(fm, RU, RW)
+    cols = [kkt_pcg(fm, x, lam, row_state, bound_state, RU[c], RW[c], max_iter, rtol) for c in range(len(RU))]
+    return np.array([c[0] for c in cols]), np.array([c[1] for c in cols]).reshape(len(RU), fm.m), np.array([c[2] for c in cols]), [c[3] for c in cols]
+
+
+def _jacobian_columns(DX, DLAM, infos):
+    status = lambda i: i["status"] if isinstance(i, dict) else i.status
+    bad = [(c, status(i)) for c, i in enumerate(infos) if status(i) != 0]
+    if bad:
+        raise RuntimeError("columns not solved (column, asm_kkt_info status): %r" % bad)
+    return DX.T.copy(), DLAM.T.copy()
+
+
+def solution_jacobian(opt, fm, x, lam, row_state, bound_state, indices=None, max_iter=None, rtol=None):
+    """(dx*/dc [n x k], dlam*/dc [m x k]) for the constants `indices` of fm's expression block (all of them when None): column q is
+    solution_sensitivity along the unit direction of constant indices[q], all from one asm_solution_sensitivity_multi call on `opt`
+    (a HipSubOptimizer whose evaluator holds fm, or any object with its solution_sensitivity_multi).  A column whose status is not 0
+    raises RuntimeError.  Below about 8 constants a loop of solution_sensitivity calls is faster ("Sensitivity matrices")."""
+    nd = len(fm.nlp.device[2])
+    idx = np.arange(nd) if indices is None else np.atleast_1d(np.asarray(indices, np.int64))
+    if idx.ndim != 1 or np.any(idx < 0) or np.any(idx >= nd):
+        raise ValueError("indices must be a list of constants in [0, %d)" % nd)
+    if not len(idx):
+        return np.zeros((fm.n, 0)), np.zeros((fm.m, 0))
+    DC = np.zeros((len(idx), nd))
+    DC[np.arange(len(idx)), idx] = 1.0
+    DX, DLAM, _, infos = opt.solution_sensitivity_multi(x, lam, row_state, bound_state, DC, max_iter, rtol)
+    return _jacobian_columns(DX, DLAM, infos)
+
+
+def bound_jacobian(opt, fm, x, lam, row_state, bound_state, rows, max_iter=None, rtol=None):
+    """(dx*/d(bound) [n x k], dlam*/d(bound) [m x k]) for the working rows `rows` (0-based): column q answers a unit move of the
+    active bound of row rows[q] - ru = 0, rw_i = -1 - all from one asm_kkt_solve_multi call on `opt`.  A column whose status is not 0 raises
+    RuntimeError."""
+    rows = np.atleast_1d(np.asarray(rows, np.int64))
+    rs = np.asarray(row_state)
+    if rows.ndim != 1 or np.any(rows < 0) or np.any(rows >= fm.m) or np.any(rs[rows] != 1):
+        raise ValueError("rows must be rows of the working set (row_state 1)")
+    if not len(rows):
+        return np.zeros((fm.n, 0)), np.zeros((fm.m, 0))
+    RW = np.zeros((len(rows), fm.m))
+    RW[np.arange(len(rows)), rows] = -1.0
+    DX, DLAM, _, infos = opt.kkt_solve_multi(x, lam, row_state, bound_state, np.zeros((len(rows), fm.n)), RW, max_iter, rtol)
+    return _jacobian_columns(DX, DLAM, infos)
 
 
 def solution_sensitivity(model_or_opt, fm, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):

@@ -336,6 +336,43 @@ class HipSubOptimizer:
                                                        self._kkt_params(max_iter, rtol), _lib.dptr(dx), _lib.dptr(dlam), _lib.dptr(dz), C.byref(info)))
         return dx, dlam[:self.m], dz, info
 
+    def _mat(self, a, cols, name, nrhs=None):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != cols or a.shape[0] < 1 or (nrhs is not None and a.shape[0] != nrhs):
+            raise ValueError("%s has shape %r, expected (%s, %d) with at least one row" % (name, a.shape, "nrhs" if nrhs is None else nrhs, cols))
+        return a if cols else np.zeros((a.shape[0], 1))
+
+    def _multi_outputs(self, nrhs):
+        return np.empty((nrhs, self.n)), np.empty((nrhs, max(self.m, 1))), np.empty((nrhs, self.n)), (_lib.KktInfo * nrhs)()
+
+    def kkt_solve_multi(self, x, lam, row_state, bound_state, RU, RW, max_iter=None, rtol=None):
+        """(DX, DLAM, DZ, infos) of asm_kkt_solve_multi: kkt_solve for the nrhs right-hand sides in the rows of RU [nrhs x n] and
+        RW [nrhs x m] on one factor; row c of DX [nrhs x n], DLAM [nrhs x m], DZ [nrhs x n] and infos[c] (asm_kkt_info) answer row c."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_params(max_iter, rtol)
+        RU = self._mat(RU, self.n, "RU")
+        RW = self._mat(RW, self.m, "RW", RU.shape[0])
+        rs, bs = self._states(row_state, bound_state)
+        nrhs = RU.shape[0]
+        DX, DLAM, DZ, infos = self._multi_outputs(nrhs)
+        self._check(self._lib.asm_kkt_solve_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(RU), _lib.dptr(RW),
+                                                  par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return DX, DLAM[:, :self.m], DZ, list(infos)
+
+    def solution_sensitivity_multi(self, x, lam, row_state, bound_state, DC, max_iter=None, rtol=None):
+        """(DX, DLAM, DZ, infos) of asm_solution_sensitivity_multi: solution_sensitivity for the nrhs directions in the rows of
+        DC [nrhs x n_dpar] on one factor, one row of the outputs per direction."""
+        nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_params(max_iter, rtol)
+        DC = self._mat(DC, nd, "DC")
+        rs, bs = self._states(row_state, bound_state)
+        nrhs = DC.shape[0]
+        DX, DLAM, DZ, infos = self._multi_outputs(nrhs)
+        self._check(self._lib.asm_solution_sensitivity_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(DC),
+                                                             par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return DX, DLAM[:, :self.m], DZ, list(infos)
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)

@@ -378,6 +378,46 @@ int asm_kkt_solve(asm_handle* h, const double* x, const double* lambda, const in
 int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                              const double* dc, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info);
 
+/* ---- Many right-hand sides on one factor: sensitivity matrices.
+ * asm_kkt_solve_multi solves the KKT system above for nrhs right-hand sides at once; asm_solution_sensitivity_multi does so for nrhs
+ * directions of the data.  All matrices are row-major with one right-hand side per row: RU, DX, DZ are nrhs x n, RW, DLAM nrhs x m, DC
+ * nrhs x n_dpar, info has nrhs entries, and row c of DX / DLAM / DZ / info answers row c of RU / RW (of DC).  DZ may be NULL.
+ * Validity, argument errors and defaults are asm_kkt_solve's (asm_solution_sensitivity's); nrhs < 1: ASM_ERR_ARG.  par, and the default
+ * max_iter = 2 (|F| - |W|) + 20 and rtol = 1e-12, hold for every column.  Not inside a scenario batch.
+ * Per column the mathematics is the method above, step by step.  Steps 1 and 2 - the Hessian values, the Jacobian, the gather, its
+ * transposed copy, the rank-K build, the factorisation and the dropped-pivot count - run once per call.  Steps 3 to 6 run on blocks of
+ * ASM_KKT_CHUNK columns; the factor and everything of steps 1 and 2 stay across the chunks, so memory is bounded whatever nrhs.
+ *   Layout: a block holds its columns as rows, pitch ldn over the variables and round_up(min(m, n), 32) over the working rows.  The
+ *   products with A and A' are k_gemm_nt launches on the matrix cores (T = V Aw', V = Y AwT'), the substitutions Dev::trsm_rows with the
+ *   factor's wide-block inverses and its transposed copy.  Systems of every order take this path: the one-workgroup small solve serves one
+ *   right-hand side and is not used.  H V is one launch that reads each Hessian entry once for all columns of the chunk; per column its
+ *   sum is asm_eval_hessian_product's, bit for bit.  (J_W' dlam_W)_B comes from a second, unmasked transposed gather of the working rows.
+ *   Lockstep iteration: the columns are independent conjugate-gradient iterations that advance together - no block method.  Each has its
+ *   own alpha, beta, ||g0||, stop code and iteration count in HBM.  A column that has converged, has g0 = 0 or has met p'Hp <= 0 is
+ *   frozen: no kernel writes its d, r or p again, and it leaves the active count in the round in which it stops (the curvature stop too).  The loop ends when no column is active or after max_iter rounds; a column still active
+ *   then has status 1.  The host reads one word per round, the number of active columns, written by the workgroup that finishes the
+ *   last column (through the host-mapped scalar block; by copy and synchronisation under ASM_HIP_SPIN=0).
+ *   info[c]: the column's status, cg_iters, res_stat, res_feas; n_free, n_rows and dropped_pivots are the call's (dropped pivots: status 3
+ *   in every column).
+ *   Column independence: a column's outputs depend on its own right-hand side and the handle's data only - not on nrhs, not on its place,
+ *   not on the other columns - bit for bit.  Every nrhs >= 1 takes the same kernels, every sum runs in an order fixed by the matrix
+ *   dimensions, and the rows of a block beyond the chunk's columns are never part of a launch.  Against asm_kkt_solve the agreement is to
+ *   tolerance: the summation orders differ.
+ * asm_solution_sensitivity_multi makes (u, w) of each direction with the cross-derivative sweep of asm_eval_data_cross - one launch set per
+ * direction, written straight into the chunk's blocks, no synchronisation between directions - and then runs the same solve.
+ * The buffers are made at the first multi call and released with asm_kkt_solve's; asm_kkt_solve itself is not affected.
+ * When to use it: a lockstep round launches block products whose time does not shrink with the number of columns, live or frozen - on
+ * the case300-sized ACOPF a round costs about seven single-column iterations.  Below about 8 columns a loop of asm_kkt_solve /
+ * asm_solution_sensitivity calls is faster; from there on the multi entries win, 4.5 times at 32 columns and 12.7 times at 64.
+ * Bound sensitivities for a set of working rows: RU = 0 and RW[c, i_c] = -1 for the row i_c of column c (the recipe above). */
+#define ASM_KKT_CHUNK 64
+int asm_kkt_solve_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                        int32_t nrhs, const double* RU, const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
+                        asm_kkt_info* info);
+int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state,
+                                   const int32_t* bound_state, int32_t nrhs, const double* DC, const asm_kkt_params* par, double* DX,
+                                   double* DLAM, double* DZ, asm_kkt_info* info);
+
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
 int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4);
@@ -767,6 +807,9 @@ int asm_test_panel_timeout(asm_handle* h, int workgroups);
 /* on != 0: every active-set attempt (polish) of the following LPs on this handle fails, so that the solve ends on its last resort - the
  * converged interior iterate, asm_solve_stats.path 10 (oracle: tests patch eqp_loop / face_polish the same way) */
 int asm_test_no_polish(asm_handle* h, int on);
+/* the lockstep rounds the last asm_kkt_solve_multi / asm_solution_sensitivity_multi on this handle ran, summed over its chunks, and the last
+ * active-column word its host loop read (0: the loop ended because no column was active) */
+int asm_test_kkt_multi_rounds(const asm_handle* h, int64_t* rounds, int32_t* last_active);
 /* C = (mode 1: C0) -/+ A B'  (A: Ma x K, B: Mb x K, row-major, K a multiple of 32) - the product kernel of the multi-right-hand-side
  * triangular solves of the null-space form */
 int asm_test_gemm_nt(asm_handle* h, const double* A, const double* B, const double* C0, int64_t Ma, int64_t Mb, int64_t K, int mode,
