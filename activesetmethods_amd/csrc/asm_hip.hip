@@ -238,6 +238,27 @@ struct FacBuf {
                                     // operation stops `band` rows below the panel's last column
 };
 
+// The buffers of the KKT solve on a working set, all in the handle's mem_kk and made where first needed after asm_eval_setup (kk_prepare,
+// kk_work); releasing the pool resets the struct.
+struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` columns (0: not made): 1 for asm_kkt_solve, KKM_CW for the multi entries
+    int64_t cap = 0;
+    double *vec = nullptr, *row = nullptr, *dlf = nullptr;      // 14 blocks cap x ldn over the variables, 5 cap x ldT over the working rows, cap x Mp over all rows
+    double* stage = nullptr;                                    // pinned: [ru | rw | directions] of a chunk, then its results
+    double *Lt = nullptr, *AfT = nullptr;                       // cap > 1, the block products' own operands: the transposed factor, the unmasked transposed working rows
+};
+struct KktBufs {
+    bool ready = false;
+    int64_t capW = 0, ldT = 0;      // the most working rows the problem admits, min(m, n); the pitch of everything over them
+    FacBuf fac;                     // S = A A' and its factor
+    double *dE = nullptr, *J = nullptr, *Aw = nullptr, *AwT = nullptr;      // Jacobian values and dense J of the solve's own, A = J[W, F] and its transposed copy
+    double *sets = nullptr, *h_sets = nullptr;                              // [mask (ldn doubles) | working-row list (Mp ints)] and its pinned image
+    int* dropped = nullptr;                                                 // the dropped-pivot count
+    // the per-column reduction state, laid out for KKM_CW columns whatever the capacity (KktMulti)
+    double *part = nullptr, *scal = nullptr;
+    unsigned *cnt = nullptr, *act = nullptr;
+    KktWork one, blk;
+};
+
 // The device and pinned host buffers of one lifetime.  Each allocation is recorded with the field that points to it (and, for mapped host
 // memory, the field that holds its device address); release() frees them all and nulls those fields.  Sizes are max(count, 1) elements.
 class BufPool {
@@ -460,23 +481,8 @@ struct asm_handle {
     ExprCross cx_C{};
     int64_t *d_cx_vptr = nullptr, *d_cx_vnode = nullptr;
     double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr;   // [lam (R) | dc (n_dpar)], [u (n) | w (R)], pinned staging of both and x
-    // KKT solve on a working set (asm_kkt_solve): Jacobian values and dense Jacobian of its own, the gathered working rows and their
-    // transposed copy, the factor of A A', work vectors and the scalar block of the conjugate-gradient kernels; made by the first call
-    // after asm_eval_setup (kk_prepare) in mem_kk
-    bool kk_ready = false;
-    int64_t kk_capW = 0, kk_ldT = 0;
-    FacBuf kk_fac;
-    double *d_kk_dE = nullptr, *d_kk_J = nullptr, *d_kk_Aw = nullptr, *d_kk_AwT = nullptr, *d_kk_vec = nullptr, *d_kk_row = nullptr;
-    double *d_kk_part = nullptr, *d_kk_scal = nullptr, *h_kk = nullptr;
-    unsigned* d_kk_arr = nullptr;
-    int *d_kk_wrow = nullptr, *d_kk_cnt = nullptr;
-    // ... and of its many-column form (asm_kkt_solve_multi), made at the first such call (kkm_prepare): the blocks of one chunk over the
-    // variables, over the working rows and over all rows, the transposed factor, the unmasked transposed working rows, the per-column
-    // reduction state, the staging buffer
-    bool kkm_ready = false;
-    double *d_kkm_vec = nullptr, *d_kkm_row = nullptr, *d_kkm_dlf = nullptr, *d_kkm_Lt = nullptr, *d_kkm_AfT = nullptr, *d_kkm_part = nullptr, *d_kkm_scal = nullptr,
-           *h_kkm = nullptr;
-    unsigned *d_kkm_cnt = nullptr, *d_kkm_act = nullptr;
+    // KKT solve on a working set (asm_kkt_solve and the multi entries): everything in mem_kk (KktBufs); the test seam of the multi entries
+    KktBufs kk;
     int64_t kkm_rounds = 0;         // lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
     int kkm_last_active = 0;
     bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
@@ -1259,6 +1265,14 @@ struct NsLayout {
     static int kcap(int k) { return (int)round_up(k + k / 4 + 64, 64); }
 };
 
+// Sequence number for the next publishing kernel (0 = the kernel does not publish: copy path)
+unsigned pub_next(asm_handle* h) {
+    if (!h->knobs.spin_read) return 0;
+    h->scal_seq += 1;
+    if (h->scal_seq == 0) h->scal_seq = 1;
+    return h->scal_seq;
+}
+
 struct Solver {
     // out = A x for a k x ncols matrix of few, long rows (the basis Zt): one workgroup per row when that fills the chip better
     unsigned gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
@@ -1445,13 +1459,6 @@ struct Solver {
         h2d_done(h);
     }
     unsigned grid_all() const { return (unsigned)((std::max(std::max(lp.n, lp.M), std::max<int64_t>(lp.ns, 1)) + 255) / 256); }
-    // Sequence number for the next publishing kernel (0 = the kernel does not publish: copy path)
-    unsigned pub_next() {
-        if (!h->knobs.spin_read) return 0;
-        h->scal_seq += 1;
-        if (h->scal_seq == 0) h->scal_seq = 1;
-        return h->scal_seq;
-    }
     // The scalar block of the last reduction kernel on the host.  pub != 0: that kernel stored the block into host-mapped memory
     // and then the sequence word; spin on the word (the stream is in order: everything before that kernel has finished too).
     void read_scal(unsigned pub) {
@@ -1504,7 +1511,7 @@ struct Solver {
     void ipm_measures() {
         dev.gemv_n_dev(h->d_Ah, P.p, P.act);
         dev.gemv_t_dev(h->d_Ah, P.y, P.aty);
-        const unsigned pub = pub_next();
+        const unsigned pub = pub_next(h);
         if (ns_live()) {
             // null-space form: the equality rows' multipliers are carried as 0, the dual residual that counts is Z'rdp (oracle: IPM.measures)
             launch_measures(0u);
@@ -2133,7 +2140,7 @@ struct Solver {
                 dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
             };
             applyS(D.dy);
-            unsigned pub = pub_next();
+            unsigned pub = pub_next(h);
             launch_res(D.dy, pub, 0, 0.0, 0.0);
             read_scal(pub);
             // the approximate preconditioners (column and reduced row form) get the tighter floor (oracle: IPM.run.solve)
@@ -2145,7 +2152,7 @@ struct Solver {
                 bool converged = false;
                 for (int it = 0; it < PCG_MAXIT; ++it) {
                     applyS(d_pcg);
-                    pub = pub_next();
+                    pub = pub_next(h);
                     launch_pcg_step1(D.dy, pub);
                     read_scal(pub);
                     h->stats_pcg += 1;
@@ -2313,7 +2320,7 @@ struct Solver {
                     launch_steps(dirC, 0u);
                     return true;
                 }
-                unsigned pub = pub_next();
+                unsigned pub = pub_next(h);
                 launch_steps(dirC, pub);
                 read_scal(pub);
                 if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
@@ -2324,7 +2331,7 @@ struct Solver {
                     const double tp = std::min(1.0, ap + MCC_DELTA), td = std::min(1.0, ad + MCC_DELTA);
                     ipm_solve(2, dirC, dirA, tp, td, deferred ? 2 : 0);
                     launch_diradd(dirA, dirC);
-                    pub = pub_next();
+                    pub = pub_next(h);
                     launch_steps(dirA, pub);
                     read_scal(pub);
                     if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
@@ -3070,7 +3077,7 @@ int row_kind(double lb, double ub) {
 // releases every buffer of the handle and resets the state that describes them
 void free_device(asm_handle* h) {
     h->mem.release(); h->mem_nsk.release(); h->mem_ev.release(); h->mem_kk.release();
-    h->kk_ready = false; h->kkm_ready = false; h->kk_fac = FacBuf();
+    h->kk = KktBufs();
     h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
     h->ahTg_valid = false;
     h->col_capable = h->ahT_valid = h->nzT_valid = false;
@@ -3984,7 +3991,7 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     P.release();
     h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
     h->cx_ready = false; h->cx_C = ExprCross{};
-    h->mem_kk.release(); h->kk_ready = false; h->kkm_ready = false; h->kk_fac = FacBuf();
+    h->mem_kk.release(); h->kk = KktBufs();
     FnStore& F = h->ev_F;
     F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
     const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
@@ -4396,246 +4403,424 @@ static void do_data_cross(asm_handle* h, const double* x, const double* lambda, 
     if (X.R > 0) std::memcpy(w + h->ev_F.n_rows, back + n, X.R * sizeof(double));
 }
 
-// ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set")
+// ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set" and "Many right-hand sides on one factor"): one
+// set-up of the face (KktFace, steps 1 and 2), one driver of steps 3 to 6 on blocks of columns (kkt_columns) and, behind KktOps, the two
+// ways to multiply and solve: KktOneColumn for asm_kkt_solve and asm_solution_sensitivity, KktBlock for the multi entries.  The entry
+// point chooses, not nrhs: a column's bits do not depend on the number of columns beside it.
+static_assert(KKM_CW == ASM_KKT_CHUNK && KKM_CW % 32 == 0 && KKM_SCAL > KKM_ITERS, "the chunk width of the header is the kernels'");
 namespace {
-// once per asm_eval_setup, at the first asm_kkt_solve: the buffers of the solve, sized for every working set the problem admits
+// once per asm_eval_setup, at the first KKT solve: what steps 1 and 2 fill, sized for every working set the problem admits, and the
+// per-column reduction state
 void kk_prepare(asm_handle* h) {
-    if (h->kk_ready) return;
+    KktBufs& K = h->kk;
+    if (K.ready) return;
     HIPCHK(hipSetDevice(h->device));
     BufPool& M = h->mem_kk;
     const hipStream_t s = h->stream;
-    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32);
-    h->kk_capW = std::max<int64_t>(std::min(h->m, h->n), 1);
-    h->kk_ldT = round_up(h->kk_capW, 32);
-    M.alloc(h->d_kk_dE, h->nnz);
-    M.zeroed(h->d_kk_J, Mp * ldn, s);
-    M.zeroed(h->d_kk_Aw, h->kk_capW * ldn, s);
-    M.zeroed(h->d_kk_AwT, ldn * h->kk_ldT, s);
-    ns_alloc_factor(h, M, h->kk_fac, h->kk_capW);
-    M.zeroed(h->d_kk_vec, 16 * ldn, s);
-    M.zeroed(h->d_kk_row, 6 * Mp, s);
-    M.zeroed(h->d_kk_part, KK_MAXWG * KK_SLOTS, s);
-    M.zeroed(h->d_kk_scal, 16, s);
-    M.zeroed(h->d_kk_arr, 4, s);
-    M.zeroed(h->d_kk_wrow, Mp, s);
-    M.zeroed(h->d_kk_cnt, 4, s);
-    M.alloc(h->h_kk, 4 * ldn + 4 * Mp + 64, BufPool::PINNED);
+    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), CW = KKM_CW;
+    K.capW = std::max<int64_t>(std::min(h->m, h->n), 1);
+    K.ldT = round_up(K.capW, 32);
+    M.alloc(K.dE, h->nnz);
+    M.zeroed(K.J, Mp * ldn, s);
+    M.zeroed(K.Aw, K.capW * ldn, s);
+    M.zeroed(K.AwT, ldn * K.ldT, s);
+    ns_alloc_factor(h, M, K.fac, K.capW);
+    M.zeroed(K.sets, ldn + (Mp + 1) / 2, s);
+    M.alloc(K.h_sets, ldn + (Mp + 1) / 2, BufPool::PINNED);
+    M.zeroed(K.dropped, 4, s);
+    M.zeroed(K.part, CW * KK_MAXWG * KK_SLOTS, s);
+    M.zeroed(K.scal, CW * KKM_SCAL + 16, s);
+    M.zeroed(K.cnt, CW + 4, s);
+    M.zeroed(K.act, CW, s);
     HIPCHK(asmb::sync(s));
-    h->kk_ready = true;
+    K.ready = true;
 }
-// the scalar block of the last k_kkt_cg_dir on the host (h_scal): the kernel's own stores and the sequence word the host spins on, or
-// (pub == 0, ASM_HIP_SPIN=0) a copy and a stream synchronisation
-void kk_read_scal(asm_handle* h, unsigned pub) {
+// the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it
+KktWork* kk_work(asm_handle* h, int64_t cap) {
+    kk_prepare(h);
+    KktBufs& K = h->kk;
+    KktWork& W = cap == 1 ? K.one : K.blk;
+    if (W.cap != 0) return &W;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->mem_kk;
+    const hipStream_t s = h->stream;
+    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), nd = std::max<int64_t>(h->ev_n_dpar, 1);
+    M.zeroed(W.vec, 14 * cap * ldn, s);
+    M.zeroed(W.row, 5 * cap * K.ldT, s);
+    M.zeroed(W.dlf, cap * Mp, s);
+    if (cap > 1) {
+        M.zeroed(W.Lt, K.fac.ld * K.fac.ld, s);
+        M.zeroed(W.AfT, ldn * K.ldT, s);
+    }
+    M.alloc(W.stage, cap * (3 * ldn + K.ldT + Mp + KKM_SCAL + nd) + 64, BufPool::PINNED);
+    HIPCHK(asmb::sync(s));
+    W.cap = cap;
+    return &W;
+}
+// the active-column word of the last k_kktm_cg_dir on the host: the kernel's own store into the host-mapped scalar block and the sequence
+// word the host spins on, or (pub == 0, ASM_HIP_SPIN=0) a copy and a stream synchronisation
+int kk_read_scal(asm_handle* h, unsigned pub) {
     if (pub == 0) {
-        HIPCHK(asmb::copy_async(h->h_scal, h->d_kk_scal, KK_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(h->h_scal, h->kk.scal + KKM_CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
-        return;
+        return (int)h->h_scal[0];
     }
     const double t0 = Solver::now_ms();
     for (unsigned long spins = 1;; ++spins) {
-        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
+        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) break;
         if (spins < 20000) __builtin_ia32_pause();
         else sched_yield();
         if ((spins & 0xffff) == 0 && Solver::now_ms() - t0 > 30000.0) {
             HIPCHK(asmb::sync(h->stream));            // a device fault surfaces here
-            if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
+            if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) break;
             throw HipError("asm_kkt_solve: the publishing kernel finished without setting its sequence word");
         }
     }
+    return (int)h->h_scal[0];
 }
-}  // namespace
-static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru,
-                         const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
-    hs_check(h, "asm_kkt_solve");
+
+// The face of a call: its counts and limits, and on the device (h->kk) the mask of F, the list of W, A = J[W, F] with its transposed copy
+// and the factor of S = A A'.
+struct KktFace {
+    int64_t nF = 0, nW = 0, nWp = 0, max_iter = 0;      // |F|, |W|, |W| rounded up to 32
+    double rtol = 0.0;
+    std::vector<int> wl;                                // the working rows, ascending (Mp entries, 0 beyond |W|)
+    const double* mask = nullptr;                       // 1.0 on F, 0.0 on B and beyond n (ldn)
+    const int* wrow = nullptr;                          // wl on the device
+    // the checks every entry shares (`me` names the caller in the messages) and steps 1 and 2 of the method
+    KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+            const asm_kkt_params* par);
+};
+KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                 const asm_kkt_params* par) {
     const int64_t n = h->n, m = h->m, ldn = h->ldn;
-    if (!x || !bound_state || !ru || !dx || !info || (m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
-    int64_t nF = 0, nW = 0;
+    KktFace& f = *this;
     for (int64_t j = 0; j < n; ++j) {
-        if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument("asm_kkt_solve: bound_state holds a value outside {-1, 0, +1}");
-        nF += bound_state[j] == 0;
+        if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
+        f.nF += bound_state[j] == 0;
     }
     for (int64_t i = 0; i < m; ++i) {
-        if (row_state[i] != 0 && row_state[i] != 1) throw std::invalid_argument("asm_kkt_solve: row_state holds a value outside {0, 1}");
-        nW += row_state[i];
+        if (row_state[i] != 0 && row_state[i] != 1) throw std::invalid_argument(me + ": row_state holds a value outside {0, 1}");
+        f.nW += row_state[i];
     }
-    if (nW > nF) throw std::invalid_argument("asm_kkt_solve: more working rows (" + std::to_string(nW) + ") than free variables (" + std::to_string(nF) + ")");
-    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument("asm_kkt_solve: max_iter < 0 or rtol not >= 0");
-    const int64_t max_iter = par ? par->max_iter : 2 * (nF - nW) + 20;
-    const double rtol = par ? par->rtol : 1e-12;
-    if (asmb::in_fiber()) throw std::logic_error("asm_kkt_solve: not inside a scenario batch");
+    const int64_t nW = f.nW;
+    if (nW > f.nF) throw std::invalid_argument(me + ": more working rows (" + std::to_string(nW) + ") than free variables (" + std::to_string(f.nF) + ")");
+    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
+    f.max_iter = par ? par->max_iter : 2 * (f.nF - nW) + 20;
+    f.rtol = par ? par->rtol : 1e-12;
+    f.nWp = round_up(nW, 32);
+    if (asmb::in_fiber()) throw std::logic_error(me + ": not inside a scenario batch");
     hs_prepare(h);
     kk_prepare(h);
     HIPCHK(hipSetDevice(h->device));
-    Dev dev(h);
+    KktBufs& K = h->kk;
     const hipStream_t s = h->stream;
     const int64_t Mp = std::max<int64_t>(h->Mp, 32);
-    // the vectors over the variables (pitch ldn, zero beyond n and on B) and over the rows
-    double* const V = h->d_kk_vec;
-    double *mask = V, *d_ru = V + ldn, *dx0 = V + 2 * ldn, *cd = V + 3 * ldn, *cr = V + 4 * ldn, *cg = V + 5 * ldn, *cp = V + 6 * ldn, *hraw = V + 7 * ldn,
-           *hp = V + 8 * ldn, *tt = V + 9 * ldn, *ddx = V + 10 * ldn, *hdx = V + 11 * ldn, *qq = V + 12 * ldn, *jtl = V + 13 * ldn, *ddz = V + 14 * ldn;
-    double* const Rw = h->d_kk_row;
-    double *rww = Rw, *tw = Rw + Mp, *yw = Rw + 2 * Mp, *dlw = Rw + 3 * Mp, *adx = Rw + 4 * Mp, *dlf = Rw + 5 * Mp;
-    const KktRed R{h->d_kk_part, h->d_kk_arr, h->d_kk_scal, h->d_hscal, h->d_hseq};
     // 1. the Hessian values of f - lambda' g at x, once: they stay in d_hs_vals for every product of the call (x goes to d_ev_xt)
     {
         std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
         for (int64_t i = 0; i < m; ++i) nl[i] = -lambda[i];
         hs_launch(h, x, 1.0, nl.data(), nullptr);      // (copies nl into the pinned staging buffer before it returns)
     }
-    const HsShared& L = *h->hs_sh;
-    auto hess_product = [&](const double* v, double* out) {
-        asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, n, out);
-    };
     // 2. the Jacobian at x: values into a buffer of the solve's own, assembled into its own dense J (the LP's dE and J stay)
     {
         const FnStore& F = h->ev_F;
-        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, 1, (int64_t)0, (int64_t)0);
+        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->d_ev_xt, h->d_ev_Et, K.dE, 1, (int64_t)0, (int64_t)0);
         const ExprTape& X = h->ev_X;
         if (h->ev_nlp_kind == ASM_NLP_EXPR && X.R > 0)
-            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, F.n_rows, h->ev_fn_nnz, 1, (int64_t)0, (int64_t)0);
+            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->d_ev_xt, h->d_ev_Et, K.dE, F.n_rows, h->ev_fn_nnz, 1, (int64_t)0, (int64_t)0);
         if (h->dense_fast) {
             const unsigned g = (unsigned)std::min<int64_t>((h->m * h->n + 255) / 256, 4096);
-            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, h->d_kk_dE, h->d_kk_J, h->m, h->n, ldn);
+            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, K.dE, K.J, h->m, h->n, ldn);
         } else if (h->nu > 0) {
             const unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
-            asmb::launch(k_assemble, dim3(g), dim3(256), s, h->d_kk_dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, h->d_kk_J, h->nu);
+            asmb::launch(k_assemble, dim3(g), dim3(256), s, K.dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, K.J, h->nu);
         }
     }
-    // 3. the sets and the right-hand sides
+    // the sets: the mask and the working-row list in one upload
     {
-        double* st = h->h_kk;
-        for (int64_t j = 0; j < ldn; ++j) { st[j] = (j < n && bound_state[j] == 0) ? 1.0 : 0.0; st[ldn + j] = j < n ? ru[j] : 0.0; }
-        int* wl = reinterpret_cast<int*>(st + 2 * ldn + Mp);
+        double* st = K.h_sets;
+        for (int64_t j = 0; j < ldn; ++j) st[j] = (j < n && bound_state[j] == 0) ? 1.0 : 0.0;
+        f.wl.assign((size_t)Mp, 0);
         int64_t q = 0;
         for (int64_t i = 0; i < m; ++i)
-            if (row_state[i]) { st[2 * ldn + q] = rw[i]; wl[q] = (int)i; ++q; }
-        for (; q < Mp; ++q) { st[2 * ldn + q] = 0.0; wl[q] = 0; }
-        HIPCHK(asmb::copy_async(mask, st, 2 * ldn * sizeof(double), hipMemcpyHostToDevice, s));
-        HIPCHK(asmb::copy_async(rww, st + 2 * ldn, Mp * sizeof(double), hipMemcpyHostToDevice, s));
-        HIPCHK(asmb::copy_async(h->d_kk_wrow, wl, Mp * sizeof(int), hipMemcpyHostToDevice, s));
+            if (row_state[i]) f.wl[q++] = (int)i;
+        std::memcpy(st + ldn, f.wl.data(), Mp * sizeof(int));
+        HIPCHK(asmb::copy_async(K.sets, st, ldn * sizeof(double) + Mp * sizeof(int), hipMemcpyHostToDevice, s));
+        f.mask = K.sets;
+        f.wrow = reinterpret_cast<const int*>(K.sets + ldn);
     }
-    const dim3 gl = asmb::blocks(ldn);
-    const dim3 gred((unsigned)std::min<int64_t>(gl.x, KK_MAXWG));
-    // A = J[W, F] as a dense operand and its transposed copy; S = A A' and its factor
+    // A = J[W, F] as a dense operand and its transposed copy with the k-padding cleared; S = A A' and its factor (Dev::chol leaves the
+    // wide-block inverses too); the dropped pivots
     if (nW > 0) {
-        asmb::launch(k_kkt_gather, dim3(gl.x, (unsigned)nW), dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, mask, nW, h->d_kk_Aw);
-        asmb::launch(k_transpose_dense, dim3((unsigned)((ldn + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, h->d_kk_Aw, ldn, nW, ldn, h->d_kk_AwT, h->kk_ldT, (int64_t)-1);
-        dev.launch_syrk(s, Dev::pick_tile(nW), h->d_kk_Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, h->kk_fac.S, h->kk_fac.ld, 0, 0);
-        dev.diag_prepare(h->kk_fac, (int)nW, 1, 0.0, 0.0);
+        const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
+        asmb::launch(k_kkt_gather, dim3(asmb::blocks(ldn).x, (unsigned)nW), dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, K.Aw);
+        asmb::launch(k_kktm_gather_t, gt, dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, f.nWp, K.AwT, K.ldT);
+        dev.launch_syrk(s, Dev::pick_tile(nW), K.Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, K.fac.S, K.fac.ld, 0, 0);
+        dev.diag_prepare(K.fac, (int)nW, 1, 0.0, 0.0);
         const int nfact = h->stats.nfact;
-        dev.chol(h->kk_fac, (int)nW, 1e-10);
+        dev.chol(K.fac, (int)nW, 1e-10);
         h->stats.nfact = nfact;          // (the LP statistics count the LP's factorisations)
-        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, h->kk_fac.S, h->kk_fac.ld, (int)nW, NS_BIG, h->d_kk_cnt);
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, K.fac.S, K.fac.ld, (int)nW, NS_BIG, K.dropped);
     } else {
-        HIPCHK(asmb::fill_async(h->d_kk_cnt, 0, 4 * sizeof(int), s));
+        HIPCHK(asmb::fill_async(K.dropped, 0, 4 * sizeof(int), s));
     }
-    // t = A' S^-1 A v  (v, t over the variables)
-    auto normal_part = [&](const double* v) {
-        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, v, tw, nW, ldn);
-        dev.chol_solve_dev(h->kk_fac, tw, yw, (int)nW);
-        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, yw, tt, ldn, nW);
-    };
-    // dst = P src = src - A' S^-1 A src
-    auto project = [&](const double* src, double* dst) {
-        if (nW == 0) {
-            if (src != dst) HIPCHK(asmb::copy_async(dst, src, ldn * sizeof(double), hipMemcpyDeviceToDevice, s));
-            return;
-        }
-        normal_part(src);
-        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, src, -1.0, tt, mask, ldn, dst);
-    };
-    // particular solution dx0 = -A' S^-1 rw_W
-    if (nW > 0) {
-        dev.chol_solve_dev(h->kk_fac, rww, yw, (int)nW);
-        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, yw, tt, ldn, nW);
-        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, -1.0, tt, 0.0, nullptr, mask, ldn, dx0);
-        // one refinement step of the normal-equation solve: dx0 -= A' S^-1 (A dx0 + rw_W)
-        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, dx0, adx, nW, ldn);
-        asmb::launch(k_kkt_axpby_mask, asmb::blocks(nW), dim3(256), s, 1.0, adx, 1.0, rww, nullptr, nW, tw);
-        dev.chol_solve_dev(h->kk_fac, tw, yw, (int)nW);
-        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, yw, tt, ldn, nW);
-        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, dx0, -1.0, tt, mask, ldn, dx0);
-    } else {
-        HIPCHK(asmb::fill_async(dx0, 0, ldn * sizeof(double), s));
+}
+
+// What the two paths do differently, on the first `cols` columns of blocks (rows of pitch ldn over the variables, ldT over the working rows).
+struct KktOps {
+    asm_handle* const h;
+    Dev& dev;
+    const KktFace& f;
+    KktWork& w;
+    const hipStream_t s;
+    const int64_t n, ldn, ldT;
+    double* const spare;             // a block over the working rows of the back end's own
+    KktOps(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww)
+        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->n), ldn(hh->ldn), ldT(hh->kk.ldT), spare(ww.row + 2 * ww.cap * hh->kk.ldT) {}
+    virtual ~KktOps() = default;
+    virtual void hess(const double* v, double* out, int cols) = 0;                  // OUT = H V from the values of step 1
+    virtual void mul_A(const double* v, double* t, int cols) = 0;                   // T = V A'
+    virtual void mul_AT(const double* y, double* v, int cols) = 0;                  // V = Y A
+    // S^-1 applied to the block b; t (b itself, or another block) is where the answer may go.  Returns where it is.
+    virtual double* solve_S(const double* b, double* t, int cols) = 0;
+    // JTL = J_W' dlam_W over all variables, those of B too, from dlam_W (dlw) or its scattered form over all rows (dlf, pitch Mp)
+    virtual void jt_dlam(const double* dlw, const double* dlf, double* jtl, int cols) = 0;
+};
+// one column: matrix-vector kernels, the factor's own substitution (the one-workgroup small solve where the factor has it) from one
+// buffer into another, J' dlam from the private dense J
+struct KktOneColumn final : KktOps {
+    using KktOps::KktOps;
+    void hess(const double* v, double* out, int) override {
+        const HsShared& L = *h->hs_sh;
+        asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, n, out);
     }
-    // projected conjugate gradients on null(A): minimise 1/2 d'H_FF d + (ru_F + H_FF dx0)'d
-    int status = 0, iters = 0;
-    HIPCHK(asmb::fill_async(cd, 0, ldn * sizeof(double), s));
-    if (nF > nW) {
-        auto pub_next = [&]() -> unsigned {
-            if (!h->knobs.spin_read) return 0;
-            h->scal_seq += 1;
-            if (h->scal_seq == 0) h->scal_seq = 1;
-            return h->scal_seq;
-        };
-        hess_product(dx0, hraw);
-        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, d_ru, 1.0, hraw, mask, ldn, cr);
-        HIPCHK(asmb::fill_async(cp, 0, ldn * sizeof(double), s));
-        // the residual is kept projected (r = g = P P r): it then has no large component in range(A') for the projection's rounding to act on
-        project(cr, cr);
-        project(cr, cr);
-        unsigned pub = pub_next();
-        asmb::launch(k_kkt_cg_dir, gred, dim3(256), s, R, cr, cr, ldn, 1, rtol, pub);
-        kk_read_scal(h, pub);
-        int stop = (int)h->h_scal[KK_STOP];
-        while (stop == 0) {
-            if (iters >= max_iter) { status = 1; break; }
-            asmb::launch(k_kkt_cg_p, gl, dim3(256), s, h->d_kk_scal, cr, cp, ldn);
-            hess_product(cp, hraw);
-            asmb::launch(k_kkt_cg_curv, gred, dim3(256), s, R, cp, hraw, mask, hp, ldn);
-            asmb::launch(k_kkt_cg_step, gl, dim3(256), s, h->d_kk_scal, cp, hp, cd, cr, ldn);
-            project(cr, cr);
-            project(cr, cr);
-            pub = pub_next();
-            asmb::launch(k_kkt_cg_dir, gred, dim3(256), s, R, cr, cr, ldn, 0, rtol, pub);
-            kk_read_scal(h, pub);
-            stop = (int)h->h_scal[KK_STOP];
-            if (stop != 2) ++iters;
-        }
-        if (stop == 2) status = 2;
+    void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nW, 4), dim3(256), s, h->kk.Aw, ldn, v, t, f.nW, ldn); }
+    void mul_AT(const double* y, double* v, int) override { asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->kk.AwT, ldT, y, v, ldn, f.nW); }
+    double* solve_S(const double* b, double* t, int) override {
+        double* const out = b == t ? spare : t;
+        dev.chol_solve_dev(h->kk.fac, b, out, (int)f.nW);
+        return out;
     }
-    // the solution, its multipliers and residuals
-    asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, dx0, 1.0, cd, mask, ldn, ddx);
-    hess_product(ddx, hdx);
-    HIPCHK(asmb::fill_async(dlf, 0, Mp * sizeof(double), s));
-    if (nW > 0) {
-        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, hdx, 1.0, d_ru, mask, ldn, qq);
-        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, qq, tw, nW, ldn);
-        dev.chol_solve_dev(h->kk_fac, tw, dlw, (int)nW);
-        // one refinement step: dlam_W += S^-1 A (q - A' dlam_W)
-        asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->d_kk_AwT, h->kk_ldT, dlw, tt, ldn, nW);
-        asmb::launch(k_kkt_axpby_mask, gl, dim3(256), s, 1.0, qq, -1.0, tt, mask, ldn, cg);
-        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, cg, tw, nW, ldn);
-        dev.chol_solve_dev(h->kk_fac, tw, yw, (int)nW);
-        asmb::launch(k_kkt_axpby_mask, asmb::blocks(nW), dim3(256), s, 1.0, dlw, 1.0, yw, nullptr, nW, dlw);
-        asmb::launch(k_kkt_scatter, asmb::blocks(nW), dim3(256), s, dlw, h->d_kk_wrow, nW, dlf);
-        asmb::launch(k_gemv_n, asmb::blocks(nW, 4), dim3(256), s, h->d_kk_Aw, ldn, ddx, adx, nW, ldn);
-        // J' dlam over all columns (the bound columns too) from the private dense J
+    void jt_dlam(const double*, const double* dlf, double* jtl, int) override {
+        const int64_t m = h->m;
         int64_t Rc = std::min<int64_t>((m + 31) / 32, ASM_TMAXCHUNKS);
         const int64_t chunk = (m + Rc - 1) / Rc;
         Rc = (m + chunk - 1) / chunk;
-        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->d_kk_J, ldn, dlf, h->d_partial, m, ldn, chunk);
-        asmb::launch(k_gemv_t_stage2, gl, dim3(256), s, h->d_partial, jtl, Rc, ldn);
-    } else {
-        HIPCHK(asmb::fill_async(jtl, 0, ldn * sizeof(double), s));
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->kk.J, ldn, dlf, h->d_partial, m, ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(ldn), dim3(256), s, h->d_partial, jtl, Rc, ldn);
     }
-    asmb::launch(k_kkt_finish, dim3(1), dim3(1024), s, R, hdx, d_ru, jtl, mask, n, adx, rww, nW, ddz);
-    double* back = h->h_kk + 2 * ldn + 2 * Mp;
-    HIPCHK(asmb::copy_async(back, ddx, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(asmb::copy_async(back + ldn, ddz, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (m > 0) HIPCHK(asmb::copy_async(back + 2 * ldn, dlf, m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(asmb::copy_async(back + 2 * ldn + Mp, h->d_kk_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(asmb::copy_async(back + 2 * ldn + Mp + 16, h->d_kk_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(asmb::sync(s));
-    dev.resolve_timing();
-    std::memcpy(dx, back, n * sizeof(double));
-    if (dz) std::memcpy(dz, back + ldn, n * sizeof(double));
-    if (m > 0) std::memcpy(dlam, back + 2 * ldn, m * sizeof(double));
-    const double* sc = back + 2 * ldn + Mp;
-    const int dropped = *reinterpret_cast<const int*>(back + 2 * ldn + Mp + 16);
-    if (dropped > 0) status = 3;
-    info->status = status; info->cg_iters = iters; info->n_free = (int32_t)nF; info->n_rows = (int32_t)nW; info->dropped_pivots = dropped;
-    info->res_stat = sc[KK_RSTAT]; info->res_feas = sc[KK_RFEAS];
+};
+// a block of columns: k_gemm_nt products on the matrix cores (Dev::gemm_nt), Dev::trsm_rows in place with the factor's wide-block
+// inverses and its transposed copy, one Hessian launch for all columns, J_W' dlam_W from the unmasked transposed working rows.  Its own
+// operands are made here, once per call.
+struct KktBlock final : KktOps {
+    KktBlock(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww) : KktOps(hh, d, ff, ww) {
+        const KktBufs& K = h->kk;
+        const int64_t nW = f.nW;
+        if (nW > 0) {
+            const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
+            asmb::launch(k_kktm_gather_t, gt, dim3(256), s, K.J, ldn, f.wrow, (const double*)nullptr, nW, f.nWp, w.AfT, ldT);
+            // (the rows of Lt up to |W| rounded up to 32 are cleared first: the k-padding beside the nW x nW square the transposition writes)
+            HIPCHK(asmb::fill_async(w.Lt, 0, f.nWp * K.fac.ld * sizeof(double), s));
+            asmb::launch(k_transpose_dense, dim3((unsigned)((nW + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, K.fac.S, K.fac.ld, nW, nW, w.Lt, K.fac.ld, nW);
+        }
+        // the blocks over the working rows are zero beyond column nW (the k-padding of the products that read them)
+        HIPCHK(asmb::fill_async(w.row, 0, 5 * w.cap * ldT * sizeof(double), s));
+    }
+    // (rows >= cols of V are read - they exist: the blocks have KKM_CW rows - not written)
+    void hess(const double* v, double* out, int cols) override {
+        const HsShared& L = *h->hs_sh;
+        const dim3 g = asmb::blocks(n);
+        if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+    }
+    void mul_A(const double* v, double* t, int cols) override { dev.gemm_nt(v, ldn, h->kk.Aw, ldn, nullptr, 0, t, ldT, cols, (int)f.nW, (int)ldn, 0); }
+    void mul_AT(const double* y, double* v, int cols) override { dev.gemm_nt(y, ldT, h->kk.AwT, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)f.nWp, 0); }
+    double* solve_S(const double* b, double* t, int cols) override {
+        if (b != t) HIPCHK(asmb::copy_async(t, b, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
+        dev.trsm_rows(h->kk.fac, t, spare, ldT, cols, (int)f.nW, w.Lt);
+        return t;
+    }
+    void jt_dlam(const double* dlw, const double*, double* jtl, int cols) override { dev.gemm_nt(dlw, ldT, w.AfT, ldT, nullptr, 0, jtl, ldn, cols, (int)ldn, (int)f.nWp, 0); }
+};
+
+// Steps 3 to 6 for nrhs columns in chunks of the work area's capacity.  sens false: the rows of RU, RW are the right-hand sides;
+// otherwise the rows of DC are directions of the data and the cross-derivative sweep makes each column's right-hand sides on the
+// device (lambda: its multipliers).  The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product and substitution is ops'.
+// rounds, last_active: the lockstep rounds of the call and the last active-column word read.
+void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, const double* RU, const double* RW, const double* DC, bool sens, const double* lambda, double* DX,
+                 double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active) {
+    const KktBufs& K = h->kk;
+    KktWork& w = ops.w;
+    const hipStream_t s = h->stream;
+    const int64_t n = h->n, m = h->m, ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW, nd = sens ? h->ev_n_dpar : 0;
+    const double* const mask = f.mask;
+    auto vblock = [&](int k) { return w.vec + (int64_t)k * cap * ldn; };
+    auto rblock = [&](int k) { return w.row + (int64_t)k * cap * ldT; };      // (block 2 is ops.spare)
+    double *b_ru = vblock(0), *dx0 = vblock(1), *cd = vblock(2), *cr = vblock(3), *cp = vblock(4), *hraw = vblock(5), *hp = vblock(6), *tt = vblock(7), *ddx = vblock(8),
+           *hdx = vblock(9), *qq = vblock(10), *jtl = vblock(11), *ddz = vblock(12), *cg = vblock(13);
+    double *rww = rblock(0), *tw = rblock(1), *dlw = rblock(3), *adx = rblock(4);
+    double* const dlf = w.dlf;
+    double* const scal = K.scal;
+    const KktMulti R{K.part, K.cnt, scal, K.act, h->d_hscal, h->d_hseq};
+    const bool cross = sens && h->d_ev_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
+    if (cross) {      // the multipliers of the expression rows, once
+        cx_prepare(h);
+        const ExprTape& X = h->ev_X;
+        if (X.R > 0) {
+            std::memcpy(h->h_cx, lambda + h->ev_F.n_rows, X.R * sizeof(double));
+            HIPCHK(asmb::copy_async(h->d_cx_in, h->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+    }
+    const dim3 gl = asmb::blocks(ldn);
+    const unsigned gred = (unsigned)std::min<int64_t>(gl.x, KK_MAXWG);
+    const bool run_cg = f.nF > nW;
+    int dropped = 0;
+    rounds = 0;
+    last_active = 0;
+    for (int64_t c0 = 0; c0 < nrhs; c0 += cap) {
+        const int cols = (int)std::min<int64_t>(cap, nrhs - c0);
+        const dim3 glc(gl.x, (unsigned)cols), grc((unsigned)((nW + 255) / 256), (unsigned)cols), gredc(gred, (unsigned)cols);
+        double* st = w.stage;                                    // [ru block | rw block | directions], then the results
+        double* back = st + cap * (ldn + ldT + std::max<int64_t>(h->ev_n_dpar, 1));
+        auto axpby = [&](double sa, const double* a, double sb, const double* b, const double* sc, double* out) {
+            asmb::launch(k_kktm_axpby, glc, dim3(256), s, sa, a, sb, b, mask, ldn, ldn, sc, out);
+        };
+        auto axpby_rows = [&](double sa, const double* a, double sb, const double* b, double* out) {
+            asmb::launch(k_kktm_axpby, grc, dim3(256), s, sa, a, sb, b, (const double*)nullptr, nW, ldT, (const double*)nullptr, out);
+        };
+        // tt = A' S^-1 b for a block b over the working rows (t: where the substitution may work)
+        auto normal_back = [&](const double* b, double* t) { ops.mul_AT(ops.solve_S(b, t, cols), tt, cols); };
+        // v -= A' S^-1 A v for the columns that sc leaves active (all of them when sc == nullptr)
+        auto project = [&](double* v, const double* sc) {
+            if (nW == 0) return;
+            ops.mul_A(v, tw, cols);
+            normal_back(tw, tw);
+            axpby(1.0, v, -1.0, tt, sc, v);
+        };
+        // 3. the right-hand sides of the chunk
+        if (!sens) {
+            for (int c = 0; c < cols; ++c) {
+                const double *u = RU + (c0 + c) * n, *rw = RW ? RW + (c0 + c) * m : nullptr;
+                double *du = st + (int64_t)c * ldn, *dw = st + cap * ldn + (int64_t)c * ldT;
+                std::memcpy(du, u, n * sizeof(double));
+                for (int64_t j = n; j < ldn; ++j) du[j] = 0.0;
+                for (int64_t q = 0; q < ldT; ++q) dw[q] = q < nW ? rw[f.wl[q]] : 0.0;
+            }
+            HIPCHK(asmb::copy_async(b_ru, st, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
+            HIPCHK(asmb::copy_async(rww, st + cap * ldn, (int64_t)cols * ldT * sizeof(double), hipMemcpyHostToDevice, s));
+        } else if (cross) {
+            // one sweep per direction, no synchronisation between them: every direction has its own staging row
+            const ExprTape& X = h->ev_X;
+            double* hd = st + cap * (ldn + ldT);
+            for (int c = 0; c < cols; ++c) {
+                std::memcpy(hd + (int64_t)c * nd, DC + (c0 + c) * nd, nd * sizeof(double));
+                HIPCHK(asmb::copy_async(h->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
+                asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->cx_C, h->d_ev_xt, h->d_cx_in + X.R, h->d_cx_in, h->ev_F.objective_scale, h->d_cx_out + n);
+                asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->cx_C, n, h->d_cx_out);
+                asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->d_cx_out, n, (int64_t)h->ev_F.n_rows, f.wrow, nW, b_ru + (int64_t)c * ldn,
+                             rww + (int64_t)c * ldT);
+            }
+        } else {
+            HIPCHK(asmb::fill_async(b_ru, 0, cap * ldn * sizeof(double), s));
+            HIPCHK(asmb::fill_async(rww, 0, cap * ldT * sizeof(double), s));
+        }
+        // particular solution dx0 = -A' S^-1 rw_W
+        if (nW > 0) {
+            normal_back(rww, tw);
+            axpby(-1.0, tt, 0.0, nullptr, nullptr, dx0);
+            // one refinement step of the normal-equation solve: dx0 -= A' S^-1 (A dx0 + rw_W)
+            ops.mul_A(dx0, adx, cols);
+            axpby_rows(1.0, adx, 1.0, rww, tw);
+            normal_back(tw, tw);
+            axpby(1.0, dx0, -1.0, tt, nullptr, dx0);
+        } else {
+            HIPCHK(asmb::fill_async(dx0, 0, cap * ldn * sizeof(double), s));
+        }
+        // 4. projected conjugate gradients on null(A), the columns in lockstep: minimise 1/2 d'H_FF d + (ru_F + H_FF dx0)'d
+        HIPCHK(asmb::fill_async(cd, 0, cap * ldn * sizeof(double), s));
+        if (run_cg) {
+            ops.hess(dx0, hraw, cols);
+            axpby(1.0, b_ru, 1.0, hraw, nullptr, cr);
+            HIPCHK(asmb::fill_async(cp, 0, cap * ldn * sizeof(double), s));
+            // the residual is kept projected (r = g = P P r): it then has no large component in range(A') for the projection's rounding to act on
+            project(cr, nullptr);
+            project(cr, nullptr);
+            unsigned pub = pub_next(h);
+            asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 1, f.rtol, pub);
+            int active = kk_read_scal(h, pub);
+            for (int64_t it = 0; active > 0 && it < f.max_iter; ++it) {
+                asmb::launch(k_kktm_cg_p, glc, dim3(256), s, (const double*)scal, (const double*)cr, cp, ldn, ldn);
+                ops.hess(cp, hraw, cols);
+                asmb::launch(k_kktm_cg_curv, gredc, dim3(256), s, R, (const double*)cp, (const double*)hraw, mask, hp, ldn, ldn);
+                asmb::launch(k_kktm_cg_step, glc, dim3(256), s, (const double*)scal, (const double*)cp, (const double*)hp, cd, cr, ldn, ldn);
+                project(cr, scal);
+                project(cr, scal);
+                pub = pub_next(h);
+                asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 0, f.rtol, pub);
+                active = kk_read_scal(h, pub);
+                rounds += 1;
+            }
+            last_active = active;
+        }
+        // 5., 6. the solutions, their multipliers and residuals
+        axpby(1.0, dx0, 1.0, cd, nullptr, ddx);
+        ops.hess(ddx, hdx, cols);
+        HIPCHK(asmb::fill_async(dlf, 0, cap * Mp * sizeof(double), s));
+        if (nW > 0) {
+            axpby(1.0, hdx, 1.0, b_ru, nullptr, qq);
+            ops.mul_A(qq, tw, cols);
+            ops.solve_S(tw, dlw, cols);
+            // one refinement step: dlam_W += S^-1 A (q - A' dlam_W)
+            ops.mul_AT(dlw, tt, cols);
+            axpby(1.0, qq, -1.0, tt, nullptr, cg);
+            ops.mul_A(cg, tw, cols);
+            axpby_rows(1.0, dlw, 1.0, ops.solve_S(tw, tw, cols), dlw);
+            asmb::launch(k_kktm_scatter, grc, dim3(256), s, (const double*)dlw, ldT, f.wrow, nW, dlf, Mp);
+            ops.mul_A(ddx, adx, cols);
+            ops.jt_dlam(dlw, dlf, jtl, cols);
+        } else {
+            HIPCHK(asmb::fill_async(jtl, 0, cap * ldn * sizeof(double), s));
+        }
+        asmb::launch(k_kktm_finish, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)hdx, (const double*)b_ru, (const double*)jtl, mask, n, ldn, (const double*)adx,
+                     (const double*)rww, nW, ldT, ddz);
+        HIPCHK(asmb::copy_async(back, ddx, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::copy_async(back + cap * ldn, ddz, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (m > 0) HIPCHK(asmb::copy_async(back + 2 * cap * ldn, dlf, (int64_t)cols * Mp * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::copy_async(back + cap * (2 * ldn + Mp), scal, (int64_t)cols * KKM_SCAL * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (c0 == 0) HIPCHK(asmb::copy_async(back + cap * (2 * ldn + Mp + KKM_SCAL), K.dropped, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::sync(s));
+        if (c0 == 0) dropped = *reinterpret_cast<const int*>(back + cap * (2 * ldn + Mp + KKM_SCAL));
+        for (int c = 0; c < cols; ++c) {
+            std::memcpy(DX + (c0 + c) * n, back + (int64_t)c * ldn, n * sizeof(double));
+            if (DZ) std::memcpy(DZ + (c0 + c) * n, back + cap * ldn + (int64_t)c * ldn, n * sizeof(double));
+            if (m > 0) std::memcpy(DLAM + (c0 + c) * m, back + 2 * cap * ldn + (int64_t)c * Mp, m * sizeof(double));
+            const double* sc = back + cap * (2 * ldn + Mp) + (int64_t)c * KKM_SCAL;
+            asm_kkt_info& o = info[c0 + c];
+            // (without an iteration - a vertex - the column's stop code and count are not written: solved, no iteration)
+            const int stop = run_cg ? (int)sc[KK_STOP] : 1;
+            o.status = dropped > 0 ? 3 : (stop == 2 ? 2 : (stop == 0 ? 1 : 0));
+            o.cg_iters = run_cg ? (int32_t)sc[KKM_ITERS] : 0; o.n_free = (int32_t)f.nF; o.n_rows = (int32_t)nW; o.dropped_pivots = dropped;
+            o.res_stat = sc[KK_RSTAT]; o.res_feas = sc[KK_RFEAS];
+        }
+    }
+    ops.dev.resolve_timing();
+}
+}  // namespace
+
+static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru,
+                         const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
+    hs_check(h, "asm_kkt_solve");
+    if (!x || !bound_state || !ru || !dx || !info || (h->m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
+    Dev dev(h);
+    const KktFace f(h, dev, "asm_kkt_solve", x, lambda, row_state, bound_state, par);
+    KktOneColumn ops(h, dev, f, *kk_work(h, 1));
+    int64_t rounds;
+    int last_active;
+    kkt_columns(h, f, ops, 1, ru, rw, nullptr, false, lambda, dx, dlam, dz, info, rounds, last_active);
 }
 static void do_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
                                     const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
@@ -4646,299 +4831,21 @@ static void do_solution_sensitivity(asm_handle* h, const double* x, const double
     do_data_cross(h, x, lambda, dc, u.data(), w.data());
     do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info);
 }
-
-// ---- many right-hand sides on one factor (include/asm_hip.h, "Many right-hand sides on one factor")
-static_assert(KKM_CW == ASM_KKT_CHUNK && KKM_CW % 32 == 0 && KKM_SCAL > KKM_ITERS, "the chunk width of the header is the kernels'");
-namespace {
-// at the first asm_kkt_solve_multi after asm_eval_setup: the buffers of one chunk, beside the single solve's in mem_kk
-void kkm_prepare(asm_handle* h) {
-    if (h->kkm_ready) return;
-    HIPCHK(hipSetDevice(h->device));
-    BufPool& M = h->mem_kk;
-    const hipStream_t s = h->stream;
-    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), ldT = h->kk_ldT, CW = KKM_CW, nd = std::max<int64_t>(h->ev_n_dpar, 1);
-    M.zeroed(h->d_kkm_vec, 14 * CW * ldn, s);
-    M.zeroed(h->d_kkm_row, 5 * CW * ldT, s);
-    M.zeroed(h->d_kkm_dlf, CW * Mp, s);
-    M.zeroed(h->d_kkm_Lt, h->kk_fac.ld * h->kk_fac.ld, s);
-    M.zeroed(h->d_kkm_AfT, ldn * ldT, s);
-    M.zeroed(h->d_kkm_part, CW * KK_MAXWG * KK_SLOTS, s);
-    M.zeroed(h->d_kkm_scal, CW * KKM_SCAL + 16, s);
-    M.zeroed(h->d_kkm_cnt, CW + 4, s);
-    M.zeroed(h->d_kkm_act, CW, s);
-    M.alloc(h->h_kkm, CW * (3 * ldn + ldT + Mp + KKM_SCAL + nd) + 64, BufPool::PINNED);
-    HIPCHK(asmb::sync(s));
-    h->kkm_ready = true;
-}
-}  // namespace
-// asm_kkt_solve_multi (DC == nullptr: the rows of RU, RW are the right-hand sides) and asm_solution_sensitivity_multi (the rows of DC
-// are directions of the data: the cross-derivative sweep makes each column's right-hand sides on the device).  Steps 1 and 2 of the
-// method once per call, then chunks of KKM_CW columns through steps 3 to 6 on blocks.
+// asm_kkt_solve_multi (sens false: the rows of RU, RW are the right-hand sides) and asm_solution_sensitivity_multi (the rows of DC are
+// directions of the data)
 static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                const double* RU, const double* RW, const double* DC, bool sens, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
                                asm_kkt_info* info) {
     const std::string me(who);
     if (sens) cx_check(h, who);
     hs_check(h, who);
-    const int64_t n = h->n, m = h->m, ldn = h->ldn, nd = sens ? h->ev_n_dpar : 0;
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
-    if (!x || !bound_state || !DX || !info || (m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
-    if (sens ? (nd > 0 && !DC) : (!RU || (m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
-    int64_t nF = 0, nW = 0;
-    for (int64_t j = 0; j < n; ++j) {
-        if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
-        nF += bound_state[j] == 0;
-    }
-    for (int64_t i = 0; i < m; ++i) {
-        if (row_state[i] != 0 && row_state[i] != 1) throw std::invalid_argument(me + ": row_state holds a value outside {0, 1}");
-        nW += row_state[i];
-    }
-    if (nW > nF) throw std::invalid_argument(me + ": more working rows (" + std::to_string(nW) + ") than free variables (" + std::to_string(nF) + ")");
-    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
-    const int64_t max_iter = par ? par->max_iter : 2 * (nF - nW) + 20;
-    const double rtol = par ? par->rtol : 1e-12;
-    if (asmb::in_fiber()) throw std::logic_error(me + ": not inside a scenario batch");
-    hs_prepare(h);
-    kk_prepare(h);
-    kkm_prepare(h);
-    const bool cross = sens && h->d_ev_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
-    if (cross) cx_prepare(h);
-    HIPCHK(hipSetDevice(h->device));
+    if (!x || !bound_state || !DX || !info || (h->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
+    if (sens ? (h->ev_n_dpar > 0 && !DC) : (!RU || (h->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
     Dev dev(h);
-    const hipStream_t s = h->stream;
-    const int64_t Mp = std::max<int64_t>(h->Mp, 32), ldT = h->kk_ldT, CW = KKM_CW, nWp = round_up(nW, 32);
-    double* const mask = h->d_kk_vec;
-    auto vblock = [&](int k) { return h->d_kkm_vec + (int64_t)k * CW * ldn; };
-    auto rblock = [&](int k) { return h->d_kkm_row + (int64_t)k * CW * ldT; };
-    double *b_ru = vblock(0), *dx0 = vblock(1), *cd = vblock(2), *cr = vblock(3), *cp = vblock(4), *hraw = vblock(5), *hp = vblock(6), *tt = vblock(7), *ddx = vblock(8),
-           *hdx = vblock(9), *qq = vblock(10), *jtl = vblock(11), *ddz = vblock(12), *cg = vblock(13);
-    double *rww = rblock(0), *tw = rblock(1), *xw = rblock(2), *dlw = rblock(3), *adx = rblock(4);
-    double* const dlf = h->d_kkm_dlf;
-    double* const scal = h->d_kkm_scal;
-    const KktMulti R{h->d_kkm_part, h->d_kkm_cnt, scal, h->d_kkm_act, h->d_hscal, h->d_hseq};
-    // 1. the Hessian values of f - lambda' g at x, once (x goes to d_ev_xt)
-    {
-        std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
-        for (int64_t i = 0; i < m; ++i) nl[i] = -lambda[i];
-        hs_launch(h, x, 1.0, nl.data(), nullptr);
-    }
-    const HsShared& L = *h->hs_sh;
-    // 2. the Jacobian at x into the solve's own value buffer and dense J
-    {
-        const FnStore& F = h->ev_F;
-        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, 1, (int64_t)0, (int64_t)0);
-        const ExprTape& X = h->ev_X;
-        if (h->ev_nlp_kind == ASM_NLP_EXPR && X.R > 0)
-            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->d_ev_xt, h->d_ev_Et, h->d_kk_dE, F.n_rows, h->ev_fn_nnz, 1, (int64_t)0, (int64_t)0);
-        if (h->dense_fast) {
-            const unsigned g = (unsigned)std::min<int64_t>((h->m * h->n + 255) / 256, 4096);
-            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, h->d_kk_dE, h->d_kk_J, h->m, h->n, ldn);
-        } else if (h->nu > 0) {
-            const unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
-            asmb::launch(k_assemble, dim3(g), dim3(256), s, h->d_kk_dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, h->d_kk_J, h->nu);
-        }
-    }
-    // the sets
-    std::vector<int> wl((size_t)Mp, 0);
-    {
-        double* st = h->h_kk;
-        for (int64_t j = 0; j < ldn; ++j) st[j] = (j < n && bound_state[j] == 0) ? 1.0 : 0.0;
-        int* dl = reinterpret_cast<int*>(st + ldn);
-        int64_t q = 0;
-        for (int64_t i = 0; i < m; ++i)
-            if (row_state[i]) wl[q++] = (int)i;
-        std::copy(wl.begin(), wl.end(), dl);
-        HIPCHK(asmb::copy_async(mask, st, ldn * sizeof(double), hipMemcpyHostToDevice, s));
-        HIPCHK(asmb::copy_async(h->d_kk_wrow, dl, Mp * sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    const dim3 gl = asmb::blocks(ldn);
-    const unsigned gred = (unsigned)std::min<int64_t>(gl.x, KK_MAXWG);
-    // A = J[W, F] as a dense operand, its transposed copy with the k-padding cleared, the unmasked transposed rows (for J' dlam on B);
-    // S = A A', its factor with the wide-block inverses (Dev::chol makes them) and the factor's transposed copy for the backward pass
-    if (nW > 0) {
-        const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((nWp + 63) / 64));
-        asmb::launch(k_kkt_gather, dim3(gl.x, (unsigned)nW), dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, mask, nW, h->d_kk_Aw);
-        asmb::launch(k_kktm_gather_t, gt, dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, mask, nW, nWp, h->d_kk_AwT, ldT);
-        asmb::launch(k_kktm_gather_t, gt, dim3(256), s, h->d_kk_J, ldn, h->d_kk_wrow, (const double*)nullptr, nW, nWp, h->d_kkm_AfT, ldT);
-        dev.launch_syrk(s, Dev::pick_tile(nW), h->d_kk_Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, h->kk_fac.S, h->kk_fac.ld, 0, 0);
-        dev.diag_prepare(h->kk_fac, (int)nW, 1, 0.0, 0.0);
-        const int nfact = h->stats.nfact;
-        dev.chol(h->kk_fac, (int)nW, 1e-10);
-        h->stats.nfact = nfact;
-        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, h->kk_fac.S, h->kk_fac.ld, (int)nW, NS_BIG, h->d_kk_cnt);
-        // (its rows up to |W| rounded up to 32 are cleared first: the k-padding beside the nW x nW square the transposition writes)
-        HIPCHK(asmb::fill_async(h->d_kkm_Lt, 0, nWp * h->kk_fac.ld * sizeof(double), s));
-        asmb::launch(k_transpose_dense, dim3((unsigned)((nW + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, h->kk_fac.S, h->kk_fac.ld, nW, nW, h->d_kkm_Lt, h->kk_fac.ld, nW);
-    } else {
-        HIPCHK(asmb::fill_async(h->d_kk_cnt, 0, 4 * sizeof(int), s));
-    }
-    // the blocks over the working rows are zero beyond column nW (the k-padding of the products that read them)
-    HIPCHK(asmb::fill_async(h->d_kkm_row, 0, 5 * CW * ldT * sizeof(double), s));
-    if (cross) {      // the multipliers of the expression rows, once
-        const ExprTape& X = h->ev_X;
-        if (X.R > 0) {
-            std::memcpy(h->h_cx, lambda + h->ev_F.n_rows, X.R * sizeof(double));
-            HIPCHK(asmb::copy_async(h->d_cx_in, h->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-    }
-    auto pub_next = [&]() -> unsigned {
-        if (!h->knobs.spin_read) return 0;
-        h->scal_seq += 1;
-        if (h->scal_seq == 0) h->scal_seq = 1;
-        return h->scal_seq;
-    };
-    // the number of columns still active after the last k_kktm_cg_dir
-    auto read_active = [&](unsigned pub) -> int {
-        if (pub == 0) {
-            HIPCHK(asmb::copy_async(h->h_scal, scal + CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHK(asmb::sync(s));
-        } else {
-            kk_read_scal(h, pub);
-        }
-        return (int)h->h_scal[0];
-    };
-    int dropped = 0;
-    h->kkm_rounds = 0;
-    h->kkm_last_active = 0;
-    for (int64_t c0 = 0; c0 < nrhs; c0 += CW) {
-        const int cols = (int)std::min<int64_t>(CW, nrhs - c0);
-        const dim3 glc(gl.x, (unsigned)cols), grc((unsigned)((nW + 255) / 256), (unsigned)cols);
-        double* st = h->h_kkm;                                   // [ru block | rw block | directions], then the results
-        double* back = st + CW * (ldn + ldT + std::max<int64_t>(h->ev_n_dpar, 1));
-        auto axpby = [&](double sa, const double* a, double sb, const double* b, const double* sc, double* out) {
-            asmb::launch(k_kktm_axpby, glc, dim3(256), s, sa, a, sb, b, (const double*)mask, ldn, ldn, sc, out);
-        };
-        auto axpby_rows = [&](double sa, const double* a, double sb, const double* b, double* out) {
-            asmb::launch(k_kktm_axpby, grc, dim3(256), s, sa, a, sb, b, (const double*)nullptr, nW, ldT, (const double*)nullptr, out);
-        };
-        auto hess_product = [&](const double* v, double* out) {
-            const dim3 g = asmb::blocks(n);
-            if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-            else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-            else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-            else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-        };
-        auto mul_A = [&](const double* v, double* t) { dev.gemm_nt(v, ldn, h->d_kk_Aw, ldn, nullptr, 0, t, ldT, cols, (int)nW, (int)ldn, 0); };                 // T = V A'
-        auto mul_AT = [&](const double* y, const double* at, double* v) { dev.gemm_nt(y, ldT, at, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)nWp, 0); };      // V = Y A
-        auto solve_S = [&](double* t) { dev.trsm_rows(h->kk_fac, t, xw, ldT, cols, (int)nW, h->d_kkm_Lt); };                                                    // in place
-        // v -= A' S^-1 A v for the columns that sc leaves active (all of them when sc == nullptr)
-        auto project = [&](double* v, const double* sc) {
-            if (nW == 0) return;
-            mul_A(v, tw);
-            solve_S(tw);
-            mul_AT(tw, h->d_kk_AwT, tt);
-            axpby(1.0, v, -1.0, tt, sc, v);
-        };
-        // 3. the right-hand sides of the chunk
-        if (!sens) {
-            for (int c = 0; c < cols; ++c) {
-                const double *u = RU + (c0 + c) * n, *w = RW ? RW + (c0 + c) * m : nullptr;
-                double *du = st + (int64_t)c * ldn, *dw = st + CW * ldn + (int64_t)c * ldT;
-                std::memcpy(du, u, n * sizeof(double));
-                for (int64_t j = n; j < ldn; ++j) du[j] = 0.0;
-                for (int64_t q = 0; q < ldT; ++q) dw[q] = q < nW ? w[wl[q]] : 0.0;
-            }
-            HIPCHK(asmb::copy_async(b_ru, st, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
-            HIPCHK(asmb::copy_async(rww, st + CW * ldn, (int64_t)cols * ldT * sizeof(double), hipMemcpyHostToDevice, s));
-        } else if (cross) {
-            // one sweep per direction, no synchronisation between them: every direction has its own staging row
-            const ExprTape& X = h->ev_X;
-            double* hd = st + CW * (ldn + ldT);
-            for (int c = 0; c < cols; ++c) {
-                std::memcpy(hd + (int64_t)c * nd, DC + (c0 + c) * nd, nd * sizeof(double));
-                HIPCHK(asmb::copy_async(h->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
-                asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->cx_C, h->d_ev_xt, h->d_cx_in + X.R, h->d_cx_in, h->ev_F.objective_scale, h->d_cx_out + n);
-                asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->cx_C, n, h->d_cx_out);
-                asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->d_cx_out, n, (int64_t)h->ev_F.n_rows, h->d_kk_wrow, nW, b_ru + (int64_t)c * ldn,
-                             rww + (int64_t)c * ldT);
-            }
-        } else {
-            HIPCHK(asmb::fill_async(b_ru, 0, CW * ldn * sizeof(double), s));
-            HIPCHK(asmb::fill_async(rww, 0, CW * ldT * sizeof(double), s));
-        }
-        HIPCHK(asmb::fill_async(scal, 0, (CW * KKM_SCAL + 16) * sizeof(double), s));
-        // particular solution dx0 = -A' S^-1 rw_W with one refinement step
-        if (nW > 0) {
-            HIPCHK(asmb::copy_async(tw, rww, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
-            solve_S(tw);
-            mul_AT(tw, h->d_kk_AwT, tt);
-            axpby(-1.0, tt, 0.0, nullptr, nullptr, dx0);
-            mul_A(dx0, adx);
-            axpby_rows(1.0, adx, 1.0, rww, tw);
-            solve_S(tw);
-            mul_AT(tw, h->d_kk_AwT, tt);
-            axpby(1.0, dx0, -1.0, tt, nullptr, dx0);
-        } else {
-            HIPCHK(asmb::fill_async(dx0, 0, CW * ldn * sizeof(double), s));
-        }
-        // 4. the columns' projected conjugate gradients in lockstep
-        HIPCHK(asmb::fill_async(cd, 0, CW * ldn * sizeof(double), s));
-        const bool run_cg = nF > nW;
-        if (run_cg) {
-            hess_product(dx0, hraw);
-            axpby(1.0, b_ru, 1.0, hraw, nullptr, cr);
-            HIPCHK(asmb::fill_async(cp, 0, CW * ldn * sizeof(double), s));
-            project(cr, nullptr);
-            project(cr, nullptr);
-            unsigned pub = pub_next();
-            asmb::launch(k_kktm_cg_dir, dim3(gred, (unsigned)cols), dim3(256), s, R, (const double*)cr, ldn, ldn, 1, rtol, pub);
-            int active = read_active(pub);
-            for (int64_t it = 0; active > 0 && it < max_iter; ++it) {
-                asmb::launch(k_kktm_cg_p, glc, dim3(256), s, (const double*)scal, (const double*)cr, cp, ldn, ldn);
-                hess_product(cp, hraw);
-                asmb::launch(k_kktm_cg_curv, dim3(gred, (unsigned)cols), dim3(256), s, R, (const double*)cp, (const double*)hraw, (const double*)mask, hp, ldn, ldn);
-                asmb::launch(k_kktm_cg_step, glc, dim3(256), s, (const double*)scal, (const double*)cp, (const double*)hp, cd, cr, ldn, ldn);
-                project(cr, scal);
-                project(cr, scal);
-                pub = pub_next();
-                asmb::launch(k_kktm_cg_dir, dim3(gred, (unsigned)cols), dim3(256), s, R, (const double*)cr, ldn, ldn, 0, rtol, pub);
-                active = read_active(pub);
-                h->kkm_rounds += 1;
-            }
-            h->kkm_last_active = active;
-        }
-        // 5., 6. the solutions, their multipliers and residuals
-        axpby(1.0, dx0, 1.0, cd, nullptr, ddx);
-        hess_product(ddx, hdx);
-        HIPCHK(asmb::fill_async(dlf, 0, CW * Mp * sizeof(double), s));
-        if (nW > 0) {
-            axpby(1.0, hdx, 1.0, b_ru, nullptr, qq);
-            mul_A(qq, tw);
-            solve_S(tw);
-            HIPCHK(asmb::copy_async(dlw, tw, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
-            mul_AT(dlw, h->d_kk_AwT, tt);
-            axpby(1.0, qq, -1.0, tt, nullptr, cg);
-            mul_A(cg, tw);
-            solve_S(tw);
-            axpby_rows(1.0, dlw, 1.0, tw, dlw);
-            asmb::launch(k_kktm_scatter, grc, dim3(256), s, (const double*)dlw, ldT, h->d_kk_wrow, nW, dlf, Mp);
-            mul_A(ddx, adx);
-            mul_AT(dlw, h->d_kkm_AfT, jtl);          // J_W' dlam_W over all columns, the bound columns too
-        } else {
-            HIPCHK(asmb::fill_async(jtl, 0, CW * ldn * sizeof(double), s));
-        }
-        asmb::launch(k_kktm_finish, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)hdx, (const double*)b_ru, (const double*)jtl, (const double*)mask, n, ldn,
-                     (const double*)adx, (const double*)rww, nW, ldT, ddz);
-        HIPCHK(asmb::copy_async(back, ddx, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(asmb::copy_async(back + CW * ldn, ddz, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(asmb::copy_async(back + 2 * CW * ldn, dlf, (int64_t)cols * Mp * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(asmb::copy_async(back + CW * (2 * ldn + Mp), scal, (int64_t)cols * KKM_SCAL * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (c0 == 0) HIPCHK(asmb::copy_async(back + CW * (2 * ldn + Mp + KKM_SCAL), h->d_kk_cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(asmb::sync(s));
-        if (c0 == 0) dropped = *reinterpret_cast<const int*>(back + CW * (2 * ldn + Mp + KKM_SCAL));
-        for (int c = 0; c < cols; ++c) {
-            std::memcpy(DX + (c0 + c) * n, back + (int64_t)c * ldn, n * sizeof(double));
-            if (DZ) std::memcpy(DZ + (c0 + c) * n, back + CW * ldn + (int64_t)c * ldn, n * sizeof(double));
-            if (m > 0) std::memcpy(DLAM + (c0 + c) * m, back + 2 * CW * ldn + (int64_t)c * Mp, m * sizeof(double));
-            const double* sc = back + CW * (2 * ldn + Mp) + (int64_t)c * KKM_SCAL;
-            asm_kkt_info& o = info[c0 + c];
-            const int stop = (int)sc[KK_STOP];
-            o.status = dropped > 0 ? 3 : (stop == 2 ? 2 : (run_cg && stop == 0 ? 1 : 0));
-            o.cg_iters = (int32_t)sc[KKM_ITERS]; o.n_free = (int32_t)nF; o.n_rows = (int32_t)nW; o.dropped_pivots = dropped;
-            o.res_stat = sc[KK_RSTAT]; o.res_feas = sc[KK_RFEAS];
-        }
-    }
-    dev.resolve_timing();
+    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par);
+    KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
+    kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->kkm_rounds, h->kkm_last_active);
 }
 
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)

@@ -1,13 +1,19 @@
-// Kernels of the KKT solve on a working set (asm_kkt_solve; include/asm_hip.h, "The KKT solve on a working set"): the gather of the
-// working rows into a dense operand, masked vector updates, and the fused updates of the projected conjugate-gradient iteration.
-// The matrix products (k_gemv_n, k_gemv_n_exact, k_gemv_t_stage*), the rank-K build, the Cholesky factorisation and its substitutions
-// and the Hessian product (k_hess_product) are the library's existing kernels.  A and S are dense here: the sparse, banded and
-// null-space forms of the LP solver have no counterpart.
-// Vectors over the variables have the pitch ldn of the dense operands and are zero beyond n and on the bound set B (mask[j] = 0 there).
-// Dot products: every workgroup reduces its share (wavefront shuffles, then LDS), stores its partial sums with agent-scope stores and
-// counts itself in; the last one to arrive adds the partials in workgroup order - a fixed order, no atomics on doubles - and writes
-// the scalars of the iteration into a block in HBM that the next kernel reads (alpha, beta and the curvature test never visit the
-// host).  The host reads one word per iteration: the stop code, published through the handle's host-mapped scalar block.
+// Kernels of the KKT solve on a working set (asm_kkt_solve and the multi entries; include/asm_hip.h, "The KKT solve on a working set" and
+// "Many right-hand sides on one factor"): the gathers of the working rows into dense operands, masked block updates, and the fused
+// updates of the projected conjugate-gradient iteration.  One family serves every entry: the right-hand sides of a chunk are the rows
+// of row-major blocks - up to KKM_CW rows of pitch ldv over the variables, of pitch ldr over the working rows - and every kernel has the
+// column in blockIdx.y; asm_kkt_solve launches them with one column.  The columns are independent iterations that advance together.  A
+// column whose stop code is set is frozen - no kernel writes its d, r or p again.  Every sum of a column runs in an order fixed by the
+// vector length alone, so a column's bits depend neither on the number of columns nor on its place among them.
+// The products with A, A' and H and the substitutions with S = A A' are not here: the host has two back ends for them (KktOneColumn:
+// k_gemv_n, k_gemv_n_exact, k_gemv_t_stage*, k_hess_product and the factor's own substitution; KktBlock: k_gemm_nt through Dev::gemm_nt
+// and Dev::trsm_rows, and k_kktm_hess_product below).  A and S are dense: the sparse, banded and null-space forms of the LP solver have
+// no counterpart.
+// Blocks over the variables are zero beyond n and on the bound set B (mask[j] = 0 there).
+// Dot products: every workgroup of a column reduces its share (wavefront shuffles, then LDS), stores its partial sums with agent-scope
+// stores and counts itself in; the last one to arrive adds the partials in workgroup order - a fixed order, no atomics on doubles - and
+// writes the column's scalars into its block in HBM that the next kernel reads (alpha, beta and the curvature test never visit the
+// host).  The host reads one word per round: the number of active columns, published through the handle's host-mapped scalar block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,8 +27,6 @@ struct KktRed {
     double* part;        // KK_MAXWG x KK_SLOTS partial sums
     unsigned* cnt;       // arrival counter, 0 between launches
     double* scal;        // KK_COUNT scalars in HBM
-    double* hscal;       // the same block in host-mapped memory
-    unsigned* hseq;      // its sequence word
 };
 
 // true in every thread of the workgroup that arrives last; called by all threads (as red_last_arrival of the interior-point kernels)
@@ -46,15 +50,6 @@ __device__ __forceinline__ double kk_total(const KktRed& R, int slot) {
     for (int w = 0; w < (int)gridDim.x; ++w) s += __hip_atomic_load(R.part + (int64_t)w * KK_SLOTS + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return s;
 }
-// the workgroup that wrote R.scal hands the block to the host: stores into host-mapped memory, a system-scope fence, the sequence word
-__device__ __forceinline__ void kk_publish(const KktRed& R, unsigned pub) {
-    if (pub == 0) return;
-    __syncthreads();
-    if (threadIdx.x < KK_COUNT) R.hscal[threadIdx.x] = R.scal[threadIdx.x];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(R.hseq, pub, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // Aw[q, j] = J[wrow[q], j] for j in F, 0 on B and in the padding: the working rows as a dense nW x ldn operand (blockIdx.y = q)
 __global__ __launch_bounds__(256) void k_kkt_gather(AsmBt abt, const double* __restrict__ J, int64_t ldn, const int* __restrict__ wrow, const double* __restrict__ mask, int64_t nW, double* __restrict__ Aw) {
@@ -63,121 +58,8 @@ __global__ __launch_bounds__(256) void k_kkt_gather(AsmBt abt, const double* __r
     if (q >= nW || j >= ldn) return;
     Aw[q * ldn + j] = mask[j] != 0.0 ? J[(int64_t)wrow[q] * ldn + j] : 0.0;
 }
-// out[wrow[q]] = y[q]: the multipliers of the working rows into their places among all m rows (out cleared before)
-__global__ __launch_bounds__(256) void k_kkt_scatter(AsmBt abt, const double* __restrict__ y, const int* __restrict__ wrow, int64_t nW, double* __restrict__ out) {
-    ASM_BARGS(abt, y, wrow, nW, out);
-    const int64_t q = blockIdx.x * 256 + threadIdx.x;
-    if (q < nW) out[wrow[q]] = y[q];
-}
-// out[j] = sa * a[j] + sb * b[j] on F, 0 elsewhere (b == nullptr: sa * a[j]; mask == nullptr, a vector over the rows: everywhere)
-__global__ __launch_bounds__(256) void k_kkt_axpby_mask(AsmBt abt, double sa, const double* a, double sb, const double* __restrict__ b, const double* __restrict__ mask, int64_t len, double* out) {      // (out may be a)
-    ASM_BARGS(abt, sa, a, sb, b, mask, len, out);
-    const int64_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= len) return;
-    double v = sa * a[j];
-    if (b) v += sb * b[j];
-    out[j] = (!mask || mask[j] != 0.0) ? v : 0.0;
-}
-// p = -g + beta p, beta from the scalar block (0 before the first iteration)
-__global__ __launch_bounds__(256) void k_kkt_cg_p(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ g, double* __restrict__ p, int64_t len) {
-    ASM_BARGS(abt, scal, g, p, len);
-    const int64_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= len) return;
-    const double beta = scal[KK_BETA];
-    p[j] = beta * p[j] - g[j];
-}
-// hp = (H p) on F; p'Hp; alpha = r'g / p'Hp, or the curvature stop when p'Hp <= 0 (or not a number)
-__global__ __launch_bounds__(256) void k_kkt_cg_curv(AsmBt abt, KktRed R, const double* __restrict__ p, const double* __restrict__ hp_raw, const double* __restrict__ mask, double* __restrict__ hp, int64_t len) {
-    ASM_BARGS(abt, R, p, hp_raw, mask, hp, len);
-    __shared__ double sh[4];
-    __shared__ bool last;
-    double acc = 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256) {
-        const double v = mask[j] != 0.0 ? hp_raw[j] : 0.0;
-        hp[j] = v;
-        acc += p[j] * v;
-    }
-    acc = blk_reduce_sum(acc, sh);
-    if (gridDim.x > 1) {
-        if (threadIdx.x == 0) kk_store(R, 0, acc);
-        if (!kk_last_arrival(R, &last)) return;
-        if (threadIdx.x == 0) acc = kk_total(R, 0);
-    }
-    if (threadIdx.x == 0) {
-        R.scal[KK_PHP] = acc;
-        if (R.scal[KK_STOP] == 0.0) {
-            if (!(acc > 0.0)) R.scal[KK_STOP] = 2.0;
-            else R.scal[KK_ALPHA] = R.scal[KK_RG] / acc;
-        }
-    }
-}
-// d += alpha p, r += alpha hp; nothing after a stop
-__global__ __launch_bounds__(256) void k_kkt_cg_step(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ p, const double* __restrict__ hp, double* __restrict__ d, double* __restrict__ r, int64_t len) {
-    ASM_BARGS(abt, scal, p, hp, d, r, len);
-    const int64_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= len || scal[KK_STOP] != 0.0) return;
-    const double alpha = scal[KK_ALPHA];
-    d[j] += alpha * p[j];
-    r[j] += alpha * hp[j];
-}
-// g = P r has been formed (the residual is kept projected: the caller passes r = g): r'g and g'g; beta = r'g / (the previous r'g); the
-// convergence test ||g|| <= rtol ||g0||.  init: the first projected residual - its norm is the reference of the test, beta = 0, and
-// g0 = 0 stops at once.  The block goes to the host (pub != 0).
-__global__ __launch_bounds__(256) void k_kkt_cg_dir(AsmBt abt, KktRed R, const double* r, const double* g, int64_t len, int init, double rtol, unsigned pub) {
-    ASM_BARGS(abt, R, r, g, len, init, rtol, pub);
-    __shared__ double sh[4];
-    __shared__ bool last;
-    double rg = 0.0, gg = 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256) {
-        const double gj = g[j];
-        rg += r[j] * gj;
-        gg += gj * gj;
-    }
-    rg = blk_reduce_sum(rg, sh);
-    gg = blk_reduce_sum(gg, sh);
-    if (gridDim.x > 1) {
-        if (threadIdx.x == 0) { kk_store(R, 0, rg); kk_store(R, 1, gg); }
-        if (!kk_last_arrival(R, &last)) return;
-        if (threadIdx.x == 0) { rg = kk_total(R, 0); gg = kk_total(R, 1); }
-    }
-    if (threadIdx.x == 0) {
-        if (init) {
-            R.scal[KK_RG] = rg; R.scal[KK_GG] = gg; R.scal[KK_R0] = sqrt(gg); R.scal[KK_BETA] = 0.0; R.scal[KK_ALPHA] = 0.0; R.scal[KK_PHP] = 0.0;
-            R.scal[KK_STOP] = gg == 0.0 ? 1.0 : 0.0;
-        } else if (R.scal[KK_STOP] == 0.0) {
-            R.scal[KK_BETA] = rg / R.scal[KK_RG];
-            R.scal[KK_RG] = rg; R.scal[KK_GG] = gg;
-            if (sqrt(gg) <= rtol * R.scal[KK_R0]) R.scal[KK_STOP] = 1.0;
-        }
-    }
-    kk_publish(R, pub);
-}
-// the bound multipliers and the residuals of the returned solution, one workgroup:
-//   dz[j] = (H dx)[j] + ru[j] - (J' dlam)[j] on B, 0 on F;   res_stat = max over F of |(H dx)[j] + ru[j] - (J' dlam)[j]|;
-//   res_feas = max over the working rows of |(A dx)[q] + rw[q]|
-__global__ __launch_bounds__(1024) void k_kkt_finish(AsmBt abt, KktRed R, const double* __restrict__ hdx, const double* __restrict__ ru, const double* __restrict__ jtl, const double* __restrict__ mask, int64_t n, const double* __restrict__ adx, const double* __restrict__ rww, int64_t nW, double* __restrict__ dz) {
-    ASM_BARGS(abt, R, hdx, ru, jtl, mask, n, adx, rww, nW, dz);
-    __shared__ double sh[16];
-    double rs = 0.0, rf = 0.0;
-    for (int64_t j = threadIdx.x; j < n; j += 1024) {
-        const double v = (hdx[j] + ru[j]) - jtl[j];
-        const bool fr = mask[j] != 0.0;
-        dz[j] = fr ? 0.0 : v;
-        if (fr) rs = fmax(rs, fabs(v));
-    }
-    for (int64_t q = threadIdx.x; q < nW; q += 1024) rf = fmax(rf, fabs(adx[q] + rww[q]));
-    rs = blk_reduce_max(rs, sh);
-    rf = blk_reduce_max(rf, sh);
-    if (threadIdx.x == 0) { R.scal[KK_RSTAT] = rs; R.scal[KK_RFEAS] = rf; }
-}
 
-// ------------------------------------------------------------------------------------------------------------------------------------
-// Many right-hand sides per solve (asm_kkt_solve_multi; include/asm_hip.h, "Many right-hand sides on one factor").  The columns of a
-// chunk are the rows of row-major blocks: KKM_CW rows of pitch ldv over the variables, of pitch ldr over the working rows.  Products
-// with A and A' and the substitutions are k_gemm_nt launches (Dev::gemm_nt, Dev::trsm_rows); the kernels here are the rest.  Each has
-// the column in blockIdx.y and does for it what its single-column form does: K independent iterations that advance together.  A
-// column whose stop code is set is frozen - no kernel writes its d, r or p again.  Every sum of a column runs in an order fixed by the
-// vector length alone, so a column's bits depend neither on the number of columns nor on its place among them.
+// The column state.  KKM_CW columns per chunk at the most; per column KKM_SCAL doubles: the KK_* slots and its iteration count.
 #define KKM_CW 64          // columns per chunk (= ASM_KKT_CHUNK)
 #define KKM_SCAL 16        // doubles per column's scalar block: the KK_* slots, then
 enum { KKM_ITERS = KK_COUNT };      // ... the iterations the column has completed
@@ -190,7 +72,7 @@ struct KktMulti {
     unsigned* hseq;      // its sequence word
 };
 __device__ __forceinline__ KktRed kkm_col(const KktMulti& M, int c) {
-    return KktRed{M.part + (int64_t)c * KK_MAXWG * KK_SLOTS, M.cnt + c, M.scal + (int64_t)c * KKM_SCAL, nullptr, nullptr};
+    return KktRed{M.part + (int64_t)c * KK_MAXWG * KK_SLOTS, M.cnt + c, M.scal + (int64_t)c * KKM_SCAL};
 }
 
 // AT[j, q] = J[wrow[q], j] for q < nW (mask != nullptr: 0 where mask[j] == 0), 0 for nW <= q < nWp: the working rows transposed into an
@@ -371,7 +253,9 @@ __global__ __launch_bounds__(256) void k_kktm_cg_dir(AsmBt abt, KktMulti M, cons
         }
     }
 }
-// the bound multipliers and the residuals of every column, one workgroup each (k_kkt_finish with the column in blockIdx.x)
+// the bound multipliers and the residuals of every column, one workgroup each (the column in blockIdx.x):
+//   dz[j] = (H dx)[j] + ru[j] - (J' dlam)[j] on B, 0 on F;   res_stat = max over F of |(H dx)[j] + ru[j] - (J' dlam)[j]|;
+//   res_feas = max over the working rows of |(A dx)[q] + rw[q]|
 __global__ __launch_bounds__(1024) void k_kktm_finish(AsmBt abt, double* __restrict__ scal, const double* __restrict__ hdx, const double* __restrict__ ru, const double* __restrict__ jtl, const double* __restrict__ mask, int64_t n, int64_t ldv, const double* __restrict__ adx, const double* __restrict__ rww, int64_t nW, int64_t ldr, double* __restrict__ dz) {
     ASM_BARGS(abt, scal, hdx, ru, jtl, mask, n, ldv, adx, rww, nW, ldr, dz);
     __shared__ double sh[16];

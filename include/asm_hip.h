@@ -387,6 +387,10 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  * Per column the mathematics is the method above, step by step.  Steps 1 and 2 - the Hessian values, the Jacobian, the gather, its
  * transposed copy, the rank-K build, the factorisation and the dropped-pivot count - run once per call.  Steps 3 to 6 run on blocks of
  * ASM_KKT_CHUNK columns; the factor and everything of steps 1 and 2 stay across the chunks, so memory is bounded whatever nrhs.
+ *   One method, two product back ends: the set-up of steps 1 and 2, the driver of steps 3 to 6 and the element-wise and reduction kernels
+ *   are the same code for asm_kkt_solve and for the multi entries - asm_kkt_solve is that driver on blocks of one column.  Only the
+ *   products with H, A and A' and the substitutions with S differ: asm_kkt_solve and asm_solution_sensitivity use matrix-vector kernels
+ *   and the factor's own substitution, the multi entries the block forms below.  The entry point chooses, never nrhs.
  *   Layout: a block holds its columns as rows, pitch ldn over the variables and round_up(min(m, n), 32) over the working rows.  The
  *   products with A and A' are k_gemm_nt launches on the matrix cores (T = V Aw', V = Y AwT'), the substitutions Dev::trsm_rows with the
  *   factor's wide-block inverses and its transposed copy.  Systems of every order take this path: the one-workgroup small solve serves one
@@ -402,10 +406,11 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  *   Column independence: a column's outputs depend on its own right-hand side and the handle's data only - not on nrhs, not on its place,
  *   not on the other columns - bit for bit.  Every nrhs >= 1 takes the same kernels, every sum runs in an order fixed by the matrix
  *   dimensions, and the rows of a block beyond the chunk's columns are never part of a launch.  Against asm_kkt_solve the agreement is to
- *   tolerance: the summation orders differ.
+ *   tolerance: the summation orders of the two back ends' products differ.
  * asm_solution_sensitivity_multi makes (u, w) of each direction with the cross-derivative sweep of asm_eval_data_cross - one launch set per
  * direction, written straight into the chunk's blocks, no synchronisation between directions - and then runs the same solve.
- * The buffers are made at the first multi call and released with asm_kkt_solve's; asm_kkt_solve itself is not affected.
+ * The buffers are made at the first multi call and released with asm_kkt_solve's; a handle that calls asm_kkt_solve alone holds blocks
+ * of one column.
  * When to use it: a lockstep round launches block products whose time does not shrink with the number of columns, live or frozen - on
  * the case300-sized ACOPF a round costs about seven single-column iterations.  Below about 8 columns a loop of asm_kkt_solve /
  * asm_solution_sensitivity calls is faster; from there on the multi entries win, 4.5 times at 32 columns and 12.7 times at 64.
