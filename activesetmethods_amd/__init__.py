@@ -7,7 +7,7 @@ from .parameters import Parameters, get_parameter, set_parameter
 from .status import ApplicationReturnStatus
 from .subproblem import QpData, HipSubOptimizer, AsmHipError
 from .slp import Model, SlpLS, SlpTR, optimize
-from . import problems, nlexpr, sensitivity
+from . import problems, nlexpr, sensitivity, eqp
 
 __all__ = ["Parameters", "get_parameter", "set_parameter", "ApplicationReturnStatus", "QpData", "HipSubOptimizer",
-           "AsmHipError", "Model", "SlpLS", "SlpTR", "optimize", "problems", "sensitivity"]
+           "AsmHipError", "Model", "SlpLS", "SlpTR", "optimize", "problems", "sensitivity", "eqp"]

@@ -80,6 +80,19 @@ class KktInfo(C.Structure):
                 ("res_stat", C.c_double), ("res_feas", C.c_double)]
 
 
+class KktStepParams(C.Structure):
+    """asm_kkt_step_params."""
+    _fields_ = [("max_iter", C.c_int32), ("rtol", C.c_double), ("normal_share", C.c_double)]
+
+
+class KktStepInfo(C.Structure):
+    """asm_kkt_step_info: asm_kkt_info's fields; boundary 0 inside the region, 1 reached on positive curvature, 2 reached along
+    p'Hp <= 0; theta, the norms of the normal step and of the step, the model value."""
+    _fields_ = [("status", C.c_int32), ("cg_iters", C.c_int32), ("n_free", C.c_int32), ("n_rows", C.c_int32), ("dropped_pivots", C.c_int32),
+                ("boundary", C.c_int32), ("res_stat", C.c_double), ("res_feas", C.c_double), ("theta", C.c_double),
+                ("norm_normal", C.c_double), ("norm_step", C.c_double), ("model", C.c_double)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
@@ -117,6 +130,8 @@ PROTOTYPES = {
     "asm_solution_sensitivity": (C.c_int, [_P, _D, _D, _I32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_kkt_solve_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_solution_sensitivity_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_kkt_step": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.c_double, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
+    "asm_kkt_step_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
     "asm_eval_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
     "asm_eval_hessian_lagrangian": (C.c_int, [_P, _D, C.c_double, _D, _D]),
     "asm_eval_hessian_product": (C.c_int, [_P, _D, C.c_double, _D, _D, _D]),

@@ -243,6 +243,7 @@ struct FacBuf {
 struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` columns (0: not made): 1 for asm_kkt_solve, KKM_CW for the multi entries
     int64_t cap = 0;
     double *vec = nullptr, *row = nullptr, *dlf = nullptr;      // 14 blocks cap x ldn over the variables, 5 cap x ldT over the working rows, cap x Mp over all rows
+    double* rad = nullptr;                                      // cap trust-region radii (asm_kkt_step)
     double* stage = nullptr;                                    // pinned: [ru | rw | directions] of a chunk, then its results
     double *Lt = nullptr, *AfT = nullptr;                       // cap > 1, the block products' own operands: the transposed factor, the unmasked transposed working rows
 };
@@ -4448,6 +4449,7 @@ KktWork* kk_work(asm_handle* h, int64_t cap) {
     M.zeroed(W.vec, 14 * cap * ldn, s);
     M.zeroed(W.row, 5 * cap * K.ldT, s);
     M.zeroed(W.dlf, cap * Mp, s);
+    M.zeroed(W.rad, cap, s);
     if (cap > 1) {
         M.zeroed(W.Lt, K.fac.ld * K.fac.ld, s);
         M.zeroed(W.AfT, ldn * K.ldT, s);
@@ -4651,8 +4653,16 @@ struct KktBlock final : KktOps {
 // otherwise the rows of DC are directions of the data and the cross-derivative sweep makes each column's right-hand sides on the
 // device (lambda: its multipliers).  The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product and substitution is ops'.
 // rounds, last_active: the lockstep rounds of the call and the last active-column word read.
+// The trust-region step (asm_kkt_step, asm_kkt_step_multi): tr.radius != nullptr holds a radius per column, and the answers go to tr.info
+// instead of info.  The same launches with the trust-region forms of k_kktm_cg_curv, k_kktm_cg_dir and k_kktm_finish, and k_kktm_normal
+// once per chunk after the normal step.
+struct KktTrust {
+    const double* radius = nullptr;      // nrhs radii, each > 0 (+inf: no region)
+    double share = 0.8;                  // the share of the radius the normal step may use
+    asm_kkt_step_info* info = nullptr;
+};
 void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, const double* RU, const double* RW, const double* DC, bool sens, const double* lambda, double* DX,
-                 double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active) {
+                 double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active, const KktTrust& tr = KktTrust()) {
     const KktBufs& K = h->kk;
     KktWork& w = ops.w;
     const hipStream_t s = h->stream;
@@ -4677,7 +4687,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     }
     const dim3 gl = asmb::blocks(ldn);
     const unsigned gred = (unsigned)std::min<int64_t>(gl.x, KK_MAXWG);
-    const bool run_cg = f.nF > nW;
+    const bool run_cg = f.nF > nW, trust = tr.radius != nullptr;
     int dropped = 0;
     rounds = 0;
     last_active = 0;
@@ -4712,6 +4722,11 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             }
             HIPCHK(asmb::copy_async(b_ru, st, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
             HIPCHK(asmb::copy_async(rww, st + cap * ldn, (int64_t)cols * ldT * sizeof(double), hipMemcpyHostToDevice, s));
+            if (trust) {      // (the staging rows of the directions are free: no sensitivity entry has a radius)
+                double* hr = st + cap * (ldn + ldT);
+                std::memcpy(hr, tr.radius + c0, cols * sizeof(double));
+                HIPCHK(asmb::copy_async(w.rad, hr, cols * sizeof(double), hipMemcpyHostToDevice, s));
+            }
         } else if (cross) {
             // one sweep per direction, no synchronisation between them: every direction has its own staging row
             const ExprTape& X = h->ev_X;
@@ -4740,6 +4755,8 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
         } else {
             HIPCHK(asmb::fill_async(dx0, 0, cap * ldn * sizeof(double), s));
         }
+        // the share of the normal step that the radius admits: theta, dx0 <- theta dx0, Dt^2
+        if (trust) asmb::launch(k_kktm_normal, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)w.rad, tr.share, dx0, ldn, ldn);
         // 4. projected conjugate gradients on null(A), the columns in lockstep: minimise 1/2 d'H_FF d + (ru_F + H_FF dx0)'d
         HIPCHK(asmb::fill_async(cd, 0, cap * ldn * sizeof(double), s));
         if (run_cg) {
@@ -4750,17 +4767,18 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             project(cr, nullptr);
             project(cr, nullptr);
             unsigned pub = pub_next(h);
-            asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 1, f.rtol, pub);
+            asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 1, f.rtol, pub, (int)trust);
             int active = kk_read_scal(h, pub);
             for (int64_t it = 0; active > 0 && it < f.max_iter; ++it) {
                 asmb::launch(k_kktm_cg_p, glc, dim3(256), s, (const double*)scal, (const double*)cr, cp, ldn, ldn);
                 ops.hess(cp, hraw, cols);
-                asmb::launch(k_kktm_cg_curv, gredc, dim3(256), s, R, (const double*)cp, (const double*)hraw, mask, hp, ldn, ldn);
+                if (trust) asmb::launch(k_kktm_cg_curv<true>, gredc, dim3(256), s, R, (const double*)cp, (const double*)hraw, mask, (const double*)cd, hp, ldn, ldn);
+                else asmb::launch(k_kktm_cg_curv<false>, gredc, dim3(256), s, R, (const double*)cp, (const double*)hraw, mask, (const double*)cd, hp, ldn, ldn);
                 asmb::launch(k_kktm_cg_step, glc, dim3(256), s, (const double*)scal, (const double*)cp, (const double*)hp, cd, cr, ldn, ldn);
                 project(cr, scal);
                 project(cr, scal);
                 pub = pub_next(h);
-                asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 0, f.rtol, pub);
+                asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 0, f.rtol, pub, (int)trust);
                 active = kk_read_scal(h, pub);
                 rounds += 1;
             }
@@ -4786,7 +4804,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             HIPCHK(asmb::fill_async(jtl, 0, cap * ldn * sizeof(double), s));
         }
         asmb::launch(k_kktm_finish, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)hdx, (const double*)b_ru, (const double*)jtl, mask, n, ldn, (const double*)adx,
-                     (const double*)rww, nW, ldT, ddz);
+                     (const double*)rww, nW, ldT, ddz, trust ? (const double*)ddx : (const double*)nullptr);
         HIPCHK(asmb::copy_async(back, ddx, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(asmb::copy_async(back + cap * ldn, ddz, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
         if (m > 0) HIPCHK(asmb::copy_async(back + 2 * cap * ldn, dlf, (int64_t)cols * Mp * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -4799,12 +4817,21 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             if (DZ) std::memcpy(DZ + (c0 + c) * n, back + cap * ldn + (int64_t)c * ldn, n * sizeof(double));
             if (m > 0) std::memcpy(DLAM + (c0 + c) * m, back + 2 * cap * ldn + (int64_t)c * Mp, m * sizeof(double));
             const double* sc = back + cap * (2 * ldn + Mp) + (int64_t)c * KKM_SCAL;
-            asm_kkt_info& o = info[c0 + c];
             // (without an iteration - a vertex - the column's stop code and count are not written: solved, no iteration)
             const int stop = run_cg ? (int)sc[KK_STOP] : 1;
-            o.status = dropped > 0 ? 3 : (stop == 2 ? 2 : (stop == 0 ? 1 : 0));
-            o.cg_iters = run_cg ? (int32_t)sc[KKM_ITERS] : 0; o.n_free = (int32_t)f.nF; o.n_rows = (int32_t)nW; o.dropped_pivots = dropped;
-            o.res_stat = sc[KK_RSTAT]; o.res_feas = sc[KK_RFEAS];
+            auto shared_fields = [&](auto& o) {
+                o.status = dropped > 0 ? 3 : (stop == 2 ? 2 : (stop == 0 ? 1 : 0));
+                o.cg_iters = run_cg ? (int32_t)sc[KKM_ITERS] : 0; o.n_free = (int32_t)f.nF; o.n_rows = (int32_t)nW; o.dropped_pivots = dropped;
+                o.res_stat = sc[KK_RSTAT]; o.res_feas = sc[KK_RFEAS];
+            };
+            if (trust) {
+                asm_kkt_step_info& o = tr.info[c0 + c];
+                shared_fields(o);
+                o.boundary = run_cg ? (int32_t)sc[KKM_BND] : 0;
+                o.theta = sc[KKM_THETA]; o.norm_normal = sc[KKM_NNORM]; o.norm_step = sc[KKM_NSTEP]; o.model = sc[KKM_MODEL];
+            } else {
+                shared_fields(info[c0 + c]);
+            }
         }
     }
     ops.dev.resolve_timing();
@@ -4846,6 +4873,37 @@ static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, 
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par);
     KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
     kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->kkm_rounds, h->kkm_last_active);
+}
+// asm_kkt_step (one column through KktOneColumn) and asm_kkt_step_multi (KktBlock): the checks of asm_kkt_solve(_multi), then
+// those of the radii and the share
+static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                        const double* RU, const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX, double* DLAM, double* DZ,
+                        asm_kkt_step_info* info) {
+    const std::string me(who);
+    hs_check(h, who);
+    if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
+    if (!x || !bound_state || !RU || !RADIUS || !DX || !info || (h->m > 0 && (!lambda || !row_state || !RW || !DLAM))) throw std::invalid_argument(me + ": null pointer");
+    for (int32_t c = 0; c < nrhs; ++c)
+        if (!(RADIUS[c] > 0.0)) throw std::invalid_argument(me + ": a radius is not > 0");
+    KktTrust tr;
+    tr.radius = RADIUS;
+    tr.info = info;
+    if (par) {
+        if (!(par->normal_share > 0.0 && par->normal_share <= 1.0)) throw std::invalid_argument(me + ": normal_share outside (0, 1]");
+        tr.share = par->normal_share;
+    }
+    const asm_kkt_params kp{par ? par->max_iter : 0, par ? par->rtol : 0.0};
+    Dev dev(h);
+    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par ? &kp : nullptr);
+    if (multi) {
+        KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
+        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, h->kkm_rounds, h->kkm_last_active, tr);
+    } else {
+        KktOneColumn ops(h, dev, f, *kk_work(h, 1));
+        int64_t rounds;
+        int last_active;
+        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, rounds, last_active, tr);
+    }
 }
 
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
@@ -4909,6 +4967,18 @@ int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double*
                                    const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
     return guarded(h, [&] {
         do_kkt_solve_multi(h, "asm_solution_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, true, par, DX, DLAM, DZ, info);
+    });
+}
+
+int asm_kkt_step(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru, const double* rw,
+                 double radius, const asm_kkt_step_params* par, double* dx, double* dlam, double* dz, asm_kkt_step_info* info) {
+    return guarded(h, [&] { do_kkt_step(h, "asm_kkt_step", false, x, lambda, row_state, bound_state, 1, ru, rw, &radius, par, dx, dlam, dz, info); });
+}
+
+int asm_kkt_step_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* RU,
+                       const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_step_info* info) {
+    return guarded(h, [&] {
+        do_kkt_step(h, "asm_kkt_step_multi", true, x, lambda, row_state, bound_state, nrhs, RU, RW, RADIUS, par, DX, DLAM, DZ, info);
     });
 }
 

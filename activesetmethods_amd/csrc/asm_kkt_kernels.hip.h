@@ -1,5 +1,5 @@
-// Kernels of the KKT solve on a working set (asm_kkt_solve and the multi entries; include/asm_hip.h, "The KKT solve on a working set" and
-// "Many right-hand sides on one factor"): the gathers of the working rows into dense operands, masked block updates, and the fused
+// Kernels of the KKT solve on a working set (asm_kkt_solve, the multi entries and the trust-region step asm_kkt_step; include/asm_hip.h,
+// "The KKT solve on a working set", "Many right-hand sides on one factor" and "Trust-region step on the working set"): the gathers of the working rows into dense operands, masked block updates, and the fused
 // updates of the projected conjugate-gradient iteration.  One family serves every entry: the right-hand sides of a chunk are the rows
 // of row-major blocks - up to KKM_CW rows of pitch ldv over the variables, of pitch ldr over the working rows - and every kernel has the
 // column in blockIdx.y; asm_kkt_solve launches them with one column.  The columns are independent iterations that advance together.  A
@@ -19,10 +19,11 @@
 #include <stdint.h>
 #include "asm_bt.hip.h"
 
-// the scalar block.  KK_STOP: 0 go on, 1 converged, 2 curvature p'Hp <= 0 (the iterate stays where it is)
+// the scalar block.  KK_STOP: 0 go on, 1 converged (or stopped on the trust-region boundary), 2 curvature p'Hp <= 0 (the iterate stays
+// where it is)
 enum { KK_RG = 0, KK_PHP, KK_ALPHA, KK_BETA, KK_GG, KK_R0, KK_STOP, KK_RSTAT, KK_RFEAS, KK_COUNT };
 #define KK_MAXWG 64
-#define KK_SLOTS 2
+#define KK_SLOTS 4         // partial sums per workgroup: p'Hp (g'g in k_kktm_cg_dir), then d'd, d'p, p'p of the trust-region step
 struct KktRed {
     double* part;        // KK_MAXWG x KK_SLOTS partial sums
     unsigned* cnt;       // arrival counter, 0 between launches
@@ -62,7 +63,9 @@ __global__ __launch_bounds__(256) void k_kkt_gather(AsmBt abt, const double* __r
 // The column state.  KKM_CW columns per chunk at the most; per column KKM_SCAL doubles: the KK_* slots and its iteration count.
 #define KKM_CW 64          // columns per chunk (= ASM_KKT_CHUNK)
 #define KKM_SCAL 16        // doubles per column's scalar block: the KK_* slots, then
-enum { KKM_ITERS = KK_COUNT };      // ... the iterations the column has completed
+// ... the iterations the column has completed and, for the trust-region step (asm_kkt_step) alone: theta, Dt^2 = radius^2 - ||theta dx0||^2,
+// the boundary code (0 inside, 1 boundary on positive curvature, 2 boundary along p'Hp <= 0), ||theta dx0||, the model value and ||dx||
+enum { KKM_ITERS = KK_COUNT, KKM_THETA, KKM_DT2, KKM_BND, KKM_NNORM, KKM_MODEL, KKM_NSTEP };
 struct KktMulti {
     double* part;        // KKM_CW x KK_MAXWG x KK_SLOTS partial sums
     unsigned* cnt;       // KKM_CW arrival counters of the columns' workgroups, then [KKM_CW] the counter of finished columns; 0 between launches
@@ -151,33 +154,99 @@ __global__ __launch_bounds__(256) void k_kktm_cg_p(AsmBt abt, const double* __re
     const double beta = sc[KK_BETA];
     p[c * ldv + j] = beta * p[c * ldv + j] - g[c * ldv + j];
 }
-// per active column: hp = (H p) on F; p'Hp; alpha = r'g / p'Hp, or the curvature stop
-__global__ __launch_bounds__(256) void k_kktm_cg_curv(AsmBt abt, KktMulti M, const double* __restrict__ p, const double* __restrict__ hp_raw, const double* __restrict__ mask, double* __restrict__ hp, int64_t len, int64_t ldv) {
-    ASM_BARGS(abt, M, p, hp_raw, mask, hp, len, ldv);
+// The normal step of the trust-region columns, one workgroup each (the column in blockIdx.x): nn = ||dx0||_2; where nn > share * radius
+// the column's dx0 is scaled by theta = share * radius / nn, theta = 1 elsewhere (dx0 is then not written); Dt^2 = radius^2 - (theta nn)^2,
+// not below 0; the boundary code starts at 0.  An infinite radius gives theta = 1 and Dt^2 = +inf.
+__global__ __launch_bounds__(1024) void k_kktm_normal(AsmBt abt, double* __restrict__ scal, const double* __restrict__ radius, double share, double* __restrict__ dx0, int64_t len, int64_t ldv) {
+    ASM_BARGS(abt, scal, radius, share, dx0, len, ldv);
+    __shared__ double sh[16];
+    const int64_t c = blockIdx.x;
+    double s2 = 0.0;
+    for (int64_t j = threadIdx.x; j < len; j += 1024) {
+        const double v = dx0[c * ldv + j];
+        s2 += v * v;
+    }
+    s2 = blk_reduce_sum(s2, sh);
+    const double nn = sqrt(s2), rad = radius[c], cap = share * rad;
+    const double theta = nn > cap ? cap / nn : 1.0;
+    if (theta != 1.0)
+        for (int64_t j = threadIdx.x; j < len; j += 1024) dx0[c * ldv + j] *= theta;
+    if (threadIdx.x == 0) {
+        double* sc = scal + c * KKM_SCAL;
+        const double tn = theta * nn;
+        sc[KKM_THETA] = theta;
+        sc[KKM_NNORM] = tn;
+        sc[KKM_DT2] = fmax(rad * rad - tn * tn, 0.0);
+        sc[KKM_BND] = 0.0;
+    }
+}
+// per active column: hp = (H p) on F; p'Hp; alpha = r'g / p'Hp, or the curvature stop.
+// TR (asm_kkt_step): the same pass also sums d'd, d'p and p'p (partial-sum slots 1 to 3, added in workgroup order as slot 0 is), and the
+// thread that has the totals applies the Steihaug-Toint rule: with gap = Dt^2 - d'd and tau = gap / (d'p + sqrt((d'p)^2 + p'p gap)) (0
+// when gap <= 0), a finite Dt^2 and p'Hp <= 0 give alpha = tau and boundary code 2; p'Hp > 0 and d'd + 2 alpha d'p + alpha^2 p'p >= Dt^2
+// give alpha = tau and boundary code 1.  Such a column takes this alpha in the round's k_kktm_cg_step and is frozen by its k_kktm_cg_dir.
+template <bool TR>
+__global__ __launch_bounds__(256) void k_kktm_cg_curv(AsmBt abt, KktMulti M, const double* __restrict__ p, const double* __restrict__ hp_raw, const double* __restrict__ mask, const double* __restrict__ d, double* __restrict__ hp, int64_t len, int64_t ldv) {
+    ASM_BARGS(abt, M, p, hp_raw, mask, d, hp, len, ldv);
     __shared__ double sh[4];
     __shared__ bool last;
     const int64_t c = blockIdx.y;
     const KktRed R = kkm_col(M, (int)c);
     if (R.scal[KK_STOP] != 0.0) return;          // (set by an earlier launch: the same in every workgroup of the column)
-    double acc = 0.0;
+    double acc = 0.0, dd = 0.0, dp = 0.0, pp = 0.0;
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256) {
         const double v = mask[j] != 0.0 ? hp_raw[c * ldv + j] : 0.0;
         hp[c * ldv + j] = v;
-        acc += p[c * ldv + j] * v;
+        const double pj = p[c * ldv + j];
+        acc += pj * v;
+        if (TR) {
+            const double dj = d[c * ldv + j];
+            dd += dj * dj;
+            dp += dj * pj;
+            pp += pj * pj;
+        }
     }
     acc = blk_reduce_sum(acc, sh);
+    if (TR) {
+        dd = blk_reduce_sum(dd, sh);
+        dp = blk_reduce_sum(dp, sh);
+        pp = blk_reduce_sum(pp, sh);
+    }
     if (gridDim.x > 1) {
-        if (threadIdx.x == 0) kk_store(R, 0, acc);
+        if (threadIdx.x == 0) {
+            kk_store(R, 0, acc);
+            if (TR) { kk_store(R, 1, dd); kk_store(R, 2, dp); kk_store(R, 3, pp); }
+        }
         if (!kk_last_arrival(R, &last)) return;
-        if (threadIdx.x == 0) acc = kk_total(R, 0);
+        if (threadIdx.x == 0) {
+            acc = kk_total(R, 0);
+            if (TR) { dd = kk_total(R, 1); dp = kk_total(R, 2); pp = kk_total(R, 3); }
+        }
     }
     if (threadIdx.x == 0) {
         R.scal[KK_PHP] = acc;
-        if (!(acc > 0.0)) {      // the curvature stop: the column leaves the active count that the round's k_kktm_cg_dir adds up
-            R.scal[KK_STOP] = 2.0;
-            __hip_atomic_store(M.active + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double dt2 = TR ? R.scal[KKM_DT2] : INFINITY;
+        double tau = 0.0;
+        if (TR) {
+            const double gap = dt2 - dd;
+            if (gap > 0.0 && gap < INFINITY) tau = gap / (dp + sqrt(dp * dp + pp * gap));
+        }
+        if (!(acc > 0.0)) {
+            if (dt2 < INFINITY) {      // along the direction of non-positive curvature to the boundary
+                R.scal[KK_ALPHA] = tau;
+                R.scal[KKM_BND] = 2.0;
+            } else {                   // the curvature stop: the column leaves the active count that the round's k_kktm_cg_dir adds up
+                R.scal[KK_STOP] = 2.0;
+                __hip_atomic_store(M.active + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         } else {
-            R.scal[KK_ALPHA] = R.scal[KK_RG] / acc;
+            const double alpha = R.scal[KK_RG] / acc;
+            if (TR && dd + 2.0 * alpha * dp + alpha * alpha * pp >= dt2) {
+                R.scal[KK_ALPHA] = tau;
+                R.scal[KKM_BND] = 1.0;
+            } else {
+                R.scal[KK_ALPHA] = alpha;
+            }
         }
     }
 }
@@ -195,8 +264,10 @@ __global__ __launch_bounds__(256) void k_kktm_cg_step(AsmBt abt, const double* _
 // per active column, with the projected residual r = g in place: r'g and g'g, beta, the convergence test against the column's own
 // ||g0|| and its iteration count (init: the reference norm, beta = 0, g0 = 0 stops at once).  The workgroup that finishes a column
 // counts the column in; the one that finishes the last column counts the columns still active and hands that word to the host.
-__global__ __launch_bounds__(256) void k_kktm_cg_dir(AsmBt abt, KktMulti M, const double* __restrict__ r, int64_t len, int64_t ldv, int init, double rtol, unsigned pub) {
-    ASM_BARGS(abt, M, r, len, ldv, init, rtol, pub);
+// tr != 0 (asm_kkt_step): a column whose k_kktm_cg_curv of this round set a boundary code has taken its last step and stops here; the
+// boundary move counts as a completed iteration.
+__global__ __launch_bounds__(256) void k_kktm_cg_dir(AsmBt abt, KktMulti M, const double* __restrict__ r, int64_t len, int64_t ldv, int init, double rtol, unsigned pub, int tr) {
+    ASM_BARGS(abt, M, r, len, ldv, init, rtol, pub, tr);
     __shared__ double sh[4];
     __shared__ bool last, lastcol;
     const int64_t c = blockIdx.y;
@@ -225,7 +296,7 @@ __global__ __launch_bounds__(256) void k_kktm_cg_dir(AsmBt abt, KktMulti M, cons
                 R.scal[KK_BETA] = gg / R.scal[KK_RG];
                 R.scal[KK_RG] = gg; R.scal[KK_GG] = gg;
                 R.scal[KKM_ITERS] += 1.0;
-                stop = sqrt(gg) <= rtol * R.scal[KK_R0] ? 1.0 : 0.0;
+                stop = sqrt(gg) <= rtol * R.scal[KK_R0] || (tr && R.scal[KKM_BND] != 0.0) ? 1.0 : 0.0;
             }
             R.scal[KK_STOP] = stop;
             __hip_atomic_store(M.active + c, stop == 0.0 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -256,20 +327,37 @@ __global__ __launch_bounds__(256) void k_kktm_cg_dir(AsmBt abt, KktMulti M, cons
 // the bound multipliers and the residuals of every column, one workgroup each (the column in blockIdx.x):
 //   dz[j] = (H dx)[j] + ru[j] - (J' dlam)[j] on B, 0 on F;   res_stat = max over F of |(H dx)[j] + ru[j] - (J' dlam)[j]|;
 //   res_feas = max over the working rows of |(A dx)[q] + rw[q]|
-__global__ __launch_bounds__(1024) void k_kktm_finish(AsmBt abt, double* __restrict__ scal, const double* __restrict__ hdx, const double* __restrict__ ru, const double* __restrict__ jtl, const double* __restrict__ mask, int64_t n, int64_t ldv, const double* __restrict__ adx, const double* __restrict__ rww, int64_t nW, int64_t ldr, double* __restrict__ dz) {
-    ASM_BARGS(abt, scal, hdx, ru, jtl, mask, n, ldv, adx, rww, nW, ldr, dz);
+// dx != nullptr (asm_kkt_step): rw is theta rw, and the column's model value ru'dx + 1/2 dx'(H dx) and ||dx||_2 join its scalars
+__global__ __launch_bounds__(1024) void k_kktm_finish(AsmBt abt, double* __restrict__ scal, const double* __restrict__ hdx, const double* __restrict__ ru, const double* __restrict__ jtl, const double* __restrict__ mask, int64_t n, int64_t ldv, const double* __restrict__ adx, const double* __restrict__ rww, int64_t nW, int64_t ldr, double* __restrict__ dz, const double* __restrict__ dx) {
+    ASM_BARGS(abt, scal, hdx, ru, jtl, mask, n, ldv, adx, rww, nW, ldr, dz, dx);
     __shared__ double sh[16];
     const int64_t c = blockIdx.x;
-    double rs = 0.0, rf = 0.0;
+    const double theta = dx ? scal[c * KKM_SCAL + KKM_THETA] : 1.0;
+    double rs = 0.0, rf = 0.0, lin = 0.0, quad = 0.0, sq = 0.0;
     for (int64_t j = threadIdx.x; j < n; j += 1024) {
         const int64_t e = c * ldv + j;
         const double v = (hdx[e] + ru[e]) - jtl[e];
         const bool fr = mask[j] != 0.0;
         dz[e] = fr ? 0.0 : v;
         if (fr) rs = fmax(rs, fabs(v));
+        if (dx) {
+            const double x = dx[e];
+            lin += ru[e] * x;
+            quad += x * hdx[e];
+            sq += x * x;
+        }
     }
-    for (int64_t q = threadIdx.x; q < nW; q += 1024) rf = fmax(rf, fabs(adx[c * ldr + q] + rww[c * ldr + q]));
+    for (int64_t q = threadIdx.x; q < nW; q += 1024) rf = fmax(rf, fabs(adx[c * ldr + q] + theta * rww[c * ldr + q]));
     rs = blk_reduce_max(rs, sh);
     rf = blk_reduce_max(rf, sh);
-    if (threadIdx.x == 0) { scal[c * KKM_SCAL + KK_RSTAT] = rs; scal[c * KKM_SCAL + KK_RFEAS] = rf; }
+    if (dx) {
+        lin = blk_reduce_sum(lin, sh);
+        quad = blk_reduce_sum(quad, sh);
+        sq = blk_reduce_sum(sq, sh);
+    }
+    if (threadIdx.x == 0) {
+        scal[c * KKM_SCAL + KK_RSTAT] = rs;
+        scal[c * KKM_SCAL + KK_RFEAS] = rf;
+        if (dx) { scal[c * KKM_SCAL + KKM_MODEL] = lin + 0.5 * quad; scal[c * KKM_SCAL + KKM_NSTEP] = sqrt(sq); }
+    }
 }

@@ -111,6 +111,20 @@ def _guarded_cholesky(S):
     return L, dropped
 
 
+def _substitute(L, b):
+    """S^-1 b from the lower factor L of S: forward, then backward substitution (b itself without rows)."""
+    nW = len(L)
+    if not nW:
+        return b
+    y = np.zeros(nW)
+    for i in range(nW):
+        y[i] = (b[i] - L[i, :i] @ y[:i]) / L[i, i]
+    z = np.zeros(nW)
+    for i in range(nW - 1, -1, -1):
+        z[i] = (y[i] - L[i + 1:, i] @ z[i + 1:]) / L[i, i]
+    return z
+
+
 def kkt_pcg(fm, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=1e-12):
     """The NumPy twin of asm_kkt_solve, step by step the method of include/asm_hip.h: S = A A' factored with the pivot guard, the
     particular solution dx0 = -A' S^-1 rw_W, projected conjugate gradients on null(A) with the projection applied twice per
@@ -125,17 +139,7 @@ def kkt_pcg(fm, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=1e-1
         max_iter = 2 * (nF - nW) + 20
     L, dropped = _guarded_cholesky(A @ A.T) if nW else (np.zeros((0, 0)), 0)
 
-    def s_solve(b):
-        if not nW:
-            return b
-        y = np.zeros(nW)
-        for i in range(nW):                                # forward, then backward substitution
-            y[i] = (b[i] - L[i, :i] @ y[:i]) / L[i, i]
-        z = np.zeros(nW)
-        for i in range(nW - 1, -1, -1):
-            z[i] = (y[i] - L[i + 1:, i] @ z[i + 1:]) / L[i, i]
-        return z
-
+    s_solve = lambda b: _substitute(L, b)
     proj = lambda v: v - A.T @ s_solve(A @ v) if nW else v.copy()
     dx0 = -(A.T @ s_solve(rw[W])) if nW else np.zeros(nF)
     if nW:

@@ -373,6 +373,41 @@ class HipSubOptimizer:
                                                              par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return DX, DLAM[:, :self.m], DZ, list(infos)
 
+    @staticmethod
+    def _kkt_step_params(max_iter, rtol, normal_share):
+        if max_iter is None and rtol is None and normal_share is None:
+            return None
+        if max_iter is None or rtol is None or normal_share is None:
+            raise ValueError("give max_iter, rtol and normal_share together (asm_kkt_step_params), or none of them for the defaults")
+        return C.byref(_lib.KktStepParams(int(max_iter), float(rtol), float(normal_share)))
+
+    def kkt_step(self, x, lam, row_state, bound_state, ru, rw, radius, max_iter=None, rtol=None, normal_share=None):
+        """(dx, dlam, dz, info) of asm_kkt_step: the trust-region step on the working set - kkt_solve with an l2 radius (+inf: kkt_solve
+        itself); info is the asm_kkt_step_info structure (asm_kkt_info's fields, boundary, theta, norm_normal, norm_step, model)."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        ru, rw = self._vec(ru, self.n, "ru"), self._vec(rw, self.m, "rw")
+        rs, bs = self._states(row_state, bound_state)
+        dx, dlam, dz, info = np.empty(self.n), np.empty(max(self.m, 1)), np.empty(self.n), _lib.KktStepInfo()
+        self._check(self._lib.asm_kkt_step(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), _lib.dptr(ru), _lib.dptr(rw), float(radius),
+                                           self._kkt_step_params(max_iter, rtol, normal_share), _lib.dptr(dx), _lib.dptr(dlam), _lib.dptr(dz), C.byref(info)))
+        return dx, dlam[:self.m], dz, info
+
+    def kkt_step_multi(self, x, lam, row_state, bound_state, RU, RW, radii, max_iter=None, rtol=None, normal_share=None):
+        """(DX, DLAM, DZ, infos) of asm_kkt_step_multi: kkt_step for the nrhs right-hand sides in the rows of RU [nrhs x n] and
+        RW [nrhs x m], each with its own radius (radii [nrhs]), on one factor - equal rows answer a ladder of radii."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_step_params(max_iter, rtol, normal_share)
+        RU = self._mat(RU, self.n, "RU")
+        RW = self._mat(RW, self.m, "RW", RU.shape[0])
+        nrhs = RU.shape[0]
+        radii = self._vec(radii, nrhs, "radii")
+        rs, bs = self._states(row_state, bound_state)
+        DX, DLAM, DZ = self._multi_outputs(nrhs)[:3]
+        infos = (_lib.KktStepInfo * nrhs)()
+        self._check(self._lib.asm_kkt_step_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(RU), _lib.dptr(RW),
+                                                 _lib.dptr(radii), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return DX, DLAM[:, :self.m], DZ, list(infos)
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)

@@ -423,6 +423,53 @@ int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double*
                                    const int32_t* bound_state, int32_t nrhs, const double* DC, const asm_kkt_params* par, double* DX,
                                    double* DLAM, double* DZ, asm_kkt_info* info);
 
+/* ---- Trust-region step on the working set: Byrd-Omojokun with Steihaug-Toint truncation.
+ * asm_kkt_step is asm_kkt_solve with an l2 radius: it minimises the model ru'dx + 1/2 dx'H dx over A dx_F = -theta rw_W, dx_B = 0,
+ * ||dx||_2 <= radius - a normal step that may use only normal_share of the radius, then projected conjugate gradients that walk to the
+ * boundary of the region where they leave it or meet non-positive curvature.  asm_kkt_step_multi does so for nrhs right-hand sides with
+ * a radius each (RADIUS [nrhs]) on one factor, in the lockstep iteration of asm_kkt_solve_multi: with the rows of RU / RW equal it answers
+ * a whole ladder of radii, which is what a trust-region driver needs after a rejected step.
+ * Validity, argument errors, layouts and "not inside a scenario batch" are asm_kkt_solve's and asm_kkt_solve_multi's.  A radius that is not
+ * > 0 (NaN included) and a normal_share outside (0, 1]: ASM_ERR_ARG.  par == NULL: asm_kkt_solve's defaults and normal_share = 0.8.
+ * radius = +INFINITY is allowed and is asm_kkt_solve, bit for bit in dx, dlam, dz and the fields asm_kkt_info has.
+ * Method per column (the steps of asm_kkt_solve; both entries run its driver and its kernels):
+ *   1., 2. unchanged, once per call.
+ *   3. dx0 as in asm_kkt_solve, with its refinement step.  nn = ||dx0||_2.  If nn > normal_share radius: theta = normal_share radius / nn
+ *      and dx0 <- theta dx0; otherwise theta = 1.  Dt^2 = radius^2 - (theta nn)^2 (not below 0): dx0 in range(A') and d in null(A) are
+ *      orthogonal, so ||dx||^2 = ||dx0||^2 + ||d||^2.
+ *   4. the iteration of asm_kkt_solve; the pass that forms p'Hp also forms d'd, d'p and p'p, directly, not by recurrence.  With
+ *      gap = Dt^2 - d'd and tau = gap / (d'p + sqrt((d'p)^2 + p'p gap)) (tau = 0 when gap <= 0), the positive root of ||d + tau p||^2 = Dt^2:
+ *        p'Hp <= 0, radius finite:    d += tau p, boundary = 2, the column stops
+ *        p'Hp <= 0, radius infinite:  as asm_kkt_solve (status 2, the iterate stays)
+ *        p'Hp > 0 and d'd + 2 alpha d'p + alpha^2 p'p >= Dt^2 (alpha = r'g / p'Hp):   d += tau p, boundary = 1, the column stops
+ *        otherwise the iteration is unchanged.
+ *      A column that stops on the boundary takes tau in place of alpha in that round's step kernel and is frozen from then on, as a
+ *      converged column is.  cg_iters counts completed iterations, and the boundary move is one: a column that reaches the boundary in
+ *      its first iteration has cg_iters = 1.
+ *   5., 6. as asm_kkt_solve with rw replaced by theta rw in res_feas; model = ru'dx + 1/2 dx'H dx, norm_normal = theta nn and
+ *      norm_step = ||dx||_2 (summed directly from dx).
+ * status keeps its four meanings; a column that stopped on the boundary has status 0.
+ * Nothing of this visits the host: the radii go to the device with the right-hand sides, theta, Dt^2 and the boundary code live in the
+ * column's scalar block, and the host still reads the one active-column word per round.  A round has the launches it had; one launch
+ * per chunk (k_kktm_normal) scales the normal steps, and the model value and the step norm are sums of the finish launch.  The three
+ * further sums use the rule of the others - per-workgroup partial sums, added in workgroup order by the last workgroup to arrive - so a
+ * column's bits depend on its own right-hand side and radius alone. */
+typedef struct { int32_t max_iter; double rtol; double normal_share; } asm_kkt_step_params;
+typedef struct {
+    int32_t status, cg_iters, n_free, n_rows, dropped_pivots;   /* as asm_kkt_info */
+    int32_t boundary;          /* 0 inside the region, 1 boundary reached on positive curvature, 2 boundary reached along p'Hp <= 0 */
+    double res_stat, res_feas; /* res_feas against theta * rw */
+    double theta;              /* share of the normal step taken: A dx_F = -theta rw_W */
+    double norm_normal, norm_step;   /* ||theta dx0||_2, ||dx||_2 */
+    double model;              /* ru'dx + 1/2 dx'H dx */
+} asm_kkt_step_info;
+int asm_kkt_step(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                 const double* ru, const double* rw, double radius, const asm_kkt_step_params* par, double* dx, double* dlam, double* dz,
+                 asm_kkt_step_info* info);
+int asm_kkt_step_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                       int32_t nrhs, const double* RU, const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX,
+                       double* DLAM, double* DZ, asm_kkt_step_info* info);
+
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
 int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4);
