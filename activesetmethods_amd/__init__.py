@@ -6,8 +6,8 @@ this package is the host-side mirror of the reference's interface for that path.
 from .parameters import Parameters, get_parameter, set_parameter
 from .status import ApplicationReturnStatus
 from .subproblem import QpData, HipSubOptimizer, AsmHipError
-from .slp import Model, SlpLS, SlpTR, optimize
+from .slp import Model, SlpEQP, SlpLS, SlpTR, optimize
 from . import problems, nlexpr, sensitivity, eqp
 
 __all__ = ["Parameters", "get_parameter", "set_parameter", "ApplicationReturnStatus", "QpData", "HipSubOptimizer",
-           "AsmHipError", "Model", "SlpLS", "SlpTR", "optimize", "problems", "sensitivity", "eqp"]
+           "AsmHipError", "Model", "SlpLS", "SlpTR", "SlpEQP", "optimize", "problems", "sensitivity", "eqp"]

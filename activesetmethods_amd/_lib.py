@@ -93,6 +93,26 @@ class KktStepInfo(C.Structure):
                 ("norm_normal", C.c_double), ("norm_step", C.c_double), ("model", C.c_double)]
 
 
+class EqpInfo(C.Structure):
+    """asm_eqp_info: asm_kkt_step_info's fields; skipped 0 none, 1 more working rows than free variables, 2 dependent working rows,
+    3 zero step; t, the norms of d = t dx, the merit function at x and at x + d."""
+    _fields_ = [("status", C.c_int32), ("cg_iters", C.c_int32), ("n_free", C.c_int32), ("n_rows", C.c_int32), ("dropped_pivots", C.c_int32),
+                ("boundary", C.c_int32), ("res_stat", C.c_double), ("res_feas", C.c_double), ("theta", C.c_double),
+                ("norm_normal", C.c_double), ("norm_step", C.c_double), ("model", C.c_double), ("skipped", C.c_int32), ("t", C.c_double),
+                ("norm_d", C.c_double), ("norm_d_inf", C.c_double), ("phi0", C.c_double), ("phi1", C.c_double)]
+
+
+class SlpEqpParams(C.Structure):
+    """asm_slp_eqp_params."""
+    _fields_ = [("radius0", C.c_double), ("radius_max", C.c_double), ("tol_active", C.c_double), ("enabled", C.c_int32)]
+
+
+class SlpEqpInfo(C.Structure):
+    """asm_slp_eqp_info: final radius of the EQP step and the trial counts of a native SLP-EQP run."""
+    _fields_ = [("radius", C.c_double), ("attempts", C.c_int32), ("accepted", C.c_int32), ("rejected", C.c_int32), ("skipped_rows", C.c_int32),
+                ("skipped_dependent", C.c_int32), ("skipped_zero", C.c_int32), ("cg_iters", C.c_int32), ("boundary", C.c_int32)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
@@ -143,6 +163,9 @@ PROTOTYPES = {
     "asm_sublp_set_ns_basis": (C.c_int, [_P, _I32, C.c_int64]),
     "asm_slp_run": (C.c_int, [_P, C.POINTER(SlpParams), _D, _D, _D, _D, _D, _D, C.POINTER(SlpResult)]),
     "asm_slp_run_tr": (C.c_int, [_P, C.POINTER(SlpParams), C.c_double, _D, _D, _D, _D, _D, _D, C.POINTER(SlpResult), C.POINTER(SlpTrInfo)]),
+    "asm_eqp_trial": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_double, _D, C.c_double, C.POINTER(KktStepParams), _D, _D, _D, _D, _I32, _I32, C.POINTER(EqpInfo)]),
+    "asm_slp_run_eqp": (C.c_int, [_P, C.POINTER(SlpParams), C.c_double, C.POINTER(SlpEqpParams), _D, _D, _D, _D, _D, _D, C.POINTER(SlpResult),
+                                  C.POINTER(SlpTrInfo), C.POINTER(SlpEqpInfo)]),
     "asm_batch_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
     "asm_batch_destroy": (C.c_int, [_P]),
     "asm_batch_last_error": (C.c_char_p, [_P]),

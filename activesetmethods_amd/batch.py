@@ -89,9 +89,10 @@ def slp_params(par, max_lp_solves=0):
 class NativeRun:
     """Outcome of one native SLP run (asm_slp_result + the final iterate): the attributes `local_stats` and the tests read from an SlpLS.
     Trust Region (`tr`: asm_slp_tr_info) adds the final radius `delta` and the step counts `accepted`, `rejected`, `shrunk`, `expanded`;
-    they are None for Line Search."""
+    they are None for Line Search.  SLP-EQP (`eqp`: asm_slp_eqp_info) adds `eqp_counts` and the final radius `Delta_E` of its step, as SlpEQP
+    names them; None otherwise."""
 
-    def __init__(self, res, x, lam, mult_x_U, mult_x_L, g, tr=None):
+    def __init__(self, res, x, lam, mult_x_U, mult_x_L, g, tr=None, eqp=None):
         self.ret, self.iter, self.lp_solves = int(res.status), int(res.iter), int(res.lp_solves)
         self.restoration_solves, self.ls_trials, self.slot = int(res.restoration_solves), int(res.ls_trials), int(res.slot)
         self.paths = [int(v) for v in res.paths]
@@ -102,6 +103,8 @@ class NativeRun:
         self.delta = float(tr.delta) if tr is not None else None
         self.accepted, self.rejected, self.shrunk, self.expanded = ((int(tr.accepted), int(tr.rejected), int(tr.shrunk), int(tr.expanded))
                                                                     if tr is not None else (None, None, None, None))
+        self.Delta_E = float(eqp.radius) if eqp is not None else None
+        self.eqp_counts = ({k: int(getattr(eqp, k)) for k, _ in eqp._fields_ if k != "radius"} if eqp is not None else None)
 
 
 class HipBatch:

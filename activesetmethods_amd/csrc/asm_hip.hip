@@ -13,6 +13,7 @@
 #include "asm_ns_kernels.hip.h"
 #include "asm_eval_kernels.hip.h"
 #include "asm_kkt_kernels.hip.h"
+#include "asm_eqp_kernels.hip.h"
 #include "asm_batch.hip.h"
 #include "../../include/asm_hip.h"
 
@@ -258,6 +259,10 @@ struct KktBufs {
     double *part = nullptr, *scal = nullptr;
     unsigned *cnt = nullptr, *act = nullptr;
     KktWork one, blk;
+    // asm_eqp_trial (eq_prepare): [the LP's row_state (M) | its bound_state (n) | twin (m) || row_state (m) | bound_state (n) | counts (4) ||
+    // side (m)], [rw (m) | dx (n) | d (n) | scalars (EQP_SCAL)], and the pinned image of both followed by n doubles for the gradient
+    int* eq_i = nullptr;
+    double *eq_d = nullptr, *eq_h = nullptr;
 };
 
 // The device and pinned host buffers of one lifetime.  Each allocation is recorded with the field that points to it (and, for mapped host
@@ -362,6 +367,7 @@ struct asm_handle {
     std::vector<hipEvent_t> la_events;
     std::string err;
     bool setup_done = false, inputs_ready = false;
+    bool inputs_from_eval = false;  // the inputs came from asm_eval_functions: the evaluator's x, E and gradient in HBM are those of x_k
     // owners of the device / pinned buffers below, one per lifetime: the problem skeleton (until the next set-up), the null-space buffers
     // sized by k (until the dimension outgrows them), the device evaluator (until the next asm_eval_setup)
     BufPool mem, mem_nsk, mem_ev;
@@ -3373,6 +3379,7 @@ void do_upload(asm_handle* h, const double* dE, const double* df, double f, cons
     h->df.assign(df, df + h->n); h->E.assign(E, E + h->m); h->x_k.assign(x_k, x_k + h->n);
     h->f = f;
     h->inputs_ready = true;
+    h->inputs_from_eval = false;
 }
 
 void do_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub) {
@@ -4066,6 +4073,7 @@ static void do_eval_functions(asm_handle* h, const double* x, double* f, double*
     h->df.assign(df, df + n); h->E.assign(E, E + m); h->x_k.assign(x, x + n);
     h->f = *f;
     h->inputs_ready = true;
+    h->inputs_from_eval = true;
     h->J_valid = false;
 }
 
@@ -5184,6 +5192,118 @@ int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const
     });
 }
 
+// ---- the SLP-EQP trial step (include/asm_hip.h, "SLP-EQP"): steps B to F of the method on the handle, after asm_eval_functions at x
+namespace {
+void eq_prepare(asm_handle* h) {
+    kk_prepare(h);
+    KktBufs& K = h->kk;
+    if (K.eq_i) return;
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->n, m = h->m, ni = h->M + 2 * n + 3 * m + 4, nd = m + 2 * n + EQP_SCAL;
+    h->mem_kk.zeroed(K.eq_i, ni, h->stream);
+    h->mem_kk.zeroed(K.eq_d, nd, h->stream);
+    h->mem_kk.alloc(K.eq_h, (ni + 1) / 2 + nd + n + 8, BufPool::PINNED);
+    HIPCHK(asmb::sync(h->stream));
+}
+}  // namespace
+static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, const int32_t* lp_row_state, const int32_t* lp_bound_state, double radius, const double* nu,
+                         double tol_active, const asm_kkt_step_params* par, double* d, double* lam_new, double* mult_x_U, double* mult_x_L, int32_t* row_state,
+                         int32_t* bound_state, asm_eqp_info* info) {
+    const char* const who = "asm_eqp_trial";
+    const std::string me(who);
+    hs_check(h, who);
+    const int64_t n = h->n, m = h->m, M = h->M;
+    if (!x || !lp_bound_state || !d || !mult_x_U || !mult_x_L || !bound_state || !info || (m > 0 && (!lambda || !lp_row_state || !nu || !lam_new || !row_state)))
+        throw std::invalid_argument(me + ": null pointer");
+    if (!(tol_active >= 0.0)) throw std::invalid_argument(me + ": tol_active is not >= 0");
+    if (!(radius > 0.0)) throw std::invalid_argument(me + ": a radius is not > 0");
+    if (par && !(par->normal_share > 0.0 && par->normal_share <= 1.0)) throw std::invalid_argument(me + ": normal_share outside (0, 1]");
+    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
+    for (int64_t j = 0; j < n; ++j)
+        if (lp_bound_state[j] < -1 || lp_bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
+    for (int64_t i = 0; i < (m > 0 ? M : 0); ++i)
+        if (lp_row_state[i] != 0 && lp_row_state[i] != 1) throw std::invalid_argument(me + ": row_state holds a value outside {0, 1}");
+    // (inputs uploaded by asm_sublp_upload leave the evaluator's x, E and gradient in HBM where an earlier evaluation put them)
+    if (!h->inputs_ready || !h->inputs_from_eval) throw std::logic_error(me + ": asm_eval_functions first");
+    if (std::memcmp(x, h->x_k.data(), n * sizeof(double)) != 0) throw std::logic_error(me + ": x is not the point of the last asm_eval_functions");
+    if (asmb::in_fiber()) throw std::logic_error(me + ": not inside a scenario batch");
+    eq_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    std::memset(info, 0, sizeof(*info));
+    for (int64_t j = 0; j < n; ++j) d[j] = mult_x_U[j] = mult_x_L[j] = 0.0;
+    for (int64_t i = 0; i < m; ++i) lam_new[i] = 0.0;
+    const KktBufs& K = h->kk;
+    const hipStream_t s = h->stream;
+    const KktRed R{K.part, K.cnt, K.scal};
+    const int64_t n_in = M + n + m, n_out = m + n + 4;      // (the side a working row sits at stays on the device: rw carries what the host needs of it)
+    int *i_lp_rows = K.eq_i, *i_lp_bnd = i_lp_rows + M, *i_twin = i_lp_bnd + n, *i_rows = i_twin + m, *i_bnd = i_rows + m, *i_cnt = i_bnd + n, *i_side = i_cnt + 4;
+    double *d_rw = K.eq_d, *d_dx = d_rw + m, *d_d = d_dx + n, *d_scal = d_d + n;
+    // B. the face: the LP's states and the twin map go up; the working set with the two counts, rw and the gradient come back (three copies, one wait)
+    int* hi = reinterpret_cast<int*>(K.eq_h);
+    double* hd = K.eq_h + (n_in + n_out + 1) / 2;
+    if (m > 0) std::memcpy(hi, lp_row_state, M * sizeof(int));
+    std::memcpy(hi + M, lp_bound_state, n * sizeof(int));
+    for (int64_t i = 0; i < m; ++i) hi[M + n + i] = -1;
+    for (size_t a = 0; a < h->adj.size(); ++a) hi[M + n + h->adj[a]] = (int)a;
+    HIPCHK(asmb::copy_async(i_lp_rows, hi, n_in * sizeof(int), hipMemcpyHostToDevice, s));
+    const SlpVecs V = ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const EqpFace P{V.E, V.g_L, V.g_U, V.x, V.x_L, V.x_U, i_lp_rows, i_lp_bnd, i_twin, n, m, tol_active};
+    const unsigned gf = (unsigned)std::min<int64_t>(asmb::blocks(std::max(n, m)).x, KK_MAXWG);
+    asmb::launch(k_eqp_face, dim3(gf), dim3(256), s, P, R, i_rows, i_bnd, i_side, d_rw, i_cnt);
+    HIPCHK(asmb::copy_async(hi + n_in, i_rows, n_out * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (m > 0) HIPCHK(asmb::copy_async(hd, d_rw, m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::copy_async(hd + m, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::sync(s));
+    const int* o_rows = hi + n_in;
+    const int *o_bnd = o_rows + m, *o_cnt = o_bnd + n;
+    std::vector<int32_t> rs((size_t)std::max<int64_t>(m, 1), 0);
+    for (int64_t i = 0; i < m; ++i) rs[i] = row_state[i] = o_rows[i];
+    for (int64_t j = 0; j < n; ++j) bound_state[j] = o_bnd[j];
+    info->n_rows = o_cnt[EQP_NW];
+    info->n_free = o_cnt[EQP_NF];
+    // C. more working rows than free variables
+    if (info->n_rows > info->n_free) { info->skipped = 1; return; }
+    // D. the trust-region step (asm_kkt_step): ru = grad f, rw_W = E_W - bound_W
+    vec ru(hd + m, hd + m + n), rw(hd, hd + m), dx((size_t)n), dlam((size_t)std::max<int64_t>(m, 1)), dz((size_t)n);
+    rw.resize((size_t)std::max<int64_t>(m, 1), 0.0);
+    asm_kkt_step_info st;
+    do_kkt_step(h, who, false, x, lambda, rs.data(), bound_state, 1, ru.data(), rw.data(), &radius, par, dx.data(), dlam.data(), dz.data(), &st);
+    info->status = st.status; info->cg_iters = st.cg_iters; info->n_free = st.n_free; info->n_rows = st.n_rows; info->dropped_pivots = st.dropped_pivots;
+    info->boundary = st.boundary; info->res_stat = st.res_stat; info->res_feas = st.res_feas; info->theta = st.theta; info->norm_normal = st.norm_normal;
+    info->norm_step = st.norm_step; info->model = st.model;
+    if (st.status == 3) { info->skipped = 2; return; }
+    // E. the fraction to the box, d = t dx and its norms
+    double* hx = K.eq_h;
+    std::memcpy(hx, dx.data(), n * sizeof(double));
+    HIPCHK(asmb::copy_async(d_dx, hx, n * sizeof(double), hipMemcpyHostToDevice, s));
+    const unsigned gt = (unsigned)std::min<int64_t>(asmb::blocks(n).x, KK_MAXWG);
+    asmb::launch(k_eqp_trial, dim3(gt), dim3(256), s, (const double*)d_dx, V.x, V.x_L, V.x_U, n, R, d_d, d_scal);
+    HIPCHK(asmb::copy_async(hx + n, d_d, (n + EQP_SCAL) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::sync(s));
+    const double* sc = hx + 2 * n;
+    info->t = sc[EQP_T]; info->norm_d = sc[EQP_NORM2]; info->norm_d_inf = sc[EQP_NORMINF];
+    if (sc[EQP_NONZERO] == 0.0) { info->skipped = 3; return; }
+    std::memcpy(d, hx + n, n * sizeof(double));
+    // F. the merit function at x and at x + d (the launch set of asm_slp_step_quality outside restoration: the slacks are not read)
+    vec ps((size_t)(2 * std::max<int64_t>(m, 1)), 0.0);
+    double q[3];
+    slp_tr_step_quality(h, d, nu, ps.data(), 0, 0.0, q);
+    info->phi0 = q[1]; info->phi1 = q[2];
+    for (int64_t i = 0; i < m; ++i) lam_new[i] = dlam[i];
+    for (int64_t j = 0; j < n; ++j) {
+        mult_x_U[j] = bound_state[j] == 1 ? dz[j] : 0.0;
+        mult_x_L[j] = bound_state[j] == -1 ? dz[j] : 0.0;
+    }
+}
+
+int asm_eqp_trial(asm_handle* h, const double* x, const double* lambda, const int32_t* lp_row_state, const int32_t* lp_bound_state, double radius, const double* nu,
+                  double tol_active, const asm_kkt_step_params* par, double* d, double* lam_new, double* mult_x_U, double* mult_x_L, int32_t* row_state,
+                  int32_t* bound_state, asm_eqp_info* info) {
+    return guarded(h, [&] {
+        do_eqp_trial(h, x, lambda, lp_row_state, lp_bound_state, radius, nu, tol_active, par, d, lam_new, mult_x_U, mult_x_L, row_state, bound_state, info);
+    });
+}
+
 // --------------------------------------------------------------------------------- kernel test hooks
 static void test_alloc(asm_handle* h, int64_t M, int64_t K) {
     // minimal "problem" so that the generic buffers exist: dense pattern M x K
@@ -6199,6 +6319,11 @@ struct SlpRunTR : SlpRun {
     vec rn;
     double Delta, Delta_max = 2.0, alpha1 = 0.1, alpha2 = 0.25;     // slp_trust_region.jl:62-65
     asm_slp_tr_info info{};
+    int32_t lp_status = 0;          // the last LP solved: its status and whether it was a restoration LP
+    bool lp_fr = false;
+    virtual ~SlpRunTR() = default;
+    // between the evaluation and the LP: nothing here (SlpRunEQP takes its step on the LP's working set)
+    virtual void second_order_step() {}
 
     SlpRunTR(asm_handle* hh, const asm_slp_params& par, double tr_size, asm_slp_result* r)
         : SlpRun(hh, par, r), rn(std::max<int64_t>(m, 1), 0.0), Delta(tr_size) {}
@@ -6250,9 +6375,11 @@ struct SlpRunTR : SlpRun {
             asmb::next_cycle();
             asmb::barrier(11);
             do_eval_functions(h, x.data(), &f, df.data(), E.data());                                    // :120
+            second_order_step();
             int32_t status = 0;
             do_solve(h, Delta, fr ? 1 : 0, p.data(), lam.data(), mU.data(), mL.data(), ps.data(), &status);
             count_lp();
+            lp_status = status; lp_fr = fr;
             if (status != ASM_OPTIMAL && status != ASM_INFEASIBLE) {                                     // :130-136 (`slp.ret == -3`: a comparison, sic)
                 double fc = 0.0, v1 = 0.0;
                 vec Ec(std::max<int64_t>(m, 1));
@@ -6295,6 +6422,50 @@ struct SlpRunTR : SlpRun {
     }
 };
 
+// SLP-EQP (include/asm_hip.h, "SLP-EQP"): SlpRunTR with the trust-region step on the working set of the last LP between the evaluation
+// and the LP - statement by statement SlpEQP.second_order_step of activesetmethods_amd/slp.py with Parameters(device_eval=True):
+// asm_eqp_trial, and asm_eval_functions again after an accepted step.  iter, lp_solves and the LP's radius are not touched.
+struct SlpRunEQP : SlpRunTR {
+    const asm_slp_eqp_params& e;
+    asm_slp_eqp_info eq{};
+    std::vector<int32_t> rs, bs;
+    vec d, lam_t, mU_t, mL_t;
+
+    SlpRunEQP(asm_handle* hh, const asm_slp_params& par, double tr_size, const asm_slp_eqp_params& ep, asm_slp_result* r)
+        : SlpRunTR(hh, par, tr_size, r), e(ep), rs(std::max<int64_t>(m, 1), 0), bs(n, 0), d(n, 0.0), lam_t(std::max<int64_t>(m, 1), 0.0), mU_t(n, 0.0), mL_t(n, 0.0) {
+        eq.radius = ep.radius0;
+    }
+
+    void second_order_step() override {
+        // A. outside restoration, after a normal-phase LP that ended OPTIMAL (its active set is the handle's h->last)
+        if (fr || lp_solves == 0 || lp_status != ASM_OPTIMAL || lp_fr || !h->last.valid || !e.enabled) return;
+        eq.attempts += 1;
+        asm_eqp_info t;
+        const std::vector<int32_t> lp_rows(h->last.rowst.begin(), h->last.rowst.end()), lp_bnd(h->last.bst.begin(), h->last.bst.end());      // (as asm_sublp_active_set)
+        do_eqp_trial(h, x.data(), lam.data(), lp_rows.data(), lp_bnd.data(), eq.radius, nu.data(), e.tol_active, nullptr, d.data(), lam_t.data(), mU_t.data(),
+                     mL_t.data(), rs.data(), bs.data(), &t);                                            // B to F
+        if (t.skipped) {
+            if (t.skipped == 1) eq.skipped_rows += 1;
+            else if (t.skipped == 2) eq.skipped_dependent += 1;
+            else eq.skipped_zero += 1;
+            if (t.skipped != 1) eq.cg_iters += t.cg_iters;
+            return;
+        }
+        eq.cg_iters += t.cg_iters;
+        eq.boundary += t.boundary != 0;
+        if (t.phi1 < t.phi0) {                                                                           // F, G
+            eq.accepted += 1;
+            for (int64_t j = 0; j < n; ++j) { x[j] = x[j] + d[j]; mU[j] = mU_t[j]; mL[j] = mL_t[j]; }
+            for (int64_t i = 0; i < m; ++i) lam[i] = lam_t[i];
+            if (t.boundary != 0 && t.t == 1.0) eq.radius = std::min(2.0 * eq.radius, e.radius_max);
+            do_eval_functions(h, x.data(), &f, df.data(), E.data());
+        } else {
+            eq.rejected += 1;
+            eq.radius = 0.5 * t.norm_d;
+        }
+    }
+};
+
 void check_tr_size(double tr_size, const char* what) {
     if (!std::isfinite(tr_size) || !(tr_size > 0.0)) throw std::invalid_argument(std::string(what) + ": tr_size must be finite and > 0");
 }
@@ -6307,6 +6478,18 @@ void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const 
     r.run(x0);
     r.outputs(x_out, lambda, mult_x_U, mult_x_L, g_out);
     if (tr) *tr = r.info;
+}
+
+void slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* ep, const double* x0, double* x_out, double* lambda,
+                 double* mult_x_U, double* mult_x_L, double* g_out, asm_slp_result* res, asm_slp_tr_info* tr, asm_slp_eqp_info* eq) {
+    hs_check(h, "asm_slp_run_eqp");
+    if (asmb::in_fiber()) throw std::logic_error("asm_slp_run_eqp: not inside a scenario batch");
+    if (res) std::memset(res, 0, sizeof(*res));
+    SlpRunEQP r(h, *par, tr_size, *ep, res);
+    r.run(x0);
+    r.outputs(x_out, lambda, mult_x_U, mult_x_L, g_out);
+    if (tr) *tr = r.info;
+    if (eq) *eq = r.eq;
 }
 
 }  // namespace
@@ -6447,6 +6630,17 @@ int asm_slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, con
         if (!par || !x0) throw std::invalid_argument("asm_slp_run_tr: null pointer");
         check_tr_size(tr_size, "asm_slp_run_tr");
         slp_run_tr(h, par, tr_size, x0, x, lambda, mult_x_U, mult_x_L, g, res, tr);
+    });
+}
+
+int asm_slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* eqp_par, const double* x0, double* x, double* lambda,
+                    double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res, asm_slp_tr_info* tr, asm_slp_eqp_info* eqp_info) {
+    return guarded(h, [&] {
+        if (!par || !eqp_par || !x0) throw std::invalid_argument("asm_slp_run_eqp: null pointer");
+        check_tr_size(tr_size, "asm_slp_run_eqp");
+        if (!std::isfinite(eqp_par->radius0) || !(eqp_par->radius0 > 0.0) || !(eqp_par->radius_max > 0.0) || !(eqp_par->tol_active >= 0.0))
+            throw std::invalid_argument("asm_slp_run_eqp: radius0 must be finite and > 0, radius_max > 0, tol_active >= 0");
+        slp_run_eqp(h, par, tr_size, eqp_par, x0, x, lambda, mult_x_U, mult_x_L, g, res, tr, eqp_info);
     });
 }
 

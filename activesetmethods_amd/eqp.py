@@ -10,9 +10,13 @@ Steihaug-Toint truncation - the equality-constrained QP of sensitivity.py with a
     kkt_step_reference_multi kkt_step_reference column by column
     fraction_to_box          the largest t in [0, 1] with lo <= t dx <= hi
     eqp_step                 one step from a point: working set, right-hand sides, kkt_step, fraction to the variable bounds
+    lp_working_set           the working set an LP's active set names at a point (include/asm_hip.h, "SLP-EQP")
+    eqp_trial_host           the NumPy twin of asm_eqp_trial: lp_working_set, kkt_step_pcg, fraction_to_box, the two merit values
 
-A driver that uses the step (SLP-EQP) is not here.
+The driver that uses the step is slp.SlpEQP (Parameters(algorithm="SLP-EQP")); its native form is asm_slp_run_eqp.
 """
+from types import SimpleNamespace
+
 import numpy as np
 
 from .moi_evaluator import lagrangian_hessian
@@ -251,3 +255,81 @@ def eqp_step(opt, fm, problem, x, lam, mult_x_U, mult_x_L, radius, tol=1e-8):
     dx, lam_new, _, info = opt.kkt_step(x, lam, row_state, bound_state, ru, rw, radius)[:4]
     t = fraction_to_box(dx, np.asarray(problem.x_L, float) - x, np.asarray(problem.x_U, float) - x)
     return x + t * dx, np.asarray(lam_new, float), info
+
+
+def lp_working_set(problem, x, S, tol=1e-8):
+    """The working set the active set S = (row_state [m + n_adj], bound_state [n], ...) of an LP solved at x names (the tuple
+    HipSubOptimizer.active_set() returns).  adj, the rows with two distinct finite bounds in index order, have their `<=` twins in rows
+    m.. of the LP's row_state.  A row is in W if it is an equality, if the LP holds it active or if its twin is active; it sits at g_L
+    (an equality), at g_U (twin active, or g_L infinite), else at g_L.  A variable is in B only where the LP reports it at a bound and
+    x is at the matching bound of the problem within tol * (1 + |bound|): a variable the trust region stopped is free.
+    Returns (row_state [m] of 0 / 1, bound_state [n] of -1 / 0 / +1, bound [m]: the bound a working row sits at, 0 elsewhere)."""
+    x = np.asarray(x, float)
+    n, m = int(problem.n), int(problem.m)
+    g_L, g_U = np.asarray(problem.g_L, float).reshape(m), np.asarray(problem.g_U, float).reshape(m)
+    x_L, x_U = np.asarray(problem.x_L, float), np.asarray(problem.x_U, float)
+    adj = np.flatnonzero(np.isfinite(g_L) & np.isfinite(g_U) & (g_L != g_U))
+    lp_rows, lp_bnd = np.asarray(S[0]), np.asarray(S[1])
+    if lp_rows.shape != (m + len(adj),) or lp_bnd.shape != (n,) or x.shape != (n,):
+        raise ValueError("x / the LP's row_state / bound_state have shapes %r / %r / %r, expected (%d,) / (%d,) / (%d,)"
+                         % (x.shape, lp_rows.shape, lp_bnd.shape, n, m + len(adj), n))
+    twin = np.zeros(m, bool)
+    twin[adj] = lp_rows[m:] != 0
+    row_state = ((g_L == g_U) | (lp_rows[:m] != 0) | twin).astype(np.int32)
+    at = np.where(g_L == g_U, g_L, np.where(twin | ~np.isfinite(g_L), g_U, g_L))
+    with np.errstate(invalid="ignore"):
+        lower = (lp_bnd == -1) & np.isfinite(x_L) & (np.abs(x - x_L) <= tol * (1.0 + np.abs(x_L)))
+        upper = (lp_bnd == 1) & np.isfinite(x_U) & (np.abs(x - x_U) <= tol * (1.0 + np.abs(x_U)))
+    bound_state = np.where(lower, -1, np.where(upper, 1, 0)).astype(np.int32)
+    return row_state, bound_state, np.where(row_state == 1, at, 0.0)
+
+
+def _merit(problem, x, nu):
+    """compute_phi of the SLP drivers outside restoration: f(x) + nu' viol(g(x))."""
+    m = int(problem.m)
+    E = np.asarray(problem.eval_g(x, np.zeros(m)), float) if m else np.zeros(0)
+    viol = np.maximum(0.0, np.maximum(E - np.asarray(problem.g_U, float), np.asarray(problem.g_L, float) - E))
+    return float(problem.eval_f(x) + np.asarray(nu, float) @ viol)
+
+
+def eqp_trial_host(fm, problem, x, lam, lp_row_state, lp_bound_state, radius, nu, tol_active=1e-8, max_iter=None, rtol=1e-12, normal_share=0.8,
+                   kkt_step=None):
+    """The NumPy twin of asm_eqp_trial: the working set of lp_working_set, ru = grad f(x), rw_W = g_W(x) - bound_W, the trust-region step
+    (kkt_step_pcg, or kkt_step(x, lam, row_state, bound_state, ru, rw, radius) -> (dx, dlam, dz, info)), d = t dx with t the fraction of
+    fraction_to_box, and the merit values f + nu' viol at x and x + d.  Returns (d, lam_new, mult_x_U, mult_x_L, row_state, bound_state,
+    info), info with the fields of asm_eqp_info: those of asm_kkt_step_info, t, norm_d, norm_d_inf, phi0, phi1 and skipped (0 none, 1 more
+    working rows than free variables, 2 dependent working rows, 3 zero step).  A skipped trial returns zeros for d and the multipliers."""
+    if not float(tol_active) >= 0.0:
+        raise ValueError("tol_active must be >= 0")
+    x, lam = np.asarray(x, float), np.asarray(lam, float)
+    n, m = int(problem.n), int(problem.m)
+    row_state, bound_state, at = lp_working_set(problem, x, (lp_row_state, lp_bound_state), tol_active)
+    info = dict(status=0, cg_iters=0, n_free=int((bound_state == 0).sum()), n_rows=int(row_state.sum()), dropped_pivots=0, boundary=0, res_stat=0.0,
+                res_feas=0.0, theta=0.0, norm_normal=0.0, norm_step=0.0, model=0.0, t=0.0, norm_d=0.0, norm_d_inf=0.0, phi0=0.0, phi1=0.0, skipped=0)
+    zero = (np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(n), row_state, bound_state)
+    if info["n_rows"] > info["n_free"]:
+        info["skipped"] = 1
+        return zero + (SimpleNamespace(**info),)
+    ru = np.asarray(fm.eval_grad_f(x, np.zeros(n)), float)
+    E = np.asarray(problem.eval_g(x, np.zeros(m)), float) if m else np.zeros(0)
+    rw = np.where(row_state == 1, E - at, 0.0)
+    if kkt_step is None:
+        dx, dlam, dz, step = kkt_step_pcg(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=max_iter, rtol=rtol, normal_share=normal_share)
+    else:
+        dx, dlam, dz, step = kkt_step(x, lam, row_state, bound_state, ru, rw, radius)[:4]
+    if not isinstance(step, dict):
+        step = {k: getattr(step, k) for k, _ in step._fields_}
+    info.update(step)
+    if info["status"] == 3:
+        info["skipped"] = 2
+        return zero + (SimpleNamespace(**info),)
+    t = fraction_to_box(dx, np.asarray(problem.x_L, float) - x, np.asarray(problem.x_U, float) - x)
+    d = t * dx
+    info.update(t=t, norm_d=float(np.sqrt(d @ d)), norm_d_inf=float(np.abs(d).max()) if n else 0.0)
+    if not d.any():
+        info["skipped"] = 3
+        return zero + (SimpleNamespace(**info),)
+    info.update(phi0=_merit(problem, x, nu), phi1=_merit(problem, x + d, nu))
+    dz = np.asarray(dz, float)
+    return (d, np.asarray(dlam, float), np.where(bound_state == 1, dz, 0.0), np.where(bound_state == -1, dz, 0.0), row_state, bound_state,
+            SimpleNamespace(**info))

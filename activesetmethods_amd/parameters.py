@@ -29,6 +29,12 @@ class Parameters:
     # not in the reference: evaluate f, grad f, g and the Jacobian values on the GPU (needs a Problem built from a FunctionModel,
     # activesetmethods_amd/moi_evaluator.py) and run the per-iteration norms / merit reductions there
     device_eval: bool = False
+    # not in the reference: algorithm = "SLP-EQP" (slp.SlpEQP, asm_slp_run_eqp) - the initial radius of its trust-region step (None:
+    # tr_size), the cap on that radius, the activity tolerance of its working set, and a switch that leaves the Trust Region driver
+    eqp_radius: Any = None
+    eqp_radius_max: float = 1.e+3
+    eqp_tol_active: float = 1.e-8
+    eqp: bool = True
 
 
 def get_parameter(params, pname):          # src/parameters.jl:31-33

@@ -5,6 +5,7 @@ outer loops, restated in Python so that the hot path can be driven where no Juli
     Model, optimize        src/model.jl:1-80
     SlpLS.run              src/algorithms/slp_line_search.jl:78-261
     SlpTR.run              src/algorithms/slp_trust_region.jl:87-251
+    SlpEQP.run             not in the reference: SlpTR.run with a trust-region step on the LP's working set (include/asm_hip.h, "SLP-EQP")
     merit / norm helpers   src/algorithms/slp.jl:54-147, src/algorithms/common.jl:35-98
 
 Every LP sub-problem goes through `parameters.external_optimizer` (default: HipSubOptimizer ->
@@ -351,6 +352,9 @@ class SlpTR(AbstractSlpOptimizer):
                 self.ret = 2
         return rho
 
+    def second_order_step(self):
+        """Between the evaluation and the LP: nothing here (SlpEQP takes its step on the LP's working set)."""
+
     def run(self, max_lp_solves=None, resume=False):
         o, pr = self.options, self.problem
         if not resume:
@@ -360,6 +364,7 @@ class SlpTR(AbstractSlpOptimizer):
             if max_lp_solves is not None and self.lp_solves >= max_lp_solves:
                 break
             self.eval_functions()
+            self.second_order_step()
             self.p, self.lam, self.mult_x_U, self.mult_x_L, self.p_slack, status = self.sub_optimize(self.Delta)
             if status not in (OPTIMAL, INFEASIBLE):
                 if self.norm_violations(1, pr.eval_g(self.x, np.zeros(pr.m))) <= o.tol_infeas:
@@ -395,10 +400,63 @@ class SlpTR(AbstractSlpOptimizer):
         self._finish()
 
 
+class SlpEQP(SlpTR):
+    """SLP-EQP: SlpTR with one insertion between eval_functions() and the LP - the trust-region step of the equality-constrained QP on
+    the working set the last LP named (include/asm_hip.h, "SLP-EQP"; eqp.py).  The step goes through one method of the sub-optimizer,
+    eqp_trial (HipSubOptimizer: asm_eqp_trial; a CPU stand-in: eqp.eqp_trial_host), and is taken when it lowers the merit function.  It
+    has a radius of its own; iter, lp_solves and the LP's radius are not touched.  Parameters(eqp=False) is SlpTR."""
+
+    def __init__(self, problem):
+        super().__init__(problem)
+        o = self.options
+        if o.external_optimizer is None and self._fm is None:
+            # asm_eqp_trial reads x, E and the gradient where the device evaluator left them: host callbacks leave nothing there
+            raise ValueError("SLP-EQP on the HIP sub-optimizer needs Parameters(device_eval=True) and a problem built from a FunctionModel")
+        self.Delta_E = float(o.tr_size if o.eqp_radius is None else o.eqp_radius)
+        if not (np.isfinite(self.Delta_E) and self.Delta_E > 0.0) or not float(o.eqp_radius_max) > 0.0 or not float(o.eqp_tol_active) >= 0.0:
+            raise ValueError("eqp_radius and eqp_radius_max must be > 0 (eqp_radius finite), eqp_tol_active >= 0")
+        self._lp_sets = None                                     # the active set of the last LP, if that was a normal-phase OPTIMAL one
+        self.eqp_counts = dict(attempts=0, accepted=0, rejected=0, skipped_rows=0, skipped_dependent=0, skipped_zero=0, cg_iters=0, boundary=0)
+
+    def sub_optimize(self, Delta=1000.0):
+        out = super().sub_optimize(Delta)
+        self._lp_sets = self.trace[-1].get("sets") if (out[5] == OPTIMAL and not self.feasibility_restoration) else None
+        return out
+
+    def second_order_step(self):
+        o, c = self.options, self.eqp_counts
+        if self.feasibility_restoration or self._lp_sets is None or not o.eqp:                      # A
+            return
+        c["attempts"] += 1
+        d, lam, mult_x_U, mult_x_L, _, _, info = self.optimizer.eqp_trial(self.x, self.lam, self._lp_sets[0], self._lp_sets[1], self.Delta_E,
+                                                                          self.nu, o.eqp_tol_active)          # B to F
+        if info.skipped:
+            c[("skipped_rows", "skipped_dependent", "skipped_zero")[info.skipped - 1]] += 1
+            if info.skipped != 1:
+                c["cg_iters"] += int(info.cg_iters)
+            return
+        c["cg_iters"] += int(info.cg_iters)
+        c["boundary"] += int(info.boundary != 0)
+        if info.phi1 < info.phi0:                                                                    # F, G
+            c["accepted"] += 1
+            self.x = self.x + d
+            self.lam, self.mult_x_U, self.mult_x_L = lam, mult_x_U, mult_x_L
+            if info.boundary != 0 and info.t == 1.0:
+                self.Delta_E = min(2.0 * self.Delta_E, float(o.eqp_radius_max))
+            self.eval_functions()
+        else:
+            c["rejected"] += 1
+            self.Delta_E = 0.5 * info.norm_d
+
+    def _finish(self):
+        super()._finish()
+        self.problem.statistics.update(eqp=dict(self.eqp_counts, radius=self.Delta_E))
+
+
 def optimize(model, max_lp_solves=None, native=False):
     """src/model.jl:63-80 (an unset `external_optimizer` selects the HIP sub-optimizer instead of status -12).
 
-    native=True: the whole run inside the library (asm_slp_run / asm_slp_run_tr by `parameters.algorithm`) on a fresh handle; needs
+    native=True: the whole run inside the library (asm_slp_run / asm_slp_run_tr / asm_slp_run_eqp by `parameters.algorithm`) on a fresh handle; needs
     `device_eval=True` and a model built from a FunctionModel.  The model is filled as the host drivers fill it; returns the NativeRun."""
     par = model.parameters
     if par.method != "SLP":
@@ -409,6 +467,8 @@ def optimize(model, max_lp_solves=None, native=False):
         slp = SlpLS(model)
     elif par.algorithm == "Trust Region":
         slp = SlpTR(model)
+    elif par.algorithm == "SLP-EQP":
+        slp = SlpEQP(model)
     else:
         raise ValueError("unknown algorithm %r" % par.algorithm)
     slp.run(max_lp_solves)
@@ -420,7 +480,7 @@ def _optimize_native(model, max_lp_solves=None):
     fm = getattr(model, "function_model", None)
     if not getattr(par, "device_eval", False) or fm is None:
         raise ValueError("optimize(native=True) needs Parameters(device_eval=True) and a model built from a FunctionModel")
-    if par.algorithm not in ("Line Search", "Trust Region"):
+    if par.algorithm not in ("Line Search", "Trust Region", "SLP-EQP"):
         raise ValueError("unknown algorithm %r" % par.algorithm)
     opt = HipSubOptimizer(QpData(np.zeros(model.n), 0.0, np.zeros(len(model.j_row)), np.zeros(model.m), model.g_L, model.g_U, model.x_L, model.x_U),
                           model.j_row, model.j_col)
@@ -434,4 +494,6 @@ def _optimize_native(model, max_lp_solves=None):
     model.x[:] = run.x; model.g[:] = run.E; model.mult_g[:] = run.lam
     model.mult_x_U[:] = run.mult_x_U; model.mult_x_L[:] = run.mult_x_L
     model.statistics.update(iter=run.iter, lp_solves=run.lp_solves)
+    if run.eqp_counts is not None:
+        model.statistics.update(eqp=dict(run.eqp_counts, radius=run.Delta_E))
     return run

@@ -408,6 +408,26 @@ class HipSubOptimizer:
                                                  _lib.dptr(radii), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return DX, DLAM[:, :self.m], DZ, list(infos)
 
+    def eqp_trial(self, x, lam, lp_row_state, lp_bound_state, radius, nu, tol_active=1e-8, max_iter=None, rtol=None, normal_share=None):
+        """(d, lam_new, mult_x_U, mult_x_L, row_state, bound_state, info) of asm_eqp_trial: the SLP-EQP trial step at the point of the last
+        eval_functions(x) - the working set the LP's active set (lp_row_state [m + n_adj], lp_bound_state [n]: active_set()) names there,
+        the trust-region step on it, d = t dx inside the variable bounds and the merit values at x and x + d (info: asm_eqp_info)."""
+        x, lam, nu = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(nu, self.m, "nu")
+        d = self.data
+        nadj = int(((d.c_lb > -np.inf) & (d.c_ub < np.inf) & (d.c_lb != d.c_ub)).sum())
+        lr = np.ascontiguousarray(np.atleast_1d(lp_row_state), dtype=np.int32)
+        lb = np.ascontiguousarray(np.atleast_1d(lp_bound_state), dtype=np.int32)
+        if lr.shape != (self.m + nadj,) or lb.shape != (self.n,):
+            raise ValueError("the LP's row_state / bound_state have shapes %r / %r, expected (%d,) / (%d,)" % (lr.shape, lb.shape, self.m + nadj, self.n))
+        if not len(lr):
+            lr = np.zeros(1, np.int32)
+        step, lam_new, mU, mL = np.empty(self.n), np.empty(max(self.m, 1)), np.empty(self.n), np.empty(self.n)
+        rs, bs, info = np.zeros(max(self.m, 1), np.int32), np.zeros(self.n, np.int32), _lib.EqpInfo()
+        self._check(self._lib.asm_eqp_trial(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(lr), _lib.i32ptr(lb), float(radius), _lib.dptr(nu), float(tol_active),
+                                            self._kkt_step_params(max_iter, rtol, normal_share), _lib.dptr(step), _lib.dptr(lam_new), _lib.dptr(mU), _lib.dptr(mL),
+                                            _lib.i32ptr(rs), _lib.i32ptr(bs), C.byref(info)))
+        return step, lam_new[:self.m], mU, mL, rs[:self.m], bs, info
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)
@@ -458,17 +478,23 @@ class HipSubOptimizer:
         return tuple(float(v) for v in out)
 
     def slp_run(self, x0, parameters, max_lp_solves=0):
-        """One complete SLP run inside the library (asm_slp_run for Line Search, asm_slp_run_tr for Trust Region, by
-        `parameters.algorithm`) from x0 on this handle; needs eval_setup.  Returns a batch.NativeRun."""
+        """One complete SLP run inside the library (asm_slp_run for Line Search, asm_slp_run_tr for Trust Region, asm_slp_run_eqp for
+        SLP-EQP, by `parameters.algorithm`) from x0 on this handle; needs eval_setup.  Returns a batch.NativeRun."""
         from .batch import NativeRun, slp_params
-        if parameters.algorithm not in ("Line Search", "Trust Region"):
-            raise ValueError("the native drivers restate run!(::SlpLS) and run!(::SlpTR) only, not %r" % parameters.algorithm)
+        if parameters.algorithm not in ("Line Search", "Trust Region", "SLP-EQP"):
+            raise ValueError("the native drivers are run!(::SlpLS), run!(::SlpTR) and SLP-EQP, not %r" % parameters.algorithm)
         par = slp_params(parameters, max_lp_solves)
         x0 = _f64(x0)
         x = np.empty(self.n); lam = np.empty(max(self.m, 1)); mU = np.empty(self.n); mL = np.empty(self.n); g = np.empty(max(self.m, 1))
         res = _lib.SlpResult()
         outs = (_lib.dptr(x), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(g), C.byref(res))
         tr = None
+        if parameters.algorithm == "SLP-EQP":
+            tr, eq = _lib.SlpTrInfo(), _lib.SlpEqpInfo()
+            ep = _lib.SlpEqpParams(float(parameters.tr_size if parameters.eqp_radius is None else parameters.eqp_radius), float(parameters.eqp_radius_max),
+                                   float(parameters.eqp_tol_active), int(bool(parameters.eqp)))
+            self._check(self._lib.asm_slp_run_eqp(self._h, C.byref(par), float(parameters.tr_size), C.byref(ep), _lib.dptr(x0), *outs, C.byref(tr), C.byref(eq)))
+            return NativeRun(res, x, lam[:self.m], mU, mL, g[:self.m], tr, eq)
         if parameters.algorithm == "Trust Region":
             tr = _lib.SlpTrInfo()
             self._check(self._lib.asm_slp_run_tr(self._h, C.byref(par), float(parameters.tr_size), _lib.dptr(x0), *outs, C.byref(tr)))

@@ -334,7 +334,7 @@ int asm_eval_hessian_structure(const asm_handle* h, int64_t* nnz, int64_t* rows,
 int asm_eval_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values);
 int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out);
 
-/* ---- The KKT solve on a working set: the equality-constrained QP behind solution sensitivities (and any later second-order step).
+/* ---- The KKT solve on a working set: the equality-constrained QP behind solution sensitivities and behind the step of SLP-EQP.
  * With F = {j : bound_state[j] = 0} (the free variables, B its complement), W = {i : row_state[i] = 1} (the working rows), H the Hessian of
  * f - lambda' g at x (what asm_eval_hessian_lagrangian(x, 1.0, -lambda) gives), J the Jacobian at x and A = J[W, F], asm_kkt_solve solves
  *   H_FF dx_F - A' dlam_W = -ru_F ,    A dx_F = -rw_W ,    dx_B = 0 ,    dlam_i = 0 (i not in W) ,
@@ -524,6 +524,69 @@ typedef struct {
 } asm_slp_tr_info;
 int asm_slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const double* x0, double* x, double* lambda,
                    double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res, asm_slp_tr_info* tr /* may be NULL */);
+
+/* ---- SLP-EQP: the Trust-Region SLP with a second-order step on the working set the LP names (not in the reference).
+ * At a solution that is not a vertex of the linearisation an LP step runs to the boundary of its region, is rejected, and the radius
+ * shrinks until it falls below tol_direction: first-order convergence at best.  SLP-EQP inserts, between the evaluation at the top of an
+ * iteration and the LP, the trust-region step of the equality-constrained QP (asm_kkt_step) on the working set of the last LP, with a
+ * radius D_E of its own, and takes the step when it lowers the merit function.  The stop tests remain the Trust-Region driver's.
+ *   A. Attempted only outside feasibility restoration, when the last LP solved was a normal-phase LP with status OPTIMAL.  S = its active
+ *      set (asm_sublp_active_set), lambda = its multipliers.
+ *   B. Working set.  adj = the rows with two distinct finite bounds, in index order; rows m.. of S's row_state are their `<=` twins.
+ *      Row i is in W if it is an equality, if row_state[i] != 0 or if its twin is active; it sits at g_L (an equality), at g_U (twin
+ *      active, or g_L infinite), else at g_L.  Variable j is in B only where S reports it at a bound and |x_j - bound| <= tol_active
+ *      (1 + |bound|) for the problem's finite bound on that side: a variable the LP's trust region stopped is free.
+ *   C. |W| > |F|: skipped (1).
+ *   D. asm_kkt_step(x, lambda, W, B, ru = grad f(x), rw_W = E_W - bound_W, radius = D_E); status 3 (dependent rows): skipped (2).
+ *   E. t = the largest value in [0, 1] with x_L <= x + t dx <= x_U, d = t dx; d identically zero: skipped (3).
+ *   F. phi0, phi1 = the merit function f + nu' viol (asm_slp_merit mode 0) at alpha = 0 and 1 with p = d; accepted iff phi1 < phi0.
+ *   G. accepted: x += d, lambda = dlam, mult_x_L = dz on B = -1, mult_x_U = dz on B = +1, 0 elsewhere; D_E = min(2 D_E, radius_max)
+ *      if the step ended on its boundary (boundary != 0) with t = 1; the functions are evaluated again.  Rejected: D_E = ||d||_2 / 2.
+ *      iter, lp_solves and the LP's radius are not touched.
+ * asm_eqp_trial is steps B to F in one call, after asm_eval_functions at x (the point the evaluator holds: E, x and the gradient are
+ * read where it left them in HBM).  lp_row_state [m + n_adj], lp_bound_state [n]: S.  nu [m]: the merit weights.  par == NULL: the
+ * defaults of asm_kkt_step.  Outputs: d [n], lam_new [m], mult_x_U, mult_x_L [n] (all zero for a skipped trial), the working set used
+ * (row_state [m] of 0 / 1, bound_state [n] of -1 / 0 / +1) and info.
+ *   k_eqp_face makes the working set, the side each working row sits at, rw and the counts |W|, |F| in one launch; the step is
+ *   asm_kkt_step's driver and kernels, unchanged; k_eqp_trial makes t, d, ||d||_2 and ||d||_inf in one launch - per-workgroup partial
+ *   sums added in workgroup order, no atomics on doubles; the two merit values are the launch set of asm_slp_step_quality.  d is, bit
+ *   for bit, t times the dx asm_kkt_step returns for the same working set, phi0 / phi1 are asm_slp_merit's values.
+ * The inputs of the next LP, the retained basis and the active sets are not touched (asm_kkt_step's guarantee).
+ * Validity and argument errors are asm_kkt_step's; tol_active not >= 0 or a state outside its value set ({0, 1} for rows, {-1, 0, +1} for
+ * bounds): ASM_ERR_ARG; ASM_ERR_STATE unless the handle's last inputs came from asm_eval_functions (not asm_sublp_upload) at this very x;
+ * not inside a scenario batch.  The handle works on after any of them. */
+typedef struct {
+    int32_t status, cg_iters, n_free, n_rows, dropped_pivots, boundary;     /* as asm_kkt_step_info (n_free, n_rows: the face's counts) */
+    double res_stat, res_feas, theta, norm_normal, norm_step, model;
+    int32_t skipped;           /* 0 none, 1 more working rows than free variables, 2 dependent working rows, 3 zero step */
+    double t;                  /* fraction of dx that stays inside the variable bounds */
+    double norm_d, norm_d_inf; /* ||d||_2, ||d||_inf */
+    double phi0, phi1;         /* merit function at x and at x + d */
+} asm_eqp_info;
+int asm_eqp_trial(asm_handle* h, const double* x, const double* lambda, const int32_t* lp_row_state, const int32_t* lp_bound_state,
+                  double radius, const double* nu, double tol_active, const asm_kkt_step_params* par, double* d, double* lam_new,
+                  double* mult_x_U, double* mult_x_L, int32_t* row_state, int32_t* bound_state, asm_eqp_info* info);
+/* The native driver: asm_slp_run_tr with the insertion above - the library calls of SlpEQP.run in activesetmethods_amd/slp.py with
+ * device_eval (asm_slp_run_tr's, asm_eqp_trial, asm_eval_functions after an accepted step).  enabled = 0 is asm_slp_run_tr, bit for bit.
+ * radius0 (finite) and radius_max must be > 0, tol_active >= 0 (else ASM_ERR_ARG).  Needs a model with second derivatives (nlp_kind 0
+ * or 3, as asm_kkt_step).  Not inside a scenario batch.  tr and eqp_info may be NULL. */
+typedef struct {
+    double radius0;            /* initial D_E */
+    double radius_max;         /* cap on D_E */
+    double tol_active;         /* the activity tolerance of step B */
+    int32_t enabled;           /* 0: no step is attempted */
+} asm_slp_eqp_params;
+typedef struct {
+    double  radius;            /* final D_E */
+    int32_t attempts;          /* trials made (= accepted + rejected + the three skipped counts) */
+    int32_t accepted, rejected;
+    int32_t skipped_rows, skipped_dependent, skipped_zero;
+    int32_t cg_iters;          /* conjugate-gradient iterations of all trials */
+    int32_t boundary;          /* trials whose step ended on the boundary of its region */
+} asm_slp_eqp_info;
+int asm_slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* eqp_par, const double* x0,
+                    double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res,
+                    asm_slp_tr_info* tr /* may be NULL */, asm_slp_eqp_info* eqp_info /* may be NULL */);
 
 /* ---- scenario batches: B sub-problems with the same pattern advance through ONE launch sequence on ONE stream --------------------------
  * The reference has no batching (one Optimizer <-> one Model <-> one SLP object, src/MOI_wrapper.jl:1093-1152); these entries are
