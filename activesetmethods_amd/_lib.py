@@ -187,6 +187,8 @@ PROTOTYPES = {
     "asm_batch_slp_run": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), _D, _D, _D, _D, _D, C.POINTER(SlpResult)]),
     "asm_batch_slp_run_tr": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), C.c_double, _D, _D, _D, _D, _D, C.POINTER(SlpResult),
                                        C.POINTER(SlpTrInfo)]),
+    "asm_batch_slp_run_eqp": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), C.c_double, C.POINTER(SlpEqpParams), _D, _D, _D, _D, _D,
+                                        C.POINTER(SlpResult), C.POINTER(SlpTrInfo), C.POINTER(SlpEqpInfo)]),
     "asm_batch_get_stats": (C.c_int, [_P, C.POINTER(BatchStats)]),
     "asm_test_syrk": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, _D, C.c_int]),
     "asm_test_syrk_update": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, C.c_int]),

@@ -86,6 +86,16 @@ def slp_params(par, max_lp_solves=0):
                           float(par.eta), float(par.tau), float(par.min_alpha))
 
 
+NATIVE_ALGORITHMS = ("Line Search", "Trust Region", "SLP-EQP")      # asm_slp_run, asm_slp_run_tr, asm_slp_run_eqp and their batch forms
+
+
+def slp_eqp_params(par):
+    """asm_slp_eqp_params from a `Parameters` object: `eqp_radius` None is `tr_size` (as SlpEQP)."""
+    from . import _lib
+    return _lib.SlpEqpParams(float(par.tr_size if par.eqp_radius is None else par.eqp_radius), float(par.eqp_radius_max), float(par.eqp_tol_active),
+                             int(bool(par.eqp)))
+
+
 class NativeRun:
     """Outcome of one native SLP run (asm_slp_result + the final iterate): the attributes `local_stats` and the tests read from an SlpLS.
     Trust Region (`tr`: asm_slp_tr_info) adds the final radius `delta` and the step counts `accepted`, `rejected`, `shrunk`, `expanded`;
@@ -225,16 +235,21 @@ class HipBatch:
         return np.stack(rows) if differ else None
 
     def slp_run(self, g_L, g_U, x_L, x_U, x0, parameters, max_lp_solves=0, data=None, data_offset=0):
-        """Complete SLP runs (`parameters.algorithm`: Line Search or Trust Region) of `len(g_L)` scenarios (rows of the 2-D arrays): list of
-        NativeRun in scenario order.  `data` [n_scen x count]: scenario s solves with dpar[data_offset, data_offset + count) = data[s]
+        """Complete SLP runs (`parameters.algorithm`: Line Search, Trust Region or SLP-EQP) of `len(g_L)` scenarios (rows of the 2-D arrays):
+        list of NativeRun in scenario order.  `data` [n_scen x count]: scenario s solves with dpar[data_offset, data_offset + count) = data[s]
         (the table stays set for data_gradient); None: every scenario with the setup data."""
         from . import _lib
         f64 = lambda a_: np.ascontiguousarray(a_, np.float64)
         g_L, g_U, x_L, x_U, x0 = map(f64, (g_L, g_U, x_L, x_U, x0))
         S = x0.shape[0]
         assert g_L.shape == (S, self.m) and g_U.shape == (S, self.m) and x_L.shape == (S, self.n) and x_U.shape == (S, self.n) and x0.shape == (S, self.n)
-        if parameters.algorithm not in ("Line Search", "Trust Region"):
-            raise ValueError("the native drivers restate run!(::SlpLS) and run!(::SlpTR) only, not %r" % parameters.algorithm)
+        if parameters.algorithm not in NATIVE_ALGORITHMS:
+            raise ValueError("the native drivers are run!(::SlpLS), run!(::SlpTR) and SLP-EQP, not %r" % parameters.algorithm)
+        if parameters.algorithm == "SLP-EQP":
+            # what SlpEQP and optimize(native=True) ask of a Parameters object: one that they refuse is refused here too, so the same
+            # object selects SLP-EQP on every route or on none (the batch itself always evaluates on the device)
+            if not getattr(parameters, "device_eval", False):
+                raise ValueError("SLP-EQP needs Parameters(device_eval=True): its trial reads what the device evaluator left in HBM")
         if data is not None and np.atleast_2d(data).shape[0] != S:
             raise ValueError("the data table has %d rows for %d scenarios" % (np.atleast_2d(data).shape[0], S))
         if data is not None or self.nlp_kind:
@@ -244,13 +259,17 @@ class HipBatch:
         res = (_lib.SlpResult * S)()
         bounds = (_lib.dptr(g_L), _lib.dptr(g_U), _lib.dptr(x_L), _lib.dptr(x_U), _lib.dptr(x0), self._C.byref(par))
         outs = (_lib.dptr(x), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(g), res)
-        if parameters.algorithm == "Trust Region":
+        tr, eq = [None] * S, [None] * S
+        if parameters.algorithm == "SLP-EQP":
+            tr, eq = (_lib.SlpTrInfo * S)(), (_lib.SlpEqpInfo * S)()
+            ep = slp_eqp_params(parameters)
+            self._check(self._lib.asm_batch_slp_run_eqp(self._b, S, *bounds, float(parameters.tr_size), self._C.byref(ep), *outs, tr, eq))
+        elif parameters.algorithm == "Trust Region":
             tr = (_lib.SlpTrInfo * S)()
             self._check(self._lib.asm_batch_slp_run_tr(self._b, S, *bounds, float(parameters.tr_size), *outs, tr))
         else:
-            tr = [None] * S
             self._check(self._lib.asm_batch_slp_run(self._b, S, *bounds, *outs))
-        return [NativeRun(res[s], x[s], lam[s, :self.m], mU[s], mL[s], g[s, :self.m], tr[s]) for s in range(S)]
+        return [NativeRun(res[s], x[s], lam[s, :self.m], mU[s], mL[s], g[s, :self.m], tr[s], eq[s]) for s in range(S)]
 
     def data_gradient(self, x, lam):
         """asm_batch_data_gradient: d(f - lam' g) / d dpar per scenario (rows of x [n_scen x n], lam [n_scen x m]), each scenario with its

@@ -4475,6 +4475,11 @@ int kk_read_scal(asm_handle* h, unsigned pub) {
         HIPCHK(asmb::sync(h->stream));
         return (int)h->h_scal[0];
     }
+    if (asmb::in_fiber()) {      // scenario batch: the publishing kernel is recorded; the round that launches it ends before this fiber resumes
+        asmb::flush_wait();
+        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) != pub) throw HipError("asm_kkt_solve: the batch round ended without the publishing kernel's sequence word");
+        return (int)h->h_scal[0];
+    }
     const double t0 = Solver::now_ms();
     for (unsigned long spins = 1;; ++spins) {
         if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) break;
@@ -4493,6 +4498,9 @@ int kk_read_scal(asm_handle* h, unsigned pub) {
 // and the factor of S = A A'.
 struct KktFace {
     int64_t nF = 0, nW = 0, nWp = 0, max_iter = 0;      // |F|, |W|, |W| rounded up to 32
+    // |W| rounded up to 64: what the grids over the working rows are sized from (every such kernel returns beyond the nW of its arguments), so
+    // that the launches of scenarios whose working sets differ by a few rows have one shape and merge (Sched::same)
+    int64_t nWg = 0;
     double rtol = 0.0;
     std::vector<int> wl;                                // the working rows, ascending (Mp entries, 0 beyond |W|)
     const double* mask = nullptr;                       // 1.0 on F, 0.0 on B and beyond n (ldn)
@@ -4519,7 +4527,8 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     f.max_iter = par ? par->max_iter : 2 * (f.nF - nW) + 20;
     f.rtol = par ? par->rtol : 1e-12;
     f.nWp = round_up(nW, 32);
-    if (asmb::in_fiber()) throw std::logic_error(me + ": not inside a scenario batch");
+    f.nWg = round_up(nW, 64);
+    // (a slot of a scenario batch has both made before its fiber starts - batch_kkt_prepare: no allocation, no list building in a round)
     hs_prepare(h);
     kk_prepare(h);
     HIPCHK(hipSetDevice(h->device));
@@ -4564,7 +4573,7 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     // wide-block inverses too); the dropped pivots
     if (nW > 0) {
         const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
-        asmb::launch(k_kkt_gather, dim3(asmb::blocks(ldn).x, (unsigned)nW), dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, K.Aw);
+        asmb::launch(k_kkt_gather, dim3(asmb::blocks(ldn).x, (unsigned)f.nWg), dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, K.Aw);
         asmb::launch(k_kktm_gather_t, gt, dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, f.nWp, K.AwT, K.ldT);
         dev.launch_syrk(s, Dev::pick_tile(nW), K.Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, K.fac.S, K.fac.ld, 0, 0);
         dev.diag_prepare(K.fac, (int)nW, 1, 0.0, 0.0);
@@ -4605,7 +4614,7 @@ struct KktOneColumn final : KktOps {
         const HsShared& L = *h->hs_sh;
         asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, n, out);
     }
-    void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nW, 4), dim3(256), s, h->kk.Aw, ldn, v, t, f.nW, ldn); }
+    void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nWg, 4), dim3(256), s, h->kk.Aw, ldn, v, t, f.nW, ldn); }
     void mul_AT(const double* y, double* v, int) override { asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->kk.AwT, ldT, y, v, ldn, f.nW); }
     double* solve_S(const double* b, double* t, int) override {
         double* const out = b == t ? spare : t;
@@ -4701,7 +4710,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     last_active = 0;
     for (int64_t c0 = 0; c0 < nrhs; c0 += cap) {
         const int cols = (int)std::min<int64_t>(cap, nrhs - c0);
-        const dim3 glc(gl.x, (unsigned)cols), grc((unsigned)((nW + 255) / 256), (unsigned)cols), gredc(gred, (unsigned)cols);
+        const dim3 glc(gl.x, (unsigned)cols), grc(asmb::blocks(f.nWg).x, (unsigned)cols), gredc(gred, (unsigned)cols);
         double* st = w.stage;                                    // [ru block | rw block | directions], then the results
         double* back = st + cap * (ldn + ldT + std::max<int64_t>(h->ev_n_dpar, 1));
         auto axpby = [&](double sa, const double* a, double sb, const double* b, const double* sc, double* out) {
@@ -4842,7 +4851,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             }
         }
     }
-    ops.dev.resolve_timing();
+    ops.dev.resolve_timing();      // (a batch slot records no events - its timing level stays 0, as for its LPs: nothing to read inside a fiber)
 }
 }  // namespace
 
@@ -5226,7 +5235,6 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     // (inputs uploaded by asm_sublp_upload leave the evaluator's x, E and gradient in HBM where an earlier evaluation put them)
     if (!h->inputs_ready || !h->inputs_from_eval) throw std::logic_error(me + ": asm_eval_functions first");
     if (std::memcmp(x, h->x_k.data(), n * sizeof(double)) != 0) throw std::logic_error(me + ": x is not the point of the last asm_eval_functions");
-    if (asmb::in_fiber()) throw std::logic_error(me + ": not inside a scenario batch");
     eq_prepare(h);
     HIPCHK(hipSetDevice(h->device));
     std::memset(info, 0, sizeof(*info));
@@ -6469,6 +6477,10 @@ struct SlpRunEQP : SlpRunTR {
 void check_tr_size(double tr_size, const char* what) {
     if (!std::isfinite(tr_size) || !(tr_size > 0.0)) throw std::invalid_argument(std::string(what) + ": tr_size must be finite and > 0");
 }
+void check_eqp_params(const asm_slp_eqp_params& ep, const char* what) {
+    if (!std::isfinite(ep.radius0) || !(ep.radius0 > 0.0) || !(ep.radius_max > 0.0) || !(ep.tol_active >= 0.0))
+        throw std::invalid_argument(std::string(what) + ": radius0 must be finite and > 0, radius_max > 0, tol_active >= 0");
+}
 
 void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const double* x0, double* x_out, double* lambda, double* mult_x_U, double* mult_x_L,
                 double* g_out, asm_slp_result* res, asm_slp_tr_info* tr) {
@@ -6483,7 +6495,6 @@ void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const 
 void slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* ep, const double* x0, double* x_out, double* lambda,
                  double* mult_x_U, double* mult_x_L, double* g_out, asm_slp_result* res, asm_slp_tr_info* tr, asm_slp_eqp_info* eq) {
     hs_check(h, "asm_slp_run_eqp");
-    if (asmb::in_fiber()) throw std::logic_error("asm_slp_run_eqp: not inside a scenario batch");
     if (res) std::memset(res, 0, sizeof(*res));
     SlpRunEQP r(h, *par, tr_size, *ep, res);
     r.run(x0);
@@ -6638,8 +6649,7 @@ int asm_slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, co
     return guarded(h, [&] {
         if (!par || !eqp_par || !x0) throw std::invalid_argument("asm_slp_run_eqp: null pointer");
         check_tr_size(tr_size, "asm_slp_run_eqp");
-        if (!std::isfinite(eqp_par->radius0) || !(eqp_par->radius0 > 0.0) || !(eqp_par->radius_max > 0.0) || !(eqp_par->tol_active >= 0.0))
-            throw std::invalid_argument("asm_slp_run_eqp: radius0 must be finite and > 0, radius_max > 0, tol_active >= 0");
+        check_eqp_params(*eqp_par, "asm_slp_run_eqp");
         slp_run_eqp(h, par, tr_size, eqp_par, x0, x, lambda, mult_x_U, mult_x_L, g, res, tr, eqp_info);
     });
 }
@@ -6904,6 +6914,18 @@ void batch_hs_prepare(asm_batch* b, const char* who) {
     hs_build(b->slots[0], *sh);
     b->hs = std::move(sh);
 }
+// what the SLP-EQP step allocates or builds at its first call on a handle, for the first `count` slots and on the calling thread, before
+// their fibers start: the Hessian workspace on the batch's shared lists, the KKT buffers, the one-column work area and the trial's
+// state.  hipMalloc and the clearing fills stay out of the rounds; a slot that has them keeps them (until the next batch set-up)
+void batch_kkt_prepare(asm_batch* b, int count) {
+    for (int s = 0; s < count; ++s)
+        in_slot("asm_slp_run_eqp", s, [&] {
+            asm_handle* h = b->slots[s];
+            if (!h->hs_ready) hs_attach(h, b->hs.get());
+            (void)kk_work(h, 1);
+            eq_prepare(h);
+        });
+}
 // asm_eval_hessian_lagrangian (v == nullptr: values [n_scen x nnz] into out) or asm_eval_hessian_product (out [n_scen x n]) of n_scen
 // scenarios, each with its data, the slots taking them in index order.  A slot attaches its workspace to the shared lists when it takes
 // its first scenario (a slot that a per-handle call prepared keeps its own lists: same pattern, same bits)
@@ -6952,6 +6974,29 @@ int asm_batch_hessian_product(asm_batch* b, int64_t n_scen, const double* x, con
         batch_hs_prepare(b, "asm_batch_hessian_product");
         if (n_scen < 1 || !x || !v || !out || (b->slots[0]->m > 0 && !lambda)) throw std::invalid_argument("asm_batch_hessian_product: no scenario or a null pointer");
         batch_hessians(b, "asm_batch_hessian_product", n_scen, x, obj_factor, lambda, v, out);
+    });
+}
+
+// n_scen complete SLP runs (SLP-EQP): asm_slp_run_eqp per scenario, the KKT solves and trial steps of the slots merged like their LPs
+int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* x0,
+                          const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* eqp_par, double* x, double* lambda, double* mult_x_U,
+                          double* mult_x_L, double* g, asm_slp_result* res, asm_slp_tr_info* tr, asm_slp_eqp_info* eqp_info) {
+    return guarded(b, [&] {
+        if (!b->setup_done) throw std::logic_error("asm_batch_slp_run_eqp: asm_batch_setup first");
+        if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !eqp_par || !res) throw std::invalid_argument("asm_batch_slp_run_eqp: bad argument");
+        check_tr_size(tr_size, "asm_batch_slp_run_eqp");
+        check_eqp_params(*eqp_par, "asm_batch_slp_run_eqp");
+        check_scen(b, n_scen, "asm_batch_slp_run_eqp");
+        // a model without second derivatives ends here, as in asm_slp_run_eqp, before any fiber starts; the lists are the batch's
+        batch_hs_prepare(b, "asm_batch_slp_run_eqp");
+        HIPCHK(hipSetDevice(b->device));
+        if (eqp_par->enabled) batch_kkt_prepare(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()));
+        const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+        // (asm_sublp_set_bounds at every scenario start forgets the slot's retained active sets and hints: no history for the step to read)
+        batch_slp_runs(b, "asm_slp_run_eqp", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
+            slp_run_eqp(h, par, tr_size, eqp_par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
+                        mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc, tr ? tr + sc : nullptr, eqp_info ? eqp_info + sc : nullptr);
+        });
     });
 }
 

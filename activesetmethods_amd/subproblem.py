@@ -480,8 +480,8 @@ class HipSubOptimizer:
     def slp_run(self, x0, parameters, max_lp_solves=0):
         """One complete SLP run inside the library (asm_slp_run for Line Search, asm_slp_run_tr for Trust Region, asm_slp_run_eqp for
         SLP-EQP, by `parameters.algorithm`) from x0 on this handle; needs eval_setup.  Returns a batch.NativeRun."""
-        from .batch import NativeRun, slp_params
-        if parameters.algorithm not in ("Line Search", "Trust Region", "SLP-EQP"):
+        from .batch import NATIVE_ALGORITHMS, NativeRun, slp_eqp_params, slp_params
+        if parameters.algorithm not in NATIVE_ALGORITHMS:
             raise ValueError("the native drivers are run!(::SlpLS), run!(::SlpTR) and SLP-EQP, not %r" % parameters.algorithm)
         par = slp_params(parameters, max_lp_solves)
         x0 = _f64(x0)
@@ -491,8 +491,7 @@ class HipSubOptimizer:
         tr = None
         if parameters.algorithm == "SLP-EQP":
             tr, eq = _lib.SlpTrInfo(), _lib.SlpEqpInfo()
-            ep = _lib.SlpEqpParams(float(parameters.tr_size if parameters.eqp_radius is None else parameters.eqp_radius), float(parameters.eqp_radius_max),
-                                   float(parameters.eqp_tol_active), int(bool(parameters.eqp)))
+            ep = slp_eqp_params(parameters)
             self._check(self._lib.asm_slp_run_eqp(self._h, C.byref(par), float(parameters.tr_size), C.byref(ep), _lib.dptr(x0), *outs, C.byref(tr), C.byref(eq)))
             return NativeRun(res, x, lam[:self.m], mU, mL, g[:self.m], tr, eq)
         if parameters.algorithm == "Trust Region":

@@ -383,7 +383,7 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  * directions of the data.  All matrices are row-major with one right-hand side per row: RU, DX, DZ are nrhs x n, RW, DLAM nrhs x m, DC
  * nrhs x n_dpar, info has nrhs entries, and row c of DX / DLAM / DZ / info answers row c of RU / RW (of DC).  DZ may be NULL.
  * Validity, argument errors and defaults are asm_kkt_solve's (asm_solution_sensitivity's); nrhs < 1: ASM_ERR_ARG.  par, and the default
- * max_iter = 2 (|F| - |W|) + 20 and rtol = 1e-12, hold for every column.  Not inside a scenario batch.
+ * max_iter = 2 (|F| - |W|) + 20 and rtol = 1e-12, hold for every column.  Per-handle calls: no batch entry runs the block forms (asm_batch_slp_run_eqp runs asm_kkt_step's single column).
  * Per column the mathematics is the method above, step by step.  Steps 1 and 2 - the Hessian values, the Jacobian, the gather, its
  * transposed copy, the rank-K build, the factorisation and the dropped-pivot count - run once per call.  Steps 3 to 6 run on blocks of
  * ASM_KKT_CHUNK columns; the factor and everything of steps 1 and 2 stay across the chunks, so memory is bounded whatever nrhs.
@@ -429,7 +429,7 @@ int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double*
  * boundary of the region where they leave it or meet non-positive curvature.  asm_kkt_step_multi does so for nrhs right-hand sides with
  * a radius each (RADIUS [nrhs]) on one factor, in the lockstep iteration of asm_kkt_solve_multi: with the rows of RU / RW equal it answers
  * a whole ladder of radii, which is what a trust-region driver needs after a rejected step.
- * Validity, argument errors, layouts and "not inside a scenario batch" are asm_kkt_solve's and asm_kkt_solve_multi's.  A radius that is not
+ * Validity, argument errors and layouts are asm_kkt_solve's and asm_kkt_solve_multi's.  A radius that is not
  * > 0 (NaN included) and a normal_share outside (0, 1]: ASM_ERR_ARG.  par == NULL: asm_kkt_solve's defaults and normal_share = 0.8.
  * radius = +INFINITY is allowed and is asm_kkt_solve, bit for bit in dx, dlam, dz and the fields asm_kkt_info has.
  * Method per column (the steps of asm_kkt_solve; both entries run its driver and its kernels):
@@ -553,8 +553,8 @@ int asm_slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, con
  *   for bit, t times the dx asm_kkt_step returns for the same working set, phi0 / phi1 are asm_slp_merit's values.
  * The inputs of the next LP, the retained basis and the active sets are not touched (asm_kkt_step's guarantee).
  * Validity and argument errors are asm_kkt_step's; tol_active not >= 0 or a state outside its value set ({0, 1} for rows, {-1, 0, +1} for
- * bounds): ASM_ERR_ARG; ASM_ERR_STATE unless the handle's last inputs came from asm_eval_functions (not asm_sublp_upload) at this very x;
- * not inside a scenario batch.  The handle works on after any of them. */
+ * bounds): ASM_ERR_ARG; ASM_ERR_STATE unless the handle's last inputs came from asm_eval_functions (not asm_sublp_upload) at this very x.
+ * The handle works on after any of them.  A per-handle call; asm_batch_slp_run_eqp runs it inside the library's scenario batch. */
 typedef struct {
     int32_t status, cg_iters, n_free, n_rows, dropped_pivots, boundary;     /* as asm_kkt_step_info (n_free, n_rows: the face's counts) */
     double res_stat, res_feas, theta, norm_normal, norm_step, model;
@@ -569,7 +569,7 @@ int asm_eqp_trial(asm_handle* h, const double* x, const double* lambda, const in
 /* The native driver: asm_slp_run_tr with the insertion above - the library calls of SlpEQP.run in activesetmethods_amd/slp.py with
  * device_eval (asm_slp_run_tr's, asm_eqp_trial, asm_eval_functions after an accepted step).  enabled = 0 is asm_slp_run_tr, bit for bit.
  * radius0 (finite) and radius_max must be > 0, tol_active >= 0 (else ASM_ERR_ARG).  Needs a model with second derivatives (nlp_kind 0
- * or 3, as asm_kkt_step).  Not inside a scenario batch.  tr and eqp_info may be NULL. */
+ * or 3, as asm_kkt_step).  tr and eqp_info may be NULL.  Its form over a scenario batch is asm_batch_slp_run_eqp. */
 typedef struct {
     double radius0;            /* initial D_E */
     double radius_max;         /* cap on D_E */
@@ -663,6 +663,27 @@ int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const
                          const double* x0, const asm_slp_params* par, double tr_size,
                          double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res,
                          asm_slp_tr_info* tr);
+/* the same with asm_slp_run_eqp per scenario: SLP-EQP in lockstep.  Outputs for scenario s equal, bit for bit, those of asm_slp_run_eqp on
+ * a fresh handle with that scenario's bounds and data and the batch's reference basis columns, whatever slot took the scenario and
+ * whatever that slot solved before (asm_sublp_set_bounds at every scenario start forgets the slot's retained active sets and hints; the
+ * step reads the active set of this run's own last LP).  enabled = 0 is asm_batch_slp_run_tr, bit for bit.
+ *   The slots run the per-handle code as fibers: the Hessian, KKT and trial kernels are recorded and merged like the LP's.  The word the
+ *   host reads per conjugate-gradient round arrives with the round that launches its kernel.  The grids over the working rows are sized
+ *   from |W| rounded up to 64 (the kernels return beyond the |W| of their arguments), so that scenarios whose working sets differ by a
+ *   few rows share a launch; the rank-K build, the factorisation and the substitutions follow |W| through their tile counts and merge
+ *   where those agree.
+ *   Memory: the first call after asm_batch_eval_setup makes, for every slot that will run and before any fiber starts, what asm_kkt_step
+ *   and asm_eqp_trial make at their first call on a handle - dense J (Mp x ldn), Aw (min(m, n) x ldn), its transposed copy, the factor of
+ *   order min(m, n) with its block inverses and the one-column work area - on the batch's shared Hessian lists.  asm_batch_setup and
+ *   asm_batch_eval_setup release it; a batch that never makes this call with enabled != 0 holds none of it.
+ * Errors are asm_slp_run_eqp's and asm_batch_slp_run_tr's: a null batch or required pointer (x0, par, eqp_par, res, the bounds),
+ * n_scen < 1, tr_size / radius0 not finite or not > 0, radius_max not > 0, tol_active not >= 0, nlp_kind 1 or 2 and an n_scen other than
+ * the height of a set scenario table: ASM_ERR_ARG; before asm_batch_setup + asm_batch_eval_setup: ASM_ERR_STATE - all before any fiber
+ * starts.  The batch works on after any of them.  tr and eqp_info [n_scen] may be NULL. */
+int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
+                          const double* x0, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* eqp_par,
+                          double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res,
+                          asm_slp_tr_info* tr /* [n_scen], may be NULL */, asm_slp_eqp_info* eqp_info /* [n_scen], may be NULL */);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
