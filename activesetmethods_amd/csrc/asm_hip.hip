@@ -239,8 +239,8 @@ struct FacBuf {
                                     // operation stops `band` rows below the panel's last column
 };
 
-// The buffers of the KKT solve on a working set, all in the handle's mem_kk and made where first needed after asm_eval_setup (kk_prepare,
-// kk_work); releasing the pool resets the struct.
+// The buffers of the KKT solve on a working set, all in the evaluator's pool and made where first needed after asm_eval_setup (kk_prepare,
+// kk_work); they go with the evaluator (EvalState).
 struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` columns (0: not made): 1 for asm_kkt_solve, KKM_CW for the multi entries
     int64_t cap = 0;
     double *vec = nullptr, *row = nullptr, *dlf = nullptr;      // 14 blocks cap x ldn over the variables, 5 cap x ldT over the working rows, cap x Mp over all rows
@@ -337,6 +337,66 @@ struct HsShared {
     int64_t nnz() const { return (int64_t)rows.size(); }
 };
 
+// The ONLY place that lays out the evaluator's vector block in HBM and its pinned staging buffer.  The block, in doubles:
+//   [ g_L, g_U (m each) | x_L, x_U (n each) | lam (m), mU, mL (n each) | nu (m), ps (2 m), p (n) | jtl (ldn) | rown (Mp) | out (OUT) ]
+// the bounds (ev_write_bounds), the one upload of asm_slp_norms, the one upload of ev_stage_step, J' lambda, the row norms of J, the
+// reduction kernels' results.  Offsets and len() use the problem's own m: a model without rows has empty row vectors, and the block
+// still ends with the whole of `out`, whose widest reader takes TRIALS + 2 <= OUT doubles.
+struct EvLayout {
+    static constexpr int64_t OUT = 16, TRIALS = 8;      // TRIALS merit values and {phi0, D} of a line search; RN_COUNT norms; 3 of a step quality
+    int64_t n = 0, m = 0, ldn = 0, Mp = 0;
+    double* d = nullptr;            // the block (EvalState's pool owns it)
+    int64_t off(int k) const {      // where vector k of the block starts; off(13) is the block's length
+        const int64_t w[13] = {m, m, n, n, m, n, n, m, 2 * m, n, ldn, Mp, OUT};
+        return k == 0 ? 0 : off(k - 1) + w[k - 1];
+    }
+    int64_t len() const { return off(13); }
+    double *g_L() const { return d + off(0); }  double *g_U() const { return d + off(1); }  double *x_L() const { return d + off(2); }  double *x_U() const { return d + off(3); }
+    double *lam() const { return d + off(4); }  double *mU() const { return d + off(5); }   double *mL() const { return d + off(6); }
+    double *nu() const { return d + off(7); }   double *ps() const { return d + off(8); }   double *p() const { return d + off(9); }
+    double *jtl() const { return d + off(10); } double *rown() const { return d + off(11); } double *out() const { return d + off(12); }
+    // The staging buffer holds one image at a time from offset 0: an evaluation [ x (n) | df (n) | E (m) | f ] (asm_eval_constraints: without
+    // df), second derivatives [ x (n) | lam (m) | v (n) ] (asm_eval_data_gradient: without v), the image of lam | mU | mL or of nu | ps | p,
+    // a read-back of `out`.  stage_len() is the maximum over these users.
+    int64_t st_df() const { return n; }     int64_t st_E(bool df) const { return df ? 2 * n : n; }  int64_t st_f(bool df) const { return st_E(df) + m; }
+    int64_t st_lam() const { return n; }    int64_t st_v() const { return n + m; }
+    int64_t stage_len() const { return std::max({st_f(true) + 1, st_v() + n, nu() - lam(), jtl() - nu(), OUT}); }
+};
+
+// Everything asm_eval_setup makes or that is made lazily after it, in one pool and with one lifetime: until the next asm_eval_setup or
+// asm_sublp_setup.  The handle holds a pointer that is null while there is no evaluator (ev_of): no ready flag, no list of fields to reset.
+struct EvalState {
+    // the flattened function store, the NLP block and its tape (nlp_kind ASM_NLP_EXPR: asm_eval_kernels.hip.h), evaluation results in HBM
+    int nlp_kind = 0;
+    int64_t nlp_rows = 0, fn_nnz = 0;
+    FnStore F{};
+    ExprTape X{};
+    double *d_dpar = nullptr, *d_x = nullptr, *d_xt = nullptr, *d_df = nullptr, *d_E = nullptr, *d_Et = nullptr, *d_f = nullptr;
+    EvLayout L;                     // reduction inputs (bounds, lambda, multipliers, nu, slacks, p) and results
+    double* h_stage = nullptr;      // pinned staging, L.stage_len() doubles
+    // NLP-block data (dpar): its length, and the range [dirty_lo, dirty_hi) asm_eval_set_data has written since asm_eval_setup (empty: the
+    // device holds the setup values); expression tapes with constants: the data-gradient occurrence list (asm_eval_data_gradient)
+    int64_t n_dpar = 0, dirty_lo = 0, dirty_hi = 0;
+    int64_t *d_ipar = nullptr, *d_cptr = nullptr;
+    double *d_cocc = nullptr, *d_lam = nullptr, *d_dgrad = nullptr, *h_dgrad = nullptr;
+    // Hessian of the Lagrangian (asm_eval_hessian_*): made by the first of those calls after asm_eval_setup (hs_prepare) from the store and
+    // the tape in HBM.  The pattern and the lists are hs_sh's (null: not prepared): the handle's own (hs_own), or for a batch slot that
+    // asm_batch_hessian_* prepared the batch's; hs_H holds those lists with this handle's four node arrays and hocc; the workspace is in `mem`
+    std::unique_ptr<HsShared> hs_own;
+    const HsShared* hs_sh = nullptr;
+    ExprHess hs_H{};
+    double *d_hs_lam = nullptr, *d_hs_v = nullptr, *d_hs_vals = nullptr, *d_hs_out = nullptr, *h_hs = nullptr;
+    void hs_forget() { hs_H = ExprHess{}; hs_sh = nullptr; }      // its lists are about to go; the workspace stays in `mem`
+    // cross derivatives with respect to the data (asm_eval_data_cross): occurrence list and workspace, made by the first call (cx_prepare)
+    ExprCross cx_C{};
+    int64_t *d_cx_vptr = nullptr, *d_cx_vnode = nullptr;
+    double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr;   // [lam (R) | dc (n_dpar)], [u (n) | w (R)], pinned staging of both and x
+    KktBufs kk;                     // KKT solve on a working set (asm_kkt_solve and the multi entries)
+    int64_t kkm_rounds = 0;         // test seam: lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
+    int kkm_last_active = 0;
+    BufPool mem;                    // declared last: it goes first, while the fields it nulls are alive
+};
+
 // environment knobs of a handle, read once in asm_create (README.md lists them)
 struct HandleKnobs {
     int timing = 1;                 // ASM_HIP_TIMING: 0, 1 or 2, the initial asm_handle::timing
@@ -368,10 +428,10 @@ struct asm_handle {
     std::string err;
     bool setup_done = false, inputs_ready = false;
     bool inputs_from_eval = false;  // the inputs came from asm_eval_functions: the evaluator's x, E and gradient in HBM are those of x_k
-    // owners of the device / pinned buffers below, one per lifetime: the problem skeleton (until the next set-up), the null-space buffers
-    // sized by k (until the dimension outgrows them), the device evaluator (until the next asm_eval_setup)
-    BufPool mem, mem_nsk, mem_ev;
-    BufPool mem_kk;                 // the KKT solve on a working set (asm_kkt_solve): until the next asm_sublp_setup or asm_eval_setup
+    // owners of the device / pinned buffers, one per lifetime: the problem skeleton (until the next set-up), the null-space buffers sized
+    // by k (until the dimension outgrows them), the device evaluator with its own pool (until the next asm_eval_setup or set-up; null: none)
+    BufPool mem, mem_nsk;
+    std::unique_ptr<EvalState> ev;
 
     // ---- problem (subproblem.jl:51-215) ----
     int64_t n = 0, m = 0, nnz = 0, nadj = 0, M = 0, Mp = 0, ldn = 0, ns = 0;
@@ -459,39 +519,7 @@ struct asm_handle {
     int* h_ascnt = nullptr;         // pinned read-back of its counters / scalars
     double* h_asscal = nullptr;
     double *d_Zbuf = nullptr, *d_nsu = nullptr, *d_nsdots = nullptr, *h_nsdots = nullptr;   // null-space active-set method (face_primal_anchored)
-    // ---- device-side evaluator (asm_eval_*): flattened function store, NLP block parameters, evaluation results in HBM
-    bool ev_ready = false;
-    int ev_nlp_kind = 0;
-    int64_t ev_nlp_rows = 0, ev_nlp_nnz = 0, ev_fn_nnz = 0;
-    FnStore ev_F;
-    ExprTape ev_X{};                // nlp_kind ASM_NLP_EXPR: the tape and its workspace (asm_eval_kernels.hip.h)
     std::vector<int64_t> j_row_h, j_col_h;   // j_str as asm_sublp_setup received it (the expression block's pattern is checked against it)
-    int64_t* d_ev_ipar = nullptr;
-    double *d_ev_dpar = nullptr, *d_ev_x = nullptr, *d_ev_xt = nullptr, *d_ev_df = nullptr, *d_ev_E = nullptr, *d_ev_Et = nullptr, *d_ev_f = nullptr;
-    double *d_ev_vecs = nullptr, *h_ev = nullptr;     // reduction inputs (lambda, multipliers, nu, slacks, p, bounds) / pinned staging
-    // NLP-block data (dpar): its length, and the range [dirty_lo, dirty_hi) asm_eval_set_data has written since asm_eval_setup (empty: the
-    // device holds the setup values); expression tapes with constants: the data-gradient occurrence list (asm_eval_data_gradient)
-    int64_t ev_n_dpar = 0, ev_dirty_lo = 0, ev_dirty_hi = 0;
-    int64_t* d_ev_cptr = nullptr;
-    double *d_ev_cocc = nullptr, *d_ev_lam = nullptr, *d_ev_dgrad = nullptr, *h_ev_dgrad = nullptr;
-    // Hessian of the Lagrangian (asm_eval_hessian_*): pattern, lists and workspace, made by the first of those calls after asm_eval_setup
-    // (hs_prepare) from the store and the tape in HBM - a handle that never asks holds none of it.  The pattern and the lists are hs_sh's:
-    // the handle's own (hs_own), or for a batch slot that asm_batch_hessian_* prepared the batch's; the workspace is the handle's (mem_ev)
-    bool hs_ready = false;
-    std::unique_ptr<HsShared> hs_own;
-    const HsShared* hs_sh = nullptr;
-    ExprHess hs_H{};                         // the lists of hs_sh with this handle's four node arrays and hocc
-    double *d_hs_lam = nullptr, *d_hs_v = nullptr, *d_hs_vals = nullptr, *d_hs_out = nullptr, *h_hs = nullptr;
-    // cross derivatives with respect to the data (asm_eval_data_cross): the per-variable occurrence list and the workspace, made by the first
-    // call after asm_eval_setup (cx_prepare) in the evaluator's pool
-    bool cx_ready = false;
-    ExprCross cx_C{};
-    int64_t *d_cx_vptr = nullptr, *d_cx_vnode = nullptr;
-    double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr;   // [lam (R) | dc (n_dpar)], [u (n) | w (R)], pinned staging of both and x
-    // KKT solve on a working set (asm_kkt_solve and the multi entries): everything in mem_kk (KktBufs); the test seam of the multi entries
-    KktBufs kk;
-    int64_t kkm_rounds = 0;         // lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
-    int kkm_last_active = 0;
     bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
     double* h_scal = nullptr;       // pinned scalar read-back; host-mapped: the reduction kernels store the block there themselves (scal_publish)
@@ -538,6 +566,18 @@ namespace {
 // operation was recorded, nothing to wait for
 inline void h2d_done(asm_handle* h) {
     if (!asmb::in_fiber()) HIPCHK(asmb::sync(h->stream));
+}
+// the handle's evaluator for entry `who`
+EvalState& ev_of(const asm_handle* h, const char* who) {
+    if (!h->ev) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
+    return *h->ev;
+}
+// the reductions' copy of the handle's bounds into the block of L
+void ev_write_bounds(const asm_handle* h, const EvLayout& L) {
+    HIPCHK(asmb::copy(L.g_L(), h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.g_U(), h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.x_L(), h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.x_U(), h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
 }
 
 // buffers of one Cholesky factor of order <= N (pitch = N rounded up to 32) with the block inverses of the substitution kernels, from `pool`
@@ -3083,8 +3123,7 @@ int row_kind(double lb, double ub) {
 
 // releases every buffer of the handle and resets the state that describes them
 void free_device(asm_handle* h) {
-    h->mem.release(); h->mem_nsk.release(); h->mem_ev.release(); h->mem_kk.release();
-    h->kk = KktBufs();
+    h->mem.release(); h->mem_nsk.release(); h->ev.reset();
     h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
     h->ahTg_valid = false;
     h->col_capable = h->ahT_valid = h->nzT_valid = false;
@@ -3092,9 +3131,6 @@ void free_device(asm_handle* h) {
     h->ns_cap = false; h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0; h->ns_npairs = 0;
     h->ns_f0 = FacBuf(); h->ns_fN = FacBuf(); h->ns_fC = FacBuf(); h->test_fac = FacBuf();
     h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
-    h->ev_ready = false;
-    h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
-    h->cx_ready = false; h->cx_C = ExprCross{};
 }
 
 // forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
@@ -3391,12 +3427,7 @@ void do_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, const 
     HIPCHK(hipSetDevice(h->device));
     h->c_lb.assign(c_lb, c_lb + h->m); h->c_ub.assign(c_ub, c_ub + h->m);
     h->v_lb.assign(v_lb, v_lb + h->n); h->v_ub.assign(v_ub, v_ub + h->n);
-    if (h->ev_ready) {              // the reductions' copy of the bounds
-        HIPCHK(asmb::copy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(asmb::copy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m + h->n, h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if (h->ev) ev_write_bounds(h, h->ev->L);
     // the retained working sets and the basis Z belong to the old instance; the basis COLUMNS of the null-space form are kept - the
     // pattern is the same, and a set that no longer spans null(A_EF) is detected and re-selected by the next LP (Solver::ns_setup)
     h->last = ActiveSet();
@@ -3651,40 +3682,50 @@ void in_slot(const char* step, int slot, F&& fn) {
 // kernels of one evaluation at the point in `xd`: values into Ed (m), objective into fd, optionally gradient / Jacobian values
 // `ntrial` > 1 (values only): the trial points of a batched line search, xd / Ed / fd advancing by ldx / ldE / 1 per point
 void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool full, int ntrial = 1, int64_t ldx = 0, int64_t ldE = 0) {
-    const FnStore& F = h->ev_F;
+    const EvalState& e = *h->ev;
+    const FnStore& F = e.F;
     const unsigned nt = (unsigned)ntrial;
     if (F.n_rows > 0)
         asmb::launch(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), h->stream, F, xd, Ed, h->d_dE, full ? 1 : 0, ldx, ldE);
-    const ExprTape& X = h->ev_X;
-    const bool expr_obj = h->ev_nlp_kind == ASM_NLP_EXPR && X.T > 0;     // the expression objective replaces the store's objective row
+    const ExprTape& X = e.X;
+    const bool expr_obj = e.nlp_kind == ASM_NLP_EXPR && X.T > 0;     // the expression objective replaces the store's objective row
     if (!expr_obj) {
         asmb::launch(k_fn_objective, dim3(nt), dim3(256), h->stream, F, xd, fd, ldx);
-        if (full) asmb::launch(k_fn_gradient, asmb::blocks(h->n), dim3(256), h->stream, F, xd, h->d_ev_df);
+        if (full) asmb::launch(k_fn_gradient, asmb::blocks(h->n), dim3(256), h->stream, F, xd, e.d_df);
     }
-    if (h->ev_nlp_kind == ASM_NLP_EXPR) {
+    if (e.nlp_kind == ASM_NLP_EXPR) {
         if (X.R > 0)
-            asmb::launch(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), h->stream, X, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
+            asmb::launch(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), h->stream, X, xd, Ed, h->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
         if (expr_obj) {
             asmb::launch(k_nlp_expr_terms, dim3((unsigned)((X.T + 255) / 256), nt), dim3(256), h->stream, X, xd, full ? 1 : 0, ldx);
             asmb::launch(k_nlp_expr_objective, dim3(nt), dim3(64), h->stream, X, F.objective_scale, fd);
-            if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->n), dim3(256), h->stream, X, F.objective_scale, h->d_ev_df);
+            if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->n), dim3(256), h->stream, X, F.objective_scale, e.d_df);
         }
-    } else if (h->ev_nlp_kind == 1) {
-        const int64_t nl = h->ev_nlp_rows / 4;
-        asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, h->d_ev_ipar, h->d_ev_dpar, xd, Ed, h->d_dE, F.n_rows, h->ev_fn_nnz,
-                     full ? 1 : 0, ldx, ldE);
-    } else if (h->ev_nlp_kind == 2) {
-        asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((h->ev_nlp_rows + 3) / 4), nt), dim3(256), h->stream, h->d_ev_dpar, h->ev_nlp_rows, h->n, xd, Ed, h->d_dE, F.n_rows,
-                     h->ev_fn_nnz, full ? 1 : 0, ldx, ldE);
+    } else if (e.nlp_kind == 1) {
+        const int64_t nl = e.nlp_rows / 4;
+        asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, e.d_ipar, e.d_dpar, xd, Ed, h->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
+    } else if (e.nlp_kind == 2) {
+        asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((e.nlp_rows + 3) / 4), nt), dim3(256), h->stream, e.d_dpar, e.nlp_rows, h->n, xd, Ed, h->d_dE, F.n_rows,
+                     e.fn_nnz, full ? 1 : 0, ldx, ldE);
     }
 }
-SlpVecs ev_vecs(asm_handle* h, const double* lam, const double* mU, const double* mL, const double* jtl, const double* rown) {
-    SlpVecs V;
-    double* b = h->d_ev_vecs;      // layout: g_L, g_U (m each) | x_L, x_U (n each), written by asm_eval_setup
-    V.g_L = b; V.g_U = b + h->m; V.x_L = b + 2 * h->m; V.x_U = b + 2 * h->m + h->n;
-    V.E = h->d_ev_E; V.x = h->d_ev_x; V.df = h->d_ev_df; V.lam = lam; V.mU = mU; V.mL = mL; V.jtl = jtl; V.rown = rown;
-    V.n = h->n; V.m = h->m;
+// the evaluation results and the bounds for the reduction kernels; norms: also what k_slp_norms alone reads
+SlpVecs ev_vecs(const EvalState& e, bool norms = false) {
+    const EvLayout& L = e.L;
+    SlpVecs V{};
+    V.g_L = L.g_L(); V.g_U = L.g_U(); V.x_L = L.x_L(); V.x_U = L.x_U();
+    V.E = e.d_E; V.x = e.d_x; V.df = e.d_df; V.n = L.n; V.m = L.m;
+    if (norms) { V.lam = L.lam(); V.mU = L.mU(); V.mL = L.mL(); V.jtl = L.jtl(); V.rown = L.rown(); }
     return V;
+}
+// nu | the slacks (2 per row, as asm_sublp_solve returns them) | p of a step into the block: one copy.  Returns the evaluator
+const EvalState& ev_stage_step(asm_handle* h, const double* nu, const double* p_slack, const double* p) {
+    const EvLayout& L = h->ev->L;
+    double* st = h->ev->h_stage;    // the image of the block from nu on
+    if (L.m) { std::memcpy(st, nu, L.m * sizeof(double)); std::memcpy(st + (L.ps() - L.nu()), p_slack, 2 * L.m * sizeof(double)); }
+    std::memcpy(st + (L.p() - L.nu()), p, L.n * sizeof(double));
+    HIPCHK(asmb::copy_async(L.nu(), st, (L.jtl() - L.nu()) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return *h->ev;
 }
 }  // namespace
 
@@ -3995,52 +4036,42 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     ExprHost xh;
     if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
     HIPCHK(hipSetDevice(h->device));
-    BufPool& P = h->mem_ev;
-    P.release();
-    h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; h->hs_own.reset();
-    h->cx_ready = false; h->cx_C = ExprCross{};
-    h->mem_kk.release(); h->kk = KktBufs();
-    FnStore& F = h->ev_F;
+    h->ev.reset();                  // the old evaluator goes before the new one is made; a failure below leaves the handle without one
+    auto e = std::make_unique<EvalState>();
+    BufPool& P = e->mem;
+    FnStore& F = e->F;
     F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
     const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
     P.upload(F.aff_ptr, aff_ptr, n_rows + 2); P.upload(F.aff_var, aff_var, na); P.upload(F.aff_coef, aff_coef, na);
     P.upload(F.quad_ptr, quad_ptr, n_rows + 2); P.upload(F.q_v1, q_v1, nq); P.upload(F.q_v2, q_v2, nq); P.upload(F.q_coef, q_coef, nq);
     P.upload(F.constant, constant, n_rows + 1); P.upload(F.jac_off, jac_off, n_rows + 1);
     P.upload(F.g_ptr, g_ptr, h->n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
-    h->ev_nlp_kind = nlp_kind; h->ev_nlp_rows = nlp_rows; h->ev_nlp_nnz = nlp_nnz; h->ev_fn_nnz = fn_nnz;
-    P.upload(h->d_ev_ipar, nlp_ipar, n_ipar);
-    P.upload(h->d_ev_dpar, nlp_dpar, n_dpar);
-    h->ev_n_dpar = n_dpar; h->ev_dirty_lo = h->ev_dirty_hi = 0;
-    P.alloc(h->d_ev_x, 0);
-    const int64_t n = h->n, m = std::max<int64_t>(h->m, 1);
-    P.zeroed(h->d_ev_x, n); P.zeroed(h->d_ev_xt, 8 * round_up(n, 32)); P.zeroed(h->d_ev_df, n); P.zeroed(h->d_ev_E, m);
-    P.zeroed(h->d_ev_Et, 8 * round_up(std::max<int64_t>(m, 1), 32));
-    P.zeroed(h->d_ev_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
-    h->ev_X = ExprTape{};
+    e->nlp_kind = nlp_kind; e->nlp_rows = nlp_rows; e->fn_nnz = fn_nnz; e->n_dpar = n_dpar;
+    P.upload(e->d_ipar, nlp_ipar, n_ipar); P.upload(e->d_dpar, nlp_dpar, n_dpar);
+    const int64_t n = h->n, m = h->m;      // (the pool makes an empty vector one element long)
+    P.zeroed(e->d_x, n); P.zeroed(e->d_xt, 8 * round_up(n, 32)); P.zeroed(e->d_df, n); P.zeroed(e->d_E, m);
+    P.zeroed(e->d_Et, 8 * round_up(std::max<int64_t>(m, 1), 32)); P.zeroed(e->d_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
     if (nlp_kind == ASM_NLP_EXPR) {
-        ExprTape& X = h->ev_X;
+        ExprTape& X = e->X;
         X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = h->n;
         P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
         P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
         P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
-        X.cst = h->d_ev_dpar;
+        X.cst = e->d_dpar;
         // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
         P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
         P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[h->n]);
         if (!xh.cptr.empty()) {     // the data gradient's occurrence list, multipliers of the rows and result (tapes with constants only)
-            P.upload(h->d_ev_cptr, xh.cptr.data(), n_dpar + 1);
-            P.zeroed(h->d_ev_cocc, xh.cptr[n_dpar]); P.zeroed(h->d_ev_lam, xh.R); P.zeroed(h->d_ev_dgrad, n_dpar);
-            P.alloc(h->h_ev_dgrad, n_dpar, BufPool::PINNED);
+            P.upload(e->d_cptr, xh.cptr.data(), n_dpar + 1);
+            P.zeroed(e->d_cocc, xh.cptr[n_dpar]); P.zeroed(e->d_lam, xh.R); P.zeroed(e->d_dgrad, n_dpar);
+            P.alloc(e->h_dgrad, n_dpar, BufPool::PINNED);
         }
     }
-    // bounds for the reductions + staging area: [g_L, g_U, x_L, x_U | lam, mU, mL, nu, ps(2m), p, jtl(ldn), rown(Mp), out(8)]
-    P.zeroed(h->d_ev_vecs, 2 * m + 2 * n + 2 * m + 2 * n + 2 * m + n + h->ldn + h->Mp + 16);
-    HIPCHK(asmb::copy(h->d_ev_vecs, h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(asmb::copy(h->d_ev_vecs + h->m, h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m, h->v_lb.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(asmb::copy(h->d_ev_vecs + 2 * h->m + n, h->v_ub.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    if (!h->h_ev) h->mem.alloc(h->h_ev, 4 * (n + m) + 64, BufPool::PINNED);
-    h->ev_ready = true;
+    e->L = EvLayout{n, m, h->ldn, h->Mp};      // the reductions' block with the bounds in it, and the staging buffer
+    P.zeroed(e->L.d, e->L.len());
+    ev_write_bounds(h, e->L);
+    P.alloc(e->h_stage, e->L.stage_len(), BufPool::PINNED);
+    h->ev = std::move(e);
 }
 
 int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const int64_t* aff_var, const double* aff_coef, const int64_t* quad_ptr,
@@ -4056,20 +4087,20 @@ int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const 
 // eval_functions! (slp.jl:186-191) on the device + what asm_sublp_upload does with the results: dE stays in HBM
 static void do_eval_functions(asm_handle* h, const double* x, double* f, double* df, double* E) {
     if (!x || !f || !df || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_functions: null pointer");
-    if (!h->ev_ready) throw std::logic_error("asm_eval_functions: asm_eval_setup first");
+    EvalState& e = ev_of(h, "asm_eval_functions");
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n, m = h->m;
-    std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(asmb::copy_async(h->d_ev_x, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    ev_launch(h, h->d_ev_x, h->d_ev_E, h->d_ev_f, true);
-    double* st = h->h_ev + n;
-    HIPCHK(asmb::copy_async(st, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (m) HIPCHK(asmb::copy_async(st + n, h->d_ev_E, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(asmb::copy_async(st + n + m, h->d_ev_f, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double *st = e.h_stage, *s_df = st + e.L.st_df(), *s_E = st + e.L.st_E(true), *s_f = st + e.L.st_f(true);
+    std::memcpy(st, x, n * sizeof(double));
+    HIPCHK(asmb::copy_async(e.d_x, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    ev_launch(h, e.d_x, e.d_E, e.d_f, true);
+    HIPCHK(asmb::copy_async(s_df, e.d_df, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (m) HIPCHK(asmb::copy_async(s_E, e.d_E, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::copy_async(s_f, e.d_f, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
-    std::memcpy(df, st, n * sizeof(double));
-    if (m) std::memcpy(E, st + n, m * sizeof(double));
-    *f = st[n + m];
+    std::memcpy(df, s_df, n * sizeof(double));
+    if (m) std::memcpy(E, s_E, m * sizeof(double));
+    *f = *s_f;
     h->df.assign(df, df + n); h->E.assign(E, E + m); h->x_k.assign(x, x + n);
     h->f = *f;
     h->inputs_ready = true;
@@ -4083,41 +4114,42 @@ int asm_eval_functions(asm_handle* h, const double* x, double* f, double* df, do
 
 // dpar[offset, offset + count) := values on the device: every later evaluation reads it, nothing else changes
 static void do_set_data(asm_handle* h, int64_t offset, int64_t count, const double* values) {
-    if (!h->ev_ready) throw std::logic_error("asm_eval_set_data: asm_eval_setup first");
-    if (!values || offset < 0 || count < 0 || offset > h->ev_n_dpar - count)
-        throw std::invalid_argument("asm_eval_set_data: null pointer or a range outside [0, n_dpar = " + std::to_string(h->ev_n_dpar) + ")");
+    EvalState& e = ev_of(h, "asm_eval_set_data");
+    if (!values || offset < 0 || count < 0 || offset > e.n_dpar - count)
+        throw std::invalid_argument("asm_eval_set_data: null pointer or a range outside [0, n_dpar = " + std::to_string(e.n_dpar) + ")");
     if (count == 0) return;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(asmb::copy_async(h->d_ev_dpar + offset, values, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(e.d_dpar + offset, values, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h2d_done(h);
-    if (h->ev_dirty_hi == h->ev_dirty_lo) { h->ev_dirty_lo = offset; h->ev_dirty_hi = offset + count; }
-    else { h->ev_dirty_lo = std::min(h->ev_dirty_lo, offset); h->ev_dirty_hi = std::max(h->ev_dirty_hi, offset + count); }
+    if (e.dirty_hi == e.dirty_lo) { e.dirty_lo = offset; e.dirty_hi = offset + count; }
+    else { e.dirty_lo = std::min(e.dirty_lo, offset); e.dirty_hi = std::max(e.dirty_hi, offset + count); }
 }
 
 // out[c] = d(f - lambda' g) / d dpar[c] at x for an expression block (k_nlp_expr_const_adj + k_nlp_expr_data_gather); the inputs of the next
 // LP are not touched (x goes where asm_eval_constraints puts its trial point)
 static void do_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
-    if (!h->ev_ready) throw std::logic_error("asm_eval_data_gradient: asm_eval_setup first");
-    if (h->ev_nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument("asm_eval_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
-    if (!x || (h->m > 0 && !lambda) || (h->ev_n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
-    const int64_t n = h->n, nd = h->ev_n_dpar;
-    if (!h->d_ev_cocc) {            // no CONST node: nothing depends on the data
+    EvalState& e = ev_of(h, "asm_eval_data_gradient");
+    if (e.nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument("asm_eval_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
+    if (!x || (h->m > 0 && !lambda) || (e.n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
+    const int64_t n = h->n, nd = e.n_dpar;
+    if (!e.d_cocc) {            // no CONST node: nothing depends on the data
         for (int64_t c = 0; c < nd; ++c) out[c] = 0.0;
         return;
     }
     HIPCHK(hipSetDevice(h->device));
-    const ExprTape& X = h->ev_X;
-    std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const ExprTape& X = e.X;
+    double *st = e.h_stage, *s_lam = st + e.L.st_lam();
+    std::memcpy(st, x, n * sizeof(double));
+    HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (X.R > 0) {
-        std::memcpy(h->h_ev + n, lambda + h->ev_F.n_rows, X.R * sizeof(double));
-        HIPCHK(asmb::copy_async(h->d_ev_lam, h->h_ev + n, X.R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        std::memcpy(s_lam, lambda + e.F.n_rows, X.R * sizeof(double));
+        HIPCHK(asmb::copy_async(e.d_lam, s_lam, X.R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    asmb::launch(k_nlp_expr_const_adj, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, h->d_ev_xt, h->d_ev_lam, h->ev_F.objective_scale, h->d_ev_cocc);
-    asmb::launch(k_nlp_expr_data_gather, asmb::blocks(nd), dim3(256), h->stream, h->d_ev_cptr, h->d_ev_cocc, nd, h->d_ev_dgrad);
-    HIPCHK(asmb::copy_async(h->h_ev_dgrad, h->d_ev_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    asmb::launch(k_nlp_expr_const_adj, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, e.d_xt, e.d_lam, e.F.objective_scale, e.d_cocc);
+    asmb::launch(k_nlp_expr_data_gather, asmb::blocks(nd), dim3(256), h->stream, e.d_cptr, e.d_cocc, nd, e.d_dgrad);
+    HIPCHK(asmb::copy_async(e.h_dgrad, e.d_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
-    std::memcpy(out, h->h_ev_dgrad, nd * sizeof(double));
+    std::memcpy(out, e.h_dgrad, nd * sizeof(double));
 }
 
 // ---- Hessian of the Lagrangian (include/asm_hip.h, "Hessian of the Lagrangian")
@@ -4180,9 +4212,9 @@ void hs_row_pairs(const int32_t* op, const int64_t* a, const int64_t* b, int64_t
 // pattern, seed threads, occurrence and product lists of h's store and tape (downloaded with blocking copies: not inside a batch fiber) into sh
 void hs_build(const asm_handle* h, HsShared& sh) {
     HIPCHK(hipSetDevice(h->device));
-    const FnStore& F = h->ev_F;
-    const ExprTape& X = h->ev_X;
-    const bool expr = h->ev_nlp_kind == ASM_NLP_EXPR;
+    const FnStore& F = h->ev->F;
+    const ExprTape& X = h->ev->X;
+    const bool expr = h->ev->nlp_kind == ASM_NLP_EXPR;
     const int64_t nr = F.n_rows, n = h->n;
     // 1. function store: the objective row's quadratic terms (unless the block has the objective), then the rows' in row order
     const std::vector<int64_t> qptr = hs_download(F.quad_ptr, nr + 2);
@@ -4260,33 +4292,32 @@ void hs_build(const asm_handle* h, HsShared& sh) {
 // the handle's own part on the lists of sh: the four node arrays, hocc and the value / product vectors.  Inside a batch fiber the clearing
 // fills are recorded with the slot's other operations
 void hs_attach(asm_handle* h, const HsShared* sh) {
-    BufPool& M = h->mem_ev;
+    EvalState& e = *h->ev;
+    BufPool& M = e.mem;
     const bool rec = asmb::in_fiber();
     auto zeroed = [&](double*& f, int64_t count) { if (rec) M.zeroed(f, count, h->stream); else M.zeroed(f, count); };
-    ExprHess& H = h->hs_H;
-    H = ExprHess{};
+    ExprHess& H = e.hs_H;          // (empty: the state is new, or hs_forget cleared it)
     H.S = sh->S;
     if (sh->S > 0) {
         H.srow = sh->srow; H.svar = sh->svar; H.woff = sh->woff; H.optr = sh->optr; H.ovar = sh->ovar;
         zeroed(H.val, sh->wnodes); zeroed(H.tval, sh->wnodes); zeroed(H.adj, sh->wnodes); zeroed(H.tadj, sh->wnodes); zeroed(H.hocc, sh->nocc);
     }
-    zeroed(h->d_hs_lam, h->m); zeroed(h->d_hs_v, h->n); zeroed(h->d_hs_vals, sh->nnz()); zeroed(h->d_hs_out, h->n);
-    M.alloc(h->h_hs, std::max(sh->nnz(), h->n), BufPool::PINNED);
-    h->hs_sh = sh;
-    h->hs_ready = true;
+    zeroed(e.d_hs_lam, h->m); zeroed(e.d_hs_v, h->n); zeroed(e.d_hs_vals, sh->nnz()); zeroed(e.d_hs_out, h->n);
+    M.alloc(e.h_hs, std::max(sh->nnz(), h->n), BufPool::PINNED);
+    e.hs_sh = sh;
 }
 // once per asm_eval_setup, at the first Hessian call of a handle
 void hs_prepare(asm_handle* h) {
-    if (h->hs_ready) return;
+    if (h->ev->hs_sh) return;
     HIPCHK(hipSetDevice(h->device));
     auto own = std::make_unique<HsShared>();
     hs_build(h, *own);
-    h->hs_own = std::move(own);
-    hs_attach(h, h->hs_own.get());
+    h->ev->hs_own = std::move(own);
+    hs_attach(h, h->ev->hs_own.get());
 }
 void hs_check(const asm_handle* h, const char* who) {
-    if (!h->ev_ready) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
-    if (h->ev_nlp_kind != ASM_NLP_NONE && h->ev_nlp_kind != ASM_NLP_EXPR)
+    const EvalState& e = ev_of(h, who);
+    if (e.nlp_kind != ASM_NLP_NONE && e.nlp_kind != ASM_NLP_EXPR)
         throw std::invalid_argument(std::string(who) + ": second derivatives exist for the function store alone (nlp_kind 0) or with an expression block (nlp_kind 3)");
 }
 // the values at (x, obj_factor, lambda) into d_hs_vals; with v also H v into d_hs_out.  x goes where asm_eval_constraints puts its trial
@@ -4294,26 +4325,27 @@ void hs_check(const asm_handle* h, const char* who) {
 void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v) {
     hs_prepare(h);
     HIPCHK(hipSetDevice(h->device));
-    const HsShared& L = *h->hs_sh;
+    EvalState& e = *h->ev;
+    const HsShared& L = *e.hs_sh;
     const int64_t n = h->n, m = h->m, nnz = L.nnz(), nfn = L.nfn;
-    const FnStore& F = h->ev_F;
-    std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double *st = e.h_stage, *s_lam = st + e.L.st_lam(), *s_v = st + e.L.st_v();
+    std::memcpy(st, x, n * sizeof(double));
+    HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (m > 0) {
-        std::memcpy(h->h_ev + n, lambda, m * sizeof(double));
-        HIPCHK(asmb::copy_async(h->d_hs_lam, h->h_ev + n, m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        std::memcpy(s_lam, lambda, m * sizeof(double));
+        HIPCHK(asmb::copy_async(e.d_hs_lam, s_lam, m * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     if (v) {
-        std::memcpy(h->h_ev + n + m, v, n * sizeof(double));
-        HIPCHK(asmb::copy_async(h->d_hs_v, h->h_ev + n + m, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        std::memcpy(s_v, v, n * sizeof(double));
+        HIPCHK(asmb::copy_async(e.d_hs_v, s_v, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    const double wobj = obj_factor * F.objective_scale;
-    if (nfn > 0) asmb::launch(k_fn_hessian, asmb::blocks(nfn), dim3(256), h->stream, L.qterm, L.qrow, F.q_coef, h->d_hs_lam, wobj, nfn, h->d_hs_vals);
-    if (h->hs_H.S > 0) {
-        asmb::launch(k_nlp_expr_hess, asmb::blocks(h->hs_H.S), dim3(256), h->stream, h->ev_X, h->hs_H, h->d_ev_xt, h->d_hs_lam + F.n_rows, wobj);
-        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, h->hs_H.hocc, nnz - nfn, h->d_hs_vals + nfn);
+    const double wobj = obj_factor * e.F.objective_scale;
+    if (nfn > 0) asmb::launch(k_fn_hessian, asmb::blocks(nfn), dim3(256), h->stream, L.qterm, L.qrow, e.F.q_coef, e.d_hs_lam, wobj, nfn, e.d_hs_vals);
+    if (e.hs_H.S > 0) {
+        asmb::launch(k_nlp_expr_hess, asmb::blocks(e.hs_H.S), dim3(256), h->stream, e.X, e.hs_H, e.d_xt, e.d_hs_lam + e.F.n_rows, wobj);
+        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, e.hs_H.hocc, nnz - nfn, e.d_hs_vals + nfn);
     }
-    if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, L.pptr, L.pent, L.poth, h->d_hs_vals, h->d_hs_v, n, h->d_hs_out);
+    if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, L.pptr, L.pent, L.poth, e.d_hs_vals, e.d_hs_v, n, e.d_hs_out);
 }
 void hs_pattern(const HsShared& sh, int64_t* nnz, int64_t* rows, int64_t* cols) {
     *nnz = sh.nnz();
@@ -4323,9 +4355,9 @@ void hs_pattern(const HsShared& sh, int64_t* nnz, int64_t* rows, int64_t* cols) 
     }
 }
 void hs_read(asm_handle* h, const double* dev, int64_t count, double* out) {
-    if (count > 0) HIPCHK(asmb::copy_async(h->h_hs, dev, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (count > 0) HIPCHK(asmb::copy_async(h->ev->h_hs, dev, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
-    if (count > 0) std::memcpy(out, h->h_hs, count * sizeof(double));
+    if (count > 0) std::memcpy(out, h->ev->h_hs, count * sizeof(double));
 }
 }  // namespace
 
@@ -4333,21 +4365,21 @@ static void do_hessian_structure(asm_handle* h, int64_t* nnz, int64_t* rows, int
     hs_check(h, "asm_eval_hessian_structure");
     if (!nnz || (rows == nullptr) != (cols == nullptr)) throw std::invalid_argument("asm_eval_hessian_structure: null pointer");
     hs_prepare(h);
-    hs_pattern(*h->hs_sh, nnz, rows, cols);
+    hs_pattern(*h->ev->hs_sh, nnz, rows, cols);
 }
 static void do_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values) {
     hs_check(h, "asm_eval_hessian_lagrangian");
     if (!x || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
     hs_prepare(h);
-    if (h->hs_sh->nnz() > 0 && !values) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
+    if (h->ev->hs_sh->nnz() > 0 && !values) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
     hs_launch(h, x, obj_factor, lambda, nullptr);
-    hs_read(h, h->d_hs_vals, h->hs_sh->nnz(), values);
+    hs_read(h, h->ev->d_hs_vals, h->ev->hs_sh->nnz(), values);
 }
 static void do_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out) {
     hs_check(h, "asm_eval_hessian_product");
     if (!x || !v || !out || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_product: null pointer");
     hs_launch(h, x, obj_factor, lambda, v);
-    hs_read(h, h->d_hs_out, h->n, out);
+    hs_read(h, h->ev->d_hs_out, h->n, out);
 }
 
 // ---- cross derivatives with respect to the data (include/asm_hip.h, "Cross derivatives of an expression block")
@@ -4355,9 +4387,10 @@ namespace {
 // once per asm_eval_setup, at the first asm_eval_data_cross: the VAR nodes of every variable in (row, then term) order, node descending
 // inside a row or term, and the workspace (blocking copies: not inside a batch fiber)
 void cx_prepare(asm_handle* h) {
-    if (h->cx_ready) return;
+    EvalState& e = *h->ev;
+    if (e.h_cx) return;            // (the last buffer it makes)
     HIPCHK(hipSetDevice(h->device));
-    const ExprTape& X = h->ev_X;
+    const ExprTape& X = e.X;
     const int64_t n = h->n, nt = X.R + X.T;
     const std::vector<int64_t> ptr = hs_download(X.ptr, nt + 1), ta = hs_download(X.a, X.L);
     const std::vector<int32_t> top = hs_download(X.op, X.L);
@@ -4369,47 +4402,45 @@ void cx_prepare(asm_handle* h) {
     for (int64_t t = 0; t < nt; ++t)
         for (int64_t k = ptr[t + 1] - 1; k >= ptr[t]; --k)
             if (top[k] == ASM_OP_VAR) vnode[fill[ta[k]]++] = k;
-    BufPool& M = h->mem_ev;
-    ExprCross& C = h->cx_C;
-    C = ExprCross{};
-    M.upload(h->d_cx_vptr, vptr.data(), n + 1); M.upload(h->d_cx_vnode, vnode.data(), vptr[n]);
-    C.vptr = h->d_cx_vptr; C.vnode = h->d_cx_vnode;
+    BufPool& M = e.mem;
+    ExprCross& C = e.cx_C;
+    M.upload(e.d_cx_vptr, vptr.data(), n + 1); M.upload(e.d_cx_vnode, vnode.data(), vptr[n]);
+    C.vptr = e.d_cx_vptr; C.vnode = e.d_cx_vnode;
     M.zeroed(C.val, X.L); M.zeroed(C.tval, X.L); M.zeroed(C.adj, X.L); M.zeroed(C.tadj, X.L); M.zeroed(C.vocc, X.L);
-    M.zeroed(h->d_cx_in, X.R + h->ev_n_dpar); M.zeroed(h->d_cx_out, n + X.R);
-    M.alloc(h->h_cx, 2 * (n + X.R) + h->ev_n_dpar, BufPool::PINNED);
-    h->cx_ready = true;
+    M.zeroed(e.d_cx_in, X.R + e.n_dpar); M.zeroed(e.d_cx_out, n + X.R);
+    M.alloc(e.h_cx, 2 * (n + X.R) + e.n_dpar, BufPool::PINNED);
 }
 void cx_check(const asm_handle* h, const char* who) {
-    if (!h->ev_ready) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
-    if (h->ev_nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument(std::string(who) + ": cross derivatives exist for expression blocks (nlp_kind 3) only");
+    const EvalState& e = ev_of(h, who);
+    if (e.nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument(std::string(who) + ": cross derivatives exist for expression blocks (nlp_kind 3) only");
 }
 }  // namespace
 // u = d/dc (grad_x L) . dc, w = (dg/dc) . dc at (x, lambda), L = f - lambda' g (k_nlp_expr_cross + k_nlp_expr_cross_gather); the inputs of
 // the next LP are not touched (x goes where asm_eval_constraints puts its trial point)
 static void do_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w) {
     cx_check(h, "asm_eval_data_cross");
-    if (!x || !u || (h->m > 0 && (!lambda || !w)) || (h->ev_n_dpar > 0 && !dc)) throw std::invalid_argument("asm_eval_data_cross: null pointer");
-    const int64_t n = h->n, m = h->m, nd = h->ev_n_dpar;
+    EvalState& e = *h->ev;
+    if (!x || !u || (h->m > 0 && (!lambda || !w)) || (e.n_dpar > 0 && !dc)) throw std::invalid_argument("asm_eval_data_cross: null pointer");
+    const int64_t n = h->n, m = h->m, nd = e.n_dpar;
     for (int64_t j = 0; j < n; ++j) u[j] = 0.0;
     for (int64_t i = 0; i < m; ++i) w[i] = 0.0;
-    if (!h->d_ev_cocc) return;      // no CONST node: nothing depends on the data
+    if (!e.d_cocc) return;      // no CONST node: nothing depends on the data
     cx_prepare(h);
     HIPCHK(hipSetDevice(h->device));
-    const ExprTape& X = h->ev_X;
-    double* st = h->h_cx;
+    const ExprTape& X = e.X;
+    double* st = e.h_cx;
     std::memcpy(st, x, n * sizeof(double));
-    if (X.R > 0) std::memcpy(st + n, lambda + h->ev_F.n_rows, X.R * sizeof(double));
+    if (X.R > 0) std::memcpy(st + n, lambda + e.F.n_rows, X.R * sizeof(double));
     std::memcpy(st + n + X.R, dc, nd * sizeof(double));
-    HIPCHK(asmb::copy_async(h->d_ev_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(asmb::copy_async(h->d_cx_in, st + n, (X.R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, h->cx_C, h->d_ev_xt, h->d_cx_in + X.R, h->d_cx_in, h->ev_F.objective_scale,
-                 h->d_cx_out + n);
-    asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), h->stream, h->cx_C, n, h->d_cx_out);
+    HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(e.d_cx_in, st + n, (X.R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, e.cx_C, e.d_xt, e.d_cx_in + X.R, e.d_cx_in, e.F.objective_scale, e.d_cx_out + n);
+    asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), h->stream, e.cx_C, n, e.d_cx_out);
     double* back = st + n + X.R + nd;
-    HIPCHK(asmb::copy_async(back, h->d_cx_out, (n + X.R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::copy_async(back, e.d_cx_out, (n + X.R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
     std::memcpy(u, back, n * sizeof(double));
-    if (X.R > 0) std::memcpy(w + h->ev_F.n_rows, back + n, X.R * sizeof(double));
+    if (X.R > 0) std::memcpy(w + e.F.n_rows, back + n, X.R * sizeof(double));
 }
 
 // ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set" and "Many right-hand sides on one factor"): one
@@ -4421,10 +4452,10 @@ namespace {
 // once per asm_eval_setup, at the first KKT solve: what steps 1 and 2 fill, sized for every working set the problem admits, and the
 // per-column reduction state
 void kk_prepare(asm_handle* h) {
-    KktBufs& K = h->kk;
+    KktBufs& K = h->ev->kk;
     if (K.ready) return;
     HIPCHK(hipSetDevice(h->device));
-    BufPool& M = h->mem_kk;
+    BufPool& M = h->ev->mem;
     const hipStream_t s = h->stream;
     const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), CW = KKM_CW;
     K.capW = std::max<int64_t>(std::min(h->m, h->n), 1);
@@ -4447,13 +4478,13 @@ void kk_prepare(asm_handle* h) {
 // the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it
 KktWork* kk_work(asm_handle* h, int64_t cap) {
     kk_prepare(h);
-    KktBufs& K = h->kk;
+    KktBufs& K = h->ev->kk;
     KktWork& W = cap == 1 ? K.one : K.blk;
     if (W.cap != 0) return &W;
     HIPCHK(hipSetDevice(h->device));
-    BufPool& M = h->mem_kk;
+    BufPool& M = h->ev->mem;
     const hipStream_t s = h->stream;
-    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), nd = std::max<int64_t>(h->ev_n_dpar, 1);
+    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), nd = std::max<int64_t>(h->ev->n_dpar, 1);
     M.zeroed(W.vec, 14 * cap * ldn, s);
     M.zeroed(W.row, 5 * cap * K.ldT, s);
     M.zeroed(W.dlf, cap * Mp, s);
@@ -4471,7 +4502,7 @@ KktWork* kk_work(asm_handle* h, int64_t cap) {
 // word the host spins on, or (pub == 0, ASM_HIP_SPIN=0) a copy and a stream synchronisation
 int kk_read_scal(asm_handle* h, unsigned pub) {
     if (pub == 0) {
-        HIPCHK(asmb::copy_async(h->h_scal, h->kk.scal + KKM_CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(h->h_scal, h->ev->kk.scal + KKM_CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
         return (int)h->h_scal[0];
     }
@@ -4494,7 +4525,7 @@ int kk_read_scal(asm_handle* h, unsigned pub) {
     return (int)h->h_scal[0];
 }
 
-// The face of a call: its counts and limits, and on the device (h->kk) the mask of F, the list of W, A = J[W, F] with its transposed copy
+// The face of a call: its counts and limits, and on the device (h->ev->kk) the mask of F, the list of W, A = J[W, F] with its transposed copy
 // and the factor of S = A A'.
 struct KktFace {
     int64_t nF = 0, nW = 0, nWp = 0, max_iter = 0;      // |F|, |W|, |W| rounded up to 32
@@ -4532,7 +4563,7 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     hs_prepare(h);
     kk_prepare(h);
     HIPCHK(hipSetDevice(h->device));
-    KktBufs& K = h->kk;
+    KktBufs& K = h->ev->kk;
     const hipStream_t s = h->stream;
     const int64_t Mp = std::max<int64_t>(h->Mp, 32);
     // 1. the Hessian values of f - lambda' g at x, once: they stay in d_hs_vals for every product of the call (x goes to d_ev_xt)
@@ -4543,11 +4574,11 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     }
     // 2. the Jacobian at x: values into a buffer of the solve's own, assembled into its own dense J (the LP's dE and J stay)
     {
-        const FnStore& F = h->ev_F;
-        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->d_ev_xt, h->d_ev_Et, K.dE, 1, (int64_t)0, (int64_t)0);
-        const ExprTape& X = h->ev_X;
-        if (h->ev_nlp_kind == ASM_NLP_EXPR && X.R > 0)
-            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->d_ev_xt, h->d_ev_Et, K.dE, F.n_rows, h->ev_fn_nnz, 1, (int64_t)0, (int64_t)0);
+        const FnStore& F = h->ev->F;
+        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->ev->d_xt, h->ev->d_Et, K.dE, 1, (int64_t)0, (int64_t)0);
+        const ExprTape& X = h->ev->X;
+        if (h->ev->nlp_kind == ASM_NLP_EXPR && X.R > 0)
+            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
         if (h->dense_fast) {
             const unsigned g = (unsigned)std::min<int64_t>((h->m * h->n + 255) / 256, 4096);
             asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, K.dE, K.J, h->m, h->n, ldn);
@@ -4596,7 +4627,7 @@ struct KktOps {
     const int64_t n, ldn, ldT;
     double* const spare;             // a block over the working rows of the back end's own
     KktOps(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww)
-        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->n), ldn(hh->ldn), ldT(hh->kk.ldT), spare(ww.row + 2 * ww.cap * hh->kk.ldT) {}
+        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->n), ldn(hh->ldn), ldT(hh->ev->kk.ldT), spare(ww.row + 2 * ww.cap * hh->ev->kk.ldT) {}
     virtual ~KktOps() = default;
     virtual void hess(const double* v, double* out, int cols) = 0;                  // OUT = H V from the values of step 1
     virtual void mul_A(const double* v, double* t, int cols) = 0;                   // T = V A'
@@ -4611,14 +4642,14 @@ struct KktOps {
 struct KktOneColumn final : KktOps {
     using KktOps::KktOps;
     void hess(const double* v, double* out, int) override {
-        const HsShared& L = *h->hs_sh;
-        asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, n, out);
+        const HsShared& L = *h->ev->hs_sh;
+        asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
     }
-    void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nWg, 4), dim3(256), s, h->kk.Aw, ldn, v, t, f.nW, ldn); }
-    void mul_AT(const double* y, double* v, int) override { asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->kk.AwT, ldT, y, v, ldn, f.nW); }
+    void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nWg, 4), dim3(256), s, h->ev->kk.Aw, ldn, v, t, f.nW, ldn); }
+    void mul_AT(const double* y, double* v, int) override { asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->ev->kk.AwT, ldT, y, v, ldn, f.nW); }
     double* solve_S(const double* b, double* t, int) override {
         double* const out = b == t ? spare : t;
-        dev.chol_solve_dev(h->kk.fac, b, out, (int)f.nW);
+        dev.chol_solve_dev(h->ev->kk.fac, b, out, (int)f.nW);
         return out;
     }
     void jt_dlam(const double*, const double* dlf, double* jtl, int) override {
@@ -4626,7 +4657,7 @@ struct KktOneColumn final : KktOps {
         int64_t Rc = std::min<int64_t>((m + 31) / 32, ASM_TMAXCHUNKS);
         const int64_t chunk = (m + Rc - 1) / Rc;
         Rc = (m + chunk - 1) / chunk;
-        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->kk.J, ldn, dlf, h->d_partial, m, ldn, chunk);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->ev->kk.J, ldn, dlf, h->d_partial, m, ldn, chunk);
         asmb::launch(k_gemv_t_stage2, asmb::blocks(ldn), dim3(256), s, h->d_partial, jtl, Rc, ldn);
     }
 };
@@ -4635,7 +4666,7 @@ struct KktOneColumn final : KktOps {
 // operands are made here, once per call.
 struct KktBlock final : KktOps {
     KktBlock(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww) : KktOps(hh, d, ff, ww) {
-        const KktBufs& K = h->kk;
+        const KktBufs& K = h->ev->kk;
         const int64_t nW = f.nW;
         if (nW > 0) {
             const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
@@ -4649,18 +4680,18 @@ struct KktBlock final : KktOps {
     }
     // (rows >= cols of V are read - they exist: the blocks have KKM_CW rows - not written)
     void hess(const double* v, double* out, int cols) override {
-        const HsShared& L = *h->hs_sh;
+        const HsShared& L = *h->ev->hs_sh;
         const dim3 g = asmb::blocks(n);
-        if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
-        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->d_hs_vals, v, ldn, n, cols, out);
+        if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
     }
-    void mul_A(const double* v, double* t, int cols) override { dev.gemm_nt(v, ldn, h->kk.Aw, ldn, nullptr, 0, t, ldT, cols, (int)f.nW, (int)ldn, 0); }
-    void mul_AT(const double* y, double* v, int cols) override { dev.gemm_nt(y, ldT, h->kk.AwT, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)f.nWp, 0); }
+    void mul_A(const double* v, double* t, int cols) override { dev.gemm_nt(v, ldn, h->ev->kk.Aw, ldn, nullptr, 0, t, ldT, cols, (int)f.nW, (int)ldn, 0); }
+    void mul_AT(const double* y, double* v, int cols) override { dev.gemm_nt(y, ldT, h->ev->kk.AwT, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)f.nWp, 0); }
     double* solve_S(const double* b, double* t, int cols) override {
         if (b != t) HIPCHK(asmb::copy_async(t, b, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
-        dev.trsm_rows(h->kk.fac, t, spare, ldT, cols, (int)f.nW, w.Lt);
+        dev.trsm_rows(h->ev->kk.fac, t, spare, ldT, cols, (int)f.nW, w.Lt);
         return t;
     }
     void jt_dlam(const double* dlw, const double*, double* jtl, int cols) override { dev.gemm_nt(dlw, ldT, w.AfT, ldT, nullptr, 0, jtl, ldn, cols, (int)ldn, (int)f.nWp, 0); }
@@ -4680,10 +4711,10 @@ struct KktTrust {
 };
 void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, const double* RU, const double* RW, const double* DC, bool sens, const double* lambda, double* DX,
                  double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active, const KktTrust& tr = KktTrust()) {
-    const KktBufs& K = h->kk;
+    const KktBufs& K = h->ev->kk;
     KktWork& w = ops.w;
     const hipStream_t s = h->stream;
-    const int64_t n = h->n, m = h->m, ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW, nd = sens ? h->ev_n_dpar : 0;
+    const int64_t n = h->n, m = h->m, ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW, nd = sens ? h->ev->n_dpar : 0;
     const double* const mask = f.mask;
     auto vblock = [&](int k) { return w.vec + (int64_t)k * cap * ldn; };
     auto rblock = [&](int k) { return w.row + (int64_t)k * cap * ldT; };      // (block 2 is ops.spare)
@@ -4693,13 +4724,13 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     double* const dlf = w.dlf;
     double* const scal = K.scal;
     const KktMulti R{K.part, K.cnt, scal, K.act, h->d_hscal, h->d_hseq};
-    const bool cross = sens && h->d_ev_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
+    const bool cross = sens && h->ev->d_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
     if (cross) {      // the multipliers of the expression rows, once
         cx_prepare(h);
-        const ExprTape& X = h->ev_X;
+        const ExprTape& X = h->ev->X;
         if (X.R > 0) {
-            std::memcpy(h->h_cx, lambda + h->ev_F.n_rows, X.R * sizeof(double));
-            HIPCHK(asmb::copy_async(h->d_cx_in, h->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
+            std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, X.R * sizeof(double));
+            HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
         }
     }
     const dim3 gl = asmb::blocks(ldn);
@@ -4712,7 +4743,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
         const int cols = (int)std::min<int64_t>(cap, nrhs - c0);
         const dim3 glc(gl.x, (unsigned)cols), grc(asmb::blocks(f.nWg).x, (unsigned)cols), gredc(gred, (unsigned)cols);
         double* st = w.stage;                                    // [ru block | rw block | directions], then the results
-        double* back = st + cap * (ldn + ldT + std::max<int64_t>(h->ev_n_dpar, 1));
+        double* back = st + cap * (ldn + ldT + std::max<int64_t>(h->ev->n_dpar, 1));
         auto axpby = [&](double sa, const double* a, double sb, const double* b, const double* sc, double* out) {
             asmb::launch(k_kktm_axpby, glc, dim3(256), s, sa, a, sb, b, mask, ldn, ldn, sc, out);
         };
@@ -4746,14 +4777,14 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             }
         } else if (cross) {
             // one sweep per direction, no synchronisation between them: every direction has its own staging row
-            const ExprTape& X = h->ev_X;
+            const ExprTape& X = h->ev->X;
             double* hd = st + cap * (ldn + ldT);
             for (int c = 0; c < cols; ++c) {
                 std::memcpy(hd + (int64_t)c * nd, DC + (c0 + c) * nd, nd * sizeof(double));
-                HIPCHK(asmb::copy_async(h->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
-                asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->cx_C, h->d_ev_xt, h->d_cx_in + X.R, h->d_cx_in, h->ev_F.objective_scale, h->d_cx_out + n);
-                asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->cx_C, n, h->d_cx_out);
-                asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->d_cx_out, n, (int64_t)h->ev_F.n_rows, f.wrow, nW, b_ru + (int64_t)c * ldn,
+                HIPCHK(asmb::copy_async(h->ev->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
+                asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->ev->cx_C, h->ev->d_xt, h->ev->d_cx_in + X.R, h->ev->d_cx_in, h->ev->F.objective_scale, h->ev->d_cx_out + n);
+                asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->ev->cx_C, n, h->ev->d_cx_out);
+                asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->ev->d_cx_out, n, (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru + (int64_t)c * ldn,
                              rww + (int64_t)c * ldT);
             }
         } else {
@@ -4869,7 +4900,7 @@ static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, c
 static void do_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
                                     const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
     cx_check(h, "asm_solution_sensitivity");
-    if (!x || !bound_state || !dx || !info || (h->m > 0 && (!lambda || !row_state || !dlam)) || (h->ev_n_dpar > 0 && !dc))
+    if (!x || !bound_state || !dx || !info || (h->m > 0 && (!lambda || !row_state || !dlam)) || (h->ev->n_dpar > 0 && !dc))
         throw std::invalid_argument("asm_solution_sensitivity: null pointer");
     std::vector<double> u((size_t)std::max<int64_t>(h->n, 1)), w((size_t)std::max<int64_t>(h->m, 1));
     do_data_cross(h, x, lambda, dc, u.data(), w.data());
@@ -4885,11 +4916,11 @@ static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, 
     hs_check(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
     if (!x || !bound_state || !DX || !info || (h->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
-    if (sens ? (h->ev_n_dpar > 0 && !DC) : (!RU || (h->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
+    if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
     Dev dev(h);
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par);
     KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
-    kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->kkm_rounds, h->kkm_last_active);
+    kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
 }
 // asm_kkt_step (one column through KktOneColumn) and asm_kkt_step_multi (KktBlock): the checks of asm_kkt_solve(_multi), then
 // those of the radii and the share
@@ -4914,7 +4945,7 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par ? &kp : nullptr);
     if (multi) {
         KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
-        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, h->kkm_rounds, h->kkm_last_active, tr);
+        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, h->ev->kkm_rounds, h->ev->kkm_last_active, tr);
     } else {
         KktOneColumn ops(h, dev, f, *kk_work(h, 1));
         int64_t rounds;
@@ -4926,18 +4957,18 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
 static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
     if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
-    if (!h->ev_ready) throw std::logic_error("asm_eval_constraints: asm_eval_setup first");
+    EvalState& e = ev_of(h, "asm_eval_constraints");
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n, m = h->m;
-    std::memcpy(h->h_ev, x, n * sizeof(double));
-    HIPCHK(asmb::copy_async(h->d_ev_xt, h->h_ev, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
-    double* st = h->h_ev + n;
-    if (m) HIPCHK(asmb::copy_async(st, h->d_ev_Et, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(asmb::copy_async(st + m, h->d_ev_f + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double *st = e.h_stage, *s_E = st + e.L.st_E(false), *s_f = st + e.L.st_f(false);
+    std::memcpy(st, x, n * sizeof(double));
+    HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    ev_launch(h, e.d_xt, e.d_Et, e.d_f + 1, false);
+    if (m) HIPCHK(asmb::copy_async(s_E, e.d_Et, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::copy_async(s_f, e.d_f + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
-    if (m) std::memcpy(E, st, m * sizeof(double));
-    *f = st[m];
+    if (m) std::memcpy(E, s_E, m * sizeof(double));
+    *f = *s_f;
 }
 
 int asm_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
@@ -5001,8 +5032,8 @@ int asm_kkt_step_multi(asm_handle* h, const double* x, const double* lambda, con
 
 int asm_test_kkt_multi_rounds(const asm_handle* h, int64_t* rounds, int32_t* last_active) {
     if (!h || !rounds || !last_active) return ASM_ERR_ARG;
-    *rounds = h->kkm_rounds;
-    *last_active = h->kkm_last_active;
+    *rounds = h->ev ? h->ev->kkm_rounds : 0;
+    *last_active = h->ev ? h->ev->kkm_last_active : 0;
     return ASM_OK;
 }
 
@@ -5024,18 +5055,18 @@ int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, 
 // evaluation results of the last asm_eval_functions and the Jacobian assembled from its dE (assembled once, shared with the LP)
 static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4) {
     if (!mult_x_U || !mult_x_L || !out4 || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_slp_norms: null pointer");
-    if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_norms: asm_eval_functions first");
+    if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_norms: asm_eval_functions first");
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n, m = h->m;
     Dev d(h);
     d.assemble();
-    double* v = h->d_ev_vecs + 2 * m + 2 * n;       // lam | mU | mL
-    double *lam = v, *mU = v + m, *mL = mU + n, *jtl = mL + n + m + 2 * m + n /* after nu (m), ps (2m), p (n) */, *rown = jtl + h->ldn, *outd = rown + h->Mp;
-    double* st = h->h_ev;
+    const EvLayout& L = h->ev->L;
+    double *lam = L.lam(), *jtl = L.jtl(), *rown = L.rown(), *outd = L.out();
+    double* st = h->ev->h_stage;    // the image of the block from lam on
     if (m) std::memcpy(st, lambda, m * sizeof(double));
-    std::memcpy(st + m, mult_x_U, n * sizeof(double));
-    std::memcpy(st + m + n, mult_x_L, n * sizeof(double));
-    HIPCHK(asmb::copy_async(lam, st, (m + 2 * n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    std::memcpy(st + (L.mU() - lam), mult_x_U, n * sizeof(double));
+    std::memcpy(st + (L.mL() - lam), mult_x_L, n * sizeof(double));
+    HIPCHK(asmb::copy_async(lam, st, (L.nu() - lam) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     // J' lambda over the first m rows: lambda padded with zeros on the extra range rows
     HIPCHK(asmb::fill_async(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
     if (m) HIPCHK(asmb::copy_async(h->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -5046,7 +5077,7 @@ static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult
         else
             asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_J, h->ldn, rown, m, h->ldn);
     }
-    asmb::launch(k_slp_norms, dim3(1), dim3(1024), h->stream, ev_vecs(h, lam, mU, mL, jtl, rown), outd);
+    asmb::launch(k_slp_norms, dim3(1), dim3(1024), h->stream, ev_vecs(*h->ev, true), outd);
     HIPCHK(asmb::copy_async(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
     for (int k = 0; k < RN_COUNT; ++k) out4[k] = st[k];
@@ -5063,72 +5094,73 @@ int asm_slp_merit(asm_handle* h, int mode, double alpha, const double* p, const 
                   double* out) {
     return guarded(h, [&] {
         if (!p || !out || (h->m > 0 && (!nu || !p_slack)) || mode < 0 || mode > 1) throw std::invalid_argument("asm_slp_merit: bad argument");
-        if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_merit: asm_eval_functions first");
+        if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_merit: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
-        const int64_t n = h->n, m = h->m;
-        double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
-        double *nud = v, *psd = v + m, *pd = psd + 2 * m, *outd = pd + n + h->ldn + h->Mp;
-        double* st = h->h_ev;
-        if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
-        std::memcpy(st + 3 * m, p, n * sizeof(double));
-        HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const double* Et = h->d_ev_E;
-        const double* ft = h->d_ev_f;
+        const EvalState& e = ev_stage_step(h, nu, p_slack, p);
+        const EvLayout& L = e.L;
+        const double *Et = e.d_E, *ft = e.d_f;
         if (mode == 0 && alpha != 0.0) {
-            asmb::launch(k_axpy_out, asmb::blocks(n), dim3(256), h->stream, h->d_ev_x, alpha, pd, h->d_ev_xt, n);
-            ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
-            Et = h->d_ev_Et;
-            ft = h->d_ev_f + 1;
+            asmb::launch(k_axpy_out, asmb::blocks(h->n), dim3(256), h->stream, e.d_x, alpha, L.p(), e.d_xt, h->n);
+            ev_launch(h, e.d_xt, e.d_Et, e.d_f + 1, false);
+            Et = e.d_Et; ft = e.d_f + 1;
         }
-        asmb::launch(k_slp_merit, dim3(1), dim3(1024), h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), Et, nud, psd, pd, alpha, feasibility, prim_infeas, ft,
-                     mode, outd, TrialAlphas(), (int64_t)0);
-        HIPCHK(asmb::copy_async(st, outd, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        asmb::launch(k_slp_merit, dim3(1), dim3(1024), h->stream, ev_vecs(e), Et, L.nu(), L.ps(), L.p(), alpha, feasibility, prim_infeas, ft, mode, L.out(), TrialAlphas(),
+                     (int64_t)0);
+        HIPCHK(asmb::copy_async(e.h_stage, L.out(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
-        *out = st[0];
+        *out = e.h_stage[0];
     });
 }
 
-// compute_alpha (slp_line_search.jl:222-244) with the trial evaluations on the device: alpha = 1, tau, tau^2, ... until
+// compute_alpha's trial loop (slp_line_search.jl:222-244) on the step ev_stage_step uploaded: alpha = 1, tau, tau^2, ... until
 //   phi(alpha) <= phi0 + eta alpha D      (accepted: *ok = 1)      or      alpha < min_alpha with the test still failing (*ok = 0).
-// The trials are pure function evaluations, so they are launched eight at a time without waiting for the verdict of the earlier ones
-// (one read-back per eight); nu, the slacks and p are uploaded once.  Same alpha, same merit values as calling asm_slp_merit per trial.
+// The trials are pure function evaluations, so they are launched eight at a time without waiting for the verdict of the earlier ones (one
+// read-back per eight): same alpha, same merit values as asm_slp_merit per trial.  phi0_D_on_device: k_slp_merit launches of the caller's
+// put phi0 and D into out[TRIALS], out[TRIALS + 1]; they come back with the first eight merit values and leave through phi0, D.
+static void slp_trials(asm_handle* h, int feasibility, double prim_infeas, bool phi0_D_on_device, double& phi0, double& D, double eta, double tau, double min_alpha,
+                       double* alpha_out, double* phi_out, int* trials_out, int* ok_out) {
+    const EvalState& e = *h->ev;
+    const EvLayout& L = e.L;
+    const int64_t n = h->n, m = h->m;
+    const SlpVecs V = ev_vecs(e);
+    constexpr int CH = (int)EvLayout::TRIALS;
+    static_assert(sizeof(TrialAlphas) == CH * sizeof(double), "one alpha per trial of a round");
+    double* st = e.h_stage;
+    double alpha = 1.0, a[CH];
+    int trials = 0;
+    *ok_out = -1;
+    for (int round = 0; *ok_out < 0; ++round) {
+        asmb::barrier(920);
+        // eight trial points per set of launches (trial index in the grid): x + alpha_t p, the function values there, the merit values
+        TrialAlphas al;
+        for (int t = 0; t < CH; ++t) { a[t] = al.a[t] = alpha; alpha *= tau; }
+        const int64_t ldx = round_up(n, 32), ldE = round_up(std::max<int64_t>(m, 1), 32);
+        asmb::launch(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), h->stream, e.d_x, al, L.p(), e.d_xt, n, ldx);
+        ev_launch(h, e.d_xt, e.d_Et, e.d_f + 1, false, CH, ldx, ldE);
+        asmb::launch(k_slp_merit, dim3(CH), dim3(1024), h->stream, V, e.d_Et, L.nu(), L.ps(), L.p(), 0.0, feasibility, prim_infeas, e.d_f + 1, 0, L.out(), al, ldE);
+        const bool first = phi0_D_on_device && round == 0;
+        HIPCHK(asmb::copy_async(st, L.out(), (CH + (first ? 2 : 0)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+        if (first) { phi0 = st[CH]; D = st[CH + 1]; }
+        for (int t = 0; t < CH && *ok_out < 0; ++t) {
+            trials += 1;
+            *ok_out = !(st[t] > phi0 + eta * a[t] * D) ? 1 : a[t] < min_alpha ? 0 : -1;
+            if (*ok_out >= 0) { *alpha_out = a[t]; if (phi_out) *phi_out = st[t]; }
+        }
+    }
+    if (trials_out) *trials_out = trials;
+}
+
+// compute_alpha with phi0 and D given; nu, the slacks and p are uploaded once
 int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double phi0,
                         double D, double eta, double tau, double min_alpha, double* alpha_out, double* phi_out, int* trials_out, int* ok_out) {
     return guarded(h, [&] {
         if (!p || !alpha_out || !ok_out || (h->m > 0 && (!nu || !p_slack)) || !(tau > 0.0 && tau < 1.0))
             throw std::invalid_argument("asm_slp_line_search: bad argument");
-        if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_line_search: asm_eval_functions first");
+        if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_line_search: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
-        const int64_t n = h->n, m = h->m;
-        double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
-        double *nud = v, *psd = v + m, *pd = psd + 2 * m, *outd = pd + n + h->ldn + h->Mp;
-        double* st = h->h_ev;
-        if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
-        std::memcpy(st + 3 * m, p, n * sizeof(double));
-        HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const SlpVecs V = ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr);
-        constexpr int CH = 8;
-        double alpha = 1.0, a[CH];
-        int trials = 0;
-        *ok_out = -1;
-        while (*ok_out < 0) {
-            asmb::barrier(920);
-            // eight trial points per set of launches (trial index in the grid): x + alpha_t p, the function values there, the merit values
-            TrialAlphas al;
-            for (int t = 0; t < CH; ++t) { a[t] = al.a[t] = alpha; alpha *= tau; }
-            const int64_t ldx = round_up(n, 32), ldE = round_up(std::max<int64_t>(m, 1), 32);
-            asmb::launch(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), h->stream, h->d_ev_x, al, pd, h->d_ev_xt, n, ldx);
-            ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false, CH, ldx, ldE);
-            asmb::launch(k_slp_merit, dim3(CH), dim3(1024), h->stream, V, h->d_ev_Et, nud, psd, pd, 0.0, feasibility, prim_infeas, h->d_ev_f + 1, 0, outd, al, ldE);
-            HIPCHK(asmb::copy_async(st, outd, CH * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(asmb::sync(h->stream));
-            for (int t = 0; t < CH && *ok_out < 0; ++t) {
-                trials += 1;
-                if (!(st[t] > phi0 + eta * a[t] * D)) { *ok_out = 1; *alpha_out = a[t]; if (phi_out) *phi_out = st[t]; }
-                else if (a[t] < min_alpha) { *ok_out = 0; *alpha_out = a[t]; if (phi_out) *phi_out = st[t]; }
-            }
-        }
-        if (trials_out) *trials_out = trials;
+        ev_stage_step(h, nu, p_slack, p);
+        slp_trials(h, feasibility, prim_infeas, false, phi0, D, eta, tau, min_alpha, alpha_out, phi_out, trials_out, ok_out);
     });
 }
 
@@ -5137,65 +5169,32 @@ int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const 
 // three read-backs).  The trial points do not depend on phi0 and D, only the acceptance test does: same launches per quantity, same values.
 static void slp_merit_and_search(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double eta, double tau,
                                  double min_alpha, double* phi0_out, double* D_out, double* alpha_out, double* phi_out, int* trials_out, int* ok_out) {
-    const int64_t n = h->n, m = h->m;
-    double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
-    double *nud = v, *psd = v + m, *pd = psd + 2 * m, *outd = pd + n + h->ldn + h->Mp;
-    double* st = h->h_ev;
-    if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
-    std::memcpy(st + 3 * m, p, n * sizeof(double));
-    HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const SlpVecs V = ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr);
-    constexpr int CH = 8;
+    const EvalState& e = ev_stage_step(h, nu, p_slack, p);
+    const EvLayout& L = e.L;
     for (int mode = 0; mode < 2; ++mode)
-        asmb::launch(k_slp_merit, dim3(1), dim3(1024), h->stream, V, h->d_ev_E, nud, psd, pd, 0.0, feasibility, prim_infeas, h->d_ev_f, mode, outd + CH + mode, TrialAlphas(),
-                     (int64_t)0);
-    double alpha = 1.0, a[CH], phi0 = 0.0, D = 0.0;
-    int trials = 0;
-    *ok_out = -1;
-    for (int round = 0; *ok_out < 0; ++round) {
-        asmb::barrier(920);
-        TrialAlphas al;
-        for (int t = 0; t < CH; ++t) { a[t] = al.a[t] = alpha; alpha *= tau; }
-        const int64_t ldx = round_up(n, 32), ldE = round_up(std::max<int64_t>(m, 1), 32);
-        asmb::launch(k_axpy_trials, dim3((unsigned)((n + 255) / 256), CH), dim3(256), h->stream, h->d_ev_x, al, pd, h->d_ev_xt, n, ldx);
-        ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false, CH, ldx, ldE);
-        asmb::launch(k_slp_merit, dim3(CH), dim3(1024), h->stream, V, h->d_ev_Et, nud, psd, pd, 0.0, feasibility, prim_infeas, h->d_ev_f + 1, 0, outd, al, ldE);
-        HIPCHK(asmb::copy_async(st, outd, (CH + (round == 0 ? 2 : 0)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(asmb::sync(h->stream));
-        if (round == 0) { phi0 = st[CH]; D = st[CH + 1]; }
-        for (int t = 0; t < CH && *ok_out < 0; ++t) {
-            trials += 1;
-            if (!(st[t] > phi0 + eta * a[t] * D)) { *ok_out = 1; *alpha_out = a[t]; *phi_out = st[t]; }
-            else if (a[t] < min_alpha) { *ok_out = 0; *alpha_out = a[t]; *phi_out = st[t]; }
-        }
-    }
-    *phi0_out = phi0; *D_out = D; *trials_out = trials;
+        asmb::launch(k_slp_merit, dim3(1), dim3(1024), h->stream, ev_vecs(e), e.d_E, L.nu(), L.ps(), L.p(), 0.0, feasibility, prim_infeas, e.d_f, mode,
+                     L.out() + EvLayout::TRIALS + mode, TrialAlphas(), (int64_t)0);
+    slp_trials(h, feasibility, prim_infeas, true, *phi0_out, *D_out, eta, tau, min_alpha, alpha_out, phi_out, trials_out, ok_out);
 }
 
 // step_quality's merit values (slp_trust_region.jl:213-216): out3 = { compute_derivative, compute_phi(x, 0, p), compute_phi(x, 1, p) } with one
 // upload of nu | slacks | p, the trial point x + p evaluated on the device and one read-back (three asm_slp_merit calls: three uploads, three read-backs).  The
 // same launches per quantity as asm_slp_merit makes (k_axpy_out + ev_launch at alpha = 1, the merit body of k_slp_merit): same values.
 static void slp_tr_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
-    const int64_t n = h->n, m = h->m;
-    double* v = h->d_ev_vecs + 2 * m + 2 * n + m + 2 * n;    // nu | ps | p
-    double *nud = v, *psd = v + m, *pd = psd + 2 * m, *outd = pd + n + h->ldn + h->Mp;
-    double* st = h->h_ev;
-    if (m) { std::memcpy(st, nu, m * sizeof(double)); std::memcpy(st + m, p_slack, 2 * m * sizeof(double)); }
-    std::memcpy(st + 3 * m, p, n * sizeof(double));
-    HIPCHK(asmb::copy_async(nud, st, (3 * m + n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    asmb::launch(k_axpy_out, asmb::blocks(n), dim3(256), h->stream, h->d_ev_x, 1.0, pd, h->d_ev_xt, n);
-    ev_launch(h, h->d_ev_xt, h->d_ev_Et, h->d_ev_f + 1, false);
-    asmb::launch(k_slp_tr_quality, dim3(3), dim3(1024), h->stream, ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr), h->d_ev_Et, nud, psd, pd, feasibility, prim_infeas,
-                 h->d_ev_f, h->d_ev_f + 1, outd);
-    HIPCHK(asmb::copy_async(st, outd, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    const EvalState& e = ev_stage_step(h, nu, p_slack, p);
+    const EvLayout& L = e.L;
+    asmb::launch(k_axpy_out, asmb::blocks(h->n), dim3(256), h->stream, e.d_x, 1.0, L.p(), e.d_xt, h->n);
+    ev_launch(h, e.d_xt, e.d_Et, e.d_f + 1, false);
+    asmb::launch(k_slp_tr_quality, dim3(3), dim3(1024), h->stream, ev_vecs(e), e.d_Et, L.nu(), L.ps(), L.p(), feasibility, prim_infeas, e.d_f, e.d_f + 1, L.out());
+    HIPCHK(asmb::copy_async(e.h_stage, L.out(), 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
-    for (int k = 0; k < 3; ++k) out3[k] = st[k];
+    for (int k = 0; k < 3; ++k) out3[k] = e.h_stage[k];
 }
 
 int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
     return guarded(h, [&] {
         if (!p || !out3 || (h->m > 0 && (!nu || !p_slack))) throw std::invalid_argument("asm_slp_step_quality: null pointer");
-        if (!h->ev_ready || !h->inputs_ready) throw std::logic_error("asm_slp_step_quality: asm_eval_functions first");
+        if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_step_quality: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
         slp_tr_step_quality(h, p, nu, p_slack, feasibility, prim_infeas, out3);
     });
@@ -5205,13 +5204,13 @@ int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const
 namespace {
 void eq_prepare(asm_handle* h) {
     kk_prepare(h);
-    KktBufs& K = h->kk;
+    KktBufs& K = h->ev->kk;
     if (K.eq_i) return;
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n, m = h->m, ni = h->M + 2 * n + 3 * m + 4, nd = m + 2 * n + EQP_SCAL;
-    h->mem_kk.zeroed(K.eq_i, ni, h->stream);
-    h->mem_kk.zeroed(K.eq_d, nd, h->stream);
-    h->mem_kk.alloc(K.eq_h, (ni + 1) / 2 + nd + n + 8, BufPool::PINNED);
+    h->ev->mem.zeroed(K.eq_i, ni, h->stream);
+    h->ev->mem.zeroed(K.eq_d, nd, h->stream);
+    h->ev->mem.alloc(K.eq_h, (ni + 1) / 2 + nd + n + 8, BufPool::PINNED);
     HIPCHK(asmb::sync(h->stream));
 }
 }  // namespace
@@ -5240,7 +5239,7 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     std::memset(info, 0, sizeof(*info));
     for (int64_t j = 0; j < n; ++j) d[j] = mult_x_U[j] = mult_x_L[j] = 0.0;
     for (int64_t i = 0; i < m; ++i) lam_new[i] = 0.0;
-    const KktBufs& K = h->kk;
+    const KktBufs& K = h->ev->kk;
     const hipStream_t s = h->stream;
     const KktRed R{K.part, K.cnt, K.scal};
     const int64_t n_in = M + n + m, n_out = m + n + 4;      // (the side a working row sits at stays on the device: rw carries what the host needs of it)
@@ -5254,13 +5253,13 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     for (int64_t i = 0; i < m; ++i) hi[M + n + i] = -1;
     for (size_t a = 0; a < h->adj.size(); ++a) hi[M + n + h->adj[a]] = (int)a;
     HIPCHK(asmb::copy_async(i_lp_rows, hi, n_in * sizeof(int), hipMemcpyHostToDevice, s));
-    const SlpVecs V = ev_vecs(h, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const SlpVecs V = ev_vecs(*h->ev);
     const EqpFace P{V.E, V.g_L, V.g_U, V.x, V.x_L, V.x_U, i_lp_rows, i_lp_bnd, i_twin, n, m, tol_active};
     const unsigned gf = (unsigned)std::min<int64_t>(asmb::blocks(std::max(n, m)).x, KK_MAXWG);
     asmb::launch(k_eqp_face, dim3(gf), dim3(256), s, P, R, i_rows, i_bnd, i_side, d_rw, i_cnt);
     HIPCHK(asmb::copy_async(hi + n_in, i_rows, n_out * sizeof(int), hipMemcpyDeviceToHost, s));
     if (m > 0) HIPCHK(asmb::copy_async(hd, d_rw, m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(asmb::copy_async(hd + m, h->d_ev_df, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(asmb::copy_async(hd + m, h->ev->d_df, n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(asmb::sync(s));
     const int* o_rows = hi + n_in;
     const int *o_bnd = o_rows + m, *o_cnt = o_bnd + n;
@@ -6311,7 +6310,7 @@ struct SlpRunLS : SlpRun {
 
 void slp_run_ls(asm_handle* h, const asm_slp_params* par, const double* x0, double* x_out, double* lambda, double* mult_x_U, double* mult_x_L, double* g_out,
                 asm_slp_result* res) {
-    if (!h->ev_ready) throw std::logic_error("asm_slp_run: asm_eval_setup first (the native driver evaluates on the device)");
+    if (!h->ev) throw std::logic_error("asm_slp_run: asm_eval_setup first (the native driver evaluates on the device)");
     if (res) std::memset(res, 0, sizeof(*res));
     SlpRunLS r(h, *par, res);
     r.run(x0);
@@ -6484,7 +6483,7 @@ void check_eqp_params(const asm_slp_eqp_params& ep, const char* what) {
 
 void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const double* x0, double* x_out, double* lambda, double* mult_x_U, double* mult_x_L,
                 double* g_out, asm_slp_result* res, asm_slp_tr_info* tr) {
-    if (!h->ev_ready) throw std::logic_error("asm_slp_run_tr: asm_eval_setup first (the native driver evaluates on the device)");
+    if (!h->ev) throw std::logic_error("asm_slp_run_tr: asm_eval_setup first (the native driver evaluates on the device)");
     if (res) std::memset(res, 0, sizeof(*res));
     SlpRunTR r(h, *par, tr_size, res);
     r.run(x0);
@@ -6574,11 +6573,11 @@ void run_fibers(asm_batch* b, int count, const char* step, W&& work) {
 // scenario sc's NLP-block data on slot handle h before its start: row sc of the scenario table, or the setup values.  What the slot's
 // earlier work wrote outside the range about to be written is restored first, so a result never depends on what the slot solved before.
 void batch_scenario_data(asm_batch* b, asm_handle* h, int64_t sc) {
-    const int64_t lo = h->ev_dirty_lo, hi = h->ev_dirty_hi;
+    const int64_t lo = h->ev->dirty_lo, hi = h->ev->dirty_hi;
     const bool covered = b->scen_cnt > 0 && lo >= b->scen_off && hi <= b->scen_off + b->scen_cnt;
     if (hi > lo && !covered) {
         do_set_data(h, lo, hi - lo, b->dpar0.data() + lo);
-        h->ev_dirty_lo = h->ev_dirty_hi = 0;
+        h->ev->dirty_lo = h->ev->dirty_hi = 0;
     }
     if (b->scen_cnt > 0) do_set_data(h, b->scen_off, b->scen_cnt, b->scen_tab.data() + sc * b->scen_cnt);
 }
@@ -6590,7 +6589,7 @@ void check_scen(const asm_batch* b, int64_t n_scen, const char* what) {
 // forget the shared Hessian lists: the slots that use them go back to "not prepared" (their workspaces leave with their evaluator pools)
 void batch_hs_drop(asm_batch* b) {
     for (asm_handle* h : b->slots)
-        if (h->hs_sh && h->hs_sh == b->hs.get()) { h->hs_ready = false; h->hs_H = ExprHess{}; h->hs_sh = nullptr; }
+        if (h->ev && h->ev->hs_sh && h->ev->hs_sh == b->hs.get()) h->ev->hs_forget();
     b->hs.reset();
 }
 void batch_free_groups(asm_batch* b) {
@@ -6750,7 +6749,7 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
 
 int asm_batch_set_scenario_data(asm_batch* b, int64_t n_scen, int64_t offset, int64_t count, const double* table) {
     return guarded(b, [&] {
-        if (!b->setup_done || !b->slots[0]->ev_ready) throw std::logic_error("asm_batch_set_scenario_data: asm_batch_eval_setup first");
+        if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error("asm_batch_set_scenario_data: asm_batch_eval_setup first");
         if (count == 0) {
             b->scen_tab.clear();
             b->scen_n = b->scen_off = b->scen_cnt = 0;
@@ -6788,7 +6787,7 @@ int asm_batch_sublp_solve(asm_batch* b, int count, const double* c_lb, const dou
         run_fibers(b, count, "asm_sublp_solve", [&](int s) {
             asm_handle* h = b->slots[s];
             if (c_lb && c_ub && v_lb && v_ub) do_set_bounds(h, c_lb + s * m, c_ub + s * m, v_lb + s * n, v_ub + s * n);
-            if (h->ev_ready) batch_scenario_data(b, h, s);
+            if (h->ev) batch_scenario_data(b, h, s);
             asmb::next_cycle();
             do_upload(h, dE + s * nnz, df + s * n, f[s], E ? E + s * m : nullptr, x_k + s * n);
             do_solve(h, delta[s], feasibility[s], p + s * n, lambda ? lambda + s * m : nullptr, mult_x_U + s * n, mult_x_L + s * n,
@@ -6880,8 +6879,8 @@ int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const
 // asm_eval_data_gradient of n_scen scenarios (each with its data, as asm_batch_slp_run gives it), the slots taking them in index order
 int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, double* out) {
     return guarded(b, [&] {
-        if (!b->setup_done || !b->slots[0]->ev_ready) throw std::logic_error("asm_batch_data_gradient: asm_batch_eval_setup first");
-        if (b->slots[0]->ev_nlp_kind != ASM_NLP_EXPR)
+        if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error("asm_batch_data_gradient: asm_batch_eval_setup first");
+        if (b->slots[0]->ev->nlp_kind != ASM_NLP_EXPR)
             throw std::invalid_argument("asm_batch_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
         const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nd = (int64_t)b->dpar0.size();
         if (n_scen < 1 || !x || (m > 0 && !lambda) || (nd > 0 && !out)) throw std::invalid_argument("asm_batch_data_gradient: bad argument");
@@ -6907,7 +6906,7 @@ namespace {
 // what every asm_batch_hessian_* entry starts with: state and kind checks, then the shared pattern and lists - built once per
 // asm_batch_eval_setup from slot 0's store and tape, on the calling thread (the build downloads with blocking copies)
 void batch_hs_prepare(asm_batch* b, const char* who) {
-    if (!b->setup_done || !b->slots[0]->ev_ready) throw std::logic_error(std::string(who) + ": asm_batch_eval_setup first");
+    if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error(std::string(who) + ": asm_batch_eval_setup first");
     hs_check(b->slots[0], who);
     if (b->hs) return;
     auto sh = std::make_unique<HsShared>();
@@ -6921,7 +6920,7 @@ void batch_kkt_prepare(asm_batch* b, int count) {
     for (int s = 0; s < count; ++s)
         in_slot("asm_slp_run_eqp", s, [&] {
             asm_handle* h = b->slots[s];
-            if (!h->hs_ready) hs_attach(h, b->hs.get());
+            if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
             (void)kk_work(h, 1);
             eq_prepare(h);
         });
@@ -6940,11 +6939,11 @@ void batch_hessians(asm_batch* b, const char* who, int64_t n_scen, const double*
         for (;;) {
             const int64_t sc = next.fetch_add(1);
             if (sc >= n_scen) break;
-            if (!h->hs_ready) hs_attach(h, b->hs.get());
+            if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
             batch_scenario_data(b, h, sc);
             asmb::next_cycle();
             hs_launch(h, x + sc * n, obj_factor ? obj_factor[sc] : 1.0, m > 0 ? lambda + sc * m : nullptr, v ? v + sc * n : nullptr);
-            hs_read(h, v ? h->d_hs_out : h->d_hs_vals, len, out + sc * len);
+            hs_read(h, v ? h->ev->d_hs_out : h->ev->d_hs_vals, len, out + sc * len);
         }
     });
 }

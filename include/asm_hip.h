@@ -347,7 +347,8 @@ int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, 
  *   3 dependent working rows (dropped_pivots > 0; the answer is the least-squares one of the remaining rows)
  * cg_iters, n_free = |F|, n_rows = |W|; res_stat / res_feas: the infinity norms of H_FF dx_F - A' dlam_W + ru_F and of A dx_F + rw_W for
  * the returned solution.
- * Everything runs on the handle's stream in buffers of the solve's own (released by asm_sublp_setup, asm_eval_setup and asm_destroy): the
+ * Everything runs on the handle's stream in buffers of the solve's own, which live as long as the evaluator (until the next asm_eval_setup,
+ * asm_sublp_setup or asm_destroy): the
  * inputs of the next LP (dE, df, E, x_k), the retained basis, hints and active sets and the solver's factors do not change.  A and
  * S = A A' are DENSE; the sparse, banded and null-space forms of the LP solver have no counterpart here.
  * Method:
