@@ -397,6 +397,61 @@ struct EvalState {
     BufPool mem;                    // declared last: it goes first, while the fields it nulls are alive
 };
 
+// Pitches and lengths of the buffers of the null-space form that do not depend on the null-space dimension, for an LP with nE hard equality
+// rows and nI inequality rows (do_setup allocates by them; Solver::nsv places the work vectors).  theta~ = [n-part (ldn) | I-part (nIp)], a row
+// of Gt = [Zt | GI'] has the same shape (pitch ldg).  Work vectors: five n-sized, three M-sized, two E-sized, then six more of n entries
+// (10 .. 13 hold k <= n entries, 14 = e, 15).  kcap: rows reserved for a basis of k rows (Solver::ns_reserve).
+struct NsLayout {
+    int64_t ldn, Mp, nE, nI, nEp, nIp, ldg;
+    NsLayout(int64_t ln, int64_t lm, int64_t ne, int64_t ni)
+        : ldn(ln), Mp(lm), nE(ne), nI(ni), nEp(round_up(ne, 32)), nIp(round_up(std::max<int64_t>(ni, 1), 32)), ldg(ln + nIp) {}
+    int64_t th_len() const { return ldg; }
+    int64_t nsv_len() const { return 11 * ldn + 3 * Mp + 2 * nEp; }
+    int64_t nsv_off(int which) const {
+        if (which < 5) return (int64_t)which * ldn;
+        if (which < 8) return 5 * ldn + (int64_t)(which - 5) * Mp;
+        if (which < 10) return 5 * ldn + 3 * Mp + (int64_t)(which - 8) * nEp;
+        return 5 * ldn + 3 * Mp + 2 * nEp + (int64_t)(which - 10) * ldn;
+    }
+    static int kcap(int k) { return (int)round_up(k + k / 4 + 64, 64); }
+};
+
+// The buffers of the null-space form sized by the null-space dimension, in a pool of their own: made by the first LP that uses the form and
+// re-made when the dimension outgrows them (Solver::ns_reserve).  NsForm holds a pointer that is null until then.
+struct NsK {
+    int cap = 0, ccap = 0, Zk = 0;  // rows reserved (NsLayout::kcap); most constraints of a reduced active-set solve; rows of the previous LP's basis still in G
+    double *R = nullptr, *X = nullptr, *G = nullptr, *N0 = nullptr, *Np = nullptr, *ZT = nullptr, *q = nullptr;   // right-hand-side blocks, Gt = [Zt | GI'], N, its split-K slices, Zt'
+    int *J = nullptr, *qi = nullptr;
+    FacBuf fN, fC;                  // factors of the k x k reduced matrix (per iteration) and of the Gram matrix of the active constraints in reduced coordinates
+    // The ONLY place that lays out the work areas qi, q of the reduced active-set solve: sel | bpos | rpos | cnt  and  Csel | d, lam, v, w, u |
+    // pbar | tbar | u0 | qh | 64 spare (u0, qh adjacent: one fill clears both).  Yields the vectors (null while qi, q are) and both lengths.
+    struct Work { NsEq Q; int64_t ilen = 0, dlen = 0; };
+    Work work(const NsLayout& L) const {
+        Work W;
+        auto I = [&](int64_t len) { int* p = qi ? qi + W.ilen : nullptr; W.ilen += len; return p; };
+        auto D = [&](int64_t len) { double* p = q ? q + W.dlen : nullptr; W.dlen += len; return p; };
+        NsEq& Q = W.Q; Q.ldc = fN.ld;
+        Q.sel = I(ccap); Q.bpos = I(L.ldn); Q.rpos = I(L.nIp); Q.cnt = I(16);
+        Q.Csel = D(ccap * Q.ldc); Q.d = D(ccap); Q.lam = D(ccap); Q.v = D(ccap); Q.w = D(ccap); Q.u = D(ccap);
+        Q.pbar = D(L.ldn); Q.tbar = D(L.Mp); Q.u0 = D(Q.ldc); Q.qh = D(Q.ldc + 64);
+        return W;
+    }
+    BufPool mem;                    // declared last, as in EvalState
+};
+// The null-space form of the interior-point Newton system (asm_ns_kernels.hip.h; oracle: class NullSpace): what do_setup makes for an LP
+// skeleton that qualifies (sparse pattern, enough hard equality rows, small null space).  The handle's pointer is null when it does not.
+struct NsForm {
+    const NsLayout L;
+    std::vector<int> eidx_h;        // host copy of Eidx: the equality rows in their reverse Cuthill-McKee order
+    int *Eidx = nullptr, *Epos = nullptr, *Iidx = nullptr, *Ipos = nullptr, *cnt = nullptr, *S0pairs = nullptr;
+    int64_t npairs = 0;             // structural non-zeros of the lower triangle of S0, listed in S0pairs (banded S0 only)
+    FacBuf f0;                      // factor of S0 = A_EF A_EF' (per LP)
+    double *Lt = nullptr, *th = nullptr, *Fm = nullptr, *v = nullptr, *Yt = nullptr;     // Yt: made by the first cold basis selection (Solver::ns_setup)
+    std::unique_ptr<NsK> k;
+    BufPool mem;                    // declared last, as in EvalState
+    explicit NsForm(const NsLayout& l) : L(l) {}
+};
+
 // environment knobs of a handle, read once in asm_create (README.md lists them)
 struct HandleKnobs {
     int timing = 1;                 // ASM_HIP_TIMING: 0, 1 or 2, the initial asm_handle::timing
@@ -428,9 +483,10 @@ struct asm_handle {
     std::string err;
     bool setup_done = false, inputs_ready = false;
     bool inputs_from_eval = false;  // the inputs came from asm_eval_functions: the evaluator's x, E and gradient in HBM are those of x_k
-    // owners of the device / pinned buffers, one per lifetime: the problem skeleton (until the next set-up), the null-space buffers sized
-    // by k (until the dimension outgrows them), the device evaluator with its own pool (until the next asm_eval_setup or set-up; null: none)
-    BufPool mem, mem_nsk;
+    // owners of the device / pinned buffers, one per lifetime: the problem skeleton (until the next set-up), the null-space form with its own
+    // pools (until the next set-up; null: the skeleton does not qualify), the device evaluator with its own (until the next asm_eval_setup or set-up; null: none)
+    BufPool mem;
+    std::unique_ptr<NsForm> nsf;
     std::unique_ptr<EvalState> ev;
 
     // ---- problem (subproblem.jl:51-215) ----
@@ -478,23 +534,12 @@ struct asm_handle {
     int nz_T = 0, nz_pitch = 0;
     double nz_fraction = 1.0;       // executed share of the (tile pair, k-chunk) products of the Schur build
     double nz_frac_cache[2] = {-1.0, -1.0};   // ... cached per handle: all rows / the equality rows (the pattern is fixed)
-    // ---- null-space form of the interior-point Newton system (asm_ns_kernels.hip.h; oracle: class NullSpace)
-    bool ns_cap = false;            // the LP skeleton qualifies (sparse pattern, enough hard equality rows, small null space)
-    int ns_nE = 0, ns_nI = 0, ns_nEp = 0, ns_nIp = 0, ns_kcap = 0;
-    int64_t ns_ldg = 0;
-    int *d_nsEidx = nullptr, *d_nsEpos = nullptr, *d_nsIidx = nullptr, *d_nsIpos = nullptr, *d_nsJ = nullptr, *d_nscnt = nullptr;
-    FacBuf ns_f0, ns_fN;            // factors of S0 = A_EF A_EF' (per LP) and of the k x k reduced matrix (per iteration)
-    double *d_nsLt = nullptr, *d_nsR = nullptr, *d_nsX = nullptr, *d_nsG = nullptr, *d_nsth = nullptr, *d_nsFm = nullptr, *d_nsv = nullptr, *d_nsYt = nullptr, *d_nsNp = nullptr, *d_nsN0 = nullptr, *d_nsZT = nullptr;
-    FacBuf ns_fC;                   // factor of the Gram matrix of the active constraints in reduced coordinates (active-set solves)
-    int ns_ccap = 0;                // most constraints it is sized for
-    int64_t ns_npairs = 0;          // structural non-zeros of the lower triangle of S0 (banded S0 only)
-    int* d_nsS0pairs = nullptr;
     // all M rows in reverse Cuthill-McKee order (sparse patterns whose bandwidth is below M / 2): the Gram matrices of row subsets taken in
     // that order are banded with half-bandwidth <= row_band
     int row_band = 0;
     int *d_rowperm = nullptr, *d_rowpos = nullptr, *d_rowpairs = nullptr, *d_cpos = nullptr;      // position -> row, row -> position, structural pairs (row_i, row_j), pos_i >= pos_j
     int64_t n_rowpairs = 0;
-    std::vector<int> row_perm_h, ns_eidx_h;      // host copies: rows by position (all rows; the equality rows of the null-space form)
+    std::vector<int> row_perm_h;    // host copy: rows by position
     int col_band = 0;               // the same for the n columns (column form of the restoration-phase Newton system)
     int *d_colperm = nullptr, *d_colpos = nullptr, *d_colpairs = nullptr;
     int64_t n_colpairs = 0;
@@ -508,9 +553,6 @@ struct asm_handle {
     int test_layout = 0, test_band_hint = 0, test_mode = 0;
     double test_rel = 0.0, test_abs = 0.0, test_thr = 1e-14;
     FacBuf test_fac;
-    int ns_Zk = 0;                  // rows of the orthonormal basis of the previous LP still resident in d_nsG (0: none)
-    int *d_nsqi = nullptr;          // sel | bpos | rpos | cnt
-    double *d_nsq = nullptr;        // Csel | d, u, lam, v, w | pbar, tbar, u0, qh
     double* d_ipm_snap = nullptr;   // best-iterate safeguard: copy of the iterate at the end of the best interior-point stage so far
     double* d_ipm = nullptr;        // arena of the device-resident interior-point state
     int* d_ipm_i = nullptr;
@@ -518,7 +560,8 @@ struct asm_handle {
     int* d_as_i = nullptr;
     int* h_ascnt = nullptr;         // pinned read-back of its counters / scalars
     double* h_asscal = nullptr;
-    double *d_Zbuf = nullptr, *d_nsu = nullptr, *d_nsdots = nullptr, *h_nsdots = nullptr;   // null-space active-set method (face_primal_anchored)
+    // anchored primal face method (face_primal_anchored), a null-space active-set method of its own: made for every skeleton, in `mem` - no part of NsForm
+    double *d_Zbuf = nullptr, *d_nsu = nullptr, *d_nsdots = nullptr, *h_nsdots = nullptr;
     std::vector<int64_t> j_row_h, j_col_h;   // j_str as asm_sublp_setup received it (the expression block's pattern is checked against it)
     bool J_valid = false;                              // the dense J in HBM matches the dE in HBM
     int64_t nsp = 0;
@@ -797,18 +840,18 @@ struct Dev {
         asmb::launch(k_schur_sparse, asmb::blocks(h->n_colpairs), dim3(256), h->stream, h->d_colpairs, h->n_colpairs, h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah),
                      dinv_dev, diag_place, f.S, f.ld, h->d_sc_pos);
     }
-    // S0 = A_EF diag(Fm) A_EF' of the null-space form (equality rows in their reverse Cuthill-McKee order, Fm in h->d_nsFm) into h->ns_f0.S
+    // S0 = A_EF diag(Fm) A_EF' of the null-space form (equality rows in their reverse Cuthill-McKee order, Fm in F.Fm) into F.f0.S
     void ns_build_S0() {
-        const int nE = h->ns_nE;
-        if (h->ns_f0.band > 0) {
+        NsForm& F = *h->nsf;
+        const int nE = (int)F.L.nE;
+        if (F.f0.band > 0) {
             // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
             // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
-            zero_band(h->ns_f0, nE, h->ns_f0.band);
-            asmb::launch(k_ns_s0_sparse, asmb::blocks(h->ns_npairs), dim3(256), h->stream, h->d_nsS0pairs, h->ns_npairs, h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah),
-                         h->d_nsEidx, h->d_nsFm, h->ns_f0.S, h->ns_f0.ld);
+            zero_band(F.f0, nE, F.f0.band);
+            asmb::launch(k_ns_s0_sparse, asmb::blocks(F.npairs), dim3(256), h->stream, F.S0pairs, F.npairs, h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), F.Eidx, F.Fm, F.f0.S, F.f0.ld);
         } else {
             // S0 = A_EF A_EF' (the share of its chunk products cached per handle: the equality rows are fixed)
-            schur_syrk(false, h->d_nsEidx, nE, h->d_nsFm, nullptr, h->ns_f0.S, h->ns_f0.ld, NzFlags::PerCall, 1);
+            schur_syrk(false, F.Eidx, nE, F.Fm, nullptr, F.f0.S, F.f0.ld, NzFlags::PerCall, 1);
         }
     }
     // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32
@@ -1293,25 +1336,6 @@ struct AsLayout {
     int64_t int_len() const { return 6 * (Mp + ldn + nsp) + 3 * Mp + 2 * ldn + 64; }
 };
 
-// Pitches and lengths of the buffers of the null-space form that do not depend on the null-space dimension, for an LP with nE hard equality
-// rows and nI inequality rows (do_setup allocates by them; Solver::nsv places the work vectors).  theta~ = [n-part (ldn) | I-part (nIp)], a row
-// of Gt = [Zt | GI'] has the same shape (pitch ldg).  Work vectors: five n-sized, three M-sized, two E-sized, then six more of n entries
-// (10 .. 13 hold k <= n entries, 14 = e, 15).  kcap: rows reserved for a basis of k rows (Solver::ns_reserve).
-struct NsLayout {
-    int64_t ldn, Mp, nE, nI, nEp, nIp, ldg;
-    NsLayout(int64_t ln, int64_t lm, int64_t ne, int64_t ni)
-        : ldn(ln), Mp(lm), nE(ne), nI(ni), nEp(round_up(ne, 32)), nIp(round_up(std::max<int64_t>(ni, 1), 32)), ldg(ln + nIp) {}
-    int64_t th_len() const { return ldg; }
-    int64_t nsv_len() const { return 11 * ldn + 3 * Mp + 2 * nEp; }
-    int64_t nsv_off(int which) const {
-        if (which < 5) return (int64_t)which * ldn;
-        if (which < 8) return 5 * ldn + (int64_t)(which - 5) * Mp;
-        if (which < 10) return 5 * ldn + 3 * Mp + (int64_t)(which - 8) * nEp;
-        return 5 * ldn + 3 * Mp + 2 * nEp + (int64_t)(which - 10) * ldn;
-    }
-    static int kcap(int k) { return (int)round_up(k + k / 4 + 64, 64); }
-};
-
 // Sequence number for the next publishing kernel (0 = the kernel does not publish: copy path)
 unsigned pub_next(asm_handle* h) {
     if (!h->knobs.spin_read) return 0;
@@ -1602,128 +1626,115 @@ struct Solver {
     bool ns_lp = false;       // this LP has a valid null-space basis (set up before the warm attempt: the active-set solves use it too)
     int ns_k = 0;
     SolveHint* cur_hint = nullptr;
-    // where the buffers of a null-space iteration live: the handle's (ns_bind()), or buffers of a test hook's with the pitches of NsLayout
+    // non-owning view of the buffers of a null-space iteration: the form's (ns_bind()), or buffers of a test hook's with the pitches of NsLayout
     struct NsArena {
         double *v = nullptr, *th = nullptr, *G = nullptr, *N0 = nullptr, *partial = nullptr;      // work vectors, theta~, Gt, unregularised N, scratch of Zt' u
         const FacBuf* fN = nullptr;
         const int *sp_ptr = nullptr, *sp_col = nullptr, *sc_ptr = nullptr, *sc_row = nullptr, *sc_pos = nullptr;
         const double* vals = nullptr;     // values of the sparse pattern; null: the handle's gathered copy of Ah (Dev::sparse_vals)
         NsIdx X = {nullptr, nullptr, nullptr, nullptr, 0, 0};
-        int64_t ldn = 0, Mp = 0, nEp = 0, nIp = 0, ldg = 0;
-        int64_t voff[16] = {0};           // offsets of the work vectors in v (NsLayout::nsv_off)
+        NsLayout L{0, 0, 0, 0};           // pitches, and the offsets of the work vectors in v (nsv)
     } ns_ar;
-    // bound once per LP, like the interior-point arena: at the start of ns_setup and again when ns_reserve has made the k-sized buffers
+    // bound once per LP, like the interior-point arena: at the start of ns_setup (the k-sized buffers may be missing) and again after ns_reserve
     void ns_bind() {
+        const NsForm& F = *h->nsf;
         NsArena a;
-        a.v = h->d_nsv; a.th = h->d_nsth; a.G = h->d_nsG; a.N0 = h->d_nsN0; a.partial = h->d_partial;
-        a.fN = &h->ns_fN;
+        a.v = F.v; a.th = F.th; a.partial = h->d_partial;
+        if (F.k) { a.G = F.k->G; a.N0 = F.k->N0; a.fN = &F.k->fN; }
         a.sp_ptr = h->d_sp_ptr; a.sp_col = h->d_sp_col; a.sc_ptr = h->d_sc_ptr; a.sc_row = h->d_sc_row; a.sc_pos = h->d_sc_pos;
-        a.X.Eidx = h->d_nsEidx; a.X.Epos = h->d_nsEpos; a.X.Iidx = h->d_nsIidx; a.X.Ipos = h->d_nsIpos; a.X.nE = h->ns_nE; a.X.nI = h->ns_nI;
-        a.ldn = h->ldn; a.Mp = h->Mp; a.nEp = h->ns_nEp; a.nIp = h->ns_nIp; a.ldg = h->ns_ldg;
+        a.X = NsIdx{F.Eidx, F.Epos, F.Iidx, F.Ipos, (int)F.L.nE, (int)F.L.nI}; a.L = F.L;
         ns_bind(a);
     }
-    void ns_bind(const NsArena& a) {
-        ns_ar = a;
-        const NsLayout nl(a.ldn, a.Mp, a.X.nE, a.X.nI);
-        for (int w = 0; w < 16; ++w) ns_ar.voff[w] = nl.nsv_off(w);
-    }
+    void ns_bind(const NsArena& a) { ns_ar = a; }
     const NsArena& nsa() const { return ns_ar; }
     NsIdx nsX() const { return nsa().X; }
     const double* ns_vals() { const NsArena& a = nsa(); return a.vals ? a.vals : dev.sparse_vals(h->d_Ah); }
-    int ns_read_cnt() {
+    int ns_count_big(const FacBuf& f, int order) {      // dropped pivots of the factor just made in f
         int v = 0;
-        HIPCHK(asmb::copy_async(&v, h->d_nscnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, f.S, f.ld, order, NS_BIG, h->nsf->cnt);
+        HIPCHK(asmb::copy_async(&v, h->nsf->cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
         return v;
     }
     // buffers sized by the null-space dimension: right-hand-side blocks R, X (k x nEp), Gt = [Zt | GI'] (k x ldg), the k x k factor
     void ns_reserve(int k) {
-        if (k <= h->ns_kcap) return;
-        if (h->ns_kcap > 0) {
+        NsForm& F = *h->nsf;
+        if (F.k && k <= F.k->cap) return;
+        if (F.k) {
             // the null space grew beyond what the first LP of the form reserved (fewer fixed columns than then): the k-sized buffers are
             // released and re-made; the carried basis goes with them
-            if (h->knobs.verbose) std::fprintf(stderr, "[asm] null-space form: dimension %d exceeds the reserved %d - buffers re-allocated\n", k, h->ns_kcap);
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] null-space form: dimension %d exceeds the reserved %d - buffers re-allocated\n", k, F.k->cap);
             HIPCHK(asmb::sync(h->stream));
-            h->mem_nsk.release();
-            h->ns_fN = FacBuf(); h->ns_fC = FacBuf();
-            h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0;
+            F.k.reset();
         }
-        BufPool& P = h->mem_nsk;
-        const int cap = NsLayout::kcap(k);
-        P.zeroed(h->d_nsR, (int64_t)cap * h->ns_nEp, h->stream);
-        P.zeroed(h->d_nsX, (int64_t)cap * h->ns_nEp, h->stream);
-        P.zeroed(h->d_nsG, (int64_t)cap * h->ns_ldg, h->stream);
-        ns_alloc_factor(h, P, h->ns_fN, cap);
-        h->ns_fN.small = true;
-        P.zeroed(h->d_nsN0, h->ns_fN.ld * h->ns_fN.ld, h->stream);
-        P.zeroed(h->d_nsNp, NS_MAX_SPLIT * h->ns_fN.ld * h->ns_fN.ld, h->stream);       // split-K slices of the reduced Newton matrix
-        P.zeroed(h->d_nsZT, h->ldn * h->ns_fN.ld, h->stream);        // transposed copy of the basis rows (right operand of the orthonormalisation product)
-        P.alloc(h->d_nsJ, cap);
-        h->ns_kcap = cap;
+        auto K = std::make_unique<NsK>();
+        BufPool& P = K->mem;
+        const int cap = K->cap = NsLayout::kcap(k);
+        P.zeroed(K->R, (int64_t)cap * F.L.nEp, h->stream); P.zeroed(K->X, (int64_t)cap * F.L.nEp, h->stream);
+        P.zeroed(K->G, (int64_t)cap * F.L.ldg, h->stream);
+        ns_alloc_factor(h, P, K->fN, cap); K->fN.small = true;
+        P.zeroed(K->N0, K->fN.ld * K->fN.ld, h->stream);
+        P.zeroed(K->Np, NS_MAX_SPLIT * K->fN.ld * K->fN.ld, h->stream);       // split-K slices of the reduced Newton matrix
+        P.zeroed(K->ZT, F.L.ldn * K->fN.ld, h->stream);       // transposed copy of the basis rows (right operand of the orthonormalisation product)
+        P.alloc(K->J, cap);
         // active-set solves in reduced coordinates: up to 2 cap constraints (an over-determined working set has more than k)
-        h->ns_ccap = (int)std::min<int64_t>(2 * cap, h->Mp);
-        ns_alloc_factor(h, P, h->ns_fC, h->ns_ccap);
-        h->ns_fC.small = true;
-        P.alloc(h->d_nsqi, (int64_t)h->ns_ccap + h->ldn + h->ns_nIp + 16);
-        P.zeroed(h->d_nsq, (int64_t)h->ns_ccap * h->ns_fN.ld + 5 * (int64_t)h->ns_ccap + h->ldn + h->Mp + 2 * h->ns_fN.ld + 64, h->stream);
+        K->ccap = (int)std::min<int64_t>(2 * cap, F.L.Mp);
+        ns_alloc_factor(h, P, K->fC, K->ccap); K->fC.small = true;
+        const NsK::Work W = K->work(F.L);
+        P.alloc(K->qi, W.ilen); P.zeroed(K->q, W.dlen, h->stream);
         HIPCHK(asmb::sync(h->stream));
+        F.k = std::move(K);
     }
-    // In place  Zt = L^-1 Zt  with the k x k factor just made in h->ns_fN.  When the factor fits into one wide block the explicit inverse of
+    // In place  Zt = L^-1 Zt  with the k x k factor just made in K.fN.  When the factor fits into one wide block the explicit inverse of
     // that block IS L^-1: one transpose + one product on the matrix cores (the rows are n long); otherwise forward substitution per column.
     void ns_ortho(int k) {
-        if (k <= h->ns_fN.wb) {
+        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        if (k <= K.fN.wb) {
             const int kp = (int)round_up(k, 32);
-            asmb::launch(k_transpose_dense, dim3((unsigned)((h->ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), h->stream, h->d_nsG, h->ns_ldg, (int64_t)k, h->ldn,
-                         h->d_nsZT, h->ns_fN.ld, (int64_t)-1);
-            dev.gemm_nt(h->ns_fN.Binv, h->ns_fN.wb, h->d_nsZT, h->ns_fN.ld, nullptr, 0, h->d_nsG, h->ns_ldg, k, (int)h->ldn, kp, 0);
+            asmb::launch(k_transpose_dense, dim3((unsigned)((h->ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), h->stream, K.G, F.L.ldg, (int64_t)k, h->ldn, K.ZT, K.fN.ld, (int64_t)-1);
+            dev.gemm_nt(K.fN.Binv, K.fN.wb, K.ZT, K.fN.ld, nullptr, 0, K.G, F.L.ldg, k, (int)h->ldn, kp, 0);
         } else {
-            asmb::launch(k_ns_ortho, asmb::blocks(h->ldn), dim3(256), h->stream, h->ns_fN.S, h->ns_fN.ld, k, h->d_nsG, h->ns_ldg, h->ldn);
+            asmb::launch(k_ns_ortho, asmb::blocks(h->ldn), dim3(256), h->stream, K.fN.S, K.fN.ld, k, K.G, F.L.ldg, h->ldn);
         }
     }
-    // The k rows in d_nsG (an approximate or an outdated basis) projected onto null(A_EF) of THIS LP and orthonormalised with their own
+    // The k rows in K.G (an approximate or an outdated basis) projected onto null(A_EF) of THIS LP and orthonormalised with their own
     // Gram matrix (pivot guard `thr`, absolute), then GI' = (A_I Z)'.  Used as the second pass of ns_basis_from and, with the previous
-    // LP's basis, as the whole set-up (oracle: NullSpace.__init__, warm_Z).  The factor of S0 must be current in h->ns_f0.
+    // LP's basis, as the whole set-up (oracle: NullSpace.__init__, warm_Z).  The factor of S0 must be current in F.f0.
     bool ns_reproject(int k, double thr) {
-        const int nE = h->ns_nE;
+        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const int nE = (int)F.L.nE, nEp = (int)F.L.nEp, nIp = (int)F.L.nIp;
         const NsIdx X = nsX();
         const double* vals = dev.sparse_vals(h->d_Ah);
         // second pass (oracle: NullSpace.basis_from): project the rows once more and orthonormalise with their own Gram matrix (~ I) -
         // the columns picked in index order can be badly conditioned, and the active-set solves need A_EF Z = 0 to 1e-13
-        asmb::launch(k_ns_rows_e, dim3((unsigned)((h->ns_nEp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, h->d_nsFm, h->d_nsG, h->ns_ldg,
-                     h->d_nsR, (int64_t)h->ns_nEp);
-        dev.trsm_rows(h->ns_f0, h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
-        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm,
-                     h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 1);
-        dev.launch_syrk(h->stream, Dev::pick_tile(k), h->d_nsG, h->ns_ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, h->ns_fN.S, h->ns_fN.ld, 0, 0);
+        asmb::launch(k_ns_rows_e, dim3((unsigned)((nEp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
+        dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
+        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, h->ldn, 1);
+        dev.launch_syrk(h->stream, Dev::pick_tile(k), K.G, F.L.ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, K.fN.S, K.fN.ld, 0, 0);
         dev.launch_ns_fill(h->d_diag0, 1.0, (int64_t)k);
-        dev.chol(h->ns_fN, k, thr);
-        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
-        const int bad2 = ns_read_cnt();
-        if (bad2 > 0) return false;
+        dev.chol(K.fN, k, thr);
+        if (ns_count_big(K.fN, k) > 0) return false;
         ns_ortho(k);
-        asmb::launch(k_ns_gi, dim3((unsigned)((h->ns_nIp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, h->d_nsG, h->ns_ldg,
-                     h->d_nsG + h->ldn, h->ns_nIp);
+        asmb::launch(k_ns_gi, dim3((unsigned)((nIp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, K.G, F.L.ldg, K.G + h->ldn, nIp);
         return true;
     }
     // Orthonormal basis from the columns J of the projector P (oracle: NullSpace.basis_from): W = S0^-1 A_EF[:, J] by block
     // substitution with all k right-hand sides at once, P[J, :] = E_J' - W' A_EF, L_J L_J' = P[J, J] (guard: pivot <= NS_WARM_THR
-    // -> not a basis), Zt = L_J^-1 P[J, :], GI' = (A_I Z)'.  The factor of S0 must be current in h->ns_f0.
+    // -> not a basis), Zt = L_J^-1 P[J, :], GI' = (A_I Z)'.  The factor of S0 must be current in F.f0.
     bool ns_basis_from(const std::vector<int>& J) {
-        const int k = (int)J.size(), nE = h->ns_nE;
+        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const int k = (int)J.size(), nE = (int)F.L.nE, nEp = (int)F.L.nEp;
         const NsIdx X = nsX();
         const double* vals = dev.sparse_vals(h->d_Ah);
-        HIPCHK(asmb::copy_async(h->d_nsJ, J.data(), k * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(K.J, J.data(), k * sizeof(int), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);
-        asmb::launch(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm, h->d_nsR, (int64_t)h->ns_nEp);
-        dev.trsm_rows(h->ns_f0, h->d_nsR, h->d_nsX, h->ns_nEp, k, nE, h->d_nsLt);
-        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, h->d_nsJ, h->d_nsFm,
-                     h->d_nsR, (int64_t)h->ns_nEp, h->d_nsG, h->ns_ldg, lp.n, h->ldn, 0);
-        asmb::launch(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_nsG, h->ns_ldg, h->d_nsJ, k, h->ns_fN.S, h->ns_fN.ld);
+        asmb::launch(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp);
+        dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
+        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, h->ldn, 0);
+        asmb::launch(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, K.G, F.L.ldg, K.J, k, K.fN.S, K.fN.ld);
         dev.launch_ns_fill(h->d_diag0, 1.0, (int64_t)k);
-        dev.chol(h->ns_fN, k, NS_WARM_THR);
-        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_fN.S, h->ns_fN.ld, k, NS_BIG, h->d_nscnt);
-        const int bad = ns_read_cnt();
-        if (bad > 0) return false;
+        dev.chol(K.fN, k, NS_WARM_THR);
+        if (ns_count_big(K.fN, k) > 0) return false;
         ns_ortho(k);
         return ns_reproject(k, NS_WARM_THR);
     }
@@ -1731,21 +1742,17 @@ struct Solver {
     // P in index order), orthonormal basis.  False: the LP keeps the row form.
     bool ns_setup() {
         ns_bind();
-        const int nE = h->ns_nE;
+        NsForm& F = *h->nsf;
+        const int nE = (int)F.L.nE, nEp = (int)F.L.nEp;
         const int64_t n = lp.n;
         const NsIdx X = nsX();
         int64_t nF = 0;
         for (int64_t j = 0; j < n; ++j) nF += lp.ub[j] > lp.lb[j];
         {
-            if (!asmb::in_fiber()) {                // (pinned staging: the copy does not go through the runtime's pageable path)
-                double* fm = h->h_pin;
-                for (int64_t j = 0; j < h->ldn; ++j) fm[j] = (j < n && lp.ub[j] > lp.lb[j]) ? 1.0 : 0.0;
-                HIPCHK(asmb::copy_async(h->d_nsFm, fm, h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            } else {
-                vec fm(h->ldn, 0.0);
-                for (int64_t j = 0; j < n; ++j) fm[j] = lp.ub[j] > lp.lb[j] ? 1.0 : 0.0;
-                HIPCHK(asmb::copy_async(h->d_nsFm, fm.data(), h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            }
+            vec own(asmb::in_fiber() ? h->ldn : 0);
+            double* fm = asmb::in_fiber() ? own.data() : h->h_pin;      // (pinned staging: the copy does not go through the runtime's pageable path)
+            for (int64_t j = 0; j < h->ldn; ++j) fm[j] = (j < n && lp.ub[j] > lp.lb[j]) ? 1.0 : 0.0;
+            HIPCHK(asmb::copy_async(F.Fm, fm, h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
             h2d_done(h);
         }
         double t_v = now_ms();
@@ -1758,24 +1765,23 @@ struct Solver {
         };
         dev.ns_build_S0();
         vlap("S0 build");
-        dev.diag_prepare(h->ns_f0, nE, 1, 0.0, 0.0);
-        dev.chol(h->ns_f0, nE, 1e-10);
+        dev.diag_prepare(F.f0, nE, 1, 0.0, 0.0);
+        dev.chol(F.f0, nE, 1e-10);
         vlap("S0 factor");
-        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, h->ns_f0.S, h->ns_f0.ld, nE, NS_BIG, h->d_nscnt);
-        const int dropped = ns_read_cnt();
+        const int dropped = ns_count_big(F.f0, nE);
         const int64_t k = nF - (nE - dropped);
         if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
         ns_reserve((int)k);
         ns_bind();
-        asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), h->stream, h->ns_f0.S, h->ns_f0.ld, (int64_t)nE, (int64_t)nE,
-                     h->d_nsLt, h->ns_f0.ld, (int64_t)(h->ns_f0.band > 0 ? h->ns_f0.band : nE));
+        asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), h->stream, F.f0.S, F.f0.ld, (int64_t)nE, (int64_t)nE,
+                     F.Lt, F.f0.ld, (int64_t)(F.f0.band > 0 ? F.f0.band : nE));
         std::vector<int>& J = cur_hint->ns_J;
         bool have = false;
         ns_was_cold = false;
         vlap("Lt");
-        if (h->ns_Zk == (int)k) have = ns_reproject((int)k, NS_ZWARM_THR);      // the previous LP's basis, one projection pass
+        if (F.k->Zk == (int)k) have = ns_reproject((int)k, NS_ZWARM_THR);      // the previous LP's basis, one projection pass
         vlap("reproject");
-        h->ns_Zk = 0;
+        F.k->Zk = 0;
         if (!have && (int64_t)J.size() == k) {
             bool free_all = true;
             for (int j : J) free_all = free_all && j >= 0 && j < n && lp.ub[j] > lp.lb[j];
@@ -1785,18 +1791,18 @@ struct Solver {
             ns_was_cold = true;
             // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main factor,
             // guarded Cholesky of T in index order with the absolute thresholds NS_SEL_THR in turn until exactly k columns are kept
-            if (!h->d_nsYt) h->mem.zeroed(h->d_nsYt, (int64_t)h->ldn * h->ns_nEp + (int64_t)h->ldn * h->ns_nEp, h->stream);
-            double* Yr = h->d_nsYt;                                  // right-hand sides, then garbage
-            double* Yt = h->d_nsYt + (int64_t)h->ldn * h->ns_nEp;   // L0^-1 a_j as rows
+            if (!F.Yt) F.mem.zeroed(F.Yt, (int64_t)h->ldn * nEp + (int64_t)h->ldn * nEp, h->stream);
+            double* Yr = F.Yt;                                  // right-hand sides, then garbage
+            double* Yt = F.Yt + (int64_t)h->ldn * nEp;   // L0^-1 a_j as rows
             const double* vals = dev.sparse_vals(h->d_Ah);
-            asmb::launch(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, nullptr, h->d_nsFm, Yr, (int64_t)h->ns_nEp);
-            dev.trsm_rows(h->ns_f0, Yr, Yt, h->ns_nEp, (int)n, nE, nullptr);
+            asmb::launch(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, nullptr, F.Fm, Yr, (int64_t)nEp);
+            dev.trsm_rows(F.f0, Yr, Yt, nEp, (int)n, nE, nullptr);
             std::vector<double> dg(n);
             FacBuf& T = h->main_fac;
             T.band = 0;
             for (int a = 0; a < 4 && !have; ++a) {
-                asmb::launch(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_nsFm);
-                dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, h->ns_nEp, nullptr, 0, (int)n, h->ns_nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
+                asmb::launch(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), h->stream, T.S, T.ld, (int)n, F.Fm);
+                dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, nEp, nullptr, 0, (int)n, nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
                 dev.launch_ns_fill(h->d_diag0, 1.0, n);
                 dev.chol(T, (int)n, NS_SEL_THR[a]);
                 asmb::launch(k_ns_diag, asmb::blocks(n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_vecN);
@@ -1811,29 +1817,19 @@ struct Solver {
         }
         if (!have) { J.clear(); return false; }
         ns_k = (int)k;
-        h->ns_Zk = (int)k;
+        F.k->Zk = (int)k;
         return true;
     }
-    double* nsv(int which) const { return ns_ar.v + ns_ar.voff[which]; }      // work vectors: 0..4 n-sized, 5..7 M-sized, 8..9 E-sized, 10..13 k-sized (k <= n), 14..15 n-sized (14 = e)
+    double* nsv(int which) const { return ns_ar.v + ns_ar.L.nsv_off(which); }      // work vectors: 0..4 n-sized, 5..7 M-sized, 8..9 E-sized, 10..13 k-sized (k <= n), 14..15 n-sized (14 = e)
     // oracle: ns_applicable
     bool ns_applicable() const {
-        if (!h->ns_cap || lp.ns != 0) return false;
+        if (!h->nsf || lp.ns != 0) return false;
         int64_t nE = 0, nF = 0;
         for (int64_t i = 0; i < lp.M; ++i) nE += lp.rtype[i] == 0;
         for (int64_t j = 0; j < lp.n; ++j) nF += lp.ub[j] > lp.lb[j];
         return nE >= NS_MIN_E && (double)(nF - nE) <= NS_MAX_RATIO * (double)lp.M;
     }
-    NsEq nsq() const {
-        NsEq Q;
-        int* qi = h->d_nsqi;
-        Q.sel = qi; Q.bpos = qi + h->ns_ccap; Q.rpos = Q.bpos + h->ldn; Q.cnt = Q.rpos + h->ns_nIp;
-        double* b = h->d_nsq;
-        Q.ldc = h->ns_fN.ld;
-        Q.Csel = b; b += (int64_t)h->ns_ccap * Q.ldc;
-        Q.d = b; b += h->ns_ccap; Q.lam = b; b += h->ns_ccap; Q.v = b; b += h->ns_ccap; Q.w = b; b += h->ns_ccap; Q.u = b; b += h->ns_ccap;
-        Q.pbar = b; b += h->ldn; Q.tbar = b; b += h->Mp; Q.u0 = b; b += Q.ldc; Q.qh = b;
-        return Q;
-    }
+    NsEq nsq() const { return h->nsf->k->work(h->nsf->L).Q; }
     // dense products with the gathered constraint matrix Csel (nact rows of pitch ldc)
     void nsq_gemv_n(const NsEq& Q, int nact, const double* x, double* out) {
         asmb::launch(k_gemv_n, asmb::blocks(nact, 4), dim3(256), h->stream, Q.Csel, Q.ldc, x, out, (int64_t)nact, Q.ldc);
@@ -1847,7 +1843,8 @@ struct Solver {
     }
     // per LP (oracle: eqp_ns, the part that does not depend on the working set): pbar, A pbar, u0 = Z'(p_ref - pbar), Z'q
     void ns_lp_vectors() {
-        const int k = ns_k, nE = h->ns_nE;
+        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const int k = ns_k, nE = (int)F.L.nE;
         const int64_t ldn = h->ldn;
         const NsIdx X = nsX();
         const NsEq Q = nsq();
@@ -1856,19 +1853,20 @@ struct Solver {
         asmb::launch(k_nseq_pfix, dim3(gN), dim3(256), h->stream, A, pfix, ldn);
         dev.gemv_n_dev(h->d_Ah, pfix, aM);
         asmb::launch(k_nseq_be, dim3(gE), dim3(256), h->stream, A, X, aM, rE);
-        dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
+        dev.chol_solve_dev(F.f0, rE, tE, nE);
         launch_ns_rowvec_e(tE, yM);
         dev.gemv_t_dev(h->d_Ah, yM, x);
         asmb::launch(k_nseq_pbar, dim3(gN), dim3(256), h->stream, A, pfix, x, d_zero, Q.pbar, vz, ldn);
         dev.gemv_n_dev(h->d_Ah, Q.pbar, Q.tbar);
         HIPCHK(asmb::fill_async(Q.u0, 0, 2 * Q.ldc * sizeof(double), h->stream));      // u0 and qh (contiguous)
-        gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)vz, Q.u0, (int64_t)k, ldn);
-        gemv_rows((const double*)h->d_nsG, h->ns_ldg, (const double*)A.q, Q.qh, (int64_t)k, ldn);
+        gemv_rows((const double*)K.G, F.L.ldg, (const double*)vz, Q.u0, (int64_t)k, ldn);
+        gemv_rows((const double*)K.G, F.L.ldg, (const double*)A.q, Q.qh, (int64_t)k, ldn);
     }
     // Equality-constrained solve on the working set `cur` in reduced coordinates (oracle: eqp_ns).  Leaves p, y, t = Ah p, tN = Ah' y
     // for the tail kernel like as_solve.  False: more active constraints than the buffers hold (the caller uses as_solve).
     bool as_solve_ns(const AsSets& cur) {
-        const int k = ns_k, nE = h->ns_nE;
+        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const int k = ns_k, nE = (int)F.L.nE;
         const int64_t M = lp.M, n = lp.n, ldn = h->ldn;
         const NsIdx X = nsX();
         const NsEq Q = nsq();
@@ -1878,14 +1876,14 @@ struct Solver {
         HIPCHK(asmb::copy_async(cnt, Q.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
         const int nact = cnt[1];
-        if (nact > NS_CMAX * k || nact > h->ns_ccap) return false;             // oracle: eqp_ns returns None - the polish attempt ends (eqp_loop)
+        if (nact > NS_CMAX * k || nact > K.ccap) return false;             // oracle: eqp_ns returns None - the polish attempt ends (eqp_loop)
         const unsigned gC = (unsigned)((Q.ldc + 255) / 256), gA = (unsigned)((nact + 255) / 256);
         double *t1 = nsv(12), *t2 = nsv(13);
         HIPCHK(asmb::copy_async(Q.u, Q.u0, Q.ldc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(asmb::fill_async(Q.lam, 0, (size_t)h->ns_ccap * sizeof(double), h->stream));
+        HIPCHK(asmb::fill_async(Q.lam, 0, (size_t)K.ccap * sizeof(double), h->stream));
         if (nact > 0) {
-            asmb::launch(k_nseq_gather, dim3(gC, (unsigned)nact), dim3(256), h->stream, A, cur, X, Q, h->d_nsG, h->ns_ldg, k, ldn);
-            const FacBuf& C = h->ns_fC;
+            asmb::launch(k_nseq_gather, dim3(gC, (unsigned)nact), dim3(256), h->stream, A, cur, X, Q, K.G, F.L.ldg, k, ldn);
+            const FacBuf& C = K.fC;
             dev.launch_syrk(h->stream, Dev::pick_tile(nact), Q.Csel, Q.ldc, nullptr, 0, nact, (int)Q.ldc, nullptr, nullptr, C.S, C.ld, 0, 0);
             dev.diag_prepare(C, nact, 1, 0.0, 0.0);
             dev.chol(C, nact, 1e-10, false);
@@ -1910,7 +1908,7 @@ struct Solver {
         asmb::launch(k_nseq_w, dim3(gN), dim3(256), h->stream, A, Q, atw, wN, ldn);
         dev.gemv_n_dev(h->d_Ah, wN, aM);
         launch_ns_gather_e(aM, 1.0, rE);
-        dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
+        dev.chol_solve_dev(F.f0, rE, tE, nE);
         asmb::launch(k_nseq_y, dim3(gM), dim3(256), h->stream, A, X, yM, tE);
         dev.gemv_n_dev(h->d_Ah, A.p, A.t);
         dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
@@ -1922,11 +1920,12 @@ struct Solver {
     // least-squares multipliers of the equality rows for the current iterate (oracle: IPM.ns_finish_y); P.rdp is the dual residual of the last
     // measures (with the equality multipliers as they stand: 0, or the values recovered at the end of the previous stage)
     void ns_finish_y() {
-        const int nE = h->ns_nE;
+        const NsForm& F = *h->nsf;
+        const int nE = (int)F.L.nE;
         double *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         dev.gemv_n_dev(h->d_Ah, P.rdp, aM);
         launch_ns_gather_e(aM, 1.0, rE);
-        dev.chol_solve_dev(h->ns_f0, rE, tE, nE);
+        dev.chol_solve_dev(F.f0, rE, tE, nE);
         // P.rdp already contains -A_E'y_E of the multipliers recovered at the end of an earlier stage: the solve gives the correction
         launch_ns_scatter_e(tE, P.y, 1);
     }
@@ -1934,59 +1933,59 @@ struct Solver {
     // through these members only; each carries its launch's grid and returns the number of workgroups it launched
     unsigned launch_theta_ns(double rho_p) {
         const NsArena& a = nsa();
-        const unsigned g = std::max(grid_all(), (unsigned)((std::max<int64_t>(a.ldn, a.nIp) + 255) / 256));
-        asmb::launch(k_ipm_theta_ns, dim3(g), dim3(256), h->stream, P, rho_p, a.X, a.th, a.ldn, (int)a.nIp);
+        const unsigned g = std::max(grid_all(), (unsigned)((std::max<int64_t>(a.L.ldn, a.L.nIp) + 255) / 256));
+        asmb::launch(k_ipm_theta_ns, dim3(g), dim3(256), h->stream, P, rho_p, a.X, a.th, a.L.ldn, (int)a.L.nIp);
         return g;
     }
     unsigned launch_ns_update(const IpmDir& C, double al, double be, double es) {
         const unsigned g = grid_all();
-        asmb::launch(k_ns_update, dim3(g), dim3(256), h->stream, P, C, al, be, nsv(14), es, nsa().ldn);
+        asmb::launch(k_ns_update, dim3(g), dim3(256), h->stream, P, C, al, be, nsv(14), es, nsa().L.ldn);
         return g;
     }
     unsigned launch_ns_update_dev(const IpmDir& C, double eta, double rerr) {
         const unsigned g = grid_all();
-        asmb::launch(k_ns_update_dev, dim3(g), dim3(256), h->stream, P, C, eta, nsv(14), nsa().ldn, rerr);
+        asmb::launch(k_ns_update_dev, dim3(g), dim3(256), h->stream, P, C, eta, nsv(14), nsa().L.ldn, rerr);
         return g;
     }
     unsigned launch_ns_dinf(const double* zr, int k, unsigned pub) { asmb::launch(k_ns_dinf, dim3(1), dim3(1024), h->stream, P, zr, k, pub); return 1; }
     // out[k] = Zt x   (x of ldn entries)
-    unsigned launch_ns_zt(const double* x, double* out, int k) { const NsArena& a = nsa(); return gemv_rows((const double*)a.G, a.ldg, x, out, (int64_t)k, a.ldn); }
+    unsigned launch_ns_zt(const double* x, double* out, int k) { const NsArena& a = nsa(); return gemv_rows((const double*)a.G, a.L.ldg, x, out, (int64_t)k, a.L.ldn); }
     unsigned launch_ns_e0(const double* pbar, double* d0) {
         const NsArena& a = nsa();
-        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
-        asmb::launch(k_ns_e0, dim3(gN), dim3(256), h->stream, P, pbar, d0, a.ldn);
+        const unsigned gN = (unsigned)((a.L.ldn + 255) / 256);
+        asmb::launch(k_ns_e0, dim3(gN), dim3(256), h->stream, P, pbar, d0, a.L.ldn);
         return gN;
     }
     unsigned launch_ns_e1(const double* d0, const double* zz, double* e) {
         const NsArena& a = nsa();
-        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
-        asmb::launch(k_ns_e1, dim3(gN), dim3(256), h->stream, P, d0, zz, e, a.ldn);
+        const unsigned gN = (unsigned)((a.L.ldn + 255) / 256);
+        asmb::launch(k_ns_e1, dim3(gN), dim3(256), h->stream, P, d0, zz, e, a.L.ldn);
         return gN;
     }
     // dpbar = -e, SC_NSERR = 0, yM = D_I^-1 (Ah dpbar)
     unsigned launch_ns_spmvn_wm_neg(const double* vals) {
         const NsArena& a = nsa();
-        const unsigned gM = (unsigned)((lp.M + 255) / 256), gN = (unsigned)((a.ldn + 255) / 256), g = std::max(gM, gN);
-        asmb::launch(k_ns_spmvn_wm_neg, dim3(g), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, nsv(14), nsv(0), a.ldn, P.scal + SC_NSERR, a.X, (const double*)(a.th + a.ldn), nsv(5), lp.M);
+        const unsigned gM = (unsigned)((lp.M + 255) / 256), gN = (unsigned)((a.L.ldn + 255) / 256), g = std::max(gM, gN);
+        asmb::launch(k_ns_spmvn_wm_neg, dim3(g), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, nsv(14), nsv(0), a.L.ldn, P.scal + SC_NSERR, a.X, (const double*)(a.th + a.L.ldn), nsv(5), lp.M);
         return g;
     }
     // K dpbar = Th dpbar + Ah' yM
     unsigned launch_ns_spmvt_kx(const double* vals) {
         const NsArena& a = nsa();
-        const dim3 g = asmb::blocks(a.ldn * 8);
-        asmb::launch(k_ns_spmvt_kx, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, nsv(0), nsv(1), lp.n, a.ldn);
+        const dim3 g = asmb::blocks(a.L.ldn * 8);
+        asmb::launch(k_ns_spmvt_kx, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, nsv(0), nsv(1), lp.n, a.L.ldn);
         return g.x;
     }
     unsigned launch_ns_rhs1_bi(const IpmDir& base, int mode, double res) {
         const NsArena& a = nsa();
         const unsigned g = grid_all();
-        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), h->stream, P, base, mode, a.X, (const double*)(a.th + a.ldn), res, nsv(7), nsv(5));
+        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), h->stream, P, base, mode, a.X, (const double*)(a.th + a.L.ldn), res, nsv(7), nsv(5));
         return g;
     }
     unsigned launch_ns_spmvt_ht(const double* vals, double res) {
         const NsArena& a = nsa();
-        const dim3 g = asmb::blocks(a.ldn * 8);
-        asmb::launch(k_ns_spmvt_ht, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, P.hp, nsv(1), res, nsv(2), nsv(3), lp.n, a.ldn);
+        const dim3 g = asmb::blocks(a.L.ldn * 8);
+        asmb::launch(k_ns_spmvt_ht, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, P.hp, nsv(1), res, nsv(2), nsv(3), lp.n, a.L.ldn);
         return g.x;
     }
     unsigned launch_ns_reduced_solve(int k, const double* ru, double* du) {
@@ -2008,20 +2007,20 @@ struct Solver {
     unsigned launch_ns_relres(const double* r, const double* rhs, int k) { asmb::launch(k_ns_relres, dim3(1), dim3(1024), h->stream, r, rhs, k, P.scal + SC_NSERR); return 1; }
     unsigned launch_ns_gemv_t_small_dp(int k, const double* du, const IpmDir& D, double res) {
         const NsArena& a = nsa();
-        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
-        asmb::launch(k_gemv_t_small_dp, dim3(gN), dim3(256), h->stream, a.G, a.ldg, k, du, P, D, (const double*)a.th, nsv(0), res, a.ldn);
+        const unsigned gN = (unsigned)((a.L.ldn + 255) / 256);
+        asmb::launch(k_gemv_t_small_dp, dim3(gN), dim3(256), h->stream, a.G, a.L.ldg, k, du, P, D, (const double*)a.th, nsv(0), res, a.L.ldn);
         return gN;
     }
     unsigned launch_ns_dp(const IpmDir& D, double res, const double* zu) {
         const NsArena& a = nsa();
-        const unsigned gN = (unsigned)((a.ldn + 255) / 256);
-        asmb::launch(k_ns_dp, dim3(gN), dim3(256), h->stream, P, D, (const double*)a.th, nsv(0), res, zu, a.ldn);
+        const unsigned gN = (unsigned)((a.L.ldn + 255) / 256);
+        asmb::launch(k_ns_dp, dim3(gN), dim3(256), h->stream, P, D, (const double*)a.th, nsv(0), res, zu, a.L.ldn);
         return gN;
     }
     unsigned launch_ns_spmvn_rows(const double* vals, const IpmDir& D) {
         const NsArena& a = nsa();
         const unsigned gM = (unsigned)((lp.M + 255) / 256);
-        asmb::launch(k_ns_spmvn_rows, dim3(gM), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, P, D, a.X, (const double*)(a.th + a.ldn), nsv(7), nsv(5));
+        asmb::launch(k_ns_spmvn_rows, dim3(gM), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, P, D, a.X, (const double*)(a.th + a.L.ldn), nsv(7), nsv(5));
         return gM;
     }
     unsigned launch_ns_gather_e(const double* r, double scale, double* out) {
@@ -2044,6 +2043,7 @@ struct Solver {
     // Per iteration (oracle: IPM.run, null-space branch): reduced matrix N = Zt Th Zt' + GI' D_I^-1 GI (an unregularised copy is kept for the
     // refinement sweep), its factor, dpbar = A_EF' S0^-1 (-rp_E) and K dpbar (shared by predictor and corrector)
     void ns_iter_setup() {
+        const NsForm& F = *h->nsf; const NsK& K = *F.k;
         const int k = ip.ns_k;
         // (theta~ was formed with the interior-point theta: k_ipm_theta_ns in ipm_run)
         // the k range (free columns + inequality rows, 19 000 at n = 11 192) is long and the matrix small (k = 519: 45 tiles of 64 x 64):
@@ -2052,9 +2052,9 @@ struct Solver {
         const int T = Dev::pick_tile(k);
         const int64_t ntile = ((k + 32 * T - 1) / (32 * T));
         int nsplit = (int)std::min<int64_t>(NS_MAX_SPLIT, std::max<int64_t>(1, 1224 / std::max<int64_t>(1, ntile * (ntile + 1) / 2)));
-        nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, h->ns_ldg / 512));
-        dev.ns_newton_matrix(h->d_nsG, h->ns_ldg, h->d_nsth, k, nsplit, h->d_nsNp, h->ns_fN, h->d_nsN0, h->d_diag0, 1e-13, 1e-30);
-        dev.chol(h->ns_fN, k, 1e-14, false);
+        nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, F.L.ldg / 512));
+        dev.ns_newton_matrix(K.G, F.L.ldg, F.th, k, nsplit, K.Np, K.fN, K.N0, h->d_diag0, 1e-13, 1e-30);
+        dev.chol(K.fN, k, 1e-14, false);
         // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
         if (!ip.ns_e_ready) {
             ip.ns_e_ready = true;
@@ -2112,16 +2112,16 @@ struct Solver {
     unsigned ns_gemv_t_dense(const double* u, int k, double* out) {
         const NsArena& a = nsa();
         if (k <= ASM_SMALL_USE) {
-            const dim3 g = asmb::blocks(a.ldn);
-            asmb::launch(k_gemv_t_small, g, dim3(256), h->stream, a.G, a.ldg, k, u, out, a.ldn);
+            const dim3 g = asmb::blocks(a.L.ldn);
+            asmb::launch(k_gemv_t_small, g, dim3(256), h->stream, a.G, a.L.ldg, k, u, out, a.L.ldn);
             return g.x;
         }
         int64_t R = std::min<int64_t>((k + 31) / 32, ASM_TMAXCHUNKS);
         int64_t chunk = (k + R - 1) / R;
         R = (k + chunk - 1) / chunk;
-        const unsigned gx = (unsigned)((a.ldn + 255) / 256);
-        asmb::launch(k_gemv_t_stage1, dim3(gx, (unsigned)R), dim3(256), h->stream, a.G, a.ldg, u, a.partial, (int64_t)k, a.ldn, chunk);
-        asmb::launch(k_gemv_t_stage2, asmb::blocks(a.ldn), dim3(256), h->stream, a.partial, out, R, a.ldn);
+        const unsigned gx = (unsigned)((a.L.ldn + 255) / 256);
+        asmb::launch(k_gemv_t_stage1, dim3(gx, (unsigned)R), dim3(256), h->stream, a.G, a.L.ldg, u, a.partial, (int64_t)k, a.L.ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(a.L.ldn), dim3(256), h->stream, a.partial, out, R, a.L.ldn);
         return gx * (unsigned)R;
     }
 
@@ -3123,15 +3123,17 @@ int row_kind(double lb, double ub) {
 
 // releases every buffer of the handle and resets the state that describes them
 void free_device(asm_handle* h) {
-    h->mem.release(); h->mem_nsk.release(); h->ev.reset();
+    h->mem.release(); h->nsf.reset(); h->ev.reset();
     h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
     h->ahTg_valid = false;
     h->col_capable = h->ahT_valid = h->nzT_valid = false;
     h->sp_ok = h->spv_Ah_valid = h->spv_J_valid = false; h->sp_nnz = 0;
-    h->ns_cap = false; h->ns_kcap = 0; h->ns_ccap = 0; h->ns_Zk = 0; h->ns_npairs = 0;
-    h->ns_f0 = FacBuf(); h->ns_fN = FacBuf(); h->ns_fC = FacBuf(); h->test_fac = FacBuf();
+    h->test_fac = FacBuf();
     h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
 }
+
+// the orthonormal basis of the previous LP is no longer resident (no form, or no k-sized buffers yet: nothing to forget)
+void ns_forget_basis(asm_handle* h) { if (h->nsf && h->nsf->k) h->nsf->k->Zk = 0; }
 
 // forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
 // the null-space form stay
@@ -3141,7 +3143,7 @@ void reset_warm(asm_handle* h, bool keep_ns_J) {
     h->warm[0] = ActiveSet(); h->warm[1] = ActiveSet();
     h->hint[0] = SolveHint(); h->hint[1] = SolveHint();
     h->hint[0].ns_J.swap(J);
-    h->ns_Zk = 0;
+    ns_forget_basis(h);
     h->hint[1].prefer_ref = true;     // restoration LPs usually have a non-unique optimum (oracle/subproblem.py)
 }
 
@@ -3318,36 +3320,33 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.alloc(h->d_nsdots, FACE_STEPS + 8);
         P.alloc(h->h_nsdots, FACE_STEPS + 8, BufPool::PINNED);
     }
-    // null-space form of the normal-phase Newton system: static part (index lists, factor of S0, work vectors); the buffers
-    // sized by the null-space dimension k are allocated by the first LP that uses the form (Solver::ns_reserve)
+    // null-space form of the normal-phase Newton system: static part (index lists, factor of S0, work vectors), installed when the whole set-up
+    // is complete; the buffers sized by the null-space dimension k are allocated by the first LP that uses the form (Solver::ns_reserve)
+    std::unique_ptr<NsForm> nsf;
     {
         int nE = 0;
         for (int64_t i = 0; i < h->M; ++i) nE += h->rtype[i] == 0;
-        h->ns_cap = h->sp_ok && nE >= NS_MIN_E && (double)(n - nE) <= NS_MAX_RATIO * (double)h->M && n <= h->Mp && h->M < (int64_t)1 << 30;
-        if (h->ns_cap) {
-            const NsLayout nlay(h->ldn, h->Mp, nE, h->M - nE);
-            h->ns_nE = nE; h->ns_nI = (int)nlay.nI;
-            h->ns_nEp = (int)nlay.nEp; h->ns_nIp = (int)nlay.nIp;
-            h->ns_ldg = nlay.ldg;
-            std::vector<int> eidx, epos, iidx, ipos;
+        if (h->sp_ok && nE >= NS_MIN_E && (double)(n - nE) <= NS_MAX_RATIO * (double)h->M && n <= h->Mp && h->M < (int64_t)1 << 30) {
+            nsf = std::make_unique<NsForm>(NsLayout(h->ldn, h->Mp, nE, h->M - nE));
+            NsForm& F = *nsf;
+            BufPool& Q = F.mem;
+            std::vector<int> epos, iidx, ipos, s0_pairs;
             int s0_band = 0;
-            std::vector<int> s0_pairs;
-            ns_index_lists(h->rtype.data(), h->M, sp_ptr, sp_col, h->ldn, eidx, epos, iidx, ipos, &s0_band, &s0_pairs);
-            h->ns_eidx_h = eidx;
-            P.upload(h->d_nsEidx, eidx.data(), nE, true); P.upload(h->d_nsEpos, epos.data(), h->M, true);
-            P.upload(h->d_nsIidx, iidx.data(), h->ns_nI, true); P.upload(h->d_nsIpos, ipos.data(), h->M, true);
-            P.zeroed(h->d_nscnt, 16);
+            ns_index_lists(h->rtype.data(), h->M, sp_ptr, sp_col, h->ldn, F.eidx_h, epos, iidx, ipos, &s0_band, &s0_pairs);
+            Q.upload(F.Eidx, F.eidx_h.data(), nE, true); Q.upload(F.Epos, epos.data(), h->M, true);
+            Q.upload(F.Iidx, iidx.data(), F.L.nI, true); Q.upload(F.Ipos, ipos.data(), h->M, true);
+            Q.zeroed(F.cnt, 16);
             const int f0_band = 2 * (int64_t)s0_band >= nE ? 0 : std::max(s0_band, 1);
-            ns_alloc_factor(h, P, h->ns_f0, h->ns_nEp, f0_band);
-            h->ns_f0.band = f0_band;
-            if (h->ns_f0.band > 0) {            // S0 is then built entry by entry from its structural pattern (k_ns_s0_sparse)
-                h->ns_npairs = (int64_t)s0_pairs.size() / 2;
-                P.upload(h->d_nsS0pairs, s0_pairs.data(), (int64_t)s0_pairs.size(), true);
+            ns_alloc_factor(h, Q, F.f0, F.L.nEp, f0_band);
+            F.f0.band = f0_band;
+            if (F.f0.band > 0) {                // S0 is then built entry by entry from its structural pattern (k_ns_s0_sparse)
+                F.npairs = (int64_t)s0_pairs.size() / 2;
+                Q.upload(F.S0pairs, s0_pairs.data(), (int64_t)s0_pairs.size(), true);
             }
-            P.zeroed(h->d_nsLt, (int64_t)h->ns_nEp * h->ns_nEp, s);
-            P.zeroed(h->d_nsth, nlay.th_len(), s);
-            P.zeroed(h->d_nsFm, h->ldn, s);
-            P.zeroed(h->d_nsv, nlay.nsv_len(), s);
+            Q.zeroed(F.Lt, F.L.nEp * F.L.nEp, s);
+            Q.zeroed(F.th, F.L.th_len(), s);
+            Q.zeroed(F.Fm, h->ldn, s);
+            Q.zeroed(F.v, F.L.nsv_len(), s);
         }
     }
     // row order of the factorisations (see asm_handle::row_band)
@@ -3399,6 +3398,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.upload(h->d_uoff, uoff.data(), h->nu); P.upload(h->d_adjoff, adjoff.data(), h->nu);
     }
     HIPCHK(asmb::sync(h->stream));
+    h->nsf = std::move(nsf);
     h->last = ActiveSet();
     reset_warm(h, false);
     std::memset(&h->stats, 0, sizeof(h->stats));
@@ -3441,7 +3441,7 @@ void do_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
     for (int64_t a = 0; a < k; ++a)
         if (J[a] < 0 || J[a] >= h->n) throw std::invalid_argument("asm_sublp_set_ns_basis: column out of range");
     h->hint[0].ns_J.assign(J, J + k);
-    h->ns_Zk = 0;
+    ns_forget_basis(h);
 }
 
 // the LP in caller units: min q'p + w's  s.t.  J_i p + E s (=,>=,<=) r_i (rows m.. = the extra `<=` rows of range constraints),
@@ -3846,9 +3846,9 @@ int asm_sublp_row_order(const asm_handle* h, int32_t* perm, int64_t* band, int32
     if (!h || !band || !n_e || !e_band) return ASM_ERR_ARG;
     *band = h->row_band;
     if (perm && h->row_band > 0) for (int64_t q = 0; q < h->M; ++q) perm[q] = h->row_perm_h[q];
-    *n_e = h->ns_cap ? h->ns_nE : 0;
-    *e_band = h->ns_cap ? h->ns_f0.band : 0;
-    if (e_rows && h->ns_cap) for (int q = 0; q < h->ns_nE; ++q) e_rows[q] = h->ns_eidx_h[q];
+    *n_e = h->nsf ? h->nsf->L.nE : 0;
+    *e_band = h->nsf ? h->nsf->f0.band : 0;
+    if (e_rows && h->nsf) std::copy(h->nsf->eidx_h.begin(), h->nsf->eidx_h.end(), e_rows);
     return ASM_OK;
 }
 
@@ -5420,8 +5420,8 @@ int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const in
         vec c(n, 1.0), rho(M);
         d.scale(c.data(), rho.data());
         d.tile_flags();
-        const bool ns = h->ns_cap;
-        const int64_t out[12] = {M, n, h->row_band, h->col_band, h->main_fac.ld, ns ? h->ns_nE : 0, ns ? h->ns_f0.band : 0, ns ? h->ns_f0.ld : 0, h->col_capable ? 1 : 0,
+        NsForm* const ns = h->nsf.get();
+        const int64_t out[12] = {M, n, h->row_band, h->col_band, h->main_fac.ld, ns ? ns->L.nE : 0, ns ? ns->f0.band : 0, ns ? ns->f0.ld : 0, h->col_capable ? 1 : 0,
                                  h->nz_valid ? 1 : 0, 0, h->sp_ok ? 1 : 0};
         for (int k = 0; k < 12; ++k) info[k] = out[k];
         if (Ah_out) for (int64_t i = 0; i < M; ++i) HIPCHK(asmb::copy(Ah_out + i * n, h->d_Ah + i * h->ldn, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -5430,9 +5430,9 @@ int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const in
             if (h->col_band > 0) HIPCHK(asmb::copy(col_order, h->d_colperm, n * sizeof(int), hipMemcpyDeviceToHost));
             else for (int64_t q = 0; q < n; ++q) col_order[q] = -1;
         }
-        if (e_order && ns) for (int q = 0; q < h->ns_nE; ++q) e_order[q] = h->ns_eidx_h[q];
+        if (e_order && ns) std::copy(ns->eidx_h.begin(), ns->eidx_h.end(), e_order);
         if (which < 0) return;
-        const FacBuf& f = which == 4 ? h->ns_f0 : h->main_fac;
+        const FacBuf& f = which == 4 && ns ? ns->f0 : h->main_fac;       // (which = 4 without the form is refused below)
         const int64_t nth = (which == 1 || which == 3) ? M : n, ndg = which == 0 ? M : ((which == 1 || which == 3) ? n : Ms);
         if (!theta || !S_inout || (which == 2 && (!idx || Ms <= 0 || Ms > M)) || ((which == 1 || which == 3) && (!h->col_capable || !diag)) ||
             (which == 3 && h->col_band <= 0) || (which == 4 && !ns) || ((which == 1 || which == 3) && n > f.ld) || (which == 0 && M == 0))
@@ -5459,7 +5459,7 @@ int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const in
         }
         case 3: d.schur_banded_cols_dev(dth, ddg); break;
         default:
-            HIPCHK(asmb::copy(h->d_nsFm, dth, h->ldn * sizeof(double), hipMemcpyDeviceToDevice));
+            HIPCHK(asmb::copy(ns->Fm, dth, h->ldn * sizeof(double), hipMemcpyDeviceToDevice));
             d.ns_build_S0();
         }
         HIPCHK(asmb::sync(h->stream));
@@ -5917,10 +5917,9 @@ int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double sc
         S.P.n = n; S.P.M = M; S.P.ns = 0; S.P.ncomp = std::max<int64_t>(1, 2 * n + (M - nE)); S.P.scale_q = scale_q;
         Solver::NsArena na;
         na.v = dD + o_v; na.th = dD + o_th; na.G = dD + o_G; na.N0 = dD + o_N0; na.partial = dD + o_part;
-        na.fN = &fN;
         na.sp_ptr = dPtr; na.sp_col = dCol; na.sc_ptr = dCp; na.sc_row = dCr; na.sc_pos = dCq; na.vals = dV;
         na.X.Eidx = dE; na.X.Epos = dEp; na.X.Iidx = dIi; na.X.Ipos = dIp; na.X.nE = (int)nE; na.X.nI = (int)(M - nE);
-        na.ldn = lay.ldn; na.Mp = lay.Mp; na.nEp = nl.nEp; na.nIp = nl.nIp; na.ldg = nl.ldg;
+        na.fN = &fN; na.L = nl;
         S.ns_bind(na);
         S.ip.ns_k = (int)k;
         const int kk = (int)k;
