@@ -116,8 +116,9 @@ struct ActiveSet {
 struct SolveHint {
     int warm_fail = 0, warm_skip = 1;     // the first re-solve of a phase is not attempted
     bool stable = false;                  // the last two LPs of the phase ended on the same active sets
-    bool prefer_ref = false;
+    bool prefer_ref;                      // starts true in the restoration phase: its LPs usually have a non-unique optimum (oracle/subproblem.py)
     std::vector<int> ns_J;                // basis columns of the null-space form retained from the previous LP of the phase
+    explicit SolveHint(bool restoration) : prefer_ref(restoration) {}
 };
 
 struct TimedRegion {
@@ -473,22 +474,11 @@ HandleKnobs read_knobs() {
     return k;
 }
 
-}  // namespace
-
-struct asm_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // look-ahead stream of the Cholesky (next panel's block chain runs beside the trailing update)
-    std::vector<hipEvent_t> la_events;
-    std::string err;
-    bool setup_done = false, inputs_ready = false;
-    bool inputs_from_eval = false;  // the inputs came from asm_eval_functions: the evaluator's x, E and gradient in HBM are those of x_k
-    // owners of the device / pinned buffers, one per lifetime: the problem skeleton (until the next set-up), the null-space form with its own
-    // pools (until the next set-up; null: the skeleton does not qualify), the device evaluator with its own (until the next asm_eval_setup or set-up; null: none)
-    BufPool mem;
-    std::unique_ptr<NsForm> nsf;
-    std::unique_ptr<EvalState> ev;
-
+// The LP skeleton: everything asm_sublp_setup makes (do_setup) and everything that is valid only for it - the uploaded inputs, the retained
+// working sets, the test hooks' factor - in one pool and with one lifetime: until the next asm_sublp_setup.  The handle holds a pointer that is
+// null while there is no skeleton (sk_of): no ready flag, no list of fields to reset; every field starts from its initialiser here.
+struct Skeleton {
+    std::unique_ptr<NsForm> nsf;    // the null-space form with its own pools (null: the skeleton does not qualify)
     // ---- problem (subproblem.jl:51-215) ----
     int64_t n = 0, m = 0, nnz = 0, nadj = 0, M = 0, Mp = 0, ldn = 0, ns = 0;
     vec c_lb, c_ub, v_lb, v_ub;
@@ -533,7 +523,7 @@ struct asm_handle {
     bool nz_valid = false;
     int nz_T = 0, nz_pitch = 0;
     double nz_fraction = 1.0;       // executed share of the (tile pair, k-chunk) products of the Schur build
-    double nz_frac_cache[2] = {-1.0, -1.0};   // ... cached per handle: all rows / the equality rows (the pattern is fixed)
+    double nz_frac_cache[2] = {-1.0, -1.0};   // ... cached: all rows / the equality rows (the pattern is fixed)
     // all M rows in reverse Cuthill-McKee order (sparse patterns whose bandwidth is below M / 2): the Gram matrices of row subsets taken in
     // that order are banded with half-bandwidth <= row_band
     int row_band = 0;
@@ -547,12 +537,7 @@ struct asm_handle {
     bool ahTg_valid = false;
     double* d_redpart = nullptr;    // partial results / arrival counter of the multi-workgroup interior-point reductions
     unsigned* d_redcnt = nullptr;
-    int test_band = 0;              // band of the matrices the kernel hooks load (test hook asm_test_set_band; 0 = dense)
-    // test hook asm_test_set_factor: where the kernel hooks factor (0: the main factor, 1: a factor buffer of their own made by
-    // ns_alloc_factor with this band hint) and the guard settings they factor with (k_diag_prepare mode / rel / absv, chol threshold)
-    int test_layout = 0, test_band_hint = 0, test_mode = 0;
-    double test_rel = 0.0, test_abs = 0.0, test_thr = 1e-14;
-    FacBuf test_fac;
+    FacBuf test_fac;                // the kernel hooks' own factor buffer (asm_test_set_factor layout 1), made by test_load_S
     double* d_ipm_snap = nullptr;   // best-iterate safeguard: copy of the iterate at the end of the best interior-point stage so far
     double* d_ipm = nullptr;        // arena of the device-resident interior-point state
     int* d_ipm_i = nullptr;
@@ -578,14 +563,38 @@ struct asm_handle {
     int64_t pin_len = 0;
 
     // ---- host copies of the evaluation results (slp.jl:8-21) ----
+    bool inputs_ready = false;
+    bool inputs_from_eval = false;  // the inputs came from asm_eval_functions: the evaluator's x, E and gradient in HBM are those of x_k
     vec df, E, x_k;
     double f = 0.0;
 
     // ---- warm start (retained active set per phase; GLPK keeps its basis, slp.jl:38-40) ----
     ActiveSet warm[2];
-    SolveHint hint[2];
-    int64_t stats_pcg = 0;          // conjugate-gradient steps since creation (verbose diagnostics)
+    SolveHint hint[2] = {SolveHint(false), SolveHint(true)};
     ActiveSet last;
+    unsigned *d_pflags = nullptr, *d_ptmo = nullptr;      // flags and time-out word of the Cholesky panel kernels
+    BufPool mem;                    // declared last, as in EvalState
+};
+
+}  // namespace
+
+struct asm_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;  // look-ahead stream of the Cholesky (next panel's block chain runs beside the trailing update)
+    std::vector<hipEvent_t> la_events;
+    std::string err;
+    // owners of the device / pinned buffers, one per lifetime: the LP skeleton with the null-space form inside it (until the next set-up; null:
+    // no set-up yet, or the last one failed), the device evaluator (until the next asm_eval_setup or set-up; null: none).  What follows
+    // them survives a set-up.
+    std::unique_ptr<Skeleton> sk;
+    std::unique_ptr<EvalState> ev;
+    int test_band = 0;              // band of the matrices the kernel hooks load (test hook asm_test_set_band; 0 = dense)
+    // test hook asm_test_set_factor: where the kernel hooks factor (0: the main factor, 1: a factor buffer of their own made by
+    // ns_alloc_factor with this band hint) and the guard settings they factor with (k_diag_prepare mode / rel / absv, chol threshold)
+    int test_layout = 0, test_band_hint = 0, test_mode = 0;
+    double test_rel = 0.0, test_abs = 0.0, test_thr = 1e-14;
+    int64_t stats_pcg = 0;          // conjugate-gradient steps since creation (verbose diagnostics)
     asm_solve_stats stats;
 
     // ---- kernel timing ----
@@ -596,7 +605,6 @@ struct asm_handle {
     int panel_wgs = 240;            // grid bound of the Cholesky panel kernels: every workgroup must be able to become resident (a batch slot: its group's share)
     int panel_wgs_dev = 240;        // the bound of the whole device (ASM_PANEL_WGS) the shares of a batch's groups are taken from
     int num_cus = 256;              // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    unsigned *d_pflags = nullptr, *d_ptmo = nullptr;
     bool test_no_polish = false;    // test hook: the active-set attempts of an LP all fail (asm_test_no_polish)
     unsigned panel_epoch = 0;
     int timing = 1;                 // HIP-event timing: 0 off, 1 the dominant kernel only (every k_syrk launch), 2 every kernel family
@@ -615,12 +623,17 @@ EvalState& ev_of(const asm_handle* h, const char* who) {
     if (!h->ev) throw std::logic_error(std::string(who) + ": asm_eval_setup first");
     return *h->ev;
 }
+// the handle's LP skeleton, or std::logic_error(what) while there is none.  An evaluator implies a skeleton: do_eval_setup needs one, do_setup drops both
+Skeleton& sk_of(const asm_handle* h, const char* what) {
+    if (!h->sk) throw std::logic_error(what);
+    return *h->sk;
+}
 // the reductions' copy of the handle's bounds into the block of L
 void ev_write_bounds(const asm_handle* h, const EvLayout& L) {
-    HIPCHK(asmb::copy(L.g_L(), h->c_lb.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(asmb::copy(L.g_U(), h->c_ub.data(), h->m * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(asmb::copy(L.x_L(), h->v_lb.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(asmb::copy(L.x_U(), h->v_ub.data(), h->n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.g_L(), h->sk->c_lb.data(), h->sk->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.g_U(), h->sk->c_ub.data(), h->sk->m * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.x_L(), h->sk->v_lb.data(), h->sk->n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(asmb::copy(L.x_U(), h->sk->v_ub.data(), h->sk->n * sizeof(double), hipMemcpyHostToDevice));
 }
 
 // buffers of one Cholesky factor of order <= N (pitch = N rounded up to 32) with the block inverses of the substitution kernels, from `pool`
@@ -644,6 +657,7 @@ void ns_alloc_factor(asm_handle* h, BufPool& pool, FacBuf& f, int64_t N, int ban
 struct Dev {
     asm_handle* h;
     explicit Dev(asm_handle* hh) : h(hh) {}
+    Skeleton& sk() const { return *h->sk; }         // the entry has checked that there is one (sk_of); kernel statistics and timing need none
     // first row that the columns [.., c1) of a banded matrix / factor cannot reach (the order Ms when the matrix is dense)
     static int rowlim(const FacBuf& f, int Ms, int c1) { return f.band > 0 ? (int)std::min<int64_t>(Ms, round_up((int64_t)c1 + f.band, 64)) : Ms; }
 
@@ -690,14 +704,14 @@ struct Dev {
     }
 
     void h2d(double* dst, const double* src, int64_t cnt, int64_t padded) {
-        double* st = h->h_pin;
+        double* st = sk().h_pin;
         std::memcpy(st, src, cnt * sizeof(double));
         for (int64_t i = cnt; i < padded; ++i) st[i] = 0.0;
         HIPCHK(asmb::copy_async(dst, st, padded * sizeof(double), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);   // staging buffer is reused by the next call
     }
     void d2h(double* dst, const double* src, int64_t cnt) {
-        double* st = h->h_pin + h->pin_len;
+        double* st = sk().h_pin + sk().pin_len;
         HIPCHK(asmb::copy_async(st, src, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
         std::memcpy(dst, st, cnt * sizeof(double));
@@ -706,73 +720,73 @@ struct Dev {
     // out[M] = A x   (A = Ah or J, M rows)
     // gathered pattern values of A (d_Ah or d_J) for the sparse products, nullptr when the pattern is dense
     const double* sparse_vals(const double* A) {
-        if (!h->sp_ok) return nullptr;
+        if (!sk().sp_ok) return nullptr;
         double* v = nullptr;
         bool* valid = nullptr;
-        if (A == h->d_Ah) { v = h->d_spv_Ah; valid = &h->spv_Ah_valid; }
-        else if (A == h->d_J) { v = h->d_spv_J; valid = &h->spv_J_valid; }
+        if (A == sk().d_Ah) { v = sk().d_spv_Ah; valid = &sk().spv_Ah_valid; }
+        else if (A == sk().d_J) { v = sk().d_spv_J; valid = &sk().spv_J_valid; }
         else return nullptr;
         if (!*valid) {
-            asmb::launch(k_sp_gather, asmb::blocks(h->sp_nnz), dim3(256), h->stream, A, h->d_sp_off, v, h->sp_nnz);
+            asmb::launch(k_sp_gather, asmb::blocks(sk().sp_nnz), dim3(256), h->stream, A, sk().d_sp_off, v, sk().sp_nnz);
             *valid = true;
         }
         return v;
     }
     void launch_gemv_n(const double* A, const double* x, double* out) {
-        if (h->M == 0) return;                         // LP without rows
+        if (sk().M == 0) return;                         // LP without rows
         if (const double* v = sparse_vals(A)) {
-            int id = begin(ASM_K_GEMV, 2.0 * h->sp_nnz, 20.0 * h->sp_nnz + 12.0 * h->M);
-            asmb::launch(k_spmv_n, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, v, x, out, h->M);
+            int id = begin(ASM_K_GEMV, 2.0 * sk().sp_nnz, 20.0 * sk().sp_nnz + 12.0 * sk().M);
+            asmb::launch(k_spmv_n, asmb::blocks(sk().M), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, v, x, out, sk().M);
             end(id);
             return;
         }
-        int id = begin(ASM_K_GEMV, 2.0 * h->M * h->n, 8.0 * h->M * h->ldn);
-        asmb::launch(k_gemv_n, asmb::blocks(h->M, 4), dim3(256), h->stream, A, h->ldn, x, out, h->M, h->ldn);
+        int id = begin(ASM_K_GEMV, 2.0 * sk().M * sk().n, 8.0 * sk().M * sk().ldn);
+        asmb::launch(k_gemv_n, asmb::blocks(sk().M, 4), dim3(256), h->stream, A, sk().ldn, x, out, sk().M, sk().ldn);
         end(id);
     }
     void launch_gemv_t(const double* A, const double* y, double* out) {
-        if (h->M == 0) {                               // LP without rows: A'y = 0
-            HIPCHK(asmb::fill_async(out, 0, h->ldn * sizeof(double), h->stream));
+        if (sk().M == 0) {                               // LP without rows: A'y = 0
+            HIPCHK(asmb::fill_async(out, 0, sk().ldn * sizeof(double), h->stream));
             return;
         }
         if (const double* v = sparse_vals(A)) {
-            int id = begin(ASM_K_GEMV, 2.0 * h->sp_nnz, 24.0 * h->sp_nnz + 12.0 * h->n);
-            asmb::launch(k_spmv_t, asmb::blocks(h->ldn * 8), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, v, y, out, h->n, h->ldn);
+            int id = begin(ASM_K_GEMV, 2.0 * sk().sp_nnz, 24.0 * sk().sp_nnz + 12.0 * sk().n);
+            asmb::launch(k_spmv_t, asmb::blocks(sk().ldn * 8), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, v, y, out, sk().n, sk().ldn);
             end(id);
             return;
         }
-        if (A == h->d_Ah && (int64_t)h->ldn * h->Mp <= ((int64_t)1 << 27)) {
+        if (A == sk().d_Ah && (int64_t)sk().ldn * sk().Mp <= ((int64_t)1 << 27)) {
             // dense LP matrix of moderate size: through a transposed copy (made once per LP), one row-wise launch
-            if (!h->d_AhTg) h->mem.zeroed(h->d_AhTg, h->ldn * h->Mp, h->stream);
-            if (!h->ahTg_valid) {
-                asmb::launch(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), h->stream, h->d_Ah, h->ldn, h->M, h->n, h->d_AhTg,
-                             h->Mp, (int64_t)-1);
-                h->ahTg_valid = true;
+            if (!sk().d_AhTg) sk().mem.zeroed(sk().d_AhTg, sk().ldn * sk().Mp, h->stream);
+            if (!sk().ahTg_valid) {
+                asmb::launch(k_transpose_dense, dim3((unsigned)((sk().n + 63) / 64), (unsigned)((sk().M + 63) / 64)), dim3(256), h->stream, sk().d_Ah, sk().ldn, sk().M, sk().n, sk().d_AhTg,
+                             sk().Mp, (int64_t)-1);
+                sk().ahTg_valid = true;
             }
-            int id = begin(ASM_K_GEMV, 2.0 * h->M * h->n, 8.0 * h->M * h->ldn);
-            asmb::launch(k_gemv_n_exact, asmb::blocks(h->ldn, 4), dim3(256), h->stream, h->d_AhTg, h->Mp, y, out, h->ldn, h->M);
+            int id = begin(ASM_K_GEMV, 2.0 * sk().M * sk().n, 8.0 * sk().M * sk().ldn);
+            asmb::launch(k_gemv_n_exact, asmb::blocks(sk().ldn, 4), dim3(256), h->stream, sk().d_AhTg, sk().Mp, y, out, sk().ldn, sk().M);
             end(id);
             return;
         }
-        int64_t R = std::min<int64_t>((h->M + 31) / 32, ASM_TMAXCHUNKS);
-        int64_t chunk = (h->M + R - 1) / R;
-        R = (h->M + chunk - 1) / chunk;
-        int id = begin(ASM_K_GEMV, 2.0 * h->M * h->n, 8.0 * h->M * h->ldn);
-        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, A, h->ldn, y, h->d_partial, h->M, h->ldn, chunk);
-        asmb::launch(k_gemv_t_stage2, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_partial, out, R, h->ldn);
+        int64_t R = std::min<int64_t>((sk().M + 31) / 32, ASM_TMAXCHUNKS);
+        int64_t chunk = (sk().M + R - 1) / R;
+        R = (sk().M + chunk - 1) / chunk;
+        int id = begin(ASM_K_GEMV, 2.0 * sk().M * sk().n, 8.0 * sk().M * sk().ldn);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, A, sk().ldn, y, sk().d_partial, sk().M, sk().ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(sk().ldn), dim3(256), h->stream, sk().d_partial, out, R, sk().ldn);
         end(id);
     }
     // out[M] = A x   (host vectors)
     void gemv_n(const double* A, const double* x, double* out) {
-        h2d(h->d_vecN, x, h->n, h->ldn);
-        launch_gemv_n(A, h->d_vecN, h->d_vecM);
-        d2h(out, h->d_vecM, h->M);
+        h2d(sk().d_vecN, x, sk().n, sk().ldn);
+        launch_gemv_n(A, sk().d_vecN, sk().d_vecM);
+        d2h(out, sk().d_vecM, sk().M);
     }
     // out[n] = A' y
     void gemv_t(const double* A, const double* y, double* out) {
-        h2d(h->d_vecM, y, h->M, h->Mp);
-        launch_gemv_t(A, h->d_vecM, h->d_vecN);
-        d2h(out, h->d_vecN, h->n);
+        h2d(sk().d_vecM, y, sk().M, sk().Mp);
+        launch_gemv_t(A, sk().d_vecM, sk().d_vecN);
+        d2h(out, sk().d_vecN, sk().n);
     }
 
     // device-pointer variants (the IPM keeps its vectors in HBM)
@@ -786,25 +800,25 @@ struct Dev {
     void schur_syrk(bool cols, const int* idx_dev, int Ms, const double* theta_dev, const double* diag_dev, double* S, int64_t ldS, NzFlags flags,
                     int cache_slot = -1) {
         if (cols) ensure_AhT();
-        const double* A = cols ? h->d_AhT : h->d_Ah;
-        const int64_t ld = cols ? h->ldT : h->ldn;
+        const double* A = cols ? sk().d_AhT : sk().d_Ah;
+        const int64_t ld = cols ? sk().ldT : sk().ldn;
         const int T = pick_tile(Ms);
         int nch = (int)(ld / ASM_KC);
         const unsigned char* nz = nullptr;
         double frac = 1.0;
         if (flags == NzFlags::PerCall) {
             const int TS = 32 * T, nt = (Ms + TS - 1) / TS;
-            if (h->nz_valid && nt > 0) {
-                unsigned char* nz2 = h->d_nz + h->nz_half;
+            if (sk().nz_valid && nt > 0) {
+                unsigned char* nz2 = sk().d_nz + sk().nz_half;
                 launch_tile_flags(A, ld, Ms, T, nch, nz2, nch, idx_dev);
                 frac = executed_fraction(nz2, nt, nch, cache_slot);
                 nz = nz2;
             }
         } else if (cols) {
-            if (h->nzT_valid) { nz = h->d_nzT; frac = h->nzT_fraction; }
+            if (sk().nzT_valid) { nz = sk().d_nzT; frac = sk().nzT_fraction; }
         } else {
-            nch = h->nz_pitch;
-            if (h->nz_valid && idx_dev == nullptr && Ms == (int)h->M && T == h->nz_T) { nz = h->d_nz; frac = h->nz_fraction; }
+            nch = sk().nz_pitch;
+            if (sk().nz_valid && idx_dev == nullptr && Ms == (int)sk().M && T == sk().nz_T) { nz = sk().d_nz; frac = sk().nz_fraction; }
         }
         int id = begin(ASM_K_SYRK, frac * (double)Ms * (Ms + 1) * ld, 8.0 * (Ms * (double)ld + 0.5 * Ms * (double)Ms));
         launch_syrk(h->stream, T, A, ld, idx_dev, 0, Ms, (int)ld, theta_dev, diag_dev, S, ldS, 0, 0, -1, nz, nch, frac);
@@ -813,8 +827,8 @@ struct Dev {
     // The main factor's Schur matrix of a row list (reduced row form, active-set partitions): with the rows in the handle's banded order
     // (row_band > 0) built from the structural pairs - cpos maps a row to its place in the list - else gathered through idx
     void schur_rows(const int* idx_dev, const int* cpos_dev, int Ms, const double* theta_dev, const double* diag_dev) {
-        if (h->row_band > 0) schur_banded_dev(cpos_dev, Ms, theta_dev, diag_dev);
-        else schur_syrk(false, idx_dev, Ms, theta_dev, diag_dev, h->main_fac.S, h->main_fac.ld, NzFlags::PerCall);
+        if (sk().row_band > 0) schur_banded_dev(cpos_dev, Ms, theta_dev, diag_dev);
+        else schur_syrk(false, idx_dev, Ms, theta_dev, diag_dev, sk().main_fac.S, sk().main_fac.ld, NzFlags::PerCall);
     }
     // clears the lower band of a banded factor's first Ms rows before an entry-by-entry build: the band plus what the blocked factorisation
     // reads beyond it (an outer panel of CHOL_NBO columns, tile rounding)
@@ -823,32 +837,32 @@ struct Dev {
         asmb::launch(k_ns_zero_band, dim3((unsigned)((wz + 255) / 256), (unsigned)Ms), dim3(256), h->stream, f.S, f.ld, Ms, (int)wz);
     }
     // S[0:Ms,0:Ms] (lower) = Ah[idx,:] diag(theta) Ah[idx,:]' + diag for a row list in the handle's reverse Cuthill-McKee order
-    // (asm_handle::row_band): banded, built entry by entry from the structural pairs - cpos maps a row to its place in the list (-1: not
+    // (Skeleton::row_band): banded, built entry by entry from the structural pairs - cpos maps a row to its place in the list (-1: not
     // in it).  The factorisation and the substitutions that follow stop at the band (the main factor's band).
     void schur_banded_dev(const int* cpos_dev, int Ms, const double* theta_dev, const double* diag_dev) {
-        FacBuf& f = h->main_fac;
-        zero_band(f, Ms, h->row_band);
-        asmb::launch(k_schur_sparse, asmb::blocks(h->n_rowpairs), dim3(256), h->stream, h->d_rowpairs, h->n_rowpairs, cpos_dev, h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah),
+        FacBuf& f = sk().main_fac;
+        zero_band(f, Ms, sk().row_band);
+        asmb::launch(k_schur_sparse, asmb::blocks(sk().n_rowpairs), dim3(256), h->stream, sk().d_rowpairs, sk().n_rowpairs, cpos_dev, sk().d_sp_ptr, sk().d_sp_col, sparse_vals(sk().d_Ah),
                      theta_dev, diag_dev, f.S, f.ld, nullptr);
     }
-    // K = diag + Ah' diag(dinv) Ah (n x n, lower) with the COLUMNS in their reverse Cuthill-McKee order (asm_handle::col_band): the column form
+    // K = diag + Ah' diag(dinv) Ah (n x n, lower) with the COLUMNS in their reverse Cuthill-McKee order (Skeleton::col_band): the column form
     // of the restoration-phase Newton system, banded and built from the structural column pairs; `diag_place` is indexed by position
     void schur_banded_cols_dev(const double* dinv_dev, const double* diag_place) {
-        FacBuf& f = h->main_fac;
-        const int n = (int)h->n;
-        zero_band(f, n, h->col_band);
-        asmb::launch(k_schur_sparse, asmb::blocks(h->n_colpairs), dim3(256), h->stream, h->d_colpairs, h->n_colpairs, h->d_colpos, h->d_sc_ptr, h->d_sc_row, sparse_vals(h->d_Ah),
-                     dinv_dev, diag_place, f.S, f.ld, h->d_sc_pos);
+        FacBuf& f = sk().main_fac;
+        const int n = (int)sk().n;
+        zero_band(f, n, sk().col_band);
+        asmb::launch(k_schur_sparse, asmb::blocks(sk().n_colpairs), dim3(256), h->stream, sk().d_colpairs, sk().n_colpairs, sk().d_colpos, sk().d_sc_ptr, sk().d_sc_row, sparse_vals(sk().d_Ah),
+                     dinv_dev, diag_place, f.S, f.ld, sk().d_sc_pos);
     }
     // S0 = A_EF diag(Fm) A_EF' of the null-space form (equality rows in their reverse Cuthill-McKee order, Fm in F.Fm) into F.f0.S
     void ns_build_S0() {
-        NsForm& F = *h->nsf;
+        NsForm& F = *sk().nsf;
         const int nE = (int)F.L.nE;
         if (F.f0.band > 0) {
             // banded S0: the band is cleared (the last factor filled it) and the ~20 structural entries per row are written as merged
             // sparse dot products of the two rows - the dense rank-K build spends 3 ms on the zeros at n = 11 192
             zero_band(F.f0, nE, F.f0.band);
-            asmb::launch(k_ns_s0_sparse, asmb::blocks(F.npairs), dim3(256), h->stream, F.S0pairs, F.npairs, h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), F.Eidx, F.Fm, F.f0.S, F.f0.ld);
+            asmb::launch(k_ns_s0_sparse, asmb::blocks(F.npairs), dim3(256), h->stream, F.S0pairs, F.npairs, sk().d_sp_ptr, sk().d_sp_col, sparse_vals(sk().d_Ah), F.Eidx, F.Fm, F.f0.S, F.f0.ld);
         } else {
             // S0 = A_EF A_EF' (the share of its chunk products cached per handle: the equality rows are fixed)
             schur_syrk(false, F.Eidx, nE, F.Fm, nullptr, F.f0.S, F.f0.ld, NzFlags::PerCall, 1);
@@ -894,7 +908,7 @@ struct Dev {
     }
     // out[i] = sum_j Ah_ij^2 thinv_j   (sparse patterns only)
     void schur_diag(const double* thinv_dev, double* out_dev) {
-        launch_sdiag_csr(h->d_sp_ptr, h->d_sp_col, sparse_vals(h->d_Ah), thinv_dev, out_dev, h->M);
+        launch_sdiag_csr(sk().d_sp_ptr, sk().d_sp_col, sparse_vals(sk().d_Ah), thinv_dev, out_dev, sk().M);
     }
     unsigned launch_sdiag_csr(const int* ptr, const int* col, const double* vals, const double* thinv_dev, double* out_dev, int64_t M) {
         const dim3 g = asmb::blocks(M);
@@ -903,34 +917,34 @@ struct Dev {
     }
     // transposed copy of Ah and its chunk flags (column form of the restoration-phase Newton system), once per LP
     void ensure_AhT() {
-        if (h->ahT_valid) return;
-        asmb::launch(k_transpose_dense, dim3((unsigned)((h->n + 63) / 64), (unsigned)((h->M + 63) / 64)), dim3(256), h->stream, h->d_Ah, h->ldn, h->M, h->n, h->d_AhT, h->ldT,
+        if (sk().ahT_valid) return;
+        asmb::launch(k_transpose_dense, dim3((unsigned)((sk().n + 63) / 64), (unsigned)((sk().M + 63) / 64)), dim3(256), h->stream, sk().d_Ah, sk().ldn, sk().M, sk().n, sk().d_AhT, sk().ldT,
                      (int64_t)-1);
-        h->nzT_valid = false;
-        const int nch = (int)(h->ldT / ASM_KC);
-        if (!h->dense_fast && nch <= ASM_MAXCHUNKS && h->nnz * 8 <= h->M * h->n) {
-            const int T = pick_tile(h->n), TS = 32 * T;
-            const int nt = (int)((h->n + TS - 1) / TS);
-            launch_tile_flags(h->d_AhT, h->ldT, h->n, T, nch, h->d_nzT, nch, nullptr);
-            h->nzT_fraction = executed_fraction(h->d_nzT, nt, nch);
-            h->nzT_valid = true;
+        sk().nzT_valid = false;
+        const int nch = (int)(sk().ldT / ASM_KC);
+        if (!sk().dense_fast && nch <= ASM_MAXCHUNKS && sk().nnz * 8 <= sk().M * sk().n) {
+            const int T = pick_tile(sk().n), TS = 32 * T;
+            const int nt = (int)((sk().n + TS - 1) / TS);
+            launch_tile_flags(sk().d_AhT, sk().ldT, sk().n, T, nch, sk().d_nzT, nch, nullptr);
+            sk().nzT_fraction = executed_fraction(sk().d_nzT, nt, nch);
+            sk().nzT_valid = true;
         }
-        h->ahT_valid = true;
+        sk().ahT_valid = true;
     }
     // per (row tile, k-chunk) non-zero flags of Ah for the chunk-skipping Schur build (sparse Jacobians only)
     void tile_flags() {
-        h->nz_valid = false;
-        if (h->M == 0) return;
-        const int nch = (int)(h->ldn / ASM_KC);
-        if (h->dense_fast || nch > ASM_MAXCHUNKS || h->nnz * 8 > h->M * h->n) return;     // dense pattern: nothing to skip
-        if (h->row_band > 0) return;      // banded row order: the full-row Schur matrix is built from its structural entries, not by k_syrk
-        h->nz_T = pick_tile(h->M);
-        const int TS = 32 * h->nz_T;
-        const int nt = (int)((h->M + TS - 1) / TS);
-        h->nz_pitch = nch;
-        launch_tile_flags(h->d_Ah, h->ldn, h->M, h->nz_T, nch, h->d_nz, h->nz_pitch, nullptr);
-        h->nz_valid = true;
-        h->nz_fraction = executed_fraction(h->d_nz, nt, nch, 0);
+        sk().nz_valid = false;
+        if (sk().M == 0) return;
+        const int nch = (int)(sk().ldn / ASM_KC);
+        if (sk().dense_fast || nch > ASM_MAXCHUNKS || sk().nnz * 8 > sk().M * sk().n) return;     // dense pattern: nothing to skip
+        if (sk().row_band > 0) return;      // banded row order: the full-row Schur matrix is built from its structural entries, not by k_syrk
+        sk().nz_T = pick_tile(sk().M);
+        const int TS = 32 * sk().nz_T;
+        const int nt = (int)((sk().M + TS - 1) / TS);
+        sk().nz_pitch = nch;
+        launch_tile_flags(sk().d_Ah, sk().ldn, sk().M, sk().nz_T, nch, sk().d_nz, sk().nz_pitch, nullptr);
+        sk().nz_valid = true;
+        sk().nz_fraction = executed_fraction(sk().d_nz, nt, nch, 0);
     }
     // nz[t][c] (pitch nzpitch) = tile t (32 T rows of the list idx, or of the first Ms rows) of A has a non-zero in k-chunk c < nch
     void launch_tile_flags(const double* A, int64_t ld, int64_t Ms, int T, int nch, unsigned char* nz, int nzpitch, const int* idx_dev) {
@@ -939,12 +953,12 @@ struct Dev {
     }
     // fraction of (tile pair, chunk) products actually executed: keeps the flop accounting of the roofline honest
     double executed_fraction(const unsigned char* d_flags, int nt, int nch, int cache_slot = -1) {
-        if (h->timing == 0) return h->nz_valid ? h->nz_fraction : 1.0;      // only the flop accounting needs it: no read-back when timing is off
+        if (h->timing == 0) return sk().nz_valid ? sk().nz_fraction : 1.0;      // only the flop accounting needs it: no read-back when timing is off
         // the flags follow the fixed pattern of the Jacobian: for the row sets that recur every LP (all rows; the equality rows of the
         // null-space form) the share is computed once per handle - the read-back and the O(nt^2 nch) host loop cost milliseconds per LP
-        if (cache_slot >= 0 && h->nz_frac_cache[cache_slot] >= 0.0) return h->nz_frac_cache[cache_slot];
+        if (cache_slot >= 0 && sk().nz_frac_cache[cache_slot] >= 0.0) return sk().nz_frac_cache[cache_slot];
         const double fr_ = executed_fraction_now(d_flags, nt, nch);
-        if (cache_slot >= 0) h->nz_frac_cache[cache_slot] = fr_;
+        if (cache_slot >= 0) sk().nz_frac_cache[cache_slot] = fr_;
         return fr_;
     }
     double executed_fraction_now(const unsigned char* d_flags, int nt, int nch) {
@@ -997,7 +1011,7 @@ struct Dev {
         if (nz && ntj == 0) blocks = (nt * (nt + 1) / 2 + 511) / 512 * 512;      // sparse build: runs of 64 tile pairs dealt to the XCD labels (tri_tile_xcd)
         // per-launch timing of the MFMA kernel itself (algorithmic flops: Ms*MsB*K over the stored triangle/rectangle)
         double fl = (MsB == Ms && ntj == 0) ? (double)Ms * (Ms + 1) * K : 2.0 * ((double)Ms * MsB - 0.5 * (double)MsB * MsB) * K;
-        if (nz) fl *= nzfrac >= 0.0 ? nzfrac : h->nz_fraction;
+        if (nz) fl *= nzfrac >= 0.0 ? nzfrac : sk().nz_fraction;
         // timed on the stream it is launched on (HIP events see only their own stream)
         int kid = begin(ASM_K_SYRK_KERNEL, fl, 8.0 * ((double)(Ms + MsB) * K + (double)Ms * MsB), s);
         struct EndGuard { Dev* d; int id; ~EndGuard() { d->end(id); } } guard_{this, kid};
@@ -1018,7 +1032,7 @@ struct Dev {
     }
 
     void diag_prepare(const FacBuf& f, int Ms, int mode, double rel, double absv, double* diag0 = nullptr) {
-        asmb::launch(k_diag_prepare, dim3(1), dim3(1024), h->stream, f.S, f.ld, Ms, diag0 ? diag0 : h->d_diag0, mode, rel, absv);
+        asmb::launch(k_diag_prepare, dim3(1), dim3(1024), h->stream, f.S, f.ld, Ms, diag0 ? diag0 : sk().d_diag0, mode, rel, absv);
     }
     // The k x k matrix of a null-space iteration, fN.S (lower) = G diag(theta) G' with its diagonal regularised (S_ii += rel S_ii + absv, the
     // plain diagonal kept in diag0), and its unregularised copy N0 (pitch fN.ld; mirrored into the upper triangle for the small systems).
@@ -1120,13 +1134,13 @@ struct Dev {
                     // one wide block: its explicit inverse is made inside the launch by helper workgroups, one per 64 x 64 tile of the block
                     // rows this inner panel finishes (k_chol_panel_inv) - no k_trtri_* launches afterwards
                     const int nst = (std::min(I1, Ms) - I0 + ASM_NB - 1) / ASM_NB, T = (Ms + ASM_NB - 1) / ASM_NB;
-                    asmb::launch_resident(k_chol_panel_inv, dim3((unsigned)(G + nst * T)), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, h->d_diag0, thr, f.Linv, h->d_pflags,
-                                          h->d_ptmo, h->panel_epoch, f.Binv, f.BinvT, f.wb, G);
+                    asmb::launch_resident(k_chol_panel_inv, dim3((unsigned)(G + nst * T)), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, sk().d_diag0, thr, f.Linv, sk().d_pflags,
+                                          sk().d_ptmo, h->panel_epoch, f.Binv, f.BinvT, f.wb, G);
                 } else if (beside_updates)
-                    asmb::launch_resident(k_chol_panel, dim3((unsigned)G), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, h->d_diag0, thr, f.Linv, h->d_pflags, h->d_ptmo,
+                    asmb::launch_resident(k_chol_panel, dim3((unsigned)G), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, sk().d_diag0, thr, f.Linv, sk().d_pflags, sk().d_ptmo,
                                           h->panel_epoch);
                 else
-                    asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, h->d_diag0, thr, f.Linv, h->d_pflags, h->d_ptmo,
+                    asmb::launch_resident(k_chol_panel_solo, dim3((unsigned)G), dim3(256), s, f.S, f.ld, I0, std::min(I1, Ms), Mi, sk().d_diag0, thr, f.Linv, sk().d_pflags, sk().d_ptmo,
                                           h->panel_epoch);
             }
             if (I1 < K1 && I1 < Mi) {
@@ -1158,7 +1172,7 @@ struct Dev {
             }
             int pid = begin(ASM_K_PANEL_KERNEL, pfl, 8.0 * 2.0 * (double)(Mi - I0) * (double)(Mi - I0) * 0.5, h->stream);
             const int nhelp = (m * (m + 1) / 2 + ASM_BAND_TPH - 1) / ASM_BAND_TPH;      // helper workgroups: one per trailing tile
-            asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), h->stream, f.S, f.ld, I0, I1, Mi, h->d_diag0, thr, f.Linv, h->d_pflags, h->d_ptmo,
+            asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), h->stream, f.S, f.ld, I0, I1, Mi, sk().d_diag0, thr, f.Linv, sk().d_pflags, sk().d_ptmo,
                                   h->panel_epoch, nrt);
             end(pid);
         }
@@ -1201,11 +1215,11 @@ struct Dev {
     }
     // out = (L L')^-1 rhs   (compact vectors of length Ms)
     void chol_solve(const FacBuf& f, const double* rhs, double* out, int Ms) {
-        h2d(h->d_vecM2, rhs, Ms, Ms);
+        h2d(sk().d_vecM2, rhs, Ms, Ms);
         int id = begin(ASM_K_TRSV, 2.0 * Ms * (double)Ms, 8.0 * Ms * (double)Ms);
-        solve_launches(f, Ms, h->d_vecM2, h->d_vecM2);
+        solve_launches(f, Ms, sk().d_vecM2, sk().d_vecM2);
         end(id);
-        d2h(out, h->d_vecM2, Ms);
+        d2h(out, sk().d_vecM2, Ms);
     }
     // the substitution runs in w (a copy of the right-hand side, updated in place); the forward diagonal products read src: w, or the
     // right-hand side itself for a system of one wide block (no copy into w first)
@@ -1215,7 +1229,7 @@ struct Dev {
     template <int WB>
     void solve_launches_wb(const FacBuf& f, int Ms, double* w, const double* src) {
         // forward: w updated in place, z -> d_vecM ; backward: x -> w (w is dead by then)
-        double* z = h->d_vecM;
+        double* z = sk().d_vecM;
         const int nB = (Ms + WB - 1) / WB;
         for (int B = 0; B < nB; ++B) {
             int b1 = std::min((B + 1) * WB, Ms);
@@ -1232,11 +1246,11 @@ struct Dev {
             int np = 0;
             if (rem > 0) {
                 np = (rem + ASM_WBROWS - 1) / ASM_WBROWS;
-                asmb::launch((k_wtrsv_bwd_panel<WB>), dim3((unsigned)np), dim3(256), h->stream, f.S, f.ld, B, Me, w, h->d_wpart);
+                asmb::launch((k_wtrsv_bwd_panel<WB>), dim3((unsigned)np), dim3(256), h->stream, f.S, f.ld, B, Me, w, sk().d_wpart);
             }
             if (np > 0) {
-                asmb::launch((k_wtrsv_bwd_reduce<WB>), dim3(WB / ASM_NB), dim3(256), h->stream, B, Ms, z, h->d_wpart, np, h->d_wt);
-                asmb::launch((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), h->stream, f.BinvT, B, Ms, h->d_wt, w, WB);
+                asmb::launch((k_wtrsv_bwd_reduce<WB>), dim3(WB / ASM_NB), dim3(256), h->stream, B, Ms, z, sk().d_wpart, np, sk().d_wt);
+                asmb::launch((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), h->stream, f.BinvT, B, Ms, sk().d_wt, w, WB);
             } else {
                 // last wide block (the only one of a small system): nothing to subtract, the diagonal product reads z itself
                 asmb::launch((k_wtrsv_bwd_diag<WB>), dim3(WB / 4), dim3(256), h->stream, f.BinvT, B, Ms, z + (int64_t)B * WB, w, Ms - B * WB);
@@ -1244,62 +1258,62 @@ struct Dev {
         }
     }
     void assemble() {
-        if (h->J_valid) return;                 // J in HBM already matches dE (one assembly per evaluation, shared by the norms and the LP)
-        h->J_valid = true;
-        h->spv_J_valid = false;
-        int id = begin(ASM_K_ASSEMBLE, 0.0, 8.0 * h->nnz + 8.0 * h->nu + (h->dense_fast ? 0.0 : 24.0 * h->nu + 8.0 * h->nnz));
-        if (h->dense_fast) {
-            int64_t total = h->m * h->n;
+        if (sk().J_valid) return;                 // J in HBM already matches dE (one assembly per evaluation, shared by the norms and the LP)
+        sk().J_valid = true;
+        sk().spv_J_valid = false;
+        int id = begin(ASM_K_ASSEMBLE, 0.0, 8.0 * sk().nnz + 8.0 * sk().nu + (sk().dense_fast ? 0.0 : 24.0 * sk().nu + 8.0 * sk().nnz));
+        if (sk().dense_fast) {
+            int64_t total = sk().m * sk().n;
             unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-            asmb::launch(k_assemble_dense, dim3(g), dim3(256), h->stream, h->d_dE, h->d_J, h->m, h->n, h->ldn);
-        } else if (h->nu > 0) {
-            unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
-            asmb::launch(k_assemble, dim3(g), dim3(256), h->stream, h->d_dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, h->d_J, h->nu);
+            asmb::launch(k_assemble_dense, dim3(g), dim3(256), h->stream, sk().d_dE, sk().d_J, sk().m, sk().n, sk().ldn);
+        } else if (sk().nu > 0) {
+            unsigned g = (unsigned)std::min<int64_t>((sk().nu + 255) / 256, 4096);
+            asmb::launch(k_assemble, dim3(g), dim3(256), h->stream, sk().d_dE, sk().d_perm, sk().d_ustart, sk().d_uoff, sk().d_adjoff, sk().d_J, sk().nu);
         }
         end(id);
     }
     // rel[j] = max_i |J_ij| / max_k |J_ik|   (host, n) - matrix-based cap of the column scale
     void col_relmax(double* rel) {
-        if (h->M == 0) { std::fill(rel, rel + h->n, 0.0); return; }
-        int64_t R = std::min<int64_t>((h->M + 31) / 32, ASM_TMAXCHUNKS);
-        int64_t chunk = (h->M + R - 1) / R;
-        R = (h->M + chunk - 1) / chunk;
-        if (h->sp_ok) {                      // sparse pattern: the same maxima over the stored entries only
-            const double* vJ = sparse_vals(h->d_J);
-            int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * h->sp_nnz);
-            asmb::launch(k_sp_row_absmax, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, vJ, h->d_rho, h->M);
-            asmb::launch(k_sp_col_relmax, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vJ, h->d_rho, h->d_vecN, h->n, h->ldn);
+        if (sk().M == 0) { std::fill(rel, rel + sk().n, 0.0); return; }
+        int64_t R = std::min<int64_t>((sk().M + 31) / 32, ASM_TMAXCHUNKS);
+        int64_t chunk = (sk().M + R - 1) / R;
+        R = (sk().M + chunk - 1) / chunk;
+        if (sk().sp_ok) {                      // sparse pattern: the same maxima over the stored entries only
+            const double* vJ = sparse_vals(sk().d_J);
+            int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * sk().sp_nnz);
+            asmb::launch(k_sp_row_absmax, asmb::blocks(sk().M), dim3(256), h->stream, sk().d_sp_ptr, vJ, sk().d_rho, sk().M);
+            asmb::launch(k_sp_col_relmax, asmb::blocks(sk().ldn), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vJ, sk().d_rho, sk().d_vecN, sk().n, sk().ldn);
             end(id);
-            d2h(rel, h->d_vecN, h->n);
+            d2h(rel, sk().d_vecN, sk().n);
             return;
         }
-        int id = begin(ASM_K_SCALE, 0.0, 8.0 * 2.0 * h->M * h->ldn);
-        asmb::launch(k_row_absmax, asmb::blocks(h->M, 4), dim3(256), h->stream, h->d_J, h->ldn, h->d_rho, h->M, h->ldn);
-        asmb::launch(k_col_relmax_stage1, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, h->d_J, h->ldn, h->d_rho, h->d_partial, h->M, h->ldn, chunk);
-        asmb::launch(k_col_relmax_stage2, asmb::blocks(h->ldn), dim3(256), h->stream, h->d_partial, h->d_vecN, R, h->ldn);
+        int id = begin(ASM_K_SCALE, 0.0, 8.0 * 2.0 * sk().M * sk().ldn);
+        asmb::launch(k_row_absmax, asmb::blocks(sk().M, 4), dim3(256), h->stream, sk().d_J, sk().ldn, sk().d_rho, sk().M, sk().ldn);
+        asmb::launch(k_col_relmax_stage1, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, sk().d_J, sk().ldn, sk().d_rho, sk().d_partial, sk().M, sk().ldn, chunk);
+        asmb::launch(k_col_relmax_stage2, asmb::blocks(sk().ldn), dim3(256), h->stream, sk().d_partial, sk().d_vecN, R, sk().ldn);
         end(id);
-        d2h(rel, h->d_vecN, h->n);
+        d2h(rel, sk().d_vecN, sk().n);
     }
     // Ah = diag(1/rho) J diag(c);  rho (host, M)
     void scale(const double* c, double* rho) {
-        h->spv_Ah_valid = false;
-        h->ahT_valid = false;
-        h->ahTg_valid = false;
-        if (h->M == 0) return;
-        h2d(h->d_c, c, h->n, h->ldn);
-        if (h->sp_ok) {
-            const double* vJ = sparse_vals(h->d_J);
-            int id = begin(ASM_K_SCALE, 0.0, 8.0 * 4.0 * h->sp_nnz);
-            asmb::launch(k_sp_scale_rows, asmb::blocks(h->M), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, h->d_sp_off, vJ, h->d_c, h->d_Ah, h->d_spv_Ah, h->d_rho, h->M);
+        sk().spv_Ah_valid = false;
+        sk().ahT_valid = false;
+        sk().ahTg_valid = false;
+        if (sk().M == 0) return;
+        h2d(sk().d_c, c, sk().n, sk().ldn);
+        if (sk().sp_ok) {
+            const double* vJ = sparse_vals(sk().d_J);
+            int id = begin(ASM_K_SCALE, 0.0, 8.0 * 4.0 * sk().sp_nnz);
+            asmb::launch(k_sp_scale_rows, asmb::blocks(sk().M), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, sk().d_sp_off, vJ, sk().d_c, sk().d_Ah, sk().d_spv_Ah, sk().d_rho, sk().M);
             end(id);
-            h->spv_Ah_valid = true;
-            d2h(rho, h->d_rho, h->M);
+            sk().spv_Ah_valid = true;
+            d2h(rho, sk().d_rho, sk().M);
             return;
         }
-        int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * h->M * h->ldn);
-        asmb::launch(k_scale_rows, dim3((unsigned)h->M), dim3(256), h->stream, h->d_J, h->d_c, h->d_Ah, h->d_rho, h->n, h->ldn);
+        int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * sk().M * sk().ldn);
+        asmb::launch(k_scale_rows, dim3((unsigned)sk().M), dim3(256), h->stream, sk().d_J, sk().d_c, sk().d_Ah, sk().d_rho, sk().n, sk().ldn);
         end(id);
-        d2h(rho, h->d_rho, h->M);
+        d2h(rho, sk().d_rho, sk().M);
     }
 };
 
@@ -1339,9 +1353,9 @@ struct AsLayout {
 // Sequence number for the next publishing kernel (0 = the kernel does not publish: copy path)
 unsigned pub_next(asm_handle* h) {
     if (!h->knobs.spin_read) return 0;
-    h->scal_seq += 1;
-    if (h->scal_seq == 0) h->scal_seq = 1;
-    return h->scal_seq;
+    h->sk->scal_seq += 1;
+    if (h->sk->scal_seq == 0) h->sk->scal_seq = 1;
+    return h->sk->scal_seq;
 }
 
 struct Solver {
@@ -1363,10 +1377,11 @@ struct Solver {
     SLP lp;
 
     explicit Solver(asm_handle* hh) : h(hh), dev(hh) {}
+    Skeleton& sk() const { return *h->sk; }
 
     void atv(const vec& y, vec& out) {
         out.resize(lp.n);
-        dev.gemv_t(h->d_Ah, y.data(), out.data());
+        dev.gemv_t(sk().d_Ah, y.data(), out.data());
     }
 
     // ---------------------------------------------------------------- interior point (oracle: class IPM)
@@ -1401,9 +1416,9 @@ struct Solver {
     } arena;
     void ipm_bind() {
         IpmArena a;
-        a.base = h->d_ipm; a.ibase = h->d_ipm_i; a.snap = h->d_ipm_snap;
-        a.ln = h->ldn; a.lm = h->Mp; a.ls = h->nsp;
-        a.hscal = h->d_hscal; a.hseq = h->d_hseq; a.rpart = h->d_redpart; a.rcnt = h->d_redcnt;
+        a.base = sk().d_ipm; a.ibase = sk().d_ipm_i; a.snap = sk().d_ipm_snap;
+        a.ln = sk().ldn; a.lm = sk().Mp; a.ls = sk().nsp;
+        a.hscal = sk().d_hscal; a.hseq = sk().d_hseq; a.rpart = sk().d_redpart; a.rcnt = sk().d_redcnt;
         ipm_bind(a);
     }
     // the ONLY place that lays the arena out
@@ -1502,11 +1517,11 @@ struct Solver {
     void ipm_upload_lp() {
         ipm_bind();
         P.n = lp.n; P.M = lp.M; P.ns = lp.ns; P.scale_q = lp.scale_q;
-        if (!asmb::in_fiber() && h->h_up) {
+        if (!asmb::in_fiber() && sk().h_up) {
             // seven vectors as three copies from pinned staging (q | lb | ub and w | slo | scoef are neighbours in the arena): a copy from a
             // pageable std::vector is staged by the runtime and blocks the host for tens of microseconds each, twice per LP
-            const int64_t ln = h->ldn, lm = h->Mp, ls = h->nsp;
-            double* st = h->h_up;
+            const int64_t ln = sk().ldn, lm = sk().Mp, ls = sk().nsp;
+            double* st = sk().h_up;
             std::memcpy(st, lp.q.data(), lp.n * sizeof(double));
             std::memcpy(st + ln, lp.lb.data(), lp.n * sizeof(double));
             std::memcpy(st + 2 * ln, lp.ub.data(), lp.n * sizeof(double));
@@ -1517,7 +1532,7 @@ struct Solver {
                 double* ss = st + 3 * ln + lm;
                 std::memcpy(ss, lp.w.data(), lp.ns * sizeof(double));
                 std::memcpy(ss + ls, lp.slo.data(), lp.ns * sizeof(double));
-                std::memcpy(ss + 2 * ls, h->scoef.data(), lp.ns * sizeof(double));
+                std::memcpy(ss + 2 * ls, sk().scoef.data(), lp.ns * sizeof(double));
                 HIPCHK(asmb::copy_async((void*)P.w, ss, 3 * ls * sizeof(double), hipMemcpyHostToDevice, h->stream));
             }
             h2d_done(h);
@@ -1525,7 +1540,7 @@ struct Solver {
         }
         up(P.q, lp.q); up(P.lb, lp.lb); up(P.ub, lp.ub); up(P.r, lp.r);
         up(P.w, lp.w); up(P.slo, lp.slo);
-        vec sc(h->scoef.begin(), h->scoef.begin() + lp.ns);
+        vec sc(sk().scoef.begin(), sk().scoef.begin() + lp.ns);
         up(P.scoef, sc);
         h2d_done(h);
     }
@@ -1534,13 +1549,13 @@ struct Solver {
     // and then the sequence word; spin on the word (the stream is in order: everything before that kernel has finished too).
     void read_scal(unsigned pub) {
         if (pub == 0) {
-            HIPCHK(asmb::copy_async(h->h_scal, P.scal, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::copy_async(sk().h_scal, P.scal, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(asmb::sync(h->stream));
             return;
         }
         if (asmb::in_fiber()) {      // scenario batch: the publishing kernel is recorded; the round that launches it ends before this fiber resumes
             asmb::flush_wait();
-            if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) != pub) throw HipError("read_scal: the batch round ended without the publishing kernel's sequence word");
+            if (__atomic_load_n(sk().h_seq, __ATOMIC_ACQUIRE) != pub) throw HipError("read_scal: the batch round ended without the publishing kernel's sequence word");
             return;
         }
         // hot spin for the common case (the kernel is next on an otherwise idle stream: 6.7 us), then yield, then sleep: with several
@@ -1548,13 +1563,13 @@ struct Solver {
         // spinning thread would burn the CPU share the launching threads need
         const double t0 = now_ms();
         for (unsigned long spins = 1;; ++spins) {
-            if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
+            if (__atomic_load_n(sk().h_seq, __ATOMIC_ACQUIRE) == pub) return;
             if (spins < 20000) __builtin_ia32_pause();
             else if (spins < 20200) sched_yield();
             else { struct timespec ts = {0, 20000}; nanosleep(&ts, nullptr); }
             if (((spins < 20200 && (spins & 0xfffff) == 0) || (spins >= 20200 && (spins & 0x3ff) == 0)) && now_ms() - t0 > 30000.0) {
                 HIPCHK(asmb::sync(h->stream));            // a device fault surfaces here
-                if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) return;
+                if (__atomic_load_n(sk().h_seq, __ATOMIC_ACQUIRE) == pub) return;
                 throw HipError("read_scal: the publishing kernel finished without setting its sequence word");
             }
         }
@@ -1568,20 +1583,20 @@ struct Solver {
         for (int64_t i = 0; i < M; ++i) nineq += lp.rtype[i] != 0;
         for (int64_t j = 0; j < n; ++j) nfree += lp.ub[j] > lp.lb[j];
         ip.ncomp = std::max<int64_t>(2 * nfree + lp.ns + nineq, 1);
-        ip.usable[(int)NewtonForm::ReducedRow] = M >= RED_MIN_M && h->sp_ok;
+        ip.usable[(int)NewtonForm::ReducedRow] = M >= RED_MIN_M && sk().sp_ok;
         ip.usable[(int)NewtonForm::NullSpace] = ns_lp && lp.ns == 0;      // basis made by solve_scaled before the warm attempt
         ip.ns_k = ns_k;
-        ip.usable[(int)NewtonForm::Column] = h->col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
+        ip.usable[(int)NewtonForm::Column] = sk().col_capable && lp.ns > 0 && M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)M;   // every row owns a slack (setup)
         ipm_upload_lp();
         P.ncomp = ip.ncomp;
         launch_init_p(lp.ns == 0 ? 1 : 0);
-        dev.gemv_n_dev(h->d_Ah, P.p, P.act);
+        dev.gemv_n_dev(sk().d_Ah, P.p, P.act);
         launch_init_rest(lp.ns == 0 ? IPM_MU0_NORMAL : 1.0);
     }
 
     void ipm_measures() {
-        dev.gemv_n_dev(h->d_Ah, P.p, P.act);
-        dev.gemv_t_dev(h->d_Ah, P.y, P.aty);
+        dev.gemv_n_dev(sk().d_Ah, P.p, P.act);
+        dev.gemv_t_dev(sk().d_Ah, P.y, P.aty);
         const unsigned pub = pub_next(h);
         if (ns_live()) {
             // null-space form: the equality rows' multipliers are carried as 0, the dual residual that counts is Z'rdp (oracle: IPM.measures)
@@ -1592,12 +1607,12 @@ struct Solver {
             launch_measures(pub);
         }
         read_scal(pub);
-        ip.pinf = h->h_scal[SC_PINF];
-        ip.dinf = h->h_scal[SC_DINF];
-        ip.mu = h->h_scal[SC_MU];
+        ip.pinf = sk().h_scal[SC_PINF];
+        ip.dinf = sk().h_scal[SC_DINF];
+        ip.mu = sk().h_scal[SC_MU];
         ip.gap = ip.mu / lp.scale_q;
-        ip.ymax = h->h_scal[SC_YMAX];
-        ip.rpmax = h->h_scal[SC_RPMAX];
+        ip.ymax = sk().h_scal[SC_YMAX];
+        ip.rpmax = sk().h_scal[SC_RPMAX];
     }
 
     // rigorous primal-infeasibility certificate test (oracle: farkas_margin)
@@ -1637,28 +1652,28 @@ struct Solver {
     } ns_ar;
     // bound once per LP, like the interior-point arena: at the start of ns_setup (the k-sized buffers may be missing) and again after ns_reserve
     void ns_bind() {
-        const NsForm& F = *h->nsf;
+        const NsForm& F = *sk().nsf;
         NsArena a;
-        a.v = F.v; a.th = F.th; a.partial = h->d_partial;
+        a.v = F.v; a.th = F.th; a.partial = sk().d_partial;
         if (F.k) { a.G = F.k->G; a.N0 = F.k->N0; a.fN = &F.k->fN; }
-        a.sp_ptr = h->d_sp_ptr; a.sp_col = h->d_sp_col; a.sc_ptr = h->d_sc_ptr; a.sc_row = h->d_sc_row; a.sc_pos = h->d_sc_pos;
+        a.sp_ptr = sk().d_sp_ptr; a.sp_col = sk().d_sp_col; a.sc_ptr = sk().d_sc_ptr; a.sc_row = sk().d_sc_row; a.sc_pos = sk().d_sc_pos;
         a.X = NsIdx{F.Eidx, F.Epos, F.Iidx, F.Ipos, (int)F.L.nE, (int)F.L.nI}; a.L = F.L;
         ns_bind(a);
     }
     void ns_bind(const NsArena& a) { ns_ar = a; }
     const NsArena& nsa() const { return ns_ar; }
     NsIdx nsX() const { return nsa().X; }
-    const double* ns_vals() { const NsArena& a = nsa(); return a.vals ? a.vals : dev.sparse_vals(h->d_Ah); }
+    const double* ns_vals() { const NsArena& a = nsa(); return a.vals ? a.vals : dev.sparse_vals(sk().d_Ah); }
     int ns_count_big(const FacBuf& f, int order) {      // dropped pivots of the factor just made in f
         int v = 0;
-        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, f.S, f.ld, order, NS_BIG, h->nsf->cnt);
-        HIPCHK(asmb::copy_async(&v, h->nsf->cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), h->stream, f.S, f.ld, order, NS_BIG, sk().nsf->cnt);
+        HIPCHK(asmb::copy_async(&v, sk().nsf->cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
         return v;
     }
     // buffers sized by the null-space dimension: right-hand-side blocks R, X (k x nEp), Gt = [Zt | GI'] (k x ldg), the k x k factor
     void ns_reserve(int k) {
-        NsForm& F = *h->nsf;
+        NsForm& F = *sk().nsf;
         if (F.k && k <= F.k->cap) return;
         if (F.k) {
             // the null space grew beyond what the first LP of the form reserved (fewer fixed columns than then): the k-sized buffers are
@@ -1688,51 +1703,51 @@ struct Solver {
     // In place  Zt = L^-1 Zt  with the k x k factor just made in K.fN.  When the factor fits into one wide block the explicit inverse of
     // that block IS L^-1: one transpose + one product on the matrix cores (the rows are n long); otherwise forward substitution per column.
     void ns_ortho(int k) {
-        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         if (k <= K.fN.wb) {
             const int kp = (int)round_up(k, 32);
-            asmb::launch(k_transpose_dense, dim3((unsigned)((h->ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), h->stream, K.G, F.L.ldg, (int64_t)k, h->ldn, K.ZT, K.fN.ld, (int64_t)-1);
-            dev.gemm_nt(K.fN.Binv, K.fN.wb, K.ZT, K.fN.ld, nullptr, 0, K.G, F.L.ldg, k, (int)h->ldn, kp, 0);
+            asmb::launch(k_transpose_dense, dim3((unsigned)((sk().ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), h->stream, K.G, F.L.ldg, (int64_t)k, sk().ldn, K.ZT, K.fN.ld, (int64_t)-1);
+            dev.gemm_nt(K.fN.Binv, K.fN.wb, K.ZT, K.fN.ld, nullptr, 0, K.G, F.L.ldg, k, (int)sk().ldn, kp, 0);
         } else {
-            asmb::launch(k_ns_ortho, asmb::blocks(h->ldn), dim3(256), h->stream, K.fN.S, K.fN.ld, k, K.G, F.L.ldg, h->ldn);
+            asmb::launch(k_ns_ortho, asmb::blocks(sk().ldn), dim3(256), h->stream, K.fN.S, K.fN.ld, k, K.G, F.L.ldg, sk().ldn);
         }
     }
     // The k rows in K.G (an approximate or an outdated basis) projected onto null(A_EF) of THIS LP and orthonormalised with their own
     // Gram matrix (pivot guard `thr`, absolute), then GI' = (A_I Z)'.  Used as the second pass of ns_basis_from and, with the previous
     // LP's basis, as the whole set-up (oracle: NullSpace.__init__, warm_Z).  The factor of S0 must be current in F.f0.
     bool ns_reproject(int k, double thr) {
-        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int nE = (int)F.L.nE, nEp = (int)F.L.nEp, nIp = (int)F.L.nIp;
         const NsIdx X = nsX();
-        const double* vals = dev.sparse_vals(h->d_Ah);
+        const double* vals = dev.sparse_vals(sk().d_Ah);
         // second pass (oracle: NullSpace.basis_from): project the rows once more and orthonormalise with their own Gram matrix (~ I) -
         // the columns picked in index order can be badly conditioned, and the active-set solves need A_EF Z = 0 to 1e-13
-        asmb::launch(k_ns_rows_e, dim3((unsigned)((nEp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
+        asmb::launch(k_ns_rows_e, dim3((unsigned)((nEp + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, X, F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
         dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
-        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, h->ldn, 1);
-        dev.launch_syrk(h->stream, Dev::pick_tile(k), K.G, F.L.ldg, nullptr, 0, k, (int)h->ldn, nullptr, nullptr, K.fN.S, K.fN.ld, 0, 0);
-        dev.launch_ns_fill(h->d_diag0, 1.0, (int64_t)k);
+        asmb::launch(k_ns_pj, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, sk().ldn, 1);
+        dev.launch_syrk(h->stream, Dev::pick_tile(k), K.G, F.L.ldg, nullptr, 0, k, (int)sk().ldn, nullptr, nullptr, K.fN.S, K.fN.ld, 0, 0);
+        dev.launch_ns_fill(sk().d_diag0, 1.0, (int64_t)k);
         dev.chol(K.fN, k, thr);
         if (ns_count_big(K.fN, k) > 0) return false;
         ns_ortho(k);
-        asmb::launch(k_ns_gi, dim3((unsigned)((nIp + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vals, X, K.G, F.L.ldg, K.G + h->ldn, nIp);
+        asmb::launch(k_ns_gi, dim3((unsigned)((nIp + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, X, K.G, F.L.ldg, K.G + sk().ldn, nIp);
         return true;
     }
     // Orthonormal basis from the columns J of the projector P (oracle: NullSpace.basis_from): W = S0^-1 A_EF[:, J] by block
     // substitution with all k right-hand sides at once, P[J, :] = E_J' - W' A_EF, L_J L_J' = P[J, J] (guard: pivot <= NS_WARM_THR
     // -> not a basis), Zt = L_J^-1 P[J, :], GI' = (A_I Z)'.  The factor of S0 must be current in F.f0.
     bool ns_basis_from(const std::vector<int>& J) {
-        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int k = (int)J.size(), nE = (int)F.L.nE, nEp = (int)F.L.nEp;
         const NsIdx X = nsX();
-        const double* vals = dev.sparse_vals(h->d_Ah);
+        const double* vals = dev.sparse_vals(sk().d_Ah);
         HIPCHK(asmb::copy_async(K.J, J.data(), k * sizeof(int), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);
-        asmb::launch(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp);
+        asmb::launch(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp);
         dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
-        asmb::launch(k_ns_pj, dim3((unsigned)((h->ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, h->ldn, 0);
+        asmb::launch(k_ns_pj, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, sk().ldn, 0);
         asmb::launch(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, K.G, F.L.ldg, K.J, k, K.fN.S, K.fN.ld);
-        dev.launch_ns_fill(h->d_diag0, 1.0, (int64_t)k);
+        dev.launch_ns_fill(sk().d_diag0, 1.0, (int64_t)k);
         dev.chol(K.fN, k, NS_WARM_THR);
         if (ns_count_big(K.fN, k) > 0) return false;
         ns_ortho(k);
@@ -1742,17 +1757,17 @@ struct Solver {
     // P in index order), orthonormal basis.  False: the LP keeps the row form.
     bool ns_setup() {
         ns_bind();
-        NsForm& F = *h->nsf;
+        NsForm& F = *sk().nsf;
         const int nE = (int)F.L.nE, nEp = (int)F.L.nEp;
         const int64_t n = lp.n;
         const NsIdx X = nsX();
         int64_t nF = 0;
         for (int64_t j = 0; j < n; ++j) nF += lp.ub[j] > lp.lb[j];
         {
-            vec own(asmb::in_fiber() ? h->ldn : 0);
-            double* fm = asmb::in_fiber() ? own.data() : h->h_pin;      // (pinned staging: the copy does not go through the runtime's pageable path)
-            for (int64_t j = 0; j < h->ldn; ++j) fm[j] = (j < n && lp.ub[j] > lp.lb[j]) ? 1.0 : 0.0;
-            HIPCHK(asmb::copy_async(F.Fm, fm, h->ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            vec own(asmb::in_fiber() ? sk().ldn : 0);
+            double* fm = asmb::in_fiber() ? own.data() : sk().h_pin;      // (pinned staging: the copy does not go through the runtime's pageable path)
+            for (int64_t j = 0; j < sk().ldn; ++j) fm[j] = (j < n && lp.ub[j] > lp.lb[j]) ? 1.0 : 0.0;
+            HIPCHK(asmb::copy_async(F.Fm, fm, sk().ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
             h2d_done(h);
         }
         double t_v = now_ms();
@@ -1791,22 +1806,22 @@ struct Solver {
             ns_was_cold = true;
             // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main factor,
             // guarded Cholesky of T in index order with the absolute thresholds NS_SEL_THR in turn until exactly k columns are kept
-            if (!F.Yt) F.mem.zeroed(F.Yt, (int64_t)h->ldn * nEp + (int64_t)h->ldn * nEp, h->stream);
+            if (!F.Yt) F.mem.zeroed(F.Yt, (int64_t)sk().ldn * nEp + (int64_t)sk().ldn * nEp, h->stream);
             double* Yr = F.Yt;                                  // right-hand sides, then garbage
-            double* Yt = F.Yt + (int64_t)h->ldn * nEp;   // L0^-1 a_j as rows
-            const double* vals = dev.sparse_vals(h->d_Ah);
-            asmb::launch(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), h->stream, h->d_sc_ptr, h->d_sc_row, h->d_sc_pos, vals, X, nullptr, F.Fm, Yr, (int64_t)nEp);
+            double* Yt = F.Yt + (int64_t)sk().ldn * nEp;   // L0^-1 a_j as rows
+            const double* vals = dev.sparse_vals(sk().d_Ah);
+            asmb::launch(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, nullptr, F.Fm, Yr, (int64_t)nEp);
             dev.trsm_rows(F.f0, Yr, Yt, nEp, (int)n, nE, nullptr);
             std::vector<double> dg(n);
-            FacBuf& T = h->main_fac;
+            FacBuf& T = sk().main_fac;
             T.band = 0;
             for (int a = 0; a < 4 && !have; ++a) {
                 asmb::launch(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), h->stream, T.S, T.ld, (int)n, F.Fm);
                 dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, nEp, nullptr, 0, (int)n, nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
-                dev.launch_ns_fill(h->d_diag0, 1.0, n);
+                dev.launch_ns_fill(sk().d_diag0, 1.0, n);
                 dev.chol(T, (int)n, NS_SEL_THR[a]);
-                asmb::launch(k_ns_diag, asmb::blocks(n), dim3(256), h->stream, T.S, T.ld, (int)n, h->d_vecN);
-                HIPCHK(asmb::copy_async(dg.data(), h->d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                asmb::launch(k_ns_diag, asmb::blocks(n), dim3(256), h->stream, T.S, T.ld, (int)n, sk().d_vecN);
+                HIPCHK(asmb::copy_async(dg.data(), sk().d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
                 HIPCHK(asmb::sync(h->stream));
                 std::vector<int> Jc;
                 for (int64_t j = 0; j < n; ++j)
@@ -1823,13 +1838,13 @@ struct Solver {
     double* nsv(int which) const { return ns_ar.v + ns_ar.L.nsv_off(which); }      // work vectors: 0..4 n-sized, 5..7 M-sized, 8..9 E-sized, 10..13 k-sized (k <= n), 14..15 n-sized (14 = e)
     // oracle: ns_applicable
     bool ns_applicable() const {
-        if (!h->nsf || lp.ns != 0) return false;
+        if (!sk().nsf || lp.ns != 0) return false;
         int64_t nE = 0, nF = 0;
         for (int64_t i = 0; i < lp.M; ++i) nE += lp.rtype[i] == 0;
         for (int64_t j = 0; j < lp.n; ++j) nF += lp.ub[j] > lp.lb[j];
         return nE >= NS_MIN_E && (double)(nF - nE) <= NS_MAX_RATIO * (double)lp.M;
     }
-    NsEq nsq() const { return h->nsf->k->work(h->nsf->L).Q; }
+    NsEq nsq() const { return sk().nsf->k->work(sk().nsf->L).Q; }
     // dense products with the gathered constraint matrix Csel (nact rows of pitch ldc)
     void nsq_gemv_n(const NsEq& Q, int nact, const double* x, double* out) {
         asmb::launch(k_gemv_n, asmb::blocks(nact, 4), dim3(256), h->stream, Q.Csel, Q.ldc, x, out, (int64_t)nact, Q.ldc);
@@ -1838,26 +1853,26 @@ struct Solver {
         int64_t R = std::min<int64_t>((nact + 31) / 32, ASM_TMAXCHUNKS);
         int64_t chunk = (nact + R - 1) / R;
         R = (nact + chunk - 1) / chunk;
-        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((Q.ldc + 255) / 256), (unsigned)R), dim3(256), h->stream, Q.Csel, Q.ldc, y, h->d_partial, (int64_t)nact, Q.ldc, chunk);
-        asmb::launch(k_gemv_t_stage2, asmb::blocks(Q.ldc), dim3(256), h->stream, h->d_partial, out, R, Q.ldc);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((Q.ldc + 255) / 256), (unsigned)R), dim3(256), h->stream, Q.Csel, Q.ldc, y, sk().d_partial, (int64_t)nact, Q.ldc, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(Q.ldc), dim3(256), h->stream, sk().d_partial, out, R, Q.ldc);
     }
     // per LP (oracle: eqp_ns, the part that does not depend on the working set): pbar, A pbar, u0 = Z'(p_ref - pbar), Z'q
     void ns_lp_vectors() {
-        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int k = ns_k, nE = (int)F.L.nE;
-        const int64_t ldn = h->ldn;
+        const int64_t ldn = sk().ldn;
         const NsIdx X = nsX();
         const NsEq Q = nsq();
         const unsigned gN = (unsigned)((ldn + 255) / 256), gE = (unsigned)((nE + 255) / 256);
         double *pfix = nsv(0), *x = nsv(1), *vz = nsv(2), *yM = nsv(5), *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
         asmb::launch(k_nseq_pfix, dim3(gN), dim3(256), h->stream, A, pfix, ldn);
-        dev.gemv_n_dev(h->d_Ah, pfix, aM);
+        dev.gemv_n_dev(sk().d_Ah, pfix, aM);
         asmb::launch(k_nseq_be, dim3(gE), dim3(256), h->stream, A, X, aM, rE);
         dev.chol_solve_dev(F.f0, rE, tE, nE);
         launch_ns_rowvec_e(tE, yM);
-        dev.gemv_t_dev(h->d_Ah, yM, x);
+        dev.gemv_t_dev(sk().d_Ah, yM, x);
         asmb::launch(k_nseq_pbar, dim3(gN), dim3(256), h->stream, A, pfix, x, d_zero, Q.pbar, vz, ldn);
-        dev.gemv_n_dev(h->d_Ah, Q.pbar, Q.tbar);
+        dev.gemv_n_dev(sk().d_Ah, Q.pbar, Q.tbar);
         HIPCHK(asmb::fill_async(Q.u0, 0, 2 * Q.ldc * sizeof(double), h->stream));      // u0 and qh (contiguous)
         gemv_rows((const double*)K.G, F.L.ldg, (const double*)vz, Q.u0, (int64_t)k, ldn);
         gemv_rows((const double*)K.G, F.L.ldg, (const double*)A.q, Q.qh, (int64_t)k, ldn);
@@ -1865,9 +1880,9 @@ struct Solver {
     // Equality-constrained solve on the working set `cur` in reduced coordinates (oracle: eqp_ns).  Leaves p, y, t = Ah p, tN = Ah' y
     // for the tail kernel like as_solve.  False: more active constraints than the buffers hold (the caller uses as_solve).
     bool as_solve_ns(const AsSets& cur) {
-        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int k = ns_k, nE = (int)F.L.nE;
-        const int64_t M = lp.M, n = lp.n, ldn = h->ldn;
+        const int64_t M = lp.M, n = lp.n, ldn = sk().ldn;
         const NsIdx X = nsX();
         const NsEq Q = nsq();
         const unsigned gM = (unsigned)((M + 255) / 256), gN = (unsigned)((ldn + 255) / 256);
@@ -1904,14 +1919,14 @@ struct Solver {
         ns_gemv_t_dense(Q.u, k, zu);
         asmb::launch(k_nseq_p, asmb::blocks(n), dim3(256), h->stream, A, cur, Q, zu, ldn);
         asmb::launch(k_nseq_yi, dim3(gM), dim3(256), h->stream, A, X, Q, yM);
-        dev.gemv_t_dev(h->d_Ah, yM, atw);
+        dev.gemv_t_dev(sk().d_Ah, yM, atw);
         asmb::launch(k_nseq_w, dim3(gN), dim3(256), h->stream, A, Q, atw, wN, ldn);
-        dev.gemv_n_dev(h->d_Ah, wN, aM);
+        dev.gemv_n_dev(sk().d_Ah, wN, aM);
         launch_ns_gather_e(aM, 1.0, rE);
         dev.chol_solve_dev(F.f0, rE, tE, nE);
         asmb::launch(k_nseq_y, dim3(gM), dim3(256), h->stream, A, X, yM, tE);
-        dev.gemv_n_dev(h->d_Ah, A.p, A.t);
-        dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
+        dev.gemv_n_dev(sk().d_Ah, A.p, A.t);
+        dev.gemv_t_dev(sk().d_Ah, A.y, A.tN);
         h->stats.eqp += 1;
         return true;
     }
@@ -1920,10 +1935,10 @@ struct Solver {
     // least-squares multipliers of the equality rows for the current iterate (oracle: IPM.ns_finish_y); P.rdp is the dual residual of the last
     // measures (with the equality multipliers as they stand: 0, or the values recovered at the end of the previous stage)
     void ns_finish_y() {
-        const NsForm& F = *h->nsf;
+        const NsForm& F = *sk().nsf;
         const int nE = (int)F.L.nE;
         double *aM = nsv(6), *rE = nsv(8), *tE = nsv(9);
-        dev.gemv_n_dev(h->d_Ah, P.rdp, aM);
+        dev.gemv_n_dev(sk().d_Ah, P.rdp, aM);
         launch_ns_gather_e(aM, 1.0, rE);
         dev.chol_solve_dev(F.f0, rE, tE, nE);
         // P.rdp already contains -A_E'y_E of the multipliers recovered at the end of an earlier stage: the solve gives the correction
@@ -2043,7 +2058,7 @@ struct Solver {
     // Per iteration (oracle: IPM.run, null-space branch): reduced matrix N = Zt Th Zt' + GI' D_I^-1 GI (an unregularised copy is kept for the
     // refinement sweep), its factor, dpbar = A_EF' S0^-1 (-rp_E) and K dpbar (shared by predictor and corrector)
     void ns_iter_setup() {
-        const NsForm& F = *h->nsf; const NsK& K = *F.k;
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int k = ip.ns_k;
         // (theta~ was formed with the interior-point theta: k_ipm_theta_ns in ipm_run)
         // the k range (free columns + inequality rows, 19 000 at n = 11 192) is long and the matrix small (k = 519: 45 tiles of 64 x 64):
@@ -2053,7 +2068,7 @@ struct Solver {
         const int64_t ntile = ((k + 32 * T - 1) / (32 * T));
         int nsplit = (int)std::min<int64_t>(NS_MAX_SPLIT, std::max<int64_t>(1, 1224 / std::max<int64_t>(1, ntile * (ntile + 1) / 2)));
         nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, F.L.ldg / 512));
-        dev.ns_newton_matrix(K.G, F.L.ldg, F.th, k, nsplit, K.Np, K.fN, K.N0, h->d_diag0, 1e-13, 1e-30);
+        dev.ns_newton_matrix(K.G, F.L.ldg, F.th, k, nsplit, K.Np, K.fN, K.N0, sk().d_diag0, 1e-13, 1e-30);
         dev.chol(K.fN, k, 1e-14, false);
         // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
         if (!ip.ns_e_ready) {
@@ -2137,30 +2152,30 @@ struct Solver {
     // out = in through the main factor of a row (column) list: gather in[idx[0:cnt]], solve, scatter back; k_red_scatter gives the
     // ndrop rows didx outside the list out = in / ddrop (pure permutations: none).  The scatter covers `len` rows.
     void solve_list(const int* idx, int cnt, const int* didx, int ndrop, const double* ddrop, const double* in, double* out, int64_t len) {
-        launch_red_gather(idx, cnt, in, h->d_rce);
-        dev.chol_solve_dev(h->main_fac, h->d_rce, h->d_rze, cnt);
-        launch_red_scatter(idx, cnt, h->d_rze, didx, ndrop, ddrop, in, out, len);
+        launch_red_gather(idx, cnt, in, sk().d_rce);
+        dev.chol_solve_dev(sk().main_fac, sk().d_rce, sk().d_rze, cnt);
+        launch_red_scatter(idx, cnt, sk().d_rze, didx, ndrop, ddrop, in, out, len);
     }
     // out = (approximate) S^-1 in : the Cholesky factor of S (row forms) or Sherman-Morrison-Woodbury through the factor of K (column form)
     void precond(const double* in, double* out) {
         const int M = (int)lp.M, n = (int)lp.n;
         switch (form) {
         case NewtonForm::ReducedRow:
-            solve_list(h->d_idx, (int)red.kept.size(), h->d_idxI, (int)red.diag.size(), h->d_rdI, in, out, M);
+            solve_list(sk().d_idx, (int)red.kept.size(), sk().d_idxI, (int)red.diag.size(), sk().d_rdI, in, out, M);
             return;
         case NewtonForm::BandedRow:      // rows in the handle's banded order
-            solve_list(h->d_rowperm, M, h->d_rowperm, 0, h->d_rze, in, out, M);
+            solve_list(sk().d_rowperm, M, sk().d_rowperm, 0, sk().d_rze, in, out, M);
             return;
         case NewtonForm::Column:
-            launch_col_scale(h->d_cdinv, in, h->d_cu);                                                                 // u = D^-1 r
-            dev.gemv_t_dev(h->d_Ah, h->d_cu, h->d_ct);                                                                 // Ah' u
-            if (h->col_band > 0) solve_list(h->d_colperm, n, h->d_colperm, 0, h->d_rze, h->d_ct, h->d_cv, n);         // K^-1 (columns in banded order)
-            else dev.chol_solve_dev(h->main_fac, h->d_ct, h->d_cv, n);                                                 // K^-1
-            dev.gemv_n_dev(h->d_Ah, h->d_cv, h->d_cw);                                                                 // Ah v
-            launch_col_finish(h->d_cdinv, h->d_cu, h->d_cw, out);
+            launch_col_scale(sk().d_cdinv, in, sk().d_cu);                                                                 // u = D^-1 r
+            dev.gemv_t_dev(sk().d_Ah, sk().d_cu, sk().d_ct);                                                                 // Ah' u
+            if (sk().col_band > 0) solve_list(sk().d_colperm, n, sk().d_colperm, 0, sk().d_rze, sk().d_ct, sk().d_cv, n);         // K^-1 (columns in banded order)
+            else dev.chol_solve_dev(sk().main_fac, sk().d_ct, sk().d_cv, n);                                                 // K^-1
+            dev.gemv_n_dev(sk().d_Ah, sk().d_cv, sk().d_cw);                                                                 // Ah v
+            launch_col_finish(sk().d_cdinv, sk().d_cu, sk().d_cw, out);
             return;
         default:      // Row (the null-space form solves in ns_newton)
-            dev.chol_solve_dev(h->main_fac, in, out, M);
+            dev.chol_solve_dev(sk().main_fac, in, out, M);
         }
     }
     // one Newton solve with the current factor (oracle: IPM.run.solve); mode 0 affine, 1 Mehrotra corrector built on
@@ -2170,21 +2185,21 @@ struct Solver {
     // iteration's solves with spec = 0 when one of them missed its tolerance: one host round trip per solve less in the common case).
     void ipm_solve(int mode, const IpmDir& base, IpmDir& D, double tp = 0.0, double td = 0.0, int spec = 0) {
         launch_rhs1(base, mode, tp, td);
-        dev.gemv_n_dev(h->d_Ah, P.tmpn, P.t1);
+        dev.gemv_n_dev(sk().d_Ah, P.tmpn, P.t1);
         launch_rhs2(mode == 2 ? 0.0 : 1.0);
         precond(P.rhs, D.dy);
         if (spec) {
-            dev.gemv_t_dev(h->d_Ah, D.dy, d_tN);
+            dev.gemv_t_dev(sk().d_Ah, D.dy, d_tN);
             launch_vec_mul(d_tN, P.thp_inv, lp.n);
-            dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
+            dev.gemv_n_dev(sk().d_Ah, d_tN, d_sres);
             launch_res(D.dy, 0u, spec, 1e-10, PCG_KAPPA * ip.rpmax);
         } else {
             // preconditioned CG on the unregularised Schur system, the Cholesky factor as preconditioner (oracle: IPM.run.solve).
             // The residual of this system is exactly the primal residual the step leaves behind, hence the tolerance.
             auto applyS = [&](const double* v) {          // d_sres = Ah Th^-1 Ah' v
-                dev.gemv_t_dev(h->d_Ah, v, d_tN);
+                dev.gemv_t_dev(sk().d_Ah, v, d_tN);
                 launch_vec_mul(d_tN, P.thp_inv, lp.n);
-                dev.gemv_n_dev(h->d_Ah, d_tN, d_sres);
+                dev.gemv_n_dev(sk().d_Ah, d_tN, d_sres);
             };
             applyS(D.dy);
             unsigned pub = pub_next(h);
@@ -2192,8 +2207,8 @@ struct Solver {
             read_scal(pub);
             // the approximate preconditioners (column and reduced row form) get the tighter floor (oracle: IPM.run.solve)
             const bool approx = form == NewtonForm::Column || form == NewtonForm::ReducedRow;
-            const double tol = std::max((approx ? 1e-13 : 1e-10) * h->h_scal[SC_RMAX], PCG_KAPPA * ip.rpmax);
-            if (h->h_scal[SC_EMAX] > tol) {
+            const double tol = std::max((approx ? 1e-13 : 1e-10) * sk().h_scal[SC_RMAX], PCG_KAPPA * ip.rpmax);
+            if (sk().h_scal[SC_EMAX] > tol) {
                 precond(P.res, d_corr);
                 launch_pcg_start();
                 bool converged = false;
@@ -2204,28 +2219,28 @@ struct Solver {
                     read_scal(pub);
                     h->stats_pcg += 1;
                     cg_max = std::max(cg_max, it + 1);
-                    if (h->h_scal[SC_STOP] != 0.0) break;
-                    if (h->h_scal[SC_EMAX] <= tol) { converged = true; break; }
+                    if (sk().h_scal[SC_STOP] != 0.0) break;
+                    if (sk().h_scal[SC_EMAX] <= tol) { converged = true; break; }
                     precond(P.res, d_corr);
                     launch_pcg_step2();
                 }
                 if (!converged) cg_fail = true;
             }
         }
-        dev.gemv_t_dev(h->d_Ah, D.dy, d_tN);
+        dev.gemv_t_dev(sk().d_Ah, D.dy, d_tN);
         launch_dir(D);
     }
 
     // reduced row form (oracle: IPM.run): inequality rows whose slack term dominates their Schur diagonal stay out of the factor and get a
     // diagonal preconditioner.  Reads both vectors back.  False: too few such rows, or no row left for the factor.
     bool red_select() {
-        dev.schur_diag(P.thp_inv, h->d_sdiag);
+        dev.schur_diag(P.thp_inv, sk().d_sdiag);
         down(red.dS, P.dS, lp.M);
-        down(red.sdiag, h->d_sdiag, lp.M);
+        down(red.sdiag, sk().d_sdiag, lp.M);
         HIPCHK(asmb::sync(h->stream));
         red.kept.clear(); red.diag.clear();
         for (int64_t q = 0; q < lp.M; ++q) {                 // kept rows in the order of the factorisations
-            const int64_t i = h->row_band > 0 ? h->row_perm_h[q] : q;
+            const int64_t i = sk().row_band > 0 ? sk().row_perm_h[q] : q;
             if (red.dS[i] > RED_TAU * red.sdiag[i]) red.diag.push_back((int)i);
             else red.kept.push_back((int)i);
         }
@@ -2236,7 +2251,7 @@ struct Solver {
         if (usable(NewtonForm::NullSpace)) return NewtonForm::NullSpace;
         if (usable(NewtonForm::Column)) return NewtonForm::Column;
         if (usable(NewtonForm::ReducedRow) && red_select()) return NewtonForm::ReducedRow;
-        return h->row_band > 0 ? NewtonForm::BandedRow : NewtonForm::Row;
+        return sk().row_band > 0 ? NewtonForm::BandedRow : NewtonForm::Row;
     }
     // The Newton matrix of the current form and its factor (oracle: IPM.run).  Column form: K = Th + Ah' D^-1 Ah (n x n) while its
     // Sherman-Morrison-Woodbury preconditioner keeps the CG short; row forms: S = Ah Th^-1 Ah' + D (kept rows, or M x M); all three in
@@ -2248,20 +2263,20 @@ struct Solver {
             return;
         }
         const int M = (int)lp.M, n = (int)lp.n;
-        FacBuf& f = h->main_fac;
-        f.band = form == NewtonForm::Column ? h->col_band : h->row_band;
+        FacBuf& f = sk().main_fac;
+        f.band = form == NewtonForm::Column ? sk().col_band : sk().row_band;
         int dim = M;
         switch (form) {
         case NewtonForm::Column:
             ip.col_iters += 1;
             dim = n;
-            launch_col_prep(IPM_RHO_P, COL_FIXED, h->d_cdinv, h->d_cth);
-            if (h->col_band > 0) {
+            launch_col_prep(IPM_RHO_P, COL_FIXED, sk().d_cdinv, sk().d_cth);
+            if (sk().col_band > 0) {
                 // columns in their banded order: K built from the structural column pairs, factor and substitutions stop at the band
-                launch_red_gather(h->d_colperm, (int)lp.n, h->d_cth, h->d_diag);
-                dev.schur_banded_cols_dev(h->d_cdinv, h->d_diag);
+                launch_red_gather(sk().d_colperm, (int)lp.n, sk().d_cth, sk().d_diag);
+                dev.schur_banded_cols_dev(sk().d_cdinv, sk().d_diag);
             } else {
-                dev.schur_syrk(true, nullptr, n, h->d_cdinv, h->d_cth, f.S, f.ld, Dev::NzFlags::Pattern);
+                dev.schur_syrk(true, nullptr, n, sk().d_cdinv, sk().d_cth, f.S, f.ld, Dev::NzFlags::Pattern);
             }
             break;
         case NewtonForm::ReducedRow: {
@@ -2271,24 +2286,24 @@ struct Solver {
             vec dE_(dim), dI_(nd);
             for (int a = 0; a < dim; ++a) dE_[a] = red.dS[red.kept[a]];
             for (int b = 0; b < nd; ++b) dI_[b] = red.sdiag[red.diag[b]] + red.dS[red.diag[b]];
-            HIPCHK(asmb::copy_async(h->d_idx, red.kept.data(), dim * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(asmb::copy_async(h->d_idxI, red.diag.data(), nd * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(asmb::copy_async(h->d_diag, dE_.data(), dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(asmb::copy_async(h->d_rdI, dI_.data(), nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(sk().d_idx, red.kept.data(), dim * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(sk().d_idxI, red.diag.data(), nd * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(sk().d_diag, dE_.data(), dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(asmb::copy_async(sk().d_rdI, dI_.data(), nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
             std::vector<int> cp;
-            if (h->row_band > 0) {      // place of every row in the list (-1: not in it)
+            if (sk().row_band > 0) {      // place of every row in the list (-1: not in it)
                 cp.assign(lp.M, -1);
                 for (int a = 0; a < dim; ++a) cp[red.kept[a]] = a;
-                HIPCHK(asmb::copy_async(h->d_cpos, cp.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(asmb::copy_async(sk().d_cpos, cp.data(), lp.M * sizeof(int), hipMemcpyHostToDevice, h->stream));
             }
             h2d_done(h);      // the host vectors go out of scope
-            dev.schur_rows(h->d_idx, h->d_cpos, dim, P.thp_inv, h->d_diag);
+            dev.schur_rows(sk().d_idx, sk().d_cpos, dim, P.thp_inv, sk().d_diag);
             break;
         }
         case NewtonForm::BandedRow:
             // full row form, rows in the banded order: S is built entry by entry, factor and substitutions stop at the band
-            launch_red_gather(h->d_rowperm, M, P.dS, h->d_diag);
-            dev.schur_banded_dev(h->d_rowpos, M, P.thp_inv, h->d_diag);
+            launch_red_gather(sk().d_rowperm, M, P.dS, sk().d_diag);
+            dev.schur_banded_dev(sk().d_rowpos, M, P.thp_inv, sk().d_diag);
             break;
         default:      // Row
             dev.schur_syrk(false, nullptr, M, P.thp_inv, P.dS, f.S, f.ld, Dev::NzFlags::Pattern);
@@ -2316,8 +2331,8 @@ struct Solver {
             ipm_measures();
             if (ns_pending) {
                 ns_pending = false;
-                if (h->knobs.verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e (null-space step, applied on the device)\n", h->h_scal[SC_AP], h->h_scal[SC_AD]);
-                if (h->h_scal[SC_NSERR] > h->knobs.ns_rerr) {
+                if (h->knobs.verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e (null-space step, applied on the device)\n", sk().h_scal[SC_AP], sk().h_scal[SC_AD]);
+                if (sk().h_scal[SC_NSERR] > h->knobs.ns_rerr) {
                     // the reduced system lost its accuracy and the device left the iterate alone: redo the iteration in row form
                     // (oracle: IPM.run) - measured again below as the row form measures it
                     drop_form(NewtonForm::NullSpace);
@@ -2370,8 +2385,8 @@ struct Solver {
                 unsigned pub = pub_next(h);
                 launch_steps(dirC, pub);
                 read_scal(pub);
-                if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
-                ap = h->h_scal[SC_AP]; ad = h->h_scal[SC_AD];
+                if (deferred && sk().h_scal[SC_SPEC] != 0.0) return false;
+                ap = sk().h_scal[SC_AP]; ad = sk().h_scal[SC_AD];
                 // Gondzio multiple centrality correctors (oracle: IPM.run): dirA is free again and receives the candidate
                 for (int kc = 0; kc < (ns ? 0 : IPM_MCC); ++kc) {      // (no correctors in null-space form: a Newton solve costs more than the factorisation there)
                     if (std::min(ap, ad) >= 0.9) break;
@@ -2381,8 +2396,8 @@ struct Solver {
                     pub = pub_next(h);
                     launch_steps(dirA, pub);
                     read_scal(pub);
-                    if (deferred && h->h_scal[SC_SPEC] != 0.0) return false;
-                    const double ap2 = h->h_scal[SC_AP], ad2 = h->h_scal[SC_AD];
+                    if (deferred && sk().h_scal[SC_SPEC] != 0.0) return false;
+                    const double ap2 = sk().h_scal[SC_AP], ad2 = sk().h_scal[SC_AD];
                     if (!(ap2 >= ap && ad2 >= ad && ap2 + ad2 >= ap + ad + MCC_GAMMA * MCC_DELTA)) break;
                     std::swap(dirA, dirC);
                     ap = ap2; ad = ad2;
@@ -2401,7 +2416,7 @@ struct Solver {
             if (h->knobs.verbose) std::fprintf(stderr, "[asm]     ap %.3e ad %.3e  cg steps so far %lld\n", ap, ad, (long long)h->stats_pcg);
             // the reduced system lost its accuracy, or the preconditioner of the column / reduced row form did: redo the iteration in the
             // next form (oracle: IPM.run)
-            if (ns ? h->h_scal[SC_NSERR] > h->knobs.ns_rerr : approx && cg_fail) {
+            if (ns ? sk().h_scal[SC_NSERR] > h->knobs.ns_rerr : approx && cg_fail) {
                 drop_form(form);
                 continue;
             }
@@ -2438,8 +2453,8 @@ struct Solver {
     } as_arena;
     void as_bind() {
         AsArena a;
-        a.base = h->d_as; a.ibase = h->d_as_i; a.rperm = h->row_band > 0 ? h->d_rowperm : nullptr;
-        a.ln = h->ldn; a.lm = h->Mp; a.ls = h->nsp;
+        a.base = sk().d_as; a.ibase = sk().d_as_i; a.rperm = sk().row_band > 0 ? sk().d_rowperm : nullptr;
+        a.ln = sk().ldn; a.lm = sk().Mp; a.ls = sk().nsp;
         as_bind(a);
     }
     // the ONLY place that lays the two arenas out (the LP vectors are those of the interior-point arena: ipm_bind comes first)
@@ -2537,8 +2552,8 @@ struct Solver {
         launch_as_clip0(nullptr, d_zero);
     }
     void as_read() {
-        HIPCHK(asmb::copy_async(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(asmb::copy_async(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(sk().h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(sk().h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
     }
     void as_copy_sets(int dst, int src) {
@@ -2560,14 +2575,14 @@ struct Solver {
     // final answer of the LP (device -> host): p, s, y, z, act and the working set `final_sets`
     void as_download(EqpOut& o, ActiveSet& as) {
         const int64_t n = lp.n, M = lp.M, ns = lp.ns;
-        if (!asmb::in_fiber() && h->d_dl) {
+        if (!asmb::in_fiber() && sk().d_dl) {
             // outside a batch: packed on the device, one copy into pinned memory (eight copies into pageable vectors cost the host tens of
             // microseconds each, with the GPU idle in between)
-            launch_as_pack(S_[final_sets], h->d_dl);
+            launch_as_pack(S_[final_sets], sk().d_dl);
             const size_t bytes = (size_t)(2 * n + 2 * M + ns) * sizeof(double) + (size_t)(M + n + ns) * sizeof(int);
-            HIPCHK(asmb::copy_async(h->h_dl, h->d_dl, bytes, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::copy_async(sk().h_dl, sk().d_dl, bytes, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(asmb::sync(h->stream));
-            const double* st = h->h_dl;
+            const double* st = sk().h_dl;
             o.p.assign(st, st + n); o.z.assign(st + n, st + 2 * n); o.y.assign(st + 2 * n, st + 2 * n + M); o.act.assign(st + 2 * n + M, st + 2 * n + 2 * M);
             o.s.assign(st + 2 * n + 2 * M, st + 2 * n + 2 * M + ns);
             const int* bi = reinterpret_cast<const int*>(st + 2 * n + 2 * M + ns);
@@ -2602,52 +2617,52 @@ struct Solver {
     bool part_factor = false;   // the main factor is the factor of the partition's Schur matrix (face_polish re-uses it for the rounds on the same sets)
     void as_solve(const AsSets& cur, const double* p_ref, const double* y_ref, int mode, bool reuse_factor = false) {
         launch_as_setup(cur, p_ref);
-        HIPCHK(asmb::copy_async(h->h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(sk().h_ascnt, A.cnt, AC_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
-        const int nH = h->h_ascnt[AC_NH], nF = h->h_ascnt[AC_NF];
-        const bool any_soft = h->h_ascnt[AC_ANYSOFT] != 0;
+        const int nH = sk().h_ascnt[AC_NH], nF = sk().h_ascnt[AC_NF];
+        const bool any_soft = sk().h_ascnt[AC_ANYSOFT] != 0;
         as_nH = nH; as_nF = nF;
         if (nH > 0) {
-            dev.gemv_n_dev(h->d_Ah, A.pB, A.t);
-            if (any_soft) dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
+            dev.gemv_n_dev(sk().d_Ah, A.pB, A.t);
+            if (any_soft) dev.gemv_t_dev(sk().d_Ah, A.y, A.tN);
             launch_as_rhs(y_ref);
         }
         if (nH > 0 && nF > 0) {
             if (!(reuse_factor && part_factor)) {
-                h->main_fac.band = h->row_band;
+                sk().main_fac.band = sk().row_band;
                 dev.schur_rows(A.Hidx, A.hpos, nH, A.Fmask, nullptr);        // (Hidx is in the banded row order when there is one: k_as_setup)
-                dev.diag_prepare(h->main_fac, nH, 1, 0.0, 0.0);
-                dev.chol(h->main_fac, nH, 1e-10);
+                dev.diag_prepare(sk().main_fac, nH, 1, 0.0, 0.0);
+                dev.chol(sk().main_fac, nH, 1e-10);
                 part_factor = false;
             }
             const int sweeps = mode == 1 ? 3 : 4;
             for (int it = 0; it < sweeps; ++it) {
                 if (mode != 2) {
-                    dev.gemv_n_dev(h->d_Ah, A.pF, A.t);                                                  // A_HF pF
+                    dev.gemv_n_dev(sk().d_Ah, A.pF, A.t);                                                  // A_HF pF
                     launch_as_res_p(nH);
-                    dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
+                    dev.chol_solve_dev(sk().main_fac, A.v, A.u, nH);
                     launch_as_scatter_h(A.u, mode == 1 ? 1 : 0);
-                    dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' u
+                    dev.gemv_t_dev(sk().d_Ah, A.yfull, A.tN);                                              // A_HF' u
                     launch_as_add_f();
                 }
                 if (mode != 1) {
                     launch_as_scatter_h(A.yH, 0);
-                    dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);                                              // A_HF' yH
+                    dev.gemv_t_dev(sk().d_Ah, A.yfull, A.tN);                                              // A_HF' yH
                     launch_as_rd();
-                    dev.gemv_n_dev(h->d_Ah, A.rd, A.t);                                                  // A_HF rd
+                    dev.gemv_n_dev(sk().d_Ah, A.rd, A.t);                                                  // A_HF rd
                     launch_as_gather_h(nH);
-                    dev.chol_solve_dev(h->main_fac, A.v, A.u, nH);
+                    dev.chol_solve_dev(sk().main_fac, A.v, A.u, nH);
                     launch_as_add_yh(nH);
                 }
             }
         }
         if (nH > 0) launch_as_merge(mode != 1 ? 1 : 0);
-        dev.gemv_n_dev(h->d_Ah, A.p, A.t);
+        dev.gemv_n_dev(sk().d_Ah, A.p, A.t);
         if (mode == 1) {
             launch_as_scatter_h(A.uacc, 0);
-            dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
+            dev.gemv_t_dev(sk().d_Ah, A.yfull, A.tN);
         } else {
-            dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
+            dev.gemv_t_dev(sk().d_Ah, A.y, A.tN);
         }
         h->stats.eqp += 1;
     }
@@ -2669,13 +2684,13 @@ struct Solver {
             }
             launch_as_finish(S_[cur], S_[nx], S_[prev], have_prev ? 1 : 0, TOL_P, TOL_D);
             as_read();
-            const double pr = h->h_asscal[AS_PR], du = h->h_asscal[AS_DU];
+            const double pr = sk().h_asscal[AS_PR], du = sk().h_asscal[AS_DU];
             h->stats.kkt_pr = pr;
             h->stats.kkt_du = du;
             final_sets = cur;
             if (h->knobs.verbose) {
                 const double t_now = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-                std::fprintf(stderr, "[asm] eqp round %d: pr %.3e du %.3e changes %d  (%.2f ms)\n", k, pr, du, h->h_ascnt[AC_NCHG], t_now - t_round);
+                std::fprintf(stderr, "[asm] eqp round %d: pr %.3e du %.3e changes %d  (%.2f ms)\n", k, pr, du, sk().h_ascnt[AC_NCHG], t_now - t_round);
                 t_round = t_now;
             }
             if (pr <= TOL_P && du <= TOL_D) return true;
@@ -2683,9 +2698,9 @@ struct Solver {
             // oracle: EQP_RUNAWAY - a correction that made the primal residual 1000 times worse has left the neighbourhood of the partition
             if (pr_last >= 0.0 && pr > EQP_RUNAWAY * std::max(pr_last, TOL_P)) break;
             pr_last = pr;
-            if (h->h_ascnt[AC_NCHG] == 0 || (have_prev && h->h_ascnt[AC_NDIFF] == 0)) break;
+            if (sk().h_ascnt[AC_NCHG] == 0 || (have_prev && sk().h_ascnt[AC_NDIFF] == 0)) break;
             // oracle: EQP_MAXCHG - a correction that moves more than 3 % of all constraints at once has run away: the next solve is not made
-            if ((double)h->h_ascnt[AC_NCHG] > std::max((double)EQP_MINCHG, EQP_MAXCHG * (double)(lp.n + lp.M + lp.ns))) break;
+            if ((double)sk().h_ascnt[AC_NCHG] > std::max((double)EQP_MINCHG, EQP_MAXCHG * (double)(lp.n + lp.M + lp.ns))) break;
             const int old_prev = prev;
             prev = cur; cur = nx; nx = old_prev;
             have_prev = true;
@@ -2749,7 +2764,7 @@ struct Solver {
     };
 
     bool face_primal_anchored() {
-        const int64_t n = lp.n, M = lp.M, ns = lp.ns, ldz = h->ldn;
+        const int64_t n = lp.n, M = lp.M, ns = lp.ns, ldz = sk().ldn;
         as_copy_sets(4, 3);
         as_solve(S_[4], nullptr, nullptr, 1);            // p0 = least-norm point of the partition; its factor, Hidx, Fmask stay
         const int nH0 = as_nH;
@@ -2762,18 +2777,18 @@ struct Solver {
         for (int st = 0; st < FACE_STEPS; ++st) {
             const int k = (int)members.size();
             if (k > 0) {
-                HIPCHK(asmb::copy_async(h->d_nsu, u.data(), k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                launch_face_ns_combine(p0, h->d_Zbuf, ldz, h->d_nsu, k, A.p);
+                HIPCHK(asmb::copy_async(sk().d_nsu, u.data(), k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                launch_face_ns_combine(p0, sk().d_Zbuf, ldz, sk().d_nsu, k, A.p);
             } else {
                 dcopy(A.p, p0, n);
             }
-            dev.gemv_n_dev(h->d_Ah, A.p, A.t);
+            dev.gemv_n_dev(sk().d_Ah, A.p, A.t);
             launch_face_ns_step(S_[4], d_pa, d_sa, d_acta, TOL_P);
             as_read();                                    // (the host copy of u is no longer needed by the device after this)
-            const int nviol = h->h_ascnt[AC_NVIOL];
+            const int nviol = sk().h_ascnt[AC_NVIOL];
             if (h->knobs.verbose && (st < 5 || st % 20 == 0 || nviol == 0))
-                std::fprintf(stderr, "[asm] face primal anchored %d: members %d viol %d hres %.2e\n", st, k, nviol, h->h_asscal[AS_HARDRES]);
-            if (h->h_asscal[AS_HARDRES] > TOL_P) return false;
+                std::fprintf(stderr, "[asm] face primal anchored %d: members %d viol %d hres %.2e\n", st, k, nviol, sk().h_asscal[AS_HARDRES]);
+            if (sk().h_asscal[AS_HARDRES] > TOL_P) return false;
             if (nviol == 0) {
                 int jw = -1;
                 double worst = FACE_TOL_M;
@@ -2784,7 +2799,7 @@ struct Solver {
                 dcopy(d_pa, A.p, n); dcopy(d_sa, A.s, ns); dcopy(d_acta, A.act, M);
                 const int last = k - 1;
                 if (jw != last) {
-                    dcopy(h->d_Zbuf + (int64_t)jw * ldz, h->d_Zbuf + (int64_t)last * ldz, ldz);
+                    dcopy(sk().d_Zbuf + (int64_t)jw * ldz, sk().d_Zbuf + (int64_t)last * ldz, ldz);
                     members[jw] = members[last]; g[jw] = g[last]; sign[jw] = sign[last];
                 }
                 members.pop_back(); g.pop_back(); sign.pop_back();
@@ -2792,31 +2807,31 @@ struct Solver {
                 u = sc.solve(g);
                 continue;
             }
-            const int fam = h->h_ascnt[AC_NCHG];
-            const int64_t e = h->h_ascnt[AC_NDIFF];
+            const int fam = sk().h_ascnt[AC_NCHG];
+            const int64_t e = sk().h_ascnt[AC_NDIFF];
             if (fam < 0) return false;                    // no blocking inequality could be named (a ratio that is not a number): k_face_ns_step
-            launch_face_ns_col(h->d_Ah, h->ldn, fam, e, p0, t0);
+            launch_face_ns_col(sk().d_Ah, sk().ldn, fam, e, p0, t0);
             if (nH0 > 0) {
-                dev.gemv_n_dev(h->d_Ah, A.rd, A.t);
+                dev.gemv_n_dev(sk().d_Ah, A.rd, A.t);
                 launch_as_gather_h(nH0);
-                dev.chol_solve_dev(h->main_fac, A.v, A.u, nH0);
+                dev.chol_solve_dev(sk().main_fac, A.v, A.u, nH0);
                 launch_as_scatter_h(A.u, 0);
-                dev.gemv_t_dev(h->d_Ah, A.yfull, A.tN);
+                dev.gemv_t_dev(sk().d_Ah, A.yfull, A.tN);
             } else {
-                HIPCHK(asmb::fill_async(A.tN, 0, h->ldn * sizeof(double), h->stream));
+                HIPCHK(asmb::fill_async(A.tN, 0, sk().ldn * sizeof(double), h->stream));
             }
-            double* znew = h->d_Zbuf + (int64_t)k * ldz;
+            double* znew = sk().d_Zbuf + (int64_t)k * ldz;
             launch_face_ns_z(znew);
-            asmb::launch(k_gemv_n, asmb::blocks(k + 1, 4), dim3(256), h->stream, h->d_Zbuf, ldz, znew, h->d_nsdots, (int64_t)(k + 1), ldz);
-            HIPCHK(asmb::copy_async(h->h_nsdots, h->d_nsdots, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(asmb::copy_async(h->h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            asmb::launch(k_gemv_n, asmb::blocks(k + 1, 4), dim3(256), h->stream, sk().d_Zbuf, ldz, znew, sk().d_nsdots, (int64_t)(k + 1), ldz);
+            HIPCHK(asmb::copy_async(sk().h_nsdots, sk().d_nsdots, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::copy_async(sk().h_asscal, A.scal, AS_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(asmb::sync(h->stream));
-            const double zz = h->h_nsdots[k], cc = h->h_asscal[AS_PR];
+            const double zz = sk().h_nsdots[k], cc = sk().h_asscal[AS_PR];
             if (!(zz > 1e-10 * cc)) return false;        // dependent on the working set although it blocks
-            vec trow(h->h_nsdots, h->h_nsdots + k + 1);
+            vec trow(sk().h_nsdots, sk().h_nsdots + k + 1);
             if (!sc.append(trow)) return false;
             members.emplace_back(fam, e);
-            g.push_back(h->h_asscal[AS_EQRES]);
+            g.push_back(sk().h_asscal[AS_EQRES]);
             sign.push_back(fam == 0 ? (double)lp.rtype[e] : (fam == 1 ? -lp.scoef[e] : (fam == 2 ? 1.0 : -1.0)));
             u = sc.solve(g);
             h->stats.eqp += 1;
@@ -2833,10 +2848,10 @@ struct Solver {
         as_solve(S_[3], d_pref, P.y, 0);
         launch_as_finish(S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
         as_read();
-        h->stats.kkt_pr = h->h_asscal[AS_PR];
-        h->stats.kkt_du = h->h_asscal[AS_DU];
-        if (h->knobs.verbose) std::fprintf(stderr, "[asm] face polish: projection of the iterate on its partition pr %.3e du %.3e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
-        if (!(h->h_asscal[AS_PR] <= TOL_P && h->h_asscal[AS_DU] <= TOL_D)) return 0;
+        h->stats.kkt_pr = sk().h_asscal[AS_PR];
+        h->stats.kkt_du = sk().h_asscal[AS_DU];
+        if (h->knobs.verbose) std::fprintf(stderr, "[asm] face polish: projection of the iterate on its partition pr %.3e du %.3e\n", sk().h_asscal[AS_PR], sk().h_asscal[AS_DU]);
+        if (!(sk().h_asscal[AS_PR] <= TOL_P && sk().h_asscal[AS_DU] <= TOL_D)) return 0;
         dcopy(d_p0, A.p, n); dcopy(d_s0, A.s, ns); dcopy(d_y0, A.y, M); dcopy(d_act0, A.act, M); dcopy(d_z0, A.z, n);
         part_factor = true;            // the main factor belongs to the partition: the first dual / primal round below re-use it
         // ---- dual: basic least-squares multipliers on the partition, sign repair (oracle: face_dual; independent of the primal
@@ -2847,8 +2862,8 @@ struct Solver {
             as_solve(S_[5], nullptr, nullptr, 2, r == 0);
             launch_face_dual_finish(S_[5], FACE_TOL_M);
             as_read();
-            if (h->knobs.verbose) std::fprintf(stderr, "[asm] face dual %d: nH %d nF %d viol %d\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL]);
-            if (h->h_ascnt[AC_NVIOL] == 0) { okd = true; break; }
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] face dual %d: nH %d nF %d viol %d\n", r, as_nH, as_nF, sk().h_ascnt[AC_NVIOL]);
+            if (sk().h_ascnt[AC_NVIOL] == 0) { okd = true; break; }
         }
         if (okd) { dcopy(d_yf, A.y, M); dcopy(d_zf, A.z, n); }
         // ---- primal: bulk rounds
@@ -2859,10 +2874,10 @@ struct Solver {
                 as_solve(S_[4], nullptr, nullptr, 1, r == 0);
                 launch_face_primal_finish(S_[4], S_[3], TOL_P, FACE_TOL_M, 0);
                 as_read();
-                if (h->knobs.verbose) std::fprintf(stderr, "[asm] face primal bulk %d: nH %d nF %d viol %d rel %d hres %.2e\n", r, as_nH, as_nF, h->h_ascnt[AC_NVIOL], h->h_ascnt[AC_NREL], h->h_asscal[AS_HARDRES]);
-                if (h->h_asscal[AS_HARDRES] > TOL_P) break;            // over-determined working set
-                if (h->h_ascnt[AC_NVIOL] > 0) continue;
-                if (h->h_ascnt[AC_NREL] == 0) { okp = true; break; }
+                if (h->knobs.verbose) std::fprintf(stderr, "[asm] face primal bulk %d: nH %d nF %d viol %d rel %d hres %.2e\n", r, as_nH, as_nF, sk().h_ascnt[AC_NVIOL], sk().h_ascnt[AC_NREL], sk().h_asscal[AS_HARDRES]);
+                if (sk().h_asscal[AS_HARDRES] > TOL_P) break;            // over-determined working set
+                if (sk().h_ascnt[AC_NVIOL] > 0) continue;
+                if (sk().h_ascnt[AC_NREL] == 0) { okp = true; break; }
             }
             // ---- primal: anchored method in the null space of the partition (oracle: _face_primal_anchored) - one factorisation,
             // one solve with it per added constraint, the k x k matrix Z'Z of the added constraints on the host
@@ -2871,7 +2886,7 @@ struct Solver {
                 as_solve(S_[4], nullptr, nullptr, 1);
                 launch_face_primal_finish(S_[4], S_[3], TOL_P, FACE_TOL_M, 1);
                 as_read();
-                okp = h->h_asscal[AS_HARDRES] <= TOL_P && h->h_ascnt[AC_NVIOL] == 0;
+                okp = sk().h_asscal[AS_HARDRES] <= TOL_P && sk().h_ascnt[AC_NVIOL] == 0;
             }
         }
         part_factor = false;
@@ -2879,10 +2894,10 @@ struct Solver {
             dcopy(A.y, d_yf, M); dcopy(A.z, d_zf, n);      // (p, s, act) are the primal stage's last solve; y, z come from the dual stage
             launch_face_kkt(S_[5]);
             as_read();
-            h->stats.kkt_pr = h->h_asscal[AS_PR];
-            h->stats.kkt_du = h->h_asscal[AS_DU];
-            if (h->knobs.verbose) std::fprintf(stderr, "[asm] face kkt pr %.2e du %.2e\n", h->h_asscal[AS_PR], h->h_asscal[AS_DU]);
-            if (h->h_asscal[AS_PR] <= TOL_P && h->h_asscal[AS_DU] <= TOL_D) { final_sets = 4; return 2; }
+            h->stats.kkt_pr = sk().h_asscal[AS_PR];
+            h->stats.kkt_du = sk().h_asscal[AS_DU];
+            if (h->knobs.verbose) std::fprintf(stderr, "[asm] face kkt pr %.2e du %.2e\n", sk().h_asscal[AS_PR], sk().h_asscal[AS_DU]);
+            if (sk().h_asscal[AS_PR] <= TOL_P && sk().h_asscal[AS_DU] <= TOL_D) { final_sets = 4; return 2; }
         }
         dcopy(A.p, d_p0, n); dcopy(A.s, d_s0, ns); dcopy(A.y, d_y0, M); dcopy(A.act, d_act0, M); dcopy(A.z, d_z0, n);
         final_sets = 3;
@@ -2895,7 +2910,7 @@ struct Solver {
     bool phase1_infeasible() {
         SLP saved = lp;
         IpmState saved_ip = ip;
-        lp.ns = h->ns;
+        lp.ns = sk().ns;
         std::fill(lp.q.begin(), lp.q.end(), 0.0);
         lp.w.assign(lp.ns, 1.0);
         lp.slo.assign(lp.ns, 0.0);
@@ -3093,8 +3108,8 @@ struct Solver {
                 launch_as_smax(P.s, A.s);
                 launch_as_sl_values();      // the tail kernel must not recompute slacks from a stale working set
             }
-            dev.gemv_n_dev(h->d_Ah, A.p, A.t);
-            dev.gemv_t_dev(h->d_Ah, A.y, A.tN);
+            dev.gemv_n_dev(sk().d_Ah, A.p, A.t);
+            dev.gemv_t_dev(sk().d_Ah, A.y, A.tN);
             launch_as_finish(S_[3], S_[1], S_[2], 0, TOL_P, TOL_D);
             as_read();
             final_sets = 3;
@@ -3121,38 +3136,25 @@ int row_kind(double lb, double ub) {
     return 9;
 }
 
-// releases every buffer of the handle and resets the state that describes them
-void free_device(asm_handle* h) {
-    h->mem.release(); h->nsf.reset(); h->ev.reset();
-    h->nz_valid = false; h->nz_frac_cache[0] = h->nz_frac_cache[1] = -1.0;
-    h->ahTg_valid = false;
-    h->col_capable = h->ahT_valid = h->nzT_valid = false;
-    h->sp_ok = h->spv_Ah_valid = h->spv_J_valid = false; h->sp_nnz = 0;
-    h->test_fac = FacBuf();
-    h->row_band = 0; h->n_rowpairs = 0; h->row_perm_h.clear(); h->col_band = 0; h->n_colpairs = 0;
-}
-
 // the orthonormal basis of the previous LP is no longer resident (no form, or no k-sized buffers yet: nothing to forget)
-void ns_forget_basis(asm_handle* h) { if (h->nsf && h->nsf->k) h->nsf->k->Zk = 0; }
+void ns_forget_basis(Skeleton& K) { if (K.nsf && K.nsf->k) K.nsf->k->Zk = 0; }
 
 // forgets the retained working sets and adaptive hints of both phases and the resident null-space basis; keep_ns_J: the basis columns of
 // the null-space form stay
-void reset_warm(asm_handle* h, bool keep_ns_J) {
+void reset_warm(Skeleton& K, bool keep_ns_J) {
     std::vector<int> J;
-    if (keep_ns_J) J.swap(h->hint[0].ns_J);
-    h->warm[0] = ActiveSet(); h->warm[1] = ActiveSet();
-    h->hint[0] = SolveHint(); h->hint[1] = SolveHint();
-    h->hint[0].ns_J.swap(J);
-    ns_forget_basis(h);
-    h->hint[1].prefer_ref = true;     // restoration LPs usually have a non-unique optimum (oracle/subproblem.py)
+    if (keep_ns_J) J.swap(K.hint[0].ns_J);
+    K.warm[0] = ActiveSet(); K.warm[1] = ActiveSet();
+    K.hint[0] = SolveHint(false); K.hint[1] = SolveHint(true);
+    K.hint[0].ns_J.swap(J);
+    ns_forget_basis(K);
 }
 
 void check_panel_timeout(asm_handle* h) {
-    if (!h->d_ptmo) return;
     unsigned tmo = 0;
-    HIPCHK(asmb::copy(&tmo, h->d_ptmo, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCHK(asmb::copy(&tmo, h->sk->d_ptmo, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (tmo != 0) {
-        HIPCHK(asmb::fill(h->d_ptmo, 0, sizeof(unsigned)));      // reported once: the handle stays usable
+        HIPCHK(asmb::fill(h->sk->d_ptmo, 0, sizeof(unsigned)));      // reported once: the handle stays usable
         throw HipError("k_chol_panel: a workgroup timed out waiting for a producer (grid not resident?)");
     }
 }
@@ -3162,49 +3164,47 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     if (n <= 0 || m < 0 || nnz < 0 || (nnz > 0 && (!j_row || !j_col)) || (m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub)
         throw std::invalid_argument("asm_sublp_setup: bad dimensions or null pointer");
     HIPCHK(hipSetDevice(h->device));
-    free_device(h);
-    h->setup_done = false;
-    h->inputs_ready = false;
-    h->J_valid = false;
-    h->n = n; h->m = m; h->nnz = nnz;
-    h->j_row_h.assign(j_row, j_row + nnz); h->j_col_h.assign(j_col, j_col + nnz);
-    h->c_lb.assign(c_lb, c_lb + m); h->c_ub.assign(c_ub, c_ub + m);
-    h->v_lb.assign(v_lb, v_lb + n); h->v_ub.assign(v_ub, v_ub + n);
-    h->kind.resize(m);
-    h->adj.clear();
+    h->ev.reset(); h->sk.reset();   // released before anything is allocated; the new skeleton is built here and installed last: a failure leaves none
+    auto sk = std::make_unique<Skeleton>();
+    Skeleton& K = *sk;
+    K.n = n; K.m = m; K.nnz = nnz;
+    K.j_row_h.assign(j_row, j_row + nnz); K.j_col_h.assign(j_col, j_col + nnz);
+    K.c_lb.assign(c_lb, c_lb + m); K.c_ub.assign(c_ub, c_ub + m);
+    K.v_lb.assign(v_lb, v_lb + n); K.v_ub.assign(v_ub, v_ub + n);
+    K.kind.resize(m);
     for (int64_t i = 0; i < m; ++i) {
-        h->kind[i] = row_kind(c_lb[i], c_ub[i]);
-        if (h->kind[i] == 9) throw Unsupported("free constraint row (c_lb=-Inf, c_ub=+Inf) is not representable");
-        if (h->kind[i] == 2) h->adj.push_back(i);
+        K.kind[i] = row_kind(c_lb[i], c_ub[i]);
+        if (K.kind[i] == 9) throw Unsupported("free constraint row (c_lb=-Inf, c_ub=+Inf) is not representable");
+        if (K.kind[i] == 2) K.adj.push_back(i);
     }
-    h->nadj = (int64_t)h->adj.size();
-    h->M = m + h->nadj;
-    h->Mp = IpmLayout(n, h->M, 0).Mp;
-    h->ldn = IpmLayout(n, h->M, 0).ldn;    // multiple of the SYRK k-chunk (ASM_KC)
-    h->rtype.assign(h->M, 0);
-    for (int64_t i = 0; i < m; ++i) h->rtype[i] = h->kind[i] == 0 ? 0 : (h->kind[i] == -1 ? -1 : 1);
-    for (int64_t k = 0; k < h->nadj; ++k) h->rtype[m + k] = -1;
+    K.nadj = (int64_t)K.adj.size();
+    K.M = m + K.nadj;
+    K.Mp = IpmLayout(n, K.M, 0).Mp;
+    K.ldn = IpmLayout(n, K.M, 0).ldn;    // multiple of the SYRK k-chunk (ASM_KC)
+    K.rtype.assign(K.M, 0);
+    for (int64_t i = 0; i < m; ++i) K.rtype[i] = K.kind[i] == 0 ? 0 : (K.kind[i] == -1 ? -1 : 1);
+    for (int64_t k = 0; k < K.nadj; ++k) K.rtype[m + k] = -1;
     // slack layout (subproblem.jl:83-112): one per row, two when both bounds are finite
-    h->srow.clear(); h->scoef.clear(); h->sown.clear(); h->nslack.assign(m, 1);
+    K.nslack.assign(m, 1);
     std::vector<int64_t> adjpos(m, -1);
-    for (int64_t k = 0; k < h->nadj; ++k) adjpos[h->adj[k]] = k;
+    for (int64_t k = 0; k < K.nadj; ++k) adjpos[K.adj[k]] = k;
     for (int64_t i = 0; i < m; ++i) {
-        h->nslack[i] = (c_lb[i] > -INF && c_ub[i] < INF) ? 2 : 1;
-        int kd = h->kind[i];
-        if (kd == 0) { h->srow.push_back((int)i); h->scoef.push_back(1.0); h->srow.push_back((int)i); h->scoef.push_back(-1.0); h->sown.push_back(i); h->sown.push_back(i); }
-        else if (kd == 2) { h->srow.push_back((int)i); h->scoef.push_back(1.0); h->srow.push_back((int)(m + adjpos[i])); h->scoef.push_back(-1.0); h->sown.push_back(i); h->sown.push_back(i); }
-        else if (kd == 1) { h->srow.push_back((int)i); h->scoef.push_back(1.0); h->sown.push_back(i); }
-        else { h->srow.push_back((int)i); h->scoef.push_back(-1.0); h->sown.push_back(i); }
+        K.nslack[i] = (c_lb[i] > -INF && c_ub[i] < INF) ? 2 : 1;
+        int kd = K.kind[i];
+        if (kd == 0) { K.srow.push_back((int)i); K.scoef.push_back(1.0); K.srow.push_back((int)i); K.scoef.push_back(-1.0); K.sown.push_back(i); K.sown.push_back(i); }
+        else if (kd == 2) { K.srow.push_back((int)i); K.scoef.push_back(1.0); K.srow.push_back((int)(m + adjpos[i])); K.scoef.push_back(-1.0); K.sown.push_back(i); K.sown.push_back(i); }
+        else if (kd == 1) { K.srow.push_back((int)i); K.scoef.push_back(1.0); K.sown.push_back(i); }
+        else { K.srow.push_back((int)i); K.scoef.push_back(-1.0); K.sown.push_back(i); }
     }
-    h->ns = (int64_t)h->srow.size();
+    K.ns = (int64_t)K.srow.size();
 
     // assembly plan: stable sort of the COO entries by (row, col)
     for (int64_t k = 0; k < nnz; ++k)
         if (j_row[k] < 1 || j_row[k] > m || j_col[k] < 1 || j_col[k] > n) throw std::invalid_argument("j_row/j_col out of range (1-based)");
-    bool dense = (nnz == m * n) && h->nadj == 0 && nnz > 0;
+    bool dense = (nnz == m * n) && K.nadj == 0 && nnz > 0;
     if (dense)
         for (int64_t k = 0; k < nnz && dense; ++k) dense = (j_row[k] - 1) * n + (j_col[k] - 1) == k;
-    h->dense_fast = dense;
+    K.dense_fast = dense;
     std::vector<int64_t> perm(nnz), ustart, uoff, adjoff;
     std::iota(perm.begin(), perm.end(), 0);
     if (!dense) {
@@ -3218,14 +3218,14 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
             int64_t r = j_row[k] - 1, c = j_col[k] - 1, key = r * n + c;
             if (key != prev) {
                 ustart.push_back(t);
-                uoff.push_back(r * h->ldn + c);
-                adjoff.push_back(adjpos[r] >= 0 ? (m + adjpos[r]) * h->ldn + c : -1);
+                uoff.push_back(r * K.ldn + c);
+                adjoff.push_back(adjpos[r] >= 0 ? (m + adjpos[r]) * K.ldn + c : -1);
                 prev = key;
             }
         }
         ustart.push_back(nnz);
     }
-    h->nu = dense ? nnz : (int64_t)uoff.size();
+    K.nu = dense ? nnz : (int64_t)uoff.size();
     // sparse pattern (CSR + CSC) of the LP matrix rows [0, M): the unique Jacobian entries plus the copies of the range
     // rows; used by the matrix-vector products when the fill is below 1/16
     std::vector<int> sp_ptr, sp_col, sc_ptr, sc_row, sc_pos;
@@ -3234,107 +3234,105 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         int64_t nadjent = 0;
         for (int64_t v : adjoff) nadjent += v >= 0;
         const int64_t nnzS = (int64_t)uoff.size() + nadjent;
-        if (!dense && nnzS > 0 && nnzS * 16 <= h->M * n && nnzS < (int64_t)1 << 30) {
+        if (!dense && nnzS > 0 && nnzS * 16 <= K.M * n && nnzS < (int64_t)1 << 30) {
             sp_off.reserve(nnzS);
             for (int64_t v : uoff) sp_off.push_back(v);                 // sorted by (row, col), rows < m
             for (int64_t v : adjoff) if (v >= 0) sp_off.push_back(v);   // rows m.., same order
-            sp_ptr.assign(h->M + 1, 0);
+            sp_ptr.assign(K.M + 1, 0);
             sp_col.resize(nnzS);
             for (int64_t k = 0; k < nnzS; ++k) {
-                sp_ptr[sp_off[k] / h->ldn + 1] += 1;
-                sp_col[k] = (int)(sp_off[k] % h->ldn);
+                sp_ptr[sp_off[k] / K.ldn + 1] += 1;
+                sp_col[k] = (int)(sp_off[k] % K.ldn);
             }
-            for (int64_t i = 0; i < h->M; ++i) sp_ptr[i + 1] += sp_ptr[i];
+            for (int64_t i = 0; i < K.M; ++i) sp_ptr[i + 1] += sp_ptr[i];
             csc_from_csr(sp_ptr, sp_col, n, sc_ptr, sc_row, sc_pos);
-            h->sp_nnz = nnzS;
+            K.sp_nnz = nnzS;
         }
     }
 
-    BufPool& P = h->mem;
+    BufPool& P = K.mem;
     const hipStream_t s = h->stream;
-    P.alloc(h->d_dE, nnz);
-    P.zeroed(h->d_J, h->Mp * h->ldn, s);
-    P.zeroed(h->d_Ah, h->Mp * h->ldn, s);
-    FacBuf& F = h->main_fac;
-    F.ld = h->Mp;
-    P.alloc(F.S, h->Mp * h->Mp);
-    P.alloc(h->d_c, h->ldn); P.alloc(h->d_rho, h->Mp); P.alloc(h->d_theta, h->ldn);
-    P.alloc(h->d_diag, h->Mp); P.alloc(h->d_diag0, h->Mp);
-    P.zeroed(h->d_vecN, h->ldn, s); P.zeroed(h->d_vecM, h->Mp, s); P.alloc(h->d_vecM2, h->Mp);
-    P.alloc(h->d_partial, (int64_t)ASM_TMAXCHUNKS * h->ldn);
-    P.alloc(h->d_idx, h->Mp);
-    P.alloc(F.Linv, (h->Mp / ASM_NB + 1) * ASM_NB * ASM_NB);
-    P.zeroed(h->d_pflags, ASM_PNL_FLAGS, s);
-    P.zeroed(h->d_ptmo, 4, s);
-    F.wb = h->M > 1536 ? 1024 : 512;      // wide-block width of the triangular solves (k_wtrsv_*<WB>)
-    if (h->M >= RED_MIN_M) {
-        P.alloc(h->d_idxI, h->Mp); P.alloc(h->d_rdI, h->Mp); P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); P.alloc(h->d_sdiag, h->Mp);
+    P.alloc(K.d_dE, nnz);
+    P.zeroed(K.d_J, K.Mp * K.ldn, s);
+    P.zeroed(K.d_Ah, K.Mp * K.ldn, s);
+    FacBuf& F = K.main_fac;
+    F.ld = K.Mp;
+    P.alloc(F.S, K.Mp * K.Mp);
+    P.alloc(K.d_c, K.ldn); P.alloc(K.d_rho, K.Mp); P.alloc(K.d_theta, K.ldn);
+    P.alloc(K.d_diag, K.Mp); P.alloc(K.d_diag0, K.Mp);
+    P.zeroed(K.d_vecN, K.ldn, s); P.zeroed(K.d_vecM, K.Mp, s); P.alloc(K.d_vecM2, K.Mp);
+    P.alloc(K.d_partial, (int64_t)ASM_TMAXCHUNKS * K.ldn);
+    P.alloc(K.d_idx, K.Mp);
+    P.alloc(F.Linv, (K.Mp / ASM_NB + 1) * ASM_NB * ASM_NB);
+    P.zeroed(K.d_pflags, ASM_PNL_FLAGS, s);
+    P.zeroed(K.d_ptmo, 4, s);
+    F.wb = K.M > 1536 ? 1024 : 512;      // wide-block width of the triangular solves (k_wtrsv_*<WB>)
+    if (K.M >= RED_MIN_M) {
+        P.alloc(K.d_idxI, K.Mp); P.alloc(K.d_rdI, K.Mp); P.alloc(K.d_rce, K.Mp); P.alloc(K.d_rze, K.Mp); P.alloc(K.d_sdiag, K.Mp);
     }
     // column form of the restoration-phase Newton system (every row owns a slack column there): n x n instead of M x M
-    h->col_capable = h->M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)h->M && n <= h->Mp;
-    if (h->col_capable) {
-        h->ldT = round_up(h->M, 32);
-        P.zeroed(h->d_AhT, n * h->ldT, s);
-        P.zeroed(h->d_cdinv, h->ldT, s); P.zeroed(h->d_cth, h->ldn, s); P.zeroed(h->d_cu, h->Mp, s); P.zeroed(h->d_ct, h->ldn, s);
-        P.zeroed(h->d_cv, h->ldn, s); P.zeroed(h->d_cw, h->Mp, s);
-        P.alloc(h->d_nzT, (n / 32 + 2) * (h->ldT / ASM_KC + 1));
+    K.col_capable = K.M >= COL_MIN_M && (double)n <= COL_MAX_RATIO * (double)K.M && n <= K.Mp;
+    if (K.col_capable) {
+        K.ldT = round_up(K.M, 32);
+        P.zeroed(K.d_AhT, n * K.ldT, s);
+        P.zeroed(K.d_cdinv, K.ldT, s); P.zeroed(K.d_cth, K.ldn, s); P.zeroed(K.d_cu, K.Mp, s); P.zeroed(K.d_ct, K.ldn, s);
+        P.zeroed(K.d_cv, K.ldn, s); P.zeroed(K.d_cw, K.Mp, s);
+        P.alloc(K.d_nzT, (n / 32 + 2) * (K.ldT / ASM_KC + 1));
     }
-    P.alloc(F.Binv, (h->Mp / F.wb + 1) * (int64_t)F.wb * F.wb);
-    P.alloc(F.BinvT, (h->Mp / F.wb + 1) * (int64_t)F.wb * F.wb);
-    P.alloc(h->d_wpart, (h->Mp / ASM_WBROWS + 2) * (int64_t)1024);
-    P.alloc(h->d_wt, 1024);
-    h->nz_half = (h->Mp / 32 + 1) * (h->ldn / ASM_KC + 1);
-    P.alloc(h->d_nz, 2 * h->nz_half);
-    if (h->sp_nnz > 0) {
-        P.upload(h->d_sp_ptr, sp_ptr.data(), h->M + 1); P.upload(h->d_sp_col, sp_col.data(), h->sp_nnz); P.upload(h->d_sp_off, sp_off.data(), h->sp_nnz);
-        P.upload(h->d_sc_ptr, sc_ptr.data(), n + 1); P.upload(h->d_sc_row, sc_row.data(), h->sp_nnz); P.upload(h->d_sc_pos, sc_pos.data(), h->sp_nnz);
-        P.alloc(h->d_spv_Ah, h->sp_nnz); P.alloc(h->d_spv_J, h->sp_nnz);
-        h->sp_ok = true;
+    P.alloc(F.Binv, (K.Mp / F.wb + 1) * (int64_t)F.wb * F.wb);
+    P.alloc(F.BinvT, (K.Mp / F.wb + 1) * (int64_t)F.wb * F.wb);
+    P.alloc(K.d_wpart, (K.Mp / ASM_WBROWS + 2) * (int64_t)1024);
+    P.alloc(K.d_wt, 1024);
+    K.nz_half = (K.Mp / 32 + 1) * (K.ldn / ASM_KC + 1);
+    P.alloc(K.d_nz, 2 * K.nz_half);
+    if (K.sp_nnz > 0) {
+        P.upload(K.d_sp_ptr, sp_ptr.data(), K.M + 1); P.upload(K.d_sp_col, sp_col.data(), K.sp_nnz); P.upload(K.d_sp_off, sp_off.data(), K.sp_nnz);
+        P.upload(K.d_sc_ptr, sc_ptr.data(), n + 1); P.upload(K.d_sc_row, sc_row.data(), K.sp_nnz); P.upload(K.d_sc_pos, sc_pos.data(), K.sp_nnz);
+        P.alloc(K.d_spv_Ah, K.sp_nnz); P.alloc(K.d_spv_J, K.sp_nnz);
+        K.sp_ok = true;
     }
-    const IpmLayout lay(n, h->M, h->ns);
-    h->nsp = lay.nsp;
+    const IpmLayout lay(n, K.M, K.ns);
+    K.nsp = lay.nsp;
     {
-        P.zeroed(h->d_ipm, lay.arena_len(), s);
-        P.alloc(h->d_ipm_snap, lay.snap_len());
+        P.zeroed(K.d_ipm, lay.arena_len(), s);
+        P.alloc(K.d_ipm_snap, lay.snap_len());
         std::vector<int> iv(lay.int_len(), -1);
-        for (int64_t i = 0; i < h->M; ++i) iv[i] = h->rtype[i];
-        for (int64_t k = 0; k < h->ns; ++k) {
-            int r_ = h->srow[k];
-            if (iv[h->Mp + r_] < 0) iv[h->Mp + r_] = (int)k; else iv[2 * h->Mp + r_] = (int)k;
-            iv[3 * h->Mp + k] = r_;
+        for (int64_t i = 0; i < K.M; ++i) iv[i] = K.rtype[i];
+        for (int64_t k = 0; k < K.ns; ++k) {
+            int r_ = K.srow[k];
+            if (iv[K.Mp + r_] < 0) iv[K.Mp + r_] = (int)k; else iv[2 * K.Mp + r_] = (int)k;
+            iv[3 * K.Mp + k] = r_;
         }
-        P.upload(h->d_ipm_i, iv.data(), (int64_t)iv.size());
-        P.alloc(h->d_redpart, IPM_RED_MAXWG * IPM_RED_SLOTS);
-        P.zeroed(h->d_redcnt, 4, s);
-        P.alloc(h->h_scal, 64, BufPool::MAPPED, &h->d_hscal);
-        P.alloc(h->h_seq, 16, BufPool::MAPPED, &h->d_hseq);
-        *h->h_seq = 0;
-        h->scal_seq = 0;
-        const AsLayout alay(h->ldn, h->Mp, h->nsp);
-        P.zeroed(h->d_as, alay.dbl_len(), s);
-        P.zeroed(h->d_as_i, alay.int_len(), s);
-        P.alloc(h->h_ascnt, 64, BufPool::PINNED);
-        P.alloc(h->h_asscal, 64, BufPool::PINNED);
-        P.zeroed(h->d_Zbuf, (int64_t)(FACE_STEPS + 1) * h->ldn, s);
-        P.alloc(h->d_nsu, FACE_STEPS + 8);
-        P.alloc(h->d_nsdots, FACE_STEPS + 8);
-        P.alloc(h->h_nsdots, FACE_STEPS + 8, BufPool::PINNED);
+        P.upload(K.d_ipm_i, iv.data(), (int64_t)iv.size());
+        P.alloc(K.d_redpart, IPM_RED_MAXWG * IPM_RED_SLOTS);
+        P.zeroed(K.d_redcnt, 4, s);
+        P.alloc(K.h_scal, 64, BufPool::MAPPED, &K.d_hscal);
+        P.alloc(K.h_seq, 16, BufPool::MAPPED, &K.d_hseq);
+        *K.h_seq = 0;
+        const AsLayout alay(K.ldn, K.Mp, K.nsp);
+        P.zeroed(K.d_as, alay.dbl_len(), s);
+        P.zeroed(K.d_as_i, alay.int_len(), s);
+        P.alloc(K.h_ascnt, 64, BufPool::PINNED);
+        P.alloc(K.h_asscal, 64, BufPool::PINNED);
+        P.zeroed(K.d_Zbuf, (int64_t)(FACE_STEPS + 1) * K.ldn, s);
+        P.alloc(K.d_nsu, FACE_STEPS + 8);
+        P.alloc(K.d_nsdots, FACE_STEPS + 8);
+        P.alloc(K.h_nsdots, FACE_STEPS + 8, BufPool::PINNED);
     }
-    // null-space form of the normal-phase Newton system: static part (index lists, factor of S0, work vectors), installed when the whole set-up
-    // is complete; the buffers sized by the null-space dimension k are allocated by the first LP that uses the form (Solver::ns_reserve)
-    std::unique_ptr<NsForm> nsf;
+    // null-space form of the normal-phase Newton system: static part (index lists, factor of S0, work vectors); the buffers sized by the
+    // null-space dimension k are allocated by the first LP that uses the form (Solver::ns_reserve)
     {
         int nE = 0;
-        for (int64_t i = 0; i < h->M; ++i) nE += h->rtype[i] == 0;
-        if (h->sp_ok && nE >= NS_MIN_E && (double)(n - nE) <= NS_MAX_RATIO * (double)h->M && n <= h->Mp && h->M < (int64_t)1 << 30) {
-            nsf = std::make_unique<NsForm>(NsLayout(h->ldn, h->Mp, nE, h->M - nE));
-            NsForm& F = *nsf;
+        for (int64_t i = 0; i < K.M; ++i) nE += K.rtype[i] == 0;
+        if (K.sp_ok && nE >= NS_MIN_E && (double)(n - nE) <= NS_MAX_RATIO * (double)K.M && n <= K.Mp && K.M < (int64_t)1 << 30) {
+            K.nsf = std::make_unique<NsForm>(NsLayout(K.ldn, K.Mp, nE, K.M - nE));
+            NsForm& F = *K.nsf;
             BufPool& Q = F.mem;
             std::vector<int> epos, iidx, ipos, s0_pairs;
             int s0_band = 0;
-            ns_index_lists(h->rtype.data(), h->M, sp_ptr, sp_col, h->ldn, F.eidx_h, epos, iidx, ipos, &s0_band, &s0_pairs);
-            Q.upload(F.Eidx, F.eidx_h.data(), nE, true); Q.upload(F.Epos, epos.data(), h->M, true);
-            Q.upload(F.Iidx, iidx.data(), F.L.nI, true); Q.upload(F.Ipos, ipos.data(), h->M, true);
+            ns_index_lists(K.rtype.data(), K.M, sp_ptr, sp_col, K.ldn, F.eidx_h, epos, iidx, ipos, &s0_band, &s0_pairs);
+            Q.upload(F.Eidx, F.eidx_h.data(), nE, true); Q.upload(F.Epos, epos.data(), K.M, true);
+            Q.upload(F.Iidx, iidx.data(), F.L.nI, true); Q.upload(F.Ipos, ipos.data(), K.M, true);
             Q.zeroed(F.cnt, 16);
             const int f0_band = 2 * (int64_t)s0_band >= nE ? 0 : std::max(s0_band, 1);
             ns_alloc_factor(h, Q, F.f0, F.L.nEp, f0_band);
@@ -3345,103 +3343,99 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
             }
             Q.zeroed(F.Lt, F.L.nEp * F.L.nEp, s);
             Q.zeroed(F.th, F.L.th_len(), s);
-            Q.zeroed(F.Fm, h->ldn, s);
+            Q.zeroed(F.Fm, K.ldn, s);
             Q.zeroed(F.v, F.L.nsv_len(), s);
         }
     }
-    // row order of the factorisations (see asm_handle::row_band)
-    h->main_fac.band = 0;
-    if (h->sp_ok && h->M >= 256) {
-        std::vector<int> all(h->M), pairs_pos;
-        for (int64_t i = 0; i < h->M; ++i) all[i] = (int)i;
+    // row order of the factorisations (see Skeleton::row_band)
+    if (K.sp_ok && K.M >= 256) {
+        std::vector<int> all(K.M), pairs_pos;
+        for (int64_t i = 0; i < K.M; ++i) all[i] = (int)i;
         int bw = 0;
-        const std::vector<int> ord = rcm_order(all, sp_ptr, sp_col, h->ldn, &bw, &pairs_pos);
-        if (2 * (int64_t)bw < h->M) {
-            h->row_band = std::max(bw, 1);
-            h->row_perm_h = ord;
-            std::vector<int> pos(h->M), pairs(pairs_pos.size());
-            for (int64_t q = 0; q < h->M; ++q) pos[ord[q]] = (int)q;
+        const std::vector<int> ord = rcm_order(all, sp_ptr, sp_col, K.ldn, &bw, &pairs_pos);
+        if (2 * (int64_t)bw < K.M) {
+            K.row_band = std::max(bw, 1);
+            K.row_perm_h = ord;
+            std::vector<int> pos(K.M), pairs(pairs_pos.size());
+            for (int64_t q = 0; q < K.M; ++q) pos[ord[q]] = (int)q;
             for (size_t t = 0; t < pairs_pos.size(); ++t) pairs[t] = ord[pairs_pos[t]];
-            h->n_rowpairs = (int64_t)pairs.size() / 2;
-            P.upload(h->d_rowperm, ord.data(), h->M); P.upload(h->d_rowpos, pos.data(), h->M); P.upload(h->d_rowpairs, pairs.data(), (int64_t)pairs.size());
-            P.upload(h->d_cpos, pos.data(), h->M);      // place of every row in the current row list of the interior-point factor (rewritten per iteration)
-            if (!h->d_rce) { P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); }
+            K.n_rowpairs = (int64_t)pairs.size() / 2;
+            P.upload(K.d_rowperm, ord.data(), K.M); P.upload(K.d_rowpos, pos.data(), K.M); P.upload(K.d_rowpairs, pairs.data(), (int64_t)pairs.size());
+            P.upload(K.d_cpos, pos.data(), K.M);      // place of every row in the current row list of the interior-point factor (rewritten per iteration)
+            if (!K.d_rce) { P.alloc(K.d_rce, K.Mp); P.alloc(K.d_rze, K.Mp); }
         }
     }
     // column order of the column form (K = Th + A' D^-1 A couples two columns when they share a row)
-    if (h->sp_ok && h->col_capable && n >= 256) {
+    if (K.sp_ok && K.col_capable && n >= 256) {
         std::vector<int> all(n), pairs_pos;
         for (int64_t j = 0; j < n; ++j) all[j] = (int)j;
         int bw = 0;
-        const std::vector<int> ord = rcm_order(all, sc_ptr, sc_row, h->Mp, &bw, &pairs_pos);
+        const std::vector<int> ord = rcm_order(all, sc_ptr, sc_row, K.Mp, &bw, &pairs_pos);
         if (2 * (int64_t)bw < n) {
-            h->col_band = std::max(bw, 1);
+            K.col_band = std::max(bw, 1);
             std::vector<int> pos(n), pairs(pairs_pos.size());
             for (int64_t q = 0; q < n; ++q) pos[ord[q]] = (int)q;
             for (size_t t = 0; t < pairs_pos.size(); ++t) pairs[t] = ord[pairs_pos[t]];
-            h->n_colpairs = (int64_t)pairs.size() / 2;
-            P.upload(h->d_colperm, ord.data(), n); P.upload(h->d_colpos, pos.data(), n); P.upload(h->d_colpairs, pairs.data(), (int64_t)pairs.size());
-            if (!h->d_rce) { P.alloc(h->d_rce, h->Mp); P.alloc(h->d_rze, h->Mp); }
+            K.n_colpairs = (int64_t)pairs.size() / 2;
+            P.upload(K.d_colperm, ord.data(), n); P.upload(K.d_colpos, pos.data(), n); P.upload(K.d_colpairs, pairs.data(), (int64_t)pairs.size());
+            if (!K.d_rce) { P.alloc(K.d_rce, K.Mp); P.alloc(K.d_rze, K.Mp); }
         }
     }
-    h->pin_len = std::max(std::max(h->ldn, h->Mp), h->nsp);
-    P.alloc(h->h_pin, 2 * h->pin_len, BufPool::PINNED);
-    P.alloc(h->h_up, 3 * h->ldn + h->Mp + 3 * h->nsp + 16, BufPool::PINNED);
-    std::memset(h->h_up, 0, (3 * h->ldn + h->Mp + 3 * h->nsp + 16) * sizeof(double));
+    K.pin_len = std::max(std::max(K.ldn, K.Mp), K.nsp);
+    P.alloc(K.h_pin, 2 * K.pin_len, BufPool::PINNED);
+    P.alloc(K.h_up, 3 * K.ldn + K.Mp + 3 * K.nsp + 16, BufPool::PINNED);
+    std::memset(K.h_up, 0, (3 * K.ldn + K.Mp + 3 * K.nsp + 16) * sizeof(double));
     {
-        const int64_t dl = 2 * h->ldn + 2 * h->Mp + h->nsp + (h->ldn + h->Mp + h->nsp + 1) / 2 + 16;
-        P.alloc(h->d_dl, dl);
-        P.alloc(h->h_dl, dl, BufPool::PINNED);
+        const int64_t dl = 2 * K.ldn + 2 * K.Mp + K.nsp + (K.ldn + K.Mp + K.nsp + 1) / 2 + 16;
+        P.alloc(K.d_dl, dl);
+        P.alloc(K.h_dl, dl, BufPool::PINNED);
     }
     if (!dense) {
-        P.upload(h->d_perm, perm.data(), nnz); P.upload(h->d_ustart, ustart.data(), h->nu + 1);
-        P.upload(h->d_uoff, uoff.data(), h->nu); P.upload(h->d_adjoff, adjoff.data(), h->nu);
+        P.upload(K.d_perm, perm.data(), nnz); P.upload(K.d_ustart, ustart.data(), K.nu + 1);
+        P.upload(K.d_uoff, uoff.data(), K.nu); P.upload(K.d_adjoff, adjoff.data(), K.nu);
     }
     HIPCHK(asmb::sync(h->stream));
-    h->nsf = std::move(nsf);
-    h->last = ActiveSet();
-    reset_warm(h, false);
     std::memset(&h->stats, 0, sizeof(h->stats));
-    h->setup_done = true;
+    h->sk = std::move(sk);
 }
 
 void do_upload(asm_handle* h, const double* dE, const double* df, double f, const double* E, const double* x_k) {
-    if ((h->nnz > 0 && !dE) || !df || (h->m > 0 && !E) || !x_k) throw std::invalid_argument("asm_sublp_upload: null pointer");
-    if (!h->setup_done) throw std::logic_error("asm_sublp_setup has not been called");
+    Skeleton& K = sk_of(h, "asm_sublp_setup has not been called");
+    if ((K.nnz > 0 && !dE) || !df || (K.m > 0 && !E) || !x_k) throw std::invalid_argument("asm_sublp_upload: null pointer");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(asmb::copy_async(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(K.d_dE, dE, K.nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h2d_done(h);
-    h->J_valid = false;
-    h->df.assign(df, df + h->n); h->E.assign(E, E + h->m); h->x_k.assign(x_k, x_k + h->n);
-    h->f = f;
-    h->inputs_ready = true;
-    h->inputs_from_eval = false;
+    K.J_valid = false;
+    K.df.assign(df, df + K.n); K.E.assign(E, E + K.m); K.x_k.assign(x_k, x_k + K.n);
+    K.f = f;
+    K.inputs_ready = true;
+    K.inputs_from_eval = false;
 }
 
 void do_set_bounds(asm_handle* h, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub) {
-    if (!h->setup_done) throw std::logic_error("asm_sublp_set_bounds: asm_sublp_setup first");
-    if ((h->m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub) throw std::invalid_argument("asm_sublp_set_bounds: null pointer");
-    for (int64_t i = 0; i < h->m; ++i)
-        if (row_kind(c_lb[i], c_ub[i]) != h->kind[i])
+    Skeleton& K = sk_of(h, "asm_sublp_set_bounds: asm_sublp_setup first");
+    if ((K.m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub) throw std::invalid_argument("asm_sublp_set_bounds: null pointer");
+    for (int64_t i = 0; i < K.m; ++i)
+        if (row_kind(c_lb[i], c_ub[i]) != K.kind[i])
             throw Unsupported("asm_sublp_set_bounds: the kind of a row changes - the LP skeleton is not representable (call asm_sublp_setup)");
     HIPCHK(hipSetDevice(h->device));
-    h->c_lb.assign(c_lb, c_lb + h->m); h->c_ub.assign(c_ub, c_ub + h->m);
-    h->v_lb.assign(v_lb, v_lb + h->n); h->v_ub.assign(v_ub, v_ub + h->n);
+    K.c_lb.assign(c_lb, c_lb + K.m); K.c_ub.assign(c_ub, c_ub + K.m);
+    K.v_lb.assign(v_lb, v_lb + K.n); K.v_ub.assign(v_ub, v_ub + K.n);
     if (h->ev) ev_write_bounds(h, h->ev->L);
     // the retained working sets and the basis Z belong to the old instance; the basis COLUMNS of the null-space form are kept - the
     // pattern is the same, and a set that no longer spans null(A_EF) is detected and re-selected by the next LP (Solver::ns_setup)
-    h->last = ActiveSet();
-    reset_warm(h, true);
-    h->inputs_ready = false;
+    K.last = ActiveSet();
+    reset_warm(K, true);
+    K.inputs_ready = false;
 }
 
 void do_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
     if (k < 0 || (k > 0 && !J)) throw std::invalid_argument("asm_sublp_set_ns_basis: bad argument");
-    if (!h->setup_done) throw std::logic_error("asm_sublp_set_ns_basis: asm_sublp_setup first");
+    Skeleton& K = sk_of(h, "asm_sublp_set_ns_basis: asm_sublp_setup first");
     for (int64_t a = 0; a < k; ++a)
-        if (J[a] < 0 || J[a] >= h->n) throw std::invalid_argument("asm_sublp_set_ns_basis: column out of range");
-    h->hint[0].ns_J.assign(J, J + k);
-    ns_forget_basis(h);
+        if (J[a] < 0 || J[a] >= K.n) throw std::invalid_argument("asm_sublp_set_ns_basis: column out of range");
+    K.hint[0].ns_J.assign(J, J + k);
+    ns_forget_basis(K);
 }
 
 // the LP in caller units: min q'p + w's  s.t.  J_i p + E s (=,>=,<=) r_i (rows m.. = the extra `<=` rows of range constraints),
@@ -3458,12 +3452,13 @@ struct LpSol {
 
 // assemble J from the dE in HBM, scale, solve, unscale (oracle: solve_lp).  `slot`: which retained active set / hints to use.
 void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
-    const int64_t n = h->n, M = h->M;
+    Skeleton& K = *h->sk;
+    const int64_t n = K.n, M = K.M;
     Solver sv(h);
     SLP& lp = sv.lp;
     std::memset(&h->stats, 0, sizeof(h->stats));
-    lp.n = n; lp.M = M; lp.ns = L.slacks ? h->ns : 0;
-    lp.rtype = h->rtype.data(); lp.srow = h->srow.data(); lp.scoef = h->scoef.data();
+    lp.n = n; lp.M = M; lp.ns = L.slacks ? K.ns : 0;
+    lp.rtype = K.rtype.data(); lp.srow = K.srow.data(); lp.scoef = K.scoef.data();
     h->stats.M = (int)M; h->stats.n = (int)n; h->stats.ns = (int)lp.ns;
     // Jacobian -> dense rows incl. range rows; scaled copy (column scale = min(box, matrix cap), oracle: scale_lp)
     vec c(n), rel(n);
@@ -3493,10 +3488,10 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
     lp.q.resize(n); lp.lb.resize(n); lp.ub.resize(n); lp.r.resize(M); lp.w.resize(lp.ns); lp.slo.resize(lp.ns);
     double qmax = 0.0;
     for (int64_t j = 0; j < n; ++j) { lp.q[j] = L.q[j] * c[j]; qmax = std::max(qmax, std::fabs(lp.q[j])); }
-    for (int64_t k = 0; k < lp.ns; ++k) { lp.w[k] = L.w[k] * rho[h->srow[k]]; qmax = std::max(qmax, std::fabs(lp.w[k])); }
+    for (int64_t k = 0; k < lp.ns; ++k) { lp.w[k] = L.w[k] * rho[K.srow[k]]; qmax = std::max(qmax, std::fabs(lp.w[k])); }
     double kap = pow2_round(qmax);
     for (int64_t j = 0; j < n; ++j) { lp.q[j] /= kap; lp.lb[j] = L.lb[j] / c[j]; lp.ub[j] = L.ub[j] / c[j]; }
-    for (int64_t k = 0; k < lp.ns; ++k) { lp.w[k] /= kap; lp.slo[k] = L.slo[k] / rho[h->srow[k]]; }
+    for (int64_t k = 0; k < lp.ns; ++k) { lp.w[k] /= kap; lp.slo[k] = L.slo[k] / rho[K.srow[k]]; }
     for (int64_t i = 0; i < M; ++i) lp.r[i] = L.r[i] / rho[i];
     lp.scale_q = 1.0;
     for (double v : lp.q) lp.scale_q = std::max(lp.scale_q, std::fabs(v));
@@ -3504,15 +3499,15 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
 
     Solver::EqpOut o;
     lap("host-lp");
-    out.status = sv.solve_scaled(&h->warm[slot], h->hint[slot]);
+    out.status = sv.solve_scaled(&K.warm[slot], K.hint[slot]);
     lap("solve");
     asmb::barrier(900);
     if (out.status == ASM_OPTIMAL) {
         sv.as_download(o, out.as);
-        const ActiveSet& prev = h->warm[slot];
-        h->hint[slot].stable = prev.valid && prev.rowst == out.as.rowst && prev.bst == out.as.bst && prev.sst == out.as.sst;
-        h->warm[slot] = out.as;
-        h->last = out.as;
+        const ActiveSet& prev = K.warm[slot];
+        K.hint[slot].stable = prev.valid && prev.rowst == out.as.rowst && prev.bst == out.as.bst && prev.sst == out.as.sst;
+        K.warm[slot] = out.as;
+        K.last = out.as;
         // unscale - bound-active components are exactly on their bound
         out.p.resize(n); out.z.resize(n); out.y.resize(M); out.s.resize(lp.ns);
         for (int64_t j = 0; j < n; ++j) {
@@ -3526,13 +3521,13 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
         for (int64_t i = 0; i < M; ++i) {
             double yi = o.y[i] * kap / rho[i];
             // multipliers with the sign their row type admits (a simplex code returns sign-feasible duals)
-            if (h->rtype[i] == 1) yi = std::max(yi, 0.0);
-            else if (h->rtype[i] == -1) yi = std::min(yi, 0.0);
+            if (K.rtype[i] == 1) yi = std::max(yi, 0.0);
+            else if (K.rtype[i] == -1) yi = std::min(yi, 0.0);
             out.y[i] = yi;
         }
-        for (int64_t k = 0; k < lp.ns; ++k) out.s[k] = o.s[k] * rho[h->srow[k]];
+        for (int64_t k = 0; k < lp.ns; ++k) out.s[k] = o.s[k] * rho[K.srow[k]];
     } else {
-        h->last = ActiveSet();
+        K.last = ActiveSet();
     }
     lap("extract");
     sv.dev.resolve_timing();
@@ -3543,31 +3538,32 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
 
 void do_solve(asm_handle* h, double delta, int feasibility, double* p_out, double* lambda, double* mult_x_U, double* mult_x_L,
               double* p_slack, int32_t* status) {
-    if (!p_out || (h->m > 0 && (!lambda || !p_slack)) || !mult_x_U || !mult_x_L || !status) throw std::invalid_argument("asm_sublp_solve: null output pointer");
+    const Skeleton& K = sk_of(h, "inputs have not been uploaded");
+    if (!p_out || (K.m > 0 && (!lambda || !p_slack)) || !mult_x_U || !mult_x_L || !status) throw std::invalid_argument("asm_sublp_solve: null output pointer");
     if (!(delta >= 0.0)) throw std::invalid_argument("asm_sublp_solve: delta must be >= 0");
-    if (!h->setup_done || !h->inputs_ready) throw std::logic_error("inputs have not been uploaded");
+    if (!K.inputs_ready) throw std::logic_error("inputs have not been uploaded");
     HIPCHK(hipSetDevice(h->device));
     auto t0 = std::chrono::steady_clock::now();
-    const int64_t n = h->n, m = h->m, M = h->M;
+    const int64_t n = K.n, m = K.m, M = K.M;
     const bool fr = feasibility != 0;
     LpRaw L;
     L.slacks = fr;
     // trust region intersected with the variable bounds (subproblem.jl:427-434)
     L.lb.resize(n); L.ub.resize(n);
     for (int64_t j = 0; j < n; ++j) {
-        L.ub[j] = std::min(delta, h->v_ub[j] - h->x_k[j]);
-        L.lb[j] = std::max(-delta, h->v_lb[j] - h->x_k[j]);
+        L.ub[j] = std::min(delta, K.v_ub[j] - K.x_k[j]);
+        L.lb[j] = std::max(-delta, K.v_lb[j] - K.x_k[j]);
     }
     // feasibility-restoration shift (subproblem.jl:287-295) and slack lower bounds (:298-381)
-    vec b(h->E);
+    vec b(K.E);
     if (fr) {
-        L.slo.reserve(h->ns);
+        L.slo.reserve(K.ns);
         for (int64_t i = 0; i < m; ++i) {
             double v = 0.0;
-            if (h->E[i] > h->c_ub[i]) v = h->c_ub[i] - h->E[i];
-            else if (h->E[i] < h->c_lb[i]) v = h->c_lb[i] - h->E[i];
+            if (K.E[i] > K.c_ub[i]) v = K.c_ub[i] - K.E[i];
+            else if (K.E[i] < K.c_lb[i]) v = K.c_lb[i] - K.E[i];
             b[i] -= std::fabs(v);
-            if (h->nslack[i] == 2) {
+            if (K.nslack[i] == 2) {
                 if (v < 0) { L.slo.push_back(0.0); L.slo.push_back(v); }
                 else { L.slo.push_back(-v); L.slo.push_back(0.0); }
             } else {
@@ -3577,34 +3573,34 @@ void do_solve(asm_handle* h, double delta, int feasibility, double* p_out, doubl
     }
     // right-hand sides (subproblem.jl:461-484)
     L.r.resize(M);
-    for (int64_t i = 0; i < m; ++i) L.r[i] = h->kind[i] == -1 ? h->c_ub[i] - b[i] : h->c_lb[i] - b[i];
-    for (int64_t k = 0; k < h->nadj; ++k) L.r[m + k] = h->c_ub[h->adj[k]] - b[h->adj[k]];
+    for (int64_t i = 0; i < m; ++i) L.r[i] = K.kind[i] == -1 ? K.c_ub[i] - b[i] : K.c_lb[i] - b[i];
+    for (int64_t k = 0; k < K.nadj; ++k) L.r[m + k] = K.c_ub[K.adj[k]] - b[K.adj[k]];
     // objective (subproblem.jl:250-272 | 384-405)
     L.q.assign(n, 0.0);
-    L.w.assign(fr ? h->ns : 0, 1.0);
-    if (!fr) L.q = h->df;
+    L.w.assign(fr ? K.ns : 0, 1.0);
+    if (!fr) L.q = K.df;
 
     LpSol sol;
     solve_raw(h, L, fr ? 1 : 0, sol);
     *status = sol.status;
     for (int64_t j = 0; j < n; ++j) { p_out[j] = 0.0; mult_x_U[j] = 0.0; mult_x_L[j] = 0.0; }
-    for (int64_t i = 0; i < m; ++i) { lambda[i] = 0.0; p_slack[2 * i] = 0.0; p_slack[2 * i + 1] = h->nslack[i] == 2 ? 0.0 : std::nan(""); }
+    for (int64_t i = 0; i < m; ++i) { lambda[i] = 0.0; p_slack[2 * i] = 0.0; p_slack[2 * i + 1] = K.nslack[i] == 2 ? 0.0 : std::nan(""); }
     if (sol.status == ASM_OPTIMAL) {
         for (int64_t j = 0; j < n; ++j) p_out[j] = sol.p[j];                                    // subproblem.jl:502
         if (fr) {
             int64_t k = 0;
             for (int64_t i = 0; i < m; ++i)
-                for (int t = 0; t < h->nslack[i]; ++t, ++k) p_slack[2 * i + t] = sol.s[k];       // :503-505
+                for (int t = 0; t < K.nslack[i]; ++t, ++k) p_slack[2 * i + t] = sol.s[k];       // :503-505
         }
         for (int64_t i = 0; i < m; ++i) lambda[i] = sol.y[i];                                   // :510-512
-        for (int64_t k = 0; k < h->nadj; ++k) lambda[h->adj[k]] += sol.y[m + k];                // :513-515
+        for (int64_t k = 0; k < K.nadj; ++k) lambda[K.adj[k]] += sol.y[m + k];                // :513-515
         for (int64_t j = 0; j < n; ++j) {                                                       // :519-529
             bool fixed = L.ub[j] <= L.lb[j];
             double mL = sol.as.bst[j] < 0 ? std::max(sol.z[j], 0.0) : 0.0;
             double mU = sol.as.bst[j] > 0 ? std::min(sol.z[j], 0.0) : 0.0;
             if (fixed) { mU = std::min(sol.z[j], 0.0); mL = std::max(sol.z[j], 0.0); }      // a fixed column reports both halves of its reduced cost
-            if (p_out[j] < h->v_ub[j] - h->x_k[j]) mU = 0.0;
-            if (p_out[j] > h->v_lb[j] - h->x_k[j]) mL = 0.0;
+            if (p_out[j] < K.v_ub[j] - K.x_k[j]) mU = 0.0;
+            if (p_out[j] > K.v_lb[j] - K.x_k[j]) mL = 0.0;
             mult_x_L[j] = mL;
             mult_x_U[j] = mU;
         }
@@ -3615,29 +3611,29 @@ void do_solve(asm_handle* h, double delta, int feasibility, double* p_out, doubl
 // The LP itself, as an MOI optimizer receives it from the reference (subproblem.jl:250-484): for AsmHip.Optimizer
 void do_lp_solve(asm_handle* h, const double* dE, const double* q, const double* r, const double* lb, const double* ub, int use_slacks,
                  const double* w, const double* slo, double* p, double* s, double* y, double* z, int32_t* bound_state, int32_t* status) {
-    if (!h->setup_done) throw std::logic_error("asm_lp_solve: asm_sublp_setup first");
+    Skeleton& K = sk_of(h, "asm_lp_solve: asm_sublp_setup first");
     HIPCHK(hipSetDevice(h->device));
     auto t0 = std::chrono::steady_clock::now();
-    const int64_t n = h->n, M = h->M;
+    const int64_t n = K.n, M = K.M;
     for (int64_t j = 0; j < n; ++j)
         if (!(lb[j] > -INF && ub[j] < INF && lb[j] <= ub[j])) throw std::invalid_argument("asm_lp_solve: every structural column needs a finite box (the trust region)");
-    HIPCHK(asmb::copy_async(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(K.d_dE, dE, K.nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(asmb::sync(h->stream));
-    h->J_valid = false;
+    K.J_valid = false;
     LpRaw L;
     L.slacks = use_slacks != 0;
     L.q.assign(q, q + n); L.r.assign(r, r + M); L.lb.assign(lb, lb + n); L.ub.assign(ub, ub + n);
-    if (L.slacks) { L.w.assign(w, w + h->ns); L.slo.assign(slo, slo + h->ns); }
+    if (L.slacks) { L.w.assign(w, w + K.ns); L.slo.assign(slo, slo + K.ns); }
     LpSol sol;
     solve_raw(h, L, L.slacks ? 1 : 0, sol);
     *status = sol.status;
     for (int64_t j = 0; j < n; ++j) { p[j] = 0.0; z[j] = 0.0; if (bound_state) bound_state[j] = 0; }
     for (int64_t i = 0; i < M; ++i) y[i] = 0.0;
-    if (s) for (int64_t k = 0; k < h->ns; ++k) s[k] = L.slacks ? slo[k] : 0.0;
+    if (s) for (int64_t k = 0; k < K.ns; ++k) s[k] = L.slacks ? slo[k] : 0.0;
     if (sol.status == ASM_OPTIMAL) {
         for (int64_t j = 0; j < n; ++j) { p[j] = sol.p[j]; z[j] = sol.z[j]; if (bound_state) bound_state[j] = sol.as.bst[j]; }
         for (int64_t i = 0; i < M; ++i) y[i] = sol.y[i];
-        if (s && L.slacks) for (int64_t k = 0; k < h->ns; ++k) s[k] = sol.s[k];
+        if (s && L.slacks) for (int64_t k = 0; k < K.ns; ++k) s[k] = sol.s[k];
     }
     h->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -3686,26 +3682,26 @@ void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool ful
     const FnStore& F = e.F;
     const unsigned nt = (unsigned)ntrial;
     if (F.n_rows > 0)
-        asmb::launch(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), h->stream, F, xd, Ed, h->d_dE, full ? 1 : 0, ldx, ldE);
+        asmb::launch(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), h->stream, F, xd, Ed, h->sk->d_dE, full ? 1 : 0, ldx, ldE);
     const ExprTape& X = e.X;
     const bool expr_obj = e.nlp_kind == ASM_NLP_EXPR && X.T > 0;     // the expression objective replaces the store's objective row
     if (!expr_obj) {
         asmb::launch(k_fn_objective, dim3(nt), dim3(256), h->stream, F, xd, fd, ldx);
-        if (full) asmb::launch(k_fn_gradient, asmb::blocks(h->n), dim3(256), h->stream, F, xd, e.d_df);
+        if (full) asmb::launch(k_fn_gradient, asmb::blocks(h->sk->n), dim3(256), h->stream, F, xd, e.d_df);
     }
     if (e.nlp_kind == ASM_NLP_EXPR) {
         if (X.R > 0)
-            asmb::launch(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), h->stream, X, xd, Ed, h->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
+            asmb::launch(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), h->stream, X, xd, Ed, h->sk->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
         if (expr_obj) {
             asmb::launch(k_nlp_expr_terms, dim3((unsigned)((X.T + 255) / 256), nt), dim3(256), h->stream, X, xd, full ? 1 : 0, ldx);
             asmb::launch(k_nlp_expr_objective, dim3(nt), dim3(64), h->stream, X, F.objective_scale, fd);
-            if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->n), dim3(256), h->stream, X, F.objective_scale, e.d_df);
+            if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->sk->n), dim3(256), h->stream, X, F.objective_scale, e.d_df);
         }
     } else if (e.nlp_kind == 1) {
         const int64_t nl = e.nlp_rows / 4;
-        asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, e.d_ipar, e.d_dpar, xd, Ed, h->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
+        asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, e.d_ipar, e.d_dpar, xd, Ed, h->sk->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
     } else if (e.nlp_kind == 2) {
-        asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((e.nlp_rows + 3) / 4), nt), dim3(256), h->stream, e.d_dpar, e.nlp_rows, h->n, xd, Ed, h->d_dE, F.n_rows,
+        asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((e.nlp_rows + 3) / 4), nt), dim3(256), h->stream, e.d_dpar, e.nlp_rows, h->sk->n, xd, Ed, h->sk->d_dE, F.n_rows,
                      e.fn_nnz, full ? 1 : 0, ldx, ldE);
     }
 }
@@ -3768,7 +3764,7 @@ int asm_destroy(asm_handle* h) {
     if (h->stream2) (void)asmb::sync(h->stream2);   // look-ahead chain may still be running after an exception
     for (auto& r : h->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
-    free_device(h);
+    h->ev.reset(); h->sk.reset();
     for (auto e : h->la_events) (void)hipEventDestroy(e);
     if (!h->batch_slot) {
         if (h->stream2) (void)hipStreamDestroy(h->stream2);
@@ -3810,7 +3806,8 @@ int asm_sublp_solve(asm_handle* h, const double* dE, const double* df, double f,
 int asm_lp_solve(asm_handle* h, const double* dE, const double* q, const double* r, const double* lb, const double* ub, int use_slacks,
                  const double* w, const double* slo, double* p, double* s, double* y, double* z, int32_t* bound_state, int32_t* status) {
     return guarded(h, [&] {
-        if ((h->nnz > 0 && !dE) || !q || (h->M > 0 && (!r || !y)) || !lb || !ub || !p || !z || !status || (use_slacks && (!w || !slo)))
+        const Skeleton& K = sk_of(h, "asm_lp_solve: asm_sublp_setup first");
+        if ((K.nnz > 0 && !dE) || !q || (K.M > 0 && (!r || !y)) || !lb || !ub || !p || !z || !status || (use_slacks && (!w || !slo)))
             throw std::invalid_argument("asm_lp_solve: null pointer");
         do_lp_solve(h, dE, q, r, lb, ub, use_slacks, w, slo, p, s, y, z, bound_state, status);
     });
@@ -3819,36 +3816,37 @@ int asm_lp_solve(asm_handle* h, const double* dE, const double* q, const double*
 int asm_sublp_active_set(const asm_handle* h, int32_t* row_state, int32_t* bound_state, int32_t* slack_state, int64_t* n_rows,
                          int64_t* n_slack) {
     if (!h) return ASM_ERR_ARG;
-    if (!h->last.valid) return ASM_ERR_STATE;
-    if (n_rows) *n_rows = (int64_t)h->last.rowst.size();
-    if (n_slack) *n_slack = (int64_t)h->last.sst.size();
-    if (row_state) for (size_t i = 0; i < h->last.rowst.size(); ++i) row_state[i] = h->last.rowst[i];
-    if (bound_state) for (size_t i = 0; i < h->last.bst.size(); ++i) bound_state[i] = h->last.bst[i];
-    if (slack_state) for (size_t i = 0; i < h->last.sst.size(); ++i) slack_state[i] = h->last.sst[i];
+    if (!h->sk || !h->sk->last.valid) return ASM_ERR_STATE;
+    const ActiveSet& last = h->sk->last;
+    if (n_rows) *n_rows = (int64_t)last.rowst.size();
+    if (n_slack) *n_slack = (int64_t)last.sst.size();
+    if (row_state) for (size_t i = 0; i < last.rowst.size(); ++i) row_state[i] = last.rowst[i];
+    if (bound_state) for (size_t i = 0; i < last.bst.size(); ++i) bound_state[i] = last.bst[i];
+    if (slack_state) for (size_t i = 0; i < last.sst.size(); ++i) slack_state[i] = last.sst[i];
     return ASM_OK;
 }
 
 int asm_sublp_reset_warm(asm_handle* h) {
     if (!h) return ASM_ERR_ARG;
-    reset_warm(h, false);
+    if (h->sk) reset_warm(*h->sk, false);
     return ASM_OK;
 }
 
 int asm_sublp_ns_basis(const asm_handle* h, int32_t* J, int64_t* k) {
     if (!h || !k) return ASM_ERR_ARG;
-    const std::vector<int>& v = h->hint[0].ns_J;
-    *k = (int64_t)v.size();
-    if (J) for (size_t a = 0; a < v.size(); ++a) J[a] = v[a];
+    *k = h->sk ? (int64_t)h->sk->hint[0].ns_J.size() : 0;        // without a skeleton: as on a new handle
+    if (J) for (int64_t a = 0; a < *k; ++a) J[a] = h->sk->hint[0].ns_J[a];
     return ASM_OK;
 }
 
 int asm_sublp_row_order(const asm_handle* h, int32_t* perm, int64_t* band, int32_t* e_rows, int64_t* n_e, int64_t* e_band) {
     if (!h || !band || !n_e || !e_band) return ASM_ERR_ARG;
-    *band = h->row_band;
-    if (perm && h->row_band > 0) for (int64_t q = 0; q < h->M; ++q) perm[q] = h->row_perm_h[q];
-    *n_e = h->nsf ? h->nsf->L.nE : 0;
-    *e_band = h->nsf ? h->nsf->f0.band : 0;
-    if (e_rows && h->nsf) std::copy(h->nsf->eidx_h.begin(), h->nsf->eidx_h.end(), e_rows);
+    const NsForm* F = h->sk ? h->sk->nsf.get() : nullptr;
+    *band = h->sk ? h->sk->row_band : 0;                          // without a skeleton: as on a new handle
+    if (perm && *band > 0) std::copy(h->sk->row_perm_h.begin(), h->sk->row_perm_h.end(), perm);
+    *n_e = F ? F->L.nE : 0;
+    *e_band = F ? F->f0.band : 0;
+    if (e_rows && F) std::copy(F->eidx_h.begin(), F->eidx_h.end(), e_rows);
     return ASM_OK;
 }
 
@@ -3887,13 +3885,14 @@ int asm_kernel_stats_reset(asm_handle* h) {
 // --------------------------------------------------------------------------------- norms on the resident Jacobian
 static void do_jac_row_norms(asm_handle* h, double* out_m) {
     if (!out_m) throw std::invalid_argument("asm_jac_row_norms: null pointer");
-    if (!h->setup_done || !h->inputs_ready) throw std::logic_error("asm_jac_row_norms: no assembled Jacobian");
+    const Skeleton& K = sk_of(h, "asm_jac_row_norms: no assembled Jacobian");
+    if (!K.inputs_ready) throw std::logic_error("asm_jac_row_norms: no assembled Jacobian");
     HIPCHK(hipSetDevice(h->device));
     Dev d(h);
     d.assemble();
-    if (h->m == 0) return;
-    asmb::launch(k_row_norms, asmb::blocks(h->m, 4), dim3(256), h->stream, h->d_J, h->ldn, h->d_vecM, h->m, h->ldn);
-    d.d2h(out_m, h->d_vecM, h->m);
+    if (K.m == 0) return;
+    asmb::launch(k_row_norms, asmb::blocks(K.m, 4), dim3(256), h->stream, K.d_J, K.ldn, K.d_vecM, K.m, K.ldn);
+    d.d2h(out_m, K.d_vecM, K.m);
 }
 
 int asm_jac_row_norms(asm_handle* h, double* out_m) {
@@ -3902,18 +3901,19 @@ int asm_jac_row_norms(asm_handle* h, double* out_m) {
 
 int asm_kt_residuals(asm_handle* h, const double* df, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out) {
     return guarded(h, [&] {
-        if (!df || !mult_x_U || !mult_x_L || !out || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_kt_residuals: null pointer");
-        if (!h->setup_done || !h->inputs_ready) throw std::logic_error("asm_kt_residuals: no assembled Jacobian");
+        const Skeleton& K = sk_of(h, "asm_kt_residuals: no assembled Jacobian");
+        if (!df || !mult_x_U || !mult_x_L || !out || (K.m > 0 && !lambda)) throw std::invalid_argument("asm_kt_residuals: null pointer");
+        if (!K.inputs_ready) throw std::logic_error("asm_kt_residuals: no assembled Jacobian");
         HIPCHK(hipSetDevice(h->device));
         Dev d(h);
         d.assemble();
-        const int64_t n = h->n, m = h->m;
-        vec lam(h->M, 0.0), jtl(n), rn(std::max<int64_t>(m, 1));
+        const int64_t n = K.n, m = K.m;
+        vec lam(K.M, 0.0), jtl(n), rn(std::max<int64_t>(m, 1));
         for (int64_t i = 0; i < m; ++i) lam[i] = lambda[i];
-        d.gemv_t(h->d_J, lam.data(), jtl.data());
+        d.gemv_t(K.d_J, lam.data(), jtl.data());
         if (m > 0) {
-            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_J, h->ldn, h->d_vecM, m, h->ldn);
-            d.d2h(rn.data(), h->d_vecM, m);
+            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, K.d_J, K.ldn, K.d_vecM, m, K.ldn);
+            d.d2h(rn.data(), K.d_vecM, m);
         }
         // common.jl:38-43
         double res = 0.0, ndf = 0.0;
@@ -3941,7 +3941,7 @@ void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_
                   int64_t n_dpar) {
     auto bad = [](const std::string& what) { throw std::invalid_argument("asm_eval_setup: expression block: " + what); };
     if (!ip || n_ipar < 3) bad("ipar too short");
-    const int64_t R = ip[0], T = ip[1], L = ip[2], n = h->n;
+    const int64_t R = ip[0], T = ip[1], L = ip[2], n = h->sk->n;
     if (R != nlp_rows) bad("ipar[0] (rows) differs from nlp_rows");
     if (R < 0 || T < 0 || L < 0 || L > (int64_t)1 << 40 || R + T > L) bad("bad row / term / node count");
     if (n_ipar != 3 + R + T + 1 + 3 * L) bad("ipar size differs from 3 + R + T + 1 + 3 L");
@@ -3990,7 +3990,7 @@ void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_
         if (j0 + (int64_t)vars.size() > nlp_nnz) bad("nlp_nnz is smaller than the pattern of the rows");
         for (size_t q = 0; q < vars.size(); ++q) {
             const int64_t e = fn_nnz + j0 + (int64_t)q;
-            if (h->j_row_h[e] != n_rows + r + 1 || h->j_col_h[e] != vars[q] + 1)
+            if (h->sk->j_row_h[e] != n_rows + r + 1 || h->sk->j_col_h[e] != vars[q] + 1)
                 bad("j_str entry " + std::to_string(e + 1) + " differs from the pattern of row " + std::to_string(r) + " (its distinct variables, ascending)");
         }
         for (int64_t k = ptr[r]; k < ptr[r + 1]; ++k)
@@ -4024,15 +4024,15 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
                           const int64_t* q_v1, const int64_t* q_v2, const double* q_coef, const double* constant, const int64_t* jac_off,
                           const int64_t* g_ptr, const int64_t* g_kind, const double* g_coef, const int64_t* g_other, double objective_scale, int nlp_kind,
                           int64_t nlp_rows, int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
-    if (!h->setup_done) throw std::logic_error("asm_eval_setup: asm_sublp_setup first (it fixes n, m and the j_str order of dE)");
+    const Skeleton& K = sk_of(h, "asm_eval_setup: asm_sublp_setup first (it fixes n, m and the j_str order of dE)");
     if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < ASM_NLP_NONE || nlp_kind > ASM_NLP_EXPR)
         throw std::invalid_argument("asm_eval_setup: bad argument");
     const int64_t fn_nnz = jac_off[n_rows];
-    if (n_rows + nlp_rows != h->m || fn_nnz + nlp_nnz != h->nnz)
+    if (n_rows + nlp_rows != K.m || fn_nnz + nlp_nnz != K.nnz)
         throw std::invalid_argument("asm_eval_setup: row / Jacobian-entry counts do not match asm_sublp_setup");
     if (nlp_kind == 1 && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
         throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
-    if (nlp_kind == 2 && (nlp_nnz != nlp_rows * h->n || n_dpar != 2 * nlp_rows * h->n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
+    if (nlp_kind == 2 && (nlp_nnz != nlp_rows * K.n || n_dpar != 2 * nlp_rows * K.n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
     ExprHost xh;
     if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
     HIPCHK(hipSetDevice(h->device));
@@ -4040,34 +4040,34 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     auto e = std::make_unique<EvalState>();
     BufPool& P = e->mem;
     FnStore& F = e->F;
-    F.n_rows = n_rows; F.n = h->n; F.objective_scale = objective_scale;
-    const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[h->n];
+    F.n_rows = n_rows; F.n = K.n; F.objective_scale = objective_scale;
+    const int64_t na = aff_ptr[n_rows + 1], nq = quad_ptr[n_rows + 1], ng = g_ptr[K.n];
     P.upload(F.aff_ptr, aff_ptr, n_rows + 2); P.upload(F.aff_var, aff_var, na); P.upload(F.aff_coef, aff_coef, na);
     P.upload(F.quad_ptr, quad_ptr, n_rows + 2); P.upload(F.q_v1, q_v1, nq); P.upload(F.q_v2, q_v2, nq); P.upload(F.q_coef, q_coef, nq);
     P.upload(F.constant, constant, n_rows + 1); P.upload(F.jac_off, jac_off, n_rows + 1);
-    P.upload(F.g_ptr, g_ptr, h->n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
+    P.upload(F.g_ptr, g_ptr, K.n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
     e->nlp_kind = nlp_kind; e->nlp_rows = nlp_rows; e->fn_nnz = fn_nnz; e->n_dpar = n_dpar;
     P.upload(e->d_ipar, nlp_ipar, n_ipar); P.upload(e->d_dpar, nlp_dpar, n_dpar);
-    const int64_t n = h->n, m = h->m;      // (the pool makes an empty vector one element long)
+    const int64_t n = K.n, m = K.m;      // (the pool makes an empty vector one element long)
     P.zeroed(e->d_x, n); P.zeroed(e->d_xt, 8 * round_up(n, 32)); P.zeroed(e->d_df, n); P.zeroed(e->d_E, m);
     P.zeroed(e->d_Et, 8 * round_up(std::max<int64_t>(m, 1), 32)); P.zeroed(e->d_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
     if (nlp_kind == ASM_NLP_EXPR) {
         ExprTape& X = e->X;
-        X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = h->n;
+        X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = K.n;
         P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
         P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
         P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
         X.cst = e->d_dpar;
         // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
         P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
-        P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[h->n]);
+        P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[K.n]);
         if (!xh.cptr.empty()) {     // the data gradient's occurrence list, multipliers of the rows and result (tapes with constants only)
             P.upload(e->d_cptr, xh.cptr.data(), n_dpar + 1);
             P.zeroed(e->d_cocc, xh.cptr[n_dpar]); P.zeroed(e->d_lam, xh.R); P.zeroed(e->d_dgrad, n_dpar);
             P.alloc(e->h_dgrad, n_dpar, BufPool::PINNED);
         }
     }
-    e->L = EvLayout{n, m, h->ldn, h->Mp};      // the reductions' block with the bounds in it, and the staging buffer
+    e->L = EvLayout{n, m, K.ldn, K.Mp};      // the reductions' block with the bounds in it, and the staging buffer
     P.zeroed(e->L.d, e->L.len());
     ev_write_bounds(h, e->L);
     P.alloc(e->h_stage, e->L.stage_len(), BufPool::PINNED);
@@ -4086,10 +4086,10 @@ int asm_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr, const 
 
 // eval_functions! (slp.jl:186-191) on the device + what asm_sublp_upload does with the results: dE stays in HBM
 static void do_eval_functions(asm_handle* h, const double* x, double* f, double* df, double* E) {
-    if (!x || !f || !df || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_functions: null pointer");
     EvalState& e = ev_of(h, "asm_eval_functions");
+    if (!x || !f || !df || (h->sk->m > 0 && !E)) throw std::invalid_argument("asm_eval_functions: null pointer");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n, m = h->m;
+    const int64_t n = h->sk->n, m = h->sk->m;
     double *st = e.h_stage, *s_df = st + e.L.st_df(), *s_E = st + e.L.st_E(true), *s_f = st + e.L.st_f(true);
     std::memcpy(st, x, n * sizeof(double));
     HIPCHK(asmb::copy_async(e.d_x, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4101,11 +4101,11 @@ static void do_eval_functions(asm_handle* h, const double* x, double* f, double*
     std::memcpy(df, s_df, n * sizeof(double));
     if (m) std::memcpy(E, s_E, m * sizeof(double));
     *f = *s_f;
-    h->df.assign(df, df + n); h->E.assign(E, E + m); h->x_k.assign(x, x + n);
-    h->f = *f;
-    h->inputs_ready = true;
-    h->inputs_from_eval = true;
-    h->J_valid = false;
+    h->sk->df.assign(df, df + n); h->sk->E.assign(E, E + m); h->sk->x_k.assign(x, x + n);
+    h->sk->f = *f;
+    h->sk->inputs_ready = true;
+    h->sk->inputs_from_eval = true;
+    h->sk->J_valid = false;
 }
 
 int asm_eval_functions(asm_handle* h, const double* x, double* f, double* df, double* E) {
@@ -4130,8 +4130,8 @@ static void do_set_data(asm_handle* h, int64_t offset, int64_t count, const doub
 static void do_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
     EvalState& e = ev_of(h, "asm_eval_data_gradient");
     if (e.nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument("asm_eval_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
-    if (!x || (h->m > 0 && !lambda) || (e.n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
-    const int64_t n = h->n, nd = e.n_dpar;
+    if (!x || (h->sk->m > 0 && !lambda) || (e.n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
+    const int64_t n = h->sk->n, nd = e.n_dpar;
     if (!e.d_cocc) {            // no CONST node: nothing depends on the data
         for (int64_t c = 0; c < nd; ++c) out[c] = 0.0;
         return;
@@ -4215,7 +4215,7 @@ void hs_build(const asm_handle* h, HsShared& sh) {
     const FnStore& F = h->ev->F;
     const ExprTape& X = h->ev->X;
     const bool expr = h->ev->nlp_kind == ASM_NLP_EXPR;
-    const int64_t nr = F.n_rows, n = h->n;
+    const int64_t nr = F.n_rows, n = h->sk->n;
     // 1. function store: the objective row's quadratic terms (unless the block has the objective), then the rows' in row order
     const std::vector<int64_t> qptr = hs_download(F.quad_ptr, nr + 2);
     const std::vector<int64_t> q1 = hs_download(F.q_v1, qptr[nr + 1]), q2 = hs_download(F.q_v2, qptr[nr + 1]);
@@ -4302,8 +4302,8 @@ void hs_attach(asm_handle* h, const HsShared* sh) {
         H.srow = sh->srow; H.svar = sh->svar; H.woff = sh->woff; H.optr = sh->optr; H.ovar = sh->ovar;
         zeroed(H.val, sh->wnodes); zeroed(H.tval, sh->wnodes); zeroed(H.adj, sh->wnodes); zeroed(H.tadj, sh->wnodes); zeroed(H.hocc, sh->nocc);
     }
-    zeroed(e.d_hs_lam, h->m); zeroed(e.d_hs_v, h->n); zeroed(e.d_hs_vals, sh->nnz()); zeroed(e.d_hs_out, h->n);
-    M.alloc(e.h_hs, std::max(sh->nnz(), h->n), BufPool::PINNED);
+    zeroed(e.d_hs_lam, h->sk->m); zeroed(e.d_hs_v, h->sk->n); zeroed(e.d_hs_vals, sh->nnz()); zeroed(e.d_hs_out, h->sk->n);
+    M.alloc(e.h_hs, std::max(sh->nnz(), h->sk->n), BufPool::PINNED);
     e.hs_sh = sh;
 }
 // once per asm_eval_setup, at the first Hessian call of a handle
@@ -4327,7 +4327,7 @@ void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* 
     HIPCHK(hipSetDevice(h->device));
     EvalState& e = *h->ev;
     const HsShared& L = *e.hs_sh;
-    const int64_t n = h->n, m = h->m, nnz = L.nnz(), nfn = L.nfn;
+    const int64_t n = h->sk->n, m = h->sk->m, nnz = L.nnz(), nfn = L.nfn;
     double *st = e.h_stage, *s_lam = st + e.L.st_lam(), *s_v = st + e.L.st_v();
     std::memcpy(st, x, n * sizeof(double));
     HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4369,7 +4369,7 @@ static void do_hessian_structure(asm_handle* h, int64_t* nnz, int64_t* rows, int
 }
 static void do_hessian_lagrangian(asm_handle* h, const double* x, double obj_factor, const double* lambda, double* values) {
     hs_check(h, "asm_eval_hessian_lagrangian");
-    if (!x || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
+    if (!x || (h->sk->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
     hs_prepare(h);
     if (h->ev->hs_sh->nnz() > 0 && !values) throw std::invalid_argument("asm_eval_hessian_lagrangian: null pointer");
     hs_launch(h, x, obj_factor, lambda, nullptr);
@@ -4377,9 +4377,9 @@ static void do_hessian_lagrangian(asm_handle* h, const double* x, double obj_fac
 }
 static void do_hessian_product(asm_handle* h, const double* x, double obj_factor, const double* lambda, const double* v, double* out) {
     hs_check(h, "asm_eval_hessian_product");
-    if (!x || !v || !out || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_product: null pointer");
+    if (!x || !v || !out || (h->sk->m > 0 && !lambda)) throw std::invalid_argument("asm_eval_hessian_product: null pointer");
     hs_launch(h, x, obj_factor, lambda, v);
-    hs_read(h, h->ev->d_hs_out, h->n, out);
+    hs_read(h, h->ev->d_hs_out, h->sk->n, out);
 }
 
 // ---- cross derivatives with respect to the data (include/asm_hip.h, "Cross derivatives of an expression block")
@@ -4391,7 +4391,7 @@ void cx_prepare(asm_handle* h) {
     if (e.h_cx) return;            // (the last buffer it makes)
     HIPCHK(hipSetDevice(h->device));
     const ExprTape& X = e.X;
-    const int64_t n = h->n, nt = X.R + X.T;
+    const int64_t n = h->sk->n, nt = X.R + X.T;
     const std::vector<int64_t> ptr = hs_download(X.ptr, nt + 1), ta = hs_download(X.a, X.L);
     const std::vector<int32_t> top = hs_download(X.op, X.L);
     std::vector<int64_t> vptr(n + 1, 0);
@@ -4420,8 +4420,8 @@ void cx_check(const asm_handle* h, const char* who) {
 static void do_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w) {
     cx_check(h, "asm_eval_data_cross");
     EvalState& e = *h->ev;
-    if (!x || !u || (h->m > 0 && (!lambda || !w)) || (e.n_dpar > 0 && !dc)) throw std::invalid_argument("asm_eval_data_cross: null pointer");
-    const int64_t n = h->n, m = h->m, nd = e.n_dpar;
+    if (!x || !u || (h->sk->m > 0 && (!lambda || !w)) || (e.n_dpar > 0 && !dc)) throw std::invalid_argument("asm_eval_data_cross: null pointer");
+    const int64_t n = h->sk->n, m = h->sk->m, nd = e.n_dpar;
     for (int64_t j = 0; j < n; ++j) u[j] = 0.0;
     for (int64_t i = 0; i < m; ++i) w[i] = 0.0;
     if (!e.d_cocc) return;      // no CONST node: nothing depends on the data
@@ -4457,10 +4457,10 @@ void kk_prepare(asm_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     BufPool& M = h->ev->mem;
     const hipStream_t s = h->stream;
-    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), CW = KKM_CW;
-    K.capW = std::max<int64_t>(std::min(h->m, h->n), 1);
+    const int64_t ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32), CW = KKM_CW;
+    K.capW = std::max<int64_t>(std::min(h->sk->m, h->sk->n), 1);
     K.ldT = round_up(K.capW, 32);
-    M.alloc(K.dE, h->nnz);
+    M.alloc(K.dE, h->sk->nnz);
     M.zeroed(K.J, Mp * ldn, s);
     M.zeroed(K.Aw, K.capW * ldn, s);
     M.zeroed(K.AwT, ldn * K.ldT, s);
@@ -4484,7 +4484,7 @@ KktWork* kk_work(asm_handle* h, int64_t cap) {
     HIPCHK(hipSetDevice(h->device));
     BufPool& M = h->ev->mem;
     const hipStream_t s = h->stream;
-    const int64_t ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), nd = std::max<int64_t>(h->ev->n_dpar, 1);
+    const int64_t ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32), nd = std::max<int64_t>(h->ev->n_dpar, 1);
     M.zeroed(W.vec, 14 * cap * ldn, s);
     M.zeroed(W.row, 5 * cap * K.ldT, s);
     M.zeroed(W.dlf, cap * Mp, s);
@@ -4502,27 +4502,27 @@ KktWork* kk_work(asm_handle* h, int64_t cap) {
 // word the host spins on, or (pub == 0, ASM_HIP_SPIN=0) a copy and a stream synchronisation
 int kk_read_scal(asm_handle* h, unsigned pub) {
     if (pub == 0) {
-        HIPCHK(asmb::copy_async(h->h_scal, h->ev->kk.scal + KKM_CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::copy_async(h->sk->h_scal, h->ev->kk.scal + KKM_CW * KKM_SCAL, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(asmb::sync(h->stream));
-        return (int)h->h_scal[0];
+        return (int)h->sk->h_scal[0];
     }
     if (asmb::in_fiber()) {      // scenario batch: the publishing kernel is recorded; the round that launches it ends before this fiber resumes
         asmb::flush_wait();
-        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) != pub) throw HipError("asm_kkt_solve: the batch round ended without the publishing kernel's sequence word");
-        return (int)h->h_scal[0];
+        if (__atomic_load_n(h->sk->h_seq, __ATOMIC_ACQUIRE) != pub) throw HipError("asm_kkt_solve: the batch round ended without the publishing kernel's sequence word");
+        return (int)h->sk->h_scal[0];
     }
     const double t0 = Solver::now_ms();
     for (unsigned long spins = 1;; ++spins) {
-        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) break;
+        if (__atomic_load_n(h->sk->h_seq, __ATOMIC_ACQUIRE) == pub) break;
         if (spins < 20000) __builtin_ia32_pause();
         else sched_yield();
         if ((spins & 0xffff) == 0 && Solver::now_ms() - t0 > 30000.0) {
             HIPCHK(asmb::sync(h->stream));            // a device fault surfaces here
-            if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == pub) break;
+            if (__atomic_load_n(h->sk->h_seq, __ATOMIC_ACQUIRE) == pub) break;
             throw HipError("asm_kkt_solve: the publishing kernel finished without setting its sequence word");
         }
     }
-    return (int)h->h_scal[0];
+    return (int)h->sk->h_scal[0];
 }
 
 // The face of a call: its counts and limits, and on the device (h->ev->kk) the mask of F, the list of W, A = J[W, F] with its transposed copy
@@ -4542,7 +4542,7 @@ struct KktFace {
 };
 KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                  const asm_kkt_params* par) {
-    const int64_t n = h->n, m = h->m, ldn = h->ldn;
+    const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn;
     KktFace& f = *this;
     for (int64_t j = 0; j < n; ++j) {
         if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
@@ -4565,7 +4565,7 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     HIPCHK(hipSetDevice(h->device));
     KktBufs& K = h->ev->kk;
     const hipStream_t s = h->stream;
-    const int64_t Mp = std::max<int64_t>(h->Mp, 32);
+    const int64_t Mp = std::max<int64_t>(h->sk->Mp, 32);
     // 1. the Hessian values of f - lambda' g at x, once: they stay in d_hs_vals for every product of the call (x goes to d_ev_xt)
     {
         std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
@@ -4579,12 +4579,12 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         const ExprTape& X = h->ev->X;
         if (h->ev->nlp_kind == ASM_NLP_EXPR && X.R > 0)
             asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
-        if (h->dense_fast) {
-            const unsigned g = (unsigned)std::min<int64_t>((h->m * h->n + 255) / 256, 4096);
-            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, K.dE, K.J, h->m, h->n, ldn);
-        } else if (h->nu > 0) {
-            const unsigned g = (unsigned)std::min<int64_t>((h->nu + 255) / 256, 4096);
-            asmb::launch(k_assemble, dim3(g), dim3(256), s, K.dE, h->d_perm, h->d_ustart, h->d_uoff, h->d_adjoff, K.J, h->nu);
+        if (h->sk->dense_fast) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->sk->m * h->sk->n + 255) / 256, 4096);
+            asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, K.dE, K.J, h->sk->m, h->sk->n, ldn);
+        } else if (h->sk->nu > 0) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->sk->nu + 255) / 256, 4096);
+            asmb::launch(k_assemble, dim3(g), dim3(256), s, K.dE, h->sk->d_perm, h->sk->d_ustart, h->sk->d_uoff, h->sk->d_adjoff, K.J, h->sk->nu);
         }
     }
     // the sets: the mask and the working-row list in one upload
@@ -4627,7 +4627,7 @@ struct KktOps {
     const int64_t n, ldn, ldT;
     double* const spare;             // a block over the working rows of the back end's own
     KktOps(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww)
-        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->n), ldn(hh->ldn), ldT(hh->ev->kk.ldT), spare(ww.row + 2 * ww.cap * hh->ev->kk.ldT) {}
+        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->sk->n), ldn(hh->sk->ldn), ldT(hh->ev->kk.ldT), spare(ww.row + 2 * ww.cap * hh->ev->kk.ldT) {}
     virtual ~KktOps() = default;
     virtual void hess(const double* v, double* out, int cols) = 0;                  // OUT = H V from the values of step 1
     virtual void mul_A(const double* v, double* t, int cols) = 0;                   // T = V A'
@@ -4653,12 +4653,12 @@ struct KktOneColumn final : KktOps {
         return out;
     }
     void jt_dlam(const double*, const double* dlf, double* jtl, int) override {
-        const int64_t m = h->m;
+        const int64_t m = h->sk->m;
         int64_t Rc = std::min<int64_t>((m + 31) / 32, ASM_TMAXCHUNKS);
         const int64_t chunk = (m + Rc - 1) / Rc;
         Rc = (m + chunk - 1) / chunk;
-        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->ev->kk.J, ldn, dlf, h->d_partial, m, ldn, chunk);
-        asmb::launch(k_gemv_t_stage2, asmb::blocks(ldn), dim3(256), s, h->d_partial, jtl, Rc, ldn);
+        asmb::launch(k_gemv_t_stage1, dim3((unsigned)((ldn + 255) / 256), (unsigned)Rc), dim3(256), s, h->ev->kk.J, ldn, dlf, h->sk->d_partial, m, ldn, chunk);
+        asmb::launch(k_gemv_t_stage2, asmb::blocks(ldn), dim3(256), s, h->sk->d_partial, jtl, Rc, ldn);
     }
 };
 // a block of columns: k_gemm_nt products on the matrix cores (Dev::gemm_nt), Dev::trsm_rows in place with the factor's wide-block
@@ -4714,7 +4714,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     const KktBufs& K = h->ev->kk;
     KktWork& w = ops.w;
     const hipStream_t s = h->stream;
-    const int64_t n = h->n, m = h->m, ldn = h->ldn, Mp = std::max<int64_t>(h->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW, nd = sens ? h->ev->n_dpar : 0;
+    const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW, nd = sens ? h->ev->n_dpar : 0;
     const double* const mask = f.mask;
     auto vblock = [&](int k) { return w.vec + (int64_t)k * cap * ldn; };
     auto rblock = [&](int k) { return w.row + (int64_t)k * cap * ldT; };      // (block 2 is ops.spare)
@@ -4723,7 +4723,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     double *rww = rblock(0), *tw = rblock(1), *dlw = rblock(3), *adx = rblock(4);
     double* const dlf = w.dlf;
     double* const scal = K.scal;
-    const KktMulti R{K.part, K.cnt, scal, K.act, h->d_hscal, h->d_hseq};
+    const KktMulti R{K.part, K.cnt, scal, K.act, h->sk->d_hscal, h->sk->d_hseq};
     const bool cross = sens && h->ev->d_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
     if (cross) {      // the multipliers of the expression rows, once
         cx_prepare(h);
@@ -4889,7 +4889,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
 static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru,
                          const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
     hs_check(h, "asm_kkt_solve");
-    if (!x || !bound_state || !ru || !dx || !info || (h->m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
+    if (!x || !bound_state || !ru || !dx || !info || (h->sk->m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
     Dev dev(h);
     const KktFace f(h, dev, "asm_kkt_solve", x, lambda, row_state, bound_state, par);
     KktOneColumn ops(h, dev, f, *kk_work(h, 1));
@@ -4900,9 +4900,9 @@ static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, c
 static void do_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
                                     const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
     cx_check(h, "asm_solution_sensitivity");
-    if (!x || !bound_state || !dx || !info || (h->m > 0 && (!lambda || !row_state || !dlam)) || (h->ev->n_dpar > 0 && !dc))
+    if (!x || !bound_state || !dx || !info || (h->sk->m > 0 && (!lambda || !row_state || !dlam)) || (h->ev->n_dpar > 0 && !dc))
         throw std::invalid_argument("asm_solution_sensitivity: null pointer");
-    std::vector<double> u((size_t)std::max<int64_t>(h->n, 1)), w((size_t)std::max<int64_t>(h->m, 1));
+    std::vector<double> u((size_t)std::max<int64_t>(h->sk->n, 1)), w((size_t)std::max<int64_t>(h->sk->m, 1));
     do_data_cross(h, x, lambda, dc, u.data(), w.data());
     do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info);
 }
@@ -4915,8 +4915,8 @@ static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, 
     if (sens) cx_check(h, who);
     hs_check(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
-    if (!x || !bound_state || !DX || !info || (h->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
-    if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
+    if (!x || !bound_state || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
+    if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->sk->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
     Dev dev(h);
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par);
     KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
@@ -4930,7 +4930,7 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
     const std::string me(who);
     hs_check(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
-    if (!x || !bound_state || !RU || !RADIUS || !DX || !info || (h->m > 0 && (!lambda || !row_state || !RW || !DLAM))) throw std::invalid_argument(me + ": null pointer");
+    if (!x || !bound_state || !RU || !RADIUS || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !RW || !DLAM))) throw std::invalid_argument(me + ": null pointer");
     for (int32_t c = 0; c < nrhs; ++c)
         if (!(RADIUS[c] > 0.0)) throw std::invalid_argument(me + ": a radius is not > 0");
     KktTrust tr;
@@ -4956,10 +4956,10 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
 
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
 static void do_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
-    if (!x || !f || (h->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
     EvalState& e = ev_of(h, "asm_eval_constraints");
+    if (!x || !f || (h->sk->m > 0 && !E)) throw std::invalid_argument("asm_eval_constraints: null pointer");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n, m = h->m;
+    const int64_t n = h->sk->n, m = h->sk->m;
     double *st = e.h_stage, *s_E = st + e.L.st_E(false), *s_f = st + e.L.st_f(false);
     std::memcpy(st, x, n * sizeof(double));
     HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4978,9 +4978,9 @@ int asm_eval_constraints(asm_handle* h, const double* x, double* f, double* E) {
 int asm_eval_jacobian_values(asm_handle* h, double* dE_out) {
     return guarded(h, [&] {
         if (!dE_out) throw std::invalid_argument("asm_eval_jacobian_values: null pointer");
-        if (!h->setup_done) throw std::logic_error("asm_eval_jacobian_values: asm_sublp_setup first");
+        const Skeleton& K = sk_of(h, "asm_eval_jacobian_values: asm_sublp_setup first");
         HIPCHK(hipSetDevice(h->device));
-        HIPCHK(asmb::copy(dE_out, h->d_dE, h->nnz * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(dE_out, K.d_dE, K.nnz * sizeof(double), hipMemcpyDeviceToHost));
     });
 }
 
@@ -5054,10 +5054,10 @@ int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, 
 // out[4] = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }  (common.jl:35-98) from the
 // evaluation results of the last asm_eval_functions and the Jacobian assembled from its dE (assembled once, shared with the LP)
 static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, const double* mult_x_L, double* out4) {
-    if (!mult_x_U || !mult_x_L || !out4 || (h->m > 0 && !lambda)) throw std::invalid_argument("asm_slp_norms: null pointer");
-    if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_norms: asm_eval_functions first");
+    if (!h->ev || !h->sk->inputs_ready) throw std::logic_error("asm_slp_norms: asm_eval_functions first");
+    if (!mult_x_U || !mult_x_L || !out4 || (h->sk->m > 0 && !lambda)) throw std::invalid_argument("asm_slp_norms: null pointer");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n, m = h->m;
+    const int64_t n = h->sk->n, m = h->sk->m;
     Dev d(h);
     d.assemble();
     const EvLayout& L = h->ev->L;
@@ -5068,14 +5068,14 @@ static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult
     std::memcpy(st + (L.mL() - lam), mult_x_L, n * sizeof(double));
     HIPCHK(asmb::copy_async(lam, st, (L.nu() - lam) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     // J' lambda over the first m rows: lambda padded with zeros on the extra range rows
-    HIPCHK(asmb::fill_async(h->d_vecM, 0, h->Mp * sizeof(double), h->stream));
-    if (m) HIPCHK(asmb::copy_async(h->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    d.launch_gemv_t(h->d_J, h->d_vecM, jtl);
+    HIPCHK(asmb::fill_async(h->sk->d_vecM, 0, h->sk->Mp * sizeof(double), h->stream));
+    if (m) HIPCHK(asmb::copy_async(h->sk->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    d.launch_gemv_t(h->sk->d_J, h->sk->d_vecM, jtl);
     if (m) {
-        if (const double* vJ = d.sparse_vals(h->d_J))      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
-            asmb::launch(k_sp_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_sp_ptr, h->d_sp_col, vJ, rown, m);
+        if (const double* vJ = d.sparse_vals(h->sk->d_J))      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
+            asmb::launch(k_sp_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->sk->d_sp_ptr, h->sk->d_sp_col, vJ, rown, m);
         else
-            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->d_J, h->ldn, rown, m, h->ldn);
+            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->sk->d_J, h->sk->ldn, rown, m, h->sk->ldn);
     }
     asmb::launch(k_slp_norms, dim3(1), dim3(1024), h->stream, ev_vecs(*h->ev, true), outd);
     HIPCHK(asmb::copy_async(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -5093,14 +5093,14 @@ int asm_slp_norms(asm_handle* h, const double* lambda, const double* mult_x_U, c
 int asm_slp_merit(asm_handle* h, int mode, double alpha, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas,
                   double* out) {
     return guarded(h, [&] {
-        if (!p || !out || (h->m > 0 && (!nu || !p_slack)) || mode < 0 || mode > 1) throw std::invalid_argument("asm_slp_merit: bad argument");
-        if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_merit: asm_eval_functions first");
+        if (!h->ev || !h->sk->inputs_ready) throw std::logic_error("asm_slp_merit: asm_eval_functions first");
+        if (!p || !out || (h->sk->m > 0 && (!nu || !p_slack)) || mode < 0 || mode > 1) throw std::invalid_argument("asm_slp_merit: bad argument");
         HIPCHK(hipSetDevice(h->device));
         const EvalState& e = ev_stage_step(h, nu, p_slack, p);
         const EvLayout& L = e.L;
         const double *Et = e.d_E, *ft = e.d_f;
         if (mode == 0 && alpha != 0.0) {
-            asmb::launch(k_axpy_out, asmb::blocks(h->n), dim3(256), h->stream, e.d_x, alpha, L.p(), e.d_xt, h->n);
+            asmb::launch(k_axpy_out, asmb::blocks(h->sk->n), dim3(256), h->stream, e.d_x, alpha, L.p(), e.d_xt, h->sk->n);
             ev_launch(h, e.d_xt, e.d_Et, e.d_f + 1, false);
             Et = e.d_Et; ft = e.d_f + 1;
         }
@@ -5121,7 +5121,7 @@ static void slp_trials(asm_handle* h, int feasibility, double prim_infeas, bool 
                        double* alpha_out, double* phi_out, int* trials_out, int* ok_out) {
     const EvalState& e = *h->ev;
     const EvLayout& L = e.L;
-    const int64_t n = h->n, m = h->m;
+    const int64_t n = h->sk->n, m = h->sk->m;
     const SlpVecs V = ev_vecs(e);
     constexpr int CH = (int)EvLayout::TRIALS;
     static_assert(sizeof(TrialAlphas) == CH * sizeof(double), "one alpha per trial of a round");
@@ -5155,9 +5155,9 @@ static void slp_trials(asm_handle* h, int feasibility, double prim_infeas, bool 
 int asm_slp_line_search(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double phi0,
                         double D, double eta, double tau, double min_alpha, double* alpha_out, double* phi_out, int* trials_out, int* ok_out) {
     return guarded(h, [&] {
-        if (!p || !alpha_out || !ok_out || (h->m > 0 && (!nu || !p_slack)) || !(tau > 0.0 && tau < 1.0))
+        if (!h->ev || !h->sk->inputs_ready) throw std::logic_error("asm_slp_line_search: asm_eval_functions first");
+        if (!p || !alpha_out || !ok_out || (h->sk->m > 0 && (!nu || !p_slack)) || !(tau > 0.0 && tau < 1.0))
             throw std::invalid_argument("asm_slp_line_search: bad argument");
-        if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_line_search: asm_eval_functions first");
         HIPCHK(hipSetDevice(h->device));
         ev_stage_step(h, nu, p_slack, p);
         slp_trials(h, feasibility, prim_infeas, false, phi0, D, eta, tau, min_alpha, alpha_out, phi_out, trials_out, ok_out);
@@ -5183,7 +5183,7 @@ static void slp_merit_and_search(asm_handle* h, const double* p, const double* n
 static void slp_tr_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
     const EvalState& e = ev_stage_step(h, nu, p_slack, p);
     const EvLayout& L = e.L;
-    asmb::launch(k_axpy_out, asmb::blocks(h->n), dim3(256), h->stream, e.d_x, 1.0, L.p(), e.d_xt, h->n);
+    asmb::launch(k_axpy_out, asmb::blocks(h->sk->n), dim3(256), h->stream, e.d_x, 1.0, L.p(), e.d_xt, h->sk->n);
     ev_launch(h, e.d_xt, e.d_Et, e.d_f + 1, false);
     asmb::launch(k_slp_tr_quality, dim3(3), dim3(1024), h->stream, ev_vecs(e), e.d_Et, L.nu(), L.ps(), L.p(), feasibility, prim_infeas, e.d_f, e.d_f + 1, L.out());
     HIPCHK(asmb::copy_async(e.h_stage, L.out(), 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -5193,8 +5193,8 @@ static void slp_tr_step_quality(asm_handle* h, const double* p, const double* nu
 
 int asm_slp_step_quality(asm_handle* h, const double* p, const double* nu, const double* p_slack, int feasibility, double prim_infeas, double* out3) {
     return guarded(h, [&] {
-        if (!p || !out3 || (h->m > 0 && (!nu || !p_slack))) throw std::invalid_argument("asm_slp_step_quality: null pointer");
-        if (!h->ev || !h->inputs_ready) throw std::logic_error("asm_slp_step_quality: asm_eval_functions first");
+        if (!h->ev || !h->sk->inputs_ready) throw std::logic_error("asm_slp_step_quality: asm_eval_functions first");
+        if (!p || !out3 || (h->sk->m > 0 && (!nu || !p_slack))) throw std::invalid_argument("asm_slp_step_quality: null pointer");
         HIPCHK(hipSetDevice(h->device));
         slp_tr_step_quality(h, p, nu, p_slack, feasibility, prim_infeas, out3);
     });
@@ -5207,7 +5207,7 @@ void eq_prepare(asm_handle* h) {
     KktBufs& K = h->ev->kk;
     if (K.eq_i) return;
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n, m = h->m, ni = h->M + 2 * n + 3 * m + 4, nd = m + 2 * n + EQP_SCAL;
+    const int64_t n = h->sk->n, m = h->sk->m, ni = h->sk->M + 2 * n + 3 * m + 4, nd = m + 2 * n + EQP_SCAL;
     h->ev->mem.zeroed(K.eq_i, ni, h->stream);
     h->ev->mem.zeroed(K.eq_d, nd, h->stream);
     h->ev->mem.alloc(K.eq_h, (ni + 1) / 2 + nd + n + 8, BufPool::PINNED);
@@ -5220,7 +5220,7 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     const char* const who = "asm_eqp_trial";
     const std::string me(who);
     hs_check(h, who);
-    const int64_t n = h->n, m = h->m, M = h->M;
+    const int64_t n = h->sk->n, m = h->sk->m, M = h->sk->M;
     if (!x || !lp_bound_state || !d || !mult_x_U || !mult_x_L || !bound_state || !info || (m > 0 && (!lambda || !lp_row_state || !nu || !lam_new || !row_state)))
         throw std::invalid_argument(me + ": null pointer");
     if (!(tol_active >= 0.0)) throw std::invalid_argument(me + ": tol_active is not >= 0");
@@ -5232,8 +5232,8 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     for (int64_t i = 0; i < (m > 0 ? M : 0); ++i)
         if (lp_row_state[i] != 0 && lp_row_state[i] != 1) throw std::invalid_argument(me + ": row_state holds a value outside {0, 1}");
     // (inputs uploaded by asm_sublp_upload leave the evaluator's x, E and gradient in HBM where an earlier evaluation put them)
-    if (!h->inputs_ready || !h->inputs_from_eval) throw std::logic_error(me + ": asm_eval_functions first");
-    if (std::memcmp(x, h->x_k.data(), n * sizeof(double)) != 0) throw std::logic_error(me + ": x is not the point of the last asm_eval_functions");
+    if (!h->sk->inputs_ready || !h->sk->inputs_from_eval) throw std::logic_error(me + ": asm_eval_functions first");
+    if (std::memcmp(x, h->sk->x_k.data(), n * sizeof(double)) != 0) throw std::logic_error(me + ": x is not the point of the last asm_eval_functions");
     eq_prepare(h);
     HIPCHK(hipSetDevice(h->device));
     std::memset(info, 0, sizeof(*info));
@@ -5251,7 +5251,7 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     if (m > 0) std::memcpy(hi, lp_row_state, M * sizeof(int));
     std::memcpy(hi + M, lp_bound_state, n * sizeof(int));
     for (int64_t i = 0; i < m; ++i) hi[M + n + i] = -1;
-    for (size_t a = 0; a < h->adj.size(); ++a) hi[M + n + h->adj[a]] = (int)a;
+    for (size_t a = 0; a < h->sk->adj.size(); ++a) hi[M + n + h->sk->adj[a]] = (int)a;
     HIPCHK(asmb::copy_async(i_lp_rows, hi, n_in * sizeof(int), hipMemcpyHostToDevice, s));
     const SlpVecs V = ev_vecs(*h->ev);
     const EqpFace P{V.E, V.g_L, V.g_U, V.x, V.x_L, V.x_U, i_lp_rows, i_lp_bnd, i_twin, n, m, tol_active};
@@ -5317,7 +5317,7 @@ static void test_alloc(asm_handle* h, int64_t M, int64_t K) {
     std::vector<int64_t> jr(1, 1), jc(1, 1);
     vec lo(M, 0.0), hi(M, 0.0), vl(K, -1.0), vu(K, 1.0);
     do_setup(h, K, M, 1, jr.data(), jc.data(), lo.data(), hi.data(), vl.data(), vu.data());
-    h->sp_ok = false;     // the hooks write arbitrary matrices into the buffers
+    h->sk->sp_ok = false;     // the hooks write arbitrary matrices into the buffers
 }
 
 int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const int32_t* idx, int64_t Ms, const double* theta,
@@ -5326,14 +5326,14 @@ int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const in
         test_alloc(h, M, K);
         Dev d(h);
         for (int64_t i = 0; i < M; ++i)
-            HIPCHK(asmb::copy(h->d_Ah + i * h->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
-        d.h2d(h->d_theta, theta, K, h->ldn);
-        if (diag) d.h2d(h->d_diag, diag, Ms, Ms);
-        if (idx) HIPCHK(asmb::copy(h->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
-        const FacBuf& F = h->main_fac;
+            HIPCHK(asmb::copy(h->sk->d_Ah + i * h->sk->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+        d.h2d(h->sk->d_theta, theta, K, h->sk->ldn);
+        if (diag) d.h2d(h->sk->d_diag, diag, Ms, Ms);
+        if (idx) HIPCHK(asmb::copy(h->sk->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
+        const FacBuf& F = h->sk->main_fac;
         HIPCHK(asmb::fill(F.S, 0, F.ld * F.ld * sizeof(double)));
-        d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, idx ? h->d_idx : nullptr, 0, (int)Ms, (int)h->ldn, h->d_theta,
-                      diag ? h->d_diag : nullptr, F.S, F.ld, 0, 0);
+        d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->sk->d_Ah, h->sk->ldn, idx ? h->sk->d_idx : nullptr, 0, (int)Ms, (int)h->sk->ldn, h->sk->d_theta,
+                      diag ? h->sk->d_diag : nullptr, F.S, F.ld, 0, 0);
         HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
             HIPCHK(asmb::copy(S_out + i * Ms, F.S + i * F.ld, Ms * sizeof(double), hipMemcpyDeviceToHost));
@@ -5409,37 +5409,37 @@ int asm_test_build_split(asm_handle* h, const double* G, int64_t k, int64_t K, c
 int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const int32_t* idx, int64_t Ms, const double* theta, const double* diag, double* S_inout,
                             double* Ah_out, int64_t* info, int32_t* row_order, int32_t* col_order, int32_t* e_order) {
     return guarded(h, [&] {
-        if (!h->setup_done) throw std::logic_error("asm_test_build_dispatch: asm_sublp_setup first");
-        if (!info || (h->nnz > 0 && !dE) || which > 4) throw std::invalid_argument("asm_test_build_dispatch: bad argument");
+        Skeleton& K = sk_of(h, "asm_test_build_dispatch: asm_sublp_setup first");
+        if (!info || (K.nnz > 0 && !dE) || which > 4) throw std::invalid_argument("asm_test_build_dispatch: bad argument");
         HIPCHK(hipSetDevice(h->device));
-        const int64_t M = h->M, n = h->n;
+        const int64_t M = K.M, n = K.n;
         Dev d(h);
-        HIPCHK(asmb::copy(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice));
-        h->J_valid = false;
+        HIPCHK(asmb::copy(K.d_dE, dE, K.nnz * sizeof(double), hipMemcpyHostToDevice));
+        K.J_valid = false;
         d.assemble();
         vec c(n, 1.0), rho(M);
         d.scale(c.data(), rho.data());
         d.tile_flags();
-        NsForm* const ns = h->nsf.get();
-        const int64_t out[12] = {M, n, h->row_band, h->col_band, h->main_fac.ld, ns ? ns->L.nE : 0, ns ? ns->f0.band : 0, ns ? ns->f0.ld : 0, h->col_capable ? 1 : 0,
-                                 h->nz_valid ? 1 : 0, 0, h->sp_ok ? 1 : 0};
+        NsForm* const ns = K.nsf.get();
+        const int64_t out[12] = {M, n, K.row_band, K.col_band, K.main_fac.ld, ns ? ns->L.nE : 0, ns ? ns->f0.band : 0, ns ? ns->f0.ld : 0, K.col_capable ? 1 : 0,
+                                 K.nz_valid ? 1 : 0, 0, K.sp_ok ? 1 : 0};
         for (int k = 0; k < 12; ++k) info[k] = out[k];
-        if (Ah_out) for (int64_t i = 0; i < M; ++i) HIPCHK(asmb::copy(Ah_out + i * n, h->d_Ah + i * h->ldn, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (row_order) for (int64_t q = 0; q < M; ++q) row_order[q] = h->row_band > 0 ? h->row_perm_h[q] : -1;
+        if (Ah_out) for (int64_t i = 0; i < M; ++i) HIPCHK(asmb::copy(Ah_out + i * n, K.d_Ah + i * K.ldn, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (row_order) for (int64_t q = 0; q < M; ++q) row_order[q] = K.row_band > 0 ? K.row_perm_h[q] : -1;
         if (col_order) {
-            if (h->col_band > 0) HIPCHK(asmb::copy(col_order, h->d_colperm, n * sizeof(int), hipMemcpyDeviceToHost));
+            if (K.col_band > 0) HIPCHK(asmb::copy(col_order, K.d_colperm, n * sizeof(int), hipMemcpyDeviceToHost));
             else for (int64_t q = 0; q < n; ++q) col_order[q] = -1;
         }
         if (e_order && ns) std::copy(ns->eidx_h.begin(), ns->eidx_h.end(), e_order);
         if (which < 0) return;
-        const FacBuf& f = which == 4 && ns ? ns->f0 : h->main_fac;       // (which = 4 without the form is refused below)
+        const FacBuf& f = which == 4 && ns ? ns->f0 : K.main_fac;       // (which = 4 without the form is refused below)
         const int64_t nth = (which == 1 || which == 3) ? M : n, ndg = which == 0 ? M : ((which == 1 || which == 3) ? n : Ms);
-        if (!theta || !S_inout || (which == 2 && (!idx || Ms <= 0 || Ms > M)) || ((which == 1 || which == 3) && (!h->col_capable || !diag)) ||
-            (which == 3 && h->col_band <= 0) || (which == 4 && !ns) || ((which == 1 || which == 3) && n > f.ld) || (which == 0 && M == 0))
+        if (!theta || !S_inout || (which == 2 && (!idx || Ms <= 0 || Ms > M)) || ((which == 1 || which == 3) && (!K.col_capable || !diag)) ||
+            (which == 3 && K.col_band <= 0) || (which == 4 && !ns) || ((which == 1 || which == 3) && n > f.ld) || (which == 0 && M == 0))
             throw std::invalid_argument("asm_test_build_dispatch: build not available on this handle");
         double *dth = nullptr, *ddg = nullptr;
         BufPool tmp;
-        tmp.zeroed(dth, std::max(h->ldn, h->Mp) + 64);
+        tmp.zeroed(dth, std::max(K.ldn, K.Mp) + 64);
         HIPCHK(asmb::copy(dth, theta, nth * sizeof(double), hipMemcpyHostToDevice));
         if (diag && which != 4) tmp.upload(ddg, diag, ndg);
         HIPCHK(asmb::copy(f.S, S_inout, f.ld * f.ld * sizeof(double), hipMemcpyHostToDevice));
@@ -5448,22 +5448,22 @@ int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const in
         case 1: d.schur_syrk(true, nullptr, (int)n, dth, ddg, f.S, f.ld, Dev::NzFlags::Pattern); break;
         case 2: {
             for (int64_t a = 0; a < Ms; ++a) if (idx[a] < 0 || idx[a] >= M) throw std::invalid_argument("asm_test_build_dispatch: row index out of range");
-            HIPCHK(asmb::copy(h->d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
-            if (h->row_band > 0) {      // place of every row in the list (-1: not in it), as the reduced row form makes it
+            HIPCHK(asmb::copy(K.d_idx, idx, Ms * sizeof(int), hipMemcpyHostToDevice));
+            if (K.row_band > 0) {      // place of every row in the list (-1: not in it), as the reduced row form makes it
                 std::vector<int> cp(M, -1);
                 for (int64_t a = 0; a < Ms; ++a) cp[idx[a]] = (int)a;
-                HIPCHK(asmb::copy(h->d_cpos, cp.data(), M * sizeof(int), hipMemcpyHostToDevice));
+                HIPCHK(asmb::copy(K.d_cpos, cp.data(), M * sizeof(int), hipMemcpyHostToDevice));
             }
-            d.schur_rows(h->d_idx, h->d_cpos, (int)Ms, dth, ddg);
+            d.schur_rows(K.d_idx, K.d_cpos, (int)Ms, dth, ddg);
             break;
         }
         case 3: d.schur_banded_cols_dev(dth, ddg); break;
         default:
-            HIPCHK(asmb::copy(ns->Fm, dth, h->ldn * sizeof(double), hipMemcpyDeviceToDevice));
+            HIPCHK(asmb::copy(ns->Fm, dth, K.ldn * sizeof(double), hipMemcpyDeviceToDevice));
             d.ns_build_S0();
         }
         HIPCHK(asmb::sync(h->stream));
-        info[10] = h->nzT_valid ? 1 : 0;
+        info[10] = K.nzT_valid ? 1 : 0;
         HIPCHK(asmb::copy(S_inout, f.S, f.ld * f.ld * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
     });
@@ -5909,7 +5909,7 @@ int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double sc
         tmp.alloc(hSeq, 16, BufPool::MAPPED, &dhSeq);
         std::memcpy(hScal, hscal_inout, SC_COUNT * sizeof(double));
         *hSeq = *hseq_inout;
-        HIPCHK(asmb::copy(h->d_diag0, dg0.data(), k * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(h->sk->d_diag0, dg0.data(), k * sizeof(double), hipMemcpyHostToDevice));
         for (int64_t i = 0; i < k; ++i)
             HIPCHK(asmb::copy(fN.S + i * fld, Nreg + i * k, (i + 1) * sizeof(double), hipMemcpyHostToDevice));
         ar.base = dD; ar.ibase = dI; ar.hscal = dhScal; ar.hseq = dhSeq;
@@ -5981,13 +5981,13 @@ int asm_test_syrk_update(asm_handle* h, const double* Pm, int64_t Ms, int64_t K,
         const int64_t N = srow0 + Ms;
         test_alloc(h, N, std::max<int64_t>(K, 16));
         Dev d(h);
-        HIPCHK(asmb::fill(h->d_Ah, 0, h->Mp * h->ldn * sizeof(double)));
+        HIPCHK(asmb::fill(h->sk->d_Ah, 0, h->sk->Mp * h->sk->ldn * sizeof(double)));
         for (int64_t i = 0; i < Ms; ++i)
-            HIPCHK(asmb::copy(h->d_Ah + (srow0 + i) * h->ldn, Pm + i * K, K * sizeof(double), hipMemcpyHostToDevice));
-        const FacBuf& F = h->main_fac;
+            HIPCHK(asmb::copy(h->sk->d_Ah + (srow0 + i) * h->sk->ldn, Pm + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+        const FacBuf& F = h->sk->main_fac;
         for (int64_t i = 0; i < Ms; ++i)
             HIPCHK(asmb::copy(F.S + (srow0 + i) * F.ld + srow0, S_inout + i * Ms, Ms * sizeof(double), hipMemcpyHostToDevice));
-        d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->d_Ah, h->ldn, nullptr, srow0, (int)Ms, (int)K, nullptr, nullptr, F.S, F.ld, srow0, 1, (int)MsB);
+        d.launch_syrk(h->stream, tile > 0 ? tile : Dev::pick_tile(Ms), h->sk->d_Ah, h->sk->ldn, nullptr, srow0, (int)Ms, (int)K, nullptr, nullptr, F.S, F.ld, srow0, 1, (int)MsB);
         HIPCHK(asmb::sync(h->stream));
         for (int64_t i = 0; i < Ms; ++i)
             HIPCHK(asmb::copy(S_inout + i * Ms, F.S + (srow0 + i) * F.ld + srow0, Ms * sizeof(double), hipMemcpyDeviceToHost));
@@ -5999,12 +5999,11 @@ int asm_test_syrk_update(asm_handle* h, const double* Pm, int64_t Ms, int64_t K,
 // this order (released with the other null-space buffers at the next set-up); either has the band of asm_test_set_band
 static void test_load_S(asm_handle* h, const double* S, int64_t N) {
     test_alloc(h, N, 16);
-    FacBuf* f = &h->main_fac;
+    FacBuf* f = &h->sk->main_fac;
     if (h->test_layout == 1) {
-        h->test_fac = FacBuf();
-        ns_alloc_factor(h, h->mem, h->test_fac, N, h->test_band_hint);
+        ns_alloc_factor(h, h->sk->mem, h->sk->test_fac, N, h->test_band_hint);
         HIPCHK(asmb::sync(h->stream));          // (the buffers are cleared on the stream)
-        f = &h->test_fac;
+        f = &h->sk->test_fac;
     }
     f->band = h->test_band;
     for (int64_t i = 0; i < N; ++i)
@@ -6012,7 +6011,7 @@ static void test_load_S(asm_handle* h, const double* S, int64_t N) {
 }
 // factorisation of the loaded matrix with the hooks' guard settings, in the buffers it was loaded into; returns that factor
 static const FacBuf& test_factor(asm_handle* h, Dev& d, int64_t N) {
-    const FacBuf& f = h->test_layout == 1 ? h->test_fac : h->main_fac;
+    const FacBuf& f = h->test_layout == 1 ? h->sk->test_fac : h->sk->main_fac;
     d.diag_prepare(f, (int)N, h->test_mode, h->test_rel, h->test_abs);
     d.chol(f, (int)N, h->test_thr);
     return f;
@@ -6064,7 +6063,7 @@ int asm_test_panel_timeout(asm_handle* h, int workgroups) {
         test_alloc(h, 64, 16);
         h->panel_epoch += 1;
         if (h->panel_epoch == 0) h->panel_epoch = 1;
-        asmb::launch(k_pnl_wait_probe, dim3((unsigned)workgroups), dim3(256), h->stream, h->d_pflags, h->panel_epoch, h->d_ptmo);
+        asmb::launch(k_pnl_wait_probe, dim3((unsigned)workgroups), dim3(256), h->stream, h->sk->d_pflags, h->panel_epoch, h->sk->d_ptmo);
         HIPCHK(asmb::sync(h->stream));
         check_panel_timeout(h);
     });
@@ -6129,9 +6128,9 @@ int asm_test_gemv(asm_handle* h, const double* A, int64_t M, int64_t K, const do
         test_alloc(h, M, K);
         Dev d(h);
         for (int64_t i = 0; i < M; ++i)
-            HIPCHK(asmb::copy(h->d_Ah + i * h->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
-        d.gemv_n(h->d_Ah, x, Ax);
-        d.gemv_t(h->d_Ah, y, ATy);
+            HIPCHK(asmb::copy(h->sk->d_Ah + i * h->sk->ldn, A + i * K, K * sizeof(double), hipMemcpyHostToDevice));
+        d.gemv_n(h->sk->d_Ah, x, Ax);
+        d.gemv_t(h->sk->d_Ah, y, ATy);
         d.resolve_timing();
     });
 }
@@ -6165,14 +6164,14 @@ int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tfl
 
 int asm_test_assemble(asm_handle* h, const double* dE, double* J_out) {
     return guarded(h, [&] {
-        if (!h->setup_done) throw std::logic_error("setup first");
-        HIPCHK(asmb::copy(h->d_dE, dE, h->nnz * sizeof(double), hipMemcpyHostToDevice));
-        h->J_valid = false;
+        Skeleton& K = sk_of(h, "setup first");
+        HIPCHK(asmb::copy(K.d_dE, dE, K.nnz * sizeof(double), hipMemcpyHostToDevice));
+        K.J_valid = false;
         Dev d(h);
         d.assemble();
         HIPCHK(asmb::sync(h->stream));
-        for (int64_t i = 0; i < h->M; ++i)
-            HIPCHK(asmb::copy(J_out + i * h->n, h->d_J + i * h->ldn, h->n * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < K.M; ++i)
+            HIPCHK(asmb::copy(J_out + i * K.n, K.d_J + i * K.ldn, K.n * sizeof(double), hipMemcpyDeviceToHost));
         d.resolve_timing();
     });
 }
@@ -6213,7 +6212,7 @@ struct SlpRun {
     int iter = 1, ret = -5, lp_solves = 0, fr_solves = 0;
     asm_slp_result* res;
 
-    SlpRun(asm_handle* hh, const asm_slp_params& par, asm_slp_result* r) : h(hh), o(par), n(hh->n), m(hh->m), res(r) {
+    SlpRun(asm_handle* hh, const asm_slp_params& par, asm_slp_result* r) : h(hh), o(par), n(hh->sk->n), m(hh->sk->m), res(r) {
         x.assign(n, 0.0); p.assign(n, 0.0); lam.assign(m, 0.0); mU.assign(n, 0.0); mL.assign(n, 0.0);
         ps.assign(2 * std::max<int64_t>(m, 1), 0.0); df.assign(n, 0.0); E.assign(std::max<int64_t>(m, 1), 0.0); nu.assign(m, 0.0);
     }
@@ -6255,7 +6254,7 @@ struct SlpRunLS : SlpRun {
     using SlpRun::SlpRun;
 
     void run(const double* x0) {
-        clamp_start(n, x0, h->v_lb.data(), h->v_ub.data(), x.data());       // slp_line_search.jl:96-104
+        clamp_start(n, x0, h->sk->v_lb.data(), h->sk->v_ub.data(), x.data());       // slp_line_search.jl:96-104
         while (true) {
             if (o.max_lp_solves > 0 && lp_solves >= o.max_lp_solves) break;
             asmb::next_cycle();
@@ -6375,7 +6374,7 @@ struct SlpRunTR : SlpRun {
     }
 
     void run(const double* x0) {
-        clamp_start(n, x0, h->v_lb.data(), h->v_ub.data(), x.data());       // slp_trust_region.jl:104-114
+        clamp_start(n, x0, h->sk->v_lb.data(), h->sk->v_ub.data(), x.data());       // slp_trust_region.jl:104-114
         while (true) {
             if (o.max_lp_solves > 0 && lp_solves >= o.max_lp_solves) break;
             asmb::next_cycle();
@@ -6390,8 +6389,8 @@ struct SlpRunTR : SlpRun {
                 double fc = 0.0, v1 = 0.0;
                 vec Ec(std::max<int64_t>(m, 1));
                 do_eval_constraints(h, x.data(), &fc, Ec.data());
-                for (int64_t i = 0; i < m; ++i) v1 += std::max(0.0, std::max(Ec[i] - h->c_ub[i], h->c_lb[i] - Ec[i]));
-                for (int64_t j = 0; j < n; ++j) v1 += std::max(0.0, std::max(x[j] - h->v_ub[j], h->v_lb[j] - x[j]));
+                for (int64_t i = 0; i < m; ++i) v1 += std::max(0.0, std::max(Ec[i] - h->sk->c_ub[i], h->sk->c_lb[i] - Ec[i]));
+                for (int64_t j = 0; j < n; ++j) v1 += std::max(0.0, std::max(x[j] - h->sk->v_ub[j], h->sk->v_lb[j] - x[j]));
                 if (v1 <= o.tol_infeas) ret = 6;
                 break;
             }
@@ -6443,11 +6442,11 @@ struct SlpRunEQP : SlpRunTR {
     }
 
     void second_order_step() override {
-        // A. outside restoration, after a normal-phase LP that ended OPTIMAL (its active set is the handle's h->last)
-        if (fr || lp_solves == 0 || lp_status != ASM_OPTIMAL || lp_fr || !h->last.valid || !e.enabled) return;
+        // A. outside restoration, after a normal-phase LP that ended OPTIMAL (its active set is the handle's h->sk->last)
+        if (fr || lp_solves == 0 || lp_status != ASM_OPTIMAL || lp_fr || !h->sk->last.valid || !e.enabled) return;
         eq.attempts += 1;
         asm_eqp_info t;
-        const std::vector<int32_t> lp_rows(h->last.rowst.begin(), h->last.rowst.end()), lp_bnd(h->last.bst.begin(), h->last.bst.end());      // (as asm_sublp_active_set)
+        const std::vector<int32_t> lp_rows(h->sk->last.rowst.begin(), h->sk->last.rowst.end()), lp_bnd(h->sk->last.bst.begin(), h->sk->last.bst.end());      // (as asm_sublp_active_set)
         do_eqp_trial(h, x.data(), lam.data(), lp_rows.data(), lp_bnd.data(), eq.radius, nu.data(), e.tol_active, nullptr, d.data(), lam_t.data(), mU_t.data(),
                      mL_t.data(), rs.data(), bs.data(), &t);                                            // B to F
         if (t.skipped) {
@@ -6720,6 +6719,7 @@ int asm_batch_setup(asm_batch* b, int64_t n, int64_t m, int64_t nnz, const int64
                     const double* v_lb, const double* v_ub) {
     return guarded(b, [&] {
         batch_hs_drop(b);
+        b->setup_done = false;      // while it holds every slot has a skeleton: the entries read slot 0's dimensions behind it
         for (size_t s = 0; s < b->slots.size(); ++s)
             in_slot("asm_sublp_setup", (int)s, [&] { do_setup(b->slots[s], n, m, nnz, j_row, j_col, c_lb, c_ub, v_lb, v_ub); });
         b->J_ref.clear();
@@ -6779,7 +6779,7 @@ int asm_batch_sublp_solve(asm_batch* b, int count, const double* c_lb, const dou
         if (!b->setup_done) throw std::logic_error("asm_batch_sublp_solve: asm_batch_setup first");
         if (count < 1 || count > (int)b->slots.size() || !dE || !df || !f || !x_k || !delta || !feasibility || !p || !mult_x_U || !mult_x_L || !status)
             throw std::invalid_argument("asm_batch_sublp_solve: bad count or null pointer");
-        const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nnz = b->slots[0]->nnz;
+        const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nnz = b->slots[0]->sk->nnz;
         if (m > 0 && (!E || !lambda || !p_slack)) throw std::invalid_argument("asm_batch_sublp_solve: null pointer");
         check_scen(b, count, "asm_batch_sublp_solve");
         HIPCHK(hipSetDevice(b->device));
@@ -6803,7 +6803,7 @@ namespace {
 template <class RunOne>
 void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
                     const double* x0, asm_slp_result* res, RunOne&& run_one) {
-    const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+    const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m;
     HIPCHK(hipSetDevice(b->device));
     if (b->J_ref.empty()) {
         // reference selection of the null-space basis columns: one LP of scenario 0 at its start point on slot 0 (cold selection); EVERY
@@ -6812,7 +6812,7 @@ void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double
         in_slot(step, 0, [&] {
             do_set_bounds(h0, c_lb, c_ub, v_lb, v_ub);
             batch_scenario_data(b, h0, 0);
-            h0->hint[0].ns_J.clear();
+            h0->sk->hint[0].ns_J.clear();
             vec xs(n), dfs(n), Es(std::max<int64_t>(m, 1)), pp(n), ll(std::max<int64_t>(m, 1)), uu(n), lo(n), sl(2 * std::max<int64_t>(m, 1));
             clamp_start(n, x0, v_lb, v_ub, xs.data());
             double f0 = 0.0;
@@ -6820,7 +6820,7 @@ void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double
             do_eval_functions(h0, xs.data(), &f0, dfs.data(), Es.data());
             do_solve(h0, 1000.0, 0, pp.data(), ll.data(), uu.data(), lo.data(), sl.data(), &st0);
         });
-        b->J_ref = h0->hint[0].ns_J;
+        b->J_ref = h0->sk->hint[0].ns_J;
     }
     const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
     std::atomic<int64_t> next{0};
@@ -6832,8 +6832,8 @@ void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double
             do_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n);
             batch_scenario_data(b, h, sc);
             // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
-            if (!b->J_ref.empty()) h->hint[0].ns_J = b->J_ref;
-            else h->hint[0].ns_J.clear();
+            if (!b->J_ref.empty()) h->sk->hint[0].ns_J = b->J_ref;
+            else h->sk->hint[0].ns_J.clear();
             run_one(h, sc);
             res[sc].slot = s;
         }
@@ -6850,7 +6850,7 @@ int asm_batch_slp_run(asm_batch* b, int64_t n_scen, const double* c_lb, const do
         if (!b->setup_done) throw std::logic_error("asm_batch_slp_run: asm_batch_setup first");
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run: bad argument");
         check_scen(b, n_scen, "asm_batch_slp_run");
-        const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+        const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m;
         batch_slp_runs(b, "asm_slp_run", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_ls(h, par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
                        mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc);
@@ -6867,7 +6867,7 @@ int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const
         if (n_scen < 1 || !c_lb || !c_ub || !v_lb || !v_ub || !x0 || !par || !res) throw std::invalid_argument("asm_batch_slp_run_tr: bad argument");
         check_tr_size(tr_size, "asm_batch_slp_run_tr");
         check_scen(b, n_scen, "asm_batch_slp_run_tr");
-        const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+        const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m;
         batch_slp_runs(b, "asm_slp_run_tr", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_tr(h, par, tr_size, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
                        mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc, tr ? tr + sc : nullptr);
@@ -6881,7 +6881,7 @@ int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const
         if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error("asm_batch_data_gradient: asm_batch_eval_setup first");
         if (b->slots[0]->ev->nlp_kind != ASM_NLP_EXPR)
             throw std::invalid_argument("asm_batch_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
-        const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nd = (int64_t)b->dpar0.size();
+        const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = (int64_t)b->dpar0.size();
         if (n_scen < 1 || !x || (m > 0 && !lambda) || (nd > 0 && !out)) throw std::invalid_argument("asm_batch_data_gradient: bad argument");
         check_scen(b, n_scen, "asm_batch_data_gradient");
         HIPCHK(hipSetDevice(b->device));
@@ -6929,7 +6929,7 @@ void batch_kkt_prepare(asm_batch* b, int count) {
 // its first scenario (a slot that a per-handle call prepared keeps its own lists: same pattern, same bits)
 void batch_hessians(asm_batch* b, const char* who, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, const double* v,
                     double* out) {
-    const int64_t n = b->slots[0]->n, m = b->slots[0]->m, nnz = b->hs->nnz(), len = v ? n : nnz;
+    const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nnz = b->hs->nnz(), len = v ? n : nnz;
     check_scen(b, n_scen, who);
     HIPCHK(hipSetDevice(b->device));
     std::atomic<int64_t> next{0};
@@ -6961,7 +6961,7 @@ int asm_batch_hessian_structure(asm_batch* b, int64_t* nnz, int64_t* rows, int64
 int asm_batch_hessian_lagrangian(asm_batch* b, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, double* values) {
     return guarded(b, [&] {
         batch_hs_prepare(b, "asm_batch_hessian_lagrangian");
-        if (n_scen < 1 || !x || (b->slots[0]->m > 0 && !lambda) || (b->hs->nnz() > 0 && !values))
+        if (n_scen < 1 || !x || (b->slots[0]->sk->m > 0 && !lambda) || (b->hs->nnz() > 0 && !values))
             throw std::invalid_argument("asm_batch_hessian_lagrangian: no scenario or a null pointer");
         batch_hessians(b, "asm_batch_hessian_lagrangian", n_scen, x, obj_factor, lambda, nullptr, values);
     });
@@ -6970,7 +6970,7 @@ int asm_batch_hessian_lagrangian(asm_batch* b, int64_t n_scen, const double* x, 
 int asm_batch_hessian_product(asm_batch* b, int64_t n_scen, const double* x, const double* obj_factor, const double* lambda, const double* v, double* out) {
     return guarded(b, [&] {
         batch_hs_prepare(b, "asm_batch_hessian_product");
-        if (n_scen < 1 || !x || !v || !out || (b->slots[0]->m > 0 && !lambda)) throw std::invalid_argument("asm_batch_hessian_product: no scenario or a null pointer");
+        if (n_scen < 1 || !x || !v || !out || (b->slots[0]->sk->m > 0 && !lambda)) throw std::invalid_argument("asm_batch_hessian_product: no scenario or a null pointer");
         batch_hessians(b, "asm_batch_hessian_product", n_scen, x, obj_factor, lambda, v, out);
     });
 }
@@ -6989,7 +6989,7 @@ int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, cons
         batch_hs_prepare(b, "asm_batch_slp_run_eqp");
         HIPCHK(hipSetDevice(b->device));
         if (eqp_par->enabled) batch_kkt_prepare(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()));
-        const int64_t n = b->slots[0]->n, m = b->slots[0]->m;
+        const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m;
         // (asm_sublp_set_bounds at every scenario start forgets the slot's retained active sets and hints: no history for the step to read)
         batch_slp_runs(b, "asm_slp_run_eqp", n_scen, c_lb, c_ub, v_lb, v_ub, x0, res, [&](asm_handle* h, int64_t sc) {
             slp_run_eqp(h, par, tr_size, eqp_par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests.util import random_subproblem, equality_rich_subproblem
+from tests.util import abi_create as _create, abi_setup as _setup, abi_set_bounds as _set_bounds, abi_solve as _solve
 
 pytestmark = pytest.mark.gpu
 
@@ -23,44 +24,6 @@ def _small(seed):
 
 def _dense():
     return random_subproblem(7, 96, 48)
-
-
-def _create(lib):
-    h = C.c_void_p()
-    assert lib.asm_create(0, C.byref(h)) == 0
-    return h
-
-
-def _setup(lib, h, sp):
-    from activesetmethods_amd import _lib
-    jr, jc = (np.ascontiguousarray(sp[k], dtype=np.int64) for k in ('j_row', 'j_col'))
-    b = [np.ascontiguousarray(sp[k], dtype=np.float64) for k in ('c_lb', 'c_ub', 'v_lb', 'v_ub')]
-    return lib.asm_sublp_setup(h, sp['n'], sp['m'], len(jr), _lib.i64ptr(jr), _lib.i64ptr(jc), *[_lib.dptr(a) for a in b])
-
-
-def _set_bounds(lib, h, sp):
-    from activesetmethods_amd import _lib
-    b = [np.ascontiguousarray(sp[k], dtype=np.float64) for k in ('c_lb', 'c_ub', 'v_lb', 'v_ub')]
-    return lib.asm_sublp_set_bounds(h, *[_lib.dptr(a) for a in b])
-
-
-def _solve(lib, h, sp, feasibility=0):
-    """One LP on a set-up handle: (the raw bytes of status, step, multipliers, slacks and active sets - outputs are zero-initialised, so
-    entries the library leaves alone compare equal -, the statistics of the solve)."""
-    from activesetmethods_amd import _lib
-    n, m = sp['n'], sp['m']
-    dE, df, E, x_k = (np.ascontiguousarray(sp[k], dtype=np.float64) for k in ('dE', 'df', 'E', 'x_k'))
-    p, lam, mU, mL, ps = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(n), np.zeros(2 * max(m, 1))
-    st = C.c_int32(0)
-    assert lib.asm_sublp_solve(h, _lib.dptr(dE), _lib.dptr(df), float(sp['f']), _lib.dptr(E), _lib.dptr(x_k), float(sp['delta']), feasibility,
-                               _lib.dptr(p), _lib.dptr(lam), _lib.dptr(mU), _lib.dptr(mL), _lib.dptr(ps), C.byref(st)) == 0
-    nr, nsl = C.c_int64(0), C.c_int64(0)
-    assert lib.asm_sublp_active_set(h, None, None, None, C.byref(nr), C.byref(nsl)) == 0
-    rows, bnd, sl = np.zeros(max(nr.value, 1), np.int32), np.zeros(n, np.int32), np.zeros(max(nsl.value, 1), np.int32)
-    assert lib.asm_sublp_active_set(h, _lib.i32ptr(rows), _lib.i32ptr(bnd), _lib.i32ptr(sl), None, None) == 0
-    s = _lib.SolveStats()
-    assert lib.asm_sublp_last_stats(h, C.byref(s)) == 0
-    return [st.value] + [a.tobytes() for a in (p, lam, mU, mL, ps, rows, bnd, sl)], {k: getattr(s, k) for k, _ in s._fields_}
 
 
 def _stretch(lib, h, sp, capable):
