@@ -460,6 +460,8 @@ struct HandleKnobs {
     bool spin_read = true;          // ASM_HIP_SPIN=0: asmb::copy_async + asmb::sync instead (14.5 us per read-back instead of 6.7 us)
     int panel_wgs = 0;              // ASM_PANEL_WGS: grid bound of the panel kernels on the whole device (0: by the device's CU count)
     bool ns_defer = true;           // ASM_NS_DEFER=0: the step of a null-space iteration is taken on the host
+    bool ns_side = true;            // ASM_NS_SIDE=0: the factor-independent head of a null-space iteration stays on the handle's stream (Solver::ns_iter_setup)
+    bool ns_fold = true;            // ASM_NS_FOLD=0: k_ns_add and k_ns_dp of a null-space Newton solve are launches of their own (k above ASM_SMALL_USE)
     double ns_rerr = NS_RERR;       // ASM_NS_RERR: accuracy bound of the reduced solves of a null-space iteration (test knob - a tiny bound
                                     // sends every LP through the fall-back to the row form)
 };
@@ -470,6 +472,8 @@ HandleKnobs read_knobs() {
     if (const char* v = std::getenv("ASM_HIP_SPIN")) k.spin_read = v[0] != '0';
     if (const char* v = std::getenv("ASM_PANEL_WGS")) k.panel_wgs = std::max(1, std::atoi(v));
     if (const char* v = std::getenv("ASM_NS_DEFER")) k.ns_defer = v[0] != '0';
+    if (const char* v = std::getenv("ASM_NS_SIDE")) k.ns_side = v[0] != '0';
+    if (const char* v = std::getenv("ASM_NS_FOLD")) k.ns_fold = v[0] != '0';
     if (const char* v = std::getenv("ASM_NS_RERR")) k.ns_rerr = std::atof(v);
     return k;
 }
@@ -583,6 +587,10 @@ struct asm_handle {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;  // look-ahead stream of the Cholesky (next panel's block chain runs beside the trailing update)
     std::vector<hipEvent_t> la_events;
+    // side stream of the null-space iterations (default priority): the launches that do not depend on the k x k factor run beside its build and
+    // factorisation (Solver::ns_iter_setup); fork / join events, made with the first fork
+    hipStream_t stream_ns = nullptr;
+    hipEvent_t ns_fork = nullptr, ns_join = nullptr;
     std::string err;
     // owners of the device / pinned buffers, one per lifetime: the LP skeleton with the null-space form inside it (until the next set-up; null:
     // no set-up yet, or the last one failed), the device evaluator (until the next asm_eval_setup or set-up; null: none).  What follows
@@ -991,6 +999,27 @@ struct Dev {
         solve_launches(f, Ms, out_dev, one_block ? rhs_dev : out_dev);
         end(id);
     }
+    // dd = (L L')^-1 rhs and du += dd (the refinement sweep of a null-space reduced solve).  A system of one wide block adds in its backward
+    // diagonal product (k_wtrsv_bwd_diag_add: the lane that stores dd[i] also stores du[i] + dd[i]); every other system, and every system with
+    // ASM_NS_FOLD=0, is chol_solve_dev followed by k_ns_add - the same values either way
+    void chol_solve_add_dev(const FacBuf& f, const double* rhs_dev, double* dd_dev, double* du_dev, int Ms) {
+        const bool small = f.small && Ms <= ASM_SMALL_USE;
+        if (!h->knobs.ns_fold || small || Ms > f.wb) {
+            chol_solve_dev(f, rhs_dev, dd_dev, Ms);
+            asmb::launch(k_ns_add, asmb::blocks(Ms), dim3(256), h->stream, du_dev, dd_dev, du_dev, (int64_t)Ms);
+            return;
+        }
+        int id = begin(ASM_K_TRSV, 2.0 * Ms * (double)Ms, 8.0 * Ms * (double)Ms);
+        double* z = sk().d_vecM;
+        if (f.wb == 1024) {
+            asmb::launch((k_wtrsv_fwd_diag<1024>), dim3(1024 / 4), dim3(256), h->stream, f.Binv, 0, Ms, rhs_dev, z);
+            asmb::launch((k_wtrsv_bwd_diag_add<1024>), dim3(1024 / 4), dim3(256), h->stream, f.BinvT, 0, Ms, z, dd_dev, Ms, du_dev);
+        } else {
+            asmb::launch((k_wtrsv_fwd_diag<512>), dim3(512 / 4), dim3(256), h->stream, f.Binv, 0, Ms, rhs_dev, z);
+            asmb::launch((k_wtrsv_bwd_diag_add<512>), dim3(512 / 4), dim3(256), h->stream, f.BinvT, 0, Ms, z, dd_dev, Ms, du_dev);
+        }
+        end(id);
+    }
 
     static int pick_tile(int64_t Ms) { return Ms >= 3072 ? 4 : (Ms >= 768 ? 2 : 1); }
 
@@ -1360,13 +1389,15 @@ unsigned pub_next(asm_handle* h) {
 
 struct Solver {
     // out = A x for a k x ncols matrix of few, long rows (the basis Zt): one workgroup per row when that fills the chip better
-    unsigned gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols) {
+    // (`on`: the stream of the launch; null: the handle's)
+    unsigned gemv_rows(const double* A, int64_t ld, const double* x, double* out, int64_t rows, int64_t ncols, hipStream_t on = nullptr) {
+        if (!on) on = h->stream;
         if (rows <= 2048 && ncols >= 2048) {
-            asmb::launch(k_gemv_n_wide, dim3((unsigned)rows), dim3(256), h->stream, A, ld, x, out, rows, ncols);
+            asmb::launch(k_gemv_n_wide, dim3((unsigned)rows), dim3(256), on, A, ld, x, out, rows, ncols);
             return (unsigned)rows;
         }
         const dim3 g = asmb::blocks(rows, 4);
-        asmb::launch(k_gemv_n, g, dim3(256), h->stream, A, ld, x, out, rows, ncols);
+        asmb::launch(k_gemv_n, g, dim3(256), on, A, ld, x, out, rows, ncols);
         return g.x;
     }
     // workgroups of the interior-point reductions (k_ipm_measures / _steps / _muaff): 1024 elements per workgroup and sweep, at most IPM_RED_MAXWG
@@ -1964,7 +1995,7 @@ struct Solver {
     }
     unsigned launch_ns_dinf(const double* zr, int k, unsigned pub) { asmb::launch(k_ns_dinf, dim3(1), dim3(1024), h->stream, P, zr, k, pub); return 1; }
     // out[k] = Zt x   (x of ldn entries)
-    unsigned launch_ns_zt(const double* x, double* out, int k) { const NsArena& a = nsa(); return gemv_rows((const double*)a.G, a.L.ldg, x, out, (int64_t)k, a.L.ldn); }
+    unsigned launch_ns_zt(const double* x, double* out, int k, hipStream_t on = nullptr) { const NsArena& a = nsa(); return gemv_rows((const double*)a.G, a.L.ldg, x, out, (int64_t)k, a.L.ldn, on); }
     unsigned launch_ns_e0(const double* pbar, double* d0) {
         const NsArena& a = nsa();
         const unsigned gN = (unsigned)((a.L.ldn + 255) / 256);
@@ -1978,29 +2009,29 @@ struct Solver {
         return gN;
     }
     // dpbar = -e, SC_NSERR = 0, yM = D_I^-1 (Ah dpbar)
-    unsigned launch_ns_spmvn_wm_neg(const double* vals) {
+    unsigned launch_ns_spmvn_wm_neg(const double* vals, hipStream_t on = nullptr) {
         const NsArena& a = nsa();
         const unsigned gM = (unsigned)((lp.M + 255) / 256), gN = (unsigned)((a.L.ldn + 255) / 256), g = std::max(gM, gN);
-        asmb::launch(k_ns_spmvn_wm_neg, dim3(g), dim3(256), h->stream, a.sp_ptr, a.sp_col, vals, nsv(14), nsv(0), a.L.ldn, P.scal + SC_NSERR, a.X, (const double*)(a.th + a.L.ldn), nsv(5), lp.M);
+        asmb::launch(k_ns_spmvn_wm_neg, dim3(g), dim3(256), on ? on : h->stream, a.sp_ptr, a.sp_col, vals, nsv(14), nsv(0), a.L.ldn, P.scal + SC_NSERR, a.X, (const double*)(a.th + a.L.ldn), nsv(5), lp.M);
         return g;
     }
     // K dpbar = Th dpbar + Ah' yM
-    unsigned launch_ns_spmvt_kx(const double* vals) {
+    unsigned launch_ns_spmvt_kx(const double* vals, hipStream_t on = nullptr) {
         const NsArena& a = nsa();
         const dim3 g = asmb::blocks(a.L.ldn * 8);
-        asmb::launch(k_ns_spmvt_kx, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, nsv(0), nsv(1), lp.n, a.L.ldn);
+        asmb::launch(k_ns_spmvt_kx, g, dim3(256), on ? on : h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, nsv(0), nsv(1), lp.n, a.L.ldn);
         return g.x;
     }
-    unsigned launch_ns_rhs1_bi(const IpmDir& base, int mode, double res) {
+    unsigned launch_ns_rhs1_bi(const IpmDir& base, int mode, double res, hipStream_t on = nullptr) {
         const NsArena& a = nsa();
         const unsigned g = grid_all();
-        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), h->stream, P, base, mode, a.X, (const double*)(a.th + a.L.ldn), res, nsv(7), nsv(5));
+        asmb::launch(k_ns_rhs1_bi, dim3(g), dim3(256), on ? on : h->stream, P, base, mode, a.X, (const double*)(a.th + a.L.ldn), res, nsv(7), nsv(5));
         return g;
     }
-    unsigned launch_ns_spmvt_ht(const double* vals, double res) {
+    unsigned launch_ns_spmvt_ht(const double* vals, double res, hipStream_t on = nullptr) {
         const NsArena& a = nsa();
         const dim3 g = asmb::blocks(a.L.ldn * 8);
-        asmb::launch(k_ns_spmvt_ht, g, dim3(256), h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, P.hp, nsv(1), res, nsv(2), nsv(3), lp.n, a.L.ldn);
+        asmb::launch(k_ns_spmvt_ht, g, dim3(256), on ? on : h->stream, a.sc_ptr, a.sc_row, a.sc_pos, vals, nsv(5), (const double*)a.th, P.hp, nsv(1), res, nsv(2), nsv(3), lp.n, a.L.ldn);
         return g.x;
     }
     unsigned launch_ns_reduced_solve(int k, const double* ru, double* du) {
@@ -2068,17 +2099,44 @@ struct Solver {
         const int64_t ntile = ((k + 32 * T - 1) / (32 * T));
         int nsplit = (int)std::min<int64_t>(NS_MAX_SPLIT, std::max<int64_t>(1, 1224 / std::max<int64_t>(1, ntile * (ntile + 1) / 2)));
         nsplit = (int)std::min<int64_t>(nsplit, std::max<int64_t>(1, F.L.ldg / 512));
+        // The head of the iteration - dpbar, K dpbar and the affine solve's right-hand sides down to ru - reads the iterate, theta~ and the sparse
+        // values only and writes work vectors 0, 1, 2, 3, 5, 7, 10, the complementarity right-hand sides and SC_NSERR; the build and the
+        // factorisation write Np, the factor with its inverses, N0, d_diag0 and the panel flags.  Nothing is shared: the head runs on the side
+        // stream beside them (the chip is nearly empty during the factorisation) and ns_newton(0) joins it before its first reduced solve.
+        // Not in a scenario batch (a slot records for one stream) and not under family timing (events of one stream).
+        ns_head_side = h->knobs.ns_side && h->stream_ns && !h->batch_slot && !asmb::in_fiber() && h->timing != 2;
+        const double* vals = ns_vals();
+        if (ns_head_side) {
+            ns_split_e_once(k);      // (e is read by the head)
+            if (!h->ns_fork) {
+                HIPCHK(hipEventCreateWithFlags(&h->ns_fork, hipEventDisableTiming));
+                HIPCHK(hipEventCreateWithFlags(&h->ns_join, hipEventDisableTiming));
+            }
+            HIPCHK(hipEventRecord(h->ns_fork, h->stream));
+        }
         dev.ns_newton_matrix(K.G, F.L.ldg, F.th, k, nsplit, K.Np, K.fN, K.N0, sk().d_diag0, 1e-13, 1e-30);
         dev.chol(K.fN, k, 1e-14, false);
-        // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
-        if (!ip.ns_e_ready) {
-            ip.ns_e_ready = true;
-            ns_split_e(k, nsq().pbar);
+        if (ns_head_side) {
+            // issued AFTER the build and the factorisation: behind a read-back the device follows the host launch by launch, and five launches
+            // issued first kept the build waiting for the host (traced: k_syrk started 57 us after k_ipm_theta_ns instead of 6)
+            HIPCHK(hipStreamWaitEvent(h->stream_ns, h->ns_fork, 0));
+            launch_ns_spmvn_wm_neg(vals, h->stream_ns);
+            launch_ns_spmvt_kx(vals, h->stream_ns);
+            ns_newton_head(0, dirA, vals, h->stream_ns);
+            HIPCHK(hipEventRecord(h->ns_join, h->stream_ns));
+            return;
         }
+        ns_split_e_once(k);
         // (fused launches: negation + clearing of the residual measure; sparse product + its row- / column-wise kernel)
-        const double* vals = ns_vals();
         launch_ns_spmvn_wm_neg(vals);
         launch_ns_spmvt_kx(vals);
+    }
+    bool ns_head_side = false;      // this iteration's head went to the side stream: ns_newton(0) joins it instead of launching its own
+    // dpbar = -e: the component of the iterate outside pbar + null(A_EF), split off once per LP and shrunk by (1 - a) with every step
+    void ns_split_e_once(int k) {
+        if (ip.ns_e_ready) return;
+        ip.ns_e_ready = true;
+        ns_split_e(k, nsq().pbar);
     }
     // e = (I - Z Zt) Fm (p - pbar)  (work vectors: d0 = 2, Z Zt d0 = 3, Zt d0 = 12, e = 14)
     void ns_split_e(int k, const double* pbar) {
@@ -2091,16 +2149,23 @@ struct Solver {
     // One Newton solve in null-space form (oracle: IPM.run, solve_ns): mode 0 affine, 1 Mehrotra corrector on `base`.  The relative residual of
     // the reduced solve (after its refinement sweep) is accumulated in SC_NSERR.
     // Work vectors: dpbar = 0, K dpbar = 1, h~ = 2, v = 3, yM = 5, bI = 7, ru = 10, du = 11, rr = 12, dd = 13.
-    void ns_newton(int mode, const IpmDir& base, IpmDir& D) {
+    // head_issued: ns_iter_setup has put the three launches of the head (ns_newton_head) on the side stream - the handle's stream waits for them here
+    void ns_newton(int mode, const IpmDir& base, IpmDir& D, bool head_issued = false) {
         const int k = ip.ns_k;
         const double res = 1.0;
         const double* vals = ns_vals();
-        launch_ns_rhs1_bi(base, mode, res);
-        launch_ns_spmvt_ht(vals, res);
-        launch_ns_zt(nsv(3), nsv(10), k);
+        if (head_issued) HIPCHK(hipStreamWaitEvent(h->stream, h->ns_join, 0));
+        else ns_newton_head(mode, base, vals, nullptr);
         ns_reduced_solve(k);
         ns_direction(k, D, res);
         launch_ns_spmvn_rows(vals, D);
+    }
+    // the right-hand sides of a Newton solve down to ru = Zt v: nothing here reads the factor (`on`: the stream of the launches; null: the handle's)
+    void ns_newton_head(int mode, const IpmDir& base, const double* vals, hipStream_t on) {
+        const double res = 1.0;
+        launch_ns_rhs1_bi(base, mode, res, on);
+        launch_ns_spmvt_ht(vals, res, on);
+        launch_ns_zt(nsv(3), nsv(10), ip.ns_k, on);
     }
     // du = N^-1 ru with one refinement sweep on the unregularised N0; SC_NSERR = max(SC_NSERR, relative residual)
     unsigned ns_reduced_solve(int k) {
@@ -2110,8 +2175,7 @@ struct Solver {
         const FacBuf& fN = *nsa().fN;
         dev.chol_solve_dev(fN, ru, du, k);
         const unsigned g = launch_ns_symv_res(k, du, ru, rr);
-        dev.chol_solve_dev(fN, rr, dd, k);
-        launch_ns_add(du, dd, du, (int64_t)k);
+        dev.chol_solve_add_dev(fN, rr, dd, du, k);      // dd = N^-1 rr, du += dd
         launch_ns_symv_res(k, du, ru, rr);
         launch_ns_relres(rr, ru, k);
         return g;
@@ -2120,11 +2184,13 @@ struct Solver {
     unsigned ns_direction(int k, const IpmDir& D, double res) {
         double *v = nsv(3), *du = nsv(11);
         if (k <= ASM_SMALL_USE) return launch_ns_gemv_t_small_dp(k, du, D, res);
+        if (h->knobs.ns_fold) return ns_gemv_t_dense(du, k, v, &D, res);      // k_ns_dp inside the second stage of the product
         ns_gemv_t_dense(du, k, v);
         return launch_ns_dp(D, res, v);
     }
-    // out[n] = Zt' u   (Zt dense, k rows of pitch ldg)
-    unsigned ns_gemv_t_dense(const double* u, int k, double* out) {
+    // out[n] = Zt' u   (Zt dense, k rows of pitch ldg).  dp_of != null (k above ASM_SMALL_USE): the second stage also forms that direction's dp
+    // and bound multipliers from its sums (k_gemv_t_stage2_dp, on launch_ns_dp's grid - the grid returned)
+    unsigned ns_gemv_t_dense(const double* u, int k, double* out, const IpmDir* dp_of = nullptr, double res = 1.0) {
         const NsArena& a = nsa();
         if (k <= ASM_SMALL_USE) {
             const dim3 g = asmb::blocks(a.L.ldn);
@@ -2136,6 +2202,10 @@ struct Solver {
         R = (k + chunk - 1) / chunk;
         const unsigned gx = (unsigned)((a.L.ldn + 255) / 256);
         asmb::launch(k_gemv_t_stage1, dim3(gx, (unsigned)R), dim3(256), h->stream, a.G, a.L.ldg, u, a.partial, (int64_t)k, a.L.ldn, chunk);
+        if (dp_of) {
+            asmb::launch(k_gemv_t_stage2_dp, dim3(gx), dim3(256), h->stream, a.partial, out, R, P, *dp_of, (const double*)a.th, nsv(0), res, a.L.ldn);
+            return gx;
+        }
         asmb::launch(k_gemv_t_stage2, asmb::blocks(a.L.ldn), dim3(256), h->stream, a.partial, out, R, a.L.ldn);
         return gx * (unsigned)R;
     }
@@ -2374,7 +2444,7 @@ struct Solver {
             auto solves = [&](const bool deferred) -> bool {
                 cg_max = 0;
                 cg_fail = false;
-                if (ns) ns_newton(0, dirA, dirA); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
+                if (ns) ns_newton(0, dirA, dirA, ns_head_side); else ipm_solve(0, dirA, dirA, 0.0, 0.0, deferred ? 1 : 0);
                 launch_steps(dirA, 0u);
                 launch_muaff(dirA, IPM_SIG_EXP);
                 if (ns) ns_newton(1, dirA, dirC); else ipm_solve(1, dirA, dirC, 0.0, 0.0, deferred ? 2 : 0);
@@ -3739,7 +3809,10 @@ int asm_create(int device, asm_handle** out) {
     if (!h) return ASM_ERR_ARG;
     h->device = device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess ||
-        hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, -1) != hipSuccess) {   // look-ahead chain: high priority
+        hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, -1) != hipSuccess ||   // look-ahead chain: high priority
+        hipStreamCreateWithFlags(&h->stream_ns, hipStreamNonBlocking) != hipSuccess) {         // side stream of the null-space iterations
+        if (h->stream2) (void)hipStreamDestroy(h->stream2);
+        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return ASM_ERR_HIP;
     }
@@ -3762,11 +3835,15 @@ int asm_destroy(asm_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)asmb::sync(h->stream);
     if (h->stream2) (void)asmb::sync(h->stream2);   // look-ahead chain may still be running after an exception
+    if (h->stream_ns) (void)asmb::sync(h->stream_ns);   // ... and the head of a null-space iteration whose join was never reached
     for (auto& r : h->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
     h->ev.reset(); h->sk.reset();
     for (auto e : h->la_events) (void)hipEventDestroy(e);
+    if (h->ns_fork) (void)hipEventDestroy(h->ns_fork);
+    if (h->ns_join) (void)hipEventDestroy(h->ns_join);
     if (!h->batch_slot) {
+        if (h->stream_ns) (void)hipStreamDestroy(h->stream_ns);
         if (h->stream2) (void)hipStreamDestroy(h->stream2);
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
@@ -6665,9 +6742,10 @@ int asm_batch_create(int device, int n_slots, asm_batch** out) {
         rc = asm_create(device, &h);
         if (rc != ASM_OK) break;
         // the slot's launches are recorded and merged onto its group's stream: no streams of its own, no look-ahead stream, no event timing
+        (void)hipStreamDestroy(h->stream_ns);
         (void)hipStreamDestroy(h->stream2);
         (void)hipStreamDestroy(h->stream);
-        h->stream = nullptr; h->stream2 = nullptr;
+        h->stream = nullptr; h->stream2 = nullptr; h->stream_ns = nullptr;
         h->batch_slot = true;
         h->timing = 0;
         b->slots.push_back(h);

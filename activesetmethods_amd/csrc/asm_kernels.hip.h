@@ -1690,10 +1690,10 @@ __global__ __launch_bounds__(256) void k_wtrsv_bwd_reduce(AsmBt abt, int B, int 
     __syncthreads();
     if (threadIdx.x < 64) t[c] = c < wdt ? z[b0 + c] - ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) : 0.0;
 }
-// x_B = X_B' t  through the transposed block inverse (row c of XT = column c of X): one wavefront per unknown
+// x_B = X_B' t  through the transposed block inverse (row c of XT = column c of X): one wavefront per unknown.  y != null: y_B += x_B as well
+// (k_ns_add on the solution, by the lane that stores it)
 template <int WB>
-__global__ __launch_bounds__(256) void k_wtrsv_bwd_diag(AsmBt abt, const double* __restrict__ BinvT, int B, int Ms, const double* __restrict__ t, double* __restrict__ x, int tlen) {
-    ASM_BARGS(abt, BinvT, B, Ms, t, x, tlen);
+__device__ __forceinline__ void wtrsv_bwd_diag_rows(const double* __restrict__ BinvT, int B, int Ms, const double* __restrict__ t, double* __restrict__ x, int tlen, double* __restrict__ y) {
     const int b0 = B * WB;
     const double* XT = BinvT + (int64_t)B * WB * WB;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1710,7 +1710,21 @@ __global__ __launch_bounds__(256) void k_wtrsv_bwd_diag(AsmBt abt, const double*
 #pragma unroll
     for (int u = 0; u < WB / 64; ++u) acc += v[u];
     acc = wave_sum(acc);
-    if (lane == 0) x[b0 + row] = acc;
+    if (lane == 0) {
+        x[b0 + row] = acc;
+        if (y) y[b0 + row] = y[b0 + row] + acc;
+    }
+}
+template <int WB>
+__global__ __launch_bounds__(256) void k_wtrsv_bwd_diag(AsmBt abt, const double* __restrict__ BinvT, int B, int Ms, const double* __restrict__ t, double* __restrict__ x, int tlen) {
+    ASM_BARGS(abt, BinvT, B, Ms, t, x, tlen);
+    wtrsv_bwd_diag_rows<WB>(BinvT, B, Ms, t, x, tlen, nullptr);
+}
+// the same with y_B += x_B: the refinement sweep of a null-space reduced solve (dd = N^-1 rr, du += dd) without its k_ns_add launch
+template <int WB>
+__global__ __launch_bounds__(256) void k_wtrsv_bwd_diag_add(AsmBt abt, const double* __restrict__ BinvT, int B, int Ms, const double* __restrict__ t, double* __restrict__ x, int tlen, double* __restrict__ y) {
+    ASM_BARGS(abt, BinvT, B, Ms, t, x, tlen, y);
+    wtrsv_bwd_diag_rows<WB>(BinvT, B, Ms, t, x, tlen, y);
 }
 // XT_B = X_B'  (LDS-tiled transpose of every 512 x 512 block inverse)
 template <int WB>

@@ -864,6 +864,25 @@ __global__ __launch_bounds__(256) void k_gemv_t_small_dp(AsmBt abt, const double
     D.dp[t] = dp;
     if (t < P.n) { D.dmuL[t] = dL; D.dmuU[t] = dU; }
 }
+// k_gemv_t_stage2 + k_ns_dp (k above ASM_SMALL_USE): the column sum of the stage-1 partials in k_gemv_t_stage2's order, stored to out as that
+// kernel stores it, then k_ns_dp's statements with zu[t] taken from the register
+__global__ __launch_bounds__(256) void k_gemv_t_stage2_dp(AsmBt abt, const double* __restrict__ partial, double* __restrict__ out, int64_t R, IpmPtrs P, IpmDir D, const double* __restrict__ th,
+                                                          const double* __restrict__ dpb, double res, int64_t ldn) {
+    ASM_BARGS(abt, partial, out, R, P, D, th, dpb, res, ldn);
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ldn) return;
+    double acc = 0.0;
+    for (int64_t r = 0; r < R; ++r) acc += partial[r * ldn + t];
+    out[t] = acc;
+    double dp = 0.0, dL = 0.0, dU = 0.0;
+    if (t < P.n && th[t] != 0.0) {
+        dp = res * dpb[t] + acc;
+        dL = (P.rcL[t] - P.muL[t] * dp) / P.tL[t];
+        dU = (P.rcU[t] + P.muU[t] * dp) / P.tU[t];
+    }
+    D.dp[t] = dp;
+    if (t < P.n) { D.dmuL[t] = dL; D.dmuU[t] = dU; }
+}
 
 // ---- banded S0 = A_EF A_EF' built from its structural pattern (equality rows in reverse Cuthill-McKee order)
 // clears row i, columns [i - w + 1, i] (w covers the band rounded up to the factorisation's tiles; the factor of the previous LP lives there)

@@ -903,8 +903,8 @@ enum {
     ASM_NS_RHS1_BI,           /* k_ns_rhs1_bi; mode, B = base direction, res */
     ASM_NS_HT,                /* k_ns_spmvt_ht; res */
     ASM_NS_RU,                /* gemv_rows: ru = Zt v */
-    ASM_NS_REDUCED_SOLVE,     /* Solver::ns_reduced_solve: k_ns_reduced_solve, or chol_solve_dev / k_ns_symv_res / k_ns_add / k_ns_relres above ASM_SMALL_USE */
-    ASM_NS_DIRECTION,         /* Solver::ns_direction: k_gemv_t_small_dp, or ns_gemv_t_dense + k_ns_dp; D, res */
+    ASM_NS_REDUCED_SOLVE,     /* Solver::ns_reduced_solve: k_ns_reduced_solve, or chol_solve_dev / k_ns_symv_res / chol_solve_add_dev (k_wtrsv_bwd_diag_add) / k_ns_relres above ASM_SMALL_USE */
+    ASM_NS_DIRECTION,         /* Solver::ns_direction: k_gemv_t_small_dp, or k_gemv_t_stage1 + k_gemv_t_stage2_dp; D, res */
     ASM_NS_ROWS,              /* k_ns_spmvn_rows; D */
     ASM_NS_NEWTON,            /* Solver::ns_newton(mode, B, D): the six stages above in one */
     ASM_NS_CHOL_SOLVE,        /* Dev::chol_solve_dev on the factor: x[1] = N^-1 x[0] (k each); k_small_solve up to ASM_SMALL_USE */
