@@ -62,6 +62,11 @@ class NsStage(C.Structure):
                 ("rerr", C.c_double), ("scale", C.c_double), ("val", C.c_double), ("x", C.c_int64 * 4), ("len", C.c_int64)]
 
 
+class NssStage(C.Structure):
+    """asm_nss_stage: one stage of asm_test_ns_setup_stages (include/asm_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("flag", C.c_int32), ("thr", C.c_double)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
@@ -201,6 +206,8 @@ PROTOTYPES = {
                                      C.POINTER(AsStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_ns_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I32, _I32, _I32, _D, _D, _D, _I64, _I32, _D, C.c_int64, _D,
                                      C.POINTER(C.c_uint32), C.POINTER(NsStage), C.c_int64, C.POINTER(C.c_uint32)]),
+    "asm_test_ns_setup_stages": (C.c_int, [_P, _D, _D, C.c_int64, C.c_int64, _I32, _I64, _I32, _D, _D, _D, _D, _D, _D, _D, _D, _D, C.c_int32, _I32, C.c_int64,
+                                           C.POINTER(NssStage), C.c_int64, C.POINTER(C.c_uint32), _I32, _I32]),
     "asm_test_cholesky": (C.c_int, [_P, _D, C.c_int64, _D]),
     "asm_test_chol_solve": (C.c_int, [_P, _D, C.c_int64, _D, _D]),
     "asm_test_no_polish": (C.c_int, [_P, C.c_int]),

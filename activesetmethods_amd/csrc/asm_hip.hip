@@ -1733,36 +1733,89 @@ struct Solver {
     }
     // In place  Zt = L^-1 Zt  with the k x k factor just made in K.fN.  When the factor fits into one wide block the explicit inverse of
     // that block IS L^-1: one transpose + one product on the matrix cores (the rows are n long); otherwise forward substitution per column.
-    void ns_ortho(int k) {
+    // (returns the workgroups of k_ns_ortho; 0 on the product branch)
+    unsigned ns_ortho(int k) {
         const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         if (k <= K.fN.wb) {
             const int kp = (int)round_up(k, 32);
             asmb::launch(k_transpose_dense, dim3((unsigned)((sk().ldn + 63) / 64), (unsigned)((k + 63) / 64)), dim3(256), h->stream, K.G, F.L.ldg, (int64_t)k, sk().ldn, K.ZT, K.fN.ld, (int64_t)-1);
             dev.gemm_nt(K.fN.Binv, K.fN.wb, K.ZT, K.fN.ld, nullptr, 0, K.G, F.L.ldg, k, (int)sk().ldn, kp, 0);
-        } else {
-            asmb::launch(k_ns_ortho, asmb::blocks(sk().ldn), dim3(256), h->stream, K.fN.S, K.fN.ld, k, K.G, F.L.ldg, sk().ldn);
+            return 0;
         }
+        const dim3 g = asmb::blocks(sk().ldn);
+        asmb::launch(k_ns_ortho, g, dim3(256), h->stream, K.fN.S, K.fN.ld, k, K.G, F.L.ldg, sk().ldn);
+        return g.x;
     }
     // The k rows in K.G (an approximate or an outdated basis) projected onto null(A_EF) of THIS LP and orthonormalised with their own
     // Gram matrix (pivot guard `thr`, absolute), then GI' = (A_I Z)'.  Used as the second pass of ns_basis_from and, with the previous
     // LP's basis, as the whole set-up (oracle: NullSpace.__init__, warm_Z).  The factor of S0 must be current in F.f0.
     bool ns_reproject(int k, double thr) {
         const NsForm& F = *sk().nsf; const NsK& K = *F.k;
-        const int nE = (int)F.L.nE, nEp = (int)F.L.nEp, nIp = (int)F.L.nIp;
-        const NsIdx X = nsX();
+        const int nE = (int)F.L.nE, nEp = (int)F.L.nEp;
         const double* vals = dev.sparse_vals(sk().d_Ah);
         // second pass (oracle: NullSpace.basis_from): project the rows once more and orthonormalise with their own Gram matrix (~ I) -
         // the columns picked in index order can be badly conditioned, and the active-set solves need A_EF Z = 0 to 1e-13
-        asmb::launch(k_ns_rows_e, dim3((unsigned)((nEp + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, X, F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
+        launch_ns_rows_e(vals, k);
         dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
-        asmb::launch(k_ns_pj, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, sk().ldn, 1);
+        launch_ns_pj(vals, k, 1);
+        launch_ns_gram(k);
+        if (ns_factor_N(k, thr) > 0) return false;
+        ns_ortho(k);
+        launch_ns_gi(vals, k);
+        return true;
+    }
+    // the launch sites of the basis set-up (vals = dev.sparse_vals(sk().d_Ah), made by the caller before its first launch); each returns the
+    // workgroups of its grid (x)
+    unsigned launch_ns_rows_e(const double* vals, int k) {      // R = (A_EF Zt')' for the k rows in K.G
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
+        const int nEp = (int)F.L.nEp;
+        const dim3 g((unsigned)((nEp + 255) / 256), (unsigned)k);
+        asmb::launch(k_ns_rows_e, g, dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, nsX(), F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
+        return g.x;
+    }
+    unsigned launch_ns_pj(const double* vals, int k, int second_pass) {      // rows of the projector from W = K.R into K.G
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
+        const dim3 g((unsigned)((sk().ldn + 255) / 256), (unsigned)k);
+        asmb::launch(k_ns_pj, g, dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, nsX(), K.J, F.Fm, K.R, (int64_t)F.L.nEp, K.G, F.L.ldg, lp.n, sk().ldn, second_pass);
+        return g.x;
+    }
+    void launch_ns_gram(int k) {      // lower triangle of Zt Zt' into K.fN.S
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         dev.launch_syrk(h->stream, Dev::pick_tile(k), K.G, F.L.ldg, nullptr, 0, k, (int)sk().ldn, nullptr, nullptr, K.fN.S, K.fN.ld, 0, 0);
+    }
+    int ns_factor_N(int k, double thr) {      // guarded factor of the k x k matrix in K.fN (pivot reference 1); its dropped pivots
+        const NsK& K = *sk().nsf->k;
         dev.launch_ns_fill(sk().d_diag0, 1.0, (int64_t)k);
         dev.chol(K.fN, k, thr);
-        if (ns_count_big(K.fN, k) > 0) return false;
-        ns_ortho(k);
-        asmb::launch(k_ns_gi, dim3((unsigned)((nIp + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, X, K.G, F.L.ldg, K.G + sk().ldn, nIp);
-        return true;
+        return ns_count_big(K.fN, k);
+    }
+    unsigned launch_ns_gi(const double* vals, int k) {      // GI' = (A_I Zt')' beside Zt
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
+        const int nIp = (int)F.L.nIp;
+        const dim3 g((unsigned)((nIp + 255) / 256), (unsigned)k);
+        asmb::launch(k_ns_gi, g, dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, nsX(), K.G, F.L.ldg, K.G + sk().ldn, nIp);
+        return g.x;
+    }
+    unsigned launch_ns_rhs_cols(const double* vals, const int* J, int nrhs, double* R) {      // columns J (null: all) of A_EF as rows of R
+        const NsForm& F = *sk().nsf;
+        asmb::launch(k_ns_rhs_cols, dim3((unsigned)nrhs), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, nsX(), J, F.Fm, R, (int64_t)F.L.nEp);
+        return (unsigned)nrhs;
+    }
+    unsigned launch_ns_gather_t(int k) {      // lower triangle of P[J, J] into K.fN.S
+        const NsForm& F = *sk().nsf; const NsK& K = *F.k;
+        const dim3 g((unsigned)((k + 255) / 256), (unsigned)k);
+        asmb::launch(k_ns_gather_t, g, dim3(256), h->stream, K.G, F.L.ldg, K.J, k, K.fN.S, K.fN.ld);
+        return g.x;
+    }
+    unsigned launch_ns_set_diag(const FacBuf& T, int n, const double* dvec) {
+        const dim3 g((unsigned)((n + 255) / 256), (unsigned)n);
+        asmb::launch(k_ns_set_diag, g, dim3(256), h->stream, T.S, T.ld, n, dvec);
+        return g.x;
+    }
+    unsigned launch_ns_diag(const FacBuf& T, int n, double* out) {
+        const dim3 g = asmb::blocks(n);
+        asmb::launch(k_ns_diag, g, dim3(256), h->stream, T.S, T.ld, n, out);
+        return g.x;
     }
     // Orthonormal basis from the columns J of the projector P (oracle: NullSpace.basis_from): W = S0^-1 A_EF[:, J] by block
     // substitution with all k right-hand sides at once, P[J, :] = E_J' - W' A_EF, L_J L_J' = P[J, J] (guard: pivot <= NS_WARM_THR
@@ -1770,17 +1823,14 @@ struct Solver {
     bool ns_basis_from(const std::vector<int>& J) {
         const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int k = (int)J.size(), nE = (int)F.L.nE, nEp = (int)F.L.nEp;
-        const NsIdx X = nsX();
         const double* vals = dev.sparse_vals(sk().d_Ah);
         HIPCHK(asmb::copy_async(K.J, J.data(), k * sizeof(int), hipMemcpyHostToDevice, h->stream));
         h2d_done(h);
-        asmb::launch(k_ns_rhs_cols, dim3((unsigned)k), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp);
+        launch_ns_rhs_cols(vals, K.J, k, K.R);
         dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
-        asmb::launch(k_ns_pj, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)k), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, K.J, F.Fm, K.R, (int64_t)nEp, K.G, F.L.ldg, lp.n, sk().ldn, 0);
-        asmb::launch(k_ns_gather_t, dim3((unsigned)((k + 255) / 256), (unsigned)k), dim3(256), h->stream, K.G, F.L.ldg, K.J, k, K.fN.S, K.fN.ld);
-        dev.launch_ns_fill(sk().d_diag0, 1.0, (int64_t)k);
-        dev.chol(K.fN, k, NS_WARM_THR);
-        if (ns_count_big(K.fN, k) > 0) return false;
+        launch_ns_pj(vals, k, 0);
+        launch_ns_gather_t(k);
+        if (ns_factor_N(k, NS_WARM_THR) > 0) return false;
         ns_ortho(k);
         return ns_reproject(k, NS_WARM_THR);
     }
@@ -1789,11 +1839,56 @@ struct Solver {
     bool ns_setup() {
         ns_bind();
         NsForm& F = *sk().nsf;
-        const int nE = (int)F.L.nE, nEp = (int)F.L.nEp;
+        const int nE = (int)F.L.nE;
         const int64_t n = lp.n;
-        const NsIdx X = nsX();
         int64_t nF = 0;
         for (int64_t j = 0; j < n; ++j) nF += lp.ub[j] > lp.lb[j];
+        const int dropped = ns_factor_S0();
+        ns_dropped = dropped;
+        const int64_t k = nF - (nE - dropped);
+        if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
+        ns_reserve((int)k);
+        ns_bind();
+        ns_make_Lt();
+        std::vector<int>& J = cur_hint->ns_J;
+        bool have = false;
+        ns_was_cold = false;
+        ns_path = 0;
+        ns_vlap("Lt");
+        if (F.k->Zk == (int)k) have = ns_reproject((int)k, NS_ZWARM_THR);      // the previous LP's basis, one projection pass
+        ns_vlap("reproject");
+        F.k->Zk = 0;
+        if (have) ns_path = 1;
+        if (!have && (int64_t)J.size() == k) {
+            bool free_all = true;
+            for (int j : J) free_all = free_all && j >= 0 && j < n && lp.ub[j] > lp.lb[j];
+            if (free_all) have = ns_basis_from(J);
+            if (have) ns_path = 2;
+        }
+        if (!have) {
+            ns_was_cold = true;
+            have = ns_cold_select(k, J);
+            if (have) ns_path = 3;
+        }
+        if (!have) { J.clear(); return false; }
+        ns_k = (int)k;
+        F.k->Zk = (int)k;
+        return true;
+    }
+    int ns_dropped = 0, ns_path = 0;      // of the last ns_setup: dropped pivots of S0; what made the basis (1 the previous basis, 2 the retained columns, 3 the cold selection, 0 none)
+    double ns_tv = 0.0;
+    void ns_vlap(const char* what) {      // ASM_HIP_VERBOSE: time since the last lap of the set-up
+        if (!h->knobs.verbose) return;
+        HIPCHK(asmb::sync(h->stream));
+        const double t = now_ms();
+        std::fprintf(stderr, "[asm] ns set-up %-10s +%.2f ms\n", what, t - ns_tv);
+        ns_tv = t;
+    }
+    // head of ns_setup: the mask of the free columns from the LP's bounds, S0 and its guarded factor in F.f0; returns its dropped pivots
+    int ns_factor_S0() {
+        NsForm& F = *sk().nsf;
+        const int nE = (int)F.L.nE;
+        const int64_t n = lp.n;
         {
             vec own(asmb::in_fiber() ? sk().ldn : 0);
             double* fm = asmb::in_fiber() ? own.data() : sk().h_pin;      // (pinned staging: the copy does not go through the runtime's pageable path)
@@ -1801,70 +1896,57 @@ struct Solver {
             HIPCHK(asmb::copy_async(F.Fm, fm, sk().ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
             h2d_done(h);
         }
-        double t_v = now_ms();
-        auto vlap = [&](const char* what) {
-            if (!h->knobs.verbose) return;
-            HIPCHK(asmb::sync(h->stream));
-            const double t = now_ms();
-            std::fprintf(stderr, "[asm] ns set-up %-10s +%.2f ms\n", what, t - t_v);
-            t_v = t;
-        };
+        ns_tv = now_ms();
         dev.ns_build_S0();
-        vlap("S0 build");
+        ns_vlap("S0 build");
         dev.diag_prepare(F.f0, nE, 1, 0.0, 0.0);
         dev.chol(F.f0, nE, 1e-10);
-        vlap("S0 factor");
-        const int dropped = ns_count_big(F.f0, nE);
-        const int64_t k = nF - (nE - dropped);
-        if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
-        ns_reserve((int)k);
-        ns_bind();
+        ns_vlap("S0 factor");
+        return ns_count_big(F.f0, nE);
+    }
+    void ns_make_Lt() {      // transposed copy of the factor of S0 (inside its band)
+        NsForm& F = *sk().nsf;
+        const int nE = (int)F.L.nE;
         asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), h->stream, F.f0.S, F.f0.ld, (int64_t)nE, (int64_t)nE,
                      F.Lt, F.f0.ld, (int64_t)(F.f0.band > 0 ? F.f0.band : nE));
-        std::vector<int>& J = cur_hint->ns_J;
+    }
+    // the two buffers of the cold selection (ldn rows of nEp each): made by the first LP that needs them
+    void ns_cold_buffers() {
+        NsForm& F = *sk().nsf;
+        const int nEp = (int)F.L.nEp;
+        if (!F.Yt) F.mem.zeroed(F.Yt, (int64_t)sk().ldn * nEp + (int64_t)sk().ldn * nEp, h->stream);
+    }
+    // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main factor,
+    // guarded Cholesky of T in index order with the absolute thresholds NS_SEL_THR in turn until exactly k columns are kept
+    bool ns_cold_select(int64_t k, std::vector<int>& J) {
+        NsForm& F = *sk().nsf;
+        const int nE = (int)F.L.nE, nEp = (int)F.L.nEp;
+        const int64_t n = lp.n;
         bool have = false;
-        ns_was_cold = false;
-        vlap("Lt");
-        if (F.k->Zk == (int)k) have = ns_reproject((int)k, NS_ZWARM_THR);      // the previous LP's basis, one projection pass
-        vlap("reproject");
-        F.k->Zk = 0;
-        if (!have && (int64_t)J.size() == k) {
-            bool free_all = true;
-            for (int j : J) free_all = free_all && j >= 0 && j < n && lp.ub[j] > lp.lb[j];
-            if (free_all) have = ns_basis_from(J);
+        ns_cold_buffers();
+        double* Yr = F.Yt;                                  // right-hand sides, then garbage
+        double* Yt = F.Yt + (int64_t)sk().ldn * nEp;   // L0^-1 a_j as rows
+        const double* vals = dev.sparse_vals(sk().d_Ah);
+        launch_ns_rhs_cols(vals, nullptr, (int)n, Yr);
+        dev.trsm_rows(F.f0, Yr, Yt, nEp, (int)n, nE, nullptr);
+        std::vector<double> dg(n);
+        FacBuf& T = sk().main_fac;
+        T.band = 0;
+        for (int a = 0; a < 4 && !have; ++a) {
+            launch_ns_set_diag(T, (int)n, F.Fm);
+            dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, nEp, nullptr, 0, (int)n, nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
+            dev.launch_ns_fill(sk().d_diag0, 1.0, n);
+            dev.chol(T, (int)n, NS_SEL_THR[a]);
+            launch_ns_diag(T, (int)n, sk().d_vecN);
+            HIPCHK(asmb::copy_async(dg.data(), sk().d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(asmb::sync(h->stream));
+            std::vector<int> Jc;
+            for (int64_t j = 0; j < n; ++j)
+                if (dg[j] < NS_BIG) Jc.push_back((int)j);
+            if ((int64_t)Jc.size() != k) continue;
+            if (ns_basis_from(Jc)) { J = Jc; have = true; }
         }
-        if (!have) {
-            ns_was_cold = true;
-            // cold selection: Y = L0^-1 A_EF for ALL columns (forward substitution only), T = I_F - Y'Y in the main factor,
-            // guarded Cholesky of T in index order with the absolute thresholds NS_SEL_THR in turn until exactly k columns are kept
-            if (!F.Yt) F.mem.zeroed(F.Yt, (int64_t)sk().ldn * nEp + (int64_t)sk().ldn * nEp, h->stream);
-            double* Yr = F.Yt;                                  // right-hand sides, then garbage
-            double* Yt = F.Yt + (int64_t)sk().ldn * nEp;   // L0^-1 a_j as rows
-            const double* vals = dev.sparse_vals(sk().d_Ah);
-            asmb::launch(k_ns_rhs_cols, dim3((unsigned)n), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, vals, X, nullptr, F.Fm, Yr, (int64_t)nEp);
-            dev.trsm_rows(F.f0, Yr, Yt, nEp, (int)n, nE, nullptr);
-            std::vector<double> dg(n);
-            FacBuf& T = sk().main_fac;
-            T.band = 0;
-            for (int a = 0; a < 4 && !have; ++a) {
-                asmb::launch(k_ns_set_diag, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), h->stream, T.S, T.ld, (int)n, F.Fm);
-                dev.launch_syrk(h->stream, Dev::pick_tile(n), Yt, nEp, nullptr, 0, (int)n, nEp, nullptr, nullptr, T.S, T.ld, 0, 1);
-                dev.launch_ns_fill(sk().d_diag0, 1.0, n);
-                dev.chol(T, (int)n, NS_SEL_THR[a]);
-                asmb::launch(k_ns_diag, asmb::blocks(n), dim3(256), h->stream, T.S, T.ld, (int)n, sk().d_vecN);
-                HIPCHK(asmb::copy_async(dg.data(), sk().d_vecN, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(asmb::sync(h->stream));
-                std::vector<int> Jc;
-                for (int64_t j = 0; j < n; ++j)
-                    if (dg[j] < NS_BIG) Jc.push_back((int)j);
-                if ((int64_t)Jc.size() != k) continue;
-                if (ns_basis_from(Jc)) { J = Jc; have = true; }
-            }
-        }
-        if (!have) { J.clear(); return false; }
-        ns_k = (int)k;
-        F.k->Zk = (int)k;
-        return true;
+        return have;
     }
     double* nsv(int which) const { return ns_ar.v + ns_ar.L.nsv_off(which); }      // work vectors: 0..4 n-sized, 5..7 M-sized, 8..9 E-sized, 10..13 k-sized (k <= n), 14..15 n-sized (14 = e)
     // oracle: ns_applicable
@@ -6045,6 +6127,181 @@ int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double sc
         HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
         std::memcpy(hscal_inout, hScal, SC_COUNT * sizeof(double));
         *hseq_inout = *hSeq;
+        S.dev.resolve_timing();
+        check_panel_timeout(h);
+    });
+}
+
+// The basis set-up of the null-space form (Solver::ns_setup and its members), one launch site per stage, on a handle asm_sublp_setup has set
+// up and whose skeleton has the form - see include/asm_hip.h.  The stages run on the form's own buffers (sk().nsf), which the caller loads and
+// gets back whole; the Jacobian is assembled and scaled as asm_test_build_dispatch does it.  Every size, index and stage order is checked
+// before anything is launched.
+int asm_test_ns_setup_stages(asm_handle* h, const double* dE, const double* fm, int64_t k, int64_t k_reserve, const int32_t* J, int64_t* layout_out, int32_t* idx_out,
+                             double* G_inout, double* R_inout, double* X_inout, double* SN_inout, double* Y_inout, double* T_inout, double* d_inout, double* f0_out,
+                             double* Lt_out, int32_t Zk, const int32_t* hint_J, int64_t nhint, const asm_nss_stage* stages, int64_t nstages, uint32_t* grid_out,
+                             int32_t* res_out, int32_t* setup_out) {
+    return guarded(h, [&] {
+        Skeleton& K = sk_of(h, "asm_test_ns_setup_stages: asm_sublp_setup first");
+        NsForm* const ns = K.nsf.get();
+        const int64_t n = K.n, M = K.M;
+        if (!ns || !layout_out || !fm || (K.nnz > 0 && !dE) || nstages < 0 || k < 1 || k > n || k_reserve < k ||
+            (double)k_reserve > 1.5 * NS_MAX_RATIO * (double)M + 8.0)
+            throw std::invalid_argument("asm_test_ns_setup_stages: no null-space form on this handle, or a bad size");
+        for (int64_t j = 0; j < n; ++j)
+            if (fm[j] != 0.0 && fm[j] != 1.0) throw std::invalid_argument("asm_test_ns_setup_stages: fm is 0 or 1");
+        if (J)
+            for (int64_t c = 0; c < k; ++c)
+                if (J[c] < 0 || J[c] >= n) throw std::invalid_argument("asm_test_ns_setup_stages: column index out of range");
+        if (nhint < 0 || nhint > n || (nhint > 0 && !hint_J)) throw std::invalid_argument("asm_test_ns_setup_stages: bad list of retained columns");
+        for (int64_t c = 0; c < nhint; ++c)
+            if (hint_J[c] < 0 || hint_J[c] >= n) throw std::invalid_argument("asm_test_ns_setup_stages: column index out of range");
+        const NsLayout& L = ns->L;
+        const int cap = NsLayout::kcap((int)k_reserve);
+        if (Zk < 0 || Zk > cap) throw std::invalid_argument("asm_test_ns_setup_stages: rows of the previous basis");
+        const int64_t Tld = K.main_fac.ld;
+        bool s0 = false, facN = false, needY = Y_inout != nullptr;
+        for (int64_t q = 0; q < nstages; ++q) {
+            if (!stages || !grid_out || !res_out) throw std::invalid_argument("asm_test_ns_setup_stages: bad buffer");
+            const asm_nss_stage& st = stages[q];
+            if (st.kind < 0 || st.kind >= ASM_NSS_NKINDS) throw std::invalid_argument("asm_test_ns_setup_stages: unknown stage");
+            if (st.flag < 0 || (st.flag > 1 && st.kind != ASM_NSS_COUNT_BIG)) throw std::invalid_argument("asm_test_ns_setup_stages: stage flag");
+            switch (st.kind) {
+            case ASM_NSS_S0_FACTOR: s0 = true; break;
+            case ASM_NSS_RHS_COLS:
+                if (st.flag == 0 && !J) throw std::invalid_argument("asm_test_ns_setup_stages: the stage needs the column list");
+                if (st.flag == 1) needY = true;
+                break;
+            case ASM_NSS_TRSM:
+                if (!s0) throw std::invalid_argument("asm_test_ns_setup_stages: a substitution before ASM_NSS_S0_FACTOR");
+                if (st.flag == 0) needY = true;
+                break;
+            case ASM_NSS_PJ:
+                if (st.flag == 0 && !J) throw std::invalid_argument("asm_test_ns_setup_stages: the stage needs the column list");
+                break;
+            case ASM_NSS_GATHER_T:
+                if (!J) throw std::invalid_argument("asm_test_ns_setup_stages: the stage needs the column list");
+                break;
+            case ASM_NSS_FACTOR_N: facN = true; break;
+            case ASM_NSS_ORTHO:
+                if (!facN) throw std::invalid_argument("asm_test_ns_setup_stages: ASM_NSS_ORTHO before ASM_NSS_FACTOR_N");
+                break;
+            case ASM_NSS_COUNT_BIG:
+                if (st.flag > Tld) throw std::invalid_argument("asm_test_ns_setup_stages: order beyond the main factor");
+                break;
+            case ASM_NSS_REPROJECT:
+                if (!s0) throw std::invalid_argument("asm_test_ns_setup_stages: a substitution before ASM_NSS_S0_FACTOR");
+                break;
+            case ASM_NSS_BASIS_FROM:
+                if (!s0) throw std::invalid_argument("asm_test_ns_setup_stages: a substitution before ASM_NSS_S0_FACTOR");
+                if (!J) throw std::invalid_argument("asm_test_ns_setup_stages: the stage needs the column list");
+                break;
+            case ASM_NSS_SETUP:
+                if (!setup_out) throw std::invalid_argument("asm_test_ns_setup_stages: bad buffer");
+                break;
+            default: break;      // ROWS_E, GRAM, GI, SET_DIAG, DIAG: nothing beyond the sizes
+            }
+        }
+        HIPCHK(hipSetDevice(h->device));
+        Solver S(h);
+        S.lp.n = n; S.lp.M = M; S.lp.ns = 0; S.lp.scale_q = 1.0;
+        S.lp.lb.assign(n, 0.0); S.lp.ub.assign(fm, fm + n);
+        // an earlier LP of the skeleton with k_reserve basis rows has made the k-sized buffers (another reservation is dropped first)
+        if (ns->k && ns->k->cap != cap) { HIPCHK(asmb::sync(h->stream)); ns->k.reset(); }
+        S.ns_bind();
+        S.ns_reserve((int)k_reserve);
+        S.ns_bind();
+        if (ns->k->cap != cap) throw std::logic_error("asm_test_ns_setup_stages: reservation");
+        if (needY) S.ns_cold_buffers();
+        {
+            const int64_t out[ASM_NSS_LAYOUT_LEN] = {K.ldn, L.nEp, L.nIp, L.ldg, L.nE, L.nI, ns->f0.band, ns->f0.ld, cap, ns->k->fN.ld, ns->k->fN.wb, n, M, Tld, K.Mp, 0};
+            for (int q = 0; q < ASM_NSS_LAYOUT_LEN; ++q) layout_out[q] = out[q];
+            if (idx_out) {
+                std::copy(ns->eidx_h.begin(), ns->eidx_h.end(), idx_out);
+                HIPCHK(asmb::copy(idx_out + L.nE, ns->Iidx, L.nI * sizeof(int), hipMemcpyDeviceToHost));
+            }
+        }
+        if (!stages) return;      // layout query
+        if (ns->f0.ld != L.nEp) throw std::logic_error("asm_test_ns_setup_stages: pitch of the factor of S0");
+        HIPCHK(asmb::copy(K.d_dE, dE, K.nnz * sizeof(double), hipMemcpyHostToDevice));
+        K.J_valid = false;
+        S.dev.assemble();
+        {
+            vec c(n, 1.0), rho(M);
+            S.dev.scale(c.data(), rho.data());
+        }
+        S.dev.tile_flags();
+        auto NK = [&]() -> NsK& { return *ns->k; };      // (never kept across ASM_NSS_SETUP: ns_reserve may re-make the buffers)
+        const int64_t fld = NK().fN.ld, ylen = 2 * K.ldn * L.nEp;
+        {
+            vec f(K.ldn, 0.0);
+            std::copy(fm, fm + n, f.begin());
+            HIPCHK(asmb::copy(ns->Fm, f.data(), K.ldn * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if (J) HIPCHK(asmb::copy(NK().J, J, k * sizeof(int), hipMemcpyHostToDevice));
+        if (G_inout) HIPCHK(asmb::copy(NK().G, G_inout, cap * L.ldg * sizeof(double), hipMemcpyHostToDevice));
+        if (R_inout) HIPCHK(asmb::copy(NK().R, R_inout, cap * L.nEp * sizeof(double), hipMemcpyHostToDevice));
+        if (X_inout) HIPCHK(asmb::copy(NK().X, X_inout, cap * L.nEp * sizeof(double), hipMemcpyHostToDevice));
+        if (SN_inout) HIPCHK(asmb::copy(NK().fN.S, SN_inout, fld * fld * sizeof(double), hipMemcpyHostToDevice));
+        if (Y_inout) HIPCHK(asmb::copy(ns->Yt, Y_inout, ylen * sizeof(double), hipMemcpyHostToDevice));
+        if (T_inout) HIPCHK(asmb::copy(K.main_fac.S, T_inout, Tld * Tld * sizeof(double), hipMemcpyHostToDevice));
+        if (d_inout) HIPCHK(asmb::copy(K.d_vecN, d_inout, K.ldn * sizeof(double), hipMemcpyHostToDevice));
+        const int kk = (int)k, nn = (int)n;
+        SolveHint hint(false);
+        for (int64_t q = 0; q < nstages; ++q) {      // one after the other on the handle's stream; the host waits only where the solver does
+            const asm_nss_stage& st = stages[q];
+            const double* vals = S.dev.sparse_vals(K.d_Ah);
+            unsigned g = 0;
+            int res = 0;
+            switch (st.kind) {
+            case ASM_NSS_S0_FACTOR: res = S.ns_factor_S0(); S.ns_make_Lt(); break;
+            case ASM_NSS_RHS_COLS: g = st.flag ? S.launch_ns_rhs_cols(vals, nullptr, nn, ns->Yt) : S.launch_ns_rhs_cols(vals, NK().J, kk, NK().R); break;
+            case ASM_NSS_ROWS_E: g = S.launch_ns_rows_e(vals, kk); break;
+            case ASM_NSS_TRSM:
+                if (st.flag) S.dev.trsm_rows(ns->f0, NK().R, NK().X, L.nEp, kk, (int)L.nE, ns->Lt);
+                else S.dev.trsm_rows(ns->f0, ns->Yt, ns->Yt + K.ldn * L.nEp, L.nEp, nn, (int)L.nE, nullptr);
+                break;
+            case ASM_NSS_PJ: g = S.launch_ns_pj(vals, kk, st.flag); break;
+            case ASM_NSS_GATHER_T: g = S.launch_ns_gather_t(kk); break;
+            case ASM_NSS_GRAM: S.launch_ns_gram(kk); break;
+            case ASM_NSS_FACTOR_N: res = S.ns_factor_N(kk, st.thr); break;
+            case ASM_NSS_ORTHO: g = S.ns_ortho(kk); break;
+            case ASM_NSS_GI: g = S.launch_ns_gi(vals, kk); break;
+            case ASM_NSS_SET_DIAG: g = S.launch_ns_set_diag(K.main_fac, nn, st.flag ? nullptr : ns->Fm); break;
+            case ASM_NSS_DIAG: g = S.launch_ns_diag(K.main_fac, nn, K.d_vecN); break;
+            case ASM_NSS_COUNT_BIG: res = S.ns_count_big(K.main_fac, st.flag); g = 1; break;
+            case ASM_NSS_REPROJECT: res = S.ns_reproject(kk, st.thr) ? 1 : 0; g = (unsigned)((L.nEp + 255) / 256); break;
+            case ASM_NSS_BASIS_FROM: res = S.ns_basis_from(std::vector<int>(J, J + k)) ? 1 : 0; g = (unsigned)kk; break;
+            default: {
+                hint.ns_J.assign(hint_J, hint_J + nhint);
+                S.cur_hint = &hint;
+                NK().Zk = Zk;
+                res = S.ns_setup() ? 1 : 0;
+                setup_out[0] = S.ns_path; setup_out[1] = res ? S.ns_k : 0; setup_out[2] = S.ns_dropped; setup_out[3] = (int32_t)hint.ns_J.size();
+                std::copy(hint.ns_J.begin(), hint.ns_J.end(), setup_out + 4);
+                if (NK().cap != cap) throw std::logic_error("asm_test_ns_setup_stages: the LP's null space is larger than k_reserve allows for");
+            }
+            }
+            grid_out[q] = g;
+            res_out[q] = res;
+        }
+        HIPCHK(asmb::sync(h->stream));
+        if (G_inout) HIPCHK(asmb::copy(G_inout, NK().G, cap * L.ldg * sizeof(double), hipMemcpyDeviceToHost));
+        if (R_inout) HIPCHK(asmb::copy(R_inout, NK().R, cap * L.nEp * sizeof(double), hipMemcpyDeviceToHost));
+        if (X_inout) HIPCHK(asmb::copy(X_inout, NK().X, cap * L.nEp * sizeof(double), hipMemcpyDeviceToHost));
+        if (SN_inout) HIPCHK(asmb::copy(SN_inout, NK().fN.S, fld * fld * sizeof(double), hipMemcpyDeviceToHost));
+        if (Y_inout) {
+            HIPCHK(asmb::copy(Y_inout, ns->Yt, ylen * sizeof(double), hipMemcpyDeviceToHost));
+            // the padding of the rows L0^-1 a_j is an operand of T in the cold selection and no launch writes it: the solver relies on the
+            // zeros it is made with, so whatever the caller loaded there does not outlive the call
+            vec y(Y_inout + K.ldn * L.nEp, Y_inout + ylen);
+            for (int64_t j = 0; j < K.ldn; ++j) std::fill(y.begin() + j * L.nEp + L.nE, y.begin() + (j + 1) * L.nEp, 0.0);
+            HIPCHK(asmb::copy(ns->Yt + K.ldn * L.nEp, y.data(), y.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if (T_inout) HIPCHK(asmb::copy(T_inout, K.main_fac.S, Tld * Tld * sizeof(double), hipMemcpyDeviceToHost));
+        if (d_inout) HIPCHK(asmb::copy(d_inout, K.d_vecN, K.ldn * sizeof(double), hipMemcpyDeviceToHost));
+        if (f0_out) HIPCHK(asmb::copy(f0_out, ns->f0.S, L.nEp * L.nEp * sizeof(double), hipMemcpyDeviceToHost));
+        if (Lt_out) HIPCHK(asmb::copy(Lt_out, ns->Lt, L.nEp * L.nEp * sizeof(double), hipMemcpyDeviceToHost));
+        ns->k->Zk = 0;      // the basis rows in G are the caller's: no later LP on this skeleton takes them for its predecessor's
         S.dev.resolve_timing();
         check_panel_timeout(h);
     });

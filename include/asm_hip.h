@@ -936,6 +936,63 @@ int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double sc
                        const int32_t* col, const double* vals, const double* Nreg, const double* N0, int64_t* layout_out, int32_t* idx_out,
                        double* dbl_inout, int64_t ndbl, double* hscal_inout, uint32_t* hseq_inout, const asm_ns_stage* stages,
                        int64_t nstages, uint32_t* grid_out);
+/* Test hook: the per-LP basis set-up of the null-space form (Solver::ns_setup with ns_reproject, ns_basis_from, ns_ortho and the cold column
+ * selection), one launch site per stage with the solver's own launch geometry, on the form's own buffers.  The handle has been set up by
+ * asm_sublp_setup and its skeleton has the form (ASM_ERR_ARG otherwise).  As in asm_test_build_dispatch the Jacobian is assembled from dE and
+ * scaled by rows (unit column scale); take the operand from there (which < 0).
+ *   fm         n entries, 1 = free column, 0 = fixed: the LP's bounds are lb = 0, ub = fm.
+ *   k, k_reserve >= k   rows of the basis the primitive stages work on; the k-sized buffers are those Solver::ns_reserve makes for an earlier LP
+ *              of the skeleton with k_reserve rows (cap = NsLayout::kcap(k_reserve) rows; buffers of another reservation are dropped first,
+ *              those of the same one are kept with what they hold).
+ *   J          the basis columns (k entries in [0, n); NULL where no stage reads them).
+ *   layout_out (ASM_NSS_LAYOUT_LEN) receives ldn, nEp, nIp, ldg, nE, nI, band of S0 (0 = dense), pitch of S0, cap, pitch and wide-block width of
+ *              the k x k factor fN, n, M, pitch of the main factor, Mp.  idx_out (nE + nI, or NULL): Eidx | Iidx.  With stages == NULL the call
+ *              makes the reservation and reports these two only.
+ *   G_inout (cap x ldg: Gt = [Zt | GI']), R_inout, X_inout (cap x nEp), SN_inout (the factor buffer of fN, pitch x pitch), Y_inout (the two
+ *              blocks of the cold selection, ldn x nEp each: right-hand sides | L0^-1 a_j), T_inout (the main factor, pitch x pitch), d_inout
+ *              (ldn: the vector ASM_NSS_DIAG writes): each loaded before the first stage and returned whole after the last; NULL: left as it is.
+ *              The solver relies on the zeros the second block of Y is made with beyond column nE (the padding of L0^-1 a_j, an operand of
+ *              the cold selection's matrix that no launch writes): the stages of the call see what the caller loaded there, the hook puts
+ *              the zeros back before it returns.
+ *   f0_out, Lt_out (nEp x nEp, or NULL): the factor of S0 and its transposed copy after the last stage.
+ *   Zk, hint_J (nhint entries)  for ASM_NSS_SETUP: rows of the previous LP's basis in G (NsK::Zk) and the retained columns (SolveHint::ns_J).
+ *   stages     run in order on the handle's stream; the host waits only where the solver does (the dropped-pivot counts, the diagonal of the
+ *              cold selection).  grid_out[q]: workgroups (x) of the stage's kernel of asm_ns_kernels.hip.h, of the first one for REPROJECT and
+ *              BASIS_FROM; 0 where the stage is a factorisation, a product or a substitution.  res_out[q]: the dropped pivots (S0_FACTOR,
+ *              FACTOR_N), the count (COUNT_BIG), 1 / 0 for the composites.  setup_out (4 + n) of the last ASM_NSS_SETUP: what made the basis (1
+ *              the previous basis, 2 the retained columns, 3 the cold selection, 0 none), k, dropped pivots of S0, length of J, J.
+ * Checked before the first launch (ASM_ERR_ARG otherwise): the sizes (1 <= k <= n, k <= k_reserve <= 1.5 NS_MAX_RATIO M + 8), fm, every column
+ * index, flags, and the order of the stages: TRSM, REPROJECT and BASIS_FROM after S0_FACTOR, ORTHO after FACTOR_N in the same call. */
+enum {
+    ASM_NSS_S0_FACTOR = 0,    /* the head of ns_setup: mask upload, Dev::ns_build_S0, diag_prepare, chol(f0, nE, 1e-10), ns_count_big, transpose into Lt */
+    ASM_NSS_RHS_COLS,         /* k_ns_rhs_cols; flag 0: columns J into R (grid k), 1: all n columns into Y (cold selection) */
+    ASM_NSS_ROWS_E,           /* k_ns_rows_e: R from Zt */
+    ASM_NSS_TRSM,             /* Dev::trsm_rows on f0; flag 1: R, X with k rows, forward and backward; 0: the n rows of Y, forward only */
+    ASM_NSS_PJ,               /* k_ns_pj; flag = second_pass */
+    ASM_NSS_GATHER_T,         /* k_ns_gather_t */
+    ASM_NSS_GRAM,             /* launch_syrk of Zt into fN.S as ns_reproject calls it */
+    ASM_NSS_FACTOR_N,         /* pivot reference 1, chol(fN, k, thr), ns_count_big */
+    ASM_NSS_ORTHO,            /* Solver::ns_ortho: k_transpose_dense + gemm_nt for k <= fN.wb, k_ns_ortho otherwise */
+    ASM_NSS_GI,               /* k_ns_gi */
+    ASM_NSS_SET_DIAG,         /* k_ns_set_diag on the main factor, order n; flag 0: the mask, 1: a null vector */
+    ASM_NSS_DIAG,             /* k_ns_diag of the main factor, order n */
+    ASM_NSS_COUNT_BIG,        /* k_ns_count_big on the main factor; flag = the order */
+    ASM_NSS_REPROJECT,        /* Solver::ns_reproject(k, thr) */
+    ASM_NSS_BASIS_FROM,       /* Solver::ns_basis_from(J) */
+    ASM_NSS_SETUP,            /* Solver::ns_setup on the LP of fm */
+    ASM_NSS_NKINDS
+};
+#define ASM_NSS_LAYOUT_LEN 16
+typedef struct asm_nss_stage {
+    int32_t kind;                 /* ASM_NSS_* */
+    int32_t flag;
+    double thr;
+} asm_nss_stage;
+int asm_test_ns_setup_stages(asm_handle* h, const double* dE, const double* fm, int64_t k, int64_t k_reserve, const int32_t* J,
+                             int64_t* layout_out, int32_t* idx_out, double* G_inout, double* R_inout, double* X_inout, double* SN_inout,
+                             double* Y_inout, double* T_inout, double* d_inout, double* f0_out, double* Lt_out, int32_t Zk,
+                             const int32_t* hint_J, int64_t nhint, const asm_nss_stage* stages, int64_t nstages, uint32_t* grid_out,
+                             int32_t* res_out, int32_t* setup_out);
 int asm_test_cholesky(asm_handle* h, const double* S /* N*N sym */, int64_t N, double* L_out /* N*N lower */);
 int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x);
 /* the bounded wait of the dataflow panel kernel with a producer that never publishes: returns ASM_ERR_HIP (reported once), the

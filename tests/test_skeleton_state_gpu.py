@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.util import random_subproblem, banded_subproblem, edge_case_subproblems
+from tests.util import random_subproblem, banded_subproblem, edge_case_subproblems, equality_rich_subproblem, NSS_KINDS
 from tests.util import abi_create as _create, abi_setup as _setup, abi_set_bounds as _set_bounds, abi_solve as _solve
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +29,8 @@ def _sp(key):
         return random_subproblem(7, 96, 48, n_range=5)
     if key[0] == 'B':
         return banded_subproblem(key[1], n=260, m=400, neq=80, nrange=20)
+    if key == 'Q':
+        return equality_rich_subproblem(62, 300, 260, 160)
     return edge_case_subproblems()[key]
 
 
@@ -48,6 +50,8 @@ def _stretch(lib, h, key):
         assert res[1][0][0] == 1, (key, res[1])
         if key[0] == 'B':
             assert res[1][1]['col_iters'] > 0, res[1][1]       # the column form of the restoration phase is in use
+    if key == 'Q':
+        assert res[0][0][0] == 1 and res[0][1]['ns_dim'] > 0, (key, res[0])      # the null-space form is in use
     return res
 
 
@@ -136,6 +140,29 @@ def test_kernel_hooks_share_the_skeleton(hip_lib):
         assert np.abs(L @ L.T - Sb).max() <= 1e-10 * np.abs(Sb).max()
         assert lib.asm_test_set_factor(h, 0, 0, 0, 0.0, 0.0, 1e-14) == 0 and lib.asm_test_set_band(h, 0) == 0
         _setup_and_compare(lib, h, ('B', 3), 'after')
+    finally:
+        assert lib.asm_destroy(h) == 0
+
+
+def test_ns_setup_hook_shares_the_skeleton(hip_lib):
+    """asm_test_ns_setup_stages works on the skeleton's own null-space form: it re-scales the Jacobian with unit column scale, makes the k-sized
+    buffers for the reservation it is given and leaves basis rows, factors and the cold selection's blocks behind.  Q =
+    equality_rich_subproblem(62, 300, 260, 160) has the form (k = 40 with every column free).  The next set-up solves like a fresh handle."""
+    from activesetmethods_amd import _lib
+    lib = hip_lib
+    sp = _sp('Q')
+    n, k = sp['n'], 40
+    h = _create(lib)
+    try:
+        _setup_and_compare(lib, h, 'Q', 'before')
+        dE, fm = np.ascontiguousarray(sp['dE'], dtype=np.float64), np.ones(n)
+        lay, grid, res, out = np.zeros(16, np.int64), np.zeros(1, np.uint32), np.zeros(1, np.int32), np.full(4 + n, -1, np.int32)
+        st = (_lib.NssStage * 1)(_lib.NssStage(NSS_KINDS.index("setup"), 0, 0.0))      # ASM_NSS_SETUP
+        assert lib.asm_test_ns_setup_stages(h, _lib.dptr(dE), _lib.dptr(fm), k, k + 17, None, _lib.i64ptr(lay), None, None, None, None, None, None, None, None, None, None,
+                                            0, None, 0, st, 1, grid.ctypes.data_as(C.POINTER(C.c_uint32)), _lib.i32ptr(res), _lib.i32ptr(out)) == 0, lib.asm_last_error(h)
+        assert res[0] == 1 and tuple(out[:4]) == (3, k, 0, k)      # a cold set-up with k basis columns
+        _setup_and_compare(lib, h, 'Q', 'after')
+        _setup_and_compare(lib, h, ('B', 3), 'another skeleton')
     finally:
         assert lib.asm_destroy(h) == 0
 

@@ -2495,3 +2495,336 @@ def ns_twin_iteration(lp, st, nsp, ns_e):
     _f(tu, st)
     st["scal"][SC["NSERR"]] = nserr
     return (pinf, dinf, mu, ap, ad, nserr), tu["e_exact"]
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# Basis set-up of the null-space form (tests/test_ns_setup_cpu.py, tests/test_ns_setup_gpu.py): twins of the launch sites of Solver::ns_setup
+# (asm_test_ns_setup_stages), written from the statements of oracle/lp_solver.py (class NullSpace) and the comments of asm_ns_kernels.hip.h, on
+# the operand as it stands on the device: Ah (M x n), the equality rows Eidx in the order of the factor of S0, the inequality rows Iidx, the
+# mask fm of the free columns.  A twin of the second group returns (value, magnitude, K) in long double for bound (a); the exact ones return
+# float64 arrays; the algorithms (substitutions, factorisations) are functions of a dtype: long double for the reference, float64 for the
+# measured allowance of convention (c).
+NSS_KINDS = ("s0_factor", "rhs_cols", "rows_e", "trsm", "pj", "gather_t", "gram", "factor_n", "ortho", "gi", "set_diag", "diag", "count_big", "reproject",
+             "basis_from", "setup")       # enum ASM_NSS_* of include/asm_hip.h
+NSS_LAYOUT = "ldn nEp nIp ldg nE nI band ld0 cap fld wb n M ldT Mp".split()
+NS_BIG, NS_WARM_THR, NS_ZWARM_THR, NS_SEL_THR, NS_MAX_RATIO = 0.5e128, 1e-6, 0.25, (1e-2, 1e-4, 1e-7, 1e-10), 0.3
+NSS_PATHS = {"basis": 1, "columns": 2, "cold": 3}
+
+
+def nss_kcap(k):
+    """NsLayout::kcap: rows reserved for a basis of k rows."""
+    return (k + k // 4 + 64 + 63) // 64 * 64
+
+
+def nss_wb(ld):
+    """ns_alloc_factor: wide-block width of a factor of pitch ld."""
+    return 1024 if (ld <= 1024 or ld > 1536) else 512
+
+
+def _up32(x):
+    return (x + 31) // 32 * 32
+
+
+class NssOp:
+    """The operand of the set-up twins."""
+
+    def __init__(self, Ah, Eidx, Iidx, fm):
+        self.A = np.ascontiguousarray(Ah, np.float64)
+        self.E, self.I = np.asarray(Eidx, np.int64), np.asarray(Iidx, np.int64)
+        self.fm = np.asarray(fm, np.float64)
+        self.M, self.n = self.A.shape
+        self.nE, self.nI = len(self.E), len(self.I)
+        self.ldn, self.nEp, self.nIp = _up32(self.n), _up32(self.nE), _up32(max(self.nI, 1))
+        self.ldg = self.ldn + self.nIp
+        self.AE, self.AI = self.A[self.E], self.A[self.I]
+        self.AEF = self.AE * self.fm
+        self.free = self.fm != 0
+
+    def with_fm(self, fm):
+        return NssOp(self.A, self.E, self.I, fm)
+
+
+def _nss_rows_dot(rows, Z):
+    """Z (k x n, long double) against the sparse rows `rows` (r x n): (value, magnitude) k x r and K (r) = non-zeros of each row, at least 1."""
+    k, r = Z.shape[0], rows.shape[0]
+    val, mag, K = np.zeros((k, r), LD), np.zeros((k, r), LD), np.ones(r, np.int64)
+    aZ = np.abs(Z)
+    for t in range(r):
+        c = np.nonzero(rows[t])[0]
+        if len(c):
+            a = rows[t, c].astype(LD)
+            val[:, t], mag[:, t], K[t] = Z[:, c] @ a, aZ[:, c] @ np.abs(a), len(c)
+    return val, mag, K
+
+
+def tw_nss_rhs_cols(op, J=None):
+    """k_ns_rhs_cols (exact): row c = column J[c] (None: column c of all n) of A_EF on the rows E, zero over the rest of the pitch nEp; a fixed
+    column gives a zero row."""
+    cols = np.arange(op.n) if J is None else np.asarray(J, np.int64)
+    R = np.zeros((len(cols), op.nEp))
+    R[:, :op.nE] = np.where(op.free[cols][:, None], op.AE[:, cols].T, 0.0)
+    return R
+
+
+def tw_nss_rows_e(op, Zt):
+    """k_ns_rows_e: R[c, e] = sum_j A[E[e], j] fm_j Zt[c, j] (k x nEp; exactly 0 beyond nE).  K = non-zeros of the row."""
+    val, mag, K = _nss_rows_dot(op.AEF, np.asarray(Zt[:, :op.n], LD))
+    pad = ((0, 0), (0, op.nEp - op.nE))
+    return np.pad(val, pad), np.pad(mag, pad), np.pad(K, (0, op.nEp - op.nE), constant_values=1)
+
+
+def tw_nss_gi(op, Zt):
+    """k_ns_gi: GI'[c, t] = sum_j A[I[t], j] Zt[c, j] (k x nIp; exactly 0 beyond nI).  K = non-zeros of the row."""
+    val, mag, K = _nss_rows_dot(op.AI, np.asarray(Zt[:, :op.n], LD))
+    pad = ((0, 0), (0, op.nIp - op.nI))
+    return np.pad(val, pad), np.pad(mag, pad), np.pad(K, (0, op.nIp - op.nI), constant_values=1)
+
+
+def tw_nss_pj(op, W, J=None, prev=None):
+    """k_ns_pj: PJ[c, j] = fm_j (base[c, j] - sum_{e} W[c, e] A[E[e], j]), base = delta(j, J[c]) in the first pass and the row already there
+    (prev) in the second (k x ldn; exactly 0 in the fixed columns and in [n, ldn)).  K = entries of column j on the equality rows, plus 1."""
+    k = W.shape[0]
+    base = np.zeros((k, op.n), LD)
+    if prev is None:
+        base[np.arange(k), np.asarray(J, np.int64)] = 1
+    else:
+        base[:] = prev[:, :op.n]
+    Wl = np.asarray(W[:, :op.nE], LD)
+    val, mag, K = _nss_rows_dot(np.ascontiguousarray(op.AE.T), Wl)
+    val, mag = base - val, np.abs(base) + mag
+    K = np.where(np.count_nonzero(op.AE, axis=0) > 0, K, 0) + 1
+    val[:, ~op.free] = 0
+    mag[:, ~op.free] = 0
+    pad = ((0, 0), (0, op.ldn - op.n))
+    return np.pad(val, pad), np.pad(mag, pad), np.pad(K, (0, op.ldn - op.n), constant_values=1)
+
+
+def tw_nss_gather_t(PJ, J):
+    """k_ns_gather_t (exact): T[c, d] = PJ[c, J[d]] for d <= c; the strictly upper part is not the kernel's."""
+    return np.tril(PJ[:len(J)][:, np.asarray(J, np.int64)])
+
+
+def tw_nss_ortho_rows(L, G, dev):
+    """k_ns_ortho, row c of Zt = L^-1 G from the rows the DEVICE wrote before it: (G[c] - sum_{d < c} L[c, d] dev[d]) / L[c, c].  K = c + 1."""
+    k = G.shape[0]
+    Ll, Dl = np.tril(np.asarray(L[:k, :k], LD), -1), np.asarray(dev, LD)
+    dg = np.asarray(np.diag(L)[:k], LD)[:, None]
+    val, mag = np.asarray(G, LD).copy(), np.abs(np.asarray(G, LD))
+    for i0 in range(0, k, 128):      # (the lower triangle only, a block of rows at a time)
+        i1 = min(k, i0 + 128)
+        val[i0:i1] -= Ll[i0:i1, :i1] @ Dl[:i1]
+        mag[i0:i1] += np.abs(Ll[i0:i1, :i1]) @ np.abs(Dl[:i1])
+    return val / dg, mag / np.abs(dg), (np.arange(k) + 1)[:, None]
+
+
+def nss_chol_guard(S, d0, thr, dtype=LD):
+    """Guarded Cholesky factor of the lower triangle of S in `dtype` (oracle: _chol_guard_loop): a pivot <= thr d0[j] becomes PIV_BIG^2."""
+    S = np.asarray(S, dtype)
+    N = S.shape[0]
+    L = np.zeros((N, N), dtype)
+    for j in range(N):
+        d = S[j, j] - L[j, :j] @ L[j, :j]
+        if not (d > thr * d0[j]):
+            d = dtype(1e128) * dtype(1e128)
+        L[j, j] = np.sqrt(d)
+        if j + 1 < N:
+            L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return L
+
+
+def _nss_potrf64(D, d0, thr):
+    """The diagonal-block step of the panel kernels (asm_kernels.hip.h: potrf64_body) in float64: the factor L of the nb x nb block D
+    (nb <= 64) in 16-wide sub-blocks - a column is scaled by the reciprocal square root of its guarded pivot (the pivot itself becomes
+    d / sqrt(d)), the columns of the sub-block are updated one by one over all rows below, the rest of the triangle by one rank-16 update -
+    and W = L^-1 by 16 x 16 blocks: diagonal blocks by substitution with the stored reciprocals, W_ij = -W_ii sum_k L_ik W_kj level by level."""
+    nb = D.shape[0]
+    A, dinv = np.tril(D).copy(), np.ones(nb)
+    for c0 in range(0, nb, 16):
+        c1 = min(nb, c0 + 16)
+        for j in range(c0, c1):
+            d = A[j, j]
+            if not (d > thr * d0[j]):
+                d = 1e256
+            inv = 1.0 / np.sqrt(d)
+            col = A[j:, j] * inv
+            col[0] = d * inv
+            A[j:, j], dinv[j] = col, inv
+            for c in range(j + 1, c1):
+                A[c:, c] -= A[c:, j] * A[c, j]
+        if c1 < nb:
+            X = A[c1:, c0:c1]
+            A[c1:, c1:] -= np.tril(X @ X.T)
+    L, W = np.tril(A), np.zeros((nb, nb))
+    blocks = [slice(b0, min(nb, b0 + 16)) for b0 in range(0, nb, 16)]
+    for sb in blocks:
+        m = sb.stop - sb.start
+        for t in range(m):
+            x = np.zeros(m)
+            for r in range(t, m):
+                x[r] = ((1.0 if r == t else 0.0) - L[sb.start + r, sb.start:sb.start + r] @ x[:r]) * dinv[sb.start + r]
+            W[sb, sb.start + t] = x
+    for lev in range(1, len(blocks)):
+        for j in range(len(blocks) - lev):
+            i = j + lev
+            T = sum(L[blocks[i], blocks[q]] @ W[blocks[q], blocks[j]] for q in range(j, i))
+            W[blocks[i], blocks[j]] = -(W[blocks[i], blocks[i]] @ T)
+    return L, W
+
+
+def nss_chol_blocked(S, d0, thr):
+    """The guarded factor of the lower triangle of S by the device's algorithm, in float64 NumPy (asm_kernels.hip.h: the panel kernels):
+    right-looking in 64-wide steps - the diagonal block and its explicit inverse (_nss_potrf64), the panel below as a product with that
+    inverse, a rank-64 update of what remains.  This, not a column loop with divisions, is "the same algorithm" convention (c) measures its
+    allowance with: on an ill-conditioned matrix the two differ tenfold in what they leave, in the same columns as the device."""
+    S = np.tril(np.asarray(S, np.float64)).copy()
+    N = S.shape[0]
+    for b0 in range(0, N, 64):
+        b1 = min(N, b0 + 64)
+        L, W = _nss_potrf64(S[b0:b1, b0:b1], d0[b0:b1], thr)
+        S[b0:b1, b0:b1] = L
+        if b1 < N:
+            P = S[b1:, b0:b1] @ W.T
+            S[b1:, b0:b1] = P
+            S[b1:, b1:] -= np.tril(P @ P.T)
+    return S
+
+
+def nss_trsm_rows(L, B, backward, dtype=LD):
+    """Rows of B solved against the lower factor L: L x = b, then (backward) L' x = z.  Long double: substitution; float64: LAPACK."""
+    N = L.shape[0]
+    if dtype is not LD:
+        from scipy.linalg import solve_triangular
+        Lt = np.tril(np.asarray(L, np.float64))
+        X = solve_triangular(Lt, np.asarray(B, np.float64).T, lower=True)
+        return (solve_triangular(Lt.T, X, lower=False) if backward else X).T
+    Ll, X = np.tril(np.asarray(L, LD)), np.zeros(B.shape, LD)
+    Bl = np.asarray(B, LD)
+    for i in range(N):
+        X[:, i] = (Bl[:, i] - X[:, :i] @ Ll[i, :i]) / Ll[i, i]
+    if backward:
+        Z, X = X, np.zeros(B.shape, LD)
+        for i in range(N - 1, -1, -1):
+            X[:, i] = (Z[:, i] - X[:, i + 1:] @ Ll[i + 1:, i]) / Ll[i, i]
+    return X
+
+
+def nss_ortho(L, G, dtype=LD):
+    """Zt = L^-1 G (forward substitution down the rows)."""
+    return nss_trsm_rows(L, np.asarray(G).T, False, dtype).T
+
+
+def _f64(x):
+    return np.asarray(x, np.float64)
+
+
+def nss_chain(op, dtype=LD, hint_J=None, warm_Z=None, M=None):
+    """The whole set-up from the twins' statements (oracle: NullSpace.__init__), every stage evaluated in `dtype` from the float64 rounding of
+    the stage before: dict(path, k, dropped, J, Zt, GI, L0) - path None and no basis when the LP keeps the row form."""
+    n, nE = op.n, op.nE
+    AEF, AI, fm = op.AEF.astype(dtype), op.AI.astype(dtype), op.fm
+    one = np.ones(n)
+    S0 = _f64(AEF @ AEF.T)
+    L0 = _f64(nss_chol_guard(S0, np.diag(S0), 1e-10, dtype))
+    dropped = int((np.diag(L0) >= NS_BIG).sum())
+    k = int(fm.sum()) - (nE - dropped)
+    out = dict(path=None, k=k, dropped=dropped, J=None, L0=L0)
+    if k < 1 or (M is not None and k > 1.5 * NS_MAX_RATIO * M + 8):
+        return out
+
+    def reproject(G, thr):
+        R = _f64(np.asarray(G, dtype) @ AEF.T)
+        W = _f64(nss_trsm_rows(L0, R, True, dtype))
+        Z1 = _f64((np.asarray(G, dtype) - np.asarray(W, dtype) @ AEF) * fm)
+        Gm = _f64(np.tril(np.asarray(Z1, dtype) @ np.asarray(Z1, dtype).T))
+        L1 = _f64(nss_chol_guard(Gm, one, thr, dtype))
+        if (np.diag(L1) >= NS_BIG).any():
+            return None
+        return _f64(nss_ortho(L1, Z1, dtype))
+
+    def basis_from(J):
+        R = tw_nss_rhs_cols(op, J)[:, :nE]
+        W = _f64(nss_trsm_rows(L0, R, True, dtype))
+        EJ = np.zeros((len(J), n))
+        EJ[np.arange(len(J)), J] = 1.0
+        PJ = _f64((EJ - np.asarray(W, dtype) @ AEF) * fm)
+        LJ = _f64(nss_chol_guard(tw_nss_gather_t(PJ, J), one, NS_WARM_THR, dtype))
+        if (np.diag(LJ) >= NS_BIG).any():
+            return None
+        return reproject(_f64(nss_ortho(LJ, PJ, dtype)), NS_WARM_THR)
+
+    Zt, path, J = None, None, None
+    if warm_Z is not None and warm_Z.shape[0] == k:
+        Zt = reproject(warm_Z[:, :n], NS_ZWARM_THR)
+        path = "basis" if Zt is not None else None
+    if Zt is None and hint_J is not None and len(hint_J) == k and np.all(fm[np.asarray(hint_J, np.int64)] > 0):
+        J = np.asarray(hint_J, np.int64)
+        Zt = basis_from(J)
+        path = "columns" if Zt is not None else None
+    if Zt is None:
+        Yt = _f64(nss_trsm_rows(L0, tw_nss_rhs_cols(op)[:, :nE], False, dtype))
+        T = _f64(np.diag(fm) - np.asarray(Yt, dtype) @ np.asarray(Yt, dtype).T)
+        for thr in NS_SEL_THR:
+            LT = nss_chol_guard(T, one, thr, dtype)
+            J = np.nonzero(_f64(np.diag(LT)) < NS_BIG)[0]
+            if len(J) == k:
+                Zt = basis_from(J)
+                if Zt is not None:
+                    path = "cold"
+                    break
+    if Zt is None:
+        return out
+    out.update(path=path, J=J if path != "basis" else (None if hint_J is None else np.asarray(hint_J, np.int64)), Zt=Zt,
+               GI=_f64(np.asarray(Zt, dtype) @ AI.T))
+    return out
+
+
+def nss_quality(op, Zt, GIt=None):
+    """max |A_EF Zt'|, max |Zt Zt' - I| and (with GIt) max |GI' - (A_I Zt')'| in long double."""
+    Z = np.asarray(Zt[:, :op.n], LD)
+    a = float(np.abs(Z @ op.AEF.astype(LD).T).max())
+    b = 0.0
+    for i0 in range(0, Z.shape[0], 128):      # (the lower triangle only, a block of rows at a time)
+        i1 = min(Z.shape[0], i0 + 128)
+        b = max(b, float(np.abs(Z[i0:i1] @ Z[:i1].T - np.eye(i1, dtype=LD)[i0:i1]).max()))
+    c = None if GIt is None else float(np.abs(np.asarray(GIt[:, :op.nI], LD) - _nss_rows_dot(op.AI, Z)[0]).max(initial=0.0))
+    return a, b, c
+
+
+# cases of the set-up tests: name -> (generator arguments or "banded", fixed columns, dependent equality row, k_reserve or None).  The
+# "banded-eq" skeleton of tests/test_builds_gpu.py (n = 500, 300 equality rows, M = 520) does not get the form - n - nE = 200 > 0.3 M - so the
+# banded case is the same generator and seed with n = 400.
+NSS_CASES = {
+    "small": ((61, 100, 70, 50), 0, False, None),             # the smallest qualifying shape: ldn - n = 28, nEp - nE = 26, nIp - nI = 14, k = 30
+    "small-fixed": ((61, 100, 70, 50), 6, False, None),       # k = 24: the zeros of the fixed columns
+    "small-dep": ((61, 100, 70, 50), 0, True, None),          # A[5] = 2 A[3]: one dropped pivot of S0, k = 31
+    "small-reserve": ((61, 100, 70, 50), 6, False, 30),       # the buffers of an earlier LP with fewer fixed columns
+    "k1": ((61, 100, 70, 50), -1, False, None),               # all but nE + 1 columns fixed
+    "one-ineq": ((64, 100, 99, 1), 0, False, None),           # nI = 1 (and k = 1): M = 100 is the least that qualifies with n = 100
+    "dense": ((62, 300, 260, 160), 5, False, None),           # dense S0, k = 35
+    "banded": ("banded", 0, False, None),                     # banded S0 (band 14 of 300): banded_subproblem(503, 400, 520, 300, 0), k = 100
+    "wide": ((63, 900, 64, 2800), 0, False, None),            # k = 836 > fN.wb = 512: k_ns_ortho, two wide blocks in the k x k factor; S0 is 64 x 64 with band 4
+    "wide-fixed": ((63, 900, 64, 2800), 400, False, 836),     # k <= 512 inside a factor of pitch 1152: the product branch of ns_ortho
+}
+
+
+def nss_case(name):
+    """(sub-problem, fm, k_reserve or None) of a case of NSS_CASES."""
+    gen, nfix, dep, kres = NSS_CASES[name]
+    sp = banded_subproblem(503, 400, 520, 300, 0) if gen == "banded" else equality_rich_subproblem(*gen)
+    n = sp["n"]
+    if dep:      # row 5 = 2 x row 3, entry by entry (the generator deals per_row = 4 entries to every row)
+        sp["j_col"], sp["dE"] = sp["j_col"].copy(), sp["dE"].copy()
+        sp["j_col"][20:24], sp["dE"][20:24] = sp["j_col"][12:16], 2.0 * sp["dE"][12:16]
+        sp["c_lb"], sp["c_ub"] = sp["c_lb"].copy(), sp["c_ub"].copy()
+        sp["c_lb"][5] = sp["c_ub"][5] = 2.0 * sp["c_lb"][3]
+    fm = np.ones(n)
+    rng = np.random.default_rng(1000 + max(nfix, 0))
+    if nfix > 0:
+        fm[rng.choice(n, nfix, replace=False)] = 0.0
+    elif nfix < 0:      # free: the column every equality row owns (a permuted identity: full row rank) and one more
+        neq = gen[2]
+        own = np.asarray(sp["j_col"])[np.arange(neq) * 4] - 1
+        fm[:] = 0.0
+        fm[own] = 1.0
+        fm[np.nonzero(fm == 0)[0][7]] = 1.0
+    return sp, fm, kres
