@@ -98,6 +98,16 @@ class KktStepInfo(C.Structure):
                 ("norm_normal", C.c_double), ("norm_step", C.c_double), ("model", C.c_double)]
 
 
+class KktFormInfo(C.Structure):
+    """asm_kkt_form_info: the form asked for and used by the last KKT call (0 dense, 1 sparse), the bandwidth and structural pairs of S in
+    the order used, whether the order came from the cache, the device bytes of each form's own buffers, host milliseconds of the ordering."""
+    _fields_ = [("form_requested", C.c_int32), ("form_used", C.c_int32), ("band", C.c_int32), ("order_reused", C.c_int32),
+                ("n_pairs", C.c_int64), ("dense_bytes", C.c_int64), ("sparse_bytes", C.c_int64), ("order_ms", C.c_double)]
+
+
+KKT_FORMS = {"dense": 0, "sparse": 1}
+
+
 class EqpInfo(C.Structure):
     """asm_eqp_info: asm_kkt_step_info's fields; skipped 0 none, 1 more working rows than free variables, 2 dependent working rows,
     3 zero step; t, the norms of d = t dx, the merit function at x and at x + d."""
@@ -157,6 +167,8 @@ PROTOTYPES = {
     "asm_solution_sensitivity_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_kkt_step": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.c_double, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
     "asm_kkt_step_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
+    "asm_kkt_set_form": (C.c_int, [_P, C.c_int32]),
+    "asm_kkt_form_info": (C.c_int, [_P, C.POINTER(KktFormInfo)]),
     "asm_eval_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
     "asm_eval_hessian_lagrangian": (C.c_int, [_P, _D, C.c_double, _D, _D]),
     "asm_eval_hessian_product": (C.c_int, [_P, _D, C.c_double, _D, _D, _D]),

@@ -89,6 +89,14 @@ def slp_params(par, max_lp_solves=0):
 NATIVE_ALGORITHMS = ("Line Search", "Trust Region", "SLP-EQP")      # asm_slp_run, asm_slp_run_tr, asm_slp_run_eqp and their batch forms
 
 
+def check_batch_kkt_form(par):
+    """The sparse form of the KKT solve is per handle only (asm_kkt_set_form): the scenario batches run the dense form, and a Parameters
+    object that asks for the sparse one is refused before anything is built or run."""
+    if getattr(par, "kkt_form", "dense") != "dense":
+        raise ValueError("Parameters(kkt_form=%r): the scenario batches (asm_batch_*) run the dense form of the KKT solve only - the sparse form "
+                         "is per handle (SlpEQP, optimize(native=True), HipSubOptimizer.set_kkt_form)" % (par.kkt_form,))
+
+
 def slp_eqp_params(par):
     """asm_slp_eqp_params from a `Parameters` object: `eqp_radius` None is `tr_size` (as SlpEQP)."""
     from . import _lib
@@ -242,6 +250,7 @@ class HipBatch:
         f64 = lambda a_: np.ascontiguousarray(a_, np.float64)
         g_L, g_U, x_L, x_U, x0 = map(f64, (g_L, g_U, x_L, x_U, x0))
         S = x0.shape[0]
+        check_batch_kkt_form(parameters)
         assert g_L.shape == (S, self.m) and g_U.shape == (S, self.m) and x_L.shape == (S, self.n) and x_U.shape == (S, self.n) and x0.shape == (S, self.n)
         if parameters.algorithm not in NATIVE_ALGORITHMS:
             raise ValueError("the native drivers are run!(::SlpLS), run!(::SlpTR) and SLP-EQP, not %r" % parameters.algorithm)
@@ -378,6 +387,7 @@ def lagrangian_hessians(hb, runs, sparse=False):
 def solve_batch_lockstep(problems, parameters, n_slots, device=0, rank=0, world=1, reduce_device=None, batch=None):
     """The scenarios of this rank (`problems`: list of Problems with one pattern, built from FunctionModels) through a HipBatch of `n_slots`
     slots; returns (runs, reduced statistics, batch statistics) like `solve_batch`.  `batch`: an existing HipBatch to re-use."""
+    check_batch_kkt_form(parameters)
     own = batch is None
     if own:
         batch = HipBatch(problems[0], min(int(n_slots), len(problems)), device)
@@ -423,6 +433,7 @@ def claim_chunks(total, chunk, store=None, key="asm_batch_next"):
 def solve_batch_dynamic(problem_of, total, parameters, n_slots, batch, chunk=None, store=None, reduce_device=None):
     """Lockstep batch with dynamic assignment: this rank claims chunks of `chunk` scenarios (default: n_slots) until the counter runs out;
     `problem_of(s)` returns the Problem of scenario s.  Returns ({scenario: NativeRun}, reduced statistics)."""
+    check_batch_kkt_form(parameters)
     chunk = int(chunk or n_slots)
     t0 = time.perf_counter()
     mine = {}

@@ -247,7 +247,7 @@ struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` col
     double *vec = nullptr, *row = nullptr, *dlf = nullptr;      // 14 blocks cap x ldn over the variables, 5 cap x ldT over the working rows, cap x Mp over all rows
     double* rad = nullptr;                                      // cap trust-region radii (asm_kkt_step)
     double* stage = nullptr;                                    // pinned: [ru | rw | directions] of a chunk, then its results
-    double *Lt = nullptr, *AfT = nullptr;                       // cap > 1, the block products' own operands: the transposed factor, the unmasked transposed working rows
+    double *Lt = nullptr, *AfT = nullptr;                       // cap > 1, the block products' own operands: the transposed factor, the unmasked transposed working rows (dense form only)
 };
 struct KktBufs {
     bool ready = false;
@@ -260,6 +260,25 @@ struct KktBufs {
     double *part = nullptr, *scal = nullptr;
     unsigned *cnt = nullptr, *act = nullptr;
     KktWork one, blk;
+    // the form of the products and of S (asm_kkt_set_form) and what the last call did (asm_kkt_form_info)
+    int form = ASM_KKT_DENSE;
+    struct asm_kkt_form_info last{};
+    bool dense_ready = false, sparse_ready = false;
+    int64_t dense_bytes = 0, sparse_bytes = 0;      // device bytes of the buffers only the one form has
+    // The factor is shared by the two forms, and the banded kernels never clear outside the band they are given, so the sparse branch of
+    // KktFace clears explicitly: fac_full_rows = the leading rows of fac.S that a call may have filled over their whole width (a dense
+    // call, or a sparse one whose band was too wide to use), fac_band_hw = the widest band a banded call has used since the buffer was made
+    int64_t fac_full_rows = 0;
+    int fac_band_hw = 0;
+    // sparse form: the CSR values of the Jacobian at x, the place of every LP row in the order of the working rows, the structural pairs of S;
+    // the order cache: the last row_state with its order (host), band and pairs (the device lists above are its device side)
+    double* sp_vals = nullptr;
+    int *wpos = nullptr, *pairs = nullptr;
+    int64_t pairs_cap = 0, n_pairs = 0;
+    std::vector<int32_t> c_state;
+    std::vector<int> c_order;
+    int c_band = 0;
+    bool c_valid = false;
     // asm_eqp_trial (eq_prepare): [the LP's row_state (M) | its bound_state (n) | twin (m) || row_state (m) | bound_state (n) | counts (4) ||
     // side (m)], [rw (m) | dx (n) | d (n) | scalars (EQP_SCAL)], and the pinned image of both followed by n doubles for the gradient
     int* eq_i = nullptr;
@@ -524,6 +543,7 @@ struct Skeleton {
     int *d_sp_ptr = nullptr, *d_sp_col = nullptr, *d_sc_ptr = nullptr, *d_sc_row = nullptr, *d_sc_pos = nullptr;
     int64_t* d_sp_off = nullptr;
     double *d_spv_Ah = nullptr, *d_spv_J = nullptr;
+    std::vector<int> sp_ptr_h, sp_col_h;      // host copy of the CSR pattern (sp_ok): the row orders made after the set-up read it (KktFace)
     bool nz_valid = false;
     int nz_T = 0, nz_pitch = 0;
     double nz_fraction = 1.0;       // executed share of the (tile pair, k-chunk) products of the Schur build
@@ -3441,6 +3461,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
         P.upload(K.d_sp_ptr, sp_ptr.data(), K.M + 1); P.upload(K.d_sp_col, sp_col.data(), K.sp_nnz); P.upload(K.d_sp_off, sp_off.data(), K.sp_nnz);
         P.upload(K.d_sc_ptr, sc_ptr.data(), n + 1); P.upload(K.d_sc_row, sc_row.data(), K.sp_nnz); P.upload(K.d_sc_pos, sc_pos.data(), K.sp_nnz);
         P.alloc(K.d_spv_Ah, K.sp_nnz); P.alloc(K.d_spv_J, K.sp_nnz);
+        K.sp_ptr_h = sp_ptr; K.sp_col_h = sp_col;
         K.sp_ok = true;
     }
     const IpmLayout lay(n, K.M, K.ns);
@@ -4603,9 +4624,10 @@ static void do_data_cross(asm_handle* h, const double* x, const double* lambda, 
 }
 
 // ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set" and "Many right-hand sides on one factor"): one
-// set-up of the face (KktFace, steps 1 and 2), one driver of steps 3 to 6 on blocks of columns (kkt_columns) and, behind KktOps, the two
-// ways to multiply and solve: KktOneColumn for asm_kkt_solve and asm_solution_sensitivity, KktBlock for the multi entries.  The entry
-// point chooses, not nrhs: a column's bits do not depend on the number of columns beside it.
+// set-up of the face (KktFace, steps 1 and 2), one driver of steps 3 to 6 on blocks of columns (kkt_columns) and, behind KktOps, the
+// ways to multiply and solve: KktOneColumn for asm_kkt_solve and asm_solution_sensitivity, KktBlock for the multi entries, and KktSparse
+// for both where the handle's form is ASM_KKT_SPARSE (asm_kkt_set_form).  The entry point and the form choose, not nrhs: a column's bits
+// do not depend on the number of columns beside it.
 static_assert(KKM_CW == ASM_KKT_CHUNK && KKM_CW % 32 == 0 && KKM_SCAL > KKM_ITERS, "the chunk width of the header is the kernels'");
 namespace {
 // once per asm_eval_setup, at the first KKT solve: what steps 1 and 2 fill, sized for every working set the problem admits, and the
@@ -4620,9 +4642,6 @@ void kk_prepare(asm_handle* h) {
     K.capW = std::max<int64_t>(std::min(h->sk->m, h->sk->n), 1);
     K.ldT = round_up(K.capW, 32);
     M.alloc(K.dE, h->sk->nnz);
-    M.zeroed(K.J, Mp * ldn, s);
-    M.zeroed(K.Aw, K.capW * ldn, s);
-    M.zeroed(K.AwT, ldn * K.ldT, s);
     ns_alloc_factor(h, M, K.fac, K.capW);
     M.zeroed(K.sets, ldn + (Mp + 1) / 2, s);
     M.alloc(K.h_sets, ldn + (Mp + 1) / 2, BufPool::PINNED);
@@ -4634,24 +4653,69 @@ void kk_prepare(asm_handle* h) {
     HIPCHK(asmb::sync(s));
     K.ready = true;
 }
-// the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it
-KktWork* kk_work(asm_handle* h, int64_t cap) {
+// what only the dense form needs, at its first call: the solve's own dense J, A = J[W, F] and its transposed copy (a handle that only
+// ever runs the sparse form never makes them)
+void kk_dense(asm_handle* h) {
+    kk_prepare(h);
+    KktBufs& K = h->ev->kk;
+    if (K.dense_ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->ev->mem;
+    const hipStream_t s = h->stream;
+    const int64_t ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32);
+    M.zeroed(K.J, Mp * ldn, s);
+    M.zeroed(K.Aw, K.capW * ldn, s);
+    M.zeroed(K.AwT, ldn * K.ldT, s);
+    K.dense_bytes += (Mp * ldn + K.capW * ldn + ldn * K.ldT) * (int64_t)sizeof(double);
+    HIPCHK(asmb::sync(s));
+    K.dense_ready = true;
+}
+// what only the sparse form needs, at its first call: the CSR values, the position list and the pair buffer.  The pairs of any working
+// set are a subset of the pairs of all m rows: the buffer is sized once from those.  False: rcm_order declines the pattern (RCM_MAX_PAIRS)
+// and the call runs the dense form.
+bool kk_sparse(asm_handle* h) {
+    kk_prepare(h);
+    KktBufs& K = h->ev->kk;
+    if (K.sparse_ready) return K.pairs_cap > 0;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->ev->mem;
+    const hipStream_t s = h->stream;
+    const Skeleton& S = *h->sk;
+    K.sparse_ready = true;
+    std::vector<int> all((size_t)S.m), prs;
+    for (int64_t i = 0; i < S.m; ++i) all[i] = (int)i;
+    int bw = 0;
+    (void)rcm_order(all, S.sp_ptr_h, S.sp_col_h, S.ldn, &bw, &prs);
+    if (S.m > 0 && prs.empty()) return false;
+    K.pairs_cap = std::max<int64_t>((int64_t)prs.size() / 2, 1);
+    M.zeroed(K.sp_vals, S.sp_nnz, s);
+    M.alloc(K.pairs, 2 * K.pairs_cap);
+    M.alloc(K.wpos, std::max<int64_t>(S.M, 1));
+    K.sparse_bytes += S.sp_nnz * (int64_t)sizeof(double) + (2 * K.pairs_cap + std::max<int64_t>(S.M, 1)) * (int64_t)sizeof(int);
+    HIPCHK(asmb::sync(s));
+    return true;
+}
+// the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it; the unmasked transposed working rows of the dense
+// block products at the first dense call
+KktWork* kk_work(asm_handle* h, int64_t cap, bool sparse = false) {
     kk_prepare(h);
     KktBufs& K = h->ev->kk;
     KktWork& W = cap == 1 ? K.one : K.blk;
-    if (W.cap != 0) return &W;
     HIPCHK(hipSetDevice(h->device));
     BufPool& M = h->ev->mem;
     const hipStream_t s = h->stream;
     const int64_t ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32), nd = std::max<int64_t>(h->ev->n_dpar, 1);
+    if (cap > 1 && !sparse && !W.AfT) {
+        M.zeroed(W.AfT, ldn * K.ldT, s);
+        K.dense_bytes += ldn * K.ldT * (int64_t)sizeof(double);
+        HIPCHK(asmb::sync(s));
+    }
+    if (W.cap != 0) return &W;
     M.zeroed(W.vec, 14 * cap * ldn, s);
     M.zeroed(W.row, 5 * cap * K.ldT, s);
     M.zeroed(W.dlf, cap * Mp, s);
     M.zeroed(W.rad, cap, s);
-    if (cap > 1) {
-        M.zeroed(W.Lt, K.fac.ld * K.fac.ld, s);
-        M.zeroed(W.AfT, ldn * K.ldT, s);
-    }
+    if (cap > 1) M.zeroed(W.Lt, K.fac.ld * K.fac.ld, s);
     M.alloc(W.stage, cap * (3 * ldn + K.ldT + Mp + KKM_SCAL + nd) + 64, BufPool::PINNED);
     HIPCHK(asmb::sync(s));
     W.cap = cap;
@@ -4692,13 +4756,53 @@ struct KktFace {
     // that the launches of scenarios whose working sets differ by a few rows have one shape and merge (Sched::same)
     int64_t nWg = 0;
     double rtol = 0.0;
-    std::vector<int> wl;                                // the working rows, ascending (Mp entries, 0 beyond |W|)
+    // the working rows (Mp entries, 0 beyond |W|): ascending in the dense form, in the reverse Cuthill-McKee order of their coupling graph in
+    // the sparse form.  Everything that touches working rows goes through this list or its device copy.
+    std::vector<int> wl;
     const double* mask = nullptr;                       // 1.0 on F, 0.0 on B and beyond n (ldn)
     const int* wrow = nullptr;                          // wl on the device
+    bool sparse = false;                                // the form of this call (asm_kkt_set_form and the fallback rules)
     // the checks every entry shares (`me` names the caller in the messages) and steps 1 and 2 of the method
     KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
             const asm_kkt_params* par);
 };
+// Sparse form: puts f.wl into the reverse Cuthill-McKee order of the working rows' coupling graph and leaves the pairs of S and the position
+// list on the device, the band and the counts in K.last.  The order, band and pairs of the last row_state are kept: an equal row_state
+// reuses them (and what is on the device) - the structure of S over W does not depend on F.
+void kk_order(asm_handle* h, KktFace& f, const int32_t* row_state) {
+    KktBufs& K = h->ev->kk;
+    const Skeleton& S = *h->sk;
+    const int64_t m = S.m, nW = f.nW;
+    const bool hit = K.c_valid && (int64_t)K.c_state.size() == m && std::equal(row_state, row_state + m, K.c_state.begin());
+    if (!hit) {
+        K.c_valid = false;      // (until the new order and both device lists are in place)
+        const double t0 = Solver::now_ms();
+        const std::vector<int> rows(f.wl.begin(), f.wl.begin() + nW);
+        std::vector<int> prs;
+        int bw = 0;
+        K.c_order.clear();
+        if (nW > 0) {
+            const std::vector<int> ord = rcm_order(rows, S.sp_ptr_h, S.sp_col_h, S.ldn, &bw, &prs);
+            if ((int64_t)prs.size() / 2 > K.pairs_cap || prs.empty()) throw HipError("asm_kkt: the pairs of a working set outgrow the pairs of all rows");
+            K.c_order.resize((size_t)nW);
+            for (int64_t q = 0; q < nW; ++q) K.c_order[q] = rows[ord[q]];
+        }
+        K.c_band = nW > 0 ? std::max(bw, 1) : 0;
+        K.n_pairs = (int64_t)prs.size() / 2;
+        K.c_state.assign(row_state, row_state + m);
+        std::vector<int> wpos((size_t)std::max<int64_t>(S.M, 1), -1);
+        for (int64_t q = 0; q < nW; ++q) wpos[K.c_order[q]] = (int)q;
+        HIPCHK(asmb::copy_async(K.wpos, wpos.data(), wpos.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (!prs.empty()) HIPCHK(asmb::copy_async(K.pairs, prs.data(), prs.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+        K.c_valid = true;
+        K.last.order_ms = Solver::now_ms() - t0;
+    }
+    for (int64_t q = 0; q < nW; ++q) f.wl[q] = K.c_order[q];
+    K.last.band = K.c_band;
+    K.last.n_pairs = K.n_pairs;
+    K.last.order_reused = hit ? 1 : 0;
+}
 KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                  const asm_kkt_params* par) {
     const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn;
@@ -4721,24 +4825,34 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     // (a slot of a scenario batch has both made before its fiber starts - batch_kkt_prepare: no allocation, no list building in a round)
     hs_prepare(h);
     kk_prepare(h);
-    HIPCHK(hipSetDevice(h->device));
     KktBufs& K = h->ev->kk;
+    // the form: sparse when asked for and possible - a sparse pattern that rcm_order accepts - else dense, which is not an error
+    f.sparse = K.form == ASM_KKT_SPARSE && h->sk->sp_ok && kk_sparse(h);
+    if (!f.sparse) kk_dense(h);
+    HIPCHK(hipSetDevice(h->device));
     const hipStream_t s = h->stream;
     const int64_t Mp = std::max<int64_t>(h->sk->Mp, 32);
+    K.last = {};
+    K.last.form_requested = K.form;
+    K.last.form_used = f.sparse ? ASM_KKT_SPARSE : ASM_KKT_DENSE;
     // 1. the Hessian values of f - lambda' g at x, once: they stay in d_hs_vals for every product of the call (x goes to d_ev_xt)
     {
         std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
         for (int64_t i = 0; i < m; ++i) nl[i] = -lambda[i];
         hs_launch(h, x, 1.0, nl.data(), nullptr);      // (copies nl into the pinned staging buffer before it returns)
     }
-    // 2. the Jacobian at x: values into a buffer of the solve's own, assembled into its own dense J (the LP's dE and J stay)
+    // 2. the Jacobian at x: values into a buffer of the solve's own, assembled into its own dense J (the LP's dE and J stay) or, sparse
+    // form, summed into the CSR list of the pattern: its first nu entries are the unique entries in k_assemble's order
     {
         const FnStore& F = h->ev->F;
         if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->ev->d_xt, h->ev->d_Et, K.dE, 1, (int64_t)0, (int64_t)0);
         const ExprTape& X = h->ev->X;
         if (h->ev->nlp_kind == ASM_NLP_EXPR && X.R > 0)
             asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
-        if (h->sk->dense_fast) {
+        if (f.sparse) {
+            const unsigned g = (unsigned)std::min<int64_t>((h->sk->nu + 255) / 256, 4096);
+            asmb::launch(k_kkts_vals, dim3(g), dim3(256), s, (const double*)K.dE, (const int64_t*)h->sk->d_perm, (const int64_t*)h->sk->d_ustart, h->sk->nu, K.sp_vals);
+        } else if (h->sk->dense_fast) {
             const unsigned g = (unsigned)std::min<int64_t>((h->sk->m * h->sk->n + 255) / 256, 4096);
             asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, K.dE, K.J, h->sk->m, h->sk->n, ldn);
         } else if (h->sk->nu > 0) {
@@ -4754,6 +4868,7 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         int64_t q = 0;
         for (int64_t i = 0; i < m; ++i)
             if (row_state[i]) f.wl[q++] = (int)i;
+        if (f.sparse) kk_order(h, f, row_state);
         std::memcpy(st + ldn, f.wl.data(), Mp * sizeof(int));
         HIPCHK(asmb::copy_async(K.sets, st, ldn * sizeof(double) + Mp * sizeof(int), hipMemcpyHostToDevice, s));
         f.mask = K.sets;
@@ -4761,8 +4876,33 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     }
     // A = J[W, F] as a dense operand and its transposed copy with the k-padding cleared; S = A A' and its factor (Dev::chol leaves the
     // wide-block inverses too); the dropped pivots
-    if (nW > 0) {
+    if (nW > 0 && f.sparse) {
+        // S = A diag(mask) A' entry by entry from the structural pairs, after the band (or, a band too wide to use, the rows) is cleared;
+        // the factor is shared with the dense form: what an earlier call may have left outside this call's band is cleared here
+        const int band = K.last.band;
+        K.fac.band = 2 * (int64_t)band >= nW ? 0 : band;
+        if (K.fac_full_rows > 0) {
+            HIPCHK(asmb::fill_async(K.fac.S, 0, K.fac_full_rows * K.fac.ld * sizeof(double), s));
+            K.fac_full_rows = 0;
+        }
+        if (K.fac.band > 0) {
+            K.fac_band_hw = std::max(K.fac_band_hw, K.fac.band);
+            dev.zero_band(K.fac, (int)nW, K.fac_band_hw);
+        } else {
+            HIPCHK(asmb::fill_async(K.fac.S, 0, nW * K.fac.ld * sizeof(double), s));
+            K.fac_full_rows = std::min<int64_t>(round_up(nW, 64), K.fac.ld);
+        }
+        asmb::launch(k_ns_s0_sparse, asmb::blocks(K.n_pairs), dim3(256), s, (const int*)K.pairs, K.n_pairs, (const int*)h->sk->d_sp_ptr, (const int*)h->sk->d_sp_col,
+                     (const double*)K.sp_vals, f.wrow, f.mask, K.fac.S, K.fac.ld);
+        dev.diag_prepare(K.fac, (int)nW, 1, 0.0, 0.0);
+        const int nfact = h->stats.nfact;
+        dev.chol(K.fac, (int)nW, 1e-10);
+        h->stats.nfact = nfact;
+        asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, K.fac.S, K.fac.ld, (int)nW, NS_BIG, K.dropped);
+    } else if (nW > 0) {
         const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
+        K.fac.band = 0;
+        K.fac_full_rows = std::max(K.fac_full_rows, std::min<int64_t>(round_up(nW, 64), K.fac.ld));
         asmb::launch(k_kkt_gather, dim3(asmb::blocks(ldn).x, (unsigned)f.nWg), dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, K.Aw);
         asmb::launch(k_kktm_gather_t, gt, dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, f.nWp, K.AwT, K.ldT);
         dev.launch_syrk(s, Dev::pick_tile(nW), K.Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, K.fac.S, K.fac.ld, 0, 0);
@@ -4854,6 +4994,56 @@ struct KktBlock final : KktOps {
         return t;
     }
     void jt_dlam(const double* dlw, const double*, double* jtl, int cols) override { dev.gemm_nt(dlw, ldT, w.AfT, ldT, nullptr, 0, jtl, ldn, cols, (int)ldn, (int)f.nWp, 0); }
+};
+// the sparse form, for both capacities: the products with A and A' from the CSR / CSC lists of the pattern and the values KktFace summed
+// into them, for every number of columns (k_kkts_mul_a, k_kkts_mul_at: the column in blockIdx.y); J_W' dlam_W is the transposed product
+// without the mask.  The Hessian products and the substitutions are those of the dense back end of the same capacity, on the banded factor:
+// chol_solve_dev for one column, trsm_rows with a transposed copy of the band for a block.
+struct KktSparse final : KktOps {
+    static constexpr int LA = 4, LAT = 8;      // lanes per working row / per variable ("KKT solve: the sparse form")
+    KktSparse(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww) : KktOps(hh, d, ff, ww) {
+        if (w.cap == 1) return;
+        const KktBufs& K = h->ev->kk;
+        const int64_t nW = f.nW;
+        if (nW > 0) {
+            // (the rows of Lt up to |W| rounded up to 32 are cleared whole: whatever an earlier call, of either form, transposed into them goes)
+            HIPCHK(asmb::fill_async(w.Lt, 0, f.nWp * K.fac.ld * sizeof(double), s));
+            asmb::launch(k_transpose_dense, dim3((unsigned)((nW + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, K.fac.S, K.fac.ld, nW, nW, w.Lt, K.fac.ld,
+                         K.fac.band > 0 ? (int64_t)K.fac.band : nW);
+        }
+        HIPCHK(asmb::fill_async(w.row, 0, 5 * w.cap * ldT * sizeof(double), s));
+    }
+    void hess(const double* v, double* out, int cols) override {
+        const HsShared& L = *h->ev->hs_sh;
+        const dim3 g = asmb::blocks(n);
+        if (w.cap == 1) asmb::launch(k_hess_product, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
+        else if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+    }
+    void mul_A(const double* v, double* t, int cols) override {
+        const Skeleton& S = *h->sk;
+        asmb::launch(k_kkts_mul_a<LA>, dim3(asmb::blocks(f.nWg * LA).x, (unsigned)cols), dim3(256), s, (const int*)S.d_sp_ptr, (const int*)S.d_sp_col, (const double*)h->ev->kk.sp_vals,
+                     f.wrow, f.mask, v, ldn, f.nW, t, ldT);
+    }
+    void at(const double* y, const double* mask, double* v, int cols) {
+        const Skeleton& S = *h->sk;
+        asmb::launch(k_kkts_mul_at<LAT>, dim3(asmb::blocks(ldn * LAT).x, (unsigned)cols), dim3(256), s, (const int*)S.d_sc_ptr, (const int*)S.d_sc_row, (const int*)S.d_sc_pos,
+                     (const double*)h->ev->kk.sp_vals, (const int*)h->ev->kk.wpos, mask, y, ldT, n, ldn, v, ldn);
+    }
+    void mul_AT(const double* y, double* v, int cols) override { at(y, f.mask, v, cols); }
+    double* solve_S(const double* b, double* t, int cols) override {
+        if (w.cap == 1) {
+            double* const out = b == t ? spare : t;
+            dev.chol_solve_dev(h->ev->kk.fac, b, out, (int)f.nW);
+            return out;
+        }
+        if (b != t) HIPCHK(asmb::copy_async(t, b, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
+        dev.trsm_rows(h->ev->kk.fac, t, spare, ldT, cols, (int)f.nW, w.Lt);
+        return t;
+    }
+    void jt_dlam(const double* dlw, const double*, double* jtl, int cols) override { at(dlw, nullptr, jtl, cols); }
 };
 
 // Steps 3 to 6 for nrhs columns in chunks of the work area's capacity.  sens false: the rows of RU, RW are the right-hand sides;
@@ -5051,10 +5241,15 @@ static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, c
     if (!x || !bound_state || !ru || !dx || !info || (h->sk->m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
     Dev dev(h);
     const KktFace f(h, dev, "asm_kkt_solve", x, lambda, row_state, bound_state, par);
-    KktOneColumn ops(h, dev, f, *kk_work(h, 1));
     int64_t rounds;
     int last_active;
-    kkt_columns(h, f, ops, 1, ru, rw, nullptr, false, lambda, dx, dlam, dz, info, rounds, last_active);
+    if (f.sparse) {
+        KktSparse ops(h, dev, f, *kk_work(h, 1, true));
+        kkt_columns(h, f, ops, 1, ru, rw, nullptr, false, lambda, dx, dlam, dz, info, rounds, last_active);
+    } else {
+        KktOneColumn ops(h, dev, f, *kk_work(h, 1));
+        kkt_columns(h, f, ops, 1, ru, rw, nullptr, false, lambda, dx, dlam, dz, info, rounds, last_active);
+    }
 }
 static void do_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
                                     const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
@@ -5078,8 +5273,13 @@ static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, 
     if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->sk->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
     Dev dev(h);
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par);
-    KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
-    kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
+    if (f.sparse) {
+        KktSparse ops(h, dev, f, *kk_work(h, KKM_CW, true));
+        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
+    } else {
+        KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
+        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
+    }
 }
 // asm_kkt_step (one column through KktOneColumn) and asm_kkt_step_multi (KktBlock): the checks of asm_kkt_solve(_multi), then
 // those of the radii and the share
@@ -5102,7 +5302,12 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
     const asm_kkt_params kp{par ? par->max_iter : 0, par ? par->rtol : 0.0};
     Dev dev(h);
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par ? &kp : nullptr);
-    if (multi) {
+    if (f.sparse) {
+        KktSparse ops(h, dev, f, *kk_work(h, multi ? KKM_CW : 1, true));
+        int64_t rounds;
+        int last_active;
+        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, multi ? h->ev->kkm_rounds : rounds, multi ? h->ev->kkm_last_active : last_active, tr);
+    } else if (multi) {
         KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
         kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, h->ev->kkm_rounds, h->ev->kkm_last_active, tr);
     } else {
@@ -5177,6 +5382,23 @@ int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double*
     });
 }
 
+int asm_kkt_set_form(asm_handle* h, int32_t form) {
+    return guarded(h, [&] {
+        EvalState& e = ev_of(h, "asm_kkt_set_form");
+        if (form != ASM_KKT_DENSE && form != ASM_KKT_SPARSE) throw std::invalid_argument("asm_kkt_set_form: form is neither ASM_KKT_DENSE nor ASM_KKT_SPARSE");
+        e.kk.form = form;
+    });
+}
+int asm_kkt_form_info(const asm_handle* h, struct asm_kkt_form_info* out) {
+    if (!h || !out) return ASM_ERR_ARG;
+    if (!h->ev) return ASM_ERR_STATE;
+    const KktBufs& K = h->ev->kk;
+    *out = K.last;
+    out->form_requested = K.form;
+    out->dense_bytes = K.dense_bytes;
+    out->sparse_bytes = K.sparse_bytes;
+    return ASM_OK;
+}
 int asm_kkt_step(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru, const double* rw,
                  double radius, const asm_kkt_step_params* par, double* dx, double* dlam, double* dz, asm_kkt_step_info* info) {
     return guarded(h, [&] { do_kkt_step(h, "asm_kkt_step", false, x, lambda, row_state, bound_state, 1, ru, rw, &radius, par, dx, dlam, dz, info); });
@@ -7255,6 +7477,7 @@ void batch_kkt_prepare(asm_batch* b, int count) {
         in_slot("asm_slp_run_eqp", s, [&] {
             asm_handle* h = b->slots[s];
             if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
+            kk_dense(h);
             (void)kk_work(h, 1);
             eq_prepare(h);
         });

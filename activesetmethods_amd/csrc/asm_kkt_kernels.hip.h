@@ -7,8 +7,8 @@
 // vector length alone, so a column's bits depend neither on the number of columns nor on its place among them.
 // The products with A, A' and H and the substitutions with S = A A' are not here: the host has two back ends for them (KktOneColumn:
 // k_gemv_n, k_gemv_n_exact, k_gemv_t_stage*, k_hess_product and the factor's own substitution; KktBlock: k_gemm_nt through Dev::gemm_nt
-// and Dev::trsm_rows, and k_kktm_hess_product below).  A and S are dense: the sparse, banded and null-space forms of the LP solver have
-// no counterpart.
+// and Dev::trsm_rows, and k_kktm_hess_product below) for the dense form and a third, KktSparse, for the sparse form: its value assembly
+// and its products with A and A' are at the end of this file.
 // Blocks over the variables are zero beyond n and on the bound set B (mask[j] = 0 there).
 // Dot products: every workgroup of a column reduces its share (wavefront shuffles, then LDS), stores its partial sums with agent-scope
 // stores and counts itself in; the last one to arrive adds the partials in workgroup order - a fixed order, no atomics on doubles - and
@@ -360,4 +360,60 @@ __global__ __launch_bounds__(1024) void k_kktm_finish(AsmBt abt, double* __restr
         scal[c * KKM_SCAL + KK_RFEAS] = rf;
         if (dx) { scal[c * KKM_SCAL + KKM_MODEL] = lin + 0.5 * quad; scal[c * KKM_SCAL + KKM_NSTEP] = sqrt(sq); }
     }
+}
+
+// ---- the sparse form (asm_kkt_set_form, ASM_KKT_SPARSE): A = J[W, F] stays in the skeleton's CSR / CSC pattern, the working rows in the
+// reverse Cuthill-McKee order of their coupling graph (wrow lists them in that order, wpos[i] is the place of row i in it, -1: not in W).
+// The products run on the same row-major blocks as the dense back ends.  Mapping ("KKT solve: the sparse form"): the outputs
+// of ONE right-hand side along the lanes, LANES lanes per output walking its entry list, the right-hand side in blockIdx.y.  A wavefront
+// then reads neighbouring outputs' lists (contiguous) and gathers from one row of the block (neighbouring rows of a banded order share
+// columns); lanes across the right-hand sides would read the block with stride ldv, one cache line per lane.  A sum runs in an order
+// fixed by the list and LANES alone - entries k, k + LANES, ... per lane, then an xor tree - so a column's bits depend neither on the
+// number of columns nor on its place; no atomics.
+
+// vals[u] = sum of dE over the duplicates of unique Jacobian entry u (k_assemble's sum, without a dense J): the first nu entries of the
+// CSR list are the unique entries in the same order
+__global__ __launch_bounds__(256) void k_kkts_vals(AsmBt abt, const double* __restrict__ dE, const int64_t* __restrict__ perm, const int64_t* __restrict__ ustart, int64_t nu, double* __restrict__ vals) {
+    ASM_BARGS(abt, dE, perm, ustart, nu, vals);
+    for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < nu; u += (int64_t)gridDim.x * blockDim.x) {
+        double acc = 0.0;
+        for (int64_t k = ustart[u]; k < ustart[u + 1]; ++k) acc = acc + dE[perm[k]];
+        vals[u] = acc;
+    }
+}
+// T[c, q] = sum over the CSR list of row wrow[q] of val_k mask[col_k] V[c, col_k], q < nW (the k-padding of T beyond nW is not written)
+template <int LANES>
+__global__ __launch_bounds__(256) void k_kkts_mul_a(AsmBt abt, const int* __restrict__ ptr, const int* __restrict__ col, const double* __restrict__ val, const int* __restrict__ wrow, const double* __restrict__ mask, const double* __restrict__ V, int64_t ldv, int64_t nW, double* __restrict__ T, int64_t ldt) {
+    ASM_BARGS(abt, ptr, col, val, wrow, mask, V, ldv, nW, T, ldt);
+    const int64_t c = blockIdx.y, q = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LANES;
+    const int sub = threadIdx.x & (LANES - 1);
+    const double* v = V + c * ldv;
+    double acc = 0.0;
+    if (q < nW) {
+        const int r = wrow[q];
+        for (int k = ptr[r] + sub; k < ptr[r + 1]; k += LANES) {
+            const int j = col[k];
+            acc += val[k] * mask[j] * v[j];
+        }
+    }
+    _Pragma("unroll") for (int o = LANES / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (sub == 0 && q < nW) T[c * ldt + q] = acc;
+}
+// V[c, j] = mask[j] * sum over the CSC list of column j of val Y[c, wpos[row]], rows outside W skipped (mask == nullptr: no mask, J_W' y
+// over all variables); 0 for n <= j < ldn
+template <int LANES>
+__global__ __launch_bounds__(256) void k_kkts_mul_at(AsmBt abt, const int* __restrict__ cptr, const int* __restrict__ row, const int* __restrict__ pos, const double* __restrict__ val, const int* __restrict__ wpos, const double* __restrict__ mask, const double* __restrict__ Y, int64_t ldy, int64_t n, int64_t ldn, double* __restrict__ V, int64_t ldv) {
+    ASM_BARGS(abt, cptr, row, pos, val, wpos, mask, Y, ldy, n, ldn, V, ldv);
+    const int64_t c = blockIdx.y, j = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LANES;
+    const int sub = threadIdx.x & (LANES - 1);
+    const double* y = Y + c * ldy;
+    double acc = 0.0;
+    if (j < n && (!mask || mask[j] != 0.0)) {
+        for (int k = cptr[j] + sub; k < cptr[j + 1]; k += LANES) {
+            const int p = wpos[row[k]];
+            if (p >= 0) acc += val[pos[k]] * y[p];
+        }
+    }
+    _Pragma("unroll") for (int o = LANES / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (sub == 0 && j < ldn) V[c * ldv + j] = acc;
 }

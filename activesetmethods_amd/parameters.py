@@ -35,6 +35,21 @@ class Parameters:
     eqp_radius_max: float = 1.e+3
     eqp_tol_active: float = 1.e-8
     eqp: bool = True
+    # not in the reference: the form of the KKT solves behind the SLP-EQP step (asm_kkt_set_form) - "dense" or "sparse" (sparse products, a
+    # banded factor of A A' in a reverse Cuthill-McKee order of the working rows).  Per handle only: the scenario batches refuse "sparse".
+    kkt_form: str = "dense"
+
+    def __post_init__(self):
+        check_kkt_form(self.kkt_form)
+
+
+KKT_FORMS = ("dense", "sparse")
+
+
+def check_kkt_form(form):
+    if form not in KKT_FORMS:
+        raise ValueError("kkt_form = %r: expected \"dense\" or \"sparse\"" % (form,))
+    return form
 
 
 def get_parameter(params, pname):          # src/parameters.jl:31-33

@@ -17,7 +17,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .parameters import Parameters
+from .parameters import Parameters, check_kkt_form
 from .subproblem import HipSubOptimizer, QpData
 
 INF = np.inf
@@ -108,6 +108,9 @@ class AbstractSlpOptimizer:
             self.optimizer = factory(data, pr.j_row, pr.j_col)
             if self._fm is not None:
                 self.optimizer.eval_setup(self._fm)
+                form = check_kkt_form(getattr(self.options, "kkt_form", "dense"))
+                if form != "dense":                 # (a stand-in optimizer without the entry keeps its one form)
+                    self.optimizer.set_kkt_form(form)
         else:
             self.optimizer.data = data                                                      # slp.jl:38-40
         if upload and not self._uploaded:
@@ -486,6 +489,7 @@ def _optimize_native(model, max_lp_solves=None):
                           model.j_row, model.j_col)
     try:
         opt.eval_setup(fm)
+        opt.set_kkt_form(check_kkt_form(getattr(par, "kkt_form", "dense")))
         run = opt.slp_run(model.x, par, max_lp_solves or 0)
     finally:
         opt.close()

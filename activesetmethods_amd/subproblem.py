@@ -313,6 +313,21 @@ class HipSubOptimizer:
             raise ValueError("give max_iter and rtol together (asm_kkt_params), or neither for the defaults")
         return C.byref(_lib.KktParams(int(max_iter), float(rtol)))
 
+    def set_kkt_form(self, form):
+        """asm_kkt_set_form: "dense" (the default) or "sparse" for every later KKT entry on this handle - kkt_solve, kkt_step, their multi
+        forms, the sensitivities, eqp_trial and the native SLP-EQP driver.  Needs eval_setup, and the next eval_setup starts from "dense"
+        again.  Without a sparse pattern the sparse form runs the dense one and says so in kkt_form_info().form_used."""
+        if form not in _lib.KKT_FORMS:
+            raise ValueError("kkt form %r: expected one of %s" % (form, ", ".join(repr(k) for k in _lib.KKT_FORMS)))
+        self._check(self._lib.asm_kkt_set_form(self._h, _lib.KKT_FORMS[form]))
+
+    def kkt_form_info(self):
+        """The asm_kkt_form_info structure of the last KKT call on this handle: form_requested, form_used (0 dense, 1 sparse), band, n_pairs,
+        order_reused, dense_bytes, sparse_bytes, order_ms."""
+        info = _lib.KktFormInfo()
+        self._check(self._lib.asm_kkt_form_info(self._h, C.byref(info)))
+        return info
+
     def kkt_solve(self, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=None):
         """(dx, dlam, dz, info) of asm_kkt_solve: the KKT system of the working set (row_state 0 / 1, bound_state -1 / 0 / +1) at (x, lam)
         with the right-hand sides (-ru, -rw); info is the asm_kkt_info structure (status 0 solved, 1 iteration limit, 2 reduced Hessian

@@ -349,8 +349,9 @@ int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, 
  * the returned solution.
  * Everything runs on the handle's stream in buffers of the solve's own, which live as long as the evaluator (until the next asm_eval_setup,
  * asm_sublp_setup or asm_destroy): the
- * inputs of the next LP (dE, df, E, x_k), the retained basis, hints and active sets and the solver's factors do not change.  A and
- * S = A A' are DENSE; the sparse, banded and null-space forms of the LP solver have no counterpart here.
+ * inputs of the next LP (dE, df, E, x_k), the retained basis, hints and active sets and the solver's factors do not change.  In the
+ * default form, described here, A and S = A A' are dense; asm_kkt_set_form (below, "The form of the KKT solve") selects a sparse form
+ * with sparse products and a banded factor.
  * Method:
  *   1. the Hessian values at (x, 1, -lambda), once; the Jacobian at x into a value buffer and a dense J of the solve's own
  *   2. A gathered into a dense |W| x ldn operand with the columns of B zeroed; S = A A' by the rank-K build, factored by the library's
@@ -470,6 +471,39 @@ int asm_kkt_step(asm_handle* h, const double* x, const double* lambda, const int
 int asm_kkt_step_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                        int32_t nrhs, const double* RU, const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX,
                        double* DLAM, double* DZ, asm_kkt_step_info* info);
+
+/* ---- The form of the KKT solve: dense (the default, the method text above) or sparse.  Per handle only: the scenario batches
+ * (asm_batch_*) run the dense form whatever is set here.
+ * asm_kkt_set_form chooses the form of every later KKT entry on the handle - asm_kkt_solve(_multi), asm_solution_sensitivity(_multi),
+ * asm_kkt_step(_multi), asm_eqp_trial and asm_slp_run_eqp - until the next asm_eval_setup, which starts from ASM_KKT_DENSE again.  Valid
+ * after asm_eval_setup (ASM_ERR_STATE before); a form other than the two below: ASM_ERR_ARG.
+ * ASM_KKT_SPARSE replaces steps 1 and 2 and the products of the method; the driver of steps 3 to 6, its kernels, statuses and outputs stay:
+ *   1. the Jacobian values go from the value buffer into the CSR list of the LP's sparse pattern (one kernel; no dense J)
+ *   2. the working rows are taken in the reverse Cuthill-McKee order of their coupling graph (two rows are coupled when they share a
+ *      column); S = A A' is built entry by entry from its structural pairs, as the null-space form builds S0, and is banded in that
+ *      order: the factorisation and the substitutions stop at the band.  A band of half the order or more is factored as a dense matrix.
+ *      The order, band and pairs of the last row_state are kept and reused when the next call's row_state is equal (the structure of S over
+ *      W does not depend on F).
+ *   The products with A and A' are sparse (k_kkts_mul_a over the CSR lists of the working rows, k_kkts_mul_at over the CSC lists of the
+ *   variables, for 1 to ASM_KKT_CHUNK columns); the substitutions are the factor's own (one column) or Dev::trsm_rows with a transposed
+ *   copy of the band (blocks).  The column independence of the multi entries holds as stated above.  Against the dense form the agreement
+ *   is to tolerance (other summation orders, another row order in the factor); dlam is returned by row as ever.
+ * Fallback, not an error: when the handle has no sparse pattern (a dense model, fill above 1/16) or the pattern's coupling graph is too
+ * dense to order (RCM_MAX_PAIRS), a call with ASM_KKT_SPARSE set runs the dense form and says so in form_used.
+ * Memory: a handle that only ever runs the sparse form never allocates the dense J, A, its transposed copy and the unmasked transposed
+ * rows (dense_bytes == 0); the factor (pitch^2 doubles, not band storage) and the blocks are shared by the forms.
+ * asm_kkt_form_info describes the last KKT call on the handle (all zero but form_requested before the first). */
+enum { ASM_KKT_DENSE = 0, ASM_KKT_SPARSE = 1 };
+struct asm_kkt_form_info {     /* a tag, not a typedef: the entry below has the same name */
+    int32_t form_requested, form_used;   /* ASM_KKT_* */
+    int32_t band;              /* bandwidth of S in the order used (at least 1 when |W| > 0); 0: dense form */
+    int32_t order_reused;      /* 1: the row order came from the cache */
+    int64_t n_pairs;           /* structural entries of the lower triangle of S, diagonal included */
+    int64_t dense_bytes, sparse_bytes;   /* device bytes of the buffers that only the dense / only the sparse form has made on this handle */
+    double order_ms;           /* host milliseconds the call spent on the row order (0 when reused) */
+};
+int asm_kkt_set_form(asm_handle* h, int32_t form);
+int asm_kkt_form_info(const asm_handle* h, struct asm_kkt_form_info* out);
 
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
