@@ -480,6 +480,8 @@ struct HandleKnobs {
     int panel_wgs = 0;              // ASM_PANEL_WGS: grid bound of the panel kernels on the whole device (0: by the device's CU count)
     bool ns_defer = true;           // ASM_NS_DEFER=0: the step of a null-space iteration is taken on the host
     bool ns_side = true;            // ASM_NS_SIDE=0: the factor-independent head of a null-space iteration stays on the handle's stream (Solver::ns_iter_setup)
+    int ns_s0side = 2;              // ASM_NS_S0SIDE: what of the null-space set-up runs on the side stream beside the factorisation of a banded S0 (Solver::ns_factor_S0) -
+                                    // 0 nothing; 1 the previous basis' right-hand sides, the wide-block inverses and the transposed copy; 2 the forward substitution as well
     bool ns_fold = true;            // ASM_NS_FOLD=0: k_ns_add and k_ns_dp of a null-space Newton solve are launches of their own (k above ASM_SMALL_USE)
     double ns_rerr = NS_RERR;       // ASM_NS_RERR: accuracy bound of the reduced solves of a null-space iteration (test knob - a tiny bound
                                     // sends every LP through the fall-back to the row form)
@@ -492,6 +494,7 @@ HandleKnobs read_knobs() {
     if (const char* v = std::getenv("ASM_PANEL_WGS")) k.panel_wgs = std::max(1, std::atoi(v));
     if (const char* v = std::getenv("ASM_NS_DEFER")) k.ns_defer = v[0] != '0';
     if (const char* v = std::getenv("ASM_NS_SIDE")) k.ns_side = v[0] != '0';
+    if (const char* v = std::getenv("ASM_NS_S0SIDE")) if (v[0] >= '0' && v[0] <= '2') k.ns_s0side = v[0] - '0';
     if (const char* v = std::getenv("ASM_NS_FOLD")) k.ns_fold = v[0] != '0';
     if (const char* v = std::getenv("ASM_NS_RERR")) k.ns_rerr = std::atof(v);
     return k;
@@ -611,6 +614,9 @@ struct asm_handle {
     // factorisation (Solver::ns_iter_setup); fork / join events, made with the first fork
     hipStream_t stream_ns = nullptr;
     hipEvent_t ns_fork = nullptr, ns_join = nullptr;
+    // events of the set-up's side sequence beside the factorisation of S0 (Solver::ns_factor_S0): fork, join, then one per wide block; made
+    // once per handle as the list grows, like la_events
+    std::vector<hipEvent_t> s0_events;
     std::string err;
     // owners of the device / pinned buffers, one per lifetime: the LP skeleton with the null-space form inside it (until the next set-up; null:
     // no set-up yet, or the last one failed), the device evaluator (until the next asm_eval_setup or set-up; null: none).  What follows
@@ -721,6 +727,9 @@ struct Dev {
         if (h->regions.empty()) return;
         HIPCHK(asmb::sync(h->stream));
         HIPCHK(asmb::sync(h->stream2));
+        // (stream_ns is not synchronised: no timed region is ever on it.  Its sequences - ns_iter_setup, ns_factor_S0 - are off under family
+        // timing (timing == 2) and the kinds timed at level 1, ASM_K_SYRK_KERNEL and ASM_K_PANEL_KERNEL, are not launched there; a timed
+        // launch on the side stream would need a synchronisation here before its events are read)
         for (auto& r : h->regions) {
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
@@ -896,20 +905,22 @@ struct Dev {
             schur_syrk(false, F.Eidx, nE, F.Fm, nullptr, F.f0.S, F.f0.ld, NzFlags::PerCall, 1);
         }
     }
-    // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32
-    void gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, const double* C0, int64_t ldc0, double* C, int64_t ldc, int Ma, int Mb, int K, int mode) {
+    // C = (C0) -/+ A B'  on the matrix cores (k_gemm_nt); K a multiple of 32.  on: the stream (null: the handle's)
+    void gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, const double* C0, int64_t ldc0, double* C, int64_t ldc, int Ma, int Mb, int K, int mode,
+                 hipStream_t on = nullptr) {
         if (Ma <= 0 || Mb <= 0) return;
-        int id = begin(ASM_K_TRSV, 2.0 * Ma * (double)Mb * K, 8.0 * ((double)(Ma + Mb) * K + (double)Ma * Mb));
+        hipStream_t s = on ? on : h->stream;
+        int id = begin(ASM_K_TRSV, 2.0 * Ma * (double)Mb * K, 8.0 * ((double)(Ma + Mb) * K + (double)Ma * Mb), s);
         // 64 x 64 tiles leave CUs idle when there are few right-hand sides: 32-row tiles then (same sums, same order)
         const int64_t t64 = (int64_t)((Mb + 63) / 64) * ((Ma + 63) / 64);
         // ... and 96 columns per workgroup when 32 x 64 tiles overshoot one workgroup per CU and 32 x 96 tiles do not
         const int64_t t3264 = (int64_t)((Mb + 63) / 64) * ((Ma + 31) / 32), t3296 = (int64_t)((Mb + 95) / 96) * ((Ma + 31) / 32);
         if (t64 < 2 * (int64_t)h->num_cus && Ma > 32 && t3264 > h->num_cus && t3296 <= h->num_cus)
-            asmb::launch(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
+            asmb::launch(k_gemm_nt32w, dim3((unsigned)((Mb + 95) / 96), (unsigned)((Ma + 31) / 32)), dim3(256), s, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         else if (t64 < 2 * (int64_t)h->num_cus && Ma > 32)
-            asmb::launch(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
+            asmb::launch(k_gemm_nt32, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 31) / 32)), dim3(256), s, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         else
-            asmb::launch(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), h->stream, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
+            asmb::launch(k_gemm_nt, dim3((unsigned)((Mb + 63) / 64), (unsigned)((Ma + 63) / 64)), dim3(256), s, A, lda, B, ldb, C0, ldc0, C, ldc, Ma, Mb, K, mode);
         end(id);
     }
     // Rows of R (nrhs x ldr, zero beyond column Ms) are right-hand sides of  L x = r  (forward) and then  L' x = z  (backward) with the
@@ -918,14 +929,22 @@ struct Dev {
     // remaining columns  R[:, rest] -= X_blk L[rest, blk]'  (K = the block width, every tile of the remainder in parallel) - both on the
     // matrix cores.  Forward: R -> X.  Backward (if Lt): X -> R.  The solution ends in R (backward) or X (forward only).
     void trsm_rows(const FacBuf& f, double* R, double* X, int64_t ldr, int nrhs, int Ms, const double* Lt) {
+        const int nB = (Ms + f.wb - 1) / f.wb;
+        for (int B = 0; B < nB; ++B) trsm_rows_fwd_step(f, R, X, ldr, nrhs, Ms, B);
+        if (Lt) trsm_rows_bwd(f, R, X, ldr, nrhs, Ms, Lt);
+    }
+    // step B of the forward half: it needs the inverse of wide block B, column block B of the factor and step B - 1 - not the rest of the
+    // factor, so it can follow a banded factorisation one wide block behind (Solver::ns_factor_S0).  on: the stream (null: the handle's)
+    void trsm_rows_fwd_step(const FacBuf& f, double* R, double* X, int64_t ldr, int nrhs, int Ms, int B, hipStream_t on = nullptr) {
+        const int WB = f.wb;
+        const int b0 = B * WB, wv = std::min(WB, Ms - b0), b1 = b0 + wv, Kb = (int)round_up(wv, 32);
+        gemm_nt(R + b0, ldr, f.Binv + (int64_t)B * WB * WB, WB, nullptr, 0, X + b0, ldr, nrhs, wv, Kb, 0, on);
+        if (b1 < Ms) gemm_nt(X + b0, ldr, f.S + (int64_t)b1 * f.ld + b0, f.ld, R + b1, ldr, R + b1, ldr, nrhs, rowlim(f, Ms, b1) - b1, Kb, 1, on);
+    }
+    // the backward half: X -> R
+    void trsm_rows_bwd(const FacBuf& f, double* R, double* X, int64_t ldr, int nrhs, int Ms, const double* Lt) {
         const int WB = f.wb;
         const int nB = (Ms + WB - 1) / WB;
-        for (int B = 0; B < nB; ++B) {
-            const int b0 = B * WB, wv = std::min(WB, Ms - b0), b1 = b0 + wv, Kb = (int)round_up(wv, 32);
-            gemm_nt(R + b0, ldr, f.Binv + (int64_t)B * WB * WB, WB, nullptr, 0, X + b0, ldr, nrhs, wv, Kb, 0);
-            if (b1 < Ms) gemm_nt(X + b0, ldr, f.S + (int64_t)b1 * f.ld + b0, f.ld, R + b1, ldr, R + b1, ldr, nrhs, rowlim(f, Ms, b1) - b1, Kb, 1);
-        }
-        if (!Lt) return;
         for (int B = nB - 1; B >= 0; --B) {
             const int b0 = B * WB, wv = std::min(WB, Ms - b0), Kb = (int)round_up(wv, 32);
             gemm_nt(X + b0, ldr, f.BinvT + (int64_t)B * WB * WB, WB, nullptr, 0, R + b0, ldr, nrhs, wv, Kb, 0);
@@ -1104,28 +1123,41 @@ struct Dev {
             diag_prepare(fN, k, 0, rel, absv, diag0);
         }
     }
+    // explicit inverses (and their transposed copies) of the wide blocks B0 .. B1-1 on stream `on` (null: the handle's).  A block's launches
+    // read its own rows of the factor and its own 64 x 64 block inverses and write its own Binv / BinvT (BinvT is the levels' scratch first)
     template <int WB>
-    void trtri_launches(const FacBuf& f, int Ms) {
+    void trtri_launches(const FacBuf& f, int Ms, int B0, int B1, hipStream_t on = nullptr) {
         constexpr int WSUB = WB / ASM_NB;
-        const unsigned nW = (unsigned)((Ms + WB - 1) / WB);
-        asmb::launch((k_trtri_init<WB>), dim3(nW, WSUB * WSUB), dim3(256), h->stream, f.Linv, Ms, f.Binv);
+        hipStream_t s = on ? on : h->stream;
+        if (B1 <= B0) return;
+        const unsigned nW = (unsigned)(B1 - B0);
+        asmb::launch((k_trtri_init<WB>), dim3(nW, WSUB * WSUB), dim3(256), s, f.Linv, Ms, f.Binv, B0);
         for (int hh = 1; hh < WSUB; hh *= 2)
             for (int stage = 0; stage < 2; ++stage)
-                asmb::launch((k_trtri_level<WB>), dim3(nW, (unsigned)(WSUB / (2 * hh)), (unsigned)(hh * hh)), dim3(256), h->stream, f.S, f.ld, Ms, f.Binv, f.BinvT, hh, stage);
-        asmb::launch((k_transpose_wb<WB>), dim3(nW, WSUB * WSUB), dim3(256), h->stream, f.Binv, f.BinvT);
+                asmb::launch((k_trtri_level<WB>), dim3(nW, (unsigned)(WSUB / (2 * hh)), (unsigned)(hh * hh)), dim3(256), s, f.S, f.ld, Ms, f.Binv, f.BinvT, hh, stage, B0);
+        asmb::launch((k_transpose_wb<WB>), dim3(nW, WSUB * WSUB), dim3(256), s, f.Binv, f.BinvT, B0);
     }
+    void trtri_blocks(const FacBuf& f, int Ms, int B0, int B1, hipStream_t on = nullptr) {
+        if (f.wb == 1024) trtri_launches<1024>(f, Ms, B0, B1, on); else trtri_launches<512>(f, Ms, B0, B1, on);
+    }
+    // called by chol_launches_band after each panel launch: columns < I1 of the factor (and their 64 x 64 block inverses) are final, which
+    // completes the first `done` wide blocks
+    using PanelDone = std::function<void(int I1, int done)>;
     // want_inverse = false: the caller only solves against the factor and the factor is a "small" one (one-workgroup solves): the
     // explicit inverses of the wide blocks are not built
-    void chol(const FacBuf& f, int Ms, double thr = 1e-14, bool want_inverse = true) {
+    // progress (only for a factor that band_panels_ok accepts): told after every panel launch how far the factor is final; its owner makes
+    // the explicit inverses of the wide blocks as they complete (trtri_blocks), none are launched here
+    void chol(const FacBuf& f, int Ms, double thr = 1e-14, bool want_inverse = true, const PanelDone* progress = nullptr) {
         if (Ms <= 0) return;
+        if (progress && !band_panels_ok(f, Ms)) throw std::logic_error("Dev::chol: panel progress is reported by the band-panel factorisation only");
         // a banded factor (band b) costs about Ms (b + 64)^2 flops and touches Ms (b + 64) entries, not Ms^3 / 3 and Ms^2 / 2
         const double bw = f.band > 0 ? (double)std::min<int64_t>(Ms, (int64_t)f.band + 64) : (double)Ms;
         int id = begin(ASM_K_CHOL, f.band > 0 ? (double)Ms * bw * bw : (double)Ms * Ms * Ms / 3.0, 8.0 * 1.5 * Ms * bw);
         const bool skip_inv = !want_inverse && f.small && Ms <= ASM_SMALL_USE;
         // a factor of ONE wide block gets its explicit inverse inside the panel launches (helper workgroups of k_chol_panel_inv)
         const bool panel_inv = !skip_inv && Ms <= f.wb && f.band == 0 && f.Binv && f.BinvT && panel_inv_grid(Ms) <= h->panel_wgs;
-        chol_launches(f, Ms, thr, panel_inv);
-        if (skip_inv || panel_inv) {
+        if (progress) chol_launches_band(f, Ms, thr, progress); else chol_launches(f, Ms, thr, panel_inv);
+        if (skip_inv || panel_inv || progress) {
             end(id);
             h->stats.nfact += 1;
             return;
@@ -1133,7 +1165,7 @@ struct Dev {
         // explicit inverses of the wide diagonal blocks by divide and conquer over the 64-wide sub-blocks: diagonal
         // blocks from the panel kernels, then log2 levels of two launches each (the scratch T uses the buffer of the
         // transposed copy, which is written afterwards)
-        if (f.wb == 1024) trtri_launches<1024>(f, Ms); else trtri_launches<512>(f, Ms);
+        trtri_blocks(f, Ms, 0, (Ms + f.wb - 1) / f.wb);
         end(id);
         h->stats.nfact += 1;
     }
@@ -1207,7 +1239,7 @@ struct Dev {
         const int m = nrt - CHOL_NBI / ASM_NB;
         return nrt <= ASM_PNL_NRT && nrt + m * (m + 1) / 2 <= h->panel_wgs;
     }
-    void chol_launches_band(const FacBuf& f, int Ms, double thr) {
+    void chol_launches_band(const FacBuf& f, int Ms, double thr, const PanelDone* progress = nullptr) {
         for (int I0 = 0, I1 = 0; I0 < Ms; I0 = I1) {
             I1 = (Ms - I0 <= CHOL_NBI + 2 * ASM_NB) ? Ms : I0 + CHOL_NBI;
             const int Mi = rowlim(f, Ms, I1);
@@ -1224,6 +1256,9 @@ struct Dev {
             asmb::launch_resident(k_chol_panel_band, dim3((unsigned)(nrt + nhelp)), dim3(256), h->stream, f.S, f.ld, I0, I1, Mi, sk().d_diag0, thr, f.Linv, sk().d_pflags, sk().d_ptmo,
                                   h->panel_epoch, nrt);
             end(pid);
+            // the launch applied its whole trailing update and later launches write columns >= I1 only: a wide block is complete once I1 has
+            // reached its end (the last one with the last launch, which may have absorbed a remainder)
+            if (progress) (*progress)(I1, I1 >= Ms ? (Ms + f.wb - 1) / f.wb : I1 / f.wb);
         }
     }
     void chol_launches(const FacBuf& f, int Ms, double thr, bool panel_inv) {
@@ -1769,14 +1804,18 @@ struct Solver {
     // The k rows in K.G (an approximate or an outdated basis) projected onto null(A_EF) of THIS LP and orthonormalised with their own
     // Gram matrix (pivot guard `thr`, absolute), then GI' = (A_I Z)'.  Used as the second pass of ns_basis_from and, with the previous
     // LP's basis, as the whole set-up (oracle: NullSpace.__init__, warm_Z).  The factor of S0 must be current in F.f0.
-    bool ns_reproject(int k, double thr) {
+    // head_done: how much of it the side sequence of ns_factor_S0 has made already for these k rows (0 nothing, 1 the right-hand sides in
+    // K.R, 2 the forward half of the substitution as well)
+    bool ns_reproject(int k, double thr, int head_done = 0) {
         const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int nE = (int)F.L.nE, nEp = (int)F.L.nEp;
         const double* vals = dev.sparse_vals(sk().d_Ah);
         // second pass (oracle: NullSpace.basis_from): project the rows once more and orthonormalise with their own Gram matrix (~ I) -
         // the columns picked in index order can be badly conditioned, and the active-set solves need A_EF Z = 0 to 1e-13
-        launch_ns_rows_e(vals, k);
-        dev.trsm_rows(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
+        if (head_done < 1) launch_ns_rows_e(vals, k);
+        if (head_done < 2)
+            for (int B = 0, nB = (nE + F.f0.wb - 1) / F.f0.wb; B < nB; ++B) dev.trsm_rows_fwd_step(F.f0, K.R, K.X, nEp, k, nE, B);
+        dev.trsm_rows_bwd(F.f0, K.R, K.X, nEp, k, nE, F.Lt);
         launch_ns_pj(vals, k, 1);
         launch_ns_gram(k);
         if (ns_factor_N(k, thr) > 0) return false;
@@ -1786,11 +1825,11 @@ struct Solver {
     }
     // the launch sites of the basis set-up (vals = dev.sparse_vals(sk().d_Ah), made by the caller before its first launch); each returns the
     // workgroups of its grid (x)
-    unsigned launch_ns_rows_e(const double* vals, int k) {      // R = (A_EF Zt')' for the k rows in K.G
+    unsigned launch_ns_rows_e(const double* vals, int k, hipStream_t on = nullptr) {      // R = (A_EF Zt')' for the k rows in K.G
         const NsForm& F = *sk().nsf; const NsK& K = *F.k;
         const int nEp = (int)F.L.nEp;
         const dim3 g((unsigned)((nEp + 255) / 256), (unsigned)k);
-        asmb::launch(k_ns_rows_e, g, dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, nsX(), F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
+        asmb::launch(k_ns_rows_e, g, dim3(256), on ? on : h->stream, sk().d_sp_ptr, sk().d_sp_col, vals, nsX(), F.Fm, K.G, F.L.ldg, K.R, (int64_t)nEp);
         return g.x;
     }
     unsigned launch_ns_pj(const double* vals, int k, int second_pass) {      // rows of the projector from W = K.R into K.G
@@ -1863,19 +1902,29 @@ struct Solver {
         const int64_t n = lp.n;
         int64_t nF = 0;
         for (int64_t j = 0; j < n; ++j) nF += lp.ub[j] > lp.lb[j];
-        const int dropped = ns_factor_S0();
+        // A banded S0 on the band-panel path with more than one wide block: what does not need the whole factor runs on the side stream beside
+        // its factorisation (ns_factor_S0).  Same exclusions as the side stream of the iterations (ns_iter_setup): not in a scenario batch,
+        // not under family timing.
+        S0Side side{h};
+        side.level = (F.f0.band > 0 && dev.band_panels_ok(F.f0, nE) && nE > F.f0.wb && h->stream_ns && !h->batch_slot && !asmb::in_fiber() && h->timing != 2)
+                         ? h->knobs.ns_s0side : 0;
+        const int dropped = ns_factor_S0(&side);
+        // joined here whatever follows: before ns_reserve (it may release the buffers the side sequence wrote), before the first launch that
+        // reads the inverses, the transposed copy, K.R or K.X, and before every return (the guard joins when an exception leaves ns_factor_S0)
+        side.join();
         ns_dropped = dropped;
         const int64_t k = nF - (nE - dropped);
         if (k < 1 || (double)k > 1.5 * NS_MAX_RATIO * (double)lp.M + 8.0) return false;
         ns_reserve((int)k);
         ns_bind();
-        ns_make_Lt();
+        if (!side.level) ns_make_Lt();
         std::vector<int>& J = cur_hint->ns_J;
         bool have = false;
         ns_was_cold = false;
         ns_path = 0;
         ns_vlap("Lt");
-        if (F.k->Zk == (int)k) have = ns_reproject((int)k, NS_ZWARM_THR);      // the previous LP's basis, one projection pass
+        // (the side sequence worked on the Zk rows of the previous basis before k was known: used if k == Zk, scratch that the other paths overwrite if not)
+        if (F.k->Zk == (int)k) have = ns_reproject((int)k, NS_ZWARM_THR, side.head_done);      // the previous LP's basis, one projection pass
         ns_vlap("reproject");
         F.k->Zk = 0;
         if (have) ns_path = 1;
@@ -1905,7 +1954,52 @@ struct Solver {
         ns_tv = t;
     }
     // head of ns_setup: the mask of the free columns from the LP's bounds, S0 and its guarded factor in F.f0; returns its dropped pivots
-    int ns_factor_S0() {
+    //
+    // side (ns_setup, level > 0; S0 banded, band-panel path, nB > 1 wide blocks): the work that does not need the whole factor goes to the side
+    // stream, beside the latency-bound panel chain that leaves most of the chip empty:
+    //   handle's stream:  S0 build, diag_prepare, FORK | panel launch, panel launch, EV_0, panel launch, ... , EV_nB-1 | count + read-back
+    //   side stream:      wait FORK, k_ns_rows_e (previous basis, Zk rows -> K.R) | wait EV_B: inverses of wide block B, then (level 2)
+    //                     forward step B of the substitution (K.R -> K.X) | ... | transposed copy of the factor, JOIN
+    // Hazards.  Columns < I1 of the factor and their 64 x 64 block inverses are final after the panel launch that ends at I1: it applies its
+    // whole trailing update itself and later launches write columns >= I1 only - the side sequence reads nothing else of the factor.  A block's
+    // inverse launches use that block's BinvT as scratch and end with its transposed copy, in this order on one stream; no other block's is
+    // touched.  d_vecM, d_diag0 and the panel flags belong to the chain; the side sequence uses none of them.  k_ns_rows_e reads the sparse
+    // values, Fm and K.G: all in place at the fork.  The rows are the PREVIOUS basis' (k is not known before the read-back): ns_setup uses
+    // K.R / K.X only if this LP's k equals Zk.  Host order: each panel launch is issued first, then what its event releases - behind a
+    // read-back the device follows the host launch by launch (ns_iter_setup).  The join is unconditional once the fork is recorded: nothing
+    // of the side sequence is in flight when ns_reserve re-makes the buffers, when K.G is rewritten or when the next LP clears the band.
+    // Residency.  k_chol_panel_band needs all its workgroups resident (they wait for each other's flags), and it now shares the chip with the
+    // side kernels, the chip-wide k_ns_rows_e beside its first launch among them.  It still makes progress: no side kernel waits for anything
+    // of a running panel launch (only for events recorded after finished ones), so every side workgroup ends by itself and frees its slot for
+    // the panel workgroups not yet dispatched; the delay is a side kernel's duration (0.3 ms at most) against the bound of the panel waits, 2^22 polls (pnl_wait: hundreds of ms).
+    struct S0Side {
+        asm_handle* h;
+        int level = 0;           // HandleKnobs::ns_s0side, or 0 where the sequence does not apply
+        int head_done = 0;       // what ns_reproject finds done for the Zk rows of the previous basis (its head_done)
+        bool forked = false, join_recorded = false, joined = false;
+        hipEvent_t ev(int i) {      // 0 fork, 1 join, 2 + B wide block B
+            while ((int)h->s0_events.size() <= i) {
+                hipEvent_t e;
+                HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                h->s0_events.push_back(e);
+            }
+            return h->s0_events[i];
+        }
+        void fork() { HIPCHK(hipEventRecord(ev(0), h->stream)); forked = true; HIPCHK(hipStreamWaitEvent(h->stream_ns, ev(0), 0)); }
+        void record_join() { HIPCHK(hipEventRecord(ev(1), h->stream_ns)); join_recorded = true; }
+        void join() {
+            if (!forked || joined) return;
+            if (!join_recorded) record_join();
+            HIPCHK(hipStreamWaitEvent(h->stream, h->s0_events[1], 0));
+            joined = true;
+        }
+        ~S0Side() {      // an exception between fork and join: the handle's stream still waits for what the side stream was given
+            if (!forked || joined || h->s0_events.size() < 2) return;
+            if (!join_recorded) (void)hipEventRecord(h->s0_events[1], h->stream_ns);
+            (void)hipStreamWaitEvent(h->stream, h->s0_events[1], 0);
+        }
+    };
+    int ns_factor_S0(S0Side* side = nullptr) {
         NsForm& F = *sk().nsf;
         const int nE = (int)F.L.nE;
         const int64_t n = lp.n;
@@ -1920,14 +2014,42 @@ struct Solver {
         dev.ns_build_S0();
         ns_vlap("S0 build");
         dev.diag_prepare(F.f0, nE, 1, 0.0, 0.0);
-        dev.chol(F.f0, nE, 1e-10);
+        if (!side || !side->level) {
+            dev.chol(F.f0, nE, 1e-10);
+            ns_vlap("S0 factor");
+            return ns_count_big(F.f0, nE);
+        }
+        hipStream_t ss = h->stream_ns;
+        const int nEp = (int)F.L.nEp, nB = (nE + F.f0.wb - 1) / F.f0.wb;
+        const int Zk = F.k ? F.k->Zk : 0;      // rows of the previous basis (0: none)
+        const double* vals = Zk > 0 ? dev.sparse_vals(sk().d_Ah) : nullptr;
+        side->ev(1 + nB);      // (the whole event list before the first launch)
+        side->fork();
+        int made = 0;          // wide blocks whose side launches are issued
+        bool first = true;
+        const Dev::PanelDone progress = [&](int, int done) {
+            if (first && Zk > 0) launch_ns_rows_e(vals, Zk, ss);
+            first = false;
+            if (done <= made) return;
+            HIPCHK(hipEventRecord(side->ev(2 + done - 1), h->stream));
+            HIPCHK(hipStreamWaitEvent(ss, side->ev(2 + done - 1), 0));
+            for (; made < done; ++made) {
+                dev.trtri_blocks(F.f0, nE, made, made + 1, ss);
+                if (side->level >= 2 && Zk > 0) dev.trsm_rows_fwd_step(F.f0, F.k->R, F.k->X, nEp, Zk, nE, made, ss);
+            }
+        };
+        dev.chol(F.f0, nE, 1e-10, true, &progress);
+        if (made != nB) throw std::logic_error("ns_factor_S0: the factorisation did not report every wide block");
+        ns_make_Lt(ss);
+        side->record_join();
+        side->head_done = Zk > 0 ? (side->level >= 2 ? 2 : 1) : 0;
         ns_vlap("S0 factor");
         return ns_count_big(F.f0, nE);
     }
-    void ns_make_Lt() {      // transposed copy of the factor of S0 (inside its band)
+    void ns_make_Lt(hipStream_t on = nullptr) {      // transposed copy of the factor of S0 (inside its band)
         NsForm& F = *sk().nsf;
         const int nE = (int)F.L.nE;
-        asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), h->stream, F.f0.S, F.f0.ld, (int64_t)nE, (int64_t)nE,
+        asmb::launch(k_transpose_dense, dim3((unsigned)((nE + 63) / 64), (unsigned)((nE + 63) / 64)), dim3(256), on ? on : h->stream, F.f0.S, F.f0.ld, (int64_t)nE, (int64_t)nE,
                      F.Lt, F.f0.ld, (int64_t)(F.f0.band > 0 ? F.f0.band : nE));
     }
     // the two buffers of the cold selection (ldn rows of nEp each): made by the first LP that needs them
@@ -3132,6 +3254,7 @@ struct Solver {
         ns_lp = false;
         h->stats.ns_dim = 0;
         h->stats.ns_cold = 0;
+        h->stats.ns_path = 0;
         if (ns_applicable()) {
             const size_t had = hint.ns_J.size();
             const double t0 = now_ms();
@@ -3139,6 +3262,7 @@ struct Solver {
             if (ns_lp) ns_lp_vectors();
             h->stats.ns_dim = ns_lp ? ns_k : 0;
             h->stats.ns_cold = (ns_lp && (had == 0 || ns_was_cold)) ? 1 : 0;
+            h->stats.ns_path = ns_lp ? ns_path : 0;
             if (h->knobs.verbose) {
                 HIPCHK(asmb::sync(h->stream));
                 std::fprintf(stderr, "[asm] null-space set-up: %s, k = %d, %s basis columns, %.2f ms\n", ns_lp ? "ok" : "not usable", ns_k, ns_was_cold ? "fresh" : "retained", now_ms() - t0);
@@ -3943,6 +4067,7 @@ int asm_destroy(asm_handle* h) {
     for (auto e : h->event_pool) (void)hipEventDestroy(e);
     h->ev.reset(); h->sk.reset();
     for (auto e : h->la_events) (void)hipEventDestroy(e);
+    for (auto e : h->s0_events) (void)hipEventDestroy(e);
     if (h->ns_fork) (void)hipEventDestroy(h->ns_fork);
     if (h->ns_join) (void)hipEventDestroy(h->ns_join);
     if (!h->batch_slot) {

@@ -1485,9 +1485,9 @@ __device__ __forceinline__ void trtri_init_tile(const double* __restrict__ Linv,
     }
 }
 template <int WB>
-__global__ __launch_bounds__(256) void k_trtri_init(AsmBt abt, const double* __restrict__ Linv, int Ms, double* __restrict__ Binv) {
-    ASM_BARGS(abt, Linv, Ms, Binv);
-    trtri_init_tile<WB>(Linv, Ms, Binv, blockIdx.x, blockIdx.y / (WB / ASM_NB), blockIdx.y % (WB / ASM_NB));
+__global__ __launch_bounds__(256) void k_trtri_init(AsmBt abt, const double* __restrict__ Linv, int Ms, double* __restrict__ Binv, int B0) {
+    ASM_BARGS(abt, Linv, Ms, Binv, B0);
+    trtri_init_tile<WB>(Linv, Ms, Binv, B0 + blockIdx.x, blockIdx.y / (WB / ASM_NB), blockIdx.y % (WB / ASM_NB));
 }
 template <int WB>
 __device__ __forceinline__ void trtri_level_tile(double* __restrict__ Pa, double* __restrict__ Qt, const double* __restrict__ L, int64_t ld, int Ms, double* __restrict__ Binv,
@@ -1553,11 +1553,11 @@ __device__ __forceinline__ void trtri_level_tile(double* __restrict__ Pa, double
         }
 }
 template <int WB>
-__global__ __launch_bounds__(256) void k_trtri_level(AsmBt abt, const double* __restrict__ L, int64_t ld, int Ms, double* __restrict__ Binv, double* __restrict__ Tbuf, int h, int stage) {
-    ASM_BARGS(abt, L, ld, Ms, Binv, Tbuf, h, stage);
+__global__ __launch_bounds__(256) void k_trtri_level(AsmBt abt, const double* __restrict__ L, int64_t ld, int Ms, double* __restrict__ Binv, double* __restrict__ Tbuf, int h, int stage, int B0) {
+    ASM_BARGS(abt, L, ld, Ms, Binv, Tbuf, h, stage, B0);
     __shared__ double Pa[ASM_NB * ASM_TP];      // left operand  P[r][k]
     __shared__ double Qt[ASM_NB * ASM_TP];      // right operand transposed  Qt[c][k] = Q[k][c]
-    trtri_level_tile<WB>(Pa, Qt, L, ld, Ms, Binv, Tbuf, h, stage, blockIdx.x, blockIdx.y, asm_bz(abt) / h, asm_bz(abt) % h);
+    trtri_level_tile<WB>(Pa, Qt, L, ld, Ms, Binv, Tbuf, h, stage, B0 + blockIdx.x, blockIdx.y, asm_bz(abt) / h, asm_bz(abt) % h);
 }
 
 // forward, wide block B:  z_B = X_B w_B   (one wavefront per row: 128 workgroups of 4 rows; all loads of a row in flight)
@@ -1744,10 +1744,10 @@ __device__ __forceinline__ void transpose_wb_tile(double* __restrict__ tile, con
     }
 }
 template <int WB>
-__global__ __launch_bounds__(256) void k_transpose_wb(AsmBt abt, const double* __restrict__ Binv, double* __restrict__ BinvT) {
-    ASM_BARGS(abt, Binv, BinvT);
+__global__ __launch_bounds__(256) void k_transpose_wb(AsmBt abt, const double* __restrict__ Binv, double* __restrict__ BinvT, int B0) {
+    ASM_BARGS(abt, Binv, BinvT, B0);
     __shared__ double tile[64 * 65];
-    transpose_wb_tile<WB>(tile, Binv, BinvT, blockIdx.x, blockIdx.y / (WB / ASM_NB), blockIdx.y % (WB / ASM_NB));
+    transpose_wb_tile<WB>(tile, Binv, BinvT, B0 + blockIdx.x, blockIdx.y / (WB / ASM_NB), blockIdx.y % (WB / ASM_NB));
 }
 
 // ---------------------------------------------------------------------------------------------------------------

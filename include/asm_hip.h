@@ -128,6 +128,8 @@ typedef struct {
     int32_t ns_cold;       /* 1: the basis columns were selected from scratch in this LP (0: the previous LP's columns were re-used) */
     int32_t restored;      /* 1: no interior-point stage ended in a successful polish and the last stage ended 10x worse than the best one - the best
                             * iterate was brought back for the final attempts (best-iterate safeguard) */
+    int32_t ns_path;       /* what made the basis of the null-space form in this LP: 1 the previous LP's basis re-projected, 2 the retained basis
+                            * columns, 3 the cold selection; 0: the form is not in use (the field fills what was padding: the layout is unchanged) */
     double  ipm_pinf, ipm_dinf, ipm_gap;
     double  kkt_pr, kkt_du;
     double  wall_ms;       /* host wall time of the solve */
