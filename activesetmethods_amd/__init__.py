@@ -7,7 +7,7 @@ from .parameters import Parameters, get_parameter, set_parameter
 from .status import ApplicationReturnStatus
 from .subproblem import QpData, HipSubOptimizer, AsmHipError
 from .slp import Model, SlpEQP, SlpLS, SlpTR, optimize
-from . import problems, nlexpr, sensitivity, eqp
+from . import problems, nlexpr, sensitivity, eqp, lmhess
 
 __all__ = ["Parameters", "get_parameter", "set_parameter", "ApplicationReturnStatus", "QpData", "HipSubOptimizer",
-           "AsmHipError", "Model", "SlpLS", "SlpTR", "SlpEQP", "optimize", "problems", "sensitivity", "eqp"]
+           "AsmHipError", "Model", "SlpLS", "SlpTR", "SlpEQP", "optimize", "problems", "sensitivity", "eqp", "lmhess"]

@@ -128,6 +128,16 @@ class SlpEqpInfo(C.Structure):
                 ("skipped_dependent", C.c_int32), ("skipped_zero", C.c_int32), ("cg_iters", C.c_int32), ("boundary", C.c_int32)]
 
 
+class LmInfo(C.Structure):
+    """asm_lm_info: the handle's Hessian type (0 exact, 1 limited-memory) and the limited-memory store - its memory, the pairs it holds,
+    whether a begin waits for its end, the pairs offered and refused since it was cleared, sigma, its device bytes."""
+    _fields_ = [("type", C.c_int32), ("memory", C.c_int32), ("pairs", C.c_int32), ("pending", C.c_int32), ("pushed", C.c_int64),
+                ("skipped_zero", C.c_int64), ("skipped_curvature", C.c_int64), ("sigma", C.c_double), ("bytes", C.c_int64)]
+
+
+HESSIAN_TYPES = {"exact": 0, "limited-memory": 1}
+LM_MAX = 32
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
@@ -183,6 +193,13 @@ PROTOTYPES = {
     "asm_eqp_trial": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_double, _D, C.c_double, C.POINTER(KktStepParams), _D, _D, _D, _D, _I32, _I32, C.POINTER(EqpInfo)]),
     "asm_slp_run_eqp": (C.c_int, [_P, C.POINTER(SlpParams), C.c_double, C.POINTER(SlpEqpParams), _D, _D, _D, _D, _D, _D, C.POINTER(SlpResult),
                                   C.POINTER(SlpTrInfo), C.POINTER(SlpEqpInfo)]),
+    "asm_hessian_set_type": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "asm_lm_reset": (C.c_int, [_P]),
+    "asm_lm_push_pair": (C.c_int, [_P, _D, _D]),
+    "asm_lm_begin": (C.c_int, [_P, _D]),
+    "asm_lm_end": (C.c_int, [_P, _D]),
+    "asm_lm_product": (C.c_int, [_P, _D, C.c_int32, _D]),
+    "asm_lm_info": (C.c_int, [_P, C.POINTER(LmInfo)]),
     "asm_batch_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
     "asm_batch_destroy": (C.c_int, [_P]),
     "asm_batch_last_error": (C.c_char_p, [_P]),

@@ -91,10 +91,14 @@ NATIVE_ALGORITHMS = ("Line Search", "Trust Region", "SLP-EQP")      # asm_slp_ru
 
 def check_batch_kkt_form(par):
     """The sparse form of the KKT solve is per handle only (asm_kkt_set_form): the scenario batches run the dense form, and a Parameters
-    object that asks for the sparse one is refused before anything is built or run."""
+    object that asks for the sparse one is refused before anything is built or run.  So is the limited-memory Hessian
+    (asm_hessian_set_type)."""
     if getattr(par, "kkt_form", "dense") != "dense":
         raise ValueError("Parameters(kkt_form=%r): the scenario batches (asm_batch_*) run the dense form of the KKT solve only - the sparse form "
                          "is per handle (SlpEQP, optimize(native=True), HipSubOptimizer.set_kkt_form)" % (par.kkt_form,))
+    if getattr(par, "hessian_type", "none") == "limited-memory":
+        raise ValueError("Parameters(hessian_type='limited-memory'): the scenario batches (asm_batch_*) use the model's own second derivatives - "
+                         "the limited-memory Hessian is per handle (SlpEQP, optimize(native=True), HipSubOptimizer.set_hessian_type)")
 
 
 def slp_eqp_params(par):

@@ -14,6 +14,7 @@
 #include "asm_eval_kernels.hip.h"
 #include "asm_kkt_kernels.hip.h"
 #include "asm_eqp_kernels.hip.h"
+#include "asm_lm_kernels.hip.h"
 #include "asm_batch.hip.h"
 #include "../../include/asm_hip.h"
 
@@ -603,6 +604,22 @@ struct Skeleton {
     BufPool mem;                    // declared last, as in EvalState
 };
 
+// The limited-memory Hessian of a handle (include/asm_hip.h, "Limited-memory Hessian").  The type and the memory survive a set-up; the
+// store is made at the first use after asm_sublp_setup (lm_store) and goes with the skeleton or the evaluator (drop): no ready flag.
+static_assert(LM_PMAX == ASM_LM_MAX && 2 * LM_PMAX <= 64, "the store's most pairs are the header's");
+struct LmState {
+    int type = ASM_HESS_EXACT, memory = 10;
+    bool pending = false;           // between asm_lm_begin and asm_lm_end
+    LmStore S{};                    // R == nullptr: not made
+    double *xs = nullptr, *gs = nullptr, *s = nullptr, *y = nullptr, *jtl = nullptr;      // the saved point and gradient, the new pair, J' lambda (ldn)
+    double *part_dot = nullptr, *part = nullptr;      // partial sums of the pair's three dots (3 per workgroup) and of T = V [S; Y]' (KKM_CW columns)
+    double *vb = nullptr, *ob = nullptr;              // asm_lm_product: a chunk of V and of OUT (made by its first call)
+    int ndot = 0, nwg = 0;          // workgroups of k_lm_pair_dots (`per` variables each) and of k_lm_psi_v
+    int64_t per = 0, bytes = 0;
+    BufPool mem;                    // declared last, as in EvalState
+    void drop() { mem.release(); S = LmStore{}; pending = false; bytes = 0; }
+};
+
 }  // namespace
 
 struct asm_handle {
@@ -623,6 +640,7 @@ struct asm_handle {
     // them survives a set-up.
     std::unique_ptr<Skeleton> sk;
     std::unique_ptr<EvalState> ev;
+    LmState lm;
     int test_band = 0;              // band of the matrices the kernel hooks load (test hook asm_test_set_band; 0 = dense)
     // test hook asm_test_set_factor: where the kernel hooks factor (0: the main factor, 1: a factor buffer of their own made by
     // ns_alloc_factor with this band hint) and the guard settings they factor with (k_diag_prepare mode / rel / absv, chol threshold)
@@ -3460,6 +3478,7 @@ void do_setup(asm_handle* h, int64_t n, int64_t m, int64_t nnz, const int64_t* j
     if (n <= 0 || m < 0 || nnz < 0 || (nnz > 0 && (!j_row || !j_col)) || (m > 0 && (!c_lb || !c_ub)) || !v_lb || !v_ub)
         throw std::invalid_argument("asm_sublp_setup: bad dimensions or null pointer");
     HIPCHK(hipSetDevice(h->device));
+    h->lm.drop();
     h->ev.reset(); h->sk.reset();   // released before anything is allocated; the new skeleton is built here and installed last: a failure leaves none
     auto sk = std::make_unique<Skeleton>();
     Skeleton& K = *sk;
@@ -4341,6 +4360,7 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     ExprHost xh;
     if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
     HIPCHK(hipSetDevice(h->device));
+    h->lm.drop();
     h->ev.reset();                  // the old evaluator goes before the new one is made; a failure below leaves the handle without one
     auto e = std::make_unique<EvalState>();
     BufPool& P = e->mem;
@@ -4748,6 +4768,157 @@ static void do_data_cross(asm_handle* h, const double* x, const double* lambda, 
     if (X.R > 0) std::memcpy(w + e.F.n_rows, back + n, X.R * sizeof(double));
 }
 
+// ---- limited-memory Hessian (include/asm_hip.h, "Limited-memory Hessian"; kernels in asm_lm_kernels.hip.h)
+namespace {
+void lm_clear(asm_handle* h) {
+    LmState& M = h->lm;
+    M.pending = false;
+    if (!M.S.R) return;
+    const LmStore& L = M.S;
+    const hipStream_t s = h->stream;
+    const int64_t P = L.P;
+    HIPCHK(asmb::fill_async(L.R, 0, 2 * P * L.ld * sizeof(double), s));
+    HIPCHK(asmb::fill_async(L.ss, 0, P * P * sizeof(double), s));
+    HIPCHK(asmb::fill_async(L.sy, 0, P * P * sizeof(double), s));
+    HIPCHK(asmb::fill_async(L.W, 0, 4 * P * P * sizeof(double), s));
+    asmb::launch(k_lm_clear, dim3(1), dim3(64), s, L);
+}
+// the handle's store, made empty at the first use after a set-up and sized from the handle's memory
+LmState* lm_store(asm_handle* h, const char* who) {
+    const Skeleton& K = sk_of(h, (std::string(who) + ": asm_sublp_setup first").c_str());
+    LmState& M = h->lm;
+    if (M.S.R) return &M;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& B = M.mem;
+    LmStore& L = M.S;
+    const int64_t n = K.n, ld = K.ldn, P = M.memory;
+    M.nwg = (int)std::max<int64_t>((n + LM_CHUNK - 1) / LM_CHUNK, 1);
+    M.ndot = (int)std::min<int64_t>(M.nwg, LM_DOTWG);
+    M.per = (n + M.ndot - 1) / M.ndot;
+    try {
+        B.alloc(L.R, 2 * P * ld); B.alloc(L.ss, P * P); B.alloc(L.sy, P * P); B.alloc(L.W, 4 * P * P); B.alloc(L.sigma, 1); B.alloc(L.st, LM_WORDS);
+        B.alloc(M.xs, n); B.alloc(M.gs, n); B.alloc(M.s, n); B.alloc(M.y, n); B.zeroed(M.jtl, ld, h->stream);
+        B.alloc(M.part_dot, 3 * LM_DOTWG); B.alloc(M.part, (int64_t)KKM_CW * M.nwg * 2 * P);
+        M.bytes = (2 * P * ld + 6 * P * P + 1 + 4 * n + ld + 3 * LM_DOTWG + (int64_t)KKM_CW * M.nwg * 2 * P) * (int64_t)sizeof(double) + LM_WORDS * (int64_t)sizeof(int);
+        L.n = n; L.ld = ld; L.P = (int)P; L.pad = 0;
+        lm_clear(h);
+        HIPCHK(asmb::sync(h->stream));
+    } catch (...) {
+        M.drop();      // (a store is whole or not there: R != nullptr is the test above)
+        throw;
+    }
+    return &M;
+}
+// the pair in M.s, M.y: the three dots, the skip rule, the rows, the Gram entries, Ws - five launches, nothing read back
+void lm_push(asm_handle* h) {
+    LmState& M = h->lm;
+    const LmStore& L = M.S;
+    const hipStream_t s = h->stream;
+    asmb::launch(k_lm_pair_dots, dim3((unsigned)M.ndot), dim3(256), s, M.s, M.y, L.n, M.per, M.part_dot);
+    asmb::launch(k_lm_pair_decide, dim3(1), dim3(64), s, L, M.part_dot, M.ndot);
+    asmb::launch(k_lm_pair_store, asmb::blocks(L.n), dim3(256), s, L, M.s, M.y);
+    asmb::launch(k_lm_pair_gram, dim3((unsigned)L.P), dim3(256), s, L);
+    asmb::launch(k_lm_middle, dim3(1), dim3(256), s, L);
+}
+// OUT = V B for cols <= KKM_CW rows of V on the device (pitches ldv, ldo; V and OUT apart): two launches
+void lm_product(asm_handle* h, const double* V, int64_t ldv, int cols, double* OUT, int64_t ldo) {
+    LmState& M = *lm_store(h, "asm_lm_product");
+    const LmStore& L = M.S;
+    asmb::launch(k_lm_psi_v, dim3((unsigned)M.nwg, (unsigned)((cols + LM_COLS - 1) / LM_COLS)), dim3(256), h->stream, L, V, ldv, cols, M.part);
+    asmb::launch(k_lm_apply, asmb::blocks(L.n), dim3(256), h->stream, L, V, ldv, cols, M.part, M.nwg, OUT, ldo);
+}
+// J' lambda into the store's own vector, by the route of asm_slp_norms: the Jacobian assembled from the last evaluation's values, lambda
+// padded with zeros on the extra range rows
+LmState* lm_jtl(asm_handle* h, const char* who, const double* lambda) {
+    const std::string me(who);
+    ev_of(h, who);
+    if (!h->sk->inputs_ready || !h->sk->inputs_from_eval) throw std::logic_error(me + ": asm_eval_functions first");
+    if (h->sk->m > 0 && !lambda) throw std::invalid_argument(me + ": null pointer");
+    LmState& M = *lm_store(h, who);
+    HIPCHK(hipSetDevice(h->device));
+    Dev d(h);
+    d.assemble();
+    d.h2d(h->sk->d_vecM, lambda, h->sk->m, h->sk->Mp);
+    d.launch_gemv_t(h->sk->d_J, h->sk->d_vecM, M.jtl);
+    return &M;
+}
+void do_lm_begin(asm_handle* h, const double* lambda) {
+    LmState& M = *lm_jtl(h, "asm_lm_begin", lambda);
+    const EvalState& e = *h->ev;
+    asmb::launch(k_lm_save, asmb::blocks(M.S.n), dim3(256), h->stream, e.d_x, e.d_df, M.jtl, M.S.n, M.xs, M.gs);
+    M.pending = true;
+    Dev(h).resolve_timing();
+}
+void do_lm_end(asm_handle* h, const double* lambda) {
+    ev_of(h, "asm_lm_end");
+    if (!h->lm.pending) return;
+    LmState& M = *lm_jtl(h, "asm_lm_end", lambda);
+    const EvalState& e = *h->ev;
+    asmb::launch(k_lm_diff, asmb::blocks(M.S.n), dim3(256), h->stream, e.d_x, e.d_df, M.jtl, M.xs, M.gs, M.S.n, M.s, M.y);
+    lm_push(h);
+    M.pending = false;
+    Dev(h).resolve_timing();
+}
+void do_lm_push_pair(asm_handle* h, const double* sv, const double* yv) {
+    if (!sv || !yv) throw std::invalid_argument("asm_lm_push_pair: null pointer");
+    LmState& M = *lm_store(h, "asm_lm_push_pair");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = M.S.n;
+    HIPCHK(asmb::copy_async(M.s, sv, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::copy_async(M.y, yv, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(asmb::sync(h->stream));      // (the caller's arrays are free again)
+    lm_push(h);
+}
+void do_lm_product(asm_handle* h, const double* V, int32_t nrhs, double* OUT) {
+    if (nrhs < 1) throw std::invalid_argument("asm_lm_product: nrhs < 1");
+    if (!V || !OUT) throw std::invalid_argument("asm_lm_product: null pointer");
+    LmState& M = *lm_store(h, "asm_lm_product");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = M.S.n, ld = M.S.ld;
+    if (!M.vb) {
+        M.mem.zeroed(M.vb, (int64_t)KKM_CW * ld, h->stream);
+        M.mem.zeroed(M.ob, (int64_t)KKM_CW * ld, h->stream);
+        M.bytes += 2 * (int64_t)KKM_CW * ld * (int64_t)sizeof(double);
+    }
+    for (int32_t c0 = 0; c0 < nrhs; c0 += KKM_CW) {
+        const int cols = (int)std::min<int32_t>(KKM_CW, nrhs - c0);
+        HIPCHK(hipMemcpy2DAsync(M.vb, ld * sizeof(double), V + (int64_t)c0 * n, n * sizeof(double), n * sizeof(double), cols, hipMemcpyHostToDevice, h->stream));
+        lm_product(h, M.vb, ld, cols, M.ob, ld);
+        HIPCHK(hipMemcpy2DAsync(OUT + (int64_t)c0 * n, n * sizeof(double), M.ob, ld * sizeof(double), n * sizeof(double), cols, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+    }
+}
+void do_lm_info(asm_handle* h, struct asm_lm_info* out) {
+    if (!out) throw std::invalid_argument("asm_lm_info: null pointer");
+    const LmState& M = h->lm;
+    std::memset(out, 0, sizeof(*out));
+    out->type = M.type; out->memory = M.memory; out->pending = M.pending ? 1 : 0; out->sigma = 1.0; out->bytes = M.bytes;
+    if (!M.S.R) return;
+    HIPCHK(hipSetDevice(h->device));
+    int st[LM_WORDS];
+    HIPCHK(asmb::sync(h->stream));
+    HIPCHK(asmb::copy(st, M.S.st, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(asmb::copy(&out->sigma, M.S.sigma, sizeof(double), hipMemcpyDeviceToHost));
+    out->pairs = st[LM_COUNT]; out->pushed = st[LM_PUSHED]; out->skipped_zero = st[LM_SKIP_ZERO]; out->skipped_curvature = st[LM_SKIP_CURV];
+}
+void do_hessian_set_type(asm_handle* h, int32_t type, int32_t memory) {
+    if (h->batch_slot) throw std::invalid_argument("asm_hessian_set_type: the type is chosen per handle, not for a slot of an asm_batch");
+    if (type != ASM_HESS_EXACT && type != ASM_HESS_LM) throw std::invalid_argument("asm_hessian_set_type: type is neither ASM_HESS_EXACT nor ASM_HESS_LM");
+    if (memory < 1 || memory > ASM_LM_MAX) throw std::invalid_argument("asm_hessian_set_type: memory outside 1 .. ASM_LM_MAX");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(asmb::sync(h->stream));
+    h->lm.drop();
+    h->lm.type = type;
+    h->lm.memory = memory;
+}
+// what stands for H in the KKT entries of this handle: the limited-memory operator takes every nlp_kind, the exact one hs_check's
+bool kkt_hess_lm(const asm_handle* h, const char* who) {
+    if (h->lm.type != ASM_HESS_LM) { hs_check(h, who); return false; }
+    ev_of(h, who);
+    return true;
+}
+}  // namespace
+
 // ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set" and "Many right-hand sides on one factor"): one
 // set-up of the face (KktFace, steps 1 and 2), one driver of steps 3 to 6 on blocks of columns (kkt_columns) and, behind KktOps, the
 // ways to multiply and solve: KktOneColumn for asm_kkt_solve and asm_solution_sensitivity, KktBlock for the multi entries, and KktSparse
@@ -4887,9 +5058,10 @@ struct KktFace {
     const double* mask = nullptr;                       // 1.0 on F, 0.0 on B and beyond n (ldn)
     const int* wrow = nullptr;                          // wl on the device
     bool sparse = false;                                // the form of this call (asm_kkt_set_form and the fallback rules)
+    bool lm = false;                                    // the limited-memory operator stands for H (asm_hessian_set_type): step 1 is skipped
     // the checks every entry shares (`me` names the caller in the messages) and steps 1 and 2 of the method
     KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
-            const asm_kkt_params* par);
+            const asm_kkt_params* par, bool use_lm = false);
 };
 // Sparse form: puts f.wl into the reverse Cuthill-McKee order of the working rows' coupling graph and leaves the pairs of S and the position
 // list on the device, the band and the counts in K.last.  The order, band and pairs of the last row_state are kept: an equal row_state
@@ -4929,9 +5101,10 @@ void kk_order(asm_handle* h, KktFace& f, const int32_t* row_state) {
     K.last.order_reused = hit ? 1 : 0;
 }
 KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
-                 const asm_kkt_params* par) {
+                 const asm_kkt_params* par, bool use_lm) {
     const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn;
     KktFace& f = *this;
+    f.lm = use_lm;
     for (int64_t j = 0; j < n; ++j) {
         if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
         f.nF += bound_state[j] == 0;
@@ -4948,7 +5121,8 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     f.nWp = round_up(nW, 32);
     f.nWg = round_up(nW, 64);
     // (a slot of a scenario batch has both made before its fiber starts - batch_kkt_prepare: no allocation, no list building in a round)
-    hs_prepare(h);
+    if (f.lm) lm_store(h, me.c_str());
+    else hs_prepare(h);
     kk_prepare(h);
     KktBufs& K = h->ev->kk;
     // the form: sparse when asked for and possible - a sparse pattern that rcm_order accepts - else dense, which is not an error
@@ -4961,7 +5135,11 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     K.last.form_requested = K.form;
     K.last.form_used = f.sparse ? ASM_KKT_SPARSE : ASM_KKT_DENSE;
     // 1. the Hessian values of f - lambda' g at x, once: they stay in d_hs_vals for every product of the call (x goes to d_ev_xt)
-    {
+    // (the limited-memory operator has nothing to evaluate: x alone goes up)
+    if (f.lm) {
+        std::memcpy(h->ev->h_stage, x, n * sizeof(double));
+        HIPCHK(asmb::copy_async(h->ev->d_xt, h->ev->h_stage, n * sizeof(double), hipMemcpyHostToDevice, s));
+    } else {
         std::vector<double> nl((size_t)std::max<int64_t>(m, 1), 0.0);
         for (int64_t i = 0; i < m; ++i) nl[i] = -lambda[i];
         hs_launch(h, x, 1.0, nl.data(), nullptr);      // (copies nl into the pinned staging buffer before it returns)
@@ -4974,6 +5152,13 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         const ExprTape& X = h->ev->X;
         if (h->ev->nlp_kind == ASM_NLP_EXPR && X.R > 0)
             asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
+        // (kinds 1 and 2 come here with the limited-memory operator only: their own kernels as ev_launch calls them, one point)
+        if (h->ev->nlp_kind == 1)
+            asmb::launch(k_nlp_acopf_ohm, asmb::blocks(h->ev->nlp_rows / 4), dim3(256), s, h->ev->d_ipar, h->ev->d_dpar, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1,
+                         (int64_t)0, (int64_t)0);
+        else if (h->ev->nlp_kind == 2)
+            asmb::launch(k_nlp_dense_quadratic, asmb::blocks(h->ev->nlp_rows, 4), dim3(256), s, h->ev->d_dpar, h->ev->nlp_rows, n, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows,
+                         h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
         if (f.sparse) {
             const unsigned g = (unsigned)std::min<int64_t>((h->sk->nu + 255) / 256, 4096);
             asmb::launch(k_kkts_vals, dim3(g), dim3(256), s, (const double*)K.dE, (const int64_t*)h->sk->d_perm, (const int64_t*)h->sk->d_ustart, h->sk->nu, K.sp_vals);
@@ -5053,7 +5238,19 @@ struct KktOps {
     KktOps(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww)
         : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->sk->n), ldn(hh->sk->ldn), ldT(hh->ev->kk.ldT), spare(ww.row + 2 * ww.cap * hh->ev->kk.ldT) {}
     virtual ~KktOps() = default;
-    virtual void hess(const double* v, double* out, int cols) = 0;                  // OUT = H V from the values of step 1
+    virtual void hess(const double* v, double* out, int cols) = 0;                  // OUT = H V from the values of step 1, or B V
+    // what every back end's hess is: the limited-memory product where the face has it, else the exact kernels on the values of step 1 -
+    // `one`: a single column of pitch n (k_hess_product), otherwise cols <= KKM_CW columns of pitch ldn
+    void hess_product(const double* v, double* out, int cols, bool one) {
+        if (f.lm) { lm_product(h, v, ldn, cols, out, ldn); return; }
+        const HsShared& L = *h->ev->hs_sh;
+        const dim3 g = asmb::blocks(n);
+        if (one) asmb::launch(k_hess_product, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
+        else if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+    }
     virtual void mul_A(const double* v, double* t, int cols) = 0;                   // T = V A'
     virtual void mul_AT(const double* y, double* v, int cols) = 0;                  // V = Y A
     // S^-1 applied to the block b; t (b itself, or another block) is where the answer may go.  Returns where it is.
@@ -5065,10 +5262,7 @@ struct KktOps {
 // buffer into another, J' dlam from the private dense J
 struct KktOneColumn final : KktOps {
     using KktOps::KktOps;
-    void hess(const double* v, double* out, int) override {
-        const HsShared& L = *h->ev->hs_sh;
-        asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
-    }
+    void hess(const double* v, double* out, int) override { hess_product(v, out, 1, true); }
     void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nWg, 4), dim3(256), s, h->ev->kk.Aw, ldn, v, t, f.nW, ldn); }
     void mul_AT(const double* y, double* v, int) override { asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->ev->kk.AwT, ldT, y, v, ldn, f.nW); }
     double* solve_S(const double* b, double* t, int) override {
@@ -5103,14 +5297,7 @@ struct KktBlock final : KktOps {
         HIPCHK(asmb::fill_async(w.row, 0, 5 * w.cap * ldT * sizeof(double), s));
     }
     // (rows >= cols of V are read - they exist: the blocks have KKM_CW rows - not written)
-    void hess(const double* v, double* out, int cols) override {
-        const HsShared& L = *h->ev->hs_sh;
-        const dim3 g = asmb::blocks(n);
-        if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-    }
+    void hess(const double* v, double* out, int cols) override { hess_product(v, out, cols, false); }
     void mul_A(const double* v, double* t, int cols) override { dev.gemm_nt(v, ldn, h->ev->kk.Aw, ldn, nullptr, 0, t, ldT, cols, (int)f.nW, (int)ldn, 0); }
     void mul_AT(const double* y, double* v, int cols) override { dev.gemm_nt(y, ldT, h->ev->kk.AwT, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)f.nWp, 0); }
     double* solve_S(const double* b, double* t, int cols) override {
@@ -5138,15 +5325,7 @@ struct KktSparse final : KktOps {
         }
         HIPCHK(asmb::fill_async(w.row, 0, 5 * w.cap * ldT * sizeof(double), s));
     }
-    void hess(const double* v, double* out, int cols) override {
-        const HsShared& L = *h->ev->hs_sh;
-        const dim3 g = asmb::blocks(n);
-        if (w.cap == 1) asmb::launch(k_hess_product, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
-        else if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-    }
+    void hess(const double* v, double* out, int cols) override { hess_product(v, out, cols, w.cap == 1); }
     void mul_A(const double* v, double* t, int cols) override {
         const Skeleton& S = *h->sk;
         asmb::launch(k_kkts_mul_a<LA>, dim3(asmb::blocks(f.nWg * LA).x, (unsigned)cols), dim3(256), s, (const int*)S.d_sp_ptr, (const int*)S.d_sp_col, (const double*)h->ev->kk.sp_vals,
@@ -5361,11 +5540,13 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
 }  // namespace
 
 static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru,
-                         const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
-    hs_check(h, "asm_kkt_solve");
+                         const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info, bool exact_only = false) {
+    // (asm_solution_sensitivity comes here too: a derivative entry, exact whatever the handle's type)
+    if (exact_only) hs_check(h, "asm_kkt_solve");
+    const bool lm = !exact_only && kkt_hess_lm(h, "asm_kkt_solve");
     if (!x || !bound_state || !ru || !dx || !info || (h->sk->m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
     Dev dev(h);
-    const KktFace f(h, dev, "asm_kkt_solve", x, lambda, row_state, bound_state, par);
+    const KktFace f(h, dev, "asm_kkt_solve", x, lambda, row_state, bound_state, par, lm);
     int64_t rounds;
     int last_active;
     if (f.sparse) {
@@ -5383,7 +5564,7 @@ static void do_solution_sensitivity(asm_handle* h, const double* x, const double
         throw std::invalid_argument("asm_solution_sensitivity: null pointer");
     std::vector<double> u((size_t)std::max<int64_t>(h->sk->n, 1)), w((size_t)std::max<int64_t>(h->sk->m, 1));
     do_data_cross(h, x, lambda, dc, u.data(), w.data());
-    do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info);
+    do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info, true);
 }
 // asm_kkt_solve_multi (sens false: the rows of RU, RW are the right-hand sides) and asm_solution_sensitivity_multi (the rows of DC are
 // directions of the data)
@@ -5392,12 +5573,13 @@ static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, 
                                asm_kkt_info* info) {
     const std::string me(who);
     if (sens) cx_check(h, who);
-    hs_check(h, who);
+    if (sens) hs_check(h, who);
+    const bool lm = !sens && kkt_hess_lm(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
     if (!x || !bound_state || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
     if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->sk->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
     Dev dev(h);
-    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par);
+    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par, lm);
     if (f.sparse) {
         KktSparse ops(h, dev, f, *kk_work(h, KKM_CW, true));
         kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
@@ -5412,7 +5594,7 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
                         const double* RU, const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX, double* DLAM, double* DZ,
                         asm_kkt_step_info* info) {
     const std::string me(who);
-    hs_check(h, who);
+    const bool lm = kkt_hess_lm(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
     if (!x || !bound_state || !RU || !RADIUS || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !RW || !DLAM))) throw std::invalid_argument(me + ": null pointer");
     for (int32_t c = 0; c < nrhs; ++c)
@@ -5426,7 +5608,7 @@ static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double
     }
     const asm_kkt_params kp{par ? par->max_iter : 0, par ? par->rtol : 0.0};
     Dev dev(h);
-    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par ? &kp : nullptr);
+    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par ? &kp : nullptr, lm);
     if (f.sparse) {
         KktSparse ops(h, dev, f, *kk_work(h, multi ? KKM_CW : 1, true));
         int64_t rounds;
@@ -5725,7 +5907,7 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
                          int32_t* bound_state, asm_eqp_info* info) {
     const char* const who = "asm_eqp_trial";
     const std::string me(who);
-    hs_check(h, who);
+    (void)kkt_hess_lm(h, who);
     const int64_t n = h->sk->n, m = h->sk->m, M = h->sk->M;
     if (!x || !lp_bound_state || !d || !mult_x_U || !mult_x_L || !bound_state || !info || (m > 0 && (!lambda || !lp_row_state || !nu || !lam_new || !row_state)))
         throw std::invalid_argument(me + ": null pointer");
@@ -5815,6 +5997,31 @@ int asm_eqp_trial(asm_handle* h, const double* x, const double* lambda, const in
     return guarded(h, [&] {
         do_eqp_trial(h, x, lambda, lp_row_state, lp_bound_state, radius, nu, tol_active, par, d, lam_new, mult_x_U, mult_x_L, row_state, bound_state, info);
     });
+}
+
+int asm_hessian_set_type(asm_handle* h, int32_t type, int32_t memory) {
+    return guarded(h, [&] { do_hessian_set_type(h, type, memory); });
+}
+int asm_lm_reset(asm_handle* h) {
+    return guarded(h, [&] {
+        HIPCHK(hipSetDevice(h->device));
+        lm_clear(h);
+    });
+}
+int asm_lm_push_pair(asm_handle* h, const double* s, const double* y) {
+    return guarded(h, [&] { do_lm_push_pair(h, s, y); });
+}
+int asm_lm_begin(asm_handle* h, const double* lambda) {
+    return guarded(h, [&] { do_lm_begin(h, lambda); });
+}
+int asm_lm_end(asm_handle* h, const double* lambda) {
+    return guarded(h, [&] { do_lm_end(h, lambda); });
+}
+int asm_lm_product(asm_handle* h, const double* V, int32_t nrhs, double* OUT) {
+    return guarded(h, [&] { do_lm_product(h, V, nrhs, OUT); });
+}
+int asm_lm_info(asm_handle* h, struct asm_lm_info* out) {
+    return guarded(h, [&] { do_lm_info(h, out); });
 }
 
 // --------------------------------------------------------------------------------- kernel test hooks
@@ -7010,6 +7217,8 @@ struct SlpRunTR : SlpRun {
     virtual ~SlpRunTR() = default;
     // between the evaluation and the LP: nothing here (SlpRunEQP takes its step on the LP's working set)
     virtual void second_order_step() {}
+    // before the accepted LP step changes x: nothing here (SlpRunEQP with the limited-memory Hessian saves the point of the next pair)
+    virtual void before_lp_step() {}
 
     SlpRunTR(asm_handle* hh, const asm_slp_params& par, double tr_size, asm_slp_result* r)
         : SlpRun(hh, par, r), rn(std::max<int64_t>(m, 1), 0.0), Delta(tr_size) {}
@@ -7096,6 +7305,7 @@ struct SlpRunTR : SlpRun {
             const double rho = step_quality();                                                            // :187-196
             if (ret == 0 || ret == 2 || ret == 6) break;
             if (rho >= 0) {
+                before_lp_step();
                 for (int64_t j = 0; j < n; ++j) x[j] = x[j] + p[j];
                 info.accepted += 1;
             } else {
@@ -7118,11 +7328,19 @@ struct SlpRunEQP : SlpRunTR {
     vec d, lam_t, mU_t, mL_t;
 
     SlpRunEQP(asm_handle* hh, const asm_slp_params& par, double tr_size, const asm_slp_eqp_params& ep, asm_slp_result* r)
-        : SlpRunTR(hh, par, tr_size, r), e(ep), rs(std::max<int64_t>(m, 1), 0), bs(n, 0), d(n, 0.0), lam_t(std::max<int64_t>(m, 1), 0.0), mU_t(n, 0.0), mL_t(n, 0.0) {
+        : SlpRunTR(hh, par, tr_size, r), e(ep), rs(std::max<int64_t>(m, 1), 0), bs(n, 0), d(n, 0.0), lam_t(std::max<int64_t>(m, 1), 0.0), mU_t(n, 0.0), mL_t(n, 0.0),
+          lm(hh->lm.type == ASM_HESS_LM) {
         eq.radius = ep.radius0;
     }
 
+    // the limited-memory Hessian's pairs, where SlpEQP of slp.py makes them: begin before each of the two updates of x (none in
+    // restoration), end after the evaluation that follows, both with the multipliers current there
+    const bool lm;
+    void before_lp_step() override {
+        if (lm && !fr) do_lm_begin(h, lam.data());
+    }
     void second_order_step() override {
+        if (lm) do_lm_end(h, lam.data());
         // A. outside restoration, after a normal-phase LP that ended OPTIMAL (its active set is the handle's h->sk->last)
         if (fr || lp_solves == 0 || lp_status != ASM_OPTIMAL || lp_fr || !h->sk->last.valid || !e.enabled) return;
         eq.attempts += 1;
@@ -7141,10 +7359,12 @@ struct SlpRunEQP : SlpRunTR {
         eq.boundary += t.boundary != 0;
         if (t.phi1 < t.phi0) {                                                                           // F, G
             eq.accepted += 1;
-            for (int64_t j = 0; j < n; ++j) { x[j] = x[j] + d[j]; mU[j] = mU_t[j]; mL[j] = mL_t[j]; }
             for (int64_t i = 0; i < m; ++i) lam[i] = lam_t[i];
+            if (lm) do_lm_begin(h, lam.data());
+            for (int64_t j = 0; j < n; ++j) { x[j] = x[j] + d[j]; mU[j] = mU_t[j]; mL[j] = mL_t[j]; }
             if (t.boundary != 0 && t.t == 1.0) eq.radius = std::min(2.0 * eq.radius, e.radius_max);
             do_eval_functions(h, x.data(), &f, df.data(), E.data());
+            if (lm) do_lm_end(h, lam.data());
         } else {
             eq.rejected += 1;
             eq.radius = 0.5 * t.norm_d;
@@ -7172,7 +7392,7 @@ void slp_run_tr(asm_handle* h, const asm_slp_params* par, double tr_size, const 
 
 void slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* ep, const double* x0, double* x_out, double* lambda,
                  double* mult_x_U, double* mult_x_L, double* g_out, asm_slp_result* res, asm_slp_tr_info* tr, asm_slp_eqp_info* eq) {
-    hs_check(h, "asm_slp_run_eqp");
+    (void)kkt_hess_lm(h, "asm_slp_run_eqp");
     if (res) std::memset(res, 0, sizeof(*res));
     SlpRunEQP r(h, *par, tr_size, *ep, res);
     r.run(x0);

@@ -19,8 +19,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from .moi_evaluator import lagrangian_hessian
-from .sensitivity import _finish, _guarded_cholesky, _rhs_matrices, _sets, _substitute, dense_jacobian, working_set
+from .sensitivity import _finish, _guarded_cholesky, _rhs_matrices, _sets, _substitute, dense_jacobian, model_hessian, working_set
 
 INF = float("inf")
 
@@ -34,14 +33,15 @@ def _check_radius(radius, normal_share):
     return radius, normal_share
 
 
-def kkt_step_pcg(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=None, rtol=1e-12, normal_share=0.8):
+def kkt_step_pcg(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=None, rtol=1e-12, normal_share=0.8, hess=None):
     """The NumPy twin of asm_kkt_step: sensitivity.kkt_pcg with the radius.  Steps 1 and 2 unchanged; step 3 scales the normal step to
     normal_share * radius where it is longer; step 4 applies the Steihaug-Toint rule from d'd, d'p and p'p summed directly; steps 5
     and 6 add the model value and the norms.  The boundary move counts as a completed iteration (cg_iters).  radius = inf is kkt_pcg,
-    bit for bit.  Returns (dx, dlam, dz, info), info a dict with the fields of asm_kkt_step_info."""
+    bit for bit.  hess: what stands for the Hessian (sensitivity.model_hessian; None: the model's own).  Returns (dx, dlam, dz, info),
+    info a dict with the fields of asm_kkt_step_info."""
     F, W, ru, rw = _sets(fm, row_state, bound_state, ru, rw)
     radius, normal_share = _check_radius(radius, normal_share)
-    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    H, J = model_hessian(fm, x, lam, hess), dense_jacobian(fm, x)
     HF, A = H[np.ix_(F, F)], J[np.ix_(W, F)]
     nF, nW = len(F), len(W)
     if max_iter is None:
@@ -114,20 +114,20 @@ def kkt_step_pcg(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=No
     return dx, dlam, dz, info
 
 
-def kkt_step_reference(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=None, rtol=1e-12, normal_share=0.8):
+def kkt_step_reference(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=None, rtol=1e-12, normal_share=0.8, hess=None):
     """An independent dense answer to the trust-region step: the minimum-norm normal step by numpy.linalg.lstsq, an orthonormal basis Z
     of null(A) from the SVD of A, textbook Steihaug conjugate gradients on Z' H_FF Z in reduced coordinates (every pass of the loop that
     moves the iterate counts as an iteration, the boundary move too), multipliers by lstsq.  Returns (dx, dlam, dz, info, trace): info a
     dict with the fields of asm_kkt_step_info except dropped_pivots and the residuals' device forms; trace a dict with nn, cap =
     normal_share * radius, dt (the tangential radius), hnorm = ||Z' H Z||_2, g0 and `iterations`, a list of dicts with php, pp, trial
-    (||u + alpha p||_2, None where p'Hp <= 0), gnorm (the residual norm after the move, None on the boundary)."""
+    (||u + alpha p||_2, None where p'Hp <= 0), gnorm (the residual norm after the move, None on the boundary).  hess as in kkt_step_pcg."""
     rs, bs = np.asarray(row_state), np.asarray(bound_state)
     ru, rw, n, m = np.asarray(ru, float), np.asarray(rw, float), fm.n, fm.m
     radius, normal_share = _check_radius(radius, normal_share)
     free, work = np.flatnonzero(bs == 0), np.flatnonzero(rs == 1)
     if len(work) > len(free):
         raise ValueError("more working rows than free variables")
-    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    H, J = model_hessian(fm, x, lam, hess), dense_jacobian(fm, x)
     Hff, A = H[free][:, free], J[work][:, free]
     k, nf = len(work), len(free)
     normal = np.linalg.lstsq(A, -rw[work], rcond=None)[0] if k else np.zeros(nf)
@@ -200,6 +200,8 @@ def kkt_step_reference(fm, x, lam, row_state, bound_state, ru, rw, radius, max_i
 
 def _columns(one, fm, x, lam, row_state, bound_state, RU, RW, radii, **kw):
     RU, RW = _rhs_matrices(fm, RU, RW)
+    if kw.get("hess") is not None:
+        kw["hess"] = model_hessian(fm, x, lam, kw["hess"])
     radii = np.asarray(radii, float)
     if radii.shape != (len(RU),):
         raise ValueError("radii must have shape (nrhs,)")
@@ -208,15 +210,15 @@ def _columns(one, fm, x, lam, row_state, bound_state, RU, RW, radii, **kw):
     return out + tuple([c[k] for c in cols] for k in range(4, len(cols[0])))
 
 
-def kkt_step_pcg_multi(fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=None, rtol=1e-12, normal_share=0.8):
+def kkt_step_pcg_multi(fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=None, rtol=1e-12, normal_share=0.8, hess=None):
     """The NumPy twin of asm_kkt_step_multi: kkt_step_pcg column by column, each with its radius.  The device advances the columns
     together and freezes a column when it stops - on the boundary too - which is this loop.  Returns (DX, DLAM, DZ, infos)."""
-    return _columns(kkt_step_pcg, fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=max_iter, rtol=rtol, normal_share=normal_share)
+    return _columns(kkt_step_pcg, fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=max_iter, rtol=rtol, normal_share=normal_share, hess=hess)
 
 
-def kkt_step_reference_multi(fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=None, rtol=1e-12, normal_share=0.8):
+def kkt_step_reference_multi(fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=None, rtol=1e-12, normal_share=0.8, hess=None):
     """kkt_step_reference column by column.  Returns (DX, DLAM, DZ, infos, traces)."""
-    return _columns(kkt_step_reference, fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=max_iter, rtol=rtol, normal_share=normal_share)
+    return _columns(kkt_step_reference, fm, x, lam, row_state, bound_state, RU, RW, radii, max_iter=max_iter, rtol=rtol, normal_share=normal_share, hess=hess)
 
 
 def fraction_to_box(dx, lo, hi):
@@ -293,12 +295,13 @@ def _merit(problem, x, nu):
 
 
 def eqp_trial_host(fm, problem, x, lam, lp_row_state, lp_bound_state, radius, nu, tol_active=1e-8, max_iter=None, rtol=1e-12, normal_share=0.8,
-                   kkt_step=None):
+                   kkt_step=None, hess=None):
     """The NumPy twin of asm_eqp_trial: the working set of lp_working_set, ru = grad f(x), rw_W = g_W(x) - bound_W, the trust-region step
     (kkt_step_pcg, or kkt_step(x, lam, row_state, bound_state, ru, rw, radius) -> (dx, dlam, dz, info)), d = t dx with t the fraction of
     fraction_to_box, and the merit values f + nu' viol at x and x + d.  Returns (d, lam_new, mult_x_U, mult_x_L, row_state, bound_state,
     info), info with the fields of asm_eqp_info: those of asm_kkt_step_info, t, norm_d, norm_d_inf, phi0, phi1 and skipped (0 none, 1 more
-    working rows than free variables, 2 dependent working rows, 3 zero step).  A skipped trial returns zeros for d and the multipliers."""
+    working rows than free variables, 2 dependent working rows, 3 zero step).  A skipped trial returns zeros for d and the multipliers.
+    hess goes to kkt_step_pcg (a callable is read when the step is taken: the twin of a store that changes between trials)."""
     if not float(tol_active) >= 0.0:
         raise ValueError("tol_active must be >= 0")
     x, lam = np.asarray(x, float), np.asarray(lam, float)
@@ -314,7 +317,7 @@ def eqp_trial_host(fm, problem, x, lam, lp_row_state, lp_bound_state, radius, nu
     E = np.asarray(problem.eval_g(x, np.zeros(m)), float) if m else np.zeros(0)
     rw = np.where(row_state == 1, E - at, 0.0)
     if kkt_step is None:
-        dx, dlam, dz, step = kkt_step_pcg(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=max_iter, rtol=rtol, normal_share=normal_share)
+        dx, dlam, dz, step = kkt_step_pcg(fm, x, lam, row_state, bound_state, ru, rw, radius, max_iter=max_iter, rtol=rtol, normal_share=normal_share, hess=hess)
     else:
         dx, dlam, dz, step = kkt_step(x, lam, row_state, bound_state, ru, rw, radius)[:4]
     if not isinstance(step, dict):

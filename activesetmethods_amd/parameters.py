@@ -38,12 +38,27 @@ class Parameters:
     # not in the reference: the form of the KKT solves behind the SLP-EQP step (asm_kkt_set_form) - "dense" or "sparse" (sparse products, a
     # banded factor of A A' in a reverse Cuthill-McKee order of the working rows).  Per handle only: the scenario batches refuse "sparse".
     kkt_form: str = "dense"
+    # `hessian_type` (above, src/parameters.jl:9-10: "approximation hessian (limited-memory), exact, or none") is read by SLP-EQP: "none" and
+    # "exact" use the model's own second derivatives, "limited-memory" a limited-memory BFGS approximation of the Hessian of the Lagrangian
+    # held on the device (asm_hessian_set_type) - for models without second derivatives.  lm_memory: the pairs it keeps (1 .. 32).  Per
+    # handle only: the scenario batches refuse "limited-memory".
+    lm_memory: int = 10
 
     def __post_init__(self):
         check_kkt_form(self.kkt_form)
+        check_hessian_type(self.hessian_type)
+        if not 1 <= int(self.lm_memory) <= 32:
+            raise ValueError("lm_memory = %r: expected 1 .. 32" % (self.lm_memory,))
 
 
 KKT_FORMS = ("dense", "sparse")
+HESSIAN_TYPES = ("none", "exact", "limited-memory")
+
+
+def check_hessian_type(kind):
+    if kind not in HESSIAN_TYPES:
+        raise ValueError("hessian_type = %r: expected \"none\", \"exact\" or \"limited-memory\"" % (kind,))
+    return kind
 
 
 def check_kkt_form(form):

@@ -27,6 +27,18 @@ PIVOT_THRESHOLD = 1e-10        # a pivot of A A' at or below this share of its d
 DROPPED = 1e256                # ... by putting this value in its place: the row leaves the solves
 
 
+def model_hessian(fm, x, lam, hess=None):
+    """The n x n matrix that stands for the Hessian of the Lagrangian in the twins: hess None - the model's own (lagrangian_hessian);
+    a matrix - that matrix; a callable - an operator on row vectors, V [k x n] -> V B (lmhess.LMHessian.product), applied once to the
+    identity."""
+    if hess is None:
+        return lagrangian_hessian(fm, x, lam)
+    H = np.asarray(hess(np.eye(fm.n)), float).T if callable(hess) else np.asarray(hess, float)
+    if H.shape != (fm.n, fm.n):
+        raise ValueError("hess has shape %r, expected (%d, %d)" % (H.shape, fm.n, fm.n))
+    return H
+
+
 def dense_jacobian(fm, x):
     """The m x n Jacobian of a FunctionModel at x (duplicates of the pattern add)."""
     j_str = fm.jacobian_structure()
@@ -125,14 +137,14 @@ def _substitute(L, b):
     return z
 
 
-def kkt_pcg(fm, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=1e-12):
+def kkt_pcg(fm, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=1e-12, hess=None):
     """The NumPy twin of asm_kkt_solve, step by step the method of include/asm_hip.h: S = A A' factored with the pivot guard, the
     particular solution dx0 = -A' S^-1 rw_W, projected conjugate gradients on null(A) with the projection applied twice per
     iteration and the residual kept projected, the multipliers from S^-1 A (H_FF dx_F + ru_F); one refinement step for each of the
-    two normal-equation solves outside the iteration.  Returns (dx, dlam, dz, info), info a dict with the fields of
-    asm_kkt_info."""
+    two normal-equation solves outside the iteration.  hess: what stands for the Hessian (model_hessian; None: the model's own).
+    Returns (dx, dlam, dz, info), info a dict with the fields of asm_kkt_info."""
     F, W, ru, rw = _sets(fm, row_state, bound_state, ru, rw)
-    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    H, J = model_hessian(fm, x, lam, hess), dense_jacobian(fm, x)
     HF, A = H[np.ix_(F, F)], J[np.ix_(W, F)]
     nF, nW = len(F), len(W)
     if max_iter is None:
@@ -213,12 +225,14 @@ def kkt_reference_multi(fm, x, lam, row_state, bound_state, RU, RW):
     return DX, DLAM, DZ
 
 
-def kkt_pcg_multi(fm, x, lam, row_state, bound_state, RU, RW, max_iter=None, rtol=1e-12):
+def kkt_pcg_multi(fm, x, lam, row_state, bound_state, RU, RW, max_iter=None, rtol=1e-12, hess=None):
     """The NumPy twin of asm_kkt_solve_multi: kkt_pcg column by column.  The device advances the columns together, each with its own
     alpha, beta, reference norm, stop code and iteration count, and freezes a column when it stops - which is this loop.  Returns
     (DX, DLAM, DZ, infos), infos a list of kkt_pcg's dicts."""
     RU, RW = _rhs_matrices(fm, RU, RW)
-    cols = [kkt_pcg(fm, x, lam, row_state, bound_state, RU[c], RW[c], max_iter, rtol) for c in range(len(RU))]
+    if hess is not None:
+        hess = model_hessian(fm, x, lam, hess)
+    cols = [kkt_pcg(fm, x, lam, row_state, bound_state, RU[c], RW[c], max_iter, rtol, hess) for c in range(len(RU))]
     return np.array([c[0] for c in cols]), np.array([c[1] for c in cols]).reshape(len(RU), fm.m), np.array([c[2] for c in cols]), [c[3] for c in cols]
 
 

@@ -17,7 +17,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .parameters import Parameters, check_kkt_form
+from .parameters import Parameters, check_hessian_type, check_kkt_form
 from .subproblem import HipSubOptimizer, QpData
 
 INF = np.inf
@@ -358,6 +358,9 @@ class SlpTR(AbstractSlpOptimizer):
     def second_order_step(self):
         """Between the evaluation and the LP: nothing here (SlpEQP takes its step on the LP's working set)."""
 
+    def before_lp_step(self):
+        """Before the accepted LP step changes x: nothing here (SlpEQP with the limited-memory Hessian saves the point of the next pair)."""
+
     def run(self, max_lp_solves=None, resume=False):
         o, pr = self.options, self.problem
         if not resume:
@@ -398,6 +401,7 @@ class SlpTR(AbstractSlpOptimizer):
             if self.ret in (0, 2, 6):
                 break
             if rho >= 0:
+                self.before_lp_step()
                 self.x = self.x + self.p
             self.iter += 1
         self._finish()
@@ -407,7 +411,12 @@ class SlpEQP(SlpTR):
     """SLP-EQP: SlpTR with one insertion between eval_functions() and the LP - the trust-region step of the equality-constrained QP on
     the working set the last LP named (include/asm_hip.h, "SLP-EQP"; eqp.py).  The step goes through one method of the sub-optimizer,
     eqp_trial (HipSubOptimizer: asm_eqp_trial; a CPU stand-in: eqp.eqp_trial_host), and is taken when it lowers the merit function.  It
-    has a radius of its own; iter, lp_solves and the LP's radius are not touched.  Parameters(eqp=False) is SlpTR."""
+    has a radius of its own; iter, lp_solves and the LP's radius are not touched.  Parameters(eqp=False) is SlpTR.
+
+    Parameters(hessian_type="limited-memory"): the sub-optimizer's limited-memory BFGS approximation stands for the Hessian of the
+    Lagrangian (set_hessian_type, once), so the model needs first derivatives only.  Its pairs come from the driver's own steps:
+    lm_begin(lam) immediately before each of the two updates of x (the accepted trial, the accepted LP step; none in restoration) and
+    lm_end(lam) after the eval_functions() that follows, with the multipliers current at both."""
 
     def __init__(self, problem):
         super().__init__(problem)
@@ -419,6 +428,8 @@ class SlpEQP(SlpTR):
         if not (np.isfinite(self.Delta_E) and self.Delta_E > 0.0) or not float(o.eqp_radius_max) > 0.0 or not float(o.eqp_tol_active) >= 0.0:
             raise ValueError("eqp_radius and eqp_radius_max must be > 0 (eqp_radius finite), eqp_tol_active >= 0")
         self._lp_sets = None                                     # the active set of the last LP, if that was a normal-phase OPTIMAL one
+        self._lm = check_hessian_type(o.hessian_type) == "limited-memory"
+        self._lm_set = False
         self.eqp_counts = dict(attempts=0, accepted=0, rejected=0, skipped_rows=0, skipped_dependent=0, skipped_zero=0, cg_iters=0, boundary=0)
 
     def sub_optimize(self, Delta=1000.0):
@@ -426,8 +437,20 @@ class SlpEQP(SlpTR):
         self._lp_sets = self.trace[-1].get("sets") if (out[5] == OPTIMAL and not self.feasibility_restoration) else None
         return out
 
+    def _ensure_optimizer(self, upload=True):
+        super()._ensure_optimizer(upload)
+        if self._lm and not self._lm_set:
+            self.optimizer.set_hessian_type("limited-memory", int(self.options.lm_memory))
+            self._lm_set = True
+
+    def before_lp_step(self):
+        if self._lm and not self.feasibility_restoration:
+            self.optimizer.lm_begin(self.lam)
+
     def second_order_step(self):
         o, c = self.options, self.eqp_counts
+        if self._lm_set:
+            self.optimizer.lm_end(self.lam)                      # the pair of an accepted LP step (nothing without a pending begin)
         if self.feasibility_restoration or self._lp_sets is None or not o.eqp:                      # A
             return
         c["attempts"] += 1
@@ -442,11 +465,15 @@ class SlpEQP(SlpTR):
         c["boundary"] += int(info.boundary != 0)
         if info.phi1 < info.phi0:                                                                    # F, G
             c["accepted"] += 1
-            self.x = self.x + d
             self.lam, self.mult_x_U, self.mult_x_L = lam, mult_x_U, mult_x_L
+            if self._lm:
+                self.optimizer.lm_begin(self.lam)
+            self.x = self.x + d
             if info.boundary != 0 and info.t == 1.0:
                 self.Delta_E = min(2.0 * self.Delta_E, float(o.eqp_radius_max))
             self.eval_functions()
+            if self._lm:
+                self.optimizer.lm_end(self.lam)
         else:
             c["rejected"] += 1
             self.Delta_E = 0.5 * info.norm_d
@@ -490,6 +517,8 @@ def _optimize_native(model, max_lp_solves=None):
     try:
         opt.eval_setup(fm)
         opt.set_kkt_form(check_kkt_form(getattr(par, "kkt_form", "dense")))
+        if par.algorithm == "SLP-EQP" and check_hessian_type(getattr(par, "hessian_type", "none")) == "limited-memory":
+            opt.set_hessian_type("limited-memory", int(par.lm_memory))
         run = opt.slp_run(model.x, par, max_lp_solves or 0)
     finally:
         opt.close()

@@ -443,6 +443,50 @@ class HipSubOptimizer:
                                             _lib.i32ptr(rs), _lib.i32ptr(bs), C.byref(info)))
         return step, lam_new[:self.m], mU, mL, rs[:self.m], bs, info
 
+    # ------------------------------------------------------------------ limited-memory Hessian (include/asm_hip.h, "Limited-memory Hessian")
+    def set_hessian_type(self, kind, memory=10):
+        """asm_hessian_set_type: "exact" (the default) or "limited-memory" with `memory` pairs (1 .. 32) for every later kkt_solve, kkt_step,
+        their multi forms, eqp_trial and the native SLP-EQP driver on this handle.  Clears the store.  The derivative entries (Hessians,
+        data_cross, the sensitivities) stay exact."""
+        if kind not in _lib.HESSIAN_TYPES:
+            raise ValueError("hessian type %r: expected one of %s" % (kind, ", ".join(repr(k) for k in _lib.HESSIAN_TYPES)))
+        self._check(self._lib.asm_hessian_set_type(self._h, _lib.HESSIAN_TYPES[kind], int(memory)))
+
+    def lm_reset(self):
+        """asm_lm_reset: forget every stored pair (B = I)."""
+        self._check(self._lib.asm_lm_reset(self._h))
+
+    def lm_push_pair(self, s, y):
+        """asm_lm_push_pair: offer the pair (s, y) to the store; the skip rule decides on the device (lm_info() counts)."""
+        s, y = self._vec(s, self.n, "s"), self._vec(y, self.n, "y")
+        self._check(self._lib.asm_lm_push_pair(self._h, _lib.dptr(s), _lib.dptr(y)))
+
+    def lm_begin(self, lam):
+        """asm_lm_begin: before x changes, save x and grad f - J' lam from where the last eval_functions left them."""
+        lam = self._vec(lam, self.m, "lam")
+        self._check(self._lib.asm_lm_begin(self._h, _lib.dptr(lam)))
+
+    def lm_end(self, lam):
+        """asm_lm_end: after the next eval_functions, form the pair with the same lam and push it; nothing without a pending lm_begin."""
+        lam = self._vec(lam, self.m, "lam")
+        self._check(self._lib.asm_lm_end(self._h, _lib.dptr(lam)))
+
+    def lm_product(self, V):
+        """asm_lm_product: B v for a vector [n], or the rows of V [nrhs x n] (a row's bits do not depend on the rows beside it)."""
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim == 1:
+            return self.lm_product(V[None, :])[0]
+        V = self._mat(V, self.n, "V")
+        out = np.empty_like(V)
+        self._check(self._lib.asm_lm_product(self._h, _lib.dptr(V), V.shape[0], _lib.dptr(out)))
+        return out
+
+    def lm_info(self):
+        """The asm_lm_info structure: type, memory, pairs, pending, pushed, skipped_zero, skipped_curvature, sigma, bytes."""
+        info = _lib.LmInfo()
+        self._check(self._lib.asm_lm_info(self._h, C.byref(info)))
+        return info
+
     def slp_norms(self, lam, mult_x_U, mult_x_L):
         """(norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf)) - common.jl:35-98 - on the device."""
         out = np.empty(4)

@@ -625,6 +625,49 @@ int asm_slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, co
                     double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res,
                     asm_slp_tr_info* tr /* may be NULL */, asm_slp_eqp_info* eqp_info /* may be NULL */);
 
+/* ---- Limited-memory Hessian: SLP-EQP for models without second derivatives ---------------------------------------------------------------
+ * A limited-memory BFGS approximation B of the Hessian of L = f - lambda' g, held on the device per handle, in the compact form of Byrd,
+ * Nocedal and Schnabel over the stored pairs (s_i, y_i) in chronological order:
+ *     B v = sigma v - Psi' W Psi v,   Psi = [sigma S; Y],   W = [[sigma S S', L], [L', -D]]^-1,
+ * sigma = y'y / s'y of the newest pair, D = diag(s_i'y_i), L_ij = s_i'y_j for i > j.  No pairs: B = I.  A pair is stored only if
+ * ||s|| > 0, s'y > 0 and s'y >= 1e-8 ||s|| ||y|| (decided on the device; the middle condition only adds y = 0), so B is positive definite.  A push to a
+ * full store drops the oldest pair.  The count, sigma, the Gram entries and W live in HBM: pushes and products read nothing back.
+ *
+ * asm_hessian_set_type selects, per handle, what stands for H in asm_kkt_solve(_multi), asm_kkt_step(_multi), asm_eqp_trial and
+ * asm_slp_run_eqp: ASM_HESS_EXACT (the default: every bit as without this section) or ASM_HESS_LM with 1 <= memory <= ASM_LM_MAX
+ * (ASM_ERR_ARG outside, for either type).  With ASM_HESS_LM those entries take every nlp_kind: the Hessian values
+ * are not evaluated and the Jacobian of kinds 1 and 2 comes from their own kernels.  The derivative entries stay exact and keep their
+ * refusals whatever the type: asm_eval_hessian_*, asm_eval_data_cross, asm_solution_sensitivity(_multi), asm_batch_*.  A slot of an
+ * asm_batch: ASM_ERR_ARG.  Every call clears the store; asm_sublp_setup and asm_eval_setup clear it too (the type and memory stay).
+ *
+ * asm_lm_push_pair feeds a pair from outside (n doubles each), under the skip rule.  asm_lm_begin / asm_lm_end make the pair of a step of
+ * an SLP driver: begin, called before x changes, saves x and grad f - J' lambda from where asm_eval_functions left them (J' lambda as
+ * asm_slp_norms forms it); end, called after the next asm_eval_functions with the same lambda, forms s = x - x_prev,
+ * y = (grad f - J' lambda) - g_prev and pushes it.  end without a pending begin does nothing.  Both: ASM_ERR_STATE before
+ * asm_eval_setup and before the first asm_eval_functions.  asm_lm_product: OUT = V B for row-major nrhs x n (a column's bits do not
+ * depend on nrhs or its place).  All of them work whatever the selected type; before asm_sublp_setup: ASM_ERR_STATE.
+ * asm_slp_run_eqp with ASM_HESS_LM makes the begin / end calls where SlpEQP of activesetmethods_amd/slp.py makes them. */
+#define ASM_LM_MAX 32
+enum { ASM_HESS_EXACT = 0, ASM_HESS_LM = 1 };
+struct asm_lm_info {           /* a tag, not a typedef: the entry below has the same name */
+    int32_t type;              /* ASM_HESS_EXACT or ASM_HESS_LM */
+    int32_t memory;            /* pairs the store holds at most */
+    int32_t pairs;             /* pairs it holds */
+    int32_t pending;           /* 1 between asm_lm_begin and asm_lm_end */
+    int64_t pushed;            /* pairs offered since the store was cleared (= stored + the two skipped counts + dropped as oldest) */
+    int64_t skipped_zero;      /* ... refused for ||s|| = 0 */
+    int64_t skipped_curvature; /* ... refused for s'y < 1e-8 ||s|| ||y|| */
+    double  sigma;             /* 1.0 without pairs */
+    int64_t bytes;             /* device bytes of the store */
+};
+int asm_hessian_set_type(asm_handle* h, int32_t type, int32_t memory);
+int asm_lm_reset(asm_handle* h);
+int asm_lm_push_pair(asm_handle* h, const double* s, const double* y);
+int asm_lm_begin(asm_handle* h, const double* lambda);
+int asm_lm_end(asm_handle* h, const double* lambda);
+int asm_lm_product(asm_handle* h, const double* V, int32_t nrhs, double* OUT);
+int asm_lm_info(asm_handle* h, struct asm_lm_info* out);
+
 /* ---- scenario batches: B sub-problems with the same pattern advance through ONE launch sequence on ONE stream --------------------------
  * The reference has no batching (one Optimizer <-> one Model <-> one SLP object, src/MOI_wrapper.jl:1093-1152); these entries are
  * SURVEY.md section 8(b)'s "batch variants with a leading scenario dimension".  An asm_batch owns n_slots handles on one device; a batch
