@@ -318,7 +318,52 @@ class AcopfModel:
         return v
 
 
-def function_model(case, nlp="acopf_ohm", branch_params=False):
+def _ohm_hessian(mdl):
+    """Second derivatives of the Ohm's-law block in closed form, the host twin of k_nlp_ohm_hess + k_nlp_expr_hess_gather
+    (include/asm_hip.h, "Hessian of the Lagrangian", 3.): (hess_rows, hess_cols, eval_hess) of an NlpBlock.
+    Every row of a branch is F = k_f vf^2 + k_t vt^2 + vf vt (P cos d + Q sin d) and the constraint is x_flow - F, so with the block's
+    multipliers lam the weights are w = -lam.  Ten occurrences per branch, in the order of `pairs` below; the pattern is the distinct
+    pairs (larger index first) sorted by (row, column), each entry the sum from 0.0 of its occurrences by branch ascending and, inside a
+    branch, in that order - the same entries the expression twin (nlp="expr") gives."""
+    c, n, nl = mdl.c, mdl.n, mdl.nl
+    f, t = c["f_bus"], c["t_bus"]
+    same = np.nonzero(f == t)[0]
+    if len(same):
+        raise ValueError("branch %d joins a bus to itself: the Ohm's-law block has no second derivatives for it" % int(same[0]))
+    ivf, ivt, iaf, iat = mdl.vm[f], mdl.vm[t], mdl.va[f], mdl.va[t]
+    pairs = ((ivf, ivf), (ivt, ivt), (ivf, ivt), (ivf, iaf), (ivf, iat), (ivt, iaf), (ivt, iat), (iaf, iaf), (iat, iat), (iaf, iat))
+    hi = np.stack([np.maximum(a, b) for a, b in pairs], axis=1).reshape(-1).astype(np.int64)        # [nl x 10], branch-major
+    lo = np.stack([np.minimum(a, b) for a, b in pairs], axis=1).reshape(-1).astype(np.int64)
+    keys, ent = np.unique(hi * n + lo, return_inverse=True)
+    ent = np.asarray(ent, np.int64).reshape(-1)
+    order = np.argsort(ent, kind="stable")                  # the occurrences entry by entry, list order inside an entry
+    cnt = np.bincount(ent, minlength=len(keys))
+    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+
+    def eval_hess(x, obj_factor, lam, values):
+        x, lam = np.asarray(x, float), np.asarray(lam, float)
+        w0, w1, w2, w3 = -lam[:nl], -lam[nl:2 * nl], -lam[2 * nl:3 * nl], -lam[3 * nl:4 * nl]
+        vf, vt = x[ivf], x[ivt]
+        d = x[iaf] - x[iat]
+        cs, sn = np.cos(d), np.sin(d)
+        skf = w0 * mdl.k_ff_p + w1 * mdl.k_ff_q
+        skt = w2 * mdl.k_tt_p + w3 * mdl.k_tt_q
+        Pw = ((w0 * mdl.a_f - w1 * mdl.b_f) + w2 * mdl.a_t) - w3 * mdl.b_t
+        Qw = ((w0 * mdl.b_f + w1 * mdl.a_f) - w2 * mdl.b_t) - w3 * mdl.a_t
+        b = Pw * cs + Qw * sn
+        r = Qw * cs - Pw * sn
+        vvb, vtr, vfr = (vf * vt) * b, vt * r, vf * r
+        occ = np.stack([2.0 * skf, 2.0 * skt, b, vtr, -vtr, vfr, -vfr, -vvb, -vvb, vvb], axis=1).reshape(-1)
+        out = np.zeros(len(keys))
+        for i in range(int(cnt.max()) if len(cnt) else 0):
+            s = cnt > i
+            out[s] = out[s] + occ[order[ptr[:-1][s] + i]]
+        values[:len(keys)] = out
+        return values
+    return keys // n + 1, keys % n + 1, eval_hess
+
+
+def function_model(case, nlp="acopf_ohm", branch_params=False, hessian=False):
     """The same polar ACOPF as a FunctionModel (moi_evaluator.py), i.e. the way the reference receives it: affine and quadratic
     scalar functions in the wrapper's six lists (angle differences linear <= / >=; reference angle, dc-line loss and the nodal
     balances of buses without shunt linear ==; thermal limits quadratic <=; balances of buses with a shunt quadratic ==) and
@@ -328,9 +373,14 @@ def function_model(case, nlp="acopf_ohm", branch_params=False):
     pattern is then its distinct variables in ascending order, the same entries as the kernel's in another order.
     branch_params=True (nlp="expr"): the Ohm's-law coefficients are parameters (nlexpr.parameters) at dpar[0:8 n_branch], in the layout of
     the kernel's dpar (k_ff_p, k_ff_q, k_tt_p, k_tt_q, a_f, b_f, a_t, b_t): every case with the same branches (line_scenario_case) gives
-    the same tape, the scenarios differ in dpar only."""
+    the same tape, the scenarios differ in dpar only.
+    hessian=True (nlp="acopf_ohm"): the block also announces its second derivatives - hess_rows / hess_cols / eval_hess in closed form
+    (_ohm_hessian) and the device kind "acopf_ohm_hess", the same kernel for values and Jacobian plus k_nlp_ohm_hess; the default builds
+    the block without them.  An expression block always has second derivatives: hessian=True with nlp="expr" is a ValueError."""
     if nlp not in ("acopf_ohm", "expr"):
         raise ValueError("nlp must be 'acopf_ohm' or 'expr', not %r" % (nlp,))
+    if hessian and nlp != "acopf_ohm":
+        raise ValueError("hessian=True is for nlp='acopf_ohm' (an expression block announces its second derivatives already)")
     if branch_params and nlp != "expr":
         raise ValueError("branch_params needs nlp='expr' (the Ohm's-law kernel's coefficients are its dpar already)")
     from .moi_evaluator import FunctionModel, ScalarFunction, NlpBlock
@@ -396,6 +446,11 @@ def function_model(case, nlp="acopf_ohm", branch_params=False):
     ipar = np.concatenate([[nl, mdl.va[0], mdl.vm[0], mdl.pf[0] if nl else 0, mdl.pt[0] if nl else 0, mdl.qf[0] if nl else 0, mdl.qt[0] if nl else 0],
                            f, t]).astype(np.int64)
     dpar = np.concatenate([mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q, mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t]).astype(np.float64)
+    if hessian:
+        hr, hc, eval_hess = _ohm_hessian(mdl)
+        fm.nlp = NlpBlock(np.zeros(4 * nl), np.zeros(4 * nl), np.concatenate(rows), np.concatenate(cols), eval_g, eval_jac_g,
+                          device=("acopf_ohm_hess", ipar, dpar), hess_rows=hr, hess_cols=hc, eval_hess=eval_hess)
+        return fm
     fm.nlp = NlpBlock(np.zeros(4 * nl), np.zeros(4 * nl), np.concatenate(rows), np.concatenate(cols), eval_g, eval_jac_g,
                       device=("acopf_ohm", ipar, dpar))
     return fm

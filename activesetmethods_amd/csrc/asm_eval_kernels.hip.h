@@ -624,6 +624,60 @@ __global__ __launch_bounds__(256) void k_nlp_expr_hess_gather(AsmBt abt, const i
     for (int64_t q = eptr[e]; q < eptr[e + 1]; ++q) g = g + hocc[eocc[q]];
     values[e] = g;
 }
+// ---- second derivatives of NLP block 1 (nlp_kind ASM_NLP_ACOPF_OHM_HESS; include/asm_hip.h, "Hessian of the Lagrangian", 3.)
+// Every row of a branch is F = k_f vf^2 + k_t vt^2 + vf vt (P cos d + Q sin d), d = va_f - va_t, with (P, Q | k_f, k_t) =
+//   pfr (a_f, b_f | k_ff_p, 0)   qfr (-b_f, a_f | k_ff_q, 0)   pto (a_t, -b_t | 0, k_tt_p)   qto (-b_t, -a_t | 0, k_tt_q)
+// and the constraint is x_flow - F: with lam the block's multipliers the weights are w = -lam.  One thread per branch forms the four
+// weighted sums in row order (from the first term), b = Pw cos d + Qw sin d, r = Qw cos d - Pw sin d, and writes its ten occurrences
+//   (vf,vf) (vt,vt) (vf,vt) (vf,va_f) (vf,va_t) (vt,va_f) (vt,va_t) (va_f,va_f) (va_t,va_t) (va_f,va_t)
+// into hocc [10][nl] (a wavefront's stores are contiguous); k_nlp_expr_hess_gather sums each entry's occurrences.  The flow variables
+// are linear and the block has no objective: nothing else enters.
+__global__ __launch_bounds__(256) void k_nlp_ohm_hess(AsmBt abt, const int64_t* __restrict__ ipar, const double* __restrict__ dpar, const double* __restrict__ x, const double* __restrict__ lam, double* __restrict__ hocc) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, ipar, dpar, x, lam, hocc);
+    const int64_t nl = ipar[0];
+    const int64_t l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= nl) return;
+    const int64_t va0 = ipar[1], vm0 = ipar[2];
+    const int64_t fb = ipar[7 + l], tb = ipar[7 + nl + l];
+    const double kffp = dpar[l], kffq = dpar[nl + l], kttp = dpar[2 * nl + l], kttq = dpar[3 * nl + l];
+    const double af = dpar[4 * nl + l], bf = dpar[5 * nl + l], at = dpar[6 * nl + l], bt = dpar[7 * nl + l];
+    const double w0 = -lam[l], w1 = -lam[nl + l], w2 = -lam[2 * nl + l], w3 = -lam[3 * nl + l];
+    const double vf = x[vm0 + fb], vt = x[vm0 + tb];
+    const double d = x[va0 + fb] - x[va0 + tb];
+    const double cs = cos(d), sn = sin(d);
+    const double skf = w0 * kffp + w1 * kffq;
+    const double skt = w2 * kttp + w3 * kttq;
+    const double Pw = ((w0 * af - w1 * bf) + w2 * at) - w3 * bt;
+    const double Qw = ((w0 * bf + w1 * af) - w2 * bt) - w3 * at;
+    const double b = Pw * cs + Qw * sn;
+    const double r = Qw * cs - Pw * sn;
+    const double vvb = (vf * vt) * b, vtr = vt * r, vfr = vf * r;
+    double* o = hocc + l;
+    o[0] = 2.0 * skf;
+    o[nl] = 2.0 * skt;
+    o[2 * nl] = b;
+    o[3 * nl] = vtr;
+    o[4 * nl] = -vtr;
+    o[5 * nl] = vfr;
+    o[6 * nl] = -vfr;
+    o[7 * nl] = -vvb;
+    o[8 * nl] = -vvb;
+    o[9 * nl] = vvb;
+}
+// ---- second derivatives of NLP block 2 (nlp_kind ASM_NLP_DENSE_QUADRATIC_HESS): hess g_i = diag(Q_i), so the block's entries are the n
+// diagonal ones and entry j is sum_i lam_i Q_ij, i ascending from 0.0.  One thread per variable (reads coalesced across j), straight into
+// the value list: no occurrence array, no gather.
+__global__ __launch_bounds__(256) void k_nlp_dense_hess(AsmBt abt, const double* __restrict__ dpar, int64_t mrows, int64_t n, const double* __restrict__ lam, double* __restrict__ values) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, dpar, mrows, n, lam, values);
+    const int64_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const double* Q = dpar + mrows * n;
+    double g = 0.0;
+    for (int64_t i = 0; i < mrows; ++i) g = g + lam[i] * Q[i * n + j];
+    values[j] = g;
+}
 // ---- cross derivatives with respect to the data (asm_eval_data_cross; include/asm_hip.h, "Cross derivatives"): the forward-over-reverse
 // sweep of k_nlp_expr_hess seeded in the constants.  One thread per row (t < R) or term; its four node arrays are its nodes' places in four
 // HBM arrays of L doubles (the workspace scheme of ExprHess with one segment per row).  The tangent of a row's last node is wrow[t]

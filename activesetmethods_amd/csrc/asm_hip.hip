@@ -384,6 +384,11 @@ struct EvLayout {
     int64_t stage_len() const { return std::max({st_f(true) + 1, st_v() + n, nu() - lam(), jtl() - nu(), OUT}); }
 };
 
+// The block kinds that run the Ohm's-law kernel / the dense quadratic kernel: kinds 4 and 5 are kinds 1 and 2 that also announce second
+// derivatives (hs_check) - same parameters, same size checks, same launches for values and Jacobian.
+inline bool nlp_is_ohm(int kind) { return kind == ASM_NLP_ACOPF_OHM || kind == ASM_NLP_ACOPF_OHM_HESS; }
+inline bool nlp_is_dense(int kind) { return kind == ASM_NLP_DENSE_QUADRATIC || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
+
 // Everything asm_eval_setup makes or that is made lazily after it, in one pool and with one lifetime: until the next asm_eval_setup or
 // asm_sublp_setup.  The handle holds a pointer that is null while there is no evaluator (ev_of): no ready flag, no list of fields to reset.
 struct EvalState {
@@ -4013,10 +4018,10 @@ void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool ful
             asmb::launch(k_nlp_expr_objective, dim3(nt), dim3(64), h->stream, X, F.objective_scale, fd);
             if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->sk->n), dim3(256), h->stream, X, F.objective_scale, e.d_df);
         }
-    } else if (e.nlp_kind == 1) {
+    } else if (nlp_is_ohm(e.nlp_kind)) {
         const int64_t nl = e.nlp_rows / 4;
         asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, e.d_ipar, e.d_dpar, xd, Ed, h->sk->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
-    } else if (e.nlp_kind == 2) {
+    } else if (nlp_is_dense(e.nlp_kind)) {
         asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((e.nlp_rows + 3) / 4), nt), dim3(256), h->stream, e.d_dpar, e.nlp_rows, h->sk->n, xd, Ed, h->sk->d_dE, F.n_rows,
                      e.fn_nnz, full ? 1 : 0, ldx, ldE);
     }
@@ -4349,14 +4354,14 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
                           const int64_t* g_ptr, const int64_t* g_kind, const double* g_coef, const int64_t* g_other, double objective_scale, int nlp_kind,
                           int64_t nlp_rows, int64_t nlp_nnz, const int64_t* nlp_ipar, int64_t n_ipar, const double* nlp_dpar, int64_t n_dpar) {
     const Skeleton& K = sk_of(h, "asm_eval_setup: asm_sublp_setup first (it fixes n, m and the j_str order of dE)");
-    if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < ASM_NLP_NONE || nlp_kind > ASM_NLP_EXPR)
+    if (n_rows < 0 || !aff_ptr || !quad_ptr || !constant || !jac_off || !g_ptr || nlp_kind < ASM_NLP_NONE || nlp_kind > ASM_NLP_DENSE_QUADRATIC_HESS)
         throw std::invalid_argument("asm_eval_setup: bad argument");
     const int64_t fn_nnz = jac_off[n_rows];
     if (n_rows + nlp_rows != K.m || fn_nnz + nlp_nnz != K.nnz)
         throw std::invalid_argument("asm_eval_setup: row / Jacobian-entry counts do not match asm_sublp_setup");
-    if (nlp_kind == 1 && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
+    if (nlp_is_ohm(nlp_kind) && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
         throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
-    if (nlp_kind == 2 && (nlp_nnz != nlp_rows * K.n || n_dpar != 2 * nlp_rows * K.n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
+    if (nlp_is_dense(nlp_kind) && (nlp_nnz != nlp_rows * K.n || n_dpar != 2 * nlp_rows * K.n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
     ExprHost xh;
     if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
     HIPCHK(hipSetDevice(h->device));
@@ -4574,9 +4579,33 @@ void hs_build(const asm_handle* h, HsShared& sh) {
             if (!P.empty()) optr.push_back((int64_t)ovar.size());
         }
     }
-    const int64_t S = (int64_t)srow.size(), nocc = (int64_t)ovar.size();
+    // 2b. Ohm's-law block with second derivatives: ten occurrences per branch, listed by branch ascending and inside a branch in the order
+    // k_nlp_ohm_hess documents; occurrence q of branch l is at hocc[q * nl + l] (oslot: where a listed occurrence lives; empty = in place)
+    std::vector<int64_t> oslot;
+    if (h->ev->nlp_kind == ASM_NLP_ACOPF_OHM_HESS) {
+        const int64_t nl = h->ev->nlp_rows / 4;
+        const std::vector<int64_t> ip = hs_download(h->ev->d_ipar, 7 + 2 * nl);
+        const int64_t va0 = ip[1], vm0 = ip[2];
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t fb = ip[7 + l], tb = ip[7 + nl + l];
+            const int64_t vf = vm0 + fb, vt = vm0 + tb, af = va0 + fb, at = va0 + tb;
+            if (ip[0] != nl || std::min({vf, vt, af, at}) < 0 || std::max({vf, vt, af, at}) >= n)
+                throw std::invalid_argument("asm_eval_hessian: the Ohm's-law block names a variable outside [0, n)");
+            if (fb == tb) throw std::invalid_argument("asm_eval_hessian: branch " + std::to_string(l) + " of the Ohm's-law block joins a bus to itself");
+            const int64_t pr[10][2] = {{vf, vf}, {vt, vt}, {vf, vt}, {vf, af}, {vf, at}, {vt, af}, {vt, at}, {af, af}, {at, at}, {af, at}};
+            for (int64_t q = 0; q < 10; ++q) {
+                okey.push_back(std::max(pr[q][0], pr[q][1]) * n + std::min(pr[q][0], pr[q][1]));
+                oslot.push_back(q * nl + l);
+            }
+        }
+    }
+    // 2c. dense quadratic block with second derivatives: the n diagonal entries, written by k_nlp_dense_hess itself (no occurrences)
+    const bool dense_hess = h->ev->nlp_kind == ASM_NLP_DENSE_QUADRATIC_HESS;
+    const int64_t S = (int64_t)srow.size(), nocc = (int64_t)okey.size();
     // the block's entries: the distinct pairs (i, j), i >= j, sorted by (i, j); every entry's occurrences in list order
     std::vector<int64_t> keys(okey);
+    if (dense_hess)
+        for (int64_t j = 0; j < n; ++j) keys.push_back(j * n + j);
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
     const int64_t nblk = (int64_t)keys.size();
@@ -4585,7 +4614,7 @@ void hs_build(const asm_handle* h, HsShared& sh) {
     for (int64_t e = 0; e < nblk; ++e) eptr[e + 1] += eptr[e];
     {
         std::vector<int64_t> fill(eptr.begin(), eptr.end() - 1);
-        for (int64_t o = 0; o < nocc; ++o) eocc[fill[oent[o]]++] = o;
+        for (int64_t o = 0; o < nocc; ++o) eocc[fill[oent[o]]++] = oslot.empty() ? o : oslot[o];
     }
     for (int64_t e = 0; e < nblk; ++e) { rows.push_back(keys[e] / n + 1); cols.push_back(keys[e] % n + 1); }
     const int64_t nnz = nfn + nblk;
@@ -4626,6 +4655,8 @@ void hs_attach(asm_handle* h, const HsShared* sh) {
     if (sh->S > 0) {
         H.srow = sh->srow; H.svar = sh->svar; H.woff = sh->woff; H.optr = sh->optr; H.ovar = sh->ovar;
         zeroed(H.val, sh->wnodes); zeroed(H.tval, sh->wnodes); zeroed(H.adj, sh->wnodes); zeroed(H.tadj, sh->wnodes); zeroed(H.hocc, sh->nocc);
+    } else if (sh->nocc > 0) {
+        zeroed(H.hocc, sh->nocc);      // the Ohm's-law block: [10][nl] occurrences, no node arrays
     }
     zeroed(e.d_hs_lam, h->sk->m); zeroed(e.d_hs_v, h->sk->n); zeroed(e.d_hs_vals, sh->nnz()); zeroed(e.d_hs_out, h->sk->n);
     M.alloc(e.h_hs, std::max(sh->nnz(), h->sk->n), BufPool::PINNED);
@@ -4642,7 +4673,7 @@ void hs_prepare(asm_handle* h) {
 }
 void hs_check(const asm_handle* h, const char* who) {
     const EvalState& e = ev_of(h, who);
-    if (e.nlp_kind != ASM_NLP_NONE && e.nlp_kind != ASM_NLP_EXPR)
+    if (e.nlp_kind == ASM_NLP_ACOPF_OHM || e.nlp_kind == ASM_NLP_DENSE_QUADRATIC)       // (their twins with second derivatives: kinds 4 and 5)
         throw std::invalid_argument(std::string(who) + ": second derivatives exist for the function store alone (nlp_kind 0) or with an expression block (nlp_kind 3)");
 }
 // the values at (x, obj_factor, lambda) into d_hs_vals; with v also H v into d_hs_out.  x goes where asm_eval_constraints puts its trial
@@ -4669,6 +4700,12 @@ void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* 
     if (e.hs_H.S > 0) {
         asmb::launch(k_nlp_expr_hess, asmb::blocks(e.hs_H.S), dim3(256), h->stream, e.X, e.hs_H, e.d_xt, e.d_hs_lam + e.F.n_rows, wobj);
         asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, e.hs_H.hocc, nnz - nfn, e.d_hs_vals + nfn);
+    } else if (e.nlp_kind == ASM_NLP_ACOPF_OHM_HESS && L.nocc > 0) {
+        // (ipar / dpar read live: asm_eval_set_data and a scenario's table row take effect with nothing cached)
+        asmb::launch(k_nlp_ohm_hess, asmb::blocks(e.nlp_rows / 4), dim3(256), h->stream, e.d_ipar, e.d_dpar, e.d_xt, e.d_hs_lam + e.F.n_rows, e.hs_H.hocc);
+        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, e.hs_H.hocc, nnz - nfn, e.d_hs_vals + nfn);
+    } else if (e.nlp_kind == ASM_NLP_DENSE_QUADRATIC_HESS && n > 0) {
+        asmb::launch(k_nlp_dense_hess, asmb::blocks(n), dim3(256), h->stream, e.d_dpar, e.nlp_rows, n, e.d_hs_lam + e.F.n_rows, e.d_hs_vals + nfn);
     }
     if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, L.pptr, L.pent, L.poth, e.d_hs_vals, e.d_hs_v, n, e.d_hs_out);
 }
@@ -5152,11 +5189,11 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         const ExprTape& X = h->ev->X;
         if (h->ev->nlp_kind == ASM_NLP_EXPR && X.R > 0)
             asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
-        // (kinds 1 and 2 come here with the limited-memory operator only: their own kernels as ev_launch calls them, one point)
-        if (h->ev->nlp_kind == 1)
+        // (kinds 1 and 2 come here with the limited-memory operator only, 4 and 5 with either: their own kernels as ev_launch calls them, one point)
+        if (nlp_is_ohm(h->ev->nlp_kind))
             asmb::launch(k_nlp_acopf_ohm, asmb::blocks(h->ev->nlp_rows / 4), dim3(256), s, h->ev->d_ipar, h->ev->d_dpar, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1,
                          (int64_t)0, (int64_t)0);
-        else if (h->ev->nlp_kind == 2)
+        else if (nlp_is_dense(h->ev->nlp_kind))
             asmb::launch(k_nlp_dense_quadratic, asmb::blocks(h->ev->nlp_rows, 4), dim3(256), s, h->ev->d_dpar, h->ev->nlp_rows, n, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows,
                          h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
         if (f.sparse) {

@@ -76,7 +76,8 @@ class ScalarFunction:
 
 
 # the device kernels an NLP block can name (NlpBlock.device[0]) -> nlp_kind of asm_eval_setup (include/asm_hip.h: ASM_NLP_*)
-NLP_KINDS = {"acopf_ohm": 1, "dense_quadratic": 2, "expr": 3}
+# ("acopf_ohm_hess" / "dense_quadratic_hess": the same kernels and parameters as kinds 1 / 2, and the block's second derivatives)
+NLP_KINDS = {"acopf_ohm": 1, "dense_quadratic": 2, "expr": 3, "acopf_ohm_hess": 4, "dense_quadratic_hess": 5}
 
 
 def nlp_kind(device):

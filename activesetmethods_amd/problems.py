@@ -139,16 +139,31 @@ def synthetic_dense_nlp(n=1000, m=500):
     return pr
 
 
-def synthetic_dense_function_model(n=1000, m=500):
+def synthetic_dense_function_model(n=1000, m=500, hessian=False):
     """The synthetic dense NLP as a FunctionModel: quadratic objective in the affine / quadratic store, the dense rows as an NLP
-    block with the `dense_quadratic` device kernel (csrc/asm_eval_kernels.hip.h).  Same problem as `synthetic_dense_nlp`."""
+    block with the `dense_quadratic` device kernel (csrc/asm_eval_kernels.hip.h).  Same problem as `synthetic_dense_nlp`.
+    hessian=True: the block also announces its second derivatives (device kind "dense_quadratic_hess", k_nlp_dense_hess): hess g_i is
+    diag(Q_i), so the pattern is the n diagonal entries and entry j is sum_i lam_i Q_ij, i ascending from 0.0."""
     from .moi_evaluator import FunctionModel, ScalarFunction, NlpBlock
     pr = synthetic_dense_nlp(n, m)
     d = pr.data
     fm = FunctionModel(n, pr.x_L, pr.x_U)
     fm.objective = ScalarFunction(0.0, [(float(d["c"][j]), j + 1) for j in range(n)], [(float(d["d"][j]), j + 1, j + 1) for j in range(n)])
-    fm.nlp = NlpBlock(pr.g_L, pr.g_U, pr.j_row, pr.j_col, pr.eval_g, pr.eval_jac_g,
-                      device=("dense_quadratic", np.zeros(1, np.int64), np.concatenate([d["A"].ravel(), d["Q"].ravel()])))
+    dpar = np.concatenate([d["A"].ravel(), d["Q"].ravel()])
+    if not hessian:
+        fm.nlp = NlpBlock(pr.g_L, pr.g_U, pr.j_row, pr.j_col, pr.eval_g, pr.eval_jac_g, device=("dense_quadratic", np.zeros(1, np.int64), dpar))
+        return fm
+    Q = np.asarray(d["Q"], float).reshape(m, n)
+
+    def eval_hess(x, obj_factor, lam, values):
+        g = np.zeros(n)
+        for i in range(m):
+            g = g + float(lam[i]) * Q[i]
+        values[:n] = g
+        return values
+    diag = np.arange(1, n + 1, dtype=np.int64)
+    fm.nlp = NlpBlock(pr.g_L, pr.g_U, pr.j_row, pr.j_col, pr.eval_g, pr.eval_jac_g, device=("dense_quadratic_hess", np.zeros(1, np.int64), dpar),
+                      hess_rows=diag, hess_cols=diag, eval_hess=eval_hess)
     return fm
 
 

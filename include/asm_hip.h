@@ -176,7 +176,9 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *   nlp_kind                     0 none; 1 Ohm's-law rows of the polar ACOPF model (4 rows and 20 values per branch;
  *                                ipar = [n_branch, va0, vm0, pf0, pt0, qf0, qt0, f_bus.., t_bus..], dpar = 8 coefficient
  *                                arrays); 2 dense quadratic rows g = A x + 1/2 Q x^2 (dpar = A then Q, row-major);
- *                                3 expression block (below)
+ *                                3 expression block (below); 4 = kind 1 and 5 = kind 2 with second derivatives: the same ipar / dpar,
+ *                                size checks, kernels and bits for values, Jacobian, asm_eval_set_data and every SLP launch - they
+ *                                differ from kinds 1 and 2 only in that the Hessian entries below accept them
  * The affine / quadratic part is bit-identical to the host evaluator (no fused multiply-add, the reference's term order).
  *
  * Expression block (nlp_kind = ASM_NLP_EXPR): the constraint and objective expressions of the reference's NLP block
@@ -221,7 +223,7 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *   values equal the host twin (activesetmethods_amd/nlexpr.py) bit for bit; the other ops differ in the math library's last bits.
  *   A malformed tape (forward or out-of-row reference, unknown op, variable / constant out of range, bad POWI exponent, size
  *   mismatch, a pattern that differs from j_str) is rejected with ASM_ERR_ARG and the handle keeps its previous evaluator. */
-enum { ASM_NLP_NONE = 0, ASM_NLP_ACOPF_OHM = 1, ASM_NLP_DENSE_QUADRATIC = 2, ASM_NLP_EXPR = 3 };
+enum { ASM_NLP_NONE = 0, ASM_NLP_ACOPF_OHM = 1, ASM_NLP_DENSE_QUADRATIC = 2, ASM_NLP_EXPR = 3, ASM_NLP_ACOPF_OHM_HESS = 4, ASM_NLP_DENSE_QUADRATIC_HESS = 5 };
 enum { ASM_OP_CONST = 0, ASM_OP_VAR = 1, ASM_OP_ADD = 2, ASM_OP_SUB = 3, ASM_OP_MUL = 4, ASM_OP_DIV = 5, ASM_OP_NEG = 6, ASM_OP_POWI = 7,
        ASM_OP_SQRT = 8, ASM_OP_EXP = 9, ASM_OP_LOG = 10, ASM_OP_SIN = 11, ASM_OP_COS = 12,
        ASM_OP_ABS = 13, ASM_OP_TAN = 14, ASM_OP_ASIN = 15, ASM_OP_ACOS = 16, ASM_OP_ATAN = 17, ASM_OP_SINH = 18, ASM_OP_COSH = 19,
@@ -281,7 +283,8 @@ int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, co
 /* ---- Hessian of the Lagrangian: hessian_lagrangian_structure / eval_hessian_lagrangian (MOI_wrapper.jl:748-774, 946-978; eval_h_cb :1071-1083)
  *   H = obj_factor * objective_scale * hess f + sum_i lambda_i hess g_i        lambda [m], PLUS sign (the MOI convention, :960-978, :1080)
  * asm_slp_run's multipliers belong to df - J'lambda: the Hessian of that Lagrangian is this one at (obj_factor 1, -lambda).
- * Valid after asm_eval_setup (ASM_ERR_STATE before) for the function store alone (nlp_kind 0) or with an expression block (kind 3); kinds 1
+ * Valid after asm_eval_setup (ASM_ERR_STATE before) for the function store alone (nlp_kind 0), with an expression block (kind 3), with the
+ * Ohm's-law block announced as ASM_NLP_ACOPF_OHM_HESS (kind 4) or the dense quadratic block as ASM_NLP_DENSE_QUADRATIC_HESS (kind 5); kinds 1
  * and 2 and null pointers: ASM_ERR_ARG.  The calls do not touch the inputs of the next LP, the retained basis or hints (as
  * asm_eval_constraints).  Pattern, lists and workspace are made by the first of these calls after asm_eval_setup.
  * Pattern (rows, cols 1-based; an off-diagonal entry (i, j) stands for both symmetric positions; duplicates add), in this order:
@@ -328,6 +331,22 @@ int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, co
  *          tadj[a] += ((z*y + w*dy) - qa*dt) / t;  tadj[b] -= ((z*u + w*du) - qb*dt) / t
  *     MIN / MAX  d and z follow the chosen operand (same tie rule)
  *   With ADD..POWI, ABS, MIN and MAX only, device values equal the host twin (nlexpr.py: ExprBlock.hessian_values) bit for bit.
+ *   3. Ohm's-law block (kind 4), in place of 2.: every row of a branch is F = k_f vf^2 + k_t vt^2 + vf vt (P cos d + Q sin d), d = va_f - va_t,
+ *      with (P, Q | k_f, k_t) = pfr (a_f, b_f | k_ff_p, 0), qfr (-b_f, a_f | k_ff_q, 0), pto (a_t, -b_t | 0, k_tt_p), qto (-b_t, -a_t | 0, k_tt_q);
+ *      the row is x_flow - F, so its weight is w = -lambda.  Per branch, each product and each sum one rounding, left to right:
+ *        Kf = w_pfr k_ff_p + w_qfr k_ff_q        Kt = w_pto k_tt_p + w_qto k_tt_q
+ *        Pw = w_pfr a_f - w_qfr b_f + w_pto a_t - w_qto b_t        Qw = w_pfr b_f + w_qfr a_f - w_pto b_t - w_qto a_t
+ *        b = Pw cos d + Qw sin d        r = Qw cos d - Pw sin d
+ *      and the branch's ten occurrences, in this order:
+ *        (vf,vf) 2 Kf   (vt,vt) 2 Kt   (vf,vt) b   (vf,va_f) vt r   (vf,va_t) -(vt r)   (vt,va_f) vf r   (vt,va_t) -(vf r)
+ *        (va_f,va_f) -((vf vt) b)   (va_t,va_t) -((vf vt) b)   (va_f,va_t) (vf vt) b
+ *      Pattern: the distinct pairs, larger index first, sorted by (i, j) - the block part of the pattern the same rows give as an
+ *      expression block.  Value of an entry: the sum from 0.0 of its occurrences by branch ascending and, inside a branch, in the order
+ *      above (parallel branches and branches that share a bus add into one entry).  The flow variables are linear and the block has no
+ *      objective: obj_factor does not enter.  A branch whose two ends are the same bus is refused by the first Hessian call (ASM_ERR_ARG).
+ *      Device and host twin (acopf.py) differ in the last bits of sin and cos only.
+ *   4. dense quadratic block (kind 5), in place of 2.: the n diagonal entries (j, j), j ascending, whatever Q holds; value
+ *      sum_i lambda[n_rows + i] Q_ij over i ascending from 0.0 (one product and one sum per term): bit-identical to the host twin.
  * asm_eval_hessian_structure: *nnz and, unless rows == cols == NULL, the pattern.
  * asm_eval_hessian_lagrangian: values [nnz] at (x, obj_factor, lambda).
  * asm_eval_hessian_product: out [n] = H v from those values: out[i] sums, from 0.0 and in entry order over all nnz entries, value * v[other
@@ -341,7 +360,7 @@ int asm_eval_hessian_product(asm_handle* h, const double* x, double obj_factor, 
  * f - lambda' g at x (what asm_eval_hessian_lagrangian(x, 1.0, -lambda) gives), J the Jacobian at x and A = J[W, F], asm_kkt_solve solves
  *   H_FF dx_F - A' dlam_W = -ru_F ,    A dx_F = -rw_W ,    dx_B = 0 ,    dlam_i = 0 (i not in W) ,
  *   dz_B = (H dx)_B + ru_B - (J_W' dlam_W)_B ,    dz_F = 0                       (dz may be NULL)
- * Valid where the Hessian calls are: nlp_kind 0 or 3 after asm_eval_setup (ASM_ERR_STATE before); kinds 1 and 2, a null pointer, a state
+ * Valid where the Hessian calls are: nlp_kind 0, 3, 4 or 5 after asm_eval_setup (ASM_ERR_STATE before); kinds 1 and 2, a null pointer, a state
  * outside its value set (row_state 0 / 1, bound_state -1 / 0 / +1), |W| > |F| and par with max_iter < 0 or rtol not >= 0: ASM_ERR_ARG.
  * par == NULL: max_iter = 2 (|F| - |W|) + 20, rtol = 1e-12.
  * info.status is a result, not an error (the call returns ASM_OK and the handle works on):
@@ -605,8 +624,8 @@ int asm_eqp_trial(asm_handle* h, const double* x, const double* lambda, const in
                   double* mult_x_U, double* mult_x_L, int32_t* row_state, int32_t* bound_state, asm_eqp_info* info);
 /* The native driver: asm_slp_run_tr with the insertion above - the library calls of SlpEQP.run in activesetmethods_amd/slp.py with
  * device_eval (asm_slp_run_tr's, asm_eqp_trial, asm_eval_functions after an accepted step).  enabled = 0 is asm_slp_run_tr, bit for bit.
- * radius0 (finite) and radius_max must be > 0, tol_active >= 0 (else ASM_ERR_ARG).  Needs a model with second derivatives (nlp_kind 0
- * or 3, as asm_kkt_step).  tr and eqp_info may be NULL.  Its form over a scenario batch is asm_batch_slp_run_eqp. */
+ * radius0 (finite) and radius_max must be > 0, tol_active >= 0 (else ASM_ERR_ARG).  Needs a model with second derivatives (nlp_kind 0,
+ * 3, 4 or 5, as asm_kkt_step).  tr and eqp_info may be NULL.  Its form over a scenario batch is asm_batch_slp_run_eqp. */
 typedef struct {
     double radius0;            /* initial D_E */
     double radius_max;         /* cap on D_E */
@@ -636,7 +655,7 @@ int asm_slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, co
  * asm_hessian_set_type selects, per handle, what stands for H in asm_kkt_solve(_multi), asm_kkt_step(_multi), asm_eqp_trial and
  * asm_slp_run_eqp: ASM_HESS_EXACT (the default: every bit as without this section) or ASM_HESS_LM with 1 <= memory <= ASM_LM_MAX
  * (ASM_ERR_ARG outside, for either type).  With ASM_HESS_LM those entries take every nlp_kind: the Hessian values
- * are not evaluated and the Jacobian of kinds 1 and 2 comes from their own kernels.  The derivative entries stay exact and keep their
+ * are not evaluated and the Jacobian of kinds 1, 2, 4 and 5 comes from their own kernels.  The derivative entries stay exact and keep their
  * refusals whatever the type: asm_eval_hessian_*, asm_eval_data_cross, asm_solution_sensitivity(_multi), asm_batch_*.  A slot of an
  * asm_batch: ASM_ERR_ARG.  Every call clears the store; asm_sublp_setup and asm_eval_setup clear it too (the type and memory stay).
  *
