@@ -16,23 +16,20 @@
 // leave the common path simply stop matching: their operations are launched on their own, in order.  Results are bit-identical to
 // the per-scenario path by construction (same kernels, same arguments, same grids).
 // Alignment: fibers wait at barriers (tags in program order); the scheduler releases the group with the smallest (cycle, tag) first
-// once nobody can run - min-PC-first reconvergence, as a SIMT machine treats a divergent loop.
+// once nobody can run - min-PC-first reconvergence, as a SIMT machine treats a divergent loop.  Fibers, scheduler and these waits are
+// host-only code in asm_fiber.h; this header is the recorder on top of them.
 #pragma once
-#include <sys/mman.h>
-#include <ucontext.h>
 #include <cstdint>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <functional>
 #include <map>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "asm_bt.hip.h"
+#include "asm_fiber.h"
 
 // copy / fill operations of recorded streams (every asmb::copy_async / asmb::fill_async inside a fiber becomes one of these)
 __global__ __launch_bounds__(256) void k_bcopy(AsmBt bt, char* dst, const char* src, int64_t bytes) {
@@ -71,10 +68,6 @@ __global__ void k_bsignal(AsmBt bt, unsigned* word, unsigned value) {
 
 namespace asmb {
 
-struct BatchError : std::runtime_error {
-    explicit BatchError(const std::string& s) : std::runtime_error(s) {}
-};
-
 // ---- argument packing: the layout rule of asm_bget (natural alignment, declaration order, entry rounded up to 16 bytes)
 template <class T>
 constexpr size_t pk_align(size_t off) { return (off + alignof(T) - 1) & ~(alignof(T) - 1); }
@@ -105,50 +98,32 @@ struct Op {
     uint32_t out_bytes;
 };
 
-struct Sched;
-
-struct Fiber {
-    enum State { RUNNABLE, WAIT_FLUSH, WAIT_BARRIER, DONE };
-    ucontext_t ctx;
-    void* stack = nullptr;
-    size_t stack_size = 0;
-    State state = RUNNABLE;
-    long cycle = 0;
-    int tag = 0;
-    int index = 0;
-    Sched* sched = nullptr;
+// what a fiber has recorded since its last flush
+struct RecFiber : Fiber {
+    using Fiber::Fiber;
     std::vector<Op> ops;
     std::vector<char> args, payload;
-    std::function<void()> body;
-    std::exception_ptr err;
     // merge cursor / per-round scratch
     size_t cursor = 0;
     std::vector<uint32_t> out_off;
 };
 
-extern thread_local Fiber* cur;
-thread_local Fiber* cur = nullptr;
-
-inline bool in_fiber() { return cur != nullptr; }
-
-struct Sched {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<Fiber*> fibers;
-    ucontext_t main_ctx;
+struct Sched : FiberSched {
+    const int device;
+    const hipStream_t stream;
     char *h_blob = nullptr, *d_blob = nullptr;
     size_t blob_cap = 0;
     char *h_out = nullptr, *d_out = nullptr;
     size_t out_cap = 0;
     unsigned *h_sig = nullptr, *d_sig = nullptr;
     unsigned round = 0;
-    int panel_wgs = 480;
-    // statistics
-    uint64_t n_rounds = 0, n_ops = 0, n_launches = 0, n_releases = 0, blob_bytes = 0;
-    double t_emit_ms = 0, t_wait_ms = 0, t_host_ms = 0;
-    bool verbose = false;                                   // ASM_BATCH_VERBOSE=1: per-kernel merge statistics at release
+    const int panel_wgs;
+    // statistics (n_releases, t_host_ms: the scheduler's)
+    uint64_t n_rounds = 0, n_ops = 0, n_launches = 0, blob_bytes = 0;
+    double t_emit_ms = 0, t_wait_ms = 0;
+    const bool verbose;                                     // ASM_BATCH_VERBOSE=1: per-kernel merge statistics when the scheduler leaves
     // HIP events around every merged launch of the dataflow panel kernels (OP_RESIDENT) on this group's stream: the family bench.py's roofline names
-    bool time_resident = false;
+    const bool time_resident;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> res_events;
     std::vector<hipEvent_t> res_pool;
     double res_ms = 0.0;
@@ -177,26 +152,37 @@ struct Sched {
         if (need <= blob_cap) return;
         if (h_blob) (void)hipHostFree(h_blob);
         if (d_blob) (void)::hipFree(d_blob);
-        blob_cap = std::max<size_t>(need * 2, (size_t)4 << 20);
-        chk(hipHostMalloc((void**)&h_blob, blob_cap), "hipHostMalloc(blob)");
-        chk(hipMalloc((void**)&d_blob, blob_cap), "hipMalloc(blob)");
+        h_blob = d_blob = nullptr, blob_cap = 0;      // (should an allocation below fail: nothing to free twice, nothing claimed)
+        const size_t cap = std::max<size_t>(need * 2, (size_t)4 << 20);
+        chk(hipHostMalloc((void**)&h_blob, cap), "hipHostMalloc(blob)");
+        chk(hipMalloc((void**)&d_blob, cap), "hipMalloc(blob)");
+        blob_cap = cap;
     }
     void reserve_out(size_t need) {
         if (need <= out_cap) return;
         if (h_out) (void)hipHostFree(h_out);
-        out_cap = std::max<size_t>(need * 2, (size_t)1 << 20);
-        chk(hipHostMalloc((void**)&h_out, out_cap, hipHostMallocMapped), "hipHostMalloc(out)");
+        h_out = nullptr, out_cap = 0;
+        const size_t cap = std::max<size_t>(need * 2, (size_t)1 << 20);
+        chk(hipHostMalloc((void**)&h_out, cap, hipHostMallocMapped), "hipHostMalloc(out)");
         chk(hipHostGetDevicePointer((void**)&d_out, h_out, 0), "hipHostGetDevicePointer(out)");
+        out_cap = cap;
     }
-    void init(int dev, hipStream_t s, int pwgs, bool verbose_, bool time_resident_) {
-        device = dev; stream = s; panel_wgs = pwgs; verbose = verbose_; time_resident = time_resident_;
-        chk(hipHostMalloc((void**)&h_sig, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(sig)");
-        chk(hipHostGetDevicePointer((void**)&d_sig, h_sig, 0), "hipHostGetDevicePointer(sig)");
-        *h_sig = 0;
-        reserve_blob((size_t)4 << 20);
-        reserve_out((size_t)1 << 20);
+    void free_buffers() {
+        if (h_blob) (void)hipHostFree(h_blob);
+        if (d_blob) (void)::hipFree(d_blob);
+        if (h_out) (void)hipHostFree(h_out);
+        if (h_sig) (void)hipHostFree(h_sig);
     }
-    void release() {
+    Sched(int dev, hipStream_t s, int pwgs, bool verbose_, bool time_resident_) : device(dev), stream(s), panel_wgs(pwgs), verbose(verbose_), time_resident(time_resident_) {
+        try {
+            chk(hipHostMalloc((void**)&h_sig, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(sig)");
+            chk(hipHostGetDevicePointer((void**)&d_sig, h_sig, 0), "hipHostGetDevicePointer(sig)");
+            *h_sig = 0;
+            reserve_blob((size_t)4 << 20);
+            reserve_out((size_t)1 << 20);
+        } catch (...) { free_buffers(); throw; }      // (no destructor runs for a constructor that throws)
+    }
+    ~Sched() override {
         if (verbose && !per_kernel.empty()) {
             std::vector<std::pair<uint64_t, const void*>> v;
             for (auto& kv : per_kernel) v.push_back({kv.second.second, kv.first});
@@ -208,58 +194,14 @@ struct Sched {
                 std::fprintf(stderr, "[asm batch]   %8llu %9llu %6.1f  %.60s\n", (unsigned long long)pk.second, (unsigned long long)pk.first, (double)pk.first / (double)pk.second, nm ? nm : "?");
             }
         }
-        for (Fiber* f : fibers) {
-            if (f->stack) munmap(f->stack, f->stack_size);
-            delete f;
-        }
-        fibers.clear();
-        if (h_blob) (void)hipHostFree(h_blob);
-        if (d_blob) (void)::hipFree(d_blob);
-        if (h_out) (void)hipHostFree(h_out);
-        if (h_sig) (void)hipHostFree(h_sig);
-        h_blob = d_blob = h_out = d_out = nullptr;
-        h_sig = d_sig = nullptr;
-        blob_cap = out_cap = 0;
+        for (auto& pr : res_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+        for (hipEvent_t e : res_pool) (void)hipEventDestroy(e);
+        free_buffers();
     }
-
-    static void trampoline(unsigned lo, unsigned hi) {
-        Fiber* f = reinterpret_cast<Fiber*>(((uintptr_t)hi << 32) | (uintptr_t)lo);
-        try {
-            f->body();
-        } catch (...) {
-            f->err = std::current_exception();
-        }
-        f->state = Fiber::DONE;
-        cur = nullptr;
-        swapcontext(&f->ctx, &f->sched->main_ctx);      // never resumed
-    }
-    Fiber* add_fiber(std::function<void()> body) {
-        Fiber* f = new Fiber();
-        f->sched = this;
-        f->index = (int)fibers.size();
-        f->body = std::move(body);
-        f->stack_size = (size_t)2 << 20;
-        f->stack = mmap(nullptr, f->stack_size, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_STACK, -1, 0);
-        if (f->stack == MAP_FAILED) { f->stack = nullptr; delete f; throw BatchError("mmap of a fiber stack failed"); }
-        getcontext(&f->ctx);
-        f->ctx.uc_stack.ss_sp = f->stack;
-        f->ctx.uc_stack.ss_size = f->stack_size;
-        f->ctx.uc_link = nullptr;
-        const uintptr_t p = (uintptr_t)f;
-        makecontext(&f->ctx, (void (*)())trampoline, 2, (unsigned)(p & 0xffffffffu), (unsigned)(p >> 32));
-        fibers.push_back(f);
-        return f;
-    }
-    void resume(Fiber* f) {
-        cur = f;
-        f->state = Fiber::RUNNABLE;
-        swapcontext(&main_ctx, &f->ctx);
-        cur = nullptr;
-    }
-    static double now_ms() {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+    void run_range(int lo, int hi, const std::function<void(int)>& body) {      // fiber s of [lo, hi) runs body(s)
+        std::vector<std::unique_ptr<Fiber>> fl;
+        for (int s = lo; s < hi; ++s) fl.push_back(std::make_unique<RecFiber>([&body, s] { body(s); }));
+        if (!fl.empty()) run(std::move(fl));
     }
 
     static bool same(const Op& a, const Op& b) {
@@ -267,12 +209,17 @@ struct Sched {
                a.arg_size == b.arg_size;
     }
 
+    void flush(std::vector<Fiber*>& waiting) override {      // (every fiber of this scheduler is a RecFiber: run_range)
+        std::vector<RecFiber*> fl(waiting.size());
+        std::transform(waiting.begin(), waiting.end(), fl.begin(), [](Fiber* f) { return static_cast<RecFiber*>(f); });
+        emit(fl);
+    }
     // merge and launch the recorded operations of `fl`, wait for the round to finish, hand the read-backs to their destinations
-    void emit(std::vector<Fiber*>& fl) {
+    void emit(std::vector<RecFiber*>& fl) {
         const double t0 = now_ms();
         // ---- sizes: tables + payloads (blob), read-back staging (out)
         size_t need_blob = 0, need_out = 0;
-        for (Fiber* f : fl) {
+        for (RecFiber* f : fl) {
             for (const Op& o : f->ops) {
                 need_blob += o.arg_size + 16;
                 if (o.src_payload >= 0) need_blob += ((size_t)o.payload_bytes + 15) & ~(size_t)15;
@@ -285,7 +232,7 @@ struct Sched {
         reserve_out(need_out + 64);
         // ---- payloads first, then one table per merged launch
         size_t bo = 0, oo = 0;
-        for (Fiber* f : fl)
+        for (RecFiber* f : fl)
             for (size_t i = 0; i < f->ops.size(); ++i) {
                 Op& o = f->ops[i];
                 if (o.src_payload >= 0) {
@@ -303,10 +250,10 @@ struct Sched {
             }
         struct Launch { const Op* op; size_t tab; unsigned nb; };
         std::vector<Launch> launches;
-        std::vector<Fiber*> group;
+        std::vector<RecFiber*> group;
         for (;;) {
-            Fiber* lead = nullptr;                       // the least advanced fiber leads (keeps the cursors together)
-            for (Fiber* f : fl)
+            RecFiber* lead = nullptr;                    // the least advanced fiber leads (keeps the cursors together)
+            for (RecFiber* f : fl)
                 if (f->cursor < f->ops.size() && (!lead || f->cursor < lead->cursor)) lead = f;
             if (!lead) break;
             const Op& X = lead->ops[lead->cursor];
@@ -314,12 +261,12 @@ struct Sched {
             if (X.flags & OP_RESIDENT) cap = std::max<size_t>(1, (size_t)panel_wgs / std::max(1u, X.gx * X.gy * X.gz));
             cap = std::min<size_t>(cap, 65535u / std::max(1u, X.gz));
             group.clear();
-            for (Fiber* f : fl)
+            for (RecFiber* f : fl)
                 if (group.size() < cap && f->cursor < f->ops.size() && (f == lead || same(f->ops[f->cursor], X))) group.push_back(f);
             bo = (bo + 15) & ~(size_t)15;
             launches.push_back({&X, bo, (unsigned)group.size()});
             if (verbose) { auto& pk = per_kernel[X.kfn]; pk.first += group.size(); pk.second += 1; }
-            for (Fiber* f : group) {
+            for (RecFiber* f : group) {
                 std::memcpy(h_blob + bo, f->args.data() + f->ops[f->cursor].arg_off, X.arg_size);
                 bo += X.arg_size;
                 f->cursor += 1;
@@ -345,11 +292,12 @@ struct Sched {
         wait_round();
         const double t2 = now_ms();
         if (!res_events.empty()) resolve_resident();
-        for (Fiber* f : fl) {
+        for (RecFiber* f : fl) {
             for (size_t i = 0; i < f->ops.size(); ++i)
                 if (f->ops[i].h_dst) std::memcpy(f->ops[i].h_dst, h_out + f->out_off[i], f->ops[i].out_bytes);
             n_ops += f->ops.size();
             f->ops.clear(); f->args.clear(); f->payload.clear();
+            f->pending = false;
         }
         n_rounds += 1;
         n_launches += launches.size() + 1;
@@ -369,76 +317,9 @@ struct Sched {
             }
         }
     }
-
-    // run every fiber to completion
-    void run() {
-        std::vector<Fiber*> fl;
-        for (;;) {
-            bool any_live = false, progressed = false;
-            for (Fiber* f : fibers) {
-                if (f->state == Fiber::RUNNABLE) {
-                    const double t0 = now_ms();
-                    resume(f);
-                    t_host_ms += now_ms() - t0;
-                    progressed = true;
-                }
-                any_live = any_live || f->state != Fiber::DONE;
-            }
-            if (!any_live) break;
-            fl.clear();
-            for (Fiber* f : fibers)
-                if (f->state == Fiber::WAIT_FLUSH) fl.push_back(f);
-            if (!fl.empty()) {
-                emit(fl);
-                for (Fiber* f : fl) f->state = Fiber::RUNNABLE;
-                continue;
-            }
-            // everybody waits at a barrier (or is done): release the group with the smallest (cycle, tag)
-            Fiber* mn = nullptr;
-            for (Fiber* f : fibers)
-                if (f->state == Fiber::WAIT_BARRIER && (!mn || f->cycle < mn->cycle || (f->cycle == mn->cycle && f->tag < mn->tag))) mn = f;
-            if (!mn) {
-                if (!progressed) throw BatchError("batch scheduler: no fiber can run");
-                continue;
-            }
-            for (Fiber* f : fibers)
-                if (f->state == Fiber::WAIT_BARRIER && f->cycle == mn->cycle && f->tag == mn->tag) f->state = Fiber::RUNNABLE;
-            n_releases += 1;
-        }
-        // a fiber that ended with recorded operations still pending (it should not): launch them so that the stream is complete
-        fl.clear();
-        for (Fiber* f : fibers)
-            if (!f->ops.empty()) fl.push_back(f);
-        if (!fl.empty()) emit(fl);
-        for (Fiber* f : fibers)
-            if (f->err) std::rethrow_exception(f->err);
-    }
 };
 
 // ---------------------------------------------------------------------------------------------- what the solver code calls
-inline void yield_to_scheduler(Fiber* f) {
-    cur = nullptr;
-    swapcontext(&f->ctx, &f->sched->main_ctx);
-}
-// the fiber needs the results of everything it has recorded
-inline void flush_wait() {
-    Fiber* f = cur;
-    if (!f) return;
-    f->state = Fiber::WAIT_FLUSH;
-    yield_to_scheduler(f);
-}
-// alignment point `tag` (tags grow in program order inside one cycle); no-op outside a batch
-inline void barrier(int tag) {
-    Fiber* f = cur;
-    if (!f) return;
-    f->tag = tag;
-    f->state = Fiber::WAIT_BARRIER;
-    yield_to_scheduler(f);
-}
-inline void next_cycle() {
-    if (cur) cur->cycle += 1;
-}
-
 template <class... KA>
 void thunk(const void* kfn, dim3 g, dim3 b, unsigned sh, hipStream_t s, AsmBt bt) {
     auto k = reinterpret_cast<void (*)(AsmBt, KA...)>(const_cast<void*>(kfn));
@@ -446,7 +327,7 @@ void thunk(const void* kfn, dim3 g, dim3 b, unsigned sh, hipStream_t s, AsmBt bt
 }
 
 template <class... KA>
-inline Op& record(Fiber* f, void (*kern)(AsmBt, KA...), dim3 g, dim3 b, unsigned sh, unsigned flags, const KA&... a) {
+inline Op& record(RecFiber* f, void (*kern)(AsmBt, KA...), dim3 g, dim3 b, unsigned sh, unsigned flags, const KA&... a) {
     constexpr size_t sz = pk_size<KA...>();
     const size_t off = f->args.size();
     f->args.resize(off + sz);
@@ -458,8 +339,11 @@ inline Op& record(Fiber* f, void (*kern)(AsmBt, KA...), dim3 g, dim3 b, unsigned
     o.arg_off = (uint32_t)off; o.arg_size = (uint32_t)sz;
     o.src_payload = -1; o.payload_bytes = 0; o.h_dst = nullptr; o.out_bytes = 0;
     f->ops.push_back(o);
+    f->pending = true;
     return f->ops.back();
 }
+// the fiber that records the calling thread's stream operations, nullptr outside a batch (a cancelled one records nothing and answers hipSuccess)
+inline RecFiber* recording() { return static_cast<RecFiber*>(cur); }
 
 // the grid of a one-dimensional launch: ceil(n / per) workgroups (n == 0 gives the zero grid that launch skips)
 inline dim3 blocks(int64_t n, int64_t per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
@@ -470,29 +354,29 @@ template <class... KA, class... A>
 inline void launch(void (*kern)(AsmBt, KA...), dim3 g, dim3 b, hipStream_t st, A&&... a) {
     static_assert(sizeof...(KA) == sizeof...(A), "kernel launch: argument count does not match the kernel's parameter list");
     if (g.x == 0 || g.y == 0 || g.z == 0) return;
-    Fiber* f = cur;
+    RecFiber* f = recording();
     if (!f) {
         kern<<<g, b, 0, st>>>(AsmBt{nullptr, 0, g.z}, conv<KA>(a)...);
         return;
     }
-    record<KA...>(f, kern, g, b, 0u, 0u, conv<KA>(a)...);
+    if (!f->cancelled) record<KA...>(f, kern, g, b, 0u, 0u, conv<KA>(a)...);
 }
 // launch whose workgroups must all be resident at once (OP_RESIDENT): the merge keeps the joint grid inside Sched::panel_wgs
 template <class... KA, class... A>
 inline void launch_resident(void (*kern)(AsmBt, KA...), dim3 g, dim3 b, hipStream_t st, A&&... a) {
     static_assert(sizeof...(KA) == sizeof...(A), "kernel launch: argument count does not match the kernel's parameter list");
-    Fiber* f = cur;
+    RecFiber* f = recording();
     if (!f) {
         kern<<<g, b, 0, st>>>(AsmBt{nullptr, 0, g.z}, conv<KA>(a)...);
         return;
     }
-    record<KA...>(f, kern, g, b, 0u, (unsigned)OP_RESIDENT, conv<KA>(a)...);
+    if (!f->cancelled) record<KA...>(f, kern, g, b, 0u, (unsigned)OP_RESIDENT, conv<KA>(a)...);
 }
 
 inline unsigned copy_grid(size_t bytes) { return (unsigned)std::min<size_t>(64, std::max<size_t>(1, (bytes + 16383) / 16384)); }
 
 inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
-    Fiber* f = cur;
+    RecFiber* f = recording();
     if (!f) {
         // outside a batch: device-to-device copies of the solver's vectors (4 - 150 KB, ~60 per LP) as a copy kernel of this library - the
         // runtime's blit path brackets each copy with its own barrier / signal packets
@@ -502,7 +386,7 @@ inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpy
         }
         return ::hipMemcpyAsync(dst, src, bytes, kind, st);
     }
-    if (bytes == 0) return hipSuccess;
+    if (bytes == 0 || f->cancelled) return hipSuccess;
     if (kind == hipMemcpyHostToDevice) {
         const size_t po = (f->payload.size() + 15) & ~(size_t)15;
         f->payload.resize(po + bytes);
@@ -522,7 +406,7 @@ inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpy
     return hipSuccess;
 }
 inline hipError_t fill_async(void* dst, int value, size_t bytes, hipStream_t st) {
-    Fiber* f = cur;
+    RecFiber* f = recording();
     if (!f) {
         if (bytes > 0 && bytes <= ((size_t)64 << 20)) {
             k_bfill<<<dim3((unsigned)std::min<size_t>(256, std::max<size_t>(1, (bytes + 16383) / 16384))), dim3(256), 0, st>>>(AsmBt{nullptr, 0, 1}, (char*)dst, value, (int64_t)bytes);
@@ -530,7 +414,7 @@ inline hipError_t fill_async(void* dst, int value, size_t bytes, hipStream_t st)
         }
         return ::hipMemsetAsync(dst, value, bytes, st);
     }
-    if (bytes == 0) return hipSuccess;
+    if (bytes == 0 || f->cancelled) return hipSuccess;
     record<char*, int, int64_t>(f, k_bfill, dim3(copy_grid(bytes)), dim3(256), 0, 0u, (char*)dst, value, (int64_t)bytes);
     return hipSuccess;
 }
@@ -542,21 +426,19 @@ inline hipError_t sync(hipStream_t st) {
 }
 // synchronous copy / fill / free
 inline hipError_t copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    Fiber* f = cur;
-    if (!f) return ::hipMemcpy(dst, src, bytes, kind);
+    if (!cur) return ::hipMemcpy(dst, src, bytes, kind);
     hipError_t e = copy_async(dst, src, bytes, kind, nullptr);
     flush_wait();
     return e;
 }
 inline hipError_t fill(void* dst, int value, size_t bytes) {
-    Fiber* f = cur;
-    if (!f) return ::hipMemset(dst, value, bytes);
+    if (!cur) return ::hipMemset(dst, value, bytes);
     hipError_t e = fill_async(dst, value, bytes, nullptr);
     flush_wait();
     return e;
 }
 inline hipError_t free(void* p) {
-    if (cur) flush_wait();      // recorded operations may still use the buffer
+    flush_wait_nothrow();      // recorded operations may still use the buffer (destructors free: no throw from here)
     return ::hipFree(p);
 }
 

@@ -7444,15 +7444,21 @@ void slp_run_eqp(asm_handle* h, const asm_slp_params* par, double tr_size, const
 // calling thread).  While one group's round executes on the device the other groups' host threads merge and launch theirs: two groups
 // hide the host side of the rounds (64 case300-sized scenarios on one GPU: 23 -> 32 solves/s).
 struct BatchGroup {
-    hipStream_t stream = nullptr;
-    asmb::Sched sched;
-    int lo = 0, hi = 0;             // slots [lo, hi)
-    std::exception_ptr err;
+    struct Stream { hipStream_t s = nullptr; Stream() { HIPCHK(hipStreamCreate(&s)); } ~Stream() { (void)hipStreamDestroy(s); } } stream;
+    asmb::Sched sched;              // (after the stream: it leaves first)
+    const int lo, hi;               // slots [lo, hi)
+    BatchGroup(int device, int lo_, int hi_, int panel_wgs, bool verbose, bool time_panels) : sched(device, stream.s, panel_wgs, verbose, time_panels), lo(lo_), hi(hi_) {}
+    ~BatchGroup() { (void)hipStreamSynchronize(stream.s); }
 };
 struct asm_batch {
     int device = 0;
     std::vector<asm_handle*> slots;
-    std::vector<BatchGroup*> groups;
+    std::vector<std::unique_ptr<BatchGroup>> groups;
+    ~asm_batch() {                  // the groups' streams drain, the slots leave, then (as members) the groups
+        (void)hipSetDevice(device);
+        for (auto& g : groups) (void)hipStreamSynchronize(g->stream.s);
+        for (asm_handle* h : slots) (void)asm_destroy(h);
+    }
     std::string err;
     std::vector<int> J_ref;         // basis columns of the null-space form every scenario starts from (first cold selection of the batch)
     std::vector<double> dpar0;      // the NLP-block data of asm_batch_eval_setup (what a scenario start restores)
@@ -7470,23 +7476,22 @@ namespace {
 // run `work(slot)` as step `step` for every slot in [0, count): the slots of a group are fibers of the group's thread, launches merged across them
 template <class W>
 void run_fibers(asm_batch* b, int count, const char* step, W&& work) {
+    if (b->groups.empty()) throw std::logic_error(std::string(step) + ": the batch has no group (asm_batch_set_groups failed)");
     const double t0 = asmb::Sched::now_ms();
-    auto run_group = [&](BatchGroup* g) {
+    std::vector<std::exception_ptr> errs(b->groups.size());
+    auto run_group = [&](size_t k) {
         try {
             HIPCHK(hipSetDevice(b->device));
-            asmb::Sched& S = g->sched;
-            for (asmb::Fiber* f : S.fibers) { if (f->stack) munmap(f->stack, f->stack_size); delete f; }
-            S.fibers.clear();
-            for (int s = g->lo; s < std::min(g->hi, count); ++s) S.add_fiber([&work, step, s] { in_slot(step, s, [&] { work(s); }); });
-            if (!S.fibers.empty()) S.run();
+            BatchGroup& g = *b->groups[k];
+            g.sched.run_range(g.lo, std::min(g.hi, count), [&work, step](int s) { in_slot(step, s, [&] { work(s); }); });
         } catch (...) {
-            g->err = std::current_exception();
+            errs[k] = std::current_exception();
         }
     };
     std::vector<std::thread> th;
     for (size_t k = 1; k < b->groups.size(); ++k)
-        if (b->groups[k]->lo < count) th.emplace_back(run_group, b->groups[k]);
-    run_group(b->groups[0]);
+        if (b->groups[k]->lo < count) th.emplace_back(run_group, k);
+    run_group(0);
     for (auto& t : th) t.join();
     b->stats.wall_ms += asmb::Sched::now_ms() - t0;
     asm_batch_stats& st = b->stats;
@@ -7496,15 +7501,19 @@ void run_fibers(asm_batch* b, int count, const char* step, W&& work) {
     st.panel_launches = st.panel_ops = 0;
     st.panel_grid_max = 0;
     for (asm_handle* sh : b->slots) { st.panel_flops += sh->kstats.flops[ASM_K_PANEL_KERNEL]; st.panel_bytes += sh->kstats.bytes[ASM_K_PANEL_KERNEL]; }
-    for (BatchGroup* g : b->groups) {
+    for (auto& g : b->groups) {
         const asmb::Sched& S = g->sched;
         st.panel_ms += S.res_ms; st.panel_launches += (int64_t)S.res_launches; st.panel_ops += (int64_t)S.res_ops;
         st.panel_grid_max = std::max(st.panel_grid_max, (int64_t)S.res_grid_max);
         st.rounds += (int64_t)S.n_rounds; st.ops += (int64_t)S.n_ops; st.launches += (int64_t)S.n_launches; st.releases += (int64_t)S.n_releases;
         st.blob_bytes += (int64_t)S.blob_bytes; st.emit_ms += S.t_emit_ms; st.wait_ms += S.t_wait_ms; st.host_ms += S.t_host_ms;
     }
-    for (BatchGroup* g : b->groups)
-        if (g->err) { std::exception_ptr e = g->err; g->err = nullptr; std::rethrow_exception(e); }
+    // a BatchError out of a scheduler is a failed round: its slots stopped half way through a solve, so the batch needs asm_batch_setup
+    // again (every other failure is one slot's own, a SlotError, and the batch works on).  The first group's error is the call's
+    for (auto& e : errs)
+        try { if (e) std::rethrow_exception(e); } catch (const asmb::BatchError&) { b->setup_done = false; } catch (...) {}
+    for (auto& e : errs)
+        if (e) std::rethrow_exception(e);
 }
 // scenario sc's NLP-block data on slot handle h before its start: row sc of the scenario table, or the setup values.  What the slot's
 // earlier work wrote outside the range about to be written is restored first, so a result never depends on what the slot solved before.
@@ -7528,35 +7537,28 @@ void batch_hs_drop(asm_batch* b) {
         if (h->ev && h->ev->hs_sh && h->ev->hs_sh == b->hs.get()) h->ev->hs_forget();
     b->hs.reset();
 }
-void batch_free_groups(asm_batch* b) {
-    for (BatchGroup* g : b->groups) {
-        g->sched.release();
-        if (g->stream) (void)hipStreamDestroy(g->stream);
-        delete g;
-    }
-    b->groups.clear();
-}
 // `n_groups` groups of (almost) equal size over the slots; the slots' launches go to their group's stream
 void batch_make_groups(asm_batch* b, int n_groups) {
     HIPCHK(hipSetDevice(b->device));
-    for (BatchGroup* g : b->groups) HIPCHK(asmb::sync(g->stream));
-    batch_free_groups(b);
     const int n = (int)b->slots.size();
     n_groups = std::max(1, std::min(n_groups, n));
+    // the former groups leave first, each once its stream has drained: new streams made beside them do not get the hardware queues they
+    // give back, and groups that share a queue run one after the other (64 case300-sized scenarios in 3 groups: 41 -> 30 solves/s)
+    b->groups.clear();
+    for (asm_handle* h : b->slots) h->stream = h->stream2 = nullptr;
+    std::vector<std::unique_ptr<BatchGroup>> groups;      // (all of them or none: a batch with no group refuses to run)
     for (int k = 0; k < n_groups; ++k) {
-        BatchGroup* g = new BatchGroup();
-        b->groups.push_back(g);
-        HIPCHK(hipStreamCreate(&g->stream));
-        g->lo = (int)((int64_t)n * k / n_groups);
-        g->hi = (int)((int64_t)n * (k + 1) / n_groups);
         // the all-resident panel kernels of the groups run side by side: together they must fit the chip (workgroups are dealt to the XCDs
         // round-robin and each XCD places its share on its own - a consumer can become resident before its producer, and with the chip
         // full of spinning consumers the producer never would).  The slots size their panel grids to the same share: a resident launch
         // wider than the share would go out unmerged at its full grid
         const int share = std::max(16, b->slots[0]->panel_wgs_dev / n_groups);
-        g->sched.init(b->device, g->stream, share, b->verbose, b->time_panels);
-        for (int s = g->lo; s < g->hi; ++s) { b->slots[s]->stream = g->stream; b->slots[s]->stream2 = g->stream; b->slots[s]->panel_wgs = share; }
+        groups.push_back(std::make_unique<BatchGroup>(b->device, (int)((int64_t)n * k / n_groups), (int)((int64_t)n * (k + 1) / n_groups), share, b->verbose,
+                                                      b->time_panels));
     }
+    b->groups.swap(groups);
+    for (auto& g : b->groups)
+        for (int s = g->lo; s < g->hi; ++s) { b->slots[s]->stream = g->stream.s; b->slots[s]->stream2 = g->stream.s; b->slots[s]->panel_wgs = g->sched.panel_wgs; }
 }
 }  // namespace
 
@@ -7622,22 +7624,13 @@ int asm_batch_create(int device, int n_slots, asm_batch** out) {
             batch_make_groups(b, ng);
         } catch (...) { rc = error_code(b->err); }
     }
-    if (rc != ASM_OK) {
-        batch_free_groups(b);
-        for (asm_handle* h : b->slots) (void)asm_destroy(h);
-        delete b;
-        return rc;
-    }
+    if (rc != ASM_OK) { delete b; return rc; }
     *out = b;
     return ASM_OK;
 }
 
 int asm_batch_destroy(asm_batch* b) {
     if (!b) return ASM_ERR_ARG;
-    (void)hipSetDevice(b->device);
-    for (BatchGroup* g : b->groups) (void)asmb::sync(g->stream);
-    for (asm_handle* h : b->slots) (void)asm_destroy(h);
-    batch_free_groups(b);
     delete b;
     return ASM_OK;
 }

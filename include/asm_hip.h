@@ -692,7 +692,10 @@ int asm_lm_info(asm_handle* h, struct asm_lm_info* out);
  * SURVEY.md section 8(b)'s "batch variants with a leading scenario dimension".  An asm_batch owns n_slots handles on one device; a batch
  * call runs one fiber per slot on the calling thread, records every slot's kernel launches and merges equal launches of different slots
  * into one (scenario index in the grid, argument table in HBM).  Results are bit-identical to the per-handle calls.
- * Arrays carry a leading scenario dimension (row-major, scenario s at offset s * length). */
+ * Arrays carry a leading scenario dimension (row-major, scenario s at offset s * length).
+ * A failed round (ASM_ERR_HIP from a batch call: a device failure while the merged launches of the slots ran) stops every slot half way
+ * through its solve.  From then on every entry except asm_batch_setup, asm_batch_set_groups, asm_batch_destroy and the getters answers ASM_ERR_STATE
+ * ("asm_batch_setup first"); asm_batch_setup makes the batch whole again.  An error of one slot's own (bad input) is not of this kind. */
 typedef struct asm_batch asm_batch;
 int asm_batch_create(int device, int n_slots, asm_batch** out);
 int asm_batch_destroy(asm_batch* b);

@@ -203,3 +203,66 @@ def test_batch_panel_grids_stay_within_the_group_share(monkeypatch):
                 assert np.array_equal(a, c)
         finally:
             opt.close()
+
+
+def test_batch_works_on_after_one_slot_refuses_its_input():
+    """One slot's own error ends that slot's fiber only.  Three slots in one group; round 0 passes delta = -1 for slot 1, which do_solve refuses
+    inside the fiber after the fiber has recorded its bound and Jacobian uploads: the call answers ASM_ERR_ARG naming slot 1, the other slots
+    run to their end, the recorded uploads are still launched, and the batch stays as it was.  Round 1, without a new set-up, equals bit for bit
+    per-handle optimizers with the same history (slot 1: bounds and upload only in round 0)."""
+    from activesetmethods_amd import _lib, batch
+    from activesetmethods_amd.subproblem import QpData, HipSubOptimizer
+    from tests.util import random_subproblem
+    lib = _lib.load()
+    base = random_subproblem(5, 24, 12, density=1.0, n_range=2)
+    fr = np.zeros(3, np.int32)
+    hb = batch.HipBatch.__new__(batch.HipBatch)
+    hb._lib, hb._C, hb._err = lib, C, RuntimeError
+    hb.n, hb.m, hb.n_slots = base["n"], base["m"], 3
+    hb._b = C.c_void_p()
+    assert lib.asm_batch_create(0, 3, C.byref(hb._b)) == 0
+    opts = []
+    try:
+        assert lib.asm_batch_groups(hb._b) == 1
+        f64 = lambda a: np.ascontiguousarray(a, np.float64)
+        jr, jc = np.ascontiguousarray(base["j_row"], np.int64), np.ascontiguousarray(base["j_col"], np.int64)
+        gl, gu, xl, xu = map(f64, (base["c_lb"], base["c_ub"], base["v_lb"], base["v_ub"]))
+        assert lib.asm_batch_setup(hb._b, base["n"], base["m"], len(jr), _lib.i64ptr(jr), _lib.i64ptr(jc), _lib.dptr(gl), _lib.dptr(gu), _lib.dptr(xl),
+                                   _lib.dptr(xu)) == 0
+        for rnd in range(2):
+            sps = [_perturbed(base, 20 * rnd + s) for s in range(3)]
+            delta = np.array([sp["delta"] for sp in sps])
+            refused = rnd == 0
+            if refused:
+                delta[1] = -1.0
+            stack = lambda k: np.stack([sp[k] for sp in sps])
+            args = (stack("dE"), stack("df"), np.array([sp["f"] for sp in sps]), stack("E"), stack("x_k"), delta, fr)
+            bounds = (stack("c_lb"), stack("c_ub"), stack("v_lb"), stack("v_ub"))
+            if refused:
+                with pytest.raises(RuntimeError, match=r"batch error -1: .*\(slot 1\).*delta") as ei:       # ASM_ERR_ARG = -1
+                    hb.sublp_solve(*args, bounds=bounds)
+                assert "slot 1" in lib.asm_batch_last_error(hb._b).decode(), ei.value
+                assert lib.asm_batch_groups(hb._b) == 1 and lib.asm_batch_slots(hb._b) == 3
+            else:
+                out = hb.sublp_solve(*args, bounds=bounds)
+            for s, sp in enumerate(sps):
+                data = QpData(sp["df"], sp["f"], sp["dE"], sp["E"], sp["c_lb"], sp["c_ub"], sp["v_lb"], sp["v_ub"])
+                if rnd == 0:
+                    opts.append(HipSubOptimizer(QpData(base["df"], 0.0, base["dE"], base["E"], base["c_lb"], base["c_ub"], base["v_lb"], base["v_ub"]), sp["j_row"],
+                                                sp["j_col"]))
+                opts[s].set_bounds(data)
+                if refused and s == 1:
+                    opts[s].upload(sp["dE"], sp["df"], sp["f"], sp["E"], sp["x_k"])
+                    continue
+                ref = opts[s].sub_optimize(sp["x_k"], sp["delta"], False)
+                if refused:
+                    continue
+                assert ref[5] == out[5][s]
+                for a, b in zip(ref[:4], (out[0][s], out[1][s], out[2][s], out[3][s])):
+                    assert np.array_equal(a, b)
+                assert np.array_equal(ref[4].raw[:2 * hb.m], out[4][s], equal_nan=True)
+                assert opts[s].last_stats()["path"] == hb.slot_stats(s)["path"]
+    finally:
+        for o in opts:
+            o.close()
+        hb.close()
