@@ -363,6 +363,60 @@ def _ohm_hessian(mdl):
     return keys // n + 1, keys % n + 1, eval_hess
 
 
+def _ohm_data_twins(mdl):
+    """Derivatives of the Ohm's-law block with respect to its data - the 8 coefficient arrays of the kernel's dpar - in closed form: the
+    host twins (data_gradient, data_cross) of k_nlp_ohm_data_grad and k_nlp_ohm_cross + k_nlp_block_cross_gather (include/asm_hip.h,
+    "Data derivatives of the block kernels"), with the signatures of nlexpr.ExprBlock's.  The block is linear in its data and has no
+    objective (`scale` is accepted and unused), so neither twin reads the coefficients: the gradient is lam_r dF_r/dc, the cross
+    derivative along dc the flows and their derivatives with dc in the coefficients' place.  Every written operation is one rounding,
+    left to right, as in the kernels; u sums each variable's occurrences from 0.0 by branch ascending and, inside a branch, in the slot
+    order vm_f, vm_t, va_f, va_t - the way _ohm_hessian forms its per-entry sums."""
+    c, n, nl = mdl.c, mdl.n, mdl.nl
+    f, t = c["f_bus"], c["t_bus"]
+    ivf, ivt, iaf, iat = mdl.vm[f], mdl.vm[t], mdl.va[f], mdl.va[t]
+    var = np.stack([ivf, ivt, iaf, iat], axis=1).reshape(-1).astype(np.int64)        # [nl x 4], branch-major
+    order = np.argsort(var, kind="stable")                  # the occurrences variable by variable, list order inside a variable
+    cnt = np.bincount(var, minlength=n)
+    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+
+    def point(x, lam):
+        x, lam = np.asarray(x, float), np.asarray(lam, float)
+        vf, vt = x[ivf], x[ivt]
+        d = x[iaf] - x[iat]
+        return vf, vt, np.cos(d), np.sin(d), vf * vt, (lam[:nl], lam[nl:2 * nl], lam[2 * nl:3 * nl], lam[3 * nl:4 * nl])
+
+    def data_gradient(x, lam, scale=1.0):
+        vf, vt, cs, sn, vv, (l0, l1, l2, l3) = point(x, lam)
+        vf2, vt2, vvc, vvs = vf * vf, vt * vt, vv * cs, vv * sn
+        return np.concatenate([l0 * vf2, l1 * vf2, l2 * vt2, l3 * vt2, l0 * vvc + l1 * vvs, l0 * vvs - l1 * vvc, l2 * vvc - l3 * vvs,
+                               -(l2 * vvs) - l3 * vvc])
+
+    def data_cross(x, lam, dc, scale=1.0):
+        dc = np.asarray(dc, float)
+        if dc.shape != (8 * nl,):
+            raise ValueError("%d data directions for %d coefficients" % (dc.size, 8 * nl))
+        vf, vt, cs, sn, vv, (l0, l1, l2, l3) = point(x, lam)
+        kffp, kffq, kttp, kttq, af, bf, at, bt = (dc[q * nl:(q + 1) * nl] for q in range(8))
+        pfr = kffp * vf * vf + af * vv * cs + bf * vv * sn
+        qfr = kffq * vf * vf - bf * vv * cs + af * vv * sn
+        pto = kttp * vt * vt + at * vv * cs - bt * vv * sn
+        qto = kttq * vt * vt - bt * vv * cs - at * vv * sn
+        dvf = (2 * kffp * vf + af * vt * cs + bf * vt * sn, 2 * kffq * vf - bf * vt * cs + af * vt * sn,
+               at * vt * cs - bt * vt * sn, -bt * vt * cs - at * vt * sn)
+        dvt = (af * vf * cs + bf * vf * sn, -bf * vf * cs + af * vf * sn, 2 * kttp * vt + at * vf * cs - bt * vf * sn,
+               2 * kttq * vt - bt * vf * cs - at * vf * sn)
+        dth = (-af * vv * sn + bf * vv * cs, bf * vv * sn + af * vv * cs, -at * vv * sn - bt * vv * cs, bt * vv * sn - at * vv * cs)
+        wsum = lambda v: ((l0 * v[0] + l1 * v[1]) + l2 * v[2]) + l3 * v[3]
+        th = wsum(dth)
+        occ = np.stack([wsum(dvf), wsum(dvt), th, -th], axis=1).reshape(-1)
+        u = np.zeros(n)
+        for i in range(int(cnt.max()) if nl else 0):
+            s = cnt > i
+            u[s] = u[s] + occ[order[ptr[:-1][s] + i]]
+        return u, np.concatenate([-pfr, -qfr, -pto, -qto])
+    return data_gradient, data_cross
+
+
 def function_model(case, nlp="acopf_ohm", branch_params=False, hessian=False):
     """The same polar ACOPF as a FunctionModel (moi_evaluator.py), i.e. the way the reference receives it: affine and quadratic
     scalar functions in the wrapper's six lists (angle differences linear <= / >=; reference angle, dc-line loss and the nodal
@@ -376,7 +430,11 @@ def function_model(case, nlp="acopf_ohm", branch_params=False, hessian=False):
     the same tape, the scenarios differ in dpar only.
     hessian=True (nlp="acopf_ohm"): the block also announces its second derivatives - hess_rows / hess_cols / eval_hess in closed form
     (_ohm_hessian) and the device kind "acopf_ohm_hess", the same kernel for values and Jacobian plus k_nlp_ohm_hess; the default builds
-    the block without them.  An expression block always has second derivatives: hessian=True with nlp="expr" is a ValueError."""
+    the block without them.  An expression block always has second derivatives: hessian=True with nlp="expr" is a ValueError.
+    "acopf_ohm_hess" is the block kernel with its derivative entries: besides the Hessian the block carries data_gradient / data_cross
+    (_ohm_data_twins), the derivatives with respect to its own dpar - the 8 coefficient arrays a line-parameter scenario varies - so
+    the value and solution sensitivities (eval_data_gradient, data_cross, solution_sensitivity(_multi), HipBatch.data_gradient) run on
+    the kernel, with the index c of dpar meaning what it means in the branch_params=True expression form."""
     if nlp not in ("acopf_ohm", "expr"):
         raise ValueError("nlp must be 'acopf_ohm' or 'expr', not %r" % (nlp,))
     if hessian and nlp != "acopf_ohm":
@@ -448,8 +506,10 @@ def function_model(case, nlp="acopf_ohm", branch_params=False, hessian=False):
     dpar = np.concatenate([mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q, mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t]).astype(np.float64)
     if hessian:
         hr, hc, eval_hess = _ohm_hessian(mdl)
+        data_gradient, data_cross = _ohm_data_twins(mdl)
         fm.nlp = NlpBlock(np.zeros(4 * nl), np.zeros(4 * nl), np.concatenate(rows), np.concatenate(cols), eval_g, eval_jac_g,
-                          device=("acopf_ohm_hess", ipar, dpar), hess_rows=hr, hess_cols=hc, eval_hess=eval_hess)
+                          device=("acopf_ohm_hess", ipar, dpar), hess_rows=hr, hess_cols=hc, eval_hess=eval_hess,
+                          data_gradient=data_gradient, data_cross=data_cross)
         return fm
     fm.nlp = NlpBlock(np.zeros(4 * nl), np.zeros(4 * nl), np.concatenate(rows), np.concatenate(cols), eval_g, eval_jac_g,
                       device=("acopf_ohm", ipar, dpar))

@@ -286,7 +286,8 @@ class HipBatch:
 
     def data_gradient(self, x, lam):
         """asm_batch_data_gradient: d(f - lam' g) / d dpar per scenario (rows of x [n_scen x n], lam [n_scen x m]), each scenario with its
-        data (the table of the last slp_run, else the setup data); [n_scen x n_dpar]."""
+        data (the table of the last slp_run, else the setup data); [n_scen x n_dpar].  For expression blocks and the block kernels with derivatives (for
+        the latter the result depends on (x, lam) only: they are linear in their data)."""
         from . import _lib
         x = np.ascontiguousarray(np.atleast_2d(x), np.float64)
         S = x.shape[0]

@@ -706,6 +706,137 @@ __global__ __launch_bounds__(256) void k_nlp_expr_cross_gather(AsmBt abt, ExprCr
     for (int64_t q = C.vptr[j]; q < C.vptr[j + 1]; ++q) g = g + C.vocc[C.vnode[q]];
     u[j] = g;
 }
+// ---- data derivatives of NLP blocks 1 and 2 (kinds ASM_NLP_ACOPF_OHM_HESS and ASM_NLP_DENSE_QUADRATIC_HESS; include/asm_hip.h, "Data
+// derivatives of the block kernels").  Both blocks are linear in their data, so nothing here reads dpar: the data gradient is the row's own
+// expression with a unit coefficient, the cross derivative the block's kernel with the direction dc where dpar stands.  No fused
+// multiply-add: every written operation is one rounding, left to right, which is what the NumPy twins do (acopf.py: _ohm_data_twins;
+// problems.py: synthetic_dense_function_model).
+// Ohm's-law block, data gradient: the constraint is x_flow - F_r(c), so out[c] = lam_r dF_r/dc.  One thread per branch, eight stores to
+// out[q * nl + l] in dpar's layout (k_ff_p, k_ff_q, k_tt_p, k_tt_q, a_f, b_f, a_t, b_t); lam: the multipliers of the block's rows.
+__global__ __launch_bounds__(256) void k_nlp_ohm_data_grad(AsmBt abt, const int64_t* __restrict__ ipar, const double* __restrict__ x, const double* __restrict__ lam, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, ipar, x, lam, out);
+    const int64_t nl = ipar[0];
+    const int64_t l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= nl) return;
+    const int64_t va0 = ipar[1], vm0 = ipar[2];
+    const int64_t fb = ipar[7 + l], tb = ipar[7 + nl + l];
+    const double l0 = lam[l], l1 = lam[nl + l], l2 = lam[2 * nl + l], l3 = lam[3 * nl + l];
+    const double vf = x[vm0 + fb], vt = x[vm0 + tb];
+    const double d = x[va0 + fb] - x[va0 + tb];
+    const double cs = cos(d), sn = sin(d);
+    const double vv = vf * vt;
+    const double vf2 = vf * vf, vt2 = vt * vt, vvc = vv * cs, vvs = vv * sn;
+    double* o = out + l;
+    o[0] = l0 * vf2;
+    o[nl] = l1 * vf2;
+    o[2 * nl] = l2 * vt2;
+    o[3 * nl] = l3 * vt2;
+    o[4 * nl] = l0 * vvc + l1 * vvs;
+    o[5 * nl] = l0 * vvs - l1 * vvc;
+    o[6 * nl] = l2 * vvc - l3 * vvs;
+    o[7 * nl] = -(l2 * vvs) - l3 * vvc;
+}
+// Ohm's-law block, cross derivatives: one thread per (branch, column), the column in blockIdx.y.  With the column's direction (dc + column *
+// ldc) where k_nlp_acopf_ohm reads dpar the thread forms that kernel's four flows F_r and its derivative families dvf_r, dvt_r, dth_r; it
+// writes w = -F_r into cx[column * ldo + n + r * nl + l] (cx: [u (n) | w (4 nl)] per column) and, with lam the multipliers of the block's
+// rows, its four occurrences of u into occ[column][4][nl]: sum_r lam_r dvf_r (vm_f), sum_r lam_r dvt_r (vm_t), theta = sum_r lam_r dth_r
+// (va_f), -theta (va_t) - the sums in row order from the first term.  k_nlp_block_cross_gather sums the occurrences of each variable.
+__global__ __launch_bounds__(256) void k_nlp_ohm_cross(AsmBt abt, const int64_t* __restrict__ ipar, const double* __restrict__ x, const double* __restrict__ dc, int64_t ldc, const double* __restrict__ lam, double* __restrict__ occ, double* __restrict__ cx, int64_t n, int64_t ldo) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, ipar, x, dc, ldc, lam, occ, cx, n, ldo);
+    const int64_t nl = ipar[0];
+    const int64_t l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= nl) return;
+    const int64_t va0 = ipar[1], vm0 = ipar[2];
+    const int64_t fb = ipar[7 + l], tb = ipar[7 + nl + l];
+    const double* c = dc + blockIdx.y * ldc;
+    const double kffp = c[l], kffq = c[nl + l], kttp = c[2 * nl + l], kttq = c[3 * nl + l];
+    const double af = c[4 * nl + l], bf = c[5 * nl + l], at = c[6 * nl + l], bt = c[7 * nl + l];
+    const double l0 = lam[l], l1 = lam[nl + l], l2 = lam[2 * nl + l], l3 = lam[3 * nl + l];
+    const double vf = x[vm0 + fb], vt = x[vm0 + tb];
+    const double d = x[va0 + fb] - x[va0 + tb];
+    const double cs = cos(d), sn = sin(d);
+    const double vv = vf * vt;
+    const double pfr = kffp * vf * vf + af * vv * cs + bf * vv * sn;
+    const double qfr = kffq * vf * vf - bf * vv * cs + af * vv * sn;
+    const double pto = kttp * vt * vt + at * vv * cs - bt * vv * sn;
+    const double qto = kttq * vt * vt - bt * vv * cs - at * vv * sn;
+    const double dvf[4] = {2 * kffp * vf + af * vt * cs + bf * vt * sn, 2 * kffq * vf - bf * vt * cs + af * vt * sn,
+                           at * vt * cs - bt * vt * sn, -bt * vt * cs - at * vt * sn};
+    const double dvt[4] = {af * vf * cs + bf * vf * sn, -bf * vf * cs + af * vf * sn, 2 * kttp * vt + at * vf * cs - bt * vf * sn,
+                           2 * kttq * vt - bt * vf * cs - at * vf * sn};
+    const double dth[4] = {-af * vv * sn + bf * vv * cs, bf * vv * sn + af * vv * cs, -at * vv * sn - bt * vv * cs, bt * vv * sn - at * vv * cs};
+    double* w = cx + blockIdx.y * ldo + n + l;
+    w[0] = -pfr;
+    w[nl] = -qfr;
+    w[2 * nl] = -pto;
+    w[3 * nl] = -qto;
+    const double th = ((l0 * dth[0] + l1 * dth[1]) + l2 * dth[2]) + l3 * dth[3];
+    double* o = occ + blockIdx.y * (4 * nl) + l;
+    o[0] = ((l0 * dvf[0] + l1 * dvf[1]) + l2 * dvf[2]) + l3 * dvf[3];
+    o[nl] = ((l0 * dvt[0] + l1 * dvt[1]) + l2 * dvt[2]) + l3 * dvt[3];
+    o[2 * nl] = th;
+    o[3 * nl] = -th;
+}
+// u of the Ohm's-law block: one thread per (variable, column) sums the variable's occurrences in list order from 0.0 - branch ascending,
+// inside a branch the slot order of k_nlp_ohm_cross (k_nlp_expr_hess_gather's scheme with a column offset; no atomics, the host twin's
+// sum).  vptr [n + 1], vocc [vptr[n]]: where each occurrence lives in a column's occ (locc doubles per column).  A variable without an
+// occurrence (flows, generators) gets 0.
+__global__ __launch_bounds__(256) void k_nlp_block_cross_gather(AsmBt abt, const int64_t* __restrict__ vptr, const int64_t* __restrict__ vocc, const double* __restrict__ occ, int64_t locc, int64_t n, double* __restrict__ cx, int64_t ldo) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, vptr, vocc, occ, locc, n, cx, ldo);
+    const int64_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const double* oc = occ + blockIdx.y * locc;
+    double g = 0.0;
+    for (int64_t q = vptr[j]; q < vptr[j + 1]; ++q) g = g + oc[vocc[q]];
+    cx[blockIdx.y * ldo + j] = g;
+}
+// Dense quadratic block, data gradient: g_i = sum_j A_ij x_j + 1/2 Q_ij x_j^2, so d(-lam' g)/dA_ij = (-lam_i) x_j and d/dQ_ij =
+// (-lam_i) (1/2 x_j^2).  One thread per entry (i, j); out in dpar's layout, A then Q, row-major.
+__global__ __launch_bounds__(256) void k_nlp_dense_data_grad(AsmBt abt, int64_t mrows, int64_t n, const double* __restrict__ x, const double* __restrict__ lam, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, mrows, n, x, lam, out);
+    const int64_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= mrows * n) return;
+    const int64_t i = e / n, j = e - i * n;
+    const double xj = x[j], wi = -lam[i];
+    out[e] = wi * xj;
+    out[mrows * n + e] = wi * (0.5 * (xj * xj));
+}
+// Dense quadratic block, cross derivatives, w: the rows of k_nlp_dense_quadratic with the column's direction (dA, dQ) where dpar stands -
+// one wavefront per row, lane-strided, then the xor tree; w_i into cx[column * ldo + n + i], the column in blockIdx.y.
+__global__ __launch_bounds__(256) void k_nlp_dense_cross_w(AsmBt abt, const double* __restrict__ dc, int64_t ldc, int64_t mrows, int64_t n, const double* __restrict__ x, double* __restrict__ cx, int64_t ldo) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, dc, ldc, mrows, n, x, cx, ldo);
+    const int64_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= mrows) return;
+    const int lane = threadIdx.x & 63;
+    const double* Ar = dc + blockIdx.y * ldc + i * n;
+    const double* Qr = Ar + mrows * n;
+    double acc = 0.0;
+    for (int64_t j = lane; j < n; j += 64) {
+        const double xj = x[j];
+        acc = acc + (Ar[j] * xj + 0.5 * Qr[j] * xj * xj);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
+    if (lane == 0) cx[blockIdx.y * ldo + n + i] = acc;
+}
+// ... and u: u_j = -sum_i lam_i (dA_ij + dQ_ij x_j), i ascending from 0.0.  One thread per (variable, column), reads coalesced across j
+// (as k_nlp_dense_hess); lam: the multipliers of the block's rows.
+__global__ __launch_bounds__(256) void k_nlp_dense_cross_u(AsmBt abt, const double* __restrict__ dc, int64_t ldc, int64_t mrows, int64_t n, const double* __restrict__ x, const double* __restrict__ lam, double* __restrict__ cx, int64_t ldo) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, dc, ldc, mrows, n, x, lam, cx, ldo);
+    const int64_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const double* dA = dc + blockIdx.y * ldc;
+    const double* dQ = dA + mrows * n;
+    const double xj = x[j];
+    double g = 0.0;
+    for (int64_t i = 0; i < mrows; ++i) g = g + lam[i] * (dA[i * n + j] + dQ[i * n + j] * xj);
+    cx[blockIdx.y * ldo + j] = -g;
+}
 // out = H v from the values: one thread per variable walks its list of (entry, other variable) in entry order - an off-diagonal entry
 // (i, j) is in the lists of i and of j - and sums values[entry] * v[other] from 0.0
 __global__ __launch_bounds__(256) void k_hess_product(AsmBt abt, const int64_t* __restrict__ pptr, const int64_t* __restrict__ pent, const int64_t* __restrict__ poth, const double* __restrict__ values, const double* __restrict__ v, int64_t n, double* __restrict__ out) {

@@ -388,6 +388,9 @@ struct EvLayout {
 // derivatives (hs_check) - same parameters, same size checks, same launches for values and Jacobian.
 inline bool nlp_is_ohm(int kind) { return kind == ASM_NLP_ACOPF_OHM || kind == ASM_NLP_ACOPF_OHM_HESS; }
 inline bool nlp_is_dense(int kind) { return kind == ASM_NLP_DENSE_QUADRATIC || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
+// ... and the two that announce their derivative entries: besides the Hessian the derivatives with respect to their own data
+// (asm_eval_data_gradient, asm_eval_data_cross and what is built on them), in closed form
+inline bool nlp_block_derivs(int kind) { return kind == ASM_NLP_ACOPF_OHM_HESS || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
 
 // Everything asm_eval_setup makes or that is made lazily after it, in one pool and with one lifetime: until the next asm_eval_setup or
 // asm_sublp_setup.  The handle holds a pointer that is null while there is no evaluator (ev_of): no ready flag, no list of fields to reset.
@@ -417,6 +420,11 @@ struct EvalState {
     ExprCross cx_C{};
     int64_t *d_cx_vptr = nullptr, *d_cx_vnode = nullptr;
     double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr;   // [lam (R) | dc (n_dpar)], [u (n) | w (R)], pinned staging of both and x
+    // kinds 4 and 5 (R = nlp_rows): d_cx_in = [lam (R) | cx_cap directions], d_cx_out = cx_cap columns [u | w], d_cx_occ = cx_cap x [4][nl]
+    // occurrences of the Ohm's-law block, d_cx_vnode where each listed occurrence lives in a column's; cx_cap is 1 or KKM_CW (cx_prepare)
+    int64_t cx_cap = 0;
+    double* d_cx_occ = nullptr;
+    bool ohm_vars_ok = true;        // kind 4: every variable the block names is inside [0, n) (checked at asm_eval_setup, refused by the data entries)
     KktBufs kk;                     // KKT solve on a working set (asm_kkt_solve and the multi entries)
     int64_t kkm_rounds = 0;         // test seam: lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
     int kkm_last_active = 0;
@@ -4397,6 +4405,19 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
             P.alloc(e->h_dgrad, n_dpar, BufPool::PINNED);
         }
     }
+    if (nlp_block_derivs(nlp_kind)) {      // the data gradient's multipliers and result: a batch calls it inside fibers and must not allocate there
+        P.zeroed(e->d_lam, nlp_rows); P.zeroed(e->d_dgrad, n_dpar);
+        P.alloc(e->h_dgrad, n_dpar, BufPool::PINNED);
+        if (nlp_kind == ASM_NLP_ACOPF_OHM_HESS) {
+            const int64_t nl = nlp_rows / 4;
+            bool ok = nlp_ipar && nlp_ipar[0] == nl;
+            for (int64_t l = 0; ok && l < 2 * nl; ++l) {
+                const int64_t b = nlp_ipar[7 + l];
+                ok = nlp_ipar[1] + b >= 0 && nlp_ipar[1] + b < n && nlp_ipar[2] + b >= 0 && nlp_ipar[2] + b < n;
+            }
+            e->ohm_vars_ok = ok;
+        }
+    }
     e->L = EvLayout{n, m, K.ldn, K.Mp};      // the reductions' block with the bounds in it, and the staging buffer
     P.zeroed(e->L.d, e->L.len());
     ev_write_bounds(h, e->L);
@@ -4455,13 +4476,36 @@ static void do_set_data(asm_handle* h, int64_t offset, int64_t count, const doub
     else { e.dirty_lo = std::min(e.dirty_lo, offset); e.dirty_hi = std::max(e.dirty_hi, offset + count); }
 }
 
-// out[c] = d(f - lambda' g) / d dpar[c] at x for an expression block (k_nlp_expr_const_adj + k_nlp_expr_data_gather); the inputs of the next
-// LP are not touched (x goes where asm_eval_constraints puts its trial point)
+// the kinds with data derivatives: expression blocks and the block kernels that announce their derivative entries (kinds 4 and 5)
+static void data_kind_check(const EvalState& e, const char* who, const char* what) {
+    if (e.nlp_kind != ASM_NLP_EXPR && !nlp_block_derivs(e.nlp_kind))
+        throw std::invalid_argument(std::string(who) + ": " + what + " exist for expression blocks (nlp_kind 3) only");
+    if (!e.ohm_vars_ok) throw std::invalid_argument(std::string(who) + ": the Ohm's-law block names a variable outside [0, n)");
+}
+// out[c] = d(f - lambda' g) / d dpar[c] at x for an expression block (k_nlp_expr_const_adj + k_nlp_expr_data_gather) or a block kernel with
+// derivative entries (one launch of k_nlp_ohm_data_grad / k_nlp_dense_data_grad); the inputs of the next LP are not touched (x goes where
+// asm_eval_constraints puts its trial point)
 static void do_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
     EvalState& e = ev_of(h, "asm_eval_data_gradient");
-    if (e.nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument("asm_eval_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
+    data_kind_check(e, "asm_eval_data_gradient", "data gradients");
     if (!x || (h->sk->m > 0 && !lambda) || (e.n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
     const int64_t n = h->sk->n, nd = e.n_dpar;
+    if (nlp_block_derivs(e.nlp_kind)) {
+        if (nd == 0) return;
+        HIPCHK(hipSetDevice(h->device));
+        const int64_t R = e.nlp_rows;
+        double *st = e.h_stage, *s_lam = st + e.L.st_lam();
+        std::memcpy(st, x, n * sizeof(double));
+        std::memcpy(s_lam, lambda + e.F.n_rows, R * sizeof(double));
+        HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(e.d_lam, s_lam, R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (nlp_is_ohm(e.nlp_kind)) asmb::launch(k_nlp_ohm_data_grad, asmb::blocks(R / 4), dim3(256), h->stream, e.d_ipar, e.d_xt, e.d_lam, e.d_dgrad);
+        else asmb::launch(k_nlp_dense_data_grad, asmb::blocks(R * n), dim3(256), h->stream, R, n, e.d_xt, e.d_lam, e.d_dgrad);
+        HIPCHK(asmb::copy_async(e.h_dgrad, e.d_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+        std::memcpy(out, e.h_dgrad, nd * sizeof(double));
+        return;
+    }
     if (!e.d_cocc) {            // no CONST node: nothing depends on the data
         for (int64_t c = 0; c < nd; ++c) out[c] = 0.0;
         return;
@@ -4746,10 +4790,39 @@ static void do_hessian_product(asm_handle* h, const double* x, double obj_factor
 
 // ---- cross derivatives with respect to the data (include/asm_hip.h, "Cross derivatives of an expression block")
 namespace {
+// Kinds 4 and 5: the lists come from ipar - per variable its occurrences of k_nlp_ohm_cross, branch ascending and inside a branch in slot
+// order (vm_f, vm_t, va_f, va_t; a branch from a bus to itself lists both occurrences of a variable, in that order) - and the column
+// buffers hold `cap` directions: 1 for asm_eval_data_cross, KKM_CW from the first multi call on (the narrower ones stay in the pool)
+void cx_prepare_block(asm_handle* h, int64_t cap) {
+    EvalState& e = *h->ev;
+    if (e.cx_cap >= cap) return;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = e.mem;
+    const int64_t n = h->sk->n, R = e.nlp_rows, nl = R / 4, nd = e.n_dpar;
+    const bool ohm = nlp_is_ohm(e.nlp_kind);
+    if (ohm && !e.d_cx_vptr) {
+        const std::vector<int64_t> ip = hs_download(e.d_ipar, 7 + 2 * nl);
+        const int64_t base[4] = {ip[2], ip[2], ip[1], ip[1]};      // vm0, vm0, va0, va0
+        auto var_of = [&](int64_t l, int q) { return base[q] + ip[7 + (q & 1) * nl + l]; };
+        std::vector<int64_t> vptr(n + 1, 0);
+        for (int64_t l = 0; l < nl; ++l)
+            for (int q = 0; q < 4; ++q) ++vptr[var_of(l, q) + 1];
+        for (int64_t j = 0; j < n; ++j) vptr[j + 1] += vptr[j];
+        std::vector<int64_t> vocc(4 * nl), fill(vptr.begin(), vptr.end() - 1);
+        for (int64_t l = 0; l < nl; ++l)
+            for (int q = 0; q < 4; ++q) vocc[fill[var_of(l, q)]++] = q * nl + l;
+        M.upload(e.d_cx_vptr, vptr.data(), n + 1); M.upload(e.d_cx_vnode, vocc.data(), 4 * nl);
+    }
+    if (ohm) M.zeroed(e.d_cx_occ, cap * 4 * nl);
+    M.zeroed(e.d_cx_in, R + cap * nd); M.zeroed(e.d_cx_out, cap * (n + R));
+    if (!e.h_cx) M.alloc(e.h_cx, 2 * (n + R) + nd, BufPool::PINNED);
+    e.cx_cap = cap;
+}
 // once per asm_eval_setup, at the first asm_eval_data_cross: the VAR nodes of every variable in (row, then term) order, node descending
 // inside a row or term, and the workspace (blocking copies: not inside a batch fiber)
-void cx_prepare(asm_handle* h) {
+void cx_prepare(asm_handle* h, int64_t cap = 1) {
     EvalState& e = *h->ev;
+    if (nlp_block_derivs(e.nlp_kind)) { cx_prepare_block(h, cap); return; }
     if (e.h_cx) return;            // (the last buffer it makes)
     HIPCHK(hipSetDevice(h->device));
     const ExprTape& X = e.X;
@@ -4773,8 +4846,24 @@ void cx_prepare(asm_handle* h) {
     M.alloc(e.h_cx, 2 * (n + X.R) + e.n_dpar, BufPool::PINNED);
 }
 void cx_check(const asm_handle* h, const char* who) {
-    const EvalState& e = ev_of(h, who);
-    if (e.nlp_kind != ASM_NLP_EXPR) throw std::invalid_argument(std::string(who) + ": cross derivatives exist for expression blocks (nlp_kind 3) only");
+    data_kind_check(ev_of(h, who), who, "cross derivatives");
+}
+// kinds 4 and 5: (u, w) of `cols` directions at d_cx_in + R (pitch n_dpar) into the columns [u (n) | w (R)] of d_cx_out, at the x in d_xt and
+// with the block's multipliers in d_cx_in - one launch and a gather (Ohm's law) or two launches (dense), grid.y = column.  A column's answer
+// depends on its own direction only.
+void cx_launch_block(asm_handle* h, int cols) {
+    EvalState& e = *h->ev;
+    const hipStream_t s = h->stream;
+    const int64_t n = h->sk->n, R = e.nlp_rows, nd = e.n_dpar, ldo = n + R;
+    const double *lam = e.d_cx_in, *dc = e.d_cx_in + R;
+    if (nlp_is_ohm(e.nlp_kind)) {
+        const int64_t nl = R / 4;
+        asmb::launch(k_nlp_ohm_cross, dim3(asmb::blocks(nl).x, (unsigned)cols), dim3(256), s, e.d_ipar, e.d_xt, dc, nd, lam, e.d_cx_occ, e.d_cx_out, n, ldo);
+        asmb::launch(k_nlp_block_cross_gather, dim3(asmb::blocks(n).x, (unsigned)cols), dim3(256), s, e.d_cx_vptr, e.d_cx_vnode, e.d_cx_occ, 4 * nl, n, e.d_cx_out, ldo);
+    } else {
+        asmb::launch(k_nlp_dense_cross_w, dim3(asmb::blocks(R, 4).x, (unsigned)cols), dim3(256), s, dc, nd, R, n, e.d_xt, e.d_cx_out, ldo);
+        asmb::launch(k_nlp_dense_cross_u, dim3(asmb::blocks(n).x, (unsigned)cols), dim3(256), s, dc, nd, R, n, e.d_xt, lam, e.d_cx_out, ldo);
+    }
 }
 }  // namespace
 // u = d/dc (grad_x L) . dc, w = (dg/dc) . dc at (x, lambda), L = f - lambda' g (k_nlp_expr_cross + k_nlp_expr_cross_gather); the inputs of
@@ -4786,6 +4875,25 @@ static void do_data_cross(asm_handle* h, const double* x, const double* lambda, 
     const int64_t n = h->sk->n, m = h->sk->m, nd = e.n_dpar;
     for (int64_t j = 0; j < n; ++j) u[j] = 0.0;
     for (int64_t i = 0; i < m; ++i) w[i] = 0.0;
+    if (nlp_block_derivs(e.nlp_kind)) {      // the column kernels on one column
+        if (nd == 0) return;
+        cx_prepare(h);
+        HIPCHK(hipSetDevice(h->device));
+        const int64_t R = e.nlp_rows;
+        double* st = e.h_cx;
+        std::memcpy(st, x, n * sizeof(double));
+        std::memcpy(st + n, lambda + e.F.n_rows, R * sizeof(double));
+        std::memcpy(st + n + R, dc, nd * sizeof(double));
+        HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::copy_async(e.d_cx_in, st + n, (R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        cx_launch_block(h, 1);
+        double* back = st + n + R + nd;
+        HIPCHK(asmb::copy_async(back, e.d_cx_out, (n + R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+        std::memcpy(u, back, n * sizeof(double));
+        std::memcpy(w + e.F.n_rows, back + n, R * sizeof(double));
+        return;
+    }
     if (!e.d_cocc) return;      // no CONST node: nothing depends on the data
     cx_prepare(h);
     HIPCHK(hipSetDevice(h->device));
@@ -5414,7 +5522,15 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     double* const dlf = w.dlf;
     double* const scal = K.scal;
     const KktMulti R{K.part, K.cnt, scal, K.act, h->sk->d_hscal, h->sk->d_hseq};
-    const bool cross = sens && h->ev->d_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
+    // kinds 4 and 5: the column kernels make a chunk's right-hand sides at once, from the block's multipliers uploaded once
+    const bool cross_block = sens && nlp_block_derivs(h->ev->nlp_kind) && nd > 0;
+    if (cross_block) {
+        cx_prepare(h, KKM_CW);
+        const int64_t R = h->ev->nlp_rows;
+        std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, R * sizeof(double));
+        HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, R * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    const bool cross = sens && !cross_block && h->ev->d_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
     if (cross) {      // the multipliers of the expression rows, once
         cx_prepare(h);
         const ExprTape& X = h->ev->X;
@@ -5465,6 +5581,15 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
                 std::memcpy(hr, tr.radius + c0, cols * sizeof(double));
                 HIPCHK(asmb::copy_async(w.rad, hr, cols * sizeof(double), hipMemcpyHostToDevice, s));
             }
+        } else if (cross_block) {
+            // the chunk's directions in the staging rows, one upload, then one launch set for all its columns
+            const int64_t R = h->ev->nlp_rows;
+            double* hd = st + cap * (ldn + ldT);
+            std::memcpy(hd, DC + c0 * nd, (int64_t)cols * nd * sizeof(double));
+            HIPCHK(asmb::copy_async(h->ev->d_cx_in + R, hd, (int64_t)cols * nd * sizeof(double), hipMemcpyHostToDevice, s));
+            cx_launch_block(h, cols);
+            asmb::launch(k_kktm_cross_rhs_cols, dim3(asmb::blocks(std::max(n, nW)).x, (unsigned)cols), dim3(256), s, (const double*)h->ev->d_cx_out, n + R, n,
+                         (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru, ldn, rww, ldT);
         } else if (cross) {
             // one sweep per direction, no synchronisation between them: every direction has its own staging row
             const ExprTape& X = h->ev->X;
@@ -7811,8 +7936,7 @@ int asm_batch_slp_run_tr(asm_batch* b, int64_t n_scen, const double* c_lb, const
 int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, double* out) {
     return guarded(b, [&] {
         if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error("asm_batch_data_gradient: asm_batch_eval_setup first");
-        if (b->slots[0]->ev->nlp_kind != ASM_NLP_EXPR)
-            throw std::invalid_argument("asm_batch_data_gradient: data gradients exist for expression blocks (nlp_kind 3) only");
+        data_kind_check(*b->slots[0]->ev, "asm_batch_data_gradient", "data gradients");
         const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = (int64_t)b->dpar0.size();
         if (n_scen < 1 || !x || (m > 0 && !lambda) || (nd > 0 && !out)) throw std::invalid_argument("asm_batch_data_gradient: bad argument");
         check_scen(b, n_scen, "asm_batch_data_gradient");

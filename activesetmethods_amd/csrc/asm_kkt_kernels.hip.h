@@ -145,6 +145,18 @@ __global__ __launch_bounds__(256) void k_kktm_cross_rhs(AsmBt abt, const double*
         rww[j] = i >= n_fn ? cx[n + i - n_fn] : 0.0;
     }
 }
+// the same for a chunk of directions at once (the block kernels' cross derivatives, k_nlp_ohm_cross / k_nlp_dense_cross_*): column
+// c = blockIdx.y of cx has pitch ldc, of ru pitch ldn, of rww pitch ldT
+__global__ __launch_bounds__(256) void k_kktm_cross_rhs_cols(AsmBt abt, const double* __restrict__ cx, int64_t ldc, int64_t n, int64_t n_fn, const int* __restrict__ wrow, int64_t nW, double* __restrict__ ru, int64_t ldn, double* __restrict__ rww, int64_t ldT) {
+    ASM_BARGS(abt, cx, ldc, n, n_fn, wrow, nW, ru, ldn, rww, ldT);
+    const int64_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    cx += c * ldc;
+    if (j < n) ru[c * ldn + j] = cx[j];
+    if (j < nW) {
+        const int64_t i = wrow[j];
+        rww[c * ldT + j] = i >= n_fn ? cx[n + i - n_fn] : 0.0;
+    }
+}
 // p[c] = -g[c] + beta_c p[c] for the active columns
 __global__ __launch_bounds__(256) void k_kktm_cg_p(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ g, double* __restrict__ p, int64_t len, int64_t ldv) {
     ASM_BARGS(abt, scal, g, p, len, ldv);

@@ -76,7 +76,8 @@ class ScalarFunction:
 
 
 # the device kernels an NLP block can name (NlpBlock.device[0]) -> nlp_kind of asm_eval_setup (include/asm_hip.h: ASM_NLP_*)
-# ("acopf_ohm_hess" / "dense_quadratic_hess": the same kernels and parameters as kinds 1 / 2, and the block's second derivatives)
+# ("acopf_ohm_hess" / "dense_quadratic_hess": the same kernels and parameters as kinds 1 / 2 with their derivative entries - the block's
+# second derivatives and its derivatives with respect to its own data)
 NLP_KINDS = {"acopf_ohm": 1, "dense_quadratic": 2, "expr": 3, "acopf_ohm_hess": 4, "dense_quadratic_hess": 5}
 
 
@@ -95,10 +96,15 @@ class NlpBlock:
     eval_grad_f(x, grad) without the sense scale; it overrides the model's own objective (MOI_wrapper.jl:809-861).
     Optional second derivatives (the evaluator's :Hess): hess_rows / hess_cols (1-based; an off-diagonal entry stands for both
     symmetric positions, duplicates add) and eval_hess(x, obj_factor, lam, values) for obj_factor * hess f + sum lam_i hess g_i
-    with `lam` the block's multipliers; absent, the block announces no Hessian."""
+    with `lam` the block's multipliers; absent, the block announces no Hessian.
+    Optional derivatives with respect to the block's data (the device kernel's dpar), with the signatures of the expression twin
+    (nlexpr.ExprBlock): data_gradient(x, lam_block, scale=1.0) -> [n_dpar] and data_cross(x, lam_block, dc, scale=1.0) -> (u [n],
+    w [block rows]); absent (None), the block has no data derivatives."""
+
+    data_gradient = data_cross = None
 
     def __init__(self, g_L, g_U, rows, cols, eval_g, eval_jac_g, device=None, has_objective=False, eval_f=None, eval_grad_f=None,
-                 hess_rows=None, hess_cols=None, eval_hess=None):
+                 hess_rows=None, hess_cols=None, eval_hess=None, data_gradient=None, data_cross=None):
         self.g_L, self.g_U = np.asarray(g_L, float), np.asarray(g_U, float)
         self.rows, self.cols = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
         self.eval_g, self.eval_jac_g = eval_g, eval_jac_g
@@ -110,6 +116,10 @@ class NlpBlock:
         self.hess_rows = None if hess_rows is None else np.asarray(hess_rows, np.int64)
         self.hess_cols = None if hess_cols is None else np.asarray(hess_cols, np.int64)
         self.eval_hess = eval_hess
+        if data_gradient is not None:                      # (set only when given: ExprBlock's own methods stay in place)
+            self.data_gradient = data_gradient
+        if data_cross is not None:
+            self.data_cross = data_cross
 
     @property
     def m(self):

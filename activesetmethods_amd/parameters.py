@@ -41,7 +41,9 @@ class Parameters:
     # `hessian_type` (above, src/parameters.jl:9-10: "approximation hessian (limited-memory), exact, or none") is read by SLP-EQP: "none" and
     # "exact" use the model's own second derivatives, "limited-memory" a limited-memory BFGS approximation of the Hessian of the Lagrangian
     # held on the device (asm_hessian_set_type) - for models without second derivatives.  lm_memory: the pairs it keeps (1 .. 32).  Per
-    # handle only: the scenario batches refuse "limited-memory".
+    # handle only: the scenario batches refuse "limited-memory".  The derivative entries (Hessians, data gradients, cross derivatives,
+    # sensitivities) stay exact whatever the type: they need an expression block or a block kernel with its derivative entries
+    # (acopf.function_model(case, hessian=True), problems.synthetic_dense_function_model(n, m, hessian=True): device kinds 4 and 5).
     lm_memory: int = 10
 
     def __post_init__(self):

@@ -143,7 +143,13 @@ def synthetic_dense_function_model(n=1000, m=500, hessian=False):
     """The synthetic dense NLP as a FunctionModel: quadratic objective in the affine / quadratic store, the dense rows as an NLP
     block with the `dense_quadratic` device kernel (csrc/asm_eval_kernels.hip.h).  Same problem as `synthetic_dense_nlp`.
     hessian=True: the block also announces its second derivatives (device kind "dense_quadratic_hess", k_nlp_dense_hess): hess g_i is
-    diag(Q_i), so the pattern is the n diagonal entries and entry j is sum_i lam_i Q_ij, i ascending from 0.0."""
+    diag(Q_i), so the pattern is the n diagonal entries and entry j is sum_i lam_i Q_ij, i ascending from 0.0.
+    "dense_quadratic_hess" is the block kernel with its derivative entries: the block also carries data_gradient / data_cross, the
+    derivatives with respect to its own dpar (A then Q, row-major; the signatures of nlexpr.ExprBlock's, `scale` unused: the block has
+    no objective), the host twins of k_nlp_dense_data_grad and k_nlp_dense_cross_w / _u.  The rows are linear in dpar, so neither
+    reads A or Q:  out[A_ij] = (-lam_i) x_j,  out[Q_ij] = (-lam_i) (0.5 (x_j x_j));  along dc = (dA, dQ):  w_i = sum_j dA_ij x_j +
+    0.5 dQ_ij x_j^2  and  u_j = -sum_i lam_i (dA_ij + dQ_ij x_j), i ascending from 0.0 (gradient and u bit for bit the device's, w
+    to summation order)."""
     from .moi_evaluator import FunctionModel, ScalarFunction, NlpBlock
     pr = synthetic_dense_nlp(n, m)
     d = pr.data
@@ -161,9 +167,23 @@ def synthetic_dense_function_model(n=1000, m=500, hessian=False):
             g = g + float(lam[i]) * Q[i]
         values[:n] = g
         return values
+
+    def data_gradient(x, lam, scale=1.0):
+        x, w = np.asarray(x, float), -np.asarray(lam, float)
+        return np.concatenate([np.outer(w, x).ravel(), np.outer(w, 0.5 * (x * x)).ravel()])
+
+    def data_cross(x, lam, dc, scale=1.0):
+        x, lam, dc = np.asarray(x, float), np.asarray(lam, float), np.asarray(dc, float)
+        if dc.shape != (2 * m * n,):
+            raise ValueError("%d data directions for %d coefficients" % (dc.size, 2 * m * n))
+        dA, dQ = dc[:m * n].reshape(m, n), dc[m * n:].reshape(m, n)
+        g = np.zeros(n)
+        for i in range(m):
+            g = g + float(lam[i]) * (dA[i] + dQ[i] * x)
+        return -g, (dA * x + 0.5 * dQ * x * x).sum(axis=1)
     diag = np.arange(1, n + 1, dtype=np.int64)
     fm.nlp = NlpBlock(pr.g_L, pr.g_U, pr.j_row, pr.j_col, pr.eval_g, pr.eval_jac_g, device=("dense_quadratic_hess", np.zeros(1, np.int64), dpar),
-                      hess_rows=diag, hess_cols=diag, eval_hess=eval_hess)
+                      hess_rows=diag, hess_cols=diag, eval_hess=eval_hess, data_gradient=data_gradient, data_cross=data_cross)
     return fm
 
 

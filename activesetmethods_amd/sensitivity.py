@@ -6,8 +6,8 @@ first-order change of (x*, lam*) along a direction dc of the data solves, with H
 
     H_FF dx_F - A' dlam_W = -u_F ,     A dx_F = -w_W ,     dx_B = 0 ,    dlam_i = 0 (i not in W)
 
-with u = d/dc (grad_x (f - lam' g)) . dc and w = (dg/dc) . dc (asm_eval_data_cross / ExprBlock.data_cross).  A constraint bound that
-moves by d(bound_i) enters as u = 0, w_i = -d(bound_i).
+with u = d/dc (grad_x (f - lam' g)) . dc and w = (dg/dc) . dc (asm_eval_data_cross / ExprBlock.data_cross, NlpBlock.data_cross of the
+block kernels with derivatives).  A constraint bound that moves by d(bound_i) enters as u = 0, w_i = -d(bound_i).
 
     working_set          (row_state, bound_state) of a solution
     kkt_reference        the system assembled densely and solved with numpy.linalg.solve: the independent answer
@@ -245,7 +245,8 @@ def _jacobian_columns(DX, DLAM, infos):
 
 
 def solution_jacobian(opt, fm, x, lam, row_state, bound_state, indices=None, max_iter=None, rtol=None):
-    """(dx*/dc [n x k], dlam*/dc [m x k]) for the constants `indices` of fm's expression block (all of them when None): column q is
+    """(dx*/dc [n x k], dlam*/dc [m x k]) for the constants `indices` of fm's NLP block (all of them when None;
+    expression blocks and the block kernels with derivatives): column q is
     solution_sensitivity along the unit direction of constant indices[q], all from one asm_solution_sensitivity_multi call on `opt`
     (a HipSubOptimizer whose evaluator holds fm, or any object with its solution_sensitivity_multi).  A column whose status is not 0
     raises RuntimeError.  Below about 8 constants a loop of solution_sensitivity calls is faster ("Sensitivity matrices")."""
@@ -278,7 +279,8 @@ def bound_jacobian(opt, fm, x, lam, row_state, bound_state, rows, max_iter=None,
 
 
 def solution_sensitivity(model_or_opt, fm, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):
-    """(dx, dlam, dz, info) of asm_solution_sensitivity for the FunctionModel `fm` (an expression block with its data) at the solution
+    """(dx, dlam, dz, info) of asm_solution_sensitivity for the FunctionModel `fm` (expression blocks and the block kernels with derivatives, with
+    its data) at the solution
     (x, lam) with the working set given, along the direction dc of the block's data.  `model_or_opt`: a HipSubOptimizer whose
     evaluator holds fm (eval_setup(fm)), or a Model built from fm - then a fresh handle is made for the call and closed again."""
     from .subproblem import HipSubOptimizer, QpData

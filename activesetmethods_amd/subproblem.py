@@ -246,7 +246,7 @@ class HipSubOptimizer:
         self._check(self._lib.asm_eval_set_data(self._h, int(offset), len(v), _lib.dptr(v)))
 
     def eval_data_gradient(self, x, lam):
-        """d(f - lam' g) / d dpar at x (asm_eval_data_gradient; expression blocks only), lam [m] in the sign convention of
+        """d(f - lam' g) / d dpar at x (asm_eval_data_gradient; expression blocks and the block kernels with derivatives, device kinds 3, 4 and 5), lam [m] in the sign convention of
         slp_run's multipliers: at an SLP solution, the derivative of the optimal value with respect to each dpar entry."""
         x, lam = _f64(x), _f64(np.atleast_1d(lam) if self.m else np.zeros(1))
         nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
@@ -298,7 +298,7 @@ class HipSubOptimizer:
 
     def data_cross(self, x, lam, dc):
         """(u, w) of asm_eval_data_cross: u [n] = d/d dpar (grad_x (f - lam' g)) . dc and w [m] = (d g / d dpar) . dc for a direction dc in the
-        expression block's data, lam [m] in the sign convention of slp_run's multipliers."""
+        block's data (expression blocks and the block kernels with derivatives), lam [m] in the sign convention of slp_run's multipliers."""
         nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
         x, lam, dc = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(dc, nd, "dc")
         u, w = np.empty(self.n), np.empty(max(self.m, 1))
@@ -342,7 +342,7 @@ class HipSubOptimizer:
 
     def solution_sensitivity(self, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):
         """(dx, dlam, dz, info) of asm_solution_sensitivity: the directional derivative of the solution and its multipliers along the
-        direction dc in the expression block's data, on the working set given."""
+        direction dc in the block's data (expression blocks and the block kernels with derivatives), on the working set given."""
         nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
         x, lam, dc = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(dc, nd, "dc")
         rs, bs = self._states(row_state, bound_state)
@@ -376,7 +376,7 @@ class HipSubOptimizer:
 
     def solution_sensitivity_multi(self, x, lam, row_state, bound_state, DC, max_iter=None, rtol=None):
         """(DX, DLAM, DZ, infos) of asm_solution_sensitivity_multi: solution_sensitivity for the nrhs directions in the rows of
-        DC [nrhs x n_dpar] on one factor, one row of the outputs per direction."""
+        DC [nrhs x n_dpar] on one factor, one row of the outputs per direction (expression blocks and the block kernels with derivatives)."""
         nd = len(self._ev_keep[2]) if getattr(self, "_ev_keep", None) is not None else 0
         x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
         par = self._kkt_params(max_iter, rtol)

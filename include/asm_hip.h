@@ -178,7 +178,8 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *                                arrays); 2 dense quadratic rows g = A x + 1/2 Q x^2 (dpar = A then Q, row-major);
  *                                3 expression block (below); 4 = kind 1 and 5 = kind 2 with second derivatives: the same ipar / dpar,
  *                                size checks, kernels and bits for values, Jacobian, asm_eval_set_data and every SLP launch - they
- *                                differ from kinds 1 and 2 only in that the Hessian entries below accept them
+ *                                differ from kinds 1 and 2 only in that the derivative entries below accept them: they are the
+ *                                block kernels with their derivative entries (the Hessian and the data derivatives)
  * The affine / quadratic part is bit-identical to the host evaluator (no fused multiply-add, the reference's term order).
  *
  * Expression block (nlp_kind = ASM_NLP_EXPR): the constraint and objective expressions of the reference's NLP block
@@ -252,7 +253,8 @@ int asm_eval_jacobian_values(asm_handle* h, double* dE_out);
  * every later evaluation (asm_eval_functions, asm_eval_constraints, the merit and line-search entries, asm_slp_run(_tr)) is bit-identical
  * to that of a handle set up from scratch with the changed dpar. */
 int asm_eval_set_data(asm_handle* h, int64_t offset, int64_t count, const double* values);
-/* The data gradient of the Lagrangian at (x, lambda), expression blocks only (other kinds: ASM_ERR_ARG):
+/* The data gradient of the Lagrangian at (x, lambda), for expression blocks (kind 3) and for the block kernels with their derivative
+ * entries (kinds 4 and 5: "Data derivatives of the block kernels" below); other kinds: ASM_ERR_ARG:
  *   out[c] = d f / d dpar[c] - sum_i lambda_i d g_i / d dpar[c]      c < n_dpar
  * f the objective as asm_eval_functions returns it (sense scale included), g the block's rows, lambda [m] in the sign convention of
  * asm_slp_run (KT residual df - J'lambda - mult_x_U - mult_x_L): at an SLP solution out is dV/d dpar, V the optimal value (envelope
@@ -267,7 +269,8 @@ int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda,
  * solution move with dpar.  With L = f - lambda' g in the convention of asm_slp_run and asm_eval_data_gradient (f with the sense scale,
  * lambda [m]) and a direction dc [n_dpar] in the data:
  *   u [n] = d/d dpar (grad_x L) . dc        w [m] = (d g / d dpar) . dc    (0 for the rows of the function store: its constants are not data)
- * Expression blocks only (other kinds: ASM_ERR_ARG); ASM_ERR_STATE before asm_eval_setup, ASM_ERR_ARG for a null pointer.  The inputs of the
+ * Expression blocks, and the block kernels with their derivative entries in the closed forms of the next section (other kinds:
+ * ASM_ERR_ARG); ASM_ERR_STATE before asm_eval_setup, ASM_ERR_ARG for a null pointer.  The inputs of the
  * next LP are not touched (as asm_eval_constraints).  The per-variable occurrence list and the workspace are made by the first call after
  * asm_eval_setup.  A tape without CONST node: u = w = 0 without a launch.
  * Order: per row or term one forward-over-reverse sweep, the one of the Hessian (the statement tangents listed under "Hessian of the
@@ -279,6 +282,39 @@ int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda,
  * nodes of j in descending node order.  No atomics.  With ADD..POWI, ABS, MIN and MAX only, device and host twin (nlexpr.py:
  * ExprBlock.data_cross) agree bit for bit, else in the math library's last bits. */
 int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w);
+
+/* ---- Data derivatives of the block kernels: kinds 4 and 5 are the Ohm's-law and the dense quadratic kernel WITH THEIR DERIVATIVE ENTRIES -
+ * besides the Hessian (below) the derivatives with respect to their own dpar, so that asm_eval_data_gradient, asm_eval_data_cross,
+ * asm_solution_sensitivity(_multi) and asm_batch_data_gradient accept them as they accept kind 3, with the same conventions (L = f - lambda' g,
+ * lambda in the sign convention of asm_slp_run, block row r = problem row n_rows + r) and the same errors.  Kinds 1 and 2 stay refused with
+ * ASM_ERR_ARG.  Both blocks are linear in dpar and have no objective, so the derivatives are closed forms that never read dpar: the results
+ * depend on (x, lambda) and the direction only, not on asm_eval_set_data or a scenario's data.  What the data gradient needs is made by
+ * asm_eval_setup, the cross workspace (per-variable occurrence lists from ipar, occurrences, [u | w] per column) by the first cross call.
+ * No fused multiply-add, no atomics; every written operation is one rounding, left to right.
+ *   Ohm's-law block (kind 4), dpar = k_ff_p, k_ff_q, k_tt_p, k_tt_q, a_f, b_f, a_t, b_t (n_branch each) - the layout and the meaning of
+ *   the 8 n_branch parameters of the same rows as an expression block with the coefficients as parameters.  Per branch l, vf, vt, d = va_f -
+ *   va_t, cs = cos(d), sn = sin(d), vv = vf * vt as in the value kernel, l0..l3 the multipliers of its rows pfr, qfr, pto, qto (row = x_flow - F_r):
+ *     data gradient out[q n_branch + l] = lambda_r dF_r/dc, with vf2 = vf*vf, vt2 = vt*vt, vvc = vv*cs, vvs = vv*sn:
+ *       l0*vf2   l1*vf2   l2*vt2   l3*vt2   l0*vvc + l1*vvs   l0*vvs - l1*vvc   l2*vvc - l3*vvs   -(l2*vvs) - l3*vvc
+ *     (one launch, one thread per branch; no sum runs across branches).
+ *     cross derivatives along dc: F_r(dc) and the families dvf_r(dc), dvt_r(dc), dth_r(dc) are the value kernel's expressions for the flows
+ *     and their derivatives with dc where dpar stands, e.g. F_pfr = k*vf*vf + a*vv*cs + b*vv*sn, evaluated left to right;
+ *       w[n_rows + r n_branch + l] = -F_r(dc)
+ *     and the branch has four occurrences in u, the sums in row order from the first term, ((l0*t0 + l1*t1) + l2*t2) + l3*t3:
+ *       vm_f: sum_r lambda_r dvf_r     vm_t: sum_r lambda_r dvt_r     va_f: theta = sum_r lambda_r dth_r     va_t: -theta
+ *     u[j] sums the occurrences of variable j from 0.0 by branch ascending and, inside a branch, in that slot order; a variable without one
+ *     (flows, generators) gets 0.  A branch from a bus to itself needs no refusal here: its two occurrences of a variable add in slot order.
+ *     Device and host twin (acopf.py: _ohm_data_twins) differ at most in the last bits of sin and cos.
+ *   Dense quadratic block (kind 5), dpar = A then Q (m_blk x n, row-major), g_i = sum_j A_ij x_j + 1/2 Q_ij x_j^2:
+ *     data gradient out[i n + j] = (-lambda_i) * x_j     out[m_blk n + i n + j] = (-lambda_i) * (0.5 * (x_j * x_j))
+ *     cross derivatives along dc = (dA, dQ):  w[n_rows + i] = sum_j (dA_ij*x_j + 0.5*dQ_ij*x_j*x_j), one wavefront per row, lane-strided from
+ *     0.0, then the xor tree of the value kernel;  u[j] = -(sum_i lambda_i * (dA_ij + dQ_ij * x_j)), i ascending from 0.0.  Gradient and u are
+ *     bit-identical to the host twin (problems.py), w agrees to summation order.
+ * asm_solution_sensitivity_multi on these kinds stages a chunk's directions once (one upload) and makes all its right-hand sides with one
+ * launch of the cross kernel, one gather (kind 5: two launches) and one scatter into the chunk's blocks, the column in grid.y - in place of
+ * one upload and three launches per direction.  Column c equals asm_eval_data_cross of that direction alone bit for bit, and a column's
+ * answer depends on its own direction only.  The staging of a chunk is ASM_KKT_CHUNK x n_dpar doubles on the host and on the device, as for
+ * every kind: for the dense block of the synthetic NLP with n = 1000, m = 500 (n_dpar = 10^6) that is 512 MB each. */
 
 /* ---- Hessian of the Lagrangian: hessian_lagrangian_structure / eval_hessian_lagrangian (MOI_wrapper.jl:748-774, 946-978; eval_h_cb :1071-1083)
  *   H = obj_factor * objective_scale * hess f + sum_i lambda_i hess g_i        lambda [m], PLUS sign (the MOI convention, :960-978, :1080)
@@ -396,8 +432,9 @@ typedef struct {
 } asm_kkt_info;
 int asm_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                   const double* ru, const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info);
-/* Solution sensitivity of an expression block's data: asm_eval_data_cross(x, lambda, dc) followed by asm_kkt_solve(ru = u, rw = w).  At an
- * SLP solution with its working set, dx = (dx* / d dpar) . dc and dlam = (dlambda* / d dpar) . dc.  Expression blocks only. */
+/* Solution sensitivity of a block's data: asm_eval_data_cross(x, lambda, dc) followed by asm_kkt_solve(ru = u, rw = w).  At an
+ * SLP solution with its working set, dx = (dx* / d dpar) . dc and dlam = (dlambda* / d dpar) . dc.  Expression blocks and the block
+ * kernels with their derivative entries (kinds 3, 4, 5). */
 int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                              const double* dc, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info);
 
@@ -431,7 +468,8 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  *   dimensions, and the rows of a block beyond the chunk's columns are never part of a launch.  Against asm_kkt_solve the agreement is to
  *   tolerance: the summation orders of the two back ends' products differ.
  * asm_solution_sensitivity_multi makes (u, w) of each direction with the cross-derivative sweep of asm_eval_data_cross - one launch set per
- * direction, written straight into the chunk's blocks, no synchronisation between directions - and then runs the same solve.
+ * direction, written straight into the chunk's blocks, no synchronisation between directions - and then runs the same solve (kinds 4
+ * and 5: one launch set per chunk, "Data derivatives of the block kernels").
  * The buffers are made at the first multi call and released with asm_kkt_solve's; a handle that calls asm_kkt_solve alone holds blocks
  * of one column.
  * When to use it: a lockstep round launches block products whose time does not shrink with the number of columns, live or frozen - on
@@ -722,7 +760,9 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
  * so results never depend on what a slot solved before.  The reference basis-column LP on slot 0 uses scenario 0's data.  The table stays
  * set until it is cleared or asm_batch_eval_setup is called again; a batch call over another number of scenarios is ASM_ERR_ARG. */
 int asm_batch_set_scenario_data(asm_batch* b, int64_t n_scen, int64_t offset, int64_t count, const double* table);
-/* asm_eval_data_gradient of n_scen scenarios, each with its data: x [n_scen x n], lambda [n_scen x m], out [n_scen x n_dpar] */
+/* asm_eval_data_gradient of n_scen scenarios, each with its data: x [n_scen x n], lambda [n_scen x m], out [n_scen x n_dpar]; the kinds
+ * of asm_eval_data_gradient (3, 4, 5).  For kinds 4 and 5 a scenario's result does not depend on its data at all, only on its (x, lambda):
+ * the blocks are linear in dpar. */
 int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, double* out);
 /* ---- Hessian of the Lagrangian of n_scen scenarios (asm_eval_hessian_* with a leading scenario dimension): the MOI plus-sign convention
  * of asm_eval_hessian_lagrangian - pass -lambda for the multipliers asm_batch_slp_run returns.  The pattern is the one
