@@ -108,6 +108,15 @@ class KktFormInfo(C.Structure):
 KKT_FORMS = {"dense": 0, "sparse": 1}
 
 
+class KktOrderInfo(C.Structure):
+    """asm_kkt_order_info: the row order of the sparse form asked for and used by the last KKT call (0 working-set, 1 static), the band and
+    the structural pairs of S over all m rows in the static order (0 before the first sparse call)."""
+    _fields_ = [("order_requested", C.c_int32), ("order_used", C.c_int32), ("all_band", C.c_int64), ("all_pairs", C.c_int64)]
+
+
+KKT_ORDERS = {"working-set": 0, "static": 1}
+
+
 class EqpInfo(C.Structure):
     """asm_eqp_info: asm_kkt_step_info's fields; skipped 0 none, 1 more working rows than free variables, 2 dependent working rows,
     3 zero step; t, the norms of d = t dx, the merit function at x and at x + d."""
@@ -179,6 +188,9 @@ PROTOTYPES = {
     "asm_kkt_step_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
     "asm_kkt_set_form": (C.c_int, [_P, C.c_int32]),
     "asm_kkt_form_info": (C.c_int, [_P, C.POINTER(KktFormInfo)]),
+    "asm_kkt_set_order": (C.c_int, [_P, C.c_int32]),
+    "asm_kkt_order_info": (C.c_int, [_P, C.POINTER(KktOrderInfo)]),
+    "asm_kkt_row_order": (C.c_int, [_P, _I32, _I64]),
     "asm_eval_hessian_structure": (C.c_int, [_P, _I64, _I64, _I64]),
     "asm_eval_hessian_lagrangian": (C.c_int, [_P, _D, C.c_double, _D, _D]),
     "asm_eval_hessian_product": (C.c_int, [_P, _D, C.c_double, _D, _D, _D]),
@@ -223,6 +235,7 @@ PROTOTYPES = {
                                        C.POINTER(SlpTrInfo)]),
     "asm_batch_slp_run_eqp": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, C.POINTER(SlpParams), C.c_double, C.POINTER(SlpEqpParams), _D, _D, _D, _D, _D,
                                         C.POINTER(SlpResult), C.POINTER(SlpTrInfo), C.POINTER(SlpEqpInfo)]),
+    "asm_batch_kkt_set_form": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "asm_batch_get_stats": (C.c_int, [_P, C.POINTER(BatchStats)]),
     "asm_test_syrk": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, _D, C.c_int]),
     "asm_test_syrk_update": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, C.c_int]),

@@ -87,15 +87,17 @@ def slp_params(par, max_lp_solves=0):
 
 
 NATIVE_ALGORITHMS = ("Line Search", "Trust Region", "SLP-EQP")      # asm_slp_run, asm_slp_run_tr, asm_slp_run_eqp and their batch forms
+KKT_DEFAULT = ("dense", "working-set")                              # what asm_batch_eval_setup starts every batch from (asm_batch_kkt_set_form)
 
 
 def check_batch_kkt_form(par):
-    """The sparse form of the KKT solve is per handle only (asm_kkt_set_form): the scenario batches run the dense form, and a Parameters
-    object that asks for the sparse one is refused before anything is built or run.  So is the limited-memory Hessian
-    (asm_hessian_set_type)."""
-    if getattr(par, "kkt_form", "dense") != "dense":
-        raise ValueError("Parameters(kkt_form=%r): the scenario batches (asm_batch_*) run the dense form of the KKT solve only - the sparse form "
-                         "is per handle (SlpEQP, optimize(native=True), HipSubOptimizer.set_kkt_form)" % (par.kkt_form,))
+    """The scenario batches run the dense form of the KKT solve, or the sparse form in the static row order (asm_batch_kkt_set_form).  The
+    sparse form in the working-set order is per handle only (it orders, uploads and waits at every new working set): a Parameters object
+    that asks for it is refused before anything is built or run.  So is the limited-memory Hessian (asm_hessian_set_type)."""
+    if getattr(par, "kkt_form", "dense") != "dense" and getattr(par, "kkt_order", "working-set") != "static":
+        raise ValueError("Parameters(kkt_form=%r, kkt_order=%r): the scenario batches (asm_batch_*) run the sparse form of the KKT solve in the "
+                         "static row order only - the working-set order is per handle (SlpEQP, optimize(native=True), "
+                         "HipSubOptimizer.set_kkt_form); give kkt_order=\"static\"" % (par.kkt_form, getattr(par, "kkt_order", "working-set")))
     if getattr(par, "hessian_type", "none") == "limited-memory":
         raise ValueError("Parameters(hessian_type='limited-memory'): the scenario batches (asm_batch_*) use the model's own second derivatives - "
                          "the limited-memory Hessian is per handle (SlpEQP, optimize(native=True), HipSubOptimizer.set_hessian_type)")
@@ -181,6 +183,7 @@ class HipBatch:
                                                    _lib.dptr(a("constant")), _lib.i64ptr(a("jac_off")), _lib.i64ptr(a("g_ptr")), _lib.i64ptr(a("g_kind")),
                                                    _lib.dptr(a("g_coef")), _lib.i64ptr(a("g_other")), float(fl["objective_scale"]), kind, rows, nnz,
                                                    _lib.i64ptr(ipar), len(ipar) if kind else 0, _lib.dptr(dpar), len(dpar) if kind else 0))
+        self._kkt = KKT_DEFAULT
 
     def _check(self, rc):
         if rc != 0:
@@ -215,6 +218,16 @@ class HipBatch:
         s = _lib.BatchStats()
         self._check(self._lib.asm_batch_get_stats(self._b, self._C.byref(s)))
         return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def set_kkt_form(self, form, order="working-set"):
+        """asm_batch_kkt_set_form: the form ("dense" / "sparse") and row order ("working-set" / "static") of the KKT solves of the SLP-EQP
+        runs on every slot.  ("sparse", "working-set") is refused: that order is per handle.  setup() starts from dense again."""
+        from . import _lib
+        if form not in _lib.KKT_FORMS or order not in _lib.KKT_ORDERS:
+            raise ValueError("kkt form %r, order %r: expected one of %s and one of %s"
+                             % (form, order, ", ".join(map(repr, _lib.KKT_FORMS)), ", ".join(map(repr, _lib.KKT_ORDERS))))
+        self._check(self._lib.asm_batch_kkt_set_form(self._b, _lib.KKT_FORMS[form], _lib.KKT_ORDERS[order]))
+        self._kkt = (form, order)
 
     def set_scenario_data(self, data, offset=0):
         """The scenario data table (asm_batch_set_scenario_data): row s of `data` [n_scen x count] is written to dpar[offset, offset + count)
@@ -267,6 +280,9 @@ class HipBatch:
             raise ValueError("the data table has %d rows for %d scenarios" % (np.atleast_2d(data).shape[0], S))
         if data is not None or self.nlp_kind:
             self.set_scenario_data(data, data_offset)
+        kkt = (getattr(parameters, "kkt_form", "dense"), getattr(parameters, "kkt_order", "working-set"))
+        if kkt != getattr(self, "_kkt", KKT_DEFAULT):      # (what the batch has: set_kkt_form, or the set-up's default)
+            self.set_kkt_form(*kkt)
         par = slp_params(parameters, max_lp_solves)
         x = np.empty((S, self.n)); lam = np.empty((S, max(self.m, 1))); mU = np.empty((S, self.n)); mL = np.empty((S, self.n)); g = np.empty((S, max(self.m, 1)))
         res = (_lib.SlpResult * S)()

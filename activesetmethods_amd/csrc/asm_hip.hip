@@ -280,6 +280,17 @@ struct KktBufs {
     std::vector<int> c_order;
     int c_band = 0;
     bool c_valid = false;
+    // the row order of the sparse form (asm_kkt_set_order) and the one the last call used; c_kind: the order the cache above was made in (a
+    // call in the other order misses: the two keep different lists on the device)
+    int order = ASM_KKT_ORDER_WORKING_SET, order_used = ASM_KKT_ORDER_WORKING_SET, c_kind = ASM_KKT_ORDER_WORKING_SET;
+    // static order: the reverse Cuthill-McKee order of all m rows (kk_sparse keeps it), its band, and the structural pairs of all rows as
+    // row-index pairs - on the host for the band of a working set, on the device (kk_static, uploaded once) for the build of S.  s_place:
+    // host scratch, the place of every row in the working set of the cache (-1: outside)
+    std::vector<int> s_order, s_pairs_h, s_place;
+    int* s_pairs = nullptr;
+    int64_t s_npairs = 0;
+    int s_band = 0;
+    std::vector<int> last_rows;      // the working rows of the last KKT call in the order used (asm_kkt_row_order)
     // asm_eqp_trial (eq_prepare): [the LP's row_state (M) | its bound_state (n) | twin (m) || row_state (m) | bound_state (n) | counts (4) ||
     // side (m)], [rw (m) | dx (n) | d (n) | scalars (EQP_SCAL)], and the pinned image of both followed by n doubles for the gradient
     int* eq_i = nullptr;
@@ -5111,9 +5122,9 @@ void kk_dense(asm_handle* h) {
     HIPCHK(asmb::sync(s));
     K.dense_ready = true;
 }
-// what only the sparse form needs, at its first call: the CSR values, the position list and the pair buffer.  The pairs of any working
-// set are a subset of the pairs of all m rows: the buffer is sized once from those.  False: rcm_order declines the pattern (RCM_MAX_PAIRS)
-// and the call runs the dense form.
+// what only the sparse form needs, at its first call: the CSR values and the position list.  The pairs of any working set are a subset of
+// the pairs of all m rows: the pair buffer of either row order (kk_pairs) is sized from those, and the order of all rows with its pairs
+// stays on the host for the static order.  False: rcm_order declines the pattern (RCM_MAX_PAIRS) and the call runs the dense form.
 bool kk_sparse(asm_handle* h) {
     kk_prepare(h);
     KktBufs& K = h->ev->kk;
@@ -5126,15 +5137,36 @@ bool kk_sparse(asm_handle* h) {
     std::vector<int> all((size_t)S.m), prs;
     for (int64_t i = 0; i < S.m; ++i) all[i] = (int)i;
     int bw = 0;
-    (void)rcm_order(all, S.sp_ptr_h, S.sp_col_h, S.ldn, &bw, &prs);
+    K.s_order = rcm_order(all, S.sp_ptr_h, S.sp_col_h, S.ldn, &bw, &prs);
     if (S.m > 0 && prs.empty()) return false;
     K.pairs_cap = std::max<int64_t>((int64_t)prs.size() / 2, 1);
+    K.s_band = bw;
+    K.s_npairs = (int64_t)prs.size() / 2;
+    K.s_pairs_h.resize(prs.size());
+    for (size_t k = 0; k < prs.size(); ++k) K.s_pairs_h[k] = K.s_order[prs[k]];      // (places in the order -> rows)
+    K.s_place.assign((size_t)std::max<int64_t>(S.m, 1), -1);
+    K.c_state.reserve((size_t)S.m);
+    K.c_order.reserve((size_t)S.m);
+    K.last_rows.reserve((size_t)S.m);
     M.zeroed(K.sp_vals, S.sp_nnz, s);
-    M.alloc(K.pairs, 2 * K.pairs_cap);
     M.alloc(K.wpos, std::max<int64_t>(S.M, 1));
-    K.sparse_bytes += S.sp_nnz * (int64_t)sizeof(double) + (2 * K.pairs_cap + std::max<int64_t>(S.M, 1)) * (int64_t)sizeof(int);
+    K.sparse_bytes += S.sp_nnz * (int64_t)sizeof(double) + std::max<int64_t>(S.M, 1) * (int64_t)sizeof(int);
     HIPCHK(asmb::sync(s));
     return true;
+}
+// the pair buffer of the row order in use, at the first sparse call in that order: 2 * pairs_cap ints either way.  Working-set order: every
+// new working set uploads its own pairs (kk_order).  Static order: the row-index pairs of all rows, uploaded here, once
+void kk_pairs(asm_handle* h, int order) {
+    KktBufs& K = h->ev->kk;
+    int*& buf = order == ASM_KKT_ORDER_STATIC ? K.s_pairs : K.pairs;
+    if (buf) return;
+    HIPCHK(hipSetDevice(h->device));
+    h->ev->mem.alloc(buf, 2 * K.pairs_cap);
+    K.sparse_bytes += 2 * K.pairs_cap * (int64_t)sizeof(int);
+    if (order == ASM_KKT_ORDER_STATIC && K.s_npairs > 0) {
+        HIPCHK(asmb::copy_async(buf, K.s_pairs_h.data(), K.s_pairs_h.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+    }
 }
 // the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it; the unmasked transposed working rows of the dense
 // block products at the first dense call
@@ -5215,9 +5247,11 @@ void kk_order(asm_handle* h, KktFace& f, const int32_t* row_state) {
     KktBufs& K = h->ev->kk;
     const Skeleton& S = *h->sk;
     const int64_t m = S.m, nW = f.nW;
-    const bool hit = K.c_valid && (int64_t)K.c_state.size() == m && std::equal(row_state, row_state + m, K.c_state.begin());
+    kk_pairs(h, ASM_KKT_ORDER_WORKING_SET);
+    const bool hit = K.c_valid && K.c_kind == ASM_KKT_ORDER_WORKING_SET && (int64_t)K.c_state.size() == m && std::equal(row_state, row_state + m, K.c_state.begin());
     if (!hit) {
         K.c_valid = false;      // (until the new order and both device lists are in place)
+        K.c_kind = ASM_KKT_ORDER_WORKING_SET;
         const double t0 = Solver::now_ms();
         const std::vector<int> rows(f.wl.begin(), f.wl.begin() + nW);
         std::vector<int> prs;
@@ -5244,6 +5278,43 @@ void kk_order(asm_handle* h, KktFace& f, const int32_t* row_state) {
     K.last.band = K.c_band;
     K.last.n_pairs = K.n_pairs;
     K.last.order_reused = hit ? 1 : 0;
+}
+// Sparse form, static order (asm_kkt_set_order): f.wl is the order of all rows (kk_sparse) filtered by row_state - the coupling graph of W is
+// an induced subgraph of that of all rows and places only move closer, so the band is at most the all-rows band.  The band (the exact
+// largest distance over the static pairs with both rows in W) and the pair count are the host's; the cache is the one of kk_order.  Nothing
+// goes up and nothing is waited for: the caller makes the position list on the device from the uploaded f.wl where this returns false.
+bool kk_order_static(asm_handle* h, KktFace& f, const int32_t* row_state) {
+    KktBufs& K = h->ev->kk;
+    const int64_t m = h->sk->m, nW = f.nW;
+    const bool hit = K.c_valid && K.c_kind == ASM_KKT_ORDER_STATIC && (int64_t)K.c_state.size() == m && std::equal(row_state, row_state + m, K.c_state.begin());
+    if (!hit) {
+        K.c_valid = false;
+        K.c_kind = ASM_KKT_ORDER_STATIC;
+        const double t0 = Solver::now_ms();
+        K.c_order.clear();
+        for (int64_t p = 0; p < m; ++p) {
+            const int r = K.s_order[p];
+            K.s_place[r] = row_state[r] ? (int)K.c_order.size() : -1;
+            if (row_state[r]) K.c_order.push_back(r);
+        }
+        int bw = 0;
+        int64_t np = 0;
+        for (int64_t t = 0; t < K.s_npairs; ++t) {
+            const int pi = K.s_place[K.s_pairs_h[2 * t]], pj = K.s_place[K.s_pairs_h[2 * t + 1]];
+            if (pi < 0 || pj < 0) continue;
+            bw = std::max(bw, std::abs(pi - pj));
+            ++np;
+        }
+        K.c_band = nW > 0 ? std::max(bw, 1) : 0;
+        K.n_pairs = np;
+        K.c_state.assign(row_state, row_state + m);
+        K.last.order_ms = Solver::now_ms() - t0;      // (c_valid: once the caller has the position list launched)
+    }
+    for (int64_t q = 0; q < nW; ++q) f.wl[q] = K.c_order[q];
+    K.last.band = K.c_band;
+    K.last.n_pairs = K.n_pairs;
+    K.last.order_reused = hit ? 1 : 0;
+    return hit;
 }
 KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                  const asm_kkt_params* par, bool use_lm) {
@@ -5273,6 +5344,9 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     // the form: sparse when asked for and possible - a sparse pattern that rcm_order accepts - else dense, which is not an error
     f.sparse = K.form == ASM_KKT_SPARSE && h->sk->sp_ok && kk_sparse(h);
     if (!f.sparse) kk_dense(h);
+    const bool fixed = f.sparse && K.order == ASM_KKT_ORDER_STATIC;
+    if (fixed) kk_pairs(h, ASM_KKT_ORDER_STATIC);
+    K.order_used = fixed ? ASM_KKT_ORDER_STATIC : ASM_KKT_ORDER_WORKING_SET;
     HIPCHK(hipSetDevice(h->device));
     const hipStream_t s = h->stream;
     const int64_t Mp = std::max<int64_t>(h->sk->Mp, 32);
@@ -5323,11 +5397,16 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         int64_t q = 0;
         for (int64_t i = 0; i < m; ++i)
             if (row_state[i]) f.wl[q++] = (int)i;
-        if (f.sparse) kk_order(h, f, row_state);
+        const bool made = !f.sparse || (fixed ? kk_order_static(h, f, row_state) : (kk_order(h, f, row_state), true));
+        K.last_rows.assign(f.wl.begin(), f.wl.begin() + f.nW);
         std::memcpy(st + ldn, f.wl.data(), Mp * sizeof(int));
         HIPCHK(asmb::copy_async(K.sets, st, ldn * sizeof(double) + Mp * sizeof(int), hipMemcpyHostToDevice, s));
         f.mask = K.sets;
         f.wrow = reinterpret_cast<const int*>(K.sets + ldn);
+        if (!made) {      // static order, a new working set: the place of every LP row in it, from the list just uploaded
+            asmb::launch(k_kkts_wpos, dim3(1), dim3(1024), s, f.wrow, f.nW, std::max<int64_t>(h->sk->M, 1), K.wpos);
+            K.c_valid = true;
+        }
     }
     // A = J[W, F] as a dense operand and its transposed copy with the k-padding cleared; S = A A' and its factor (Dev::chol leaves the
     // wide-block inverses too); the dropped pivots
@@ -5347,8 +5426,14 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
             HIPCHK(asmb::fill_async(K.fac.S, 0, nW * K.fac.ld * sizeof(double), s));
             K.fac_full_rows = std::min<int64_t>(round_up(nW, 64), K.fac.ld);
         }
-        asmb::launch(k_ns_s0_sparse, asmb::blocks(K.n_pairs), dim3(256), s, (const int*)K.pairs, K.n_pairs, (const int*)h->sk->d_sp_ptr, (const int*)h->sk->d_sp_col,
-                     (const double*)K.sp_vals, f.wrow, f.mask, K.fac.S, K.fac.ld);
+        // (static order: every structural pair of all rows through the position list, those with a row outside W skipped - one grid for
+        // every working set and every scenario of a batch)
+        if (fixed)
+            asmb::launch(k_schur_sparse, asmb::blocks(K.s_npairs), dim3(256), s, (const int*)K.s_pairs, K.s_npairs, (const int*)K.wpos, (const int*)h->sk->d_sp_ptr,
+                         (const int*)h->sk->d_sp_col, (const double*)K.sp_vals, f.mask, (const double*)nullptr, K.fac.S, K.fac.ld, (const int*)nullptr);
+        else
+            asmb::launch(k_ns_s0_sparse, asmb::blocks(K.n_pairs), dim3(256), s, (const int*)K.pairs, K.n_pairs, (const int*)h->sk->d_sp_ptr, (const int*)h->sk->d_sp_col,
+                         (const double*)K.sp_vals, f.wrow, f.mask, K.fac.S, K.fac.ld);
         dev.diag_prepare(K.fac, (int)nW, 1, 0.0, 0.0);
         const int nfact = h->stats.nfact;
         dev.chol(K.fac, (int)nW, 1e-10);
@@ -5857,6 +5942,29 @@ int asm_kkt_set_form(asm_handle* h, int32_t form) {
         if (form != ASM_KKT_DENSE && form != ASM_KKT_SPARSE) throw std::invalid_argument("asm_kkt_set_form: form is neither ASM_KKT_DENSE nor ASM_KKT_SPARSE");
         e.kk.form = form;
     });
+}
+int asm_kkt_set_order(asm_handle* h, int32_t order) {
+    return guarded(h, [&] {
+        EvalState& e = ev_of(h, "asm_kkt_set_order");
+        if (order != ASM_KKT_ORDER_WORKING_SET && order != ASM_KKT_ORDER_STATIC)
+            throw std::invalid_argument("asm_kkt_set_order: order is neither ASM_KKT_ORDER_WORKING_SET nor ASM_KKT_ORDER_STATIC");
+        e.kk.order = order;
+    });
+}
+int asm_kkt_order_info(const asm_handle* h, struct asm_kkt_order_info* out) {
+    if (!h || !out) return ASM_ERR_ARG;
+    if (!h->ev) return ASM_ERR_STATE;
+    const KktBufs& K = h->ev->kk;
+    *out = {K.order, K.order_used, K.s_band, K.s_npairs};
+    return ASM_OK;
+}
+int asm_kkt_row_order(const asm_handle* h, int32_t* rows, int64_t* nW) {
+    if (!h || !nW) return ASM_ERR_ARG;
+    if (!h->ev) return ASM_ERR_STATE;
+    const std::vector<int>& L = h->ev->kk.last_rows;
+    *nW = (int64_t)L.size();
+    if (rows) std::copy(L.begin(), L.end(), rows);
+    return ASM_OK;
 }
 int asm_kkt_form_info(const asm_handle* h, struct asm_kkt_form_info* out) {
     if (!h || !out) return ASM_ERR_ARG;
@@ -7591,6 +7699,7 @@ struct asm_batch {
     int64_t scen_n = 0, scen_off = 0, scen_cnt = 0;
     std::unique_ptr<HsShared> hs;   // pattern and lists of the Hessian of the Lagrangian, one copy for every slot (asm_batch_hessian_*); dropped by
                                     // asm_batch_eval_setup
+    int kkt_form = ASM_KKT_DENSE, kkt_order = ASM_KKT_ORDER_WORKING_SET;      // asm_batch_kkt_set_form; asm_batch_eval_setup starts from these
     bool setup_done = false;
     asm_batch_stats stats;
     bool verbose = false;           // ASM_BATCH_VERBOSE=1: per-kernel merge statistics of every group at release
@@ -7800,6 +7909,21 @@ int asm_batch_eval_setup(asm_batch* b, int64_t n_rows, const int64_t* aff_ptr, c
         else b->dpar0.clear();
         b->scen_tab.clear();
         b->scen_n = b->scen_off = b->scen_cnt = 0;
+        b->kkt_form = ASM_KKT_DENSE;
+        b->kkt_order = ASM_KKT_ORDER_WORKING_SET;
+    });
+}
+
+int asm_batch_kkt_set_form(asm_batch* b, int32_t form, int32_t order) {
+    return guarded(b, [&] {
+        if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error("asm_batch_kkt_set_form: asm_batch_eval_setup first");
+        if ((form != ASM_KKT_DENSE && form != ASM_KKT_SPARSE) || (order != ASM_KKT_ORDER_WORKING_SET && order != ASM_KKT_ORDER_STATIC))
+            throw std::invalid_argument("asm_batch_kkt_set_form: form is neither ASM_KKT_DENSE nor ASM_KKT_SPARSE, or order neither ASM_KKT_ORDER_WORKING_SET nor ASM_KKT_ORDER_STATIC");
+        if (form == ASM_KKT_SPARSE && order != ASM_KKT_ORDER_STATIC)
+            throw std::invalid_argument("asm_batch_kkt_set_form: the sparse form in the working-set order is per handle - it orders the rows on the host, uploads "
+                                        "and synchronises at every new working set, which a round of the batch cannot; use ASM_KKT_ORDER_STATIC");
+        b->kkt_form = form;
+        b->kkt_order = order;
     });
 }
 
@@ -7970,14 +8094,26 @@ void batch_hs_prepare(asm_batch* b, const char* who) {
 }
 // what the SLP-EQP step allocates or builds at its first call on a handle, for the first `count` slots and on the calling thread, before
 // their fibers start: the Hessian workspace on the batch's shared lists, the KKT buffers, the one-column work area and the trial's
-// state.  hipMalloc and the clearing fills stay out of the rounds; a slot that has them keeps them (until the next batch set-up)
+// state.  hipMalloc and the clearing fills stay out of the rounds; a slot that has them keeps them (until the next batch set-up).
+// Every slot gets the batch's form and order (asm_batch_kkt_set_form) and what that form needs, nothing of the other.  The dense fallback
+// of the sparse form is decided here, on slot 0, for all slots (they share the pattern): no sparse pattern, or one that rcm_order
+// declines.  What a slot then holds besides the shared factor (ld^2 doubles, ld = min(m, n) rounded up) and the one-column work area, with
+// ldn, Mp, ldT the padded n, m, min(m, n):
+//   dense    (Mp ldn + min(m, n) ldn + ldn ldT) doubles: J, A and its transposed copy (asm_kkt_form_info: dense_bytes)
+//   sparse   nnz doubles + (M + 2 pairs) ints: the CSR values, the position list, the row-index pairs of all rows (sparse_bytes), and on
+//            the host the order of all rows (m ints), the pairs again and the cache of the last working set (3 m ints)
 void batch_kkt_prepare(asm_batch* b, int count) {
+    bool sparse = b->kkt_form == ASM_KKT_SPARSE && b->slots[0]->sk->sp_ok;
     for (int s = 0; s < count; ++s)
         in_slot("asm_slp_run_eqp", s, [&] {
             asm_handle* h = b->slots[s];
             if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
-            kk_dense(h);
-            (void)kk_work(h, 1);
+            h->ev->kk.form = b->kkt_form;
+            h->ev->kk.order = b->kkt_order;
+            sparse = sparse && kk_sparse(h);
+            if (sparse) kk_pairs(h, ASM_KKT_ORDER_STATIC);
+            else kk_dense(h);
+            (void)kk_work(h, 1, sparse);
             eq_prepare(h);
         });
 }

@@ -393,6 +393,15 @@ __global__ __launch_bounds__(256) void k_kkts_vals(AsmBt abt, const double* __re
         vals[u] = acc;
     }
 }
+// the static row order (asm_kkt_set_order): the position list from the uploaded working rows, wpos[i] = -1 for all M LP rows and then
+// wpos[wrow[q]] = q, q < nW.  One workgroup, so that the clearing is ordered before the scatter by its barrier; the grid is (1) for
+// every working set and every scenario.  S is then built by k_schur_sparse from the row-index pairs of all rows through this list.
+__global__ __launch_bounds__(1024) void k_kkts_wpos(AsmBt abt, const int* __restrict__ wrow, int64_t nW, int64_t M, int* __restrict__ wpos) {
+    ASM_BARGS(abt, wrow, nW, M, wpos);
+    for (int64_t i = threadIdx.x; i < M; i += 1024) wpos[i] = -1;
+    __syncthreads();
+    for (int64_t q = threadIdx.x; q < nW; q += 1024) wpos[wrow[q]] = (int)q;
+}
 // T[c, q] = sum over the CSR list of row wrow[q] of val_k mask[col_k] V[c, col_k], q < nW (the k-padding of T beyond nW is not written)
 template <int LANES>
 __global__ __launch_bounds__(256) void k_kkts_mul_a(AsmBt abt, const int* __restrict__ ptr, const int* __restrict__ col, const double* __restrict__ val, const int* __restrict__ wrow, const double* __restrict__ mask, const double* __restrict__ V, int64_t ldv, int64_t nW, double* __restrict__ T, int64_t ldt) {

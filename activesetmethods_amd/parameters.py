@@ -36,8 +36,11 @@ class Parameters:
     eqp_tol_active: float = 1.e-8
     eqp: bool = True
     # not in the reference: the form of the KKT solves behind the SLP-EQP step (asm_kkt_set_form) - "dense" or "sparse" (sparse products, a
-    # banded factor of A A' in a reverse Cuthill-McKee order of the working rows).  Per handle only: the scenario batches refuse "sparse".
+    # banded factor of A A' in a reverse Cuthill-McKee order of the working rows).  kkt_order (asm_kkt_set_order), the row order of the
+    # sparse form: "working-set" orders every new working set on the host, "static" restricts one order of all rows, made once.  The
+    # scenario batches run "sparse" in the "static" order only.
     kkt_form: str = "dense"
+    kkt_order: str = "working-set"
     # `hessian_type` (above, src/parameters.jl:9-10: "approximation hessian (limited-memory), exact, or none") is read by SLP-EQP: "none" and
     # "exact" use the model's own second derivatives, "limited-memory" a limited-memory BFGS approximation of the Hessian of the Lagrangian
     # held on the device (asm_hessian_set_type) - for models without second derivatives.  lm_memory: the pairs it keeps (1 .. 32).  Per
@@ -48,12 +51,14 @@ class Parameters:
 
     def __post_init__(self):
         check_kkt_form(self.kkt_form)
+        check_kkt_order(self.kkt_order)
         check_hessian_type(self.hessian_type)
         if not 1 <= int(self.lm_memory) <= 32:
             raise ValueError("lm_memory = %r: expected 1 .. 32" % (self.lm_memory,))
 
 
 KKT_FORMS = ("dense", "sparse")
+KKT_ORDERS = ("working-set", "static")
 HESSIAN_TYPES = ("none", "exact", "limited-memory")
 
 
@@ -67,6 +72,12 @@ def check_kkt_form(form):
     if form not in KKT_FORMS:
         raise ValueError("kkt_form = %r: expected \"dense\" or \"sparse\"" % (form,))
     return form
+
+
+def check_kkt_order(order):
+    if not isinstance(order, str) or order not in KKT_ORDERS:
+        raise ValueError("kkt_order = %r: expected \"working-set\" or \"static\"" % (order,))
+    return order
 
 
 def get_parameter(params, pname):          # src/parameters.jl:31-33

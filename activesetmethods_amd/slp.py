@@ -17,7 +17,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .parameters import Parameters, check_hessian_type, check_kkt_form
+from .parameters import Parameters, check_hessian_type, check_kkt_form, check_kkt_order
 from .subproblem import HipSubOptimizer, QpData
 
 INF = np.inf
@@ -111,6 +111,9 @@ class AbstractSlpOptimizer:
                 form = check_kkt_form(getattr(self.options, "kkt_form", "dense"))
                 if form != "dense":                 # (a stand-in optimizer without the entry keeps its one form)
                     self.optimizer.set_kkt_form(form)
+                order = check_kkt_order(getattr(self.options, "kkt_order", "working-set"))
+                if order != "working-set":
+                    self.optimizer.set_kkt_order(order)
         else:
             self.optimizer.data = data                                                      # slp.jl:38-40
         if upload and not self._uploaded:
@@ -517,6 +520,7 @@ def _optimize_native(model, max_lp_solves=None):
     try:
         opt.eval_setup(fm)
         opt.set_kkt_form(check_kkt_form(getattr(par, "kkt_form", "dense")))
+        opt.set_kkt_order(check_kkt_order(getattr(par, "kkt_order", "working-set")))
         if par.algorithm == "SLP-EQP" and check_hessian_type(getattr(par, "hessian_type", "none")) == "limited-memory":
             opt.set_hessian_type("limited-memory", int(par.lm_memory))
         run = opt.slp_run(model.x, par, max_lp_solves or 0)

@@ -328,6 +328,29 @@ class HipSubOptimizer:
         self._check(self._lib.asm_kkt_form_info(self._h, C.byref(info)))
         return info
 
+    def set_kkt_order(self, order):
+        """asm_kkt_set_order: the row order of the sparse form, "working-set" (the default: a new order for every new working set, made on
+        the host) or "static" (one order of all rows, made once, restricted to the working set: no ordering, upload or wait per call).
+        Needs eval_setup, and the next eval_setup starts from "working-set" again.  No effect in the dense form."""
+        if not isinstance(order, str) or order not in _lib.KKT_ORDERS:
+            raise ValueError("kkt order %r: expected one of %s" % (order, ", ".join(repr(k) for k in _lib.KKT_ORDERS)))
+        self._check(self._lib.asm_kkt_set_order(self._h, _lib.KKT_ORDERS[order]))
+
+    def kkt_order_info(self):
+        """The asm_kkt_order_info structure: order_requested, order_used by the last KKT call (0 working-set, 1 static), all_band and
+        all_pairs of the order of all rows."""
+        info = _lib.KktOrderInfo()
+        self._check(self._lib.asm_kkt_order_info(self._h, C.byref(info)))
+        return info
+
+    def kkt_row_order(self):
+        """asm_kkt_row_order: the working rows (0-based) of the last KKT call on this handle in the order it used."""
+        nW = C.c_int64(0)
+        self._check(self._lib.asm_kkt_row_order(self._h, None, C.byref(nW)))
+        rows = np.zeros(max(int(nW.value), 1), np.int32)
+        self._check(self._lib.asm_kkt_row_order(self._h, _lib.i32ptr(rows), C.byref(nW)))
+        return rows[:int(nW.value)]
+
     def kkt_solve(self, x, lam, row_state, bound_state, ru, rw, max_iter=None, rtol=None):
         """(dx, dlam, dz, info) of asm_kkt_solve: the KKT system of the working set (row_state 0 / 1, bound_state -1 / 0 / +1) at (x, lam)
         with the right-hand sides (-ru, -rw); info is the asm_kkt_info structure (status 0 solved, 1 iteration limit, 2 reduced Hessian

@@ -531,8 +531,8 @@ int asm_kkt_step_multi(asm_handle* h, const double* x, const double* lambda, con
                        int32_t nrhs, const double* RU, const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX,
                        double* DLAM, double* DZ, asm_kkt_step_info* info);
 
-/* ---- The form of the KKT solve: dense (the default, the method text above) or sparse.  Per handle only: the scenario batches
- * (asm_batch_*) run the dense form whatever is set here.
+/* ---- The form of the KKT solve: dense (the default, the method text above) or sparse.  Per handle: the scenario batches
+ * (asm_batch_*) take their form from asm_batch_kkt_set_form, whatever is set here.
  * asm_kkt_set_form chooses the form of every later KKT entry on the handle - asm_kkt_solve(_multi), asm_solution_sensitivity(_multi),
  * asm_kkt_step(_multi), asm_eqp_trial and asm_slp_run_eqp - until the next asm_eval_setup, which starts from ASM_KKT_DENSE again.  Valid
  * after asm_eval_setup (ASM_ERR_STATE before); a form other than the two below: ASM_ERR_ARG.
@@ -563,6 +563,31 @@ struct asm_kkt_form_info {     /* a tag, not a typedef: the entry below has the 
 };
 int asm_kkt_set_form(asm_handle* h, int32_t form);
 int asm_kkt_form_info(const asm_handle* h, struct asm_kkt_form_info* out);
+
+/* ---- The row order of the sparse form.  asm_kkt_set_order has the state rules of asm_kkt_set_form (ASM_ERR_STATE before asm_eval_setup,
+ * ASM_ERR_ARG for other values, back to the default at the next asm_eval_setup) and no effect in the dense form.
+ *   ASM_KKT_ORDER_WORKING_SET (the default)  step 2 above: a reverse Cuthill-McKee order of every new working set, made on the host, its
+ *       position list and pairs uploaded, the stream waited for.
+ *   ASM_KKT_ORDER_STATIC  the reverse Cuthill-McKee order of ALL m rows, made once at the first sparse call, restricted to the working
+ *       set.  The coupling graph of W is an induced subgraph and places only move closer, so S is banded with at most the all-rows band;
+ *       the band used is the exact largest distance over the structural pairs of all rows with both rows in W (host, cached on an equal
+ *       row_state like the order above: order_reused keeps its meaning), n_pairs their number.  Per call nothing is ordered, nothing
+ *       goes up besides the one copy of the sets, and the stream is not waited for: k_kkts_wpos makes the position list on the device
+ *       from the uploaded working rows, and S is built from the row-index pairs of all rows (on the device since the first call in this
+ *       order) through that list, pairs with a row outside W skipped.  The band is not rounded.  Everything after the build of S is
+ *       shared with the other order; the answers agree to tolerance (another row order in the factor).
+ * asm_kkt_order_info: the order requested and the one the last KKT call used (ASM_KKT_ORDER_WORKING_SET for a dense call, the fallback
+ * included), the band and the structural pairs of all m rows (0 before the first sparse call).  asm_kkt_row_order: the working rows of the
+ * last KKT call in the order used (ascending in the dense form); rows may be NULL to read *nW alone.  band, n_pairs, order_reused and
+ * order_ms of asm_kkt_form_info describe the call in either order. */
+enum { ASM_KKT_ORDER_WORKING_SET = 0, ASM_KKT_ORDER_STATIC = 1 };
+struct asm_kkt_order_info {
+    int32_t order_requested, order_used;   /* ASM_KKT_ORDER_* */
+    int64_t all_band, all_pairs;
+};
+int asm_kkt_set_order(asm_handle* h, int32_t order);
+int asm_kkt_order_info(const asm_handle* h, struct asm_kkt_order_info* out);
+int asm_kkt_row_order(const asm_handle* h, int32_t* rows, int64_t* nW);
 
 /* ---- per-iteration reductions of the SLP callers on the evaluation results in HBM (need asm_eval_functions) ----------
  * out4 = { norm_violations(Inf), norm_violations(1), KT_residuals, norm_complementarity(Inf) }   (common.jl:35-98). */
@@ -826,6 +851,18 @@ int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, cons
                           const double* x0, const asm_slp_params* par, double tr_size, const asm_slp_eqp_params* eqp_par,
                           double* x, double* lambda, double* mult_x_U, double* mult_x_L, double* g, asm_slp_result* res,
                           asm_slp_tr_info* tr /* [n_scen], may be NULL */, asm_slp_eqp_info* eqp_info /* [n_scen], may be NULL */);
+/* The form and row order of the KKT solves of asm_batch_slp_run_eqp, for every slot.  Valid after asm_batch_eval_setup (ASM_ERR_STATE
+ * before), which starts from (ASM_KKT_DENSE, ASM_KKT_ORDER_WORKING_SET) again.  (ASM_KKT_DENSE, either order) and (ASM_KKT_SPARSE,
+ * ASM_KKT_ORDER_STATIC) are accepted; (ASM_KKT_SPARSE, ASM_KKT_ORDER_WORKING_SET) is ASM_ERR_ARG - that order is made on the host with
+ * uploads and a wait at every new working set, which a round cannot do - and so are values outside the enums.  The batch works on after
+ * a refusal, in the form it had.
+ *   The next asm_batch_slp_run_eqp gives every slot that will run, before any fiber starts, what the chosen form needs and nothing of
+ *   the other: a batch that only runs the sparse form has dense_bytes == 0 on every slot (asm_kkt_form_info through asm_batch_handle).
+ *   The dense fallback is decided there once for all slots: without a sparse pattern on slot 0, or with one too dense to order, every
+ *   slot runs the dense form.  Inside a round the static order neither allocates on the device, nor waits for the stream, nor copies
+ *   from pageable memory.  Bit-identity as stated above: scenario s equals asm_slp_run_eqp on a fresh handle with the same form and
+ *   order. */
+int asm_batch_kkt_set_form(asm_batch* b, int32_t form, int32_t order);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
