@@ -363,6 +363,85 @@ class HipBatch:
         self._check(self._lib.asm_batch_hessian_product(self._b, S, _lib.dptr(x), _lib.dptr(of), _lib.dptr(lam), _lib.dptr(v), _lib.dptr(out)))
         return out
 
+    def _kkt_args(self, x, lam, row_state, bound_state, max_iter, rtol):
+        """x [n_scen x n], lam [n_scen x m], row_state [n_scen x m], bound_state [n_scen x n] as contiguous arrays and the asm_kkt_params
+        argument; ValueError for shapes that do not fit the batch."""
+        from .subproblem import HipSubOptimizer
+        x = np.ascontiguousarray(x, np.float64)
+        if x.ndim != 2 or x.shape[1] != self.n or x.shape[0] < 1:
+            raise ValueError("x has shape %r, expected [n_scen x %d] with at least one scenario" % (x.shape, self.n))
+        S = x.shape[0]
+        lam = np.ascontiguousarray(lam, np.float64) if self.m else np.zeros((S, 1))
+        rs = np.ascontiguousarray(row_state, np.int32) if self.m else np.zeros((S, 1), np.int32)
+        bs = np.ascontiguousarray(bound_state, np.int32)
+        if self.m and (lam.shape != (S, self.m) or rs.shape != (S, self.m)):
+            raise ValueError("lam / row_state have shapes %r / %r, expected %r" % (lam.shape, rs.shape, (S, self.m)))
+        if bs.shape != (S, self.n):
+            raise ValueError("bound_state has shape %r, expected %r" % (bs.shape, (S, self.n)))
+        return S, x, lam, rs, bs, HipSubOptimizer._kkt_params(max_iter, rtol)
+
+    def _kkt_outputs(self, S, nrhs):
+        from . import _lib
+        return np.empty((S, nrhs, self.n)), np.empty((S, nrhs, max(self.m, 1))), np.empty((S, nrhs, self.n)), (_lib.KktInfo * (S * nrhs))()
+
+    @staticmethod
+    def _kkt_result(S, nrhs, m, DX, DLAM, DZ, infos):
+        return DX, DLAM[:, :, :m], DZ, [[infos[s * nrhs + c] for c in range(nrhs)] for s in range(S)]
+
+    def kkt_solve_multi(self, x, lam, row_state, bound_state, RU, RW, max_iter=None, rtol=None):
+        """(DX [n_scen x nrhs x n], DLAM [n_scen x nrhs x m], DZ [n_scen x nrhs x n], infos[s][c]) of asm_batch_kkt_solve: per scenario
+        HipSubOptimizer.kkt_solve_multi - bit for bit what a fresh handle with the scenario's data and the batch's KKT form gives - for
+        the rows of x, lam, row_state, bound_state and the right-hand sides RU [n_scen x nrhs x n], RW [n_scen x nrhs x m].  Each
+        scenario runs with its data (the table of the last slp_run / set_scenario_data, else the setup data)."""
+        from . import _lib
+        S, x, lam, rs, bs, par = self._kkt_args(x, lam, row_state, bound_state, max_iter, rtol)
+        RU = np.ascontiguousarray(RU, np.float64)
+        if RU.ndim != 3 or RU.shape[0] != S or RU.shape[1] < 1 or RU.shape[2] != self.n:
+            raise ValueError("RU has shape %r, expected (%d, nrhs, %d) with at least one column" % (RU.shape, S, self.n))
+        nrhs = RU.shape[1]
+        RW = np.ascontiguousarray(RW, np.float64) if self.m else np.zeros((S, nrhs, 1))
+        if self.m and RW.shape != (S, nrhs, self.m):
+            raise ValueError("RW has shape %r, expected %r" % (RW.shape, (S, nrhs, self.m)))
+        DX, DLAM, DZ, infos = self._kkt_outputs(S, nrhs)
+        self._check(self._lib.asm_batch_kkt_solve(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(RU), _lib.dptr(RW), par,
+                                                  _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return self._kkt_result(S, nrhs, self.m, DX, DLAM, DZ, infos)
+
+    def solution_sensitivity_multi(self, x, lam, row_state, bound_state, DC, max_iter=None, rtol=None):
+        """asm_batch_solution_sensitivity: per scenario HipSubOptimizer.solution_sensitivity_multi along the directions DC of the NLP block's
+        data - [nrhs x n_dpar], the same for every scenario, or [n_scen x nrhs x n_dpar]; the outputs of kkt_solve_multi."""
+        from . import _lib
+        S, x, lam, rs, bs, par = self._kkt_args(x, lam, row_state, bound_state, max_iter, rtol)
+        DC = np.ascontiguousarray(DC, np.float64)
+        if DC.ndim not in (2, 3) or DC.shape[-1] != self.n_dpar or DC.shape[-2] < 1 or (DC.ndim == 3 and DC.shape[0] != S):
+            raise ValueError("DC has shape %r, expected (nrhs, %d) or (%d, nrhs, %d) with at least one direction" % (DC.shape, self.n_dpar, S, self.n_dpar))
+        nrhs, per = DC.shape[-2], int(DC.ndim == 3)
+        if not self.n_dpar:
+            DC = np.zeros((S, nrhs, 1))
+        DX, DLAM, DZ, infos = self._kkt_outputs(S, nrhs)
+        self._check(self._lib.asm_batch_solution_sensitivity(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(DC), per, par,
+                                                             _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return self._kkt_result(S, nrhs, self.m, DX, DLAM, DZ, infos)
+
+    def bound_sensitivity(self, x, lam, row_state, bound_state, rows, delta=None, max_iter=None, rtol=None):
+        """asm_batch_bound_sensitivity: per scenario HipSubOptimizer.bound_sensitivity_multi for the rows `rows` (0-based, the same for every
+        scenario; delta None: unit moves) - column c is the answer to rw[rows[c]] = -delta[c], the zero column where the row is outside the
+        scenario's working set; the outputs of kkt_solve_multi."""
+        from . import _lib
+        S, x, lam, rs, bs, par = self._kkt_args(x, lam, row_state, bound_state, max_iter, rtol)
+        rows = np.ascontiguousarray(np.atleast_1d(rows), np.int32)
+        if rows.ndim != 1 or len(rows) < 1:
+            raise ValueError("rows has shape %r, expected (nrhs,) with at least one row" % (rows.shape,))
+        nrhs = len(rows)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.atleast_1d(delta), np.float64)
+            if delta.shape != (nrhs,):
+                raise ValueError("delta has shape %r, expected %r" % (delta.shape, (nrhs,)))
+        DX, DLAM, DZ, infos = self._kkt_outputs(S, nrhs)
+        self._check(self._lib.asm_batch_bound_sensitivity(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.i32ptr(rows),
+                                                          None if delta is None else _lib.dptr(delta), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return self._kkt_result(S, nrhs, self.m, DX, DLAM, DZ, infos)
+
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.
         Returns (p, lambda, mult_x_U, mult_x_L, p_slack, status) with a leading scenario dimension."""
@@ -403,6 +482,59 @@ def lagrangian_hessians(hb, runs, sparse=False):
     rows, cols = hb.hessian_structure()
     values = hb.eval_hessian_lagrangian(x, 1.0, lam)
     return [hessian_matrix(rows, cols, values[s], hb.n, sparse) for s in range(len(runs))]
+
+
+def working_sets(problems, runs, tol=1e-6):
+    """(row_state [S x m], bound_state [S x n], int32) of the scenarios `problems` at their `runs` (what HipBatch.slp_run or
+    solve_batch_lockstep returned): sensitivity.working_set per scenario, stacked."""
+    from .sensitivity import working_set
+    if len(problems) != len(runs) or not len(runs):
+        raise ValueError("%d problems for %d runs (at least one of each)" % (len(problems), len(runs)))
+    sets = [working_set(p, r.x, r.lam, r.mult_x_U, r.mult_x_L, tol) for p, r in zip(problems, runs)]
+    return np.stack([s[0] for s in sets]).astype(np.int32), np.stack([s[1] for s in sets]).astype(np.int32)
+
+
+def _run_points(hb, runs):
+    x = np.stack([np.asarray(r.x, float) for r in runs])
+    lam = np.stack([np.asarray(r.lam, float) for r in runs]) if hb.m else np.zeros((len(runs), 0))
+    return x, lam
+
+
+def _jacobian_stacks(DX, DLAM, infos):
+    status = np.array([[i.status for i in row] for row in infos], np.int32)
+    return np.transpose(DX, (0, 2, 1)).copy(), np.transpose(DLAM, (0, 2, 1)).copy(), status
+
+
+def solution_jacobians(hb, problems, runs, indices=None, tol=1e-6):
+    """(dx*/dc [S x n x k], dlam*/dc [S x m x k], status [S x k]) of the scenarios of the HipBatch `hb` at their runs, for the constants
+    `indices` of the NLP block's data (all of them when None): column q is the solution sensitivity along the unit direction of constant
+    indices[q] on the scenario's working set (working_sets with `tol`), every scenario with its data - one
+    asm_batch_solution_sensitivity call.  The batch counterpart of sensitivity.solution_jacobian; a column that is not solved is
+    reported in `status` (asm_kkt_info.status), not raised."""
+    nd = hb.n_dpar
+    idx = np.arange(nd) if indices is None else np.atleast_1d(np.asarray(indices, np.int64))
+    if idx.ndim != 1 or not len(idx) or np.any(idx < 0) or np.any(idx >= nd):
+        raise ValueError("indices must be a non-empty list of constants in [0, %d)" % nd)
+    rs, bs = working_sets(problems, runs, tol)
+    x, lam = _run_points(hb, runs)
+    DC = np.zeros((len(idx), nd))
+    DC[np.arange(len(idx)), idx] = 1.0
+    DX, DLAM, _, infos = hb.solution_sensitivity_multi(x, lam, rs, bs, DC)
+    return _jacobian_stacks(DX, DLAM, infos)
+
+
+def bound_jacobians(hb, problems, runs, rows, tol=1e-6):
+    """(dx*/d(bound) [S x n x k], dlam*/d(bound) [S x m x k], status [S x k]) of the scenarios of `hb` at their runs: column q answers a
+    unit move of the active bound of row rows[q] (0-based, the same rows for every scenario) - the zero column in a scenario whose
+    working set does not hold the row - from one asm_batch_bound_sensitivity call.  The batch counterpart of sensitivity.bound_jacobian;
+    it reports the column statuses and does not raise on one that is not 0."""
+    rows = np.atleast_1d(np.asarray(rows, np.int64))
+    if rows.ndim != 1 or not len(rows) or np.any(rows < 0) or np.any(rows >= hb.m):
+        raise ValueError("rows must be a non-empty list of rows in [0, %d)" % hb.m)
+    rs, bs = working_sets(problems, runs, tol)
+    x, lam = _run_points(hb, runs)
+    DX, DLAM, _, infos = hb.bound_sensitivity(x, lam, rs, bs, rows)
+    return _jacobian_stacks(DX, DLAM, infos)
 
 
 def solve_batch_lockstep(problems, parameters, n_slots, device=0, rank=0, world=1, reduce_device=None, batch=None):

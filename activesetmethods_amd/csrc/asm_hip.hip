@@ -247,6 +247,7 @@ struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` col
     int64_t cap = 0;
     double *vec = nullptr, *row = nullptr, *dlf = nullptr;      // 14 blocks cap x ldn over the variables, 5 cap x ldT over the working rows, cap x Mp over all rows
     double* rad = nullptr;                                      // cap trust-region radii (asm_kkt_step)
+    double* bnd = nullptr;                                      // cap > 1: [delta (cap doubles) | rows (cap ints)] of a chunk of bound sensitivities (k_kktm_bound_rhs)
     double* stage = nullptr;                                    // pinned: [ru | rw | directions] of a chunk, then its results
     double *Lt = nullptr, *AfT = nullptr;                       // cap > 1, the block products' own operands: the transposed factor, the unmasked transposed working rows (dense form only)
 };
@@ -5168,8 +5169,8 @@ void kk_pairs(asm_handle* h, int order) {
         HIPCHK(asmb::sync(h->stream));
     }
 }
-// the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it; the unmasked transposed working rows of the dense
-// block products at the first dense call
+// the work area of capacity cap (1 or KKM_CW), made at the first call that asks for it (for a slot of a scenario batch before its fiber
+// starts: batch_kkt_prepare); the unmasked transposed working rows of the dense block products at the first dense call
 KktWork* kk_work(asm_handle* h, int64_t cap, bool sparse = false) {
     kk_prepare(h);
     KktBufs& K = h->ev->kk;
@@ -5189,6 +5190,7 @@ KktWork* kk_work(asm_handle* h, int64_t cap, bool sparse = false) {
     M.zeroed(W.dlf, cap * Mp, s);
     M.zeroed(W.rad, cap, s);
     if (cap > 1) M.zeroed(W.Lt, K.fac.ld * K.fac.ld, s);
+    if (cap > 1) M.zeroed(W.bnd, cap + (cap + 1) / 2, s);
     M.alloc(W.stage, cap * (3 * ldn + K.ldT + Mp + KKM_SCAL + nd) + 64, BufPool::PINNED);
     HIPCHK(asmb::sync(s));
     W.cap = cap;
@@ -5582,18 +5584,26 @@ struct KktSparse final : KktOps {
 
 // Steps 3 to 6 for nrhs columns in chunks of the work area's capacity.  sens false: the rows of RU, RW are the right-hand sides;
 // otherwise the rows of DC are directions of the data and the cross-derivative sweep makes each column's right-hand sides on the
-// device (lambda: its multipliers).  The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product and substitution is ops'.
+// device (lambda: its multipliers); bd.rows != nullptr: bound sensitivities, the right-hand sides made by k_kktm_bound_rhs (KktBound).
+// The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product and substitution is ops'.
 // rounds, last_active: the lockstep rounds of the call and the last active-column word read.
 // The trust-region step (asm_kkt_step, asm_kkt_step_multi): tr.radius != nullptr holds a radius per column, and the answers go to tr.info
 // instead of info.  The same launches with the trust-region forms of k_kktm_cg_curv, k_kktm_cg_dir and k_kktm_finish, and k_kktm_normal
 // once per chunk after the normal step.
+// Bound sensitivities (asm_bound_sensitivity_multi): rows != nullptr holds a row per column, and column c is ru = 0, rw[rows[c]] = -delta[c]
+// (delta == nullptr: -1.0).  RU and RW are not read: k_kktm_bound_rhs makes a chunk's right-hand sides on the device from its rows and
+// deltas, 12 bytes per column in one upload - no n- or m-long vector is staged or uploaded.
+struct KktBound {
+    const int32_t* rows = nullptr;       // nrhs row indices in [0, m)
+    const double* delta = nullptr;       // nrhs moves, or nullptr
+};
 struct KktTrust {
     const double* radius = nullptr;      // nrhs radii, each > 0 (+inf: no region)
     double share = 0.8;                  // the share of the radius the normal step may use
     asm_kkt_step_info* info = nullptr;
 };
 void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, const double* RU, const double* RW, const double* DC, bool sens, const double* lambda, double* DX,
-                 double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active, const KktTrust& tr = KktTrust()) {
+                 double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active, const KktTrust& tr = KktTrust(), const KktBound& bd = KktBound()) {
     const KktBufs& K = h->ev->kk;
     KktWork& w = ops.w;
     const hipStream_t s = h->stream;
@@ -5651,7 +5661,16 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             axpby(1.0, v, -1.0, tt, sc, v);
         };
         // 3. the right-hand sides of the chunk
-        if (!sens) {
+        if (bd.rows) {
+            // [delta | rows] of the chunk's columns in the (unused) staging rows of ru, one upload, one launch
+            int* hr = reinterpret_cast<int*>(st + cols);
+            int* dr = reinterpret_cast<int*>(w.bnd + cols);
+            if (bd.delta) std::memcpy(st, bd.delta + c0, cols * sizeof(double));
+            for (int c = 0; c < cols; ++c) hr[c] = bd.rows[c0 + c];
+            HIPCHK(asmb::copy_async(w.bnd, st, cols * (sizeof(double) + sizeof(int)), hipMemcpyHostToDevice, s));
+            asmb::launch(k_kktm_bound_rhs, dim3(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols), dim3(256), s, (const int*)dr, bd.delta ? (const double*)w.bnd : (const double*)nullptr,
+                         f.wrow, nW, b_ru, ldn, rww, ldT);
+        } else if (!sens) {
             for (int c = 0; c < cols; ++c) {
                 const double *u = RU + (c0 + c) * n, *rw = RW ? RW + (c0 + c) * m : nullptr;
                 double *du = st + (int64_t)c * ldn, *dw = st + cap * ldn + (int64_t)c * ldT;
@@ -5813,26 +5832,33 @@ static void do_solution_sensitivity(asm_handle* h, const double* x, const double
     do_data_cross(h, x, lambda, dc, u.data(), w.data());
     do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info, true);
 }
-// asm_kkt_solve_multi (sens false: the rows of RU, RW are the right-hand sides) and asm_solution_sensitivity_multi (the rows of DC are
-// directions of the data)
+// asm_kkt_solve_multi (sens false: the rows of RU, RW are the right-hand sides), asm_solution_sensitivity_multi (the rows of DC are
+// directions of the data) and asm_bound_sensitivity_multi (bd.rows: a row per column, RU and RW not read - a derivative entry like the
+// second, exact whatever the handle's type)
 static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                const double* RU, const double* RW, const double* DC, bool sens, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
-                               asm_kkt_info* info) {
+                               asm_kkt_info* info, const KktBound& bd = KktBound()) {
     const std::string me(who);
+    const bool bound = bd.rows != nullptr;
     if (sens) cx_check(h, who);
-    if (sens) hs_check(h, who);
-    const bool lm = !sens && kkt_hess_lm(h, who);
+    if (sens || bound) hs_check(h, who);
+    const bool lm = !sens && !bound && kkt_hess_lm(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
     if (!x || !bound_state || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
-    if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->sk->m > 0 && !RW))) throw std::invalid_argument(me + ": null pointer");
+    if (bound) {
+        for (int32_t c = 0; c < nrhs; ++c)
+            if (bd.rows[c] < 0 || bd.rows[c] >= h->sk->m) throw std::invalid_argument(me + ": a row index outside [0, m)");
+    } else if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->sk->m > 0 && !RW))) {
+        throw std::invalid_argument(me + ": null pointer");
+    }
     Dev dev(h);
     const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par, lm);
     if (f.sparse) {
         KktSparse ops(h, dev, f, *kk_work(h, KKM_CW, true));
-        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
+        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active, KktTrust(), bd);
     } else {
         KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
-        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active);
+        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active, KktTrust(), bd);
     }
 }
 // asm_kkt_step (one column through KktOneColumn) and asm_kkt_step_multi (KktBlock): the checks of asm_kkt_solve(_multi), then
@@ -5933,6 +5959,14 @@ int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double*
                                    const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
     return guarded(h, [&] {
         do_kkt_solve_multi(h, "asm_solution_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, true, par, DX, DLAM, DZ, info);
+    });
+}
+
+int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const int32_t* rows,
+                                const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(h, [&] {
+        if (!rows) throw std::invalid_argument("asm_bound_sensitivity_multi: null pointer");
+        do_kkt_solve_multi(h, "asm_bound_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, nullptr, false, par, DX, DLAM, DZ, info, KktBound{rows, delta});
     });
 }
 
@@ -8102,10 +8136,14 @@ void batch_hs_prepare(asm_batch* b, const char* who) {
 //   dense    (Mp ldn + min(m, n) ldn + ldn ldT) doubles: J, A and its transposed copy (asm_kkt_form_info: dense_bytes)
 //   sparse   nnz doubles + (M + 2 pairs) ints: the CSR values, the position list, the row-index pairs of all rows (sparse_bytes), and on
 //            the host the order of all rows (m ints), the pairs again and the cache of the last working set (3 m ints)
-void batch_kkt_prepare(asm_batch* b, int count) {
+// The multi entries (asm_batch_kkt_solve and the two sensitivity entries, cap = KKM_CW) come here too: the work area of 64 columns
+// - 14 ldn + 5 ldT + Mp doubles per column, the transposed factor (ld^2) and, dense form, the unmasked transposed working rows (ldn ldT) -
+// instead of the one-column area and the trial's state, and with `cross` what the cross-derivative sweep of the slot's kind needs
+// (cx_prepare downloads with blocking copies), under the conditions kkt_columns reads it.
+void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_eqp", int64_t cap = 1, bool cross = false) {
     bool sparse = b->kkt_form == ASM_KKT_SPARSE && b->slots[0]->sk->sp_ok;
     for (int s = 0; s < count; ++s)
-        in_slot("asm_slp_run_eqp", s, [&] {
+        in_slot(step, s, [&] {
             asm_handle* h = b->slots[s];
             if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
             h->ev->kk.form = b->kkt_form;
@@ -8113,9 +8151,53 @@ void batch_kkt_prepare(asm_batch* b, int count) {
             sparse = sparse && kk_sparse(h);
             if (sparse) kk_pairs(h, ASM_KKT_ORDER_STATIC);
             else kk_dense(h);
-            (void)kk_work(h, 1, sparse);
-            eq_prepare(h);
+            (void)kk_work(h, cap, sparse);
+            if (cap == 1) eq_prepare(h);
+            const EvalState& e = *h->ev;
+            if (cross && (nlp_block_derivs(e.nlp_kind) ? e.n_dpar > 0 : e.d_cocc != nullptr)) cx_prepare(h, KKM_CW);
         });
+}
+// The three multi entries on n_scen scenarios, the slots taking them in index order: per scenario do_kkt_solve_multi under the per-handle
+// entry's name `step`, on the scenario's rows of every array and with its data.  Exactly one of (RU, RW), DC (sens; dc_stride: doubles
+// from one scenario's directions to the next, 0 when they are shared) and bd.rows says what the columns are.  Everything that can be
+// refused without a launch is refused here, on the calling thread, and what a slot allocates or builds at its first call is made before
+// the fibers start (batch_kkt_prepare).
+void batch_kkt_multi(asm_batch* b, const char* who, const char* step, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                     const int32_t* bound_state, int32_t nrhs, const double* RU, const double* RW, const double* DC, int64_t dc_stride, bool sens, const KktBound* bound,
+                     const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    const std::string me(who);
+    // a model without second derivatives ends here, as in asm_batch_hessian_*, one without cross derivatives as in the per-handle entry
+    batch_hs_prepare(b, who);
+    if (sens) cx_check(b->slots[0], who);
+    const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = (int64_t)b->dpar0.size();
+    if (n_scen < 1 || nrhs < 1) throw std::invalid_argument(me + ": n_scen < 1 or nrhs < 1");
+    if (!x || !bound_state || !DX || !info || (m > 0 && (!lambda || !row_state || !DLAM)) || (bound && !bound->rows)) throw std::invalid_argument(me + ": null pointer");
+    const KktBound bd = bound ? *bound : KktBound();
+    if (bd.rows) {
+        for (int32_t c = 0; c < nrhs; ++c)
+            if (bd.rows[c] < 0 || bd.rows[c] >= m) throw std::invalid_argument(me + ": a row index outside [0, m)");
+    } else if (sens ? (nd > 0 && !DC) : (!RU || (m > 0 && !RW))) {
+        throw std::invalid_argument(me + ": null pointer");
+    }
+    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
+    check_scen(b, n_scen, who);
+    HIPCHK(hipSetDevice(b->device));
+    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
+    batch_kkt_prepare(b, count, step, KKM_CW, sens);
+    std::atomic<int64_t> next{0};
+    run_fibers(b, count, step, [&](int s) {
+        asm_handle* h = b->slots[s];
+        for (;;) {
+            const int64_t sc = next.fetch_add(1);
+            if (sc >= n_scen) break;
+            batch_scenario_data(b, h, sc);
+            asmb::next_cycle();
+            const int64_t o = sc * nrhs;
+            do_kkt_solve_multi(h, step, x + sc * n, m > 0 ? lambda + sc * m : nullptr, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n, nrhs, RU ? RU + o * n : nullptr,
+                               RW ? RW + o * m : nullptr, DC ? DC + sc * dc_stride : nullptr, sens, par, DX + o * n, m > 0 ? DLAM + o * m : nullptr, DZ ? DZ + o * n : nullptr,
+                               info + o, bd);
+        }
+    });
 }
 // asm_eval_hessian_lagrangian (v == nullptr: values [n_scen x nnz] into out) or asm_eval_hessian_product (out [n_scen x n]) of n_scen
 // scenarios, each with its data, the slots taking them in index order.  A slot attaches its workspace to the shared lists when it takes
@@ -8188,6 +8270,34 @@ int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, cons
             slp_run_eqp(h, par, tr_size, eqp_par, x0 + sc * n, x ? x + sc * n : nullptr, lambda ? lambda + sc * m : nullptr, mult_x_U ? mult_x_U + sc * n : nullptr,
                         mult_x_L ? mult_x_L + sc * n : nullptr, g ? g + sc * m : nullptr, res + sc, tr ? tr + sc : nullptr, eqp_info ? eqp_info + sc : nullptr);
         });
+    });
+}
+
+// asm_kkt_solve_multi, asm_solution_sensitivity_multi and asm_bound_sensitivity_multi of n_scen scenarios (include/asm_hip.h, "Scenario
+// batches: KKT solves and sensitivities")
+int asm_batch_kkt_solve(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                        const double* RU, const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(b, [&] {
+        batch_kkt_multi(b, "asm_batch_kkt_solve", "asm_kkt_solve_multi", n_scen, x, lambda, row_state, bound_state, nrhs, RU, RW, nullptr, 0, false, nullptr, par, DX, DLAM, DZ, info);
+    });
+}
+
+int asm_batch_solution_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                   const double* DC, int32_t dc_per_scenario, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(b, [&] {
+        if (dc_per_scenario != 0 && dc_per_scenario != 1) throw std::invalid_argument("asm_batch_solution_sensitivity: dc_per_scenario is neither 0 nor 1");
+        const int64_t stride = dc_per_scenario ? (int64_t)std::max<int32_t>(nrhs, 0) * (int64_t)b->dpar0.size() : 0;
+        batch_kkt_multi(b, "asm_batch_solution_sensitivity", "asm_solution_sensitivity_multi", n_scen, x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, stride, true,
+                        nullptr, par, DX, DLAM, DZ, info);
+    });
+}
+
+int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                const int32_t* rows, const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(b, [&] {
+        const KktBound bd{rows, delta};
+        batch_kkt_multi(b, "asm_batch_bound_sensitivity", "asm_bound_sensitivity_multi", n_scen, x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, nullptr, 0, false,
+                        &bd, par, DX, DLAM, DZ, info);
     });
 }
 

@@ -157,6 +157,16 @@ __global__ __launch_bounds__(256) void k_kktm_cross_rhs_cols(AsmBt abt, const do
         rww[c * ldT + j] = i >= n_fn ? cx[n + i - n_fn] : 0.0;
     }
 }
+// The right-hand sides of a chunk of bound sensitivities (asm_bound_sensitivity_multi): column c = blockIdx.y is ru = 0 and
+// rw[rows[c]] = -delta[c] (delta == nullptr: -1.0), nothing else.  Every thread clears its entry of the column's ru (pitch ldn, all of
+// it) and rww (pitch ldT, all of it); the thread whose place in the working-row list wrow (the order the form solves in) holds rows[c]
+// stores -delta[c] instead - a row outside the working set has no such place and the column stays zero.  One writer per entry.
+__global__ __launch_bounds__(256) void k_kktm_bound_rhs(AsmBt abt, const int* __restrict__ rows, const double* __restrict__ delta, const int* __restrict__ wrow, int64_t nW, double* __restrict__ ru, int64_t ldn, double* __restrict__ rww, int64_t ldT) {
+    ASM_BARGS(abt, rows, delta, wrow, nW, ru, ldn, rww, ldT);
+    const int64_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j < ldn) ru[c * ldn + j] = 0.0;
+    if (j < ldT) rww[c * ldT + j] = (j < nW && wrow[j] == rows[c]) ? -(delta ? delta[c] : 1.0) : 0.0;
+}
 // p[c] = -g[c] + beta_c p[c] for the active columns
 __global__ __launch_bounds__(256) void k_kktm_cg_p(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ g, double* __restrict__ p, int64_t len, int64_t ldv) {
     ASM_BARGS(abt, scal, g, p, len, ldv);

@@ -17,7 +17,10 @@ block kernels with derivatives).  A constraint bound that moves by d(bound_i) en
     kkt_pcg_multi        kkt_pcg column by column: what the lockstep iteration of asm_kkt_solve_multi computes
     solution_jacobian    dx*/dc and dlam*/dc for a list of constants, as matrices (asm_solution_sensitivity_multi, unit directions)
     bound_jacobian       dx*/d(bound) and dlam*/d(bound) for a list of working rows (asm_kkt_solve_multi)
+    bound_rhs            the right-hand sides of bound sensitivities as matrices: what asm_bound_sensitivity_multi makes on the device
     predict              the first-order prediction x + step * dx
+
+For the scenarios of a HipBatch: batch.working_sets, batch.solution_jacobians, batch.bound_jacobians.
 """
 import numpy as np
 
@@ -276,6 +279,21 @@ def bound_jacobian(opt, fm, x, lam, row_state, bound_state, rows, max_iter=None,
     RW[np.arange(len(rows)), rows] = -1.0
     DX, DLAM, _, infos = opt.kkt_solve_multi(x, lam, row_state, bound_state, np.zeros((len(rows), fm.n)), RW, max_iter, rtol)
     return _jacobian_columns(DX, DLAM, infos)
+
+
+def bound_rhs(m, n, rows, delta=None):
+    """(RU [k x n], RW [k x m]) of the bound sensitivities of rows `rows` (0-based, duplicates allowed): RU = 0 and RW[c, rows[c]] =
+    -delta[c] (delta None: -1), nothing else - what k_kktm_bound_rhs writes on the device for asm_bound_sensitivity_multi, restricted there
+    to the working rows (a row outside the working set leaves its column zero)."""
+    rows = np.atleast_1d(np.asarray(rows, np.int64))
+    if rows.ndim != 1 or np.any(rows < 0) or np.any(rows >= m):
+        raise ValueError("rows must be a list of rows in [0, %d)" % m)
+    d = np.ones(len(rows)) if delta is None else np.atleast_1d(np.asarray(delta, float))
+    if d.shape != rows.shape:
+        raise ValueError("delta has shape %r, expected %r" % (d.shape, rows.shape))
+    RU, RW = np.zeros((len(rows), n)), np.zeros((len(rows), m))
+    RW[np.arange(len(rows)), rows] = -d
+    return RU, RW
 
 
 def solution_sensitivity(model_or_opt, fm, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):

@@ -411,6 +411,24 @@ class HipSubOptimizer:
                                                              par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return DX, DLAM[:, :self.m], DZ, list(infos)
 
+    def bound_sensitivity_multi(self, x, lam, row_state, bound_state, rows, delta=None, max_iter=None, rtol=None):
+        """(DX, DLAM, DZ, infos) of asm_bound_sensitivity_multi: column c is kkt_solve_multi with ru = 0 and rw[rows[c]] = -delta[c]
+        (delta None: -1), bit for bit, with the right-hand sides made on the device (sensitivity.bound_rhs states them).  rows: 0-based
+        rows, duplicates allowed; a row outside the working set gives the zero column."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_params(max_iter, rtol)
+        rows = np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
+        if rows.ndim != 1 or len(rows) < 1:
+            raise ValueError("rows has shape %r, expected (nrhs,) with at least one row" % (rows.shape,))
+        nrhs = len(rows)
+        if delta is not None:
+            delta = self._vec(delta, nrhs, "delta")
+        rs, bs = self._states(row_state, bound_state)
+        DX, DLAM, DZ, infos = self._multi_outputs(nrhs)
+        self._check(self._lib.asm_bound_sensitivity_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.i32ptr(rows),
+                                                          None if delta is None else _lib.dptr(delta), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return DX, DLAM[:, :self.m], DZ, list(infos)
+
     @staticmethod
     def _kkt_step_params(max_iter, rtol, normal_share):
         if max_iter is None and rtol is None and normal_share is None:

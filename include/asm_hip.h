@@ -443,7 +443,7 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  * directions of the data.  All matrices are row-major with one right-hand side per row: RU, DX, DZ are nrhs x n, RW, DLAM nrhs x m, DC
  * nrhs x n_dpar, info has nrhs entries, and row c of DX / DLAM / DZ / info answers row c of RU / RW (of DC).  DZ may be NULL.
  * Validity, argument errors and defaults are asm_kkt_solve's (asm_solution_sensitivity's); nrhs < 1: ASM_ERR_ARG.  par, and the default
- * max_iter = 2 (|F| - |W|) + 20 and rtol = 1e-12, hold for every column.  Per-handle calls: no batch entry runs the block forms (asm_batch_slp_run_eqp runs asm_kkt_step's single column).
+ * max_iter = 2 (|F| - |W|) + 20 and rtol = 1e-12, hold for every column.  For scenario batches: "Scenario batches: KKT solves and sensitivities" below.
  * Per column the mathematics is the method above, step by step.  Steps 1 and 2 - the Hessian values, the Jacobian, the gather, its
  * transposed copy, the rank-K build, the factorisation and the dropped-pivot count - run once per call.  Steps 3 to 6 run on blocks of
  * ASM_KKT_CHUNK columns; the factor and everything of steps 1 and 2 stay across the chunks, so memory is bounded whatever nrhs.
@@ -475,7 +475,13 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  * When to use it: a lockstep round launches block products whose time does not shrink with the number of columns, live or frozen - on
  * the case300-sized ACOPF a round costs about seven single-column iterations.  Below about 8 columns a loop of asm_kkt_solve /
  * asm_solution_sensitivity calls is faster; from there on the multi entries win, 4.5 times at 32 columns and 12.7 times at 64.
- * Bound sensitivities for a set of working rows: RU = 0 and RW[c, i_c] = -1 for the row i_c of column c (the recipe above). */
+ * Bound sensitivities for a set of working rows: RU = 0 and RW[c, i_c] = -1 for the row i_c of column c (the recipe above).
+ * asm_bound_sensitivity_multi is that recipe without the matrices: column c is asm_kkt_solve_multi with ru = 0 and rw[rows[c]] = -delta[c]
+ * (delta == NULL: -1.0), bit for bit - DX, DLAM, DZ and info.  rows: nrhs 0-based row indices, duplicates allowed; an index outside [0, m),
+ * or rows == NULL, is ASM_ERR_ARG.  A row outside the working set gives the zero column: status 0, no iteration, exact zeros.  A chunk's
+ * right-hand sides are made on the device (k_kktm_bound_rhs: every entry cleared, and the thread whose place in the working-row list
+ * holds rows[c] stores -delta[c]) from one upload of 12 bytes per column - nothing of length n or m is staged.  A derivative entry like
+ * asm_solution_sensitivity_multi: the exact Hessian whatever asm_hessian_set_type chose, and that entry's refusals. */
 #define ASM_KKT_CHUNK 64
 int asm_kkt_solve_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                         int32_t nrhs, const double* RU, const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
@@ -483,6 +489,9 @@ int asm_kkt_solve_multi(asm_handle* h, const double* x, const double* lambda, co
 int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state,
                                    const int32_t* bound_state, int32_t nrhs, const double* DC, const asm_kkt_params* par, double* DX,
                                    double* DLAM, double* DZ, asm_kkt_info* info);
+int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                                int32_t nrhs, const int32_t* rows, const double* delta /* [nrhs], or NULL: 1.0 */, const asm_kkt_params* par,
+                                double* DX, double* DLAM, double* DZ, asm_kkt_info* info);
 
 /* ---- Trust-region step on the working set: Byrd-Omojokun with Steihaug-Toint truncation.
  * asm_kkt_step is asm_kkt_solve with an l2 radius: it minimises the model ru'dx + 1/2 dx'H dx over A dx_F = -theta rw_W, dx_B = 0,
@@ -863,6 +872,38 @@ int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, cons
  *   from pageable memory.  Bit-identity as stated above: scenario s equals asm_slp_run_eqp on a fresh handle with the same form and
  *   order. */
 int asm_batch_kkt_set_form(asm_batch* b, int32_t form, int32_t order);
+/* ---- Scenario batches: KKT solves and sensitivities.
+ * asm_kkt_solve_multi, asm_solution_sensitivity_multi and asm_bound_sensitivity_multi with a leading scenario dimension on every array
+ * but rows and delta (and DC with dc_per_scenario == 0), which all scenarios share: x, bound_state are n_scen x n, lambda, row_state
+ * n_scen x m, RU, DX, DZ n_scen x nrhs x n, RW, DLAM n_scen x nrhs x m, info n_scen x nrhs, DC nrhs x n_dpar or n_scen x nrhs x n_dpar.
+ * n_scen may exceed the slot count: the slots take the scenarios in index order, each evaluated with its row of the scenario data table
+ * (asm_batch_set_scenario_data) or, without a table, with the data of asm_batch_eval_setup.
+ *   Per scenario the entry IS the per-handle entry, for every nrhs: scenario s is bit-identical to that entry on a fresh handle that has
+ *   the scenario's data and the batch's form and order (asm_batch_kkt_set_form) - whatever the slot, the group, the slot count or the
+ *   scenarios beside it.  The slots' launches merge as in every batch entry, and the lockstep rounds of the columns become rounds of the
+ *   batch: the host reads one word per slot and round.
+ *   Before any fiber starts every slot that will run gets the work area of ASM_KKT_CHUNK columns in the batch's form - per column
+ *   14 ldn + 5 ldT + Mp doubles, and per slot the transposed factor (ld^2 doubles) and, dense form, the unmasked transposed working rows
+ *   (ldn ldT doubles) - the Hessian workspace on the batch's shared lists and, for asm_batch_solution_sensitivity, the cross-derivative
+ *   workspace: no allocation, no clearing fill and no blocking copy inside a round.  The dense fallback of the sparse form is decided on
+ *   slot 0 for all slots.  The Hessian is the exact one.
+ *   Errors: ASM_ERR_STATE before asm_batch_setup / asm_batch_eval_setup; a model without second derivatives is refused as by
+ *   asm_batch_hessian_*, one without cross derivatives (asm_batch_solution_sensitivity) as by asm_solution_sensitivity_multi, both before
+ *   any fiber starts; n_scen < 1, nrhs < 1, a null required pointer, a row index outside [0, m), dc_per_scenario outside {0, 1}:
+ *   ASM_ERR_ARG; n_scen unequal to the height of a scenario table: as every batch entry.  A scenario's own refusal (more working rows
+ *   than free variables, a state outside its values) is that slot's error with the per-handle code, and the batch stays usable.  A column
+ *   status - iteration limit, indefinite reduced Hessian, dropped pivots - is reported in info and is not an error. */
+int asm_batch_kkt_solve(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                        const int32_t* bound_state, int32_t nrhs, const double* RU, const double* RW, const asm_kkt_params* par, double* DX,
+                        double* DLAM, double* DZ /* may be NULL */, asm_kkt_info* info);
+int asm_batch_solution_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                                   const int32_t* bound_state, int32_t nrhs, const double* DC,
+                                   int32_t dc_per_scenario /* 0: [nrhs x n_dpar] for all; 1: [n_scen x nrhs x n_dpar] */,
+                                   const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info);
+int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                                const int32_t* bound_state, int32_t nrhs, const int32_t* rows /* [nrhs], shared */,
+                                const double* delta /* [nrhs] or NULL: 1.0, shared */, const asm_kkt_params* par, double* DX, double* DLAM,
+                                double* DZ, asm_kkt_info* info);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
