@@ -365,8 +365,9 @@ def _ohm_hessian(mdl):
 
 def _ohm_data_twins(mdl):
     """Derivatives of the Ohm's-law block with respect to its data - the 8 coefficient arrays of the kernel's dpar - in closed form: the
-    host twins (data_gradient, data_cross) of k_nlp_ohm_data_grad and k_nlp_ohm_cross + k_nlp_block_cross_gather (include/asm_hip.h,
-    "Data derivatives of the block kernels"), with the signatures of nlexpr.ExprBlock's.  The block is linear in its data and has no
+    host twins (data_gradient, data_cross, data_cross_t) of k_nlp_ohm_data_grad, k_nlp_ohm_cross + k_nlp_block_cross_gather and
+    k_nlp_ohm_cross_t (include/asm_hip.h, "Data derivatives of the block kernels", "Transposed cross derivatives"), with the signatures of
+    nlexpr.ExprBlock's.  The block is linear in its data and has no
     objective (`scale` is accepted and unused), so neither twin reads the coefficients: the gradient is lam_r dF_r/dc, the cross
     derivative along dc the flows and their derivatives with dc in the coefficients' place.  Every written operation is one rounding,
     left to right, as in the kernels; u sums each variable's occurrences from 0.0 by branch ascending and, inside a branch, in the slot
@@ -414,7 +415,23 @@ def _ohm_data_twins(mdl):
             s = cnt > i
             u[s] = u[s] + occ[order[ptr[:-1][s] + i]]
         return u, np.concatenate([-pfr, -qfr, -pto, -qto])
-    return data_gradient, data_cross
+
+    def data_cross_t(x, lam, vx, vl, scale=1.0):
+        """The transposed cross derivative (k_nlp_ohm_cross_t): out[c] = d/dc [D_vx (-lam' g) + vl' g] with g_r = x_flow - F_r, F_r linear
+        in its coefficients - data_gradient's pattern on (lam, the basis values' derivatives along vx) minus that on (vl, the values)."""
+        vx, vl = np.asarray(vx, float), np.asarray(vl, float)
+        vf, vt, cs, sn, vv, (l0, l1, l2, l3) = point(x, lam)
+        v0, v1, v2, v3 = vl[:nl], vl[nl:2 * nl], vl[2 * nl:3 * nl], vl[3 * nl:4 * nl]
+        dvf, dvt, dd = vx[ivf], vx[ivt], vx[iaf] - vx[iat]
+        vf2, vt2, vvc, vvs = vf * vf, vt * vt, vv * cs, vv * sn
+        tvv = dvf * vt + vf * dvt
+        tvf2, tvt2 = 2.0 * (vf * dvf), 2.0 * (vt * dvt)
+        tvvc, tvvs = tvv * cs - vvs * dd, tvv * sn + vvc * dd
+        return np.concatenate([l0 * tvf2 - v0 * vf2, l1 * tvf2 - v1 * vf2, l2 * tvt2 - v2 * vt2, l3 * tvt2 - v3 * vt2,
+                               (l0 * tvvc + l1 * tvvs) - (v0 * vvc + v1 * vvs), (l0 * tvvs - l1 * tvvc) - (v0 * vvs - v1 * vvc),
+                               (l2 * tvvc - l3 * tvvs) - (v2 * vvc - v3 * vvs), (-(l2 * tvvs) - l3 * tvvc) - (-(v2 * vvs) - v3 * vvc)])
+    data_cross.transposed = data_cross_t                    # (how a block carries it: NlpBlock.data_cross_t)
+    return data_gradient, data_cross, data_cross_t
 
 
 def function_model(case, nlp="acopf_ohm", branch_params=False, hessian=False):
@@ -506,7 +523,7 @@ def function_model(case, nlp="acopf_ohm", branch_params=False, hessian=False):
     dpar = np.concatenate([mdl.k_ff_p, mdl.k_ff_q, mdl.k_tt_p, mdl.k_tt_q, mdl.a_f, mdl.b_f, mdl.a_t, mdl.b_t]).astype(np.float64)
     if hessian:
         hr, hc, eval_hess = _ohm_hessian(mdl)
-        data_gradient, data_cross = _ohm_data_twins(mdl)
+        data_gradient, data_cross, _ = _ohm_data_twins(mdl)
         fm.nlp = NlpBlock(np.zeros(4 * nl), np.zeros(4 * nl), np.concatenate(rows), np.concatenate(cols), eval_g, eval_jac_g,
                           device=("acopf_ohm_hess", ipar, dpar), hess_rows=hr, hess_cols=hc, eval_hess=eval_hess,
                           data_gradient=data_gradient, data_cross=data_cross)

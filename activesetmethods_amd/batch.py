@@ -442,6 +442,27 @@ class HipBatch:
                                                           None if delta is None else _lib.dptr(delta), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return self._kkt_result(S, nrhs, self.m, DX, DLAM, DZ, infos)
 
+    def solution_adjoint(self, x, lam, row_state, bound_state, GX, GL, max_iter=None, rtol=None):
+        """(OUT [n_scen x nrhs x n_dpar], DBOUND [n_scen x nrhs x m], AX [n_scen x nrhs x n], AL [n_scen x nrhs x m], infos[s][c]) of
+        asm_batch_solution_adjoint: per scenario HipSubOptimizer.solution_adjoint_multi - bit for bit what a fresh handle with the
+        scenario's data and the batch's KKT form gives - for the nrhs functions whose gradients are GX [n_scen x nrhs x n] and
+        GL [n_scen x nrhs x m]: the gradient of each with respect to every constant of the block's data and every row bound."""
+        from . import _lib
+        S, x, lam, rs, bs, par = self._kkt_args(x, lam, row_state, bound_state, max_iter, rtol)
+        GX = np.ascontiguousarray(GX, np.float64)
+        if GX.ndim != 3 or GX.shape[0] != S or GX.shape[1] < 1 or GX.shape[2] != self.n:
+            raise ValueError("GX has shape %r, expected (%d, nrhs, %d) with at least one function" % (GX.shape, S, self.n))
+        nrhs = GX.shape[1]
+        GL = np.ascontiguousarray(GL, np.float64) if self.m else np.zeros((S, nrhs, 1))
+        if self.m and GL.shape != (S, nrhs, self.m):
+            raise ValueError("GL has shape %r, expected %r" % (GL.shape, (S, nrhs, self.m)))
+        nd = self.n_dpar
+        OUT, DBOUND, AL = np.empty((S, nrhs, max(nd, 1))), np.empty((S, nrhs, max(self.m, 1))), np.empty((S, nrhs, max(self.m, 1)))
+        AX, infos = np.empty((S, nrhs, self.n)), (_lib.KktInfo * (S * nrhs))()
+        self._check(self._lib.asm_batch_solution_adjoint(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(GX), _lib.dptr(GL), par,
+                                                         _lib.dptr(OUT), _lib.dptr(DBOUND), _lib.dptr(AX), _lib.dptr(AL), infos))
+        return OUT[:, :, :nd], DBOUND[:, :, :self.m], AX, AL[:, :, :self.m], [[infos[s * nrhs + c] for c in range(nrhs)] for s in range(S)]
+
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.
         Returns (p, lambda, mult_x_U, mult_x_L, p_slack, status) with a leading scenario dimension."""
@@ -521,6 +542,24 @@ def solution_jacobians(hb, problems, runs, indices=None, tol=1e-6):
     DC[np.arange(len(idx)), idx] = 1.0
     DX, DLAM, _, infos = hb.solution_sensitivity_multi(x, lam, rs, bs, DC)
     return _jacobian_stacks(DX, DLAM, infos)
+
+
+def solution_adjoints(hb, problems, runs, GX, GL, tol=1e-6):
+    """(d phi / d dpar [S x k x n_dpar], d phi / d(bound) [S x k x m], status [S x k]) of the scenarios of the HipBatch `hb` at their runs
+    for k functions per scenario with gradients GX [S x k x n] and GL [S x k x m] (or [k x n] and [k x m], the same functions for every
+    scenario), on each scenario's working set (working_sets with `tol`) and with its data - one asm_batch_solution_adjoint call, one
+    KKT solve per function whatever n_dpar.  The reverse-mode counterpart of solution_jacobians; a function whose solve did not
+    end with status 0 is reported in `status`, not raised."""
+    S = len(runs)
+    GX, GL = np.asarray(GX, float), np.asarray(GL, float)
+    if GX.ndim == 2:
+        GX = np.broadcast_to(GX, (S,) + GX.shape)
+    if GL.ndim == 2:
+        GL = np.broadcast_to(GL, (S,) + GL.shape)
+    rs, bs = working_sets(problems, runs, tol)
+    x, lam = _run_points(hb, runs)
+    OUT, DBOUND, _, _, infos = hb.solution_adjoint(x, lam, rs, bs, GX, GL)
+    return OUT, DBOUND, np.array([[i.status for i in row] for row in infos], np.int32)
 
 
 def bound_jacobians(hb, problems, runs, rows, tol=1e-6):

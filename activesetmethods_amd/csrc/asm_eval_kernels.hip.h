@@ -423,9 +423,14 @@ __device__ __noinline__ double expr_libm2(int32_t op, double u) {
         default: return log(u);           // ASM_OP_LOG
     }
 }
-// forward sweep with tangent: tval = d val / d x_seed, statement by statement the tangent of expr_forward.  DATA: the seed is a direction
-// dc in the constants instead - a CONST node with operand a has the tangent dc[a], every VAR node 0 (asm_eval_data_cross)
-template <bool DATA = false>
+// what seeds a second-order sweep and what it writes: EXPR2_HESS the unit tangent of variable `seed`, adjoint tangents of the VAR nodes into
+// the thread's occurrence list; EXPR2_DATA a direction dc in the constants, the adjoint tangent of every VAR node an occurrence of its own
+// (asm_eval_data_cross); EXPR2_DATA_T a direction vx in the variables, an occurrence per CONST node (asm_eval_data_cross_t)
+enum { EXPR2_HESS = 0, EXPR2_DATA = 1, EXPR2_DATA_T = 2 };
+// forward sweep with tangent: tval = d val / d x_seed, statement by statement the tangent of expr_forward.  EXPR2_DATA: the seed is a direction
+// dc in the constants instead - a CONST node with operand a has the tangent dc[a], every VAR node 0 (asm_eval_data_cross).  EXPR2_DATA_T: the
+// seed is a direction in the variables, passed as dc - a VAR node of variable a has the tangent dc[a], every CONST node 0
+template <int DATA = EXPR2_HESS>
 __device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, int64_t seed, double* val, double* tval,
                                               const double* __restrict__ dc = nullptr) {
 #pragma clang fp contract(off)
@@ -435,12 +440,13 @@ __device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int
         double v, d;
         if (op == ASM_OP_CONST) {
             v = X.cst[a];
-            if constexpr (DATA) d = dc[a];
+            if constexpr (DATA == EXPR2_DATA) d = dc[a];
             else d = 0.0;
         }
         else if (op == ASM_OP_VAR) {
             v = x[a];
-            if constexpr (DATA) d = 0.0;
+            if constexpr (DATA == EXPR2_DATA) d = 0.0;
+            else if constexpr (DATA == EXPR2_DATA_T) d = dc[a];
             else d = a == seed ? 1.0 : 0.0;
         }
         else {
@@ -491,21 +497,27 @@ __device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int
 }
 // reverse sweep with tangent: adj as expr_reverse forms it, tadj = d adj / d x_seed, statement by statement; the adjoint tangent of a VAR
 // node whose variable is in the thread's occurrence list is added to hocc there (several VAR nodes of a variable: reverse node order).
-// DATA: every VAR node is an occurrence of its own instead - hocc[node] = wt * its adjoint tangent (one product), no list
-template <bool DATA = false>
+// EXPR2_DATA: every VAR node is an occurrence of its own instead - hocc[node] = wt * its adjoint tangent (one product), no list.
+// EXPR2_DATA_T: every CONST node k is an occurrence, hocc[slot[k]] = wt * tadj[k] + wa * adj[k] (two products, one sum; without `both` the
+// first product alone), and the VAR nodes write nothing
+template <int DATA = EXPR2_HESS>
 __device__ __forceinline__ void expr_reverse2(const ExprTape& X, int64_t k0, int64_t k1, const double* val, const double* tval, double* adj, double* tadj,
-                                              const int64_t* __restrict__ ovar, int64_t o0, int64_t o1, double* __restrict__ hocc, double wt = 0.0) {
+                                              const int64_t* __restrict__ ovar, int64_t o0, int64_t o1, double* __restrict__ hocc, double wt = 0.0,
+                                              double wa = 0.0, bool both = false) {
 #pragma clang fp contract(off)
     for (int64_t k = k0; k < k1; ++k) { adj[k] = 0.0; tadj[k] = 0.0; }
     adj[k1 - 1] = 1.0;
     for (int64_t k = k1 - 1; k >= k0; --k) {
         const int32_t op = X.op[k];
-        if (op == ASM_OP_CONST) continue;
+        if (op == ASM_OP_CONST) {
+            if constexpr (DATA == EXPR2_DATA_T) hocc[X.slot[k]] = both ? wt * tadj[k] + wa * adj[k] : wt * tadj[k];
+            continue;
+        }
         const double w = adj[k], z = tadj[k];
         const int64_t a = X.a[k], b = X.b[k];
         if (op == ASM_OP_VAR) {
-            if constexpr (DATA) hocc[k] = wt * z;
-            else
+            if constexpr (DATA == EXPR2_DATA) hocc[k] = wt * z;
+            else if constexpr (DATA == EXPR2_HESS)
                 for (int64_t o = o0; o < o1; ++o)
                     if (ovar[o] == a) { hocc[o] = hocc[o] + z; break; }
             continue;
@@ -692,9 +704,9 @@ __global__ __launch_bounds__(256) void k_nlp_expr_cross(AsmBt abt, ExprTape X, E
     const int64_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= X.R + X.T) return;
     const int64_t k0 = X.ptr[t], k1 = X.ptr[t + 1];
-    expr_forward2<true>(X, k0, k1, x, -1, C.val, C.tval, dc);
+    expr_forward2<EXPR2_DATA>(X, k0, k1, x, -1, C.val, C.tval, dc);
     if (t < X.R) wrow[t] = C.tval[k1 - 1];
-    expr_reverse2<true>(X, k0, k1, C.val, C.tval, C.adj, C.tadj, nullptr, 0, 0, C.vocc, t < X.R ? -lam[t] : scale);
+    expr_reverse2<EXPR2_DATA>(X, k0, k1, C.val, C.tval, C.adj, C.tadj, nullptr, 0, 0, C.vocc, t < X.R ? -lam[t] : scale);
 }
 // one thread per variable sums its occurrences in list order from 0.0 (fixed order, no atomics: the host twin's sum)
 __global__ __launch_bounds__(256) void k_nlp_expr_cross_gather(AsmBt abt, ExprCross C, int64_t n, double* __restrict__ u) {
@@ -836,6 +848,74 @@ __global__ __launch_bounds__(256) void k_nlp_dense_cross_u(AsmBt abt, const doub
     double g = 0.0;
     for (int64_t i = 0; i < mrows; ++i) g = g + lam[i] * (dA[i * n + j] + dQ[i * n + j] * xj);
     cx[blockIdx.y * ldo + j] = -g;
+}
+// ---- transposed cross derivatives (asm_eval_data_cross_t; include/asm_hip.h, "Transposed cross derivatives"): for weights vx [n] and vl (the
+// block's rows), out[c] = d/d dpar[c] [ D_vx L + vl' g ] - for every direction dc, dc' out = vx' u + vl' w with (u, w) of asm_eval_data_cross.
+// Expression block: the sweep of k_nlp_expr_cross with the other seed - a VAR node of variable j has the tangent vx[j], a CONST node 0 (a
+// CONST exponent of POW stays out, as there).  One thread per row (t < R) or term, its node arrays as in k_nlp_expr_cross; in the reverse pass
+// every CONST node yields one occurrence into the cocc list of k_nlp_expr_const_adj (same slot, same cptr grouping): for a node of row t
+// (-lam[t]) * tadj + vl[t] * adj - two products, one sum - and for a node of a term scale * tadj.  k_nlp_expr_data_gather sums per dpar index.
+__global__ __launch_bounds__(256) void k_nlp_expr_cross_t(AsmBt abt, ExprTape X, ExprCross C, const double* __restrict__ x, const double* __restrict__ vx, const double* __restrict__ lam, const double* __restrict__ vl, double scale, double* __restrict__ cocc) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, X, C, x, vx, lam, vl, scale, cocc);
+    const int64_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= X.R + X.T) return;
+    const int64_t k0 = X.ptr[t], k1 = X.ptr[t + 1];
+    const bool row = t < X.R;
+    expr_forward2<EXPR2_DATA_T>(X, k0, k1, x, -1, C.val, C.tval, vx);
+    expr_reverse2<EXPR2_DATA_T>(X, k0, k1, C.val, C.tval, C.adj, C.tadj, nullptr, 0, 0, cocc, row ? -lam[t] : scale, row ? vl[t] : 0.0, row);
+}
+// Ohm's-law block: one thread per (branch, column), the column in blockIdx.y; a column's weights are [vx (n) | vl (4 nl)] at v + column * ldv,
+// its outputs out + column * ldo in dpar's layout.  The block is linear in its data, nothing reads dpar.  With the four basis values of
+// k_nlp_ohm_data_grad, vf2 = vf*vf, vt2 = vt*vt, vvc = vv*cs, vvs = vv*sn, and their derivatives along vx at the branch's four variables
+// (dvf, dvt the entries of vx at vm_f, vm_t; dd = vx[va_f] - vx[va_t]; tvv = dvf*vt + vf*dvt):
+//   tvf2 = 2*(vf*dvf)    tvt2 = 2*(vt*dvt)    tvvc = tvv*cs - vvs*dd    tvvs = tvv*sn + vvc*dd
+// every output is k_nlp_ohm_data_grad's pattern with (lam, derivative) minus the same pattern with (vl, value) - the constraint is x_flow - F_r.
+__global__ __launch_bounds__(256) void k_nlp_ohm_cross_t(AsmBt abt, const int64_t* __restrict__ ipar, const double* __restrict__ x, const double* __restrict__ lam, const double* __restrict__ v, int64_t ldv, int64_t n, double* __restrict__ out, int64_t ldo) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, ipar, x, lam, v, ldv, n, out, ldo);
+    const int64_t nl = ipar[0];
+    const int64_t l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= nl) return;
+    const int64_t va0 = ipar[1], vm0 = ipar[2];
+    const int64_t fb = ipar[7 + l], tb = ipar[7 + nl + l];
+    const double* vx = v + blockIdx.y * ldv;
+    const double* vl = vx + n;
+    const double l0 = lam[l], l1 = lam[nl + l], l2 = lam[2 * nl + l], l3 = lam[3 * nl + l];
+    const double v0 = vl[l], v1 = vl[nl + l], v2 = vl[2 * nl + l], v3 = vl[3 * nl + l];
+    const double vf = x[vm0 + fb], vt = x[vm0 + tb];
+    const double d = x[va0 + fb] - x[va0 + tb];
+    const double dvf = vx[vm0 + fb], dvt = vx[vm0 + tb];
+    const double dd = vx[va0 + fb] - vx[va0 + tb];
+    const double cs = cos(d), sn = sin(d);
+    const double vv = vf * vt;
+    const double vf2 = vf * vf, vt2 = vt * vt, vvc = vv * cs, vvs = vv * sn;
+    const double tvv = dvf * vt + vf * dvt;
+    const double tvf2 = 2.0 * (vf * dvf), tvt2 = 2.0 * (vt * dvt);
+    const double tvvc = tvv * cs - vvs * dd, tvvs = tvv * sn + vvc * dd;
+    double* o = out + blockIdx.y * ldo + l;
+    o[0] = l0 * tvf2 - v0 * vf2;
+    o[nl] = l1 * tvf2 - v1 * vf2;
+    o[2 * nl] = l2 * tvt2 - v2 * vt2;
+    o[3 * nl] = l3 * tvt2 - v3 * vt2;
+    o[4 * nl] = (l0 * tvvc + l1 * tvvs) - (v0 * vvc + v1 * vvs);
+    o[5 * nl] = (l0 * tvvs - l1 * tvvc) - (v0 * vvs - v1 * vvc);
+    o[6 * nl] = (l2 * tvvc - l3 * tvvs) - (v2 * vvc - v3 * vvs);
+    o[7 * nl] = (-(l2 * tvvs) - l3 * tvvc) - (-(v2 * vvs) - v3 * vvc);
+}
+// Dense quadratic block: one thread per entry (i, j) and column (blockIdx.y), weights and outputs laid out as for k_nlp_ohm_cross_t:
+//   out[A_ij] = (-lam_i) * vx_j + vl_i * x_j        out[Q_ij] = (-lam_i) * (x_j * vx_j) + vl_i * (0.5 * (x_j * x_j))
+__global__ __launch_bounds__(256) void k_nlp_dense_cross_t(AsmBt abt, int64_t mrows, int64_t n, const double* __restrict__ x, const double* __restrict__ lam, const double* __restrict__ v, int64_t ldv, double* __restrict__ out, int64_t ldo) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, mrows, n, x, lam, v, ldv, out, ldo);
+    const int64_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= mrows * n) return;
+    const int64_t i = e / n, j = e - i * n;
+    const double* vx = v + blockIdx.y * ldv;
+    const double xj = x[j], vxj = vx[j], wi = -lam[i], vli = vx[n + i];
+    double* o = out + blockIdx.y * ldo;
+    o[e] = wi * vxj + vli * xj;
+    o[mrows * n + e] = wi * (xj * vxj) + vli * (0.5 * (xj * xj));
 }
 // out = H v from the values: one thread per variable walks its list of (entry, other variable) in entry order - an off-diagonal entry
 // (i, j) is in the lists of i and of j - and sums values[entry] * v[other] from 0.0

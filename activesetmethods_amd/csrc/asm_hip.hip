@@ -436,6 +436,11 @@ struct EvalState {
     // occurrences of the Ohm's-law block, d_cx_vnode where each listed occurrence lives in a column's; cx_cap is 1 or KKM_CW (cx_prepare)
     int64_t cx_cap = 0;
     double* d_cx_occ = nullptr;
+    // transposed cross derivatives (asm_eval_data_cross_t and the adjoint entries; ct_prepare): with R the block's rows, d_ct_in = [lam (R) |
+    // ct_cap columns [vx (n) | vl (R)]], d_ct_out = ct_cap columns of n_dpar, h_ct the pinned staging of x, both and the read-back; ct_cap
+    // is 1 or KKM_CW.  Kind 3 runs in cx_C's node arrays and d_cocc.
+    int64_t ct_cap = 0;
+    double *d_ct_in = nullptr, *d_ct_out = nullptr, *h_ct = nullptr;
     bool ohm_vars_ok = true;        // kind 4: every variable the block names is inside [0, n) (checked at asm_eval_setup, refused by the data entries)
     KktBufs kk;                     // KKT solve on a working set (asm_kkt_solve and the multi entries)
     int64_t kkm_rounds = 0;         // test seam: lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
@@ -4925,6 +4930,83 @@ static void do_data_cross(asm_handle* h, const double* x, const double* lambda, 
     if (X.R > 0) std::memcpy(w + e.F.n_rows, back + n, X.R * sizeof(double));
 }
 
+// ---- transposed cross derivatives (include/asm_hip.h, "Transposed cross derivatives")
+namespace {
+// whether anything depends on the block's data: a tape without a CONST node and a block without data give an all-zero answer, no launch
+bool ct_active(const EvalState& e) { return nlp_block_derivs(e.nlp_kind) ? e.n_dpar > 0 : e.d_cocc != nullptr; }
+// the workspace for `cap` columns: 1 for asm_eval_data_cross_t and asm_solution_adjoint, KKM_CW from the first multi call on (the narrower
+// ones stay in the pool).  Kind 3 borrows the node arrays of the cross sweep (cx_prepare: blocking copies, not inside a batch fiber)
+void ct_prepare(asm_handle* h, int64_t cap) {
+    EvalState& e = *h->ev;
+    if (e.ct_cap >= cap) return;
+    const bool block = nlp_block_derivs(e.nlp_kind);
+    if (!block) cx_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->sk->n, R = block ? e.nlp_rows : e.X.R, nd = e.n_dpar;
+    BufPool& M = e.mem;
+    M.zeroed(e.d_ct_in, R + cap * (n + R)); M.zeroed(e.d_ct_out, cap * nd);
+    M.alloc(e.h_ct, n + R + cap * (n + R + nd), BufPool::PINNED);
+    e.ct_cap = cap;
+}
+// OUT [ncol x n_dpar]: row c = the transposed cross derivative at (x, lambda) for the weights (sx * VX[c], VL[c]) (VX ncol x n, VL ncol x m;
+// sx = -1 turns an adjoint state's ax into the weight -ax, exactly), in chunks of `cap` columns.  x and the block's multipliers go up once;
+// a chunk is one upload, its launches and one read-back: kinds 4 and 5 one launch for all its columns (grid.y = column), kind 3 one
+// launch pair per column, no synchronisation between columns.  A column's answer depends on its own weights only.
+void ct_columns(asm_handle* h, const double* x, const double* lambda, int64_t ncol, const double* VX, double sx, const double* VL, double* OUT, int64_t cap) {
+    EvalState& e = *h->ev;
+    const int64_t n = h->sk->n, m = h->sk->m, nd = e.n_dpar;
+    if (!ct_active(e)) {
+        for (int64_t q = 0; q < ncol * nd; ++q) OUT[q] = 0.0;
+        return;
+    }
+    ct_prepare(h, cap);
+    HIPCHK(hipSetDevice(h->device));
+    const hipStream_t s = h->stream;
+    const bool block = nlp_block_derivs(e.nlp_kind);
+    const int64_t R = block ? e.nlp_rows : e.X.R, r0 = e.F.n_rows, ldv = n + R;
+    double *st = e.h_ct, *s_in = st + n, *back = s_in + R + cap * ldv;
+    std::memcpy(st, x, n * sizeof(double));
+    if (R > 0) std::memcpy(s_in, lambda + r0, R * sizeof(double));
+    HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, s));
+    if (R > 0) HIPCHK(asmb::copy_async(e.d_ct_in, s_in, R * sizeof(double), hipMemcpyHostToDevice, s));
+    const double* lam = e.d_ct_in;
+    double* dv = e.d_ct_in + R;
+    for (int64_t c0 = 0; c0 < ncol; c0 += cap) {
+        const int cols = (int)std::min<int64_t>(cap, ncol - c0);
+        for (int c = 0; c < cols; ++c) {
+            double* sv = s_in + R + (int64_t)c * ldv;
+            const double* vx = VX + (c0 + c) * n;
+            for (int64_t j = 0; j < n; ++j) sv[j] = sx * vx[j];
+            if (R > 0) std::memcpy(sv + n, VL + (c0 + c) * m + r0, R * sizeof(double));
+        }
+        HIPCHK(asmb::copy_async(dv, s_in + R, (int64_t)cols * ldv * sizeof(double), hipMemcpyHostToDevice, s));
+        if (nlp_is_ohm(e.nlp_kind)) {
+            asmb::launch(k_nlp_ohm_cross_t, dim3(asmb::blocks(R / 4).x, (unsigned)cols), dim3(256), s, e.d_ipar, e.d_xt, lam, (const double*)dv, ldv, n, e.d_ct_out, nd);
+        } else if (block) {
+            asmb::launch(k_nlp_dense_cross_t, dim3(asmb::blocks(R * n).x, (unsigned)cols), dim3(256), s, R, n, e.d_xt, lam, (const double*)dv, ldv, e.d_ct_out, nd);
+        } else {
+            const ExprTape& X = e.X;
+            for (int c = 0; c < cols; ++c) {
+                const double* v = dv + (int64_t)c * ldv;
+                asmb::launch(k_nlp_expr_cross_t, asmb::blocks(X.R + X.T), dim3(256), s, X, e.cx_C, e.d_xt, v, lam, v + n, e.F.objective_scale, e.d_cocc);
+                asmb::launch(k_nlp_expr_data_gather, asmb::blocks(nd), dim3(256), s, e.d_cptr, e.d_cocc, nd, e.d_ct_out + (int64_t)c * nd);
+            }
+        }
+        HIPCHK(asmb::copy_async(back, e.d_ct_out, (int64_t)cols * nd * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::sync(s));
+        std::memcpy(OUT + c0 * nd, back, (int64_t)cols * nd * sizeof(double));
+    }
+}
+}  // namespace
+// out[c] = d/d dpar[c] [ D_vx L + vl' g ] at (x, lambda), L = f - lambda' g; the inputs of the next LP are not touched (x goes where
+// asm_eval_constraints puts its trial point)
+static void do_data_cross_t(asm_handle* h, const double* x, const double* lambda, const double* vx, const double* vl, double* out) {
+    cx_check(h, "asm_eval_data_cross_t");
+    EvalState& e = *h->ev;
+    if (!x || !vx || (h->sk->m > 0 && (!lambda || !vl)) || (e.n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_cross_t: null pointer");
+    ct_columns(h, x, lambda, 1, vx, 1.0, vl, out, 1);
+}
+
 // ---- limited-memory Hessian (include/asm_hip.h, "Limited-memory Hessian"; kernels in asm_lm_kernels.hip.h)
 namespace {
 void lm_clear(asm_handle* h) {
@@ -5834,15 +5916,15 @@ static void do_solution_sensitivity(asm_handle* h, const double* x, const double
 }
 // asm_kkt_solve_multi (sens false: the rows of RU, RW are the right-hand sides), asm_solution_sensitivity_multi (the rows of DC are
 // directions of the data) and asm_bound_sensitivity_multi (bd.rows: a row per column, RU and RW not read - a derivative entry like the
-// second, exact whatever the handle's type)
+// second, exact whatever the handle's type; exact_only: the adjoint entries, derivative entries too)
 static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                const double* RU, const double* RW, const double* DC, bool sens, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
-                               asm_kkt_info* info, const KktBound& bd = KktBound()) {
+                               asm_kkt_info* info, const KktBound& bd = KktBound(), bool exact_only = false) {
     const std::string me(who);
     const bool bound = bd.rows != nullptr;
     if (sens) cx_check(h, who);
-    if (sens || bound) hs_check(h, who);
-    const bool lm = !sens && !bound && kkt_hess_lm(h, who);
+    if (sens || bound || exact_only) hs_check(h, who);
+    const bool lm = !sens && !bound && !exact_only && kkt_hess_lm(h, who);
     if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
     if (!x || !bound_state || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
     if (bound) {
@@ -5860,6 +5942,54 @@ static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, 
         KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
         kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active, KktTrust(), bd);
     }
+}
+// ---- adjoint solution sensitivities (include/asm_hip.h, "Adjoint solution sensitivities"): per function the adjoint state (ax, al) =
+// asm_kkt_solve(ru = -gx, rw = gl), then out = the transposed cross derivative for the weights (-ax, al) and dbound_i = -al_i on the working
+// rows, 0.0 elsewhere.  A derivative entry: the exact Hessian whatever the handle's type.
+namespace {
+// the kinds the adjoint entries serve: those of asm_solution_sensitivity, and the function store alone (kind 0) - no data, an empty out,
+// but the bound gradient and the adjoint state need no data derivative.  Kinds 1 and 2 end in the solve's hs_check.
+void adjoint_check(const asm_handle* h, const char* who) {
+    if (ev_of(h, who).nlp_kind != 0) cx_check(h, who);
+}
+void adjoint_dbound(const int32_t* row_state, int64_t m, int64_t ncol, const double* AL, double* DBOUND) {
+    if (!DBOUND) return;
+    for (int64_t c = 0; c < ncol; ++c)
+        for (int64_t i = 0; i < m; ++i) DBOUND[c * m + i] = row_state[i] == 1 ? -AL[c * m + i] : 0.0;
+}
+// the multi entry on a handle, for the per-handle call and for a batch fiber: RU = -GX made by the caller, AX and AL not null
+void adjoint_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* RU,
+                   const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+    do_kkt_solve_multi(h, who, x, lambda, row_state, bound_state, nrhs, RU, GL, nullptr, false, par, AX, AL, nullptr, info, KktBound(), true);
+    ct_columns(h, x, lambda, nrhs, AX, -1.0, AL, OUT, KKM_CW);
+    adjoint_dbound(row_state, h->sk->m, nrhs, AL, DBOUND);
+}
+}  // namespace
+static void do_solution_adjoint(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* gx, const double* gl,
+                                const asm_kkt_params* par, double* out, double* dbound, double* ax, double* al, asm_kkt_info* info) {
+    adjoint_check(h, "asm_solution_adjoint");
+    const int64_t n = h->sk->n, m = h->sk->m;
+    if (!x || !bound_state || !gx || !info || (m > 0 && (!lambda || !row_state || !gl)) || (h->ev->n_dpar > 0 && !out))
+        throw std::invalid_argument("asm_solution_adjoint: null pointer");
+    std::vector<double> ru((size_t)std::max<int64_t>(n, 1)), sx(ax ? 0 : (size_t)std::max<int64_t>(n, 1)), sl(al ? 0 : (size_t)std::max<int64_t>(m, 1));
+    for (int64_t j = 0; j < n; ++j) ru[j] = -gx[j];
+    if (!ax) ax = sx.data();
+    if (!al) al = sl.data();
+    do_kkt_solve(h, x, lambda, row_state, bound_state, ru.data(), gl, par, ax, al, nullptr, info, true);
+    ct_columns(h, x, lambda, 1, ax, -1.0, al, out, 1);
+    adjoint_dbound(row_state, m, 1, al, dbound);
+}
+static void do_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
+                                      const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+    const char* who = "asm_solution_adjoint_multi";
+    adjoint_check(h, who);
+    hs_check(h, who);
+    const int64_t n = h->sk->n, m = h->sk->m;
+    if (nrhs < 1) throw std::invalid_argument(std::string(who) + ": nrhs < 1");
+    if (!x || !bound_state || !GX || !info || (m > 0 && (!lambda || !row_state || !GL)) || (h->ev->n_dpar > 0 && !OUT)) throw std::invalid_argument(std::string(who) + ": null pointer");
+    std::vector<double> ru((size_t)std::max<int64_t>(nrhs * n, 1)), sx(AX ? 0 : (size_t)std::max<int64_t>(nrhs * n, 1)), sl(AL ? 0 : (size_t)std::max<int64_t>(nrhs * m, 1));
+    for (int64_t q = 0; q < nrhs * n; ++q) ru[q] = -GX[q];
+    adjoint_multi(h, who, x, lambda, row_state, bound_state, nrhs, ru.data(), GL, par, OUT, DBOUND, AX ? AX : sx.data(), AL ? AL : sl.data(), info);
 }
 // asm_kkt_step (one column through KktOneColumn) and asm_kkt_step_multi (KktBlock): the checks of asm_kkt_solve(_multi), then
 // those of the radii and the share
@@ -5968,6 +6098,20 @@ int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* la
         if (!rows) throw std::invalid_argument("asm_bound_sensitivity_multi: null pointer");
         do_kkt_solve_multi(h, "asm_bound_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, nullptr, false, par, DX, DLAM, DZ, info, KktBound{rows, delta});
     });
+}
+
+int asm_eval_data_cross_t(asm_handle* h, const double* x, const double* lambda, const double* vx, const double* vl, double* out) {
+    return guarded(h, [&] { do_data_cross_t(h, x, lambda, vx, vl, out); });
+}
+
+int asm_solution_adjoint(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* gx, const double* gl,
+                         const asm_kkt_params* par, double* out, double* dbound, double* ax, double* al, asm_kkt_info* info) {
+    return guarded(h, [&] { do_solution_adjoint(h, x, lambda, row_state, bound_state, gx, gl, par, out, dbound, ax, al, info); });
+}
+
+int asm_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
+                               const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+    return guarded(h, [&] { do_solution_adjoint_multi(h, x, lambda, row_state, bound_state, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
 }
 
 int asm_kkt_set_form(asm_handle* h, int32_t form) {
@@ -8139,8 +8283,9 @@ void batch_hs_prepare(asm_batch* b, const char* who) {
 // The multi entries (asm_batch_kkt_solve and the two sensitivity entries, cap = KKM_CW) come here too: the work area of 64 columns
 // - 14 ldn + 5 ldT + Mp doubles per column, the transposed factor (ld^2) and, dense form, the unmasked transposed working rows (ldn ldT) -
 // instead of the one-column area and the trial's state, and with `cross` what the cross-derivative sweep of the slot's kind needs
-// (cx_prepare downloads with blocking copies), under the conditions kkt_columns reads it.
-void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_eqp", int64_t cap = 1, bool cross = false) {
+// (cx_prepare downloads with blocking copies), under the conditions kkt_columns reads it; with `cross_t` the workspace of the transposed
+// sweep (asm_batch_solution_adjoint), under the conditions ct_columns reads it.
+void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_eqp", int64_t cap = 1, bool cross = false, bool cross_t = false) {
     bool sparse = b->kkt_form == ASM_KKT_SPARSE && b->slots[0]->sk->sp_ok;
     for (int s = 0; s < count; ++s)
         in_slot(step, s, [&] {
@@ -8155,6 +8300,7 @@ void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_
             if (cap == 1) eq_prepare(h);
             const EvalState& e = *h->ev;
             if (cross && (nlp_block_derivs(e.nlp_kind) ? e.n_dpar > 0 : e.d_cocc != nullptr)) cx_prepare(h, KKM_CW);
+            if (cross_t && ct_active(e)) ct_prepare(h, KKM_CW);
         });
 }
 // The three multi entries on n_scen scenarios, the slots taking them in index order: per scenario do_kkt_solve_multi under the per-handle
@@ -8196,6 +8342,41 @@ void batch_kkt_multi(asm_batch* b, const char* who, const char* step, int64_t n_
             do_kkt_solve_multi(h, step, x + sc * n, m > 0 ? lambda + sc * m : nullptr, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n, nrhs, RU ? RU + o * n : nullptr,
                                RW ? RW + o * m : nullptr, DC ? DC + sc * dc_stride : nullptr, sens, par, DX + o * n, m > 0 ? DLAM + o * m : nullptr, DZ ? DZ + o * n : nullptr,
                                info + o, bd);
+        }
+    });
+}
+// asm_solution_adjoint_multi on n_scen scenarios, the slots taking them in index order: the checks of batch_kkt_multi, the negated
+// gradients and (where the caller wants none) the adjoint states' buffers made here for all scenarios, the workspaces before the fibers start
+void batch_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
+                   const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+    const char *who = "asm_batch_solution_adjoint", *step = "asm_solution_adjoint_multi";
+    const std::string me(who);
+    batch_hs_prepare(b, who);
+    adjoint_check(b->slots[0], who);
+    const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = b->slots[0]->ev->n_dpar;
+    if (n_scen < 1 || nrhs < 1) throw std::invalid_argument(me + ": n_scen < 1 or nrhs < 1");
+    if (!x || !bound_state || !GX || !info || (m > 0 && (!lambda || !row_state || !GL)) || (nd > 0 && !OUT)) throw std::invalid_argument(me + ": null pointer");
+    if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
+    check_scen(b, n_scen, who);
+    HIPCHK(hipSetDevice(b->device));
+    const int64_t cols = n_scen * nrhs;
+    std::vector<double> ru((size_t)std::max<int64_t>(cols * n, 1)), sx(AX ? 0 : (size_t)std::max<int64_t>(cols * n, 1)), sl(AL ? 0 : (size_t)std::max<int64_t>(cols * m, 1));
+    for (int64_t q = 0; q < cols * n; ++q) ru[q] = -GX[q];
+    if (!AX) AX = sx.data();
+    if (!AL) AL = sl.data();
+    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
+    batch_kkt_prepare(b, count, step, KKM_CW, false, true);
+    std::atomic<int64_t> next{0};
+    run_fibers(b, count, step, [&](int s) {
+        asm_handle* h = b->slots[s];
+        for (;;) {
+            const int64_t sc = next.fetch_add(1);
+            if (sc >= n_scen) break;
+            batch_scenario_data(b, h, sc);
+            asmb::next_cycle();
+            const int64_t o = sc * nrhs;
+            adjoint_multi(h, step, x + sc * n, m > 0 ? lambda + sc * m : nullptr, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n, nrhs, ru.data() + o * n,
+                          m > 0 ? GL + o * m : nullptr, par, OUT + o * nd, DBOUND ? DBOUND + o * m : nullptr, AX + o * n, AL + o * m, info + o);
         }
     });
 }
@@ -8290,6 +8471,11 @@ int asm_batch_solution_sensitivity(asm_batch* b, int64_t n_scen, const double* x
         batch_kkt_multi(b, "asm_batch_solution_sensitivity", "asm_solution_sensitivity_multi", n_scen, x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, stride, true,
                         nullptr, par, DX, DLAM, DZ, info);
     });
+}
+
+int asm_batch_solution_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                               const double* GX, const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+    return guarded(b, [&] { batch_adjoint(b, n_scen, x, lambda, row_state, bound_state, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
 }
 
 int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,

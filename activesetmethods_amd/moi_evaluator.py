@@ -99,7 +99,9 @@ class NlpBlock:
     with `lam` the block's multipliers; absent, the block announces no Hessian.
     Optional derivatives with respect to the block's data (the device kernel's dpar), with the signatures of the expression twin
     (nlexpr.ExprBlock): data_gradient(x, lam_block, scale=1.0) -> [n_dpar] and data_cross(x, lam_block, dc, scale=1.0) -> (u [n],
-    w [block rows]); absent (None), the block has no data derivatives."""
+    w [block rows]); absent (None), the block has no data derivatives.  The transposed cross derivative that goes with data_cross,
+    data_cross_t(x, lam_block, vx, vl_block, scale=1.0) -> [n_dpar], travels as that callable's attribute `transposed` (the block's own
+    attributes stay the two above); None when there is none."""
 
     data_gradient = data_cross = None
 
@@ -120,6 +122,10 @@ class NlpBlock:
             self.data_gradient = data_gradient
         if data_cross is not None:
             self.data_cross = data_cross
+
+    @property
+    def data_cross_t(self):
+        return getattr(self.data_cross, "transposed", None)
 
     @property
     def m(self):

@@ -485,9 +485,10 @@ class _HessSweep(_Sweep):
                     aux.append(None)
             self.aux.append(aux)
 
-    def forward2(self, x, consts, dc=None):
-        """Values V and tangents D.  With `dc` (the data cross derivatives, expr_forward2<DATA>): the seed is that direction in the
-        constants - a CONST node with operand a has the tangent dc[a], every VAR node 0."""
+    def forward2(self, x, consts, dc=None, vx=None):
+        """Values V and tangents D.  With `dc` (the data cross derivatives, expr_forward2<EXPR2_DATA>): the seed is that direction in
+        the constants - a CONST node with operand a has the tangent dc[a], every VAR node 0.  With `vx` (the transposed cross
+        derivatives, EXPR2_DATA_T): a direction in the variables - a VAR node of variable a has the tangent vx[a], every CONST node 0."""
         V = np.zeros((self.nr, max(self.K, 1)))
         D = np.zeros_like(V)
         with np.errstate(all="ignore"):
@@ -499,7 +500,7 @@ class _HessSweep(_Sweep):
                             D[r, k] = dc[a]
                         continue
                     if o == VAR:
-                        V[r, k], D[r, k] = x[a], (aux[0] if dc is None else 0.0)
+                        V[r, k], D[r, k] = x[a], (vx[a] if vx is not None else aux[0] if dc is None else 0.0)
                         continue
                     u, du = V[r, a], D[r, a]
                     if o in _BINARY:
@@ -575,10 +576,12 @@ class _HessSweep(_Sweep):
                     V[r, k], D[r, k] = v, d
         return V, D
 
-    def reverse2(self, V, D, hocc, weight=None):
+    def reverse2(self, V, D, hocc, weight=None, cslot=None, wadj=None, both=None):
         """Adjoints W and their tangents Z from the last node of every thread back; the adjoint tangent of a VAR node whose
-        variable is in the thread's occurrence list is added to hocc there.  With `weight` (one per thread; expr_reverse2<DATA>):
-        every VAR node is an occurrence of its own, hocc[node in the tape] = weight * its adjoint tangent."""
+        variable is in the thread's occurrence list is added to hocc there.  With `weight` (one per thread; expr_reverse2<EXPR2_DATA>):
+        every VAR node is an occurrence of its own, hocc[node in the tape] = weight * its adjoint tangent.  With `cslot` as well (the
+        slot of every node of the tape; EXPR2_DATA_T): the CONST nodes are the occurrences instead, hocc[cslot[node]] = weight *
+        adjoint tangent + wadj * adjoint for the threads named in `both`, weight * adjoint tangent alone for the others."""
         W = np.zeros_like(V)
         Z = np.zeros_like(V)
         W[np.arange(self.nr), self.last] = 1.0
@@ -586,9 +589,14 @@ class _HessSweep(_Sweep):
             for k in range(self.K - 1, -1, -1):
                 for (o, r, a, b, _), aux in zip(self.steps[k], self.aux[k]):
                     if o == CONST:
+                        if cslot is not None:
+                            t1 = weight[r] * Z[r, k]
+                            hocc[cslot[self.start[r] + k]] = np.where(both[r], t1 + wadj[r] * W[r, k], t1)
                         continue
                     w, z = W[r, k], Z[r, k]
                     if o == VAR:
+                        if cslot is not None:
+                            continue
                         if weight is not None:
                             hocc[self.start[r] + k] = weight[r] * z
                             continue
@@ -748,6 +756,7 @@ class ExprBlock(NlpBlock):
         self.c_ptr = np.concatenate([[0], np.cumsum(np.bincount(a[kc], minlength=len(tape.consts)))]).astype(np.int64)
         self.n_var = n_var
         self._consts = tape.dpar()
+        self._slot = slot
         self._rows = _Sweep(ptr[:R + 1], op, tape.a, tape.b, slot)
         self._terms = _Sweep(ptr[R:] - ptr[R], op[ptr[R]:], tape.a[ptr[R]:], tape.b[ptr[R]:], slot[ptr[R]:])
         self._n_occ = len(kv)
@@ -878,6 +887,31 @@ class ExprBlock(NlpBlock):
             s = cnt > i
             u[s] = u[s] + vocc[vnode[vptr[:-1][s] + i]]
         return u[:self.n_var], w
+
+    def data_cross_t(self, x, lam, vx, vl, scale=1.0):
+        """Host twin of asm_eval_data_cross_t: out [n_dpar] with out[c] = d/d dpar[c] [D_vx (scale * f - lam' g) + vl' g], `lam` and
+        `vl` on the block's rows, `vx` a direction in the variables: dc' out = vx' u + vl' w for (u, w) = data_cross(x, lam, dc).  The
+        sweep of data_cross seeded in the variables; every CONST node is an occurrence - (-lam[r]) * adjoint tangent + vl[r] * adjoint
+        in a row r, scale * adjoint tangent in a term - and out[c] sums those of dpar[c] from 0.0 in data_gradient's order
+        (k_nlp_expr_cross_t, k_nlp_expr_data_gather)."""
+        tape = self.tape
+        R, T = tape.R, tape.T
+        x, lam, vx, vl = (np.asarray(v, float) for v in (x, lam, vx, vl))
+        cnt = np.diff(self.c_ptr)
+        out = np.zeros(len(cnt))
+        if not np.any(tape.op == CONST) or R + T == 0:
+            return out
+        ptr = tape.ptr
+        sweep = _HessSweep(ptr[:-1].copy(), np.diff(ptr), tape.op, tape.a, tape.b, np.full(R + T, -1, np.int64), np.zeros(0, np.int64),
+                           max(self.n_var, 1))
+        V, D = sweep.forward2(x, self._consts, vx=vx)
+        cocc = np.zeros(int(self.c_ptr[-1]))
+        sweep.reverse2(V, D, cocc, weight=np.concatenate([-lam[:R], np.full(T, float(scale))]), cslot=self._slot,
+                       wadj=np.concatenate([vl[:R], np.zeros(T)]), both=np.arange(R + T) < R)
+        for i in range(int(cnt.max()) if len(cnt) else 0):
+            s = cnt > i
+            out[s] = out[s] + cocc[self.c_ptr[:-1][s] + i]
+        return out
 
     # ---- host callbacks (the twins of k_nlp_expr_rows / _terms / _objective / _gradient)
     def _eval_g(self, x, out):

@@ -181,6 +181,13 @@ def synthetic_dense_function_model(n=1000, m=500, hessian=False):
         for i in range(m):
             g = g + float(lam[i]) * (dA[i] + dQ[i] * x)
         return -g, (dA * x + 0.5 * dQ * x * x).sum(axis=1)
+
+    def data_cross_t(x, lam, vx, vl, scale=1.0):
+        """The transposed cross derivative (k_nlp_dense_cross_t), bit for bit: out[A_ij] = (-lam_i) vx_j + vl_i x_j and out[Q_ij] =
+        (-lam_i) (x_j vx_j) + vl_i (0.5 (x_j x_j))."""
+        x, w, vx, vl = np.asarray(x, float), -np.asarray(lam, float), np.asarray(vx, float), np.asarray(vl, float)
+        return np.concatenate([(np.outer(w, vx) + np.outer(vl, x)).ravel(), (np.outer(w, x * vx) + np.outer(vl, 0.5 * (x * x))).ravel()])
+    data_cross.transposed = data_cross_t                    # (how a block carries it: NlpBlock.data_cross_t)
     diag = np.arange(1, n + 1, dtype=np.int64)
     fm.nlp = NlpBlock(pr.g_L, pr.g_U, pr.j_row, pr.j_col, pr.eval_g, pr.eval_jac_g, device=("dense_quadratic_hess", np.zeros(1, np.int64), dpar),
                       hess_rows=diag, hess_cols=diag, eval_hess=eval_hess, data_gradient=data_gradient, data_cross=data_cross)

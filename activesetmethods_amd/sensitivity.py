@@ -20,6 +20,14 @@ block kernels with derivatives).  A constraint bound that moves by d(bound_i) en
     bound_rhs            the right-hand sides of bound sensitivities as matrices: what asm_bound_sensitivity_multi makes on the device
     predict              the first-order prediction x + step * dx
 
+Reverse mode ("Adjoint solution sensitivities"): for one function phi(x*, lam*) with gradients (gx, gl) the KKT matrix of the working
+set is symmetric, so d phi / d dpar for ALL constants is one solve - the adjoint state (ax, al) = kkt(ru = -gx, rw = gl) - and one
+transposed cross derivative with the weights (-ax, al); d phi / d(bound_i) = -al_i on the working rows.
+
+    model_cross_t        the host twin of asm_eval_data_cross_t for a FunctionModel (the block's data_cross_t on the model's rows)
+    adjoint_reference    the dense kkt_reference plus that twin: the independent answer
+    solution_adjoint     the device call on a handle (asm_solution_adjoint), or on a fresh one for a Model
+
 For the scenarios of a HipBatch: batch.working_sets, batch.solution_jacobians, batch.bound_jacobians.
 """
 import numpy as np
@@ -309,6 +317,44 @@ def solution_sensitivity(model_or_opt, fm, x, lam, row_state, bound_state, dc, m
     try:
         opt.eval_setup(fm)
         return opt.solution_sensitivity(x, lam, row_state, bound_state, dc, max_iter, rtol)
+    finally:
+        opt.close()
+
+
+def model_cross_t(fm, x, lam, vx, vl):
+    """out [n_dpar] of the host twin of asm_eval_data_cross_t for the FunctionModel `fm`: the block's data_cross_t with the block's part
+    of lam and vl (its rows follow the function store's) and the model's sense scale; empty without an NLP block."""
+    if fm.nlp is None:
+        return np.zeros(0)
+    if getattr(fm.nlp, "data_cross_t", None) is None:
+        raise ValueError("the model's NLP block has no data derivatives")
+    off = fm.nlp_constraint_offset
+    return np.asarray(fm.nlp.data_cross_t(np.asarray(x, float), np.asarray(lam, float)[off:], np.asarray(vx, float), np.asarray(vl, float)[off:],
+                                          fm.objective_scale), float)
+
+
+def adjoint_reference(fm, x, lam, row_state, bound_state, gx, gl):
+    """(out [n_dpar], dbound [m], ax [n], al [m]) for a function with gradients gx, gl at the solution (x, lam) with its working set:
+    the adjoint state from the dense kkt_reference(ru = -gx, rw = gl), out = model_cross_t(vx = -ax, vl = al), dbound = -al on the
+    working rows and 0 elsewhere."""
+    gx, gl = np.asarray(gx, float), np.asarray(gl, float)
+    ax, al, _ = kkt_reference(fm, x, lam, row_state, bound_state, -gx, gl)
+    dbound = np.where(np.asarray(row_state) == 1, -al, 0.0)
+    return model_cross_t(fm, x, lam, -ax, al), dbound, ax, al
+
+
+def solution_adjoint(model_or_opt, fm, x, lam, row_state, bound_state, gx, gl, max_iter=None, rtol=None):
+    """(out, dbound, ax, al, info) of asm_solution_adjoint for the FunctionModel `fm` at the solution (x, lam) with the working set
+    given: the gradient of a function phi(x*, lam*) with gradients (gx, gl) with respect to every constant of the block's data and
+    every row bound, from one KKT solve.  `model_or_opt` as for solution_sensitivity."""
+    from .subproblem import HipSubOptimizer, QpData
+    if isinstance(model_or_opt, HipSubOptimizer):
+        return model_or_opt.solution_adjoint(x, lam, row_state, bound_state, gx, gl, max_iter, rtol)
+    mdl = model_or_opt
+    opt = HipSubOptimizer(QpData(np.zeros(mdl.n), 0.0, np.zeros(len(mdl.j_row)), np.zeros(mdl.m), mdl.g_L, mdl.g_U, mdl.x_L, mdl.x_U), mdl.j_row, mdl.j_col)
+    try:
+        opt.eval_setup(fm)
+        return opt.solution_adjoint(x, lam, row_state, bound_state, gx, gl, max_iter, rtol)
     finally:
         opt.close()
 

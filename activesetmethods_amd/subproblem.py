@@ -214,6 +214,7 @@ class HipSubOptimizer:
             rows, nnz = fm.nlp.m, len(fm.nlp.rows)
             ipar, dpar = np.ascontiguousarray(ipar, np.int64), np.ascontiguousarray(dpar, np.float64)
         self._ev_keep = (fl, ipar, dpar)
+        self._ev_nd = len(dpar) if kind else 0             # n_dpar as the library counts it: none without an NLP block
         a = lambda k: fl[k]
         self._check(self._lib.asm_eval_setup(self._h, fl["n_rows"], _lib.i64ptr(a("aff_ptr")), _lib.i64ptr(a("aff_var")), _lib.dptr(a("aff_coef")),
                                              _lib.i64ptr(a("quad_ptr")), _lib.i64ptr(a("q_v1")), _lib.i64ptr(a("q_v2")), _lib.dptr(a("q_coef")),
@@ -428,6 +429,47 @@ class HipSubOptimizer:
         self._check(self._lib.asm_bound_sensitivity_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.i32ptr(rows),
                                                           None if delta is None else _lib.dptr(delta), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return DX, DLAM[:, :self.m], DZ, list(infos)
+
+    # ------------------------------------------------------------------ adjoint sensitivities (include/asm_hip.h: "Adjoint solution sensitivities")
+    def data_cross_t(self, x, lam, vx, vl):
+        """out [n_dpar] of asm_eval_data_cross_t: out[c] = vx' d/d dpar[c] (grad_x (f - lam' g)) + vl' d g / d dpar[c] for weights vx [n],
+        vl [m] - for every direction dc, dc' out = vx' u + vl' w with (u, w) = data_cross(x, lam, dc).  Expression blocks and the block
+        kernels with derivatives."""
+        nd = getattr(self, "_ev_nd", 0)
+        x, lam, vx, vl = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(vx, self.n, "vx"), self._vec(vl, self.m, "vl")
+        out = np.empty(max(nd, 1))
+        self._check(self._lib.asm_eval_data_cross_t(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(vx), _lib.dptr(vl), _lib.dptr(out)))
+        return out[:nd]
+
+    def solution_adjoint(self, x, lam, row_state, bound_state, gx, gl, max_iter=None, rtol=None):
+        """(out, dbound, ax, al, info) of asm_solution_adjoint for a function phi(x*, lam*) with gradients gx [n], gl [m], on the working
+        set given: out [n_dpar] = d phi / d dpar, dbound [m] = d phi / d(bound of row i) (0 outside the working set), (ax, al) the adjoint
+        state kkt_solve(ru = -gx, rw = gl), info the solve's asm_kkt_info.  One KKT solve whatever n_dpar."""
+        nd = getattr(self, "_ev_nd", 0)
+        x, lam, gx, gl = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(gx, self.n, "gx"), self._vec(gl, self.m, "gl")
+        rs, bs = self._states(row_state, bound_state)
+        out, dbound, ax, al, info = np.empty(max(nd, 1)), np.empty(max(self.m, 1)), np.empty(self.n), np.empty(max(self.m, 1)), _lib.KktInfo()
+        self._check(self._lib.asm_solution_adjoint(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), _lib.dptr(gx), _lib.dptr(gl),
+                                                   self._kkt_params(max_iter, rtol), _lib.dptr(out), _lib.dptr(dbound), _lib.dptr(ax), _lib.dptr(al), C.byref(info)))
+        return out[:nd], dbound[:self.m], ax, al[:self.m], info
+
+    def solution_adjoint_multi(self, x, lam, row_state, bound_state, GX, GL, max_iter=None, rtol=None):
+        """(OUT, DBOUND, AX, AL, infos) of asm_solution_adjoint_multi: solution_adjoint for the nrhs functions whose gradients are the rows
+        of GX [nrhs x n] and GL [nrhs x m], on one factor; row c of OUT [nrhs x n_dpar], DBOUND, AL [nrhs x m], AX [nrhs x n] and infos[c]
+        answer row c."""
+        nd = getattr(self, "_ev_nd", 0)
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_params(max_iter, rtol)
+        GX = self._mat(GX, self.n, "GX")
+        GL = self._mat(GL, self.m, "GL", GX.shape[0])
+        rs, bs = self._states(row_state, bound_state)
+        nrhs = GX.shape[0]
+        OUT, DBOUND, AL = np.empty((nrhs, max(nd, 1))), np.empty((nrhs, max(self.m, 1))), np.empty((nrhs, max(self.m, 1)))
+        AX, infos = np.empty((nrhs, self.n)), (_lib.KktInfo * nrhs)()
+        # (the library's matrices are packed: nrhs x n_dpar and nrhs x m, so a padded column is given only when the true width is 0)
+        self._check(self._lib.asm_solution_adjoint_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(GX), _lib.dptr(GL),
+                                                         par, _lib.dptr(OUT), _lib.dptr(DBOUND), _lib.dptr(AX), _lib.dptr(AL), infos))
+        return OUT[:, :nd], DBOUND[:, :self.m], AX, AL[:, :self.m], list(infos)
 
     @staticmethod
     def _kkt_step_params(max_iter, rtol, normal_share):

@@ -493,6 +493,63 @@ int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* la
                                 int32_t nrhs, const int32_t* rows, const double* delta /* [nrhs], or NULL: 1.0 */, const asm_kkt_params* par,
                                 double* DX, double* DLAM, double* DZ, asm_kkt_info* info);
 
+/* ---- Adjoint solution sensitivities: the gradient of one function of the solution with respect to all data, from one KKT solve.
+ * The forward entries answer "how do x* and lambda* move along one direction dc of the data" at one KKT right-hand side per direction.  The
+ * reverse question - given phi(x*, lambda*) with gradients gx [n] and gl [m], what is d phi / d dpar[c] for every c - needs one solve,
+ * because the KKT matrix of the working set is symmetric: with u_k = d/d c_k (grad_x L), w_k = d g / d c_k and M = [H_FF, -A'; -A, 0],
+ * the forward sensitivity is (dx, dlam) = M^-1 (-u_k, w_k), so gx'dx + gl'dlam = (M^-1 (gx, gl))' (-u_k, w_k).
+ *   1. adjoint state: (ax, al) = asm_kkt_solve(ru = -gx, rw = gl), no dz; ax is zero on B and al outside W, as that solve guarantees.
+ *   2. d phi / d dpar = asm_eval_data_cross_t(vx = -ax, vl = al), the transposed cross derivative below.
+ *   3. d phi / d bound_i = -al_i for a working row i, 0.0 for every other row: the recipe "ru = 0, rw_i = -delta" read backwards.
+ * Weights on the bound multipliers z and derivatives with respect to variable bounds are not part of these entries.
+ * Transposed cross derivatives.  asm_eval_data_cross_t: for weights vx [n], vl [m] at (x, lambda),
+ *   out[c] = vx' d/d dpar[c] (grad_x L) + vl' d g / d dpar[c] = d/d dpar[c] [ D_vx L(x, lambda; dpar) + vl' g(x; dpar) ],   c < n_dpar,
+ * L = f - lambda' g and D_vx the directional derivative along vx in x.  Rows of the function store contribute nothing.  For every dc,
+ * dc' out = vx' u + vl' w with (u, w) of asm_eval_data_cross(dc).  Kinds, errors and refusals are asm_eval_data_cross's (kinds 3, 4, 5;
+ * ASM_ERR_STATE before asm_eval_setup; kinds 0, 1, 2 and null pointers ASM_ERR_ARG); the inputs of the next LP are not touched.  The
+ * workspace ([lam | vx | vl] and n_dpar outputs per column, one column, ASM_KKT_CHUNK from the first multi call on) is made by the first
+ * call.  No fused multiply-add, no atomics; every written operation is one rounding, left to right, every sum in an order fixed by the model:
+ *   expression block (kind 3): the forward-over-reverse sweep of the Hessian and of asm_eval_data_cross with the other seed - a VAR node
+ *     of variable j has the tangent vx[j], a CONST node 0 - and the formulas of "Hessian of the Lagrangian", 2.  A CONST exponent of POW
+ *     stays out of the sweep, as in asm_eval_data_cross: its occurrence is 0.  One thread per row or term.  In the reverse pass a CONST
+ *     node with adjoint adj and adjoint tangent tadj yields one occurrence: for a node of block row r
+ *       (-lambda[n_rows + r]) * tadj + vl[n_rows + r] * adj        (two products, one sum)
+ *     and for a node of a term objective_scale * tadj.  out[c] sums the occurrences of dpar[c] in the list order of
+ *     asm_eval_data_gradient, from 0.0.  A tape without a CONST node: nothing is launched, out is all zero (empty for n_dpar = 0).  With
+ *     ADD..POWI, ABS, MIN and MAX only, device and host twin (nlexpr.py: ExprBlock.data_cross_t) agree bit for bit.
+ *   Ohm's-law block (kind 4): per branch l, with vf, vt, d, cs, sn, vv and the basis values vf2, vt2, vvc, vvs of the data gradient, l0..l3
+ *     and v0..v3 the entries of lambda and vl on its rows pfr, qfr, pto, qto, dvf = vx[vm_f], dvt = vx[vm_t], dd = vx[va_f] - vx[va_t]:
+ *       tvv = dvf*vt + vf*dvt    tvf2 = 2*(vf*dvf)    tvt2 = 2*(vt*dvt)    tvvc = tvv*cs - vvs*dd    tvvs = tvv*sn + vvc*dd
+ *     and out[q n_branch + l], q = 0..7, is the data gradient's pattern with (lambda, derivative) minus that with (vl, value):
+ *       l0*tvf2 - v0*vf2    l1*tvf2 - v1*vf2    l2*tvt2 - v2*vt2    l3*tvt2 - v3*vt2
+ *       (l0*tvvc + l1*tvvs) - (v0*vvc + v1*vvs)        (l0*tvvs - l1*tvvc) - (v0*vvs - v1*vvc)
+ *       (l2*tvvc - l3*tvvs) - (v2*vvc - v3*vvs)        (-(l2*tvvs) - l3*tvvc) - (-(v2*vvs) - v3*vvc)
+ *     One thread per (branch, column).  Device and host twin (acopf.py: _ohm_data_twins) differ at most in the last bits of sin and cos.
+ *   dense quadratic block (kind 5): one thread per entry (i, j) and column, li = lambda[n_rows + i], vi = vl[n_rows + i]:
+ *       out[i n + j] = (-li)*vx_j + vi*x_j        out[m_blk n + i n + j] = (-li)*(x_j*vx_j) + vi*(0.5*(x_j*x_j))
+ *     bit-identical to the host twin (problems.py).
+ * asm_solution_adjoint: steps 1 to 3 - the solve through asm_kkt_solve's single-column back end, then asm_eval_data_cross_t on (-ax, al):
+ * out equals that call on its own bit for bit.  out [n_dpar]; dbound [m], ax [n] and al [m] may be NULL.  info is the solve's; a status
+ * other than 0 is a result, not an error, and the outputs then come from the iterate reached.  par as for asm_kkt_solve.  A derivative
+ * entry like asm_solution_sensitivity: the exact Hessian whatever asm_hessian_set_type chose, and that entry's refusals - but for the
+ * function store alone (nlp_kind 0), which the adjoint entries serve: there is no data and out is empty (n_dpar = 0, out may be NULL),
+ * while dbound, ax and al need no data derivative.
+ * asm_solution_adjoint_multi: nrhs functions at once, one per row of GX [nrhs x n] and GL [nrhs x m]; OUT nrhs x n_dpar, DBOUND and AL
+ * nrhs x m, AX nrhs x n (DBOUND, AX, AL may be NULL), info [nrhs].  The solve is asm_kkt_solve_multi's - one factor, chunks of
+ * ASM_KKT_CHUNK columns in lockstep - and the transposed sweep runs per chunk: one upload of the chunk's weights, one launch for all its
+ * columns (kinds 4 and 5, the column in grid.y) or one launch pair per column (kind 3), one read-back.  Column independence holds as for
+ * the other multi entries, bit for bit; against asm_solution_adjoint the agreement is to tolerance (the two back ends).  nrhs < 1:
+ * ASM_ERR_ARG; validity and refusals are asm_solution_sensitivity_multi's.  The staging of a chunk is ASM_KKT_CHUNK x (n + n_dpar)
+ * doubles.  Both KKT forms serve the entries: they add nothing form-specific. */
+int asm_eval_data_cross_t(asm_handle* h, const double* x, const double* lambda, const double* vx, const double* vl, double* out);
+int asm_solution_adjoint(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                         const double* gx, const double* gl, const asm_kkt_params* par, double* out /* [n_dpar] */,
+                         double* dbound /* [m], may be NULL */, double* ax /* [n], may be NULL */, double* al /* [m], may be NULL */,
+                         asm_kkt_info* info);
+int asm_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                               int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par, double* OUT /* nrhs x n_dpar */,
+                               double* DBOUND, double* AX, double* AL, asm_kkt_info* info);
+
 /* ---- Trust-region step on the working set: Byrd-Omojokun with Steihaug-Toint truncation.
  * asm_kkt_step is asm_kkt_solve with an l2 radius: it minimises the model ru'dx + 1/2 dx'H dx over A dx_F = -theta rw_W, dx_B = 0,
  * ||dx||_2 <= radius - a normal step that may use only normal_share of the radius, then projected conjugate gradients that walk to the
@@ -904,6 +961,14 @@ int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, c
                                 const int32_t* bound_state, int32_t nrhs, const int32_t* rows /* [nrhs], shared */,
                                 const double* delta /* [nrhs] or NULL: 1.0, shared */, const asm_kkt_params* par, double* DX, double* DLAM,
                                 double* DZ, asm_kkt_info* info);
+/* asm_solution_adjoint_multi with a leading scenario dimension on every array: GX, AX n_scen x nrhs x n, GL, DBOUND, AL n_scen x nrhs x m,
+ * OUT n_scen x nrhs x n_dpar, info n_scen x nrhs (DBOUND, AX, AL may be NULL).  Everything said above holds: each scenario runs with its
+ * row of the scenario data table, n_scen may exceed the slot count, the solves run in the batch's KKT form, the workspaces - the transposed
+ * sweep's too - are made before the fibers start, and scenario s is bit-identical to asm_solution_adjoint_multi on a fresh handle with that
+ * scenario's data.  Errors as for asm_batch_solution_sensitivity. */
+int asm_batch_solution_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                               const int32_t* bound_state, int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par,
+                               double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
