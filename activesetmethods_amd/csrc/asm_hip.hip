@@ -241,6 +241,8 @@ struct FacBuf {
                                     // operation stops `band` rows below the panel's last column
 };
 
+// the lockstep rounds of a KKT call, summed over its chunks, and the last active-column word it read
+struct KktCounters { int64_t rounds = 0; int last_active = 0; };
 // The buffers of the KKT solve on a working set, all in the evaluator's pool and made where first needed after asm_eval_setup (kk_prepare,
 // kk_work); they go with the evaluator (EvalState).
 struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` columns (0: not made): 1 for asm_kkt_solve, KKM_CW for the multi entries
@@ -443,8 +445,7 @@ struct EvalState {
     double *d_ct_in = nullptr, *d_ct_out = nullptr, *h_ct = nullptr;
     bool ohm_vars_ok = true;        // kind 4: every variable the block names is inside [0, n) (checked at asm_eval_setup, refused by the data entries)
     KktBufs kk;                     // KKT solve on a working set (asm_kkt_solve and the multi entries)
-    int64_t kkm_rounds = 0;         // test seam: lockstep rounds of the last multi call, summed over its chunks; the last active-column word it read
-    int kkm_last_active = 0;
+    KktCounters kkm;                // test seam: the counters of the last multi call
     BufPool mem;                    // declared last: it goes first, while the fields it nulls are alive
 };
 
@@ -5161,8 +5162,8 @@ bool kkt_hess_lm(const asm_handle* h, const char* who) {
 // ---- the KKT solve on a working set (include/asm_hip.h, "The KKT solve on a working set" and "Many right-hand sides on one factor"): one
 // set-up of the face (KktFace, steps 1 and 2), one driver of steps 3 to 6 on blocks of columns (kkt_columns) and, behind KktOps, the
 // ways to multiply and solve: KktOneColumn for asm_kkt_solve and asm_solution_sensitivity, KktBlock for the multi entries, and KktSparse
-// for both where the handle's form is ASM_KKT_SPARSE (asm_kkt_set_form).  The entry point and the form choose, not nrhs: a column's bits
-// do not depend on the number of columns beside it.
+// for both where the handle's form is ASM_KKT_SPARSE (asm_kkt_set_form).  The entry point and the form choose (kkt_run), not nrhs: a
+// column's bits do not depend on the number of columns beside it.  A call is described by values: KktPoint, KktRhs, KktOut, KktInfoSink, KktTrust.
 static_assert(KKM_CW == ASM_KKT_CHUNK && KKM_CW % 32 == 0 && KKM_SCAL > KKM_ITERS, "the chunk width of the header is the kernels'");
 namespace {
 // once per asm_eval_setup, at the first KKT solve: what steps 1 and 2 fill, sized for every working set the problem admits, and the
@@ -5664,32 +5665,155 @@ struct KktSparse final : KktOps {
     void jt_dlam(const double* dlw, const double*, double* jtl, int cols) override { at(dlw, nullptr, jtl, cols); }
 };
 
-// Steps 3 to 6 for nrhs columns in chunks of the work area's capacity.  sens false: the rows of RU, RW are the right-hand sides;
-// otherwise the rows of DC are directions of the data and the cross-derivative sweep makes each column's right-hand sides on the
-// device (lambda: its multipliers); bd.rows != nullptr: bound sensitivities, the right-hand sides made by k_kktm_bound_rhs (KktBound).
-// The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product and substitution is ops'.
-// rounds, last_active: the lockstep rounds of the call and the last active-column word read.
-// The trust-region step (asm_kkt_step, asm_kkt_step_multi): tr.radius != nullptr holds a radius per column, and the answers go to tr.info
-// instead of info.  The same launches with the trust-region forms of k_kktm_cg_curv, k_kktm_cg_dir and k_kktm_finish, and k_kktm_normal
-// once per chunk after the normal step.
-// Bound sensitivities (asm_bound_sensitivity_multi): rows != nullptr holds a row per column, and column c is ru = 0, rw[rows[c]] = -delta[c]
-// (delta == nullptr: -1.0).  RU and RW are not read: k_kktm_bound_rhs makes a chunk's right-hand sides on the device from its rows and
-// deltas, 12 bytes per column in one upload - no n- or m-long vector is staged or uploaded.
-struct KktBound {
-    const int32_t* rows = nullptr;       // nrhs row indices in [0, m)
-    const double* delta = nullptr;       // nrhs moves, or nullptr
+// ---- what travels together through the KKT entries: plain values, nothing owned
+// The point of a call and its sets.  at(): scenario sc's rows of arrays with a leading scenario dimension (no rows, no arrays over them)
+struct KktPoint {
+    const double *x = nullptr, *lambda = nullptr;
+    const int32_t *row_state = nullptr, *bound_state = nullptr;
+    KktPoint at(int64_t sc, int64_t n, int64_t m) const { return {x + sc * n, m > 0 ? lambda + sc * m : nullptr, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n}; }
 };
+// Where the columns' answers go, a row per column (DZ may be absent).  at(): the rows from column o on
+struct KktOut {
+    double *DX = nullptr, *DLAM = nullptr, *DZ = nullptr;
+    KktOut at(int64_t o, int64_t n, int64_t m) const { return {DX + o * n, m > 0 ? DLAM + o * m : nullptr, DZ ? DZ + o * n : nullptr}; }
+};
+// What the columns of a call are - one of three, made by the constructor of its name:
+//   given(RU, RW)        the rows of RU, RW are the right-hand sides (asm_kkt_solve(_multi), the step entries, the adjoint states)
+//   data(DC)             the rows of DC are directions of the data: the cross-derivative sweep makes each column's right-hand sides on
+//                        the device (asm_solution_sensitivity_multi)
+//   bound(rows, delta)   a row in [0, m) per column: column c is ru = 0, rw[rows[c]] = -delta[c] (delta == nullptr: -1.0), made on the device
+//                        by k_kktm_bound_rhs from 12 bytes per column - no n- or m-long vector is staged (asm_bound_sensitivity_multi)
+struct KktRhs {
+    enum Kind { GIVEN, DATA, BOUND } kind;
+    const double *RU = nullptr, *RW = nullptr, *DC = nullptr, *delta = nullptr;
+    const int32_t* rows = nullptr;
+    static KktRhs given(const double* RU, const double* RW) { KktRhs r(GIVEN); r.RU = RU; r.RW = RW; return r; }
+    static KktRhs data(const double* DC) { KktRhs r(DATA); r.DC = DC; return r; }
+    static KktRhs bound(const int32_t* rows, const double* delta) { KktRhs r(BOUND); r.rows = rows; r.delta = delta; return r; }
+    bool derivative() const { return kind != GIVEN; }      // a derivative entry: the exact Hessian whatever the handle's type
+    // scenario sc's n_col columns of a batch call; dc_stride: doubles from one scenario's directions to the next, 0 when they are shared
+    // (the rows and moves of BOUND always are)
+    KktRhs at(int64_t sc, int64_t n_col, int64_t n, int64_t m, int64_t dc_stride) const {
+        KktRhs r = *this;
+        if (kind == GIVEN) { r.RU = RU + sc * n_col * n; r.RW = m > 0 ? RW + sc * n_col * m : nullptr; }
+        if (kind == DATA && DC) r.DC = DC + sc * dc_stride;
+        return r;
+    }
+private:
+    explicit KktRhs(Kind k) : kind(k) {}
+};
+// Where a column's info goes: asm_kkt_info, or asm_kkt_step_info with the fields of the trust-region step
+struct KktInfoSink {
+    asm_kkt_info* plain = nullptr;
+    asm_kkt_step_info* step = nullptr;
+    KktInfoSink(asm_kkt_info* p) : plain(p) {}
+    KktInfoSink(asm_kkt_step_info* s) : step(s) {}
+    bool null() const { return !plain && !step; }
+};
+// The trust-region step (asm_kkt_step, asm_kkt_step_multi): a radius per column, each > 0 (+inf: no region), and the share of it the
+// normal step may use.  The same launches with the trust-region forms of k_kktm_cg_curv, k_kktm_cg_dir and k_kktm_finish, and
+// k_kktm_normal once per chunk after the normal step.
 struct KktTrust {
-    const double* radius = nullptr;      // nrhs radii, each > 0 (+inf: no region)
-    double share = 0.8;                  // the share of the radius the normal step may use
-    asm_kkt_step_info* info = nullptr;
+    bool on = false;
+    const double* radius = nullptr;
+    double share = 0.8;
+    static KktTrust step(const double* radius, double share) { return {true, radius, share}; }
+    void check(const std::string& me, int32_t nrhs) const {      // the refusals of the step entries, after those every entry shares
+        if (!on) return;
+        if (!radius) throw std::invalid_argument(me + ": null pointer");
+        for (int32_t c = 0; c < nrhs; ++c)
+            if (!(radius[c] > 0.0)) throw std::invalid_argument(me + ": a radius is not > 0");
+        if (!(share > 0.0 && share <= 1.0)) throw std::invalid_argument(me + ": normal_share outside (0, 1]");
+    }
 };
-void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, const double* RU, const double* RW, const double* DC, bool sens, const double* lambda, double* DX,
-                 double* DLAM, double* DZ, asm_kkt_info* info, int64_t& rounds, int& last_active, const KktTrust& tr = KktTrust(), const KktBound& bd = KktBound()) {
+// Step 3 for the chunk of `cols` columns from column c0 on: its right-hand sides into the blocks b_ru (over the variables) and rww (over
+// the working rows), by the way of rhs.kind.  The staging area is [ru block | rw block | directions]; the first chunk of a DATA call
+// uploads the multipliers of the cross-derivative sweep, once.
+void kkt_stage_rhs(asm_handle* h, const KktFace& f, KktWork& w, const KktRhs& rhs, const double* lambda, const KktTrust& tr, int64_t c0, int cols, double* b_ru, double* rww) {
+    const hipStream_t s = h->stream;
+    const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn, ldT = h->ev->kk.ldT, cap = w.cap, nW = f.nW;
+    double* st = w.stage;
+    switch (rhs.kind) {
+    case KktRhs::BOUND: {
+        // [delta | rows] of the chunk's columns in the (unused) staging rows of ru, one upload, one launch
+        int* hr = reinterpret_cast<int*>(st + cols);
+        int* dr = reinterpret_cast<int*>(w.bnd + cols);
+        if (rhs.delta) std::memcpy(st, rhs.delta + c0, cols * sizeof(double));
+        for (int c = 0; c < cols; ++c) hr[c] = rhs.rows[c0 + c];
+        HIPCHK(asmb::copy_async(w.bnd, st, cols * (sizeof(double) + sizeof(int)), hipMemcpyHostToDevice, s));
+        asmb::launch(k_kktm_bound_rhs, dim3(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols), dim3(256), s, (const int*)dr, rhs.delta ? (const double*)w.bnd : (const double*)nullptr,
+                     f.wrow, nW, b_ru, ldn, rww, ldT);
+        return;
+    }
+    case KktRhs::GIVEN: {
+        for (int c = 0; c < cols; ++c) {
+            const double *u = rhs.RU + (c0 + c) * n, *rw = rhs.RW ? rhs.RW + (c0 + c) * m : nullptr;
+            double *du = st + (int64_t)c * ldn, *dw = st + cap * ldn + (int64_t)c * ldT;
+            std::memcpy(du, u, n * sizeof(double));
+            for (int64_t j = n; j < ldn; ++j) du[j] = 0.0;
+            for (int64_t q = 0; q < ldT; ++q) dw[q] = q < nW ? rw[f.wl[q]] : 0.0;
+        }
+        HIPCHK(asmb::copy_async(b_ru, st, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(asmb::copy_async(rww, st + cap * ldn, (int64_t)cols * ldT * sizeof(double), hipMemcpyHostToDevice, s));
+        if (tr.on) {      // (the staging rows of the directions are free: no sensitivity entry has a radius)
+            double* hr = st + cap * (ldn + ldT);
+            std::memcpy(hr, tr.radius + c0, cols * sizeof(double));
+            HIPCHK(asmb::copy_async(w.rad, hr, cols * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+        return;
+    }
+    case KktRhs::DATA:
+        break;
+    }
+    const int64_t nd = h->ev->n_dpar;
+    double* hd = st + cap * (ldn + ldT);
+    if (nlp_block_derivs(h->ev->nlp_kind) && nd > 0) {
+        // kinds 4 and 5: the column kernels make a chunk's right-hand sides at once, from the block's multipliers uploaded once
+        const int64_t R = h->ev->nlp_rows;
+        if (c0 == 0) {
+            cx_prepare(h, KKM_CW);
+            std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, R * sizeof(double));
+            HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, R * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+        // the chunk's directions in the staging rows, one upload, then one launch set for all its columns
+        std::memcpy(hd, rhs.DC + c0 * nd, (int64_t)cols * nd * sizeof(double));
+        HIPCHK(asmb::copy_async(h->ev->d_cx_in + R, hd, (int64_t)cols * nd * sizeof(double), hipMemcpyHostToDevice, s));
+        cx_launch_block(h, cols);
+        asmb::launch(k_kktm_cross_rhs_cols, dim3(asmb::blocks(std::max(n, nW)).x, (unsigned)cols), dim3(256), s, (const double*)h->ev->d_cx_out, n + R, n,
+                     (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru, ldn, rww, ldT);
+    } else if (h->ev->d_cocc != nullptr) {
+        const ExprTape& X = h->ev->X;
+        if (c0 == 0) {      // the multipliers of the expression rows, once
+            cx_prepare(h);
+            if (X.R > 0) {
+                std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, X.R * sizeof(double));
+                HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
+            }
+        }
+        // one sweep per direction, no synchronisation between them: every direction has its own staging row
+        for (int c = 0; c < cols; ++c) {
+            std::memcpy(hd + (int64_t)c * nd, rhs.DC + (c0 + c) * nd, nd * sizeof(double));
+            HIPCHK(asmb::copy_async(h->ev->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
+            asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->ev->cx_C, h->ev->d_xt, h->ev->d_cx_in + X.R, h->ev->d_cx_in, h->ev->F.objective_scale, h->ev->d_cx_out + n);
+            asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->ev->cx_C, n, h->ev->d_cx_out);
+            asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->ev->d_cx_out, n, (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru + (int64_t)c * ldn,
+                         rww + (int64_t)c * ldT);
+        }
+    } else {      // no CONST node: nothing depends on the data, u = w = 0
+        HIPCHK(asmb::fill_async(b_ru, 0, cap * ldn * sizeof(double), s));
+        HIPCHK(asmb::fill_async(rww, 0, cap * ldT * sizeof(double), s));
+    }
+}
+// Steps 3 to 6 for the nrhs columns that `rhs` describes, in chunks of the work area's capacity (lambda: the multipliers of the point, read
+// by the cross-derivative sweeps).  The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product
+// and substitution is ops'.  The answers go to `out`, a column's info to `sink` - the one place below that writes it - with the fields
+// of the step where `tr` is on.
+void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, const KktRhs& rhs, const double* lambda, const KktOut& out, const KktInfoSink& sink,
+                 const KktTrust& tr, KktCounters& cnt) {
     const KktBufs& K = h->ev->kk;
     KktWork& w = ops.w;
     const hipStream_t s = h->stream;
-    const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW, nd = sens ? h->ev->n_dpar : 0;
+    const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn, Mp = std::max<int64_t>(h->sk->Mp, 32), ldT = K.ldT, cap = w.cap, nW = f.nW;
     const double* const mask = f.mask;
     auto vblock = [&](int k) { return w.vec + (int64_t)k * cap * ldn; };
     auto rblock = [&](int k) { return w.row + (int64_t)k * cap * ldT; };      // (block 2 is ops.spare)
@@ -5699,29 +5823,11 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     double* const dlf = w.dlf;
     double* const scal = K.scal;
     const KktMulti R{K.part, K.cnt, scal, K.act, h->sk->d_hscal, h->sk->d_hseq};
-    // kinds 4 and 5: the column kernels make a chunk's right-hand sides at once, from the block's multipliers uploaded once
-    const bool cross_block = sens && nlp_block_derivs(h->ev->nlp_kind) && nd > 0;
-    if (cross_block) {
-        cx_prepare(h, KKM_CW);
-        const int64_t R = h->ev->nlp_rows;
-        std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, R * sizeof(double));
-        HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, R * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    const bool cross = sens && !cross_block && h->ev->d_cocc != nullptr;      // (no CONST node: nothing depends on the data, u = w = 0)
-    if (cross) {      // the multipliers of the expression rows, once
-        cx_prepare(h);
-        const ExprTape& X = h->ev->X;
-        if (X.R > 0) {
-            std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, X.R * sizeof(double));
-            HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-    }
     const dim3 gl = asmb::blocks(ldn);
     const unsigned gred = (unsigned)std::min<int64_t>(gl.x, KK_MAXWG);
-    const bool run_cg = f.nF > nW, trust = tr.radius != nullptr;
+    const bool run_cg = f.nF > nW, trust = tr.on;
     int dropped = 0;
-    rounds = 0;
-    last_active = 0;
+    cnt = {};
     for (int64_t c0 = 0; c0 < nrhs; c0 += cap) {
         const int cols = (int)std::min<int64_t>(cap, nrhs - c0);
         const dim3 glc(gl.x, (unsigned)cols), grc(asmb::blocks(f.nWg).x, (unsigned)cols), gredc(gred, (unsigned)cols);
@@ -5743,55 +5849,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             axpby(1.0, v, -1.0, tt, sc, v);
         };
         // 3. the right-hand sides of the chunk
-        if (bd.rows) {
-            // [delta | rows] of the chunk's columns in the (unused) staging rows of ru, one upload, one launch
-            int* hr = reinterpret_cast<int*>(st + cols);
-            int* dr = reinterpret_cast<int*>(w.bnd + cols);
-            if (bd.delta) std::memcpy(st, bd.delta + c0, cols * sizeof(double));
-            for (int c = 0; c < cols; ++c) hr[c] = bd.rows[c0 + c];
-            HIPCHK(asmb::copy_async(w.bnd, st, cols * (sizeof(double) + sizeof(int)), hipMemcpyHostToDevice, s));
-            asmb::launch(k_kktm_bound_rhs, dim3(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols), dim3(256), s, (const int*)dr, bd.delta ? (const double*)w.bnd : (const double*)nullptr,
-                         f.wrow, nW, b_ru, ldn, rww, ldT);
-        } else if (!sens) {
-            for (int c = 0; c < cols; ++c) {
-                const double *u = RU + (c0 + c) * n, *rw = RW ? RW + (c0 + c) * m : nullptr;
-                double *du = st + (int64_t)c * ldn, *dw = st + cap * ldn + (int64_t)c * ldT;
-                std::memcpy(du, u, n * sizeof(double));
-                for (int64_t j = n; j < ldn; ++j) du[j] = 0.0;
-                for (int64_t q = 0; q < ldT; ++q) dw[q] = q < nW ? rw[f.wl[q]] : 0.0;
-            }
-            HIPCHK(asmb::copy_async(b_ru, st, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
-            HIPCHK(asmb::copy_async(rww, st + cap * ldn, (int64_t)cols * ldT * sizeof(double), hipMemcpyHostToDevice, s));
-            if (trust) {      // (the staging rows of the directions are free: no sensitivity entry has a radius)
-                double* hr = st + cap * (ldn + ldT);
-                std::memcpy(hr, tr.radius + c0, cols * sizeof(double));
-                HIPCHK(asmb::copy_async(w.rad, hr, cols * sizeof(double), hipMemcpyHostToDevice, s));
-            }
-        } else if (cross_block) {
-            // the chunk's directions in the staging rows, one upload, then one launch set for all its columns
-            const int64_t R = h->ev->nlp_rows;
-            double* hd = st + cap * (ldn + ldT);
-            std::memcpy(hd, DC + c0 * nd, (int64_t)cols * nd * sizeof(double));
-            HIPCHK(asmb::copy_async(h->ev->d_cx_in + R, hd, (int64_t)cols * nd * sizeof(double), hipMemcpyHostToDevice, s));
-            cx_launch_block(h, cols);
-            asmb::launch(k_kktm_cross_rhs_cols, dim3(asmb::blocks(std::max(n, nW)).x, (unsigned)cols), dim3(256), s, (const double*)h->ev->d_cx_out, n + R, n,
-                         (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru, ldn, rww, ldT);
-        } else if (cross) {
-            // one sweep per direction, no synchronisation between them: every direction has its own staging row
-            const ExprTape& X = h->ev->X;
-            double* hd = st + cap * (ldn + ldT);
-            for (int c = 0; c < cols; ++c) {
-                std::memcpy(hd + (int64_t)c * nd, DC + (c0 + c) * nd, nd * sizeof(double));
-                HIPCHK(asmb::copy_async(h->ev->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
-                asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->ev->cx_C, h->ev->d_xt, h->ev->d_cx_in + X.R, h->ev->d_cx_in, h->ev->F.objective_scale, h->ev->d_cx_out + n);
-                asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->ev->cx_C, n, h->ev->d_cx_out);
-                asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->ev->d_cx_out, n, (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru + (int64_t)c * ldn,
-                             rww + (int64_t)c * ldT);
-            }
-        } else {
-            HIPCHK(asmb::fill_async(b_ru, 0, cap * ldn * sizeof(double), s));
-            HIPCHK(asmb::fill_async(rww, 0, cap * ldT * sizeof(double), s));
-        }
+        kkt_stage_rhs(h, f, w, rhs, lambda, tr, c0, cols, b_ru, rww);
         // particular solution dx0 = -A' S^-1 rw_W
         if (nW > 0) {
             normal_back(rww, tw);
@@ -5829,9 +5887,9 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
                 pub = pub_next(h);
                 asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 0, f.rtol, pub, (int)trust);
                 active = kk_read_scal(h, pub);
-                rounds += 1;
+                cnt.rounds += 1;
             }
-            last_active = active;
+            cnt.last_active = active;
         }
         // 5., 6. the solutions, their multipliers and residuals
         axpby(1.0, dx0, 1.0, cd, nullptr, ddx);
@@ -5862,9 +5920,9 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
         HIPCHK(asmb::sync(s));
         if (c0 == 0) dropped = *reinterpret_cast<const int*>(back + cap * (2 * ldn + Mp + KKM_SCAL));
         for (int c = 0; c < cols; ++c) {
-            std::memcpy(DX + (c0 + c) * n, back + (int64_t)c * ldn, n * sizeof(double));
-            if (DZ) std::memcpy(DZ + (c0 + c) * n, back + cap * ldn + (int64_t)c * ldn, n * sizeof(double));
-            if (m > 0) std::memcpy(DLAM + (c0 + c) * m, back + 2 * cap * ldn + (int64_t)c * Mp, m * sizeof(double));
+            std::memcpy(out.DX + (c0 + c) * n, back + (int64_t)c * ldn, n * sizeof(double));
+            if (out.DZ) std::memcpy(out.DZ + (c0 + c) * n, back + cap * ldn + (int64_t)c * ldn, n * sizeof(double));
+            if (m > 0) std::memcpy(out.DLAM + (c0 + c) * m, back + 2 * cap * ldn + (int64_t)c * Mp, m * sizeof(double));
             const double* sc = back + cap * (2 * ldn + Mp) + (int64_t)c * KKM_SCAL;
             // (without an iteration - a vertex - the column's stop code and count are not written: solved, no iteration)
             const int stop = run_cg ? (int)sc[KK_STOP] : 1;
@@ -5873,75 +5931,74 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
                 o.cg_iters = run_cg ? (int32_t)sc[KKM_ITERS] : 0; o.n_free = (int32_t)f.nF; o.n_rows = (int32_t)nW; o.dropped_pivots = dropped;
                 o.res_stat = sc[KK_RSTAT]; o.res_feas = sc[KK_RFEAS];
             };
-            if (trust) {
-                asm_kkt_step_info& o = tr.info[c0 + c];
+            if (sink.step) {
+                asm_kkt_step_info& o = sink.step[c0 + c];
                 shared_fields(o);
                 o.boundary = run_cg ? (int32_t)sc[KKM_BND] : 0;
                 o.theta = sc[KKM_THETA]; o.norm_normal = sc[KKM_NNORM]; o.norm_step = sc[KKM_NSTEP]; o.model = sc[KKM_MODEL];
             } else {
-                shared_fields(info[c0 + c]);
+                shared_fields(sink.plain[c0 + c]);
             }
         }
     }
     ops.dev.resolve_timing();      // (a batch slot records no events - its timing level stays 0, as for its LPs: nothing to read inside a fiber)
 }
+// The refusals the entries of the family share, under the entry's name `who`: per handle (kkt_run) and, on the calling thread, for a
+// scenario batch - which so refuses exactly what its fibers would.  out == nullptr: the adjoint entries, whose states are optional.
+void kkt_check_args(const std::string& who, int64_t m, int64_t nd, int32_t nrhs, const KktPoint& p, const KktRhs& rhs, const KktOut* out, const KktInfoSink& sink) {
+    if (nrhs < 1) throw std::invalid_argument(who + ": nrhs < 1");
+    bool null = !p.x || !p.bound_state || sink.null() || (m > 0 && (!p.lambda || !p.row_state));
+    if (out) null = null || !out->DX || (m > 0 && !out->DLAM);
+    if (rhs.kind == KktRhs::GIVEN) null = null || !rhs.RU || (m > 0 && !rhs.RW);
+    if (rhs.kind == KktRhs::DATA) null = null || (nd > 0 && !rhs.DC);
+    if (rhs.kind == KktRhs::BOUND) null = null || !rhs.rows;
+    if (null) throw std::invalid_argument(who + ": null pointer");
+    if (rhs.kind == KktRhs::BOUND)
+        for (int32_t c = 0; c < nrhs; ++c)
+            if (rhs.rows[c] < 0 || rhs.rows[c] >= m) throw std::invalid_argument(who + ": a row index outside [0, m)");
+}
+// Every per-handle entry of the family, under its name `who`: its refusals, the face, the back end, the columns, the round counters.
+// cap, the capacity of the work area - 1 (asm_kkt_solve, asm_kkt_step and what runs through them) or KKM_CW (the multi entries) - and
+// the form choose the back end, here and nowhere else.  Only a call with cap == KKM_CW leaves its counters on the handle
+// (asm_test_kkt_multi_rounds: the last multi call).  exact_only: a derivative entry with given columns (adjoint states, asm_solution_sensitivity).
+void kkt_run(asm_handle* h, const char* who, int64_t cap, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, const asm_kkt_params* par, const KktOut& out,
+             const KktInfoSink& sink, const KktTrust& tr = KktTrust(), bool exact_only = false) {
+    const std::string me(who);
+    const bool exact = rhs.derivative() || exact_only;
+    if (rhs.kind == KktRhs::DATA) cx_check(h, who);
+    if (exact) hs_check(h, who);
+    const bool lm = !exact && kkt_hess_lm(h, who);
+    kkt_check_args(me, h->sk->m, h->ev->n_dpar, nrhs, p, rhs, &out, sink);
+    tr.check(me, nrhs);
+    Dev dev(h);
+    const KktFace f(h, dev, me, p.x, p.lambda, p.row_state, p.bound_state, par, lm);
+    KktCounters own;
+    KktCounters& cnt = cap == KKM_CW ? h->ev->kkm : own;
+    auto columns = [&](KktOps&& ops) { kkt_columns(h, f, ops, nrhs, rhs, p.lambda, out, sink, tr, cnt); };
+    if (f.sparse) columns(KktSparse(h, dev, f, *kk_work(h, cap, true)));
+    else if (cap == 1) columns(KktOneColumn(h, dev, f, *kk_work(h, 1)));
+    else columns(KktBlock(h, dev, f, *kk_work(h, cap)));
+}
 }  // namespace
 
-static void do_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru,
-                         const double* rw, const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info, bool exact_only = false) {
-    // (asm_solution_sensitivity comes here too: a derivative entry, exact whatever the handle's type)
-    if (exact_only) hs_check(h, "asm_kkt_solve");
-    const bool lm = !exact_only && kkt_hess_lm(h, "asm_kkt_solve");
-    if (!x || !bound_state || !ru || !dx || !info || (h->sk->m > 0 && (!lambda || !row_state || !rw || !dlam))) throw std::invalid_argument("asm_kkt_solve: null pointer");
-    Dev dev(h);
-    const KktFace f(h, dev, "asm_kkt_solve", x, lambda, row_state, bound_state, par, lm);
-    int64_t rounds;
-    int last_active;
-    if (f.sparse) {
-        KktSparse ops(h, dev, f, *kk_work(h, 1, true));
-        kkt_columns(h, f, ops, 1, ru, rw, nullptr, false, lambda, dx, dlam, dz, info, rounds, last_active);
-    } else {
-        KktOneColumn ops(h, dev, f, *kk_work(h, 1));
-        kkt_columns(h, f, ops, 1, ru, rw, nullptr, false, lambda, dx, dlam, dz, info, rounds, last_active);
-    }
+// asm_kkt_solve; asm_solution_sensitivity comes here too (exact_only), with the column it made
+static void do_kkt_solve(asm_handle* h, const KktPoint& p, const double* ru, const double* rw, const asm_kkt_params* par, const KktOut& out, asm_kkt_info* info,
+                         bool exact_only = false) {
+    kkt_run(h, "asm_kkt_solve", 1, p, 1, KktRhs::given(ru, rw), par, out, info, KktTrust(), exact_only);
 }
-static void do_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
-                                    const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
+static void do_solution_sensitivity(asm_handle* h, const KktPoint& p, const double* dc, const asm_kkt_params* par, const KktOut& out, asm_kkt_info* info) {
     cx_check(h, "asm_solution_sensitivity");
-    if (!x || !bound_state || !dx || !info || (h->sk->m > 0 && (!lambda || !row_state || !dlam)) || (h->ev->n_dpar > 0 && !dc))
+    if (!p.x || !p.bound_state || !out.DX || !info || (h->sk->m > 0 && (!p.lambda || !p.row_state || !out.DLAM)) || (h->ev->n_dpar > 0 && !dc))
         throw std::invalid_argument("asm_solution_sensitivity: null pointer");
     std::vector<double> u((size_t)std::max<int64_t>(h->sk->n, 1)), w((size_t)std::max<int64_t>(h->sk->m, 1));
-    do_data_cross(h, x, lambda, dc, u.data(), w.data());
-    do_kkt_solve(h, x, lambda, row_state, bound_state, u.data(), w.data(), par, dx, dlam, dz, info, true);
+    do_data_cross(h, p.x, p.lambda, dc, u.data(), w.data());
+    do_kkt_solve(h, p, u.data(), w.data(), par, out, info, true);
 }
-// asm_kkt_solve_multi (sens false: the rows of RU, RW are the right-hand sides), asm_solution_sensitivity_multi (the rows of DC are
-// directions of the data) and asm_bound_sensitivity_multi (bd.rows: a row per column, RU and RW not read - a derivative entry like the
-// second, exact whatever the handle's type; exact_only: the adjoint entries, derivative entries too)
-static void do_kkt_solve_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
-                               const double* RU, const double* RW, const double* DC, bool sens, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
-                               asm_kkt_info* info, const KktBound& bd = KktBound(), bool exact_only = false) {
-    const std::string me(who);
-    const bool bound = bd.rows != nullptr;
-    if (sens) cx_check(h, who);
-    if (sens || bound || exact_only) hs_check(h, who);
-    const bool lm = !sens && !bound && !exact_only && kkt_hess_lm(h, who);
-    if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
-    if (!x || !bound_state || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
-    if (bound) {
-        for (int32_t c = 0; c < nrhs; ++c)
-            if (bd.rows[c] < 0 || bd.rows[c] >= h->sk->m) throw std::invalid_argument(me + ": a row index outside [0, m)");
-    } else if (sens ? (h->ev->n_dpar > 0 && !DC) : (!RU || (h->sk->m > 0 && !RW))) {
-        throw std::invalid_argument(me + ": null pointer");
-    }
-    Dev dev(h);
-    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par, lm);
-    if (f.sparse) {
-        KktSparse ops(h, dev, f, *kk_work(h, KKM_CW, true));
-        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active, KktTrust(), bd);
-    } else {
-        KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
-        kkt_columns(h, f, ops, nrhs, RU, RW, DC, sens, lambda, DX, DLAM, DZ, info, h->ev->kkm_rounds, h->ev->kkm_last_active, KktTrust(), bd);
-    }
+// The multi entries under the name `who`, for the per-handle call and for a batch fiber: asm_kkt_solve_multi (KktRhs::given),
+// asm_solution_sensitivity_multi (data) and asm_bound_sensitivity_multi (bound)
+static void do_kkt_solve_multi(asm_handle* h, const char* who, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, const asm_kkt_params* par, const KktOut& out,
+                               asm_kkt_info* info) {
+    kkt_run(h, who, KKM_CW, p, nrhs, rhs, par, out, info);
 }
 // ---- adjoint solution sensitivities (include/asm_hip.h, "Adjoint solution sensitivities"): per function the adjoint state (ax, al) =
 // asm_kkt_solve(ru = -gx, rw = gl), then out = the transposed cross derivative for the weights (-ax, al) and dbound_i = -al_i on the working
@@ -5952,80 +6009,59 @@ namespace {
 void adjoint_check(const asm_handle* h, const char* who) {
     if (ev_of(h, who).nlp_kind != 0) cx_check(h, who);
 }
+// the refusals of the adjoint entries, per handle and for a batch: those of the solve with the gradients as its columns, and OUT
+void adjoint_check_args(const std::string& who, int64_t m, int64_t nd, int32_t nrhs, const KktPoint& p, const double* GX, const double* GL, const double* OUT,
+                        asm_kkt_info* info) {
+    kkt_check_args(who, m, nd, nrhs, p, KktRhs::given(GX, GL), nullptr, info);
+    if (nd > 0 && !OUT) throw std::invalid_argument(who + ": null pointer");
+}
+// what the adjoint entries set up for ncol functions: ru = -GX, and buffers of their own for the adjoint states the caller does not take
+struct AdjointSetup {
+    std::vector<double> ru, sx, sl;
+    KktOut state;      // AX and AL, the caller's or the buffers here
+    AdjointSetup(int64_t ncol, int64_t n, int64_t m, const double* GX, double* AX, double* AL)
+        : ru((size_t)std::max<int64_t>(ncol * n, 1)), sx(AX ? 0 : ru.size()), sl(AL ? 0 : (size_t)std::max<int64_t>(ncol * m, 1)),
+          state{AX ? AX : sx.data(), AL ? AL : sl.data(), nullptr} {
+        for (int64_t q = 0; q < ncol * n; ++q) ru[q] = -GX[q];
+    }
+};
 void adjoint_dbound(const int32_t* row_state, int64_t m, int64_t ncol, const double* AL, double* DBOUND) {
     if (!DBOUND) return;
     for (int64_t c = 0; c < ncol; ++c)
         for (int64_t i = 0; i < m; ++i) DBOUND[c * m + i] = row_state[i] == 1 ? -AL[c * m + i] : 0.0;
 }
-// the multi entry on a handle, for the per-handle call and for a batch fiber: RU = -GX made by the caller, AX and AL not null
-void adjoint_multi(asm_handle* h, const char* who, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* RU,
-                   const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
-    do_kkt_solve_multi(h, who, x, lambda, row_state, bound_state, nrhs, RU, GL, nullptr, false, par, AX, AL, nullptr, info, KktBound(), true);
-    ct_columns(h, x, lambda, nrhs, AX, -1.0, AL, OUT, KKM_CW);
-    adjoint_dbound(row_state, h->sk->m, nrhs, AL, DBOUND);
+// what follows the checks and the set-up in every adjoint entry, per handle and in a batch fiber: the states by the solve `who` of
+// capacity cap on rhs = given(-GX, GL), exact whatever the handle's type, then the data derivatives and the bound gradients
+void adjoint_multi(asm_handle* h, const char* who, int64_t cap, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, const asm_kkt_params* par, double* OUT, double* DBOUND,
+                   const KktOut& state, asm_kkt_info* info) {
+    kkt_run(h, who, cap, p, nrhs, rhs, par, state, info, KktTrust(), true);
+    ct_columns(h, p.x, p.lambda, nrhs, state.DX, -1.0, state.DLAM, OUT, cap);
+    adjoint_dbound(p.row_state, h->sk->m, nrhs, state.DLAM, DBOUND);
 }
 }  // namespace
-static void do_solution_adjoint(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* gx, const double* gl,
-                                const asm_kkt_params* par, double* out, double* dbound, double* ax, double* al, asm_kkt_info* info) {
+static void do_solution_adjoint(asm_handle* h, const KktPoint& p, const double* gx, const double* gl, const asm_kkt_params* par, double* out, double* dbound, double* ax,
+                                double* al, asm_kkt_info* info) {
     adjoint_check(h, "asm_solution_adjoint");
     const int64_t n = h->sk->n, m = h->sk->m;
-    if (!x || !bound_state || !gx || !info || (m > 0 && (!lambda || !row_state || !gl)) || (h->ev->n_dpar > 0 && !out))
-        throw std::invalid_argument("asm_solution_adjoint: null pointer");
-    std::vector<double> ru((size_t)std::max<int64_t>(n, 1)), sx(ax ? 0 : (size_t)std::max<int64_t>(n, 1)), sl(al ? 0 : (size_t)std::max<int64_t>(m, 1));
-    for (int64_t j = 0; j < n; ++j) ru[j] = -gx[j];
-    if (!ax) ax = sx.data();
-    if (!al) al = sl.data();
-    do_kkt_solve(h, x, lambda, row_state, bound_state, ru.data(), gl, par, ax, al, nullptr, info, true);
-    ct_columns(h, x, lambda, 1, ax, -1.0, al, out, 1);
-    adjoint_dbound(row_state, m, 1, al, dbound);
+    adjoint_check_args("asm_solution_adjoint", m, h->ev->n_dpar, 1, p, gx, gl, out, info);
+    const AdjointSetup A(1, n, m, gx, ax, al);
+    adjoint_multi(h, "asm_kkt_solve", 1, p, 1, KktRhs::given(A.ru.data(), gl), par, out, dbound, A.state, info);
 }
-static void do_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
-                                      const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+static void do_solution_adjoint_multi(asm_handle* h, const KktPoint& p, int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par, double* OUT,
+                                      double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
     const char* who = "asm_solution_adjoint_multi";
     adjoint_check(h, who);
     hs_check(h, who);
     const int64_t n = h->sk->n, m = h->sk->m;
-    if (nrhs < 1) throw std::invalid_argument(std::string(who) + ": nrhs < 1");
-    if (!x || !bound_state || !GX || !info || (m > 0 && (!lambda || !row_state || !GL)) || (h->ev->n_dpar > 0 && !OUT)) throw std::invalid_argument(std::string(who) + ": null pointer");
-    std::vector<double> ru((size_t)std::max<int64_t>(nrhs * n, 1)), sx(AX ? 0 : (size_t)std::max<int64_t>(nrhs * n, 1)), sl(AL ? 0 : (size_t)std::max<int64_t>(nrhs * m, 1));
-    for (int64_t q = 0; q < nrhs * n; ++q) ru[q] = -GX[q];
-    adjoint_multi(h, who, x, lambda, row_state, bound_state, nrhs, ru.data(), GL, par, OUT, DBOUND, AX ? AX : sx.data(), AL ? AL : sl.data(), info);
+    adjoint_check_args(who, m, h->ev->n_dpar, nrhs, p, GX, GL, OUT, info);
+    const AdjointSetup A(nrhs, n, m, GX, AX, AL);
+    adjoint_multi(h, who, KKM_CW, p, nrhs, KktRhs::given(A.ru.data(), GL), par, OUT, DBOUND, A.state, info);
 }
-// asm_kkt_step (one column through KktOneColumn) and asm_kkt_step_multi (KktBlock): the checks of asm_kkt_solve(_multi), then
-// those of the radii and the share
-static void do_kkt_step(asm_handle* h, const char* who, bool multi, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
-                        const double* RU, const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX, double* DLAM, double* DZ,
-                        asm_kkt_step_info* info) {
-    const std::string me(who);
-    const bool lm = kkt_hess_lm(h, who);
-    if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
-    if (!x || !bound_state || !RU || !RADIUS || !DX || !info || (h->sk->m > 0 && (!lambda || !row_state || !RW || !DLAM))) throw std::invalid_argument(me + ": null pointer");
-    for (int32_t c = 0; c < nrhs; ++c)
-        if (!(RADIUS[c] > 0.0)) throw std::invalid_argument(me + ": a radius is not > 0");
-    KktTrust tr;
-    tr.radius = RADIUS;
-    tr.info = info;
-    if (par) {
-        if (!(par->normal_share > 0.0 && par->normal_share <= 1.0)) throw std::invalid_argument(me + ": normal_share outside (0, 1]");
-        tr.share = par->normal_share;
-    }
+// asm_kkt_step (one column) and asm_kkt_step_multi: the solve's entry with a radius per column and the share of the normal step
+static void do_kkt_step(asm_handle* h, const char* who, bool multi, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, const double* RADIUS,
+                        const asm_kkt_step_params* par, const KktOut& out, asm_kkt_step_info* info) {
     const asm_kkt_params kp{par ? par->max_iter : 0, par ? par->rtol : 0.0};
-    Dev dev(h);
-    const KktFace f(h, dev, me, x, lambda, row_state, bound_state, par ? &kp : nullptr, lm);
-    if (f.sparse) {
-        KktSparse ops(h, dev, f, *kk_work(h, multi ? KKM_CW : 1, true));
-        int64_t rounds;
-        int last_active;
-        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, multi ? h->ev->kkm_rounds : rounds, multi ? h->ev->kkm_last_active : last_active, tr);
-    } else if (multi) {
-        KktBlock ops(h, dev, f, *kk_work(h, KKM_CW));
-        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, h->ev->kkm_rounds, h->ev->kkm_last_active, tr);
-    } else {
-        KktOneColumn ops(h, dev, f, *kk_work(h, 1));
-        int64_t rounds;
-        int last_active;
-        kkt_columns(h, f, ops, nrhs, RU, RW, nullptr, false, lambda, DX, DLAM, DZ, nullptr, rounds, last_active, tr);
-    }
+    kkt_run(h, who, multi ? KKM_CW : 1, p, nrhs, rhs, par ? &kp : nullptr, out, info, KktTrust::step(RADIUS, par ? par->normal_share : KktTrust().share));
 }
 
 // eval_f + eval_g at a trial point (compute_alpha, slp_line_search.jl:222-244; step_quality, slp_trust_region.jl:213-251)
@@ -6072,31 +6108,29 @@ int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, co
 
 int asm_kkt_solve(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru, const double* rw,
                   const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
-    return guarded(h, [&] { do_kkt_solve(h, x, lambda, row_state, bound_state, ru, rw, par, dx, dlam, dz, info); });
+    return guarded(h, [&] { do_kkt_solve(h, {x, lambda, row_state, bound_state}, ru, rw, par, {dx, dlam, dz}, info); });
 }
 
 int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* dc,
                              const asm_kkt_params* par, double* dx, double* dlam, double* dz, asm_kkt_info* info) {
-    return guarded(h, [&] { do_solution_sensitivity(h, x, lambda, row_state, bound_state, dc, par, dx, dlam, dz, info); });
+    return guarded(h, [&] { do_solution_sensitivity(h, {x, lambda, row_state, bound_state}, dc, par, {dx, dlam, dz}, info); });
 }
 
 int asm_kkt_solve_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* RU,
                         const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
-    return guarded(h, [&] { do_kkt_solve_multi(h, "asm_kkt_solve_multi", x, lambda, row_state, bound_state, nrhs, RU, RW, nullptr, false, par, DX, DLAM, DZ, info); });
+    return guarded(h, [&] { do_kkt_solve_multi(h, "asm_kkt_solve_multi", {x, lambda, row_state, bound_state}, nrhs, KktRhs::given(RU, RW), par, {DX, DLAM, DZ}, info); });
 }
 
 int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* DC,
                                    const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
-    return guarded(h, [&] {
-        do_kkt_solve_multi(h, "asm_solution_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, true, par, DX, DLAM, DZ, info);
-    });
+    return guarded(h, [&] { do_kkt_solve_multi(h, "asm_solution_sensitivity_multi", {x, lambda, row_state, bound_state}, nrhs, KktRhs::data(DC), par, {DX, DLAM, DZ}, info); });
 }
 
 int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const int32_t* rows,
                                 const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
     return guarded(h, [&] {
         if (!rows) throw std::invalid_argument("asm_bound_sensitivity_multi: null pointer");
-        do_kkt_solve_multi(h, "asm_bound_sensitivity_multi", x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, nullptr, false, par, DX, DLAM, DZ, info, KktBound{rows, delta});
+        do_kkt_solve_multi(h, "asm_bound_sensitivity_multi", {x, lambda, row_state, bound_state}, nrhs, KktRhs::bound(rows, delta), par, {DX, DLAM, DZ}, info);
     });
 }
 
@@ -6106,12 +6140,12 @@ int asm_eval_data_cross_t(asm_handle* h, const double* x, const double* lambda, 
 
 int asm_solution_adjoint(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* gx, const double* gl,
                          const asm_kkt_params* par, double* out, double* dbound, double* ax, double* al, asm_kkt_info* info) {
-    return guarded(h, [&] { do_solution_adjoint(h, x, lambda, row_state, bound_state, gx, gl, par, out, dbound, ax, al, info); });
+    return guarded(h, [&] { do_solution_adjoint(h, {x, lambda, row_state, bound_state}, gx, gl, par, out, dbound, ax, al, info); });
 }
 
 int asm_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
                                const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
-    return guarded(h, [&] { do_solution_adjoint_multi(h, x, lambda, row_state, bound_state, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
+    return guarded(h, [&] { do_solution_adjoint_multi(h, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
 }
 
 int asm_kkt_set_form(asm_handle* h, int32_t form) {
@@ -6156,20 +6190,18 @@ int asm_kkt_form_info(const asm_handle* h, struct asm_kkt_form_info* out) {
 }
 int asm_kkt_step(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* ru, const double* rw,
                  double radius, const asm_kkt_step_params* par, double* dx, double* dlam, double* dz, asm_kkt_step_info* info) {
-    return guarded(h, [&] { do_kkt_step(h, "asm_kkt_step", false, x, lambda, row_state, bound_state, 1, ru, rw, &radius, par, dx, dlam, dz, info); });
+    return guarded(h, [&] { do_kkt_step(h, "asm_kkt_step", false, {x, lambda, row_state, bound_state}, 1, KktRhs::given(ru, rw), &radius, par, {dx, dlam, dz}, info); });
 }
 
 int asm_kkt_step_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* RU,
                        const double* RW, const double* RADIUS, const asm_kkt_step_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_step_info* info) {
-    return guarded(h, [&] {
-        do_kkt_step(h, "asm_kkt_step_multi", true, x, lambda, row_state, bound_state, nrhs, RU, RW, RADIUS, par, DX, DLAM, DZ, info);
-    });
+    return guarded(h, [&] { do_kkt_step(h, "asm_kkt_step_multi", true, {x, lambda, row_state, bound_state}, nrhs, KktRhs::given(RU, RW), RADIUS, par, {DX, DLAM, DZ}, info); });
 }
 
 int asm_test_kkt_multi_rounds(const asm_handle* h, int64_t* rounds, int32_t* last_active) {
     if (!h || !rounds || !last_active) return ASM_ERR_ARG;
-    *rounds = h->ev ? h->ev->kkm_rounds : 0;
-    *last_active = h->ev ? h->ev->kkm_last_active : 0;
+    *rounds = h->ev ? h->ev->kkm.rounds : 0;
+    *last_active = h->ev ? h->ev->kkm.last_active : 0;
     return ASM_OK;
 }
 
@@ -6410,7 +6442,7 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     vec ru(hd + m, hd + m + n), rw(hd, hd + m), dx((size_t)n), dlam((size_t)std::max<int64_t>(m, 1)), dz((size_t)n);
     rw.resize((size_t)std::max<int64_t>(m, 1), 0.0);
     asm_kkt_step_info st;
-    do_kkt_step(h, who, false, x, lambda, rs.data(), bound_state, 1, ru.data(), rw.data(), &radius, par, dx.data(), dlam.data(), dz.data(), &st);
+    do_kkt_step(h, who, false, {x, lambda, rs.data(), bound_state}, 1, KktRhs::given(ru.data(), rw.data()), &radius, par, {dx.data(), dlam.data(), dz.data()}, &st);
     info->status = st.status; info->cg_iters = st.cg_iters; info->n_free = st.n_free; info->n_rows = st.n_rows; info->dropped_pivots = st.dropped_pivots;
     info->boundary = st.boundary; info->res_stat = st.res_stat; info->res_feas = st.res_feas; info->theta = st.theta; info->norm_normal = st.norm_normal;
     info->norm_step = st.norm_step; info->model = st.model;
@@ -7943,6 +7975,19 @@ void check_scen(const asm_batch* b, int64_t n_scen, const char* what) {
     if (b->scen_cnt > 0 && n_scen != b->scen_n)
         throw std::invalid_argument(std::string(what) + ": " + std::to_string(n_scen) + " scenarios, the scenario data table has " + std::to_string(b->scen_n));
 }
+// body(h, sc, slot) for every scenario sc in [0, n_scen) as step `step`: the first min(n_scen, slots) slots run as fibers and take the
+// scenarios in index order.  What a scenario starts with - its data, its bounds, a new merge cycle - is the body's
+template <class Body>
+void for_each_scenario(asm_batch* b, int64_t n_scen, const char* step, Body&& body) {
+    std::atomic<int64_t> next{0};
+    run_fibers(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), step, [&](int s) {
+        for (;;) {
+            const int64_t sc = next.fetch_add(1);
+            if (sc >= n_scen) break;
+            body(b->slots[s], sc, s);
+        }
+    });
+}
 // forget the shared Hessian lists: the slots that use them go back to "not prepared" (their workspaces leave with their evaluator pools)
 void batch_hs_drop(asm_batch* b) {
     for (asm_handle* h : b->slots)
@@ -8181,21 +8226,14 @@ void batch_slp_runs(asm_batch* b, const char* step, int64_t n_scen, const double
         });
         b->J_ref = h0->sk->hint[0].ns_J;
     }
-    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
-    std::atomic<int64_t> next{0};
-    run_fibers(b, count, step, [&](int s) {
-        asm_handle* h = b->slots[s];
-        for (;;) {
-            const int64_t sc = next.fetch_add(1);
-            if (sc >= n_scen) break;
-            do_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n);
-            batch_scenario_data(b, h, sc);
-            // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
-            if (!b->J_ref.empty()) h->sk->hint[0].ns_J = b->J_ref;
-            else h->sk->hint[0].ns_J.clear();
-            run_one(h, sc);
-            res[sc].slot = s;
-        }
+    for_each_scenario(b, n_scen, step, [&](asm_handle* h, int64_t sc, int s) {
+        do_set_bounds(h, c_lb + sc * m, c_ub + sc * m, v_lb + sc * n, v_ub + sc * n);
+        batch_scenario_data(b, h, sc);
+        // every scenario starts from the batch's reference basis columns (results do not depend on which slot solved what before)
+        if (!b->J_ref.empty()) h->sk->hint[0].ns_J = b->J_ref;
+        else h->sk->hint[0].ns_J.clear();
+        run_one(h, sc);
+        res[sc].slot = s;
     });
 }
 }  // namespace
@@ -8243,16 +8281,10 @@ int asm_batch_data_gradient(asm_batch* b, int64_t n_scen, const double* x, const
         if (n_scen < 1 || !x || (m > 0 && !lambda) || (nd > 0 && !out)) throw std::invalid_argument("asm_batch_data_gradient: bad argument");
         check_scen(b, n_scen, "asm_batch_data_gradient");
         HIPCHK(hipSetDevice(b->device));
-        std::atomic<int64_t> next{0};
-        run_fibers(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), "asm_eval_data_gradient", [&](int s) {
-            asm_handle* h = b->slots[s];
-            for (;;) {
-                const int64_t sc = next.fetch_add(1);
-                if (sc >= n_scen) break;
-                batch_scenario_data(b, h, sc);
-                asmb::next_cycle();
-                do_data_gradient(h, x + sc * n, m > 0 ? lambda + sc * m : nullptr, out + sc * nd);
-            }
+        for_each_scenario(b, n_scen, "asm_eval_data_gradient", [&](asm_handle* h, int64_t sc, int) {
+            batch_scenario_data(b, h, sc);
+            asmb::next_cycle();
+            do_data_gradient(h, x + sc * n, m > 0 ? lambda + sc * m : nullptr, out + sc * nd);
         });
     });
 }
@@ -8283,7 +8315,7 @@ void batch_hs_prepare(asm_batch* b, const char* who) {
 // The multi entries (asm_batch_kkt_solve and the two sensitivity entries, cap = KKM_CW) come here too: the work area of 64 columns
 // - 14 ldn + 5 ldT + Mp doubles per column, the transposed factor (ld^2) and, dense form, the unmasked transposed working rows (ldn ldT) -
 // instead of the one-column area and the trial's state, and with `cross` what the cross-derivative sweep of the slot's kind needs
-// (cx_prepare downloads with blocking copies), under the conditions kkt_columns reads it; with `cross_t` the workspace of the transposed
+// (cx_prepare downloads with blocking copies), under the conditions kkt_stage_rhs reads it for KktRhs::data; with `cross_t` the workspace of the transposed
 // sweep (asm_batch_solution_adjoint), under the conditions ct_columns reads it.
 void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_eqp", int64_t cap = 1, bool cross = false, bool cross_t = false) {
     bool sparse = b->kkt_form == ASM_KKT_SPARSE && b->slots[0]->sk->sp_ok;
@@ -8303,81 +8335,54 @@ void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_
             if (cross_t && ct_active(e)) ct_prepare(h, KKM_CW);
         });
 }
-// The three multi entries on n_scen scenarios, the slots taking them in index order: per scenario do_kkt_solve_multi under the per-handle
-// entry's name `step`, on the scenario's rows of every array and with its data.  Exactly one of (RU, RW), DC (sens; dc_stride: doubles
-// from one scenario's directions to the next, 0 when they are shared) and bd.rows says what the columns are.  Everything that can be
-// refused without a launch is refused here, on the calling thread, and what a slot allocates or builds at its first call is made before
-// the fibers start (batch_kkt_prepare).
-void batch_kkt_multi(asm_batch* b, const char* who, const char* step, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
-                     const int32_t* bound_state, int32_t nrhs, const double* RU, const double* RW, const double* DC, int64_t dc_stride, bool sens, const KktBound* bound,
-                     const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+// The three multi entries on n_scen scenarios, the slots taking them in index order (for_each_scenario): per scenario do_kkt_solve_multi
+// under the per-handle entry's name `step`, on the scenario's part of the point, of the columns `rhs` and of the outputs (KktPoint::at,
+// KktRhs::at with dc_stride, KktOut::at) and with its data.  Everything that can be refused without a launch is refused here, on the
+// calling thread - the arguments by the per-handle entry's own kkt_check_args under the batch entry's name `who` - and what a slot
+// allocates or builds at its first call is made before the fibers start (batch_kkt_prepare).
+void batch_kkt_multi(asm_batch* b, const char* who, const char* step, int64_t n_scen, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, int64_t dc_stride,
+                     const asm_kkt_params* par, const KktOut& out, asm_kkt_info* info) {
     const std::string me(who);
+    const bool data = rhs.kind == KktRhs::DATA;
     // a model without second derivatives ends here, as in asm_batch_hessian_*, one without cross derivatives as in the per-handle entry
     batch_hs_prepare(b, who);
-    if (sens) cx_check(b->slots[0], who);
+    if (data) cx_check(b->slots[0], who);
     const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = (int64_t)b->dpar0.size();
     if (n_scen < 1 || nrhs < 1) throw std::invalid_argument(me + ": n_scen < 1 or nrhs < 1");
-    if (!x || !bound_state || !DX || !info || (m > 0 && (!lambda || !row_state || !DLAM)) || (bound && !bound->rows)) throw std::invalid_argument(me + ": null pointer");
-    const KktBound bd = bound ? *bound : KktBound();
-    if (bd.rows) {
-        for (int32_t c = 0; c < nrhs; ++c)
-            if (bd.rows[c] < 0 || bd.rows[c] >= m) throw std::invalid_argument(me + ": a row index outside [0, m)");
-    } else if (sens ? (nd > 0 && !DC) : (!RU || (m > 0 && !RW))) {
-        throw std::invalid_argument(me + ": null pointer");
-    }
+    kkt_check_args(me, m, nd, nrhs, p, rhs, &out, info);
     if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
     check_scen(b, n_scen, who);
     HIPCHK(hipSetDevice(b->device));
-    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
-    batch_kkt_prepare(b, count, step, KKM_CW, sens);
-    std::atomic<int64_t> next{0};
-    run_fibers(b, count, step, [&](int s) {
-        asm_handle* h = b->slots[s];
-        for (;;) {
-            const int64_t sc = next.fetch_add(1);
-            if (sc >= n_scen) break;
-            batch_scenario_data(b, h, sc);
-            asmb::next_cycle();
-            const int64_t o = sc * nrhs;
-            do_kkt_solve_multi(h, step, x + sc * n, m > 0 ? lambda + sc * m : nullptr, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n, nrhs, RU ? RU + o * n : nullptr,
-                               RW ? RW + o * m : nullptr, DC ? DC + sc * dc_stride : nullptr, sens, par, DX + o * n, m > 0 ? DLAM + o * m : nullptr, DZ ? DZ + o * n : nullptr,
-                               info + o, bd);
-        }
+    batch_kkt_prepare(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), step, KKM_CW, data);
+    for_each_scenario(b, n_scen, step, [&](asm_handle* h, int64_t sc, int) {
+        batch_scenario_data(b, h, sc);
+        asmb::next_cycle();
+        const int64_t o = sc * nrhs;
+        do_kkt_solve_multi(h, step, p.at(sc, n, m), nrhs, rhs.at(sc, nrhs, n, m, dc_stride), par, out.at(o, n, m), info + o);
     });
 }
-// asm_solution_adjoint_multi on n_scen scenarios, the slots taking them in index order: the checks of batch_kkt_multi, the negated
-// gradients and (where the caller wants none) the adjoint states' buffers made here for all scenarios, the workspaces before the fibers start
-void batch_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
-                   const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
+// asm_solution_adjoint_multi on n_scen scenarios, the slots taking them in index order: the checks as in batch_kkt_multi, the set-up of
+// the adjoint entries (AdjointSetup) for the functions of all scenarios, the workspaces before the fibers start
+void batch_adjoint(asm_batch* b, int64_t n_scen, const KktPoint& p, int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par, double* OUT,
+                   double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
     const char *who = "asm_batch_solution_adjoint", *step = "asm_solution_adjoint_multi";
     const std::string me(who);
     batch_hs_prepare(b, who);
     adjoint_check(b->slots[0], who);
     const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = b->slots[0]->ev->n_dpar;
     if (n_scen < 1 || nrhs < 1) throw std::invalid_argument(me + ": n_scen < 1 or nrhs < 1");
-    if (!x || !bound_state || !GX || !info || (m > 0 && (!lambda || !row_state || !GL)) || (nd > 0 && !OUT)) throw std::invalid_argument(me + ": null pointer");
+    adjoint_check_args(me, m, nd, nrhs, p, GX, GL, OUT, info);
     if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
     check_scen(b, n_scen, who);
     HIPCHK(hipSetDevice(b->device));
-    const int64_t cols = n_scen * nrhs;
-    std::vector<double> ru((size_t)std::max<int64_t>(cols * n, 1)), sx(AX ? 0 : (size_t)std::max<int64_t>(cols * n, 1)), sl(AL ? 0 : (size_t)std::max<int64_t>(cols * m, 1));
-    for (int64_t q = 0; q < cols * n; ++q) ru[q] = -GX[q];
-    if (!AX) AX = sx.data();
-    if (!AL) AL = sl.data();
-    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
-    batch_kkt_prepare(b, count, step, KKM_CW, false, true);
-    std::atomic<int64_t> next{0};
-    run_fibers(b, count, step, [&](int s) {
-        asm_handle* h = b->slots[s];
-        for (;;) {
-            const int64_t sc = next.fetch_add(1);
-            if (sc >= n_scen) break;
-            batch_scenario_data(b, h, sc);
-            asmb::next_cycle();
-            const int64_t o = sc * nrhs;
-            adjoint_multi(h, step, x + sc * n, m > 0 ? lambda + sc * m : nullptr, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n, nrhs, ru.data() + o * n,
-                          m > 0 ? GL + o * m : nullptr, par, OUT + o * nd, DBOUND ? DBOUND + o * m : nullptr, AX + o * n, AL + o * m, info + o);
-        }
+    const AdjointSetup A(n_scen * nrhs, n, m, GX, AX, AL);
+    const KktRhs rhs = KktRhs::given(A.ru.data(), GL);
+    batch_kkt_prepare(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), step, KKM_CW, false, true);
+    for_each_scenario(b, n_scen, step, [&](asm_handle* h, int64_t sc, int) {
+        batch_scenario_data(b, h, sc);
+        asmb::next_cycle();
+        const int64_t o = sc * nrhs;
+        adjoint_multi(h, step, KKM_CW, p.at(sc, n, m), nrhs, rhs.at(sc, nrhs, n, m, 0), par, OUT + o * nd, DBOUND ? DBOUND + o * m : nullptr, A.state.at(o, n, m), info + o);
     });
 }
 // asm_eval_hessian_lagrangian (v == nullptr: values [n_scen x nnz] into out) or asm_eval_hessian_product (out [n_scen x n]) of n_scen
@@ -8388,18 +8393,12 @@ void batch_hessians(asm_batch* b, const char* who, int64_t n_scen, const double*
     const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nnz = b->hs->nnz(), len = v ? n : nnz;
     check_scen(b, n_scen, who);
     HIPCHK(hipSetDevice(b->device));
-    std::atomic<int64_t> next{0};
-    run_fibers(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), v ? "asm_eval_hessian_product" : "asm_eval_hessian_lagrangian", [&](int s) {
-        asm_handle* h = b->slots[s];
-        for (;;) {
-            const int64_t sc = next.fetch_add(1);
-            if (sc >= n_scen) break;
-            if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
-            batch_scenario_data(b, h, sc);
-            asmb::next_cycle();
-            hs_launch(h, x + sc * n, obj_factor ? obj_factor[sc] : 1.0, m > 0 ? lambda + sc * m : nullptr, v ? v + sc * n : nullptr);
-            hs_read(h, v ? h->ev->d_hs_out : h->ev->d_hs_vals, len, out + sc * len);
-        }
+    for_each_scenario(b, n_scen, v ? "asm_eval_hessian_product" : "asm_eval_hessian_lagrangian", [&](asm_handle* h, int64_t sc, int) {
+        if (!h->ev->hs_sh) hs_attach(h, b->hs.get());
+        batch_scenario_data(b, h, sc);
+        asmb::next_cycle();
+        hs_launch(h, x + sc * n, obj_factor ? obj_factor[sc] : 1.0, m > 0 ? lambda + sc * m : nullptr, v ? v + sc * n : nullptr);
+        hs_read(h, v ? h->ev->d_hs_out : h->ev->d_hs_vals, len, out + sc * len);
     });
 }
 }  // namespace
@@ -8459,7 +8458,7 @@ int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, cons
 int asm_batch_kkt_solve(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                         const double* RU, const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
     return guarded(b, [&] {
-        batch_kkt_multi(b, "asm_batch_kkt_solve", "asm_kkt_solve_multi", n_scen, x, lambda, row_state, bound_state, nrhs, RU, RW, nullptr, 0, false, nullptr, par, DX, DLAM, DZ, info);
+        batch_kkt_multi(b, "asm_batch_kkt_solve", "asm_kkt_solve_multi", n_scen, {x, lambda, row_state, bound_state}, nrhs, KktRhs::given(RU, RW), 0, par, {DX, DLAM, DZ}, info);
     });
 }
 
@@ -8468,22 +8467,21 @@ int asm_batch_solution_sensitivity(asm_batch* b, int64_t n_scen, const double* x
     return guarded(b, [&] {
         if (dc_per_scenario != 0 && dc_per_scenario != 1) throw std::invalid_argument("asm_batch_solution_sensitivity: dc_per_scenario is neither 0 nor 1");
         const int64_t stride = dc_per_scenario ? (int64_t)std::max<int32_t>(nrhs, 0) * (int64_t)b->dpar0.size() : 0;
-        batch_kkt_multi(b, "asm_batch_solution_sensitivity", "asm_solution_sensitivity_multi", n_scen, x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, DC, stride, true,
-                        nullptr, par, DX, DLAM, DZ, info);
+        batch_kkt_multi(b, "asm_batch_solution_sensitivity", "asm_solution_sensitivity_multi", n_scen, {x, lambda, row_state, bound_state}, nrhs, KktRhs::data(DC), stride, par,
+                        {DX, DLAM, DZ}, info);
     });
 }
 
 int asm_batch_solution_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                const double* GX, const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
-    return guarded(b, [&] { batch_adjoint(b, n_scen, x, lambda, row_state, bound_state, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
+    return guarded(b, [&] { batch_adjoint(b, n_scen, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
 }
 
 int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                 const int32_t* rows, const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
     return guarded(b, [&] {
-        const KktBound bd{rows, delta};
-        batch_kkt_multi(b, "asm_batch_bound_sensitivity", "asm_bound_sensitivity_multi", n_scen, x, lambda, row_state, bound_state, nrhs, nullptr, nullptr, nullptr, 0, false,
-                        &bd, par, DX, DLAM, DZ, info);
+        batch_kkt_multi(b, "asm_batch_bound_sensitivity", "asm_bound_sensitivity_multi", n_scen, {x, lambda, row_state, bound_state}, nrhs, KktRhs::bound(rows, delta), 0, par,
+                        {DX, DLAM, DZ}, info);
     });
 }
 
