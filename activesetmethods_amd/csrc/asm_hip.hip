@@ -398,19 +398,27 @@ struct EvLayout {
     int64_t stage_len() const { return std::max({st_f(true) + 1, st_v() + n, nu() - lam(), jtl() - nu(), OUT}); }
 };
 
-// The block kinds that run the Ohm's-law kernel / the dense quadratic kernel: kinds 4 and 5 are kinds 1 and 2 that also announce second
-// derivatives (hs_check) - same parameters, same size checks, same launches for values and Jacobian.
-inline bool nlp_is_ohm(int kind) { return kind == ASM_NLP_ACOPF_OHM || kind == ASM_NLP_ACOPF_OHM_HESS; }
-inline bool nlp_is_dense(int kind) { return kind == ASM_NLP_DENSE_QUADRATIC || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
-// ... and the two that announce their derivative entries: besides the Hessian the derivatives with respect to their own data
-// (asm_eval_data_gradient, asm_eval_data_cross and what is built on them), in closed form
-inline bool nlp_block_derivs(int kind) { return kind == ASM_NLP_ACOPF_OHM_HESS || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
+// What runs an NLP block: nothing (the function store alone), the expression tape, the Ohm's-law kernel or the dense quadratic kernel.
+// The kinds of the header map onto it below ("NLP block kinds"); the rest of the file reads what asm_eval_setup stored in EvalState.
+enum class NlpFamily { NONE, EXPR, OHM, DENSE };
+
+// The host-side form of an expression block after validation (expr_prepare): node references absolute, the slots of the VAR nodes
+// (rows: Jacobian value from j0; terms: position in the per-variable gradient list)
+struct ExprHost {
+    int64_t R = 0, T = 0, L = 0;
+    std::vector<int64_t> ptr, jptr, a, b, slot, gptr, cptr;   // cptr [n_dpar+1]: the CONST nodes grouped by dpar index (empty: no CONST node)
+    std::vector<int32_t> op;
+};
 
 // Everything asm_eval_setup makes or that is made lazily after it, in one pool and with one lifetime: until the next asm_eval_setup or
 // asm_sublp_setup.  The handle holds a pointer that is null while there is no evaluator (ev_of): no ready flag, no list of fields to reset.
 struct EvalState {
-    // the flattened function store, the NLP block and its tape (nlp_kind ASM_NLP_EXPR: asm_eval_kernels.hip.h), evaluation results in HBM
-    int nlp_kind = 0;
+    // What the block's kind means, derived once (nlp_setup): the family; whether second derivatives are announced (hs_check: every kind but
+    // 1 and 2); whether derivatives with respect to the block's data exist (data_kind_check: kinds 3, 4 and 5); whether anything depends
+    // on the data - a tape with a CONST node, a kernel with derivative entries and data - or every data derivative is zero, no launch
+    NlpFamily family = NlpFamily::NONE;
+    bool has_hess = true, has_data = false, data_dep = false;
+    // the flattened function store, the NLP block (nlp_rows rows whatever the family) and its tape (asm_eval_kernels.hip.h), results in HBM
     int64_t nlp_rows = 0, fn_nnz = 0;
     FnStore F{};
     ExprTape X{};
@@ -430,24 +438,348 @@ struct EvalState {
     ExprHess hs_H{};
     double *d_hs_lam = nullptr, *d_hs_v = nullptr, *d_hs_vals = nullptr, *d_hs_out = nullptr, *h_hs = nullptr;
     void hs_forget() { hs_H = ExprHess{}; hs_sh = nullptr; }      // its lists are about to go; the workspace stays in `mem`
-    // cross derivatives with respect to the data (asm_eval_data_cross): occurrence list and workspace, made by the first call (cx_prepare)
+    // cross derivatives with respect to the data (asm_eval_data_cross and the sensitivity entries), made by the first call (cx_prepare).
+    // With R = nlp_rows: d_cx_in = [lam (R) | cx_cap directions of n_dpar], d_cx_out = cx_cap columns [u (n) | w (R)], h_cx the pinned
+    // staging of x, lam, one direction and one column.  The tape sweeps one direction at a time in cx_C's node arrays (cx_cap stays 1);
+    // the kernels take 1 or KKM_CW columns, the Ohm's-law one with d_cx_occ = cx_cap x [4][nl] occurrences.  d_cx_vptr / d_cx_vnode: per
+    // variable its VAR nodes (tape) or where its occurrences live in a column's (Ohm's law)
     ExprCross cx_C{};
     int64_t *d_cx_vptr = nullptr, *d_cx_vnode = nullptr;
-    double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr;   // [lam (R) | dc (n_dpar)], [u (n) | w (R)], pinned staging of both and x
-    // kinds 4 and 5 (R = nlp_rows): d_cx_in = [lam (R) | cx_cap directions], d_cx_out = cx_cap columns [u | w], d_cx_occ = cx_cap x [4][nl]
-    // occurrences of the Ohm's-law block, d_cx_vnode where each listed occurrence lives in a column's; cx_cap is 1 or KKM_CW (cx_prepare)
+    double *d_cx_in = nullptr, *d_cx_out = nullptr, *h_cx = nullptr, *d_cx_occ = nullptr;
     int64_t cx_cap = 0;
-    double* d_cx_occ = nullptr;
-    // transposed cross derivatives (asm_eval_data_cross_t and the adjoint entries; ct_prepare): with R the block's rows, d_ct_in = [lam (R) |
-    // ct_cap columns [vx (n) | vl (R)]], d_ct_out = ct_cap columns of n_dpar, h_ct the pinned staging of x, both and the read-back; ct_cap
-    // is 1 or KKM_CW.  Kind 3 runs in cx_C's node arrays and d_cocc.
+    // transposed cross derivatives (asm_eval_data_cross_t and the adjoint entries; ct_prepare): d_ct_in = [lam (R) | ct_cap columns
+    // [vx (n) | vl (R)]], d_ct_out = ct_cap columns of n_dpar, h_ct the pinned staging of x, both and the read-back; ct_cap is 1 or
+    // KKM_CW.  The tape runs in cx_C's node arrays and d_cocc.
     int64_t ct_cap = 0;
     double *d_ct_in = nullptr, *d_ct_out = nullptr, *h_ct = nullptr;
-    bool ohm_vars_ok = true;        // kind 4: every variable the block names is inside [0, n) (checked at asm_eval_setup, refused by the data entries)
+    bool ohm_vars_ok = true;        // Ohm's law with derivatives: every variable the block names is inside [0, n) (nlp_setup; refused by the data entries)
     KktBufs kk;                     // KKT solve on a working set (asm_kkt_solve and the multi entries)
     KktCounters kkm;                // test seam: the counters of the last multi call
     BufPool mem;                    // declared last: it goes first, while the fields it nulls are alive
 };
+
+// ---- NLP block kinds.  The ONLY place that knows what a kind of the header (ASM_NLP_*) means and what its family launches, with which
+// grid and in which workspace.  The entries stage, check and read back the same way for every kind; where the kinds differ they call a
+// function of this section or read the four facts nlp_setup stored (family, has_hess, has_data, data_dep), never the kind.  Kinds 4 and
+// 5 are kinds 1 and 2 - same parameters, size checks and launches for values and Jacobian - that also announce their derivative entries:
+// the Hessian and, in closed form, the derivatives with respect to their own data.  A new kind adds its case to nlp_family, nlp_setup's
+// facts, nlp_check_sizes and nlp_rows_launch, and per derivative entry it announces to nlp_hess_lists / nlp_hess_launch,
+// nlp_data_grad_launch, cx_prepare / nlp_cross_launch, nlp_cross_t_launch.  The caller has set the device; the launches go to `s`.
+inline bool nlp_is_ohm(int kind) { return kind == ASM_NLP_ACOPF_OHM || kind == ASM_NLP_ACOPF_OHM_HESS; }
+inline bool nlp_is_dense(int kind) { return kind == ASM_NLP_DENSE_QUADRATIC || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
+inline bool nlp_block_derivs(int kind) { return kind == ASM_NLP_ACOPF_OHM_HESS || kind == ASM_NLP_DENSE_QUADRATIC_HESS; }
+inline NlpFamily nlp_family(int kind) {
+    return kind == ASM_NLP_EXPR ? NlpFamily::EXPR : nlp_is_ohm(kind) ? NlpFamily::OHM : nlp_is_dense(kind) ? NlpFamily::DENSE : NlpFamily::NONE;
+}
+// the parameter sizes of the kernel families (a tape's checks are expr_prepare's)
+void nlp_check_sizes(int kind, int64_t n, int64_t nlp_rows, int64_t nlp_nnz, int64_t n_ipar, int64_t n_dpar) {
+    if (nlp_is_ohm(kind) && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
+        throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
+    if (nlp_is_dense(kind) && (nlp_nnz != nlp_rows * n || n_dpar != 2 * nlp_rows * n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
+}
+// The block's part of asm_eval_setup, after F, nlp_rows, n_dpar and the parameters: the four facts, the tape (xh: what expr_prepare made
+// of ipar) with its workspace, and what the data gradient needs - a batch calls that inside fibers and must not allocate there
+void nlp_setup(EvalState& e, int kind, const ExprHost& xh, const int64_t* ipar) {
+    BufPool& P = e.mem;
+    const int64_t n = e.F.n, nd = e.n_dpar;
+    e.family = nlp_family(kind);
+    e.has_hess = kind != ASM_NLP_ACOPF_OHM && kind != ASM_NLP_DENSE_QUADRATIC;     // (their twins with second derivatives: kinds 4 and 5)
+    e.has_data = e.family == NlpFamily::EXPR || nlp_block_derivs(kind);
+    e.data_dep = e.family == NlpFamily::EXPR ? !xh.cptr.empty() : nlp_block_derivs(kind) && nd > 0;
+    if (e.family == NlpFamily::EXPR) {
+        ExprTape& X = e.X;
+        X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = n;
+        P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
+        P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
+        P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
+        X.cst = e.d_dpar;
+        // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
+        P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
+        P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[n]);
+        if (e.data_dep) {           // the data gradient's occurrence list
+            P.upload(e.d_cptr, xh.cptr.data(), nd + 1);
+            P.zeroed(e.d_cocc, xh.cptr[nd]);
+        }
+    }
+    if (e.family == NlpFamily::EXPR ? e.data_dep : e.has_data) {       // the data gradient's multipliers of the rows and result
+        P.zeroed(e.d_lam, e.nlp_rows); P.zeroed(e.d_dgrad, nd);
+        P.alloc(e.h_dgrad, nd, BufPool::PINNED);
+    }
+    if (e.family == NlpFamily::OHM && e.has_data) {
+        const int64_t nl = e.nlp_rows / 4;
+        bool ok = ipar && ipar[0] == nl;
+        for (int64_t l = 0; ok && l < 2 * nl; ++l) {
+            const int64_t b = ipar[7 + l];
+            ok = ipar[1] + b >= 0 && ipar[1] + b < n && ipar[2] + b >= 0 && ipar[2] + b < n;
+        }
+        e.ohm_vars_ok = ok;
+    }
+}
+
+// Rows of the function store and of the block at the point xd: values into Ed, with `full` the Jacobian values into dE.  nt > 1 (values
+// only): the trial points of a batched line search, xd / Ed advancing by ldx / ldE per point.  Two functions because asm_eval_functions
+// launches the store's objective between them
+void fn_rows_launch(const EvalState& e, hipStream_t s, const double* xd, double* Ed, double* dE, int full, unsigned nt = 1, int64_t ldx = 0, int64_t ldE = 0) {
+    asmb::launch(k_fn_rows, dim3(asmb::blocks(e.F.n_rows).x, nt), dim3(256), s, e.F, xd, Ed, dE, full, ldx, ldE);
+}
+void nlp_rows_launch(const EvalState& e, hipStream_t s, const double* xd, double* Ed, double* dE, int full, unsigned nt = 1, int64_t ldx = 0, int64_t ldE = 0) {
+    const int64_t R = e.nlp_rows, r0 = e.F.n_rows;
+    switch (e.family) {
+    case NlpFamily::NONE: break;
+    case NlpFamily::EXPR: asmb::launch(k_nlp_expr_rows, dim3(asmb::blocks(R).x, nt), dim3(256), s, e.X, xd, Ed, dE, r0, e.fn_nnz, full, ldx, ldE); break;
+    case NlpFamily::OHM: asmb::launch(k_nlp_acopf_ohm, dim3(asmb::blocks(R / 4).x, nt), dim3(256), s, e.d_ipar, e.d_dpar, xd, Ed, dE, r0, e.fn_nnz, full, ldx, ldE); break;
+    case NlpFamily::DENSE: asmb::launch(k_nlp_dense_quadratic, dim3(asmb::blocks(R, 4).x, nt), dim3(256), s, e.d_dpar, R, e.F.n, xd, Ed, dE, r0, e.fn_nnz, full, ldx, ldE); break;
+    }
+}
+// whether the block's objective replaces the store's objective row (a tape with terms), and its value into fd, with `full` its gradient into d_df
+bool nlp_has_objective(const EvalState& e) { return e.family == NlpFamily::EXPR && e.X.T > 0; }
+void nlp_objective_launch(const EvalState& e, hipStream_t s, const double* xd, double* fd, int full, unsigned nt, int64_t ldx) {
+    if (!nlp_has_objective(e)) return;
+    asmb::launch(k_nlp_expr_terms, dim3(asmb::blocks(e.X.T).x, nt), dim3(256), s, e.X, xd, full, ldx);
+    asmb::launch(k_nlp_expr_objective, dim3(nt), dim3(64), s, e.X, e.F.objective_scale, fd);
+    if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(e.F.n), dim3(256), s, e.X, e.F.objective_scale, e.d_df);
+}
+
+template <class T>
+std::vector<T> hs_download(const T* dev, int64_t count) {      // (a blocking copy: not inside a batch fiber)
+    std::vector<T> v((size_t)std::max<int64_t>(count, 0));
+    if (count > 0) HIPCHK(asmb::copy(v.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
+    return v;
+}
+// the interaction set P(last node) of the row or term with nodes [k0, k1) (absolute references), as pairs (j, i), j <= i, sorted by (j, i):
+// the union over the nodes the last one depends on of what each op adds (the header's rule; POW / ATAN2 cover their operands' sets)
+void hs_row_pairs(const int32_t* op, const int64_t* a, const int64_t* b, int64_t k0, int64_t k1, std::vector<std::vector<int64_t>>& L, std::vector<char>& reach,
+                  std::vector<std::pair<int64_t, int64_t>>& P) {
+    const int64_t len = k1 - k0;
+    if ((int64_t)L.size() < len) L.resize(len);
+    reach.assign(len, 0);
+    reach[len - 1] = 1;
+    for (int64_t q = len - 1; q >= 0; --q) {
+        const int32_t o = op[k0 + q];
+        if (!reach[q] || o == ASM_OP_CONST || o == ASM_OP_VAR) continue;
+        reach[a[k0 + q] - k0] = 1;
+        if ((o >= ASM_OP_ADD && o <= ASM_OP_DIV) || o >= ASM_OP_POW) reach[b[k0 + q] - k0] = 1;
+    }
+    P.clear();
+    auto cross = [&P](const std::vector<int64_t>& A, const std::vector<int64_t>& B) {
+        for (int64_t i : A)
+            for (int64_t j : B) P.emplace_back(std::min(i, j), std::max(i, j));
+    };
+    for (int64_t q = 0; q < len; ++q) {
+        const int64_t k = k0 + q;
+        const int32_t o = op[k];
+        std::vector<int64_t>& Lq = L[q];
+        Lq.clear();
+        if (o == ASM_OP_CONST) continue;
+        if (o == ASM_OP_VAR) { Lq.push_back(a[k]); continue; }
+        const std::vector<int64_t>& La = L[a[k] - k0];
+        const bool binary = (o >= ASM_OP_ADD && o <= ASM_OP_DIV) || o >= ASM_OP_POW;
+        if (!binary) Lq = La;
+        else {
+            const std::vector<int64_t>& Lb = L[b[k] - k0];
+            Lq.resize(La.size() + Lb.size());
+            Lq.erase(std::set_union(La.begin(), La.end(), Lb.begin(), Lb.end(), Lq.begin()), Lq.end());
+        }
+        if (!reach[q]) continue;
+        switch (o) {
+            case ASM_OP_ADD: case ASM_OP_SUB: case ASM_OP_NEG: case ASM_OP_MIN: case ASM_OP_MAX: break;
+            case ASM_OP_MUL: cross(La, L[b[k] - k0]); break;
+            case ASM_OP_DIV: cross(La, L[b[k] - k0]); cross(L[b[k] - k0], L[b[k] - k0]); break;
+            case ASM_OP_POWI: if (b[k] != 1) cross(La, La); break;
+            case ASM_OP_POW: case ASM_OP_ATAN2: cross(Lq, Lq); break;
+            default: cross(La, La); break;       // every other unary op
+        }
+    }
+    std::sort(P.begin(), P.end());
+    P.erase(std::unique(P.begin(), P.end()), P.end());
+}
+// The block's second derivatives for hs_build: the tape's seed threads (srow, svar, woff over wnodes workspace nodes) with their
+// occurrence lists (optr, ovar), the key i * n + j, i >= j, of every occurrence in list order (okey), where a listed occurrence lives
+// (oslot; empty: in place), and the keys of entries the launch writes itself, without occurrences (own)
+struct HsBlockLists {
+    std::vector<int64_t> srow, svar, woff, optr{0}, ovar, okey, oslot, own;
+    int64_t wnodes = 0;
+};
+HsBlockLists nlp_hess_lists(const EvalState& e) {
+    HsBlockLists B;
+    const int64_t n = e.F.n;
+    switch (e.family) {
+    case NlpFamily::NONE: break;
+    case NlpFamily::EXPR: {
+        // per row / term its interaction set, one seed thread per smaller index j with its occurrence list (i ascending)
+        const ExprTape& X = e.X;
+        const std::vector<int64_t> ptr = hs_download(X.ptr, X.R + X.T + 1), ta = hs_download(X.a, X.L), tb = hs_download(X.b, X.L);
+        const std::vector<int32_t> top = hs_download(X.op, X.L);
+        std::vector<std::vector<int64_t>> L;
+        std::vector<char> reach;
+        std::vector<std::pair<int64_t, int64_t>> P;
+        for (int64_t t = 0; t < X.R + X.T; ++t) {
+            hs_row_pairs(top.data(), ta.data(), tb.data(), ptr[t], ptr[t + 1], L, reach, P);
+            for (size_t q = 0; q < P.size(); ++q) {
+                if (q == 0 || P[q].first != P[q - 1].first) {
+                    if (q) B.optr.push_back((int64_t)B.ovar.size());
+                    B.srow.push_back(t); B.svar.push_back(P[q].first); B.woff.push_back(B.wnodes);
+                    B.wnodes += ptr[t + 1] - ptr[t];
+                }
+                B.ovar.push_back(P[q].second);
+                B.okey.push_back(P[q].second * n + P[q].first);
+            }
+            if (!P.empty()) B.optr.push_back((int64_t)B.ovar.size());
+        }
+        break;
+    }
+    case NlpFamily::OHM: {
+        // ten occurrences per branch, listed by branch ascending and inside a branch in the order k_nlp_ohm_hess documents; occurrence q
+        // of branch l is at hocc[q * nl + l]
+        if (!e.has_hess) break;
+        const int64_t nl = e.nlp_rows / 4;
+        const std::vector<int64_t> ip = hs_download(e.d_ipar, 7 + 2 * nl);
+        const int64_t va0 = ip[1], vm0 = ip[2];
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t fb = ip[7 + l], tb = ip[7 + nl + l];
+            const int64_t vf = vm0 + fb, vt = vm0 + tb, af = va0 + fb, at = va0 + tb;
+            if (ip[0] != nl || std::min({vf, vt, af, at}) < 0 || std::max({vf, vt, af, at}) >= n)
+                throw std::invalid_argument("asm_eval_hessian: the Ohm's-law block names a variable outside [0, n)");
+            if (fb == tb) throw std::invalid_argument("asm_eval_hessian: branch " + std::to_string(l) + " of the Ohm's-law block joins a bus to itself");
+            const int64_t pr[10][2] = {{vf, vf}, {vt, vt}, {vf, vt}, {vf, af}, {vf, at}, {vt, af}, {vt, at}, {af, af}, {at, at}, {af, at}};
+            for (int64_t q = 0; q < 10; ++q) {
+                B.okey.push_back(std::max(pr[q][0], pr[q][1]) * n + std::min(pr[q][0], pr[q][1]));
+                B.oslot.push_back(q * nl + l);
+            }
+        }
+        break;
+    }
+    case NlpFamily::DENSE:      // the n diagonal entries, written by k_nlp_dense_hess itself
+        if (e.has_hess)
+            for (int64_t j = 0; j < n; ++j) B.own.push_back(j * n + j);
+        break;
+    }
+    return B;
+}
+// the block's values at (d_xt, lam) into vals, its nblk entries of the pattern: the occurrences into hs_H.hocc and their sums by the lists
+// of L, or the entries in place.  (ipar / dpar read live: asm_eval_set_data and a scenario's table row take effect with nothing cached)
+void nlp_hess_launch(const EvalState& e, hipStream_t s, const HsShared& L, const double* lam, double wobj, int64_t nblk, double* vals) {
+    if (e.family == NlpFamily::DENSE && e.has_hess) asmb::launch(k_nlp_dense_hess, asmb::blocks(e.F.n), dim3(256), s, e.d_dpar, e.nlp_rows, e.F.n, lam, vals);
+    if (e.family == NlpFamily::EXPR && e.hs_H.S > 0) asmb::launch(k_nlp_expr_hess, asmb::blocks(e.hs_H.S), dim3(256), s, e.X, e.hs_H, e.d_xt, lam, wobj);
+    else if (e.family == NlpFamily::OHM && e.has_hess && L.nocc > 0) asmb::launch(k_nlp_ohm_hess, asmb::blocks(e.nlp_rows / 4), dim3(256), s, e.d_ipar, e.d_dpar, e.d_xt, lam, e.hs_H.hocc);
+    else return;      // no occurrences to sum
+    asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nblk), dim3(256), s, L.eptr, L.eocc, e.hs_H.hocc, nblk, vals);
+}
+
+// d_dgrad[c] = d(f - lam' g) / d dpar[c] at (d_xt, d_lam).  This and the launches below: for a block whose data_dep holds
+void nlp_expr_data_gather(const EvalState& e, hipStream_t s, double* out) {      // out[c] = the sum of constant c's occurrences in d_cocc
+    asmb::launch(k_nlp_expr_data_gather, asmb::blocks(e.n_dpar), dim3(256), s, e.d_cptr, e.d_cocc, e.n_dpar, out);
+}
+void nlp_data_grad_launch(const EvalState& e, hipStream_t s) {
+    const int64_t R = e.nlp_rows, n = e.F.n;
+    if (e.family == NlpFamily::EXPR) {
+        asmb::launch(k_nlp_expr_const_adj, asmb::blocks(R + e.X.T), dim3(256), s, e.X, e.d_xt, e.d_lam, e.F.objective_scale, e.d_cocc);
+        nlp_expr_data_gather(e, s, e.d_dgrad);
+    } else if (e.family == NlpFamily::OHM) asmb::launch(k_nlp_ohm_data_grad, asmb::blocks(R / 4), dim3(256), s, e.d_ipar, e.d_xt, e.d_lam, e.d_dgrad);
+    else asmb::launch(k_nlp_dense_data_grad, asmb::blocks(R * n), dim3(256), s, R, n, e.d_xt, e.d_lam, e.d_dgrad);
+}
+
+// The lists and the workspace of the cross derivatives, at the first call that needs them and again when the kernels' columns grow: 1
+// for asm_eval_data_cross, KKM_CW from the first multi call on (the narrower buffers stay in the pool; a tape keeps its one column).
+// Blocking copies: not inside a batch fiber.  Tape: the VAR nodes of every variable in (row, then term) order, node descending inside
+// a row or term, and the sweep's node arrays.  Ohm's law: per variable its occurrences of k_nlp_ohm_cross, branch ascending and inside a
+// branch in slot order (vm_f, vm_t, va_f, va_t; a branch from a bus to itself lists both occurrences of a variable, in that order)
+void cx_prepare(EvalState& e, int64_t cap) {
+    if (e.family == NlpFamily::EXPR) cap = 1;
+    if (e.cx_cap >= cap) return;
+    BufPool& M = e.mem;
+    const int64_t n = e.F.n, R = e.nlp_rows, nl = R / 4, nd = e.n_dpar;
+    if (!e.d_cx_vptr && e.family != NlpFamily::DENSE) {
+        std::vector<std::pair<int64_t, int64_t>> occ;      // (variable, what its list names) in list order
+        if (e.family == NlpFamily::EXPR) {
+            const ExprTape& X = e.X;
+            const std::vector<int64_t> ptr = hs_download(X.ptr, X.R + X.T + 1), ta = hs_download(X.a, X.L);
+            const std::vector<int32_t> top = hs_download(X.op, X.L);
+            for (int64_t t = 0; t < X.R + X.T; ++t)
+                for (int64_t k = ptr[t + 1] - 1; k >= ptr[t]; --k)
+                    if (top[k] == ASM_OP_VAR) occ.emplace_back(ta[k], k);
+        } else {
+            const std::vector<int64_t> ip = hs_download(e.d_ipar, 7 + 2 * nl);
+            const int64_t base[4] = {ip[2], ip[2], ip[1], ip[1]};      // vm0, vm0, va0, va0
+            for (int64_t l = 0; l < nl; ++l)
+                for (int q = 0; q < 4; ++q) occ.emplace_back(base[q] + ip[7 + (q & 1) * nl + l], q * nl + l);
+        }
+        std::vector<int64_t> vptr(n + 1, 0), vnode(occ.size());
+        for (const auto& o : occ) ++vptr[o.first + 1];
+        for (int64_t j = 0; j < n; ++j) vptr[j + 1] += vptr[j];
+        std::vector<int64_t> fill(vptr.begin(), vptr.end() - 1);
+        for (const auto& o : occ) vnode[fill[o.first]++] = o.second;
+        M.upload(e.d_cx_vptr, vptr.data(), n + 1); M.upload(e.d_cx_vnode, vnode.data(), (int64_t)vnode.size());
+    }
+    if (e.family == NlpFamily::EXPR) {      // (cx_cap was 0: once) the sweep's node arrays
+        ExprCross& C = e.cx_C;
+        const int64_t L = e.X.L;
+        C.vptr = e.d_cx_vptr; C.vnode = e.d_cx_vnode;
+        M.zeroed(C.val, L); M.zeroed(C.tval, L); M.zeroed(C.adj, L); M.zeroed(C.tadj, L); M.zeroed(C.vocc, L);
+    }
+    if (e.family == NlpFamily::OHM) M.zeroed(e.d_cx_occ, cap * 4 * nl);
+    M.zeroed(e.d_cx_in, R + cap * nd); M.zeroed(e.d_cx_out, cap * (n + R));
+    if (!e.h_cx) M.alloc(e.h_cx, 2 * (n + R) + nd, BufPool::PINNED);
+    e.cx_cap = cap;
+}
+// the workspace of the transposed cross derivatives for `cap` columns: 1 for asm_eval_data_cross_t and asm_solution_adjoint, KKM_CW from
+// the first multi call on (the narrower ones stay in the pool).  A tape borrows the node arrays of the cross sweep (cx_prepare)
+void ct_prepare(EvalState& e, int64_t cap) {
+    if (e.ct_cap >= cap) return;
+    if (e.family == NlpFamily::EXPR) cx_prepare(e, 1);
+    const int64_t n = e.F.n, R = e.nlp_rows, nd = e.n_dpar;
+    BufPool& M = e.mem;
+    M.zeroed(e.d_ct_in, R + cap * (n + R)); M.zeroed(e.d_ct_out, cap * nd);
+    M.alloc(e.h_ct, n + R + cap * (n + R + nd), BufPool::PINNED);
+    e.ct_cap = cap;
+}
+// where kkt_stage_rhs wants the cross derivatives of a chunk: column c as the right-hand sides b_ru + c ldn and, on the working rows, rww + c ldT
+struct CxRhs { const int* wrow; int64_t nW; double* b_ru; int64_t ldn; double* rww; int64_t ldT; };
+// Cross derivatives (u, w) of `cols` <= cx_cap directions at d_xt, with the block's multipliers in d_cx_in: u = d/dc (grad_x L) . dc,
+// w = (dg/dc) . dc, L = f - lambda' g.  hd: the directions in pinned memory (pitch n_dpar), uploaded here; null: one direction, already
+// behind the multipliers.  to: every column on into the right-hand sides of a KKT solve; null: it stays in d_cx_out = [u (n) | w (R)].
+// The kernels take the columns at once (grid.y = column): one upload, one launch and a gather (Ohm's law) or two launches (dense).  The
+// tape has one column: per direction its upload, its launch pair and its hand-over, no synchronisation between them.  A column's answer
+// depends on its own direction only
+void nlp_cross_launch(const EvalState& e, hipStream_t s, int cols, const double* hd, const CxRhs* to) {
+    const int64_t n = e.F.n, R = e.nlp_rows, r0 = e.F.n_rows, nd = e.n_dpar, ldo = n + R, nl = R / 4;
+    const double* lam = e.d_cx_in;
+    double* dc = e.d_cx_in + R;
+    const unsigned nc = (unsigned)cols;
+    const dim3 gto = asmb::blocks(to ? std::max(n, to->nW) : 0);
+    if (e.family == NlpFamily::EXPR) {
+        for (int c = 0; c < cols; ++c) {
+            if (hd) HIPCHK(asmb::copy_async(dc, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
+            asmb::launch(k_nlp_expr_cross, asmb::blocks(R + e.X.T), dim3(256), s, e.X, e.cx_C, e.d_xt, dc, lam, e.F.objective_scale, e.d_cx_out + n);
+            asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, e.cx_C, n, e.d_cx_out);
+            if (to) asmb::launch(k_kktm_cross_rhs, gto, dim3(256), s, e.d_cx_out, n, r0, to->wrow, to->nW, to->b_ru + (int64_t)c * to->ldn, to->rww + (int64_t)c * to->ldT);
+        }
+        return;
+    }
+    if (hd) HIPCHK(asmb::copy_async(dc, hd, (int64_t)cols * nd * sizeof(double), hipMemcpyHostToDevice, s));
+    if (e.family == NlpFamily::OHM) {
+        asmb::launch(k_nlp_ohm_cross, dim3(asmb::blocks(nl).x, nc), dim3(256), s, e.d_ipar, e.d_xt, dc, nd, lam, e.d_cx_occ, e.d_cx_out, n, ldo);
+        asmb::launch(k_nlp_block_cross_gather, dim3(asmb::blocks(n).x, nc), dim3(256), s, e.d_cx_vptr, e.d_cx_vnode, e.d_cx_occ, 4 * nl, n, e.d_cx_out, ldo);
+    } else {
+        asmb::launch(k_nlp_dense_cross_w, dim3(asmb::blocks(R, 4).x, nc), dim3(256), s, dc, nd, R, n, e.d_xt, e.d_cx_out, ldo);
+        asmb::launch(k_nlp_dense_cross_u, dim3(asmb::blocks(n).x, nc), dim3(256), s, dc, nd, R, n, e.d_xt, lam, e.d_cx_out, ldo);
+    }
+    if (to) asmb::launch(k_kktm_cross_rhs_cols, dim3(gto.x, nc), dim3(256), s, e.d_cx_out, ldo, n, r0, to->wrow, to->nW, to->b_ru, to->ldn, to->rww, to->ldT);
+}
+// Transposed cross derivatives of `cols` <= ct_cap weight columns [vx (n) | vl (R)] at d_ct_in + R, at d_xt and with the block's
+// multipliers in d_ct_in: column c of d_ct_out (pitch n_dpar).  The kernels take the columns at once (grid.y = column), the tape one
+// launch pair per column
+void nlp_cross_t_launch(const EvalState& e, hipStream_t s, int cols) {
+    const int64_t n = e.F.n, R = e.nlp_rows, nd = e.n_dpar, ldv = n + R;
+    const double *lam = e.d_ct_in, *dv = e.d_ct_in + R;
+    if (e.family == NlpFamily::OHM) asmb::launch(k_nlp_ohm_cross_t, dim3(asmb::blocks(R / 4).x, (unsigned)cols), dim3(256), s, e.d_ipar, e.d_xt, lam, dv, ldv, n, e.d_ct_out, nd);
+    if (e.family == NlpFamily::DENSE) asmb::launch(k_nlp_dense_cross_t, dim3(asmb::blocks(R * n).x, (unsigned)cols), dim3(256), s, R, n, e.d_xt, lam, dv, ldv, e.d_ct_out, nd);
+    for (int c = 0; e.family == NlpFamily::EXPR && c < cols; ++c) {
+        const double* v = dv + (int64_t)c * ldv;
+        asmb::launch(k_nlp_expr_cross_t, asmb::blocks(R + e.X.T), dim3(256), s, e.X, e.cx_C, e.d_xt, v, lam, v + n, e.F.objective_scale, e.d_cocc);
+        nlp_expr_data_gather(e, s, e.d_ct_out + (int64_t)c * nd);
+    }
+}
 
 // Pitches and lengths of the buffers of the null-space form that do not depend on the null-space dimension, for an LP with nE hard equality
 // rows and nI inequality rows (do_setup allocates by them; Solver::nsv places the work vectors).  theta~ = [n-part (ldn) | I-part (nIp)], a row
@@ -4028,29 +4360,13 @@ void ev_launch(asm_handle* h, const double* xd, double* Ed, double* fd, bool ful
     const EvalState& e = *h->ev;
     const FnStore& F = e.F;
     const unsigned nt = (unsigned)ntrial;
-    if (F.n_rows > 0)
-        asmb::launch(k_fn_rows, dim3((unsigned)((F.n_rows + 255) / 256), nt), dim3(256), h->stream, F, xd, Ed, h->sk->d_dE, full ? 1 : 0, ldx, ldE);
-    const ExprTape& X = e.X;
-    const bool expr_obj = e.nlp_kind == ASM_NLP_EXPR && X.T > 0;     // the expression objective replaces the store's objective row
-    if (!expr_obj) {
+    fn_rows_launch(e, h->stream, xd, Ed, h->sk->d_dE, full ? 1 : 0, nt, ldx, ldE);
+    if (!nlp_has_objective(e)) {
         asmb::launch(k_fn_objective, dim3(nt), dim3(256), h->stream, F, xd, fd, ldx);
         if (full) asmb::launch(k_fn_gradient, asmb::blocks(h->sk->n), dim3(256), h->stream, F, xd, e.d_df);
     }
-    if (e.nlp_kind == ASM_NLP_EXPR) {
-        if (X.R > 0)
-            asmb::launch(k_nlp_expr_rows, dim3((unsigned)((X.R + 255) / 256), nt), dim3(256), h->stream, X, xd, Ed, h->sk->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
-        if (expr_obj) {
-            asmb::launch(k_nlp_expr_terms, dim3((unsigned)((X.T + 255) / 256), nt), dim3(256), h->stream, X, xd, full ? 1 : 0, ldx);
-            asmb::launch(k_nlp_expr_objective, dim3(nt), dim3(64), h->stream, X, F.objective_scale, fd);
-            if (full) asmb::launch(k_nlp_expr_gradient, asmb::blocks(h->sk->n), dim3(256), h->stream, X, F.objective_scale, e.d_df);
-        }
-    } else if (nlp_is_ohm(e.nlp_kind)) {
-        const int64_t nl = e.nlp_rows / 4;
-        asmb::launch(k_nlp_acopf_ohm, dim3((unsigned)((nl + 255) / 256), nt), dim3(256), h->stream, e.d_ipar, e.d_dpar, xd, Ed, h->sk->d_dE, F.n_rows, e.fn_nnz, full ? 1 : 0, ldx, ldE);
-    } else if (nlp_is_dense(e.nlp_kind)) {
-        asmb::launch(k_nlp_dense_quadratic, dim3((unsigned)((e.nlp_rows + 3) / 4), nt), dim3(256), h->stream, e.d_dpar, e.nlp_rows, h->sk->n, xd, Ed, h->sk->d_dE, F.n_rows,
-                     e.fn_nnz, full ? 1 : 0, ldx, ldE);
-    }
+    nlp_rows_launch(e, h->stream, xd, Ed, h->sk->d_dE, full ? 1 : 0, nt, ldx, ldE);
+    nlp_objective_launch(e, h->stream, xd, fd, full ? 1 : 0, nt, ldx);
 }
 // the evaluation results and the bounds for the reduction kernels; norms: also what k_slp_norms alone reads
 SlpVecs ev_vecs(const EvalState& e, bool norms = false) {
@@ -4285,13 +4601,7 @@ int asm_kt_residuals(asm_handle* h, const double* df, const double* lambda, cons
 
 // --------------------------------------------------------------------------------- device-side evaluators (rows a2 / f3)
 namespace {
-// the host-side form of an expression block (include/asm_hip.h, "Expression block") after validation: node references absolute,
-// the slots of the VAR nodes (rows: Jacobian value from j0; terms: position in the per-variable gradient list)
-struct ExprHost {
-    int64_t R = 0, T = 0, L = 0;
-    std::vector<int64_t> ptr, jptr, a, b, slot, gptr, cptr;   // cptr [n_dpar+1]: the CONST nodes grouped by dpar index (empty: no CONST node)
-    std::vector<int32_t> op;
-};
+// an expression block (include/asm_hip.h, "Expression block") validated into its host-side form xh
 void expr_prepare(const asm_handle* h, ExprHost& xh, int64_t n_rows, int64_t fn_nnz, int64_t nlp_rows, int64_t nlp_nnz, const int64_t* ip, int64_t n_ipar,
                   int64_t n_dpar) {
     auto bad = [](const std::string& what) { throw std::invalid_argument("asm_eval_setup: expression block: " + what); };
@@ -4385,11 +4695,9 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     const int64_t fn_nnz = jac_off[n_rows];
     if (n_rows + nlp_rows != K.m || fn_nnz + nlp_nnz != K.nnz)
         throw std::invalid_argument("asm_eval_setup: row / Jacobian-entry counts do not match asm_sublp_setup");
-    if (nlp_is_ohm(nlp_kind) && (nlp_rows % 4 != 0 || nlp_nnz != 5 * nlp_rows || n_ipar != 7 + 2 * (nlp_rows / 4) || n_dpar != 8 * (nlp_rows / 4)))
-        throw std::invalid_argument("asm_eval_setup: ACOPF block parameter sizes");
-    if (nlp_is_dense(nlp_kind) && (nlp_nnz != nlp_rows * K.n || n_dpar != 2 * nlp_rows * K.n)) throw std::invalid_argument("asm_eval_setup: dense block parameter sizes");
+    nlp_check_sizes(nlp_kind, K.n, nlp_rows, nlp_nnz, n_ipar, n_dpar);
     ExprHost xh;
-    if (nlp_kind == ASM_NLP_EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
+    if (nlp_family(nlp_kind) == NlpFamily::EXPR) expr_prepare(h, xh, n_rows, fn_nnz, nlp_rows, nlp_nnz, nlp_ipar, n_ipar, n_dpar);   // all checks before any state changes
     HIPCHK(hipSetDevice(h->device));
     h->lm.drop();
     h->ev.reset();                  // the old evaluator goes before the new one is made; a failure below leaves the handle without one
@@ -4402,40 +4710,12 @@ static void do_eval_setup(asm_handle* h, int64_t n_rows, const int64_t* aff_ptr,
     P.upload(F.quad_ptr, quad_ptr, n_rows + 2); P.upload(F.q_v1, q_v1, nq); P.upload(F.q_v2, q_v2, nq); P.upload(F.q_coef, q_coef, nq);
     P.upload(F.constant, constant, n_rows + 1); P.upload(F.jac_off, jac_off, n_rows + 1);
     P.upload(F.g_ptr, g_ptr, K.n + 1); P.upload(F.g_kind, g_kind, ng); P.upload(F.g_coef, g_coef, ng); P.upload(F.g_other, g_other, ng);
-    e->nlp_kind = nlp_kind; e->nlp_rows = nlp_rows; e->fn_nnz = fn_nnz; e->n_dpar = n_dpar;
+    e->nlp_rows = nlp_rows; e->fn_nnz = fn_nnz; e->n_dpar = n_dpar;
     P.upload(e->d_ipar, nlp_ipar, n_ipar); P.upload(e->d_dpar, nlp_dpar, n_dpar);
     const int64_t n = K.n, m = K.m;      // (the pool makes an empty vector one element long)
     P.zeroed(e->d_x, n); P.zeroed(e->d_xt, 8 * round_up(n, 32)); P.zeroed(e->d_df, n); P.zeroed(e->d_E, m);
     P.zeroed(e->d_Et, 8 * round_up(std::max<int64_t>(m, 1), 32)); P.zeroed(e->d_f, 16);      // xt / Et / f[1..8]: eight trial points of the batched line search
-    if (nlp_kind == ASM_NLP_EXPR) {
-        ExprTape& X = e->X;
-        X.R = xh.R; X.T = xh.T; X.L = xh.L; X.n = K.n;
-        P.upload(X.ptr, xh.ptr.data(), (int64_t)xh.ptr.size()); P.upload(X.jptr, xh.jptr.data(), (int64_t)xh.jptr.size());
-        P.upload(X.a, xh.a.data(), xh.L); P.upload(X.b, xh.b.data(), xh.L); P.upload(X.slot, xh.slot.data(), xh.L);
-        P.upload(X.op, xh.op.data(), xh.L); P.upload(X.gptr, xh.gptr.data(), (int64_t)xh.gptr.size());
-        X.cst = e->d_dpar;
-        // workspace, sized here once: node values of 8 trial points, one set of adjoints, term values of 8 points, term adjoints
-        P.zeroed(X.val, 8 * xh.L); P.zeroed(X.adj, xh.L);
-        P.zeroed(X.tval, 8 * xh.T); P.zeroed(X.gocc, xh.gptr[K.n]);
-        if (!xh.cptr.empty()) {     // the data gradient's occurrence list, multipliers of the rows and result (tapes with constants only)
-            P.upload(e->d_cptr, xh.cptr.data(), n_dpar + 1);
-            P.zeroed(e->d_cocc, xh.cptr[n_dpar]); P.zeroed(e->d_lam, xh.R); P.zeroed(e->d_dgrad, n_dpar);
-            P.alloc(e->h_dgrad, n_dpar, BufPool::PINNED);
-        }
-    }
-    if (nlp_block_derivs(nlp_kind)) {      // the data gradient's multipliers and result: a batch calls it inside fibers and must not allocate there
-        P.zeroed(e->d_lam, nlp_rows); P.zeroed(e->d_dgrad, n_dpar);
-        P.alloc(e->h_dgrad, n_dpar, BufPool::PINNED);
-        if (nlp_kind == ASM_NLP_ACOPF_OHM_HESS) {
-            const int64_t nl = nlp_rows / 4;
-            bool ok = nlp_ipar && nlp_ipar[0] == nl;
-            for (int64_t l = 0; ok && l < 2 * nl; ++l) {
-                const int64_t b = nlp_ipar[7 + l];
-                ok = nlp_ipar[1] + b >= 0 && nlp_ipar[1] + b < n && nlp_ipar[2] + b >= 0 && nlp_ipar[2] + b < n;
-            }
-            e->ohm_vars_ok = ok;
-        }
-    }
+    nlp_setup(*e, nlp_kind, xh, nlp_ipar);
     e->L = EvLayout{n, m, K.ldn, K.Mp};      // the reductions' block with the bounds in it, and the staging buffer
     P.zeroed(e->L.d, e->L.len());
     ev_write_bounds(h, e->L);
@@ -4496,49 +4776,29 @@ static void do_set_data(asm_handle* h, int64_t offset, int64_t count, const doub
 
 // the kinds with data derivatives: expression blocks and the block kernels that announce their derivative entries (kinds 4 and 5)
 static void data_kind_check(const EvalState& e, const char* who, const char* what) {
-    if (e.nlp_kind != ASM_NLP_EXPR && !nlp_block_derivs(e.nlp_kind))
-        throw std::invalid_argument(std::string(who) + ": " + what + " exist for expression blocks (nlp_kind 3) only");
+    if (!e.has_data) throw std::invalid_argument(std::string(who) + ": " + what + " exist for expression blocks (nlp_kind 3) only");
     if (!e.ohm_vars_ok) throw std::invalid_argument(std::string(who) + ": the Ohm's-law block names a variable outside [0, n)");
 }
-// out[c] = d(f - lambda' g) / d dpar[c] at x for an expression block (k_nlp_expr_const_adj + k_nlp_expr_data_gather) or a block kernel with
-// derivative entries (one launch of k_nlp_ohm_data_grad / k_nlp_dense_data_grad); the inputs of the next LP are not touched (x goes where
+// out[c] = d(f - lambda' g) / d dpar[c] at x (nlp_data_grad_launch); the inputs of the next LP are not touched (x goes where
 // asm_eval_constraints puts its trial point)
 static void do_data_gradient(asm_handle* h, const double* x, const double* lambda, double* out) {
     EvalState& e = ev_of(h, "asm_eval_data_gradient");
     data_kind_check(e, "asm_eval_data_gradient", "data gradients");
     if (!x || (h->sk->m > 0 && !lambda) || (e.n_dpar > 0 && !out)) throw std::invalid_argument("asm_eval_data_gradient: null pointer");
-    const int64_t n = h->sk->n, nd = e.n_dpar;
-    if (nlp_block_derivs(e.nlp_kind)) {
-        if (nd == 0) return;
-        HIPCHK(hipSetDevice(h->device));
-        const int64_t R = e.nlp_rows;
-        double *st = e.h_stage, *s_lam = st + e.L.st_lam();
-        std::memcpy(st, x, n * sizeof(double));
-        std::memcpy(s_lam, lambda + e.F.n_rows, R * sizeof(double));
-        HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(asmb::copy_async(e.d_lam, s_lam, R * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (nlp_is_ohm(e.nlp_kind)) asmb::launch(k_nlp_ohm_data_grad, asmb::blocks(R / 4), dim3(256), h->stream, e.d_ipar, e.d_xt, e.d_lam, e.d_dgrad);
-        else asmb::launch(k_nlp_dense_data_grad, asmb::blocks(R * n), dim3(256), h->stream, R, n, e.d_xt, e.d_lam, e.d_dgrad);
-        HIPCHK(asmb::copy_async(e.h_dgrad, e.d_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(asmb::sync(h->stream));
-        std::memcpy(out, e.h_dgrad, nd * sizeof(double));
-        return;
-    }
-    if (!e.d_cocc) {            // no CONST node: nothing depends on the data
+    const int64_t n = h->sk->n, nd = e.n_dpar, R = e.nlp_rows;
+    if (!e.data_dep) {          // nothing depends on the data
         for (int64_t c = 0; c < nd; ++c) out[c] = 0.0;
         return;
     }
     HIPCHK(hipSetDevice(h->device));
-    const ExprTape& X = e.X;
     double *st = e.h_stage, *s_lam = st + e.L.st_lam();
     std::memcpy(st, x, n * sizeof(double));
     HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (X.R > 0) {
-        std::memcpy(s_lam, lambda + e.F.n_rows, X.R * sizeof(double));
-        HIPCHK(asmb::copy_async(e.d_lam, s_lam, X.R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (R > 0) {                // (a tape of objective terms alone has no rows)
+        std::memcpy(s_lam, lambda + e.F.n_rows, R * sizeof(double));
+        HIPCHK(asmb::copy_async(e.d_lam, s_lam, R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    asmb::launch(k_nlp_expr_const_adj, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, e.d_xt, e.d_lam, e.F.objective_scale, e.d_cocc);
-    asmb::launch(k_nlp_expr_data_gather, asmb::blocks(nd), dim3(256), h->stream, e.d_cptr, e.d_cocc, nd, e.d_dgrad);
+    nlp_data_grad_launch(e, h->stream);
     HIPCHK(asmb::copy_async(e.h_dgrad, e.d_dgrad, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
     std::memcpy(out, e.h_dgrad, nd * sizeof(double));
@@ -4546,67 +4806,10 @@ static void do_data_gradient(asm_handle* h, const double* x, const double* lambd
 
 // ---- Hessian of the Lagrangian (include/asm_hip.h, "Hessian of the Lagrangian")
 namespace {
-extern "C++" {
-template <class T>
-std::vector<T> hs_download(const T* dev, int64_t count) {
-    std::vector<T> v((size_t)std::max<int64_t>(count, 0));
-    if (count > 0) HIPCHK(asmb::copy(v.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
-    return v;
-}
-}
-// the interaction set P(last node) of the row or term with nodes [k0, k1) (absolute references), as pairs (j, i), j <= i, sorted by (j, i):
-// the union over the nodes the last one depends on of what each op adds (the header's rule; POW / ATAN2 cover their operands' sets)
-void hs_row_pairs(const int32_t* op, const int64_t* a, const int64_t* b, int64_t k0, int64_t k1, std::vector<std::vector<int64_t>>& L, std::vector<char>& reach,
-                  std::vector<std::pair<int64_t, int64_t>>& P) {
-    const int64_t len = k1 - k0;
-    if ((int64_t)L.size() < len) L.resize(len);
-    reach.assign(len, 0);
-    reach[len - 1] = 1;
-    for (int64_t q = len - 1; q >= 0; --q) {
-        const int32_t o = op[k0 + q];
-        if (!reach[q] || o == ASM_OP_CONST || o == ASM_OP_VAR) continue;
-        reach[a[k0 + q] - k0] = 1;
-        if ((o >= ASM_OP_ADD && o <= ASM_OP_DIV) || o >= ASM_OP_POW) reach[b[k0 + q] - k0] = 1;
-    }
-    P.clear();
-    auto cross = [&P](const std::vector<int64_t>& A, const std::vector<int64_t>& B) {
-        for (int64_t i : A)
-            for (int64_t j : B) P.emplace_back(std::min(i, j), std::max(i, j));
-    };
-    for (int64_t q = 0; q < len; ++q) {
-        const int64_t k = k0 + q;
-        const int32_t o = op[k];
-        std::vector<int64_t>& Lq = L[q];
-        Lq.clear();
-        if (o == ASM_OP_CONST) continue;
-        if (o == ASM_OP_VAR) { Lq.push_back(a[k]); continue; }
-        const std::vector<int64_t>& La = L[a[k] - k0];
-        const bool binary = (o >= ASM_OP_ADD && o <= ASM_OP_DIV) || o >= ASM_OP_POW;
-        if (!binary) Lq = La;
-        else {
-            const std::vector<int64_t>& Lb = L[b[k] - k0];
-            Lq.resize(La.size() + Lb.size());
-            Lq.erase(std::set_union(La.begin(), La.end(), Lb.begin(), Lb.end(), Lq.begin()), Lq.end());
-        }
-        if (!reach[q]) continue;
-        switch (o) {
-            case ASM_OP_ADD: case ASM_OP_SUB: case ASM_OP_NEG: case ASM_OP_MIN: case ASM_OP_MAX: break;
-            case ASM_OP_MUL: cross(La, L[b[k] - k0]); break;
-            case ASM_OP_DIV: cross(La, L[b[k] - k0]); cross(L[b[k] - k0], L[b[k] - k0]); break;
-            case ASM_OP_POWI: if (b[k] != 1) cross(La, La); break;
-            case ASM_OP_POW: case ASM_OP_ATAN2: cross(Lq, Lq); break;
-            default: cross(La, La); break;       // every other unary op
-        }
-    }
-    std::sort(P.begin(), P.end());
-    P.erase(std::unique(P.begin(), P.end()), P.end());
-}
 // pattern, seed threads, occurrence and product lists of h's store and tape (downloaded with blocking copies: not inside a batch fiber) into sh
 void hs_build(const asm_handle* h, HsShared& sh) {
     HIPCHK(hipSetDevice(h->device));
     const FnStore& F = h->ev->F;
-    const ExprTape& X = h->ev->X;
-    const bool expr = h->ev->nlp_kind == ASM_NLP_EXPR;
     const int64_t nr = F.n_rows, n = h->sk->n;
     // 1. function store: the objective row's quadratic terms (unless the block has the objective), then the rows' in row order
     const std::vector<int64_t> qptr = hs_download(F.quad_ptr, nr + 2);
@@ -4615,68 +4818,24 @@ void hs_build(const asm_handle* h, HsShared& sh) {
     auto store_row = [&](int64_t r, int64_t tag) {
         for (int64_t k = qptr[r]; k < qptr[r + 1]; ++k) { rows.push_back(q1[k] + 1); cols.push_back(q2[k] + 1); qterm.push_back(k); qrow.push_back(tag); }
     };
-    if (!(expr && X.T > 0)) store_row(nr, -1);
+    if (!nlp_has_objective(*h->ev)) store_row(nr, -1);
     for (int64_t r = 0; r < nr; ++r) store_row(r, r);
     const int64_t nfn = (int64_t)rows.size();
-    // 2. expression block: per row / term its interaction set, one seed thread per smaller index j with its occurrence list (i ascending)
-    std::vector<int64_t> srow, svar, woff, optr(1, 0), ovar, okey;
-    int64_t wnodes = 0;
-    if (expr) {
-        const std::vector<int64_t> ptr = hs_download(X.ptr, X.R + X.T + 1), ta = hs_download(X.a, X.L), tb = hs_download(X.b, X.L);
-        const std::vector<int32_t> top = hs_download(X.op, X.L);
-        std::vector<std::vector<int64_t>> L;
-        std::vector<char> reach;
-        std::vector<std::pair<int64_t, int64_t>> P;
-        for (int64_t t = 0; t < X.R + X.T; ++t) {
-            hs_row_pairs(top.data(), ta.data(), tb.data(), ptr[t], ptr[t + 1], L, reach, P);
-            for (size_t q = 0; q < P.size(); ++q) {
-                if (q == 0 || P[q].first != P[q - 1].first) {
-                    if (q) optr.push_back((int64_t)ovar.size());
-                    srow.push_back(t); svar.push_back(P[q].first); woff.push_back(wnodes);
-                    wnodes += ptr[t + 1] - ptr[t];
-                }
-                ovar.push_back(P[q].second);
-                okey.push_back(P[q].second * n + P[q].first);
-            }
-            if (!P.empty()) optr.push_back((int64_t)ovar.size());
-        }
-    }
-    // 2b. Ohm's-law block with second derivatives: ten occurrences per branch, listed by branch ascending and inside a branch in the order
-    // k_nlp_ohm_hess documents; occurrence q of branch l is at hocc[q * nl + l] (oslot: where a listed occurrence lives; empty = in place)
-    std::vector<int64_t> oslot;
-    if (h->ev->nlp_kind == ASM_NLP_ACOPF_OHM_HESS) {
-        const int64_t nl = h->ev->nlp_rows / 4;
-        const std::vector<int64_t> ip = hs_download(h->ev->d_ipar, 7 + 2 * nl);
-        const int64_t va0 = ip[1], vm0 = ip[2];
-        for (int64_t l = 0; l < nl; ++l) {
-            const int64_t fb = ip[7 + l], tb = ip[7 + nl + l];
-            const int64_t vf = vm0 + fb, vt = vm0 + tb, af = va0 + fb, at = va0 + tb;
-            if (ip[0] != nl || std::min({vf, vt, af, at}) < 0 || std::max({vf, vt, af, at}) >= n)
-                throw std::invalid_argument("asm_eval_hessian: the Ohm's-law block names a variable outside [0, n)");
-            if (fb == tb) throw std::invalid_argument("asm_eval_hessian: branch " + std::to_string(l) + " of the Ohm's-law block joins a bus to itself");
-            const int64_t pr[10][2] = {{vf, vf}, {vt, vt}, {vf, vt}, {vf, af}, {vf, at}, {vt, af}, {vt, at}, {af, af}, {at, at}, {af, at}};
-            for (int64_t q = 0; q < 10; ++q) {
-                okey.push_back(std::max(pr[q][0], pr[q][1]) * n + std::min(pr[q][0], pr[q][1]));
-                oslot.push_back(q * nl + l);
-            }
-        }
-    }
-    // 2c. dense quadratic block with second derivatives: the n diagonal entries, written by k_nlp_dense_hess itself (no occurrences)
-    const bool dense_hess = h->ev->nlp_kind == ASM_NLP_DENSE_QUADRATIC_HESS;
-    const int64_t S = (int64_t)srow.size(), nocc = (int64_t)okey.size();
+    // 2. the block: its seed threads, occurrences and the entries its launch writes in place
+    const HsBlockLists B = nlp_hess_lists(*h->ev);
+    const int64_t S = (int64_t)B.srow.size(), nocc = (int64_t)B.okey.size();
     // the block's entries: the distinct pairs (i, j), i >= j, sorted by (i, j); every entry's occurrences in list order
-    std::vector<int64_t> keys(okey);
-    if (dense_hess)
-        for (int64_t j = 0; j < n; ++j) keys.push_back(j * n + j);
+    std::vector<int64_t> keys(B.okey);
+    keys.insert(keys.end(), B.own.begin(), B.own.end());
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
     const int64_t nblk = (int64_t)keys.size();
     std::vector<int64_t> eptr(nblk + 1, 0), eocc(nocc), oent(nocc);
-    for (int64_t o = 0; o < nocc; ++o) { oent[o] = std::lower_bound(keys.begin(), keys.end(), okey[o]) - keys.begin(); ++eptr[oent[o] + 1]; }
+    for (int64_t o = 0; o < nocc; ++o) { oent[o] = std::lower_bound(keys.begin(), keys.end(), B.okey[o]) - keys.begin(); ++eptr[oent[o] + 1]; }
     for (int64_t e = 0; e < nblk; ++e) eptr[e + 1] += eptr[e];
     {
         std::vector<int64_t> fill(eptr.begin(), eptr.end() - 1);
-        for (int64_t o = 0; o < nocc; ++o) eocc[fill[oent[o]]++] = oslot.empty() ? o : oslot[o];
+        for (int64_t o = 0; o < nocc; ++o) eocc[fill[oent[o]]++] = B.oslot.empty() ? o : B.oslot[o];
     }
     for (int64_t e = 0; e < nblk; ++e) { rows.push_back(keys[e] / n + 1); cols.push_back(keys[e] % n + 1); }
     const int64_t nnz = nfn + nblk;
@@ -4699,10 +4858,10 @@ void hs_build(const asm_handle* h, HsShared& sh) {
     M.upload(sh.eptr, eptr.data(), nblk + 1); M.upload(sh.eocc, eocc.data(), nocc);
     M.upload(sh.pptr, pptr.data(), n + 1); M.upload(sh.pent, pent.data(), pptr[n]); M.upload(sh.poth, poth.data(), pptr[n]);
     if (S > 0) {
-        M.upload(sh.srow, srow.data(), S); M.upload(sh.svar, svar.data(), S); M.upload(sh.woff, woff.data(), S);
-        M.upload(sh.optr, optr.data(), S + 1); M.upload(sh.ovar, ovar.data(), nocc);
+        M.upload(sh.srow, B.srow.data(), S); M.upload(sh.svar, B.svar.data(), S); M.upload(sh.woff, B.woff.data(), S);
+        M.upload(sh.optr, B.optr.data(), S + 1); M.upload(sh.ovar, B.ovar.data(), nocc);
     }
-    sh.nfn = nfn; sh.wnodes = wnodes; sh.S = S; sh.nocc = nocc;
+    sh.nfn = nfn; sh.wnodes = B.wnodes; sh.S = S; sh.nocc = nocc;
     sh.rows.swap(rows); sh.cols.swap(cols);
 }
 // the handle's own part on the lists of sh: the four node arrays, hocc and the value / product vectors.  Inside a batch fiber the clearing
@@ -4714,12 +4873,11 @@ void hs_attach(asm_handle* h, const HsShared* sh) {
     auto zeroed = [&](double*& f, int64_t count) { if (rec) M.zeroed(f, count, h->stream); else M.zeroed(f, count); };
     ExprHess& H = e.hs_H;          // (empty: the state is new, or hs_forget cleared it)
     H.S = sh->S;
-    if (sh->S > 0) {
+    if (sh->S > 0) {               // seed threads (a tape): their lists and four node arrays
         H.srow = sh->srow; H.svar = sh->svar; H.woff = sh->woff; H.optr = sh->optr; H.ovar = sh->ovar;
-        zeroed(H.val, sh->wnodes); zeroed(H.tval, sh->wnodes); zeroed(H.adj, sh->wnodes); zeroed(H.tadj, sh->wnodes); zeroed(H.hocc, sh->nocc);
-    } else if (sh->nocc > 0) {
-        zeroed(H.hocc, sh->nocc);      // the Ohm's-law block: [10][nl] occurrences, no node arrays
+        zeroed(H.val, sh->wnodes); zeroed(H.tval, sh->wnodes); zeroed(H.adj, sh->wnodes); zeroed(H.tadj, sh->wnodes);
     }
+    if (sh->nocc > 0) zeroed(H.hocc, sh->nocc);      // the occurrences the block's launch writes, whatever lists them (nlp_hess_lists)
     zeroed(e.d_hs_lam, h->sk->m); zeroed(e.d_hs_v, h->sk->n); zeroed(e.d_hs_vals, sh->nnz()); zeroed(e.d_hs_out, h->sk->n);
     M.alloc(e.h_hs, std::max(sh->nnz(), h->sk->n), BufPool::PINNED);
     e.hs_sh = sh;
@@ -4735,7 +4893,7 @@ void hs_prepare(asm_handle* h) {
 }
 void hs_check(const asm_handle* h, const char* who) {
     const EvalState& e = ev_of(h, who);
-    if (e.nlp_kind == ASM_NLP_ACOPF_OHM || e.nlp_kind == ASM_NLP_DENSE_QUADRATIC)       // (their twins with second derivatives: kinds 4 and 5)
+    if (!e.has_hess)
         throw std::invalid_argument(std::string(who) + ": second derivatives exist for the function store alone (nlp_kind 0) or with an expression block (nlp_kind 3)");
 }
 // the values at (x, obj_factor, lambda) into d_hs_vals; with v also H v into d_hs_out.  x goes where asm_eval_constraints puts its trial
@@ -4759,16 +4917,7 @@ void hs_launch(asm_handle* h, const double* x, double obj_factor, const double* 
     }
     const double wobj = obj_factor * e.F.objective_scale;
     if (nfn > 0) asmb::launch(k_fn_hessian, asmb::blocks(nfn), dim3(256), h->stream, L.qterm, L.qrow, e.F.q_coef, e.d_hs_lam, wobj, nfn, e.d_hs_vals);
-    if (e.hs_H.S > 0) {
-        asmb::launch(k_nlp_expr_hess, asmb::blocks(e.hs_H.S), dim3(256), h->stream, e.X, e.hs_H, e.d_xt, e.d_hs_lam + e.F.n_rows, wobj);
-        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, e.hs_H.hocc, nnz - nfn, e.d_hs_vals + nfn);
-    } else if (e.nlp_kind == ASM_NLP_ACOPF_OHM_HESS && L.nocc > 0) {
-        // (ipar / dpar read live: asm_eval_set_data and a scenario's table row take effect with nothing cached)
-        asmb::launch(k_nlp_ohm_hess, asmb::blocks(e.nlp_rows / 4), dim3(256), h->stream, e.d_ipar, e.d_dpar, e.d_xt, e.d_hs_lam + e.F.n_rows, e.hs_H.hocc);
-        asmb::launch(k_nlp_expr_hess_gather, asmb::blocks(nnz - nfn), dim3(256), h->stream, L.eptr, L.eocc, e.hs_H.hocc, nnz - nfn, e.d_hs_vals + nfn);
-    } else if (e.nlp_kind == ASM_NLP_DENSE_QUADRATIC_HESS && n > 0) {
-        asmb::launch(k_nlp_dense_hess, asmb::blocks(n), dim3(256), h->stream, e.d_dpar, e.nlp_rows, n, e.d_hs_lam + e.F.n_rows, e.d_hs_vals + nfn);
-    }
+    nlp_hess_launch(e, h->stream, L, e.d_hs_lam + e.F.n_rows, wobj, nnz - nfn, e.d_hs_vals + nfn);
     if (v) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), h->stream, L.pptr, L.pent, L.poth, e.d_hs_vals, e.d_hs_v, n, e.d_hs_out);
 }
 void hs_pattern(const HsShared& sh, int64_t* nnz, int64_t* rows, int64_t* cols) {
@@ -4808,169 +4957,55 @@ static void do_hessian_product(asm_handle* h, const double* x, double obj_factor
 
 // ---- cross derivatives with respect to the data (include/asm_hip.h, "Cross derivatives of an expression block")
 namespace {
-// Kinds 4 and 5: the lists come from ipar - per variable its occurrences of k_nlp_ohm_cross, branch ascending and inside a branch in slot
-// order (vm_f, vm_t, va_f, va_t; a branch from a bus to itself lists both occurrences of a variable, in that order) - and the column
-// buffers hold `cap` directions: 1 for asm_eval_data_cross, KKM_CW from the first multi call on (the narrower ones stay in the pool)
-void cx_prepare_block(asm_handle* h, int64_t cap) {
-    EvalState& e = *h->ev;
-    if (e.cx_cap >= cap) return;
-    HIPCHK(hipSetDevice(h->device));
-    BufPool& M = e.mem;
-    const int64_t n = h->sk->n, R = e.nlp_rows, nl = R / 4, nd = e.n_dpar;
-    const bool ohm = nlp_is_ohm(e.nlp_kind);
-    if (ohm && !e.d_cx_vptr) {
-        const std::vector<int64_t> ip = hs_download(e.d_ipar, 7 + 2 * nl);
-        const int64_t base[4] = {ip[2], ip[2], ip[1], ip[1]};      // vm0, vm0, va0, va0
-        auto var_of = [&](int64_t l, int q) { return base[q] + ip[7 + (q & 1) * nl + l]; };
-        std::vector<int64_t> vptr(n + 1, 0);
-        for (int64_t l = 0; l < nl; ++l)
-            for (int q = 0; q < 4; ++q) ++vptr[var_of(l, q) + 1];
-        for (int64_t j = 0; j < n; ++j) vptr[j + 1] += vptr[j];
-        std::vector<int64_t> vocc(4 * nl), fill(vptr.begin(), vptr.end() - 1);
-        for (int64_t l = 0; l < nl; ++l)
-            for (int q = 0; q < 4; ++q) vocc[fill[var_of(l, q)]++] = q * nl + l;
-        M.upload(e.d_cx_vptr, vptr.data(), n + 1); M.upload(e.d_cx_vnode, vocc.data(), 4 * nl);
-    }
-    if (ohm) M.zeroed(e.d_cx_occ, cap * 4 * nl);
-    M.zeroed(e.d_cx_in, R + cap * nd); M.zeroed(e.d_cx_out, cap * (n + R));
-    if (!e.h_cx) M.alloc(e.h_cx, 2 * (n + R) + nd, BufPool::PINNED);
-    e.cx_cap = cap;
-}
-// once per asm_eval_setup, at the first asm_eval_data_cross: the VAR nodes of every variable in (row, then term) order, node descending
-// inside a row or term, and the workspace (blocking copies: not inside a batch fiber)
-void cx_prepare(asm_handle* h, int64_t cap = 1) {
-    EvalState& e = *h->ev;
-    if (nlp_block_derivs(e.nlp_kind)) { cx_prepare_block(h, cap); return; }
-    if (e.h_cx) return;            // (the last buffer it makes)
-    HIPCHK(hipSetDevice(h->device));
-    const ExprTape& X = e.X;
-    const int64_t n = h->sk->n, nt = X.R + X.T;
-    const std::vector<int64_t> ptr = hs_download(X.ptr, nt + 1), ta = hs_download(X.a, X.L);
-    const std::vector<int32_t> top = hs_download(X.op, X.L);
-    std::vector<int64_t> vptr(n + 1, 0);
-    for (int64_t k = 0; k < X.L; ++k)
-        if (top[k] == ASM_OP_VAR) ++vptr[ta[k] + 1];
-    for (int64_t j = 0; j < n; ++j) vptr[j + 1] += vptr[j];
-    std::vector<int64_t> vnode(vptr[n]), fill(vptr.begin(), vptr.end() - 1);
-    for (int64_t t = 0; t < nt; ++t)
-        for (int64_t k = ptr[t + 1] - 1; k >= ptr[t]; --k)
-            if (top[k] == ASM_OP_VAR) vnode[fill[ta[k]]++] = k;
-    BufPool& M = e.mem;
-    ExprCross& C = e.cx_C;
-    M.upload(e.d_cx_vptr, vptr.data(), n + 1); M.upload(e.d_cx_vnode, vnode.data(), vptr[n]);
-    C.vptr = e.d_cx_vptr; C.vnode = e.d_cx_vnode;
-    M.zeroed(C.val, X.L); M.zeroed(C.tval, X.L); M.zeroed(C.adj, X.L); M.zeroed(C.tadj, X.L); M.zeroed(C.vocc, X.L);
-    M.zeroed(e.d_cx_in, X.R + e.n_dpar); M.zeroed(e.d_cx_out, n + X.R);
-    M.alloc(e.h_cx, 2 * (n + X.R) + e.n_dpar, BufPool::PINNED);
-}
-void cx_check(const asm_handle* h, const char* who) {
-    data_kind_check(ev_of(h, who), who, "cross derivatives");
-}
-// kinds 4 and 5: (u, w) of `cols` directions at d_cx_in + R (pitch n_dpar) into the columns [u (n) | w (R)] of d_cx_out, at the x in d_xt and
-// with the block's multipliers in d_cx_in - one launch and a gather (Ohm's law) or two launches (dense), grid.y = column.  A column's answer
-// depends on its own direction only.
-void cx_launch_block(asm_handle* h, int cols) {
-    EvalState& e = *h->ev;
-    const hipStream_t s = h->stream;
-    const int64_t n = h->sk->n, R = e.nlp_rows, nd = e.n_dpar, ldo = n + R;
-    const double *lam = e.d_cx_in, *dc = e.d_cx_in + R;
-    if (nlp_is_ohm(e.nlp_kind)) {
-        const int64_t nl = R / 4;
-        asmb::launch(k_nlp_ohm_cross, dim3(asmb::blocks(nl).x, (unsigned)cols), dim3(256), s, e.d_ipar, e.d_xt, dc, nd, lam, e.d_cx_occ, e.d_cx_out, n, ldo);
-        asmb::launch(k_nlp_block_cross_gather, dim3(asmb::blocks(n).x, (unsigned)cols), dim3(256), s, e.d_cx_vptr, e.d_cx_vnode, e.d_cx_occ, 4 * nl, n, e.d_cx_out, ldo);
-    } else {
-        asmb::launch(k_nlp_dense_cross_w, dim3(asmb::blocks(R, 4).x, (unsigned)cols), dim3(256), s, dc, nd, R, n, e.d_xt, e.d_cx_out, ldo);
-        asmb::launch(k_nlp_dense_cross_u, dim3(asmb::blocks(n).x, (unsigned)cols), dim3(256), s, dc, nd, R, n, e.d_xt, lam, e.d_cx_out, ldo);
-    }
-}
+void cx_check(const asm_handle* h, const char* who) { data_kind_check(ev_of(h, who), who, "cross derivatives"); }
 }  // namespace
-// u = d/dc (grad_x L) . dc, w = (dg/dc) . dc at (x, lambda), L = f - lambda' g (k_nlp_expr_cross + k_nlp_expr_cross_gather); the inputs of
+// u = d/dc (grad_x L) . dc, w = (dg/dc) . dc at (x, lambda), L = f - lambda' g (nlp_cross_launch on one direction); the inputs of
 // the next LP are not touched (x goes where asm_eval_constraints puts its trial point)
 static void do_data_cross(asm_handle* h, const double* x, const double* lambda, const double* dc, double* u, double* w) {
     cx_check(h, "asm_eval_data_cross");
     EvalState& e = *h->ev;
     if (!x || !u || (h->sk->m > 0 && (!lambda || !w)) || (e.n_dpar > 0 && !dc)) throw std::invalid_argument("asm_eval_data_cross: null pointer");
-    const int64_t n = h->sk->n, m = h->sk->m, nd = e.n_dpar;
+    const int64_t n = h->sk->n, m = h->sk->m, nd = e.n_dpar, R = e.nlp_rows;
     for (int64_t j = 0; j < n; ++j) u[j] = 0.0;
     for (int64_t i = 0; i < m; ++i) w[i] = 0.0;
-    if (nlp_block_derivs(e.nlp_kind)) {      // the column kernels on one column
-        if (nd == 0) return;
-        cx_prepare(h);
-        HIPCHK(hipSetDevice(h->device));
-        const int64_t R = e.nlp_rows;
-        double* st = e.h_cx;
-        std::memcpy(st, x, n * sizeof(double));
-        std::memcpy(st + n, lambda + e.F.n_rows, R * sizeof(double));
-        std::memcpy(st + n + R, dc, nd * sizeof(double));
-        HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(asmb::copy_async(e.d_cx_in, st + n, (R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        cx_launch_block(h, 1);
-        double* back = st + n + R + nd;
-        HIPCHK(asmb::copy_async(back, e.d_cx_out, (n + R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(asmb::sync(h->stream));
-        std::memcpy(u, back, n * sizeof(double));
-        std::memcpy(w + e.F.n_rows, back + n, R * sizeof(double));
-        return;
-    }
-    if (!e.d_cocc) return;      // no CONST node: nothing depends on the data
-    cx_prepare(h);
+    if (!e.data_dep) return;    // nothing depends on the data
     HIPCHK(hipSetDevice(h->device));
-    const ExprTape& X = e.X;
-    double* st = e.h_cx;
+    cx_prepare(e, 1);
+    double *st = e.h_cx, *back = st + n + R + nd;      // [x | lam | dc] up in two copies, [u | w] back
     std::memcpy(st, x, n * sizeof(double));
-    if (X.R > 0) std::memcpy(st + n, lambda + e.F.n_rows, X.R * sizeof(double));
-    std::memcpy(st + n + X.R, dc, nd * sizeof(double));
+    if (R > 0) std::memcpy(st + n, lambda + e.F.n_rows, R * sizeof(double));
+    std::memcpy(st + n + R, dc, nd * sizeof(double));
     HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(asmb::copy_async(e.d_cx_in, st + n, (X.R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), h->stream, X, e.cx_C, e.d_xt, e.d_cx_in + X.R, e.d_cx_in, e.F.objective_scale, e.d_cx_out + n);
-    asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), h->stream, e.cx_C, n, e.d_cx_out);
-    double* back = st + n + X.R + nd;
-    HIPCHK(asmb::copy_async(back, e.d_cx_out, (n + X.R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(asmb::copy_async(e.d_cx_in, st + n, (R + nd) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    nlp_cross_launch(e, h->stream, 1, nullptr, nullptr);
+    HIPCHK(asmb::copy_async(back, e.d_cx_out, (n + R) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
     std::memcpy(u, back, n * sizeof(double));
-    if (X.R > 0) std::memcpy(w + e.F.n_rows, back + n, X.R * sizeof(double));
+    if (R > 0) std::memcpy(w + e.F.n_rows, back + n, R * sizeof(double));
 }
 
 // ---- transposed cross derivatives (include/asm_hip.h, "Transposed cross derivatives")
 namespace {
-// whether anything depends on the block's data: a tape without a CONST node and a block without data give an all-zero answer, no launch
-bool ct_active(const EvalState& e) { return nlp_block_derivs(e.nlp_kind) ? e.n_dpar > 0 : e.d_cocc != nullptr; }
-// the workspace for `cap` columns: 1 for asm_eval_data_cross_t and asm_solution_adjoint, KKM_CW from the first multi call on (the narrower
-// ones stay in the pool).  Kind 3 borrows the node arrays of the cross sweep (cx_prepare: blocking copies, not inside a batch fiber)
-void ct_prepare(asm_handle* h, int64_t cap) {
-    EvalState& e = *h->ev;
-    if (e.ct_cap >= cap) return;
-    const bool block = nlp_block_derivs(e.nlp_kind);
-    if (!block) cx_prepare(h);
-    HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->sk->n, R = block ? e.nlp_rows : e.X.R, nd = e.n_dpar;
-    BufPool& M = e.mem;
-    M.zeroed(e.d_ct_in, R + cap * (n + R)); M.zeroed(e.d_ct_out, cap * nd);
-    M.alloc(e.h_ct, n + R + cap * (n + R + nd), BufPool::PINNED);
-    e.ct_cap = cap;
-}
 // OUT [ncol x n_dpar]: row c = the transposed cross derivative at (x, lambda) for the weights (sx * VX[c], VL[c]) (VX ncol x n, VL ncol x m;
 // sx = -1 turns an adjoint state's ax into the weight -ax, exactly), in chunks of `cap` columns.  x and the block's multipliers go up once;
-// a chunk is one upload, its launches and one read-back: kinds 4 and 5 one launch for all its columns (grid.y = column), kind 3 one
-// launch pair per column, no synchronisation between columns.  A column's answer depends on its own weights only.
+// a chunk is one upload, its launches (nlp_cross_t_launch, no synchronisation between columns) and one read-back.  A column's answer
+// depends on its own weights only.
 void ct_columns(asm_handle* h, const double* x, const double* lambda, int64_t ncol, const double* VX, double sx, const double* VL, double* OUT, int64_t cap) {
     EvalState& e = *h->ev;
     const int64_t n = h->sk->n, m = h->sk->m, nd = e.n_dpar;
-    if (!ct_active(e)) {
+    if (!e.data_dep) {          // nothing depends on the data
         for (int64_t q = 0; q < ncol * nd; ++q) OUT[q] = 0.0;
         return;
     }
-    ct_prepare(h, cap);
     HIPCHK(hipSetDevice(h->device));
+    ct_prepare(e, cap);
     const hipStream_t s = h->stream;
-    const bool block = nlp_block_derivs(e.nlp_kind);
-    const int64_t R = block ? e.nlp_rows : e.X.R, r0 = e.F.n_rows, ldv = n + R;
+    const int64_t R = e.nlp_rows, r0 = e.F.n_rows, ldv = n + R;
     double *st = e.h_ct, *s_in = st + n, *back = s_in + R + cap * ldv;
     std::memcpy(st, x, n * sizeof(double));
     if (R > 0) std::memcpy(s_in, lambda + r0, R * sizeof(double));
     HIPCHK(asmb::copy_async(e.d_xt, st, n * sizeof(double), hipMemcpyHostToDevice, s));
     if (R > 0) HIPCHK(asmb::copy_async(e.d_ct_in, s_in, R * sizeof(double), hipMemcpyHostToDevice, s));
-    const double* lam = e.d_ct_in;
     double* dv = e.d_ct_in + R;
     for (int64_t c0 = 0; c0 < ncol; c0 += cap) {
         const int cols = (int)std::min<int64_t>(cap, ncol - c0);
@@ -4981,18 +5016,7 @@ void ct_columns(asm_handle* h, const double* x, const double* lambda, int64_t nc
             if (R > 0) std::memcpy(sv + n, VL + (c0 + c) * m + r0, R * sizeof(double));
         }
         HIPCHK(asmb::copy_async(dv, s_in + R, (int64_t)cols * ldv * sizeof(double), hipMemcpyHostToDevice, s));
-        if (nlp_is_ohm(e.nlp_kind)) {
-            asmb::launch(k_nlp_ohm_cross_t, dim3(asmb::blocks(R / 4).x, (unsigned)cols), dim3(256), s, e.d_ipar, e.d_xt, lam, (const double*)dv, ldv, n, e.d_ct_out, nd);
-        } else if (block) {
-            asmb::launch(k_nlp_dense_cross_t, dim3(asmb::blocks(R * n).x, (unsigned)cols), dim3(256), s, R, n, e.d_xt, lam, (const double*)dv, ldv, e.d_ct_out, nd);
-        } else {
-            const ExprTape& X = e.X;
-            for (int c = 0; c < cols; ++c) {
-                const double* v = dv + (int64_t)c * ldv;
-                asmb::launch(k_nlp_expr_cross_t, asmb::blocks(X.R + X.T), dim3(256), s, X, e.cx_C, e.d_xt, v, lam, v + n, e.F.objective_scale, e.d_cocc);
-                asmb::launch(k_nlp_expr_data_gather, asmb::blocks(nd), dim3(256), s, e.d_cptr, e.d_cocc, nd, e.d_ct_out + (int64_t)c * nd);
-            }
-        }
+        nlp_cross_t_launch(e, s, cols);
         HIPCHK(asmb::copy_async(back, e.d_ct_out, (int64_t)cols * nd * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(asmb::sync(s));
         std::memcpy(OUT + c0 * nd, back, (int64_t)cols * nd * sizeof(double));
@@ -5451,18 +5475,9 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
     // 2. the Jacobian at x: values into a buffer of the solve's own, assembled into its own dense J (the LP's dE and J stay) or, sparse
     // form, summed into the CSR list of the pattern: its first nu entries are the unique entries in k_assemble's order
     {
-        const FnStore& F = h->ev->F;
-        if (F.n_rows > 0) asmb::launch(k_fn_rows, asmb::blocks(F.n_rows), dim3(256), s, F, h->ev->d_xt, h->ev->d_Et, K.dE, 1, (int64_t)0, (int64_t)0);
-        const ExprTape& X = h->ev->X;
-        if (h->ev->nlp_kind == ASM_NLP_EXPR && X.R > 0)
-            asmb::launch(k_nlp_expr_rows, asmb::blocks(X.R), dim3(256), s, X, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
-        // (kinds 1 and 2 come here with the limited-memory operator only, 4 and 5 with either: their own kernels as ev_launch calls them, one point)
-        if (nlp_is_ohm(h->ev->nlp_kind))
-            asmb::launch(k_nlp_acopf_ohm, asmb::blocks(h->ev->nlp_rows / 4), dim3(256), s, h->ev->d_ipar, h->ev->d_dpar, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows, h->ev->fn_nnz, 1,
-                         (int64_t)0, (int64_t)0);
-        else if (nlp_is_dense(h->ev->nlp_kind))
-            asmb::launch(k_nlp_dense_quadratic, asmb::blocks(h->ev->nlp_rows, 4), dim3(256), s, h->ev->d_dpar, h->ev->nlp_rows, n, h->ev->d_xt, h->ev->d_Et, K.dE, F.n_rows,
-                         h->ev->fn_nnz, 1, (int64_t)0, (int64_t)0);
+        // (the kernel families without second derivatives come here with the limited-memory operator only)
+        fn_rows_launch(*h->ev, s, h->ev->d_xt, h->ev->d_Et, K.dE, 1);
+        nlp_rows_launch(*h->ev, s, h->ev->d_xt, h->ev->d_Et, K.dE, 1);
         if (f.sparse) {
             const unsigned g = (unsigned)std::min<int64_t>((h->sk->nu + 255) / 256, 4096);
             asmb::launch(k_kkts_vals, dim3(g), dim3(256), s, (const double*)K.dE, (const int64_t*)h->sk->d_perm, (const int64_t*)h->sk->d_ustart, h->sk->nu, K.sp_vals);
@@ -5765,44 +5780,25 @@ void kkt_stage_rhs(asm_handle* h, const KktFace& f, KktWork& w, const KktRhs& rh
     case KktRhs::DATA:
         break;
     }
-    const int64_t nd = h->ev->n_dpar;
-    double* hd = st + cap * (ldn + ldT);
-    if (nlp_block_derivs(h->ev->nlp_kind) && nd > 0) {
-        // kinds 4 and 5: the column kernels make a chunk's right-hand sides at once, from the block's multipliers uploaded once
-        const int64_t R = h->ev->nlp_rows;
-        if (c0 == 0) {
-            cx_prepare(h, KKM_CW);
-            std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, R * sizeof(double));
-            HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, R * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-        // the chunk's directions in the staging rows, one upload, then one launch set for all its columns
-        std::memcpy(hd, rhs.DC + c0 * nd, (int64_t)cols * nd * sizeof(double));
-        HIPCHK(asmb::copy_async(h->ev->d_cx_in + R, hd, (int64_t)cols * nd * sizeof(double), hipMemcpyHostToDevice, s));
-        cx_launch_block(h, cols);
-        asmb::launch(k_kktm_cross_rhs_cols, dim3(asmb::blocks(std::max(n, nW)).x, (unsigned)cols), dim3(256), s, (const double*)h->ev->d_cx_out, n + R, n,
-                     (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru, ldn, rww, ldT);
-    } else if (h->ev->d_cocc != nullptr) {
-        const ExprTape& X = h->ev->X;
-        if (c0 == 0) {      // the multipliers of the expression rows, once
-            cx_prepare(h);
-            if (X.R > 0) {
-                std::memcpy(h->ev->h_cx, lambda + h->ev->F.n_rows, X.R * sizeof(double));
-                HIPCHK(asmb::copy_async(h->ev->d_cx_in, h->ev->h_cx, X.R * sizeof(double), hipMemcpyHostToDevice, s));
-            }
-        }
-        // one sweep per direction, no synchronisation between them: every direction has its own staging row
-        for (int c = 0; c < cols; ++c) {
-            std::memcpy(hd + (int64_t)c * nd, rhs.DC + (c0 + c) * nd, nd * sizeof(double));
-            HIPCHK(asmb::copy_async(h->ev->d_cx_in + X.R, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
-            asmb::launch(k_nlp_expr_cross, asmb::blocks(X.R + X.T), dim3(256), s, X, h->ev->cx_C, h->ev->d_xt, h->ev->d_cx_in + X.R, h->ev->d_cx_in, h->ev->F.objective_scale, h->ev->d_cx_out + n);
-            asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, h->ev->cx_C, n, h->ev->d_cx_out);
-            asmb::launch(k_kktm_cross_rhs, asmb::blocks(std::max(n, nW)), dim3(256), s, h->ev->d_cx_out, n, (int64_t)h->ev->F.n_rows, f.wrow, nW, b_ru + (int64_t)c * ldn,
-                         rww + (int64_t)c * ldT);
-        }
-    } else {      // no CONST node: nothing depends on the data, u = w = 0
+    EvalState& e = *h->ev;
+    if (!e.data_dep) {      // nothing depends on the data, u = w = 0
         HIPCHK(asmb::fill_async(b_ru, 0, cap * ldn * sizeof(double), s));
         HIPCHK(asmb::fill_async(rww, 0, cap * ldT * sizeof(double), s));
+        return;
     }
+    const int64_t nd = e.n_dpar, R = e.nlp_rows;
+    if (c0 == 0) {          // the multipliers of the block's rows, once
+        cx_prepare(e, KKM_CW);
+        if (R > 0) {
+            std::memcpy(e.h_cx, lambda + e.F.n_rows, R * sizeof(double));
+            HIPCHK(asmb::copy_async(e.d_cx_in, e.h_cx, R * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+    }
+    // the chunk's directions in the staging rows - every direction has its own - and their cross derivatives into the chunk's right-hand sides
+    double* hd = st + cap * (ldn + ldT);
+    std::memcpy(hd, rhs.DC + c0 * nd, (int64_t)cols * nd * sizeof(double));
+    const CxRhs to{f.wrow, nW, b_ru, ldn, rww, ldT};
+    nlp_cross_launch(e, s, cols, hd, &to);
 }
 // Steps 3 to 6 for the nrhs columns that `rhs` describes, in chunks of the work area's capacity (lambda: the multipliers of the point, read
 // by the cross-derivative sweeps).  The element-wise and reduction kernels are the k_kktm_* family whatever the capacity; every product
@@ -6007,7 +6003,7 @@ namespace {
 // the kinds the adjoint entries serve: those of asm_solution_sensitivity, and the function store alone (kind 0) - no data, an empty out,
 // but the bound gradient and the adjoint state need no data derivative.  Kinds 1 and 2 end in the solve's hs_check.
 void adjoint_check(const asm_handle* h, const char* who) {
-    if (ev_of(h, who).nlp_kind != 0) cx_check(h, who);
+    if (ev_of(h, who).family != NlpFamily::NONE) cx_check(h, who);
 }
 // the refusals of the adjoint entries, per handle and for a batch: those of the solve with the gradients as its columns, and OUT
 void adjoint_check_args(const std::string& who, int64_t m, int64_t nd, int32_t nrhs, const KktPoint& p, const double* GX, const double* GL, const double* OUT,
@@ -8330,9 +8326,11 @@ void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_
             else kk_dense(h);
             (void)kk_work(h, cap, sparse);
             if (cap == 1) eq_prepare(h);
-            const EvalState& e = *h->ev;
-            if (cross && (nlp_block_derivs(e.nlp_kind) ? e.n_dpar > 0 : e.d_cocc != nullptr)) cx_prepare(h, KKM_CW);
-            if (cross_t && ct_active(e)) ct_prepare(h, KKM_CW);
+            EvalState& e = *h->ev;
+            if (!e.data_dep) return;       // (what kkt_stage_rhs and ct_columns ask before they read either workspace)
+            HIPCHK(hipSetDevice(h->device));
+            if (cross) cx_prepare(e, KKM_CW);
+            if (cross_t) ct_prepare(e, KKM_CW);
         });
 }
 // The three multi entries on n_scen scenarios, the slots taking them in index order (for_each_scenario): per scenario do_kkt_solve_multi
