@@ -67,6 +67,12 @@ class NssStage(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flag", C.c_int32), ("thr", C.c_double)]
 
 
+class KktStage(C.Structure):
+    """asm_kkt_stage: one stage of asm_test_kkt_stages (include/asm_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("flag", C.c_int32 * 3), ("pub", C.c_uint32), ("pad_", C.c_int32), ("s", C.c_double * 2), ("len", C.c_int64 * 3),
+                ("x", C.c_int64 * 7), ("ix", C.c_int64 * 7), ("lx", C.c_int64 * 3)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("ops", C.c_int64), ("launches", C.c_int64), ("releases", C.c_int64), ("blob_bytes", C.c_int64),
                 ("emit_ms", C.c_double), ("wait_ms", C.c_double), ("host_ms", C.c_double), ("wall_ms", C.c_double),
@@ -254,6 +260,9 @@ PROTOTYPES = {
                                       _D, C.POINTER(C.c_uint32), C.POINTER(IpmStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_as_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I64, _D, C.c_int64, _I32, C.c_int64, _D, C.c_int64,
                                      C.POINTER(AsStage), C.c_int64, C.POINTER(C.c_uint32)]),
+    "asm_test_kkt_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _I64, _D, C.c_int64, _I32, C.c_int64, _I64, C.c_int64,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _D, C.POINTER(C.c_uint32), C.POINTER(KktStage), C.c_int64,
+                                      C.POINTER(C.c_uint32)]),
     "asm_test_ns_stages": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _I32, _I32, _I32, _D, _D, _D, _I64, _I32, _D, C.c_int64, _D,
                                      C.POINTER(C.c_uint32), C.POINTER(NsStage), C.c_int64, C.POINTER(C.c_uint32)]),
     "asm_test_ns_setup_stages": (C.c_int, [_P, _D, _D, C.c_int64, C.c_int64, _I32, _I64, _I32, _D, _D, _D, _D, _D, _D, _D, _D, _D, C.c_int32, _I32, C.c_int64,

@@ -733,6 +733,133 @@ void ct_prepare(EvalState& e, int64_t cap) {
     M.alloc(e.h_ct, n + R + cap * (n + R + nd), BufPool::PINNED);
     e.ct_cap = cap;
 }
+// ---- The launch sites of the KKT column family and of the SLP-EQP trial step (asm_kkt_kernels.hip.h, asm_eqp_kernels.hip.h): one function per
+// launch of a kernel of the two headers.  Each computes its grid from the sizes it is given and the pitches held here, launches, and returns
+// the workgroups (x times y) it asked for.  The drivers (KktFace, the KktOps back ends, kkt_stage_rhs, kkt_columns, nlp_cross_launch,
+// asm_eqp_trial) and the test hook asm_test_kkt_stages go through these; nothing else launches a kernel of the two headers.
+struct KktSites {
+    hipStream_t s;
+    int64_t ldn, ldT;      // pitch of the blocks over the variables / over the working rows
+    unsigned gred;         // workgroups per column of the reductions over the variables: min(ceil(ldn / 256), KK_MAXWG)
+    static constexpr int LA = 4, LAT = 8;      // lanes per working row / per variable of the sparse products ("KKT solve: the sparse form")
+    KktSites(hipStream_t st, int64_t ldn_, int64_t ldT_) : s(st), ldn(ldn_), ldT(ldT_), gred((unsigned)std::min<int64_t>(asmb::blocks(ldn_).x, KK_MAXWG)) {}
+    static unsigned wg(const dim3& g) { return g.x * g.y; }
+    dim3 over_vars(int cols) const { return dim3(asmb::blocks(ldn).x, (unsigned)cols); }
+    static dim3 over_rows(int64_t nWg, int cols) { return dim3(asmb::blocks(nWg).x, (unsigned)cols); }
+    unsigned gather(const double* J, const int* wrow, const double* mask, int64_t nW, int64_t nWg, double* Aw) const {
+        const dim3 g(asmb::blocks(ldn).x, (unsigned)nWg);
+        asmb::launch(k_kkt_gather, g, dim3(256), s, J, ldn, wrow, mask, nW, Aw);
+        return wg(g);
+    }
+    unsigned gather_t(const double* J, const int* wrow, const double* mask, int64_t nW, int64_t nWp, double* AT) const {
+        const dim3 g((unsigned)((ldn + 63) / 64), (unsigned)((nWp + 63) / 64));
+        asmb::launch(k_kktm_gather_t, g, dim3(256), s, J, ldn, wrow, mask, nW, nWp, AT, ldT);
+        return wg(g);
+    }
+    // cols <= KKM_CW columns of pitch ldn: the template by the number of columns
+    unsigned hess_product(const int64_t* pptr, const int64_t* pent, const int64_t* poth, const double* values, const double* v, int64_t n, int cols, double* out) const {
+        const dim3 g = asmb::blocks(n);
+        if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, pptr, pent, poth, values, v, ldn, n, cols, out);
+        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, pptr, pent, poth, values, v, ldn, n, cols, out);
+        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, pptr, pent, poth, values, v, ldn, n, cols, out);
+        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, pptr, pent, poth, values, v, ldn, n, cols, out);
+        return wg(g);
+    }
+    unsigned axpby(double sa, const double* a, double sb, const double* b, const double* mask, const double* scal, double* out, int cols) const {
+        const dim3 g = over_vars(cols);
+        asmb::launch(k_kktm_axpby, g, dim3(256), s, sa, a, sb, b, mask, ldn, ldn, scal, out);
+        return wg(g);
+    }
+    unsigned axpby_rows(double sa, const double* a, double sb, const double* b, int64_t nW, int64_t nWg, double* out, int cols) const {
+        const dim3 g = over_rows(nWg, cols);
+        asmb::launch(k_kktm_axpby, g, dim3(256), s, sa, a, sb, b, (const double*)nullptr, nW, ldT, (const double*)nullptr, out);
+        return wg(g);
+    }
+    unsigned scatter(const double* y, const int* wrow, int64_t nW, int64_t nWg, double* out, int64_t ldo, int cols) const {
+        const dim3 g = over_rows(nWg, cols);
+        asmb::launch(k_kktm_scatter, g, dim3(256), s, y, ldT, wrow, nW, out, ldo);
+        return wg(g);
+    }
+    unsigned cross_rhs(const double* cx, int64_t n, int64_t n_fn, const int* wrow, int64_t nW, double* ru, double* rww) const {
+        const dim3 g = asmb::blocks(std::max(n, nW));
+        asmb::launch(k_kktm_cross_rhs, g, dim3(256), s, cx, n, n_fn, wrow, nW, ru, rww);
+        return wg(g);
+    }
+    unsigned cross_rhs_cols(const double* cx, int64_t ldc, int64_t n, int64_t n_fn, const int* wrow, int64_t nW, double* ru, double* rww, int cols) const {
+        const dim3 g(asmb::blocks(std::max(n, nW)).x, (unsigned)cols);
+        asmb::launch(k_kktm_cross_rhs_cols, g, dim3(256), s, cx, ldc, n, n_fn, wrow, nW, ru, ldn, rww, ldT);
+        return wg(g);
+    }
+    unsigned bound_rhs(const int* rows, const double* delta, const int* wrow, int64_t nW, double* ru, double* rww, int cols) const {
+        const dim3 g(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols);
+        asmb::launch(k_kktm_bound_rhs, g, dim3(256), s, rows, delta, wrow, nW, ru, ldn, rww, ldT);
+        return wg(g);
+    }
+    unsigned cg_p(const double* scal, const double* g_, double* p, int cols) const {
+        const dim3 g = over_vars(cols);
+        asmb::launch(k_kktm_cg_p, g, dim3(256), s, scal, g_, p, ldn, ldn);
+        return wg(g);
+    }
+    unsigned normal(double* scal, const double* radius, double share, double* dx0, int cols) const {
+        const dim3 g((unsigned)cols);
+        asmb::launch(k_kktm_normal, g, dim3(1024), s, scal, radius, share, dx0, ldn, ldn);
+        return wg(g);
+    }
+    unsigned cg_curv(bool trust, const KktMulti& R, const double* p, const double* hp_raw, const double* mask, const double* d, double* hp, int cols) const {
+        const dim3 g(gred, (unsigned)cols);
+        if (trust) asmb::launch(k_kktm_cg_curv<true>, g, dim3(256), s, R, p, hp_raw, mask, d, hp, ldn, ldn);
+        else asmb::launch(k_kktm_cg_curv<false>, g, dim3(256), s, R, p, hp_raw, mask, d, hp, ldn, ldn);
+        return wg(g);
+    }
+    unsigned cg_step(const double* scal, const double* p, const double* hp, double* d, double* r, int cols) const {
+        const dim3 g = over_vars(cols);
+        asmb::launch(k_kktm_cg_step, g, dim3(256), s, scal, p, hp, d, r, ldn, ldn);
+        return wg(g);
+    }
+    unsigned cg_dir(const KktMulti& R, const double* r, int init, double rtol, unsigned pub, int trust, int cols) const {
+        const dim3 g(gred, (unsigned)cols);
+        asmb::launch(k_kktm_cg_dir, g, dim3(256), s, R, r, ldn, ldn, init, rtol, pub, trust);
+        return wg(g);
+    }
+    unsigned finish(double* scal, const double* hdx, const double* ru, const double* jtl, const double* mask, int64_t n, const double* adx, const double* rww, int64_t nW,
+                    double* dz, const double* dx, int cols) const {
+        const dim3 g((unsigned)cols);
+        asmb::launch(k_kktm_finish, g, dim3(1024), s, scal, hdx, ru, jtl, mask, n, ldn, adx, rww, nW, ldT, dz, dx);
+        return wg(g);
+    }
+    unsigned kkts_vals(const double* dE, const int64_t* perm, const int64_t* ustart, int64_t nu, double* vals) const {
+        const dim3 g((unsigned)std::min<int64_t>((nu + 255) / 256, 4096));
+        asmb::launch(k_kkts_vals, g, dim3(256), s, dE, perm, ustart, nu, vals);
+        return wg(g);
+    }
+    unsigned kkts_wpos(const int* wrow, int64_t nW, int64_t M, int* wpos) const {
+        const dim3 g(1);
+        asmb::launch(k_kkts_wpos, g, dim3(1024), s, wrow, nW, std::max<int64_t>(M, 1), wpos);
+        return wg(g);
+    }
+    unsigned kkts_mul_a(const int* ptr, const int* col, const double* val, const int* wrow, const double* mask, const double* v, int64_t nW, int64_t nWg, double* t, int cols) const {
+        const dim3 g(asmb::blocks(nWg * LA).x, (unsigned)cols);
+        asmb::launch(k_kkts_mul_a<LA>, g, dim3(256), s, ptr, col, val, wrow, mask, v, ldn, nW, t, ldT);
+        return wg(g);
+    }
+    unsigned kkts_mul_at(const int* cptr, const int* row, const int* pos, const double* val, const int* wpos, const double* mask, const double* y, int64_t n, double* v,
+                         int cols) const {
+        const dim3 g(asmb::blocks(ldn * LAT).x, (unsigned)cols);
+        asmb::launch(k_kkts_mul_at<LAT>, g, dim3(256), s, cptr, row, pos, val, wpos, mask, y, ldT, n, ldn, v, ldn);
+        return wg(g);
+    }
+    // (the two kernels of the trial step use neither pitch)
+    unsigned eqp_face(const EqpFace& P, const KktRed& R, int* rows, int* bnd, int* side, double* rw, int* counts) const {
+        const dim3 g((unsigned)std::min<int64_t>(asmb::blocks(std::max(P.n, P.m)).x, KK_MAXWG));
+        asmb::launch(k_eqp_face, g, dim3(256), s, P, R, rows, bnd, side, rw, counts);
+        return wg(g);
+    }
+    unsigned eqp_trial(const double* dx, const double* x, const double* x_L, const double* x_U, int64_t n, const KktRed& R, double* d, double* out) const {
+        const dim3 g((unsigned)std::min<int64_t>(asmb::blocks(n).x, KK_MAXWG));
+        asmb::launch(k_eqp_trial, g, dim3(256), s, dx, x, x_L, x_U, n, R, d, out);
+        return wg(g);
+    }
+};
 // where kkt_stage_rhs wants the cross derivatives of a chunk: column c as the right-hand sides b_ru + c ldn and, on the working rows, rww + c ldT
 struct CxRhs { const int* wrow; int64_t nW; double* b_ru; int64_t ldn; double* rww; int64_t ldT; };
 // Cross derivatives (u, w) of `cols` <= cx_cap directions at d_xt, with the block's multipliers in d_cx_in: u = d/dc (grad_x L) . dc,
@@ -746,13 +873,12 @@ void nlp_cross_launch(const EvalState& e, hipStream_t s, int cols, const double*
     const double* lam = e.d_cx_in;
     double* dc = e.d_cx_in + R;
     const unsigned nc = (unsigned)cols;
-    const dim3 gto = asmb::blocks(to ? std::max(n, to->nW) : 0);
     if (e.family == NlpFamily::EXPR) {
         for (int c = 0; c < cols; ++c) {
             if (hd) HIPCHK(asmb::copy_async(dc, hd + (int64_t)c * nd, nd * sizeof(double), hipMemcpyHostToDevice, s));
             asmb::launch(k_nlp_expr_cross, asmb::blocks(R + e.X.T), dim3(256), s, e.X, e.cx_C, e.d_xt, dc, lam, e.F.objective_scale, e.d_cx_out + n);
             asmb::launch(k_nlp_expr_cross_gather, asmb::blocks(n), dim3(256), s, e.cx_C, n, e.d_cx_out);
-            if (to) asmb::launch(k_kktm_cross_rhs, gto, dim3(256), s, e.d_cx_out, n, r0, to->wrow, to->nW, to->b_ru + (int64_t)c * to->ldn, to->rww + (int64_t)c * to->ldT);
+            if (to) KktSites(s, to->ldn, to->ldT).cross_rhs(e.d_cx_out, n, r0, to->wrow, to->nW, to->b_ru + (int64_t)c * to->ldn, to->rww + (int64_t)c * to->ldT);
         }
         return;
     }
@@ -764,7 +890,7 @@ void nlp_cross_launch(const EvalState& e, hipStream_t s, int cols, const double*
         asmb::launch(k_nlp_dense_cross_w, dim3(asmb::blocks(R, 4).x, nc), dim3(256), s, dc, nd, R, n, e.d_xt, e.d_cx_out, ldo);
         asmb::launch(k_nlp_dense_cross_u, dim3(asmb::blocks(n).x, nc), dim3(256), s, dc, nd, R, n, e.d_xt, lam, e.d_cx_out, ldo);
     }
-    if (to) asmb::launch(k_kktm_cross_rhs_cols, dim3(gto.x, nc), dim3(256), s, e.d_cx_out, ldo, n, r0, to->wrow, to->nW, to->b_ru, to->ldn, to->rww, to->ldT);
+    if (to) KktSites(s, to->ldn, to->ldT).cross_rhs_cols(e.d_cx_out, ldo, n, r0, to->wrow, to->nW, to->b_ru, to->rww, cols);
 }
 // Transposed cross derivatives of `cols` <= ct_cap weight columns [vx (n) | vl (R)] at d_ct_in + R, at d_xt and with the block's
 // multipliers in d_ct_in: column c of d_ct_out (pitch n_dpar).  The kernels take the columns at once (grid.y = column), the tape one
@@ -5479,8 +5605,7 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         fn_rows_launch(*h->ev, s, h->ev->d_xt, h->ev->d_Et, K.dE, 1);
         nlp_rows_launch(*h->ev, s, h->ev->d_xt, h->ev->d_Et, K.dE, 1);
         if (f.sparse) {
-            const unsigned g = (unsigned)std::min<int64_t>((h->sk->nu + 255) / 256, 4096);
-            asmb::launch(k_kkts_vals, dim3(g), dim3(256), s, (const double*)K.dE, (const int64_t*)h->sk->d_perm, (const int64_t*)h->sk->d_ustart, h->sk->nu, K.sp_vals);
+            KktSites(s, ldn, K.ldT).kkts_vals(K.dE, h->sk->d_perm, h->sk->d_ustart, h->sk->nu, K.sp_vals);
         } else if (h->sk->dense_fast) {
             const unsigned g = (unsigned)std::min<int64_t>((h->sk->m * h->sk->n + 255) / 256, 4096);
             asmb::launch(k_assemble_dense, dim3(g), dim3(256), s, K.dE, K.J, h->sk->m, h->sk->n, ldn);
@@ -5504,7 +5629,7 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         f.mask = K.sets;
         f.wrow = reinterpret_cast<const int*>(K.sets + ldn);
         if (!made) {      // static order, a new working set: the place of every LP row in it, from the list just uploaded
-            asmb::launch(k_kkts_wpos, dim3(1), dim3(1024), s, f.wrow, f.nW, std::max<int64_t>(h->sk->M, 1), K.wpos);
+            KktSites(s, ldn, K.ldT).kkts_wpos(f.wrow, f.nW, h->sk->M, K.wpos);
             K.c_valid = true;
         }
     }
@@ -5540,11 +5665,11 @@ KktFace::KktFace(asm_handle* h, Dev& dev, const std::string& me, const double* x
         h->stats.nfact = nfact;
         asmb::launch(k_ns_count_big, dim3(1), dim3(1024), s, K.fac.S, K.fac.ld, (int)nW, NS_BIG, K.dropped);
     } else if (nW > 0) {
-        const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
+        const KktSites at(s, ldn, K.ldT);
         K.fac.band = 0;
         K.fac_full_rows = std::max(K.fac_full_rows, std::min<int64_t>(round_up(nW, 64), K.fac.ld));
-        asmb::launch(k_kkt_gather, dim3(asmb::blocks(ldn).x, (unsigned)f.nWg), dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, K.Aw);
-        asmb::launch(k_kktm_gather_t, gt, dim3(256), s, K.J, ldn, f.wrow, f.mask, nW, f.nWp, K.AwT, K.ldT);
+        at.gather(K.J, f.wrow, f.mask, nW, f.nWg, K.Aw);
+        at.gather_t(K.J, f.wrow, f.mask, nW, f.nWp, K.AwT);
         dev.launch_syrk(s, Dev::pick_tile(nW), K.Aw, ldn, nullptr, 0, (int)nW, (int)ldn, nullptr, nullptr, K.fac.S, K.fac.ld, 0, 0);
         dev.diag_prepare(K.fac, (int)nW, 1, 0.0, 0.0);
         const int nfact = h->stats.nfact;
@@ -5564,9 +5689,11 @@ struct KktOps {
     KktWork& w;
     const hipStream_t s;
     const int64_t n, ldn, ldT;
+    const KktSites site;             // the launch sites of the family's own kernels
     double* const spare;             // a block over the working rows of the back end's own
     KktOps(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww)
-        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->sk->n), ldn(hh->sk->ldn), ldT(hh->ev->kk.ldT), spare(ww.row + 2 * ww.cap * hh->ev->kk.ldT) {}
+        : h(hh), dev(d), f(ff), w(ww), s(hh->stream), n(hh->sk->n), ldn(hh->sk->ldn), ldT(hh->ev->kk.ldT), site(hh->stream, hh->sk->ldn, hh->ev->kk.ldT),
+          spare(ww.row + 2 * ww.cap * hh->ev->kk.ldT) {}
     virtual ~KktOps() = default;
     virtual void hess(const double* v, double* out, int cols) = 0;                  // OUT = H V from the values of step 1, or B V
     // what every back end's hess is: the limited-memory product where the face has it, else the exact kernels on the values of step 1 -
@@ -5574,12 +5701,8 @@ struct KktOps {
     void hess_product(const double* v, double* out, int cols, bool one) {
         if (f.lm) { lm_product(h, v, ldn, cols, out, ldn); return; }
         const HsShared& L = *h->ev->hs_sh;
-        const dim3 g = asmb::blocks(n);
-        if (one) asmb::launch(k_hess_product, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
-        else if (cols <= 8) asmb::launch(k_kktm_hess_product<8>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 16) asmb::launch(k_kktm_hess_product<16>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else if (cols <= 32) asmb::launch(k_kktm_hess_product<32>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
-        else asmb::launch(k_kktm_hess_product<64>, g, dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, ldn, n, cols, out);
+        if (one) asmb::launch(k_hess_product, asmb::blocks(n), dim3(256), s, L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, out);
+        else site.hess_product(L.pptr, L.pent, L.poth, h->ev->d_hs_vals, v, n, cols, out);
     }
     virtual void mul_A(const double* v, double* t, int cols) = 0;                   // T = V A'
     virtual void mul_AT(const double* y, double* v, int cols) = 0;                  // V = Y A
@@ -5617,8 +5740,7 @@ struct KktBlock final : KktOps {
         const KktBufs& K = h->ev->kk;
         const int64_t nW = f.nW;
         if (nW > 0) {
-            const dim3 gt((unsigned)((ldn + 63) / 64), (unsigned)((f.nWp + 63) / 64));
-            asmb::launch(k_kktm_gather_t, gt, dim3(256), s, K.J, ldn, f.wrow, (const double*)nullptr, nW, f.nWp, w.AfT, ldT);
+            site.gather_t(K.J, f.wrow, nullptr, nW, f.nWp, w.AfT);
             // (the rows of Lt up to |W| rounded up to 32 are cleared first: the k-padding beside the nW x nW square the transposition writes)
             HIPCHK(asmb::fill_async(w.Lt, 0, f.nWp * K.fac.ld * sizeof(double), s));
             asmb::launch(k_transpose_dense, dim3((unsigned)((nW + 63) / 64), (unsigned)((nW + 63) / 64)), dim3(256), s, K.fac.S, K.fac.ld, nW, nW, w.Lt, K.fac.ld, nW);
@@ -5642,7 +5764,6 @@ struct KktBlock final : KktOps {
 // without the mask.  The Hessian products and the substitutions are those of the dense back end of the same capacity, on the banded factor:
 // chol_solve_dev for one column, trsm_rows with a transposed copy of the band for a block.
 struct KktSparse final : KktOps {
-    static constexpr int LA = 4, LAT = 8;      // lanes per working row / per variable ("KKT solve: the sparse form")
     KktSparse(asm_handle* hh, Dev& d, const KktFace& ff, KktWork& ww) : KktOps(hh, d, ff, ww) {
         if (w.cap == 1) return;
         const KktBufs& K = h->ev->kk;
@@ -5658,13 +5779,11 @@ struct KktSparse final : KktOps {
     void hess(const double* v, double* out, int cols) override { hess_product(v, out, cols, w.cap == 1); }
     void mul_A(const double* v, double* t, int cols) override {
         const Skeleton& S = *h->sk;
-        asmb::launch(k_kkts_mul_a<LA>, dim3(asmb::blocks(f.nWg * LA).x, (unsigned)cols), dim3(256), s, (const int*)S.d_sp_ptr, (const int*)S.d_sp_col, (const double*)h->ev->kk.sp_vals,
-                     f.wrow, f.mask, v, ldn, f.nW, t, ldT);
+        site.kkts_mul_a(S.d_sp_ptr, S.d_sp_col, h->ev->kk.sp_vals, f.wrow, f.mask, v, f.nW, f.nWg, t, cols);
     }
     void at(const double* y, const double* mask, double* v, int cols) {
         const Skeleton& S = *h->sk;
-        asmb::launch(k_kkts_mul_at<LAT>, dim3(asmb::blocks(ldn * LAT).x, (unsigned)cols), dim3(256), s, (const int*)S.d_sc_ptr, (const int*)S.d_sc_row, (const int*)S.d_sc_pos,
-                     (const double*)h->ev->kk.sp_vals, (const int*)h->ev->kk.wpos, mask, y, ldT, n, ldn, v, ldn);
+        site.kkts_mul_at(S.d_sc_ptr, S.d_sc_row, S.d_sc_pos, h->ev->kk.sp_vals, h->ev->kk.wpos, mask, y, n, v, cols);
     }
     void mul_AT(const double* y, double* v, int cols) override { at(y, f.mask, v, cols); }
     double* solve_S(const double* b, double* t, int cols) override {
@@ -5756,8 +5875,7 @@ void kkt_stage_rhs(asm_handle* h, const KktFace& f, KktWork& w, const KktRhs& rh
         if (rhs.delta) std::memcpy(st, rhs.delta + c0, cols * sizeof(double));
         for (int c = 0; c < cols; ++c) hr[c] = rhs.rows[c0 + c];
         HIPCHK(asmb::copy_async(w.bnd, st, cols * (sizeof(double) + sizeof(int)), hipMemcpyHostToDevice, s));
-        asmb::launch(k_kktm_bound_rhs, dim3(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols), dim3(256), s, (const int*)dr, rhs.delta ? (const double*)w.bnd : (const double*)nullptr,
-                     f.wrow, nW, b_ru, ldn, rww, ldT);
+        KktSites(s, ldn, ldT).bound_rhs(dr, rhs.delta ? (const double*)w.bnd : (const double*)nullptr, f.wrow, nW, b_ru, rww, cols);
         return;
     }
     case KktRhs::GIVEN: {
@@ -5819,21 +5937,19 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
     double* const dlf = w.dlf;
     double* const scal = K.scal;
     const KktMulti R{K.part, K.cnt, scal, K.act, h->sk->d_hscal, h->sk->d_hseq};
-    const dim3 gl = asmb::blocks(ldn);
-    const unsigned gred = (unsigned)std::min<int64_t>(gl.x, KK_MAXWG);
+    const KktSites& at = ops.site;
     const bool run_cg = f.nF > nW, trust = tr.on;
     int dropped = 0;
     cnt = {};
     for (int64_t c0 = 0; c0 < nrhs; c0 += cap) {
         const int cols = (int)std::min<int64_t>(cap, nrhs - c0);
-        const dim3 glc(gl.x, (unsigned)cols), grc(asmb::blocks(f.nWg).x, (unsigned)cols), gredc(gred, (unsigned)cols);
         double* st = w.stage;                                    // [ru block | rw block | directions], then the results
         double* back = st + cap * (ldn + ldT + std::max<int64_t>(h->ev->n_dpar, 1));
         auto axpby = [&](double sa, const double* a, double sb, const double* b, const double* sc, double* out) {
-            asmb::launch(k_kktm_axpby, glc, dim3(256), s, sa, a, sb, b, mask, ldn, ldn, sc, out);
+            at.axpby(sa, a, sb, b, mask, sc, out, cols);
         };
         auto axpby_rows = [&](double sa, const double* a, double sb, const double* b, double* out) {
-            asmb::launch(k_kktm_axpby, grc, dim3(256), s, sa, a, sb, b, (const double*)nullptr, nW, ldT, (const double*)nullptr, out);
+            at.axpby_rows(sa, a, sb, b, nW, f.nWg, out, cols);
         };
         // tt = A' S^-1 b for a block b over the working rows (t: where the substitution may work)
         auto normal_back = [&](const double* b, double* t) { ops.mul_AT(ops.solve_S(b, t, cols), tt, cols); };
@@ -5859,7 +5975,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             HIPCHK(asmb::fill_async(dx0, 0, cap * ldn * sizeof(double), s));
         }
         // the share of the normal step that the radius admits: theta, dx0 <- theta dx0, Dt^2
-        if (trust) asmb::launch(k_kktm_normal, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)w.rad, tr.share, dx0, ldn, ldn);
+        if (trust) at.normal(scal, w.rad, tr.share, dx0, cols);
         // 4. projected conjugate gradients on null(A), the columns in lockstep: minimise 1/2 d'H_FF d + (ru_F + H_FF dx0)'d
         HIPCHK(asmb::fill_async(cd, 0, cap * ldn * sizeof(double), s));
         if (run_cg) {
@@ -5870,18 +5986,17 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             project(cr, nullptr);
             project(cr, nullptr);
             unsigned pub = pub_next(h);
-            asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 1, f.rtol, pub, (int)trust);
+            at.cg_dir(R, cr, 1, f.rtol, pub, (int)trust, cols);
             int active = kk_read_scal(h, pub);
             for (int64_t it = 0; active > 0 && it < f.max_iter; ++it) {
-                asmb::launch(k_kktm_cg_p, glc, dim3(256), s, (const double*)scal, (const double*)cr, cp, ldn, ldn);
+                at.cg_p(scal, cr, cp, cols);
                 ops.hess(cp, hraw, cols);
-                if (trust) asmb::launch(k_kktm_cg_curv<true>, gredc, dim3(256), s, R, (const double*)cp, (const double*)hraw, mask, (const double*)cd, hp, ldn, ldn);
-                else asmb::launch(k_kktm_cg_curv<false>, gredc, dim3(256), s, R, (const double*)cp, (const double*)hraw, mask, (const double*)cd, hp, ldn, ldn);
-                asmb::launch(k_kktm_cg_step, glc, dim3(256), s, (const double*)scal, (const double*)cp, (const double*)hp, cd, cr, ldn, ldn);
+                at.cg_curv(trust, R, cp, hraw, mask, cd, hp, cols);
+                at.cg_step(scal, cp, hp, cd, cr, cols);
                 project(cr, scal);
                 project(cr, scal);
                 pub = pub_next(h);
-                asmb::launch(k_kktm_cg_dir, gredc, dim3(256), s, R, (const double*)cr, ldn, ldn, 0, f.rtol, pub, (int)trust);
+                at.cg_dir(R, cr, 0, f.rtol, pub, (int)trust, cols);
                 active = kk_read_scal(h, pub);
                 cnt.rounds += 1;
             }
@@ -5900,14 +6015,13 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             axpby(1.0, qq, -1.0, tt, nullptr, cg);
             ops.mul_A(cg, tw, cols);
             axpby_rows(1.0, dlw, 1.0, ops.solve_S(tw, tw, cols), dlw);
-            asmb::launch(k_kktm_scatter, grc, dim3(256), s, (const double*)dlw, ldT, f.wrow, nW, dlf, Mp);
+            at.scatter(dlw, f.wrow, nW, f.nWg, dlf, Mp, cols);
             ops.mul_A(ddx, adx, cols);
             ops.jt_dlam(dlw, dlf, jtl, cols);
         } else {
             HIPCHK(asmb::fill_async(jtl, 0, cap * ldn * sizeof(double), s));
         }
-        asmb::launch(k_kktm_finish, dim3((unsigned)cols), dim3(1024), s, scal, (const double*)hdx, (const double*)b_ru, (const double*)jtl, mask, n, ldn, (const double*)adx,
-                     (const double*)rww, nW, ldT, ddz, trust ? (const double*)ddx : (const double*)nullptr);
+        at.finish(scal, hdx, b_ru, jtl, mask, n, adx, rww, nW, ddz, trust ? (const double*)ddx : (const double*)nullptr, cols);
         HIPCHK(asmb::copy_async(back, ddx, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(asmb::copy_async(back + cap * ldn, ddz, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
         if (m > 0) HIPCHK(asmb::copy_async(back + 2 * cap * ldn, dlf, (int64_t)cols * Mp * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -6419,8 +6533,8 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     HIPCHK(asmb::copy_async(i_lp_rows, hi, n_in * sizeof(int), hipMemcpyHostToDevice, s));
     const SlpVecs V = ev_vecs(*h->ev);
     const EqpFace P{V.E, V.g_L, V.g_U, V.x, V.x_L, V.x_U, i_lp_rows, i_lp_bnd, i_twin, n, m, tol_active};
-    const unsigned gf = (unsigned)std::min<int64_t>(asmb::blocks(std::max(n, m)).x, KK_MAXWG);
-    asmb::launch(k_eqp_face, dim3(gf), dim3(256), s, P, R, i_rows, i_bnd, i_side, d_rw, i_cnt);
+    const KktSites at(s, h->sk->ldn, K.ldT);
+    at.eqp_face(P, R, i_rows, i_bnd, i_side, d_rw, i_cnt);
     HIPCHK(asmb::copy_async(hi + n_in, i_rows, n_out * sizeof(int), hipMemcpyDeviceToHost, s));
     if (m > 0) HIPCHK(asmb::copy_async(hd, d_rw, m * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(asmb::copy_async(hd + m, h->ev->d_df, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -6447,8 +6561,7 @@ static void do_eqp_trial(asm_handle* h, const double* x, const double* lambda, c
     double* hx = K.eq_h;
     std::memcpy(hx, dx.data(), n * sizeof(double));
     HIPCHK(asmb::copy_async(d_dx, hx, n * sizeof(double), hipMemcpyHostToDevice, s));
-    const unsigned gt = (unsigned)std::min<int64_t>(asmb::blocks(n).x, KK_MAXWG);
-    asmb::launch(k_eqp_trial, dim3(gt), dim3(256), s, (const double*)d_dx, V.x, V.x_L, V.x_U, n, R, d_d, d_scal);
+    at.eqp_trial(d_dx, V.x, V.x_L, V.x_U, n, R, d_d, d_scal);
     HIPCHK(asmb::copy_async(hx + n, d_d, (n + EQP_SCAL) * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(asmb::sync(s));
     const double* sc = hx + 2 * n;
@@ -6973,6 +7086,199 @@ int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double s
         HIPCHK(asmb::sync(h->stream));
         HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHK(asmb::copy(int_inout, dI, nint * sizeof(int), hipMemcpyDeviceToHost));
+    });
+}
+
+// The kernels of the KKT column family and of the SLP-EQP trial step (asm_kkt_kernels.hip.h, asm_eqp_kernels.hip.h), one launch per stage,
+// through the launch sites the drivers use (KktSites) and on blocks of the hook's own with the solver's pitches - see include/asm_hip.h.
+// Every size, offset and index is checked here before anything is launched.
+int asm_test_kkt_stages(asm_handle* h, int64_t n, int64_t M, int64_t nW, int64_t capW, int32_t cols, int64_t* layout_out, double* dbl_inout, int64_t ndbl,
+                        int32_t* int_inout, int64_t nint, const int64_t* i64, int64_t ni64, uint32_t* cnt_inout, uint32_t* act_inout, double* hscal_inout,
+                        uint32_t* hseq_inout, const asm_kkt_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return guarded(h, [&] {
+        const int64_t LIM = (int64_t)1 << 20, CW = KKM_CW;
+        if (!layout_out || n < 1 || n > LIM || M < 0 || M > LIM || nW < 0 || nW > capW || capW > LIM || (nW > 0 && M == 0) || cols < 1 || cols > CW || nstages < 0)
+            throw std::invalid_argument("asm_test_kkt_stages: bad size");
+        const int64_t ldn = IpmLayout(n, M, 0).ldn, Mp = std::max<int64_t>(IpmLayout(n, M, 0).Mp, 32), ldT = round_up(std::max<int64_t>(capW, 1), 32);
+        const int64_t nWp = round_up(nW, 32), nWg = round_up(nW, 64);
+        const int64_t o_vec = 0, o_row = o_vec + 14 * CW * ldn, o_dlf = o_row + 5 * CW * ldT, o_mask = o_dlf + CW * Mp, o_rad = o_mask + ldn, o_scal = o_rad + CW,
+                      o_part = o_scal + CW * KKM_SCAL + 16, dbl_total = o_part + CW * KK_MAXWG * KK_SLOTS;
+        const int64_t io_wrow = 0, io_wpos = Mp, io_rows = 2 * Mp, io_counts = io_rows + CW, int_total = io_counts + 4;
+        {
+            const int64_t lay[ASM_KKT_LAYOUT_LEN] = {ldn, ldT, Mp, nWp, nWg, dbl_total, int_total, o_vec, o_row, o_dlf, o_mask, o_rad, o_scal, o_part,
+                                                     io_wrow, io_wpos, io_rows, io_counts, KKM_SCAL, KK_MAXWG * KK_SLOTS};
+            for (int k = 0; k < ASM_KKT_LAYOUT_LEN; ++k) layout_out[k] = lay[k];
+        }
+        if (!dbl_inout) return;      // layout query
+        if (!int_inout || !cnt_inout || !act_inout || !hscal_inout || !hseq_inout || (nstages > 0 && (!stages || !grid_out)) || ndbl < dbl_total || nint < int_total ||
+            ndbl > ((int64_t)1 << 31) || nint > ((int64_t)1 << 31) || ni64 < 0 || ni64 > ((int64_t)1 << 31) || (ni64 > 0 && !i64))
+            throw std::invalid_argument("asm_test_kkt_stages: bad buffer");
+        const int32_t* iv = int_inout;
+        auto bad = [](const char* what) { throw std::invalid_argument(std::string("asm_test_kkt_stages: ") + what); };
+        auto dspan = [&](int64_t off, int64_t len, bool nullable = false) {
+            if (nullable && off == -1) return;
+            if (off < 0 || len < 0 || off > ndbl || len > ndbl - off) bad("vector outside the double block");
+        };
+        auto ilist = [&](int64_t off, int64_t len, int64_t lo, int64_t hi) {      // an int list with entries in [lo, hi)
+            if (off < 0 || len < 0 || off > nint || len > nint - off) bad("list outside the int block");
+            for (int64_t a = 0; a < len; ++a)
+                if (iv[off + a] < lo || iv[off + a] >= hi) bad("index out of range");
+        };
+        auto iptr = [&](int64_t off, int64_t len) -> int64_t {                     // a pointer list of len + 1 entries: from >= 0, not decreasing; its last entry
+            ilist(off, len + 1, 0, (int64_t)1 << 31);
+            for (int64_t a = 0; a < len; ++a)
+                if (iv[off + a] > iv[off + a + 1]) bad("pointer list decreases");
+            return iv[off + len];
+        };
+        auto llist = [&](int64_t off, int64_t len, int64_t lo, int64_t hi) {
+            if (off < 0 || len < 0 || off > ni64 || len > ni64 - off) bad("list outside the 64-bit block");
+            for (int64_t a = 0; a < len; ++a)
+                if (i64[off + a] < lo || i64[off + a] >= hi) bad("index out of range");
+        };
+        auto lptr = [&](int64_t off, int64_t len) -> int64_t {
+            llist(off, len + 1, 0, (int64_t)1 << 31);
+            for (int64_t a = 0; a < len; ++a)
+                if (i64[off + a] > i64[off + a + 1]) bad("pointer list decreases");
+            return i64[off + len];
+        };
+        ilist(io_wrow, nW, 0, M);
+        ilist(io_rows, cols, 0, std::max<int64_t>(M, 1));
+        const int64_t vb = (int64_t)cols * ldn, rb = (int64_t)cols * ldT;      // the first `cols` rows of a block over the variables / the working rows
+        bool own_wpos = false;
+        for (int64_t q = 0; q < nstages; ++q) {
+            const asm_kkt_stage& st = stages[q];
+            const int64_t* x = st.x;
+            for (int a = 0; a < 3; ++a)
+                if (st.len[a] < 0 || st.len[a] > ((int64_t)1 << 24)) bad("length out of range");
+            switch (st.kind) {
+            case ASM_KKT_GATHER: case ASM_KKT_GATHER_T:
+                if (st.len[0] < M) bad("the matrix has fewer rows than the LP");
+                dspan(x[0], st.len[0] * ldn); dspan(x[1], st.kind == ASM_KKT_GATHER ? nW * ldn : ldn * ldT);
+                break;
+            case ASM_KKT_HESS_PRODUCT: {
+                const int64_t nnz = lptr(st.lx[0], n);
+                llist(st.lx[1], nnz, 0, st.len[0]); llist(st.lx[2], nnz, 0, n);
+                dspan(x[0], CW * ldn); dspan(x[1], vb); dspan(x[2], st.len[0]);
+                break;
+            }
+            case ASM_KKT_AXPBY: { const int64_t b = st.flag[2] ? rb : vb; dspan(x[0], b); dspan(x[1], b, true); dspan(x[2], b); break; }
+            case ASM_KKT_SCATTER: dspan(x[0], rb); dspan(x[1], (int64_t)cols * Mp); break;
+            case ASM_KKT_CROSS_RHS: case ASM_KKT_CROSS_RHS_COLS: {
+                const bool one = st.kind == ASM_KKT_CROSS_RHS;
+                if (st.len[0] < 0 || st.len[0] > M) bad("function rows outside [0, M]");
+                const int64_t lc = n + M - st.len[0];
+                if (!one && st.len[1] < lc) bad("pitch of the cross derivatives");
+                dspan(x[0], one ? lc : (int64_t)cols * st.len[1]); dspan(x[1], one ? n : vb); dspan(x[2], one ? nW : rb);
+                break;
+            }
+            case ASM_KKT_BOUND_RHS: dspan(x[0], cols, true); dspan(x[1], vb); dspan(x[2], rb); break;
+            case ASM_KKT_CG_P: dspan(x[0], vb); dspan(x[1], vb); break;
+            case ASM_KKT_NORMAL: case ASM_KKT_CG_DIR: dspan(x[0], vb); break;
+            case ASM_KKT_CG_CURV: case ASM_KKT_CG_STEP: dspan(x[0], vb); dspan(x[1], vb); dspan(x[2], vb); dspan(x[3], vb); break;
+            case ASM_KKT_FINISH: dspan(x[0], vb); dspan(x[1], vb); dspan(x[2], vb); dspan(x[3], rb); dspan(x[4], rb); dspan(x[5], vb); dspan(x[6], vb, true); break;
+            case ASM_KKTS_VALS: {
+                const int64_t ndup = lptr(st.lx[1], st.len[0]);
+                llist(st.lx[0], ndup, 0, st.len[1]);
+                dspan(x[0], st.len[1]); dspan(x[1], st.len[0]);
+                break;
+            }
+            case ASM_KKTS_WPOS: own_wpos = true; break;
+            case ASM_KKTS_MUL_A: {
+                const int64_t nnz = iptr(st.ix[0], M);
+                ilist(st.ix[1], nnz, 0, n);
+                dspan(x[0], nnz); dspan(x[1], vb); dspan(x[2], rb);
+                break;
+            }
+            case ASM_KKTS_MUL_AT: {
+                const int64_t nnz = iptr(st.ix[0], n);
+                ilist(st.ix[1], nnz, 0, M); ilist(st.ix[2], nnz, 0, st.len[0]);
+                if (!own_wpos) ilist(io_wpos, M, -1, nW);
+                dspan(x[0], st.len[0]); dspan(x[1], rb); dspan(x[2], vb);
+                break;
+            }
+            case ASM_EQP_FACE: {
+                const int64_t ne = st.len[0], me = st.len[1], na = st.len[2];
+                if (ne < 0 || me < 0 || na < 0 || ne > LIM || me > LIM || na > me || std::max(ne, me) < 1) bad("sizes of the face");
+                dspan(x[0], me); dspan(x[1], me); dspan(x[2], me); dspan(x[3], ne); dspan(x[4], ne); dspan(x[5], ne); dspan(x[6], me);
+                ilist(st.ix[0], me + na, 0, 2); ilist(st.ix[1], ne, -1, 2); ilist(st.ix[2], me, -1, na);
+                const int64_t lo = (int64_t)INT32_MIN, hi = (int64_t)INT32_MAX + 1;
+                ilist(st.ix[3], me, lo, hi); ilist(st.ix[4], ne, lo, hi); ilist(st.ix[5], me, lo, hi); ilist(st.ix[6], EQP_COUNTS, lo, hi);
+                break;
+            }
+            case ASM_EQP_TRIAL:
+                if (st.len[0] < 1 || st.len[0] > LIM) bad("size of the trial step");
+                for (int a = 0; a < 5; ++a) dspan(x[a], st.len[0]);
+                dspan(x[5], EQP_SCAL);
+                break;
+            default: bad("unknown stage");
+            }
+        }
+        HIPCHK(hipSetDevice(h->device));
+        double *dD = nullptr, *hScal = nullptr, *dhScal = nullptr;
+        int* dI = nullptr;
+        int64_t* dL = nullptr;
+        unsigned *dCnt = nullptr, *dAct = nullptr, *hSeq = nullptr, *dhSeq = nullptr;
+        BufPool tmp;
+        tmp.upload(dD, dbl_inout, ndbl);
+        tmp.upload(dI, (const int*)int_inout, nint);
+        tmp.upload(dL, i64, ni64);
+        tmp.upload(dCnt, (const unsigned*)cnt_inout, CW + 1);
+        tmp.upload(dAct, (const unsigned*)act_inout, CW);
+        tmp.alloc(hScal, 64, BufPool::MAPPED, &dhScal);
+        tmp.alloc(hSeq, 16, BufPool::MAPPED, &dhSeq);
+        hScal[0] = hscal_inout[0];
+        *hSeq = *hseq_inout;
+        const KktSites at(h->stream, ldn, ldT);
+        double* const scal = dD + o_scal;
+        const KktMulti R{dD + o_part, dCnt, scal, dAct, dhScal, dhSeq};
+        const KktRed R0{dD + o_part, dCnt, scal};
+        const double* const mask = dD + o_mask;
+        const int *wrow = dI + io_wrow, *rows = dI + io_rows;
+        int* const wpos = dI + io_wpos;
+        auto X = [&](int64_t off) { return off < 0 ? nullptr : dD + off; };
+        for (int64_t q = 0; q < nstages; ++q) {      // one after the other on the handle's stream, no host synchronisation in between
+            const asm_kkt_stage& st = stages[q];
+            const int64_t* x = st.x;
+            const double* const m_or_null = st.flag[0] ? mask : nullptr;
+            unsigned g = 0;
+            switch (st.kind) {
+            case ASM_KKT_GATHER: g = at.gather(X(x[0]), wrow, mask, nW, nWg, X(x[1])); break;
+            case ASM_KKT_GATHER_T: g = at.gather_t(X(x[0]), wrow, m_or_null, nW, nWp, X(x[1])); break;
+            case ASM_KKT_HESS_PRODUCT: g = at.hess_product(dL + st.lx[0], dL + st.lx[1], dL + st.lx[2], X(x[2]), X(x[0]), n, cols, X(x[1])); break;
+            case ASM_KKT_AXPBY:
+                if (st.flag[2]) g = at.axpby_rows(st.s[0], X(x[0]), st.s[1], X(x[1]), nW, nWg, X(x[2]), cols);
+                else g = at.axpby(st.s[0], X(x[0]), st.s[1], X(x[1]), m_or_null, st.flag[1] ? scal : nullptr, X(x[2]), cols);
+                break;
+            case ASM_KKT_SCATTER: g = at.scatter(X(x[0]), wrow, nW, nWg, X(x[1]), Mp, cols); break;
+            case ASM_KKT_CROSS_RHS: g = at.cross_rhs(X(x[0]), n, st.len[0], wrow, nW, X(x[1]), X(x[2])); break;
+            case ASM_KKT_CROSS_RHS_COLS: g = at.cross_rhs_cols(X(x[0]), st.len[1], n, st.len[0], wrow, nW, X(x[1]), X(x[2]), cols); break;
+            case ASM_KKT_BOUND_RHS: g = at.bound_rhs(rows, X(x[0]), wrow, nW, X(x[1]), X(x[2]), cols); break;
+            case ASM_KKT_CG_P: g = at.cg_p(scal, X(x[0]), X(x[1]), cols); break;
+            case ASM_KKT_NORMAL: g = at.normal(scal, dD + o_rad, st.s[0], X(x[0]), cols); break;
+            case ASM_KKT_CG_CURV: g = at.cg_curv(st.flag[0] != 0, R, X(x[0]), X(x[1]), mask, X(x[2]), X(x[3]), cols); break;
+            case ASM_KKT_CG_STEP: g = at.cg_step(scal, X(x[0]), X(x[1]), X(x[2]), X(x[3]), cols); break;
+            case ASM_KKT_CG_DIR: g = at.cg_dir(R, X(x[0]), st.flag[0], st.s[0], st.pub, st.flag[1], cols); break;
+            case ASM_KKT_FINISH: g = at.finish(scal, X(x[0]), X(x[1]), X(x[2]), mask, n, X(x[3]), X(x[4]), nW, X(x[5]), X(x[6]), cols); break;
+            case ASM_KKTS_VALS: g = at.kkts_vals(X(x[0]), dL + st.lx[0], dL + st.lx[1], st.len[0], X(x[1])); break;
+            case ASM_KKTS_WPOS: g = at.kkts_wpos(wrow, nW, M, wpos); break;
+            case ASM_KKTS_MUL_A: g = at.kkts_mul_a(dI + st.ix[0], dI + st.ix[1], X(x[0]), wrow, mask, X(x[1]), nW, nWg, X(x[2]), cols); break;
+            case ASM_KKTS_MUL_AT: g = at.kkts_mul_at(dI + st.ix[0], dI + st.ix[1], dI + st.ix[2], X(x[0]), wpos, m_or_null, X(x[1]), n, X(x[2]), cols); break;
+            case ASM_EQP_FACE: {
+                const EqpFace P{X(x[0]), X(x[1]), X(x[2]), X(x[3]), X(x[4]), X(x[5]), dI + st.ix[0], dI + st.ix[1], dI + st.ix[2], st.len[0], st.len[1], st.s[0]};
+                g = at.eqp_face(P, R0, dI + st.ix[3], dI + st.ix[4], dI + st.ix[5], X(x[6]), dI + st.ix[6]);
+                break;
+            }
+            default: g = at.eqp_trial(X(x[0]), X(x[1]), X(x[2]), X(x[3]), st.len[0], R0, X(x[4]), X(x[5]));
+            }
+            grid_out[q] = g;
+        }
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(dbl_inout, dD, ndbl * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(int_inout, dI, nint * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(cnt_inout, dCnt, (CW + 1) * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(act_inout, dAct, CW * sizeof(unsigned), hipMemcpyDeviceToHost));
+        hscal_inout[0] = hScal[0];
+        *hseq_inout = *hSeq;
     });
 }
 

@@ -1277,6 +1277,64 @@ int asm_test_ns_setup_stages(asm_handle* h, const double* dE, const double* fm, 
                              double* Y_inout, double* T_inout, double* d_inout, double* f0_out, double* Lt_out, int32_t Zk,
                              const int32_t* hint_J, int64_t nhint, const asm_nss_stage* stages, int64_t nstages, uint32_t* grid_out,
                              int32_t* res_out, int32_t* setup_out);
+/* Test hook: the kernels of the KKT column family (asm_kkt_kernels.hip.h) and of the SLP-EQP trial step (asm_eqp_kernels.hip.h), one launch
+ * site per stage - the functions the drivers themselves launch through - on blocks the hook allocates with the solver's pitches.  Needs a
+ * handle from asm_create only, no model.  n variables, M LP rows, nW <= capW working rows, cols <= ASM_KKT_CHUNK columns; ldn = n rounded up
+ * to 32, ldT = max(capW, 1) rounded up to 32, Mp = max(M, 1) rounded up to 16 and not below 32, nWp / nWg = nW rounded up to 32 / 64.
+ * layout_out (ASM_KKT_LAYOUT_LEN) receives: ldn, ldT, Mp, nWp, nWg, the length of the double block, of the int block, then the offsets in
+ * the double block of: the 14 blocks over the variables (block k at + k 64 ldn: b_ru dx0 d r p hraw hp tt dx hdx q jtl dz g), the 5 blocks
+ * over the working rows (block k at + k 64 ldT: rww tw spare dlw adx), dlf (64 x Mp), mask (ldn), rad (64), scal (64 x 16 + 1: the columns'
+ * scalar blocks, then the active-column word), part (64 x KK_MAXWG x KK_SLOTS); then the offsets in the int block of wrow (Mp), wpos (Mp),
+ * rows (64), counts (4); then the doubles per scalar block and the partial-sum slots per column.  With dbl_inout == NULL the call only
+ * reports the layout.
+ *   dbl_inout / int_inout   the blocks, each followed by vectors / lists of the caller's that stages name by offset; loaded before the first
+ *                           stage, returned whole after the last.  i64 (ni64 entries): read-only 64-bit lists, named by offset lx[].
+ *   cnt_inout (65), act_inout (64)   the arrival counters (the last one counts finished columns) and the active flags
+ *   hscal_inout (1), hseq_inout (1)  the host-mapped active-column word and its sequence word, made as asm_sublp_setup makes the handle's
+ * Products with A, A', H by the dense back ends and the substitutions are inputs, not stages.  The kernels run with an empty batch table.
+ * Checked before the first launch (ASM_ERR_ARG otherwise): sizes, every offset and length against its block, every index a list holds
+ * (wrow, wpos, rows, col, row, pos, poth, pent, perm, twin, the LP states), that pointer lists do not decrease, and cols.
+ * x[] / ix[] entries of -1 pass a null pointer where the kernel takes one (*). */
+enum {
+    ASM_KKT_GATHER = 0,      /* J = x[0] (len[0] rows of ldn), Aw = x[1] (nW rows of ldn) */
+    ASM_KKT_GATHER_T,        /* J = x[0] (len[0] rows), AT = x[1] (ldn x ldT); flag[0]: masked */
+    ASM_KKT_HESS_PRODUCT,    /* V = x[0] (64 rows of ldn), OUT = x[1] (cols rows), values = x[2] (len[0]); pptr = lx[0] (n + 1), pent = lx[1], poth = lx[2] */
+    ASM_KKT_AXPBY,           /* a = x[0], b = x[1] (*), out = x[2]; s[0] = sa, s[1] = sb; flag[0]: mask, flag[1]: scal, flag[2]: blocks over the working rows */
+    ASM_KKT_SCATTER,         /* y = x[0] (cols rows of ldT), out = x[1] (cols rows of Mp) */
+    ASM_KKT_CROSS_RHS,       /* cx = x[0] (n + M - len[0]), n_fn = len[0]; ru = x[1] (n), rww = x[2] (nW) */
+    ASM_KKT_CROSS_RHS_COLS,  /* cx = x[0] (cols rows of pitch len[1] >= n + M - len[0]), n_fn = len[0]; ru = x[1], rww = x[2] (blocks) */
+    ASM_KKT_BOUND_RHS,       /* delta = x[0] (*) (cols), ru = x[1], rww = x[2] (blocks); the rows list of the int block */
+    ASM_KKT_CG_P,            /* g = x[0], p = x[1] */
+    ASM_KKT_NORMAL,          /* dx0 = x[0]; s[0] = share; the radii of the double block */
+    ASM_KKT_CG_CURV,         /* p = x[0], hp_raw = x[1], d = x[2], hp = x[3]; flag[0]: the trust-region form */
+    ASM_KKT_CG_STEP,         /* p = x[0], hp = x[1], d = x[2], r = x[3] */
+    ASM_KKT_CG_DIR,          /* r = x[0]; flag[0]: init, flag[1]: tr; s[0] = rtol; pub */
+    ASM_KKT_FINISH,          /* hdx = x[0], ru = x[1], jtl = x[2], adx = x[3], rww = x[4], dz = x[5], dx = x[6] (*) */
+    ASM_KKTS_VALS,           /* dE = x[0] (len[1]), vals = x[1] (len[0] = nu); perm = lx[0], ustart = lx[1] (nu + 1) */
+    ASM_KKTS_WPOS,           /* wrow, wpos of the int block */
+    ASM_KKTS_MUL_A,          /* val = x[0], V = x[1], T = x[2] (blocks); ptr = ix[0] (M + 1), col = ix[1] */
+    ASM_KKTS_MUL_AT,         /* val = x[0] (len[0]), Y = x[1], V = x[2] (blocks); cptr = ix[0] (n + 1), row = ix[1], pos = ix[2]; flag[0]: masked */
+    ASM_EQP_FACE,            /* len[0] = n, len[1] = m, len[2] = twins; s[0] = tol; E g_L g_U x x_L x_U = x[0 .. 5], rw = x[6]; lp_rows lp_bnd twin = ix[0 .. 2],
+                                rows bnd side counts = ix[3 .. 6] */
+    ASM_EQP_TRIAL,           /* len[0] = n; dx x x_L x_U = x[0 .. 3], d = x[4], out = x[5] (4) */
+    ASM_KKT_NKINDS
+};
+#define ASM_KKT_LAYOUT_LEN 20
+typedef struct asm_kkt_stage {
+    int32_t kind;                 /* ASM_KKT_* / ASM_KKTS_* / ASM_EQP_* */
+    int32_t flag[3];
+    uint32_t pub;                 /* k_kktm_cg_dir: 0, or the sequence number to publish */
+    int32_t pad_;
+    double s[2];
+    int64_t len[3];
+    int64_t x[7];                 /* offsets into dbl_inout */
+    int64_t ix[7];                /* offsets into int_inout */
+    int64_t lx[3];                /* offsets into i64 */
+} asm_kkt_stage;
+int asm_test_kkt_stages(asm_handle* h, int64_t n, int64_t M, int64_t nW, int64_t capW, int32_t cols, int64_t* layout_out, double* dbl_inout,
+                        int64_t ndbl, int32_t* int_inout, int64_t nint, const int64_t* i64, int64_t ni64, uint32_t* cnt_inout,
+                        uint32_t* act_inout, double* hscal_inout, uint32_t* hseq_inout, const asm_kkt_stage* stages, int64_t nstages,
+                        uint32_t* grid_out);
 int asm_test_cholesky(asm_handle* h, const double* S /* N*N sym */, int64_t N, double* L_out /* N*N lower */);
 int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x);
 /* the bounded wait of the dataflow panel kernel with a producer that never publishes: returns ASM_ERR_HIP (reported once), the
