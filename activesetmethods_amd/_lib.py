@@ -194,6 +194,9 @@ PROTOTYPES = {
     "asm_eval_data_cross_t": (C.c_int, [_P, _D, _D, _D, _D, _D]),
     "asm_solution_adjoint": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_solution_adjoint_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_var_bound_sensitivity_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_solution_adjoint_z": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_solution_adjoint_z_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_kkt_step": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.c_double, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
     "asm_kkt_step_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
     "asm_kkt_set_form": (C.c_int, [_P, C.c_int32]),
@@ -249,6 +252,8 @@ PROTOTYPES = {
     "asm_batch_kkt_solve": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_solution_sensitivity": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, C.c_int32, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_bound_sensitivity": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_batch_var_bound_sensitivity": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_batch_solution_adjoint_z": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_solution_adjoint": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_get_stats": (C.c_int, [_P, C.POINTER(BatchStats)]),
     "asm_test_syrk": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _I32, C.c_int64, _D, _D, _D, C.c_int]),

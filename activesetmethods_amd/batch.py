@@ -463,6 +463,51 @@ class HipBatch:
                                                          _lib.dptr(OUT), _lib.dptr(DBOUND), _lib.dptr(AX), _lib.dptr(AL), infos))
         return OUT[:, :, :nd], DBOUND[:, :, :self.m], AX, AL[:, :, :self.m], [[infos[s * nrhs + c] for c in range(nrhs)] for s in range(S)]
 
+    def var_bound_sensitivity(self, x, lam, row_state, bound_state, vars, delta=None, max_iter=None, rtol=None):
+        """asm_batch_var_bound_sensitivity: per scenario HipSubOptimizer.var_bound_sensitivity_multi for the variables `vars` (0-based, the
+        same for every scenario; delta None: unit moves) - column c answers a move of the bound variable vars[c] sits at, the zero column
+        where the variable is free in the scenario; the outputs of kkt_solve_multi."""
+        from . import _lib
+        S, x, lam, rs, bs, par = self._kkt_args(x, lam, row_state, bound_state, max_iter, rtol)
+        vars = np.ascontiguousarray(np.atleast_1d(vars), np.int32)
+        if vars.ndim != 1 or len(vars) < 1:
+            raise ValueError("vars has shape %r, expected (nrhs,) with at least one variable" % (vars.shape,))
+        nrhs = len(vars)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.atleast_1d(delta), np.float64)
+            if delta.shape != (nrhs,):
+                raise ValueError("delta has shape %r, expected %r" % (delta.shape, (nrhs,)))
+        DX, DLAM, DZ, infos = self._kkt_outputs(S, nrhs)
+        self._check(self._lib.asm_batch_var_bound_sensitivity(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.i32ptr(vars),
+                                                              None if delta is None else _lib.dptr(delta), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return self._kkt_result(S, nrhs, self.m, DX, DLAM, DZ, infos)
+
+    def solution_adjoint_z(self, x, lam, row_state, bound_state, GX, GL, GZ=None, max_iter=None, rtol=None):
+        """(OUT, DBOUND [n_scen x nrhs x m], DXBOUND [n_scen x nrhs x n], AX, AL, infos[s][c]) of asm_batch_solution_adjoint_z: per scenario
+        HipSubOptimizer.solution_adjoint_z_multi, bit for bit - solution_adjoint with weights GZ [n_scen x nrhs x n] on the bound
+        multipliers (None: 0) and the gradients with respect to the variable bounds."""
+        from . import _lib
+        S, x, lam, rs, bs, par = self._kkt_args(x, lam, row_state, bound_state, max_iter, rtol)
+        GX = np.ascontiguousarray(GX, np.float64)
+        if GX.ndim != 3 or GX.shape[0] != S or GX.shape[1] < 1 or GX.shape[2] != self.n:
+            raise ValueError("GX has shape %r, expected (%d, nrhs, %d) with at least one function" % (GX.shape, S, self.n))
+        nrhs = GX.shape[1]
+        GL = np.ascontiguousarray(GL, np.float64) if self.m else np.zeros((S, nrhs, 1))
+        if self.m and GL.shape != (S, nrhs, self.m):
+            raise ValueError("GL has shape %r, expected %r" % (GL.shape, (S, nrhs, self.m)))
+        if GZ is not None:
+            GZ = np.ascontiguousarray(GZ, np.float64)
+            if GZ.shape != GX.shape:
+                raise ValueError("GZ has shape %r, expected %r" % (GZ.shape, GX.shape))
+        nd = self.n_dpar
+        OUT, DBOUND, AL = np.empty((S, nrhs, max(nd, 1))), np.empty((S, nrhs, max(self.m, 1))), np.empty((S, nrhs, max(self.m, 1)))
+        AX, DXBOUND, infos = np.empty((S, nrhs, self.n)), np.empty((S, nrhs, self.n)), (_lib.KktInfo * (S * nrhs))()
+        self._check(self._lib.asm_batch_solution_adjoint_z(self._b, S, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(GX), _lib.dptr(GL),
+                                                           None if GZ is None else _lib.dptr(GZ), par, _lib.dptr(OUT), _lib.dptr(DBOUND), _lib.dptr(DXBOUND),
+                                                           _lib.dptr(AX), _lib.dptr(AL), infos))
+        return (OUT[:, :, :nd], DBOUND[:, :, :self.m], DXBOUND, AX, AL[:, :, :self.m],
+                [[infos[s * nrhs + c] for c in range(nrhs)] for s in range(S)])
+
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.
         Returns (p, lambda, mult_x_U, mult_x_L, p_slack, status) with a leading scenario dimension."""
@@ -574,6 +619,21 @@ def bound_jacobians(hb, problems, runs, rows, tol=1e-6):
     x, lam = _run_points(hb, runs)
     DX, DLAM, _, infos = hb.bound_sensitivity(x, lam, rs, bs, rows)
     return _jacobian_stacks(DX, DLAM, infos)
+
+
+def var_bound_jacobians(hb, problems, runs, vars, tol=1e-6):
+    """(dx*/d(xbound) [S x n x k], dlam*/d(xbound) [S x m x k], dz*/d(xbound) [S x n x k], status [S x k]) of the scenarios of `hb` at their
+    runs: column q answers a unit move of the bound that variable vars[q] sits at (0-based, the same variables for every scenario) - the
+    zero column in a scenario where the variable is free - from one asm_batch_var_bound_sensitivity call.  The batch counterpart of
+    sensitivity.var_bound_jacobian; it reports the column statuses and does not raise on one that is not 0."""
+    vars = np.atleast_1d(np.asarray(vars, np.int64))
+    if vars.ndim != 1 or not len(vars) or np.any(vars < 0) or np.any(vars >= hb.n):
+        raise ValueError("vars must be a non-empty list of variables in [0, %d)" % hb.n)
+    rs, bs = working_sets(problems, runs, tol)
+    x, lam = _run_points(hb, runs)
+    DX, DLAM, DZ, infos = hb.var_bound_sensitivity(x, lam, rs, bs, vars)
+    dx, dlam, status = _jacobian_stacks(DX, DLAM, infos)
+    return dx, dlam, np.transpose(DZ, (0, 2, 1)).copy(), status
 
 
 def solve_batch_lockstep(problems, parameters, n_slots, device=0, rank=0, world=1, reduce_device=None, batch=None):

@@ -249,7 +249,7 @@ struct KktWork {                    // steps 3 to 6 on blocks of up to `cap` col
     int64_t cap = 0;
     double *vec = nullptr, *row = nullptr, *dlf = nullptr;      // 14 blocks cap x ldn over the variables, 5 cap x ldT over the working rows, cap x Mp over all rows
     double* rad = nullptr;                                      // cap trust-region radii (asm_kkt_step)
-    double* bnd = nullptr;                                      // cap > 1: [delta (cap doubles) | rows (cap ints)] of a chunk of bound sensitivities (k_kktm_bound_rhs)
+    double* bnd = nullptr;                                      // cap > 1: [delta (cap doubles) | rows or variables (cap ints)] of a chunk of bound sensitivities (k_kktm_bound_rhs, k_kktm_var_*)
     double* stage = nullptr;                                    // pinned: [ru | rw | directions] of a chunk, then its results
     double *Lt = nullptr, *AfT = nullptr;                       // cap > 1, the block products' own operands: the transposed factor, the unmasked transposed working rows (dense form only)
 };
@@ -259,6 +259,7 @@ struct KktBufs {
     FacBuf fac;                     // S = A A' and its factor
     double *dE = nullptr, *J = nullptr, *Aw = nullptr, *AwT = nullptr;      // Jacobian values and dense J of the solve's own, A = J[W, F] and its transposed copy
     double *sets = nullptr, *h_sets = nullptr;                              // [mask (ldn doubles) | working-row list (Mp ints)] and its pinned image
+    double *cmask = nullptr, *Ab = nullptr;                                 // asm_solution_adjoint_z* with weights on z (kk_gz): the mask of B, and J[W, B] (dense form only)
     int* dropped = nullptr;                                                 // the dropped-pivot count
     // the per-column reduction state, laid out for KKM_CW columns whatever the capacity (KktMulti)
     double *part = nullptr, *scal = nullptr;
@@ -793,6 +794,34 @@ struct KktSites {
     unsigned bound_rhs(const int* rows, const double* delta, const int* wrow, int64_t nW, double* ru, double* rww, int cols) const {
         const dim3 g(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols);
         asmb::launch(k_kktm_bound_rhs, g, dim3(256), s, rows, delta, wrow, nW, ru, ldn, rww, ldT);
+        return wg(g);
+    }
+    unsigned var_unit(const int* vars, const double* mask, double* E, int cols) const {
+        const dim3 g = over_vars(cols);
+        asmb::launch(k_kktm_var_unit, g, dim3(256), s, vars, mask, E, ldn);
+        return wg(g);
+    }
+    // J: the dense J of the solve, or nullptr in the sparse form (rww is then cleared for var_col)
+    unsigned var_rhs(const int* vars, const double* delta, const double* mask, const double* hcol, int64_t n, const double* J, const int* wrow, int64_t nW, double* ru, double* rww,
+                     int cols) const {
+        const dim3 g(asmb::blocks(std::max(ldn, ldT)).x, (unsigned)cols);
+        asmb::launch(k_kktm_var_rhs, g, dim3(256), s, vars, delta, mask, hcol, n, J, wrow, nW, ru, ldn, rww, ldT);
+        return wg(g);
+    }
+    unsigned var_col(const int* vars, const double* delta, const double* mask, const int* cptr, const int* row, const int* pos, const double* val, const int* wpos, double* rww,
+                     int cols) const {
+        const dim3 g(1, (unsigned)cols);
+        asmb::launch(k_kkts_var_col, g, dim3(256), s, vars, delta, mask, cptr, row, pos, val, wpos, rww, ldT);
+        return wg(g);
+    }
+    unsigned var_dx(const int* vars, const double* delta, const double* mask, int cols, double* dx) const {
+        const dim3 g = asmb::blocks(cols);
+        asmb::launch(k_kktm_var_dx, g, dim3(256), s, vars, delta, mask, cols, dx, ldn);
+        return wg(g);
+    }
+    unsigned gz_mask(const double* gz, const double* mask, int64_t n, double* gzb, double* cmask, int cols) const {
+        const dim3 g = over_vars(cols);
+        asmb::launch(k_kktm_gz_mask, g, dim3(256), s, gz, mask, n, ldn, gzb, cmask);
         return wg(g);
     }
     unsigned cg_p(const double* scal, const double* g_, double* p, int cols) const {
@@ -5429,6 +5458,23 @@ KktWork* kk_work(asm_handle* h, int64_t cap, bool sparse = false) {
     W.cap = cap;
     return &W;
 }
+// what only a call with weights on the bound multipliers needs (asm_solution_adjoint_z*, KktRhs::with_gz), at its first such call - for a
+// slot of a scenario batch before its fiber starts: the mask of B and, where the call will run the dense form, J[W, B] as a dense operand
+void kk_gz(asm_handle* h) {
+    kk_prepare(h);
+    KktBufs& K = h->ev->kk;
+    const bool sparse = K.form == ASM_KKT_SPARSE && h->sk->sp_ok && kk_sparse(h);
+    if (K.cmask && (sparse || K.Ab)) return;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->ev->mem;
+    const int64_t ldn = h->sk->ldn;
+    if (!K.cmask) M.zeroed(K.cmask, ldn, h->stream);
+    if (!sparse && !K.Ab) {
+        M.zeroed(K.Ab, K.capW * ldn, h->stream);
+        K.dense_bytes += K.capW * ldn * (int64_t)sizeof(double);
+    }
+    HIPCHK(asmb::sync(h->stream));
+}
 // the active-column word of the last k_kktm_cg_dir on the host: the kernel's own store into the host-mapped scalar block and the sequence
 // word the host spins on, or (pub == 0, ASM_HIP_SPIN=0) a copy and a stream synchronisation
 int kk_read_scal(asm_handle* h, unsigned pub) {
@@ -5706,6 +5752,8 @@ struct KktOps {
     }
     virtual void mul_A(const double* v, double* t, int cols) = 0;                   // T = V A'
     virtual void mul_AT(const double* y, double* v, int cols) = 0;                  // V = Y A
+    // T = V J[W, B]', the product with the columns that mul_A masks out (the weights on z of the adjoint entries; kk_gz made K.cmask, K.Ab)
+    virtual void mul_AB(const double* v, double* t, int cols) = 0;
     // S^-1 applied to the block b; t (b itself, or another block) is where the answer may go.  Returns where it is.
     virtual double* solve_S(const double* b, double* t, int cols) = 0;
     // JTL = J_W' dlam_W over all variables, those of B too, from dlam_W (dlw) or its scattered form over all rows (dlf, pitch Mp)
@@ -5718,6 +5766,11 @@ struct KktOneColumn final : KktOps {
     void hess(const double* v, double* out, int) override { hess_product(v, out, 1, true); }
     void mul_A(const double* v, double* t, int) override { asmb::launch(k_gemv_n, asmb::blocks(f.nWg, 4), dim3(256), s, h->ev->kk.Aw, ldn, v, t, f.nW, ldn); }
     void mul_AT(const double* y, double* v, int) override { asmb::launch(k_gemv_n_exact, asmb::blocks(ldn, 4), dim3(256), s, h->ev->kk.AwT, ldT, y, v, ldn, f.nW); }
+    void mul_AB(const double* v, double* t, int) override {
+        const KktBufs& K = h->ev->kk;
+        site.gather(K.J, f.wrow, K.cmask, f.nW, f.nWg, K.Ab);
+        asmb::launch(k_gemv_n, asmb::blocks(f.nWg, 4), dim3(256), s, K.Ab, ldn, v, t, f.nW, ldn);
+    }
     double* solve_S(const double* b, double* t, int) override {
         double* const out = b == t ? spare : t;
         dev.chol_solve_dev(h->ev->kk.fac, b, out, (int)f.nW);
@@ -5752,6 +5805,11 @@ struct KktBlock final : KktOps {
     void hess(const double* v, double* out, int cols) override { hess_product(v, out, cols, false); }
     void mul_A(const double* v, double* t, int cols) override { dev.gemm_nt(v, ldn, h->ev->kk.Aw, ldn, nullptr, 0, t, ldT, cols, (int)f.nW, (int)ldn, 0); }
     void mul_AT(const double* y, double* v, int cols) override { dev.gemm_nt(y, ldT, h->ev->kk.AwT, ldT, nullptr, 0, v, ldn, cols, (int)ldn, (int)f.nWp, 0); }
+    void mul_AB(const double* v, double* t, int cols) override {
+        const KktBufs& K = h->ev->kk;
+        site.gather(K.J, f.wrow, K.cmask, f.nW, f.nWg, K.Ab);
+        dev.gemm_nt(v, ldn, K.Ab, ldn, nullptr, 0, t, ldT, cols, (int)f.nW, (int)ldn, 0);
+    }
     double* solve_S(const double* b, double* t, int cols) override {
         if (b != t) HIPCHK(asmb::copy_async(t, b, (int64_t)cols * ldT * sizeof(double), hipMemcpyDeviceToDevice, s));
         dev.trsm_rows(h->ev->kk.fac, t, spare, ldT, cols, (int)f.nW, w.Lt);
@@ -5786,6 +5844,10 @@ struct KktSparse final : KktOps {
         site.kkts_mul_at(S.d_sc_ptr, S.d_sc_row, S.d_sc_pos, h->ev->kk.sp_vals, h->ev->kk.wpos, mask, y, n, v, cols);
     }
     void mul_AT(const double* y, double* v, int cols) override { at(y, f.mask, v, cols); }
+    void mul_AB(const double* v, double* t, int cols) override {
+        const Skeleton& S = *h->sk;
+        site.kkts_mul_a(S.d_sp_ptr, S.d_sp_col, h->ev->kk.sp_vals, f.wrow, h->ev->kk.cmask, v, f.nW, f.nWg, t, cols);
+    }
     double* solve_S(const double* b, double* t, int cols) override {
         if (w.cap == 1) {
             double* const out = b == t ? spare : t;
@@ -5811,25 +5873,33 @@ struct KktOut {
     double *DX = nullptr, *DLAM = nullptr, *DZ = nullptr;
     KktOut at(int64_t o, int64_t n, int64_t m) const { return {DX + o * n, m > 0 ? DLAM + o * m : nullptr, DZ ? DZ + o * n : nullptr}; }
 };
-// What the columns of a call are - one of three, made by the constructor of its name:
+// What the columns of a call are - one of four, made by the constructor of its name:
 //   given(RU, RW)        the rows of RU, RW are the right-hand sides (asm_kkt_solve(_multi), the step entries, the adjoint states)
 //   data(DC)             the rows of DC are directions of the data: the cross-derivative sweep makes each column's right-hand sides on
 //                        the device (asm_solution_sensitivity_multi)
 //   bound(rows, delta)   a row in [0, m) per column: column c is ru = 0, rw[rows[c]] = -delta[c] (delta == nullptr: -1.0), made on the device
 //                        by k_kktm_bound_rhs from 12 bytes per column - no n- or m-long vector is staged (asm_bound_sensitivity_multi)
+//   var_bound(vars, delta)  a variable in [0, n) per column, whose bound moves by delta[c] (delta == nullptr: 1.0): column c is
+//                        ru = delta H[:, j], rw = delta J[W, j], made on the device from 12 bytes per column (k_kktm_var_unit, one Hessian
+//                        product of the back end, k_kktm_var_rhs and in the sparse form k_kkts_var_col), and dx[j] = delta after the finish
+//                        step (k_kktm_var_dx); a variable outside B gives the zero column (asm_var_bound_sensitivity_multi)
+// A given() call may carry weights on the bound multipliers, with_gz(GZ), a row of n per column (asm_solution_adjoint_z*): the staged
+// columns are then corrected on the device to ru - H gz_B and rw - J[W, B] gz_B, gz_B = GZ on B and 0.0 on F.
 struct KktRhs {
-    enum Kind { GIVEN, DATA, BOUND } kind;
-    const double *RU = nullptr, *RW = nullptr, *DC = nullptr, *delta = nullptr;
-    const int32_t* rows = nullptr;
+    enum Kind { GIVEN, DATA, BOUND, VAR_BOUND } kind;
+    const double *RU = nullptr, *RW = nullptr, *DC = nullptr, *delta = nullptr, *GZ = nullptr;
+    const int32_t* rows = nullptr;      // BOUND: rows; VAR_BOUND: variables
     static KktRhs given(const double* RU, const double* RW) { KktRhs r(GIVEN); r.RU = RU; r.RW = RW; return r; }
     static KktRhs data(const double* DC) { KktRhs r(DATA); r.DC = DC; return r; }
     static KktRhs bound(const int32_t* rows, const double* delta) { KktRhs r(BOUND); r.rows = rows; r.delta = delta; return r; }
+    static KktRhs var_bound(const int32_t* vars, const double* delta) { KktRhs r(VAR_BOUND); r.rows = vars; r.delta = delta; return r; }
+    KktRhs with_gz(const double* gz) const { KktRhs r = *this; r.GZ = gz; return r; }
     bool derivative() const { return kind != GIVEN; }      // a derivative entry: the exact Hessian whatever the handle's type
     // scenario sc's n_col columns of a batch call; dc_stride: doubles from one scenario's directions to the next, 0 when they are shared
-    // (the rows and moves of BOUND always are)
+    // (the rows and moves of BOUND, the variables and moves of VAR_BOUND always are)
     KktRhs at(int64_t sc, int64_t n_col, int64_t n, int64_t m, int64_t dc_stride) const {
         KktRhs r = *this;
-        if (kind == GIVEN) { r.RU = RU + sc * n_col * n; r.RW = m > 0 ? RW + sc * n_col * m : nullptr; }
+        if (kind == GIVEN) { r.RU = RU + sc * n_col * n; r.RW = m > 0 ? RW + sc * n_col * m : nullptr; if (GZ) r.GZ = GZ + sc * n_col * n; }
         if (kind == DATA && DC) r.DC = DC + sc * dc_stride;
         return r;
     }
@@ -5863,11 +5933,31 @@ struct KktTrust {
 // Step 3 for the chunk of `cols` columns from column c0 on: its right-hand sides into the blocks b_ru (over the variables) and rww (over
 // the working rows), by the way of rhs.kind.  The staging area is [ru block | rw block | directions]; the first chunk of a DATA call
 // uploads the multipliers of the cross-derivative sweep, once.
-void kkt_stage_rhs(asm_handle* h, const KktFace& f, KktWork& w, const KktRhs& rhs, const double* lambda, const KktTrust& tr, int64_t c0, int cols, double* b_ru, double* rww) {
+// VAR_BOUND, and GIVEN with weights on z, multiply on the device: by ops, into the blocks va, vb over the variables and ta over the
+// working rows, free until step 4.
+void kkt_stage_rhs(asm_handle* h, const KktFace& f, KktOps& ops, const KktRhs& rhs, const double* lambda, const KktTrust& tr, int64_t c0, int cols, double* b_ru, double* rww,
+                   double* va, double* vb, double* ta) {
+    KktWork& w = ops.w;
     const hipStream_t s = h->stream;
     const int64_t n = h->sk->n, m = h->sk->m, ldn = h->sk->ldn, ldT = h->ev->kk.ldT, cap = w.cap, nW = f.nW;
     double* st = w.stage;
     switch (rhs.kind) {
+    case KktRhs::VAR_BOUND: {
+        // [delta | vars] of the chunk's columns, one upload as for BOUND; the unit block, its Hessian product, the scaling and the column of J
+        const KktBufs& K = h->ev->kk;
+        const Skeleton& S = *h->sk;
+        int* hr = reinterpret_cast<int*>(st + cols);
+        const int* dv = reinterpret_cast<const int*>(w.bnd + cols);
+        const double* dd = rhs.delta ? (const double*)w.bnd : (const double*)nullptr;
+        if (rhs.delta) std::memcpy(st, rhs.delta + c0, cols * sizeof(double));
+        for (int c = 0; c < cols; ++c) hr[c] = rhs.rows[c0 + c];
+        HIPCHK(asmb::copy_async(w.bnd, st, cols * (sizeof(double) + sizeof(int)), hipMemcpyHostToDevice, s));
+        ops.site.var_unit(dv, f.mask, vb, cols);
+        ops.hess(vb, va, cols);
+        ops.site.var_rhs(dv, dd, f.mask, va, n, f.sparse ? (const double*)nullptr : (const double*)K.J, f.wrow, nW, b_ru, rww, cols);
+        if (f.sparse && nW > 0) ops.site.var_col(dv, dd, f.mask, S.d_sc_ptr, S.d_sc_row, S.d_sc_pos, K.sp_vals, K.wpos, rww, cols);
+        return;
+    }
     case KktRhs::BOUND: {
         // [delta | rows] of the chunk's columns in the (unused) staging rows of ru, one upload, one launch
         int* hr = reinterpret_cast<int*>(st + cols);
@@ -5892,6 +5982,24 @@ void kkt_stage_rhs(asm_handle* h, const KktFace& f, KktWork& w, const KktRhs& rh
             double* hr = st + cap * (ldn + ldT);
             std::memcpy(hr, tr.radius + c0, cols * sizeof(double));
             HIPCHK(asmb::copy_async(w.rad, hr, cols * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+        if (rhs.GZ) {
+            // the weights on z, staged where the chunk's results will come back (free until then): gz_B by the complementary mask, then
+            // ru -= H gz_B (one Hessian product on the block) and rw -= J[W, B] gz_B (the one product with the columns of B)
+            double* hg = st + cap * (ldn + ldT + std::max<int64_t>(h->ev->n_dpar, 1));
+            for (int c = 0; c < cols; ++c) {
+                double* dg = hg + (int64_t)c * ldn;
+                std::memcpy(dg, rhs.GZ + (c0 + c) * n, n * sizeof(double));
+                for (int64_t j = n; j < ldn; ++j) dg[j] = 0.0;
+            }
+            HIPCHK(asmb::copy_async(va, hg, (int64_t)cols * ldn * sizeof(double), hipMemcpyHostToDevice, s));
+            ops.site.gz_mask(va, f.mask, n, vb, h->ev->kk.cmask, cols);
+            ops.hess(vb, va, cols);
+            ops.site.axpby(1.0, b_ru, -1.0, va, nullptr, nullptr, b_ru, cols);
+            if (nW > 0) {
+                ops.mul_AB(vb, ta, cols);
+                ops.site.axpby_rows(1.0, rww, -1.0, ta, nW, f.nWg, rww, cols);
+            }
         }
         return;
     }
@@ -5961,7 +6069,7 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             axpby(1.0, v, -1.0, tt, sc, v);
         };
         // 3. the right-hand sides of the chunk
-        kkt_stage_rhs(h, f, w, rhs, lambda, tr, c0, cols, b_ru, rww);
+        kkt_stage_rhs(h, f, ops, rhs, lambda, tr, c0, cols, b_ru, rww, hraw, hp, tw);
         // particular solution dx0 = -A' S^-1 rw_W
         if (nW > 0) {
             normal_back(rww, tw);
@@ -6022,6 +6130,9 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
             HIPCHK(asmb::fill_async(jtl, 0, cap * ldn * sizeof(double), s));
         }
         at.finish(scal, hdx, b_ru, jtl, mask, n, adx, rww, nW, ddz, trust ? (const double*)ddx : (const double*)nullptr, cols);
+        // (a variable-bound column: the moved variable itself, dx[j] = delta; the chunk's [delta | vars] are still in w.bnd)
+        if (rhs.kind == KktRhs::VAR_BOUND)
+            at.var_dx(reinterpret_cast<const int*>(w.bnd + cols), rhs.delta ? (const double*)w.bnd : (const double*)nullptr, mask, cols, ddx);
         HIPCHK(asmb::copy_async(back, ddx, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(asmb::copy_async(back + cap * ldn, ddz, (int64_t)cols * ldn * sizeof(double), hipMemcpyDeviceToHost, s));
         if (m > 0) HIPCHK(asmb::copy_async(back + 2 * cap * ldn, dlf, (int64_t)cols * Mp * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -6055,14 +6166,18 @@ void kkt_columns(asm_handle* h, const KktFace& f, KktOps& ops, int32_t nrhs, con
 }
 // The refusals the entries of the family share, under the entry's name `who`: per handle (kkt_run) and, on the calling thread, for a
 // scenario batch - which so refuses exactly what its fibers would.  out == nullptr: the adjoint entries, whose states are optional.
-void kkt_check_args(const std::string& who, int64_t m, int64_t nd, int32_t nrhs, const KktPoint& p, const KktRhs& rhs, const KktOut* out, const KktInfoSink& sink) {
+void kkt_check_args(const std::string& who, int64_t m, int64_t nd, int32_t nrhs, const KktPoint& p, const KktRhs& rhs, const KktOut* out, const KktInfoSink& sink,
+                    int64_t n = 0) {      // (n: read for VAR_BOUND alone)
     if (nrhs < 1) throw std::invalid_argument(who + ": nrhs < 1");
     bool null = !p.x || !p.bound_state || sink.null() || (m > 0 && (!p.lambda || !p.row_state));
     if (out) null = null || !out->DX || (m > 0 && !out->DLAM);
     if (rhs.kind == KktRhs::GIVEN) null = null || !rhs.RU || (m > 0 && !rhs.RW);
     if (rhs.kind == KktRhs::DATA) null = null || (nd > 0 && !rhs.DC);
-    if (rhs.kind == KktRhs::BOUND) null = null || !rhs.rows;
+    if (rhs.kind == KktRhs::BOUND || rhs.kind == KktRhs::VAR_BOUND) null = null || !rhs.rows;
     if (null) throw std::invalid_argument(who + ": null pointer");
+    if (rhs.kind == KktRhs::VAR_BOUND)
+        for (int32_t c = 0; c < nrhs; ++c)
+            if (rhs.rows[c] < 0 || rhs.rows[c] >= n) throw std::invalid_argument(who + ": a variable index outside [0, n)");
     if (rhs.kind == KktRhs::BOUND)
         for (int32_t c = 0; c < nrhs; ++c)
             if (rhs.rows[c] < 0 || rhs.rows[c] >= m) throw std::invalid_argument(who + ": a row index outside [0, m)");
@@ -6078,8 +6193,9 @@ void kkt_run(asm_handle* h, const char* who, int64_t cap, const KktPoint& p, int
     if (rhs.kind == KktRhs::DATA) cx_check(h, who);
     if (exact) hs_check(h, who);
     const bool lm = !exact && kkt_hess_lm(h, who);
-    kkt_check_args(me, h->sk->m, h->ev->n_dpar, nrhs, p, rhs, &out, sink);
+    kkt_check_args(me, h->sk->m, h->ev->n_dpar, nrhs, p, rhs, &out, sink, h->sk->n);
     tr.check(me, nrhs);
+    if (rhs.GZ) kk_gz(h);
     Dev dev(h);
     const KktFace f(h, dev, me, p.x, p.lambda, p.row_state, p.bound_state, par, lm);
     KktCounters own;
@@ -6105,7 +6221,7 @@ static void do_solution_sensitivity(asm_handle* h, const KktPoint& p, const doub
     do_kkt_solve(h, p, u.data(), w.data(), par, out, info, true);
 }
 // The multi entries under the name `who`, for the per-handle call and for a batch fiber: asm_kkt_solve_multi (KktRhs::given),
-// asm_solution_sensitivity_multi (data) and asm_bound_sensitivity_multi (bound)
+// asm_solution_sensitivity_multi (data), asm_bound_sensitivity_multi (bound) and asm_var_bound_sensitivity_multi (var_bound)
 static void do_kkt_solve_multi(asm_handle* h, const char* who, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, const asm_kkt_params* par, const KktOut& out,
                                asm_kkt_info* info) {
     kkt_run(h, who, KKM_CW, p, nrhs, rhs, par, out, info);
@@ -6148,7 +6264,46 @@ void adjoint_multi(asm_handle* h, const char* who, int64_t cap, const KktPoint& 
     ct_columns(h, p.x, p.lambda, nrhs, state.DX, -1.0, state.DLAM, OUT, cap);
     adjoint_dbound(p.row_state, h->sk->m, nrhs, state.DLAM, DBOUND);
 }
+// the same for the entries with weights on the bound multipliers (asm_solution_adjoint_z*): rhs carries GZ (KktRhs::with_gz; absent: the
+// launches of adjoint_multi, nothing prepared with zeros), the solve also returns its dz, the transposed sweep takes vx = gz_B - ax, and
+// dxbound_j = -dz_j on B, 0.0 on F
+void adjoint_z_multi(asm_handle* h, const char* who, int64_t cap, const KktPoint& p, int32_t nrhs, const KktRhs& rhs, const asm_kkt_params* par, double* OUT, double* DBOUND,
+                     double* DXBOUND, const KktOut& state, asm_kkt_info* info) {
+    const int64_t n = h->sk->n;
+    std::vector<double> dz((size_t)std::max<int64_t>(nrhs * n, 1));
+    kkt_run(h, who, cap, p, nrhs, rhs, par, {state.DX, state.DLAM, dz.data()}, info, KktTrust(), true);
+    if (rhs.GZ) {
+        std::vector<double> vx(dz.size());
+        for (int64_t c = 0; c < nrhs; ++c)
+            for (int64_t j = 0; j < n; ++j) vx[c * n + j] = (p.bound_state[j] != 0 ? rhs.GZ[c * n + j] : 0.0) - state.DX[c * n + j];
+        ct_columns(h, p.x, p.lambda, nrhs, vx.data(), 1.0, state.DLAM, OUT, cap);
+    } else {
+        ct_columns(h, p.x, p.lambda, nrhs, state.DX, -1.0, state.DLAM, OUT, cap);
+    }
+    adjoint_dbound(p.row_state, h->sk->m, nrhs, state.DLAM, DBOUND);
+    if (DXBOUND)
+        for (int64_t c = 0; c < nrhs; ++c)
+            for (int64_t j = 0; j < n; ++j) DXBOUND[c * n + j] = p.bound_state[j] != 0 ? -dz[c * n + j] : 0.0;
+}
 }  // namespace
+static void do_solution_adjoint_z(asm_handle* h, const KktPoint& p, const double* gx, const double* gl, const double* gz, const asm_kkt_params* par, double* out, double* dbound,
+                                  double* dxbound, double* ax, double* al, asm_kkt_info* info) {
+    adjoint_check(h, "asm_solution_adjoint_z");
+    const int64_t n = h->sk->n, m = h->sk->m;
+    adjoint_check_args("asm_solution_adjoint_z", m, h->ev->n_dpar, 1, p, gx, gl, out, info);
+    const AdjointSetup A(1, n, m, gx, ax, al);
+    adjoint_z_multi(h, "asm_kkt_solve", 1, p, 1, KktRhs::given(A.ru.data(), gl).with_gz(gz), par, out, dbound, dxbound, A.state, info);
+}
+static void do_solution_adjoint_z_multi(asm_handle* h, const KktPoint& p, int32_t nrhs, const double* GX, const double* GL, const double* GZ, const asm_kkt_params* par,
+                                        double* OUT, double* DBOUND, double* DXBOUND, double* AX, double* AL, asm_kkt_info* info) {
+    const char* who = "asm_solution_adjoint_z_multi";
+    adjoint_check(h, who);
+    hs_check(h, who);
+    const int64_t n = h->sk->n, m = h->sk->m;
+    adjoint_check_args(who, m, h->ev->n_dpar, nrhs, p, GX, GL, OUT, info);
+    const AdjointSetup A(nrhs, n, m, GX, AX, AL);
+    adjoint_z_multi(h, who, KKM_CW, p, nrhs, KktRhs::given(A.ru.data(), GL).with_gz(GZ), par, OUT, DBOUND, DXBOUND, A.state, info);
+}
 static void do_solution_adjoint(asm_handle* h, const KktPoint& p, const double* gx, const double* gl, const asm_kkt_params* par, double* out, double* dbound, double* ax,
                                 double* al, asm_kkt_info* info) {
     adjoint_check(h, "asm_solution_adjoint");
@@ -6256,6 +6411,24 @@ int asm_solution_adjoint(asm_handle* h, const double* x, const double* lambda, c
 int asm_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
                                const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
     return guarded(h, [&] { do_solution_adjoint_multi(h, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
+}
+
+int asm_var_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                    const int32_t* vars, const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(h, [&] {
+        do_kkt_solve_multi(h, "asm_var_bound_sensitivity_multi", {x, lambda, row_state, bound_state}, nrhs, KktRhs::var_bound(vars, delta), par, {DX, DLAM, DZ}, info);
+    });
+}
+
+int asm_solution_adjoint_z(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, const double* gx, const double* gl,
+                           const double* gz, const asm_kkt_params* par, double* out, double* dbound, double* dxbound, double* ax, double* al, asm_kkt_info* info) {
+    return guarded(h, [&] { do_solution_adjoint_z(h, {x, lambda, row_state, bound_state}, gx, gl, gz, par, out, dbound, dxbound, ax, al, info); });
+}
+
+int asm_solution_adjoint_z_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* GX,
+                                 const double* GL, const double* GZ, const asm_kkt_params* par, double* OUT, double* DBOUND, double* DXBOUND, double* AX, double* AL,
+                                 asm_kkt_info* info) {
+    return guarded(h, [&] { do_solution_adjoint_z_multi(h, {x, lambda, row_state, bound_state}, nrhs, GX, GL, GZ, par, OUT, DBOUND, DXBOUND, AX, AL, info); });
 }
 
 int asm_kkt_set_form(asm_handle* h, int32_t form) {
@@ -8639,7 +8812,7 @@ void batch_kkt_prepare(asm_batch* b, int count, const char* step = "asm_slp_run_
             if (cross_t) ct_prepare(e, KKM_CW);
         });
 }
-// The three multi entries on n_scen scenarios, the slots taking them in index order (for_each_scenario): per scenario do_kkt_solve_multi
+// The four multi entries on n_scen scenarios, the slots taking them in index order (for_each_scenario): per scenario do_kkt_solve_multi
 // under the per-handle entry's name `step`, on the scenario's part of the point, of the columns `rhs` and of the outputs (KktPoint::at,
 // KktRhs::at with dc_stride, KktOut::at) and with its data.  Everything that can be refused without a launch is refused here, on the
 // calling thread - the arguments by the per-handle entry's own kkt_check_args under the batch entry's name `who` - and what a slot
@@ -8653,7 +8826,7 @@ void batch_kkt_multi(asm_batch* b, const char* who, const char* step, int64_t n_
     if (data) cx_check(b->slots[0], who);
     const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m, nd = (int64_t)b->dpar0.size();
     if (n_scen < 1 || nrhs < 1) throw std::invalid_argument(me + ": n_scen < 1 or nrhs < 1");
-    kkt_check_args(me, m, nd, nrhs, p, rhs, &out, info);
+    kkt_check_args(me, m, nd, nrhs, p, rhs, &out, info, n);
     if (par && (par->max_iter < 0 || !(par->rtol >= 0.0))) throw std::invalid_argument(me + ": max_iter < 0 or rtol not >= 0");
     check_scen(b, n_scen, who);
     HIPCHK(hipSetDevice(b->device));
@@ -8667,9 +8840,11 @@ void batch_kkt_multi(asm_batch* b, const char* who, const char* step, int64_t n_
 }
 // asm_solution_adjoint_multi on n_scen scenarios, the slots taking them in index order: the checks as in batch_kkt_multi, the set-up of
 // the adjoint entries (AdjointSetup) for the functions of all scenarios, the workspaces before the fibers start
+// z: asm_batch_solution_adjoint_z - asm_solution_adjoint_z_multi per scenario, with the weights GZ (may be absent) and the variable-bound
+// gradients DXBOUND; what a slot needs for the weights (kk_gz) is made before the fibers start, too
 void batch_adjoint(asm_batch* b, int64_t n_scen, const KktPoint& p, int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par, double* OUT,
-                   double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
-    const char *who = "asm_batch_solution_adjoint", *step = "asm_solution_adjoint_multi";
+                   double* DBOUND, double* AX, double* AL, asm_kkt_info* info, bool z = false, const double* GZ = nullptr, double* DXBOUND = nullptr) {
+    const char *who = z ? "asm_batch_solution_adjoint_z" : "asm_batch_solution_adjoint", *step = z ? "asm_solution_adjoint_z_multi" : "asm_solution_adjoint_multi";
     const std::string me(who);
     batch_hs_prepare(b, who);
     adjoint_check(b->slots[0], who);
@@ -8680,13 +8855,19 @@ void batch_adjoint(asm_batch* b, int64_t n_scen, const KktPoint& p, int32_t nrhs
     check_scen(b, n_scen, who);
     HIPCHK(hipSetDevice(b->device));
     const AdjointSetup A(n_scen * nrhs, n, m, GX, AX, AL);
-    const KktRhs rhs = KktRhs::given(A.ru.data(), GL);
-    batch_kkt_prepare(b, (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size()), step, KKM_CW, false, true);
+    const KktRhs rhs = KktRhs::given(A.ru.data(), GL).with_gz(GZ);
+    const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
+    batch_kkt_prepare(b, count, step, KKM_CW, false, true);
+    for (int s = 0; GZ && s < count; ++s) in_slot(step, s, [&] { kk_gz(b->slots[s]); });
     for_each_scenario(b, n_scen, step, [&](asm_handle* h, int64_t sc, int) {
         batch_scenario_data(b, h, sc);
         asmb::next_cycle();
         const int64_t o = sc * nrhs;
-        adjoint_multi(h, step, KKM_CW, p.at(sc, n, m), nrhs, rhs.at(sc, nrhs, n, m, 0), par, OUT + o * nd, DBOUND ? DBOUND + o * m : nullptr, A.state.at(o, n, m), info + o);
+        if (z)
+            adjoint_z_multi(h, step, KKM_CW, p.at(sc, n, m), nrhs, rhs.at(sc, nrhs, n, m, 0), par, OUT + o * nd, DBOUND ? DBOUND + o * m : nullptr,
+                            DXBOUND ? DXBOUND + o * n : nullptr, A.state.at(o, n, m), info + o);
+        else
+            adjoint_multi(h, step, KKM_CW, p.at(sc, n, m), nrhs, rhs.at(sc, nrhs, n, m, 0), par, OUT + o * nd, DBOUND ? DBOUND + o * m : nullptr, A.state.at(o, n, m), info + o);
     });
 }
 // asm_eval_hessian_lagrangian (v == nullptr: values [n_scen x nnz] into out) or asm_eval_hessian_product (out [n_scen x n]) of n_scen
@@ -8757,7 +8938,7 @@ int asm_batch_slp_run_eqp(asm_batch* b, int64_t n_scen, const double* c_lb, cons
     });
 }
 
-// asm_kkt_solve_multi, asm_solution_sensitivity_multi and asm_bound_sensitivity_multi of n_scen scenarios (include/asm_hip.h, "Scenario
+// asm_kkt_solve_multi, asm_solution_sensitivity_multi, asm_bound_sensitivity_multi and asm_var_bound_sensitivity_multi of n_scen scenarios (include/asm_hip.h, "Scenario
 // batches: KKT solves and sensitivities")
 int asm_batch_kkt_solve(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                         const double* RU, const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
@@ -8779,6 +8960,20 @@ int asm_batch_solution_sensitivity(asm_batch* b, int64_t n_scen, const double* x
 int asm_batch_solution_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                const double* GX, const double* GL, const asm_kkt_params* par, double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info) {
     return guarded(b, [&] { batch_adjoint(b, n_scen, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
+}
+
+int asm_batch_solution_adjoint_z(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                 const double* GX, const double* GL, const double* GZ, const asm_kkt_params* par, double* OUT, double* DBOUND, double* DXBOUND, double* AX,
+                                 double* AL, asm_kkt_info* info) {
+    return guarded(b, [&] { batch_adjoint(b, n_scen, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info, true, GZ, DXBOUND); });
+}
+
+int asm_batch_var_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                    const int32_t* vars, const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
+    return guarded(b, [&] {
+        batch_kkt_multi(b, "asm_batch_var_bound_sensitivity", "asm_var_bound_sensitivity_multi", n_scen, {x, lambda, row_state, bound_state}, nrhs,
+                        KktRhs::var_bound(vars, delta), 0, par, {DX, DLAM, DZ}, info);
+    });
 }
 
 int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,

@@ -167,6 +167,60 @@ __global__ __launch_bounds__(256) void k_kktm_bound_rhs(AsmBt abt, const int* __
     if (j < ldn) ru[c * ldn + j] = 0.0;
     if (j < ldT) rww[c * ldT + j] = (j < nW && wrow[j] == rows[c]) ? -(delta ? delta[c] : 1.0) : 0.0;
 }
+// ---- The right-hand sides of a chunk of variable-bound sensitivities (asm_var_bound_sensitivity_multi): column c = blockIdx.y moves the
+// bound of variable j = vars[c] by delta[c] (delta == nullptr: 1.0) and is ru = delta H[:, j] over all n entries, rw = delta J[W, j].  A
+// variable outside B (mask[j] != 0) gives the zero column.  Four kernels, one writer per entry each:
+//   k_kktm_var_unit   E[c, :] = e_j (the zero row for a variable outside B): the operand of the chunk's Hessian product
+//   k_kktm_var_rhs    ru[c, k] = delta hcol[c, k] (one multiplication of what the Hessian product stored, 0 beyond n) and, dense form
+//                     (J != nullptr), rww[c, q] = delta J[wrow[q], j]; sparse form (J == nullptr) rww is cleared for
+//   k_kkts_var_col    rww[c, wpos[row]] = delta val over the CSC list of column j, rows outside W skipped (one workgroup per column)
+//   k_kktm_var_dx     after the finish step: dx[c, j] = delta for a variable of B
+__global__ __launch_bounds__(256) void k_kktm_var_unit(AsmBt abt, const int* __restrict__ vars, const double* __restrict__ mask, double* __restrict__ E, int64_t ldn) {
+    ASM_BARGS(abt, vars, mask, E, ldn);
+    const int64_t c = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= ldn) return;
+    const int64_t j = vars[c];
+    E[c * ldn + k] = (k == j && mask[j] == 0.0) ? 1.0 : 0.0;
+}
+__global__ __launch_bounds__(256) void k_kktm_var_rhs(AsmBt abt, const int* __restrict__ vars, const double* __restrict__ delta, const double* __restrict__ mask, const double* __restrict__ hcol, int64_t n, const double* __restrict__ J, const int* __restrict__ wrow, int64_t nW, double* __restrict__ ru, int64_t ldn, double* __restrict__ rww, int64_t ldT) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, vars, delta, mask, hcol, n, J, wrow, nW, ru, ldn, rww, ldT);
+    const int64_t c = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = vars[c];
+    const bool in_b = mask[j] == 0.0;
+    const double d = delta ? delta[c] : 1.0;
+    if (k < ldn) ru[c * ldn + k] = (in_b && k < n) ? d * hcol[c * ldn + k] : 0.0;
+    if (k < ldT) rww[c * ldT + k] = (in_b && J && k < nW) ? d * J[(int64_t)wrow[k] * ldn + j] : 0.0;
+}
+__global__ __launch_bounds__(256) void k_kkts_var_col(AsmBt abt, const int* __restrict__ vars, const double* __restrict__ delta, const double* __restrict__ mask, const int* __restrict__ cptr, const int* __restrict__ row, const int* __restrict__ pos, const double* __restrict__ val, const int* __restrict__ wpos, double* __restrict__ rww, int64_t ldT) {
+#pragma clang fp contract(off)
+    ASM_BARGS(abt, vars, delta, mask, cptr, row, pos, val, wpos, rww, ldT);
+    const int64_t c = blockIdx.y;
+    const int j = vars[c];
+    if (mask[j] != 0.0) return;
+    const double d = delta ? delta[c] : 1.0;
+    for (int k = cptr[j] + (int)threadIdx.x; k < cptr[j + 1]; k += 256) {
+        const int p = wpos[row[k]];
+        if (p >= 0) rww[c * ldT + p] = d * val[pos[k]];
+    }
+}
+__global__ __launch_bounds__(256) void k_kktm_var_dx(AsmBt abt, const int* __restrict__ vars, const double* __restrict__ delta, const double* __restrict__ mask, int cols, double* __restrict__ dx, int64_t ldn) {
+    ASM_BARGS(abt, vars, delta, mask, cols, dx, ldn);
+    const int64_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    const int64_t j = vars[c];
+    if (mask[j] == 0.0) dx[c * ldn + j] = delta ? delta[c] : 1.0;
+}
+// ---- The weights on the bound multipliers of the adjoint entries (asm_solution_adjoint_z*): gzb[c, j] = gz[c, j] on B, 0.0 on F and beyond
+// n - z exists on B only - and, by the workgroups of column 0, the complementary mask cmask[j] = 1.0 on B, 0.0 elsewhere
+__global__ __launch_bounds__(256) void k_kktm_gz_mask(AsmBt abt, const double* __restrict__ gz, const double* __restrict__ mask, int64_t n, int64_t ldn, double* __restrict__ gzb, double* __restrict__ cmask) {
+    ASM_BARGS(abt, gz, mask, n, ldn, gzb, cmask);
+    const int64_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= ldn) return;
+    const bool b = j < n && mask[j] == 0.0;
+    gzb[c * ldn + j] = b ? gz[c * ldn + j] : 0.0;
+    if (c == 0) cmask[j] = b ? 1.0 : 0.0;
+}
 // p[c] = -g[c] + beta_c p[c] for the active columns
 __global__ __launch_bounds__(256) void k_kktm_cg_p(AsmBt abt, const double* __restrict__ scal, const double* __restrict__ g, double* __restrict__ p, int64_t len, int64_t ldv) {
     ASM_BARGS(abt, scal, g, p, len, ldv);

@@ -28,7 +28,16 @@ transposed cross derivative with the weights (-ax, al); d phi / d(bound_i) = -al
     adjoint_reference    the dense kkt_reference plus that twin: the independent answer
     solution_adjoint     the device call on a handle (asm_solution_adjoint), or on a fresh one for a Model
 
-For the scenarios of a HipBatch: batch.working_sets, batch.solution_jacobians, batch.bound_jacobians.
+Variable bounds and the bound multipliers z: the bounds of variables in B move by delta (supported on B), so dx_B = delta; (dx_F, dlam, dz)
+is the solve with ru = H delta, rw = J delta, then dx += delta.  In reverse, phi(x*, lam*, z*) with a gradient gz on B: the adjoint solve
+takes gx + H gz and gl - J gz, the transposed sweep vx = gz - ax, and d phi / d(xbound_j) = -dz_j of the adjoint solve on B.
+
+    var_bound_rhs        the right-hand sides of variable-bound sensitivities: what asm_var_bound_sensitivity_multi makes on the device
+    var_bound_reference  the dense system with dx_B = delta imposed directly: the independent answer
+    var_bound_jacobian   dx*, dlam*, dz* / d(xbound) for a list of variables at a bound (asm_var_bound_sensitivity_multi)
+    adjoint_reference_z  adjoint_reference with weights on z and the gradient with respect to the variable bounds
+
+For the scenarios of a HipBatch: batch.working_sets, batch.solution_jacobians, batch.bound_jacobians, batch.var_bound_jacobians.
 """
 import numpy as np
 
@@ -304,6 +313,75 @@ def bound_rhs(m, n, rows, delta=None):
     return RU, RW
 
 
+def _vars_delta(n, vars, delta):
+    vars = np.atleast_1d(np.asarray(vars, np.int64))
+    if vars.ndim != 1 or np.any(vars < 0) or np.any(vars >= n):
+        raise ValueError("vars must be a list of variables in [0, %d)" % n)
+    d = np.ones(len(vars)) if delta is None else np.atleast_1d(np.asarray(delta, float))
+    if d.shape != vars.shape:
+        raise ValueError("delta has shape %r, expected %r" % (d.shape, vars.shape))
+    return vars, d
+
+
+def var_bound_rhs(H, J, n, m, bound_state, vars, delta=None):
+    """(RU [k x n], RW [k x m], D [k x n]) of the variable-bound sensitivities of the variables `vars` (0-based, duplicates allowed) for
+    the Hessian H [n x n] and Jacobian J [m x n]: D[c] = delta[c] e_j (delta None: 1), RU[c] = delta[c] H[:, j], RW[c] = delta[c] J[:, j] -
+    what asm_var_bound_sensitivity_multi makes on the device (RW restricted there to the working rows).  The column's answer is the
+    solve of (RU[c], RW[c]) plus D[c] on dx.  A variable outside B (bound_state[j] == 0) leaves all three rows zero."""
+    vars, d = _vars_delta(n, vars, delta)
+    H, J, bs = np.asarray(H, float), np.asarray(J, float).reshape(m, n), np.asarray(bound_state)
+    RU, RW, D = np.zeros((len(vars), n)), np.zeros((len(vars), m)), np.zeros((len(vars), n))
+    for c, j in enumerate(vars):
+        if bs[j] == 0:
+            continue
+        RU[c], RW[c], D[c, j] = d[c] * H[:, j], d[c] * J[:, j], d[c]
+    return RU, RW, D
+
+
+def var_bound_reference(fm, x, lam, row_state, bound_state, vars, delta=None):
+    """(DX [k x n], DLAM [k x m], DZ [k x n]): the sensitivities to a move of the bounds the variables `vars` sit at, with dx_B = delta
+    imposed directly on the dense system - H_FF dx_F - A' dlam = -H_FB delta_B, A dx_F = -J[W, B] delta_B, then
+    dz = H[B, :] dx - J[W, B]' dlam - and numpy.linalg.solve: the independent answer (it does not go through the right-hand sides of
+    var_bound_rhs).  A variable outside B gives the zero column."""
+    vars, d = _vars_delta(fm.n, vars, delta)
+    F, W, _, _ = _sets(fm, row_state, bound_state, np.zeros(fm.n), np.zeros(fm.m))
+    B = np.nonzero(np.asarray(bound_state) != 0)[0]
+    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    A = J[np.ix_(W, F)]
+    nF, nW, K = len(F), len(W), len(vars)
+    M = np.zeros((nF + nW, nF + nW))
+    M[:nF, :nF] = H[np.ix_(F, F)]
+    M[:nF, nF:] = -A.T
+    M[nF:, :nF] = A
+    DX, DLAM, DZ = np.zeros((K, fm.n)), np.zeros((K, fm.m)), np.zeros((K, fm.n))
+    for c, j in enumerate(vars):
+        if bound_state[j] == 0:
+            continue
+        dB = np.zeros(fm.n)
+        dB[j] = d[c]
+        sol = np.linalg.solve(M, np.concatenate([-(H[np.ix_(F, B)] @ dB[B]), -(J[np.ix_(W, B)] @ dB[B])])) if nF + nW else np.zeros(0)
+        dx = dB.copy()
+        dx[F] = sol[:nF]
+        DX[c], DLAM[c, W] = dx, sol[nF:]
+        DZ[c, B] = H[B] @ dx - J[np.ix_(W, B)].T @ sol[nF:]
+    return DX, DLAM, DZ
+
+
+def var_bound_jacobian(opt, fm, x, lam, row_state, bound_state, vars, max_iter=None, rtol=None):
+    """(dx*/d(xbound) [n x k], dlam*/d(xbound) [m x k], dz*/d(xbound) [n x k]) for the variables `vars` (0-based) at a bound: column q
+    answers a unit move of the bound variable vars[q] sits at, all from one asm_var_bound_sensitivity_multi call on `opt`.  A column
+    whose status is not 0 raises RuntimeError."""
+    vars = np.atleast_1d(np.asarray(vars, np.int64))
+    bs = np.asarray(bound_state)
+    if vars.ndim != 1 or np.any(vars < 0) or np.any(vars >= fm.n) or np.any(bs[vars] == 0):
+        raise ValueError("vars must be variables at a bound (bound_state -1 or +1)")
+    if not len(vars):
+        return np.zeros((fm.n, 0)), np.zeros((fm.m, 0)), np.zeros((fm.n, 0))
+    DX, DLAM, DZ, infos = opt.var_bound_sensitivity_multi(x, lam, row_state, bound_state, vars, None, max_iter, rtol)
+    dx, dlam = _jacobian_columns(DX, DLAM, infos)
+    return dx, dlam, DZ.T.copy()
+
+
 def solution_sensitivity(model_or_opt, fm, x, lam, row_state, bound_state, dc, max_iter=None, rtol=None):
     """(dx, dlam, dz, info) of asm_solution_sensitivity for the FunctionModel `fm` (expression blocks and the block kernels with derivatives, with
     its data) at the solution
@@ -341,6 +419,19 @@ def adjoint_reference(fm, x, lam, row_state, bound_state, gx, gl):
     ax, al, _ = kkt_reference(fm, x, lam, row_state, bound_state, -gx, gl)
     dbound = np.where(np.asarray(row_state) == 1, -al, 0.0)
     return model_cross_t(fm, x, lam, -ax, al), dbound, ax, al
+
+
+def adjoint_reference_z(fm, x, lam, row_state, bound_state, gx, gl, gz):
+    """(out [n_dpar], dbound [m], dxbound [n], ax [n], al [m]) for a function phi(x*, lam*, z*) with gradients gx, gl, gz (gz counts on B
+    only): with gx~ = gx + H gz and gl~ = gl - J gz the adjoint state (ax, al, dz) = kkt_reference(ru = -gx~, rw = gl~),
+    out = model_cross_t(vx = gz - ax, vl = al), dbound = -al on the working rows, dxbound = -dz on B; 0 elsewhere."""
+    gx, gl = np.asarray(gx, float), np.asarray(gl, float)
+    on_b = np.asarray(bound_state) != 0
+    gzb = np.where(on_b, np.asarray(gz, float), 0.0)
+    H, J = lagrangian_hessian(fm, x, lam), dense_jacobian(fm, x)
+    ax, al, dz = kkt_reference(fm, x, lam, row_state, bound_state, -(gx + H @ gzb), gl - J @ gzb)
+    dbound = np.where(np.asarray(row_state) == 1, -al, 0.0)
+    return model_cross_t(fm, x, lam, gzb - ax, al), dbound, np.where(on_b, -dz, 0.0), ax, al
 
 
 def solution_adjoint(model_or_opt, fm, x, lam, row_state, bound_state, gx, gl, max_iter=None, rtol=None):

@@ -430,6 +430,27 @@ class HipSubOptimizer:
                                                           None if delta is None else _lib.dptr(delta), par, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return DX, DLAM[:, :self.m], DZ, list(infos)
 
+    def var_bound_sensitivity_multi(self, x, lam, row_state, bound_state, vars, delta=None, max_iter=None, rtol=None):
+        """(DX, DLAM, DZ, infos) of asm_var_bound_sensitivity_multi: column c moves the bound that variable vars[c] sits at by delta[c]
+        (delta None: 1) - kkt_solve_multi with ru = delta H[:, j], rw = delta J[:, j], bit for bit, and DX[c, j] = delta[c] - with the
+        right-hand sides made on the device (sensitivity.var_bound_rhs states them).  vars: 0-based variables, duplicates allowed; a
+        variable outside B gives the zero column.  vars None goes to the library as a null pointer (refused)."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_params(max_iter, rtol)
+        if vars is not None:
+            vars = np.ascontiguousarray(np.atleast_1d(vars), dtype=np.int32)
+            if vars.ndim != 1 or len(vars) < 1:
+                raise ValueError("vars has shape %r, expected (nrhs,) with at least one variable" % (vars.shape,))
+        nrhs = 1 if vars is None else len(vars)
+        if delta is not None:
+            delta = self._vec(delta, nrhs, "delta")
+        rs, bs = self._states(row_state, bound_state)
+        DX, DLAM, DZ, infos = self._multi_outputs(nrhs)
+        self._check(self._lib.asm_var_bound_sensitivity_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs,
+                                                              None if vars is None else _lib.i32ptr(vars), None if delta is None else _lib.dptr(delta), par,
+                                                              _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
+        return DX, DLAM[:, :self.m], DZ, list(infos)
+
     # ------------------------------------------------------------------ adjoint sensitivities (include/asm_hip.h: "Adjoint solution sensitivities")
     def data_cross_t(self, x, lam, vx, vl):
         """out [n_dpar] of asm_eval_data_cross_t: out[c] = vx' d/d dpar[c] (grad_x (f - lam' g)) + vl' d g / d dpar[c] for weights vx [n],
@@ -470,6 +491,41 @@ class HipSubOptimizer:
         self._check(self._lib.asm_solution_adjoint_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(GX), _lib.dptr(GL),
                                                          par, _lib.dptr(OUT), _lib.dptr(DBOUND), _lib.dptr(AX), _lib.dptr(AL), infos))
         return OUT[:, :nd], DBOUND[:, :self.m], AX, AL[:, :self.m], list(infos)
+
+    def solution_adjoint_z(self, x, lam, row_state, bound_state, gx, gl, gz=None, max_iter=None, rtol=None):
+        """(out, dbound, dxbound, ax, al, info) of asm_solution_adjoint_z for a function phi(x*, lam*, z*) with gradients gx [n], gl [m] and
+        gz [n] (None: 0; entries on free variables are ignored - z exists on B only): solution_adjoint's outputs and
+        dxbound [n] = d phi / d(bound variable j sits at), 0 on F.  gz None: solution_adjoint's bits."""
+        nd = getattr(self, "_ev_nd", 0)
+        x, lam, gx, gl = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam"), self._vec(gx, self.n, "gx"), self._vec(gl, self.m, "gl")
+        if gz is not None:
+            gz = self._vec(gz, self.n, "gz")
+        rs, bs = self._states(row_state, bound_state)
+        out, dbound, ax, al, info = np.empty(max(nd, 1)), np.empty(max(self.m, 1)), np.empty(self.n), np.empty(max(self.m, 1)), _lib.KktInfo()
+        dxbound = np.empty(self.n)
+        self._check(self._lib.asm_solution_adjoint_z(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), _lib.dptr(gx), _lib.dptr(gl),
+                                                     None if gz is None else _lib.dptr(gz), self._kkt_params(max_iter, rtol), _lib.dptr(out), _lib.dptr(dbound),
+                                                     _lib.dptr(dxbound), _lib.dptr(ax), _lib.dptr(al), C.byref(info)))
+        return out[:nd], dbound[:self.m], dxbound, ax, al[:self.m], info
+
+    def solution_adjoint_z_multi(self, x, lam, row_state, bound_state, GX, GL, GZ=None, max_iter=None, rtol=None):
+        """(OUT, DBOUND, DXBOUND, AX, AL, infos) of asm_solution_adjoint_z_multi: solution_adjoint_z for the nrhs functions whose gradients
+        are the rows of GX [nrhs x n], GL [nrhs x m] and GZ [nrhs x n] (None: 0), on one factor."""
+        nd = getattr(self, "_ev_nd", 0)
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        par = self._kkt_params(max_iter, rtol)
+        GX = self._mat(GX, self.n, "GX")
+        GL = self._mat(GL, self.m, "GL", GX.shape[0])
+        if GZ is not None:
+            GZ = self._mat(GZ, self.n, "GZ", GX.shape[0])
+        rs, bs = self._states(row_state, bound_state)
+        nrhs = GX.shape[0]
+        OUT, DBOUND, AL = np.empty((nrhs, max(nd, 1))), np.empty((nrhs, max(self.m, 1))), np.empty((nrhs, max(self.m, 1)))
+        AX, DXBOUND, infos = np.empty((nrhs, self.n)), np.empty((nrhs, self.n)), (_lib.KktInfo * nrhs)()
+        self._check(self._lib.asm_solution_adjoint_z_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(GX), _lib.dptr(GL),
+                                                           None if GZ is None else _lib.dptr(GZ), par, _lib.dptr(OUT), _lib.dptr(DBOUND), _lib.dptr(DXBOUND),
+                                                           _lib.dptr(AX), _lib.dptr(AL), infos))
+        return OUT[:, :nd], DBOUND[:, :self.m], DXBOUND, AX, AL[:, :self.m], list(infos)
 
     @staticmethod
     def _kkt_step_params(max_iter, rtol, normal_share):

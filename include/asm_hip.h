@@ -481,7 +481,19 @@ int asm_solution_sensitivity(asm_handle* h, const double* x, const double* lambd
  * or rows == NULL, is ASM_ERR_ARG.  A row outside the working set gives the zero column: status 0, no iteration, exact zeros.  A chunk's
  * right-hand sides are made on the device (k_kktm_bound_rhs: every entry cleared, and the thread whose place in the working-row list
  * holds rows[c] stores -delta[c]) from one upload of 12 bytes per column - nothing of length n or m is staged.  A derivative entry like
- * asm_solution_sensitivity_multi: the exact Hessian whatever asm_hessian_set_type chose, and that entry's refusals. */
+ * asm_solution_sensitivity_multi: the exact Hessian whatever asm_hessian_set_type chose, and that entry's refusals.
+ * Variable-bound sensitivities: the bounds of variables in B move by delta, a vector supported on B, so dx_B = delta.  (dx_F, dlam, dz) is
+ * the solve with ru = H delta over all n entries and rw = J delta on W, then dx += delta; the solve's own dz is already right (ru on B
+ * carries H_BB delta).  asm_var_bound_sensitivity_multi is that recipe without the matrices: column c moves the bound of variable vars[c]
+ * by delta[c] (delta == NULL: 1.0) and equals asm_kkt_solve_multi with RU[c] = delta[c] H[:, j], RW[c] = delta[c] J[:, j] bit for bit in
+ * DLAM, DZ, info and DX, except that DX[c, j] = delta[c].  vars: nrhs 0-based variable indices, duplicates allowed; an index outside
+ * [0, n), or vars == NULL, is ASM_ERR_ARG.  A variable outside B (bound_state[j] == 0) gives the zero column: status 0, no iteration,
+ * exact zeros.  A chunk's right-hand sides are made on the device from one upload of 12 bytes per column - nothing of length n or m is
+ * staged: k_kktm_var_unit writes the unit block, the chunk's Hessian product (the kernel of the solve's own products, its summation
+ * order) gives H[:, j], k_kktm_var_rhs multiplies by delta[c] - one multiplication, no fused multiply-add - and reads J[wrow[q], j] from
+ * the matrix the form itself uses: the solve's dense J, or (sparse form, k_kkts_var_col) the CSR values through the pattern's CSC column j
+ * and the position list, rows outside W skipped, in both row orders.  After the finish step k_kktm_var_dx stores dx[j] = delta[c].  A
+ * derivative entry with the refusals of asm_bound_sensitivity_multi; the function store alone (nlp_kind 0) is served. */
 #define ASM_KKT_CHUNK 64
 int asm_kkt_solve_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                         int32_t nrhs, const double* RU, const double* RW, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ,
@@ -492,6 +504,9 @@ int asm_solution_sensitivity_multi(asm_handle* h, const double* x, const double*
 int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                                 int32_t nrhs, const int32_t* rows, const double* delta /* [nrhs], or NULL: 1.0 */, const asm_kkt_params* par,
                                 double* DX, double* DLAM, double* DZ, asm_kkt_info* info);
+int asm_var_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state,
+                                    const int32_t* bound_state, int32_t nrhs, const int32_t* vars, const double* delta /* [nrhs], or NULL: 1.0 */,
+                                    const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info);
 
 /* ---- Adjoint solution sensitivities: the gradient of one function of the solution with respect to all data, from one KKT solve.
  * The forward entries answer "how do x* and lambda* move along one direction dc of the data" at one KKT right-hand side per direction.  The
@@ -501,7 +516,7 @@ int asm_bound_sensitivity_multi(asm_handle* h, const double* x, const double* la
  *   1. adjoint state: (ax, al) = asm_kkt_solve(ru = -gx, rw = gl), no dz; ax is zero on B and al outside W, as that solve guarantees.
  *   2. d phi / d dpar = asm_eval_data_cross_t(vx = -ax, vl = al), the transposed cross derivative below.
  *   3. d phi / d bound_i = -al_i for a working row i, 0.0 for every other row: the recipe "ru = 0, rw_i = -delta" read backwards.
- * Weights on the bound multipliers z and derivatives with respect to variable bounds are not part of these entries.
+ * Weights on the bound multipliers z and derivatives with respect to variable bounds: asm_solution_adjoint_z below.
  * Transposed cross derivatives.  asm_eval_data_cross_t: for weights vx [n], vl [m] at (x, lambda),
  *   out[c] = vx' d/d dpar[c] (grad_x L) + vl' d g / d dpar[c] = d/d dpar[c] [ D_vx L(x, lambda; dpar) + vl' g(x; dpar) ],   c < n_dpar,
  * L = f - lambda' g and D_vx the directional derivative along vx in x.  Rows of the function store contribute nothing.  For every dc,
@@ -549,6 +564,25 @@ int asm_solution_adjoint(asm_handle* h, const double* x, const double* lambda, c
 int asm_solution_adjoint_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
                                int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par, double* OUT /* nrhs x n_dpar */,
                                double* DBOUND, double* AX, double* AL, asm_kkt_info* info);
+/* The adjoint entries with weights on the bound multipliers and gradients with respect to variable bounds: phi(x*, lambda*, z*) has the
+ * gradients gx [n], gl [m] and gz [n].  z exists on B only: entries of gz on F are ignored, they are treated as 0.0.  With
+ * gx~ = gx + H gz and gl~ = gl - J gz the adjoint state is (ax, al, dz) = asm_kkt_solve(ru = -gx~, rw = gl~) with dz on, and
+ *   d phi / d dpar     = asm_eval_data_cross_t(vx = gz - ax, vl = al)   (the supports of gz and ax are disjoint)
+ *   d phi / d bound_i  = -al_i on W, 0.0 elsewhere
+ *   d phi / d xbound_j = -dz_j on B, 0.0 on F: dxbound [n], may be NULL - the derivative with respect to the bound that variable j sits at.
+ * gx~ and gl~ are made on the device: the chunk's gz goes up, k_kktm_gz_mask clears it on F, one Hessian product on the block gives H gz
+ * and one product with J[W, B] - the columns that the solve's own products mask out - gives J gz on the working rows (dense form: the
+ * working rows gathered with the complementary mask feeding k_gemm_nt, or k_gemv_n for one column; sparse form: k_kkts_mul_a with the
+ * complementary mask).  gz == NULL: out, dbound, ax, al and info equal asm_solution_adjoint(_multi) bit for bit - the preparation is
+ * skipped, not run with zeros - and dxbound is still returned.  Kinds, refusals, par, info, column independence and the function store
+ * alone (nlp_kind 0: out empty) are as for asm_solution_adjoint(_multi); GZ nrhs x n, DXBOUND nrhs x n (both may be NULL). */
+int asm_solution_adjoint_z(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                           const double* gx, const double* gl, const double* gz /* [n], may be NULL = 0 */, const asm_kkt_params* par,
+                           double* out /* [n_dpar] */, double* dbound /* [m], may be NULL */, double* dxbound /* [n], may be NULL */,
+                           double* ax /* [n], may be NULL */, double* al /* [m], may be NULL */, asm_kkt_info* info);
+int asm_solution_adjoint_z_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state,
+                                 int32_t nrhs, const double* GX, const double* GL, const double* GZ, const asm_kkt_params* par,
+                                 double* OUT /* nrhs x n_dpar */, double* DBOUND, double* DXBOUND, double* AX, double* AL, asm_kkt_info* info);
 
 /* ---- Trust-region step on the working set: Byrd-Omojokun with Steihaug-Toint truncation.
  * asm_kkt_step is asm_kkt_solve with an l2 radius: it minimises the model ru'dx + 1/2 dx'H dx over A dx_F = -theta rw_W, dx_B = 0,
@@ -969,6 +1003,20 @@ int asm_batch_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, c
 int asm_batch_solution_adjoint(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
                                const int32_t* bound_state, int32_t nrhs, const double* GX, const double* GL, const asm_kkt_params* par,
                                double* OUT, double* DBOUND, double* AX, double* AL, asm_kkt_info* info);
+/* asm_var_bound_sensitivity_multi with a leading scenario dimension, as asm_batch_bound_sensitivity: vars and delta are shared by the
+ * scenarios, an index outside [0, n) is ASM_ERR_ARG, and scenario s is bit-identical to the per-handle entry on a fresh handle with that
+ * scenario's data (dense form, and sparse form in the static order).
+ * asm_solution_adjoint_z_multi with a leading scenario dimension, as asm_batch_solution_adjoint: GZ, DXBOUND n_scen x nrhs x n (both may
+ * be NULL); what the weights need on a slot - the complementary mask and, dense form, J[W, B] (min(m, n) ldn doubles) - is made before
+ * the fibers start. */
+int asm_batch_var_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                                    const int32_t* bound_state, int32_t nrhs, const int32_t* vars /* [nrhs], shared */,
+                                    const double* delta /* [nrhs] or NULL: 1.0, shared */, const asm_kkt_params* par, double* DX, double* DLAM,
+                                    double* DZ, asm_kkt_info* info);
+int asm_batch_solution_adjoint_z(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state,
+                                 const int32_t* bound_state, int32_t nrhs, const double* GX, const double* GL, const double* GZ,
+                                 const asm_kkt_params* par, double* OUT, double* DBOUND, double* DXBOUND, double* AX, double* AL,
+                                 asm_kkt_info* info);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
