@@ -212,6 +212,25 @@ __device__ __noinline__ double expr_libm(int32_t op, double u, double y) {
         default: return atan2(u, y);      // ASM_OP_ATAN2
     }
 }
+// ATAN2's adjoints (w y) / t and (w u) / t, t = u u + y y, with u and y scaled by a power of two s first: us = u s and ys = y s have their
+// larger magnitude in [1/2, 1), so ts = us us + ys ys neither underflows nor overflows where the quotients are representable (at
+// (1e-200, 1e-200) u u is 0 and the plain form returns inf for 5e199).  A power of two scales exactly: q(w, ys) = ((w ys) / ts) s has the bits
+// of (w y) / t wherever that form neither underflows nor overflows.  The exponent is kept within +-1000 so that s itself is a normal number.
+struct ExprAtan2 {
+    double s, us, ys, ts;
+    __device__ __forceinline__ ExprAtan2(double u, double y) {
+#pragma clang fp contract(off)
+        int e;
+        (void)frexp(fmax(fabs(u), fabs(y)), &e);
+        s = ldexp(1.0, e < -1000 ? 1000 : (e > 1000 ? -1000 : -e));
+        us = u * s; ys = y * s;
+        ts = us * us + ys * ys;
+    }
+    __device__ __forceinline__ double q(double w, double vs) const {
+#pragma clang fp contract(off)
+        return ((w * vs) / ts) * s;
+    }
+};
 // forward sweep over nodes [k0, k1) at x: every node value into val (absolute indices), returns the last one
 __device__ __forceinline__ double expr_forward(const ExprTape& X, int64_t k0, int64_t k1, const double* __restrict__ x, double* val) {
 #pragma clang fp contract(off)
@@ -278,8 +297,8 @@ __device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int6
             case ASM_OP_COS: adj[a] = adj[a] - w * sin(val[a]); break;
             case ASM_OP_ABS: adj[a] = adj[a] + w * copysign(1.0, val[a]); break;
             case ASM_OP_TAN: { const double v = val[k]; adj[a] = adj[a] + w * (1.0 + v * v); break; }
-            case ASM_OP_ASIN: { const double u = val[a]; adj[a] = adj[a] + w / sqrt(1.0 - u * u); break; }
-            case ASM_OP_ACOS: { const double u = val[a]; adj[a] = adj[a] - w / sqrt(1.0 - u * u); break; }
+            case ASM_OP_ASIN: { const double u = val[a]; adj[a] = adj[a] + w / sqrt((1.0 - u) * (1.0 + u)); break; }
+            case ASM_OP_ACOS: { const double u = val[a]; adj[a] = adj[a] - w / sqrt((1.0 - u) * (1.0 + u)); break; }
             case ASM_OP_ATAN: { const double u = val[a]; adj[a] = adj[a] + w / (1.0 + u * u); break; }
             case ASM_OP_SINH: adj[a] = adj[a] + w * expr_libm(ASM_OP_COSH, val[a], 0.0); break;
             case ASM_OP_COSH: adj[a] = adj[a] + w * expr_libm(ASM_OP_SINH, val[a], 0.0); break;
@@ -296,9 +315,9 @@ __device__ __forceinline__ void expr_reverse(const ExprTape& X, int64_t k0, int6
                 break;
             }
             case ASM_OP_ATAN2: {
-                const double u = val[a], y = val[b], t = u * u + y * y;
-                adj[a] = adj[a] + (w * y) / t;
-                adj[b] = adj[b] - (w * u) / t;
+                const ExprAtan2 S(val[a], val[b]);
+                adj[a] = adj[a] + S.q(w, S.ys);
+                adj[b] = adj[b] - S.q(w, S.us);
                 break;
             }
             case ASM_OP_MIN: { const int64_t c = val[b] < val[a] ? b : a; adj[c] = adj[c] + w; break; }
@@ -472,8 +491,8 @@ __device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int
                     v = expr_libm(op, u, y);
                     switch (op) {
                         case ASM_OP_TAN: d = du * (1.0 + v * v); break;
-                        case ASM_OP_ASIN: d = du / sqrt(1.0 - u * u); break;
-                        case ASM_OP_ACOS: d = -(du / sqrt(1.0 - u * u)); break;
+                        case ASM_OP_ASIN: d = du / sqrt((1.0 - u) * (1.0 + u)); break;
+                        case ASM_OP_ACOS: d = -(du / sqrt((1.0 - u) * (1.0 + u))); break;
                         case ASM_OP_ATAN: d = du / (1.0 + u * u); break;
                         case ASM_OP_SINH: d = du * expr_libm(ASM_OP_COSH, u, 0.0); break;
                         case ASM_OP_COSH: d = du * expr_libm(ASM_OP_SINH, u, 0.0); break;
@@ -485,9 +504,12 @@ __device__ __forceinline__ void expr_forward2(const ExprTape& X, int64_t k0, int
                         case ASM_OP_CBRT: d = du / (3.0 * (v * v)); break;
                         case ASM_OP_POW:
                             d = du * (y * expr_libm(ASM_OP_POW, u, y - 1.0));
-                            if (X.op[b] != ASM_OP_CONST) d = d + dy * (v * expr_libm2(ASM_OP_LOG, u));
+                            // a CONST exponent has a tangent in EXPR2_DATA alone (dc[a]); its term enters only where that is nonzero, so
+                            // that pow(u, 2.0) at u <= 0 stays finite along every direction that leaves the exponent alone
+                            if constexpr (DATA == EXPR2_DATA) { if (X.op[b] != ASM_OP_CONST || dy != 0.0) d = d + dy * (v * expr_libm2(ASM_OP_LOG, u)); }
+                            else { if (X.op[b] != ASM_OP_CONST) d = d + dy * (v * expr_libm2(ASM_OP_LOG, u)); }
                             break;
-                        default: { const double t = u * u + y * y; d = (du * y) / t - (dy * u) / t; break; }   // ASM_OP_ATAN2
+                        default: { const ExprAtan2 S(u, y); d = S.q(du, S.ys) - S.q(dy, S.us); break; }   // ASM_OP_ATAN2
                     }
             }
         }
@@ -561,7 +583,7 @@ __device__ __forceinline__ void expr_reverse2(const ExprTape& X, int64_t k0, int
             case ASM_OP_ABS: { const double s = copysign(1.0, u); adj[a] = adj[a] + w * s; tadj[a] = tadj[a] + z * s; break; }
             case ASM_OP_TAN: { const double g = 1.0 + v * v; adj[a] = adj[a] + w * g; tadj[a] = tadj[a] + (z * g + w * (2.0 * (v * d))); break; }
             case ASM_OP_ASIN: case ASM_OP_ACOS: {
-                const double r = sqrt(1.0 - u * u), q = w / r, dr = -((u * du) / r), dq = (z - q * dr) / r;
+                const double r = sqrt((1.0 - u) * (1.0 + u)), q = w / r, dr = -((u * du) / r), dq = (z - q * dr) / r;
                 if (op == ASM_OP_ASIN) { adj[a] = adj[a] + q; tadj[a] = tadj[a] + dq; }
                 else { adj[a] = adj[a] - q; tadj[a] = tadj[a] - dq; }
                 break;
@@ -588,24 +610,35 @@ __device__ __forceinline__ void expr_reverse2(const ExprTape& X, int64_t k0, int
             case ASM_OP_CBRT: { const double g = 3.0 * (v * v), q = w / g; adj[a] = adj[a] + q; tadj[a] = tadj[a] + (z - q * (6.0 * (v * d))) / g; break; }
             case ASM_OP_POW: {
                 const double y = val[b], dy = tval[b];
-                const bool bc = X.op[b] == ASM_OP_CONST;         // a CONST exponent: no term with dy, nothing to b
+                // bc: no term with dy; nb: nothing to b.  EXPR2_HESS: a CONST exponent has neither (its tangent is 0 and nobody reads its
+                // adjoint).  EXPR2_DATA: its tangent is dc[a], the terms enter where that is nonzero (a zero direction on pow(u, 2.0) with
+                // u <= 0 stays finite); the CONST node writes nothing.  EXPR2_DATA_T: its tangent is 0 - the terms with dy stay out, so no
+                // 0 * log(u) forms and a's entries stay finite for u < 0 - and it receives adj and tadj: its occurrence is NaN or inf where
+                // log(u) is, as in the first-order data sweep
+                bool bc = X.op[b] == ASM_OP_CONST, nb = bc;
+                if constexpr (DATA == EXPR2_DATA) { bc = bc && dy == 0.0; nb = bc; }
+                else if constexpr (DATA == EXPR2_DATA_T) nb = false;
                 const double p1 = expr_libm(ASM_OP_POW, u, y - 1.0), p2 = expr_libm(ASM_OP_POW, u, y - 2.0), A = y * p1;
                 double dp1 = du * ((y - 1.0) * p2), lu = 0.0;
-                if (!bc) { lu = expr_libm2(ASM_OP_LOG, u); dp1 = dp1 + dy * (p1 * lu); }
+                if (!nb) lu = expr_libm2(ASM_OP_LOG, u);
+                if (!bc) dp1 = dp1 + dy * (p1 * lu);
                 double dA = y * dp1;
                 if (!bc) dA = dA + dy * p1;
                 adj[a] = adj[a] + w * A; tadj[a] = tadj[a] + (z * A + w * dA);
-                if (!bc) {
+                if (!nb) {
                     const double B = v * lu, dB = d * lu + v * (du / u);
                     adj[b] = adj[b] + w * B; tadj[b] = tadj[b] + (z * B + w * dB);
                 }
                 break;
             }
             case ASM_OP_ATAN2: {
-                const double y = val[b], dy = tval[b], t = u * u + y * y, dt = 2.0 * (u * du) + 2.0 * (y * dy);
-                const double qa = (w * y) / t, qb = (w * u) / t;
-                adj[a] = adj[a] + qa; tadj[a] = tadj[a] + ((z * y + w * dy) - qa * dt) / t;
-                adj[b] = adj[b] - qb; tadj[b] = tadj[b] - ((z * u + w * du) - qb * dt) / t;
+                // the statements of the header with numerator and t scaled by s and s s (ExprAtan2): the same bits where nothing underflows
+                const double y = val[b], dy = tval[b];
+                const ExprAtan2 S(u, y);
+                const double dts = 2.0 * (S.us * du) + 2.0 * (S.ys * dy);
+                const double qa = S.q(w, S.ys), qb = S.q(w, S.us);
+                adj[a] = adj[a] + qa; tadj[a] = tadj[a] + (((z * S.ys + (w * dy) * S.s) - qa * dts) / S.ts) * S.s;
+                adj[b] = adj[b] - qb; tadj[b] = tadj[b] - (((z * S.us + (w * du) * S.s) - qb * dts) / S.ts) * S.s;
                 break;
             }
             case ASM_OP_MIN: { const int64_t c = val[b] < u ? b : a; adj[c] = adj[c] + w; tadj[c] = tadj[c] + z; break; }
@@ -852,7 +885,7 @@ __global__ __launch_bounds__(256) void k_nlp_dense_cross_u(AsmBt abt, const doub
 // ---- transposed cross derivatives (asm_eval_data_cross_t; include/asm_hip.h, "Transposed cross derivatives"): for weights vx [n] and vl (the
 // block's rows), out[c] = d/d dpar[c] [ D_vx L + vl' g ] - for every direction dc, dc' out = vx' u + vl' w with (u, w) of asm_eval_data_cross.
 // Expression block: the sweep of k_nlp_expr_cross with the other seed - a VAR node of variable j has the tangent vx[j], a CONST node 0 (a
-// CONST exponent of POW stays out, as there).  One thread per row (t < R) or term, its node arrays as in k_nlp_expr_cross; in the reverse pass
+// CONST exponent of POW is a CONST node like any other: it receives its adjoint and adjoint tangent).  One thread per row (t < R) or term, its node arrays as in k_nlp_expr_cross; in the reverse pass
 // every CONST node yields one occurrence into the cocc list of k_nlp_expr_const_adj (same slot, same cptr grouping): for a node of row t
 // (-lam[t]) * tadj + vl[t] * adj - two products, one sum - and for a node of a term scale * tadj.  k_nlp_expr_data_gather sums per dpar index.
 __global__ __launch_bounds__(256) void k_nlp_expr_cross_t(AsmBt abt, ExprTape X, ExprCross C, const double* __restrict__ x, const double* __restrict__ vx, const double* __restrict__ lam, const double* __restrict__ vl, double scale, double* __restrict__ cocc) {

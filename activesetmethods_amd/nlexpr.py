@@ -249,6 +249,15 @@ def _powi(u, e):
     return 1.0 / pk, float(e) / (pk * u)
 
 
+def _atan2_scaled(u, y):
+    """(s, us, ys, ts) of ExprAtan2 (asm_eval_kernels.hip.h): u and y scaled by the power of two s that puts the larger magnitude in
+    [1/2, 1), ts = us us + ys ys; ((w ys) / ts) s is (w y) / (u u + y y) without the underflow or overflow of the squares."""
+    e = np.frexp(np.fmax(np.abs(u), np.abs(y)))[1]
+    s = np.ldexp(1.0, np.where(e < -1000, 1000, np.where(e > 1000, -1000, -e)))
+    us, ys = u * s, y * s
+    return s, us, ys, us * us + ys * ys
+
+
 _NP_UNARY = {ABS: np.abs, TAN: np.tan, ASIN: np.arcsin, ACOS: np.arccos, ATAN: np.arctan, SINH: np.sinh, COSH: np.cosh,
              TANH: np.tanh, LOG10: np.log10, LOG2: np.log2, LOG1P: np.log1p, EXPM1: np.expm1, CBRT: np.cbrt}
 
@@ -382,10 +391,10 @@ class _Sweep:
                         W[r, a] = W[r, a] + w * (1.0 + v * v)
                     elif o == ASIN:
                         u = V[r, a]
-                        W[r, a] = W[r, a] + w / np.sqrt(1.0 - u * u)
+                        W[r, a] = W[r, a] + w / np.sqrt((1.0 - u) * (1.0 + u))
                     elif o == ACOS:
                         u = V[r, a]
-                        W[r, a] = W[r, a] - w / np.sqrt(1.0 - u * u)
+                        W[r, a] = W[r, a] - w / np.sqrt((1.0 - u) * (1.0 + u))
                     elif o == ATAN:
                         u = V[r, a]
                         W[r, a] = W[r, a] + w / (1.0 + u * u)
@@ -412,10 +421,9 @@ class _Sweep:
                         W[r, a] = W[r, a] + w * (y * np.power(u, y - 1.0))
                         W[r, b] = W[r, b] + w * (V[r, k] * np.log(u))
                     elif o == ATAN2:
-                        u, y = V[r, a], V[r, b]
-                        t = u * u + y * y
-                        W[r, a] = W[r, a] + (w * y) / t
-                        W[r, b] = W[r, b] - (w * u) / t
+                        s, us, ys, ts = _atan2_scaled(V[r, a], V[r, b])
+                        W[r, a] = W[r, a] + ((w * ys) / ts) * s
+                        W[r, b] = W[r, b] - ((w * us) / ts) * s
                     else:                                 # MIN, MAX: all of w to the chosen operand (ties and NaN: a)
                         u, y = V[r, a], V[r, b]
                         c = np.where(y < u if o == MIN else y > u, b, a)
@@ -542,19 +550,20 @@ class _HessSweep(_Sweep):
                     elif o == POW:
                         v = np.power(u, y)
                         d = du * (y * np.power(u, y - 1.0))
-                        d = np.where(aux, d, d + dy * (v * np.log(u)))
+                        # a CONST exponent has a tangent with `dc` alone; its term enters only where that is nonzero
+                        d = np.where(aux & (dy == 0.0) if dc is not None else aux, d, d + dy * (v * np.log(u)))
                     elif o == ATAN2:
                         v = np.arctan2(u, y)
-                        t = u * u + y * y
-                        d = (du * y) / t - (dy * u) / t
+                        s, us, ys, ts = _atan2_scaled(u, y)
+                        d = ((du * ys) / ts) * s - ((dy * us) / ts) * s
                     else:
                         v = _NP_UNARY[o](u)
                         if o == TAN:
                             d = du * (1.0 + v * v)
                         elif o == ASIN:
-                            d = du / np.sqrt(1.0 - u * u)
+                            d = du / np.sqrt((1.0 - u) * (1.0 + u))
                         elif o == ACOS:
-                            d = -(du / np.sqrt(1.0 - u * u))
+                            d = -(du / np.sqrt((1.0 - u) * (1.0 + u)))
                         elif o == ATAN:
                             d = du / (1.0 + u * u)
                         elif o == SINH:
@@ -655,7 +664,7 @@ class _HessSweep(_Sweep):
                         g = 1.0 + v * v
                         add(a, w * g, z * g + w * (2.0 * (v * d)))
                     elif o == ASIN or o == ACOS:
-                        rt = np.sqrt(1.0 - u * u)
+                        rt = np.sqrt((1.0 - u) * (1.0 + u))
                         q = w / rt
                         dr = -((u * du) / rt)
                         (add if o == ASIN else sub)(a, q, (z - q * dr) / rt)
@@ -689,7 +698,13 @@ class _HessSweep(_Sweep):
                         q = w / g
                         add(a, q, (z - q * (6.0 * (v * d))) / g)
                     elif o == POW:
-                        bc = aux                              # a CONST exponent: no term with dy, nothing to b
+                        # bc: no term with dy; nb: nothing to b (expr_reverse2).  Hessian: a CONST exponent has neither.  EXPR2_DATA: its
+                        # terms enter where its tangent dc[a] is nonzero.  EXPR2_DATA_T: its tangent is 0, and it receives W and Z
+                        bc = nb = aux
+                        if cslot is not None:
+                            nb = np.zeros_like(aux)
+                        elif weight is not None:
+                            bc = nb = aux & (dy == 0.0)
                         p1, p2, lu = np.power(u, y - 1.0), np.power(u, y - 2.0), np.log(u)
                         A = y * p1
                         dp1 = du * ((y - 1.0) * p2)
@@ -699,16 +714,16 @@ class _HessSweep(_Sweep):
                         add(a, w * A, z * A + w * dA)
                         B = v * lu
                         dB = d * lu + v * (du / u)
-                        nb = ~bc
-                        rb, cb = r[nb], b[nb]
-                        W[rb, cb] = W[rb, cb] + (w * B)[nb]
-                        Z[rb, cb] = Z[rb, cb] + (z * B + w * dB)[nb]
+                        tb = ~nb
+                        rb, cb = r[tb], b[tb]
+                        W[rb, cb] = W[rb, cb] + (w * B)[tb]
+                        Z[rb, cb] = Z[rb, cb] + (z * B + w * dB)[tb]
                     elif o == ATAN2:
-                        t = u * u + y * y
-                        dt = 2.0 * (u * du) + 2.0 * (y * dy)
-                        qa, qb = (w * y) / t, (w * u) / t
-                        add(a, qa, ((z * y + w * dy) - qa * dt) / t)
-                        sub(b, qb, ((z * u + w * du) - qb * dt) / t)
+                        s, us, ys, ts = _atan2_scaled(u, y)
+                        dts = 2.0 * (us * du) + 2.0 * (ys * dy)
+                        qa, qb = ((w * ys) / ts) * s, ((w * us) / ts) * s
+                        add(a, qa, (((z * ys + (w * dy) * s) - qa * dts) / ts) * s)
+                        sub(b, qb, (((z * us + (w * du) * s) - qb * dts) / ts) * s)
                     else:                                 # MIN, MAX
                         c = np.where(y < u if o == MIN else y > u, b, a)
                         add(c, w, z)

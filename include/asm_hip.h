@@ -196,19 +196,22 @@ int asm_jac_row_norms(asm_handle* h, double* out_m);
  *   "+=" is adj = adj + (the right side), each parenthesis one rounding, in this order):
  *     ABS    fabs(u)          adj[a] += w * copysign(1.0, u)           (+1 at +0.0, -1 at -0.0)
  *     TAN    tan(u)           adj[a] += w * (1 + v*v)
- *     ASIN   asin(u)          adj[a] += w / sqrt(1 - u*u)
- *     ACOS   acos(u)          adj[a] -= w / sqrt(1 - u*u)
+ *     ASIN   asin(u)          adj[a] += w / sqrt((1 - u) * (1 + u))    (not 1 - u*u: that cancels near +-1; 1 - u is exact for 1/2 <= u <= 2)
+ *     ACOS   acos(u)          adj[a] -= w / sqrt((1 - u) * (1 + u))
  *     ATAN   atan(u)          adj[a] += w / (1 + u*u)
  *     SINH   sinh(u)          adj[a] += w * cosh(u)
  *     COSH   cosh(u)          adj[a] += w * sinh(u)
- *     TANH   tanh(u)          adj[a] += w * (1 - v*v)
+ *     TANH   tanh(u)          adj[a] += w * (1 - v*v)                  (1 - v*v cancels as |v| -> 1: the absolute error is that of v, a few eps - at u = 9, 1.6e7 eps of the result)
  *     LOG10  log10(u)         adj[a] += w / (u * ln10)                  (ln10, ln2: the doubles nearest to ln 10, ln 2)
  *     LOG2   log2(u)          adj[a] += w / (u * ln2)
  *     LOG1P  log1p(u)         adj[a] += w / (1 + u)
- *     EXPM1  expm1(u)         adj[a] += w * (v + 1)
+ *     EXPM1  expm1(u)         adj[a] += w * (v + 1)                    (v + 1 cancels as v -> -1: absolute error a few eps - at u = -20, 9e7 eps of the result)
  *     CBRT   cbrt(u)          adj[a] += w / (3 * (v*v))
- *     POW    pow(u, y)        adj[a] += w * (y * pow(u, y - 1));  then adj[b] += w * (v * log(u))  (a CONST b drops its adjoint)
- *     ATAN2  atan2(u, y)      t = u*u + y*y;  adj[a] += (w * y) / t;  then adj[b] -= (w * u) / t   (Julia atan(a, b))
+ *     POW    pow(u, y)        adj[a] += w * (y * pow(u, y - 1));  then adj[b] += w * (v * log(u))  (a CONST b keeps it: its share of asm_eval_data_gradient, NaN or inf for u <= 0)
+ *     ATAN2  atan2(u, y)      t = u*u + y*y;  adj[a] += (w * y) / t;  then adj[b] -= (w * u) / t   (Julia atan(a, b)).  Formed as
+ *                             s = 2^-e, e the binary exponent of max(|u|, |y|) (kept within +-1000); us = u*s; ys = y*s; ts = us*us + ys*ys;
+ *                             adj[a] += ((w * ys) / ts) * s;  adj[b] -= ((w * us) / ts) * s  - the same bits wherever u*u + y*y neither
+ *                             underflows nor overflows, and the quotient itself where it does ((1e-200, 1e-200): 5e199, not inf)
  *     MIN    y < u ? y : u    w to the chosen operand: adj[b] += w if y < u, else adj[a] += w (ties and NaN go to a)
  *     MAX    y > u ? y : u    adj[b] += w if y > u, else adj[a] += w
  *   Domain errors (log of a negative number, asin outside [-1, 1], ...) give NaN or inf as the math library does.
@@ -275,8 +278,11 @@ int asm_eval_data_gradient(asm_handle* h, const double* x, const double* lambda,
  * asm_eval_setup.  A tape without CONST node: u = w = 0 without a launch.
  * Order: per row or term one forward-over-reverse sweep, the one of the Hessian (the statement tangents listed under "Hessian of the
  * Lagrangian" below, each parenthesis one rounding, no fused multiply-add) with another seed: a CONST node with operand a has the tangent
- * dc[a], every VAR node the tangent 0.  A CONST exponent of POW stays out of the sweep as in the first-order rule (no term with its
- * tangent, nothing to its adjoint).  w[n_rows + r] is the tangent of the last node of block row r.  The adjoint tangent z that reaches a
+ * dc[a], every VAR node the tangent 0.  A CONST exponent of POW is a CONST node like any other: its tangent is dc[a], and the terms with it
+ * (the "then" steps of POW below) enter where that tangent is nonzero.  Where it is 0 they are left out, not multiplied by 0: for u <= 0, where
+ * log(u) is NaN or -inf, pow(u, 2.0) has finite u and w along every direction that leaves its exponent alone - and for a dc that is zero on
+ * every exponent the results are those of a sweep that ignores exponents, bit for bit; a nonzero dc[a] at u <= 0 gives NaN or inf in that
+ * row's or term's share of u and in its w.  w[n_rows + r] is the tangent of the last node of block row r.  The adjoint tangent z that reaches a
  * VAR node is one occurrence: (-lambda[n_rows + r]) * z for a node of block row r, objective_scale * z for a node of a term (one product).
  * u[j] sums the occurrences of variable j from 0.0 in this order: rows in row order, then terms in term order; inside a row or term its VAR
  * nodes of j in descending node order.  No atomics.  With ADD..POWI, ABS, MIN and MAX only, device and host twin (nlexpr.py:
@@ -351,7 +357,7 @@ int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, co
  *     COS  d = -(du*sin(u))                tadj[a] -= (z*sin(u) + w*(cos(u)*du))
  *     ABS  d = du*copysign(1.0, u)         tadj[a] += z*copysign(1.0, u)                                       (zero curvature)
  *     TAN  d = du*(1 + v*v)                g = 1 + v*v;  tadj[a] += (z*g + w*(2*(v*d)))
- *     ASIN d = du / sqrt(1 - u*u)          r = sqrt(1 - u*u);  q = w/r;  dr = -((u*du) / r);  tadj[a] += (z - q*dr) / r      (ACOS: d, tadj negated)
+ *     ASIN d = du / sqrt((1 - u)*(1 + u))  r = sqrt((1 - u)*(1 + u));  q = w/r;  dr = -((u*du) / r);  tadj[a] += (z - q*dr) / r      (ACOS: d, tadj negated)
  *     ATAN d = du / (1 + u*u)              g = 1 + u*u;  q = w/g;  tadj[a] += (z - q*(2*(u*du))) / g
  *     SINH d = du*cosh(u)                  tadj[a] += (z*cosh(u) + w*(sinh(u)*du))
  *     COSH d = du*sinh(u)                  tadj[a] += (z*sinh(u) + w*(cosh(u)*du))
@@ -362,9 +368,13 @@ int asm_eval_data_cross(asm_handle* h, const double* x, const double* lambda, co
  *     CBRT d = du / (3*(v*v))              g = 3*(v*v);  q = w/g;  tadj[a] += (z - q*(6*(v*d))) / g
  *     POW  p1 = pow(u, y-1), p2 = pow(u, y-2), lu = log(u), A = y*p1, B = v*lu;  d = du*A, then d = d + dy*B;
  *          dp1 = du*((y-1)*p2), then dp1 = dp1 + dy*(p1*lu);  dA = y*dp1, then dA = dA + dy*p1;  tadj[a] += (z*A + w*dA);
- *          dB = d*lu + v*(du/u);  tadj[b] += (z*B + w*dB).  A CONST b: every "then" step and the statements on b are left out.
+ *          dB = d*lu + v*(du/u);  tadj[b] += (z*B + w*dB).  A CONST b in the Hessian: every "then" step and the statements on b are left out
+ *          (asm_eval_data_cross and asm_eval_data_cross_t say what they do with it).  TANH and EXPM1 carry the cancellation of their first-order
+ *          statements: absolute errors of a few eps (1 + v*v) * 2|v| and a few eps (|v| + 1).
  *     ATAN2 t = u*u + y*y;  d = (du*y)/t - (dy*u)/t;  dt = 2*(u*du) + 2*(y*dy);  qa = (w*y)/t;  qb = (w*u)/t;
- *          tadj[a] += ((z*y + w*dy) - qa*dt) / t;  tadj[b] -= ((z*u + w*du) - qb*dt) / t
+ *          tadj[a] += ((z*y + w*dy) - qa*dt) / t;  tadj[b] -= ((z*u + w*du) - qb*dt) / t  - formed with s, us, ys, ts of the first order:
+ *          d = ((du*ys)/ts)*s - ((dy*us)/ts)*s;  dts = 2*(us*du) + 2*(ys*dy);  tadj[a] += (((z*ys + (w*dy)*s) - qa*dts) / ts) * s, b alike:
+ *          the same bits wherever nothing underflows or overflows
  *     MIN / MAX  d and z follow the chosen operand (same tie rule)
  *   With ADD..POWI, ABS, MIN and MAX only, device values equal the host twin (nlexpr.py: ExprBlock.hessian_values) bit for bit.
  *   3. Ohm's-law block (kind 4), in place of 2.: every row of a branch is F = k_f vf^2 + k_t vt^2 + vf vt (P cos d + Q sin d), d = va_f - va_t,
@@ -526,7 +536,9 @@ int asm_var_bound_sensitivity_multi(asm_handle* h, const double* x, const double
  * call.  No fused multiply-add, no atomics; every written operation is one rounding, left to right, every sum in an order fixed by the model:
  *   expression block (kind 3): the forward-over-reverse sweep of the Hessian and of asm_eval_data_cross with the other seed - a VAR node
  *     of variable j has the tangent vx[j], a CONST node 0 - and the formulas of "Hessian of the Lagrangian", 2.  A CONST exponent of POW
- *     stays out of the sweep, as in asm_eval_data_cross: its occurrence is 0.  One thread per row or term.  In the reverse pass a CONST
+ *     receives adj and tadj (the statements on b) and yields its occurrence like every CONST node; its tangent is 0, so the "then" steps stay
+ *     out - no 0 * log(u) forms, and every entry that does not belong to the exponent stays finite for u < 0.  The exponent's own entry is NaN
+ *     or inf where log(u) is (u <= 0), as in asm_eval_data_gradient.  One thread per row or term.  In the reverse pass a CONST
  *     node with adjoint adj and adjoint tangent tadj yields one occurrence: for a node of block row r
  *       (-lambda[n_rows + r]) * tadj + vl[n_rows + r] * adj        (two products, one sum)
  *     and for a node of a term objective_scale * tadj.  out[c] sums the occurrences of dpar[c] in the list order of

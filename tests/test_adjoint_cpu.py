@@ -58,7 +58,8 @@ def test_transposed_twin_identity(case):
 
 
 def test_transposed_twin_summation_order_and_the_const_exponent():
-    """Rows before terms from 0.0 for a shared parameter; the CONST exponent of a POW yields the occurrence 0; no CONST node: empty."""
+    """Rows before terms from 0.0 for a shared parameter; the CONST exponent of a POW yields its occurrence (closed form); no CONST node:
+    empty."""
     from activesetmethods_amd import nlexpr
     from activesetmethods_amd.nlexpr import ExprBlock, parameters, variables
     x = variables(2)
@@ -73,7 +74,15 @@ def test_transposed_twin_summation_order_and_the_const_exponent():
     q = parameters([2.5])
     pw = ExprBlock([(nlexpr.pow(x[0], q[0]) + q[0] * x[1], 0.0, 0.0)], n=2, parameters=q)
     got = pw.data_cross_t(np.array([1.3, 0.4]), np.array([1.0]), np.array([1.0, 1.0]), np.array([2.0]))
-    assert got.tolist() == [(-1.0) * 1.0 + 2.0 * 0.4]                     # only the product sees the parameter
+    # g = x0^q + q x1:  out = vx' (-lam d/dq grad g) + vl dg/dq = -(x0^(q-1) (1 + q log x0)) - 1 + 2 (x0^q log x0 + x1)
+    lx = float(np.log(1.3))
+    want = -(1.3 ** 1.5 * (1.0 + 2.5 * lx)) - 1.0 + 2.0 * (1.3 ** 2.5 * lx + 0.4)
+    size = 1.3 ** 1.5 * (1.0 + 2.5 * lx) + 1.0 + 2.0 * (1.3 ** 2.5 * lx + 0.4)
+    assert got.shape == (1,) and abs(got[0] - want) <= 8 * np.finfo(float).eps * size
+    # the entries that are not the exponent's stay finite at a base below 0; the exponent's own is NaN, as data_gradient's
+    pz = ExprBlock([(nlexpr.pow(x[0], 2.0) + q[0] * x[1], 0.0, 0.0)], n=2, parameters=q)
+    got = pz.data_cross_t(np.array([-1.3, 0.4]), np.array([1.0]), np.array([1.0, 1.0]), np.array([2.0]))
+    assert got[0] == (-1.0) * 1.0 + 2.0 * 0.4 and np.isnan(got[1]) and np.isnan(pz.data_gradient(np.array([-1.3, 0.4]), np.array([1.0]))[1])
     nc = ExprBlock([(x[0] * x[1], 0.0, 0.0)], objective=x[0] * x[0], n=2)
     assert nc.data_cross_t(xv, np.array([1.0]), vx, np.array([1.0])).shape == (0,)
 

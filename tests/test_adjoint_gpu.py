@@ -55,7 +55,12 @@ def test_cross_t_without_constants_and_with_a_const_exponent():
     opt = _handle_for(pw.to_problem(), pw)
     xv, lam, vx, vl = np.array([1.3, 0.4]), np.array([0.5, 1.0]), np.array([1.0, -3.0]), np.array([0.25, 2.0])
     out, twin = opt.data_cross_t(xv, lam, vx, vl), sensitivity.model_cross_t(pw, xv, lam, vx, vl)
-    assert out.tolist() == [(-1.0) * (-3.0) + 2.0 * 0.4] and np.array_equal(out, twin)      # only the product sees the parameter
+    # g = x0^q + q x1 with lam 1, vl 2:  out = vx' (-(x0^(q-1) (1 + q log x0), 1)) + 2 (x0^q log x0 + x1); pow and log are the libraries':
+    # the closed form and the twin at LIBM_BAR
+    lx = float(np.log(1.3))
+    want = -(1.3 ** 1.5 * (1.0 + 2.5 * lx)) + 3.0 + 2.0 * (1.3 ** 2.5 * lx + 0.4)
+    size = 1.3 ** 1.5 * (1.0 + 2.5 * lx) + 3.0 + 2.0 * (1.3 ** 2.5 * lx + 0.4)
+    assert out.shape == (1,) and abs(out[0] - want) <= LIBM_BAR * size and abs(out[0] - twin[0]) <= LIBM_BAR * size
     opt.close()
 
 

@@ -36,8 +36,8 @@ def _dpar_index(blk):
 
 
 def _torch_value(root, z, c, slot):
-    """The value of the graph `root` with variable j read from z[j] and every CONST node from c[its dpar slot]; the CONST exponent
-    of a POW stays a plain number (the tape keeps it out of the derivative sweeps)."""
+    """The value of the graph `root` with variable j read from z[j] and every CONST node from c[its dpar slot], the CONST exponent
+    of a POW included."""
     import torch
     un = {nlexpr.NEG: torch.neg, nlexpr.SQRT: torch.sqrt, nlexpr.EXP: torch.exp, nlexpr.LOG: torch.log, nlexpr.SIN: torch.sin,
           nlexpr.COS: torch.cos, nlexpr.ABS: torch.abs, nlexpr.TAN: torch.tan, nlexpr.ASIN: torch.asin, nlexpr.ACOS: torch.acos,
@@ -62,8 +62,6 @@ def _torch_value(root, z, c, slot):
             v = z[e.arg]
         elif e.op == nlexpr.POWI:
             v = a[0] ** int(e.arg)
-        elif e.op == nlexpr.POW and e.args[1].op == nlexpr.CONST:
-            v = a[0] ** float(a[1].detach())
         elif e.op in bi:
             v = bi[e.op](a[0], a[1])
         else:
@@ -101,6 +99,12 @@ def cross_cases():
         v = np.random.default_rng(seed + 3).uniform(-1.5, 1.5, 3)
         blk, n = random_param_block(seed, v, exact=seed % 2 == 1)
         out.append(("random %d" % seed, blk, rng.uniform(-1, 1, n), 1.0))
+    x = variables(2)
+    q = parameters([2.5, 1.7])                                   # parameters as exponents: of a variable, of a product with a parameter, in a term
+    pw = ExprBlock([(nlexpr.pow(x[0], q[0]) + q[0] * x[1], 0.0, 0.0), (nlexpr.pow(x[1] * q[1], q[0]) - x[0], 0.0, 0.0)],
+                   objective=nlexpr.pow(x[0] + x[1], q[1]) * q[0] + nlexpr.pow(x[1], 1.5), n=2, parameters=q)
+    for s in (1.0, -1.0):
+        out.append(("parameter exponent %g" % s, pw, np.array([1.3, 0.4]), s))
     return out
 
 
@@ -121,7 +125,7 @@ def test_data_cross_against_torch_autograd(case):
 
 def test_data_cross_summation_order_and_the_const_exponent():
     """A parameter shared by two rows and a term; a row without constants; u[j] sums rows before terms from 0.0; the CONST exponent of
-    a POW takes no tangent; a tape without CONST node gives zeros."""
+    a POW takes its tangent like any other constant (closed form); a tape without CONST node gives zeros."""
     x = variables(2)
     p = parameters([3.0])
     blk = ExprBlock([(p[0] * x[0] * x[1], 0.0, 0.0), (x[0] * x[1], 0.0, 0.0), (x[0] * (p[0] * x[0]), 0.0, 0.0)],
@@ -136,7 +140,14 @@ def test_data_cross_summation_order_and_the_const_exponent():
     q = parameters([2.5])
     pw = ExprBlock([(nlexpr.pow(x[0], q[0]) + q[0] * x[1], 0.0, 0.0)], n=2, parameters=q)
     u, w = pw.data_cross(np.array([1.3, 0.4]), np.array([1.0]), np.array([1.0]))
-    assert w.tolist() == [0.4] and u.tolist() == [-0.0, -1.0]           # only the product sees the direction
+    # g = x0^q + q x1:  w = dg/dq = x0^q log x0 + x1,  u = -lam d/dq grad g = -(x0^(q-1) (1 + q log x0), 1)
+    lx, eps = float(np.log(1.3)), np.finfo(float).eps
+    want_w, want_u0 = 1.3 ** 2.5 * lx + 0.4, -(1.3 ** 1.5 * (1.0 + 2.5 * lx))
+    assert abs(w[0] - want_w) <= 8 * eps * abs(want_w) and abs(u[0] - want_u0) <= 8 * eps * abs(want_u0) and u[1] == -1.0
+    # a direction that leaves the exponent alone: today's bits, finite at a base below 0
+    pz = ExprBlock([(nlexpr.pow(x[0], 2.0) + q[0] * x[1], 0.0, 0.0)], n=2, parameters=q)
+    u, w = pz.data_cross(np.array([-1.3, 0.4]), np.array([1.0]), np.array([1.0, 0.0]))
+    assert w.tolist() == [0.4] and u.tolist() == [-0.0, -1.0]
     nc = ExprBlock([(x[0] * x[1], 0.0, 0.0)], objective=x[0] * x[0], n=2)
     u, w = nc.data_cross(xv, np.array([1.0]), np.zeros(0))
     assert not u.any() and not w.any()
