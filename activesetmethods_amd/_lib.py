@@ -111,6 +111,12 @@ class KktFormInfo(C.Structure):
                 ("n_pairs", C.c_int64), ("dense_bytes", C.c_int64), ("sparse_bytes", C.c_int64), ("order_ms", C.c_double)]
 
 
+class RangeInfo(C.Structure):
+    """asm_range_info: the range [t_lo, t_hi] of a sensitivity column and what blocks at either end - position (row i, or m + variable
+    j; -1 none) and kind (sensitivity.RANGE_KINDS)."""
+    _fields_ = [("t_lo", C.c_double), ("t_hi", C.c_double), ("pos_lo", C.c_int32), ("kind_lo", C.c_int32), ("pos_hi", C.c_int32), ("kind_hi", C.c_int32)]
+
+
 KKT_FORMS = {"dense": 0, "sparse": 1}
 
 
@@ -195,6 +201,7 @@ PROTOTYPES = {
     "asm_solution_adjoint": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_solution_adjoint_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_var_bound_sensitivity_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_sensitivity_range_multi": (C.c_int, [_P, _D, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(RangeInfo)]),
     "asm_solution_adjoint_z": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_solution_adjoint_z_multi": (C.c_int, [_P, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_kkt_step": (C.c_int, [_P, _D, _D, _I32, _I32, _D, _D, C.c_double, C.POINTER(KktStepParams), _D, _D, _D, C.POINTER(KktStepInfo)]),
@@ -253,6 +260,7 @@ PROTOTYPES = {
     "asm_batch_solution_sensitivity": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, C.c_int32, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_bound_sensitivity": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_var_bound_sensitivity": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _I32, _D, C.POINTER(KktParams), _D, _D, _D, C.POINTER(KktInfo)]),
+    "asm_batch_sensitivity_range": (C.c_int, [_P, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(RangeInfo)]),
     "asm_batch_solution_adjoint_z": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_solution_adjoint": (C.c_int, [_P, C.c_int64, _D, _D, _I32, _I32, C.c_int32, _D, _D, C.POINTER(KktParams), _D, _D, _D, _D, C.POINTER(KktInfo)]),
     "asm_batch_get_stats": (C.c_int, [_P, C.POINTER(BatchStats)]),

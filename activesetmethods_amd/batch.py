@@ -508,6 +508,36 @@ class HipBatch:
         return (OUT[:, :, :nd], DBOUND[:, :, :self.m], DXBOUND, AX, AL[:, :, :self.m],
                 [[infos[s * nrhs + c] for c in range(nrhs)] for s in range(S)])
 
+    def sensitivity_range(self, g_L, g_U, x_L, x_U, x, lam, mult_x_U, mult_x_L, row_state, bound_state, DX, DLAM, DZ):
+        """asm_batch_sensitivity_range: per scenario HipSubOptimizer.sensitivity_range, bit for bit what a fresh handle with the scenario's
+        bounds (rows of g_L, g_U [n_scen x m], x_L, x_U [n_scen x n], as slp_run takes them) and data gives, for the columns DX, DZ
+        [n_scen x nrhs x n] and DLAM [n_scen x nrhs x m].  Returns a structured array [n_scen x nrhs] with the fields of asm_range_info."""
+        from . import _lib
+        S, x, lam, rs, bs, _ = self._kkt_args(x, lam, row_state, bound_state, None, None)
+        f64 = lambda a_: np.ascontiguousarray(a_, np.float64)
+        g_L, g_U, x_L, x_U, mU, mL = map(f64, (g_L, g_U, x_L, x_U, mult_x_U, mult_x_L))
+        if self.m and (g_L.shape != (S, self.m) or g_U.shape != (S, self.m)):
+            raise ValueError("g_L / g_U have shapes %r / %r, expected %r" % (g_L.shape, g_U.shape, (S, self.m)))
+        for name, a in (("x_L", x_L), ("x_U", x_U), ("mult_x_U", mU), ("mult_x_L", mL)):
+            if a.shape != (S, self.n):
+                raise ValueError("%s has shape %r, expected %r" % (name, a.shape, (S, self.n)))
+        if not self.m:
+            g_L = g_U = np.zeros((S, 1))
+        z = mU + mL
+        DX = f64(DX)
+        if DX.ndim != 3 or DX.shape[0] != S or DX.shape[1] < 1 or DX.shape[2] != self.n:
+            raise ValueError("DX has shape %r, expected (%d, nrhs, %d) with at least one column" % (DX.shape, S, self.n))
+        nrhs = DX.shape[1]
+        DZ = f64(DZ)
+        DLAM = f64(DLAM) if self.m else np.zeros((S, nrhs, 1))
+        if DZ.shape != DX.shape or (self.m and DLAM.shape != (S, nrhs, self.m)):
+            raise ValueError("DZ / DLAM have shapes %r / %r, expected %r / %r" % (DZ.shape, DLAM.shape, DX.shape, (S, nrhs, self.m)))
+        out = np.zeros((S, nrhs), dtype=_lib.RangeInfo)
+        self._check(self._lib.asm_batch_sensitivity_range(self._b, S, _lib.dptr(g_L), _lib.dptr(g_U), _lib.dptr(x_L), _lib.dptr(x_U), _lib.dptr(x), _lib.dptr(lam),
+                                                          _lib.dptr(z), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ),
+                                                          out.ctypes.data_as(self._C.POINTER(_lib.RangeInfo))))
+        return out
+
     def sublp_solve(self, dE, df, f, E, x_k, delta, feasibility, bounds=None):
         """asm_sublp_solve for `count` = len(f) <= n_slots scenarios in lockstep; `bounds` = (g_L, g_U, x_L, x_U) per scenario or None.
         Returns (p, lambda, mult_x_U, mult_x_L, p_slack, status) with a leading scenario dimension."""
@@ -634,6 +664,18 @@ def var_bound_jacobians(hb, problems, runs, vars, tol=1e-6):
     DX, DLAM, DZ, infos = hb.var_bound_sensitivity(x, lam, rs, bs, vars)
     dx, dlam, status = _jacobian_stacks(DX, DLAM, infos)
     return dx, dlam, np.transpose(DZ, (0, 2, 1)).copy(), status
+
+
+def validity_ranges(hb, problems, runs, DX, DLAM, DZ, tol=1e-6):
+    """The validity ranges (structured array [S x k], the fields of asm_range_info) of the sensitivity columns DX [S x k x n],
+    DLAM [S x k x m], DZ [S x k x n] of the scenarios of `hb` at their runs - each on its working set (working_sets with `tol`), with its
+    bounds and its data: one asm_batch_sensitivity_range call.  The batch counterpart of sensitivity.validity_range; a scenario whose
+    columns all have t_lo <= -1 and t_hi >= 1 for a unit data change keeps the base case's working set to first order."""
+    rs, bs = working_sets(problems, runs, tol)
+    x, lam = _run_points(hb, runs)
+    stack = lambda name: np.stack([np.asarray(getattr(p, name), float) for p in problems]) if name[0] == "x" or hb.m else np.zeros((len(problems), 0))
+    mU, mL = np.stack([np.asarray(r.mult_x_U, float) for r in runs]), np.stack([np.asarray(r.mult_x_L, float) for r in runs])
+    return hb.sensitivity_range(stack("g_L"), stack("g_U"), stack("x_L"), stack("x_U"), x, lam, mU, mL, rs, bs, DX, DLAM, DZ)
 
 
 def solve_batch_lockstep(problems, parameters, n_slots, device=0, rank=0, world=1, reduce_device=None, batch=None):

@@ -14,6 +14,7 @@
 #include "asm_eval_kernels.hip.h"
 #include "asm_kkt_kernels.hip.h"
 #include "asm_eqp_kernels.hip.h"
+#include "asm_range_kernels.hip.h"
 #include "asm_lm_kernels.hip.h"
 #include "asm_batch.hip.h"
 #include "../../include/asm_hip.h"
@@ -301,6 +302,22 @@ struct KktBufs {
     double *eq_d = nullptr, *eq_h = nullptr;
 };
 
+// What asm_sensitivity_range_multi keeps (rg_prepare, at the first call after asm_eval_setup): the Jacobian at the call's x as the values
+// of the skeleton's CSR list (vals; a pattern without one: the dense rows J), the point's vectors, the blocks of a chunk's
+// columns, the partial candidates of the two launches and the results.  Nothing here is read by another entry.
+struct RangeBufs {
+    bool ready = false;
+    int64_t n_row_wg = 0, n_var_wg = 0;
+    double *dE = nullptr, *vals = nullptr, *J = nullptr;        // nnz Jacobian values of the evaluation; sp_nnz CSR values, or Mp x ldn dense rows
+    double* pt = nullptr;                                       // [lam (Mp) | z (ldn)] and behind them, as ints, [row_state (Mp) | bound_state (ldn)]
+    double* cols = nullptr;                                     // a chunk's columns, packed: [DX (cols x ldn) | DZ (cols x ldn) | DLAM (cols x Mp)]
+    double* part_t = nullptr;                                   // the partial candidates (RangeRed): slots x RG_CW x 2 ratios,
+    int* part_k = nullptr;                                      // their positions and kinds,
+    unsigned* cnt = nullptr;                                    // the arrival counters
+    RangeOut* out = nullptr;                                    // RG_CW results
+    double* stage = nullptr;                                    // pinned: the image of pt or of cols, then the results
+};
+
 // The device and pinned host buffers of one lifetime.  Each allocation is recorded with the field that points to it (and, for mapped host
 // memory, the field that holds its device address); release() frees them all and nulls those fields.  Sizes are max(count, 1) elements.
 class BufPool {
@@ -456,6 +473,7 @@ struct EvalState {
     bool ohm_vars_ok = true;        // Ohm's law with derivatives: every variable the block names is inside [0, n) (nlp_setup; refused by the data entries)
     KktBufs kk;                     // KKT solve on a working set (asm_kkt_solve and the multi entries)
     KktCounters kkm;                // test seam: the counters of the last multi call
+    RangeBufs rg;                   // validity ranges (asm_sensitivity_range_multi)
     BufPool mem;                    // declared last: it goes first, while the fields it nulls are alive
 };
 
@@ -6413,6 +6431,117 @@ int asm_solution_adjoint_multi(asm_handle* h, const double* x, const double* lam
     return guarded(h, [&] { do_solution_adjoint_multi(h, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info); });
 }
 
+// ---- Validity ranges (include/asm_hip.h, "Validity ranges"): how far a column (dx, dlam, dz) of the sensitivity entries may be followed
+// before the working set changes.  The ONE place that launches asm_range_kernels.hip.h.
+static_assert(RG_CW == ASM_KKT_CHUNK && RG_CW % RG_CPB == 0 && RG_CPB == 4 * RG_CPT, "the chunk width of the header is the kernels'");
+static_assert(sizeof(RangeOut) == sizeof(asm_range_info) && offsetof(RangeOut, pos_hi) == offsetof(asm_range_info, pos_hi), "asm_range_info is the kernels' RangeOut");
+// what the entry refuses without a launch, per handle and - on the calling thread - for a scenario batch (n_scen points)
+static void rg_check_args(const std::string& me, int64_t n, int64_t m, int64_t n_scen, const double* x, const double* lambda, const double* z, const int32_t* row_state,
+                          const int32_t* bound_state, int32_t nrhs, const double* DX, const double* DLAM, const double* DZ, const asm_range_info* out) {
+    if (nrhs < 1) throw std::invalid_argument(me + ": nrhs < 1");
+    if (!x || !z || !bound_state || !DX || !DZ || !out || (m > 0 && (!lambda || !row_state || !DLAM))) throw std::invalid_argument(me + ": null pointer");
+    for (int64_t j = 0; j < n_scen * n; ++j)
+        if (bound_state[j] < -1 || bound_state[j] > 1) throw std::invalid_argument(me + ": bound_state holds a value outside {-1, 0, +1}");
+    for (int64_t i = 0; i < n_scen * m; ++i)
+        if (row_state[i] != 0 && row_state[i] != 1) throw std::invalid_argument(me + ": row_state holds a value outside {0, 1}");
+}
+// once per asm_eval_setup, at the first call (for a slot of a scenario batch before its fiber starts)
+static void rg_prepare(asm_handle* h) {
+    RangeBufs& G = h->ev->rg;
+    if (G.ready) return;
+    HIPCHK(hipSetDevice(h->device));
+    BufPool& M = h->ev->mem;
+    const hipStream_t s = h->stream;
+    const Skeleton& S = *h->sk;
+    const int64_t ldn = S.ldn, Mp = std::max<int64_t>(S.Mp, 32), ni = (Mp + ldn + 1) / 2, per = 2 * ldn + Mp;
+    G.n_row_wg = (S.m + RG_TILE - 1) / RG_TILE;
+    G.n_var_wg = (S.n + RG_TILE - 1) / RG_TILE;
+    const int64_t slots = G.n_row_wg + G.n_var_wg;
+    M.alloc(G.dE, S.nnz);
+    if (S.sp_ok) M.zeroed(G.vals, S.sp_nnz, s);
+    else M.zeroed(G.J, Mp * ldn, s);
+    M.zeroed(G.pt, Mp + ldn + ni, s);
+    M.zeroed(G.cols, RG_CW * per, s);
+    M.zeroed(G.part_t, slots * RG_CW * 2, s);
+    M.zeroed(G.part_k, slots * RG_CW * 4, s);
+    M.zeroed(G.cnt, RG_CW / RG_CPB + 2, s);
+    M.zeroed(G.out, RG_CW, s);
+    M.alloc(G.stage, std::max(Mp + ldn + ni, RG_CW * per) + RG_CW * (int64_t)(sizeof(RangeOut) / sizeof(double)), BufPool::PINNED);
+    HIPCHK(asmb::sync(s));
+    G.ready = true;
+}
+// The entry under the name `who`, for the per-handle call and for a batch fiber (the arguments are checked by the caller).  E and the
+// Jacobian values at x by the evaluator's launches into buffers of the entry's own (d_xt, d_Et and RangeBufs: the LP's inputs stay), the
+// values summed into the CSR list of the pattern or assembled into dense rows; then per chunk one upload, the two launches, one read-back.
+static void rg_run(asm_handle* h, const double* x, const double* lambda, const double* z, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                   const double* DX, const double* DLAM, const double* DZ, asm_range_info* out) {
+    rg_prepare(h);
+    HIPCHK(hipSetDevice(h->device));
+    EvalState& e = *h->ev;
+    RangeBufs& G = e.rg;
+    const Skeleton& S = *h->sk;
+    const hipStream_t s = h->stream;
+    const int64_t n = S.n, m = S.m, ldn = S.ldn, Mp = std::max<int64_t>(S.Mp, 32);
+    // the point: x where the evaluator's launches read it; [lam | z | row_state | bound_state] in one upload
+    std::memcpy(e.h_stage, x, n * sizeof(double));
+    HIPCHK(asmb::copy_async(e.d_xt, e.h_stage, n * sizeof(double), hipMemcpyHostToDevice, s));
+    double* st = G.stage;
+    int* sti = reinterpret_cast<int*>(st + Mp + ldn);
+    for (int64_t i = 0; i < Mp; ++i) { st[i] = i < m ? lambda[i] : 0.0; sti[i] = i < m ? row_state[i] : 0; }
+    for (int64_t j = 0; j < ldn; ++j) { st[Mp + j] = j < n ? z[j] : 0.0; sti[Mp + j] = j < n ? bound_state[j] : 0; }
+    HIPCHK(asmb::copy_async(G.pt, st, (Mp + ldn) * sizeof(double) + (Mp + ldn) * sizeof(int), hipMemcpyHostToDevice, s));
+    h2d_done(h);      // (the staging area is written again for the first chunk)
+    fn_rows_launch(e, s, e.d_xt, e.d_Et, G.dE, 1);
+    nlp_rows_launch(e, s, e.d_xt, e.d_Et, G.dE, 1);
+    if (S.sp_ok) {
+        asmb::launch(k_kkts_vals, dim3((unsigned)std::min<int64_t>((S.nu + 255) / 256, 4096)), dim3(256), s, G.dE, S.d_perm, S.d_ustart, S.nu, G.vals);
+    } else if (S.dense_fast) {
+        asmb::launch(k_assemble_dense, dim3((unsigned)std::min<int64_t>((m * n + 255) / 256, 4096)), dim3(256), s, G.dE, G.J, m, n, ldn);
+    } else if (S.nu > 0) {
+        asmb::launch(k_assemble, dim3((unsigned)std::min<int64_t>((S.nu + 255) / 256, 4096)), dim3(256), s, G.dE, S.d_perm, S.d_ustart, S.d_uoff, S.d_adjoff, G.J, S.nu);
+    }
+    const EvLayout& L = e.L;
+    const RangePoint P{e.d_Et, L.g_L(), L.g_U(), G.pt, reinterpret_cast<const int*>(G.pt + Mp + ldn), e.d_xt, L.x_L(), L.x_U(), G.pt + Mp,
+                       reinterpret_cast<const int*>(G.pt + Mp + ldn) + Mp, m, n};
+    const RangeRed R{G.part_t, G.part_k, G.cnt};
+    for (int32_t c0 = 0; c0 < nrhs; c0 += RG_CW) {
+        const int cols = (int)std::min<int32_t>(RG_CW, nrhs - c0);
+        // the chunk's columns, packed [DX (cols x ldn) | DZ (cols x ldn) | DLAM (cols x Mp)] with the padding cleared: one upload
+        double *sx = st, *sz = sx + (int64_t)cols * ldn, *sl = sz + (int64_t)cols * ldn;
+        for (int c = 0; c < cols; ++c) {
+            std::memcpy(sx + (int64_t)c * ldn, DX + (int64_t)(c0 + c) * n, n * sizeof(double));
+            std::memcpy(sz + (int64_t)c * ldn, DZ + (int64_t)(c0 + c) * n, n * sizeof(double));
+            for (int64_t j = n; j < ldn; ++j) sx[(int64_t)c * ldn + j] = sz[(int64_t)c * ldn + j] = 0.0;
+            if (m > 0) std::memcpy(sl + (int64_t)c * Mp, DLAM + (int64_t)(c0 + c) * m, m * sizeof(double));
+            for (int64_t i = m; i < Mp; ++i) sl[(int64_t)c * Mp + i] = 0.0;
+        }
+        HIPCHK(asmb::copy_async(G.cols, st, (int64_t)cols * (2 * ldn + Mp) * sizeof(double), hipMemcpyHostToDevice, s));
+        const double *dx = G.cols, *dz = dx + (int64_t)cols * ldn, *dl = dz + (int64_t)cols * ldn;
+        const unsigned gy = (unsigned)((cols + RG_CPB - 1) / RG_CPB);
+        if (S.sp_ok)
+            asmb::launch(k_range_rows_sparse, dim3((unsigned)G.n_row_wg, gy), dim3(256), s, P, (const int*)S.d_sp_ptr, (const int*)S.d_sp_col, (const double*)G.vals, dx, ldn, dl, Mp, cols, R);
+        else
+            asmb::launch(k_range_rows_dense, dim3((unsigned)G.n_row_wg, gy), dim3(256), s, P, (const double*)G.J, dx, ldn, dl, Mp, cols, R);
+        asmb::launch(k_range_vars, dim3((unsigned)G.n_var_wg, gy), dim3(256), s, P, dx, dz, ldn, cols, (int)G.n_row_wg, R, G.out);
+        RangeOut* back = reinterpret_cast<RangeOut*>(st + std::max(Mp + ldn + (Mp + ldn + 1) / 2, RG_CW * (2 * ldn + Mp)));
+        HIPCHK(asmb::copy_async(back, G.out, cols * sizeof(RangeOut), hipMemcpyDeviceToHost, s));
+        HIPCHK(asmb::sync(s));
+        std::memcpy(out + c0, back, cols * sizeof(RangeOut));
+    }
+}
+static void do_sensitivity_range(asm_handle* h, const double* x, const double* lambda, const double* z, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                 const double* DX, const double* DLAM, const double* DZ, asm_range_info* out) {
+    const char* who = "asm_sensitivity_range_multi";
+    ev_of(h, who);
+    rg_check_args(who, h->sk->n, h->sk->m, 1, x, lambda, z, row_state, bound_state, nrhs, DX, DLAM, DZ, out);
+    rg_run(h, x, lambda, z, row_state, bound_state, nrhs, DX, DLAM, DZ, out);
+}
+
+int asm_sensitivity_range_multi(asm_handle* h, const double* x, const double* lambda, const double* z, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
+                                const double* DX, const double* DLAM, const double* DZ, asm_range_info* out) {
+    return guarded(h, [&] { do_sensitivity_range(h, x, lambda, z, row_state, bound_state, nrhs, DX, DLAM, DZ, out); });
+}
+
 int asm_var_bound_sensitivity_multi(asm_handle* h, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,
                                     const int32_t* vars, const double* delta, const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info) {
     return guarded(h, [&] {
@@ -8966,6 +9095,35 @@ int asm_batch_solution_adjoint_z(asm_batch* b, int64_t n_scen, const double* x, 
                                  const double* GX, const double* GL, const double* GZ, const asm_kkt_params* par, double* OUT, double* DBOUND, double* DXBOUND, double* AX,
                                  double* AL, asm_kkt_info* info) {
     return guarded(b, [&] { batch_adjoint(b, n_scen, {x, lambda, row_state, bound_state}, nrhs, GX, GL, par, OUT, DBOUND, AX, AL, info, true, GZ, DXBOUND); });
+}
+
+// asm_sensitivity_range_multi of n_scen scenarios, each with its bounds (as asm_batch_slp_run takes them) and its data, the slots taking them
+// in index order.  Everything that can be refused without a launch is refused here, on the calling thread, by the per-handle entry's own
+// rg_check_args; what a slot allocates at its first call is made before the fibers start (rg_prepare).
+int asm_batch_sensitivity_range(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub, const double* x,
+                                const double* lambda, const double* z, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs, const double* DX,
+                                const double* DLAM, const double* DZ, asm_range_info* out) {
+    return guarded(b, [&] {
+        const char *who = "asm_batch_sensitivity_range", *step = "asm_sensitivity_range_multi";
+        const std::string me(who);
+        if (!b->setup_done || !b->slots[0]->ev) throw std::logic_error(me + ": asm_batch_eval_setup first");
+        const int64_t n = b->slots[0]->sk->n, m = b->slots[0]->sk->m;
+        if (n_scen < 1) throw std::invalid_argument(me + ": n_scen < 1");
+        if (!v_lb || !v_ub || (m > 0 && (!c_lb || !c_ub))) throw std::invalid_argument(me + ": null pointer");
+        rg_check_args(me, n, m, n_scen, x, lambda, z, row_state, bound_state, nrhs, DX, DLAM, DZ, out);
+        check_scen(b, n_scen, who);
+        HIPCHK(hipSetDevice(b->device));
+        const int count = (int)std::min<int64_t>(n_scen, (int64_t)b->slots.size());
+        for (int s = 0; s < count; ++s) in_slot(step, s, [&] { rg_prepare(b->slots[s]); });
+        for_each_scenario(b, n_scen, step, [&](asm_handle* h, int64_t sc, int) {
+            do_set_bounds(h, m > 0 ? c_lb + sc * m : nullptr, m > 0 ? c_ub + sc * m : nullptr, v_lb + sc * n, v_ub + sc * n);
+            batch_scenario_data(b, h, sc);
+            asmb::next_cycle();
+            const int64_t o = sc * nrhs;
+            rg_run(h, x + sc * n, m > 0 ? lambda + sc * m : nullptr, z + sc * n, m > 0 ? row_state + sc * m : nullptr, bound_state + sc * n, nrhs, DX + o * n,
+                   m > 0 ? DLAM + o * m : nullptr, DZ + o * n, out + o);
+        });
+    });
 }
 
 int asm_batch_var_bound_sensitivity(asm_batch* b, int64_t n_scen, const double* x, const double* lambda, const int32_t* row_state, const int32_t* bound_state, int32_t nrhs,

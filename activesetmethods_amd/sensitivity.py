@@ -37,7 +37,15 @@ takes gx + H gz and gl - J gz, the transposed sweep vx = gz - ax, and d phi / d(
     var_bound_jacobian   dx*, dlam*, dz* / d(xbound) for a list of variables at a bound (asm_var_bound_sensitivity_multi)
     adjoint_reference_z  adjoint_reference with weights on z and the gradient with respect to the variable bounds
 
-For the scenarios of a HipBatch: batch.working_sets, batch.solution_jacobians, batch.bound_jacobians, batch.var_bound_jacobians.
+Validity ranges ("Validity ranges"): how far a column (dx, dlam, dz) may be followed before the working set changes - an inactive row
+or a free variable reaches a bound, a multiplier of a working row or of a bound reaches zero.
+
+    validity_range_host  the NumPy twin and the specification of the rule, V = J dx from dense_jacobian
+    validity_range       the device call on a handle (asm_sensitivity_range_multi)
+    RANGE_KINDS          names of the kinds 0..6 of what blocks
+
+For the scenarios of a HipBatch: batch.working_sets, batch.solution_jacobians, batch.bound_jacobians, batch.var_bound_jacobians,
+batch.validity_ranges.
 """
 import numpy as np
 
@@ -448,6 +456,112 @@ def solution_adjoint(model_or_opt, fm, x, lam, row_state, bound_state, gx, gl, m
         return opt.solution_adjoint(x, lam, row_state, bound_state, gx, gl, max_iter, rtol)
     finally:
         opt.close()
+
+
+RANGE_KINDS = ("none", "row reaches g_L", "row reaches g_U", "variable reaches x_L", "variable reaches x_U", "row multiplier reaches 0",
+               "bound multiplier reaches 0")        # asm_range_info.kind_*: ASM_RANGE_* 0..6
+RANGE_DTYPE = np.dtype([("t_lo", np.float64), ("t_hi", np.float64), ("pos_lo", np.int32), ("kind_lo", np.int32), ("pos_hi", np.int32),
+                        ("kind_hi", np.int32)], align=True)
+
+
+def _range_model(p, x):
+    """(g_L, g_U, x_L, x_U, E, J) of a Problem or a FunctionModel at x: the bounds, g(x) and the dense Jacobian (duplicates add)."""
+    x = np.asarray(x, float)
+    if hasattr(p, "constraint_bounds"):
+        g_L, g_U = p.constraint_bounds()
+        J = dense_jacobian(p, x)
+    else:
+        g_L, g_U = np.asarray(p.g_L, float), np.asarray(p.g_U, float)
+        J = np.zeros((p.m, p.n))
+        if len(p.j_row):
+            np.add.at(J, (np.asarray(p.j_row, np.int64) - 1, np.asarray(p.j_col, np.int64) - 1), p.eval_jac_g(x, np.zeros(len(p.j_row))))
+    m = int(p.m)
+    E = np.asarray(p.eval_g(x, np.zeros(m)), float) if m else np.zeros(0)
+    return np.asarray(g_L, float).reshape(m), np.asarray(g_U, float).reshape(m), np.asarray(p.x_L, float), np.asarray(p.x_U, float), E, J
+
+
+def validity_range_host(problem_or_fm, x, lam, mult_x_U, mult_x_L, row_state, bound_state, DX, DLAM, DZ, dtype=np.float64, runner_up=False):
+    """The NumPy twin of asm_sensitivity_range_multi and the specification of the rule (include/asm_hip.h, "Validity ranges"): for every
+    column c - row c of DX [k x n], DLAM [k x m], DZ [k x n] - the range [t_lo, t_hi] of t on which x + t dx, lam + t dlam, z + t dz
+    (z = mult_x_U + mult_x_L) keep the working set (row_state, bound_state) of `problem_or_fm` (a Problem or a FunctionModel) to first
+    order, and what blocks at either end.  With sg = +1 for the upper and -1 for the lower range, V = J dx from dense_jacobian, and the
+    candidates in position order (rows 0 .. m - 1, then variable j at m + j):
+        row i outside W     sg V_i < 0 and g_L_i > -inf: (g_L_i - E_i) / (sg V_i), kind 1; else sg V_i > 0 and g_U_i < inf: kind 2
+        row i in W, g_L_i != g_U_i   at its upper bound (!(g_L_i > -inf) or g_U_i < inf and |E_i - g_U_i| < |E_i - g_L_i|) with
+                            sg dlam_i > 0, at its lower bound with sg dlam_i < 0: -lam_i / (sg dlam_i), kind 5
+        variable j in F     sg dx_j < 0 and x_L_j > -inf: (x_L_j - x_j) / (sg dx_j), kind 3; else sg dx_j > 0 and x_U_j < inf: kind 4
+        variable j in B     at +1 with sg dz_j > 0, at -1 with sg dz_j < 0: -z_j / (sg dz_j), kind 6
+    every ratio clamped from below at 0, one that is not below +inf no candidate; the smallest ratio wins, on equal ratios the smallest
+    position; +inf, position -1 and kind 0 without a candidate; t_hi = best, t_lo = 0 - best.  Returns a structured array [k] with the
+    fields of asm_range_info (RANGE_DTYPE; t in float64 whatever `dtype`, the type of the arithmetic).  runner_up: also (k x 2) the
+    smallest ratio at another position than the winner's, columns (lower, upper), +inf without one."""
+    T = np.dtype(dtype).type
+    g_L, g_U, x_L, x_U, E, J = (np.asarray(a, T) for a in _range_model(problem_or_fm, x))
+    m, n = J.shape
+    x, lam = np.asarray(x, T).reshape(n), np.asarray(lam, T).reshape(m)
+    z = np.asarray(mult_x_U, T).reshape(n) + np.asarray(mult_x_L, T).reshape(n)
+    rs, bs = np.asarray(row_state).reshape(m), np.asarray(bound_state).reshape(n)
+    DX, DZ = np.atleast_2d(np.asarray(DX, T)), np.atleast_2d(np.asarray(DZ, T))
+    k = DX.shape[0]
+    DLAM = np.asarray(DLAM, T).reshape(k, m)
+    if DX.shape != (k, n) or DZ.shape != (k, n) or k < 1:
+        raise ValueError("DX, DLAM, DZ must have shapes (k, n), (k, m), (k, n) with k >= 1")
+    if np.any((rs != 0) & (rs != 1)) or np.any(np.abs(bs) > 1):
+        raise ValueError("row_state must hold 0 / 1 and bound_state -1 / 0 / +1")
+    V = DX @ J.T                                               # k x m
+    inf = T(np.inf)
+    upper = ~(g_L > -inf) | ((g_U < inf) & (np.abs(E - g_U) < np.abs(E - g_L)))
+    out = np.zeros(k, RANGE_DTYPE)
+    second = np.full((k, 2), np.inf)
+    pos = np.arange(m + n)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for side, sg in enumerate((T(-1.0), T(1.0))):
+            v, dl, vx, dv = sg * V, sg * DLAM, sg * DX, sg * DZ
+            ratio = np.full((k, m + n), inf, T)
+            kind = np.zeros((k, m + n), np.int32)
+
+            def offer(cond, num, den, kd, at):
+                r = np.where(cond, num / np.where(cond, den, T(1.0)), inf)
+                sl = (slice(None), at)
+                ratio[sl] = np.where(cond, r, ratio[sl])
+                kind[sl] = np.where(cond, kd, kind[sl])
+
+            rows, vars_ = slice(0, m), slice(m, m + n)
+            out_w, in_w = (rs == 0)[None, :], ((rs == 1) & (g_L != g_U))[None, :]
+            lo1 = out_w & (v < 0) & (g_L > -inf)[None, :]
+            offer(lo1, (g_L - E)[None, :], v, 1, rows)
+            offer(out_w & ~lo1 & (v > 0) & (g_U < inf)[None, :], (g_U - E)[None, :], v, 2, rows)
+            offer(in_w & np.where(upper[None, :], dl > 0, dl < 0), -lam[None, :], dl, 5, rows)
+            free, atb = (bs == 0)[None, :], (bs != 0)[None, :]
+            lo3 = free & (vx < 0) & (x_L > -inf)[None, :]
+            offer(lo3, (x_L - x)[None, :], vx, 3, vars_)
+            offer(free & ~lo3 & (vx > 0) & (x_U < inf)[None, :], (x_U - x)[None, :], vx, 4, vars_)
+            offer(atb & np.where((bs > 0)[None, :], dv > 0, dv < 0), -z[None, :], dv, 6, vars_)
+            ratio = np.where(ratio < 0, T(0.0), ratio)
+            ok = ratio < inf
+            ratio = np.where(ok, ratio, inf)
+            kind = np.where(ok, kind, 0)
+            best = np.argmin(ratio, axis=1)                    # (the first of equal minima: the smallest position)
+            for c in range(k):
+                b = ratio[c, best[c]]
+                if b < inf:
+                    p_, kd = int(pos[best[c]]), int(kind[c, best[c]])
+                    others = np.delete(ratio[c], best[c])
+                    second[c, side] = float(others.min()) if len(others) else np.inf
+                else:
+                    p_, kd = -1, 0
+                t = float(T(0.0) - b) if side == 0 else float(b)
+                out[c][("t_lo", "t_hi")[side]] = t
+                out[c][("pos_lo", "pos_hi")[side]] = p_
+                out[c][("kind_lo", "kind_hi")[side]] = kd
+    return (out, second) if runner_up else out
+
+
+def validity_range(opt, x, lam, mult_x_U, mult_x_L, row_state, bound_state, DX, DLAM, DZ):
+    """The validity ranges of the sensitivity columns DX, DLAM, DZ on the device: asm_sensitivity_range_multi on `opt`, a HipSubOptimizer
+    whose evaluator holds the model and whose bounds are the problem's (or any object with its sensitivity_range).  A structured array
+    with the fields of asm_range_info; validity_range_host is the NumPy twin."""
+    return opt.sensitivity_range(x, lam, mult_x_U, mult_x_L, row_state, bound_state, DX, DLAM, DZ)
 
 
 def predict(x, dx, step):

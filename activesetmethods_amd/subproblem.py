@@ -451,6 +451,24 @@ class HipSubOptimizer:
                                                               _lib.dptr(DX), _lib.dptr(DLAM), _lib.dptr(DZ), infos))
         return DX, DLAM[:, :self.m], DZ, list(infos)
 
+    # ------------------------------------------------------------------ validity ranges (include/asm_hip.h: "Validity ranges")
+    def sensitivity_range(self, x, lam, mult_x_U, mult_x_L, row_state, bound_state, DX, DLAM, DZ):
+        """asm_sensitivity_range_multi: for every column (row c of DX [nrhs x n], DLAM [nrhs x m], DZ [nrhs x n] - the outputs of the
+        sensitivity entries) the range of t on which x + t DX[c], lam + t DLAM[c], z + t DZ[c] keep the working set (row_state,
+        bound_state), z = mult_x_U + mult_x_L, with the handle's bounds.  Returns a structured array [nrhs] with the fields of
+        asm_range_info: t_lo <= 0 <= t_hi and what blocks at either end, pos_* (row i, or m + variable j; -1 none) and kind_*
+        (sensitivity.RANGE_KINDS).  sensitivity.validity_range_host is its NumPy twin."""
+        x, lam = self._vec(x, self.n, "x"), self._vec(lam, self.m, "lam")
+        z = self._vec(mult_x_U, self.n, "mult_x_U") + self._vec(mult_x_L, self.n, "mult_x_L")
+        DX = self._mat(DX, self.n, "DX")
+        nrhs = DX.shape[0]
+        DLAM, DZ = self._mat(DLAM, self.m, "DLAM", nrhs), self._mat(DZ, self.n, "DZ", nrhs)
+        rs, bs = self._states(row_state, bound_state)
+        out = np.zeros(nrhs, dtype=_lib.RangeInfo)
+        self._check(self._lib.asm_sensitivity_range_multi(self._h, _lib.dptr(x), _lib.dptr(lam), _lib.dptr(z), _lib.i32ptr(rs), _lib.i32ptr(bs), nrhs, _lib.dptr(DX),
+                                                          _lib.dptr(DLAM), _lib.dptr(DZ), out.ctypes.data_as(C.POINTER(_lib.RangeInfo))))
+        return out
+
     # ------------------------------------------------------------------ adjoint sensitivities (include/asm_hip.h: "Adjoint solution sensitivities")
     def data_cross_t(self, x, lam, vx, vl):
         """out [n_dpar] of asm_eval_data_cross_t: out[c] = vx' d/d dpar[c] (grad_x (f - lam' g)) + vl' d g / d dpar[c] for weights vx [n],

@@ -518,6 +518,56 @@ int asm_var_bound_sensitivity_multi(asm_handle* h, const double* x, const double
                                     const int32_t* bound_state, int32_t nrhs, const int32_t* vars, const double* delta /* [nrhs], or NULL: 1.0 */,
                                     const asm_kkt_params* par, double* DX, double* DLAM, double* DZ, asm_kkt_info* info);
 
+/* ---- Validity ranges: how far a sensitivity column may be followed before the working set changes.
+ * The sensitivity entries return derivatives (dx, dlam, dz) on a fixed working set W, B.  asm_sensitivity_range_multi returns, per column,
+ * the interval [t_lo, t_hi] of t on which x + t dx, lambda + t dlam, z + t dz keep that working set to first order: the ranging output of
+ * LP and QP codes.  The rule uses E + t V with V = J dx; it is exact for affine rows and a quadratic objective, the linearised range else.
+ *   Inputs: x [n], lambda [m], z [n] (z = mult_x_U + mult_x_L, read on B only), row_state [m] in {0, 1}, bound_state [n] in {-1, 0, +1};
+ *   the problem's bounds g_L, g_U, x_L, x_U as asm_sublp_set_bounds left them; E = g(x) and J at x, evaluated by the entry; per column c
+ *   row c of DX [nrhs x n], DLAM [nrhs x m], DZ [nrhs x n].  Signs are the drivers': lambda_i >= 0 at g_L, <= 0 at g_U, z_j >= 0 at a
+ *   lower bound, <= 0 at an upper bound.
+ *   For sg = +1 (the upper range) and sg = -1 (the lower one) the candidates are visited in position order - rows 0 .. m - 1, then
+ *   variable j at position m + j - with v = sg V_i, dl = sg dlam_i, vx = sg dx_j, dv = sg dz_j:
+ *     row i outside W:  if v < 0 and g_L_i > -inf: (g_L_i - E_i) / v, kind 1; else if v > 0 and g_U_i < inf: (g_U_i - E_i) / v, kind 2
+ *     row i in W, g_L_i != g_U_i:  upper = !(g_L_i > -inf) || (g_U_i < inf && |E_i - g_U_i| < |E_i - g_L_i|);
+ *                       if (upper ? dl > 0 : dl < 0): -lambda_i / dl, kind 5.  An equality row in W offers nothing.
+ *     variable j in F:  if vx < 0 and x_L_j > -inf: (x_L_j - x_j) / vx, kind 3; else if vx > 0 and x_U_j < inf: (x_U_j - x_j) / vx, kind 4
+ *     variable j in B:  if (bound_state_j > 0 ? dv > 0 : dv < 0): -z_j / dv, kind 6
+ *   Every ratio is clamped from below at 0 (r < 0 ? 0 : r): a violated inactive row or a multiplier of the wrong sign makes the range 0 on
+ *   that side.  A ratio that is not below +inf is no candidate.  The side's result is the smallest ratio, on equal ratios the smallest
+ *   position; best = +inf, position -1 and kind 0 mean no candidate.  t_hi = best >= 0, t_lo = 0 - best <= 0.
+ *   V_i is summed from 0.0 over the row's entries in the order of its pattern - the CSR list of the skeleton where the pattern has one,
+ *   j = 0 .. n - 1 over the dense row otherwise - product then sum, no fused multiply-add, by one thread.  No atomics on doubles: partial
+ *   minima per workgroup, combined by the last workgroup to arrive in workgroup order (asm_range_kernels.hip.h).  A column's result
+ *   depends on that column alone, bit for bit: not on nrhs, its place, its neighbours or the KKT form set on the handle.
+ * The entry evaluates E and the Jacobian values at x with the evaluator's own launches into buffers of its own, as the KKT entries do, for
+ * every nlp_kind (first derivatives only).  Columns go in chunks of ASM_KKT_CHUNK: one upload and one read-back per chunk.  It does not
+ * touch the next LP's inputs, the retained basis or the active sets.  Memory, made at the first call: the Jacobian values (nnz), the CSR
+ * values (or Mp x ldn dense rows for a pattern without a CSR list), ASM_KKT_CHUNK x (2 ldn + Mp) doubles for a chunk,
+ * (ceil(m / 64) + ceil(n / 64)) x ASM_KKT_CHUNK x 2 partial candidates of 16 bytes, and the pinned image of a chunk.
+ * Errors: ASM_ERR_STATE before asm_sublp_setup and asm_eval_setup; a null pointer (lambda, row_state, DLAM may be NULL for m = 0),
+ * nrhs < 1, a state outside its value set: ASM_ERR_ARG.  The handle works on afterwards.
+ * asm_batch_sensitivity_range: the same with a leading scenario dimension on every array - bounds n_scen x m and n_scen x n as in
+ * asm_batch_slp_run, x, z, bound_state n_scen x n, lambda, row_state n_scen x m, DX, DZ n_scen x nrhs x n, DLAM n_scen x nrhs x m, out
+ * n_scen x nrhs.  Each scenario runs with its bounds and its row of the scenario data table; n_scen may exceed the slot count; the work
+ * areas are made before any fiber starts, where the argument refusals happen too; scenario s is bit-identical to the per-handle entry on
+ * a fresh handle with that scenario's bounds and data. */
+typedef struct {
+    double t_lo, t_hi;       /* the range of t: t_lo <= 0 <= t_hi, -inf / +inf without a candidate */
+    int32_t pos_lo, kind_lo; /* what blocks at t_lo: position (row i, or m + variable j; -1 none) and kind (ASM_RANGE_*) */
+    int32_t pos_hi, kind_hi; /* the same at t_hi */
+} asm_range_info;
+#define ASM_RANGE_NONE 0
+#define ASM_RANGE_ROW_LOWER 1  /* an inactive row reaches g_L */
+#define ASM_RANGE_ROW_UPPER 2  /* an inactive row reaches g_U */
+#define ASM_RANGE_VAR_LOWER 3  /* a free variable reaches x_L */
+#define ASM_RANGE_VAR_UPPER 4  /* a free variable reaches x_U */
+#define ASM_RANGE_ROW_MULT 5   /* the multiplier of a working row reaches 0 */
+#define ASM_RANGE_VAR_MULT 6   /* a bound multiplier reaches 0 */
+int asm_sensitivity_range_multi(asm_handle* h, const double* x, const double* lambda, const double* z, const int32_t* row_state,
+                                const int32_t* bound_state, int32_t nrhs, const double* DX, const double* DLAM, const double* DZ,
+                                asm_range_info* out);
+
 /* ---- Adjoint solution sensitivities: the gradient of one function of the solution with respect to all data, from one KKT solve.
  * The forward entries answer "how do x* and lambda* move along one direction dc of the data" at one KKT right-hand side per direction.  The
  * reverse question - given phi(x*, lambda*) with gradients gx [n] and gl [m], what is d phi / d dpar[c] for every c - needs one solve,
@@ -1029,6 +1079,10 @@ int asm_batch_solution_adjoint_z(asm_batch* b, int64_t n_scen, const double* x, 
                                  const int32_t* bound_state, int32_t nrhs, const double* GX, const double* GL, const double* GZ,
                                  const asm_kkt_params* par, double* OUT, double* DBOUND, double* DXBOUND, double* AX, double* AL,
                                  asm_kkt_info* info);
+/* asm_sensitivity_range_multi with a leading scenario dimension ("Validity ranges" above) */
+int asm_batch_sensitivity_range(asm_batch* b, int64_t n_scen, const double* c_lb, const double* c_ub, const double* v_lb, const double* v_ub,
+                                const double* x, const double* lambda, const double* z, const int32_t* row_state, const int32_t* bound_state,
+                                int32_t nrhs, const double* DX, const double* DLAM, const double* DZ, asm_range_info* out);
 /* what the launch merging did since the batch was created */
 typedef struct {
     int64_t rounds;        /* scheduler rounds (one blob copy + one completion wait each) */
