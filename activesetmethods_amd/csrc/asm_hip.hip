@@ -1335,16 +1335,26 @@ struct Dev {
         asmb::launch(k_gemv_n, asmb::blocks(sk().M, 4), dim3(256), h->stream, A, sk().ldn, x, out, sk().M, sk().ldn);
         end(id);
     }
-    void launch_gemv_t(const double* A, const double* y, double* out) {
+    // the row chunks of the two-stage column reductions over the M rows (k_gemv_t_stage1/2, k_col_relmax_stage1/2): R chunks of `chunk` rows,
+    // the last one shorter
+    void col_chunks(int64_t& R, int64_t& chunk) const {
+        R = std::min<int64_t>((sk().M + 31) / 32, ASM_TMAXCHUNKS);
+        chunk = (sk().M + R - 1) / R;
+        R = (sk().M + chunk - 1) / chunk;
+    }
+    // out[ldn] = A'y; returns the route taken: GemvT_Csc the CSC copy of a sparse pattern, GemvT_Copy the transposed copy of a dense Ah,
+    // GemvT_TwoStage the two-stage column reduction, GemvT_None an LP without rows
+    enum { GemvT_None = -1, GemvT_Csc = 0, GemvT_Copy = 1, GemvT_TwoStage = 2 };
+    int launch_gemv_t(const double* A, const double* y, double* out) {
         if (sk().M == 0) {                               // LP without rows: A'y = 0
             HIPCHK(asmb::fill_async(out, 0, sk().ldn * sizeof(double), h->stream));
-            return;
+            return GemvT_None;
         }
         if (const double* v = sparse_vals(A)) {
             int id = begin(ASM_K_GEMV, 2.0 * sk().sp_nnz, 24.0 * sk().sp_nnz + 12.0 * sk().n);
             asmb::launch(k_spmv_t, asmb::blocks(sk().ldn * 8), dim3(256), h->stream, sk().d_sc_ptr, sk().d_sc_row, sk().d_sc_pos, v, y, out, sk().n, sk().ldn);
             end(id);
-            return;
+            return GemvT_Csc;
         }
         if (A == sk().d_Ah && (int64_t)sk().ldn * sk().Mp <= ((int64_t)1 << 27)) {
             // dense LP matrix of moderate size: through a transposed copy (made once per LP), one row-wise launch
@@ -1357,15 +1367,15 @@ struct Dev {
             int id = begin(ASM_K_GEMV, 2.0 * sk().M * sk().n, 8.0 * sk().M * sk().ldn);
             asmb::launch(k_gemv_n_exact, asmb::blocks(sk().ldn, 4), dim3(256), h->stream, sk().d_AhTg, sk().Mp, y, out, sk().ldn, sk().M);
             end(id);
-            return;
+            return GemvT_Copy;
         }
-        int64_t R = std::min<int64_t>((sk().M + 31) / 32, ASM_TMAXCHUNKS);
-        int64_t chunk = (sk().M + R - 1) / R;
-        R = (sk().M + chunk - 1) / chunk;
+        int64_t R, chunk;
+        col_chunks(R, chunk);
         int id = begin(ASM_K_GEMV, 2.0 * sk().M * sk().n, 8.0 * sk().M * sk().ldn);
         asmb::launch(k_gemv_t_stage1, dim3((unsigned)((sk().ldn + 255) / 256), (unsigned)R), dim3(256), h->stream, A, sk().ldn, y, sk().d_partial, sk().M, sk().ldn, chunk);
         asmb::launch(k_gemv_t_stage2, asmb::blocks(sk().ldn), dim3(256), h->stream, sk().d_partial, out, R, sk().ldn);
         end(id);
+        return GemvT_TwoStage;
     }
     // out[M] = A x   (host vectors)
     void gemv_n(const double* A, const double* x, double* out) {
@@ -1373,11 +1383,12 @@ struct Dev {
         launch_gemv_n(A, sk().d_vecN, sk().d_vecM);
         d2h(out, sk().d_vecM, sk().M);
     }
-    // out[n] = A' y
-    void gemv_t(const double* A, const double* y, double* out) {
+    // out[n] = A' y; returns launch_gemv_t's route
+    int gemv_t(const double* A, const double* y, double* out) {
         h2d(sk().d_vecM, y, sk().M, sk().Mp);
-        launch_gemv_t(A, sk().d_vecM, sk().d_vecN);
+        const int route = launch_gemv_t(A, sk().d_vecM, sk().d_vecN);
         d2h(out, sk().d_vecN, sk().n);
+        return route;
     }
 
     // device-pointer variants (the IPM keeps its vectors in HBM)
@@ -1913,9 +1924,8 @@ struct Dev {
     // rel[j] = max_i |J_ij| / max_k |J_ik|   (host, n) - matrix-based cap of the column scale
     void col_relmax(double* rel) {
         if (sk().M == 0) { std::fill(rel, rel + sk().n, 0.0); return; }
-        int64_t R = std::min<int64_t>((sk().M + 31) / 32, ASM_TMAXCHUNKS);
-        int64_t chunk = (sk().M + R - 1) / R;
-        R = (sk().M + chunk - 1) / chunk;
+        int64_t R, chunk;
+        col_chunks(R, chunk);
         if (sk().sp_ok) {                      // sparse pattern: the same maxima over the stored entries only
             const double* vJ = sparse_vals(sk().d_J);
             int id = begin(ASM_K_SCALE, 0.0, 8.0 * 3.0 * sk().sp_nnz);
@@ -1952,6 +1962,38 @@ struct Dev {
         asmb::launch(k_scale_rows, dim3((unsigned)sk().M), dim3(256), h->stream, sk().d_J, sk().d_c, sk().d_Ah, sk().d_rho, sk().n, sk().ldn);
         end(id);
         d2h(rho, sk().d_rho, sk().M);
+    }
+    // From the dE in HBM to the scaled LP matrix (oracle: scale_lp): assemble J, rel = col_relmax, the column scale
+    // c_j = pow2_round(min(box half-width, 1 / rel_j)), Ah = diag(1 / rho) J diag(c).  rel, c (n) and rho (M) on the host.  `after(name)` runs
+    // after each stage that ran.  The stages hook runs a subset (`stages`, ASM_SKS_* bits) and may scale by a c of its own (`c_use`).
+    template <class After>
+    void scaled_matrix(const double* lb, const double* ub, double* rel, double* c, double* rho, After&& after, unsigned stages = ASM_SKS_ASSEMBLE | ASM_SKS_COLSCALE | ASM_SKS_SCALE,
+                       const double* c_use = nullptr) {
+        if (stages & ASM_SKS_ASSEMBLE) {
+            assemble();
+            after("assemble");
+        }
+        if (stages & ASM_SKS_COLSCALE) {
+            col_relmax(rel);
+            after("relmax");
+            for (int64_t j = 0; j < sk().n; ++j) {
+                double c_mat = rel[j] > 0.0 ? 1.0 / rel[j] : 1.0;
+                c[j] = pow2_round(std::min(std::max(ub[j], -lb[j]), c_mat));
+            }
+        }
+        if (stages & ASM_SKS_SCALE) {
+            scale(c_use ? c_use : c, rho);
+            after("scale");
+        }
+    }
+    // out[i] = ||J_i||_2 over the first m rows (device); from_pattern: from the CSR copy where the pattern is sparse (the same bits, k_sp_row_norms)
+    void launch_row_norms(double* out, bool from_pattern) {
+        const int64_t m = sk().m;
+        if (m == 0) return;
+        if (const double* vJ = from_pattern ? sparse_vals(sk().d_J) : nullptr)      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
+            asmb::launch(k_sp_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, sk().d_sp_ptr, sk().d_sp_col, vJ, out, m);
+        else
+            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, sk().d_J, sk().ldn, out, m, sk().ldn);
     }
 };
 
@@ -4313,7 +4355,7 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
     lp.rtype = K.rtype.data(); lp.srow = K.srow.data(); lp.scoef = K.scoef.data();
     h->stats.M = (int)M; h->stats.n = (int)n; h->stats.ns = (int)lp.ns;
     // Jacobian -> dense rows incl. range rows; scaled copy (column scale = min(box, matrix cap), oracle: scale_lp)
-    vec c(n), rel(n);
+    vec c(n), rel(n), rho(M);
     const double tr0 = Solver::now_ms();
     auto lap = [&](const char* what) {
         if (!h->knobs.verbose) return;
@@ -4324,17 +4366,7 @@ void solve_raw(asm_handle* h, const LpRaw& L, int slot, LpSol& out) {
         last = t;
     };
     asmb::barrier(20);
-    sv.dev.assemble();
-    lap("assemble");
-    sv.dev.col_relmax(rel.data());
-    lap("relmax");
-    for (int64_t j = 0; j < n; ++j) {
-        double c_mat = rel[j] > 0.0 ? 1.0 / rel[j] : 1.0;
-        c[j] = pow2_round(std::min(std::max(L.ub[j], -L.lb[j]), c_mat));
-    }
-    vec rho(M);
-    sv.dev.scale(c.data(), rho.data());
-    lap("scale");
+    sv.dev.scaled_matrix(L.lb.data(), L.ub.data(), rel.data(), c.data(), rho.data(), lap);
     sv.dev.tile_flags();
     lap("flags");
     lp.q.resize(n); lp.lb.resize(n); lp.ub.resize(n); lp.r.resize(M); lp.w.resize(lp.ns); lp.slo.resize(lp.ns);
@@ -4735,7 +4767,7 @@ static void do_jac_row_norms(asm_handle* h, double* out_m) {
     Dev d(h);
     d.assemble();
     if (K.m == 0) return;
-    asmb::launch(k_row_norms, asmb::blocks(K.m, 4), dim3(256), h->stream, K.d_J, K.ldn, K.d_vecM, K.m, K.ldn);
+    d.launch_row_norms(K.d_vecM, false);
     d.d2h(out_m, K.d_vecM, K.m);
 }
 
@@ -4756,7 +4788,7 @@ int asm_kt_residuals(asm_handle* h, const double* df, const double* lambda, cons
         for (int64_t i = 0; i < m; ++i) lam[i] = lambda[i];
         d.gemv_t(K.d_J, lam.data(), jtl.data());
         if (m > 0) {
-            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, K.d_J, K.ldn, K.d_vecM, m, K.ldn);
+            d.launch_row_norms(K.d_vecM, false);
             d.d2h(rn.data(), K.d_vecM, m);
         }
         // common.jl:38-43
@@ -6651,12 +6683,7 @@ static void do_slp_norms(asm_handle* h, const double* lambda, const double* mult
     HIPCHK(asmb::fill_async(h->sk->d_vecM, 0, h->sk->Mp * sizeof(double), h->stream));
     if (m) HIPCHK(asmb::copy_async(h->sk->d_vecM, lam, m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     d.launch_gemv_t(h->sk->d_J, h->sk->d_vecM, jtl);
-    if (m) {
-        if (const double* vJ = d.sparse_vals(h->sk->d_J))      // sparse pattern: from the CSR copy (13 k entries instead of a 75 MB dense sweep at case300 size)
-            asmb::launch(k_sp_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->sk->d_sp_ptr, h->sk->d_sp_col, vJ, rown, m);
-        else
-            asmb::launch(k_row_norms, asmb::blocks(m, 4), dim3(256), h->stream, h->sk->d_J, h->sk->ldn, rown, m, h->sk->ldn);
-    }
+    d.launch_row_norms(rown, true);
     asmb::launch(k_slp_norms, dim3(1), dim3(1024), h->stream, ev_vecs(*h->ev, true), outd);
     HIPCHK(asmb::copy_async(st, outd, RN_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(asmb::sync(h->stream));
@@ -8148,6 +8175,64 @@ int asm_test_assemble(asm_handle* h, const double* dE, double* J_out) {
     });
 }
 
+int asm_test_skeleton_stages(asm_handle* h, uint32_t stages, const double* dE, const double* lb, const double* ub, const double* c_in,
+                             const double* x, const double* y, int64_t* info_out, double* J_out, double* rmax_out, double* rel_out,
+                             double* c_out, double* rho_out, double* Ah_out, double* spvAh_out, double* Jx_out, double* JTy_out, double* Ahx_out,
+                             double* AhTy_out, int32_t* route_out, double* norms_out, double* spnorms_out) {
+    return guarded(h, [&] {
+        Skeleton& K = sk_of(h, "asm_test_skeleton_stages: asm_sublp_setup first");
+        const int64_t n = K.n, m = K.m, M = K.M;
+        const bool bad = (stages & ~(uint32_t)ASM_SKS_ALL) || !info_out
+            || ((stages & ASM_SKS_ASSEMBLE) && ((K.nnz > 0 && !dE) || !J_out))
+            || ((stages & ASM_SKS_COLSCALE) && (!lb || !ub || !rel_out || !c_out || (M > 0 && !rmax_out)))
+            || ((stages & ASM_SKS_SCALE) && ((!c_in && !(stages & ASM_SKS_COLSCALE)) || !Ah_out || (M > 0 && !rho_out)))
+            || ((stages & ASM_SKS_PRODUCTS) && (!x || !JTy_out || !AhTy_out || !route_out || (M > 0 && (!y || !Jx_out || !Ahx_out))))
+            || ((stages & ASM_SKS_NORMS) && m > 0 && !norms_out);
+        if (bad) throw std::invalid_argument("asm_test_skeleton_stages: unknown stage or null pointer");
+        HIPCHK(hipSetDevice(h->device));
+        Dev d(h);
+        int64_t R = 0, chunk = 0;
+        if (M > 0) d.col_chunks(R, chunk);
+        const int64_t info[ASM_SKS_INFO_LEN] = {n, m, M, K.Mp, K.ldn, K.sp_ok ? 1 : 0, K.sp_nnz, K.dense_fast ? 1 : 0, R, chunk};
+        std::copy(info, info + ASM_SKS_INFO_LEN, info_out);
+        auto image = [&](double* out, const double* src, int64_t len) {
+            HIPCHK(asmb::sync(h->stream));
+            HIPCHK(asmb::copy(out, src, len * sizeof(double), hipMemcpyDeviceToHost));
+        };
+        if (stages & ASM_SKS_ASSEMBLE) {
+            HIPCHK(asmb::copy(K.d_dE, dE, K.nnz * sizeof(double), hipMemcpyHostToDevice));
+            K.J_valid = false;
+            K.inputs_ready = false;
+        }
+        vec rel(n), c(n), rho(M);
+        d.scaled_matrix(lb, ub, rel.data(), c.data(), rho.data(), [&](const char* what) {
+            if (what[0] == 'a') image(J_out, K.d_J, K.Mp * K.ldn);
+            if (what[0] == 'r' && M > 0) image(rmax_out, K.d_rho, M);      // the row maxima are in d_rho until the scale puts rho there
+            if (what[0] == 's') {
+                image(Ah_out, K.d_Ah, K.Mp * K.ldn);
+                if (K.sp_ok && spvAh_out) image(spvAh_out, K.d_spv_Ah, K.sp_nnz);
+            }
+        }, stages & (ASM_SKS_ASSEMBLE | ASM_SKS_COLSCALE | ASM_SKS_SCALE), c_in);
+        if (stages & ASM_SKS_COLSCALE) { std::copy(rel.begin(), rel.end(), rel_out); std::copy(c.begin(), c.end(), c_out); }
+        if (stages & ASM_SKS_SCALE) std::copy(rho.begin(), rho.end(), rho_out);
+        if (stages & ASM_SKS_PRODUCTS) {
+            const double none = 0.0;      // an LP without rows: y is empty, A x has no entries
+            if (M > 0) d.gemv_n(K.d_J, x, Jx_out);
+            route_out[0] = d.gemv_t(K.d_J, M > 0 ? y : &none, JTy_out);
+            if (M > 0) d.gemv_n(K.d_Ah, x, Ahx_out);
+            route_out[1] = d.gemv_t(K.d_Ah, M > 0 ? y : &none, AhTy_out);
+        }
+        if ((stages & ASM_SKS_NORMS) && m > 0) {
+            d.launch_row_norms(K.d_vecM, false);
+            d.d2h(norms_out, K.d_vecM, m);
+            if (K.sp_ok && spnorms_out) {
+                d.launch_row_norms(K.d_vecM2, true);
+                d.d2h(spnorms_out, K.d_vecM2, m);
+            }
+        }
+        d.resolve_timing();
+    });
+}
 
 int asm_sublp_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
     return guarded(h, [&] { do_set_ns_basis(h, J, k); });

@@ -1469,6 +1469,31 @@ int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* 
 int asm_test_gemv(asm_handle* h, const double* A, int64_t M, int64_t K, const double* x, const double* y,
                   double* Ax, double* ATy);
 int asm_test_assemble(asm_handle* h, const double* dE, double* J_out /* (m+nadj)*n */);
+/* The stages between "dE is on the device" and "the scaled LP matrix is ready and can be multiplied", on the skeleton asm_sublp_setup made
+ * (dense_fast, general dense or sparse pattern - whichever the set-up chose), through the functions asm_sublp_solve launches them by.  The
+ * stages named in `stages` run in this order, each from the state the previous one (or an earlier call) left:
+ *   ASM_SKS_ASSEMBLE   dE (nnz) is uploaded and J assembled; J_out: the whole Mp x ldn image of J, padding included
+ *   ASM_SKS_COLSCALE   rmax_out (M): the row maxima max_k |J_ik| as the column reduction divides by them (1 for a row of zeros); rel_out (n): the
+ *                      column maxima of |J_ij| / max_k |J_ik|; c_out (n): the column scale pow2_round(min(max(ub, -lb), 1 / rel)) of the box
+ *                      lb / ub (n each)
+ *   ASM_SKS_SCALE      Ah = diag(1 / rho) J diag(c) with c = c_in (n) when given, else the c of ASM_SKS_COLSCALE of this call (neither:
+ *                      ASM_ERR_ARG); rho_out (M), Ah_out: the Mp x ldn image of Ah, spvAh_out (sp_nnz; may be NULL): on a sparse pattern the
+ *                      scaled values in pattern order
+ *   ASM_SKS_PRODUCTS   Jx_out = J x (M), JTy_out = J'y (n), Ahx_out = Ah x, AhTy_out = Ah'y for the probes x (n) and y (M); route_out[0 / 1]: the
+ *                      route of J'y / Ah'y - 0 the CSC copy, 1 the transposed copy, 2 the two-stage column reduction, -1 an LP without rows
+ *   ASM_SKS_NORMS      norms_out (m): the row norms of J by the dense kernel; spnorms_out (m; may be NULL): on a sparse pattern the same from
+ *                      the CSR copy
+ * info_out (ASM_SKS_INFO_LEN, filled by every accepted call, stages == 0 included): n, m, M, Mp, ldn, sparse pattern (0 / 1), its entries,
+ * dense_fast (0 / 1), the chunk count R and the rows per chunk of the two-stage column reductions.  ASM_ERR_STATE before asm_sublp_setup;
+ * a stage bit outside ASM_SKS_ALL, info_out == NULL or a null pointer among what a requested stage reads or writes (unless marked): ASM_ERR_ARG,
+ * checked before anything runs.  ASM_SKS_ASSEMBLE drops the inputs of a resident solve (asm_sublp_upload again); bounds, retained sets and
+ * hints stay, and asm_sublp_solve works on as before. */
+enum { ASM_SKS_ASSEMBLE = 1, ASM_SKS_COLSCALE = 2, ASM_SKS_SCALE = 4, ASM_SKS_PRODUCTS = 8, ASM_SKS_NORMS = 16, ASM_SKS_ALL = 31 };
+#define ASM_SKS_INFO_LEN 10
+int asm_test_skeleton_stages(asm_handle* h, uint32_t stages, const double* dE, const double* lb, const double* ub, const double* c_in,
+                             const double* x, const double* y, int64_t* info_out, double* J_out, double* rmax_out, double* rel_out,
+                             double* c_out, double* rho_out, double* Ah_out, double* spvAh_out, double* Jx_out, double* JTy_out, double* Ahx_out,
+                             double* AhTy_out, int32_t* route_out, double* norms_out, double* spnorms_out);
 /* FP64 MFMA peak probe (back-to-back v_mfma_f64_16x16x4_f64, registers only): measured roofline denominator. */
 int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tflops);
 

@@ -91,12 +91,17 @@ def test_cholesky_pivot_guard(hip_lib, handle):
 
 @pytest.mark.parametrize("M,K", [(5, 3), (130, 77), (500, 1000), (1000, 129)])
 def test_gemv(hip_lib, handle, M, K):
+    """A x by k_gemv_n and A'y on a dense Ah loaded into a test skeleton.  A'y reaches the transposed-copy route of launch_gemv_t only
+    (k_transpose_dense + k_gemv_n_exact); the CSC and the two-stage routes are in tests/test_skeleton_stages_gpu.py.  A sum of L products in
+    any order, with or without FMA, is within (L + 2) eps sum |a| |x| of the exact value: L = ldn along a row, M along a column."""
     rng = np.random.default_rng(M + K)
     A = rng.standard_normal((M, K)); x = rng.standard_normal(K); y = rng.standard_normal(M)
     Ax = np.zeros(M); ATy = np.zeros(K)
     assert hip_lib.asm_test_gemv(handle, _d(A), M, K, _d(x), _d(y), _d(Ax), _d(ATy)) == 0
-    assert np.abs(Ax - A @ x).max() < 1e-12 * K
-    assert np.abs(ATy - A.T @ y).max() < 1e-12 * M
+    LD, eps, ldn = np.longdouble, np.longdouble(2.0 ** -52), (K + 31) // 32 * 32
+    Al, xl, yl = A.astype(LD), x.astype(LD), y.astype(LD)
+    assert (np.abs(Ax - Al @ xl) <= (ldn + 2) * eps * (np.abs(Al) @ np.abs(xl))).all()
+    assert (np.abs(ATy - Al.T @ yl) <= (M + 2) * eps * (np.abs(Al).T @ np.abs(yl))).all()
 
 
 @pytest.mark.parametrize("seed,n,m,density,dup,nrange", [(1, 7, 5, 0.5, 0.5, 2), (2, 60, 40, 0.1, 0.3, 5), (3, 50, 30, 1.0, 0.0, 0),
