@@ -80,6 +80,11 @@ class BatchStats(C.Structure):
                 ("panel_grid_max", C.c_int64)]
 
 
+class BatchKernelRow(C.Structure):
+    """asm_batch_kernel_row: one row of asm_test_batch_kernel_table (include/asm_hip.h)."""
+    _fields_ = [("name", C.c_char * 256), ("operations", C.c_int64), ("launches", C.c_int64), ("nb_max", C.c_int32), ("gz", C.c_int32)]
+
+
 class KktParams(C.Structure):
     """asm_kkt_params."""
     _fields_ = [("max_iter", C.c_int32), ("rtol", C.c_double)]
@@ -163,6 +168,7 @@ _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
 _I32 = C.POINTER(C.c_int32)
+_U8 = C.POINTER(C.c_uint8)
 
 PROTOTYPES = {
     "asm_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
@@ -293,7 +299,28 @@ PROTOTYPES = {
     "asm_test_assemble": (C.c_int, [_P, _D, _D]),
     "asm_test_skeleton_stages": (C.c_int, [_P, C.c_uint32, _D, _D, _D, _D, _D, _D, _I64, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _I32, _D, _D]),
     "asm_test_mfma_peak": (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    "asm_test_copy_fill": (C.c_int, [_P, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _U8, _U8, _U8, _U8, _U8, _U8]),
+    "asm_batch_test_run": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _I32]),
+    "asm_batch_test_record_size": (C.c_int64, [C.c_int32]),
+    "asm_test_batch_kernel_counting": (C.c_int, [_P, C.c_int]),
+    "asm_test_batch_panel_share": (C.c_int, [_P, C.c_int]),
+    "asm_test_batch_kernel_table": (C.c_int, [_P, C.POINTER(BatchKernelRow), C.c_int64, _I64, C.c_int]),
 }
+
+# asm_batch_test_run: the families (ASM_TF_* of include/asm_hip.h, in order) by the hook they run.  A family's record (asm_test_*_args) has the
+# hook's parameters after h as its fields, in order: hook_record(hook) makes that structure from the hook's prototype
+TEST_FAMILIES = ("asm_test_skeleton_stages", "asm_test_ipm_stages", "asm_test_as_stages", "asm_test_ns_stages", "asm_test_ns_setup_stages", "asm_test_kkt_stages",
+                 "asm_test_cholesky", "asm_test_chol_solve", "asm_test_trsm_rows", "asm_test_gemm_nt", "asm_test_gemv", "asm_test_syrk", "asm_test_syrk_update",
+                 "asm_test_build_split", "asm_test_copy_fill")
+_RECORDS = {}
+
+
+def hook_record(hook):
+    if hook not in _RECORDS:
+        fields = [("a%d" % i, t) for i, t in enumerate(PROTOTYPES[hook][1][1:])]
+        _RECORDS[hook] = type(hook + "_args", (C.Structure,), {"_fields_": fields})
+    return _RECORDS[hook]
+
 
 _lib = None
 

@@ -143,7 +143,10 @@ struct Sched : FiberSched {
         }
         res_events.clear();
     }
-    std::map<const void*, std::pair<uint64_t, uint64_t>> per_kernel;      // kernel -> (operations recorded, launches made)
+    // per-kernel merge table, kept while `counting` is on (ASM_BATCH_VERBOSE=1, or the test entry asm_test_batch_kernel_counting)
+    struct KernelCount { uint64_t ops = 0, launches = 0; unsigned nb_max = 0; };      // operations recorded, launches made, most scenarios of one launch
+    bool counting = false;
+    std::map<std::pair<const void*, unsigned>, KernelCount> per_kernel;   // (kernel, gridDim.z of one scenario) -> counts
 
     static void chk(hipError_t e, const char* what) {
         if (e != hipSuccess) throw BatchError(std::string(what) + ": " + hipGetErrorString(e));
@@ -173,7 +176,7 @@ struct Sched : FiberSched {
         if (h_out) (void)hipHostFree(h_out);
         if (h_sig) (void)hipHostFree(h_sig);
     }
-    Sched(int dev, hipStream_t s, int pwgs, bool verbose_, bool time_resident_) : device(dev), stream(s), panel_wgs(pwgs), verbose(verbose_), time_resident(time_resident_) {
+    Sched(int dev, hipStream_t s, int pwgs, bool verbose_, bool time_resident_) : device(dev), stream(s), panel_wgs(pwgs), verbose(verbose_), time_resident(time_resident_), counting(verbose_) {
         try {
             chk(hipHostMalloc((void**)&h_sig, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(sig)");
             chk(hipHostGetDevicePointer((void**)&d_sig, h_sig, 0), "hipHostGetDevicePointer(sig)");
@@ -184,12 +187,14 @@ struct Sched : FiberSched {
     }
     ~Sched() override {
         if (verbose && !per_kernel.empty()) {
+            std::map<const void*, std::pair<uint64_t, uint64_t>> by_kernel;      // kernel -> (operations, launches), every gz together
+            for (auto& kv : per_kernel) { auto& pk = by_kernel[kv.first.first]; pk.first += kv.second.ops; pk.second += kv.second.launches; }
             std::vector<std::pair<uint64_t, const void*>> v;
-            for (auto& kv : per_kernel) v.push_back({kv.second.second, kv.first});
+            for (auto& kv : by_kernel) v.push_back({kv.second.second, kv.first});
             std::sort(v.rbegin(), v.rend());
             std::fprintf(stderr, "[asm batch] rounds %llu, launches by kernel (launches, operations, operations per launch):\n", (unsigned long long)n_rounds);
             for (size_t i = 0; i < v.size() && i < 40; ++i) {
-                const auto& pk = per_kernel[v[i].second];
+                const auto& pk = by_kernel[v[i].second];
                 const char* nm = hipKernelNameRefByPtr(v[i].second, stream);
                 std::fprintf(stderr, "[asm batch]   %8llu %9llu %6.1f  %.60s\n", (unsigned long long)pk.second, (unsigned long long)pk.first, (double)pk.first / (double)pk.second, nm ? nm : "?");
             }
@@ -265,7 +270,10 @@ struct Sched : FiberSched {
                 if (group.size() < cap && f->cursor < f->ops.size() && (f == lead || same(f->ops[f->cursor], X))) group.push_back(f);
             bo = (bo + 15) & ~(size_t)15;
             launches.push_back({&X, bo, (unsigned)group.size()});
-            if (verbose) { auto& pk = per_kernel[X.kfn]; pk.first += group.size(); pk.second += 1; }
+            if (counting) {
+                KernelCount& pk = per_kernel[{X.kfn, X.gz}];
+                pk.ops += group.size(); pk.launches += 1; pk.nb_max = std::max(pk.nb_max, (unsigned)group.size());
+            }
             for (RecFiber* f : group) {
                 std::memcpy(h_blob + bo, f->args.data() + f->ops[f->cursor].arg_off, X.arg_size);
                 bo += X.arg_size;

@@ -6951,8 +6951,19 @@ static void test_alloc(asm_handle* h, int64_t M, int64_t K) {
     h->sk->sp_ok = false;     // the hooks write arbitrary matrices into the buffers
 }
 
+// The kernel hooks that also run on the fibers of a scenario batch (asm_batch_test_run) have their body in an internal function test_*(h, record):
+// the record's fields are the hook's parameters after h, the value is the hook's return code.  The hook itself only fills the record.
+static int test_syrk(asm_handle* h, const asm_test_syrk_args& a_);
 int asm_test_syrk(asm_handle* h, const double* A, int64_t M, int64_t K, const int32_t* idx, int64_t Ms, const double* theta,
                   const double* diag, double* S_out, int tile) {
+    return test_syrk(h, asm_test_syrk_args{A, M, K, idx, Ms, theta, diag, S_out, tile});
+}
+static int test_syrk(asm_handle* h, const asm_test_syrk_args& a_) {
+    const double *A = a_.A, *theta = a_.theta, *diag = a_.diag;
+    const int64_t M = a_.M, K = a_.K, Ms = a_.Ms;
+    const int32_t* idx = a_.idx;
+    double* S_out = a_.S_out;
+    const int tile = a_.tile;
     return guarded(h, [&] {
         test_alloc(h, M, K);
         Dev d(h);
@@ -7006,8 +7017,17 @@ int asm_test_build_flagged(asm_handle* h, const double* A, int64_t M, int64_t K,
 // The k x k matrix of a null-space iteration on buffers of the caller's, by the statements of the solver (Dev::ns_newton_matrix: split-K build
 // + reduction for nsplit > 1, else the plain build, its copy and k_diag_prepare).  G is k x K; every output has the pitch ld = k rounded up to
 // 32 and is pre-filled by the caller: parts (nsplit x ld x ld; untouched for nsplit = 1), S, N0 (ld x ld each), diag0 (ld).
+static int test_build_split(asm_handle* h, const asm_test_build_split_args& a_);
 int asm_test_build_split(asm_handle* h, const double* G, int64_t k, int64_t K, const double* theta, int nsplit, double rel, double absv, double* parts_inout,
                          double* S_inout, double* N0_inout, double* diag0_inout) {
+    return test_build_split(h, asm_test_build_split_args{G, k, K, theta, nsplit, rel, absv, parts_inout, S_inout, N0_inout, diag0_inout});
+}
+static int test_build_split(asm_handle* h, const asm_test_build_split_args& a_) {
+    const double *G = a_.G, *theta = a_.theta;
+    const int64_t k = a_.k, K = a_.K;
+    const int nsplit = a_.nsplit;
+    const double rel = a_.rel, absv = a_.absv;
+    double *parts_inout = a_.parts_inout, *S_inout = a_.S_inout, *N0_inout = a_.N0_inout, *diag0_inout = a_.diag0_inout;
     return guarded(h, [&] {
         if (!G || !theta || !parts_inout || !S_inout || !N0_inout || !diag0_inout || k <= 0 || K <= 0 || K % ASM_KC != 0 || nsplit < 1 || nsplit > NS_MAX_SPLIT)
             throw std::invalid_argument("asm_test_build_split: bad argument");
@@ -7103,9 +7123,21 @@ int asm_test_build_dispatch(asm_handle* h, const double* dE, int which, const in
 // The interior-point stage kernels (asm_ipm_kernels.hip.h), one launch per stage, through the launch-site members of Solver and on an arena
 // laid out by Solver::ipm_bind with the pitches of IpmLayout - see include/asm_hip.h.  Every offset and index a stage reads is checked here
 // against the buffers before anything is launched.
+static int test_ipm_stages(asm_handle* h, const asm_test_ipm_stages_args& a_);
 int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t ncomp, double scale_q, int64_t* layout_out, double* dbl_inout, int64_t ndbl,
                         const int32_t* ints, int64_t nint, double* snap_inout, double* rpart_inout, uint32_t* rcnt_inout, double* hscal_inout, uint32_t* hseq_inout,
                         const asm_ipm_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return test_ipm_stages(h, asm_test_ipm_stages_args{n, M, ns, ncomp, scale_q, layout_out, dbl_inout, ndbl, ints, nint, snap_inout, rpart_inout, rcnt_inout,
+                                                       hscal_inout, hseq_inout, stages, nstages, grid_out});
+}
+static int test_ipm_stages(asm_handle* h, const asm_test_ipm_stages_args& a_) {
+    const int64_t n = a_.n, M = a_.M, ns = a_.ns, ncomp = a_.ncomp, ndbl = a_.ndbl, nint = a_.nint, nstages = a_.nstages;
+    const double scale_q = a_.scale_q;
+    int64_t* layout_out = a_.layout_out;
+    double *dbl_inout = a_.dbl_inout, *snap_inout = a_.snap_inout, *rpart_inout = a_.rpart_inout, *hscal_inout = a_.hscal_inout;
+    const int32_t* ints = a_.ints;
+    uint32_t *rcnt_inout = a_.rcnt_inout, *hseq_inout = a_.hseq_inout, *grid_out = a_.grid_out;
+    const asm_ipm_stage* stages = a_.stages;
     return guarded(h, [&] {
         const int64_t LIM = (int64_t)1 << 24;
         if (!layout_out || n < 1 || M < 0 || ns < 0 || n > LIM || M > LIM || ns > LIM || ncomp < 1 || (ns > 0 && M == 0) || nstages < 0)
@@ -7237,8 +7269,20 @@ int asm_test_ipm_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, int64_t
 // The active-set and optimal-face kernels (asm_as_kernels.hip.h), one launch per stage, through the launch-site members of Solver and on arenas
 // laid out by Solver::as_bind with the pitches of AsLayout - see include/asm_hip.h.  Every offset, set number, family / index pair and every
 // index the caller's lists hold is checked here against the buffers before anything is launched.
+static int test_as_stages(asm_handle* h, const asm_test_as_stages_args& a_);
 int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double scale_q, int64_t* layout_out, double* dbl_inout, int64_t ndbl, int32_t* int_inout,
                        int64_t nint, const double* Ah, int64_t ah_rows, const asm_as_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return test_as_stages(h, asm_test_as_stages_args{n, M, ns, scale_q, layout_out, dbl_inout, ndbl, int_inout, nint, Ah, ah_rows, stages, nstages, grid_out});
+}
+static int test_as_stages(asm_handle* h, const asm_test_as_stages_args& a_) {
+    const int64_t n = a_.n, M = a_.M, ns = a_.ns, ndbl = a_.ndbl, nint = a_.nint, ah_rows = a_.ah_rows, nstages = a_.nstages;
+    const double scale_q = a_.scale_q;
+    int64_t* layout_out = a_.layout_out;
+    double* dbl_inout = a_.dbl_inout;
+    int32_t* int_inout = a_.int_inout;
+    const double* Ah = a_.Ah;
+    const asm_as_stage* stages = a_.stages;
+    uint32_t* grid_out = a_.grid_out;
     return guarded(h, [&] {
         const int64_t LIM = (int64_t)1 << 24;
         if (!layout_out || n < 1 || M < 0 || ns < 0 || n > LIM || M > LIM || ns > LIM || (ns > 0 && M == 0) || nstages < 0)
@@ -7421,9 +7465,22 @@ int asm_test_as_stages(asm_handle* h, int64_t n, int64_t M, int64_t ns, double s
 // The kernels of the KKT column family and of the SLP-EQP trial step (asm_kkt_kernels.hip.h, asm_eqp_kernels.hip.h), one launch per stage,
 // through the launch sites the drivers use (KktSites) and on blocks of the hook's own with the solver's pitches - see include/asm_hip.h.
 // Every size, offset and index is checked here before anything is launched.
+static int test_kkt_stages(asm_handle* h, const asm_test_kkt_stages_args& a_);
 int asm_test_kkt_stages(asm_handle* h, int64_t n, int64_t M, int64_t nW, int64_t capW, int32_t cols, int64_t* layout_out, double* dbl_inout, int64_t ndbl,
                         int32_t* int_inout, int64_t nint, const int64_t* i64, int64_t ni64, uint32_t* cnt_inout, uint32_t* act_inout, double* hscal_inout,
                         uint32_t* hseq_inout, const asm_kkt_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return test_kkt_stages(h, asm_test_kkt_stages_args{n, M, nW, capW, cols, layout_out, dbl_inout, ndbl, int_inout, nint, i64, ni64, cnt_inout, act_inout, hscal_inout,
+                                                       hseq_inout, stages, nstages, grid_out});
+}
+static int test_kkt_stages(asm_handle* h, const asm_test_kkt_stages_args& a_) {
+    const int64_t n = a_.n, M = a_.M, nW = a_.nW, capW = a_.capW, ndbl = a_.ndbl, nint = a_.nint, ni64 = a_.ni64, nstages = a_.nstages;
+    const int32_t cols = a_.cols;
+    int64_t* layout_out = a_.layout_out;
+    double *dbl_inout = a_.dbl_inout, *hscal_inout = a_.hscal_inout;
+    int32_t* int_inout = a_.int_inout;
+    const int64_t* i64 = a_.i64;
+    uint32_t *cnt_inout = a_.cnt_inout, *act_inout = a_.act_inout, *hseq_inout = a_.hseq_inout, *grid_out = a_.grid_out;
+    const asm_kkt_stage* stages = a_.stages;
     return guarded(h, [&] {
         const int64_t LIM = (int64_t)1 << 20, CW = KKM_CW;
         if (!layout_out || n < 1 || n > LIM || M < 0 || M > LIM || nW < 0 || nW > capW || capW > LIM || (nW > 0 && M == 0) || cols < 1 || cols > CW || nstages < 0)
@@ -7615,9 +7672,23 @@ int asm_test_kkt_stages(asm_handle* h, int64_t n, int64_t M, int64_t nW, int64_t
 // launch-site members of Solver / Dev and on buffers of the caller's laid out with the pitches of IpmLayout and NsLayout - see
 // include/asm_hip.h.  The CSC view and the index lists are made by the routines do_setup uses; the factor is what Dev::chol leaves in a buffer
 // of ns_alloc_factor.  Every size, offset and index is checked here before anything is launched.
+static int test_ns_stages(asm_handle* h, const asm_test_ns_stages_args& a_);
 int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double scale_q, const int32_t* rtype, const int32_t* ptr, const int32_t* col, const double* vals,
                        const double* Nreg, const double* N0, int64_t* layout_out, int32_t* idx_out, double* dbl_inout, int64_t ndbl, double* hscal_inout,
                        uint32_t* hseq_inout, const asm_ns_stage* stages, int64_t nstages, uint32_t* grid_out) {
+    return test_ns_stages(h, asm_test_ns_stages_args{n, M, k, scale_q, rtype, ptr, col, vals, Nreg, N0, layout_out, idx_out, dbl_inout, ndbl, hscal_inout, hseq_inout,
+                                                     stages, nstages, grid_out});
+}
+static int test_ns_stages(asm_handle* h, const asm_test_ns_stages_args& a_) {
+    const int64_t n = a_.n, M = a_.M, k = a_.k, ndbl = a_.ndbl, nstages = a_.nstages;
+    const double scale_q = a_.scale_q;
+    const int32_t *rtype = a_.rtype, *ptr = a_.ptr, *col = a_.col;
+    const double *vals = a_.vals, *Nreg = a_.Nreg, *N0 = a_.N0;
+    int64_t* layout_out = a_.layout_out;
+    int32_t* idx_out = a_.idx_out;
+    double *dbl_inout = a_.dbl_inout, *hscal_inout = a_.hscal_inout;
+    uint32_t *hseq_inout = a_.hseq_inout, *grid_out = a_.grid_out;
+    const asm_ns_stage* stages = a_.stages;
     return guarded(h, [&] {
         const int64_t LIM = (int64_t)1 << 20;
         if (!layout_out || !rtype || n < 1 || M < 1 || n > LIM || M > LIM || k < 1 || k > n || k > ASM_SMALL_MAX || nstages < 0)
@@ -7801,10 +7872,25 @@ int asm_test_ns_stages(asm_handle* h, int64_t n, int64_t M, int64_t k, double sc
 // up and whose skeleton has the form - see include/asm_hip.h.  The stages run on the form's own buffers (sk().nsf), which the caller loads and
 // gets back whole; the Jacobian is assembled and scaled as asm_test_build_dispatch does it.  Every size, index and stage order is checked
 // before anything is launched.
+static int test_ns_setup_stages(asm_handle* h, const asm_test_ns_setup_stages_args& a_);
 int asm_test_ns_setup_stages(asm_handle* h, const double* dE, const double* fm, int64_t k, int64_t k_reserve, const int32_t* J, int64_t* layout_out, int32_t* idx_out,
                              double* G_inout, double* R_inout, double* X_inout, double* SN_inout, double* Y_inout, double* T_inout, double* d_inout, double* f0_out,
                              double* Lt_out, int32_t Zk, const int32_t* hint_J, int64_t nhint, const asm_nss_stage* stages, int64_t nstages, uint32_t* grid_out,
                              int32_t* res_out, int32_t* setup_out) {
+    return test_ns_setup_stages(h, asm_test_ns_setup_stages_args{dE, fm, k, k_reserve, J, layout_out, idx_out, G_inout, R_inout, X_inout, SN_inout, Y_inout, T_inout,
+                                                                 d_inout, f0_out, Lt_out, Zk, hint_J, nhint, stages, nstages, grid_out, res_out, setup_out});
+}
+static int test_ns_setup_stages(asm_handle* h, const asm_test_ns_setup_stages_args& a_) {
+    const double *dE = a_.dE, *fm = a_.fm;
+    const int64_t k = a_.k, k_reserve = a_.k_reserve, nhint = a_.nhint, nstages = a_.nstages;
+    const int32_t *J = a_.J, *hint_J = a_.hint_J;
+    int64_t* layout_out = a_.layout_out;
+    int32_t *idx_out = a_.idx_out, *res_out = a_.res_out, *setup_out = a_.setup_out;
+    double *G_inout = a_.G_inout, *R_inout = a_.R_inout, *X_inout = a_.X_inout, *SN_inout = a_.SN_inout, *Y_inout = a_.Y_inout, *T_inout = a_.T_inout;
+    double *d_inout = a_.d_inout, *f0_out = a_.f0_out, *Lt_out = a_.Lt_out;
+    const int32_t Zk = a_.Zk;
+    const asm_nss_stage* stages = a_.stages;
+    uint32_t* grid_out = a_.grid_out;
     return guarded(h, [&] {
         Skeleton& K = sk_of(h, "asm_test_ns_setup_stages: asm_sublp_setup first");
         NsForm* const ns = K.nsf.get();
@@ -7974,7 +8060,15 @@ int asm_test_ns_setup_stages(asm_handle* h, const double* dE, const double* fm, 
 
 // S[a,b] -= sum_k P[a,k] P[b,k] for a >= b (and b < MsB when MsB >= 0): the Cholesky update as the factorisation launches it
 // (k_syrk_upd for tile 4, the generic kernel otherwise), with an offset origin inside a larger matrix (srow0) like a trailing update
+static int test_syrk_update(asm_handle* h, const asm_test_syrk_update_args& a_);
 int asm_test_syrk_update(asm_handle* h, const double* Pm, int64_t Ms, int64_t K, int64_t MsB, int64_t srow0, double* S_inout, int tile) {
+    return test_syrk_update(h, asm_test_syrk_update_args{Pm, Ms, K, MsB, srow0, S_inout, tile});
+}
+static int test_syrk_update(asm_handle* h, const asm_test_syrk_update_args& a_) {
+    const double* Pm = a_.P;
+    const int64_t Ms = a_.Ms, K = a_.K, MsB = a_.MsB, srow0 = a_.srow0;
+    double* S_inout = a_.S_inout;
+    const int tile = a_.tile;
     return guarded(h, [&] {
         if (K % 64 != 0) throw HipError("asm_test_syrk_update: K must be a multiple of 64 (panel widths)");
         const int64_t N = srow0 + Ms;
@@ -8025,7 +8119,12 @@ int asm_test_set_factor(asm_handle* h, int layout, int band_hint, int mode, doub
     });
 }
 
-int asm_test_cholesky(asm_handle* h, const double* S, int64_t N, double* L_out) {
+static int test_cholesky(asm_handle* h, const asm_test_cholesky_args& a_);
+int asm_test_cholesky(asm_handle* h, const double* S, int64_t N, double* L_out) { return test_cholesky(h, asm_test_cholesky_args{S, N, L_out}); }
+static int test_cholesky(asm_handle* h, const asm_test_cholesky_args& a_) {
+    const double* S = a_.S;
+    const int64_t N = a_.N;
+    double* L_out = a_.L_out;
     return guarded(h, [&] {
         test_load_S(h, S, N);
         Dev d(h);
@@ -8068,7 +8167,12 @@ int asm_test_panel_timeout(asm_handle* h, int workgroups) {
     });
 }
 
-int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x) {
+static int test_chol_solve(asm_handle* h, const asm_test_chol_solve_args& a_);
+int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double* b, double* x) { return test_chol_solve(h, asm_test_chol_solve_args{S, N, b, x}); }
+static int test_chol_solve(asm_handle* h, const asm_test_chol_solve_args& a_) {
+    const double *S = a_.S, *b = a_.b;
+    const int64_t N = a_.N;
+    double* x = a_.x;
     return guarded(h, [&] {
         test_load_S(h, S, N);
         Dev d(h);
@@ -8078,7 +8182,15 @@ int asm_test_chol_solve(asm_handle* h, const double* S, int64_t N, const double*
     });
 }
 
+static int test_gemm_nt(asm_handle* h, const asm_test_gemm_nt_args& a_);
 int asm_test_gemm_nt(asm_handle* h, const double* A, const double* B, const double* C0, int64_t Ma, int64_t Mb, int64_t K, int mode, double* C_out) {
+    return test_gemm_nt(h, asm_test_gemm_nt_args{A, B, C0, Ma, Mb, K, mode, C_out});
+}
+static int test_gemm_nt(asm_handle* h, const asm_test_gemm_nt_args& a_) {
+    const double *A = a_.A, *B = a_.B, *C0 = a_.C0;
+    const int64_t Ma = a_.Ma, Mb = a_.Mb, K = a_.K;
+    const int mode = a_.mode;
+    double* C_out = a_.C_out;
     return guarded(h, [&] {
         if (Ma <= 0 || Mb <= 0 || K <= 0 || K % 32 != 0 || !A || !B || !C_out || (mode != 0 && !C0)) throw std::invalid_argument("asm_test_gemm_nt: bad argument");
         HIPCHK(hipSetDevice(h->device));
@@ -8102,7 +8214,15 @@ int asm_test_gemm_nt(asm_handle* h, const double* A, const double* B, const doub
     });
 }
 
+static int test_trsm_rows(asm_handle* h, const asm_test_trsm_rows_args& a_);
 int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* R, int64_t nrhs, int backward, double* X_out) {
+    return test_trsm_rows(h, asm_test_trsm_rows_args{S, N, R, nrhs, backward, X_out});
+}
+static int test_trsm_rows(asm_handle* h, const asm_test_trsm_rows_args& a_) {
+    const double *S = a_.S, *R = a_.R;
+    const int64_t N = a_.N, nrhs = a_.nrhs;
+    const int backward = a_.backward;
+    double* X_out = a_.X_out;
     return guarded(h, [&] {
         if (N <= 0 || nrhs <= 0 || !S || !R || !X_out) throw std::invalid_argument("asm_test_trsm_rows: bad argument");
         test_load_S(h, S, N);
@@ -8122,7 +8242,14 @@ int asm_test_trsm_rows(asm_handle* h, const double* S, int64_t N, const double* 
     });
 }
 
+static int test_gemv(asm_handle* h, const asm_test_gemv_args& a_);
 int asm_test_gemv(asm_handle* h, const double* A, int64_t M, int64_t K, const double* x, const double* y, double* Ax, double* ATy) {
+    return test_gemv(h, asm_test_gemv_args{A, M, K, x, y, Ax, ATy});
+}
+static int test_gemv(asm_handle* h, const asm_test_gemv_args& a_) {
+    const double *A = a_.A, *x = a_.x, *y = a_.y;
+    const int64_t M = a_.M, K = a_.K;
+    double *Ax = a_.Ax, *ATy = a_.ATy;
     return guarded(h, [&] {
         test_alloc(h, M, K);
         Dev d(h);
@@ -8175,10 +8302,22 @@ int asm_test_assemble(asm_handle* h, const double* dE, double* J_out) {
     });
 }
 
+static int test_skeleton_stages(asm_handle* h, const asm_test_skeleton_stages_args& a_);
 int asm_test_skeleton_stages(asm_handle* h, uint32_t stages, const double* dE, const double* lb, const double* ub, const double* c_in,
                              const double* x, const double* y, int64_t* info_out, double* J_out, double* rmax_out, double* rel_out,
                              double* c_out, double* rho_out, double* Ah_out, double* spvAh_out, double* Jx_out, double* JTy_out, double* Ahx_out,
                              double* AhTy_out, int32_t* route_out, double* norms_out, double* spnorms_out) {
+    return test_skeleton_stages(h, asm_test_skeleton_stages_args{stages, dE, lb, ub, c_in, x, y, info_out, J_out, rmax_out, rel_out, c_out, rho_out, Ah_out, spvAh_out,
+                                                                 Jx_out, JTy_out, Ahx_out, AhTy_out, route_out, norms_out, spnorms_out});
+}
+static int test_skeleton_stages(asm_handle* h, const asm_test_skeleton_stages_args& a_) {
+    const uint32_t stages = a_.stages;
+    const double *dE = a_.dE, *lb = a_.lb, *ub = a_.ub, *c_in = a_.c_in, *x = a_.x, *y = a_.y;
+    int64_t* info_out = a_.info_out;
+    double *J_out = a_.J_out, *rmax_out = a_.rmax_out, *rel_out = a_.rel_out, *c_out = a_.c_out, *rho_out = a_.rho_out, *Ah_out = a_.Ah_out;
+    double *spvAh_out = a_.spvAh_out, *Jx_out = a_.Jx_out, *JTy_out = a_.JTy_out, *Ahx_out = a_.Ahx_out, *AhTy_out = a_.AhTy_out;
+    int32_t* route_out = a_.route_out;
+    double *norms_out = a_.norms_out, *spnorms_out = a_.spnorms_out;
     return guarded(h, [&] {
         Skeleton& K = sk_of(h, "asm_test_skeleton_stages: asm_sublp_setup first");
         const int64_t n = K.n, m = K.m, M = K.M;
@@ -8232,6 +8371,36 @@ int asm_test_skeleton_stages(asm_handle* h, uint32_t stages, const double* dE, c
         }
         d.resolve_timing();
     });
+}
+
+// asmb::copy_async (H2D, D2D, D2H) and asmb::fill_async at the caller's offsets inside two device buffers with a 64-byte margin on each side
+static int test_copy_fill(asm_handle* h, const asm_test_copy_fill_args& a) {
+    return guarded(h, [&] {
+        auto inside = [&](int64_t off) { return off >= 0 && off <= a.span - a.bytes; };
+        const bool h2d = a.ops & ASM_CF_H2D, d2d = a.ops & ASM_CF_D2D, fill = a.ops & ASM_CF_FILL, d2h = a.ops & ASM_CF_D2H;
+        if ((a.ops & ~(uint32_t)ASM_CF_ALL) || a.span < 0 || a.span > ((int64_t)1 << 30) || a.bytes < 0 || a.bytes > a.span || !a.a_init || !a.b_init || !a.a_out ||
+            !a.b_out || (h2d && (!a.host_src || !inside(a.dst_off))) || (d2d && (!inside(a.src_off) || !inside(a.dst_off))) || (fill && !inside(a.fill_off)) ||
+            (d2h && (!a.host_out || !inside(a.src_off))))
+            throw std::invalid_argument("asm_test_copy_fill: unknown operation, null pointer or a range outside the buffer");
+        HIPCHK(hipSetDevice(h->device));
+        const int64_t total = 64 + a.span + 64;
+        char *dA = nullptr, *dB = nullptr;      // (hipMalloc aligns to 256 bytes: the working area at + 64 is 64-byte aligned)
+        BufPool tmp;
+        tmp.alloc(dA, total); tmp.alloc(dB, total);
+        HIPCHK(asmb::copy(dA, a.a_init, total, hipMemcpyHostToDevice));
+        HIPCHK(asmb::copy(dB, a.b_init, total, hipMemcpyHostToDevice));
+        if (h2d) HIPCHK(asmb::copy_async(dA + 64 + a.dst_off, a.host_src, a.bytes, hipMemcpyHostToDevice, h->stream));
+        if (d2d) HIPCHK(asmb::copy_async(dB + 64 + a.dst_off, dA + 64 + a.src_off, a.bytes, hipMemcpyDeviceToDevice, h->stream));
+        if (fill) HIPCHK(asmb::fill_async(dB + 64 + a.fill_off, a.value, a.bytes, h->stream));
+        if (d2h) HIPCHK(asmb::copy_async(a.host_out, dB + 64 + a.src_off, a.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(asmb::sync(h->stream));
+        HIPCHK(asmb::copy(a.a_out, dA, total, hipMemcpyDeviceToHost));
+        HIPCHK(asmb::copy(a.b_out, dB, total, hipMemcpyDeviceToHost));
+    });
+}
+int asm_test_copy_fill(asm_handle* h, uint32_t ops, int64_t span, int64_t bytes, int64_t dst_off, int64_t src_off, int64_t fill_off, int32_t value,
+                       const uint8_t* a_init, const uint8_t* b_init, const uint8_t* host_src, uint8_t* host_out, uint8_t* a_out, uint8_t* b_out) {
+    return test_copy_fill(h, asm_test_copy_fill_args{ops, span, bytes, dst_off, src_off, fill_off, value, a_init, b_init, host_src, host_out, a_out, b_out});
 }
 
 int asm_sublp_set_ns_basis(asm_handle* h, const int32_t* J, int64_t k) {
@@ -8602,6 +8771,7 @@ struct asm_batch {
     bool setup_done = false;
     asm_batch_stats stats;
     bool verbose = false;           // ASM_BATCH_VERBOSE=1: per-kernel merge statistics of every group at release
+    bool count_kernels = false;     // test entry asm_test_batch_kernel_counting: the groups keep their per-kernel merge tables
     bool time_panels = true;        // HIP events around the groups' merged panel launches (off when ASM_HIP_TIMING=0, as for a handle)
 };
 
@@ -8703,6 +8873,7 @@ void batch_make_groups(asm_batch* b, int n_groups) {
                                                       b->time_panels));
     }
     b->groups.swap(groups);
+    for (auto& g : b->groups) g->sched.counting = b->verbose || b->count_kernels;
     for (auto& g : b->groups)
         for (int s = g->lo; s < g->hi; ++s) { b->slots[s]->stream = g->stream.s; b->slots[s]->stream2 = g->stream.s; b->slots[s]->panel_wgs = g->sched.panel_wgs; }
 }
@@ -9238,6 +9409,78 @@ int asm_batch_get_stats(const asm_batch* b, asm_batch_stats* out) {
     if (!b || !out) return ASM_ERR_ARG;
     *out = b->stats;
     return ASM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// one family of asm_batch_test_run: the record's size and the hook's internal function on record `sc` of the caller's array
+struct TestFamily { int64_t size; int (*run)(asm_handle*, const void* records, int64_t sc); };
+template <class Rec, int (*Fn)(asm_handle*, const Rec&)>
+constexpr TestFamily test_family() {
+    return {(int64_t)sizeof(Rec), [](asm_handle* h, const void* records, int64_t sc) { return Fn(h, static_cast<const Rec*>(records)[sc]); }};
+}
+const TestFamily TEST_FAMILIES[ASM_TF_COUNT] = {      // in the order of the ASM_TF_* numbers
+    test_family<asm_test_skeleton_stages_args, test_skeleton_stages>(), test_family<asm_test_ipm_stages_args, test_ipm_stages>(),
+    test_family<asm_test_as_stages_args, test_as_stages>(), test_family<asm_test_ns_stages_args, test_ns_stages>(),
+    test_family<asm_test_ns_setup_stages_args, test_ns_setup_stages>(), test_family<asm_test_kkt_stages_args, test_kkt_stages>(),
+    test_family<asm_test_cholesky_args, test_cholesky>(), test_family<asm_test_chol_solve_args, test_chol_solve>(),
+    test_family<asm_test_trsm_rows_args, test_trsm_rows>(), test_family<asm_test_gemm_nt_args, test_gemm_nt>(), test_family<asm_test_gemv_args, test_gemv>(),
+    test_family<asm_test_syrk_args, test_syrk>(), test_family<asm_test_syrk_update_args, test_syrk_update>(),
+    test_family<asm_test_build_split_args, test_build_split>(), test_family<asm_test_copy_fill_args, test_copy_fill>(),
+};
+}  // namespace
+
+extern "C" {
+
+int64_t asm_batch_test_record_size(int32_t family) { return family >= 0 && family < ASM_TF_COUNT ? TEST_FAMILIES[family].size : -1; }
+
+int asm_batch_test_run(asm_batch* b, int32_t family, int64_t n_scen, const void* records, int32_t* status_out) {
+    return guarded(b, [&] {
+        if (family < 0 || family >= ASM_TF_COUNT || n_scen < 1 || !records || !status_out) throw std::invalid_argument("asm_batch_test_run: bad argument");
+        HIPCHK(hipSetDevice(b->device));
+        const TestFamily& F = TEST_FAMILIES[family];
+        for_each_scenario(b, n_scen, "asm_batch_test_run", [&](asm_handle* h, int64_t sc, int) {
+            asmb::next_cycle();
+            status_out[sc] = F.run(h, records, sc);      // (the hook's own failure is the scenario's status; a cancelled fiber unwinds through it)
+        });
+    });
+}
+
+int asm_test_batch_panel_share(const asm_batch* b, int group) {
+    return (b && group >= 0 && group < (int)b->groups.size()) ? b->groups[group]->sched.panel_wgs : -1;
+}
+
+int asm_test_batch_kernel_counting(asm_batch* b, int on) {
+    return guarded(b, [&] {
+        b->count_kernels = on != 0;
+        for (auto& g : b->groups) { g->sched.counting = b->count_kernels || b->verbose; g->sched.per_kernel.clear(); }
+    });
+}
+
+int asm_test_batch_kernel_table(asm_batch* b, asm_batch_kernel_row* rows, int64_t cap, int64_t* n_rows, int reset) {
+    return guarded(b, [&] {
+        if (!n_rows || cap < 0 || (cap > 0 && !rows)) throw std::invalid_argument("asm_test_batch_kernel_table: bad argument");
+        std::map<std::pair<const void*, unsigned>, asmb::Sched::KernelCount> sum;
+        for (auto& g : b->groups)
+            for (auto& kv : g->sched.per_kernel) {
+                asmb::Sched::KernelCount& c = sum[kv.first];
+                c.ops += kv.second.ops; c.launches += kv.second.launches; c.nb_max = std::max(c.nb_max, kv.second.nb_max);
+            }
+        *n_rows = (int64_t)sum.size();
+        int64_t i = 0;
+        HIPCHK(hipSetDevice(b->device));
+        for (auto& kv : sum) {
+            if (i >= cap) break;
+            asm_batch_kernel_row& r = rows[i++];
+            const char* nm = hipKernelNameRefByPtr(kv.first.first, b->groups.empty() ? nullptr : b->groups[0]->stream.s);
+            std::snprintf(r.name, sizeof(r.name), "%s", nm ? nm : "?");
+            r.operations = (int64_t)kv.second.ops; r.launches = (int64_t)kv.second.launches;
+            r.nb_max = (int32_t)kv.second.nb_max; r.gz = (int32_t)kv.first.second;
+        }
+        if (reset)
+            for (auto& g : b->groups) g->sched.per_kernel.clear();
+    });
 }
 
 }  // extern "C"

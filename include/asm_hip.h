@@ -1497,6 +1497,69 @@ int asm_test_skeleton_stages(asm_handle* h, uint32_t stages, const double* dE, c
 /* FP64 MFMA peak probe (back-to-back v_mfma_f64_16x16x4_f64, registers only): measured roofline denominator. */
 int asm_test_mfma_peak(asm_handle* h, int iters, int waves_per_simd, double* tflops);
 
+/* Test hook for the copy and fill operations of the stream recorder (csrc/asm_batch.hip.h: k_bcopy / k_bfill).  Two device buffers A and B of
+ * 64 + span + 64 bytes each (a 64-byte margin on each side, the working area 64-byte aligned behind the first) are loaded with a_init / b_init
+ * (64 + span + 64 bytes each), then asmb::copy_async / asmb::fill_async run on the handle's stream in this order, each with the call's `bytes`,
+ * for every bit of `ops`:
+ *   ASM_CF_H2D    host_src (bytes)  -> A + 64 + dst_off        ASM_CF_D2D   A + 64 + src_off -> B + 64 + dst_off
+ *   ASM_CF_FILL   value -> B + 64 + fill_off                    ASM_CF_D2H   B + 64 + src_off -> host_out (bytes)
+ * a_out / b_out: the whole buffers afterwards, margins included.  Offsets >= 0 and offset + bytes <= span, else ASM_ERR_ARG (nothing runs);
+ * bytes == 0 is accepted and changes nothing.  On a plain handle these are the plain stream operations, on a batch slot
+ * (asm_batch_test_run) recorded operations merged across the scenarios. */
+enum { ASM_CF_H2D = 1, ASM_CF_D2D = 2, ASM_CF_FILL = 4, ASM_CF_D2H = 8, ASM_CF_ALL = 15 };
+int asm_test_copy_fill(asm_handle* h, uint32_t ops, int64_t span, int64_t bytes, int64_t dst_off, int64_t src_off, int64_t fill_off, int32_t value,
+                       const uint8_t* a_init, const uint8_t* b_init, const uint8_t* host_src, uint8_t* host_out, uint8_t* a_out, uint8_t* b_out);
+
+/* The kernel hooks above on the fibers of a scenario batch: scenario s of n_scen runs hook `family` on its slot's handle exactly as the
+ * per-handle hook would (the slots take the scenarios in index order, as in every asm_batch_* entry), so the launches, copies and fills of
+ * the scenarios are recorded and merged.  records: n_scen records of the family's type below - the hook's parameters after h, in order;
+ * status_out[s]: the code the per-handle hook would have returned for scenario s (its message in the slot handle's asm_last_error).  The
+ * call itself fails only for a bad argument or a failed round.  Hooks that need asm_sublp_setup first need asm_batch_setup here.
+ * asm_test_mfma_peak and asm_test_panel_timeout stay per-handle.  asm_batch_test_record_size: sizeof the family's record (-1: no such family). */
+enum { ASM_TF_SKELETON_STAGES = 0, ASM_TF_IPM_STAGES, ASM_TF_AS_STAGES, ASM_TF_NS_STAGES, ASM_TF_NS_SETUP_STAGES, ASM_TF_KKT_STAGES, ASM_TF_CHOLESKY,
+       ASM_TF_CHOL_SOLVE, ASM_TF_TRSM_ROWS, ASM_TF_GEMM_NT, ASM_TF_GEMV, ASM_TF_SYRK, ASM_TF_SYRK_UPDATE, ASM_TF_BUILD_SPLIT, ASM_TF_COPY_FILL, ASM_TF_COUNT };
+typedef struct { uint32_t stages; const double *dE, *lb, *ub, *c_in, *x, *y; int64_t* info_out; double *J_out, *rmax_out, *rel_out, *c_out, *rho_out, *Ah_out,
+                 *spvAh_out, *Jx_out, *JTy_out, *Ahx_out, *AhTy_out; int32_t* route_out; double *norms_out, *spnorms_out; } asm_test_skeleton_stages_args;
+typedef struct { int64_t n, M, ns, ncomp; double scale_q; int64_t* layout_out; double* dbl_inout; int64_t ndbl; const int32_t* ints; int64_t nint;
+                 double *snap_inout, *rpart_inout; uint32_t* rcnt_inout; double* hscal_inout; uint32_t* hseq_inout; const asm_ipm_stage* stages;
+                 int64_t nstages; uint32_t* grid_out; } asm_test_ipm_stages_args;
+typedef struct { int64_t n, M, ns; double scale_q; int64_t* layout_out; double* dbl_inout; int64_t ndbl; int32_t* int_inout; int64_t nint; const double* Ah;
+                 int64_t ah_rows; const asm_as_stage* stages; int64_t nstages; uint32_t* grid_out; } asm_test_as_stages_args;
+typedef struct { int64_t n, M, k; double scale_q; const int32_t *rtype, *ptr, *col; const double *vals, *Nreg, *N0; int64_t* layout_out; int32_t* idx_out;
+                 double* dbl_inout; int64_t ndbl; double* hscal_inout; uint32_t* hseq_inout; const asm_ns_stage* stages; int64_t nstages;
+                 uint32_t* grid_out; } asm_test_ns_stages_args;
+typedef struct { const double *dE, *fm; int64_t k, k_reserve; const int32_t* J; int64_t* layout_out; int32_t* idx_out; double *G_inout, *R_inout, *X_inout,
+                 *SN_inout, *Y_inout, *T_inout, *d_inout, *f0_out, *Lt_out; int32_t Zk; const int32_t* hint_J; int64_t nhint; const asm_nss_stage* stages;
+                 int64_t nstages; uint32_t* grid_out; int32_t *res_out, *setup_out; } asm_test_ns_setup_stages_args;
+typedef struct { int64_t n, M, nW, capW; int32_t cols; int64_t* layout_out; double* dbl_inout; int64_t ndbl; int32_t* int_inout; int64_t nint; const int64_t* i64;
+                 int64_t ni64; uint32_t *cnt_inout, *act_inout; double* hscal_inout; uint32_t* hseq_inout; const asm_kkt_stage* stages; int64_t nstages;
+                 uint32_t* grid_out; } asm_test_kkt_stages_args;
+typedef struct { const double* S; int64_t N; double* L_out; } asm_test_cholesky_args;
+typedef struct { const double* S; int64_t N; const double* b; double* x; } asm_test_chol_solve_args;
+typedef struct { const double* S; int64_t N; const double* R; int64_t nrhs; int backward; double* X_out; } asm_test_trsm_rows_args;
+typedef struct { const double *A, *B, *C0; int64_t Ma, Mb, K; int mode; double* C_out; } asm_test_gemm_nt_args;
+typedef struct { const double* A; int64_t M, K; const double *x, *y; double *Ax, *ATy; } asm_test_gemv_args;
+typedef struct { const double* A; int64_t M, K; const int32_t* idx; int64_t Ms; const double *theta, *diag; double* S_out; int tile; } asm_test_syrk_args;
+typedef struct { const double* P; int64_t Ms, K, MsB, srow0; double* S_inout; int tile; } asm_test_syrk_update_args;
+typedef struct { const double* G; int64_t k, K; const double* theta; int nsplit; double rel, absv; double *parts_inout, *S_inout, *N0_inout,
+                 *diag0_inout; } asm_test_build_split_args;
+typedef struct { uint32_t ops; int64_t span, bytes, dst_off, src_off, fill_off; int32_t value; const uint8_t *a_init, *b_init, *host_src; uint8_t *host_out,
+                 *a_out, *b_out; } asm_test_copy_fill_args;
+int asm_batch_test_run(asm_batch* b, int32_t family, int64_t n_scen, const void* records, int32_t* status_out);
+int64_t asm_batch_test_record_size(int32_t family);
+
+/* Per-kernel merge table of a batch: for every (kernel, gridDim.z of one scenario) the groups' schedulers launched while counting was on - the
+ * kernel's name (hipKernelNameRefByPtr, cut to 255 characters), the operations the slots recorded, the launches made for them, the most
+ * scenarios one launch served (nb_max) and gz.  asm_test_batch_kernel_counting switches the counting of every group (off by default unless
+ * ASM_BATCH_VERBOSE=1; it survives asm_batch_set_groups) and clears the table; asm_test_batch_kernel_table writes up to `cap` rows, *n_rows =
+ * the number there are (rows may be NULL with cap 0), and clears the table when reset != 0.  Rows are summed over the groups. */
+typedef struct { char name[256]; int64_t operations, launches; int32_t nb_max, gz; } asm_batch_kernel_row;
+int asm_test_batch_kernel_counting(asm_batch* b, int on);
+/* the panel budget of a group of the batch: the most workgroups an all-resident launch of its scheduler may have, merged launches included
+ * (the device's budget divided by the number of groups; asm_batch_stats.panel_grid_max stays within it).  -1: no such batch or group. */
+int asm_test_batch_panel_share(const asm_batch* b, int group);
+int asm_test_batch_kernel_table(asm_batch* b, asm_batch_kernel_row* rows, int64_t cap, int64_t* n_rows, int reset);
+
 #ifdef __cplusplus
 }
 #endif
